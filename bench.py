@@ -49,6 +49,29 @@ WORKLOADS = {
 # oracle over the FULL frame of the workload (stated in DESIGN.md).  bench.py re-measures it on the
 # cpu_baseline sample and reports both.
 ALGO_BYTES_PER_RAY = {"terrain16_1080p": 243.0228, "terrain16_4k": 243.0108}  # tools/ray_stats.py
+DUMP_BUDGET_BYTES = 64_000_000  # --dump-outputs: the 1080p frame's records fit whole (58 MB), the 4K frame's are sampled
+
+
+def dump_outputs(out_dir, frame, colour_wire):
+    """--dump-outputs: the frame (n_rays x 4 record words, or n_rays x 1 RGBA8 words) as float arrays, one .npy per field.  The
+    u32 record words (value, info, normal_bits) go to float64, which holds them exactly; t is the record's own f32; the image goes
+    to float32 R, G, B, A columns.  A frame larger than the budget is cut to a fixed seeded sample of rays, written in ray order
+    with the rays' indices (ray_index.npy)."""
+    os.makedirs(out_dir, exist_ok=True)
+    n = frame.shape[0]
+    per_ray = 16 if colour_wire else 28
+    if n * per_ray > DUMP_BUDGET_BYTES:
+        k = (DUMP_BUDGET_BYTES - 4096) // (per_ray + 8)  # (4096: room for the .npy headers)
+        idx = np.sort(np.random.default_rng(0).choice(n, size=k, replace=False))
+        frame = frame[idx]
+        np.save(os.path.join(out_dir, "ray_index.npy"), idx.astype(np.float64))
+    if colour_wire:
+        arrays = {"rgba": frame.reshape(-1).view(np.uint8).reshape(-1, 4).astype(np.float32)}
+    else:
+        arrays = {"value": frame[:, 0].astype(np.float64), "t": np.ascontiguousarray(frame[:, 1]).view(np.float32),
+                  "info": frame[:, 2].astype(np.float64), "normal_bits": frame[:, 3].astype(np.float64)}
+    for name, arr in arrays.items():
+        np.save(os.path.join(out_dir, f"{name}.npy"), arr)
 
 
 def free_port():
@@ -110,7 +133,7 @@ def main():
                     help="consecutive frames rotate over this many HIP streams / device contexts, so the serial tail of one "
                          "frame's rays overlaps the next frames.  0 = default: 1 at N=1 (frames serial, which is what "
                          "roofline.* describes), 3 at N>1 (a rank's share of a sharded frame is too small to fill a GPU).  "
-                         "More than 3 needs more hardware queues than ROCm's default of 4: GPU_MAX_HW_QUEUES=8 is set then")
+                         "Lanes beyond the process's hardware queues share queues with other lanes, so they overlap less")
     ap.add_argument("--wire", default="packed12", choices=["packed12", "full16", "rgba8"],
                     help="N>1: what the frame-end gather carries per ray: the 12-byte wire record (the fourth word of svo_hit "
                          "repeats bits of the third; rank 0 rebuilds it while un-permuting), the full 16-byte record, or -- rgba8 -- "
@@ -121,11 +144,15 @@ def main():
                          "process group on a single GPU")
     ap.add_argument("--opt", action="append", default=[], help="developer: NAME=VALUE for svo_set_option on every lane (e.g. PAIR_TABLE=0)")
     ap.add_argument("--cpu-frac", type=int, default=1, help="cpu_baseline traces the top 1/n of the frame's rows")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the frame the last timed step produced (rank 0: the fields of its hit records, or the RGBA8 image of "
+                         "the colour wire) as DIR/<name>.npy, float32 / float64, at most 64 MB in all (a seeded sample of rays "
+                         "beyond that, indices in ray_index.npy)")
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
         spawn_ranks(a)
-    if a.frames_in_flight > 3:
-        os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")  # before the HIP runtime starts: one hardware queue per lane
 
     import torch
     import torch.distributed as dist
@@ -561,6 +588,8 @@ def main():
                                                      "instructions issued beside them cost nothing"}
         if cpu is not None:
             result["cpu_baseline"] = cpu
+        if a.dump_outputs:
+            dump_outputs(a.dump_outputs, frame, colour_wire)
         print(json.dumps(result), flush=True)
     if pipelined:
         dist.barrier()
