@@ -24,6 +24,9 @@
  *   svo_scan_read                 map_async + device.poll(Wait) + counter reset
  *                                 (adaptive.rs:12-23, :76-87)
  *   svo_sync                      device.poll(Maintain::Wait)
+ *   svo_proc_generate_chunk       Procedural::generate_chunk (procedural.rs:101-199, procedual.wgsl:150-201), restated
+ *                                 deterministically: canonical breadth-first tree instead of the racy insertion
+ *   svo_world_generate            World::generate_world (world.rs:63-139)
  *   svo_comm_* / svo_gather_frame no reference counterpart (the reference drives one device, main.rs:40-88): the
  *                                 frame-end exchange of the tile-sharded multi-GPU frame, RCCL behind the boundary
  *                                 (SURVEY.md 8b "Threading", 8e): communicator set-up for one process per GPU
@@ -52,7 +55,8 @@ typedef enum svo_status {
     SVO_ERR_HIP = -2,     /* a HIP runtime call failed; see svo_last_error */
     SVO_ERR_STATE = -3,   /* call order (e.g. render before nodes_alloc) */
     SVO_ERR_NO_DEVICE = -4,
-    SVO_ERR_COMM = -5     /* RCCL missing or a collective call failed; see svo_last_error */
+    SVO_ERR_COMM = -5,    /* RCCL missing or a collective call failed; see svo_last_error */
+    SVO_ERR_CAP = -6      /* the result would exceed a caller-given cap (svo_proc_params.max_nodes); nothing was written */
 } svo_status;
 
 /* Uniform flags: the reference's five 1-byte bools (render.rs:294-299) as explicit bits. */
@@ -275,6 +279,40 @@ int svo_diag_strip_classes(svo_ctx *ctx, uint8_t *host_out, size_t n_strips);
 int svo_scan_dispatch(svo_ctx *ctx, uint32_t node_length);
 int svo_scan_read(svo_ctx *ctx, uint32_t *sub, uint32_t *n_sub, uint32_t *unsub, uint32_t *n_unsub,
                   size_t capacity);
+
+/* ---- procedural world generator (the reference's third kernel, procedual.wgsl) ----
+ * A chunk covers the world cube [pos, pos + 2 / 2^base_depth)^3 with 2^chunk_depth cells per axis; cell (x, y, z) samples
+ * the island's signed distance at world = pos + (cell / 2^(base_depth + chunk_depth)) * 2.  Solid cells (sdf < 0) are
+ * block 3 (grass) when the cell one voxel above is outside (sdf > 0), else block 1 (stone).  The tree is the union of the
+ * root-to-cell paths of the solid cells, breadth-first (root group at 0, each level's groups in the order of their
+ * parents, so every level is in Morton order): interior word = index of the child group, leaf = SVO_CHUNK_OFFSET + block,
+ * empty slot = SVO_CHUNK_OFFSET, colours 0.  Bit-exact and the same on every run. */
+struct svo_cpu_octree;
+struct svo_world;
+typedef struct svo_proc_params {
+    float pos[3];          /* the chunk's lower corner, world coordinates */
+    uint32_t base_depth;   /* levels above the chunk (0..21); the reference passes world_depth */
+    uint32_t chunk_depth;  /* 2..9 (the reference: 9); depth 1 is refused (the reference drops every depth-1 chunk) */
+    uint64_t max_nodes;    /* cap on the chunk's node count; 0 = 256 000 000 (procedural.rs:4) */
+} svo_proc_params;
+/* *out = the chunk as a CpuOctree (caller frees it, or hands it to svo_world_insert), or NULL for a chunk without a solid
+ * cell.  SVO_ERR_CAP (with a message) when the exact node count exceeds max_nodes.  Blocking. */
+int svo_proc_generate_chunk(svo_ctx *ctx, const svo_proc_params *params, struct svo_cpu_octree **out);
+/* World::generate_world into w's path, which must not exist yet (it is created): chunks x, y, z (that nesting) at
+ * (x, y, z) * 2 / 2^world_depth - 1 with base_depth = world_depth, id SVO_CHUNK_OFFSET / 2 + i (i counts empty chunks
+ * too); every non-empty chunk is inserted, mipped, saved as <id>.bin and reduced to its top_mip; the root (chunk 0)
+ * references them and is saved as 0.bin.  Blocks 1..8 must be in w.  world_depth 1..4, chunk_depth 2..9. */
+int svo_world_generate(svo_ctx *ctx, struct svo_world *w, uint32_t world_depth, uint32_t chunk_depth);
+/* Diagnostics: the signed distance at n points (xyz: 3 floats each; host pointers, blocking), and one chunk's class
+ * bytes (0 empty, 1 stone, 3 grass) in the reference's id order, id = x + side*y + side^2*z (host pointer, 8^chunk_depth
+ * bytes, blocking). */
+int svo_proc_sdf(svo_ctx *ctx, const float *xyz, size_t n, float *out);
+int svo_proc_classify(svo_ctx *ctx, const svo_proc_params *params, uint8_t *cells_out);
+/* Times (ms) of the last svo_proc_generate_chunk: [0] classify kernel, [1] occupancy pyramid and ranks, [2] emit (device
+ * events); [3] host wall time until the nodes are emitted, [4] read-back copy, [5] CpuOctree build.  Of the last
+ * svo_world_generate, summed over its chunks: [6] GPU (wall), [7] read-back and build, [8] mips, [9] chunk file writes. */
+#define SVO_PROC_TIMES 10
+int svo_proc_timing(svo_ctx *ctx, float ms_out[SVO_PROC_TIMES]);
 
 #ifdef __cplusplus
 }

@@ -574,6 +574,7 @@ int svo_ctx_destroy(svo_ctx *ctx) {
     (void)hipSetDevice(ctx->device);
     if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
     svo_comm_release(ctx);
+    svo_proc_release(ctx);
     release_store(ctx);
     if (ctx->top_table) (void)hipFree(ctx->top_table);
     if (ctx->status) (void)hipFree(ctx->status);

@@ -10,6 +10,7 @@
 
 #include "svo_device.h"
 #include "svo_hip.h"
+#include "svo_host.h"
 
 // The device node buffer (render.rs:53-61) and what is derived from it.  Several contexts can trace from one store
 // (svo_nodes_share: frames in flight on several streams): they share the words, the generation counter that tells every
@@ -103,6 +104,7 @@ struct svo_ctx {
     // launch timing: a ring of (start, stop) event pairs recorded around trace launches
     std::vector<hipEvent_t> ev;  // 2 per slot
     size_t ev_slots = 0, ev_count = 0;
+    struct svo_proc_state *proc = nullptr;  // procedural generator's workspace (svo_proc.hip)
     std::string err;
 };
 
@@ -112,3 +114,8 @@ int svo_fail(svo_ctx *ctx, int code, const char *what);
 int svo_fail_hip(svo_ctx *ctx, hipError_t e, const char *what);
 // svo_comm.cpp
 void svo_comm_release(svo_ctx *ctx);
+// svo_proc.hip
+void svo_proc_release(svo_ctx *ctx);
+// svo_host.cpp (internal helpers of svo_world_generate)
+std::string svo_world_path(const svo_world *w);
+void svo_cpu_octree_drop_nodes(svo_cpu_octree *t);  // frees the nodes, keeps top_mip (world.rs:122)

@@ -1193,3 +1193,10 @@ uint32_t svo_nodes_max_depth(const uint32_t *words, uint64_t n) {
 }
 
 }  // extern "C"
+
+// ------------------------------------------------------------------------------------------
+// Internal helpers of svo_world_generate (svo_proc.hip); declared in csrc/svo_ctx.h, not part of the C ABI
+// ------------------------------------------------------------------------------------------
+std::string svo_world_path(const svo_world *w) { return w->path; }
+
+void svo_cpu_octree_drop_nodes(svo_cpu_octree *t) { std::vector<svo_cpu_octree::Node>().swap(t->nodes); }

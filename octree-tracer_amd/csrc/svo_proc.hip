@@ -1,0 +1,627 @@
+// svo_proc.hip -- the procedural world generator (the reference's third kernel: procedual.wgsl main + sdf, driven by
+// procedural.rs Procedural::generate_chunk and world.rs World::generate_world), restated deterministically
+// (DESIGN.md 11).  The reference inserts every solid cell into a shared tree with unsynchronised atomics, so its node
+// order changes from run to run; here the tree is the canonical breadth-first form of the same shape, built by scans:
+//
+//   classify   one lane per cell, lanes in Morton order (a wave64 covers a 4x4x4 brick): sdf, "above" sdf for solid
+//              cells, one class byte per cell; __ballot(solid) is the child masks of the brick's 8 parents
+//   reduce     child masks level by level up to the root (a node is interior iff its mask is non-zero)
+//   ranks      per level, an exclusive scan of the interior flags in Morton order (tile counts, one-block scan of
+//              the tile counts, tile re-scan): every interior node's rank, hence its child group's index, and the
+//              exact node count, which is read back and checked before anything is emitted
+//   emit       one lane per interior parent: its 8-node group in the 8-byte <id>.bin layout
+//
+// All work runs on the context's stream.  Sizes come from the count pass; there are no atomics and no retries.
+#include <hip/hip_runtime.h>
+
+#include <sys/stat.h>
+
+#include <cerrno>
+#include <chrono>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "svo_ctx.h"
+#include "svo_host.h"
+
+namespace {
+
+constexpr uint32_t kChunkOffset = SVO_CHUNK_OFFSET;
+constexpr uint64_t kDefaultMaxNodes = 256000000ull;  // procedural.rs:4
+constexpr uint32_t kTile = 4096;                     // bytes of one level's flags per scan tile (256 lanes x 16)
+constexpr uint32_t kTopThreads = 1024;
+
+// ---- sdf (procedual.wgsl:109-148 over common.wgsl:43-191), one IEEE f32 operation per step, in the order of
+// DESIGN.md 11; compiled with -ffp-contract=off, so no step is fused ----
+namespace sdf {
+
+__device__ inline float step(float edge, float x) { return x >= edge ? 1.0f : 0.0f; }
+__device__ inline float clamp01(float x) { return fminf(fmaxf(x, 0.0f), 1.0f); }
+__device__ inline float sign(float x) { return x > 0.0f ? 1.0f : (x < 0.0f ? -1.0f : 0.0f); }
+__device__ inline float smoothstep(float e0, float e1, float x) {
+    const float t = clamp01((x - e0) / (e1 - e0));
+    return (t * t) * (3.0f - 2.0f * t);
+}
+// x % 289 (fmodf).  Every x this is called with is integer-valued: lattice coordinates are floor()s, and permute's
+// arguments stay integers below 2^24 in magnitude (|x| < 579, so (x * 34 + 1) * x < 1.2e7 is exact).  For such x
+// the integer remainder is the exact fmodf value (sign of the dividend; a zero's sign is lost, which the next
+// `p - 49 * floor(...)` erases anyway) and costs a few instructions instead of fmodf's software loop.  Anything
+// else (|x| >= 2^24, inf, NaN) takes fmodf itself.
+__device__ inline float mod289(float x) {
+    if (fabsf(x) < 16777216.0f) return float(int(x) % 289);
+    return fmodf(x, 289.0f);
+}
+__device__ inline float permute(float x) { return mod289((x * 34.0f + 1.0f) * x); }
+
+__device__ float simplex(float vx, float vy, float vz) {
+    const float c6 = 1.0f / 6.0f, c3 = 1.0f / 3.0f;
+    const float s = (vx * c3 + vy * c3) + vz * c3;
+    float ix = floorf(vx + s), iy = floorf(vy + s), iz = floorf(vz + s);
+    const float t = (ix * c6 + iy * c6) + iz * c6;
+    float x0[3] = {(vx - ix) + t, (vy - iy) + t, (vz - iz) + t};
+    const float g[3] = {step(x0[1], x0[0]), step(x0[2], x0[1]), step(x0[0], x0[2])};
+    const float l[3] = {1.0f - g[0], 1.0f - g[1], 1.0f - g[2]};
+    const float i1[3] = {fminf(g[0], l[2]), fminf(g[1], l[0]), fminf(g[2], l[1])};
+    const float i2[3] = {fmaxf(g[0], l[2]), fmaxf(g[1], l[0]), fmaxf(g[2], l[1])};
+    const float c6x2 = 2.0f * c6, c6x3 = 3.0f * c6;
+    float xk[4][3];
+    for (int a = 0; a < 3; a++) {
+        xk[0][a] = x0[a];
+        xk[1][a] = (x0[a] - i1[a]) + c6;
+        xk[2][a] = (x0[a] - i2[a]) + c6x2;
+        xk[3][a] = (x0[a] - 1.0f) + c6x3;
+    }
+    ix = mod289(ix);
+    iy = mod289(iy);
+    iz = mod289(iz);
+    const float n7 = 1.0f / 7.0f;
+    const float nsx = n7 * 2.0f - 0.0f, nsy = n7 * 0.5f - 1.0f, nsz = n7 * 1.0f - 0.0f;
+    float out = 0.0f;
+    for (int k = 0; k < 4; k++) {
+        // corner k of vec4(0, i1, i2, 1)
+        const float cz = k == 0 ? 0.0f : (k == 1 ? i1[2] : (k == 2 ? i2[2] : 1.0f));
+        const float cy = k == 0 ? 0.0f : (k == 1 ? i1[1] : (k == 2 ? i2[1] : 1.0f));
+        const float cx = k == 0 ? 0.0f : (k == 1 ? i1[0] : (k == 2 ? i2[0] : 1.0f));
+        float p = permute(iz + cz);
+        p = permute((p + iy) + cy);
+        p = permute((p + ix) + cx);
+        const float j = p - 49.0f * floorf((p * nsz) * nsz);
+        const float xs = floorf(j * nsz);
+        const float ys = floorf(j - 7.0f * xs);
+        const float gx = xs * nsx + nsy, gy = ys * nsx + nsy;
+        const float h = (1.0f - fabsf(gx)) - fabsf(gy);
+        const float sh = -step(h, 0.0f);
+        float ax = gx + (floorf(gx) * 2.0f + 1.0f) * sh;
+        float ay = gy + (floorf(gy) * 2.0f + 1.0f) * sh;
+        const float norm = 1.79284291400159f - 0.85373472095314f * ((ax * ax + ay * ay) + h * h);
+        ax = ax * norm;
+        ay = ay * norm;
+        const float az = h * norm;
+        float m = 0.6f - ((xk[k][0] * xk[k][0] + xk[k][1] * xk[k][1]) + xk[k][2] * xk[k][2]);
+        m = fmaxf(m, 0.0f);
+        m = m * m;
+        const float d = (ax * xk[k][0] + ay * xk[k][1]) + az * xk[k][2];
+        const float term = (m * m) * d;
+        out = k == 0 ? term : out + term;
+    }
+    return 42.0f * out;
+}
+
+__device__ inline float box(float px, float py, float pz, float sx, float sy, float sz) {
+    const float qx = fabsf(px) - sx, qy = fabsf(py) - sy, qz = fabsf(pz) - sz;
+    const float mx = fmaxf(qx, 0.0f), my = fmaxf(qy, 0.0f), mz = fmaxf(qz, 0.0f);
+    return sqrtf((mx * mx + my * my) + mz * mz) + fminf(fmaxf(fmaxf(qx, qy), qz), 0.0f);
+}
+
+__device__ inline float cone(float px, float py, float pz, float cx, float cy, float h) {
+    const float qx = h * (cx / cy), qy = h * -1.0f;
+    const float wx = sqrtf(px * px + pz * pz), wy = py;
+    const float t = clamp01((wx * qx + wy * qy) / (qx * qx + qy * qy));
+    const float ax = wx - qx * t, ay = wy - qy * t;
+    const float t2 = clamp01(wx / qx);
+    const float bx = wx - qx * t2, by = wy - qy * 1.0f;
+    const float k = sign(qy);
+    const float d = fminf(ax * ax + ay * ay, bx * bx + by * by);
+    const float s = fmaxf(k * (wx * qy - wy * qx), k * (wy - qy));
+    return sqrtf(d) * sign(s);
+}
+
+__device__ inline float smin(float a, float b, float k) {
+    const float h = clamp01(0.5f + (0.5f * (a - b)) / k);
+    return (a * (1.0f - h) + b * h) - (k * h) * (1.0f - h);
+}
+
+__device__ float eval(float px, float py, float pz) {
+    float v = (0.0f + box(px, py, pz, 0.7f, 0.1f, 0.7f)) - 0.1f;
+    const float s = 1.6f;
+    const float q1x = px * s, q1y = py * s, q1z = pz * s;
+    const float base = simplex(q1x, q1y, q1z) + 0.5f * simplex(q1x * 2.0f, q1y * 2.0f, q1z * 2.0f);
+    v = v + 0.07f * base;
+    const float dist = sqrtf(px * px + pz * pz);
+    const float cn = cone(px * 1.5f - 0.0f, py * -1.5f - 1.0f, pz * 1.5f - 0.0f, 0.5f, 0.5f, 0.9f) - 0.1f;
+    v = smin(v, cn, 0.2f);
+    const float q3x = px * 2.3f, q3y = py * 0.4f, q3z = pz * 2.3f;
+    float spike = simplex(q3x, q3y, q3z) + 0.5f * simplex(q3x * 2.0f, q3y * 2.0f, q3z * 2.0f);
+    const float hb = smoothstep(0.0f, -1.5f, py) + smoothstep(0.0f, 0.2f, py);
+    spike = ((spike + 1.6f * dist) + hb * 2.0f) - 1.0f;
+    return v + 0.3f * spike;
+}
+
+}  // namespace sdf
+
+struct ChunkGeom {
+    float px, py, pz;  // lower corner
+    float cell;        // 2 / 2^(base_depth + chunk_depth): a cell's edge in world units (exact)
+    uint32_t depth;    // chunk_depth
+};
+
+__device__ inline void morton_decode(uint32_t m, uint32_t depth, uint32_t &x, uint32_t &y, uint32_t &z) {
+    x = y = z = 0;
+    for (uint32_t b = 0; b < depth; b++) {
+        z |= ((m >> (3 * b)) & 1u) << b;
+        y |= ((m >> (3 * b + 1)) & 1u) << b;
+        x |= ((m >> (3 * b + 2)) & 1u) << b;
+    }
+}
+
+// class byte of one cell: 0 empty, 3 grass (nothing solid one voxel above), 1 stone (procedual.wgsl:189-201)
+__device__ inline uint32_t classify_cell(const ChunkGeom &g, uint32_t x, uint32_t y, uint32_t z) {
+    // world = pos + (cell / 2^full) * 2; the product cell * (2 / 2^full) is the same exact value
+    const float wx = g.px + float(x) * g.cell, wy = g.py + float(y) * g.cell, wz = g.pz + float(z) * g.cell;
+    if (!(sdf::eval(wx, wy, wz) < 0.0f)) return 0;
+    return sdf::eval(wx + 0.0f, wy + g.cell, wz + 0.0f) > 0.0f ? 3u : 1u;
+}
+
+// Lane m = Morton index of the cell.  n_cells is a multiple of 64 (chunk_depth >= 2), so every wave is whole.
+__global__ __launch_bounds__(256) void proc_classify_kernel(ChunkGeom g, uint32_t n_cells, uint8_t *cls, uint8_t *parent_masks) {
+    const uint32_t m = blockIdx.x * 256u + threadIdx.x;
+    if (m >= n_cells) return;
+    uint32_t x, y, z;
+    morton_decode(m, g.depth, x, y, z);
+    const uint32_t c = classify_cell(g, x, y, z);
+    cls[m] = (uint8_t)c;
+    // bit i of the ballot = lane i = child (i & 7) of parent (m >> 3): byte j is parent j's child mask
+    const uint64_t solid = __ballot(c != 0u);
+    if ((threadIdx.x & 63u) == 0) reinterpret_cast<uint64_t *>(parent_masks)[m >> 6] = solid;
+}
+
+__device__ inline uint32_t nonzero_bytes(uint32_t w) {  // bit 8k set iff byte k of w is non-zero
+    w |= w >> 4;
+    w |= w >> 2;
+    w |= w >> 1;
+    return w & 0x01010101u;
+}
+
+// mask of parent p at level L-1 from the 8 child masks of level L
+__global__ __launch_bounds__(256) void proc_reduce_kernel(const uint8_t *child_masks, uint32_t n_parents, uint8_t *parent_masks) {
+    const uint32_t p = blockIdx.x * 256u + threadIdx.x;
+    if (p >= n_parents) return;
+    const uint2 v = reinterpret_cast<const uint2 *>(child_masks)[p];
+    const uint32_t lo = nonzero_bytes(v.x), hi = nonzero_bytes(v.y);
+    uint32_t mask = 0;
+    for (int c = 0; c < 4; c++) mask |= ((lo >> (8 * c)) & 1u) << c | ((hi >> (8 * c)) & 1u) << (c + 4);
+    parent_masks[p] = (uint8_t)mask;
+}
+
+template <int N>
+__device__ inline uint32_t block_exclusive_scan(uint32_t v, uint32_t *total) {
+    __shared__ uint32_t s[N];
+    const int t = threadIdx.x;
+    s[t] = v;
+    __syncthreads();
+    for (int off = 1; off < N; off <<= 1) {
+        const uint32_t a = t >= off ? s[t - off] : 0u;
+        __syncthreads();
+        s[t] += a;
+        __syncthreads();
+    }
+    if (total) *total = s[N - 1];
+    return s[t] - v;
+}
+
+__device__ inline uint32_t count16(const uint4 q) {
+    return __popc(nonzero_bytes(q.x)) + __popc(nonzero_bytes(q.y)) + __popc(nonzero_bytes(q.z)) + __popc(nonzero_bytes(q.w));
+}
+
+// ranks, phase 1: interior nodes per tile (the level's mask bytes are zero-padded to whole tiles)
+__global__ __launch_bounds__(256) void proc_tile_count_kernel(const uint8_t *masks, uint32_t *tile_sum) {
+    const uint4 q = reinterpret_cast<const uint4 *>(masks)[blockIdx.x * 256u + threadIdx.x];
+    uint32_t total;
+    block_exclusive_scan<256>(count16(q), &total);
+    if (threadIdx.x == 0) tile_sum[blockIdx.x] = total;
+}
+
+// ranks, phase 2: one block scans the tile counts in place (exclusive) and writes the level's interior count
+__global__ __launch_bounds__(kTopThreads) void proc_tile_scan_kernel(uint32_t *tile_sum, uint32_t n_tiles, uint32_t *level_total) {
+    const uint32_t per = (n_tiles + kTopThreads - 1) / kTopThreads;
+    const uint32_t lo = threadIdx.x * per, hi = min(lo + per, n_tiles);
+    uint32_t sum = 0;
+    for (uint32_t i = lo; i < hi; i++) sum += tile_sum[i];
+    uint32_t total;
+    uint32_t run = block_exclusive_scan<kTopThreads>(sum, &total);
+    for (uint32_t i = lo; i < hi; i++) {
+        const uint32_t v = tile_sum[i];
+        tile_sum[i] = run;
+        run += v;
+    }
+    if (threadIdx.x == 0) *level_total = total;
+}
+
+// ranks, phase 3: every node's exclusive rank among the interior nodes of its level
+__global__ __launch_bounds__(256) void proc_tile_rank_kernel(const uint8_t *masks, const uint32_t *tile_off, uint32_t *rank) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    const uint4 q = reinterpret_cast<const uint4 *>(masks)[i];
+    uint32_t r = block_exclusive_scan<256>(count16(q), nullptr) + tile_off[blockIdx.x];
+    const uint32_t w[4] = {nonzero_bytes(q.x), nonzero_bytes(q.y), nonzero_bytes(q.z), nonzero_bytes(q.w)};
+    uint4 *out = reinterpret_cast<uint4 *>(rank) + 4u * i;
+    for (int k = 0; k < 4; k++) {
+        uint4 o;
+        o.x = r; r += w[k] & 1u;
+        o.y = r; r += (w[k] >> 8) & 1u;
+        o.z = r; r += (w[k] >> 16) & 1u;
+        o.w = r; r += (w[k] >> 24) & 1u;
+        out[k] = o;
+    }
+}
+
+// One lane per node p of level L-1: an interior p owns the group base_l + 8 * rank(p) of level L.  Its 8 words: an
+// interior child's pointer (base_next + 8 * its rank), CHUNK_OFFSET + class at the last level, CHUNK_OFFSET when empty.
+// Nodes are written in the 8-byte <id>.bin layout (pointer, r g b = 0, pad = 0).
+__global__ __launch_bounds__(256) void proc_emit_kernel(const uint8_t *parent_masks, const uint32_t *parent_rank, uint32_t n_parents,
+                                                       const uint8_t *child_bytes, const uint32_t *child_rank, uint32_t last,
+                                                       uint32_t base_l, uint32_t base_next, uint32_t n_nodes, uint4 *out) {
+    const uint32_t p = blockIdx.x * 256u + threadIdx.x;
+    if (p >= n_parents || parent_masks[p] == 0) return;
+    const uint32_t dst = base_l + 8u * parent_rank[p];
+    if (dst + 8u > n_nodes) return;  // (cannot happen: the ranks and n_nodes come from the same counts)
+    const uint2 cb = reinterpret_cast<const uint2 *>(child_bytes)[p];
+    uint32_t w[8];
+    for (int c = 0; c < 8; c++) {
+        const uint32_t b = ((c < 4 ? cb.x : cb.y) >> (8 * (c & 3))) & 0xFFu;
+        w[c] = last ? kChunkOffset + b : (b ? base_next + 8u * child_rank[8u * p + c] : kChunkOffset);
+    }
+    uint4 *o = out + dst / 2u;
+    for (int k = 0; k < 4; k++) o[k] = make_uint4(w[2 * k], 0u, w[2 * k + 1], 0u);
+}
+
+__global__ __launch_bounds__(256) void proc_sdf_kernel(const float *xyz, uint32_t n, float *out) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) return;
+    out[i] = sdf::eval(xyz[3u * i], xyz[3u * i + 1u], xyz[3u * i + 2u]);
+}
+
+int fail(svo_ctx *ctx, int code, const std::string &what) { return svo_fail(ctx, code, what.c_str()); }
+
+#define HIP_TRY(ctx, expr)                                             \
+    do {                                                               \
+        hipError_t e_ = (expr);                                        \
+        if (e_ != hipSuccess) return svo_fail_hip(ctx, e_, #expr);    \
+    } while (0)
+
+uint32_t blocks_for(uint64_t n) { return (uint32_t)((n + 255u) / 256u); }
+uint64_t pad_tile(uint64_t n) { return (n + kTile - 1) / kTile * kTile; }
+
+double now_ms() {
+    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
+}
+
+}  // namespace
+
+// Per-context workspace of the generator (svo_ctx::proc), sized for the deepest chunk generated so far.
+struct svo_proc_state {
+    uint32_t depth = 0;               // chunk_depth the level buffers are laid out for
+    uint32_t alloc_depth = 0;         // chunk_depth they were allocated for (>= depth)
+    uint8_t *cls = nullptr;           // 8^depth class bytes, Morton order
+    uint8_t *masks = nullptr;         // levels 0 .. depth-1: child masks, each level zero-padded to whole tiles
+    uint32_t *ranks = nullptr;        // levels 0 .. depth-1: exclusive ranks of the interior nodes
+    uint32_t *tiles = nullptr;        // levels 0 .. depth-1: tile counts, then tile offsets
+    uint32_t *totals = nullptr;       // interior nodes per level (device)
+    uint32_t *totals_host = nullptr;  // (pinned)
+    size_t mask_bytes = 0;
+    uint64_t mask_off[10] = {}, rank_off[10] = {}, tile_off[10] = {};
+    uint32_t n_tiles[10] = {};
+    uint4 *out = nullptr;  // emitted nodes, 8 bytes each
+    size_t out_bytes = 0;
+    uint8_t *stage = nullptr;  // pinned read-back buffer
+    size_t stage_bytes = 0;
+    hipEvent_t ev[4] = {};
+    float ms[SVO_PROC_TIMES] = {};
+
+    void release() {
+        for (void *p : {(void *)cls, (void *)masks, (void *)ranks, (void *)tiles, (void *)totals, (void *)out})
+            if (p) (void)hipFree(p);
+        if (totals_host) (void)hipHostFree(totals_host);
+        if (stage) (void)hipHostFree(stage);
+        for (hipEvent_t e : ev)
+            if (e) (void)hipEventDestroy(e);
+    }
+};
+
+void svo_proc_release(svo_ctx *ctx) {
+    if (!ctx->proc) return;
+    ctx->proc->release();
+    delete ctx->proc;
+    ctx->proc = nullptr;
+}
+
+namespace {
+
+int check_params(svo_ctx *ctx, const svo_proc_params *p) {
+    if (!p) return fail(ctx, SVO_ERR_ARG, "null params");
+    if (p->chunk_depth < 2 || p->chunk_depth > 9)
+        return fail(ctx, SVO_ERR_ARG, "chunk_depth must be 2..9 (got " + std::to_string(p->chunk_depth) + ")");
+    if (p->base_depth > 21) return fail(ctx, SVO_ERR_ARG, "base_depth must be <= 21");
+    return SVO_OK;
+}
+
+ChunkGeom geom_of(const svo_proc_params *p) {
+    ChunkGeom g;
+    g.px = p->pos[0];
+    g.py = p->pos[1];
+    g.pz = p->pos[2];
+    g.cell = 2.0f / float(1u << (p->base_depth + p->chunk_depth));
+    g.depth = p->chunk_depth;
+    return g;
+}
+
+// workspace for chunks of `depth` levels (kept between calls; regrown for a deeper chunk)
+int ensure_state(svo_ctx *ctx, uint32_t depth) {
+    if (!ctx->proc) {
+        ctx->proc = new svo_proc_state();
+        for (hipEvent_t &e : ctx->proc->ev) HIP_TRY(ctx, hipEventCreate(&e));
+        HIP_TRY(ctx, hipHostMalloc((void **)&ctx->proc->totals_host, 16 * sizeof(uint32_t), hipHostMallocDefault));
+        HIP_TRY(ctx, hipMalloc((void **)&ctx->proc->totals, 16 * sizeof(uint32_t)));
+    }
+    svo_proc_state *s = ctx->proc;
+    if (s->depth == depth) return SVO_OK;
+    if (s->alloc_depth < depth) {  // a shallower chunk reuses the buffers of a deeper one: every level fits
+        for (void *p : {(void *)s->cls, (void *)s->masks, (void *)s->ranks, (void *)s->tiles})
+            if (p) (void)hipFree(p);
+        s->cls = s->masks = nullptr;
+        s->ranks = s->tiles = nullptr;
+        s->alloc_depth = 0;
+        s->depth = 0;
+    }
+    uint64_t mb = 0, rb = 0, tb = 0;
+    for (uint32_t l = 0; l < depth; l++) {
+        const uint64_t n = pad_tile(1ull << (3 * l));
+        s->mask_off[l] = mb;
+        s->rank_off[l] = rb;
+        s->tile_off[l] = tb;
+        s->n_tiles[l] = (uint32_t)(n / kTile);
+        mb += n;
+        rb += n;
+        tb += n / kTile;
+    }
+    s->mask_bytes = mb;
+    if (!s->cls) {
+        HIP_TRY(ctx, hipMalloc((void **)&s->cls, 1ull << (3 * depth)));
+        HIP_TRY(ctx, hipMalloc((void **)&s->masks, mb));
+        HIP_TRY(ctx, hipMalloc((void **)&s->ranks, rb * sizeof(uint32_t)));
+        HIP_TRY(ctx, hipMalloc((void **)&s->tiles, tb * sizeof(uint32_t)));
+    }
+    if (!s->alloc_depth) s->alloc_depth = depth;
+    s->depth = depth;
+    return SVO_OK;
+}
+
+int launch_classify(svo_ctx *ctx, const svo_proc_params *p) {
+    svo_proc_state *s = ctx->proc;
+    const uint32_t n_cells = 1u << (3 * p->chunk_depth);
+    HIP_TRY(ctx, hipMemsetAsync(s->masks, 0, s->mask_bytes, ctx->stream));
+    proc_classify_kernel<<<blocks_for(n_cells), 256, 0, ctx->stream>>>(geom_of(p), n_cells, s->cls,
+                                                                         s->masks + s->mask_off[p->chunk_depth - 1]);
+    HIP_TRY(ctx, hipGetLastError());
+    return SVO_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int svo_proc_sdf(svo_ctx *ctx, const float *xyz, size_t n, float *out) {
+    if (!ctx) return SVO_ERR_ARG;
+    if ((!xyz || !out) && n) return fail(ctx, SVO_ERR_ARG, "null points or output");
+    if (n > (1ull << 28)) return fail(ctx, SVO_ERR_ARG, "at most 2^28 points per call");
+    if (!n) return SVO_OK;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    float *d = nullptr;
+    HIP_TRY(ctx, hipMalloc((void **)&d, n * 4 * sizeof(float)));
+    hipError_t e = hipMemcpyAsync(d, xyz, n * 3 * sizeof(float), hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) {
+        proc_sdf_kernel<<<blocks_for(n), 256, 0, ctx->stream>>>(d, (uint32_t)n, d + 3 * n);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(out, d + 3 * n, n * sizeof(float), hipMemcpyDeviceToHost, ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    (void)hipFree(d);
+    return e == hipSuccess ? SVO_OK : svo_fail_hip(ctx, e, "svo_proc_sdf");
+}
+
+int svo_proc_classify(svo_ctx *ctx, const svo_proc_params *params, uint8_t *cells_out) {
+    if (!ctx) return SVO_ERR_ARG;
+    int rc = check_params(ctx, params);
+    if (rc) return rc;
+    if (!cells_out) return fail(ctx, SVO_ERR_ARG, "null output");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if ((rc = ensure_state(ctx, params->chunk_depth))) return rc;
+    if ((rc = launch_classify(ctx, params))) return rc;
+    const uint32_t d = params->chunk_depth, side = 1u << d, n = 1u << (3 * d);
+    std::vector<uint8_t> morton(n);
+    HIP_TRY(ctx, hipMemcpyAsync(morton.data(), ctx->proc->cls, n, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    // the reference's id order: id = x + side * y + side^2 * z (procedual.wgsl:160-170)
+    for (uint32_t z = 0; z < side; z++)
+        for (uint32_t y = 0; y < side; y++)
+            for (uint32_t x = 0; x < side; x++) {
+                uint32_t m = 0;
+                for (uint32_t b = 0; b < d; b++)
+                    m |= ((x >> b) & 1u) << (3 * b + 2) | ((y >> b) & 1u) << (3 * b + 1) | ((z >> b) & 1u) << (3 * b);
+                cells_out[x + side * y + side * side * z] = morton[m];
+            }
+    return SVO_OK;
+}
+
+int svo_proc_generate_chunk(svo_ctx *ctx, const svo_proc_params *params, svo_cpu_octree **out) {
+    if (!ctx) return SVO_ERR_ARG;
+    if (!out) return fail(ctx, SVO_ERR_ARG, "null output");
+    *out = nullptr;
+    int rc = check_params(ctx, params);
+    if (rc) return rc;
+    const uint64_t max_nodes = params->max_nodes ? params->max_nodes : kDefaultMaxNodes;
+    const double t0 = now_ms();
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if ((rc = ensure_state(ctx, params->chunk_depth))) return rc;
+    svo_proc_state *s = ctx->proc;
+    const uint32_t depth = params->chunk_depth;
+
+    HIP_TRY(ctx, hipEventRecord(s->ev[0], ctx->stream));
+    if ((rc = launch_classify(ctx, params))) return rc;
+    HIP_TRY(ctx, hipEventRecord(s->ev[1], ctx->stream));
+    // occupancy pyramid: level L-1's masks from level L's
+    for (uint32_t l = depth - 1; l >= 1; l--) {
+        const uint32_t n_par = 1u << (3 * (l - 1));
+        proc_reduce_kernel<<<blocks_for(n_par), 256, 0, ctx->stream>>>(s->masks + s->mask_off[l], n_par, s->masks + s->mask_off[l - 1]);
+        HIP_TRY(ctx, hipGetLastError());
+    }
+    // ranks of the interior nodes of every level, and their counts
+    for (uint32_t l = 0; l < depth; l++) {
+        const uint8_t *m = s->masks + s->mask_off[l];
+        uint32_t *tiles = s->tiles + s->tile_off[l];
+        proc_tile_count_kernel<<<s->n_tiles[l], 256, 0, ctx->stream>>>(m, tiles);
+        proc_tile_scan_kernel<<<1, kTopThreads, 0, ctx->stream>>>(tiles, s->n_tiles[l], s->totals + l);
+        proc_tile_rank_kernel<<<s->n_tiles[l], 256, 0, ctx->stream>>>(m, tiles, s->ranks + s->rank_off[l]);
+        HIP_TRY(ctx, hipGetLastError());
+    }
+    HIP_TRY(ctx, hipEventRecord(s->ev[2], ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(s->totals_host, s->totals, depth * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+
+    // breadth-first bases: level 1 (the root group) at 0, level L+1 behind level L's 8 * interior(L-1) nodes
+    uint64_t base[11] = {0, 0};
+    for (uint32_t l = 1; l <= depth; l++) base[l + 1] = base[l] + 8ull * s->totals_host[l - 1];
+    const uint64_t n_nodes = base[depth + 1];
+    if (s->totals_host[0] == 0) {  // no solid cell: the reference's "len <= 8 -> None" (procedural.rs:167)
+        s->ms[0] = s->ms[1] = s->ms[2] = s->ms[4] = s->ms[5] = 0.0f;
+        s->ms[3] = float(now_ms() - t0);
+        return SVO_OK;
+    }
+    if (n_nodes > max_nodes)
+        return fail(ctx, SVO_ERR_CAP, "chunk needs " + std::to_string(n_nodes) + " nodes, over max_nodes = " + std::to_string(max_nodes) +
+                                          " (the reference panics here, procedural.rs:171-172)");
+    const size_t bytes = n_nodes * 8;
+    if (s->out_bytes < bytes) {
+        if (s->out) (void)hipFree(s->out);
+        s->out = nullptr;
+        s->out_bytes = 0;
+        HIP_TRY(ctx, hipMalloc((void **)&s->out, bytes));
+        s->out_bytes = bytes;
+    }
+    for (uint32_t l = 1; l <= depth; l++) {
+        const uint32_t n_par = 1u << (3 * (l - 1));
+        const bool last = l == depth;
+        proc_emit_kernel<<<blocks_for(n_par), 256, 0, ctx->stream>>>(
+            s->masks + s->mask_off[l - 1], s->ranks + s->rank_off[l - 1], n_par, last ? s->cls : s->masks + s->mask_off[l],
+            last ? nullptr : s->ranks + s->rank_off[l], last ? 1u : 0u, (uint32_t)base[l], (uint32_t)base[l + 1], (uint32_t)n_nodes, s->out);
+        HIP_TRY(ctx, hipGetLastError());
+    }
+    HIP_TRY(ctx, hipEventRecord(s->ev[3], ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    const double t1 = now_ms();
+    if (s->stage_bytes < bytes) {
+        if (s->stage) (void)hipHostFree(s->stage);
+        s->stage = nullptr;
+        s->stage_bytes = 0;
+        HIP_TRY(ctx, hipHostMalloc((void **)&s->stage, bytes, hipHostMallocDefault));
+        s->stage_bytes = bytes;
+    }
+    HIP_TRY(ctx, hipMemcpyAsync(s->stage, s->out, bytes, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    const double t2 = now_ms();
+    char why[128] = "";
+    *out = svo_cpu_octree_from_bin(s->stage, bytes, why, sizeof why);
+    if (!*out) return fail(ctx, SVO_ERR_STATE, std::string("emitted tree rejected: ") + why);
+    const double t3 = now_ms();
+    HIP_TRY(ctx, hipEventElapsedTime(&s->ms[0], s->ev[0], s->ev[1]));
+    HIP_TRY(ctx, hipEventElapsedTime(&s->ms[1], s->ev[1], s->ev[2]));
+    HIP_TRY(ctx, hipEventElapsedTime(&s->ms[2], s->ev[2], s->ev[3]));
+    s->ms[3] = float(t1 - t0);
+    s->ms[4] = float(t2 - t1);
+    s->ms[5] = float(t3 - t2);
+    return SVO_OK;
+}
+
+int svo_proc_timing(svo_ctx *ctx, float ms_out[SVO_PROC_TIMES]) {
+    if (!ctx || !ms_out) return SVO_ERR_ARG;
+    if (!ctx->proc) return fail(ctx, SVO_ERR_STATE, "no chunk generated on this context yet");
+    memcpy(ms_out, ctx->proc->ms, sizeof ctx->proc->ms);
+    return SVO_OK;
+}
+
+// World::generate_world (world.rs:63-139) without its "delete the directory if it is called tmp" rule.
+int svo_world_generate(svo_ctx *ctx, svo_world *w, uint32_t world_depth, uint32_t chunk_depth) {
+    if (!ctx) return SVO_ERR_ARG;
+    if (!w) return fail(ctx, SVO_ERR_ARG, "null world");
+    if (world_depth < 1 || world_depth > 4) return fail(ctx, SVO_ERR_ARG, "world_depth must be 1..4");
+    if (chunk_depth < 2 || chunk_depth > 9) return fail(ctx, SVO_ERR_ARG, "chunk_depth must be 2..9");
+    for (uint32_t b = 1; b <= 8; b++)  // mips of block leaves need the blocks' top_mip (World::new, world.rs:19-58)
+        if (!svo_world_chunk(w, b)) return fail(ctx, SVO_ERR_STATE, "block " + std::to_string(b) + " is not loaded (insert blocks 1..8 first)");
+    const std::string path = svo_world_path(w);
+    if (path.empty()) return fail(ctx, SVO_ERR_ARG, "world has no path");
+    if (mkdir(path.c_str(), 0777) != 0)
+        return fail(ctx, errno == EEXIST ? SVO_ERR_ARG : SVO_ERR_STATE,
+                    errno == EEXIST ? "File already exists" : "cannot create " + path + ": " + strerror(errno));
+    auto world_fail = [&](const char *what) { return fail(ctx, SVO_ERR_STATE, std::string(what) + ": " + svo_world_last_error(w)); };
+    float times[4] = {0, 0, 0, 0};  // GPU, read-back, mips, writes
+    svo_cpu_octree *root = svo_cpu_octree_new(0);
+    const uint32_t n = 1u << world_depth;
+    const float voxel = 2.0f / float(n);
+    uint32_t i = 0;
+    for (uint32_t x = 0; x < n; x++)
+        for (uint32_t y = 0; y < n; y++)
+            for (uint32_t z = 0; z < n; z++, i++) {
+                svo_proc_params p{};
+                p.pos[0] = float(x) * voxel - 1.0f;
+                p.pos[1] = float(y) * voxel - 1.0f;
+                p.pos[2] = float(z) * voxel - 1.0f;
+                p.base_depth = world_depth;
+                p.chunk_depth = chunk_depth;
+                const uint32_t id = kChunkOffset / 2 + i;
+                svo_cpu_octree *chunk = nullptr;
+                int rc = svo_proc_generate_chunk(ctx, &p, &chunk);
+                if (rc) {
+                    svo_cpu_octree_free(root);
+                    return rc;
+                }
+                times[0] += ctx->proc->ms[3];
+                times[1] += ctx->proc->ms[4] + ctx->proc->ms[5];
+                if (!chunk) continue;
+                svo_world_insert(w, id, chunk);
+                double t = now_ms();
+                if (svo_world_generate_mip_tree(w, id, nullptr) != 0) {
+                    svo_cpu_octree_free(root);
+                    return world_fail("mips");
+                }
+                times[2] += float(now_ms() - t);
+                t = now_ms();
+                if (svo_world_save_chunk(w, id) != 0) {
+                    svo_cpu_octree_free(root);
+                    return world_fail("save");
+                }
+                times[3] += float(now_ms() - t);
+                svo_cpu_octree_drop_nodes(chunk);  // keep only top_mip in memory (world.rs:122)
+                svo_cpu_octree_put_in_block(root, p.pos, id, world_depth);
+            }
+    svo_world_insert(w, 0, root);
+    double t = now_ms();
+    if (svo_world_generate_mip_tree(w, 0, nullptr) != 0) return world_fail("mips");
+    times[2] += float(now_ms() - t);
+    t = now_ms();
+    if (svo_world_save_chunk(w, 0) != 0) return world_fail("save");
+    times[3] += float(now_ms() - t);
+    memcpy(ctx->proc->ms + 6, times, sizeof times);
+    return SVO_OK;
+}
+
+}  // extern "C"

@@ -41,6 +41,18 @@ class World:
             raise ValueError(err.value.decode())
         return cls(path, _handle=h)
 
+    @staticmethod
+    def generate_world(path, procedural, world_depth=1, chunk_depth=9, blocks_dir=None):
+        """world.rs:63-139: write a new world to directory `path` (which must not exist; the reference's rule that
+        empties an existing directory named "tmp" is not kept).  Every non-empty chunk becomes <id>.bin, the root
+        0.bin; open the result with World.load_world(path).  The mips need blocks 1..8 (blocks_dir, as World.new)."""
+        if os.path.exists(path):
+            raise ValueError("File already exists")
+        if blocks_dir is None:
+            raise ValueError("generate_world needs blocks_dir: the mips of the chunks take blocks 1..8's colours")
+        w = World.new(path, blocks_dir)
+        procedural.gpu.check(lib().svo_world_generate(procedural.gpu._h, w._h, int(world_depth), int(chunk_depth)))
+
     def __del__(self):
         if getattr(self, "_h", None) and lib is not None:  # (module globals are gone at interpreter exit)
             lib().svo_world_free(self._h)
