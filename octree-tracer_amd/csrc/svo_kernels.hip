@@ -21,30 +21,12 @@
 #include "svo_device.h"
 #include "svo_trace_fn.h"
 
-// Build-time switches kept for same-box A/B builds (-DSVO_...=n); the defaults are what measured fastest.
-#ifndef SVO_WALK_STOP
-#define SVO_WALK_STOP 1
-#endif
-#ifndef SVO_TOP_IN_LDS   // 0: the top table is read from global memory (2 KiB less LDS per workgroup)
-#define SVO_TOP_IN_LDS 1
-#endif
-#ifndef SVO_WALK_TRIPS   // 1: the walk's depth limit is a count of its iterations (wave-uniform) instead of a test of every lane's level
-#define SVO_WALK_TRIPS 1
-#endif
-#ifndef SVO_WALK_ASM   // 1: the walk's loop hand-written (all but the timeline build): what follows a word's arrival is a compare, one scalar
-#define SVO_WALK_ASM 1  // instruction on the execute mask and the branch
-#endif
-#ifndef SVO_WALK_LUT   // 1: the walk takes the child indices of six levels at a time from one register built with three LDS look-ups (a 64-entry
-#define SVO_WALK_LUT 2  // bit-spreading table) instead of three bit-field extracts and two shift-ors per level (trees up to depth 16; the counting kernels too: SVO_WALK_LUT_CNT)
-#endif
-#ifndef SVO_WALK_LUT_CNT   // the same walk in the counting instantiations (hit counters live), the saturation notes as one carry bit per level
-#define SVO_WALK_LUT_CNT 1
-#endif
+// Build-time switches (-DSVO_...=n).  Two instrumentation builds of the timeline tools: SVO_DBG_LIGHT below and
+// SVO_PROBE_CLAIM_LATENCY (ray pick-up).  The rest set a number for A/B sweeps and carry no second code path: SVO_WAVES_PER_SIMD,
+// SVO_WAVES_PER_SIMD_CNT, SVO_COUNT_FLUSH_AT (here), SVO_COUNTER_STRIDE, SVO_COST_SHIFT (svo_device.h) and SVO_SAT_TAGS (svo_trace_fn.h).
+// The code paths that lost their A/B tests left the source; DESIGN.md Appendix A records each of them.
 #ifndef SVO_DBG_LIGHT   // 1: the timeline instantiation records only its time stamps (start, loop entry, generations, dry, end) and runs the
 #define SVO_DBG_LIGHT 0  // product's hand-written walk at the product's occupancy: a progress curve that is not distorted by the phase clocks
-#endif
-#ifndef SVO_CAM_SCALAR
-#define SVO_CAM_SCALAR 0
 #endif
 #ifndef SVO_WAVES_PER_SIMD_CNT   // of the counting instantiations (hit counters live)
 #define SVO_WAVES_PER_SIMD_CNT 6
@@ -319,7 +301,7 @@ __device__ __forceinline__ const TraceArgs &fresh_args() {
 // instead of into another region's data.  A new region goes IN FRONT of `stacks`.
 template <int BLOCK, int NS, int K, bool CNT>
 struct StackLds {
-    static constexpr int top = SVO_TOP_IN_LDS != 0 ? (1 << (3 * K)) : 0;                              // top table
+    static constexpr int top = 1 << (3 * K);                                                          // top table
     static constexpr int lut = top;                                                                   // the walk's bit-spreading table, 64 words
     static constexpr int pools = lut + 64;                                                            // [BLOCK / 64][kPoolWords][64]
     static constexpr int counting = pools + (BLOCK / 64) * (kPoolWords * 64);                         // CNT: queues, saturation tags, per-cell flags
@@ -340,12 +322,11 @@ __global__ __launch_bounds__(BLOCK, NS > 12 ? 4 : (CNT ? SVO_WAVES_PER_SIMD_CNT 
     constexpr int SMAX = K + 1 + NS;   // last level kept on the LDS stack = deepest level resolved
     static_assert(SMAX <= D - 1, "stack deeper than the path codes");
     constexpr int TBL = 1 << (3 * K);
-    constexpr bool kTopInLds = SVO_TOP_IN_LDS != 0;
     using Lds = StackLds<BLOCK, NS, K, CNT>;  // (the layout: one definition for kernel and launch)
     constexpr int kLutWords = 64;
     constexpr int LOFF = Lds::lut;
     constexpr int TOFF = Lds::pools;  // LDS words in front of the ray pools
-    constexpr bool kLut = SVO_WALK_LUT != 0 && NS <= 12 && (!CNT || SVO_WALK_LUT_CNT != 0);
+    constexpr bool kLut = NS <= 12;
     constexpr int SOFF = Lds::stacks;
     static_assert(Lds::total == SOFF + NS * BLOCK, "the ancestor stacks are the last LDS region (see StackLds)");
     static_assert(D == 23, "2^D + code must be an f32 with unit spacing");
@@ -369,7 +350,6 @@ __global__ __launch_bounds__(BLOCK, NS > 12 ? 4 : (CNT ? SVO_WAVES_PER_SIMD_CNT 
         sS0 = uni(copysign_bits(1.0f, sDr0)); sS1 = uni(copysign_bits(1.0f, sDr1)); sS2 = uni(copysign_bits(1.0f, sDr2));
     }
     extern __shared__ uint32_t lds[];
-    const uint32_t *tbl = kTopInLds ? lds : a.top_table;  // TBL entries
     uint32_t *pool_all = lds + TOFF;  // [BLOCK / 64][kPoolWords][64]; behind them the counting queues and tables (CNT), then the stacks [NS][BLOCK]
     // CNT: level-1 / level-2 cell -> child group (kTopAuxEntries words behind the top table): read from global memory, where the
     // 288 bytes stay in the L1 -- in LDS they cost the sixth workgroup per CU (the allocation granule)
@@ -492,16 +472,14 @@ __global__ __launch_bounds__(BLOCK, NS > 12 ? 4 : (CNT ? SVO_WAVES_PER_SIMD_CNT 
         cq_n += (uint32_t)__popcll(m);
     };
 
-    if (kTopInLds) {
-        for (uint32_t i = tid; i < (uint32_t)TBL; i += BLOCK) lds[i] = a.top_table[i];
-    }
+    for (uint32_t i = tid; i < (uint32_t)TBL; i += BLOCK) lds[i] = a.top_table[i];
     if (kLut && tid < (uint32_t)kLutWords) {  // entry v: bit j of v moved to bit 3 j, as a float (the three axes are combined by two fmas)
         uint32_t sp3 = 0u;
 #pragma unroll
         for (int j = 0; j < 6; j++) sp3 |= ((tid >> j) & 1u) << (3 * j);
         lds[LOFF + tid] = __float_as_uint((float)sp3);
     }
-    if (kTopInLds || kLut) __syncthreads();
+    __syncthreads();
 
     const uint32_t n_items = a.work.n_items;
     const uint32_t wave_id = __builtin_amdgcn_readfirstlane((blockIdx.x * BLOCK + tid) >> 6);
@@ -591,9 +569,8 @@ __global__ __launch_bounds__(BLOCK, NS > 12 ? 4 : (CNT ? SVO_WAVES_PER_SIMD_CNT 
     uint32_t sp = colbase + (kRb + (uint32_t)SBASE) * kRow;  // LDS slot (byte offset) one row BELOW the walk's next push
     uint32_t leaf_off = 0, leaf_w = 0;  // current leaf: byte offset of its word, and the word
     auto sabs = [](float x) -> float { return SHD ? __builtin_fabsf(x) : x; };  // (only the SHD instantiation has negative states)
-    constexpr bool kWalkStops = SVO_WALK_STOP != 0 && !CNT;
-    constexpr bool kWalkTrips = SVO_WALK_TRIPS != 0;
-    constexpr bool kWalkAsm = SVO_WALK_ASM != 0 && kWalkTrips && !DBGH;
+    constexpr bool kWalkStops = !CNT;   // the walk marks rays that end in their leaf (the counting kernel's step 3a sees them once more)
+    constexpr bool kWalkAsm = !DBGH;    // the walk's loop hand-written (the timeline build keeps the C++ loop for its tallies)
     uint32_t satm = 0;                // CNT: bit l = the word of level l on the lane's current path is known to be saturated (step 3a)
 
     // (re)start a descent: from the LDS top table when the restart level r is at most K+1 (the table also
@@ -610,7 +587,7 @@ __global__ __launch_bounds__(BLOCK, NS > 12 ? 4 : (CNT ? SVO_WAVES_PER_SIMD_CNT 
         if (__ballot(top)) {  // wave-uniform: most rounds no lane crosses a level-(K+1) boundary
             const uint32_t cell = (__builtin_amdgcn_ubfe(mu0, D - K, K) << (2 * K)) | (__builtin_amdgcn_ubfe(mu1, D - K, K) << K) |
                                   __builtin_amdgcn_ubfe(mu2, D - K, K);
-            const uint32_t e = kTopInLds ? lds_at(top ? cell * 4u : sp) : (top ? a.top_table[cell] : lds_at(sp));
+            const uint32_t e = lds_at(top ? cell * 4u : sp);
             sh = (kShMagic + (uint32_t)(D + 1)) - (top ? (e >> 27) : rb - kRb);
             nidx = e & 0x07FFFFFFu;
             // a walk from the table starts at level K+1 or above: its first push (if any) is the group of level K+2, row 0
@@ -629,7 +606,7 @@ __global__ __launch_bounds__(BLOCK, NS > 12 ? 4 : (CNT ? SVO_WAVES_PER_SIMD_CNT 
         const uint32_t steps = (uint32_t)stepsf;
         // a ray that ends without stopping in its leaf left the cube -- its count is at most 100 -- or ran into the step limit,
         // which is the one way to count 101 (shader.wgsl:237-244)
-        const bool too_deep = leaf_w < (kVoxelOffset << 4) || (kWalkTrips && __uint_as_float(sh) < kMagic + (float)(D - SMAX)), solid = (leaf_w >> 4) != kVoxelOffset, inb = steps == 101u;
+        const bool too_deep = leaf_w < (kVoxelOffset << 4) || __uint_as_float(sh) < kMagic + (float)(D - SMAX), solid = (leaf_w >> 4) != kVoxelOffset, inb = steps == 101u;
         const bool stop_here = too_deep || solid;
         if (too_deep) atomicOr(a.status, 1u);  // reported by svo_sync
         const uint32_t L = (uint32_t)D - sh_of(sh), nm = (uint32_t)__builtin_fmaf(nmf, 1.0f / kNudge, 0.5f);  // (nmf is 0 .. 7 times k, up to rounding)
@@ -698,308 +675,182 @@ __global__ __launch_bounds__(BLOCK, NS > 12 ? 4 : (CNT ? SVO_WAVES_PER_SIMD_CNT 
 
     // the one-level walk: one dependent word per level below (sh, nidx), ancestors pushed on the lane's LDS stack
     auto descend = [&]() {
-            uint32_t off, w, key;
-            // sh -= 1, then the child the position selects at the level of that bit: x << 2 | y << 1 | z.  Three-operand forms the
-            // compiler does not pick by itself, in ONE asm statement (the compiler pads every inline-asm statement with an s_nop, and
-            // keeping the decrement inside saves a copy of the counter)
-            // kLut (round 5): those five instructions of the 4-cycle group, once per level and lane, were a third of the walk's issue cycles.
-            // The child indices of SIX levels are taken at once instead: the six code bits of every axis below the restart level index a
-            // 64-entry LDS table that spreads them to every third bit (as a float), m = 4 sx + 2 sy + sz + 2^23 is two fmas and an add of
-            // the 2-cycle group, and a level's child index is ONE bit-field extract of m at a wave-uniform position (the lanes of a walk
-            // start at different levels but advance together).  Six levels later (one walk in a hundred) the look-up is repeated.
-            // First code bit wanted = sh - 1 >= D - SMAX = 7, so the table offset (code >> (sh - 8)) & 0xFC needs no left shift.
-            uint32_t m = 0u;
-            int32_t pos = 0;  // wave-uniform: bit position in m of the child index worked out last
-            auto lut_fetch = [&](float first_bit_minus_7) {  // (as the bits of 2^23 + that number: a shift amount is read from the low five bits)
-                const uint32_t k = __float_as_uint(first_bit_minus_7);
-                const float fx = __uint_as_float(lds_at((uint32_t)LOFF * 4u + ((mu0 >> (k & 31u)) & 0xFCu)));
-                const float fy = __uint_as_float(lds_at((uint32_t)LOFF * 4u + ((mu1 >> (k & 31u)) & 0xFCu)));
-                const float fz = __uint_as_float(lds_at((uint32_t)LOFF * 4u + ((mu2 >> (k & 31u)) & 0xFCu)));
-                m = __float_as_uint(__builtin_fmaf(fx, 4.0f, __builtin_fmaf(fy, 2.0f, fz + kMagic)));
-            };
-            constexpr bool kLutLate = SVO_WALK_LUT == 2;  // the first word's child the old way, the look-up in the shadow of the first load
-            if (kLut && !kLutLate) {
-                lut_fetch(__uint_as_float(sh) - 8.0f);
-                pos = 18;
+        uint32_t off, w;
+        // kLut (round 5): the child indices of SIX levels are taken at once: the six code bits of every axis below the restart level
+        // index a 64-entry LDS table that spreads them to every third bit (as a float), m = 4 sx + 2 sy + sz + 2^23 is two fmas and an
+        // add of the 2-cycle group, and a level's child index is ONE bit-field extract of m at a wave-uniform position (the lanes of a
+        // walk start at different levels but advance together) instead of child_bfe's five instructions of the 4-cycle group, which were
+        // a third of the walk's issue cycles.  Six levels later (one walk in a hundred) the look-up is repeated.  The first word's child
+        // is child_bfe's, and the first look-up is made in the shadow of the first load.
+        // First code bit wanted = sh - 1 >= D - SMAX = 7, so the table offset (code >> (sh - 8)) & 0xFC needs no left shift.
+        uint32_t m = 0u;
+        int32_t pos = 0;  // wave-uniform: bit position in m of the child index worked out last
+        auto lut_fetch = [&](float first_bit_minus_7) {  // (as the bits of 2^23 + that number: a shift amount is read from the low five bits)
+            const uint32_t k = __float_as_uint(first_bit_minus_7);
+            const float fx = __uint_as_float(lds_at((uint32_t)LOFF * 4u + ((mu0 >> (k & 31u)) & 0xFCu)));
+            const float fy = __uint_as_float(lds_at((uint32_t)LOFF * 4u + ((mu1 >> (k & 31u)) & 0xFCu)));
+            const float fz = __uint_as_float(lds_at((uint32_t)LOFF * 4u + ((mu2 >> (k & 31u)) & 0xFCu)));
+            m = __float_as_uint(__builtin_fmaf(fx, 4.0f, __builtin_fmaf(fy, 2.0f, fz + kMagic)));
+        };
+        // sh -= 1, then the child the position selects at the level of that bit: x << 2 | y << 1 | z.  Three-operand forms the
+        // compiler does not pick by itself, in ONE asm statement (the compiler pads every inline-asm statement with an s_nop, and
+        // keeping the decrement inside saves a copy of the counter)
+        auto child_bfe = [&]() -> uint32_t {
+            uint32_t c, tmp;
+            asm("v_add_f32 %2, -1.0, %2\n\t"
+                "v_bfe_u32 %0, %3, %2, 1\n\t"
+                "v_bfe_u32 %1, %4, %2, 1\n\t"
+                "v_lshl_or_b32 %0, %0, 1, %1\n\t"
+                "v_bfe_u32 %1, %5, %2, 1\n\t"
+                "v_lshl_or_b32 %0, %0, 1, %1"
+                : "=&v"(c), "=&v"(tmp), "+v"(sh)
+                : "v"(mu0), "v"(mu1), "v"(mu2));
+            return c;
+        };
+        auto child_below = [&]() -> uint32_t {
+            if (!kLut) return child_bfe();
+            sh = __float_as_uint(__uint_as_float(sh) - 1.0f);
+            pos -= 3;
+            if (pos < 0) {
+                lut_fetch(__uint_as_float(sh) - 7.0f);  // (sh is the bit of the level whose child is wanted now)
+                pos = 15;
             }
-            bool first_child = true;
-            auto child_below = [&]() -> uint32_t {
-                if (kLut && !(kLutLate && first_child)) {
-                    sh = __float_as_uint(__uint_as_float(sh) - 1.0f);
-                    pos -= 3;
-                    if (pos < 0) {
-                        lut_fetch(__uint_as_float(sh) - 7.0f);  // (sh is the bit of the level whose child is wanted now)
-                        pos = 15;
-                    }
-                    return __builtin_amdgcn_ubfe(m, (uint32_t)pos, 3u);
+            return __builtin_amdgcn_ubfe(m, (uint32_t)pos, 3u);
+        };
+        auto tally = [&]() {
+            if (DBGH) {
+                const uint64_t in_loop = __ballot(true);
+                if (lane == (uint32_t)__ffsll((unsigned long long)in_loop) - 1u) {  // (tallies summed over lanes at the end)
+                    if (!CNT) dbg_desc_iters += 1u;
+                    if (!CNT) dbg_desc_lanes += (uint32_t)__popcll(in_loop);
                 }
-                uint32_t c, tmp;
-                asm("v_add_f32 %2, -1.0, %2\n\t"
-                    "v_bfe_u32 %0, %3, %2, 1\n\t"
-                    "v_bfe_u32 %1, %4, %2, 1\n\t"
-                    "v_lshl_or_b32 %0, %0, 1, %1\n\t"
-                    "v_bfe_u32 %1, %5, %2, 1\n\t"
-                    "v_lshl_or_b32 %0, %0, 1, %1"
-                    : "=&v"(c), "=&v"(tmp), "+v"(sh)
-                    : "v"(mu0), "v"(mu1), "v"(mu2));
-                return c;
-            };
-            auto tally = [&]() {
-                if (DBGH) {
-                    const uint64_t in_loop = __ballot(true);
-                    if (lane == (uint32_t)__ffsll((unsigned long long)in_loop) - 1u) {  // (tallies summed over lanes at the end)
-                        if (!CNT) dbg_desc_iters += 1u;
-                        if (!CNT) dbg_desc_lanes += (uint32_t)__popcll(in_loop);
-                    }
-                }
-            };
-            // The loop is rotated twice.  (1) A word is read, then looked at: a leaf, or level SMAX, ends the walk BEFORE anything is
-            // pushed for it.  (2) While a word travels the child index of the NEXT level is worked out -- it depends on the position
-            // only -- so that between a word's arrival and the next load stand a shift and an add instead of eight instructions.
-            uint32_t c = child_below();
-            first_child = false;
-            bool first_word = true;
-            auto read_word = [&]() {
-                tally();
-                off = (nidx + c) << 2;
-                w = __builtin_amdgcn_raw_buffer_load_b32(rs, (int)off, 0, 0);
-                if (kLut && kLutLate && first_word) {
-                    __builtin_amdgcn_sched_barrier(0);  // (the look-up's address arithmetic behind the load, not in front of it)
-                    lut_fetch(__uint_as_float(sh) - 7.0f);  // (sh is the bit of the word in flight: the first of the six)
-                    asm volatile("" : "+v"(m));  // (here, under the load -- the compiler would sink it behind the wait for the word)
-                    pos = 15;
-                }
-                first_word = false;
-                // (a counter never goes down within a frame; the hand-written loop of the look-up-table walk takes its notes itself, see satb)
-                if (CNT && !(kWalkAsm && kLut)) satm |= ((w & 15u) == 15u ? 1u : 0u) << (((uint32_t)D - sh_of(sh)) & 31u);
-                c = child_below();  // (sh now points one level below the word in flight)
-                if (kLut) asm volatile("" : "+v"(c));  // (before the wait for the word, not behind it)
-                // sign bit: a leaf (word >= VOXEL_OFFSET << 4), or level SMAX reached (deeper trees are refused)
-                key = kWalkTrips ? w : (w | (sh_of(sh) - (uint32_t)(D - SMAX)));
-            };
-            read_word();
-            // kWalkTrips: a walk reads at most NS words below its first one in a tree of the declared depth -- the last of them, at level
-            // SMAX, a leaf.  In a deeper tree the count (one scalar subtraction per iteration instead of two vector instructions per lane)
-            // ends the walk; lanes that started low have gone past level SMAX by then: their pushes fell off the end of the LDS
-            // allocation (see SOFF).  A word found below level SMAX is handed on as an interior word, which is what the walk of rounds
-            // 1-3 stopped at: the ray ends there with the "too deep" record and svo_sync reports the frame.
-            uint32_t trips = (uint32_t)NS;
-            uint32_t satb = 0u;  // CNT, look-up-table walk: one saturation bit per word the hand-written loop has gone through, the last one lowest
-            if (kWalkAsm) {
-                // The same loop as below, instruction for instruction, but for its control: the compiler keeps the lanes that have
-                // left in a second mask and folds the count's flag into it -- four scalar instructions between a word's arrival
-                // and the next load; every instruction there costs the walk its latency (profiles/r04_walk_critical_path_ab.log).
-                if (CNT && kLut && (int32_t)w >= 0) {
-                    // (hit counters live, look-up-table walk: the loop of the kLut branch below plus the saturation note of the word that has
-                    // just arrived -- three instructions: its counter bits, a compare, and satb = 2 satb + carry.  After n iterations bit
-                    // n - 1 - i of satb belongs to the word of iteration i; the walk turns them into level bits of satm when it is over.)
-                    uint32_t tmp, cnt4;
-                    uint64_t saved;
-                    asm volatile(
-                        "s_mov_b64 %[sv], exec\n"
-                        "1:\n\t"
-                        "v_and_b32 %[t2], 15, %[w]\n\t"
-                        "v_lshrrev_b32 %[nidx], 4, %[w]\n\t"
-                        "v_add_lshl_u32 %[off], %[nidx], %[c], 2\n\t"
-                        "buffer_load_dword %[w], %[off], %[rs], 0 offen\n\t"
-                        "s_add_i32 %[trips], %[trips], -1\n\t"
-                        "v_cmp_eq_u32 vcc, 15, %[t2]\n\t"
-                        "v_addc_co_u32 %[satb], vcc, %[satb], %[satb], vcc\n\t"
-                        "v_add_u32 %[sp], %[row], %[sp]\n\t"
-                        "v_add_f32 %[sh], -1.0, %[sh]\n\t"
-                        "s_add_i32 %[pos], %[pos], -3\n\t"
-                        "s_cmp_lt_i32 %[pos], 0\n\t"
-                        "s_cbranch_scc1 3f\n"
-                        "4:\n\t"
-                        "v_bfe_u32 %[c], %[m], %[pos], 3\n\t"
-                        "ds_write_b32 %[sp], %[nidx]\n\t"
-                        "s_cmp_eq_u32 %[trips], 0\n\t"
-                        "s_cbranch_scc1 2f\n\t"
-                        "s_waitcnt vmcnt(0)\n\t"
-                        "v_cmp_gt_i32 vcc, 0, %[w]\n\t"
-                        "s_andn2_b64 exec, exec, vcc\n\t"
-                        "s_cbranch_execnz 1b\n\t"
-                        "s_branch 2f\n"
-                        "3:\n\t"
-                        "v_add_f32 %[m], 0xc0e00000, %[sh]\n\t"
-                        "v_lshrrev_b32 %[c], %[m], %[m0]\n\t"
-                        "v_lshrrev_b32 %[t], %[m], %[m1]\n\t"
-                        "v_lshrrev_b32 %[m], %[m], %[m2]\n\t"
-                        "v_and_b32 %[c], 0xfc, %[c]\n\t"
-                        "v_and_b32 %[t], 0xfc, %[t]\n\t"
-                        "v_and_b32 %[m], 0xfc, %[m]\n\t"
-                        "ds_read_b32 %[c], %[c] offset:%[lut]\n\t"
-                        "ds_read_b32 %[t], %[t] offset:%[lut]\n\t"
-                        "ds_read_b32 %[m], %[m] offset:%[lut]\n\t"
-                        "s_waitcnt lgkmcnt(0)\n\t"
-                        "v_add_f32 %[m], 0x4b000000, %[m]\n\t"
-                        "v_fmac_f32 %[m], 2.0, %[t]\n\t"
-                        "v_fmac_f32 %[m], 4.0, %[c]\n\t"
-                        "s_mov_b32 %[pos], 15\n\t"
-                        "s_branch 4b\n"
-                        "2:\n\t"
-                        "s_waitcnt vmcnt(0)\n\t"
-                        "s_mov_b64 exec, %[sv]"
-                        : [w] "+v"(w), [nidx] "+v"(nidx), [off] "+v"(off), [c] "+v"(c), [t] "=&v"(tmp), [t2] "=&v"(cnt4), [sp] "+v"(sp), [sh] "+v"(sh),
-                          [m] "+v"(m), [satb] "+v"(satb), [trips] "+s"(trips), [pos] "+s"(pos), [sv] "=&s"(saved)
-                        : [m0] "v"(mu0), [m1] "v"(mu1), [m2] "v"(mu2), [rs] "s"(rs_asm), [row] "s"((uint32_t)(BLOCK * 4)), [lut] "n"(LOFF * 4)
-                        : "vcc", "scc", "memory");
-                } else if (CNT && !kLut && (int32_t)w >= 0) {
-                    // (hit counters live: an interior word whose counter has reached 15 is noted in satm, bit = its level, while the
-                    // next word travels -- only the counter bits are taken before the load is issued; the word that ends the walk
-                    // needs no note: step 3a looks at the leaf's own counter, and bit L is cleared by every restart before it is read)
-                    uint32_t tmp, cnt4;
-                    uint64_t saved;
-                    asm volatile(
-                        "s_mov_b64 %[sv], exec\n"
-                        "1:\n\t"
-                        "v_and_b32 %[t2], 15, %[w]\n\t"
-                        "v_lshrrev_b32 %[nidx], 4, %[w]\n\t"
-                        "v_add_lshl_u32 %[off], %[nidx], %[c], 2\n\t"
-                        "buffer_load_dword %[w], %[off], %[rs], 0 offen\n\t"
-                        "s_add_i32 %[trips], %[trips], -1\n\t"
-                        "v_cmp_eq_u32 vcc, 15, %[t2]\n\t"
-                        "v_sub_u32 %[t], %[dm1], %[sh]\n\t"
-                        "v_cndmask_b32_e64 %[t2], 0, 1, vcc\n\t"
-                        "v_lshlrev_b32 %[t2], %[t], %[t2]\n\t"
-                        "v_or_b32 %[satm], %[satm], %[t2]\n\t"
-                        "v_add_u32 %[sp], %[row], %[sp]\n\t"
-                        "v_add_f32 %[sh], -1.0, %[sh]\n\t"
-                        "v_bfe_u32 %[c], %[m0], %[sh], 1\n\t"
-                        "v_bfe_u32 %[t], %[m1], %[sh], 1\n\t"
-                        "v_lshl_or_b32 %[c], %[c], 1, %[t]\n\t"
-                        "v_bfe_u32 %[t], %[m2], %[sh], 1\n\t"
-                        "v_lshl_or_b32 %[c], %[c], 1, %[t]\n\t"
-                        "ds_write_b32 %[sp], %[nidx]\n\t"
-                        "s_cmp_eq_u32 %[trips], 0\n\t"
-                        "s_cbranch_scc1 2f\n\t"
-                        "s_waitcnt vmcnt(0)\n\t"
-                        "v_cmp_gt_i32 vcc, 0, %[w]\n\t"
-                        "s_andn2_b64 exec, exec, vcc\n\t"
-                        "s_cbranch_execnz 1b\n"
-                        "2:\n\t"
-                        "s_waitcnt vmcnt(0)\n\t"
-                        "s_mov_b64 exec, %[sv]"
-                        : [w] "+v"(w), [nidx] "+v"(nidx), [off] "+v"(off), [c] "+v"(c), [t] "=&v"(tmp), [t2] "=&v"(cnt4), [sp] "+v"(sp), [sh] "+v"(sh),
-                          [satm] "+v"(satm), [trips] "+s"(trips), [sv] "=&s"(saved)
-                        : [m0] "v"(mu0), [m1] "v"(mu1), [m2] "v"(mu2), [rs] "s"(rs_asm), [row] "s"((uint32_t)(BLOCK * 4)), [dm1] "s"((uint32_t)(D - 1))
-                        : "vcc", "scc", "memory");
-                } else if (!CNT && kLut && (int32_t)w >= 0) {
-                    // (the loop of the next branch with the child index taken from m: one bit-field extract at the scalar position pos;
-                    // label 3 is the table look-up for the next six levels, taken when pos runs out -- in the shadow of the load like the rest)
-                    uint32_t tmp;
-                    uint64_t saved;
-                    asm volatile(
-                        "s_mov_b64 %[sv], exec\n"
-                        "1:\n\t"
-                        "v_lshrrev_b32 %[nidx], 4, %[w]\n\t"
-                        "v_add_lshl_u32 %[off], %[nidx], %[c], 2\n\t"
-                        "buffer_load_dword %[w], %[off], %[rs], 0 offen\n\t"
-                        "s_add_i32 %[trips], %[trips], -1\n\t"
-                        "v_add_u32 %[sp], %[row], %[sp]\n\t"
-                        "v_add_f32 %[sh], -1.0, %[sh]\n\t"
-                        "s_add_i32 %[pos], %[pos], -3\n\t"
-                        "s_cmp_lt_i32 %[pos], 0\n\t"
-                        "s_cbranch_scc1 3f\n"
-                        "4:\n\t"
-                        "v_bfe_u32 %[c], %[m], %[pos], 3\n\t"
-                        "ds_write_b32 %[sp], %[nidx]\n\t"
-                        "s_cmp_eq_u32 %[trips], 0\n\t"
-                        "s_cbranch_scc1 2f\n\t"
-                        "s_waitcnt vmcnt(0)\n\t"
-                        "v_cmp_gt_i32 vcc, 0, %[w]\n\t"
-                        "s_andn2_b64 exec, exec, vcc\n\t"
-                        "s_cbranch_execnz 1b\n\t"
-                        "s_branch 2f\n"
-                        "3:\n\t"
-                        "v_add_f32 %[m], 0xc0e00000, %[sh]\n\t"
-                        "v_lshrrev_b32 %[c], %[m], %[m0]\n\t"
-                        "v_lshrrev_b32 %[t], %[m], %[m1]\n\t"
-                        "v_lshrrev_b32 %[m], %[m], %[m2]\n\t"
-                        "v_and_b32 %[c], 0xfc, %[c]\n\t"
-                        "v_and_b32 %[t], 0xfc, %[t]\n\t"
-                        "v_and_b32 %[m], 0xfc, %[m]\n\t"
-                        "ds_read_b32 %[c], %[c] offset:%[lut]\n\t"
-                        "ds_read_b32 %[t], %[t] offset:%[lut]\n\t"
-                        "ds_read_b32 %[m], %[m] offset:%[lut]\n\t"
-                        "s_waitcnt lgkmcnt(0)\n\t"
-                        "v_add_f32 %[m], 0x4b000000, %[m]\n\t"
-                        "v_fmac_f32 %[m], 2.0, %[t]\n\t"
-                        "v_fmac_f32 %[m], 4.0, %[c]\n\t"
-                        "s_mov_b32 %[pos], 15\n\t"
-                        "s_branch 4b\n"
-                        "2:\n\t"
-                        "s_waitcnt vmcnt(0)\n\t"
-                        "s_mov_b64 exec, %[sv]"
-                        : [w] "+v"(w), [nidx] "+v"(nidx), [off] "+v"(off), [c] "+v"(c), [t] "=&v"(tmp), [sp] "+v"(sp), [sh] "+v"(sh), [m] "+v"(m),
-                          [trips] "+s"(trips), [pos] "+s"(pos), [sv] "=&s"(saved)
-                        : [m0] "v"(mu0), [m1] "v"(mu1), [m2] "v"(mu2), [rs] "s"(rs_asm), [row] "s"((uint32_t)(BLOCK * 4)), [lut] "n"(LOFF * 4)
-                        : "vcc", "scc", "memory");
-                } else if (!CNT && (int32_t)w >= 0) {
-                    uint32_t tmp;
-                    uint64_t saved;
-                    asm volatile(
-                        "s_mov_b64 %[sv], exec\n"
-                        "1:\n\t"
-                        "v_lshrrev_b32 %[nidx], 4, %[w]\n\t"
-                        "v_add_lshl_u32 %[off], %[nidx], %[c], 2\n\t"
-                        "buffer_load_dword %[w], %[off], %[rs], 0 offen\n\t"
-                        "s_add_i32 %[trips], %[trips], -1\n\t"
-                        "v_add_u32 %[sp], %[row], %[sp]\n\t"
-                        "v_add_f32 %[sh], -1.0, %[sh]\n\t"
-                        "v_bfe_u32 %[c], %[m0], %[sh], 1\n\t"
-                        "v_bfe_u32 %[t], %[m1], %[sh], 1\n\t"
-                        "v_lshl_or_b32 %[c], %[c], 1, %[t]\n\t"
-                        "v_bfe_u32 %[t], %[m2], %[sh], 1\n\t"
-                        "v_lshl_or_b32 %[c], %[c], 1, %[t]\n\t"
-                        "ds_write_b32 %[sp], %[nidx]\n\t"
-                        "s_cmp_eq_u32 %[trips], 0\n\t"
-                        "s_cbranch_scc1 2f\n\t"
-                        "s_waitcnt vmcnt(0)\n\t"
-                        "v_cmp_gt_i32 vcc, 0, %[w]\n\t"
-                        "s_andn2_b64 exec, exec, vcc\n\t"
-                        "s_cbranch_execnz 1b\n"
-                        "2:\n\t"
-                        "s_waitcnt vmcnt(0)\n\t"
-                        "s_mov_b64 exec, %[sv]"
-                        : [w] "+v"(w), [nidx] "+v"(nidx), [off] "+v"(off), [c] "+v"(c), [t] "=&v"(tmp), [sp] "+v"(sp), [sh] "+v"(sh),
-                          [trips] "+s"(trips), [sv] "=&s"(saved)
-                        : [m0] "v"(mu0), [m1] "v"(mu1), [m2] "v"(mu2), [rs] "s"(rs_asm), [row] "s"((uint32_t)(BLOCK * 4))
-                        : "vcc", "scc", "memory");
-                }
-            } else
-            while ((int32_t)key >= 0 && (!kWalkTrips || trips != 0u)) {
-                if (kWalkTrips) trips -= 1u;
+            }
+        };
+        // The loop is rotated twice.  (1) A word is read, then looked at: a leaf, or level SMAX, ends the walk BEFORE anything is
+        // pushed for it.  (2) While a word travels the child index of the NEXT level is worked out -- it depends on the position
+        // only -- so that between a word's arrival and the next load stand a shift and an add instead of eight instructions.
+        uint32_t c = child_bfe();
+        auto read_word = [&](bool first) {
+            tally();
+            off = (nidx + c) << 2;
+            w = __builtin_amdgcn_raw_buffer_load_b32(rs, (int)off, 0, 0);
+            if (kLut && first) {
+                __builtin_amdgcn_sched_barrier(0);  // (the look-up's address arithmetic behind the load, not in front of it)
+                lut_fetch(__uint_as_float(sh) - 7.0f);  // (sh is the bit of the word in flight: the first of the six)
+                asm volatile("" : "+v"(m));  // (here, under the load -- the compiler would sink it behind the wait for the word)
+                pos = 15;
+            }
+            // (a counter never goes down within a frame; the hand-written loop of the look-up-table walk takes its notes itself, see satb)
+            if (CNT && !(kWalkAsm && kLut)) satm |= ((w & 15u) == 15u ? 1u : 0u) << (((uint32_t)D - sh_of(sh)) & 31u);
+            c = child_below();  // (sh now points one level below the word in flight)
+            if (kLut) asm volatile("" : "+v"(c));  // (before the wait for the word, not behind it)
+        };
+        read_word(true);
+        // A walk reads at most NS words below its first one in a tree of the declared depth -- the last of them, at level SMAX, a leaf;
+        // the word's sign bit says whether it is one (word >= VOXEL_OFFSET << 4).  In a deeper tree the count of iterations (one scalar
+        // subtraction instead of two vector instructions per lane) ends the walk; lanes that started low have gone past level SMAX by
+        // then: their pushes fell off the end of the LDS allocation (see SOFF).  A word found below level SMAX is handed on as an
+        // interior word, which is what the walk of rounds 1-3 stopped at: the ray ends there with the "too deep" record and svo_sync
+        // reports the frame.
+        uint32_t trips = (uint32_t)NS;
+        uint32_t satb = 0u;  // CNT, look-up-table walk: one saturation bit per word the hand-written loop has gone through, the last one lowest
+        if (kWalkAsm) {
+            // The same loop as the C++ one below, instruction for instruction, but for its control: the compiler keeps the lanes that
+            // have left in a second mask and folds the count's flag into it -- four scalar instructions between a word's arrival and
+            // the next load; every instruction there costs the walk its latency (profiles/r04_walk_critical_path_ab.log).  Its text
+            // is written once, in fragments; each of the four forms names its fragments and adds only its own operands to the shared
+            // ones (an operand a form does not use still takes a vector register).
+#define WALK_ENTRY "s_mov_b64 %[sv], exec\n1:\n\t"
+#define WALK_CNT_BITS "v_and_b32 %[t2], 15, %[w]\n\t"
+#define WALK_LOAD "v_lshrrev_b32 %[nidx], 4, %[w]\n\t" "v_add_lshl_u32 %[off], %[nidx], %[c], 2\n\t"                            \
+                  "buffer_load_dword %[w], %[off], %[rs], 0 offen\n\t" "s_add_i32 %[trips], %[trips], -1\n\t"
+// (hit counters live, look-up-table walk: the saturation note of the word that has just arrived -- three instructions: its counter
+// bits, a compare, and satb = 2 satb + carry.  After n iterations bit n - 1 - i of satb belongs to the word of iteration i; the walk
+// turns them into level bits of satm when it is over.)
+#define WALK_SAT_CARRY "v_cmp_eq_u32 vcc, 15, %[t2]\n\t" "v_addc_co_u32 %[satb], vcc, %[satb], %[satb], vcc\n\t"
+// (hit counters live, the other walk: an interior word whose counter has reached 15 is noted in satm, bit = its level, while the next
+// word travels -- only the counter bits are taken before the load is issued; the word that ends the walk needs no note: step 3a looks
+// at the leaf's own counter, and bit L is cleared by every restart before it is read)
+#define WALK_SAT_LEVEL "v_cmp_eq_u32 vcc, 15, %[t2]\n\t" "v_sub_u32 %[t], %[dm1], %[sh]\n\t" "v_cndmask_b32_e64 %[t2], 0, 1, vcc\n\t" \
+                       "v_lshlrev_b32 %[t2], %[t], %[t2]\n\t" "v_or_b32 %[satm], %[satm], %[t2]\n\t"
+#define WALK_STEP "v_add_u32 %[sp], %[row], %[sp]\n\t" "v_add_f32 %[sh], -1.0, %[sh]\n\t"
+// (kLut: the child index from m, one bit-field extract at the scalar position pos; label 3, WALK_LUT_REFILL, is the table look-up
+// for the next six levels, taken when pos runs out -- in the shadow of the load like the rest)
+#define WALK_CHILD_LUT "s_add_i32 %[pos], %[pos], -3\n\t" "s_cmp_lt_i32 %[pos], 0\n\t" "s_cbranch_scc1 3f\n4:\n\t"               \
+                       "v_bfe_u32 %[c], %[m], %[pos], 3\n\t"
+// (the other walk: child_bfe's instructions)
+#define WALK_CHILD_BFE "v_bfe_u32 %[c], %[m0], %[sh], 1\n\t" "v_bfe_u32 %[t], %[m1], %[sh], 1\n\t"                               \
+                       "v_lshl_or_b32 %[c], %[c], 1, %[t]\n\t" "v_bfe_u32 %[t], %[m2], %[sh], 1\n\t"                             \
+                       "v_lshl_or_b32 %[c], %[c], 1, %[t]\n\t"
+#define WALK_LOOP "ds_write_b32 %[sp], %[nidx]\n\t" "s_cmp_eq_u32 %[trips], 0\n\t" "s_cbranch_scc1 2f\n\t" "s_waitcnt vmcnt(0)\n\t" \
+                  "v_cmp_gt_i32 vcc, 0, %[w]\n\t" "s_andn2_b64 exec, exec, vcc\n\t" "s_cbranch_execnz 1b\n\t"
+#define WALK_LUT_REFILL "s_branch 2f\n3:\n\t" "v_add_f32 %[m], 0xc0e00000, %[sh]\n\t"                                             \
+                        "v_lshrrev_b32 %[c], %[m], %[m0]\n\t" "v_lshrrev_b32 %[t], %[m], %[m1]\n\t" "v_lshrrev_b32 %[m], %[m], %[m2]\n\t" \
+                        "v_and_b32 %[c], 0xfc, %[c]\n\t" "v_and_b32 %[t], 0xfc, %[t]\n\t" "v_and_b32 %[m], 0xfc, %[m]\n\t"         \
+                        "ds_read_b32 %[c], %[c] offset:%[lut]\n\t" "ds_read_b32 %[t], %[t] offset:%[lut]\n\t"                     \
+                        "ds_read_b32 %[m], %[m] offset:%[lut]\n\t" "s_waitcnt lgkmcnt(0)\n\t"                                      \
+                        "v_add_f32 %[m], 0x4b000000, %[m]\n\t" "v_fmac_f32 %[m], 2.0, %[t]\n\t" "v_fmac_f32 %[m], 4.0, %[c]\n\t"    \
+                        "s_mov_b32 %[pos], 15\n\t" "s_branch 4b\n\t"
+#define WALK_EXIT "2:\n\t" "s_waitcnt vmcnt(0)\n\t" "s_mov_b64 exec, %[sv]"
+#define WALK_OUT [w] "+v"(w), [nidx] "+v"(nidx), [off] "+v"(off), [c] "+v"(c), [t] "=&v"(tmp), [sp] "+v"(sp), [sh] "+v"(sh),      \
+                 [trips] "+s"(trips), [sv] "=&s"(saved)
+#define WALK_IN [m0] "v"(mu0), [m1] "v"(mu1), [m2] "v"(mu2), [rs] "s"(rs_asm), [row] "s"((uint32_t)(BLOCK * 4))
+            uint32_t tmp, cnt4;
+            uint64_t saved;
+            if ((int32_t)w >= 0) {
+                if (CNT && kLut)
+                    asm volatile(WALK_ENTRY WALK_CNT_BITS WALK_LOAD WALK_SAT_CARRY WALK_STEP WALK_CHILD_LUT WALK_LOOP WALK_LUT_REFILL WALK_EXIT
+                                 : WALK_OUT, [t2] "=&v"(cnt4), [m] "+v"(m), [satb] "+v"(satb), [pos] "+s"(pos)
+                                 : WALK_IN, [lut] "n"(LOFF * 4) : "vcc", "scc", "memory");
+                else if (CNT)
+                    asm volatile(WALK_ENTRY WALK_CNT_BITS WALK_LOAD WALK_SAT_LEVEL WALK_STEP WALK_CHILD_BFE WALK_LOOP WALK_EXIT
+                                 : WALK_OUT, [t2] "=&v"(cnt4), [satm] "+v"(satm)
+                                 : WALK_IN, [dm1] "s"((uint32_t)(D - 1)) : "vcc", "scc", "memory");
+                else if (kLut)
+                    asm volatile(WALK_ENTRY WALK_LOAD WALK_STEP WALK_CHILD_LUT WALK_LOOP WALK_LUT_REFILL WALK_EXIT
+                                 : WALK_OUT, [m] "+v"(m), [pos] "+s"(pos)
+                                 : WALK_IN, [lut] "n"(LOFF * 4) : "vcc", "scc", "memory");
+                else
+                    asm volatile(WALK_ENTRY WALK_LOAD WALK_STEP WALK_CHILD_BFE WALK_LOOP WALK_EXIT
+                                 : WALK_OUT : WALK_IN : "vcc", "scc", "memory");
+            }
+#undef WALK_ENTRY
+#undef WALK_CNT_BITS
+#undef WALK_LOAD
+#undef WALK_SAT_CARRY
+#undef WALK_SAT_LEVEL
+#undef WALK_STEP
+#undef WALK_CHILD_LUT
+#undef WALK_CHILD_BFE
+#undef WALK_LOOP
+#undef WALK_LUT_REFILL
+#undef WALK_EXIT
+#undef WALK_OUT
+#undef WALK_IN
+        } else {
+            while ((int32_t)w >= 0 && trips != 0u) {
+                trips -= 1u;
                 nidx = w >> 4;
                 sp += (uint32_t)(BLOCK * 4);
-                if (kWalkTrips) asm("" : "+v"(sp));  // (keeps the compiler from turning sp into base + a scalar: one more v_add per iteration)
+                asm("" : "+v"(sp));  // (keeps the compiler from turning sp into base + a scalar: one more v_add per iteration)
                 lds_at(sp) = nidx;
-#if defined(SVO_DUMMY_WALK_S) || defined(SVO_DUMMY_WALK_F)
-                {
-#ifdef SVO_DUMMY_WALK_S
-                    for (int i_ = 0; i_ < SVO_DUMMY_WALK_S; i_++) { uint32_t t_; asm volatile("v_bfe_u32 %0, %1, 1, 30" : "=v"(t_) : "v"(mu0)); }
-#endif
-#ifdef SVO_DUMMY_WALK_F
-                    for (int i_ = 0; i_ < SVO_DUMMY_WALK_F; i_++) { uint32_t t_; asm volatile("v_add_f32 %0, 1.0, %1" : "=v"(t_) : "v"(mu0)); }
-#endif
-                }
-#endif
-                read_word();
+                read_word(false);
             }
-            sh = __float_as_uint(__uint_as_float(sh) + 1.0f);  // back to the leaf's own bit
-            // (the loop's notes: bit j of satb = the word j + 1 levels above the leaf, i.e. level L - 1 - j with L = D - sh; 32 - L = 9 + sh)
-            if (CNT && kWalkAsm && kLut) satm |= __builtin_bitreverse32(satb) >> ((sh + (uint32_t)(32 - D)) & 31u);
-            // (a word found below level SMAX -- the tree is deeper than declared -- ends the ray like the interior word the walk of rounds 1-3
-            // stopped at; compared as floats: sh may have passed 0)
-            const bool below = kWalkTrips && __uint_as_float(sh) < kMagic + (float)(D - SMAX);
-            if (kWalkTrips && !kWalkStops) w = below ? 0u : w;
-            leaf_off = off;
-            leaf_w = w;
-            // ST_DESC -> ST_LEAF; or straight to ST_PENDING when the ray ends in this leaf (anything but an empty leaf: a solid one, or
-            // an interior word at level SMAX) -- with live hit counters the step section has to see the lane once more (step 3a)
-            if (kWalkStops) stf *= ((w >> 4) != kVoxelOffset || below) ? 0.25f : 0.5f;
-            else stf *= 0.5f;
-            };
+        }
+        sh = __float_as_uint(__uint_as_float(sh) + 1.0f);  // back to the leaf's own bit
+        // (the loop's notes: bit j of satb = the word j + 1 levels above the leaf, i.e. level L - 1 - j with L = D - sh; 32 - L = 9 + sh)
+        if (CNT && kWalkAsm && kLut) satm |= __builtin_bitreverse32(satb) >> ((sh + (uint32_t)(32 - D)) & 31u);
+        // (a word found below level SMAX -- the tree is deeper than declared -- ends the ray like the interior word the walk of rounds 1-3
+        // stopped at; compared as floats: sh may have passed 0)
+        const bool below = __uint_as_float(sh) < kMagic + (float)(D - SMAX);
+        if (!kWalkStops) w = below ? 0u : w;
+        leaf_off = off;
+        leaf_w = w;
+        // ST_DESC -> ST_LEAF; or straight to ST_PENDING when the ray ends in this leaf (anything but an empty leaf: a solid one, or
+        // an interior word at level SMAX) -- with live hit counters the step section has to see the lane once more (step 3a)
+        if (kWalkStops) stf *= ((w >> 4) != kVoxelOffset || below) ? 0.25f : 0.5f;
+        else stf *= 0.5f;
+    };
 
     // Camera shortcut.  Every primary ray of a camera that stands INSIDE the cube starts at the same point, hence in the
     // same leaf, with the same ancestors: the first walk of a ray -- the longest it ever makes, root to leaf, while the
@@ -1010,11 +861,7 @@ __global__ __launch_bounds__(BLOCK, NS > 12 ? 4 : (CNT ? SVO_WAVES_PER_SIMD_CNT 
     // (Not with live hit counters: the copied leaf word would carry the counter bits it had when the wave started, and
     // every ray's compare-and-swap on that one word would fail once -- two million serialised atomics on one address.)
     constexpr bool CAM = !CNT;
-    // (kCamScalar: the camera's walk in eighteen scalar registers instead of the lanes of one vector register -- a build-time trial:
-    // the compiler parks the array in vector registers and spills, 52 bytes of scratch, so it stays off)
-    constexpr bool kCamScalar = SVO_CAM_SCALAR != 0 && NS <= 12;
     uint32_t camv = 0;
-    uint32_t cam_rows[NS] = {}, cam_leaf_off = 0, cam_leaf_w = 0, cam_sh = 0, cam_mu0 = 0, cam_mu1 = 0, cam_mu2 = 0;
     bool cam_ok = false;  // wave-uniform
     if (CAM && a.cam_shortcut && a.work.mode != 2) {
         const RayIn r0 = gen_ray(a.u, 0u, 0u);  // (the position does not depend on the pixel)
@@ -1030,16 +877,6 @@ __global__ __launch_bounds__(BLOCK, NS > 12 ? 4 : (CNT ? SVO_WAVES_PER_SIMD_CNT 
             v = lane == (uint32_t)NS + 1u ? leaf_w : v;
             v = lane == (uint32_t)NS + 2u ? sh : v;  // (D - the leaf's level)
             camv = v;
-            if (kCamScalar) {
-#pragma unroll
-                for (int l = 0; l < NS; l++) cam_rows[l] = (uint32_t)__builtin_amdgcn_readlane((int)v, l);
-                cam_leaf_off = (uint32_t)__builtin_amdgcn_readfirstlane((int)leaf_off);
-                cam_leaf_w = (uint32_t)__builtin_amdgcn_readfirstlane((int)leaf_w);
-                cam_sh = (uint32_t)__builtin_amdgcn_readfirstlane((int)sh);
-                cam_mu0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)mu0);
-                cam_mu1 = (uint32_t)__builtin_amdgcn_readfirstlane((int)mu1);
-                cam_mu2 = (uint32_t)__builtin_amdgcn_readfirstlane((int)mu2);
-            }
             // worth it when the camera's leaf is deep (the copy at pick-up costs about two walk iterations)
             cam_ok = (uint32_t)D - sh_of((uint32_t)__builtin_amdgcn_readfirstlane(sh)) >= (uint32_t)(SBASE + 2);
             stf = ST_IDLE;
@@ -1245,22 +1082,13 @@ __global__ __launch_bounds__(BLOCK, NS > 12 ? 4 : (CNT ? SVO_WAVES_PER_SIMD_CNT 
                         nmf = 0.0f;
                         if (CAM && cam_ok && dist == 0.0f) {
                             // a ray from the camera's own position: the walk the wave made at the start (see above), path codes included
-                            if (kCamScalar) {
-#pragma unroll
-                                for (int l = 0; l < NS; l++) lds_at(colbase + (kRb + (uint32_t)SBASE + (uint32_t)l) * kRow) = cam_rows[l];  // (rows below the leaf: never read)
-                                leaf_off = cam_leaf_off;
-                                leaf_w = cam_leaf_w;
-                                sh = cam_sh;
-                                mu0 = cam_mu0; mu1 = cam_mu1; mu2 = cam_mu2;
-                            } else {
-                                const uint32_t sh0 = (uint32_t)__builtin_amdgcn_readlane((int)camv, NS + 2), L0 = (uint32_t)D - sh_of(sh0);
-                                for (uint32_t l = 0; l < (uint32_t)NS && l + (uint32_t)SBASE <= L0; l++)
-                                    lds_at(colbase + (kRb + (uint32_t)SBASE + l) * kRow) = (uint32_t)__builtin_amdgcn_readlane((int)camv, (int)l);
-                                leaf_off = (uint32_t)__builtin_amdgcn_readlane((int)camv, NS);
-                                leaf_w = (uint32_t)__builtin_amdgcn_readlane((int)camv, NS + 1);
-                                sh = sh0;
-                                mu0 = entry_magic<GE>(P0); mu1 = entry_magic<GE>(P1); mu2 = entry_magic<GE>(P2);
-                            }
+                            const uint32_t sh0 = (uint32_t)__builtin_amdgcn_readlane((int)camv, NS + 2), L0 = (uint32_t)D - sh_of(sh0);
+                            for (uint32_t l = 0; l < (uint32_t)NS && l + (uint32_t)SBASE <= L0; l++)
+                                lds_at(colbase + (kRb + (uint32_t)SBASE + l) * kRow) = (uint32_t)__builtin_amdgcn_readlane((int)camv, (int)l);
+                            leaf_off = (uint32_t)__builtin_amdgcn_readlane((int)camv, NS);
+                            leaf_w = (uint32_t)__builtin_amdgcn_readlane((int)camv, NS + 1);
+                            sh = sh0;
+                            mu0 = entry_magic<GE>(P0); mu1 = entry_magic<GE>(P1); mu2 = entry_magic<GE>(P2);
                             stf = (kWalkStops && (leaf_w >> 4) != kVoxelOffset) ? ST_PENDING : ST_LEAF;  // at its leaf, no step taken
                         } else {
                             // entry path codes (the position may sit a rounding error outside the cube: clamp)
@@ -1307,11 +1135,10 @@ __global__ __launch_bounds__(BLOCK, NS > 12 ? 4 : (CNT ? SVO_WAVES_PER_SIMD_CNT 
             // (Wave-uniform control flow around per-lane predicates: the queue cursor is a scalar.)
             // (a lane whose walk ended below level SMAX -- a tree deeper than declared: its ray ends with the "too deep" record and the frame
             // is refused -- reports no visits: ADVICE r4)
-            const bool at_leaf = sabs(stf) == ST_LEAF && !(kWalkTrips && __uint_as_float(sh) < kMagic + (float)(D - SMAX));
+            const bool at_leaf = sabs(stf) == ST_LEAF && !(__uint_as_float(sh) < kMagic + (float)(D - SMAX));
             const uint64_t c_c0 = DBGH ? __builtin_amdgcn_s_memtime() : 0ull;
             if (__ballot(at_leaf) != 0ull) {
-                // (a word below level SMAX ends the ray: the tree is deeper than declared -- with kWalkTrips such a lane is not at_leaf)
-                const uint32_t L = kWalkTrips ? (uint32_t)D - sh_of(sh) : min((uint32_t)D - sh_of(sh), (uint32_t)SMAX);
+                const uint32_t L = (uint32_t)D - sh_of(sh);  // (at most SMAX: a lane whose walk ended below level SMAX is not at_leaf)
                 uint32_t todo = at_leaf ? (~satm & ((1u << L) - 2u)) : 0u;  // levels 1 .. L-1 not known to be saturated
                 constexpr uint32_t kTopLv = (2u << K) - 2u;  // levels 1 .. K
                 auto cell_k = [&](uint32_t x0, uint32_t x1, uint32_t x2) -> uint32_t {
@@ -1337,7 +1164,7 @@ __global__ __launch_bounds__(BLOCK, NS > 12 ? 4 : (CNT ? SVO_WAVES_PER_SIMD_CNT 
                         g = lds_at(colbase + (l + kRb) * kRow);
                     } else if (l >= 2u) {
                         const uint32_t cell = (__builtin_amdgcn_ubfe(mu0, shc, kk) << (2u * kk)) | (__builtin_amdgcn_ubfe(mu1, shc, kk) << kk) | __builtin_amdgcn_ubfe(mu2, shc, kk);
-                        g = kk == (uint32_t)K ? (tbl[cell] & 0x07FFFFFFu) : aux[(kk == 1u ? 0u : 8u) + cell];
+                        g = kk == (uint32_t)K ? (lds[cell] & 0x07FFFFFFu) : aux[(kk == 1u ? 0u : 8u) + cell];
                     }
                     const uint32_t bit = (uint32_t)D - l;  // (l = 0: bit D, which belongs to the exponent of kMagic -- and p is replaced below)
                     uint32_t p = g + ((__builtin_amdgcn_ubfe(mu0, bit, 1u) << 2) | (__builtin_amdgcn_ubfe(mu1, bit, 1u) << 1) |
@@ -1422,9 +1249,6 @@ __global__ __launch_bounds__(BLOCK, NS > 12 ? 4 : (CNT ? SVO_WAVES_PER_SIMD_CNT 
                     const uint32_t lbit = __float_as_uint(__builtin_fmaf(Hm, 2.0f, kMagic)) & ((1u << D) - 1u);  // 1 << sh
                     const uint32_t diff = ((mu0 ^ n0) | (mu1 ^ n1) | (mu2 ^ n2)) | lbit;
                     mu0 = n0; mu1 = n1; mu2 = n2;
-#ifdef SVO_DUMMY_STEP_S
-                    for (int i_ = 0; i_ < SVO_DUMMY_STEP_S; i_++) { uint32_t t_; asm volatile("v_bfe_u32 %0, %1, 1, 30" : "=v"(t_) : "v"(mu0)); }
-#endif
                     const uint32_t rb = (uint32_t)__builtin_clz(diff);  // r + (31 - D); diff != 0
                     if (CNT) {  // levels r and below belong to a new path
                         satm &= (1u << (rb - kRb)) - 1u;
@@ -2163,11 +1987,8 @@ __global__ __launch_bounds__(256) void strip_cull_kernel(TraceArgs a, const uint
 }
 
 // blocks per row for the schedule builder's column-major ranks (0: rank in strip order): frames of one rectangle of whole pixel blocks
-#ifndef SVO_ORDER_COLMAJOR
-#define SVO_ORDER_COLMAJOR 1
-#endif
 static uint32_t order_bpr(const WorkDesc &w, uint32_t n_strips) {
-    if (!SVO_ORDER_COLMAJOR || w.mode == 2 || w.n_rects > 1u || w.bpr == 0u || n_strips % w.bpr != 0u || n_strips * 64u != w.n_items) return 0u;
+    if (w.mode == 2 || w.n_rects > 1u || w.bpr == 0u || n_strips % w.bpr != 0u || n_strips * 64u != w.n_items) return 0u;
     return w.bpr;
 }
 

@@ -6,10 +6,6 @@
 
 #include "svo_device.h"
 
-#ifndef SVO_STREAM_RECORDS
-#define SVO_STREAM_RECORDS 1
-#endif
-
 namespace svo {
 
 // ---------------------------------------------------------------------------------------------
@@ -113,11 +109,7 @@ __device__ __forceinline__ void write_hit(svo_hit *hits, uint32_t out, uint32_t 
     // node lines they push out are fetched again; nobody reads a record before the frame is over)
     typedef uint32_t rec_t __attribute__((ext_vector_type(4)));
     const rec_t rec = {value, __float_as_uint(t), (steps & 0xFFu) | ((depth & 0xFFu) << 8) | (hit << 16) | (ncode << 17), ncode};
-#if SVO_STREAM_RECORDS
     __builtin_nontemporal_store(rec, reinterpret_cast<rec_t *>(hits) + out);
-#else
-    reinterpret_cast<rec_t *>(hits)[out] = rec;
-#endif
 }
 
 __device__ __forceinline__ float code_to_normal(uint32_t c) { return c == 1u ? 1.0f : (c == 2u ? -1.0f : 0.0f); }
@@ -291,17 +283,10 @@ __device__ __forceinline__ float div_by_recip(float a, float d, float y) {
 
 // RN(1 / d) for 2^-20 <= |d| <= 2^64: the hardware reciprocal (1 ulp) and one Newton step; equal to the IEEE division for every
 // such d ON gfx950 (tools/rcptest_gpu.hip compares all of them -- tests/test_lds_oob_gpu.py runs it on the GPU under test --; svo_kernels.hip
-// refuses to build for another target; SVO_RECIP_IEEE=1 builds the division instead)
-#ifndef SVO_RECIP_IEEE
-#define SVO_RECIP_IEEE 0
-#endif
+// refuses to build for another target)
 __device__ __forceinline__ float recip_rn(float d) {
-#if SVO_RECIP_IEEE
-    return 1.0f / d;
-#else
     const float r = __builtin_amdgcn_rcpf(d);
     return __builtin_fmaf(__builtin_fmaf(-d, r, 1.0f), r, r);
-#endif
 }
 
 // floor(x) and floor(-x) = -ceil(x) as integers in one instruction (|x| < 2^24 here, no saturation involved)
