@@ -3,8 +3,10 @@
 // and the device halves of render.rs / compute.rs (citations in the header).
 #include <hip/hip_runtime.h>
 
+#include <array>
 #include <cmath>
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <new>
 #include <string>
@@ -134,6 +136,82 @@ struct TraceOpts {
     svo_hit *shadow_out = nullptr;  // STACK: trace the shadow ray of every hit inside this launch, records here
 };
 
+// The arguments every launch over the context's tree starts from: nodes, uniforms, work layout and records.
+svo::TraceArgs trace_args(const svo_ctx *ctx, const svo::WorkDesc &work, svo_hit *hits) {
+    svo::TraceArgs a{};
+    a.nodes = ctx->nodes;
+    a.n_words = (uint32_t)ctx->capacity;
+    a.u = ctx->uniforms;
+    a.work = work;
+    a.hits = hits;
+    return a;
+}
+
+// n explicit rays, one item each
+svo::WorkDesc ray_work(size_t n) {
+    svo::WorkDesc w{};
+    w.mode = 2;
+    w.n_items = (uint32_t)n;
+    w.bpr = w.bprect = w.tiles_x = 1;
+    return w;
+}
+
+// Before a STACK trace (svo_sched.h: plan_before_trace): the slot's buffers, equal shares for a new layout, and the lists the
+// trace claims from -- this frame's filtered ones, built here, or the ones kept from an earlier frame.
+int schedule_before(svo_ctx *ctx, svo_ctx::Sched &sc, const svo::FrameFacts &f, svo::TraceArgs &a, uint32_t n_strips) {
+    if (f.schedule && sc.cap < n_strips) {
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        HIP_TRY(ctx, sc.alloc(n_strips));
+    }
+    const svo::TracePlan plan = svo::plan_before_trace(sc.state, f);
+    if (!f.schedule) return SVO_OK;
+    if (plan.reset_shares) {
+        static const auto equal_shares = [] {  // (static: the copy is asynchronous)
+            std::array<uint32_t, svo::kBalanceWords> w{};
+            for (uint32_t k = 0; k <= 8; k++) w[k] = k * 8192u;
+            return w;
+        }();
+        HIP_TRY(ctx, hipMemcpyAsync(sc.buf.balance, equal_shares.data(), sizeof(equal_shares), hipMemcpyHostToDevice, ctx->stream));
+    }
+    a.balance = plan.feed_balance ? sc.buf.balance : nullptr;
+    a.order_cap = svo::order_list_cap(n_strips);
+    if (f.filtered) {
+        // slots without a ray (secondary rays of pixels that hit nothing): this frame's lists leave out the strips
+        // that consist of nothing else, ordered by the costs of an earlier frame when there are any
+        // (likewise for pixel frames seen from outside the cube: strips of sky are culled before the trace, their zero
+        // records written by the culling pass)
+        const uint8_t *prev = plan.prior_costs ? sc.buf.cost : nullptr;
+        if (a.skip)
+            HIP_TRY(ctx, svo::launch_schedule_skipping(a, prev, sc.buf.cls_now, sc.buf.order, n_strips, a.order_cap, ctx->stream));
+        else
+            HIP_TRY(ctx, svo::launch_schedule_culling(a, prev, sc.buf.cls_now, sc.buf.order, n_strips, a.order_cap, ctx->stream));
+        a.order = sc.buf.order;
+    } else if (plan.stored_lists) {
+        a.order = sc.buf.order;
+    }
+    return SVO_OK;
+}
+
+// After a STACK trace (svo_sched.h: plan_after_trace): the post pass -- deferred rays, counter re-arm, and what the plan measures
+// and builds for the next frames.
+int schedule_after(svo_ctx *ctx, svo_ctx::Sched &sc, svo::FrameFacts &f, const svo::TraceArgs &a, const svo::LaunchInfo &li,
+                   int sched_slot) {
+    // (caller-supplied rays cannot be compared: they always count as moving)
+    f.same_input = (a.work.mode != 2 || sched_slot == 1) && sc.built_nodes_version == ctx->store->version &&
+                   memcmp(&sc.built_uniforms, &ctx->uniforms, sizeof(svo_uniforms)) == 0;
+    f.moving = sc.have_prev && memcmp(&sc.prev_uniforms, &ctx->uniforms, sizeof(svo_uniforms)) != 0;
+    const svo::PostPlan plan = svo::plan_after_trace(sc.state, f);
+    HIP_TRY(ctx, svo::launch_post(a, li, plan, sc.buf, ctx->stream));
+    sc.prev_uniforms = ctx->uniforms;
+    sc.have_prev = true;
+    if (plan.rebuild) {
+        sc.key = a.work;
+        sc.built_uniforms = ctx->uniforms;
+        sc.built_nodes_version = ctx->store->version;
+    }
+    return SVO_OK;
+}
+
 int trace_launch(svo_ctx *ctx, const svo::WorkDesc &work, const float *rays, svo_hit *hits, const TraceOpts &opt) {
     int rc = bind(ctx);
     if (rc) return rc;
@@ -147,19 +225,16 @@ int trace_launch(svo_ctx *ctx, const svo::WorkDesc &work, const float *rays, svo
         rc = order_after_last_write(ctx);
         if (rc) return rc;
     }
+    const bool debug_hits = (ctx->uniforms.flags & SVO_F_PAUSE_ADAPTIVE) && (ctx->uniforms.flags & SVO_F_SHOW_HITS);
+    const bool stack = want_stack && !debug_hits;
     svo::WorkDesc wd = work;
     auto magic = [](uint32_t d) -> uint32_t { return d <= 1u ? 0u : (uint32_t)(0x100000000ull / d) + 1u; };
     wd.magic_bpr = magic(wd.bpr);
     wd.magic_bprect = magic(wd.bprect);
     wd.magic_tiles_x = magic(wd.tiles_x);
-    svo::TraceArgs a{};
-    a.nodes = ctx->nodes;
-    a.n_words = (uint32_t)ctx->capacity;
+    svo::TraceArgs a = trace_args(ctx, wd, hits);
     a.top_table = ctx->top_table;
-    a.u = ctx->uniforms;
-    a.work = wd;
     a.rays = rays;
-    a.hits = hits;
     a.aux_t = opt.aux_t;
     a.status = ctx->status;
     a.refill_min = ctx->refill_min;
@@ -169,56 +244,24 @@ int trace_launch(svo_ctx *ctx, const svo::WorkDesc &work, const float *rays, svo
     // shader.wgsl:159: counters are live unless pause_adaptive; rays handed in by the caller (svo_trace_rays) never count
     const bool counting = (work.mode != 2 || opt.count_rays) && !(ctx->uniforms.flags & SVO_F_PAUSE_ADAPTIVE);
     a.count_nodes = counting ? ctx->nodes : nullptr;
-    const bool debug_hits = (ctx->uniforms.flags & SVO_F_PAUSE_ADAPTIVE) && (ctx->uniforms.flags & SVO_F_SHOW_HITS);
-    const bool stack = want_stack && !debug_hits;
     a.shadow_hits = stack ? opt.shadow_out : nullptr;
+
     const uint32_t n_strips = (wd.n_items + 63u) / 64u;
-    const bool schedule = ctx->schedule && n_strips <= svo::kMaxScheduledStrips;
     svo_ctx::Sched &sc = ctx->sched[opt.sched_slot & 1];
-    const bool cull = stack && schedule && wd.mode != 2 && hits != nullptr && cull_worthwhile(ctx);
-    const bool filtered = stack && schedule && (opt.skip != nullptr || cull);
-    if (stack && schedule) {
-        if (sc.cap < n_strips) {
-            HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-            if (sc.cost) (void)hipFree(sc.cost);
-            if (sc.cls_now) (void)hipFree(sc.cls_now);
-            if (sc.order) (void)hipFree(sc.order);
-            if (sc.balance) (void)hipFree(sc.balance);
-            sc = svo_ctx::Sched{};
-            size_t want = n_strips < 4096 ? 4096 : n_strips;
-            HIP_TRY(ctx, hipMalloc((void **)&sc.cost, want + 32 + svo::kOrderHistWords * sizeof(uint32_t)));
-            HIP_TRY(ctx, hipMalloc((void **)&sc.cls_now, want + 32 + svo::kOrderHistWords * sizeof(uint32_t)));
-            HIP_TRY(ctx, hipMalloc((void **)&sc.order, (2 * want + 8 * (svo::kCostClasses + 8) + 8) * sizeof(uint32_t)));  // (8 lists of order_list_cap entries)
-            HIP_TRY(ctx, hipMalloc((void **)&sc.balance, svo::kBalanceWords * sizeof(uint32_t)));
-            sc.cap = want;
-        }
-        // costs and order are only meaningful for the same work layout (same pixels behind every strip)
-        if (sc.valid && memcmp(&sc.key, &wd, sizeof(wd)) != 0) sc.valid = false;
-        if (!sc.valid) {  // a new layout starts from equal shares of the lists
-            uint32_t init[svo::kBalanceWords] = {};
-            for (uint32_t k = 0; k <= 8; k++) init[k] = k * 8192u;
-            HIP_TRY(ctx, hipMemcpyAsync(sc.balance, init, sizeof(init), hipMemcpyHostToDevice, ctx->stream));
-            sc.balance_frames = 0;
-        }
-        a.balance = ctx->list_balance ? sc.balance : nullptr;
-        a.order_cap = svo::order_list_cap(wd, n_strips);
-        if (filtered) {
-            // slots without a ray (secondary rays of pixels that hit nothing): this frame's lists leave out the strips
-            // that consist of nothing else, ordered by the costs of an earlier frame when there are any
-            // (likewise for pixel frames seen from outside the cube: strips of sky are culled before the trace, their zero
-            // records written by the culling pass)
-            if (opt.skip)
-                HIP_TRY(ctx, svo::launch_schedule_skipping(opt.skip, wd.n_items, sc.valid ? sc.cost : nullptr, sc.cls_now, sc.order, n_strips,
-                                                           a.order_cap, ctx->stream));
-            else
-                HIP_TRY(ctx, svo::launch_schedule_culling(a, sc.valid ? sc.cost : nullptr, sc.cls_now, sc.order, n_strips, a.order_cap,
-                                                          ctx->stream));
-            a.order = sc.order;
-            sc.order_filtered = true;  // these lists leave strips out: good for this frame only
-        } else {
-            a.order = (sc.valid && !sc.order_filtered) ? sc.order : nullptr;
-        }
+    svo::FrameFacts f;
+    f.schedule = ctx->schedule && n_strips <= svo::kMaxScheduledStrips;
+    f.filtered = f.schedule && (opt.skip != nullptr || (wd.mode != 2 && hits != nullptr && cull_worthwhile(ctx)));
+    f.same_layout = memcmp(&sc.key, &wd, sizeof(wd)) == 0;  // (same pixels behind every strip)
+    f.mode = wd.mode;
+    f.n_rects = wd.n_rects;
+    f.motion_floor = ctx->motion_floor;
+    f.sched_period = ctx->sched_period;
+    f.balance = ctx->list_balance;
+    if (stack) {
+        rc = schedule_before(ctx, sc, f, a, n_strips);
+        if (rc) return rc;
     }
+
     svo::LaunchInfo li{};
     li.variant = stack ? SVO_VARIANT_STACK : SVO_VARIANT_RESTART;
     li.grid_blocks = ctx->grid_blocks;
@@ -238,8 +281,7 @@ int trace_launch(svo_ctx *ctx, const svo::WorkDesc &work, const float *rays, svo
         HIP_TRY(ctx, hipMemsetAsync(ctx->defer_buf, 0, (svo::kCounterWords + 2 * (want + 1)) * sizeof(uint32_t), ctx->stream));
         ctx->defer_items = want;
     }
-    li.counters = ctx->defer_buf;
-    li.work_counter = ctx->defer_buf;  // (strips are always claimed dynamically; SVO_OPT_DYNAMIC_STRIPS is accepted and ignored)
+    li.counters = ctx->defer_buf;  // (strips are always claimed dynamically)
     if (ctx->defer_buf) {
         uint32_t *lists = ctx->defer_buf + svo::kCounterWords;
         const size_t stride = ctx->defer_items + 1;
@@ -254,45 +296,10 @@ int trace_launch(svo_ctx *ctx, const svo::WorkDesc &work, const float *rays, svo
         HIP_TRY(ctx, hipEventRecord(ctx->ev[2 * slot + 1], ctx->stream));
         ctx->ev_count++;
     }
-    if (stack) {
-        // deferred rays, scheduling feedback for the next frames, counter re-arm
-        // Rebuild the schedule when there is none, and every sched_period frames while the input moves.  A ray's step
-        // count does not depend on the order it was traced in, so a schedule measured on this camera and tree stays
-        // exact as long as both stay put (caller-supplied rays cannot be compared: they always count as moving; 64
-        // frames is a backstop for node buffers written behind this context's back).
-        const bool same_input = (wd.mode != 2 || opt.sched_slot == 1) && sc.built_nodes_version == ctx->store->version &&
-                                memcmp(&sc.built_uniforms, &ctx->uniforms, sizeof(svo_uniforms)) == 0 && sc.age < 64;
-        const bool moving = sc.have_prev && memcmp(&sc.prev_uniforms, &ctx->uniforms, sizeof(svo_uniforms)) != 0;
-        // (a frame traced with complete lists also feeds the time its lists took back into their shares: while camera and tree stay
-        // put the lists are rebuilt for the first sixteen such frames, then the shares have settled)
-        const bool fed_back = a.balance != nullptr && a.order != nullptr && !filtered;
-        const bool rebuild = schedule && (!sc.valid || (sc.order_filtered && !filtered) || (!same_input && sc.age + 1 >= ctx->sched_period) ||
-                                          (same_input && sc.floored && !moving) || (same_input && fed_back && sc.balance_frames < 16u));
-        // (a resting view rebuilt for the shares' sake only: its strips' cost classes are the ones measured last time, the pass is skipped)
-        const bool shares_only = rebuild && sc.valid && same_input && fed_back && sc.balance_frames < 16u && !(sc.order_filtered && !filtered) &&
-                                 !(sc.floored && !moving);
-        // a camera in motion: strips near the long ones of this frame are not scheduled as cheap (strip_danger_kernel)
-        const bool floor_now = rebuild && !filtered && moving && ctx->motion_floor != 0u && wd.mode == 0 && wd.n_rects == 1u;
-        // (a launch with a skip mask builds its lists before the trace, every frame: here only the costs are measured)
-        HIP_TRY(ctx, svo::launch_post(a, li, rebuild ? sc.cost : nullptr, sc.order, n_strips, svo::order_list_cap(wd, n_strips),
-                                      rebuild && !filtered, ctx->stream, floor_now ? sc.cls_now : nullptr, ctx->motion_floor,
-                                      (fed_back && (!same_input || sc.balance_frames < 16u)) ? sc.balance_frames + 1u : 0u, shares_only));
-        if (fed_back) sc.balance_frames++;
-        if (rebuild && !filtered) sc.floored = floor_now;
-        sc.prev_uniforms = ctx->uniforms;
-        sc.have_prev = true;
-        ctx->frame_parity ^= 1;
-        if (rebuild) {
-            if (!filtered) sc.order_filtered = false;  // the post pass has just built complete lists
-            sc.key = wd;
-            sc.valid = true;
-            sc.age = 0;
-            sc.built_uniforms = ctx->uniforms;
-            sc.built_nodes_version = ctx->store->version;
-        } else if (schedule) {
-            sc.age++;
-        }
-    }
+    if (!stack) return SVO_OK;
+    rc = schedule_after(ctx, sc, f, a, li, opt.sched_slot);  // deferred rays, scheduling feedback for the next frames, counter re-arm
+    if (rc) return rc;
+    ctx->frame_parity ^= 1;
     return SVO_OK;
 }
 
@@ -302,8 +309,7 @@ int trace_launch(svo_ctx *ctx, const svo::WorkDesc &work, const float *rays, svo
 // there is one launch, one set of claims, one tail.  (Until the claim counters were split -- eight per list -- a 1080p frame
 // of the depth-16 terrain was 5 % slower fused and the automatic mode fused only deep trees, 4K frames and counting frames;
 // since then: 1080p 0.646 -> 0.581 ms, 4K 2.04 -> 1.78 ms, depth-20 fractal -24 %.)
-bool fuse_shadow_rays(const svo_ctx *ctx, size_t n_pixels) {
-    (void)n_pixels;
+bool fuse_shadow_rays(const svo_ctx *ctx) {
     const bool want = ctx->fused_shadows != 0;
     if (!want || ctx->variant == SVO_VARIANT_RESTART || ctx->tree_depth > (uint32_t)svo::stack_max_depth(true)) return false;
     const float *sd = ctx->uniforms.sun_dir;
@@ -344,7 +350,7 @@ int trace_common(svo_ctx *ctx, const svo::WorkDesc &work, const float *rays, svo
         if (rc) return rc;
         hits = (svo_hit *)ctx->shade_hits;
     }
-    const bool fused = shadows && fuse_shadow_rays(ctx, n);
+    const bool fused = shadows && fuse_shadow_rays(ctx);
     TraceOpts primary;
     if (fused) {
         rc = ensure_dev(ctx, &ctx->shade_shadow, &ctx->shade_shadow_bytes, n * sizeof(svo_hit));
@@ -357,12 +363,7 @@ int trace_common(svo_ctx *ctx, const svo::WorkDesc &work, const float *rays, svo
     }
     rc = trace_launch(ctx, work, nullptr, hits, primary);
     if (rc) return rc;
-    svo::TraceArgs a{};
-    a.nodes = ctx->nodes;
-    a.n_words = (uint32_t)ctx->capacity;
-    a.u = ctx->uniforms;
-    a.work = work;
-    a.hits = hits;
+    const svo::TraceArgs a = trace_args(ctx, work, hits);
     if (shadows && !fused) {
         rc = ensure_dev(ctx, &ctx->shade_rays, &ctx->shade_rays_bytes, n * 6 * sizeof(float));
         if (rc) return rc;
@@ -372,15 +373,11 @@ int trace_common(svo_ctx *ctx, const svo::WorkDesc &work, const float *rays, svo
         if (rc) return rc;
         HIP_TRY(ctx, svo::launch_secondary_gen(a, (const float *)ctx->shade_aux, (float *)ctx->shade_rays, (uint8_t *)ctx->shade_skip,
                                                (svo_hit *)ctx->shade_shadow, 0u, 1u, (uint32_t)n, ctx->stream));
-        svo::WorkDesc rw{};
-        rw.mode = 2;
-        rw.n_items = (uint32_t)n;
-        rw.bpr = rw.bprect = rw.tiles_x = 1;
         TraceOpts shadow;
         shadow.count_rays = true;
         shadow.sched_slot = 1;
         shadow.skip = (const uint8_t *)ctx->shade_skip;
-        rc = trace_launch(ctx, rw, (const float *)ctx->shade_rays, (svo_hit *)ctx->shade_shadow, shadow);
+        rc = trace_launch(ctx, ray_work(n), (const float *)ctx->shade_rays, (svo_hit *)ctx->shade_shadow, shadow);
         if (rc) return rc;
     }
     HIP_TRY(ctx, svo::launch_shade(a, shadows ? (const svo_hit *)ctx->shade_shadow : nullptr, rgba, ctx->stream));
@@ -408,7 +405,7 @@ int trace_secondary(svo_ctx *ctx, const svo::WorkDesc &work, uint32_t n_secondar
     if (rc) return rc;
     // ray 0, the shadow ray, can run inside the primary launch (its records go straight to the first set)
     const bool debug_view = (ctx->uniforms.flags & SVO_F_PAUSE_ADAPTIVE) && (ctx->uniforms.flags & SVO_F_SHOW_HITS);
-    const bool fused = !debug_view && fuse_shadow_rays(ctx, n);
+    const bool fused = !debug_view && fuse_shadow_rays(ctx);
     const uint32_t k_first = fused ? 1u : 0u;
     TraceOpts popt;
     popt.aux_t = (float *)ctx->shade_aux;
@@ -416,26 +413,27 @@ int trace_secondary(svo_ctx *ctx, const svo::WorkDesc &work, uint32_t n_secondar
     rc = trace_launch(ctx, work, nullptr, primary, popt);
     if (rc) return rc;
     if (k_first == n_secondary) return SVO_OK;
-    svo::TraceArgs a{};
-    a.nodes = ctx->nodes;
-    a.n_words = (uint32_t)ctx->capacity;
-    a.u = ctx->uniforms;
-    a.work = work;
-    a.hits = primary;
+    const svo::TraceArgs a = trace_args(ctx, work, primary);
     rc = ensure_dev(ctx, &ctx->shade_skip, &ctx->shade_skip_bytes, n * n_secondary);
     if (rc) return rc;
     svo_hit *rest = secondary + (size_t)k_first * n;
     HIP_TRY(ctx, svo::launch_secondary_gen(a, (const float *)ctx->shade_aux, (float *)ctx->shade_rays, (uint8_t *)ctx->shade_skip, rest,
                                            k_first, n_secondary, (uint32_t)n, ctx->stream));
-    svo::WorkDesc rw{};
-    rw.mode = 2;
-    rw.n_items = (uint32_t)(n * (n_secondary - k_first));
-    rw.bpr = rw.bprect = rw.tiles_x = 1;
     TraceOpts sopt;
     sopt.count_rays = true;  // like the shadow ray, which passes primary = true (shader.wgsl:276)
     sopt.sched_slot = 1;
     sopt.skip = (const uint8_t *)ctx->shade_skip;
-    return trace_launch(ctx, rw, (const float *)ctx->shade_rays, rest, sopt);
+    return trace_launch(ctx, ray_work(n * (n_secondary - k_first)), (const float *)ctx->shade_rays, rest, sopt);
+}
+
+// pixel blocks of 2^bw_log2 x 64 / 2^bw_log2 over a w x h rectangle
+void set_blocks(svo::WorkDesc &work, uint32_t bw_log2, uint32_t w, uint32_t h) {
+    const uint32_t bw = 1u << bw_log2, bh = 64u >> bw_log2;
+    work.w = w;
+    work.h = h;
+    work.bw_log2 = bw_log2;
+    work.bpr = (w + bw - 1) / bw;
+    work.bprect = work.bpr * ((h + bh - 1) / bh);
 }
 
 int make_tiles_work(svo_ctx *ctx, uint32_t width, uint32_t height, uint32_t tile_w, uint32_t tile_h, uint32_t first_tile,
@@ -449,13 +447,7 @@ int make_tiles_work(svo_ctx *ctx, uint32_t width, uint32_t height, uint32_t tile
     uint32_t tiles_x = width / tile_w, tiles = tiles_x * (height / tile_h);
     work = svo::WorkDesc{};
     work.mode = 1;
-    work.w = tile_w; work.h = tile_h;
-    work.bw_log2 = ctx->block_w_log2;
-    {
-        const uint32_t bw = 1u << work.bw_log2, bh = 64u >> work.bw_log2;
-        work.bpr = (tile_w + bw - 1) / bw;
-        work.bprect = work.bpr * ((tile_h + bh - 1) / bh);
-    }
+    set_blocks(work, ctx->block_w_log2, tile_w, tile_h);
     work.n_rects = first_tile < tiles ? (tiles - first_tile + tile_stride - 1) / tile_stride : 0;
     work.tiles_x = tiles_x;
     work.first_tile = first_tile;
@@ -476,13 +468,8 @@ int make_rect_work(svo_ctx *ctx, uint32_t width, uint32_t height, uint32_t x0, u
     if ((uint64_t)w * h > (1u << 26)) return fail(ctx, SVO_ERR_ARG, "tile too large");
     work = svo::WorkDesc{};
     work.mode = 0;
-    work.x0 = x0; work.y0 = y0; work.w = w; work.h = h;
-    work.bw_log2 = ctx->block_w_log2;
-    {
-        const uint32_t bw = 1u << work.bw_log2, bh = 64u >> work.bw_log2;
-        work.bpr = (w + bw - 1) / bw;
-        work.bprect = work.bpr * ((h + bh - 1) / bh);
-    }
+    work.x0 = x0; work.y0 = y0;
+    set_blocks(work, ctx->block_w_log2, w, h);
     work.n_rects = 1;
     work.tiles_x = 1;
     work.n_items = work.bprect * 64u;
@@ -500,6 +487,26 @@ int ensure_stage(svo_ctx *ctx, size_t bytes) {
 }
 
 }  // namespace
+
+// The device buffers of a schedule slot for up to n_strips strips (at least 4096); the slot starts over.
+hipError_t svo_ctx::Sched::alloc(uint32_t n_strips) {
+    release();
+    const uint32_t want = n_strips < 4096u ? 4096u : n_strips;
+    const size_t cls_bytes = want + 32 + svo::kOrderHistWords * sizeof(uint32_t);  // class bytes, then the chunk histograms
+    const size_t order_words = 8 + 8 * (svo::order_list_cap(want) + 8);  // 8 lengths, 8 lists (and 8 spare entries each)
+    hipError_t e = hipMalloc((void **)&buf.cost, cls_bytes);
+    if (e == hipSuccess) e = hipMalloc((void **)&buf.cls_now, cls_bytes);
+    if (e == hipSuccess) e = hipMalloc((void **)&buf.order, order_words * sizeof(uint32_t));
+    if (e == hipSuccess) e = hipMalloc((void **)&buf.balance, svo::kBalanceWords * sizeof(uint32_t));
+    if (e == hipSuccess) cap = want;
+    return e;
+}
+
+void svo_ctx::Sched::release() {
+    for (void *p : {(void *)buf.cost, (void *)buf.cls_now, (void *)buf.order, (void *)buf.balance})
+        if (p) (void)hipFree(p);
+    *this = Sched{};
+}
 
 extern "C" {
 
@@ -550,6 +557,7 @@ int svo_ctx_create(int hip_device, svo_ctx **out) {
     svo_ctx *ctx = new (std::nothrow) svo_ctx();
     if (!ctx) return SVO_ERR_HIP;
     ctx->device = hip_device;
+    ctx->list_balance = getenv("SVO_NO_LIST_BALANCE") == nullptr;
     hipError_t e = hipSetDevice(hip_device);
     hipDeviceProp_t prop;
     if (e == hipSuccess) e = hipGetDeviceProperties(&prop, hip_device);
@@ -579,11 +587,7 @@ int svo_ctx_destroy(svo_ctx *ctx) {
     if (ctx->top_table) (void)hipFree(ctx->top_table);
     if (ctx->status) (void)hipFree(ctx->status);
     if (ctx->defer_buf) (void)hipFree(ctx->defer_buf);
-    for (auto &sc : ctx->sched) {
-        if (sc.cost) (void)hipFree(sc.cost);
-        if (sc.cls_now) (void)hipFree(sc.cls_now);
-        if (sc.order) (void)hipFree(sc.order);
-    }
+    for (auto &sc : ctx->sched) sc.release();
     for (void *p : {ctx->shade_hits, ctx->shade_aux, ctx->shade_rays, ctx->shade_shadow, ctx->shade_skip, ctx->scatter_buf})
         if (p) (void)hipFree(p);
     if (ctx->scan_sub) (void)hipFree(ctx->scan_sub);  // scan_unsub is the second half of the same allocation
@@ -643,14 +647,13 @@ int svo_set_option(svo_ctx *ctx, int option, int64_t value) {
             if (value < 64 || value > 2048 || (value & 63)) return fail(ctx, SVO_ERR_ARG, "strip_items must be a multiple of 64 in [64, 2048]");
             ctx->strip_items = (uint32_t)value;
             return SVO_OK;
-        case SVO_OPT_DYNAMIC_STRIPS:
-            ctx->dynamic_strips = value != 0;
+        case SVO_OPT_DYNAMIC_STRIPS:  // (strips are always claimed dynamically)
             return SVO_OK;
         case SVO_OPT_SCHEDULE:
             if (value < 0 || value > 1024) return fail(ctx, SVO_ERR_ARG, "schedule period out of range");
             ctx->schedule = value != 0;
             if (value) ctx->sched_period = (uint32_t)value;
-            ctx->sched[0].valid = ctx->sched[1].valid = false;
+            ctx->sched[0].state.valid = ctx->sched[1].state.valid = false;
             return SVO_OK;
         case SVO_OPT_TREE_DEPTH:
             if (value < 1 || value > 31) return fail(ctx, SVO_ERR_ARG, "tree depth must be 1..31");
@@ -679,8 +682,7 @@ int svo_set_option(svo_ctx *ctx, int option, int64_t value) {
             return SVO_OK;
         case SVO_OPT_PRIO_STEPS:
             if (value < 0 || value > 255) return fail(ctx, SVO_ERR_ARG, "prio_steps must be 0..255");
-            ctx->prio_steps = (uint32_t)value;
-            return SVO_OK;
+            return SVO_OK;  // (no longer used)
         default:
             return fail(ctx, SVO_ERR_ARG, "unknown option");
     }
@@ -950,11 +952,7 @@ int svo_pack_records(svo_ctx *ctx, const svo_hit *records, size_t n, uint32_t *w
 int svo_trace_rays(svo_ctx *ctx, const float *rays, size_t n_rays, svo_hit *hits_out) {
     if (!ctx || (!rays && n_rays)) return SVO_ERR_ARG;
     if (n_rays > (1u << 26)) return fail(ctx, SVO_ERR_ARG, "too many rays for one call");
-    svo::WorkDesc work{};
-    work.mode = 2;
-    work.n_items = (uint32_t)n_rays;
-    work.bpr = work.bprect = work.tiles_x = 1;
-    return trace_common(ctx, work, rays, hits_out, nullptr);
+    return trace_common(ctx, ray_work(n_rays), rays, hits_out, nullptr);
 }
 
 int svo_last_render_ms(svo_ctx *ctx, float *ms) {
@@ -1000,11 +998,11 @@ int svo_diag_gather(svo_ctx *ctx, uint32_t stride_bytes, uint32_t n_loads) {
 int svo_diag_strip_classes(svo_ctx *ctx, uint8_t *host_out, size_t n_strips) {
     if (!ctx || (!host_out && n_strips)) return SVO_ERR_ARG;
     const svo_ctx::Sched &sc = ctx->sched[0];
-    if (!sc.cls_now || !sc.order_filtered) return fail(ctx, SVO_ERR_STATE, "the last pixel frame was traced without a culling pass");
+    if (!sc.buf.cls_now || !sc.state.order_filtered) return fail(ctx, SVO_ERR_STATE, "the last pixel frame was traced without a culling pass");
     if (n_strips > sc.cap) return fail(ctx, SVO_ERR_ARG, "more strips than the last frame had");
     int rc = bind(ctx);
     if (rc || n_strips == 0) return rc;
-    HIP_TRY(ctx, hipMemcpyAsync(host_out, sc.cls_now, n_strips, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(host_out, sc.buf.cls_now, n_strips, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return SVO_OK;
 }

@@ -1,7 +1,6 @@
 // svo_ctx.h -- the device context behind the opaque `svo_ctx` of include/svo_hip.h; shared by svo_abi.cpp (trace / scan
 // dispatch) and svo_comm.cpp (RCCL frame gather).  Internal: not part of the boundary.
 #pragma once
-#include <cstdlib>
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -62,35 +61,29 @@ struct svo_ctx {
     int occupancy[16] = {};  // resident workgroups per CU of each STACK instantiation on this device (0: not asked yet)
     uint32_t refill_min = 32;  // (round 5: 16 until the schedule's locality work; profiles/r05_refill_sweep.log)
     bool scan_clears = false;
-    int fused_shadows = 2;  // 0: off, 1: on, 2: by frame size and tree depth (see trace_common)
+    int fused_shadows = 2;  // 0: off, 1: on, 2: automatic (see fuse_shadow_rays)
     void *scatter_buf = nullptr;
     size_t scatter_bytes = 0;
-    uint32_t prio_steps = 0;
     uint32_t block_w_log2 = 3;  // 64-pixel blocks of 8x8
     uint32_t tree_depth = 16;  // caller's bound on the octree depth (the reference's Settings.octree_depth)
-    // scheduling feedback (strip order from an earlier frame of the same work layout); slot 1: shadow rays
+    // scheduling feedback (strip order from an earlier frame of the same work layout); slot 1: shadow rays.  What is decided per
+    // frame is svo_sched.h's; svo_abi.cpp's trace_launch measures its facts and runs the launches.
     struct Sched {
-        uint8_t *cost = nullptr;
-        uint8_t *cls_now = nullptr;  // launches with a skip mask: this frame's classes (0xFF = strip without a ray)
-        uint32_t *order = nullptr;
-        uint32_t *balance = nullptr;  // kBalanceWords: the lists' shares and the stamps they follow (svo_kernels.hip: balance_step)
-        uint32_t balance_frames = 0;  // scheduled frames of this layout whose stamps have been fed back
+        svo::SchedState state;
+        svo::SchedBuffers buf{};  // for up to `cap` strips
         size_t cap = 0;
-        bool valid = false;
-        bool order_filtered = false;  // `order` was built for one frame without its empty / culled strips: not a general schedule
-        uint32_t age = 0;
-        svo::WorkDesc key{};
+        svo::WorkDesc key{};  // the work layout of the costs
         // what the schedule was measured on: while camera and tree stay the same it stays exact and is not rebuilt
         svo_uniforms built_uniforms{};
         uint64_t built_nodes_version = 0;
-        // camera motion (SVO_OPT_SCHEDULE_MOTION): the uniforms of the previous frame, and whether the lists in `order` were
-        // built with the floor for strips near long ones (then they are rebuilt once more, exactly, when the camera rests)
+        // camera motion (SVO_OPT_SCHEDULE_MOTION): the uniforms of the previous frame
         svo_uniforms prev_uniforms{};
         bool have_prev = false;
-        bool floored = false;
+        hipError_t alloc(uint32_t n_strips);  // frees what there is and starts the slot over (svo_abi.cpp)
+        void release();
     };
     Sched sched[2];
-    bool list_balance = getenv("SVO_NO_LIST_BALANCE") == nullptr;  // (A/B switch of the list-share feedback, svo_kernels.hip: balance_step)
+    bool list_balance = true;  // unless SVO_NO_LIST_BALANCE is set (A/B switch of the list-share feedback, svo_kernels.hip: balance_step)
     uint32_t motion_floor = 0x1204;  // SVO_OPT_SCHEDULE_MOTION: class floor | radius << 8 | min_count << 12; 0 = off
     bool schedule = true;
     uint32_t sched_period = 2;  // frames between schedule rebuilds (tools/perf_probe.py --motion: 2 keeps the gain under camera motion)
@@ -100,7 +93,6 @@ struct svo_ctx {
     size_t shade_hits_bytes = 0, shade_aux_bytes = 0, shade_rays_bytes = 0, shade_shadow_bytes = 0, shade_skip_bytes = 0;
     uint32_t *debug_buf = nullptr;  // caller-provided device buffer for the per-wave timeline (diagnostics)
     uint32_t strip_items = 64;
-    bool dynamic_strips = true;
     // launch timing: a ring of (start, stop) event pairs recorded around trace launches
     std::vector<hipEvent_t> ev;  // 2 per slot
     size_t ev_slots = 0, ev_count = 0;

@@ -5,6 +5,7 @@
 #include <stdint.h>
 
 #include "svo_hip.h"
+#include "svo_sched.h"
 
 namespace svo {
 
@@ -64,7 +65,7 @@ struct TraceArgs {
     uint32_t *debug;            // optional: 16 words per wave (start, queue-dry, end ticks of 10 ns, rounds, active-lane sum, ..., phase cycles)
     const uint8_t *skip;        // mode 2, optional: one byte per ray; non-zero = no ray here, its (all-zero) record is already written
     uint32_t *balance;          // STACK, optional: kBalanceWords words of the schedule's list-share feedback (see launch_post); the trace kernel
-                                // records when its first wave started ([9], min) and when a sample of every list's workgroups ended, 10 ns ticks
+                                // records when its first wave started (kBalanceStart) and when a sample of every list's workgroups ended, 10 ns ticks
     svo_hit *shadow_hits;       // STACK, optional (fused shadow rays): the lane that finishes a primary ray with a hit goes on with that
                                 // pixel's shadow ray (shader.wgsl:275-280) and writes its record here; pixels without one get zeros
 };
@@ -77,7 +78,6 @@ struct LaunchInfo {
     bool deep_stack;         // STACK: 19-level ancestor stack (trees deeper than 16 levels)
     uint32_t strip_items;    // STACK: pixel slots a wave claims at a time (multiple of 64)
     uint32_t *counters;      // STACK: kCounterWords claim-counter words, zero when a frame starts
-    uint32_t *work_counter;  // STACK: counters + 0 for dynamic strip claiming, or nullptr (static round-robin)
     uint32_t *defer;         // STACK: this frame's deferred list: count, then one slot per item handed to RESTART
     uint32_t *next_defer_count;  // STACK: count word of the other list (lists alternate between frames)
 };
@@ -96,20 +96,32 @@ constexpr uint32_t kMaxScheduledStrips = 1u << 20;  // (2^26 items / 64)
 #endif
 constexpr uint32_t kCostShift = SVO_COST_SHIFT, kCostClasses = 128u >> SVO_COST_SHIFT;
 constexpr uint32_t kOrderHistWords = 64 * kCostClasses;  // chunk histograms of the schedule builder, stored behind the class bytes
-// list-share feedback of a schedule: [0..8] cumulative shares of the 8 lists (16-bit fractions, [0] = 0, [8] = 65536), [9] the start
-// stamp of the last frame's first workgroup, [18] updates so far, [19] the last trace launch's workgroups; behind them (kBalanceHead) one end stamp per workgroup of the trace
-// launch (workgroup b started on list b % 8)
+// list-share feedback of a schedule (balance_step): [0..8] cumulative shares of the 8 lists (16-bit fractions, [0] = 0, [8] = 65536),
+// then the words below; behind them (kBalanceHead) one end stamp per workgroup of the trace launch (workgroup b started on list b % 8)
+constexpr uint32_t kBalanceStart = 9;         // start stamp of the last frame's first workgroup
+constexpr uint32_t kBalanceUpdates = 18;      // updates so far
+constexpr uint32_t kBalanceStamps = 19;       // the last trace launch's workgroups
+constexpr uint32_t kBalanceBestTime = 20;     // the shortest frame so far (ticks; 0: none yet)
+constexpr uint32_t kBalanceBestShares = 21;   // [21..29] the shares it was traced with
 constexpr uint32_t kBalanceHead = 32, kBalanceSlots = 4096, kBalanceWords = kBalanceHead + kBalanceSlots;
 // entries reserved per list of a schedule: a list holds its share of every cost class -- an eighth, or what the feedback gives it
 // (at most twice that)
-inline uint32_t order_list_cap(const WorkDesc &, uint32_t n_strips) { return (n_strips + 3u) / 4u + kCostClasses; }
-hipError_t launch_post(const TraceArgs &args, const LaunchInfo &li, uint8_t *cost, uint32_t *sched, uint32_t n_strips,
-                       uint32_t cap, bool build_schedule, hipStream_t stream, uint8_t *moved = nullptr, uint32_t motion_floor = 0,
-                       uint32_t balance_update = 0, bool reuse_cost = false);
+inline uint32_t order_list_cap(uint32_t n_strips) { return (n_strips + 3u) / 4u + kCostClasses; }
+// the device buffers of one schedule slot (svo_ctx::Sched)
+struct SchedBuffers {
+    uint8_t *cost;      // the strips' cost classes; kOrderHistWords words of chunk histograms behind them
+    uint8_t *cls_now;   // this frame's classes (filtered lists, motion floor); same layout
+    uint32_t *order;    // 8 list lengths, then 8 lists of order_list_cap entries
+    uint32_t *balance;  // kBalanceWords
+};
+hipError_t launch_post(const TraceArgs &args, const LaunchInfo &li, const PostPlan &plan, const SchedBuffers &buf, hipStream_t stream);
+// svo_sched.hip: launch_post's list build (args.order_cap entries per list, shares from args.balance)
+hipError_t launch_build_lists(const TraceArgs &args, uint32_t motion_floor, const SchedBuffers &buf, hipStream_t stream);
 
-// explicit rays with a skip mask: this frame's strip lists without the strips that hold no ray (classes from `prev`, or screen order)
-hipError_t launch_schedule_skipping(const uint8_t *skip, uint32_t n_items, const uint8_t *prev, uint8_t *cls, uint32_t *sched,
-                                    uint32_t n_strips, uint32_t cap, hipStream_t stream);
+// explicit rays with a skip mask (args.skip): this frame's strip lists without the strips that hold no ray (classes from `prev`, or
+// screen order)
+hipError_t launch_schedule_skipping(const TraceArgs &args, const uint8_t *prev, uint8_t *cls, uint32_t *sched, uint32_t n_strips,
+                                    uint32_t cap, hipStream_t stream);
 // pixel frames seen from outside the cube: this frame's strip lists without the strips whose rays all miss it (their all-zero
 // records are written here); args carries the work layout, the uniforms and the output buffers of the trace that follows
 hipError_t launch_schedule_culling(const TraceArgs &args, const uint8_t *prev, uint8_t *cls, uint32_t *sched, uint32_t n_strips,
