@@ -27,6 +27,9 @@
  *   svo_proc_generate_chunk       Procedural::generate_chunk (procedural.rs:101-199, procedual.wgsl:150-201), restated
  *                                 deterministically: canonical breadth-first tree instead of the racy insertion
  *   svo_world_generate            World::generate_world (world.rs:63-139)
+ *   svo_nodes_build / _dense      no reference counterpart (the reference builds trees on the host, cpu_octree.rs): the
+ *                                 tree of a device voxel list or dense colour grid, built on the GPU into the node
+ *                                 buffer, canonical breadth-first
  *   svo_comm_* / svo_gather_frame no reference counterpart (the reference drives one device, main.rs:40-88): the
  *                                 frame-end exchange of the tile-sharded multi-GPU frame, RCCL behind the boundary
  *                                 (SURVEY.md 8b "Threading", 8e): communicator set-up for one process per GPU
@@ -183,6 +186,8 @@ int svo_nodes_device_ptr(svo_ctx *ctx, uint32_t **out, size_t *capacity_words);
 int svo_buffer_alloc(svo_ctx *ctx, size_t bytes, void **device_out);
 int svo_buffer_free(svo_ctx *ctx, void *device_ptr);
 int svo_buffer_read(svo_ctx *ctx, const void *device_ptr, void *host_out, size_t bytes);
+/* The partner of svo_buffer_read: host memory to a device buffer, behind everything enqueued on the ctx stream; blocking. */
+int svo_buffer_write(svo_ctx *ctx, void *device_dst, const void *host_src, size_t bytes);
 
 int svo_set_uniforms(svo_ctx *ctx, const svo_uniforms *u);
 
@@ -313,6 +318,38 @@ int svo_proc_classify(svo_ctx *ctx, const svo_proc_params *params, uint8_t *cell
  * svo_world_generate, summed over its chunks: [6] GPU (wall), [7] read-back and build, [8] mips, [9] chunk file writes. */
 #define SVO_PROC_TIMES 10
 int svo_proc_timing(svo_ctx *ctx, float ms_out[SVO_PROC_TIMES]);
+
+/* ---- trees built on the GPU ----
+ * Voxel i has cell (x, y, z), each in [0, 2^depth), and colour 0x00RRGGBB (Rgb::cpu_value; the low 24 bits count).  The
+ * tree is the union of the voxels' root-to-leaf paths, every voxel a leaf at `depth`: what sequential put(p, leaf, depth)
+ * builds with p = cell / 2^depth * 2 - 1, the last of several voxels in one cell winning.  Child index at level L:
+ * x bit << 2 | y bit << 1 | z bit, bit depth - L.  Words in the GPU layout: interior = child group << 4, leaf =
+ * (SVO_VOXEL_OFFSET + colour) << 4, empty = SVO_VOXEL_OFFSET << 4 (a colour-0 voxel is an empty leaf on an existing
+ * path), hit counters 0; canonical breadth-first (root group at 0, each level's groups in the order of their parents):
+ * svo_nodes_relayout(words, n, 32, ...) of the host-built tree.  The same words on every run and for any order of
+ * distinct voxels.  Written from word 0 of the node buffer; *n_words_out = 8 * (1 + interior nodes below the root), 8
+ * empty words for n == 0.
+ * Errors leave the node buffer untouched: SVO_ERR_ARG for a bad depth, n >= 2^31, NULL xyz with n > 0, or a coordinate
+ * outside [0, 2^depth) (checked on the device); SVO_ERR_CAP when the word count exceeds max_words, the capacity or 2^27;
+ * SVO_ERR_STATE without a node buffer.  Runs on the ctx stream and blocks only to read the level counts back; the emit
+ * is enqueued (a following svo_render on the stream sees the tree), ordered and recorded like svo_nodes_write, so every
+ * context sharing the buffer rebuilds its top table.  Inputs must stay valid until svo_sync.  SVO_OPT_TREE_DEPTH is the
+ * caller's to raise when depth exceeds it. */
+typedef struct svo_build_params {
+    uint32_t depth;          /* 1..21 (dense: 1..10) */
+    uint32_t default_colour; /* used when colours == NULL */
+    uint64_t max_words;      /* 0 = the node buffer's capacity; never above SVO_VOXEL_OFFSET */
+} svo_build_params;
+/* xyz: n * 3 u32 (x, y, z interleaved), colours: n u32 or NULL -- DEVICE pointers on the ctx's device */
+int svo_nodes_build(svo_ctx *ctx, const uint32_t *xyz, const uint32_t *colours, size_t n, const svo_build_params *p,
+                    uint64_t *n_words_out);
+/* grid: side^3 u32 (DEVICE), side = 2^depth, cell (x, y, z) at grid[(x * side + y) * side + z]; a cell is a voxel iff
+ * non-zero, with the low 24 bits as its colour.  The same words as svo_nodes_build of the non-zero cells. */
+int svo_nodes_build_dense(svo_ctx *ctx, const uint32_t *grid, const svo_build_params *p, uint64_t *n_words_out);
+/* Times (ms) of the last build: [0] keys, [1] sort (0 for a dense grid), [2] levels, [3] count read-back, [4] emit (device
+ * events; waits for the emit), [5] host wall time of the call. */
+#define SVO_BUILD_TIMES 6
+int svo_build_timing(svo_ctx *ctx, float ms_out[SVO_BUILD_TIMES]);
 
 #ifdef __cplusplus
 }

@@ -227,6 +227,21 @@ class Render {  // render.rs:3-285
         : Render(gpu, w, h, octree.raw_data(), octree.len(), capacity) {}
     // queue.write_buffer(&node_buffer, 0, nodes) (app.rs:113-118)
     void write_nodes(const uint32_t *words, size_t n) { gpu_.check(svo_nodes_write(gpu_.ctx(), 0, words, n)); }
+    // the tree of n voxels built on the GPU into the node buffer (svo_nodes_build): xyz (n * 3) and colours
+    // (n, or null for `colour`) are DEVICE pointers; returns the word count.  Raises SVO_OPT_TREE_DEPTH to depth, never
+    // lowers it.
+    uint64_t build_nodes(const uint32_t *xyz_dev, const uint32_t *colours_dev, size_t n, uint32_t depth, uint32_t colour = 0xFFFFFF,
+                         uint64_t max_words = 0) {
+        if (depth > declared_depth_) {
+            gpu_.set_option(SVO_OPT_TREE_DEPTH, depth);
+            declared_depth_ = depth;
+        }
+        const svo_build_params p{depth, colour, max_words};
+        uint64_t n_words = 0;
+        gpu_.check(svo_nodes_build(gpu_.ctx(), xyz_dev, colours_dev, n, &p, &n_words));
+        gpu_.poll_wait();  // the inputs may go away
+        return n_words;
+    }
     // incremental form of the same upload: only the words that changed (svo_nodes_scatter; pair it with
     // gpu.set_option(SVO_OPT_SCAN_CLEARS_COUNTERS, 1), which takes over the counter reset of the full upload)
     void scatter_nodes(const std::vector<uint32_t> &indices, const std::vector<uint32_t> &words) {
@@ -273,6 +288,7 @@ class Render {  // render.rs:3-285
 
   private:
     const Gpu &gpu_;
+    uint32_t declared_depth_ = 16;  // SVO_OPT_TREE_DEPTH as this Render last set it (the library's default: 16)
 };
 
 // One process, one thread, N GPUs -- the reference's threading model (main.rs:40-88) extended to a tile-sharded frame

@@ -47,6 +47,15 @@ class ProcParams(C.Structure):
     ]
 
 
+class BuildParams(C.Structure):
+    """svo_build_params: a tree built on the GPU (include/svo_hip.h)."""
+    _fields_ = [
+        ("depth", C.c_uint32),
+        ("default_colour", C.c_uint32),
+        ("max_words", C.c_uint64),
+    ]
+
+
 DEVICE_SYMBOLS = [
     "svo_device_count", "svo_buffer_alloc", "svo_buffer_free", "svo_buffer_read", "svo_ctx_create", "svo_ctx_destroy", "svo_ctx_set_stream", "svo_set_option", "svo_last_error", "svo_sync",
     "svo_nodes_alloc", "svo_nodes_bind_device", "svo_nodes_write", "svo_nodes_scatter", "svo_nodes_read", "svo_nodes_device_ptr", "svo_nodes_share", "svo_nodes_invalidate",
@@ -54,6 +63,7 @@ DEVICE_SYMBOLS = [
     "svo_set_uniforms", "svo_render", "svo_render_host", "svo_render_tiles", "svo_render_secondary", "svo_render_tiles_secondary", "svo_assemble_tiles", "svo_assemble_tiles_packed", "svo_assemble_tiles_rgba", "svo_pack_records", "svo_trace_rays",
     "svo_last_render_ms", "svo_timing_collect", "svo_diag_gather", "svo_diag_strip_classes", "svo_scan_dispatch", "svo_scan_read",
     "svo_proc_generate_chunk", "svo_world_generate", "svo_proc_sdf", "svo_proc_classify", "svo_proc_timing",
+    "svo_nodes_build", "svo_nodes_build_dense", "svo_buffer_write", "svo_build_timing",
 ]
 HOST_SYMBOLS = [
     "svo_cpu_octree_new", "svo_cpu_octree_free", "svo_cpu_octree_len", "svo_cpu_octree_load_file",
@@ -140,6 +150,10 @@ def lib():
     sig("svo_proc_sdf", C.c_int, vp, vp, sz, vp)
     sig("svo_proc_classify", C.c_int, vp, C.POINTER(ProcParams), vp)
     sig("svo_proc_timing", C.c_int, vp, fp)
+    sig("svo_nodes_build", C.c_int, vp, vp, vp, sz, C.POINTER(BuildParams), C.POINTER(u64))
+    sig("svo_nodes_build_dense", C.c_int, vp, vp, C.POINTER(BuildParams), C.POINTER(u64))
+    sig("svo_buffer_write", C.c_int, vp, vp, vp, sz)
+    sig("svo_build_timing", C.c_int, vp, fp)
     # host data model (include/svo_host.h)
     sig("svo_cpu_octree_new", vp, C.c_uint8)
     sig("svo_cpu_octree_free", None, vp)

@@ -488,6 +488,9 @@ int ensure_stage(svo_ctx *ctx, size_t bytes) {
 
 }  // namespace
 
+int svo_store_order_after_write(svo_ctx *ctx) { return order_after_last_write(ctx); }
+int svo_store_note_write(svo_ctx *ctx) { return note_write(ctx, true); }
+
 // The device buffers of a schedule slot for up to n_strips strips (at least 4096); the slot starts over.
 hipError_t svo_ctx::Sched::alloc(uint32_t n_strips) {
     release();
@@ -539,6 +542,15 @@ int svo_buffer_free(svo_ctx *ctx, void *device_ptr) {
     return SVO_OK;
 }
 
+int svo_buffer_write(svo_ctx *ctx, void *device_dst, const void *host_src, size_t bytes) {
+    if (!ctx || ((!device_dst || !host_src) && bytes)) return SVO_ERR_ARG;
+    int rc = bind(ctx);
+    if (rc || bytes == 0) return rc;
+    HIP_TRY(ctx, hipMemcpyAsync(device_dst, host_src, bytes, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return SVO_OK;
+}
+
 int svo_buffer_read(svo_ctx *ctx, const void *device_ptr, void *host_out, size_t bytes) {
     if (!ctx || ((!device_ptr || !host_out) && bytes)) return SVO_ERR_ARG;
     int rc = bind(ctx);
@@ -583,6 +595,7 @@ int svo_ctx_destroy(svo_ctx *ctx) {
     if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
     svo_comm_release(ctx);
     svo_proc_release(ctx);
+    svo_build_release(ctx);
     release_store(ctx);
     if (ctx->top_table) (void)hipFree(ctx->top_table);
     if (ctx->status) (void)hipFree(ctx->status);

@@ -1,0 +1,625 @@
+// svo_build.hip -- render-ready trees built on the GPU from a voxel list or a dense colour grid.  The
+// same idea as the procedural generator (svo_proc.hip): the tree is the canonical breadth-first form of the union of
+// the voxels' root-to-leaf paths, built with scans and without atomics, so the words do not depend on the run or on the
+// order of distinct input voxels.
+//
+//   keys     one lane per voxel: Morton key (3 * depth bits, level 1 in the top bits) and payload = input index; a
+//            coordinate outside [0, 2^depth) sets the error word
+//   sort     stable LSD radix sort, 8-bit digits: per-tile digit counts, one scan of the counts, a stable scatter that
+//            ranks a tile's items with wave64 ballots.  Stability keeps equal keys in input order
+//   levels   per level a flag on the LAST element of every run of equal keys, a scan of the flags (tile counts, one
+//            block over the tile counts, tile re-scan) and a compaction to the next level up.  The first pass (leaf
+//            level) keeps the last voxel of a run of equal cells: repeated put(), last one wins.  The counts of all
+//            levels are read back in one copy and checked against the cap before anything is written
+//   emit     the level passes again, top level last, now also writing every node's slot,
+//            base_L + 8 * parent_rank + (key & 7), into the node buffer filled with the empty word
+//
+// An element's parent rank is the exclusive scan of the parent-level flags at that element: every run before its own has
+// its flag (its last element) in front of it.  The dense grid skips keys and sort: lanes walk the cells in Morton order
+// and the flag is "cell non-zero", which yields the leaf level already sorted and unique.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <chrono>
+#include <cstring>
+#include <string>
+
+#include "svo_ctx.h"
+
+namespace {
+
+constexpr uint32_t kThreads = 256;
+constexpr uint32_t kPer = 16;                     // items per thread of a tile
+constexpr uint32_t kTile = kThreads * kPer;       // items per tile (sort, scans and compactions alike)
+constexpr uint32_t kTopThreads = 1024;
+constexpr uint32_t kEmptyWord = SVO_VOXEL_OFFSET << 4;
+constexpr uint64_t kMaxWords = SVO_VOXEL_OFFSET;  // 2^27: pointers and colours must stay apart
+constexpr int kErrSlot = 24;                      // counts[0..21]: nodes per level; counts[24]: range error
+constexpr int kCountSlots = 32;
+
+enum Mode { kDedupe = 0, kParent = 1, kDense = 2 };
+
+template <int N>
+__device__ inline uint32_t block_exclusive_scan(uint32_t v, uint32_t *total) {
+    __shared__ uint32_t s[N];
+    const int t = threadIdx.x;
+    s[t] = v;
+    __syncthreads();
+    for (int off = 1; off < N; off <<= 1) {
+        const uint32_t a = t >= off ? s[t - off] : 0u;
+        __syncthreads();
+        s[t] += a;
+        __syncthreads();
+    }
+    if (total) *total = s[N - 1];
+    const uint32_t r = s[t] - v;
+    __syncthreads();  // (a following call reuses s)
+    return r;
+}
+
+__device__ inline uint64_t morton3(uint32_t x, uint32_t y, uint32_t z, uint32_t depth) {
+    uint64_t k = 0;
+    for (uint32_t b = 0; b < depth; b++)
+        k |= uint64_t((x >> b) & 1u) << (3 * b + 2) | uint64_t((y >> b) & 1u) << (3 * b + 1) | uint64_t((z >> b) & 1u) << (3 * b);
+    return k;
+}
+
+__device__ inline uint32_t input_count(const uint32_t *m_dev, uint32_t m_max) { return m_dev ? min(*m_dev, m_max) : m_max; }
+
+// ---- keys ----
+__global__ __launch_bounds__(kThreads) void build_keys_kernel(const uint32_t *xyz, uint32_t n, uint32_t depth, uint64_t *keys,
+                                                              uint32_t *vals, uint32_t *err) {
+    const uint32_t i = blockIdx.x * kThreads + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t x = xyz[3 * size_t(i)], y = xyz[3 * size_t(i) + 1], z = xyz[3 * size_t(i) + 2];
+    if ((x | y | z) >> depth) *err = 1u;  // (every writer stores the same value)
+    keys[i] = morton3(x, y, z, depth);
+    vals[i] = i;
+}
+
+// ---- sort ----
+// Lanes of the wave whose digit equals this lane's, among `valid` (8 ballots, one per digit bit).
+__device__ inline uint64_t match_digit(uint32_t d, uint64_t valid) {
+    uint64_t peers = valid;
+    for (int b = 0; b < 8; b++) {
+        const uint64_t bal = __ballot((d >> b) & 1u);
+        peers &= ((d >> b) & 1u) ? bal : ~bal;
+    }
+    return peers;
+}
+
+__device__ inline uint64_t lanes_below() {
+    const uint32_t lane = __lane_id();
+    return lane ? (~0ull >> (64 - lane)) : 0ull;
+}
+
+// Tile t's count of every digit at hist[digit * n_tiles + t], so that one exclusive scan of hist gives every (digit, tile)
+// its first output position.  Counted per wave with ballots into wave-private LDS rows: no atomics.
+__global__ __launch_bounds__(kThreads) void build_hist_kernel(const uint64_t *keys, uint32_t n, uint32_t shift, uint32_t *hist,
+                                                              uint32_t n_tiles) {
+    __shared__ uint32_t cnt[kThreads / 64][256];
+    const uint32_t w = threadIdx.x / 64;
+    for (uint32_t r = 0; r < kThreads / 64; r++) cnt[r][threadIdx.x] = 0;
+    __syncthreads();
+    const uint32_t base = blockIdx.x * kTile;
+    for (uint32_t r = 0; r < kPer; r++) {
+        const uint32_t i = base + r * kThreads + threadIdx.x;
+        const bool v = i < n;
+        const uint32_t d = v ? uint32_t(keys[i] >> shift) & 0xFFu : 0u;
+        const uint64_t peers = match_digit(d, __ballot(v));
+        if (v && (peers & lanes_below()) == 0) cnt[w][d] += __popcll(peers);  // the group's lowest lane
+    }
+    __syncthreads();
+    uint32_t s = 0;
+    for (uint32_t r = 0; r < kThreads / 64; r++) s += cnt[r][threadIdx.x];
+    hist[threadIdx.x * n_tiles + blockIdx.x] = s;
+}
+
+// Stable scatter of one tile: item i of round r is tile item r * 256 + threadIdx.x, so rounds, waves and lanes walk the
+// tile in input order.  An item goes to run[d] (where digit d's next item of this tile goes) + the counts of d in the
+// waves before its own in this round + its rank among its wave's lanes with digit d.
+__global__ __launch_bounds__(kThreads) void build_scatter_kernel(const uint64_t *keys_in, const uint32_t *vals_in, uint32_t n,
+                                                                 uint32_t shift, const uint32_t *hist, uint32_t n_tiles,
+                                                                 uint64_t *keys_out, uint32_t *vals_out) {
+    __shared__ uint32_t run[256];
+    __shared__ uint32_t cnt[kThreads / 64][256];
+    const uint32_t w = threadIdx.x / 64;
+    run[threadIdx.x] = hist[threadIdx.x * n_tiles + blockIdx.x];
+    for (uint32_t r = 0; r < kThreads / 64; r++) cnt[r][threadIdx.x] = 0;
+    const uint32_t base = blockIdx.x * kTile;
+    uint64_t k[kPer];
+    uint32_t v[kPer];
+    for (uint32_t r = 0; r < kPer; r++) {
+        const uint32_t i = base + r * kThreads + threadIdx.x;
+        k[r] = i < n ? keys_in[i] : 0ull;
+        v[r] = i < n ? vals_in[i] : 0u;
+    }
+    __syncthreads();
+    for (uint32_t r = 0; r < kPer; r++) {
+        const bool valid = base + r * kThreads + threadIdx.x < n;
+        const uint32_t d = uint32_t(k[r] >> shift) & 0xFFu;
+        const uint64_t peers = match_digit(d, __ballot(valid));
+        const uint32_t below = __popcll(peers & lanes_below());
+        if (valid && below == 0) cnt[w][d] = __popcll(peers);
+        __syncthreads();
+        if (valid) {
+            uint32_t pos = run[d] + below;
+            for (uint32_t q = 0; q < w; q++) pos += cnt[q][d];
+            if (pos < n) {  // (always: the counts and the scatter walk the same tile)
+                keys_out[pos] = k[r];
+                vals_out[pos] = v[r];
+            }
+        }
+        __syncthreads();
+        uint32_t s = 0;
+        for (uint32_t q = 0; q < kThreads / 64; q++) {
+            s += cnt[q][threadIdx.x];
+            cnt[q][threadIdx.x] = 0;
+        }
+        run[threadIdx.x] += s;
+        __syncthreads();
+    }
+}
+
+// ---- generic exclusive scan of a u32 array (the digit counts), tiles of kTile ----
+__global__ __launch_bounds__(kThreads) void build_sum_kernel(const uint32_t *a, uint32_t n, uint32_t *tile_sum) {
+    const uint32_t i0 = blockIdx.x * kTile + threadIdx.x * kPer;
+    uint32_t s = 0;
+    for (uint32_t j = 0; j < kPer; j++)
+        if (i0 + j < n) s += a[i0 + j];
+    uint32_t total;
+    block_exclusive_scan<kThreads>(s, &total);
+    if (threadIdx.x == 0) tile_sum[blockIdx.x] = total;
+}
+
+__global__ __launch_bounds__(kThreads) void build_add_kernel(uint32_t *a, uint32_t n, const uint32_t *tile_off) {
+    const uint32_t i0 = blockIdx.x * kTile + threadIdx.x * kPer;
+    uint32_t v[kPer], s = 0;
+    for (uint32_t j = 0; j < kPer; j++) {
+        v[j] = i0 + j < n ? a[i0 + j] : 0u;
+        s += v[j];
+    }
+    uint32_t r = block_exclusive_scan<kThreads>(s, nullptr) + tile_off[blockIdx.x];
+    for (uint32_t j = 0; j < kPer; j++) {
+        if (i0 + j < n) a[i0 + j] = r;
+        r += v[j];
+    }
+}
+
+// One block scans the tile sums in place (exclusive) and writes their total.  The tile count is n_tiles, or, with m_dev,
+// that of the *m_dev (at most m_max) items a compaction reads.
+__global__ __launch_bounds__(kTopThreads) void build_top_kernel(uint32_t *tile_sum, uint32_t n_tiles, const uint32_t *m_dev,
+                                                                uint32_t m_max, uint32_t *total_out) {
+    if (m_dev) n_tiles = (input_count(m_dev, m_max) + kTile - 1) / kTile;
+    const uint32_t per = (n_tiles + kTopThreads - 1) / kTopThreads;
+    const uint32_t lo = threadIdx.x * per, hi = min(lo + per, n_tiles);
+    uint32_t sum = 0;
+    for (uint32_t i = lo; i < hi; i++) sum += tile_sum[i];
+    uint32_t total;
+    uint32_t run = block_exclusive_scan<kTopThreads>(sum, &total);
+    for (uint32_t i = lo; i < hi; i++) {
+        const uint32_t v = tile_sum[i];
+        tile_sum[i] = run;
+        run += v;
+    }
+    if (threadIdx.x == 0) *total_out = total;
+}
+
+// ---- levels: flags, scans, compaction, emit ----
+struct LevelIn {
+    const uint64_t *keys;     // kDedupe: sorted keys; kParent: this level's unique keys
+    const uint32_t *vals;     // kDedupe: input index of each key; kParent: leaf colours (last level only) or null
+    const uint32_t *colours;  // kDedupe: the caller's colours or null; kDense: the grid
+    uint32_t colour;          // kDedupe without colours
+    const uint32_t *m_dev;    // number of input items on the device (null: m_max)
+    uint32_t m_max;           // host bound of that number (the input buffer's size)
+    uint32_t depth;           // kDense: grid depth
+};
+
+struct LevelOut {
+    uint64_t *keys;     // compacted keys, one per run
+    uint32_t *colours;  // kDedupe / kDense: the leaf colour of each
+    uint32_t cap;       // room in keys / colours
+    // emit (kParent only; words null: counting pass)
+    uint32_t *words;
+    uint32_t base;       // first word of this level
+    uint32_t base_next;  // first word of the level below (interior nodes point there)
+    uint32_t last;       // this is the leaf level
+    uint32_t n_words;
+};
+
+// Loads thread t's 16 consecutive items and their flags (bit j: item i0 + j ends a run / is kept).
+template <int M>
+__device__ inline uint32_t load_flags(const LevelIn &in, uint32_t m, uint32_t i0, uint64_t *k) {
+    uint32_t f = 0;
+    if (M == kDense) {
+        const uint32_t side = 1u << in.depth;
+        for (uint32_t j = 0; j < kPer; j++) {
+            const uint32_t i = i0 + j;
+            k[j] = 0;
+            if (i >= m) continue;
+            uint32_t x = 0, y = 0, z = 0;
+            for (uint32_t b = 0; b < in.depth; b++) {
+                z |= ((i >> (3 * b)) & 1u) << b;
+                y |= ((i >> (3 * b + 1)) & 1u) << b;
+                x |= ((i >> (3 * b + 2)) & 1u) << b;
+            }
+            const uint32_t c = in.colours[(size_t(x) * side + y) * side + z];
+            k[j] = i | uint64_t(c) << 32;  // (the cell's value rides in the high half)
+            if (c) f |= 1u << j;
+        }
+        return f;
+    }
+    const uint32_t shift = M == kParent ? 3u : 0u;
+    for (uint32_t j = 0; j < kPer; j++) k[j] = i0 + j < m ? in.keys[i0 + j] : 0ull;
+    const uint64_t after = i0 + kPer < m ? in.keys[i0 + kPer] : 0ull;
+    for (uint32_t j = 0; j < kPer; j++) {
+        const uint32_t i = i0 + j;
+        if (i >= m) break;
+        const bool end = i + 1 == m || (k[j] >> shift) != ((j + 1 < kPer ? k[j + 1] : after) >> shift);
+        f |= uint32_t(end) << j;
+    }
+    return f;
+}
+
+template <int M>
+__global__ __launch_bounds__(kThreads) void build_count_kernel(LevelIn in, uint32_t *tile_sum) {
+    const uint32_t m = input_count(in.m_dev, in.m_max);
+    if (blockIdx.x * kTile >= m) return;  // (the grid covers the bound; the top kernel reads only the live tiles)
+    uint64_t k[kPer];
+    const uint32_t f = load_flags<M>(in, m, blockIdx.x * kTile + threadIdx.x * kPer, k);
+    uint32_t total;
+    block_exclusive_scan<kThreads>(__popc(f), &total);
+    if (threadIdx.x == 0) tile_sum[blockIdx.x] = total;
+}
+
+template <int M>
+__global__ __launch_bounds__(kThreads) void build_compact_kernel(LevelIn in, const uint32_t *tile_off, LevelOut out) {
+    const uint32_t m = input_count(in.m_dev, in.m_max);
+    if (blockIdx.x * kTile >= m) return;
+    const uint32_t i0 = blockIdx.x * kTile + threadIdx.x * kPer;
+    uint64_t k[kPer];
+    const uint32_t f = load_flags<M>(in, m, i0, k);
+    uint32_t r = block_exclusive_scan<kThreads>(__popc(f), nullptr) + tile_off[blockIdx.x];
+    for (uint32_t j = 0; j < kPer; j++) {
+        const uint32_t i = i0 + j;
+        if (i >= m) break;
+        if (M == kParent && out.words) {  // node i of this level: its parent's rank is r
+            const uint32_t dst = out.base + 8u * r + uint32_t(k[j] & 7u);
+            const uint32_t word = out.last ? (SVO_VOXEL_OFFSET + (in.vals[i] & 0xFFFFFFu)) << 4 : (out.base_next + 8u * i) << 4;
+            if (dst < out.n_words) out.words[dst] = word;  // (always: the counts and the ranks come from the same flags)
+        }
+        if ((f >> j) & 1u) {
+            if (r < out.cap) {
+                out.keys[r] = M == kParent ? k[j] >> 3 : (M == kDense ? k[j] & 0xFFFFFFFFu : k[j]);
+                if (M == kDedupe) out.colours[r] = (in.colours ? in.colours[in.vals[i]] : in.colour) & 0xFFFFFFu;
+                if (M == kDense) out.colours[r] = uint32_t(k[j] >> 32) & 0xFFFFFFu;
+            }
+            r++;
+        }
+    }
+}
+
+int fail(svo_ctx *ctx, int code, const std::string &what) { return svo_fail(ctx, code, what.c_str()); }
+
+#define HIP_TRY(ctx, expr)                                          \
+    do {                                                            \
+        hipError_t e_ = (expr);                                     \
+        if (e_ != hipSuccess) return svo_fail_hip(ctx, e_, #expr); \
+    } while (0)
+
+uint32_t tiles_for(uint64_t n) { return (uint32_t)((n + kTile - 1) / kTile); }
+
+double now_ms() {
+    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
+}
+
+}  // namespace
+
+// Per-context workspace of the builder (svo_ctx::build): O(items), grown when a larger input comes, freed by
+// svo_build_release.  keys[0] / keys[1] and vals[0] / vals[1] are the sort's ping-pong buffers, later the level passes'
+// (keys[0], keys[1] by turns); keys[2] / leaf_colours hold the leaf level from the level pass to the emit.
+struct svo_build_state {
+    uint64_t *keys[3] = {};
+    uint32_t *vals[2] = {};
+    uint32_t *leaf_colours = nullptr;
+    size_t items = 0;           // room in every one of them
+    uint32_t *hist = nullptr;   // the sort's digit counts, 256 per tile
+    size_t hist_items = 0;
+    uint32_t *tiles = nullptr;  // tile sums / offsets of a scan
+    size_t tile_items = 0;
+    uint32_t *counts = nullptr;       // kCountSlots words (device): unique nodes per level, error word
+    uint32_t *counts_host = nullptr;  // (pinned)
+    hipEvent_t ev[7] = {};          // start, keys, sort, levels, read-back, emit start, emit end
+    bool sorted = false, timed = true;  // the last build sorted / its device times are in ms
+    float ms[SVO_BUILD_TIMES] = {};
+
+    void release() {
+        for (void *p : {(void *)keys[0], (void *)keys[1], (void *)keys[2], (void *)vals[0], (void *)vals[1], (void *)leaf_colours,
+                        (void *)hist, (void *)tiles, (void *)counts})
+            if (p) (void)hipFree(p);
+        if (counts_host) (void)hipHostFree(counts_host);
+        for (hipEvent_t e : ev)
+            if (e) (void)hipEventDestroy(e);
+    }
+};
+
+void svo_build_release(svo_ctx *ctx) {
+    if (!ctx->build) return;
+    ctx->build->release();
+    delete ctx->build;
+    ctx->build = nullptr;
+}
+
+namespace {
+
+template <typename T>
+int grow(svo_ctx *ctx, T **p, size_t *have, size_t want) {
+    if (*have >= want) return SVO_OK;
+    if (*p) (void)hipFree(*p);
+    *p = nullptr;
+    *have = 0;
+    HIP_TRY(ctx, hipMalloc((void **)p, want * sizeof(T)));
+    *have = want;
+    return SVO_OK;
+}
+
+// workspace for `items` keys (and the tile sums of scans over at most `scan_items` items)
+int ensure_state(svo_ctx *ctx, size_t items, size_t scan_items, size_t hist_items) {
+    if (!ctx->build) {
+        ctx->build = new svo_build_state();
+        for (hipEvent_t &e : ctx->build->ev) HIP_TRY(ctx, hipEventCreate(&e));
+        HIP_TRY(ctx, hipHostMalloc((void **)&ctx->build->counts_host, kCountSlots * sizeof(uint32_t), hipHostMallocDefault));
+        HIP_TRY(ctx, hipMalloc((void **)&ctx->build->counts, kCountSlots * sizeof(uint32_t)));
+    }
+    svo_build_state *s = ctx->build;
+    if (s->items < items) {
+        for (void *p : {(void *)s->keys[0], (void *)s->keys[1], (void *)s->keys[2], (void *)s->vals[0], (void *)s->vals[1],
+                        (void *)s->leaf_colours})
+            if (p) (void)hipFree(p);
+        s->keys[0] = s->keys[1] = s->keys[2] = nullptr;
+        s->vals[0] = s->vals[1] = s->leaf_colours = nullptr;
+        s->items = 0;
+        for (int k = 0; k < 3; k++) HIP_TRY(ctx, hipMalloc((void **)&s->keys[k], items * sizeof(uint64_t)));
+        for (int k = 0; k < 2; k++) HIP_TRY(ctx, hipMalloc((void **)&s->vals[k], items * sizeof(uint32_t)));
+        HIP_TRY(ctx, hipMalloc((void **)&s->leaf_colours, items * sizeof(uint32_t)));
+        s->items = items;
+    }
+    int rc = grow(ctx, &s->hist, &s->hist_items, hist_items);
+    if (rc) return rc;
+    return grow(ctx, &s->tiles, &s->tile_items, (size_t)tiles_for(scan_items) + 1);
+}
+
+// Exclusive scan of hist[0, n) in place.
+int scan_u32(svo_ctx *ctx, uint32_t *a, uint32_t n) {
+    svo_build_state *s = ctx->build;
+    const uint32_t nt = tiles_for(n);
+    build_sum_kernel<<<nt, kThreads, 0, ctx->stream>>>(a, n, s->tiles);
+    build_top_kernel<<<1, kTopThreads, 0, ctx->stream>>>(s->tiles, nt, nullptr, 0, s->counts + kErrSlot + 1);
+    build_add_kernel<<<nt, kThreads, 0, ctx->stream>>>(a, n, s->tiles);
+    HIP_TRY(ctx, hipGetLastError());
+    return SVO_OK;
+}
+
+// One level pass: flags, tile counts, scan (the total goes to *total), compaction (and, with out.words, emit).
+// `bound` is the host's bound of the input count: the grid covers it.
+template <int M>
+int level_pass(svo_ctx *ctx, const LevelIn &in, const LevelOut &out, uint64_t bound, uint32_t *total) {
+    svo_build_state *s = ctx->build;
+    const uint32_t nt = std::max(tiles_for(bound), 1u);
+    build_count_kernel<M><<<nt, kThreads, 0, ctx->stream>>>(in, s->tiles);
+    build_top_kernel<<<1, kTopThreads, 0, ctx->stream>>>(s->tiles, nt, in.m_dev, in.m_max, total);
+    build_compact_kernel<M><<<nt, kThreads, 0, ctx->stream>>>(in, s->tiles, out);
+    HIP_TRY(ctx, hipGetLastError());
+    return SVO_OK;
+}
+
+// The parent passes L = depth .. stop over the leaf level in keys[2] / leaf_colours: level L's unique keys in, level
+// L-1's out (keys[0] and keys[1] by turns), m_{L-1} into counts[L-1].  With words: the emit, level L's slots too.
+int parent_passes(svo_ctx *ctx, uint32_t depth, uint32_t stop, const uint64_t *bound, uint32_t *words, const uint64_t *base,
+                  uint64_t n_words) {
+    svo_build_state *s = ctx->build;
+    const uint64_t *src = s->keys[2];
+    for (uint32_t l = depth, turn = 0; l >= stop; l--, turn ^= 1) {
+        LevelIn in{};
+        in.keys = src;
+        in.vals = l == depth ? s->leaf_colours : nullptr;
+        in.m_dev = s->counts + l;
+        in.m_max = (uint32_t)s->items;
+        LevelOut out{};
+        out.keys = s->keys[turn];
+        out.cap = (uint32_t)s->items;
+        out.words = words;
+        if (words) {
+            out.base = (uint32_t)base[l];
+            out.base_next = l < depth ? (uint32_t)base[l + 1] : 0u;
+            out.last = l == depth;
+            out.n_words = (uint32_t)n_words;
+        }
+        int rc = level_pass<kParent>(ctx, in, out, bound[l], s->counts + l - 1);
+        if (rc) return rc;
+        src = s->keys[turn];
+    }
+    return SVO_OK;
+}
+
+int check_common(svo_ctx *ctx, const svo_build_params *p, uint32_t max_depth, uint64_t *n_words_out) {
+    if (n_words_out) *n_words_out = 0;
+    if (!p) return fail(ctx, SVO_ERR_ARG, "null params");
+    if (p->depth < 1 || p->depth > max_depth)
+        return fail(ctx, SVO_ERR_ARG, "depth must be 1.." + std::to_string(max_depth) + " (got " + std::to_string(p->depth) + ")");
+    return SVO_OK;
+}
+
+int check_store(svo_ctx *ctx) {
+    if (!ctx->store) return fail(ctx, SVO_ERR_STATE, "svo_nodes_alloc / svo_nodes_bind_device not called");
+    return SVO_OK;
+}
+
+uint64_t word_limit(const svo_ctx *ctx, const svo_build_params *p) {
+    uint64_t lim = std::min<uint64_t>(ctx->capacity, kMaxWords);
+    return p->max_words ? std::min<uint64_t>(lim, p->max_words) : lim;
+}
+
+// Both entry points after their leaf pass: the other level passes, one read-back of the counts, the cap, the emit.
+int finish(svo_ctx *ctx, const svo_build_params *p, uint64_t leaf_bound, double t0, bool sorted, uint64_t *n_words_out) {
+    svo_build_state *s = ctx->build;
+    const uint32_t depth = p->depth;
+    uint64_t bound[23] = {};  // host bounds of the unique nodes per level
+    bound[depth] = std::min<uint64_t>(leaf_bound, s->items);
+    for (uint32_t l = depth; l-- > 0;) bound[l] = std::min<uint64_t>(bound[l + 1], 1ull << (3 * l));  // m_L <= 8^L
+    int rc = parent_passes(ctx, depth, 2, bound, nullptr, nullptr, 0);
+    if (rc) return rc;
+    HIP_TRY(ctx, hipEventRecord(s->ev[3], ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(s->counts_host, s->counts, kCountSlots * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipEventRecord(s->ev[4], ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    const uint32_t *m = s->counts_host;
+    if (m[kErrSlot]) return fail(ctx, SVO_ERR_ARG, "a voxel coordinate is outside [0, 2^depth) (depth " + std::to_string(depth) + ")");
+    const uint64_t limit = word_limit(ctx, p);
+    if (m[depth] > s->items)  // (dense: more solid cells than the cap has words)
+        return fail(ctx, SVO_ERR_CAP, std::to_string(m[depth]) + " leaves cannot fit in " + std::to_string(limit) + " words");
+    // breadth-first bases: level 1 (the root group) at 0, level L+1 behind level L's 8 * m_{L-1} words
+    uint64_t base[23] = {0, 0};
+    for (uint32_t l = 1; l < depth; l++) base[l + 1] = base[l] + 8ull * (l == 1 ? 1u : m[l - 1]);
+    const uint64_t n_words = base[depth] + 8ull * (depth == 1 ? 1u : m[depth - 1]);
+    if (n_words > limit)
+        return fail(ctx, SVO_ERR_CAP, "the tree needs " + std::to_string(n_words) + " words, over the limit of " + std::to_string(limit) +
+                                          " (max_words, the node buffer's capacity, 2^27)");
+    for (uint32_t l = 1; l <= depth; l++) bound[l] = m[l];
+    // emit: behind every earlier write to the store, whichever context issued it
+    rc = svo_store_order_after_write(ctx);
+    if (rc) return rc;
+    HIP_TRY(ctx, hipEventRecord(s->ev[5], ctx->stream));
+    HIP_TRY(ctx, hipMemsetD32Async((hipDeviceptr_t)ctx->nodes, (int)kEmptyWord, n_words, ctx->stream));
+    rc = parent_passes(ctx, depth, 1, bound, ctx->nodes, base, n_words);
+    if (rc) return rc;
+    HIP_TRY(ctx, hipEventRecord(s->ev[6], ctx->stream));
+    rc = svo_store_note_write(ctx);
+    if (rc) return rc;
+    *n_words_out = n_words;
+    s->ms[5] = float(now_ms() - t0);
+    s->sorted = sorted;
+    s->timed = false;  // (the emit is still in flight: svo_build_timing reads the events)
+    return SVO_OK;
+}
+
+// n == 0 (CpuOctree::new(0)): the root group of 8 empty words.
+int build_empty(svo_ctx *ctx, const svo_build_params *p, uint64_t *n_words_out) {
+    if (word_limit(ctx, p) < 8) return fail(ctx, SVO_ERR_CAP, "the empty tree needs 8 words, over max_words");
+    int rc = svo_store_order_after_write(ctx);
+    if (rc) return rc;
+    HIP_TRY(ctx, hipMemsetD32Async((hipDeviceptr_t)ctx->nodes, (int)kEmptyWord, 8, ctx->stream));
+    rc = svo_store_note_write(ctx);
+    if (rc) return rc;
+    if (ctx->build) {
+        memset(ctx->build->ms, 0, sizeof ctx->build->ms);
+        ctx->build->timed = true;
+    }
+    *n_words_out = 8;
+    return SVO_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int svo_nodes_build(svo_ctx *ctx, const uint32_t *xyz, const uint32_t *colours, size_t n, const svo_build_params *p,
+                    uint64_t *n_words_out) {
+    if (!ctx) return SVO_ERR_ARG;
+    int rc = check_common(ctx, p, 21, n_words_out);
+    if (rc) return rc;
+    if (n >= (1ull << 31)) return fail(ctx, SVO_ERR_ARG, "at most 2^31 - 1 voxels per build");
+    if (!xyz && n) return fail(ctx, SVO_ERR_ARG, "null coordinates");
+    if (!n_words_out) return fail(ctx, SVO_ERR_ARG, "null n_words_out");
+    if ((rc = check_store(ctx))) return rc;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (!n) return build_empty(ctx, p, n_words_out);
+    const double t0 = now_ms();
+    const uint32_t depth = p->depth, nt = tiles_for(n);
+    if ((rc = ensure_state(ctx, n, std::max<uint64_t>(n, 256ull * nt), 256ull * nt))) return rc;
+    svo_build_state *s = ctx->build;
+    HIP_TRY(ctx, hipEventRecord(s->ev[0], ctx->stream));
+    HIP_TRY(ctx, hipMemsetAsync(s->counts, 0, kCountSlots * sizeof(uint32_t), ctx->stream));
+    build_keys_kernel<<<(uint32_t)((n + kThreads - 1) / kThreads), kThreads, 0, ctx->stream>>>(xyz, (uint32_t)n, depth, s->keys[0],
+                                                                                               s->vals[0], s->counts + kErrSlot);
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, hipEventRecord(s->ev[1], ctx->stream));
+    const uint32_t passes = (3 * depth + 7) / 8;
+    for (uint32_t k = 0; k < passes; k++) {
+        const uint32_t a = k & 1;
+        build_hist_kernel<<<nt, kThreads, 0, ctx->stream>>>(s->keys[a], (uint32_t)n, 8 * k, s->hist, nt);
+        HIP_TRY(ctx, hipGetLastError());
+        if ((rc = scan_u32(ctx, s->hist, 256 * nt))) return rc;
+        build_scatter_kernel<<<nt, kThreads, 0, ctx->stream>>>(s->keys[a], s->vals[a], (uint32_t)n, 8 * k, s->hist, nt, s->keys[a ^ 1],
+                                                               s->vals[a ^ 1]);
+        HIP_TRY(ctx, hipGetLastError());
+    }
+    HIP_TRY(ctx, hipEventRecord(s->ev[2], ctx->stream));
+    // leaf level: the last voxel of every run of equal keys
+    LevelIn in{};
+    in.keys = s->keys[passes & 1];
+    in.vals = s->vals[passes & 1];
+    in.colours = colours;
+    in.colour = p->default_colour;
+    in.m_max = (uint32_t)n;
+    LevelOut out{};
+    out.keys = s->keys[2];
+    out.colours = s->leaf_colours;
+    out.cap = (uint32_t)s->items;
+    if ((rc = level_pass<kDedupe>(ctx, in, out, n, s->counts + depth))) return rc;
+    return finish(ctx, p, n, t0, true, n_words_out);
+}
+
+int svo_nodes_build_dense(svo_ctx *ctx, const uint32_t *grid, const svo_build_params *p, uint64_t *n_words_out) {
+    if (!ctx) return SVO_ERR_ARG;
+    int rc = check_common(ctx, p, 10, n_words_out);
+    if (rc) return rc;
+    if (!grid) return fail(ctx, SVO_ERR_ARG, "null grid");
+    if (!n_words_out) return fail(ctx, SVO_ERR_ARG, "null n_words_out");
+    if ((rc = check_store(ctx))) return rc;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const double t0 = now_ms();
+    const uint32_t depth = p->depth;
+    const uint64_t cells = 1ull << (3 * depth);
+    // every leaf takes a word: a grid with more solid cells than the limit has words fails the cap, so the leaf level
+    // needs no more room than that
+    const uint64_t room = std::max<uint64_t>(std::min(cells, word_limit(ctx, p)), 1);
+    if ((rc = ensure_state(ctx, room, cells, 0))) return rc;
+    svo_build_state *s = ctx->build;
+    HIP_TRY(ctx, hipEventRecord(s->ev[0], ctx->stream));
+    HIP_TRY(ctx, hipMemsetAsync(s->counts, 0, kCountSlots * sizeof(uint32_t), ctx->stream));
+    HIP_TRY(ctx, hipEventRecord(s->ev[1], ctx->stream));
+    HIP_TRY(ctx, hipEventRecord(s->ev[2], ctx->stream));
+    LevelIn in{};
+    in.colours = grid;
+    in.m_max = (uint32_t)cells;
+    in.depth = depth;
+    LevelOut out{};
+    out.keys = s->keys[2];
+    out.colours = s->leaf_colours;
+    out.cap = (uint32_t)s->items;
+    if ((rc = level_pass<kDense>(ctx, in, out, cells, s->counts + depth))) return rc;
+    return finish(ctx, p, cells, t0, false, n_words_out);
+}
+
+int svo_build_timing(svo_ctx *ctx, float ms_out[SVO_BUILD_TIMES]) {
+    if (!ctx || !ms_out) return SVO_ERR_ARG;
+    if (!ctx->build) return fail(ctx, SVO_ERR_STATE, "no tree built on this context yet");
+    svo_build_state *s = ctx->build;
+    if (!s->timed) {
+        const int first[5] = {0, 1, 2, 3, 5}, last[5] = {1, 2, 3, 4, 6};
+        HIP_TRY(ctx, hipSetDevice(ctx->device));
+        HIP_TRY(ctx, hipEventSynchronize(s->ev[6]));
+        for (int k = 0; k < 5; k++) {
+            s->ms[k] = 0.0f;
+            if (k == 1 && !s->sorted) continue;  // (dense: no sort)
+            HIP_TRY(ctx, hipEventElapsedTime(&s->ms[k], s->ev[first[k]], s->ev[last[k]]));
+        }
+        s->timed = true;
+    }
+    memcpy(ms_out, ctx->build->ms, sizeof ctx->build->ms);
+    return SVO_OK;
+}
+
+}  // extern "C"

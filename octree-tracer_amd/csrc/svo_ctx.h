@@ -97,6 +97,7 @@ struct svo_ctx {
     std::vector<hipEvent_t> ev;  // 2 per slot
     size_t ev_slots = 0, ev_count = 0;
     struct svo_proc_state *proc = nullptr;  // procedural generator's workspace (svo_proc.hip)
+    struct svo_build_state *build = nullptr;  // tree builder's workspace (svo_build.hip)
     std::string err;
 };
 
@@ -104,10 +105,16 @@ struct svo_ctx {
 // svo_abi.cpp
 int svo_fail(svo_ctx *ctx, int code, const char *what);
 int svo_fail_hip(svo_ctx *ctx, hipError_t e, const char *what);
+// a write to the bound node store: enqueue it behind the store's last write (any context's), then record it, which makes
+// every context bound to the store rebuild its top table and schedule
+int svo_store_order_after_write(svo_ctx *ctx);
+int svo_store_note_write(svo_ctx *ctx);
 // svo_comm.cpp
 void svo_comm_release(svo_ctx *ctx);
 // svo_proc.hip
 void svo_proc_release(svo_ctx *ctx);
+// svo_build.hip
+void svo_build_release(svo_ctx *ctx);
 // svo_host.cpp (internal helpers of svo_world_generate)
 std::string svo_world_path(const svo_world *w);
 void svo_cpu_octree_drop_nodes(svo_cpu_octree *t);  // frees the nodes, keeps top_mip (world.rs:122)

@@ -49,6 +49,13 @@ class Gpu:
         self.check(lib().svo_last_render_ms(self._h, C.byref(ms)))
         return ms.value
 
+    def build_timing(self):
+        """ms of the last Render.build_nodes / build_nodes_dense: keys, sort, levels, count read-back, emit (device events),
+        host wall time of the call (svo_build_timing)"""
+        ms = (C.c_float * 6)()
+        self.check(lib().svo_build_timing(self._h, ms))
+        return list(ms)
+
     def strip_classes(self, n_strips):
         """class byte per 64-pixel block of the last pixel frame that ran the culling pass (0xFF = culled); diagnostics"""
         import numpy as np

@@ -4,12 +4,13 @@ import ctypes as C
 import numpy as np
 import torch
 
-from ._lib import Uniforms, lib
+from ._lib import BuildParams, Uniforms, lib
 from .camera import camera_matrices
 
 F_PAUSE_ADAPTIVE, F_SHOW_STEPS, F_SHOW_HITS, F_SHADOWS, F_MISC_BOOL = 1, 2, 4, 8, 16
 HIT_DTYPE = np.dtype([("value", "<u4"), ("t", "<f4"), ("info", "<u4"), ("normal_bits", "<u4")])
 DEFAULT_NODE_CAPACITY = 10_000_000  # render.rs:53
+EMPTY_WORD = (1 << 27) << 4  # an empty slot: (VOXEL_OFFSET + colour 0) << 4
 
 
 class Render:
@@ -62,6 +63,67 @@ class Render:
         self.gpu.check(lib().svo_nodes_write(self.gpu._h, offset, words.ctypes.data, words.size))
         self.gpu.sync()  # the host array may be released by the caller
         self.node_length = max(self.node_length, offset + words.size)
+
+    @classmethod
+    def from_voxels(cls, gpu, size, coords, depth, colours=None, capacity=None):
+        """A Render whose tree is built on the GPU from a voxel list (build_nodes)."""
+        self = cls(gpu, size, np.full(8, EMPTY_WORD, dtype=np.uint32), capacity)
+        self.build_nodes(coords, depth, colours)
+        return self
+
+    def build_nodes(self, coords, depth, colours=None, colour=0xFFFFFF, max_words=None):
+        """Build the tree of a voxel list on the GPU into the node buffer from word 0 (svo_nodes_build).
+        coords: (N, 3) integer cells in [0, 2^depth), a torch tensor on this context's device or numpy (copied there);
+        colours: N values 0x00RRGGBB or None (every voxel `colour`).  Returns the word count."""
+        dev = torch.device("cuda", self.gpu.device)
+        xyz = _device_u32(coords, dev, clamp=True)
+        if xyz.dim() != 2 or xyz.shape[1] != 3:
+            raise ValueError(f"coords must be (N, 3), got {tuple(xyz.shape)}")
+        n = xyz.shape[0]
+        col = None
+        if colours is not None:
+            col = _device_u32(colours, dev, mask=0xFFFFFF).reshape(-1)
+            if col.numel() != n:
+                raise ValueError(f"{col.numel()} colours for {n} voxels")
+        p = self._build_params(depth, colour, max_words)
+        out = C.c_uint64()
+        torch.cuda.current_stream(dev).synchronize()  # the inputs were made on torch's stream
+        rc = lib().svo_nodes_build(self.gpu._h, xyz.data_ptr() if n else None, col.data_ptr() if col is not None and n else None, n,
+                                   C.byref(p), C.byref(out))
+        self.gpu.check(rc)
+        self.gpu.sync()  # (the inputs may be released by the caller)
+        self.node_length = out.value
+        return out.value
+
+    def build_nodes_dense(self, grid, max_words=None):
+        """Build the tree of a dense (side, side, side) colour grid indexed [x, y, z] (non-zero = voxel, low 24 bits the
+        colour; side = 2^depth, depth 1..10) on the GPU (svo_nodes_build_dense).  Returns the word count."""
+        dev = torch.device("cuda", self.gpu.device)
+        g = _device_u32(grid, dev, cells=True)
+        side = g.shape[0] if g.dim() == 3 else 0
+        depth = side.bit_length() - 1
+        if g.dim() != 3 or tuple(g.shape) != (side,) * 3 or side != 1 << depth:
+            raise ValueError(f"grid must be (side, side, side) with side a power of two, got {tuple(g.shape)}")
+        p = self._build_params(depth, 0, max_words)
+        out = C.c_uint64()
+        torch.cuda.current_stream(dev).synchronize()
+        self.gpu.check(lib().svo_nodes_build_dense(self.gpu._h, g.data_ptr(), C.byref(p), C.byref(out)))
+        self.gpu.sync()
+        self.node_length = out.value
+        return out.value
+
+    def _build_params(self, depth, colour, max_words):
+        depth = int(depth)
+        # the trace kernels must know how deep the tree goes (SVO_OPT_TREE_DEPTH; raised, never lowered)
+        if 1 <= depth <= 21 and depth > getattr(self, "_declared_depth", 16):
+            from .gpu import OPT_TREE_DEPTH
+            self.gpu.set_option(OPT_TREE_DEPTH, depth)
+            self._declared_depth = depth
+        p = BuildParams()
+        p.depth = max(0, depth)
+        p.default_colour = int(colour) & 0xFFFFFF
+        p.max_words = int(max_words or 0)
+        return p
 
     def scatter_nodes(self, indices, words, node_length=None):
         """Incremental upload: words[i] -> node buffer [indices[i]] (svo_nodes_scatter)."""
@@ -214,6 +276,25 @@ class Render:
             hits = self.alloc_hits(n, rays.device)
         self.gpu.check(lib().svo_trace_rays(self.gpu._h, rays.data_ptr(), n, hits.data_ptr()))
         return hits
+
+
+def _device_u32(a, dev, clamp=False, mask=None, cells=False):
+    """An integer array as a contiguous int32 tensor on `dev` holding u32 bit patterns.  clamp: values outside [0, 2^31)
+    become -1 or 2^31 - 1, out of range for any depth, so the device's range check still sees them; mask: keep those bits;
+    cells: a wide value stays non-zero iff it was (its low 24 bits kept)."""
+    t = a if isinstance(a, torch.Tensor) else torch.as_tensor(np.ascontiguousarray(a))
+    if t.dtype.is_floating_point or t.dtype.is_complex or t.dtype == torch.bool:
+        raise TypeError(f"integer input expected, got {t.dtype}")
+    t = t.to(dev)
+    if t.dtype != torch.int32 or mask is not None:
+        t = t.to(torch.int64)
+        if mask is not None:
+            t = t & mask
+        elif clamp:
+            t = t.clamp(-1, 2**31 - 1)
+        elif cells:
+            t = torch.where(t != 0, (t & 0xFFFFFF) | (1 << 24), 0)
+    return t.to(torch.int32).contiguous()
 
 
 def hits_to_numpy(hits):
