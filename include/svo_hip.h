@@ -351,6 +351,39 @@ int svo_nodes_build_dense(svo_ctx *ctx, const uint32_t *grid, const svo_build_pa
 #define SVO_BUILD_TIMES 6
 int svo_build_timing(svo_ctx *ctx, float ms_out[SVO_BUILD_TIMES]);
 
+/* ---- the adaptive step on the GPU ----
+ * Device form of the streaming loop's list processing: after svo_adaptive_step the node buffer, the node positions, the
+ * hole stack, the tree length, the world's chunk set and the counts equal what svo_adaptive_subdivide(sorted(sub)) then
+ * svo_adaptive_unsubdivide(sorted(unsub)) make of the same state, bit for bit.  The state lives with the context:
+ * svo_adaptive_attach uploads the host octree's positions, hole stack and length and mirrors every resident chunk of w
+ * (the words must already be in the node buffer; SVO_OPT_SCAN_CLEARS_COUNTERS must be 1).  w stays the owner of chunk
+ * data and must outlive the attachment: chunk loads go through svo_world_load_chunk, removals through svo_world_remove.
+ * Attach again after any other change to the tree or the world. */
+typedef struct svo_adaptive_result {
+    uint32_t n_sub, n_unsub;    /* nodes subdivided / unsubdivided (the host calls' return values) */
+    uint64_t chunks_loaded;     /* chunks the subdivide pass loaded */
+    uint64_t length;            /* the tree's length afterwards (svo_octree_len) */
+    uint32_t n_removed;         /* chunks the unsubdivide pass dropped ... */
+    const uint32_t *removed;    /* ... their ids, ascending; valid until the next call on ctx */
+} svo_adaptive_result;
+struct svo_octree;
+int svo_adaptive_attach(svo_ctx *ctx, struct svo_world *w, const struct svo_octree *o);
+/* d_sub / d_unsub: DEVICE lists of node indices (any order; both or neither).  NULL: the context's own scan lists, clamped
+ * like svo_scan_read (min(count, capacity - 1)) with their counters reset -- no list crosses PCIe.  Blocking.
+ * SVO_ERR_STATE, with nothing written, for a subdivide list that the parallel form cannot take (an entry listed twice,
+ * an entry >= length, an entry inside a hole group the pass reuses, an entry whose walk ends at another listed leaf):
+ * it needs the sequential host path.  SVO_ERR_CAP, nothing written, when the new groups would pass the capacity.  Any
+ * other error (where the host calls fail too) leaves the state unspecified until the next attach. */
+int svo_adaptive_step(svo_ctx *ctx, const uint32_t *d_sub, uint32_t n_sub, const uint32_t *d_unsub, uint32_t n_unsub,
+                      svo_adaptive_result *out);
+/* o := the device state (words without counters, positions, hole stack, length); clears o's dirty set.  Blocking. */
+int svo_adaptive_download(svo_ctx *ctx, struct svo_octree *o);
+int svo_adaptive_length(svo_ctx *ctx, uint64_t *len_out);
+/* Times (ms) of the last step: [0] sorting both lists, [1] subdivide pass, [2] unsubdivide pass (device events, read-backs
+ * and chunk loads included), [3] host wall time of the call. */
+#define SVO_ADAPT_TIMES 4
+int svo_adaptive_timing(svo_ctx *ctx, float ms_out[SVO_ADAPT_TIMES]);
+
 #ifdef __cplusplus
 }
 #endif

@@ -85,6 +85,9 @@ void svo_octree_pos_offset(uint32_t child_index, uint32_t depth, float out[3]);
 size_t svo_octree_holes(const svo_octree *o);
 void svo_octree_set_node(svo_octree *o, size_t index, uint32_t word);   /* octree.nodes[i] = word (adaptive.rs:117) */
 void svo_octree_position(const svo_octree *o, size_t index, float out[3]); /* octree.positions[i] */
+/* octree.hole_stack (bottom first) / every position (3 floats per node); returns the count, copies when cap suffices */
+size_t svo_octree_hole_stack(const svo_octree *o, uint32_t *out, size_t cap);
+size_t svo_octree_positions(const svo_octree *o, float *out, size_t cap);
 /* Words written (subdivide, unsubdivide, set_node, svo_adaptive_*) since the previous call, each index once, with
  * their current values: the input of svo_nodes_scatter.  Returns the count; with NULL outputs or cap too small nothing
  * is consumed. */

@@ -242,6 +242,17 @@ class Render {  // render.rs:3-285
         gpu_.poll_wait();  // the inputs may go away
         return n_words;
     }
+    // the adaptive step on the GPU (svo_adaptive_*): attach once (SVO_OPT_SCAN_CLEARS_COUNTERS = 1, the
+    // octree's words in the node buffer, `world` kept alive), then after each scan step() over the scan's own lists (or
+    // explicit DEVICE lists); download() brings the host octree up to date
+    void adaptive_attach(World &world, const Octree &octree) { gpu_.check(svo_adaptive_attach(gpu_.ctx(), world.raw(), octree.raw())); }
+    svo_adaptive_result adaptive_step(const uint32_t *sub_dev = nullptr, uint32_t n_sub = 0, const uint32_t *unsub_dev = nullptr,
+                                      uint32_t n_unsub = 0) {
+        svo_adaptive_result r{};
+        gpu_.check(svo_adaptive_step(gpu_.ctx(), sub_dev, n_sub, unsub_dev, n_unsub, &r));
+        return r;
+    }
+    void adaptive_download(Octree &octree) { gpu_.check(svo_adaptive_download(gpu_.ctx(), octree.raw())); }
     // incremental form of the same upload: only the words that changed (svo_nodes_scatter; pair it with
     // gpu.set_option(SVO_OPT_SCAN_CLEARS_COUNTERS, 1), which takes over the counter reset of the full upload)
     void scatter_nodes(const std::vector<uint32_t> &indices, const std::vector<uint32_t> &words) {

@@ -56,6 +56,18 @@ class BuildParams(C.Structure):
     ]
 
 
+class AdaptiveResult(C.Structure):
+    """svo_adaptive_result: one device adaptive step (include/svo_hip.h)."""
+    _fields_ = [
+        ("n_sub", C.c_uint32),
+        ("n_unsub", C.c_uint32),
+        ("chunks_loaded", C.c_uint64),
+        ("length", C.c_uint64),
+        ("n_removed", C.c_uint32),
+        ("removed", C.POINTER(C.c_uint32)),
+    ]
+
+
 DEVICE_SYMBOLS = [
     "svo_device_count", "svo_buffer_alloc", "svo_buffer_free", "svo_buffer_read", "svo_ctx_create", "svo_ctx_destroy", "svo_ctx_set_stream", "svo_set_option", "svo_last_error", "svo_sync",
     "svo_nodes_alloc", "svo_nodes_bind_device", "svo_nodes_write", "svo_nodes_scatter", "svo_nodes_read", "svo_nodes_device_ptr", "svo_nodes_share", "svo_nodes_invalidate",
@@ -64,6 +76,7 @@ DEVICE_SYMBOLS = [
     "svo_last_render_ms", "svo_timing_collect", "svo_diag_gather", "svo_diag_strip_classes", "svo_scan_dispatch", "svo_scan_read",
     "svo_proc_generate_chunk", "svo_world_generate", "svo_proc_sdf", "svo_proc_classify", "svo_proc_timing",
     "svo_nodes_build", "svo_nodes_build_dense", "svo_buffer_write", "svo_build_timing",
+    "svo_adaptive_attach", "svo_adaptive_step", "svo_adaptive_download", "svo_adaptive_length", "svo_adaptive_timing",
 ]
 HOST_SYMBOLS = [
     "svo_cpu_octree_new", "svo_cpu_octree_free", "svo_cpu_octree_len", "svo_cpu_octree_load_file",
@@ -73,7 +86,7 @@ HOST_SYMBOLS = [
     "svo_cpu_octree_generate_mips", "svo_vox_parse", "svo_vox_write", "svo_rsvo_write",
     "svo_octree_new", "svo_octree_from_words", "svo_octree_free", "svo_octree_len", "svo_octree_raw_data",
     "svo_octree_get_node", "svo_octree_subdivide", "svo_octree_unsubdivide", "svo_octree_find_voxel",
-    "svo_octree_expanded", "svo_octree_pos_offset", "svo_octree_holes", "svo_octree_set_node", "svo_octree_position", "svo_octree_take_dirty", "svo_camera_matrices",
+    "svo_octree_expanded", "svo_octree_pos_offset", "svo_octree_holes", "svo_octree_set_node", "svo_octree_position", "svo_octree_hole_stack", "svo_octree_positions", "svo_octree_take_dirty", "svo_camera_matrices",
     "svo_world_new", "svo_world_free", "svo_world_last_error", "svo_world_insert", "svo_world_remove",
     "svo_world_chunk", "svo_world_chunk_ids", "svo_world_find_voxel", "svo_world_generate_mip_tree",
     "svo_world_save_chunk", "svo_world_load_chunk", "svo_world_load", "svo_cpu_octree_bin", "svo_cpu_octree_from_bin",
@@ -154,6 +167,11 @@ def lib():
     sig("svo_nodes_build_dense", C.c_int, vp, vp, C.POINTER(BuildParams), C.POINTER(u64))
     sig("svo_buffer_write", C.c_int, vp, vp, vp, sz)
     sig("svo_build_timing", C.c_int, vp, fp)
+    sig("svo_adaptive_attach", C.c_int, vp, vp, vp)
+    sig("svo_adaptive_step", C.c_int, vp, vp, u32, vp, u32, C.POINTER(AdaptiveResult))
+    sig("svo_adaptive_download", C.c_int, vp, vp)
+    sig("svo_adaptive_length", C.c_int, vp, C.POINTER(u64))
+    sig("svo_adaptive_timing", C.c_int, vp, fp)
     # host data model (include/svo_host.h)
     sig("svo_cpu_octree_new", vp, C.c_uint8)
     sig("svo_cpu_octree_free", None, vp)
@@ -186,6 +204,8 @@ def lib():
     sig("svo_octree_holes", sz, vp)
     sig("svo_octree_set_node", None, vp, sz, u32)
     sig("svo_octree_position", None, vp, sz, fp)
+    sig("svo_octree_hole_stack", sz, vp, vp, sz)
+    sig("svo_octree_positions", sz, vp, vp, sz)
     sig("svo_octree_take_dirty", sz, vp, vp, vp, sz)
     sig("svo_world_new", vp, cp)
     sig("svo_world_free", None, vp)

@@ -596,6 +596,7 @@ int svo_ctx_destroy(svo_ctx *ctx) {
     svo_comm_release(ctx);
     svo_proc_release(ctx);
     svo_build_release(ctx);
+    svo_adapt_release(ctx);
     release_store(ctx);
     if (ctx->top_table) (void)hipFree(ctx->top_table);
     if (ctx->status) (void)hipFree(ctx->status);

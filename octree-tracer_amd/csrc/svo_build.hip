@@ -522,6 +522,52 @@ int build_empty(svo_ctx *ctx, const svo_build_params *p, uint64_t *n_words_out) 
 
 }  // namespace
 
+namespace {
+
+__global__ __launch_bounds__(kThreads) void build_widen_kernel(const uint32_t *in, uint32_t n, uint64_t *keys, uint32_t *vals) {
+    const uint32_t i = blockIdx.x * kThreads + threadIdx.x;
+    if (i >= n) return;
+    keys[i] = in[i];
+    vals[i] = i;
+}
+
+__global__ __launch_bounds__(kThreads) void build_narrow_kernel(const uint64_t *keys, uint32_t n, uint32_t *out) {
+    const uint32_t i = blockIdx.x * kThreads + threadIdx.x;
+    if (i < n) out[i] = (uint32_t)keys[i];
+}
+
+}  // namespace
+
+// The radix sort and the scan above, for other passes on the ctx stream (svo_adapt.hip sorts its node lists with them).
+int svo_build_sort_u32(svo_ctx *ctx, const uint32_t *in, uint32_t n, uint32_t *out) {
+    if (!n) return SVO_OK;
+    const uint32_t nt = tiles_for(n), grid = (n + kThreads - 1) / kThreads;
+    int rc = ensure_state(ctx, n, std::max<uint64_t>(n, 256ull * nt), 256ull * nt);
+    if (rc) return rc;
+    svo_build_state *s = ctx->build;
+    build_widen_kernel<<<grid, kThreads, 0, ctx->stream>>>(in, n, s->keys[0], s->vals[0]);
+    HIP_TRY(ctx, hipGetLastError());
+    for (uint32_t k = 0; k < 4; k++) {  // (4 passes of 8 bits: the result is back in keys[0])
+        const uint32_t a = k & 1;
+        build_hist_kernel<<<nt, kThreads, 0, ctx->stream>>>(s->keys[a], n, 8 * k, s->hist, nt);
+        HIP_TRY(ctx, hipGetLastError());
+        if ((rc = scan_u32(ctx, s->hist, 256 * nt))) return rc;
+        build_scatter_kernel<<<nt, kThreads, 0, ctx->stream>>>(s->keys[a], s->vals[a], n, 8 * k, s->hist, nt, s->keys[a ^ 1],
+                                                               s->vals[a ^ 1]);
+        HIP_TRY(ctx, hipGetLastError());
+    }
+    build_narrow_kernel<<<grid, kThreads, 0, ctx->stream>>>(s->keys[0], n, out);
+    HIP_TRY(ctx, hipGetLastError());
+    return SVO_OK;
+}
+
+int svo_build_scan_u32(svo_ctx *ctx, uint32_t *a, uint32_t n) {
+    if (!n) return SVO_OK;
+    int rc = ensure_state(ctx, 0, n, 0);
+    if (rc) return rc;
+    return scan_u32(ctx, a, n);
+}
+
 extern "C" {
 
 int svo_nodes_build(svo_ctx *ctx, const uint32_t *xyz, const uint32_t *colours, size_t n, const svo_build_params *p,

@@ -98,6 +98,7 @@ struct svo_ctx {
     size_t ev_slots = 0, ev_count = 0;
     struct svo_proc_state *proc = nullptr;  // procedural generator's workspace (svo_proc.hip)
     struct svo_build_state *build = nullptr;  // tree builder's workspace (svo_build.hip)
+    struct svo_adapt_state *adapt = nullptr;  // device adaptive state (svo_adapt.hip)
     std::string err;
 };
 
@@ -115,6 +116,16 @@ void svo_comm_release(svo_ctx *ctx);
 void svo_proc_release(svo_ctx *ctx);
 // svo_build.hip
 void svo_build_release(svo_ctx *ctx);
+// the builder's stable radix sort of n u32 keys (in -> out, may alias) and in-place exclusive scan of n u32, for other
+// passes on the ctx stream; both use the builder's workspace
+int svo_build_sort_u32(svo_ctx *ctx, const uint32_t *in, uint32_t n, uint32_t *out);
+int svo_build_scan_u32(svo_ctx *ctx, uint32_t *a, uint32_t n);
+// svo_adapt.hip
+void svo_adapt_release(svo_ctx *ctx);
 // svo_host.cpp (internal helpers of svo_world_generate)
 std::string svo_world_path(const svo_world *w);
 void svo_cpu_octree_drop_nodes(svo_cpu_octree *t);  // frees the nodes, keeps top_mip (world.rs:122)
+// svo_host.cpp (internal helpers of the device adaptive state): the octree's words, positions (3 floats per node) and hole
+// stack (bottom first) as they are; svo_octree_assign replaces all three and clears the dirty set
+size_t svo_octree_state(const svo_octree *o, const uint32_t **nodes, const float **positions, std::vector<uint32_t> &holes);
+void svo_octree_assign(svo_octree *o, const uint32_t *nodes, const float *positions, size_t n, const uint32_t *holes, size_t n_holes);

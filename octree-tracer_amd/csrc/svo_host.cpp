@@ -474,6 +474,16 @@ void svo_octree_set_node(svo_octree *o, size_t index, uint32_t word) { o->nodes[
 void svo_octree_position(const svo_octree *o, size_t index, float out[3]) {
     out[0] = o->positions[index].x; out[1] = o->positions[index].y; out[2] = o->positions[index].z;
 }
+size_t svo_octree_hole_stack(const svo_octree *o, uint32_t *out, size_t cap) {
+    const size_t n = o->hole_stack.size();
+    if (out && cap >= n) for (size_t i = 0; i < n; i++) out[i] = uint32_t(o->hole_stack[i]);
+    return n;
+}
+size_t svo_octree_positions(const svo_octree *o, float *out, size_t cap) {
+    const size_t n = o->positions.size();
+    if (out && cap >= 3 * n) for (size_t i = 0; i < n; i++) { out[3 * i] = o->positions[i].x; out[3 * i + 1] = o->positions[i].y; out[3 * i + 2] = o->positions[i].z; }
+    return n;
+}
 
 int svo_octree_subdivide(svo_octree *o, size_t node, const uint8_t mask_rgb[24], uint32_t depth) {
     if ((o->nodes[node] >> 4) < kVoxelOffset) return -1;  // "Node already subdivided!" octree.rs:73-75
@@ -1200,3 +1210,22 @@ uint32_t svo_nodes_max_depth(const uint32_t *words, uint64_t n) {
 std::string svo_world_path(const svo_world *w) { return w->path; }
 
 void svo_cpu_octree_drop_nodes(svo_cpu_octree *t) { std::vector<svo_cpu_octree::Node>().swap(t->nodes); }
+
+// The device adaptive state (svo_adapt.hip) uploads and restores the octree as it is: words, positions (three floats per
+// node, Vec3's layout), hole stack (bottom first).
+size_t svo_octree_state(const svo_octree *o, const uint32_t **nodes, const float **positions, std::vector<uint32_t> &holes) {
+    static_assert(sizeof(Vec3) == 3 * sizeof(float), "positions are uploaded as packed float triples");
+    *nodes = o->nodes.data();
+    *positions = reinterpret_cast<const float *>(o->positions.data());
+    holes.assign(o->hole_stack.begin(), o->hole_stack.end());
+    return o->nodes.size();
+}
+
+void svo_octree_assign(svo_octree *o, const uint32_t *nodes, const float *positions, size_t n, const uint32_t *holes, size_t n_holes) {
+    o->nodes.assign(nodes, nodes + n);
+    o->positions.resize(n);
+    if (n) memcpy(o->positions.data(), positions, n * sizeof(Vec3));
+    o->hole_stack.assign(holes, holes + n_holes);
+    o->dirty.clear();
+    o->dirty_flag.clear();
+}

@@ -109,6 +109,20 @@ class Octree:
         lib().svo_octree_position(self._h, index, out)
         return tuple(out)
 
+    def positions(self):
+        """Every node's position, (len, 3) float32."""
+        n = lib().svo_octree_positions(self._h, None, 0)
+        out = np.empty((n, 3), dtype=np.float32)
+        lib().svo_octree_positions(self._h, out.ctypes.data, out.size)
+        return out
+
+    def hole_stack(self):
+        """The freed groups, bottom first (the next subdivide takes the last)."""
+        n = lib().svo_octree_hole_stack(self._h, None, 0)
+        out = np.empty(n, dtype=np.uint32)
+        lib().svo_octree_hole_stack(self._h, out.ctypes.data, n)
+        return out
+
     def take_dirty(self):
         """(indices, words) written since the previous call, each index once: the input of Render.scatter_nodes."""
         n = lib().svo_octree_take_dirty(self._h, None, None, 0)
