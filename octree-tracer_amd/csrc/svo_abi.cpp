@@ -28,15 +28,6 @@ namespace {
 
 constexpr size_t kScanCapacity = 1024000;  // adaptive.rs:3-4
 
-int fail(svo_ctx *ctx, int code, const char *what) { return svo_fail(ctx, code, what); }
-int fail_hip(svo_ctx *ctx, hipError_t e, const char *what) { return svo_fail_hip(ctx, e, what); }
-
-#define HIP_TRY(ctx, expr)                                   \
-    do {                                                     \
-        hipError_t e_ = (expr);                              \
-        if (e_ != hipSuccess) return fail_hip(ctx, e_, #expr); \
-    } while (0)
-
 int bind(svo_ctx *ctx) {
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     return SVO_OK;
@@ -322,42 +313,31 @@ bool fuse_shadow_rays(const svo_ctx *ctx) {
     return true;
 }
 
-int ensure_dev(svo_ctx *ctx, void **buf, size_t *have, size_t bytes) {
-    if (*have >= bytes) return SVO_OK;
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    if (*buf) (void)hipFree(*buf);
-    *buf = nullptr;
-    *have = 0;
-    HIP_TRY(ctx, hipMalloc(buf, bytes));
-    *have = bytes;
-    return SVO_OK;
-}
-
 // Trace (and, when rgba is asked for, shade) the pixels of `work`: fs_main, shader.wgsl:250-304.
 int trace_common(svo_ctx *ctx, const svo::WorkDesc &work, const float *rays, svo_hit *hits, uint32_t *rgba) {
-    if (!ctx->nodes) return fail(ctx, SVO_ERR_STATE, "svo_nodes_alloc / svo_nodes_bind_device not called");
-    if (work.mode != 2 && !ctx->have_uniforms) return fail(ctx, SVO_ERR_STATE, "svo_set_uniforms not called");
-    if (!hits && !rgba) return fail(ctx, SVO_ERR_ARG, "both hits_out and rgba_out are NULL");
+    if (!ctx->nodes) return svo_fail(ctx, SVO_ERR_STATE, "svo_nodes_alloc / svo_nodes_bind_device not called");
+    if (work.mode != 2 && !ctx->have_uniforms) return svo_fail(ctx, SVO_ERR_STATE, "svo_set_uniforms not called");
+    if (!hits && !rgba) return svo_fail(ctx, SVO_ERR_ARG, "both hits_out and rgba_out are NULL");
     if (!rgba) return trace_launch(ctx, work, rays, hits, TraceOpts{});
-    if (work.mode == 2) return fail(ctx, SVO_ERR_ARG, "explicit rays have no pixels to shade");
+    if (work.mode == 2) return svo_fail(ctx, SVO_ERR_ARG, "explicit rays have no pixels to shade");
     int rc = bind(ctx);
     if (rc) return rc;
     const size_t n = (size_t)work.n_rects * work.w * work.h;  // records of this call
     const uint32_t f = ctx->uniforms.flags;
     const bool shadows = (f & SVO_F_SHADOWS) && !(f & SVO_F_SHOW_STEPS) && !(f & SVO_F_SHOW_HITS);
     if (!hits) {
-        rc = ensure_dev(ctx, &ctx->shade_hits, &ctx->shade_hits_bytes, n * sizeof(svo_hit));
+        rc = svo_grow(ctx, &ctx->shade_hits_bytes, n * sizeof(svo_hit), &ctx->shade_hits);
         if (rc) return rc;
         hits = (svo_hit *)ctx->shade_hits;
     }
     const bool fused = shadows && fuse_shadow_rays(ctx);
     TraceOpts primary;
     if (fused) {
-        rc = ensure_dev(ctx, &ctx->shade_shadow, &ctx->shade_shadow_bytes, n * sizeof(svo_hit));
+        rc = svo_grow(ctx, &ctx->shade_shadow_bytes, n * sizeof(svo_hit), &ctx->shade_shadow);
         if (rc) return rc;
         primary.shadow_out = (svo_hit *)ctx->shade_shadow;
     } else {
-        rc = ensure_dev(ctx, &ctx->shade_aux, &ctx->shade_aux_bytes, n * sizeof(float));
+        rc = svo_grow(ctx, &ctx->shade_aux_bytes, n * sizeof(float), &ctx->shade_aux);
         if (rc) return rc;
         primary.aux_t = (float *)ctx->shade_aux;
     }
@@ -365,11 +345,11 @@ int trace_common(svo_ctx *ctx, const svo::WorkDesc &work, const float *rays, svo
     if (rc) return rc;
     const svo::TraceArgs a = trace_args(ctx, work, hits);
     if (shadows && !fused) {
-        rc = ensure_dev(ctx, &ctx->shade_rays, &ctx->shade_rays_bytes, n * 6 * sizeof(float));
+        rc = svo_grow(ctx, &ctx->shade_rays_bytes, n * 6 * sizeof(float), &ctx->shade_rays);
         if (rc) return rc;
-        rc = ensure_dev(ctx, &ctx->shade_shadow, &ctx->shade_shadow_bytes, n * sizeof(svo_hit));
+        rc = svo_grow(ctx, &ctx->shade_shadow_bytes, n * sizeof(svo_hit), &ctx->shade_shadow);
         if (rc) return rc;
-        rc = ensure_dev(ctx, &ctx->shade_skip, &ctx->shade_skip_bytes, n);
+        rc = svo_grow(ctx, &ctx->shade_skip_bytes, n, &ctx->shade_skip);
         if (rc) return rc;
         HIP_TRY(ctx, svo::launch_secondary_gen(a, (const float *)ctx->shade_aux, (float *)ctx->shade_rays, (uint8_t *)ctx->shade_skip,
                                                (svo_hit *)ctx->shade_shadow, 0u, 1u, (uint32_t)n, ctx->stream));
@@ -387,21 +367,21 @@ int trace_common(svo_ctx *ctx, const svo::WorkDesc &work, const float *rays, svo
 // Primary rays of `work`, then n_secondary rays from every hit pixel (ray 0: fs_main's shadow ray), traced as one
 // launch of explicit rays; records ray-major: secondary[k * n + record].
 int trace_secondary(svo_ctx *ctx, const svo::WorkDesc &work, uint32_t n_secondary, svo_hit *primary, svo_hit *secondary) {
-    if (!ctx->nodes) return fail(ctx, SVO_ERR_STATE, "svo_nodes_alloc / svo_nodes_bind_device not called");
-    if (!secondary) return fail(ctx, SVO_ERR_ARG, "secondary_out is NULL");
-    if (n_secondary < 1 || n_secondary > 4) return fail(ctx, SVO_ERR_ARG, "n_secondary must be 1..4");
+    if (!ctx->nodes) return svo_fail(ctx, SVO_ERR_STATE, "svo_nodes_alloc / svo_nodes_bind_device not called");
+    if (!secondary) return svo_fail(ctx, SVO_ERR_ARG, "secondary_out is NULL");
+    if (n_secondary < 1 || n_secondary > 4) return svo_fail(ctx, SVO_ERR_ARG, "n_secondary must be 1..4");
     int rc = bind(ctx);
     if (rc) return rc;
     const size_t n = (size_t)work.n_rects * work.w * work.h;
-    if (n * n_secondary > (1u << 26)) return fail(ctx, SVO_ERR_ARG, "too many secondary rays for one call");
+    if (n * n_secondary > (1u << 26)) return svo_fail(ctx, SVO_ERR_ARG, "too many secondary rays for one call");
     if (!primary) {
-        rc = ensure_dev(ctx, &ctx->shade_hits, &ctx->shade_hits_bytes, n * sizeof(svo_hit));
+        rc = svo_grow(ctx, &ctx->shade_hits_bytes, n * sizeof(svo_hit), &ctx->shade_hits);
         if (rc) return rc;
         primary = (svo_hit *)ctx->shade_hits;
     }
-    rc = ensure_dev(ctx, &ctx->shade_aux, &ctx->shade_aux_bytes, n * sizeof(float));
+    rc = svo_grow(ctx, &ctx->shade_aux_bytes, n * sizeof(float), &ctx->shade_aux);
     if (rc) return rc;
-    rc = ensure_dev(ctx, &ctx->shade_rays, &ctx->shade_rays_bytes, n * n_secondary * 6 * sizeof(float));
+    rc = svo_grow(ctx, &ctx->shade_rays_bytes, n * n_secondary * 6 * sizeof(float), &ctx->shade_rays);
     if (rc) return rc;
     // ray 0, the shadow ray, can run inside the primary launch (its records go straight to the first set)
     const bool debug_view = (ctx->uniforms.flags & SVO_F_PAUSE_ADAPTIVE) && (ctx->uniforms.flags & SVO_F_SHOW_HITS);
@@ -414,7 +394,7 @@ int trace_secondary(svo_ctx *ctx, const svo::WorkDesc &work, uint32_t n_secondar
     if (rc) return rc;
     if (k_first == n_secondary) return SVO_OK;
     const svo::TraceArgs a = trace_args(ctx, work, primary);
-    rc = ensure_dev(ctx, &ctx->shade_skip, &ctx->shade_skip_bytes, n * n_secondary);
+    rc = svo_grow(ctx, &ctx->shade_skip_bytes, n * n_secondary, &ctx->shade_skip);
     if (rc) return rc;
     svo_hit *rest = secondary + (size_t)k_first * n;
     HIP_TRY(ctx, svo::launch_secondary_gen(a, (const float *)ctx->shade_aux, (float *)ctx->shade_rays, (uint8_t *)ctx->shade_skip, rest,
@@ -438,12 +418,12 @@ void set_blocks(svo::WorkDesc &work, uint32_t bw_log2, uint32_t w, uint32_t h) {
 
 int make_tiles_work(svo_ctx *ctx, uint32_t width, uint32_t height, uint32_t tile_w, uint32_t tile_h, uint32_t first_tile,
                     uint32_t tile_stride, svo::WorkDesc &work) {
-    if (!ctx->have_uniforms) return fail(ctx, SVO_ERR_STATE, "svo_set_uniforms not called");
+    if (!ctx->have_uniforms) return svo_fail(ctx, SVO_ERR_STATE, "svo_set_uniforms not called");
     if ((float)width != ctx->uniforms.dimensions[0] || (float)height != ctx->uniforms.dimensions[1])
-        return fail(ctx, SVO_ERR_ARG, "width/height differ from uniforms.dimensions");
+        return svo_fail(ctx, SVO_ERR_ARG, "width/height differ from uniforms.dimensions");
     if (tile_w == 0 || tile_h == 0 || width % tile_w || height % tile_h)
-        return fail(ctx, SVO_ERR_ARG, "frame must be a whole number of tiles");
-    if (tile_stride == 0) return fail(ctx, SVO_ERR_ARG, "tile_stride must be >= 1");
+        return svo_fail(ctx, SVO_ERR_ARG, "frame must be a whole number of tiles");
+    if (tile_stride == 0) return svo_fail(ctx, SVO_ERR_ARG, "tile_stride must be >= 1");
     uint32_t tiles_x = width / tile_w, tiles = tiles_x * (height / tile_h);
     work = svo::WorkDesc{};
     work.mode = 1;
@@ -453,19 +433,19 @@ int make_tiles_work(svo_ctx *ctx, uint32_t width, uint32_t height, uint32_t tile
     work.first_tile = first_tile;
     work.tile_stride = tile_stride;
     uint64_t items = (uint64_t)work.n_rects * work.bprect * 64u;
-    if (items > (1u << 26)) return fail(ctx, SVO_ERR_ARG, "too many pixels for one call");
+    if (items > (1u << 26)) return svo_fail(ctx, SVO_ERR_ARG, "too many pixels for one call");
     work.n_items = (uint32_t)items;
     return SVO_OK;
 }
 
 int make_rect_work(svo_ctx *ctx, uint32_t width, uint32_t height, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h,
                    svo::WorkDesc &work) {
-    if (!ctx->have_uniforms) return fail(ctx, SVO_ERR_STATE, "svo_set_uniforms not called");
+    if (!ctx->have_uniforms) return svo_fail(ctx, SVO_ERR_STATE, "svo_set_uniforms not called");
     if ((float)width != ctx->uniforms.dimensions[0] || (float)height != ctx->uniforms.dimensions[1])
-        return fail(ctx, SVO_ERR_ARG, "width/height differ from uniforms.dimensions");
+        return svo_fail(ctx, SVO_ERR_ARG, "width/height differ from uniforms.dimensions");
     if (w == 0 || h == 0 || x0 + (uint64_t)w > width || y0 + (uint64_t)h > height)
-        return fail(ctx, SVO_ERR_ARG, "tile rectangle outside the frame");
-    if ((uint64_t)w * h > (1u << 26)) return fail(ctx, SVO_ERR_ARG, "tile too large");
+        return svo_fail(ctx, SVO_ERR_ARG, "tile rectangle outside the frame");
+    if ((uint64_t)w * h > (1u << 26)) return svo_fail(ctx, SVO_ERR_ARG, "tile too large");
     work = svo::WorkDesc{};
     work.mode = 0;
     work.x0 = x0; work.y0 = y0;
@@ -473,16 +453,6 @@ int make_rect_work(svo_ctx *ctx, uint32_t width, uint32_t height, uint32_t x0, u
     work.n_rects = 1;
     work.tiles_x = 1;
     work.n_items = work.bprect * 64u;
-    return SVO_OK;
-}
-
-int ensure_stage(svo_ctx *ctx, size_t bytes) {
-    if (ctx->stage_bytes >= bytes) return SVO_OK;
-    if (ctx->stage) (void)hipFree(ctx->stage);
-    ctx->stage = nullptr;
-    ctx->stage_bytes = 0;
-    HIP_TRY(ctx, hipMalloc(&ctx->stage, bytes));
-    ctx->stage_bytes = bytes;
     return SVO_OK;
 }
 
@@ -594,9 +564,9 @@ int svo_ctx_destroy(svo_ctx *ctx) {
     (void)hipSetDevice(ctx->device);
     if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
     svo_comm_release(ctx);
-    svo_proc_release(ctx);
-    svo_build_release(ctx);
-    svo_adapt_release(ctx);
+    ctx->proc.reset();
+    ctx->build.reset();
+    ctx->adapt.reset();
     release_store(ctx);
     if (ctx->top_table) (void)hipFree(ctx->top_table);
     if (ctx->status) (void)hipFree(ctx->status);
@@ -625,11 +595,11 @@ int svo_set_option(svo_ctx *ctx, int option, int64_t value) {
     if (!ctx) return SVO_ERR_ARG;
     switch (option) {
         case SVO_OPT_VARIANT:
-            if (value != SVO_VARIANT_RESTART && value != SVO_VARIANT_STACK) return fail(ctx, SVO_ERR_ARG, "unknown variant");
+            if (value != SVO_VARIANT_RESTART && value != SVO_VARIANT_STACK) return svo_fail(ctx, SVO_ERR_ARG, "unknown variant");
             ctx->variant = (int)value;
             return SVO_OK;
         case SVO_OPT_TIMING: {
-            if (value < 0 || value > 65536) return fail(ctx, SVO_ERR_ARG, "timing ring size out of range");
+            if (value < 0 || value > 65536) return svo_fail(ctx, SVO_ERR_ARG, "timing ring size out of range");
             int rc = bind(ctx);
             if (rc) return rc;
             HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
@@ -643,46 +613,46 @@ int svo_set_option(svo_ctx *ctx, int option, int64_t value) {
             return SVO_OK;
         }
         case SVO_OPT_GRID_BLOCKS:
-            if (value < 0 || value > 65535) return fail(ctx, SVO_ERR_ARG, "grid_blocks out of range");
+            if (value < 0 || value > 65535) return svo_fail(ctx, SVO_ERR_ARG, "grid_blocks out of range");
             ctx->grid_blocks = (int)value;
             return SVO_OK;
         case SVO_OPT_REFILL_MIN:
-            if (value < 1 || value > 64) return fail(ctx, SVO_ERR_ARG, "refill_min must be 1..64");
+            if (value < 1 || value > 64) return svo_fail(ctx, SVO_ERR_ARG, "refill_min must be 1..64");
             ctx->refill_min = (uint32_t)value;
             return SVO_OK;
         case SVO_OPT_SCAN_CLEARS_COUNTERS:
             ctx->scan_clears = value != 0;
             return SVO_OK;
         case SVO_OPT_FUSED_SHADOWS:
-            if (value < 0 || value > 2) return fail(ctx, SVO_ERR_ARG, "fused shadows: 0 (off), 1 (on) or 2 (automatic)");
+            if (value < 0 || value > 2) return svo_fail(ctx, SVO_ERR_ARG, "fused shadows: 0 (off), 1 (on) or 2 (automatic)");
             ctx->fused_shadows = (int)value;
             return SVO_OK;
         case SVO_OPT_STRIP_ITEMS:
-            if (value < 64 || value > 2048 || (value & 63)) return fail(ctx, SVO_ERR_ARG, "strip_items must be a multiple of 64 in [64, 2048]");
+            if (value < 64 || value > 2048 || (value & 63)) return svo_fail(ctx, SVO_ERR_ARG, "strip_items must be a multiple of 64 in [64, 2048]");
             ctx->strip_items = (uint32_t)value;
             return SVO_OK;
         case SVO_OPT_DYNAMIC_STRIPS:  // (strips are always claimed dynamically)
             return SVO_OK;
         case SVO_OPT_SCHEDULE:
-            if (value < 0 || value > 1024) return fail(ctx, SVO_ERR_ARG, "schedule period out of range");
+            if (value < 0 || value > 1024) return svo_fail(ctx, SVO_ERR_ARG, "schedule period out of range");
             ctx->schedule = value != 0;
             if (value) ctx->sched_period = (uint32_t)value;
             ctx->sched[0].state.valid = ctx->sched[1].state.valid = false;
             return SVO_OK;
         case SVO_OPT_TREE_DEPTH:
-            if (value < 1 || value > 31) return fail(ctx, SVO_ERR_ARG, "tree depth must be 1..31");
+            if (value < 1 || value > 31) return svo_fail(ctx, SVO_ERR_ARG, "tree depth must be 1..31");
             ctx->tree_depth = (uint32_t)value;  // (which kernel that means is decided per launch, see trace_launch)
             return SVO_OK;
         case SVO_OPT_SCHEDULE_MOTION:
             if (value < 0 || (value & 15) > 12 || ((value >> 8) & 15) > 4 || (value >> 12) > 80)
-                return fail(ctx, SVO_ERR_ARG, "schedule motion: class floor (0..12, 0 = off) | radius (0..4) << 8 | min_count (0..80) << 12");
+                return svo_fail(ctx, SVO_ERR_ARG, "schedule motion: class floor (0..12, 0 = off) | radius (0..4) << 8 | min_count (0..80) << 12");
             ctx->motion_floor = (uint32_t)value;
             return SVO_OK;
         case SVO_OPT_CAMERA_SHORTCUT:
             ctx->cam_shortcut = value != 0;
             return SVO_OK;
         case SVO_OPT_CULL:
-            if (value < 0 || value > 2) return fail(ctx, SVO_ERR_ARG, "cull: 0 (off), 1 (whenever the camera is outside the cube) or 2 (automatic)");
+            if (value < 0 || value > 2) return svo_fail(ctx, SVO_ERR_ARG, "cull: 0 (off), 1 (whenever the camera is outside the cube) or 2 (automatic)");
             ctx->cull_mode = (int)value;
             return SVO_OK;
         case SVO_OPT_PAIR_TABLE:  // (the table left the library in round 3)
@@ -691,14 +661,14 @@ int svo_set_option(svo_ctx *ctx, int option, int64_t value) {
             ctx->debug_buf = (uint32_t *)(uintptr_t)value;  // device pointer, 64 B per wave of the grid; 0 = off
             return SVO_OK;
         case SVO_OPT_BLOCK_SHAPE:
-            if (value < 0 || value > 6) return fail(ctx, SVO_ERR_ARG, "block width log2 must be 0..6");
+            if (value < 0 || value > 6) return svo_fail(ctx, SVO_ERR_ARG, "block width log2 must be 0..6");
             ctx->block_w_log2 = (uint32_t)value;
             return SVO_OK;
         case SVO_OPT_PRIO_STEPS:
-            if (value < 0 || value > 255) return fail(ctx, SVO_ERR_ARG, "prio_steps must be 0..255");
+            if (value < 0 || value > 255) return svo_fail(ctx, SVO_ERR_ARG, "prio_steps must be 0..255");
             return SVO_OK;  // (no longer used)
         default:
-            return fail(ctx, SVO_ERR_ARG, "unknown option");
+            return svo_fail(ctx, SVO_ERR_ARG, "unknown option");
     }
 }
 
@@ -715,13 +685,13 @@ int svo_sync(svo_ctx *ctx) {
     HIP_TRY(ctx, hipMemcpy(&st, ctx->status, sizeof(st), hipMemcpyDeviceToHost));
     if (st & 2u) {
         HIP_TRY(ctx, hipMemset(ctx->status, 0, sizeof(uint32_t)));
-        return fail(ctx, SVO_ERR_STATE, "fused shadow ray outside the range of the fast arithmetic (set SVO_OPT_FUSED_SHADOWS to 0)");
+        return svo_fail(ctx, SVO_ERR_STATE, "fused shadow ray outside the range of the fast arithmetic (set SVO_OPT_FUSED_SHADOWS to 0)");
     }
     if (st & 1u) {
         HIP_TRY(ctx, hipMemset(ctx->status, 0, sizeof(uint32_t)));
-        return fail(ctx, SVO_ERR_STATE,
-                    "octree deeper than SVO_OPT_TREE_DEPTH declares (the frame's records are not valid); "
-                    "raise SVO_OPT_TREE_DEPTH (above 22: the general kernel) or use SVO_VARIANT_RESTART");
+        return svo_fail(ctx, SVO_ERR_STATE,
+                        "octree deeper than SVO_OPT_TREE_DEPTH declares (the frame's records are not valid); "
+                        "raise SVO_OPT_TREE_DEPTH (above 22: the general kernel) or use SVO_VARIANT_RESTART");
     }
     return SVO_OK;
 }
@@ -729,7 +699,7 @@ int svo_sync(svo_ctx *ctx) {
 int svo_nodes_alloc(svo_ctx *ctx, size_t capacity_words) {
     if (!ctx) return SVO_ERR_ARG;
     if (capacity_words < 8 || capacity_words > (size_t)SVO_VOXEL_OFFSET)
-        return fail(ctx, SVO_ERR_ARG, "capacity_words must be in [8, 2^27]");
+        return svo_fail(ctx, SVO_ERR_ARG, "capacity_words must be in [8, 2^27]");
     int rc = bind(ctx);
     if (rc) return rc;
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
@@ -739,7 +709,7 @@ int svo_nodes_alloc(svo_ctx *ctx, size_t capacity_words) {
     svo_node_store *st = new (std::nothrow) svo_node_store();
     if (!st) {
         (void)hipFree(words);
-        return fail(ctx, SVO_ERR_HIP, "out of host memory");
+        return svo_fail(ctx, SVO_ERR_HIP, "out of host memory");
     }
     st->device = ctx->device;
     st->nodes = words;
@@ -754,13 +724,13 @@ int svo_nodes_alloc(svo_ctx *ctx, size_t capacity_words) {
 int svo_nodes_bind_device(svo_ctx *ctx, uint32_t *device_words, size_t capacity_words) {
     if (!ctx || !device_words) return SVO_ERR_ARG;
     if (capacity_words < 8 || capacity_words > (size_t)SVO_VOXEL_OFFSET)
-        return fail(ctx, SVO_ERR_ARG, "capacity_words must be in [8, 2^27]");
+        return svo_fail(ctx, SVO_ERR_ARG, "capacity_words must be in [8, 2^27]");
     int rc = bind(ctx);
     if (rc) return rc;
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     release_store(ctx);
     svo_node_store *st = new (std::nothrow) svo_node_store();
-    if (!st) return fail(ctx, SVO_ERR_HIP, "out of host memory");
+    if (!st) return svo_fail(ctx, SVO_ERR_HIP, "out of host memory");
     st->device = ctx->device;
     st->nodes = device_words;
     st->capacity = capacity_words;
@@ -771,8 +741,8 @@ int svo_nodes_bind_device(svo_ctx *ctx, uint32_t *device_words, size_t capacity_
 
 int svo_nodes_share(svo_ctx *ctx, svo_ctx *owner) {
     if (!ctx || !owner) return SVO_ERR_ARG;
-    if (!owner->store) return fail(ctx, SVO_ERR_STATE, "the owner has no node buffer (svo_nodes_alloc / svo_nodes_bind_device)");
-    if (owner->device != ctx->device) return fail(ctx, SVO_ERR_ARG, "contexts on different devices cannot share a node buffer");
+    if (!owner->store) return svo_fail(ctx, SVO_ERR_STATE, "the owner has no node buffer (svo_nodes_alloc / svo_nodes_bind_device)");
+    if (owner->device != ctx->device) return svo_fail(ctx, SVO_ERR_ARG, "contexts on different devices cannot share a node buffer");
     if (ctx->store == owner->store) return SVO_OK;
     int rc = bind(ctx);
     if (rc) return rc;
@@ -785,7 +755,7 @@ int svo_nodes_share(svo_ctx *ctx, svo_ctx *owner) {
 
 int svo_nodes_invalidate(svo_ctx *ctx) {
     if (!ctx) return SVO_ERR_ARG;
-    if (!ctx->store) return fail(ctx, SVO_ERR_STATE, "svo_nodes_alloc / svo_nodes_bind_device not called");
+    if (!ctx->store) return svo_fail(ctx, SVO_ERR_STATE, "svo_nodes_alloc / svo_nodes_bind_device not called");
     int rc = bind(ctx);
     if (rc) return rc;
     return note_write(ctx, true);
@@ -793,9 +763,9 @@ int svo_nodes_invalidate(svo_ctx *ctx) {
 
 int svo_nodes_write(svo_ctx *ctx, size_t word_offset, const uint32_t *host_words, size_t n) {
     if (!ctx || (!host_words && n)) return SVO_ERR_ARG;
-    if (!ctx->nodes) return fail(ctx, SVO_ERR_STATE, "svo_nodes_alloc not called");
+    if (!ctx->nodes) return svo_fail(ctx, SVO_ERR_STATE, "svo_nodes_alloc not called");
     if (word_offset > ctx->capacity || n > ctx->capacity - word_offset)
-        return fail(ctx, SVO_ERR_ARG, "write past the node buffer capacity");
+        return svo_fail(ctx, SVO_ERR_ARG, "write past the node buffer capacity");
     int rc = bind(ctx);
     if (rc) return rc;
     if (n) {
@@ -809,15 +779,15 @@ int svo_nodes_write(svo_ctx *ctx, size_t word_offset, const uint32_t *host_words
 
 int svo_nodes_scatter(svo_ctx *ctx, const uint32_t *indices, const uint32_t *host_words, size_t n) {
     if (!ctx || ((!indices || !host_words) && n)) return SVO_ERR_ARG;
-    if (!ctx->nodes) return fail(ctx, SVO_ERR_STATE, "svo_nodes_alloc not called");
-    if (n > (1u << 28)) return fail(ctx, SVO_ERR_ARG, "too many words for one scatter");
+    if (!ctx->nodes) return svo_fail(ctx, SVO_ERR_STATE, "svo_nodes_alloc not called");
+    if (n > (1u << 28)) return svo_fail(ctx, SVO_ERR_ARG, "too many words for one scatter");
     for (size_t i = 0; i < n; i++)
-        if (indices[i] >= ctx->capacity) return fail(ctx, SVO_ERR_ARG, "scatter index past the node buffer capacity");
+        if (indices[i] >= ctx->capacity) return svo_fail(ctx, SVO_ERR_ARG, "scatter index past the node buffer capacity");
     int rc = bind(ctx);
     if (rc || n == 0) return rc;
     rc = order_after_last_write(ctx);  // a shared store: writes land in the order they were issued, whichever context issued them
     if (rc) return rc;
-    rc = ensure_dev(ctx, &ctx->scatter_buf, &ctx->scatter_bytes, 2 * n * sizeof(uint32_t));
+    rc = svo_grow(ctx, &ctx->scatter_bytes, 2 * n * sizeof(uint32_t), &ctx->scatter_buf);
     if (rc) return rc;
     uint32_t *d_idx = (uint32_t *)ctx->scatter_buf, *d_val = d_idx + n;
     HIP_TRY(ctx, hipMemcpyAsync(d_idx, indices, n * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
@@ -828,9 +798,9 @@ int svo_nodes_scatter(svo_ctx *ctx, const uint32_t *indices, const uint32_t *hos
 
 int svo_nodes_read(svo_ctx *ctx, size_t word_offset, uint32_t *host_words, size_t n) {
     if (!ctx || (!host_words && n)) return SVO_ERR_ARG;
-    if (!ctx->nodes) return fail(ctx, SVO_ERR_STATE, "svo_nodes_alloc not called");
+    if (!ctx->nodes) return svo_fail(ctx, SVO_ERR_STATE, "svo_nodes_alloc not called");
     if (word_offset > ctx->capacity || n > ctx->capacity - word_offset)
-        return fail(ctx, SVO_ERR_ARG, "read past the node buffer capacity");
+        return svo_fail(ctx, SVO_ERR_ARG, "read past the node buffer capacity");
     int rc = bind(ctx);
     if (rc) return rc;
     if (n) {
@@ -870,14 +840,14 @@ int svo_render(svo_ctx *ctx, uint32_t width, uint32_t height, uint32_t x0, uint3
 int svo_render_host(svo_ctx *ctx, uint32_t width, uint32_t height, uint32_t x0, uint32_t y0, uint32_t tile_w,
                     uint32_t tile_h, svo_hit *hits_out, uint32_t *rgba_out) {
     if (!ctx) return SVO_ERR_ARG;
-    if (!hits_out && !rgba_out) return fail(ctx, SVO_ERR_ARG, "both hits_out and rgba_out are NULL");
+    if (!hits_out && !rgba_out) return svo_fail(ctx, SVO_ERR_ARG, "both hits_out and rgba_out are NULL");
     svo::WorkDesc work;
     int rc = make_rect_work(ctx, width, height, x0, y0, tile_w, tile_h, work);
     if (rc) return rc;
     size_t n = (size_t)tile_w * tile_h;
     rc = bind(ctx);
     if (rc) return rc;
-    rc = ensure_stage(ctx, n * (sizeof(svo_hit) + sizeof(uint32_t)));
+    rc = svo_grow(ctx, &ctx->stage_bytes, n * (sizeof(svo_hit) + sizeof(uint32_t)), &ctx->stage);
     if (rc) return rc;
     svo_hit *dh = (svo_hit *)ctx->stage;
     uint32_t *dc = (uint32_t *)((char *)ctx->stage + n * sizeof(svo_hit));
@@ -920,10 +890,10 @@ static int assemble_common(svo_ctx *ctx, const void *gathered, bool packed, uint
                            uint32_t height, uint32_t tile_w, uint32_t tile_h, svo_hit *frame_out) {
     if (!ctx || !gathered || !frame_out) return SVO_ERR_ARG;
     if (world == 0 || tile_w == 0 || tile_h == 0 || width % tile_w || height % tile_h)
-        return fail(ctx, SVO_ERR_ARG, "frame must be a whole number of tiles");
+        return svo_fail(ctx, SVO_ERR_ARG, "frame must be a whole number of tiles");
     const uint64_t tiles = (uint64_t)(width / tile_w) * (height / tile_h);
-    if ((uint64_t)n_pad * world < tiles) return fail(ctx, SVO_ERR_ARG, "gathered buffer holds fewer tiles than the frame");
-    if ((uint64_t)width * height > (1u << 26)) return fail(ctx, SVO_ERR_ARG, "frame too large");
+    if ((uint64_t)n_pad * world < tiles) return svo_fail(ctx, SVO_ERR_ARG, "gathered buffer holds fewer tiles than the frame");
+    if ((uint64_t)width * height > (1u << 26)) return svo_fail(ctx, SVO_ERR_ARG, "frame too large");
     int rc = bind(ctx);
     if (rc) return rc;
     HIP_TRY(ctx, svo::launch_assemble_tiles(gathered, packed, frame_out, world, n_pad, width, height, tile_w, tile_h, ctx->stream));
@@ -944,10 +914,10 @@ int svo_assemble_tiles_rgba(svo_ctx *ctx, const uint32_t *gathered_rgba, uint32_
                             uint32_t tile_w, uint32_t tile_h, uint32_t *rgba_frame_out) {
     if (!ctx || !gathered_rgba || !rgba_frame_out) return SVO_ERR_ARG;
     if (world == 0 || tile_w == 0 || tile_h == 0 || width % tile_w || height % tile_h)
-        return fail(ctx, SVO_ERR_ARG, "frame must be a whole number of tiles");
+        return svo_fail(ctx, SVO_ERR_ARG, "frame must be a whole number of tiles");
     const uint64_t tiles = (uint64_t)(width / tile_w) * (height / tile_h);
-    if ((uint64_t)n_pad * world < tiles) return fail(ctx, SVO_ERR_ARG, "gathered buffer holds fewer tiles than the frame");
-    if ((uint64_t)width * height > (1u << 26)) return fail(ctx, SVO_ERR_ARG, "frame too large");
+    if ((uint64_t)n_pad * world < tiles) return svo_fail(ctx, SVO_ERR_ARG, "gathered buffer holds fewer tiles than the frame");
+    if ((uint64_t)width * height > (1u << 26)) return svo_fail(ctx, SVO_ERR_ARG, "frame too large");
     int rc = bind(ctx);
     if (rc) return rc;
     HIP_TRY(ctx, svo::launch_assemble_tiles_rgba(gathered_rgba, rgba_frame_out, world, n_pad, width, height, tile_w, tile_h, ctx->stream));
@@ -956,7 +926,7 @@ int svo_assemble_tiles_rgba(svo_ctx *ctx, const uint32_t *gathered_rgba, uint32_
 
 int svo_pack_records(svo_ctx *ctx, const svo_hit *records, size_t n, uint32_t *wire_out) {
     if (!ctx || ((!records || !wire_out) && n)) return SVO_ERR_ARG;
-    if (n > (1u << 26)) return fail(ctx, SVO_ERR_ARG, "too many records for one call");
+    if (n > (1u << 26)) return svo_fail(ctx, SVO_ERR_ARG, "too many records for one call");
     int rc = bind(ctx);
     if (rc) return rc;
     HIP_TRY(ctx, svo::launch_pack_records(records, wire_out, (uint32_t)n, ctx->stream));
@@ -965,13 +935,13 @@ int svo_pack_records(svo_ctx *ctx, const svo_hit *records, size_t n, uint32_t *w
 
 int svo_trace_rays(svo_ctx *ctx, const float *rays, size_t n_rays, svo_hit *hits_out) {
     if (!ctx || (!rays && n_rays)) return SVO_ERR_ARG;
-    if (n_rays > (1u << 26)) return fail(ctx, SVO_ERR_ARG, "too many rays for one call");
+    if (n_rays > (1u << 26)) return svo_fail(ctx, SVO_ERR_ARG, "too many rays for one call");
     return trace_common(ctx, ray_work(n_rays), rays, hits_out, nullptr);
 }
 
 int svo_last_render_ms(svo_ctx *ctx, float *ms) {
     if (!ctx || !ms) return SVO_ERR_ARG;
-    if (!ctx->ev_slots || !ctx->ev_count) return fail(ctx, SVO_ERR_STATE, "no timed launch (set SVO_OPT_TIMING first)");
+    if (!ctx->ev_slots || !ctx->ev_count) return svo_fail(ctx, SVO_ERR_STATE, "no timed launch (set SVO_OPT_TIMING first)");
     int rc = bind(ctx);
     if (rc) return rc;
     const size_t slot = (ctx->ev_count - 1) % ctx->ev_slots;
@@ -983,7 +953,7 @@ int svo_last_render_ms(svo_ctx *ctx, float *ms) {
 int svo_timing_collect(svo_ctx *ctx, float *ms_out, size_t cap, size_t *n_out) {
     if (!ctx || !n_out || (!ms_out && cap)) return SVO_ERR_ARG;
     *n_out = 0;
-    if (!ctx->ev_slots) return fail(ctx, SVO_ERR_STATE, "timing is off (set SVO_OPT_TIMING first)");
+    if (!ctx->ev_slots) return svo_fail(ctx, SVO_ERR_STATE, "timing is off (set SVO_OPT_TIMING first)");
     int rc = bind(ctx);
     if (rc) return rc;
     size_t n = ctx->ev_count < ctx->ev_slots ? ctx->ev_count : ctx->ev_slots;
@@ -1001,8 +971,8 @@ int svo_timing_collect(svo_ctx *ctx, float *ms_out, size_t cap, size_t *n_out) {
 
 int svo_diag_gather(svo_ctx *ctx, uint32_t stride_bytes, uint32_t n_loads) {
     if (!ctx || stride_bytes < 4 || (stride_bytes & 3)) return SVO_ERR_ARG;
-    if (!ctx->nodes) return fail(ctx, SVO_ERR_STATE, "svo_nodes_alloc not called");
-    if ((uint64_t)n_loads * (stride_bytes / 4) > ctx->capacity) return fail(ctx, SVO_ERR_ARG, "pattern exceeds the node buffer");
+    if (!ctx->nodes) return svo_fail(ctx, SVO_ERR_STATE, "svo_nodes_alloc not called");
+    if ((uint64_t)n_loads * (stride_bytes / 4) > ctx->capacity) return svo_fail(ctx, SVO_ERR_ARG, "pattern exceeds the node buffer");
     int rc = bind(ctx);
     if (rc) return rc;
     HIP_TRY(ctx, svo::launch_diag_gather(ctx->nodes, (uint32_t)ctx->capacity, stride_bytes / 4, n_loads, ctx->status, ctx->stream));
@@ -1012,8 +982,8 @@ int svo_diag_gather(svo_ctx *ctx, uint32_t stride_bytes, uint32_t n_loads) {
 int svo_diag_strip_classes(svo_ctx *ctx, uint8_t *host_out, size_t n_strips) {
     if (!ctx || (!host_out && n_strips)) return SVO_ERR_ARG;
     const svo_ctx::Sched &sc = ctx->sched[0];
-    if (!sc.buf.cls_now || !sc.state.order_filtered) return fail(ctx, SVO_ERR_STATE, "the last pixel frame was traced without a culling pass");
-    if (n_strips > sc.cap) return fail(ctx, SVO_ERR_ARG, "more strips than the last frame had");
+    if (!sc.buf.cls_now || !sc.state.order_filtered) return svo_fail(ctx, SVO_ERR_STATE, "the last pixel frame was traced without a culling pass");
+    if (n_strips > sc.cap) return svo_fail(ctx, SVO_ERR_ARG, "more strips than the last frame had");
     int rc = bind(ctx);
     if (rc || n_strips == 0) return rc;
     HIP_TRY(ctx, hipMemcpyAsync(host_out, sc.buf.cls_now, n_strips, hipMemcpyDeviceToHost, ctx->stream));
@@ -1023,7 +993,7 @@ int svo_diag_strip_classes(svo_ctx *ctx, uint8_t *host_out, size_t n_strips) {
 
 int svo_scan_dispatch(svo_ctx *ctx, uint32_t node_length) {
     if (!ctx) return SVO_ERR_ARG;
-    if (!ctx->nodes) return fail(ctx, SVO_ERR_STATE, "svo_nodes_alloc not called");
+    if (!ctx->nodes) return svo_fail(ctx, SVO_ERR_STATE, "svo_nodes_alloc not called");
     int rc = bind(ctx);
     if (rc) return rc;
     if (!ctx->scan_sub) {
@@ -1047,7 +1017,7 @@ int svo_scan_dispatch(svo_ctx *ctx, uint32_t node_length) {
 
 int svo_scan_read(svo_ctx *ctx, uint32_t *sub, uint32_t *n_sub, uint32_t *unsub, uint32_t *n_unsub, size_t capacity) {
     if (!ctx || !sub || !unsub || !n_sub || !n_unsub || capacity < 1) return SVO_ERR_ARG;
-    if (!ctx->scan_sub) return fail(ctx, SVO_ERR_STATE, "svo_scan_dispatch not called");
+    if (!ctx->scan_sub) return svo_fail(ctx, SVO_ERR_STATE, "svo_scan_dispatch not called");
     int rc = bind(ctx);
     if (rc) return rc;
     uint32_t counts[2] = {0, 0};

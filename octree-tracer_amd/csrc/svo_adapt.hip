@@ -18,7 +18,6 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <chrono>
 #include <cstring>
 #include <string>
 #include <vector>
@@ -308,38 +307,14 @@ __global__ __launch_bounds__(kThreads) void unsub_apply_kernel(Tree t, const uin
     if ((res[k] & 0xFFu) == kDone && n_holes + rank[k] < hole_cap) holes[n_holes + rank[k]] = grp[k];
 }
 
-int fail(svo_ctx *ctx, int code, const std::string &what) { return svo_fail(ctx, code, what.c_str()); }
-
-#define HIP_TRY(ctx, expr)                                          \
-    do {                                                            \
-        hipError_t e_ = (expr);                                     \
-        if (e_ != hipSuccess) return svo_fail_hip(ctx, e_, #expr); \
-    } while (0)
-
-uint32_t grid_for(uint64_t n) { return (uint32_t)((n + kThreads - 1) / kThreads); }
-
-double now_ms() {
-    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
-}
-
-template <typename T>
-int grow(svo_ctx *ctx, T **p, size_t *have, size_t want) {
-    if (*have >= want) return SVO_OK;
-    if (*p) (void)hipFree(*p);
-    *p = nullptr;
-    *have = 0;
-    HIP_TRY(ctx, hipMalloc((void **)p, want * sizeof(T)));
-    *have = want;
-    return SVO_OK;
-}
-
 }  // namespace
 
 struct svo_adapt_state {
     svo_world *world = nullptr;
     uint32_t *nodes_at_attach = nullptr;  // the node buffer the state belongs to
-    size_t capacity = 0;
-    float *pos = nullptr;                 // 3 * capacity
+    size_t capacity = 0;                  // the node buffer's at attach
+    float *pos = nullptr;                 // 3 per node
+    size_t pos_items = 0;
     uint32_t *holes = nullptr;
     size_t hole_cap = 0;
     uint32_t n_holes = 0;
@@ -354,8 +329,10 @@ struct svo_adapt_state {
     size_t rm_cap = 0;
     // per-entry workspace
     uint32_t *list[2] = {};  // sorted subdivide / unsubdivide lists
-    uint32_t *res = nullptr, *src = nullptr, *val = nullptr, *flag = nullptr, *req = nullptr;
+    uint32_t *res = nullptr, *src = nullptr, *val = nullptr, *flag = nullptr;
     size_t items = 0;
+    uint32_t *req = nullptr;  // 2 per entry
+    size_t req_items = 0;
     uint32_t *bits = nullptr;
     size_t bit_words = 0;
     Status *st = nullptr, *st_host = nullptr;
@@ -364,7 +341,7 @@ struct svo_adapt_state {
     hipEvent_t ev[4] = {};  // start, sorted, subdivided, unsubdivided
     float ms[SVO_ADAPT_TIMES] = {};
 
-    void release() {
+    ~svo_adapt_state() {
         for (void *p : {(void *)pos, (void *)holes, (void *)wn, (void *)tab_dev, (void *)rm, (void *)list[0], (void *)list[1],
                         (void *)res, (void *)src, (void *)val, (void *)flag, (void *)req, (void *)bits, (void *)st})
             if (p) (void)hipFree(p);
@@ -375,21 +352,14 @@ struct svo_adapt_state {
     }
 };
 
-void svo_adapt_release(svo_ctx *ctx) {
-    if (!ctx->adapt) return;
-    ctx->adapt->release();
-    delete ctx->adapt;
-    ctx->adapt = nullptr;
-}
-
 namespace {
 
 // the table (and the rank array sized to it) to the device; blocking, so the host vector may change afterwards
 int upload_table(svo_ctx *ctx) {
-    svo_adapt_state *a = ctx->adapt;
-    int rc = grow(ctx, &a->tab_dev, &a->tab_cap, std::max<size_t>(a->tab.size(), 16));
+    svo_adapt_state *a = ctx->adapt.get();
+    int rc = svo_grow(ctx, &a->tab_cap, std::max<size_t>(a->tab.size(), 16), &a->tab_dev);
     if (rc) return rc;
-    if ((rc = grow(ctx, &a->rm, &a->rm_cap, std::max<size_t>(a->tab.size(), 16)))) return rc;
+    if ((rc = svo_grow(ctx, &a->rm_cap, std::max<size_t>(a->tab.size(), 16), &a->rm))) return rc;
     if (!a->tab.empty())
         HIP_TRY(ctx, hipMemcpyAsync(a->tab_dev, a->tab.data(), a->tab.size() * sizeof(Chunk), hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
@@ -411,21 +381,17 @@ int put_chunk_nodes(svo_ctx *ctx, const svo_cpu_octree *t, uint32_t at, size_t c
 
 // The whole mirror from the host world (attach, or a load that does not fit): every chunk, compact, twice the room.
 int rebuild_mirror(svo_ctx *ctx, size_t extra) {
-    svo_adapt_state *a = ctx->adapt;
+    svo_adapt_state *a = ctx->adapt.get();
     std::vector<uint32_t> ids(svo_world_chunk_ids(a->world, nullptr, 0));
     svo_world_chunk_ids(a->world, ids.data(), ids.size());
     std::vector<Chunk> old;
     old.swap(a->tab);
     size_t total = 0;
     for (uint32_t id : ids) total += svo_cpu_octree_len(svo_world_chunk(a->world, id));
-    if (total + extra >= kNone) return fail(ctx, SVO_ERR_CAP, "the world mirror would pass 2^32 nodes");
+    if (total + extra >= kNone) return svo_fail(ctx, SVO_ERR_CAP, "the world mirror would pass 2^32 nodes");
     if (a->wn_cap < total + extra) {
-        if (a->wn) (void)hipFree(a->wn);
-        a->wn = nullptr;
-        a->wn_cap = 0;
-        const size_t want = std::min<size_t>(2 * (total + extra) + 4096, kNone - 1);
-        HIP_TRY(ctx, hipMalloc((void **)&a->wn, want * sizeof(uint2)));
-        a->wn_cap = want;
+        const int rc = svo_grow(ctx, &a->wn_cap, std::min<size_t>(2 * (total + extra) + 4096, kNone - 1), &a->wn);
+        if (rc) return rc;
     }
     a->wn_used = 0;
     for (uint32_t id : ids) {
@@ -447,7 +413,7 @@ int rebuild_mirror(svo_ctx *ctx, size_t extra) {
 
 // Chunk `id` was just loaded into the host world by entry `rank`: into the mirror and the table.
 int mirror_add(svo_ctx *ctx, uint32_t id, uint32_t rank) {
-    svo_adapt_state *a = ctx->adapt;
+    svo_adapt_state *a = ctx->adapt.get();
     const svo_cpu_octree *t = svo_world_chunk(a->world, id);
     const size_t cnt = svo_cpu_octree_len(t);
     if (a->wn_used + cnt > a->wn_cap) {
@@ -477,12 +443,12 @@ const char *code_text(uint32_t code) {
 }
 
 int entry_fail(svo_ctx *ctx, int code, uint32_t packed, const char *pass) {
-    return fail(ctx, code, std::string(pass) + " entry " + std::to_string(packed >> 8) + ": " + code_text(packed & 0xFFu) +
-                               (code == SVO_ERR_STATE ? " (this list needs the sequential host path, svo_adaptive_subdivide)" : ""));
+    return svo_fail(ctx, code, std::string(pass) + " entry " + std::to_string(packed >> 8) + ": " + code_text(packed & 0xFFu) +
+                                   (code == SVO_ERR_STATE ? " (this list needs the sequential host path, svo_adaptive_subdivide)" : ""));
 }
 
 int read_status(svo_ctx *ctx, const uint32_t *total_dev) {
-    svo_adapt_state *a = ctx->adapt;
+    svo_adapt_state *a = ctx->adapt.get();
     if (total_dev) HIP_TRY(ctx, hipMemcpyAsync(&a->st->total, total_dev, sizeof(uint32_t), hipMemcpyDeviceToDevice, ctx->stream));
     HIP_TRY(ctx, hipMemcpyAsync(a->st_host, a->st, sizeof(Status), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
@@ -501,15 +467,15 @@ Tree tree_of(svo_ctx *ctx) { return Tree{ctx->nodes, ctx->adapt->pos, ctx->adapt
 
 // ---- the subdivide pass over the sorted list a->list[0][0, n) ----
 int subdivide_pass(svo_ctx *ctx, uint32_t n, svo_adaptive_result *out) {
-    svo_adapt_state *a = ctx->adapt;
-    const uint32_t *list = a->list[0];
+    svo_adapt_state *a = ctx->adapt.get();
+    const uint32_t *list = a->list[0], grid = svo_div_up(n, kThreads);
     int rc;
     // plan until no entry asks for a chunk that is not in the table (every load makes a new chunk resident for the
     // entries after its loader, whose walks may then reach further)
     for (int round = 0;; round++) {
         if ((rc = clear_status(ctx))) return rc;
-        sub_plan_kernel<<<grid_for(n), kThreads, 0, ctx->stream>>>(tree_of(ctx), list, n, a->tab_dev, (uint32_t)a->tab.size(), a->wn,
-                                                                   a->res, a->src, a->flag, a->req, a->st);
+        sub_plan_kernel<<<grid, kThreads, 0, ctx->stream>>>(tree_of(ctx), list, n, a->tab_dev, (uint32_t)a->tab.size(), a->wn,
+                                                            a->res, a->src, a->flag, a->req, a->st);
         HIP_TRY(ctx, hipGetLastError());
         if ((rc = read_status(ctx, nullptr))) return rc;
         const Status s = *a->st_host;
@@ -518,7 +484,7 @@ int subdivide_pass(svo_ctx *ctx, uint32_t n, svo_adaptive_result *out) {
             if (s.err != kNone) return entry_fail(ctx, SVO_ERR_STATE, s.err, "subdivide");
             break;
         }
-        if (round >= 64) return fail(ctx, SVO_ERR_STATE, "subdivide: chunk loads do not settle");
+        if (round >= 64) return svo_fail(ctx, SVO_ERR_STATE, "subdivide: chunk loads do not settle");
         std::vector<uint32_t> req(2 * s.n_req);
         HIP_TRY(ctx, hipMemcpy(req.data(), a->req, req.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
         std::vector<std::pair<uint32_t, uint32_t>> first;  // (id, lowest rank)
@@ -541,22 +507,22 @@ int subdivide_pass(svo_ctx *ctx, uint32_t n, svo_adaptive_result *out) {
     HIP_TRY(ctx, hipMemsetAsync(a->flag + n, 0, sizeof(uint32_t), ctx->stream));
     if ((rc = svo_build_scan_u32(ctx, a->flag, n + 1))) return rc;
     if (a->n_holes)
-        sub_popped_kernel<<<grid_for(std::min(n, a->n_holes)), kThreads, 0, ctx->stream>>>(a->holes, a->n_holes, list, n, a->flag + n,
-                                                                                           a->st);
+        sub_popped_kernel<<<svo_div_up(std::min(n, a->n_holes), kThreads), kThreads, 0, ctx->stream>>>(a->holes, a->n_holes, list, n,
+                                                                                                       a->flag + n, a->st);
     HIP_TRY(ctx, hipGetLastError());
     if ((rc = read_status(ctx, a->flag + n))) return rc;
     const uint32_t done = a->st_host->total;
     if (a->st_host->popped_hit)
-        return fail(ctx, SVO_ERR_STATE, "subdivide: an entry lies in a hole group this pass reuses (this list needs the sequential host "
-                                        "path, svo_adaptive_subdivide)");
+        return svo_fail(ctx, SVO_ERR_STATE, "subdivide: an entry lies in a hole group this pass reuses (this list needs the sequential "
+                                            "host path, svo_adaptive_subdivide)");
     const uint32_t pops = std::min(done, a->n_holes);
     const uint64_t new_len = uint64_t(a->len) + 8ull * (done - pops);
     if (new_len > ctx->capacity || new_len > kVoxelOff)
-        return fail(ctx, SVO_ERR_CAP, "subdivide: " + std::to_string(done) + " subdivisions need " + std::to_string(new_len) +
-                                          " words, over the node buffer's capacity of " + std::to_string(ctx->capacity));
+        return svo_fail(ctx, SVO_ERR_CAP, "subdivide: " + std::to_string(done) + " subdivisions need " + std::to_string(new_len) +
+                                              " words, over the node buffer's capacity of " + std::to_string(ctx->capacity));
     if (done) {
-        sub_apply_kernel<<<grid_for(n), kThreads, 0, ctx->stream>>>(tree_of(ctx), list, n, a->res, a->src, a->flag, a->holes, a->n_holes,
-                                                                    a->wn, (uint32_t)ctx->capacity, a->st);
+        sub_apply_kernel<<<grid, kThreads, 0, ctx->stream>>>(tree_of(ctx), list, n, a->res, a->src, a->flag, a->holes, a->n_holes,
+                                                             a->wn, (uint32_t)ctx->capacity, a->st);
         HIP_TRY(ctx, hipGetLastError());
     }
     a->n_holes -= pops;
@@ -567,24 +533,24 @@ int subdivide_pass(svo_ctx *ctx, uint32_t n, svo_adaptive_result *out) {
 
 // ---- the unsubdivide pass over the sorted list a->list[1][0, n) ----
 int unsubdivide_pass(svo_ctx *ctx, uint32_t n, svo_adaptive_result *out) {
-    svo_adapt_state *a = ctx->adapt;
-    const uint32_t *list = a->list[1];
+    svo_adapt_state *a = ctx->adapt.get();
+    const uint32_t *list = a->list[1], grid = svo_div_up(n, kThreads);
     int rc;
     const size_t words = (a->len + 31) / 32;
-    if ((rc = grow(ctx, &a->bits, &a->bit_words, std::max<size_t>(words, 1)))) return rc;
+    if ((rc = svo_grow(ctx, &a->bit_words, std::max<size_t>(words, 1), &a->bits))) return rc;
     HIP_TRY(ctx, hipMemsetAsync(a->bits, 0, words * sizeof(uint32_t), ctx->stream));
     HIP_TRY(ctx, hipMemsetAsync(a->rm, 0xFF, a->rm_cap * sizeof(uint32_t), ctx->stream));
     if ((rc = clear_status(ctx))) return rc;
-    unsub_mark_kernel<<<grid_for(n), kThreads, 0, ctx->stream>>>(list, n, a->len, a->bits);
-    unsub_plan_kernel<<<grid_for(n), kThreads, 0, ctx->stream>>>(tree_of(ctx), list, n, a->bits, a->tab_dev, (uint32_t)a->tab.size(),
-                                                                 a->wn, a->res, a->val, a->src, a->flag, a->rm, a->st);
+    unsub_mark_kernel<<<grid, kThreads, 0, ctx->stream>>>(list, n, a->len, a->bits);
+    unsub_plan_kernel<<<grid, kThreads, 0, ctx->stream>>>(tree_of(ctx), list, n, a->bits, a->tab_dev, (uint32_t)a->tab.size(),
+                                                          a->wn, a->res, a->val, a->src, a->flag, a->rm, a->st);
     HIP_TRY(ctx, hipGetLastError());
     if ((rc = read_status(ctx, nullptr))) return rc;
     if (a->st_host->err != kNone) return entry_fail(ctx, SVO_ERR_STATE, a->st_host->err, "unsubdivide");
     const bool removals = a->st_host->removals != 0;
     if (removals) {
-        unsub_check_kernel<<<grid_for(n), kThreads, 0, ctx->stream>>>(tree_of(ctx), list, n, a->res, a->tab_dev, (uint32_t)a->tab.size(),
-                                                                      a->wn, a->rm, a->st);
+        unsub_check_kernel<<<grid, kThreads, 0, ctx->stream>>>(tree_of(ctx), list, n, a->res, a->tab_dev, (uint32_t)a->tab.size(),
+                                                               a->wn, a->rm, a->st);
         HIP_TRY(ctx, hipGetLastError());
     }
     HIP_TRY(ctx, hipMemsetAsync(a->flag + n, 0, sizeof(uint32_t), ctx->stream));
@@ -603,8 +569,8 @@ int unsubdivide_pass(svo_ctx *ctx, uint32_t n, svo_adaptive_result *out) {
         a->holes = bigger;
         a->hole_cap = cap;
     }
-    unsub_apply_kernel<<<grid_for(n), kThreads, 0, ctx->stream>>>(tree_of(ctx), list, n, a->res, a->val, a->src, a->flag, a->holes,
-                                                                  a->n_holes, (uint32_t)a->hole_cap);
+    unsub_apply_kernel<<<grid, kThreads, 0, ctx->stream>>>(tree_of(ctx), list, n, a->res, a->val, a->src, a->flag, a->holes,
+                                                           a->n_holes, (uint32_t)a->hole_cap);
     HIP_TRY(ctx, hipGetLastError());
     a->n_holes += done;
     out->n_unsub = done;
@@ -628,9 +594,9 @@ int unsubdivide_pass(svo_ctx *ctx, uint32_t n, svo_adaptive_result *out) {
 }
 
 int check_attached(svo_ctx *ctx) {
-    if (!ctx->adapt || !ctx->adapt->world) return fail(ctx, SVO_ERR_STATE, "svo_adaptive_attach not called");
+    if (!ctx->adapt || !ctx->adapt->world) return svo_fail(ctx, SVO_ERR_STATE, "svo_adaptive_attach not called");
     if (ctx->nodes != ctx->adapt->nodes_at_attach || ctx->capacity != ctx->adapt->capacity)
-        return fail(ctx, SVO_ERR_STATE, "the node buffer changed since svo_adaptive_attach: attach again");
+        return svo_fail(ctx, SVO_ERR_STATE, "the node buffer changed since svo_adaptive_attach: attach again");
     return SVO_OK;
 }
 
@@ -640,34 +606,29 @@ extern "C" {
 
 int svo_adaptive_attach(svo_ctx *ctx, svo_world *w, const svo_octree *o) {
     if (!ctx || !w || !o) return SVO_ERR_ARG;
-    if (!ctx->store || !ctx->nodes) return fail(ctx, SVO_ERR_STATE, "svo_nodes_alloc / svo_nodes_bind_device not called");
+    if (!ctx->store || !ctx->nodes) return svo_fail(ctx, SVO_ERR_STATE, "svo_nodes_alloc / svo_nodes_bind_device not called");
     if (!ctx->scan_clears)
-        return fail(ctx, SVO_ERR_STATE, "the device adaptive step needs SVO_OPT_SCAN_CLEARS_COUNTERS=1 (the scan resets the counters)");
+        return svo_fail(ctx, SVO_ERR_STATE, "the device adaptive step needs SVO_OPT_SCAN_CLEARS_COUNTERS=1 (the scan resets the counters)");
     const uint32_t *nodes;
     const float *pos;
     std::vector<uint32_t> holes;
     const size_t len = svo_octree_state(o, &nodes, &pos, holes);
-    if (len > ctx->capacity || len > kVoxelOff) return fail(ctx, SVO_ERR_CAP, "the octree is longer than the node buffer");
+    if (len > ctx->capacity || len > kVoxelOff) return svo_fail(ctx, SVO_ERR_CAP, "the octree is longer than the node buffer");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     if (!ctx->adapt) {
-        ctx->adapt = new svo_adapt_state();
-        svo_adapt_state *a = ctx->adapt;
+        ctx->adapt = svo_workspace_new<svo_adapt_state>();
+        svo_adapt_state *a = ctx->adapt.get();
         for (hipEvent_t &e : a->ev) HIP_TRY(ctx, hipEventCreate(&e));
         HIP_TRY(ctx, hipMalloc((void **)&a->st, sizeof(Status)));
         HIP_TRY(ctx, hipHostMalloc((void **)&a->st_host, sizeof(Status), hipHostMallocDefault));
         HIP_TRY(ctx, hipHostMalloc((void **)&a->counts_host, 2 * sizeof(uint32_t), hipHostMallocDefault));
     }
-    svo_adapt_state *a = ctx->adapt;
+    svo_adapt_state *a = ctx->adapt.get();
     a->world = nullptr;  // (attached only once everything is up)
     int rc;
-    if (a->capacity != ctx->capacity) {
-        if (a->pos) (void)hipFree(a->pos);
-        a->pos = nullptr;
-        a->capacity = 0;
-        HIP_TRY(ctx, hipMalloc((void **)&a->pos, 3 * ctx->capacity * sizeof(float)));
-        a->capacity = ctx->capacity;
-    }
-    if ((rc = grow(ctx, &a->holes, &a->hole_cap, std::max<size_t>(holes.size() + kListCap, ctx->capacity / 8 + 1)))) return rc;
+    if ((rc = svo_grow(ctx, &a->pos_items, 3 * ctx->capacity, &a->pos))) return rc;
+    a->capacity = ctx->capacity;
+    if ((rc = svo_grow(ctx, &a->hole_cap, std::max<size_t>(holes.size() + kListCap, ctx->capacity / 8 + 1), &a->holes))) return rc;
     // (the order behind the store's last write: the plan kernels read the words)
     if ((rc = svo_store_order_after_write(ctx))) return rc;
     if (len) HIP_TRY(ctx, hipMemcpyAsync(a->pos, pos, 3 * len * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
@@ -689,18 +650,18 @@ int svo_adaptive_attach(svo_ctx *ctx, svo_world *w, const svo_octree *o) {
 int svo_adaptive_step(svo_ctx *ctx, const uint32_t *d_sub, uint32_t n_sub, const uint32_t *d_unsub, uint32_t n_unsub,
                       svo_adaptive_result *out) {
     if (!ctx || !out) return SVO_ERR_ARG;
-    if ((d_sub == nullptr) != (d_unsub == nullptr)) return fail(ctx, SVO_ERR_ARG, "give both lists or neither");
+    if ((d_sub == nullptr) != (d_unsub == nullptr)) return svo_fail(ctx, SVO_ERR_ARG, "give both lists or neither");
     int rc = check_attached(ctx);
     if (rc) return rc;
-    svo_adapt_state *a = ctx->adapt;
+    svo_adapt_state *a = ctx->adapt.get();
     memset(out, 0, sizeof *out);
     a->removed.clear();
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const double t0 = now_ms();
+    const double t0 = svo_now_ms();
     if ((rc = svo_store_order_after_write(ctx))) return rc;
     HIP_TRY(ctx, hipEventRecord(a->ev[0], ctx->stream));
     if (!d_sub) {  // the scan's own lists, clamped like svo_scan_read (adaptive.rs:22,86), their counters reset
-        if (!ctx->scan_sub) return fail(ctx, SVO_ERR_STATE, "svo_scan_dispatch not called");
+        if (!ctx->scan_sub) return svo_fail(ctx, SVO_ERR_STATE, "svo_scan_dispatch not called");
         HIP_TRY(ctx, hipMemcpyAsync(&a->counts_host[0], ctx->scan_sub, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
         HIP_TRY(ctx, hipMemcpyAsync(&a->counts_host[1], ctx->scan_unsub, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
         HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
@@ -712,18 +673,10 @@ int svo_adaptive_step(svo_ctx *ctx, const uint32_t *d_sub, uint32_t n_sub, const
         HIP_TRY(ctx, hipMemsetAsync(ctx->scan_sub, 0, sizeof(uint32_t), ctx->stream));
         HIP_TRY(ctx, hipMemsetAsync(ctx->scan_unsub, 0, sizeof(uint32_t), ctx->stream));
     }
-    if (n_sub >= kMaxRank || n_unsub >= kMaxRank) return fail(ctx, SVO_ERR_ARG, "at most 2^24 - 1 entries per list");
+    if (n_sub >= kMaxRank || n_unsub >= kMaxRank) return svo_fail(ctx, SVO_ERR_ARG, "at most 2^24 - 1 entries per list");
     const size_t items = std::max<size_t>(std::max(n_sub, n_unsub), 1) + 1;
-    if (a->items < items) {
-        for (uint32_t **p : {&a->list[0], &a->list[1], &a->res, &a->src, &a->val, &a->flag})
-            if (*p) (void)hipFree(*p), *p = nullptr;
-        if (a->req) (void)hipFree(a->req), a->req = nullptr;
-        a->items = 0;
-        for (uint32_t **p : {&a->list[0], &a->list[1], &a->res, &a->src, &a->val, &a->flag})
-            HIP_TRY(ctx, hipMalloc((void **)p, items * sizeof(uint32_t)));
-        HIP_TRY(ctx, hipMalloc((void **)&a->req, 2 * items * sizeof(uint32_t)));
-        a->items = items;
-    }
+    if ((rc = svo_grow(ctx, &a->items, items, &a->list[0], &a->list[1], &a->res, &a->src, &a->val, &a->flag))) return rc;
+    if ((rc = svo_grow(ctx, &a->req_items, 2 * items, &a->req))) return rc;
     if ((rc = svo_build_sort_u32(ctx, d_sub, n_sub, a->list[0]))) return rc;
     if ((rc = svo_build_sort_u32(ctx, d_unsub, n_unsub, a->list[1]))) return rc;
     HIP_TRY(ctx, hipEventRecord(a->ev[1], ctx->stream));
@@ -738,7 +691,7 @@ int svo_adaptive_step(svo_ctx *ctx, const uint32_t *d_sub, uint32_t n_sub, const
     if ((rc = svo_store_note_write(ctx))) return rc;
     HIP_TRY(ctx, hipEventSynchronize(a->ev[3]));
     for (int k = 0; k < 3; k++) HIP_TRY(ctx, hipEventElapsedTime(&a->ms[k], a->ev[k], a->ev[k + 1]));
-    a->ms[3] = float(now_ms() - t0);
+    a->ms[3] = float(svo_now_ms() - t0);
     out->length = a->len;
     out->n_removed = (uint32_t)a->removed.size();
     out->removed = a->removed.data();
@@ -749,7 +702,7 @@ int svo_adaptive_download(svo_ctx *ctx, svo_octree *o) {
     if (!ctx || !o) return SVO_ERR_ARG;
     int rc = check_attached(ctx);
     if (rc) return rc;
-    svo_adapt_state *a = ctx->adapt;
+    svo_adapt_state *a = ctx->adapt.get();
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     std::vector<uint32_t> nodes(a->len), holes(a->n_holes);
     std::vector<float> pos(3 * size_t(a->len));
@@ -776,7 +729,7 @@ int svo_adaptive_length(svo_ctx *ctx, uint64_t *len_out) {
 
 int svo_adaptive_timing(svo_ctx *ctx, float ms_out[SVO_ADAPT_TIMES]) {
     if (!ctx || !ms_out) return SVO_ERR_ARG;
-    if (!ctx->adapt) return fail(ctx, SVO_ERR_STATE, "svo_adaptive_attach not called");
+    if (!ctx->adapt) return svo_fail(ctx, SVO_ERR_STATE, "svo_adaptive_attach not called");
     memcpy(ms_out, ctx->adapt->ms, sizeof ctx->adapt->ms);
     return SVO_OK;
 }

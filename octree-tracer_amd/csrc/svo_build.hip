@@ -20,18 +20,14 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <chrono>
 #include <cstring>
 #include <string>
 
 #include "svo_ctx.h"
+#include "svo_scan.h"  // (tiles of kTile items: sort, scans and compactions alike)
 
 namespace {
 
-constexpr uint32_t kThreads = 256;
-constexpr uint32_t kPer = 16;                     // items per thread of a tile
-constexpr uint32_t kTile = kThreads * kPer;       // items per tile (sort, scans and compactions alike)
-constexpr uint32_t kTopThreads = 1024;
 constexpr uint32_t kEmptyWord = SVO_VOXEL_OFFSET << 4;
 constexpr uint64_t kMaxWords = SVO_VOXEL_OFFSET;  // 2^27: pointers and colours must stay apart
 constexpr int kErrSlot = 24;                      // counts[0..21]: nodes per level; counts[24]: range error
@@ -39,32 +35,12 @@ constexpr int kCountSlots = 32;
 
 enum Mode { kDedupe = 0, kParent = 1, kDense = 2 };
 
-template <int N>
-__device__ inline uint32_t block_exclusive_scan(uint32_t v, uint32_t *total) {
-    __shared__ uint32_t s[N];
-    const int t = threadIdx.x;
-    s[t] = v;
-    __syncthreads();
-    for (int off = 1; off < N; off <<= 1) {
-        const uint32_t a = t >= off ? s[t - off] : 0u;
-        __syncthreads();
-        s[t] += a;
-        __syncthreads();
-    }
-    if (total) *total = s[N - 1];
-    const uint32_t r = s[t] - v;
-    __syncthreads();  // (a following call reuses s)
-    return r;
-}
-
 __device__ inline uint64_t morton3(uint32_t x, uint32_t y, uint32_t z, uint32_t depth) {
     uint64_t k = 0;
     for (uint32_t b = 0; b < depth; b++)
         k |= uint64_t((x >> b) & 1u) << (3 * b + 2) | uint64_t((y >> b) & 1u) << (3 * b + 1) | uint64_t((z >> b) & 1u) << (3 * b);
     return k;
 }
-
-__device__ inline uint32_t input_count(const uint32_t *m_dev, uint32_t m_max) { return m_dev ? min(*m_dev, m_max) : m_max; }
 
 // ---- keys ----
 __global__ __launch_bounds__(kThreads) void build_keys_kernel(const uint32_t *xyz, uint32_t n, uint32_t depth, uint64_t *keys,
@@ -186,25 +162,6 @@ __global__ __launch_bounds__(kThreads) void build_add_kernel(uint32_t *a, uint32
     }
 }
 
-// One block scans the tile sums in place (exclusive) and writes their total.  The tile count is n_tiles, or, with m_dev,
-// that of the *m_dev (at most m_max) items a compaction reads.
-__global__ __launch_bounds__(kTopThreads) void build_top_kernel(uint32_t *tile_sum, uint32_t n_tiles, const uint32_t *m_dev,
-                                                                uint32_t m_max, uint32_t *total_out) {
-    if (m_dev) n_tiles = (input_count(m_dev, m_max) + kTile - 1) / kTile;
-    const uint32_t per = (n_tiles + kTopThreads - 1) / kTopThreads;
-    const uint32_t lo = threadIdx.x * per, hi = min(lo + per, n_tiles);
-    uint32_t sum = 0;
-    for (uint32_t i = lo; i < hi; i++) sum += tile_sum[i];
-    uint32_t total;
-    uint32_t run = block_exclusive_scan<kTopThreads>(sum, &total);
-    for (uint32_t i = lo; i < hi; i++) {
-        const uint32_t v = tile_sum[i];
-        tile_sum[i] = run;
-        run += v;
-    }
-    if (threadIdx.x == 0) *total_out = total;
-}
-
 // ---- levels: flags, scans, compaction, emit ----
 struct LevelIn {
     const uint64_t *keys;     // kDedupe: sorted keys; kParent: this level's unique keys
@@ -300,24 +257,10 @@ __global__ __launch_bounds__(kThreads) void build_compact_kernel(LevelIn in, con
     }
 }
 
-int fail(svo_ctx *ctx, int code, const std::string &what) { return svo_fail(ctx, code, what.c_str()); }
-
-#define HIP_TRY(ctx, expr)                                          \
-    do {                                                            \
-        hipError_t e_ = (expr);                                     \
-        if (e_ != hipSuccess) return svo_fail_hip(ctx, e_, #expr); \
-    } while (0)
-
-uint32_t tiles_for(uint64_t n) { return (uint32_t)((n + kTile - 1) / kTile); }
-
-double now_ms() {
-    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
-}
-
 }  // namespace
 
-// Per-context workspace of the builder (svo_ctx::build): O(items), grown when a larger input comes, freed by
-// svo_build_release.  keys[0] / keys[1] and vals[0] / vals[1] are the sort's ping-pong buffers, later the level passes'
+// Per-context workspace of the builder (svo_ctx::build): O(items), grown when a larger input comes, freed with the
+// context.  keys[0] / keys[1] and vals[0] / vals[1] are the sort's ping-pong buffers, later the level passes'
 // (keys[0], keys[1] by turns); keys[2] / leaf_colours hold the leaf level from the level pass to the emit.
 struct svo_build_state {
     uint64_t *keys[3] = {};
@@ -334,7 +277,7 @@ struct svo_build_state {
     bool sorted = false, timed = true;  // the last build sorted / its device times are in ms
     float ms[SVO_BUILD_TIMES] = {};
 
-    void release() {
+    ~svo_build_state() {
         for (void *p : {(void *)keys[0], (void *)keys[1], (void *)keys[2], (void *)vals[0], (void *)vals[1], (void *)leaf_colours,
                         (void *)hist, (void *)tiles, (void *)counts})
             if (p) (void)hipFree(p);
@@ -344,60 +287,48 @@ struct svo_build_state {
     }
 };
 
-void svo_build_release(svo_ctx *ctx) {
-    if (!ctx->build) return;
-    ctx->build->release();
-    delete ctx->build;
-    ctx->build = nullptr;
-}
-
 namespace {
-
-template <typename T>
-int grow(svo_ctx *ctx, T **p, size_t *have, size_t want) {
-    if (*have >= want) return SVO_OK;
-    if (*p) (void)hipFree(*p);
-    *p = nullptr;
-    *have = 0;
-    HIP_TRY(ctx, hipMalloc((void **)p, want * sizeof(T)));
-    *have = want;
-    return SVO_OK;
-}
 
 // workspace for `items` keys (and the tile sums of scans over at most `scan_items` items)
 int ensure_state(svo_ctx *ctx, size_t items, size_t scan_items, size_t hist_items) {
     if (!ctx->build) {
-        ctx->build = new svo_build_state();
+        ctx->build = svo_workspace_new<svo_build_state>();
         for (hipEvent_t &e : ctx->build->ev) HIP_TRY(ctx, hipEventCreate(&e));
         HIP_TRY(ctx, hipHostMalloc((void **)&ctx->build->counts_host, kCountSlots * sizeof(uint32_t), hipHostMallocDefault));
         HIP_TRY(ctx, hipMalloc((void **)&ctx->build->counts, kCountSlots * sizeof(uint32_t)));
     }
-    svo_build_state *s = ctx->build;
-    if (s->items < items) {
-        for (void *p : {(void *)s->keys[0], (void *)s->keys[1], (void *)s->keys[2], (void *)s->vals[0], (void *)s->vals[1],
-                        (void *)s->leaf_colours})
-            if (p) (void)hipFree(p);
-        s->keys[0] = s->keys[1] = s->keys[2] = nullptr;
-        s->vals[0] = s->vals[1] = s->leaf_colours = nullptr;
-        s->items = 0;
-        for (int k = 0; k < 3; k++) HIP_TRY(ctx, hipMalloc((void **)&s->keys[k], items * sizeof(uint64_t)));
-        for (int k = 0; k < 2; k++) HIP_TRY(ctx, hipMalloc((void **)&s->vals[k], items * sizeof(uint32_t)));
-        HIP_TRY(ctx, hipMalloc((void **)&s->leaf_colours, items * sizeof(uint32_t)));
-        s->items = items;
-    }
-    int rc = grow(ctx, &s->hist, &s->hist_items, hist_items);
-    if (rc) return rc;
-    return grow(ctx, &s->tiles, &s->tile_items, (size_t)tiles_for(scan_items) + 1);
+    svo_build_state *s = ctx->build.get();
+    int rc = svo_grow(ctx, &s->items, items, &s->keys[0], &s->keys[1], &s->keys[2], &s->vals[0], &s->vals[1], &s->leaf_colours);
+    if (!rc) rc = svo_grow(ctx, &s->hist_items, hist_items, &s->hist);
+    if (!rc) rc = svo_grow(ctx, &s->tile_items, (size_t)svo_div_up(scan_items, kTile) + 1, &s->tiles);
+    return rc;
 }
 
 // Exclusive scan of hist[0, n) in place.
 int scan_u32(svo_ctx *ctx, uint32_t *a, uint32_t n) {
-    svo_build_state *s = ctx->build;
-    const uint32_t nt = tiles_for(n);
+    svo_build_state *s = ctx->build.get();
+    const uint32_t nt = svo_div_up(n, kTile);
     build_sum_kernel<<<nt, kThreads, 0, ctx->stream>>>(a, n, s->tiles);
-    build_top_kernel<<<1, kTopThreads, 0, ctx->stream>>>(s->tiles, nt, nullptr, 0, s->counts + kErrSlot + 1);
+    tile_offsets_kernel<<<1, kTopThreads, 0, ctx->stream>>>(s->tiles, nt, nullptr, 0, s->counts + kErrSlot + 1);
     build_add_kernel<<<nt, kThreads, 0, ctx->stream>>>(a, n, s->tiles);
     HIP_TRY(ctx, hipGetLastError());
+    return SVO_OK;
+}
+
+// `passes` stable 8-bit radix passes over the n items in keys[0] / vals[0]; the result is in keys[passes & 1] / vals[passes & 1].
+int sort_passes(svo_ctx *ctx, uint32_t n, uint32_t passes) {
+    svo_build_state *s = ctx->build.get();
+    const uint32_t nt = svo_div_up(n, kTile);
+    for (uint32_t k = 0; k < passes; k++) {
+        const uint32_t a = k & 1;
+        build_hist_kernel<<<nt, kThreads, 0, ctx->stream>>>(s->keys[a], n, 8 * k, s->hist, nt);
+        HIP_TRY(ctx, hipGetLastError());
+        int rc = scan_u32(ctx, s->hist, 256 * nt);
+        if (rc) return rc;
+        build_scatter_kernel<<<nt, kThreads, 0, ctx->stream>>>(s->keys[a], s->vals[a], n, 8 * k, s->hist, nt, s->keys[a ^ 1],
+                                                               s->vals[a ^ 1]);
+        HIP_TRY(ctx, hipGetLastError());
+    }
     return SVO_OK;
 }
 
@@ -405,10 +336,10 @@ int scan_u32(svo_ctx *ctx, uint32_t *a, uint32_t n) {
 // `bound` is the host's bound of the input count: the grid covers it.
 template <int M>
 int level_pass(svo_ctx *ctx, const LevelIn &in, const LevelOut &out, uint64_t bound, uint32_t *total) {
-    svo_build_state *s = ctx->build;
-    const uint32_t nt = std::max(tiles_for(bound), 1u);
+    svo_build_state *s = ctx->build.get();
+    const uint32_t nt = std::max(svo_div_up(bound, kTile), 1u);
     build_count_kernel<M><<<nt, kThreads, 0, ctx->stream>>>(in, s->tiles);
-    build_top_kernel<<<1, kTopThreads, 0, ctx->stream>>>(s->tiles, nt, in.m_dev, in.m_max, total);
+    tile_offsets_kernel<<<1, kTopThreads, 0, ctx->stream>>>(s->tiles, nt, in.m_dev, in.m_max, total);
     build_compact_kernel<M><<<nt, kThreads, 0, ctx->stream>>>(in, s->tiles, out);
     HIP_TRY(ctx, hipGetLastError());
     return SVO_OK;
@@ -418,7 +349,7 @@ int level_pass(svo_ctx *ctx, const LevelIn &in, const LevelOut &out, uint64_t bo
 // L-1's out (keys[0] and keys[1] by turns), m_{L-1} into counts[L-1].  With words: the emit, level L's slots too.
 int parent_passes(svo_ctx *ctx, uint32_t depth, uint32_t stop, const uint64_t *bound, uint32_t *words, const uint64_t *base,
                   uint64_t n_words) {
-    svo_build_state *s = ctx->build;
+    svo_build_state *s = ctx->build.get();
     const uint64_t *src = s->keys[2];
     for (uint32_t l = depth, turn = 0; l >= stop; l--, turn ^= 1) {
         LevelIn in{};
@@ -445,14 +376,14 @@ int parent_passes(svo_ctx *ctx, uint32_t depth, uint32_t stop, const uint64_t *b
 
 int check_common(svo_ctx *ctx, const svo_build_params *p, uint32_t max_depth, uint64_t *n_words_out) {
     if (n_words_out) *n_words_out = 0;
-    if (!p) return fail(ctx, SVO_ERR_ARG, "null params");
+    if (!p) return svo_fail(ctx, SVO_ERR_ARG, "null params");
     if (p->depth < 1 || p->depth > max_depth)
-        return fail(ctx, SVO_ERR_ARG, "depth must be 1.." + std::to_string(max_depth) + " (got " + std::to_string(p->depth) + ")");
+        return svo_fail(ctx, SVO_ERR_ARG, "depth must be 1.." + std::to_string(max_depth) + " (got " + std::to_string(p->depth) + ")");
     return SVO_OK;
 }
 
 int check_store(svo_ctx *ctx) {
-    if (!ctx->store) return fail(ctx, SVO_ERR_STATE, "svo_nodes_alloc / svo_nodes_bind_device not called");
+    if (!ctx->store) return svo_fail(ctx, SVO_ERR_STATE, "svo_nodes_alloc / svo_nodes_bind_device not called");
     return SVO_OK;
 }
 
@@ -463,7 +394,7 @@ uint64_t word_limit(const svo_ctx *ctx, const svo_build_params *p) {
 
 // Both entry points after their leaf pass: the other level passes, one read-back of the counts, the cap, the emit.
 int finish(svo_ctx *ctx, const svo_build_params *p, uint64_t leaf_bound, double t0, bool sorted, uint64_t *n_words_out) {
-    svo_build_state *s = ctx->build;
+    svo_build_state *s = ctx->build.get();
     const uint32_t depth = p->depth;
     uint64_t bound[23] = {};  // host bounds of the unique nodes per level
     bound[depth] = std::min<uint64_t>(leaf_bound, s->items);
@@ -475,17 +406,17 @@ int finish(svo_ctx *ctx, const svo_build_params *p, uint64_t leaf_bound, double 
     HIP_TRY(ctx, hipEventRecord(s->ev[4], ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     const uint32_t *m = s->counts_host;
-    if (m[kErrSlot]) return fail(ctx, SVO_ERR_ARG, "a voxel coordinate is outside [0, 2^depth) (depth " + std::to_string(depth) + ")");
+    if (m[kErrSlot]) return svo_fail(ctx, SVO_ERR_ARG, "a voxel coordinate is outside [0, 2^depth) (depth " + std::to_string(depth) + ")");
     const uint64_t limit = word_limit(ctx, p);
     if (m[depth] > s->items)  // (dense: more solid cells than the cap has words)
-        return fail(ctx, SVO_ERR_CAP, std::to_string(m[depth]) + " leaves cannot fit in " + std::to_string(limit) + " words");
+        return svo_fail(ctx, SVO_ERR_CAP, std::to_string(m[depth]) + " leaves cannot fit in " + std::to_string(limit) + " words");
     // breadth-first bases: level 1 (the root group) at 0, level L+1 behind level L's 8 * m_{L-1} words
     uint64_t base[23] = {0, 0};
     for (uint32_t l = 1; l < depth; l++) base[l + 1] = base[l] + 8ull * (l == 1 ? 1u : m[l - 1]);
     const uint64_t n_words = base[depth] + 8ull * (depth == 1 ? 1u : m[depth - 1]);
     if (n_words > limit)
-        return fail(ctx, SVO_ERR_CAP, "the tree needs " + std::to_string(n_words) + " words, over the limit of " + std::to_string(limit) +
-                                          " (max_words, the node buffer's capacity, 2^27)");
+        return svo_fail(ctx, SVO_ERR_CAP, "the tree needs " + std::to_string(n_words) + " words, over the limit of " +
+                                              std::to_string(limit) + " (max_words, the node buffer's capacity, 2^27)");
     for (uint32_t l = 1; l <= depth; l++) bound[l] = m[l];
     // emit: behind every earlier write to the store, whichever context issued it
     rc = svo_store_order_after_write(ctx);
@@ -498,7 +429,7 @@ int finish(svo_ctx *ctx, const svo_build_params *p, uint64_t leaf_bound, double 
     rc = svo_store_note_write(ctx);
     if (rc) return rc;
     *n_words_out = n_words;
-    s->ms[5] = float(now_ms() - t0);
+    s->ms[5] = float(svo_now_ms() - t0);
     s->sorted = sorted;
     s->timed = false;  // (the emit is still in flight: svo_build_timing reads the events)
     return SVO_OK;
@@ -506,7 +437,7 @@ int finish(svo_ctx *ctx, const svo_build_params *p, uint64_t leaf_bound, double 
 
 // n == 0 (CpuOctree::new(0)): the root group of 8 empty words.
 int build_empty(svo_ctx *ctx, const svo_build_params *p, uint64_t *n_words_out) {
-    if (word_limit(ctx, p) < 8) return fail(ctx, SVO_ERR_CAP, "the empty tree needs 8 words, over max_words");
+    if (word_limit(ctx, p) < 8) return svo_fail(ctx, SVO_ERR_CAP, "the empty tree needs 8 words, over max_words");
     int rc = svo_store_order_after_write(ctx);
     if (rc) return rc;
     HIP_TRY(ctx, hipMemsetD32Async((hipDeviceptr_t)ctx->nodes, (int)kEmptyWord, 8, ctx->stream));
@@ -519,10 +450,6 @@ int build_empty(svo_ctx *ctx, const svo_build_params *p, uint64_t *n_words_out) 
     *n_words_out = 8;
     return SVO_OK;
 }
-
-}  // namespace
-
-namespace {
 
 __global__ __launch_bounds__(kThreads) void build_widen_kernel(const uint32_t *in, uint32_t n, uint64_t *keys, uint32_t *vals) {
     const uint32_t i = blockIdx.x * kThreads + threadIdx.x;
@@ -541,21 +468,13 @@ __global__ __launch_bounds__(kThreads) void build_narrow_kernel(const uint64_t *
 // The radix sort and the scan above, for other passes on the ctx stream (svo_adapt.hip sorts its node lists with them).
 int svo_build_sort_u32(svo_ctx *ctx, const uint32_t *in, uint32_t n, uint32_t *out) {
     if (!n) return SVO_OK;
-    const uint32_t nt = tiles_for(n), grid = (n + kThreads - 1) / kThreads;
+    const uint32_t nt = svo_div_up(n, kTile), grid = svo_div_up(n, kThreads);
     int rc = ensure_state(ctx, n, std::max<uint64_t>(n, 256ull * nt), 256ull * nt);
     if (rc) return rc;
-    svo_build_state *s = ctx->build;
+    svo_build_state *s = ctx->build.get();
     build_widen_kernel<<<grid, kThreads, 0, ctx->stream>>>(in, n, s->keys[0], s->vals[0]);
     HIP_TRY(ctx, hipGetLastError());
-    for (uint32_t k = 0; k < 4; k++) {  // (4 passes of 8 bits: the result is back in keys[0])
-        const uint32_t a = k & 1;
-        build_hist_kernel<<<nt, kThreads, 0, ctx->stream>>>(s->keys[a], n, 8 * k, s->hist, nt);
-        HIP_TRY(ctx, hipGetLastError());
-        if ((rc = scan_u32(ctx, s->hist, 256 * nt))) return rc;
-        build_scatter_kernel<<<nt, kThreads, 0, ctx->stream>>>(s->keys[a], s->vals[a], n, 8 * k, s->hist, nt, s->keys[a ^ 1],
-                                                               s->vals[a ^ 1]);
-        HIP_TRY(ctx, hipGetLastError());
-    }
+    if ((rc = sort_passes(ctx, n, 4))) return rc;  // (4 passes of 8 bits: the result is back in keys[0])
     build_narrow_kernel<<<grid, kThreads, 0, ctx->stream>>>(s->keys[0], n, out);
     HIP_TRY(ctx, hipGetLastError());
     return SVO_OK;
@@ -575,32 +494,24 @@ int svo_nodes_build(svo_ctx *ctx, const uint32_t *xyz, const uint32_t *colours, 
     if (!ctx) return SVO_ERR_ARG;
     int rc = check_common(ctx, p, 21, n_words_out);
     if (rc) return rc;
-    if (n >= (1ull << 31)) return fail(ctx, SVO_ERR_ARG, "at most 2^31 - 1 voxels per build");
-    if (!xyz && n) return fail(ctx, SVO_ERR_ARG, "null coordinates");
-    if (!n_words_out) return fail(ctx, SVO_ERR_ARG, "null n_words_out");
+    if (n >= (1ull << 31)) return svo_fail(ctx, SVO_ERR_ARG, "at most 2^31 - 1 voxels per build");
+    if (!xyz && n) return svo_fail(ctx, SVO_ERR_ARG, "null coordinates");
+    if (!n_words_out) return svo_fail(ctx, SVO_ERR_ARG, "null n_words_out");
     if ((rc = check_store(ctx))) return rc;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     if (!n) return build_empty(ctx, p, n_words_out);
-    const double t0 = now_ms();
-    const uint32_t depth = p->depth, nt = tiles_for(n);
+    const double t0 = svo_now_ms();
+    const uint32_t depth = p->depth, nt = svo_div_up(n, kTile);
     if ((rc = ensure_state(ctx, n, std::max<uint64_t>(n, 256ull * nt), 256ull * nt))) return rc;
-    svo_build_state *s = ctx->build;
+    svo_build_state *s = ctx->build.get();
     HIP_TRY(ctx, hipEventRecord(s->ev[0], ctx->stream));
     HIP_TRY(ctx, hipMemsetAsync(s->counts, 0, kCountSlots * sizeof(uint32_t), ctx->stream));
-    build_keys_kernel<<<(uint32_t)((n + kThreads - 1) / kThreads), kThreads, 0, ctx->stream>>>(xyz, (uint32_t)n, depth, s->keys[0],
-                                                                                               s->vals[0], s->counts + kErrSlot);
+    build_keys_kernel<<<svo_div_up(n, kThreads), kThreads, 0, ctx->stream>>>(xyz, (uint32_t)n, depth, s->keys[0], s->vals[0],
+                                                                             s->counts + kErrSlot);
     HIP_TRY(ctx, hipGetLastError());
     HIP_TRY(ctx, hipEventRecord(s->ev[1], ctx->stream));
     const uint32_t passes = (3 * depth + 7) / 8;
-    for (uint32_t k = 0; k < passes; k++) {
-        const uint32_t a = k & 1;
-        build_hist_kernel<<<nt, kThreads, 0, ctx->stream>>>(s->keys[a], (uint32_t)n, 8 * k, s->hist, nt);
-        HIP_TRY(ctx, hipGetLastError());
-        if ((rc = scan_u32(ctx, s->hist, 256 * nt))) return rc;
-        build_scatter_kernel<<<nt, kThreads, 0, ctx->stream>>>(s->keys[a], s->vals[a], (uint32_t)n, 8 * k, s->hist, nt, s->keys[a ^ 1],
-                                                               s->vals[a ^ 1]);
-        HIP_TRY(ctx, hipGetLastError());
-    }
+    if ((rc = sort_passes(ctx, (uint32_t)n, passes))) return rc;
     HIP_TRY(ctx, hipEventRecord(s->ev[2], ctx->stream));
     // leaf level: the last voxel of every run of equal keys
     LevelIn in{};
@@ -621,18 +532,18 @@ int svo_nodes_build_dense(svo_ctx *ctx, const uint32_t *grid, const svo_build_pa
     if (!ctx) return SVO_ERR_ARG;
     int rc = check_common(ctx, p, 10, n_words_out);
     if (rc) return rc;
-    if (!grid) return fail(ctx, SVO_ERR_ARG, "null grid");
-    if (!n_words_out) return fail(ctx, SVO_ERR_ARG, "null n_words_out");
+    if (!grid) return svo_fail(ctx, SVO_ERR_ARG, "null grid");
+    if (!n_words_out) return svo_fail(ctx, SVO_ERR_ARG, "null n_words_out");
     if ((rc = check_store(ctx))) return rc;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const double t0 = now_ms();
+    const double t0 = svo_now_ms();
     const uint32_t depth = p->depth;
     const uint64_t cells = 1ull << (3 * depth);
     // every leaf takes a word: a grid with more solid cells than the limit has words fails the cap, so the leaf level
     // needs no more room than that
     const uint64_t room = std::max<uint64_t>(std::min(cells, word_limit(ctx, p)), 1);
     if ((rc = ensure_state(ctx, room, cells, 0))) return rc;
-    svo_build_state *s = ctx->build;
+    svo_build_state *s = ctx->build.get();
     HIP_TRY(ctx, hipEventRecord(s->ev[0], ctx->stream));
     HIP_TRY(ctx, hipMemsetAsync(s->counts, 0, kCountSlots * sizeof(uint32_t), ctx->stream));
     HIP_TRY(ctx, hipEventRecord(s->ev[1], ctx->stream));
@@ -651,8 +562,8 @@ int svo_nodes_build_dense(svo_ctx *ctx, const uint32_t *grid, const svo_build_pa
 
 int svo_build_timing(svo_ctx *ctx, float ms_out[SVO_BUILD_TIMES]) {
     if (!ctx || !ms_out) return SVO_ERR_ARG;
-    if (!ctx->build) return fail(ctx, SVO_ERR_STATE, "no tree built on this context yet");
-    svo_build_state *s = ctx->build;
+    if (!ctx->build) return svo_fail(ctx, SVO_ERR_STATE, "no tree built on this context yet");
+    svo_build_state *s = ctx->build.get();
     if (!s->timed) {
         const int first[5] = {0, 1, 2, 3, 5}, last[5] = {1, 2, 3, 4, 6};
         HIP_TRY(ctx, hipSetDevice(ctx->device));

@@ -1,10 +1,15 @@
-// svo_ctx.h -- the device context behind the opaque `svo_ctx` of include/svo_hip.h; shared by svo_abi.cpp (trace / scan
-// dispatch) and svo_comm.cpp (RCCL frame gather).  Internal: not part of the boundary.
+// svo_ctx.h -- the device context behind the opaque `svo_ctx` of include/svo_hip.h, and the host helpers of the files that
+// use it: svo_abi.cpp (trace / scan dispatch), svo_comm.cpp (RCCL frame gather) and the GPU tree passes (svo_proc.hip,
+// svo_build.hip, svo_adapt.hip).  Internal: not part of the boundary.
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <chrono>
 #include <cstdint>
+#include <memory>
 #include <string>
+#include <type_traits>
+#include <utility>
 #include <vector>
 
 #include "svo_device.h"
@@ -25,6 +30,18 @@ struct svo_node_store {
     hipEvent_t last_write = nullptr;   // recorded on the writing context's stream after every write
     hipStream_t last_writer = nullptr; // that stream: other streams wait for the event before they read
 };
+
+// The workspace of a GPU pass, kept per context and freed by its destructor.  Its type is complete only in the pass's own
+// file, so the deleter is bound there, by svo_workspace_new.
+struct svo_proc_state;
+struct svo_build_state;
+struct svo_adapt_state;
+template <typename T>
+using svo_workspace = std::unique_ptr<T, void (*)(T *)>;
+template <typename T>
+svo_workspace<T> svo_workspace_new() {
+    return svo_workspace<T>(new T(), [](T *p) { delete p; });
+}
 
 struct svo_ctx {
     int device = 0;
@@ -96,9 +113,9 @@ struct svo_ctx {
     // launch timing: a ring of (start, stop) event pairs recorded around trace launches
     std::vector<hipEvent_t> ev;  // 2 per slot
     size_t ev_slots = 0, ev_count = 0;
-    struct svo_proc_state *proc = nullptr;  // procedural generator's workspace (svo_proc.hip)
-    struct svo_build_state *build = nullptr;  // tree builder's workspace (svo_build.hip)
-    struct svo_adapt_state *adapt = nullptr;  // device adaptive state (svo_adapt.hip)
+    svo_workspace<svo_proc_state> proc{nullptr, nullptr};    // procedural generator's workspace (svo_proc.hip)
+    svo_workspace<svo_build_state> build{nullptr, nullptr};  // tree builder's workspace (svo_build.hip)
+    svo_workspace<svo_adapt_state> adapt{nullptr, nullptr};  // device adaptive state (svo_adapt.hip)
     std::string err;
 };
 
@@ -106,22 +123,55 @@ struct svo_ctx {
 // svo_abi.cpp
 int svo_fail(svo_ctx *ctx, int code, const char *what);
 int svo_fail_hip(svo_ctx *ctx, hipError_t e, const char *what);
+inline int svo_fail(svo_ctx *ctx, int code, const std::string &what) { return svo_fail(ctx, code, what.c_str()); }
+
+#define HIP_TRY(ctx, expr)                                          \
+    do {                                                            \
+        hipError_t e_ = (expr);                                     \
+        if (e_ != hipSuccess) return svo_fail_hip(ctx, e_, #expr); \
+    } while (0)
+
+inline double svo_now_ms() {
+    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
+}
+
+// blocks of `per` items that cover n
+inline uint32_t svo_div_up(uint64_t n, uint64_t per) { return (uint32_t)((n + per - 1) / per); }
+
+// Grows a group of buffers to `want` items of its own type each (a void buffer counts bytes): when *have < want, waits
+// for the context's stream, frees all of them and allocates them again; *have becomes `want` only when every allocation
+// succeeded.  svo_grow allocates device memory, svo_grow_pinned pinned host memory.
+template <typename... T>
+int svo_grow_group(svo_ctx *ctx, bool pinned, size_t *have, size_t want, T **...bufs) {
+    if (*have >= want) return SVO_OK;
+    const std::pair<void **, size_t> group[] = {{(void **)bufs, sizeof(std::conditional_t<std::is_void<T>::value, char, T>)}...};
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    for (auto &b : group) {
+        if (*b.first) (void)(pinned ? hipHostFree(*b.first) : hipFree(*b.first));
+        *b.first = nullptr;
+    }
+    *have = 0;
+    for (auto &b : group)
+        HIP_TRY(ctx, pinned ? hipHostMalloc(b.first, want * b.second, hipHostMallocDefault) : hipMalloc(b.first, want * b.second));
+    *have = want;
+    return SVO_OK;
+}
+template <typename... T>
+int svo_grow(svo_ctx *ctx, size_t *have, size_t want, T **...bufs) { return svo_grow_group(ctx, false, have, want, bufs...); }
+template <typename... T>
+int svo_grow_pinned(svo_ctx *ctx, size_t *have, size_t want, T **...bufs) { return svo_grow_group(ctx, true, have, want, bufs...); }
+
 // a write to the bound node store: enqueue it behind the store's last write (any context's), then record it, which makes
 // every context bound to the store rebuild its top table and schedule
 int svo_store_order_after_write(svo_ctx *ctx);
 int svo_store_note_write(svo_ctx *ctx);
 // svo_comm.cpp
 void svo_comm_release(svo_ctx *ctx);
-// svo_proc.hip
-void svo_proc_release(svo_ctx *ctx);
 // svo_build.hip
-void svo_build_release(svo_ctx *ctx);
 // the builder's stable radix sort of n u32 keys (in -> out, may alias) and in-place exclusive scan of n u32, for other
 // passes on the ctx stream; both use the builder's workspace
 int svo_build_sort_u32(svo_ctx *ctx, const uint32_t *in, uint32_t n, uint32_t *out);
 int svo_build_scan_u32(svo_ctx *ctx, uint32_t *a, uint32_t n);
-// svo_adapt.hip
-void svo_adapt_release(svo_ctx *ctx);
 // svo_host.cpp (internal helpers of svo_world_generate)
 std::string svo_world_path(const svo_world *w);
 void svo_cpu_octree_drop_nodes(svo_cpu_octree *t);  // frees the nodes, keeps top_mip (world.rs:122)

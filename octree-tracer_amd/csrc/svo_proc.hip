@@ -17,20 +17,18 @@
 #include <sys/stat.h>
 
 #include <cerrno>
-#include <chrono>
 #include <cstring>
 #include <string>
 #include <vector>
 
 #include "svo_ctx.h"
 #include "svo_host.h"
+#include "svo_scan.h"  // (a level's mask bytes are scanned in tiles of kTile)
 
 namespace {
 
 constexpr uint32_t kChunkOffset = SVO_CHUNK_OFFSET;
 constexpr uint64_t kDefaultMaxNodes = 256000000ull;  // procedural.rs:4
-constexpr uint32_t kTile = 4096;                     // bytes of one level's flags per scan tile (256 lanes x 16)
-constexpr uint32_t kTopThreads = 1024;
 
 // ---- sdf (procedual.wgsl:109-148 over common.wgsl:43-191), one IEEE f32 operation per step, in the order of
 // DESIGN.md 11; compiled with -ffp-contract=off, so no step is fused ----
@@ -204,22 +202,6 @@ __global__ __launch_bounds__(256) void proc_reduce_kernel(const uint8_t *child_m
     parent_masks[p] = (uint8_t)mask;
 }
 
-template <int N>
-__device__ inline uint32_t block_exclusive_scan(uint32_t v, uint32_t *total) {
-    __shared__ uint32_t s[N];
-    const int t = threadIdx.x;
-    s[t] = v;
-    __syncthreads();
-    for (int off = 1; off < N; off <<= 1) {
-        const uint32_t a = t >= off ? s[t - off] : 0u;
-        __syncthreads();
-        s[t] += a;
-        __syncthreads();
-    }
-    if (total) *total = s[N - 1];
-    return s[t] - v;
-}
-
 __device__ inline uint32_t count16(const uint4 q) {
     return __popc(nonzero_bytes(q.x)) + __popc(nonzero_bytes(q.y)) + __popc(nonzero_bytes(q.z)) + __popc(nonzero_bytes(q.w));
 }
@@ -230,22 +212,6 @@ __global__ __launch_bounds__(256) void proc_tile_count_kernel(const uint8_t *mas
     uint32_t total;
     block_exclusive_scan<256>(count16(q), &total);
     if (threadIdx.x == 0) tile_sum[blockIdx.x] = total;
-}
-
-// ranks, phase 2: one block scans the tile counts in place (exclusive) and writes the level's interior count
-__global__ __launch_bounds__(kTopThreads) void proc_tile_scan_kernel(uint32_t *tile_sum, uint32_t n_tiles, uint32_t *level_total) {
-    const uint32_t per = (n_tiles + kTopThreads - 1) / kTopThreads;
-    const uint32_t lo = threadIdx.x * per, hi = min(lo + per, n_tiles);
-    uint32_t sum = 0;
-    for (uint32_t i = lo; i < hi; i++) sum += tile_sum[i];
-    uint32_t total;
-    uint32_t run = block_exclusive_scan<kTopThreads>(sum, &total);
-    for (uint32_t i = lo; i < hi; i++) {
-        const uint32_t v = tile_sum[i];
-        tile_sum[i] = run;
-        run += v;
-    }
-    if (threadIdx.x == 0) *level_total = total;
 }
 
 // ranks, phase 3: every node's exclusive rank among the interior nodes of its level
@@ -291,20 +257,7 @@ __global__ __launch_bounds__(256) void proc_sdf_kernel(const float *xyz, uint32_
     out[i] = sdf::eval(xyz[3u * i], xyz[3u * i + 1u], xyz[3u * i + 2u]);
 }
 
-int fail(svo_ctx *ctx, int code, const std::string &what) { return svo_fail(ctx, code, what.c_str()); }
-
-#define HIP_TRY(ctx, expr)                                             \
-    do {                                                               \
-        hipError_t e_ = (expr);                                        \
-        if (e_ != hipSuccess) return svo_fail_hip(ctx, e_, #expr);    \
-    } while (0)
-
-uint32_t blocks_for(uint64_t n) { return (uint32_t)((n + 255u) / 256u); }
 uint64_t pad_tile(uint64_t n) { return (n + kTile - 1) / kTile * kTile; }
-
-double now_ms() {
-    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
-}
 
 }  // namespace
 
@@ -322,13 +275,13 @@ struct svo_proc_state {
     uint64_t mask_off[10] = {}, rank_off[10] = {}, tile_off[10] = {};
     uint32_t n_tiles[10] = {};
     uint4 *out = nullptr;  // emitted nodes, 8 bytes each
-    size_t out_bytes = 0;
+    size_t out_items = 0;
     uint8_t *stage = nullptr;  // pinned read-back buffer
     size_t stage_bytes = 0;
     hipEvent_t ev[4] = {};
     float ms[SVO_PROC_TIMES] = {};
 
-    void release() {
+    ~svo_proc_state() {
         for (void *p : {(void *)cls, (void *)masks, (void *)ranks, (void *)tiles, (void *)totals, (void *)out})
             if (p) (void)hipFree(p);
         if (totals_host) (void)hipHostFree(totals_host);
@@ -338,20 +291,13 @@ struct svo_proc_state {
     }
 };
 
-void svo_proc_release(svo_ctx *ctx) {
-    if (!ctx->proc) return;
-    ctx->proc->release();
-    delete ctx->proc;
-    ctx->proc = nullptr;
-}
-
 namespace {
 
 int check_params(svo_ctx *ctx, const svo_proc_params *p) {
-    if (!p) return fail(ctx, SVO_ERR_ARG, "null params");
+    if (!p) return svo_fail(ctx, SVO_ERR_ARG, "null params");
     if (p->chunk_depth < 2 || p->chunk_depth > 9)
-        return fail(ctx, SVO_ERR_ARG, "chunk_depth must be 2..9 (got " + std::to_string(p->chunk_depth) + ")");
-    if (p->base_depth > 21) return fail(ctx, SVO_ERR_ARG, "base_depth must be <= 21");
+        return svo_fail(ctx, SVO_ERR_ARG, "chunk_depth must be 2..9 (got " + std::to_string(p->chunk_depth) + ")");
+    if (p->base_depth > 21) return svo_fail(ctx, SVO_ERR_ARG, "base_depth must be <= 21");
     return SVO_OK;
 }
 
@@ -368,12 +314,12 @@ ChunkGeom geom_of(const svo_proc_params *p) {
 // workspace for chunks of `depth` levels (kept between calls; regrown for a deeper chunk)
 int ensure_state(svo_ctx *ctx, uint32_t depth) {
     if (!ctx->proc) {
-        ctx->proc = new svo_proc_state();
+        ctx->proc = svo_workspace_new<svo_proc_state>();
         for (hipEvent_t &e : ctx->proc->ev) HIP_TRY(ctx, hipEventCreate(&e));
         HIP_TRY(ctx, hipHostMalloc((void **)&ctx->proc->totals_host, 16 * sizeof(uint32_t), hipHostMallocDefault));
         HIP_TRY(ctx, hipMalloc((void **)&ctx->proc->totals, 16 * sizeof(uint32_t)));
     }
-    svo_proc_state *s = ctx->proc;
+    svo_proc_state *s = ctx->proc.get();
     if (s->depth == depth) return SVO_OK;
     if (s->alloc_depth < depth) {  // a shallower chunk reuses the buffers of a deeper one: every level fits
         for (void *p : {(void *)s->cls, (void *)s->masks, (void *)s->ranks, (void *)s->tiles})
@@ -407,10 +353,10 @@ int ensure_state(svo_ctx *ctx, uint32_t depth) {
 }
 
 int launch_classify(svo_ctx *ctx, const svo_proc_params *p) {
-    svo_proc_state *s = ctx->proc;
+    svo_proc_state *s = ctx->proc.get();
     const uint32_t n_cells = 1u << (3 * p->chunk_depth);
     HIP_TRY(ctx, hipMemsetAsync(s->masks, 0, s->mask_bytes, ctx->stream));
-    proc_classify_kernel<<<blocks_for(n_cells), 256, 0, ctx->stream>>>(geom_of(p), n_cells, s->cls,
+    proc_classify_kernel<<<svo_div_up(n_cells, 256), 256, 0, ctx->stream>>>(geom_of(p), n_cells, s->cls,
                                                                          s->masks + s->mask_off[p->chunk_depth - 1]);
     HIP_TRY(ctx, hipGetLastError());
     return SVO_OK;
@@ -422,15 +368,15 @@ extern "C" {
 
 int svo_proc_sdf(svo_ctx *ctx, const float *xyz, size_t n, float *out) {
     if (!ctx) return SVO_ERR_ARG;
-    if ((!xyz || !out) && n) return fail(ctx, SVO_ERR_ARG, "null points or output");
-    if (n > (1ull << 28)) return fail(ctx, SVO_ERR_ARG, "at most 2^28 points per call");
+    if ((!xyz || !out) && n) return svo_fail(ctx, SVO_ERR_ARG, "null points or output");
+    if (n > (1ull << 28)) return svo_fail(ctx, SVO_ERR_ARG, "at most 2^28 points per call");
     if (!n) return SVO_OK;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     float *d = nullptr;
     HIP_TRY(ctx, hipMalloc((void **)&d, n * 4 * sizeof(float)));
     hipError_t e = hipMemcpyAsync(d, xyz, n * 3 * sizeof(float), hipMemcpyHostToDevice, ctx->stream);
     if (e == hipSuccess) {
-        proc_sdf_kernel<<<blocks_for(n), 256, 0, ctx->stream>>>(d, (uint32_t)n, d + 3 * n);
+        proc_sdf_kernel<<<svo_div_up(n, 256), 256, 0, ctx->stream>>>(d, (uint32_t)n, d + 3 * n);
         e = hipGetLastError();
     }
     if (e == hipSuccess) e = hipMemcpyAsync(out, d + 3 * n, n * sizeof(float), hipMemcpyDeviceToHost, ctx->stream);
@@ -443,7 +389,7 @@ int svo_proc_classify(svo_ctx *ctx, const svo_proc_params *params, uint8_t *cell
     if (!ctx) return SVO_ERR_ARG;
     int rc = check_params(ctx, params);
     if (rc) return rc;
-    if (!cells_out) return fail(ctx, SVO_ERR_ARG, "null output");
+    if (!cells_out) return svo_fail(ctx, SVO_ERR_ARG, "null output");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     if ((rc = ensure_state(ctx, params->chunk_depth))) return rc;
     if ((rc = launch_classify(ctx, params))) return rc;
@@ -465,15 +411,15 @@ int svo_proc_classify(svo_ctx *ctx, const svo_proc_params *params, uint8_t *cell
 
 int svo_proc_generate_chunk(svo_ctx *ctx, const svo_proc_params *params, svo_cpu_octree **out) {
     if (!ctx) return SVO_ERR_ARG;
-    if (!out) return fail(ctx, SVO_ERR_ARG, "null output");
+    if (!out) return svo_fail(ctx, SVO_ERR_ARG, "null output");
     *out = nullptr;
     int rc = check_params(ctx, params);
     if (rc) return rc;
     const uint64_t max_nodes = params->max_nodes ? params->max_nodes : kDefaultMaxNodes;
-    const double t0 = now_ms();
+    const double t0 = svo_now_ms();
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     if ((rc = ensure_state(ctx, params->chunk_depth))) return rc;
-    svo_proc_state *s = ctx->proc;
+    svo_proc_state *s = ctx->proc.get();
     const uint32_t depth = params->chunk_depth;
 
     HIP_TRY(ctx, hipEventRecord(s->ev[0], ctx->stream));
@@ -482,7 +428,7 @@ int svo_proc_generate_chunk(svo_ctx *ctx, const svo_proc_params *params, svo_cpu
     // occupancy pyramid: level L-1's masks from level L's
     for (uint32_t l = depth - 1; l >= 1; l--) {
         const uint32_t n_par = 1u << (3 * (l - 1));
-        proc_reduce_kernel<<<blocks_for(n_par), 256, 0, ctx->stream>>>(s->masks + s->mask_off[l], n_par, s->masks + s->mask_off[l - 1]);
+        proc_reduce_kernel<<<svo_div_up(n_par, 256), 256, 0, ctx->stream>>>(s->masks + s->mask_off[l], n_par, s->masks + s->mask_off[l - 1]);
         HIP_TRY(ctx, hipGetLastError());
     }
     // ranks of the interior nodes of every level, and their counts
@@ -490,7 +436,7 @@ int svo_proc_generate_chunk(svo_ctx *ctx, const svo_proc_params *params, svo_cpu
         const uint8_t *m = s->masks + s->mask_off[l];
         uint32_t *tiles = s->tiles + s->tile_off[l];
         proc_tile_count_kernel<<<s->n_tiles[l], 256, 0, ctx->stream>>>(m, tiles);
-        proc_tile_scan_kernel<<<1, kTopThreads, 0, ctx->stream>>>(tiles, s->n_tiles[l], s->totals + l);
+        tile_offsets_kernel<<<1, kTopThreads, 0, ctx->stream>>>(tiles, s->n_tiles[l], nullptr, 0, s->totals + l);
         proc_tile_rank_kernel<<<s->n_tiles[l], 256, 0, ctx->stream>>>(m, tiles, s->ranks + s->rank_off[l]);
         HIP_TRY(ctx, hipGetLastError());
     }
@@ -504,45 +450,33 @@ int svo_proc_generate_chunk(svo_ctx *ctx, const svo_proc_params *params, svo_cpu
     const uint64_t n_nodes = base[depth + 1];
     if (s->totals_host[0] == 0) {  // no solid cell: the reference's "len <= 8 -> None" (procedural.rs:167)
         s->ms[0] = s->ms[1] = s->ms[2] = s->ms[4] = s->ms[5] = 0.0f;
-        s->ms[3] = float(now_ms() - t0);
+        s->ms[3] = float(svo_now_ms() - t0);
         return SVO_OK;
     }
     if (n_nodes > max_nodes)
-        return fail(ctx, SVO_ERR_CAP, "chunk needs " + std::to_string(n_nodes) + " nodes, over max_nodes = " + std::to_string(max_nodes) +
-                                          " (the reference panics here, procedural.rs:171-172)");
+        return svo_fail(ctx, SVO_ERR_CAP, "chunk needs " + std::to_string(n_nodes) + " nodes, over max_nodes = " +
+                                              std::to_string(max_nodes) + " (the reference panics here, procedural.rs:171-172)");
     const size_t bytes = n_nodes * 8;
-    if (s->out_bytes < bytes) {
-        if (s->out) (void)hipFree(s->out);
-        s->out = nullptr;
-        s->out_bytes = 0;
-        HIP_TRY(ctx, hipMalloc((void **)&s->out, bytes));
-        s->out_bytes = bytes;
-    }
+    if ((rc = svo_grow(ctx, &s->out_items, bytes / sizeof(uint4), &s->out))) return rc;
     for (uint32_t l = 1; l <= depth; l++) {
         const uint32_t n_par = 1u << (3 * (l - 1));
         const bool last = l == depth;
-        proc_emit_kernel<<<blocks_for(n_par), 256, 0, ctx->stream>>>(
+        proc_emit_kernel<<<svo_div_up(n_par, 256), 256, 0, ctx->stream>>>(
             s->masks + s->mask_off[l - 1], s->ranks + s->rank_off[l - 1], n_par, last ? s->cls : s->masks + s->mask_off[l],
             last ? nullptr : s->ranks + s->rank_off[l], last ? 1u : 0u, (uint32_t)base[l], (uint32_t)base[l + 1], (uint32_t)n_nodes, s->out);
         HIP_TRY(ctx, hipGetLastError());
     }
     HIP_TRY(ctx, hipEventRecord(s->ev[3], ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    const double t1 = now_ms();
-    if (s->stage_bytes < bytes) {
-        if (s->stage) (void)hipHostFree(s->stage);
-        s->stage = nullptr;
-        s->stage_bytes = 0;
-        HIP_TRY(ctx, hipHostMalloc((void **)&s->stage, bytes, hipHostMallocDefault));
-        s->stage_bytes = bytes;
-    }
+    const double t1 = svo_now_ms();
+    if ((rc = svo_grow_pinned(ctx, &s->stage_bytes, bytes, &s->stage))) return rc;
     HIP_TRY(ctx, hipMemcpyAsync(s->stage, s->out, bytes, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    const double t2 = now_ms();
+    const double t2 = svo_now_ms();
     char why[128] = "";
     *out = svo_cpu_octree_from_bin(s->stage, bytes, why, sizeof why);
-    if (!*out) return fail(ctx, SVO_ERR_STATE, std::string("emitted tree rejected: ") + why);
-    const double t3 = now_ms();
+    if (!*out) return svo_fail(ctx, SVO_ERR_STATE, std::string("emitted tree rejected: ") + why);
+    const double t3 = svo_now_ms();
     HIP_TRY(ctx, hipEventElapsedTime(&s->ms[0], s->ev[0], s->ev[1]));
     HIP_TRY(ctx, hipEventElapsedTime(&s->ms[1], s->ev[1], s->ev[2]));
     HIP_TRY(ctx, hipEventElapsedTime(&s->ms[2], s->ev[2], s->ev[3]));
@@ -554,7 +488,7 @@ int svo_proc_generate_chunk(svo_ctx *ctx, const svo_proc_params *params, svo_cpu
 
 int svo_proc_timing(svo_ctx *ctx, float ms_out[SVO_PROC_TIMES]) {
     if (!ctx || !ms_out) return SVO_ERR_ARG;
-    if (!ctx->proc) return fail(ctx, SVO_ERR_STATE, "no chunk generated on this context yet");
+    if (!ctx->proc) return svo_fail(ctx, SVO_ERR_STATE, "no chunk generated on this context yet");
     memcpy(ms_out, ctx->proc->ms, sizeof ctx->proc->ms);
     return SVO_OK;
 }
@@ -562,17 +496,17 @@ int svo_proc_timing(svo_ctx *ctx, float ms_out[SVO_PROC_TIMES]) {
 // World::generate_world (world.rs:63-139) without its "delete the directory if it is called tmp" rule.
 int svo_world_generate(svo_ctx *ctx, svo_world *w, uint32_t world_depth, uint32_t chunk_depth) {
     if (!ctx) return SVO_ERR_ARG;
-    if (!w) return fail(ctx, SVO_ERR_ARG, "null world");
-    if (world_depth < 1 || world_depth > 4) return fail(ctx, SVO_ERR_ARG, "world_depth must be 1..4");
-    if (chunk_depth < 2 || chunk_depth > 9) return fail(ctx, SVO_ERR_ARG, "chunk_depth must be 2..9");
+    if (!w) return svo_fail(ctx, SVO_ERR_ARG, "null world");
+    if (world_depth < 1 || world_depth > 4) return svo_fail(ctx, SVO_ERR_ARG, "world_depth must be 1..4");
+    if (chunk_depth < 2 || chunk_depth > 9) return svo_fail(ctx, SVO_ERR_ARG, "chunk_depth must be 2..9");
     for (uint32_t b = 1; b <= 8; b++)  // mips of block leaves need the blocks' top_mip (World::new, world.rs:19-58)
-        if (!svo_world_chunk(w, b)) return fail(ctx, SVO_ERR_STATE, "block " + std::to_string(b) + " is not loaded (insert blocks 1..8 first)");
+        if (!svo_world_chunk(w, b)) return svo_fail(ctx, SVO_ERR_STATE, "block " + std::to_string(b) + " is not loaded (insert blocks 1..8 first)");
     const std::string path = svo_world_path(w);
-    if (path.empty()) return fail(ctx, SVO_ERR_ARG, "world has no path");
+    if (path.empty()) return svo_fail(ctx, SVO_ERR_ARG, "world has no path");
     if (mkdir(path.c_str(), 0777) != 0)
-        return fail(ctx, errno == EEXIST ? SVO_ERR_ARG : SVO_ERR_STATE,
-                    errno == EEXIST ? "File already exists" : "cannot create " + path + ": " + strerror(errno));
-    auto world_fail = [&](const char *what) { return fail(ctx, SVO_ERR_STATE, std::string(what) + ": " + svo_world_last_error(w)); };
+        return svo_fail(ctx, errno == EEXIST ? SVO_ERR_ARG : SVO_ERR_STATE,
+                        errno == EEXIST ? "File already exists" : "cannot create " + path + ": " + strerror(errno));
+    auto world_fail = [&](const char *what) { return svo_fail(ctx, SVO_ERR_STATE, std::string(what) + ": " + svo_world_last_error(w)); };
     float times[4] = {0, 0, 0, 0};  // GPU, read-back, mips, writes
     svo_cpu_octree *root = svo_cpu_octree_new(0);
     const uint32_t n = 1u << world_depth;
@@ -598,28 +532,28 @@ int svo_world_generate(svo_ctx *ctx, svo_world *w, uint32_t world_depth, uint32_
                 times[1] += ctx->proc->ms[4] + ctx->proc->ms[5];
                 if (!chunk) continue;
                 svo_world_insert(w, id, chunk);
-                double t = now_ms();
+                double t = svo_now_ms();
                 if (svo_world_generate_mip_tree(w, id, nullptr) != 0) {
                     svo_cpu_octree_free(root);
                     return world_fail("mips");
                 }
-                times[2] += float(now_ms() - t);
-                t = now_ms();
+                times[2] += float(svo_now_ms() - t);
+                t = svo_now_ms();
                 if (svo_world_save_chunk(w, id) != 0) {
                     svo_cpu_octree_free(root);
                     return world_fail("save");
                 }
-                times[3] += float(now_ms() - t);
+                times[3] += float(svo_now_ms() - t);
                 svo_cpu_octree_drop_nodes(chunk);  // keep only top_mip in memory (world.rs:122)
                 svo_cpu_octree_put_in_block(root, p.pos, id, world_depth);
             }
     svo_world_insert(w, 0, root);
-    double t = now_ms();
+    double t = svo_now_ms();
     if (svo_world_generate_mip_tree(w, 0, nullptr) != 0) return world_fail("mips");
-    times[2] += float(now_ms() - t);
-    t = now_ms();
+    times[2] += float(svo_now_ms() - t);
+    t = svo_now_ms();
     if (svo_world_save_chunk(w, 0) != 0) return world_fail("save");
-    times[3] += float(now_ms() - t);
+    times[3] += float(svo_now_ms() - t);
     memcpy(ctx->proc->ms + 6, times, sizeof times);
     return SVO_OK;
 }

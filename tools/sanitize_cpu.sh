@@ -9,12 +9,21 @@ ROOT=$(cd "$(dirname "$0")/.." && pwd)
 OUT=/tmp/svo_asan
 mkdir -p "$OUT"
 SAN="-fsanitize=address,undefined -fno-sanitize-recover=undefined -fno-omit-frame-pointer -g -O1"
-g++ $SAN -std=c++17 -ffp-contract=off -fPIC -I"$ROOT/include" -c "$ROOT/octree-tracer_amd/csrc/svo_host.cpp" -o "$OUT/svo_host.o"
-HIPFLAGS="-O3 -std=c++17 --offload-arch=gfx950 -ffp-contract=off -fPIC -I$ROOT/include -Wno-unused-function"
-for f in svo_kernels svo_sched svo_proc; do /opt/rocm/bin/hipcc $HIPFLAGS -c "$ROOT/octree-tracer_amd/csrc/$f.hip" -o "$OUT/$f.o"; done
-/opt/rocm/bin/hipcc $HIPFLAGS -c "$ROOT/octree-tracer_amd/csrc/svo_abi.cpp" -o "$OUT/svo_abi.o"
-/opt/rocm/bin/hipcc $HIPFLAGS -c "$ROOT/octree-tracer_amd/csrc/svo_comm.cpp" -o "$OUT/svo_comm.o"
-/opt/rocm/bin/hipcc --offload-arch=gfx950 -fPIC -shared -o "$OUT/libsvo_hip.so" "$OUT/svo_kernels.o" "$OUT/svo_sched.o" "$OUT/svo_proc.o" "$OUT/svo_abi.o" "$OUT/svo_comm.o" "$OUT/svo_host.o" -ldl
+# the library's sources and flags are the Makefile's: svo_host.cpp goes through g++ with the sanitizers, the rest through hipcc
+csrc=$ROOT/octree-tracer_amd/csrc
+mkvar() { make -s --no-print-directory -C "$csrc" --eval="_v: ; @echo \$($1)" _v; }
+FLAGS=$(mkvar FLAGS)
+objs=()
+for f in $(mkvar SRC); do
+    o="$OUT/${f%.*}.o"
+    if [ "$f" = svo_host.cpp ]; then
+        (cd "$csrc" && g++ $SAN -std=c++17 -ffp-contract=off -fPIC -I../../include -c "$f" -o "$o")
+    else
+        (cd "$csrc" && ${HIPCC:-/opt/rocm/bin/hipcc} $FLAGS -c "$f" -o "$o")
+    fi
+    objs+=("$o")
+done
+(cd "$csrc" && ${HIPCC:-/opt/rocm/bin/hipcc} $FLAGS -shared -o "$OUT/libsvo_hip.so" "${objs[@]}" -ldl)
 gcc $SAN -std=c11 -ffp-contract=off -fno-fast-math -fPIC -pthread -shared -o "$OUT/libsvo_oracle.so" "$ROOT/oracle/svo_oracle.c" -lm -lpthread
 cd "$ROOT"
 LD_PRELOAD="$(gcc -print-file-name=libasan.so):$(gcc -print-file-name=libubsan.so)" \
