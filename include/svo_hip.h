@@ -315,7 +315,9 @@ int svo_proc_sdf(svo_ctx *ctx, const float *xyz, size_t n, float *out);
 int svo_proc_classify(svo_ctx *ctx, const svo_proc_params *params, uint8_t *cells_out);
 /* Times (ms) of the last svo_proc_generate_chunk: [0] classify kernel, [1] occupancy pyramid and ranks, [2] emit (device
  * events); [3] host wall time until the nodes are emitted, [4] read-back copy, [5] CpuOctree build.  Of the last
- * svo_world_generate, summed over its chunks: [6] GPU (wall), [7] read-back and build, [8] mips, [9] chunk file writes. */
+ * svo_world_generate, summed over its chunks: [6] GPU (wall), [7] read-back (no CpuOctree is built: the chunks are
+ * mipped on the device and written from the pinned stage), [8] mips (device events, and the root's on the host),
+ * [9] chunk file writes. */
 #define SVO_PROC_TIMES 10
 int svo_proc_timing(svo_ctx *ctx, float ms_out[SVO_PROC_TIMES]);
 
@@ -350,6 +352,38 @@ int svo_nodes_build_dense(svo_ctx *ctx, const uint32_t *grid, const svo_build_pa
  * events; waits for the emit), [5] host wall time of the call. */
 #define SVO_BUILD_TIMES 6
 int svo_build_timing(svo_ctx *ctx, float ms_out[SVO_BUILD_TIMES]);
+
+/* ---- mip-coloured chunk trees and streamable worlds built on the GPU ----
+ * Inputs as svo_nodes_build: xyz n * 3 u32 and colours n u32 (0x00RRGGBB) or NULL, DEVICE pointers on the ctx's device;
+ * the last voxel of a cell wins; a colour-0 voxel is an empty leaf on a path that exists.  A chunk tree is the host
+ * CpuOctree of sequential put_in_voxel(cell / 2^d * 2 - 1, rgb, d) with d its depth, in canonical breadth-first order and
+ * with the bytes of svo_cpu_octree_bin: interior pointer = index of its child group, leaf = SVO_CHUNK_OFFSET with the
+ * voxel's r g b (r = colour >> 16), empty = SVO_CHUNK_OFFSET with rgb 0.  Interior rgb and top_mip are what
+ * svo_world_generate_mip_tree computes.  The same bytes on every run and for any order of distinct voxels.
+ * Errors create nothing (no directory, no file) and leave the context usable: SVO_ERR_ARG for bad depths, n >= 2^31, NULL
+ * xyz with n > 0, a coordinate outside [0, 2^depth) (checked on the device) or an existing path ("File already exists");
+ * SVO_ERR_CAP (with a message) when a chunk's node count exceeds max_nodes or 2^31.  Blocking. */
+typedef struct svo_chunk_build_params {
+    uint32_t depth;          /* 1..21: cells in [0, 2^depth) per axis */
+    uint32_t world_depth;    /* svo_world_build: 1..4, chunk depth = depth - world_depth >= 1; svo_cpu_octree_build: 0 */
+    uint32_t default_colour; /* used when colours == NULL */
+    uint64_t max_nodes;      /* per chunk; 0 = 256 000 000 (procedural.rs:4) */
+} svo_chunk_build_params;
+/* One mip-coloured CpuOctree from a DEVICE voxel list (caller frees it); *out NULL for n == 0. */
+int svo_cpu_octree_build(svo_ctx *ctx, const uint32_t *xyz, const uint32_t *colours, size_t n, const svo_chunk_build_params *p,
+                         struct svo_cpu_octree **out);
+/* A chunked world in w's path (must not exist; created), as svo_world_generate lays one out: chunk (cx, cy, cz) = the top
+ * world_depth bits of the cells, id SVO_CHUNK_OFFSET / 2 + (cx * s + cy) * s + cz with s = 2^world_depth, local cells
+ * cell & (2^(depth - world_depth) - 1).  <id>.bin per non-empty chunk (each stays in w with its nodes dropped and its
+ * top_mip kept); the root references them by put_in_block in id order, is mipped over their top_mips and saved as 0.bin,
+ * last. */
+int svo_world_build(svo_ctx *ctx, struct svo_world *w, const uint32_t *xyz, const uint32_t *colours, size_t n,
+                    const svo_chunk_build_params *p);
+/* Times (ms) of the last svo_cpu_octree_build / svo_world_build: [0] keys, [1] sort, [2] levels, [3] count read-back,
+ * [4] emit, [5] mips (device events); [6] chunk read-back, [7] chunk files and root (svo_cpu_octree_build: the CpuOctree),
+ * [8] host wall time of the call. */
+#define SVO_WORLD_BUILD_TIMES 9
+int svo_world_build_timing(svo_ctx *ctx, float ms_out[SVO_WORLD_BUILD_TIMES]);
 
 /* ---- the adaptive step on the GPU ----
  * Device form of the streaming loop's list processing: after svo_adaptive_step the node buffer, the node positions, the

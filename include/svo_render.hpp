@@ -10,6 +10,7 @@
 #include <cstdint>
 #include <stdexcept>
 #include <memory>
+#include <optional>
 #include <string>
 #include <utility>
 #include <vector>
@@ -100,6 +101,16 @@ class CpuOctree {  // cpu_octree.rs:17-273
         if (!t) throw Error(SVO_ERR_ARG, err);
         return CpuOctree(t);
     }
+    // the mip-coloured tree of n voxels built on the GPU (svo_cpu_octree_build): xyz (n * 3) and colours (n,
+    // or null for `colour`) are DEVICE pointers; nothing for n == 0
+    static std::optional<CpuOctree> build(const Gpu &gpu, const uint32_t *xyz_dev, const uint32_t *colours_dev, size_t n, uint32_t depth,
+                                          uint32_t colour = 0xFFFFFF, uint64_t max_nodes = 0) {
+        const svo_chunk_build_params p{depth, 0, colour, max_nodes};
+        svo_cpu_octree *t = nullptr;
+        gpu.check(svo_cpu_octree_build(gpu.ctx(), xyz_dev, colours_dev, n, &p, &t));
+        if (!t) return std::nullopt;
+        return CpuOctree(t);
+    }
     svo_cpu_octree *raw() const { return t_; }
     svo_cpu_octree *release() { return std::exchange(t_, nullptr); }  // hand the tree to a World
 
@@ -153,6 +164,15 @@ class World {  // world.rs:5-336: chunk table with block instancing
         svo_world *w = svo_world_load(path.c_str(), err, sizeof err);
         if (!w) throw Error(SVO_ERR_ARG, err);
         return World(w);
+    }
+    // a new streamable world in directory `path` (must not exist) from n voxels, built on the GPU (svo_world_build,
+    // DESIGN.md 14); returns load_world(path)
+    static World build_world(const std::string &path, const Gpu &gpu, const uint32_t *xyz_dev, const uint32_t *colours_dev, size_t n,
+                             uint32_t depth, uint32_t world_depth = 1, uint32_t colour = 0xFFFFFF, uint64_t max_nodes = 0) {
+        World w(path);
+        const svo_chunk_build_params p{depth, world_depth, colour, max_nodes};
+        gpu.check(svo_world_build(gpu.ctx(), w.raw(), xyz_dev, colours_dev, n, &p));
+        return load_world(path);
     }
     ~World() { svo_world_free(w_); }
     World(World &&o) noexcept : w_(std::exchange(o.w_, nullptr)) {}

@@ -56,6 +56,16 @@ class BuildParams(C.Structure):
     ]
 
 
+class ChunkBuildParams(C.Structure):
+    """svo_chunk_build_params: a mip-coloured tree or a chunked world built on the GPU (include/svo_hip.h)."""
+    _fields_ = [
+        ("depth", C.c_uint32),
+        ("world_depth", C.c_uint32),
+        ("default_colour", C.c_uint32),
+        ("max_nodes", C.c_uint64),
+    ]
+
+
 class AdaptiveResult(C.Structure):
     """svo_adaptive_result: one device adaptive step (include/svo_hip.h)."""
     _fields_ = [
@@ -77,6 +87,7 @@ DEVICE_SYMBOLS = [
     "svo_proc_generate_chunk", "svo_world_generate", "svo_proc_sdf", "svo_proc_classify", "svo_proc_timing",
     "svo_nodes_build", "svo_nodes_build_dense", "svo_buffer_write", "svo_build_timing",
     "svo_adaptive_attach", "svo_adaptive_step", "svo_adaptive_download", "svo_adaptive_length", "svo_adaptive_timing",
+    "svo_cpu_octree_build", "svo_world_build", "svo_world_build_timing",
 ]
 HOST_SYMBOLS = [
     "svo_cpu_octree_new", "svo_cpu_octree_free", "svo_cpu_octree_len", "svo_cpu_octree_load_file",
@@ -167,6 +178,9 @@ def lib():
     sig("svo_nodes_build_dense", C.c_int, vp, vp, C.POINTER(BuildParams), C.POINTER(u64))
     sig("svo_buffer_write", C.c_int, vp, vp, vp, sz)
     sig("svo_build_timing", C.c_int, vp, fp)
+    sig("svo_cpu_octree_build", C.c_int, vp, vp, vp, sz, C.POINTER(ChunkBuildParams), C.POINTER(vp))
+    sig("svo_world_build", C.c_int, vp, vp, vp, vp, sz, C.POINTER(ChunkBuildParams))
+    sig("svo_world_build_timing", C.c_int, vp, fp)
     sig("svo_adaptive_attach", C.c_int, vp, vp, vp)
     sig("svo_adaptive_step", C.c_int, vp, vp, u32, vp, u32, C.POINTER(AdaptiveResult))
     sig("svo_adaptive_download", C.c_int, vp, vp)

@@ -49,6 +49,17 @@ class CpuOctree:
         return cls._wrap(lib().svo_cpu_octree_from_voxels(size, xyzi.ctypes.data, xyzi.shape[0],
                                                           palette.ctypes.data, err, 256), err)
 
+    @classmethod
+    def build(cls, gpu, coords, depth, colours=None, colour=0xFFFFFF, max_nodes=None):
+        """The mip-coloured tree of (N, 3) voxel cells in [0, 2^depth), depth 1..21, built on the GPU (svo_cpu_octree_build,
+        DESIGN.md 14): the tree sequential put_in_voxel + generate_mip_tree make, breadth-first.  colours: 0x00RRGGBB per
+        voxel (None: `colour`); the last voxel of a cell wins.  Torch tensors on gpu's device or numpy arrays.  None for
+        no voxels; a tree of more than max_nodes nodes (default 256 000 000) raises SvoError."""
+        out = C.c_void_p()
+        with _chunk_inputs(gpu, coords, depth, colours, colour, 0, max_nodes) as (xyz, col, n, p):
+            gpu.check(lib().svo_cpu_octree_build(gpu._h, xyz, col, n, C.byref(p), C.byref(out)))
+        return cls(_handle=out.value) if out.value else None
+
     def __del__(self):
         if getattr(self, "_h", None) and self._owned and lib is not None:  # (module globals are gone at interpreter exit)
             lib().svo_cpu_octree_free(self._h)
@@ -115,6 +126,40 @@ class CpuOctree:
         buf = np.empty(n, dtype=np.uint8)
         lib().svo_rsvo_write(self._h, buf.ctypes.data, n)
         return buf.tobytes()
+
+
+class _chunk_inputs:
+    """Device pointers and svo_chunk_build_params of a chunk build, as Render.build_nodes prepares them; the tensors
+    live until the with-block ends."""
+
+    def __init__(self, gpu, coords, depth, colours, colour, world_depth, max_nodes):
+        import torch
+        from ._lib import ChunkBuildParams
+        from .render import _device_u32
+        dev = torch.device("cuda", gpu.device)
+        self.xyz = _device_u32(coords, dev, clamp=True)
+        if self.xyz.dim() != 2 or self.xyz.shape[1] != 3:
+            raise ValueError(f"coords must be (N, 3), got {tuple(self.xyz.shape)}")
+        self.n = self.xyz.shape[0]
+        self.col = None
+        if colours is not None:
+            self.col = _device_u32(colours, dev, mask=0xFFFFFF).reshape(-1)
+            if self.col.numel() != self.n:
+                raise ValueError(f"{self.col.numel()} colours for {self.n} voxels")
+        p = ChunkBuildParams()
+        p.depth = max(0, int(depth))
+        p.world_depth = max(0, int(world_depth))
+        p.default_colour = int(colour) & 0xFFFFFF
+        p.max_nodes = int(max_nodes or 0)
+        self.p = p
+        torch.cuda.current_stream(dev).synchronize()  # the inputs were made on torch's stream
+
+    def __enter__(self):
+        n = self.n
+        return (self.xyz.data_ptr() if n else None, self.col.data_ptr() if self.col is not None and n else None, n, self.p)
+
+    def __exit__(self, *exc):
+        return False
 
 
 def vox_parse(data: bytes):

@@ -17,13 +17,22 @@
 // An element's parent rank is the exclusive scan of the parent-level flags at that element: every run before its own has
 // its flag (its last element) in front of it.  The dense grid skips keys and sort: lanes walk the cells in Morton order
 // and the flag is "cell non-zero", which yields the leaf level already sorted and unique.
+//
+// Chunk trees (svo_cpu_octree_build, svo_world_build) take the same keys, sort and level passes in kChunk
+// mode: the counting passes also find every chunk's run in each level's sorted keys, and the emit writes 8-byte <id>.bin
+// nodes per chunk, which the shared mip pass (svo_mip.h) colours bottom-up before they are staged chunk by chunk.
 #include <hip/hip_runtime.h>
 
+#include <sys/stat.h>
+
 #include <algorithm>
+#include <cerrno>
 #include <cstring>
 #include <string>
+#include <vector>
 
 #include "svo_ctx.h"
+#include "svo_mip.h"   // (chunk trees: the mip pass svo_proc.hip shares)
 #include "svo_scan.h"  // (tiles of kTile items: sort, scans and compactions alike)
 
 namespace {
@@ -33,7 +42,7 @@ constexpr uint64_t kMaxWords = SVO_VOXEL_OFFSET;  // 2^27: pointers and colours 
 constexpr int kErrSlot = 24;                      // counts[0..21]: nodes per level; counts[24]: range error
 constexpr int kCountSlots = 32;
 
-enum Mode { kDedupe = 0, kParent = 1, kDense = 2 };
+enum Mode { kDedupe = 0, kParent = 1, kDense = 2, kChunk = 3 };  // kChunk: kParent whose emit writes chunk trees
 
 __device__ inline uint64_t morton3(uint32_t x, uint32_t y, uint32_t z, uint32_t depth) {
     uint64_t k = 0;
@@ -183,6 +192,14 @@ struct LevelOut {
     uint32_t base_next;  // first word of the level below (interior nodes point there)
     uint32_t last;       // this is the leaf level
     uint32_t n_words;
+    // chunk emit (kChunk only; nodes null: counting pass).  Chunk c = key >> cshift owns the nodes from coff[c] on; its
+    // local level bases are cbase[c * stride + L]; start_up / start_here: the first index of chunk c in the level above /
+    // this level's unique keys
+    uint2 *nodes;
+    uint64_t n_nodes;
+    const uint64_t *coff;
+    const uint32_t *cbase, *start_up, *start_here;
+    uint32_t cshift, level, stride;  // level: this level's chunk-local number L
 };
 
 // Loads thread t's 16 consecutive items and their flags (bit j: item i0 + j ends a run / is kept).
@@ -207,7 +224,7 @@ __device__ inline uint32_t load_flags(const LevelIn &in, uint32_t m, uint32_t i0
         }
         return f;
     }
-    const uint32_t shift = M == kParent ? 3u : 0u;
+    const uint32_t shift = M == kParent || M == kChunk ? 3u : 0u;
     for (uint32_t j = 0; j < kPer; j++) k[j] = i0 + j < m ? in.keys[i0 + j] : 0ull;
     const uint64_t after = i0 + kPer < m ? in.keys[i0 + kPer] : 0ull;
     for (uint32_t j = 0; j < kPer; j++) {
@@ -246,15 +263,67 @@ __global__ __launch_bounds__(kThreads) void build_compact_kernel(LevelIn in, con
             const uint32_t word = out.last ? (SVO_VOXEL_OFFSET + (in.vals[i] & 0xFFFFFFu)) << 4 : (out.base_next + 8u * i) << 4;
             if (dst < out.n_words) out.words[dst] = word;  // (always: the counts and the ranks come from the same flags)
         }
+        if (M == kChunk && out.nodes) {  // node i of this level, in chunk c: its parent's rank within the chunk is r - start_up[c]
+            const uint32_t c = uint32_t(k[j] >> out.cshift);
+            const uint32_t *b = out.cbase + size_t(c) * out.stride;
+            const uint64_t dst = out.coff[c] + b[out.level] + 8u * (r - out.start_up[c]) + uint32_t(k[j] & 7u);
+            uint2 node;
+            if (out.last) {  // leaf: SVO_CHUNK_OFFSET, r g b of 0x00RRGGBB (Rgb::cpu_value)
+                const uint32_t v = in.vals[i];
+                node = make_uint2(SVO_CHUNK_OFFSET, (v >> 16 & 0xFFu) | (v & 0xFF00u) | (v & 0xFFu) << 16);
+            } else {  // interior: its child group, behind this level in the chunk; rgb comes from the mip pass
+                node = make_uint2(b[out.level + 1] + 8u * (i - out.start_here[c]), 0u);
+            }
+            if (dst < out.n_nodes) out.nodes[dst] = node;  // (always, as above)
+        }
         if ((f >> j) & 1u) {
             if (r < out.cap) {
-                out.keys[r] = M == kParent ? k[j] >> 3 : (M == kDense ? k[j] & 0xFFFFFFFFu : k[j]);
+                out.keys[r] = M == kParent || M == kChunk ? k[j] >> 3 : (M == kDense ? k[j] & 0xFFFFFFFFu : k[j]);
                 if (M == kDedupe) out.colours[r] = (in.colours ? in.colours[in.vals[i]] : in.colour) & 0xFFFFFFu;
                 if (M == kDense) out.colours[r] = uint32_t(k[j] >> 32) & 0xFFFFFFu;
             }
             r++;
         }
     }
+}
+
+// ---- chunk trees ----
+// The runs of a level's sorted unique keys per chunk (c = key >> shift < n_chunks): start[c] = the first index of chunk c,
+// start[n_chunks] = m.  Lane i writes the starts of the chunks from the previous key's chunk (exclusive) to its own
+// (inclusive), the last lane those behind it: every entry is written once, without atomics.
+__global__ __launch_bounds__(kThreads) void build_runs_kernel(const uint64_t *keys, const uint32_t *m_dev, uint32_t m_max,
+                                                              uint32_t shift, uint32_t n_chunks, uint32_t *start) {
+    const uint32_t m = input_count(m_dev, m_max);
+    const uint32_t i = blockIdx.x * kThreads + threadIdx.x;
+    if (i >= m) return;
+    const uint32_t c = min(uint32_t(keys[i] >> shift), n_chunks - 1);
+    const uint32_t from = i ? min(uint32_t(keys[i - 1] >> shift), n_chunks - 1) + 1 : 0u;
+    for (uint32_t cc = from; cc <= c; cc++) start[cc] = i;
+    if (i + 1 == m)
+        for (uint32_t cc = c + 1; cc <= n_chunks; cc++) start[cc] = m;
+}
+
+// One level of every chunk: lane j is slot j of the level's groups, in chunk order (8 * start_up[c] is chunk c's first
+// slot); its node is cbase[c * stride + level] + the slot's offset in the chunk.
+__global__ __launch_bounds__(kThreads) void build_mip_kernel(uint2 *nodes, const uint64_t *coff, const uint32_t *cbase,
+                                                             const uint32_t *start_up, uint32_t n_chunks, uint32_t stride,
+                                                             uint32_t level, uint32_t n_lanes) {
+    const uint32_t j = blockIdx.x * kThreads + threadIdx.x;
+    if (j >= n_lanes) return;
+    const uint32_t p = j >> 3;
+    uint32_t lo = 0, hi = n_chunks;  // the chunk c with start_up[c] <= p < start_up[c + 1]
+    while (hi - lo > 1) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (start_up[mid] <= p) lo = mid;
+        else hi = mid;
+    }
+    const uint32_t *b = cbase + size_t(lo) * stride;
+    mip_node(nodes + coff[lo], b[level] + (j - 8u * start_up[lo]), b[stride - 1]);
+}
+
+__global__ __launch_bounds__(kThreads) void build_fill_kernel(uint2 *nodes, uint64_t n) {
+    for (uint64_t i = blockIdx.x * uint64_t(kThreads) + threadIdx.x; i < n; i += uint64_t(gridDim.x) * kThreads)
+        nodes[i] = make_uint2(SVO_CHUNK_OFFSET, 0u);
 }
 
 }  // namespace
@@ -276,13 +345,29 @@ struct svo_build_state {
     hipEvent_t ev[7] = {};          // start, keys, sort, levels, read-back, emit start, emit end
     bool sorted = false, timed = true;  // the last build sorted / its device times are in ms
     float ms[SVO_BUILD_TIMES] = {};
+    // chunk trees (svo_world_build, svo_cpu_octree_build)
+    uint32_t *runs = nullptr, *runs_host = nullptr;  // per level 0..21: n_chunks + 1 chunk starts (device / pinned)
+    size_t runs_items = 0, runs_host_items = 0;
+    uint32_t *cbase = nullptr;  // per chunk: chunk-local level bases 1 .. chunk_depth + 1 (the last = its node count)
+    size_t cbase_items = 0;
+    uint64_t *coff = nullptr;   // per chunk: its first node in `nodes`
+    size_t coff_items = 0;
+    uint2 *nodes = nullptr;     // every chunk's nodes, one chunk after another
+    size_t node_items = 0;
+    void *stage = nullptr;      // pinned: one chunk's bytes on their way to a file or a CpuOctree
+    size_t stage_bytes = 0;
+    hipEvent_t cev[3] = {};     // emit start, emit end, mips end
+    float cms[SVO_WORLD_BUILD_TIMES] = {};
 
     ~svo_build_state() {
         for (void *p : {(void *)keys[0], (void *)keys[1], (void *)keys[2], (void *)vals[0], (void *)vals[1], (void *)leaf_colours,
-                        (void *)hist, (void *)tiles, (void *)counts})
+                        (void *)hist, (void *)tiles, (void *)counts, (void *)runs, (void *)cbase, (void *)coff, (void *)nodes})
             if (p) (void)hipFree(p);
-        if (counts_host) (void)hipHostFree(counts_host);
+        for (void *p : {(void *)counts_host, (void *)runs_host, stage})
+            if (p) (void)hipHostFree(p);
         for (hipEvent_t e : ev)
+            if (e) (void)hipEventDestroy(e);
+        for (hipEvent_t e : cev)
             if (e) (void)hipEventDestroy(e);
     }
 };
@@ -345,10 +430,18 @@ int level_pass(svo_ctx *ctx, const LevelIn &in, const LevelOut &out, uint64_t bo
     return SVO_OK;
 }
 
+// A chunked build: chunk c of level L's keys is key >> 3 * (L - world_depth).  Counting passes (nodes null)
+// also write the chunk runs of levels world_depth .. depth - 1 into runs; the emit writes chunk trees into nodes.
+struct ChunkPlan {
+    uint32_t world_depth, n_chunks;
+    uint2 *nodes;
+    uint64_t n_nodes;
+};
+
 // The parent passes L = depth .. stop over the leaf level in keys[2] / leaf_colours: level L's unique keys in, level
 // L-1's out (keys[0] and keys[1] by turns), m_{L-1} into counts[L-1].  With words: the emit, level L's slots too.
 int parent_passes(svo_ctx *ctx, uint32_t depth, uint32_t stop, const uint64_t *bound, uint32_t *words, const uint64_t *base,
-                  uint64_t n_words) {
+                  uint64_t n_words, const ChunkPlan *plan = nullptr) {
     svo_build_state *s = ctx->build.get();
     const uint64_t *src = s->keys[2];
     for (uint32_t l = depth, turn = 0; l >= stop; l--, turn ^= 1) {
@@ -367,7 +460,30 @@ int parent_passes(svo_ctx *ctx, uint32_t depth, uint32_t stop, const uint64_t *b
             out.last = l == depth;
             out.n_words = (uint32_t)n_words;
         }
-        int rc = level_pass<kParent>(ctx, in, out, bound[l], s->counts + l - 1);
+        int rc;
+        if (plan) {
+            const uint32_t wd = plan->world_depth, row = plan->n_chunks + 1;
+            if (!plan->nodes && l < depth && l >= wd) {
+                build_runs_kernel<<<std::max(svo_div_up(bound[l], kThreads), 1u), kThreads, 0, ctx->stream>>>(
+                    src, s->counts + l, in.m_max, 3 * (l - wd), plan->n_chunks, s->runs + size_t(l) * row);
+                HIP_TRY(ctx, hipGetLastError());
+            }
+            if (plan->nodes) {
+                out.nodes = plan->nodes;
+                out.n_nodes = plan->n_nodes;
+                out.coff = s->coff;
+                out.cbase = s->cbase;
+                out.start_up = s->runs + size_t(l - 1) * row;
+                out.start_here = s->runs + size_t(l) * row;
+                out.cshift = 3 * (l - wd);
+                out.level = l - wd;
+                out.stride = depth - wd + 2;
+                out.last = l == depth;
+            }
+            rc = level_pass<kChunk>(ctx, in, out, bound[l], s->counts + l - 1);
+        } else {
+            rc = level_pass<kParent>(ctx, in, out, bound[l], s->counts + l - 1);
+        }
         if (rc) return rc;
         src = s->keys[turn];
     }
@@ -487,6 +603,183 @@ int svo_build_scan_u32(svo_ctx *ctx, uint32_t *a, uint32_t n) {
     return scan_u32(ctx, a, n);
 }
 
+namespace {
+
+constexpr uint64_t kDefaultMaxNodes = 256000000ull;  // procedural.rs:4
+
+// The chunk trees of n voxels: keys and sort as svo_nodes_build, the counting passes with the chunk runs
+// of every level, one read-back of the counts and runs, the caps, then (directory `dir` made when given) the emit into
+// one buffer, the mips and, chunk by chunk in id order, one copy into the pinned stage that take(id index, bytes, nodes)
+// consumes.  Nothing is created before every cap has been checked.
+template <class Take>
+int chunk_build(svo_ctx *ctx, const uint32_t *xyz, const uint32_t *colours, size_t n, const svo_chunk_build_params *p,
+                const std::string &dir, Take take) {
+    const double t0 = svo_now_ms();
+    const uint32_t depth = p->depth, wd = p->world_depth, cd = depth - wd, n_chunks = 1u << (3 * wd), row = n_chunks + 1;
+    const uint64_t cap = std::min<uint64_t>(p->max_nodes ? p->max_nodes : kDefaultMaxNodes, 1ull << 31);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (!n) {  // nothing to build: the empty world is its root alone
+        if (!dir.empty() && mkdir(dir.c_str(), 0777) != 0)
+            return svo_fail(ctx, errno == EEXIST ? SVO_ERR_ARG : SVO_ERR_STATE,
+                            errno == EEXIST ? "File already exists" : "cannot create " + dir + ": " + strerror(errno));
+        if (ctx->build) memset(ctx->build->cms, 0, sizeof ctx->build->cms);
+        return SVO_OK;
+    }
+    const uint32_t nt = svo_div_up(n, kTile);
+    int rc = ensure_state(ctx, n, std::max<uint64_t>(n, 256ull * nt), 256ull * nt);
+    if (rc) return rc;
+    svo_build_state *s = ctx->build.get();
+    if (!s->cev[0])
+        for (hipEvent_t &e : s->cev) HIP_TRY(ctx, hipEventCreate(&e));
+    const size_t runs_items = size_t(depth + 1) * row;
+    if ((rc = svo_grow(ctx, &s->runs_items, runs_items, &s->runs))) return rc;
+    if ((rc = svo_grow_pinned(ctx, &s->runs_host_items, runs_items, &s->runs_host))) return rc;
+    memset(s->cms, 0, sizeof s->cms);
+
+    HIP_TRY(ctx, hipEventRecord(s->ev[0], ctx->stream));
+    HIP_TRY(ctx, hipMemsetAsync(s->counts, 0, kCountSlots * sizeof(uint32_t), ctx->stream));
+    HIP_TRY(ctx, hipMemsetAsync(s->runs, 0, runs_items * sizeof(uint32_t), ctx->stream));
+    build_keys_kernel<<<svo_div_up(n, kThreads), kThreads, 0, ctx->stream>>>(xyz, (uint32_t)n, depth, s->keys[0], s->vals[0],
+                                                                             s->counts + kErrSlot);
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, hipEventRecord(s->ev[1], ctx->stream));
+    const uint32_t passes = (3 * depth + 7) / 8;
+    if ((rc = sort_passes(ctx, (uint32_t)n, passes))) return rc;
+    HIP_TRY(ctx, hipEventRecord(s->ev[2], ctx->stream));
+    LevelIn in{};
+    in.keys = s->keys[passes & 1];
+    in.vals = s->vals[passes & 1];
+    in.colours = colours;
+    in.colour = p->default_colour;
+    in.m_max = (uint32_t)n;
+    LevelOut out{};
+    out.keys = s->keys[2];
+    out.colours = s->leaf_colours;
+    out.cap = (uint32_t)s->items;
+    if ((rc = level_pass<kDedupe>(ctx, in, out, n, s->counts + depth))) return rc;
+    uint64_t bound[23] = {};
+    bound[depth] = n;
+    for (uint32_t l = depth; l-- > 0;) bound[l] = std::min<uint64_t>(bound[l + 1], 1ull << (3 * l));
+    ChunkPlan plan{wd, n_chunks, nullptr, 0};
+    if ((rc = parent_passes(ctx, depth, std::max(wd, 1u), bound, nullptr, nullptr, 0, &plan))) return rc;
+    HIP_TRY(ctx, hipEventRecord(s->ev[3], ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(s->counts_host, s->counts, kCountSlots * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(s->runs_host, s->runs, runs_items * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipEventRecord(s->ev[4], ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    const uint32_t *m = s->counts_host;
+    if (m[kErrSlot]) return svo_fail(ctx, SVO_ERR_ARG, "a voxel coordinate is outside [0, 2^depth) (depth " + std::to_string(depth) + ")");
+
+    // every chunk's local level bases (breadth-first: level 1 at 0, level L + 1 behind level L's groups) and its place
+    const uint32_t stride = cd + 2;
+    std::vector<uint32_t> cbase(size_t(n_chunks) * stride, 0u);
+    std::vector<uint64_t> coff(n_chunks, 0ull);
+    uint64_t total = 0, largest = 0;
+    for (uint32_t c = 0; c < n_chunks; c++) {
+        auto count = [&](uint32_t l) -> uint64_t {  // chunk c's nodes at level l
+            const uint32_t *r = s->runs_host + size_t(l) * row;
+            return l == 0 ? 1u : r[c + 1] - r[c];
+        };
+        uint32_t *b = cbase.data() + size_t(c) * stride;
+        uint64_t at = 0;
+        for (uint32_t L = 1; L <= cd; L++) {
+            b[L] = (uint32_t)at;
+            at += 8 * count(wd + L - 1);
+            if (at > cap) {
+                uint32_t cx = 0, cy = 0, cz = 0;
+                for (uint32_t k = 0; k < wd; k++) {
+                    cx |= (c >> (3 * k + 2) & 1u) << k;
+                    cy |= (c >> (3 * k + 1) & 1u) << k;
+                    cz |= (c >> (3 * k) & 1u) << k;
+                }
+                return svo_fail(ctx, SVO_ERR_CAP, "chunk (" + std::to_string(cx) + ", " + std::to_string(cy) + ", " + std::to_string(cz) +
+                                                      ") needs more than " + std::to_string(cap) + " nodes (max_nodes " +
+                                                      std::to_string(p->max_nodes) + ", 0 = 256 000 000; at most 2^31)");
+            }
+        }
+        b[cd + 1] = (uint32_t)at;
+        coff[c] = total;
+        total += at;
+        largest = std::max(largest, at);
+    }
+    if ((rc = svo_grow(ctx, &s->cbase_items, cbase.size(), &s->cbase))) return rc;
+    if ((rc = svo_grow(ctx, &s->coff_items, coff.size(), &s->coff))) return rc;
+    if ((rc = svo_grow(ctx, &s->node_items, total, &s->nodes))) return rc;
+    if ((rc = svo_grow_pinned(ctx, &s->stage_bytes, largest * 8, &s->stage))) return rc;
+    if (!dir.empty() && mkdir(dir.c_str(), 0777) != 0)
+        return svo_fail(ctx, errno == EEXIST ? SVO_ERR_ARG : SVO_ERR_STATE,
+                        errno == EEXIST ? "File already exists" : "cannot create " + dir + ": " + strerror(errno));
+
+    // emit and mips
+    HIP_TRY(ctx, hipMemcpyAsync(s->cbase, cbase.data(), cbase.size() * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(s->coff, coff.data(), coff.size() * sizeof(uint64_t), hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, hipEventRecord(s->cev[0], ctx->stream));
+    build_fill_kernel<<<std::max(std::min(svo_div_up(total, kThreads), 65536u), 1u), kThreads, 0, ctx->stream>>>(s->nodes, total);
+    HIP_TRY(ctx, hipGetLastError());
+    for (uint32_t l = 1; l <= depth; l++) bound[l] = m[l];
+    plan.nodes = s->nodes;
+    plan.n_nodes = total;
+    if ((rc = parent_passes(ctx, depth, wd + 1, bound, nullptr, nullptr, 0, &plan))) return rc;
+    HIP_TRY(ctx, hipEventRecord(s->cev[1], ctx->stream));
+    for (uint32_t l = depth - 1; l > wd; l--) {  // bottom-up; level `depth` is all leaves
+        const uint32_t lanes = 8u * m[l - 1];
+        build_mip_kernel<<<svo_div_up(lanes, kThreads), kThreads, 0, ctx->stream>>>(s->nodes, s->coff, s->cbase, s->runs + size_t(l - 1) * row,
+                                                                                     n_chunks, stride, l - wd, lanes);
+        HIP_TRY(ctx, hipGetLastError());
+    }
+    HIP_TRY(ctx, hipEventRecord(s->cev[2], ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+
+    // chunks in id order: (cx * side + cy) * side + cz, chunk index = Morton code of (cx, cy, cz)
+    const uint32_t side = 1u << wd;
+    double copy_ms = 0, take_ms = 0;
+    for (uint32_t id = 0; id < n_chunks; id++) {
+        const uint32_t cx = id / (side * side), cy = id / side % side, cz = id % side;
+        uint32_t c = 0;
+        for (uint32_t b = 0; b < wd; b++) c |= (cx >> b & 1u) << (3 * b + 2) | (cy >> b & 1u) << (3 * b + 1) | (cz >> b & 1u) << (3 * b);
+        const uint64_t nodes = cbase[size_t(c) * stride + cd + 1];
+        if (!nodes) continue;
+        double t = svo_now_ms();
+        HIP_TRY(ctx, hipMemcpyAsync(s->stage, s->nodes + coff[c], nodes * 8, hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        copy_ms += svo_now_ms() - t;
+        t = svo_now_ms();
+        if ((rc = take(id, (const uint8_t *)s->stage, nodes))) return rc;
+        take_ms += svo_now_ms() - t;
+    }
+    const int first[6] = {0, 1, 2, 3, 0, 1}, last[6] = {1, 2, 3, 4, 1, 2};
+    for (int k = 0; k < 6; k++)
+        HIP_TRY(ctx, hipEventElapsedTime(&s->cms[k], k < 4 ? s->ev[first[k]] : s->cev[first[k]], k < 4 ? s->ev[last[k]] : s->cev[last[k]]));
+    s->cms[6] = float(copy_ms);
+    s->cms[7] = float(take_ms);
+    s->cms[8] = float(svo_now_ms() - t0);
+    return SVO_OK;
+}
+
+// top_mip of a chunk: the mip of its root group (nodes 0..7 in the <id>.bin layout)
+void chunk_top_mip(const uint8_t *bytes, uint8_t rgb[3]) {
+    uint32_t v[8];
+    for (int c = 0; c < 8; c++) v[c] = bytes[8 * c + 4] | bytes[8 * c + 5] << 8 | bytes[8 * c + 6] << 16;
+    const uint32_t t = mip_of(v);
+    rgb[0] = t & 0xFFu;
+    rgb[1] = t >> 8 & 0xFFu;
+    rgb[2] = t >> 16 & 0xFFu;
+}
+
+int check_chunk_params(svo_ctx *ctx, const uint32_t *xyz, size_t n, const svo_chunk_build_params *p, bool world) {
+    if (!p) return svo_fail(ctx, SVO_ERR_ARG, "null params");
+    if (p->depth < 1 || p->depth > 21) return svo_fail(ctx, SVO_ERR_ARG, "depth must be 1..21 (got " + std::to_string(p->depth) + ")");
+    if (!world && p->world_depth != 0) return svo_fail(ctx, SVO_ERR_ARG, "world_depth must be 0 for a single tree");
+    if (world && (p->world_depth < 1 || p->world_depth > 4 || p->world_depth >= p->depth))
+        return svo_fail(ctx, SVO_ERR_ARG, "world_depth must be 1..4 and below depth (got " + std::to_string(p->world_depth) +
+                                              ", depth " + std::to_string(p->depth) + ")");
+    if (n >= (1ull << 31)) return svo_fail(ctx, SVO_ERR_ARG, "at most 2^31 - 1 voxels per build");
+    if (!xyz && n) return svo_fail(ctx, SVO_ERR_ARG, "null coordinates");
+    return SVO_OK;
+}
+
+}  // namespace
+
 extern "C" {
 
 int svo_nodes_build(svo_ctx *ctx, const uint32_t *xyz, const uint32_t *colours, size_t n, const svo_build_params *p,
@@ -576,6 +869,81 @@ int svo_build_timing(svo_ctx *ctx, float ms_out[SVO_BUILD_TIMES]) {
         s->timed = true;
     }
     memcpy(ms_out, ctx->build->ms, sizeof ctx->build->ms);
+    return SVO_OK;
+}
+
+int svo_cpu_octree_build(svo_ctx *ctx, const uint32_t *xyz, const uint32_t *colours, size_t n, const svo_chunk_build_params *p,
+                         svo_cpu_octree **out) {
+    if (!ctx) return SVO_ERR_ARG;
+    if (!out) return svo_fail(ctx, SVO_ERR_ARG, "null output");
+    *out = nullptr;
+    int rc = check_chunk_params(ctx, xyz, n, p, false);
+    if (rc) return rc;
+    svo_cpu_octree *tree = nullptr;
+    rc = chunk_build(ctx, xyz, colours, n, p, std::string(), [&](uint32_t, const uint8_t *bytes, uint64_t nodes) -> int {
+        char why[128] = "";
+        tree = svo_cpu_octree_from_bin(bytes, nodes * 8, why, sizeof why);
+        if (!tree) return svo_fail(ctx, SVO_ERR_STATE, std::string("emitted tree rejected: ") + why);
+        uint8_t top[3];
+        chunk_top_mip(bytes, top);
+        svo_cpu_octree_set_top_mip(tree, top);
+        return SVO_OK;
+    });
+    if (rc) {
+        svo_cpu_octree_free(tree);
+        return rc;
+    }
+    *out = tree;
+    return SVO_OK;
+}
+
+int svo_world_build(svo_ctx *ctx, svo_world *w, const uint32_t *xyz, const uint32_t *colours, size_t n, const svo_chunk_build_params *p) {
+    if (!ctx) return SVO_ERR_ARG;
+    if (!w) return svo_fail(ctx, SVO_ERR_ARG, "null world");
+    int rc = check_chunk_params(ctx, xyz, n, p, true);
+    if (rc) return rc;
+    const std::string path = svo_world_path(w);
+    if (path.empty()) return svo_fail(ctx, SVO_ERR_ARG, "world has no path");
+    struct stat st;
+    if (stat(path.c_str(), &st) == 0) return svo_fail(ctx, SVO_ERR_ARG, "File already exists");  // World::generate_world's words
+    const uint32_t wd = p->world_depth, side = 1u << wd;
+    const float voxel = 2.0f / float(side);
+    svo_cpu_octree *root = svo_cpu_octree_new(0);
+    // as svo_world_generate: every non-empty chunk saved and kept as its top_mip, referenced from the root in id order
+    rc = chunk_build(ctx, xyz, colours, n, p, path, [&](uint32_t i, const uint8_t *bytes, uint64_t nodes) -> int {
+        const uint32_t id = SVO_CHUNK_OFFSET / 2 + i;
+        if (svo_world_write_chunk(w, id, bytes, nodes * 8) != 0)
+            return svo_fail(ctx, SVO_ERR_STATE, std::string("save: ") + svo_world_last_error(w));
+        uint8_t top[3];
+        chunk_top_mip(bytes, top);
+        svo_cpu_octree *chunk = svo_cpu_octree_new(0);
+        svo_cpu_octree_drop_nodes(chunk);
+        svo_cpu_octree_set_top_mip(chunk, top);
+        svo_world_insert(w, id, chunk);
+        const float pos[3] = {float(i / (side * side)) * voxel - 1.0f, float(i / side % side) * voxel - 1.0f, float(i % side) * voxel - 1.0f};
+        svo_cpu_octree_put_in_block(root, pos, id, wd);
+        return SVO_OK;
+    });
+    if (rc) {
+        svo_cpu_octree_free(root);
+        return rc;
+    }
+    const double t = svo_now_ms();
+    svo_world_insert(w, 0, root);
+    if (svo_world_generate_mip_tree(w, 0, nullptr) != 0 || svo_world_save_chunk(w, 0) != 0)
+        return svo_fail(ctx, SVO_ERR_STATE, std::string("root: ") + svo_world_last_error(w));
+    const float root_ms = float(svo_now_ms() - t);
+    if (ctx->build) {
+        ctx->build->cms[7] += root_ms;
+        ctx->build->cms[8] += root_ms;
+    }
+    return SVO_OK;
+}
+
+int svo_world_build_timing(svo_ctx *ctx, float ms_out[SVO_WORLD_BUILD_TIMES]) {
+    if (!ctx || !ms_out) return SVO_ERR_ARG;
+    if (!ctx->build) return svo_fail(ctx, SVO_ERR_STATE, "no chunk tree built on this context yet");
+    memcpy(ms_out, ctx->build->cms, sizeof ctx->build->cms);
     return SVO_OK;
 }
 

@@ -172,9 +172,13 @@ void svo_comm_release(svo_ctx *ctx);
 // passes on the ctx stream; both use the builder's workspace
 int svo_build_sort_u32(svo_ctx *ctx, const uint32_t *in, uint32_t n, uint32_t *out);
 int svo_build_scan_u32(svo_ctx *ctx, uint32_t *a, uint32_t n);
-// svo_host.cpp (internal helpers of svo_world_generate)
+// svo_host.cpp (internal helpers of svo_world_generate and the chunk builder, svo_build.hip)
 std::string svo_world_path(const svo_world *w);
 void svo_cpu_octree_drop_nodes(svo_cpu_octree *t);  // frees the nodes, keeps top_mip (world.rs:122)
+void svo_cpu_octree_set_top_mip(svo_cpu_octree *t, const uint8_t rgb[3]);
+void svo_cpu_octree_top_mip(const svo_cpu_octree *t, uint8_t rgb[3]);
+// <w's path>/<id>.bin from `len` bytes in the <id>.bin layout; 0 or -1 (svo_world_last_error says why)
+int svo_world_write_chunk(svo_world *w, uint32_t id, const void *bytes, size_t len);
 // svo_host.cpp (internal helpers of the device adaptive state): the octree's words, positions (3 floats per node) and hole
 // stack (bottom first) as they are; svo_octree_assign replaces all three and clears the dirty set
 size_t svo_octree_state(const svo_octree *o, const uint32_t **nodes, const float **positions, std::vector<uint32_t> &holes);

@@ -1211,6 +1211,16 @@ std::string svo_world_path(const svo_world *w) { return w->path; }
 
 void svo_cpu_octree_drop_nodes(svo_cpu_octree *t) { std::vector<svo_cpu_octree::Node>().swap(t->nodes); }
 
+void svo_cpu_octree_set_top_mip(svo_cpu_octree *t, const uint8_t rgb[3]) { t->top_mip = Rgb{rgb[0], rgb[1], rgb[2]}; }
+void svo_cpu_octree_top_mip(const svo_cpu_octree *t, uint8_t rgb[3]) { rgb[0] = t->top_mip.r; rgb[1] = t->top_mip.g; rgb[2] = t->top_mip.b; }
+
+int svo_world_write_chunk(svo_world *w, uint32_t id, const void *bytes, size_t len) {
+    FILE *f = fopen(chunk_file(*w, id).c_str(), "wb");
+    if (!f) return world_fail(w, "cannot create " + chunk_file(*w, id));
+    const bool ok = fwrite(bytes, 1, len, f) == len;
+    return fclose(f) == 0 && ok ? 0 : world_fail(w, "short write to " + chunk_file(*w, id));
+}
+
 // The device adaptive state (svo_adapt.hip) uploads and restores the octree as it is: words, positions (three floats per
 // node, Vec3's layout), hole stack (bottom first).
 size_t svo_octree_state(const svo_octree *o, const uint32_t **nodes, const float **positions, std::vector<uint32_t> &holes) {

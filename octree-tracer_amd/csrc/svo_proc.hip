@@ -10,6 +10,7 @@
 //              the tile counts, tile re-scan): every interior node's rank, hence its child group's index, and the
 //              exact node count, which is read back and checked before anything is emitted
 //   emit       one lane per interior parent: its 8-node group in the 8-byte <id>.bin layout
+//   mips       (svo_world_generate only) block leaves take their block's top_mip, then svo_mip.h's pass bottom-up
 //
 // All work runs on the context's stream.  Sizes come from the count pass; there are no atomics and no retries.
 #include <hip/hip_runtime.h>
@@ -23,6 +24,7 @@
 
 #include "svo_ctx.h"
 #include "svo_host.h"
+#include "svo_mip.h"   // (the world path mips its chunks on the device, as svo_world_build does)
 #include "svo_scan.h"  // (a level's mask bytes are scanned in tiles of kTile)
 
 namespace {
@@ -257,6 +259,17 @@ __global__ __launch_bounds__(256) void proc_sdf_kernel(const float *xyz, uint32_
     out[i] = sdf::eval(xyz[3u * i], xyz[3u * i + 1u], xyz[3u * i + 2u]);
 }
 
+// generate_world's block leaves: a leaf SVO_CHUNK_OFFSET + b takes block b's top_mip (world.rs:249-253); table[0] = 0
+struct BlockMips {
+    uint32_t rgb[9];
+};
+__global__ __launch_bounds__(256) void proc_block_mips_kernel(uint2 *nodes, uint32_t first, uint32_t count, BlockMips table) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= count) return;
+    const uint32_t b = nodes[first + i].x - kChunkOffset;
+    if (b < 9u) nodes[first + i].y = table.rgb[b];
+}
+
 uint64_t pad_tile(uint64_t n) { return (n + kTile - 1) / kTile * kTile; }
 
 }  // namespace
@@ -279,6 +292,7 @@ struct svo_proc_state {
     uint8_t *stage = nullptr;  // pinned read-back buffer
     size_t stage_bytes = 0;
     hipEvent_t ev[4] = {};
+    hipEvent_t mev[2] = {};  // svo_world_generate: around a chunk's device mips
     float ms[SVO_PROC_TIMES] = {};
 
     ~svo_proc_state() {
@@ -287,6 +301,8 @@ struct svo_proc_state {
         if (totals_host) (void)hipHostFree(totals_host);
         if (stage) (void)hipHostFree(stage);
         for (hipEvent_t e : ev)
+            if (e) (void)hipEventDestroy(e);
+        for (hipEvent_t e : mev)
             if (e) (void)hipEventDestroy(e);
     }
 };
@@ -316,6 +332,7 @@ int ensure_state(svo_ctx *ctx, uint32_t depth) {
     if (!ctx->proc) {
         ctx->proc = svo_workspace_new<svo_proc_state>();
         for (hipEvent_t &e : ctx->proc->ev) HIP_TRY(ctx, hipEventCreate(&e));
+        for (hipEvent_t &e : ctx->proc->mev) HIP_TRY(ctx, hipEventCreate(&e));
         HIP_TRY(ctx, hipHostMalloc((void **)&ctx->proc->totals_host, 16 * sizeof(uint32_t), hipHostMallocDefault));
         HIP_TRY(ctx, hipMalloc((void **)&ctx->proc->totals, 16 * sizeof(uint32_t)));
     }
@@ -409,16 +426,18 @@ int svo_proc_classify(svo_ctx *ctx, const svo_proc_params *params, uint8_t *cell
     return SVO_OK;
 }
 
-int svo_proc_generate_chunk(svo_ctx *ctx, const svo_proc_params *params, svo_cpu_octree **out) {
-    if (!ctx) return SVO_ERR_ARG;
-    if (!out) return svo_fail(ctx, SVO_ERR_ARG, "null output");
-    *out = nullptr;
-    int rc = check_params(ctx, params);
-    if (rc) return rc;
+}  // extern "C"
+
+namespace {
+
+// svo_proc_generate_chunk up to the emitted nodes: s->out holds *n_nodes_out nodes (0: no solid cell) in the <id>.bin
+// layout, level L at base[L] .. base[L + 1]; ms[0..3] are set but for the events' [0..2].
+int emit_chunk(svo_ctx *ctx, const svo_proc_params *params, double t0, uint64_t base[11], uint64_t *n_nodes_out) {
+    *n_nodes_out = 0;
     const uint64_t max_nodes = params->max_nodes ? params->max_nodes : kDefaultMaxNodes;
-    const double t0 = svo_now_ms();
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    if ((rc = ensure_state(ctx, params->chunk_depth))) return rc;
+    int rc = ensure_state(ctx, params->chunk_depth);
+    if (rc) return rc;
     svo_proc_state *s = ctx->proc.get();
     const uint32_t depth = params->chunk_depth;
 
@@ -445,7 +464,7 @@ int svo_proc_generate_chunk(svo_ctx *ctx, const svo_proc_params *params, svo_cpu
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
 
     // breadth-first bases: level 1 (the root group) at 0, level L+1 behind level L's 8 * interior(L-1) nodes
-    uint64_t base[11] = {0, 0};
+    base[0] = base[1] = 0;
     for (uint32_t l = 1; l <= depth; l++) base[l + 1] = base[l] + 8ull * s->totals_host[l - 1];
     const uint64_t n_nodes = base[depth + 1];
     if (s->totals_host[0] == 0) {  // no solid cell: the reference's "len <= 8 -> None" (procedural.rs:167)
@@ -468,6 +487,27 @@ int svo_proc_generate_chunk(svo_ctx *ctx, const svo_proc_params *params, svo_cpu
     }
     HIP_TRY(ctx, hipEventRecord(s->ev[3], ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    s->ms[3] = float(svo_now_ms() - t0);
+    *n_nodes_out = n_nodes;
+    return SVO_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int svo_proc_generate_chunk(svo_ctx *ctx, const svo_proc_params *params, svo_cpu_octree **out) {
+    if (!ctx) return SVO_ERR_ARG;
+    if (!out) return svo_fail(ctx, SVO_ERR_ARG, "null output");
+    *out = nullptr;
+    int rc = check_params(ctx, params);
+    if (rc) return rc;
+    const double t0 = svo_now_ms();
+    uint64_t base[11], n_nodes = 0;
+    if ((rc = emit_chunk(ctx, params, t0, base, &n_nodes))) return rc;
+    if (!n_nodes) return SVO_OK;
+    svo_proc_state *s = ctx->proc.get();
+    const size_t bytes = n_nodes * 8;
     const double t1 = svo_now_ms();
     if ((rc = svo_grow_pinned(ctx, &s->stage_bytes, bytes, &s->stage))) return rc;
     HIP_TRY(ctx, hipMemcpyAsync(s->stage, s->out, bytes, hipMemcpyDeviceToHost, ctx->stream));
@@ -480,7 +520,6 @@ int svo_proc_generate_chunk(svo_ctx *ctx, const svo_proc_params *params, svo_cpu
     HIP_TRY(ctx, hipEventElapsedTime(&s->ms[0], s->ev[0], s->ev[1]));
     HIP_TRY(ctx, hipEventElapsedTime(&s->ms[1], s->ev[1], s->ev[2]));
     HIP_TRY(ctx, hipEventElapsedTime(&s->ms[2], s->ev[2], s->ev[3]));
-    s->ms[3] = float(t1 - t0);
     s->ms[4] = float(t2 - t1);
     s->ms[5] = float(t3 - t2);
     return SVO_OK;
@@ -508,6 +547,12 @@ int svo_world_generate(svo_ctx *ctx, svo_world *w, uint32_t world_depth, uint32_
                         errno == EEXIST ? "File already exists" : "cannot create " + path + ": " + strerror(errno));
     auto world_fail = [&](const char *what) { return svo_fail(ctx, SVO_ERR_STATE, std::string(what) + ": " + svo_world_last_error(w)); };
     float times[4] = {0, 0, 0, 0};  // GPU, read-back, mips, writes
+    BlockMips blocks{};  // block leaves take their block's top_mip (as svo_world_generate_mip_tree does)
+    for (uint32_t b = 1; b <= 8; b++) {
+        uint8_t rgb[3];
+        svo_cpu_octree_top_mip(svo_world_chunk(w, b), rgb);
+        blocks.rgb[b] = rgb[0] | rgb[1] << 8 | rgb[2] << 16;
+    }
     svo_cpu_octree *root = svo_cpu_octree_new(0);
     const uint32_t n = 1u << world_depth;
     const float voxel = 2.0f / float(n);
@@ -522,29 +567,54 @@ int svo_world_generate(svo_ctx *ctx, svo_world *w, uint32_t world_depth, uint32_
                 p.base_depth = world_depth;
                 p.chunk_depth = chunk_depth;
                 const uint32_t id = kChunkOffset / 2 + i;
-                svo_cpu_octree *chunk = nullptr;
-                int rc = svo_proc_generate_chunk(ctx, &p, &chunk);
+                uint64_t base[11], n_nodes = 0;
+                int rc = check_params(ctx, &p);
+                if (!rc) rc = emit_chunk(ctx, &p, svo_now_ms(), base, &n_nodes);
                 if (rc) {
                     svo_cpu_octree_free(root);
                     return rc;
                 }
-                times[0] += ctx->proc->ms[3];
-                times[1] += ctx->proc->ms[4] + ctx->proc->ms[5];
-                if (!chunk) continue;
-                svo_world_insert(w, id, chunk);
-                double t = svo_now_ms();
-                if (svo_world_generate_mip_tree(w, id, nullptr) != 0) {
-                    svo_cpu_octree_free(root);
-                    return world_fail("mips");
+                svo_proc_state *s = ctx->proc.get();
+                times[0] += s->ms[3];
+                if (!n_nodes) continue;
+                // mips on the device: block leaves first, then the interior levels bottom-up
+                uint2 *nodes = reinterpret_cast<uint2 *>(s->out);
+                HIP_TRY(ctx, hipEventRecord(s->mev[0], ctx->stream));
+                const uint32_t leaves = uint32_t(base[chunk_depth + 1] - base[chunk_depth]);
+                proc_block_mips_kernel<<<svo_div_up(leaves, 256), 256, 0, ctx->stream>>>(nodes, (uint32_t)base[chunk_depth], leaves, blocks);
+                for (uint32_t l = chunk_depth - 1; l >= 1; l--) {
+                    const uint32_t count = uint32_t(base[l + 1] - base[l]);
+                    mip_level_kernel<<<svo_div_up(count, 256), 256, 0, ctx->stream>>>(nodes, (uint32_t)base[l], count, (uint32_t)n_nodes);
                 }
-                times[2] += float(svo_now_ms() - t);
+                HIP_TRY(ctx, hipGetLastError());
+                HIP_TRY(ctx, hipEventRecord(s->mev[1], ctx->stream));
+                // one copy into the pinned stage; <id>.bin and top_mip come from there
+                double t = svo_now_ms();
+                const size_t bytes = n_nodes * 8;
+                if ((rc = svo_grow_pinned(ctx, &s->stage_bytes, bytes, &s->stage))) {
+                    svo_cpu_octree_free(root);
+                    return rc;
+                }
+                HIP_TRY(ctx, hipMemcpyAsync(s->stage, s->out, bytes, hipMemcpyDeviceToHost, ctx->stream));
+                HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+                times[1] += float(svo_now_ms() - t);
+                float mip_ms = 0.0f;
+                HIP_TRY(ctx, hipEventElapsedTime(&mip_ms, s->mev[0], s->mev[1]));
+                times[2] += mip_ms;
                 t = svo_now_ms();
-                if (svo_world_save_chunk(w, id) != 0) {
+                if (svo_world_write_chunk(w, id, s->stage, bytes) != 0) {
                     svo_cpu_octree_free(root);
                     return world_fail("save");
                 }
                 times[3] += float(svo_now_ms() - t);
+                uint32_t top[8];  // top_mip: the mip of the root group
+                for (int c = 0; c < 8; c++) top[c] = reinterpret_cast<const uint32_t *>(s->stage)[2 * c + 1];
+                const uint32_t v = mip_of(top);
+                const uint8_t rgb[3] = {uint8_t(v), uint8_t(v >> 8), uint8_t(v >> 16)};
+                svo_cpu_octree *chunk = svo_cpu_octree_new(0);
                 svo_cpu_octree_drop_nodes(chunk);  // keep only top_mip in memory (world.rs:122)
+                svo_cpu_octree_set_top_mip(chunk, rgb);
+                svo_world_insert(w, id, chunk);
                 svo_cpu_octree_put_in_block(root, p.pos, id, world_depth);
             }
     svo_world_insert(w, 0, root);

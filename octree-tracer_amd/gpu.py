@@ -56,6 +56,14 @@ class Gpu:
         self.check(lib().svo_build_timing(self._h, ms))
         return list(ms)
 
+    def world_build_timing(self):
+        """ms of the last CpuOctree.build / World.build_world: keys, sort, levels, count read-back, emit, mips (device
+        events), chunk read-back, chunk files and root (CpuOctree.build: the tree), host wall time of the call
+        (svo_world_build_timing)"""
+        ms = (C.c_float * 9)()
+        self.check(lib().svo_world_build_timing(self._h, ms))
+        return list(ms)
+
     def strip_classes(self, n_strips):
         """class byte per 64-pixel block of the last pixel frame that ran the culling pass (0xFF = culled); diagnostics"""
         import numpy as np

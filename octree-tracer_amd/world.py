@@ -53,6 +53,19 @@ class World:
         w = World.new(path, blocks_dir)
         procedural.gpu.check(lib().svo_world_generate(procedural.gpu._h, w._h, int(world_depth), int(chunk_depth)))
 
+    @staticmethod
+    def build_world(path, gpu, coords, depth, colours=None, world_depth=1, colour=0xFFFFFF, max_nodes=None):
+        """Write a new streamable world to directory `path` (which must not exist) from (N, 3) voxel cells in
+        [0, 2^depth), built on the GPU (svo_world_build): chunk (cx, cy, cz) = the top world_depth bits of
+        the cells, <id>.bin per non-empty chunk with its mips, 0.bin the root as generate_world makes it.  colours:
+        0x00RRGGBB per voxel (None: `colour`).  A chunk of more than max_nodes nodes (default 256 000 000) raises
+        SvoError and nothing is created.  Returns World.load_world(path)."""
+        from .cpu_octree import _chunk_inputs
+        w = World(path)
+        with _chunk_inputs(gpu, coords, depth, colours, colour, world_depth, max_nodes) as (xyz, col, n, p):
+            gpu.check(lib().svo_world_build(gpu._h, w._h, xyz, col, n, C.byref(p)))
+        return World.load_world(path)
+
     def __del__(self):
         if getattr(self, "_h", None) and lib is not None:  # (module globals are gone at interpreter exit)
             lib().svo_world_free(self._h)

@@ -74,8 +74,8 @@ def main():
         size = sum(os.path.getsize(os.path.join(path, f)) for f in os.listdir(path))
         rest = wall - t["world_gpu"] - t["world_copy_and_build"] - t["world_mips"] - t["world_writes"]
         log(f"# generate_world(world_depth=1, chunk_depth={cd}): {len(os.listdir(path))} files, {size / 1e6:.1f} MB")
-        log(f"wall {wall:.1f} ms = gpu {t['world_gpu']:.1f} + read-back and CpuOctree build {t['world_copy_and_build']:.1f} + "
-            f"mips {t['world_mips']:.1f} + file writes {t['world_writes']:.1f} + other {rest:.1f}")
+        log(f"wall {wall:.1f} ms = gpu {t['world_gpu']:.1f} + read-back {t['world_copy_and_build']:.1f} + "
+            f"device mips {t['world_mips']:.1f} + file writes {t['world_writes']:.1f} + other {rest:.1f}")
     finally:
         shutil.rmtree(scratch, ignore_errors=True)
     gpu.close()
