@@ -417,6 +417,24 @@ int svo_adaptive_length(svo_ctx *ctx, uint64_t *len_out);
  * and chunk loads included), [3] host wall time of the call. */
 #define SVO_ADAPT_TIMES 4
 int svo_adaptive_timing(svo_ctx *ctx, float ms_out[SVO_ADAPT_TIMES]);
+/* Device form of svo_world_expand: refines the attached tree to a view's level of detail without the words
+ * or the positions leaving the device.  Afterwards the node buffer's words [0, length), the positions, the length and
+ * out->n_sub (the subdivisions; n_unsub, n_removed stay 0) equal, bit for bit, what
+ * svo_world_expand(w, o, max_depth, cam, lod_c, min(max_words, capacity)) makes of the attached octree and world on the
+ * host.  cam may be NULL (then, or with lod_c <= 0, every leaf above max_depth is refined); max_words 0 means the node
+ * buffer's capacity and a larger value is clamped to it: reaching the cap is where expansion stops, not an error.
+ * The world's chunk set equals the host's too, except when the cap cuts a level short: leaves behind the cut may then
+ * have loaded chunks the host never asked for (a superset of the host's set).
+ * SVO_ERR_ARG for max_depth > 31; SVO_ERR_STATE, nothing written, when the attached tree's hole stack is not empty (the
+ * host then reuses groups in an order the sorted pass does not reproduce: expand such a tree with svo_world_expand);
+ * otherwise the errors of svo_adaptive_step's subdivide pass.  Blocking. */
+int svo_adaptive_expand(svo_ctx *ctx, uint32_t max_depth, const float cam[3], float lod_c, uint64_t max_words,
+                        svo_adaptive_result *out);
+/* Times of the last svo_adaptive_expand: [0] listing the leaves, [1] choosing each level's candidates, [2] the subdivide
+ * passes with the next frontier (ms, device events, read-backs and chunk loads included), [3] host wall time of the call
+ * (ms), [4] the number of levels. */
+#define SVO_ADAPT_EXPAND_TIMES 5
+int svo_adaptive_expand_timing(svo_ctx *ctx, float ms_out[SVO_ADAPT_EXPAND_TIMES]);
 
 #ifdef __cplusplus
 }

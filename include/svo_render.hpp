@@ -272,6 +272,13 @@ class Render {  // render.rs:3-285
         gpu_.check(svo_adaptive_step(gpu_.ctx(), sub_dev, n_sub, unsub_dev, n_unsub, &r));
         return r;
     }
+    // the device form of World::expand on the attached state (svo_adaptive_expand): r.n_sub subdivisions,
+    // r.length words; max_words 0 = the node buffer's capacity.  Throws for a tree with free groups in its hole stack.
+    svo_adaptive_result adaptive_expand(uint32_t max_depth, const float *cam = nullptr, float lod_c = 0.0f, uint64_t max_words = 0) {
+        svo_adaptive_result r{};
+        gpu_.check(svo_adaptive_expand(gpu_.ctx(), max_depth, cam, cam ? lod_c : 0.0f, max_words, &r));
+        return r;
+    }
     void adaptive_download(Octree &octree) { gpu_.check(svo_adaptive_download(gpu_.ctx(), octree.raw())); }
     // incremental form of the same upload: only the words that changed (svo_nodes_scatter; pair it with
     // gpu.set_option(SVO_OPT_SCAN_CLEARS_COUNTERS, 1), which takes over the counter reset of the full upload)

@@ -87,6 +87,7 @@ DEVICE_SYMBOLS = [
     "svo_proc_generate_chunk", "svo_world_generate", "svo_proc_sdf", "svo_proc_classify", "svo_proc_timing",
     "svo_nodes_build", "svo_nodes_build_dense", "svo_buffer_write", "svo_build_timing",
     "svo_adaptive_attach", "svo_adaptive_step", "svo_adaptive_download", "svo_adaptive_length", "svo_adaptive_timing",
+    "svo_adaptive_expand", "svo_adaptive_expand_timing",
     "svo_cpu_octree_build", "svo_world_build", "svo_world_build_timing",
 ]
 HOST_SYMBOLS = [
@@ -186,6 +187,8 @@ def lib():
     sig("svo_adaptive_download", C.c_int, vp, vp)
     sig("svo_adaptive_length", C.c_int, vp, C.POINTER(u64))
     sig("svo_adaptive_timing", C.c_int, vp, fp)
+    sig("svo_adaptive_expand", C.c_int, vp, u32, fp, f32, u64, C.POINTER(AdaptiveResult))
+    sig("svo_adaptive_expand_timing", C.c_int, vp, fp)
     # host data model (include/svo_host.h)
     sig("svo_cpu_octree_new", vp, C.c_uint8)
     sig("svo_cpu_octree_free", None, vp)

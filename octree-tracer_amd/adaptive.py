@@ -1,7 +1,8 @@
 """View-dependent LOD streaming on top of the device scan: reference src/adaptive.rs
 (process_subdivision :6-68, process_unsubdivision :70-126) and the frame update of src/app.rs:94-118.
 The list processing itself is native: on the host (svo_adaptive_subdivide / svo_adaptive_unsubdivide) or, with
-AdaptiveLoop(on_device=True) / DeviceAdaptive, on the GPU (svo_adaptive_step)."""
+AdaptiveLoop(on_device=True) / DeviceAdaptive, on the GPU (svo_adaptive_step).  DeviceAdaptive.expand is
+the device form of World.expand (svo_adaptive_expand)."""
 import ctypes as C
 
 import numpy as np
@@ -83,6 +84,26 @@ class DeviceAdaptive:
                      "removed": [res.removed[i] for i in range(res.n_removed)]}
         return res.n_sub, res.n_unsub
 
+    def expand(self, max_depth, cam=None, lod_c=0.0, max_words=None):
+        """World.expand(octree, max_depth, cam, lod_c, max_words) on the device state (svo_adaptive_expand): the words,
+        positions, length and the returned number of subdivisions equal the host call's, bit for bit; the host octree is
+        stale until download().  max_words: None or 0 for the node buffer's capacity (a larger value is clamped to it).
+        Raises SvoError for a tree with free groups in its hole stack (expand that one on the host)."""
+        res = AdaptiveResult()
+        camv = (C.c_float * 3)(*(float(c) for c in cam)) if cam is not None else None
+        self.gpu.check(lib().svo_adaptive_expand(self.gpu._h, int(max_depth), camv, float(lod_c if cam is not None else 0.0),
+                                                 int(max_words or 0), C.byref(res)))
+        self.length = res.length
+        self.render.node_length = max(self.render.node_length, res.length)
+        self.last = {"n_sub": res.n_sub, "n_unsub": 0, "chunks_loaded": res.chunks_loaded, "length": res.length, "removed": []}
+        return res.n_sub
+
+    def expand_timing(self):
+        """Of the last expand: ms listing the leaves, choosing candidates, subdividing (device events), host wall ms, levels."""
+        out = (C.c_float * 5)()
+        self.gpu.check(lib().svo_adaptive_expand_timing(self.gpu._h, out))
+        return list(out[:4]) + [int(out[4])]
+
     def _dummy(self):
         if getattr(self, "_one", None) is None:
             self._one = torch.zeros(1, dtype=torch.int32, device=torch.device("cuda", self.gpu.device))
@@ -110,14 +131,18 @@ class AdaptiveLoop:
 
     on_device=True (implies incremental) keeps the list processing on the GPU too (DeviceAdaptive): trace -> scan ->
     svo_adaptive_step over the scan's lists in place; no list and no word crosses PCIe.  The frames equal those of
-    incremental=True with deterministic=True; the host `octree` is stale until download()."""
+    incremental=True with deterministic=True; the host `octree` is stale until download().
 
-    def __init__(self, gpu, render, compute, octree, world, incremental=False, on_device=False):
+    device=<DeviceAdaptive> (implies on_device) continues from a state that is already attached, e.g. the one
+    Render.from_world returns: no second attach, and `octree` may be its stale host octree."""
+
+    def __init__(self, gpu, render, compute, octree, world, incremental=False, on_device=False, device=None):
         self.gpu, self.render, self.compute, self.octree, self.world = gpu, render, compute, octree, world
+        on_device = on_device or device is not None
         self.incremental = incremental or on_device
         gpu.set_option(OPT_SCAN_CLEARS_COUNTERS, 1 if self.incremental else 0)
         octree.take_dirty()  # the device already holds the octree as it is now
-        self.device = DeviceAdaptive(gpu, render, octree, world) if on_device else None
+        self.device = device if device is not None else DeviceAdaptive(gpu, render, octree, world) if on_device else None
 
     def frame(self, settings, character, deterministic=False):
         self.render.update(settings, character)

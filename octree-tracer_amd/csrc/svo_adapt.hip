@@ -15,6 +15,11 @@
 //                written colour and the chunk to drop; a scan gives the hole pushes in list order; the apply writes.
 //
 // Both lists are sorted first with the tree builder's radix sort (svo_build.hip).
+//
+// svo_adaptive_expand is the device form of svo_world_expand on the same state: the host's frontier walk
+// taken level by level.  A kernel lists the tree's leaves with their depths in index order; per level a kernel keeps
+// the leaves the view refines (already sorted, so no radix sort), the subdivide pass above runs on them with a success
+// limit for the word cap, and a kernel writes the next frontier: the 8 slots of every group the pass made, in order.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -23,10 +28,10 @@
 #include <vector>
 
 #include "svo_ctx.h"
+#include "svo_scan.h"  // (kThreads; tiles of kTile items for the expand's compactions)
 
 namespace {
 
-constexpr uint32_t kThreads = 256;
 constexpr uint32_t kVoxelOff = SVO_VOXEL_OFFSET;
 constexpr uint32_t kChunkOff = SVO_CHUNK_OFFSET;
 constexpr uint32_t kNone = 0xFFFFFFFFu;
@@ -217,10 +222,12 @@ __global__ __launch_bounds__(kThreads) void sub_popped_kernel(const uint32_t *ho
 
 __global__ __launch_bounds__(kThreads) void sub_apply_kernel(Tree t, const uint32_t *list, uint32_t n, const uint32_t *res,
                                                              const uint32_t *src, const uint32_t *rank, const uint32_t *holes,
-                                                             uint32_t n_holes, const uint2 *wn, uint32_t capacity, Status *st) {
+                                                             uint32_t n_holes, const uint2 *wn, uint32_t capacity, uint32_t limit,
+                                                             Status *st) {
     const uint32_t k = blockIdx.x * kThreads + threadIdx.x;
     if (k >= n || (res[k] & 0xFFu) != kDone) return;
     const uint32_t s = rank[k];
+    if (s >= limit) return;  // (svo_adaptive_expand: behind the word cap)
     const uint32_t g = s < n_holes ? holes[n_holes - 1 - s] : t.len + 8u * (s - n_holes);
     if (g >= capacity || capacity - g < 8u) return report(&st->err, k, kErrRange);
     const uint32_t node = list[k], depth = (res[k] >> 8) + 1u, first = src[k];
@@ -307,6 +314,100 @@ __global__ __launch_bounds__(kThreads) void unsub_apply_kernel(Tree t, const uin
     if ((res[k] & 0xFFu) == kDone && n_holes + rank[k] < hole_cap) holes[n_holes + rank[k]] = grp[k];
 }
 
+// ---- expand ----
+// A frontier entry is node index | depth << 27: an index is below 2^27 (SVO_VOXEL_OFFSET), a depth at most 31.
+constexpr uint32_t kDepthShift = 27, kIndexMask = (1u << kDepthShift) - 1u;
+
+// The initial frontier: every leaf of [0, len) with the depth of the walk to its position, in index order.  Tiles of
+// kTile words, kPer consecutive words per lane; the count kernel only tests the words, the emit kernel walks.
+__global__ __launch_bounds__(kThreads) void frontier_count_kernel(const uint32_t *nodes, uint32_t len, uint32_t *tile_sum) {
+    const uint32_t i0 = blockIdx.x * kTile + threadIdx.x * kPer;
+    uint32_t c = 0;
+    for (uint32_t j = 0; j < kPer; j++)
+        if (i0 + j < len && is_leaf(nodes[i0 + j])) c++;
+    uint32_t total;
+    block_exclusive_scan<kThreads>(c, &total);
+    if (threadIdx.x == 0) tile_sum[blockIdx.x] = total;
+}
+
+__global__ __launch_bounds__(kThreads) void frontier_emit_kernel(Tree t, const uint32_t *tile_off, uint32_t *out, uint32_t out_cap,
+                                                                 Status *st) {
+    const uint32_t i0 = blockIdx.x * kTile + threadIdx.x * kPer;
+    uint32_t leaf = 0;
+    for (uint32_t j = 0; j < kPer; j++)
+        if (i0 + j < t.len && is_leaf(t.nodes[i0 + j])) leaf |= 1u << j;
+    uint32_t r = block_exclusive_scan<kThreads>(__popc(leaf), nullptr) + tile_off[blockIdx.x];
+    for (uint32_t j = 0; j < kPer; j++) {
+        if (!((leaf >> j) & 1u)) continue;
+        const uint32_t i = i0 + j;
+        uint32_t at = 0;
+        const uint32_t d = tree_walk(t.nodes, t.len, load_pos(t.pos, i), [](uint32_t, uint32_t w) { return is_leaf(w); }, at);
+        if (!d) report(&st->err, min(i, kMaxRank - 1u), kErrWalk);
+        if (r < out_cap) out[r] = i | d << kDepthShift;  // (always: the counts come from the same words)
+        r++;
+    }
+}
+
+// svo_world_expand's rule for one frontier leaf (svo_host.cpp), operation by operation: deeper than max_depth never;
+// with a camera, only while 2^d * distance(camera, the leaf's cube) < lod_c (a NaN does not refine).
+struct View {
+    float cam[3], lod_c;
+    uint32_t max_depth, use_cam;
+};
+
+__device__ inline bool view_refines(const float *pos, uint32_t entry, const View &v) {
+    const uint32_t d = entry >> kDepthShift;
+    if (d >= v.max_depth) return false;
+    if (!v.use_cam) return true;
+    const float3 c = load_pos(pos, entry & kIndexMask);
+    const float h = 1.0f / float(1u << d);  // half edge of a depth-d cube
+    const float cc[3] = {c.x, c.y, c.z};
+    float d2 = 0.0f;
+    for (int k = 0; k < 3; k++) {
+        const float lo = cc[k] - h, hi = cc[k] + h;
+        const float dist = v.cam[k] < lo ? lo - v.cam[k] : (v.cam[k] > hi ? v.cam[k] - hi : 0.0f);
+        d2 += dist * dist;
+    }
+    return float(1u << d) * __fsqrt_rn(d2) < v.lod_c;
+}
+
+__global__ __launch_bounds__(kThreads) void cand_count_kernel(const uint32_t *frontier, uint32_t n, const float *pos, View v,
+                                                              uint32_t *tile_sum) {
+    const uint32_t i0 = blockIdx.x * kTile + threadIdx.x * kPer;
+    uint32_t c = 0;
+    for (uint32_t j = 0; j < kPer; j++)
+        if (i0 + j < n && view_refines(pos, frontier[i0 + j], v)) c++;
+    uint32_t total;
+    block_exclusive_scan<kThreads>(c, &total);
+    if (threadIdx.x == 0) tile_sum[blockIdx.x] = total;
+}
+
+// the passing node indices, in frontier order, into list[0, total)
+__global__ __launch_bounds__(kThreads) void cand_emit_kernel(const uint32_t *frontier, uint32_t n, const float *pos, View v,
+                                                             const uint32_t *tile_off, uint32_t *list) {
+    const uint32_t i0 = blockIdx.x * kTile + threadIdx.x * kPer;
+    uint32_t e[kPer], pass = 0;
+    for (uint32_t j = 0; j < kPer; j++) {
+        e[j] = i0 + j < n ? frontier[i0 + j] : 0u;
+        if (i0 + j < n && view_refines(pos, e[j], v)) pass |= 1u << j;
+    }
+    uint32_t r = block_exclusive_scan<kThreads>(__popc(pass), nullptr) + tile_off[blockIdx.x];
+    for (uint32_t j = 0; j < kPer; j++)
+        if ((pass >> j) & 1u) list[r++] = e[j] & kIndexMask;  // (r < n: at most one index per frontier entry)
+}
+
+// Success s (< limit) of the pass made the group at len_before + 8 s out of a leaf of depth d: its 8 slots, depth d + 1,
+// are entries [8 s, 8 s + 8) of the next frontier.  rank is the pass's scanned flag array.
+__global__ __launch_bounds__(kThreads) void next_frontier_kernel(uint32_t n, const uint32_t *res, const uint32_t *rank,
+                                                                 uint32_t limit, uint32_t len_before, uint32_t *out) {
+    const uint32_t k = blockIdx.x * kThreads + threadIdx.x;
+    if (k >= n || (res[k] & 0xFFu) != kDone) return;
+    const uint32_t s = rank[k];
+    if (s >= limit) return;
+    const uint32_t g = len_before + 8u * s, d = (res[k] >> 8) + 1u;
+    for (uint32_t i = 0; i < 8; i++) out[8u * s + i] = (g + i) | d << kDepthShift;
+}
+
 }  // namespace
 
 struct svo_adapt_state {
@@ -340,10 +441,17 @@ struct svo_adapt_state {
     std::vector<uint32_t> removed;
     hipEvent_t ev[4] = {};  // start, sorted, subdivided, unsubdivided
     float ms[SVO_ADAPT_TIMES] = {};
+    // svo_adaptive_expand: this level's frontier and the next one's, the compactions' tile sums
+    uint32_t *frontier[2] = {};
+    size_t frontier_items[2] = {};
+    uint32_t *tiles = nullptr;
+    size_t tile_items = 0;
+    float expand_ms[SVO_ADAPT_EXPAND_TIMES] = {};
 
     ~svo_adapt_state() {
         for (void *p : {(void *)pos, (void *)holes, (void *)wn, (void *)tab_dev, (void *)rm, (void *)list[0], (void *)list[1],
-                        (void *)res, (void *)src, (void *)val, (void *)flag, (void *)req, (void *)bits, (void *)st})
+                        (void *)res, (void *)src, (void *)val, (void *)flag, (void *)req, (void *)bits, (void *)st, (void *)frontier[0],
+                        (void *)frontier[1], (void *)tiles})
             if (p) (void)hipFree(p);
         for (void *p : {(void *)st_host, (void *)counts_host})
             if (p) (void)hipHostFree(p);
@@ -466,7 +574,8 @@ int clear_status(svo_ctx *ctx) {
 Tree tree_of(svo_ctx *ctx) { return Tree{ctx->nodes, ctx->adapt->pos, ctx->adapt->len}; }
 
 // ---- the subdivide pass over the sorted list a->list[0][0, n) ----
-int subdivide_pass(svo_ctx *ctx, uint32_t n, svo_adaptive_result *out) {
+// Only the first `limit` successes in list order are applied (svo_adaptive_expand's word cap; kNone: all of them).
+int subdivide_pass(svo_ctx *ctx, uint32_t n, uint32_t limit, svo_adaptive_result *out) {
     svo_adapt_state *a = ctx->adapt.get();
     const uint32_t *list = a->list[0], grid = svo_div_up(n, kThreads);
     int rc;
@@ -511,7 +620,7 @@ int subdivide_pass(svo_ctx *ctx, uint32_t n, svo_adaptive_result *out) {
                                                                                                        a->flag + n, a->st);
     HIP_TRY(ctx, hipGetLastError());
     if ((rc = read_status(ctx, a->flag + n))) return rc;
-    const uint32_t done = a->st_host->total;
+    const uint32_t done = std::min(a->st_host->total, limit);
     if (a->st_host->popped_hit)
         return svo_fail(ctx, SVO_ERR_STATE, "subdivide: an entry lies in a hole group this pass reuses (this list needs the sequential "
                                             "host path, svo_adaptive_subdivide)");
@@ -522,7 +631,7 @@ int subdivide_pass(svo_ctx *ctx, uint32_t n, svo_adaptive_result *out) {
                                               " words, over the node buffer's capacity of " + std::to_string(ctx->capacity));
     if (done) {
         sub_apply_kernel<<<grid, kThreads, 0, ctx->stream>>>(tree_of(ctx), list, n, a->res, a->src, a->flag, a->holes, a->n_holes,
-                                                             a->wn, (uint32_t)ctx->capacity, a->st);
+                                                             a->wn, (uint32_t)ctx->capacity, limit, a->st);
         HIP_TRY(ctx, hipGetLastError());
     }
     a->n_holes -= pops;
@@ -592,6 +701,19 @@ int unsubdivide_pass(svo_ctx *ctx, uint32_t n, svo_adaptive_result *out) {
     }
     return SVO_OK;
 }
+
+// loads that failed in a subdivide pass are forgotten: the next pass may try them again, as the host does; the others
+// are resident for every entry from here on.  True when the table changed (the caller uploads it).
+bool forget_load_ranks(svo_adapt_state *a) {
+    bool changed = false;
+    for (const Chunk &c : a->tab) changed |= c.rank != kNone;
+    a->tab.erase(std::remove_if(a->tab.begin(), a->tab.end(), [](const Chunk &c) { return c.rank == kFailed; }), a->tab.end());
+    for (Chunk &c : a->tab) c.rank = kNone;
+    return changed;
+}
+
+// what a buffer of `have` items grows to for `want`: at least twice its size, so a run of growing levels reallocates rarely
+size_t grown(size_t have, size_t want) { return have >= want ? have : std::max(want, 2 * have); }
 
 int check_attached(svo_ctx *ctx) {
     if (!ctx->adapt || !ctx->adapt->world) return svo_fail(ctx, SVO_ERR_STATE, "svo_adaptive_attach not called");
@@ -680,10 +802,8 @@ int svo_adaptive_step(svo_ctx *ctx, const uint32_t *d_sub, uint32_t n_sub, const
     if ((rc = svo_build_sort_u32(ctx, d_sub, n_sub, a->list[0]))) return rc;
     if ((rc = svo_build_sort_u32(ctx, d_unsub, n_unsub, a->list[1]))) return rc;
     HIP_TRY(ctx, hipEventRecord(a->ev[1], ctx->stream));
-    if (n_sub && (rc = subdivide_pass(ctx, n_sub, out))) return rc;
-    // loads that failed in this pass are forgotten: the next pass may try them again, as the host does
-    a->tab.erase(std::remove_if(a->tab.begin(), a->tab.end(), [](const Chunk &c) { return c.rank == kFailed; }), a->tab.end());
-    for (Chunk &c : a->tab) c.rank = kNone;
+    if (n_sub && (rc = subdivide_pass(ctx, n_sub, kNone, out))) return rc;
+    forget_load_ranks(a);
     HIP_TRY(ctx, hipEventRecord(a->ev[2], ctx->stream));
     if ((rc = upload_table(ctx))) return rc;
     if (n_unsub && (rc = unsubdivide_pass(ctx, n_unsub, out))) return rc;
@@ -695,6 +815,120 @@ int svo_adaptive_step(svo_ctx *ctx, const uint32_t *d_sub, uint32_t n_sub, const
     out->length = a->len;
     out->n_removed = (uint32_t)a->removed.size();
     out->removed = a->removed.data();
+    return SVO_OK;
+}
+
+int svo_adaptive_expand(svo_ctx *ctx, uint32_t max_depth, const float cam[3], float lod_c, uint64_t max_words,
+                        svo_adaptive_result *out) {
+    if (!ctx || !out) return SVO_ERR_ARG;
+    if (max_depth > kMaxTreeDepth) return svo_fail(ctx, SVO_ERR_ARG, "max_depth above 31");
+    int rc = check_attached(ctx);
+    if (rc) return rc;
+    svo_adapt_state *a = ctx->adapt.get();
+    if (a->n_holes)  // the host's frontier is then not ascending, and the sorted pass would hand out other groups
+        return svo_fail(ctx, SVO_ERR_STATE, "the attached tree has " + std::to_string(a->n_holes) + " free groups in its hole stack: "
+                                            "expanding it needs the sequential host path, svo_world_expand");
+    memset(out, 0, sizeof *out);
+    a->removed.clear();
+    memset(a->expand_ms, 0, sizeof a->expand_ms);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const double t0 = svo_now_ms();
+    const uint64_t cap = std::min<uint64_t>(std::min<uint64_t>(max_words ? max_words : ctx->capacity, ctx->capacity), kVoxelOff);
+    View view{};
+    view.max_depth = max_depth;
+    view.use_cam = cam && lod_c > 0.0f;
+    view.lod_c = lod_c;
+    if (cam) memcpy(view.cam, cam, sizeof view.cam);
+    if ((rc = svo_store_order_after_write(ctx))) return rc;
+    float ms = 0.0f;
+    uint64_t n_sub = 0;
+
+    // the initial frontier: the leaves of [0, len) (at most len of them)
+    uint32_t cur = 0, n_front = 0;
+    if (a->len) {
+        const uint32_t nt = svo_div_up(a->len, kTile);
+        if ((rc = svo_grow(ctx, &a->frontier_items[0], a->len, &a->frontier[0]))) return rc;
+        if ((rc = svo_grow(ctx, &a->tile_items, nt + 1, &a->tiles))) return rc;
+        if ((rc = clear_status(ctx))) return rc;
+        HIP_TRY(ctx, hipEventRecord(a->ev[0], ctx->stream));
+        frontier_count_kernel<<<nt, kThreads, 0, ctx->stream>>>(ctx->nodes, a->len, a->tiles);
+        tile_offsets_kernel<<<1, kTopThreads, 0, ctx->stream>>>(a->tiles, nt, nullptr, 0, &a->st->total);
+        frontier_emit_kernel<<<nt, kThreads, 0, ctx->stream>>>(tree_of(ctx), a->tiles, a->frontier[0], a->len, a->st);
+        HIP_TRY(ctx, hipGetLastError());
+        HIP_TRY(ctx, hipEventRecord(a->ev[1], ctx->stream));
+        if ((rc = read_status(ctx, nullptr))) return rc;
+        if (a->st_host->err != kNone) return entry_fail(ctx, SVO_ERR_STATE, a->st_host->err, "expand: leaf");
+        n_front = a->st_host->total;
+        HIP_TRY(ctx, hipEventElapsedTime(&ms, a->ev[0], a->ev[1]));
+        a->expand_ms[0] = ms;
+    }
+
+    // level by level; a level of 2^24 entries or more goes through the pass in consecutive slices (its rank packing)
+    uint32_t levels = 0;
+    bool full = false;  // the cap leaves no room for another group: the host stops at its next candidate
+    while (n_front && !full) {
+        levels++;
+        const uint32_t nxt = cur ^ 1u;
+        const uint64_t room = cap > a->len ? cap - a->len : 0;
+        const size_t next_max = std::max<uint64_t>(std::min<uint64_t>(8ull * n_front, room), 8);  // 8 slots per success
+        if ((rc = svo_grow(ctx, &a->frontier_items[nxt], grown(a->frontier_items[nxt], next_max), &a->frontier[nxt]))) return rc;
+        uint32_t n_next = 0;
+        for (uint32_t lo = 0; lo < n_front && !full; lo += kMaxRank - 1u) {
+            const uint32_t n = std::min(n_front - lo, kMaxRank - 1u), nt = svo_div_up(n, kTile);
+            const uint32_t limit = (uint32_t)((cap > a->len ? cap - a->len : 0) / 8u);
+            if (!limit) {
+                full = true;
+                break;
+            }
+            if ((rc = svo_grow(ctx, &a->items, grown(a->items, size_t(n) + 1), &a->list[0], &a->list[1], &a->res, &a->src, &a->val,
+                               &a->flag)))
+                return rc;
+            if ((rc = svo_grow(ctx, &a->req_items, 2 * a->items, &a->req))) return rc;
+            if ((rc = svo_grow(ctx, &a->tile_items, nt + 1, &a->tiles))) return rc;
+            if ((rc = clear_status(ctx))) return rc;
+            HIP_TRY(ctx, hipEventRecord(a->ev[0], ctx->stream));
+            cand_count_kernel<<<nt, kThreads, 0, ctx->stream>>>(a->frontier[cur] + lo, n, a->pos, view, a->tiles);
+            tile_offsets_kernel<<<1, kTopThreads, 0, ctx->stream>>>(a->tiles, nt, nullptr, 0, &a->st->total);
+            cand_emit_kernel<<<nt, kThreads, 0, ctx->stream>>>(a->frontier[cur] + lo, n, a->pos, view, a->tiles, a->list[0]);
+            HIP_TRY(ctx, hipGetLastError());
+            HIP_TRY(ctx, hipEventRecord(a->ev[1], ctx->stream));
+            if ((rc = read_status(ctx, nullptr))) return rc;
+            const uint32_t n_cand = a->st_host->total;
+            HIP_TRY(ctx, hipEventElapsedTime(&ms, a->ev[0], a->ev[1]));
+            a->expand_ms[1] += ms;
+            if (!n_cand) continue;
+            const uint32_t len_before = a->len;
+            svo_adaptive_result pass{};
+            if ((rc = subdivide_pass(ctx, n_cand, limit, &pass))) return rc;
+            if (pass.n_sub)
+                next_frontier_kernel<<<svo_div_up(n_cand, kThreads), kThreads, 0, ctx->stream>>>(n_cand, a->res, a->flag, limit, len_before,
+                                                                                                 a->frontier[nxt] + n_next);
+            HIP_TRY(ctx, hipGetLastError());
+            HIP_TRY(ctx, hipEventRecord(a->ev[2], ctx->stream));
+            if (forget_load_ranks(a) && (rc = upload_table(ctx))) return rc;
+            HIP_TRY(ctx, hipEventSynchronize(a->ev[2]));
+            HIP_TRY(ctx, hipEventElapsedTime(&ms, a->ev[1], a->ev[2]));
+            a->expand_ms[2] += ms;
+            n_next += 8u * pass.n_sub;
+            n_sub += pass.n_sub;
+            out->chunks_loaded += pass.chunks_loaded;
+        }
+        cur = nxt;
+        n_front = n_next;
+    }
+    if ((rc = svo_store_note_write(ctx))) return rc;
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    a->expand_ms[3] = float(svo_now_ms() - t0);
+    a->expand_ms[4] = float(levels);
+    out->n_sub = (uint32_t)n_sub;
+    out->length = a->len;
+    return SVO_OK;
+}
+
+int svo_adaptive_expand_timing(svo_ctx *ctx, float ms_out[SVO_ADAPT_EXPAND_TIMES]) {
+    if (!ctx || !ms_out) return SVO_ERR_ARG;
+    if (!ctx->adapt) return svo_fail(ctx, SVO_ERR_STATE, "svo_adaptive_attach not called");
+    memcpy(ms_out, ctx->adapt->expand_ms, sizeof ctx->adapt->expand_ms);
     return SVO_OK;
 }
 

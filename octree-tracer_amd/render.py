@@ -57,6 +57,23 @@ class Render:
         words = octree.raw_data() if hasattr(octree, "raw_data") else octree
         return cls(gpu, size, words, capacity)
 
+    @classmethod
+    def from_world(cls, gpu, size, world, max_depth, cam=None, lod_c=0.0, capacity=None):
+        """A Render whose tree is `world` expanded to a view's level of detail on the GPU: the root
+        chunk's 8 children are uploaded, the device adaptive state is attached (OPT_SCAN_CLEARS_COUNTERS is set) and
+        DeviceAdaptive.expand(max_depth, cam, lod_c) refines them in place, as World.expand does on the host.  Returns
+        (render, device_adaptive); device_adaptive.octree is the 8-node host octree, stale until download(), and can be
+        handed to AdaptiveLoop(..., device=device_adaptive) to go on streaming without a second attach."""
+        from .adaptive import DeviceAdaptive
+        from .gpu import OPT_SCAN_CLEARS_COUNTERS
+        octree = world.root_octree()
+        self = cls(gpu, size, octree.raw_data(), capacity)
+        self._declare_depth(max_depth)
+        gpu.set_option(OPT_SCAN_CLEARS_COUNTERS, 1)
+        device = DeviceAdaptive(gpu, self, octree, world)
+        device.expand(max_depth, cam=cam, lod_c=lod_c)
+        return self, device
+
     def write_nodes(self, words, offset=0):
         """queue.write_buffer(&node_buffer, 0, nodes) (app.rs:113-118)"""
         words = np.ascontiguousarray(words, dtype=np.uint32)
@@ -112,13 +129,16 @@ class Render:
         self.node_length = out.value
         return out.value
 
-    def _build_params(self, depth, colour, max_words):
-        depth = int(depth)
+    def _declare_depth(self, depth):
         # the trace kernels must know how deep the tree goes (SVO_OPT_TREE_DEPTH; raised, never lowered)
         if 1 <= depth <= 21 and depth > getattr(self, "_declared_depth", 16):
             from .gpu import OPT_TREE_DEPTH
             self.gpu.set_option(OPT_TREE_DEPTH, depth)
             self._declared_depth = depth
+
+    def _build_params(self, depth, colour, max_words):
+        depth = int(depth)
+        self._declare_depth(depth)
         p = BuildParams()
         p.depth = max(0, depth)
         p.default_colour = int(colour) & 0xFFFFFF
