@@ -21,6 +21,12 @@
 // Chunk trees (svo_cpu_octree_build, svo_world_build) take the same keys, sort and level passes in kChunk
 // mode: the counting passes also find every chunk's run in each level's sorted keys, and the emit writes 8-byte <id>.bin
 // nodes per chunk, which the shared mip pass (svo_mip.h) colours bottom-up before they are staged chunk by chunk.
+//
+// The list entry points share one front end (check_list, list_leaves: keys, sort, leaf pass), level_bounds and
+// read_counts.  Shared with the other passes: the tile shape and scans (svo_scan.h), the Morton convention
+// (svo_morton.h), mip_of and the mip pass (svo_mip.h), svo_grow (svo_ctx.h).  This file also holds what the others
+// borrow: svo_build_sort_u32 / svo_build_scan_u32 (svo_adapt.hip) and svo_world_writer, the one place that lays out a
+// generated world's directory (svo_world_build here, svo_world_generate in svo_proc.hip).
 #include <hip/hip_runtime.h>
 
 #include <sys/stat.h>
@@ -32,8 +38,9 @@
 #include <vector>
 
 #include "svo_ctx.h"
-#include "svo_mip.h"   // (chunk trees: the mip pass svo_proc.hip shares)
-#include "svo_scan.h"  // (tiles of kTile items: sort, scans and compactions alike)
+#include "svo_mip.h"     // (chunk trees: the mip pass svo_proc.hip shares)
+#include "svo_morton.h"  // (keys, the dense grid's cell order, chunk indices)
+#include "svo_scan.h"    // (tiles of kTile items: sort, scans and compactions alike)
 
 namespace {
 
@@ -44,13 +51,6 @@ constexpr int kCountSlots = 32;
 
 enum Mode { kDedupe = 0, kParent = 1, kDense = 2, kChunk = 3 };  // kChunk: kParent whose emit writes chunk trees
 
-__device__ inline uint64_t morton3(uint32_t x, uint32_t y, uint32_t z, uint32_t depth) {
-    uint64_t k = 0;
-    for (uint32_t b = 0; b < depth; b++)
-        k |= uint64_t((x >> b) & 1u) << (3 * b + 2) | uint64_t((y >> b) & 1u) << (3 * b + 1) | uint64_t((z >> b) & 1u) << (3 * b);
-    return k;
-}
-
 // ---- keys ----
 __global__ __launch_bounds__(kThreads) void build_keys_kernel(const uint32_t *xyz, uint32_t n, uint32_t depth, uint64_t *keys,
                                                               uint32_t *vals, uint32_t *err) {
@@ -58,7 +58,7 @@ __global__ __launch_bounds__(kThreads) void build_keys_kernel(const uint32_t *xy
     if (i >= n) return;
     const uint32_t x = xyz[3 * size_t(i)], y = xyz[3 * size_t(i) + 1], z = xyz[3 * size_t(i) + 2];
     if ((x | y | z) >> depth) *err = 1u;  // (every writer stores the same value)
-    keys[i] = morton3(x, y, z, depth);
+    keys[i] = morton_encode(x, y, z, depth);
     vals[i] = i;
 }
 
@@ -212,12 +212,8 @@ __device__ inline uint32_t load_flags(const LevelIn &in, uint32_t m, uint32_t i0
             const uint32_t i = i0 + j;
             k[j] = 0;
             if (i >= m) continue;
-            uint32_t x = 0, y = 0, z = 0;
-            for (uint32_t b = 0; b < in.depth; b++) {
-                z |= ((i >> (3 * b)) & 1u) << b;
-                y |= ((i >> (3 * b + 1)) & 1u) << b;
-                x |= ((i >> (3 * b + 2)) & 1u) << b;
-            }
+            uint32_t x, y, z;
+            morton_decode(i, in.depth, x, y, z);
             const uint32_t c = in.colours[(size_t(x) * side + y) * side + z];
             k[j] = i | uint64_t(c) << 32;  // (the cell's value rides in the high half)
             if (c) f |= 1u << j;
@@ -326,6 +322,16 @@ __global__ __launch_bounds__(kThreads) void build_fill_kernel(uint2 *nodes, uint
         nodes[i] = make_uint2(SVO_CHUNK_OFFSET, 0u);
 }
 
+// The events of a build and the two timing ledgers read from them: slot k of a ledger is the time from its first event to
+// its last (include/svo_hip.h: SVO_BUILD_TIMES, SVO_WORLD_BUILD_TIMES; the remaining slots are host wall times).
+enum Ev { kEvStart, kEvKeys, kEvSort, kEvLevels, kEvCounts, kEvEmit, kEvEmitEnd, kEvChunkEmit, kEvChunkEmitEnd, kEvChunkMips, kEvs };
+struct Slot {
+    Ev first, last;
+};
+constexpr Slot kBuildSlots[5] = {{kEvStart, kEvKeys}, {kEvKeys, kEvSort}, {kEvSort, kEvLevels}, {kEvLevels, kEvCounts}, {kEvEmit, kEvEmitEnd}};
+constexpr Slot kChunkSlots[6] = {{kEvStart, kEvKeys},    {kEvKeys, kEvSort},           {kEvSort, kEvLevels},
+                                 {kEvLevels, kEvCounts}, {kEvChunkEmit, kEvChunkEmitEnd}, {kEvChunkEmitEnd, kEvChunkMips}};
+
 }  // namespace
 
 // Per-context workspace of the builder (svo_ctx::build): O(items), grown when a larger input comes, freed with the
@@ -342,7 +348,7 @@ struct svo_build_state {
     size_t tile_items = 0;
     uint32_t *counts = nullptr;       // kCountSlots words (device): unique nodes per level, error word
     uint32_t *counts_host = nullptr;  // (pinned)
-    hipEvent_t ev[7] = {};          // start, keys, sort, levels, read-back, emit start, emit end
+    hipEvent_t ev[kEvs] = {};
     bool sorted = false, timed = true;  // the last build sorted / its device times are in ms
     float ms[SVO_BUILD_TIMES] = {};
     // chunk trees (svo_world_build, svo_cpu_octree_build)
@@ -356,7 +362,6 @@ struct svo_build_state {
     size_t node_items = 0;
     void *stage = nullptr;      // pinned: one chunk's bytes on their way to a file or a CpuOctree
     size_t stage_bytes = 0;
-    hipEvent_t cev[3] = {};     // emit start, emit end, mips end
     float cms[SVO_WORLD_BUILD_TIMES] = {};
 
     ~svo_build_state() {
@@ -366,8 +371,6 @@ struct svo_build_state {
         for (void *p : {(void *)counts_host, (void *)runs_host, stage})
             if (p) (void)hipHostFree(p);
         for (hipEvent_t e : ev)
-            if (e) (void)hipEventDestroy(e);
-        for (hipEvent_t e : cev)
             if (e) (void)hipEventDestroy(e);
     }
 };
@@ -490,11 +493,24 @@ int parent_passes(svo_ctx *ctx, uint32_t depth, uint32_t stop, const uint64_t *b
     return SVO_OK;
 }
 
-int check_common(svo_ctx *ctx, const svo_build_params *p, uint32_t max_depth, uint64_t *n_words_out) {
-    if (n_words_out) *n_words_out = 0;
-    if (!p) return svo_fail(ctx, SVO_ERR_ARG, "null params");
-    if (p->depth < 1 || p->depth > max_depth)
-        return svo_fail(ctx, SVO_ERR_ARG, "depth must be 1.." + std::to_string(max_depth) + " (got " + std::to_string(p->depth) + ")");
+// The parameters every build has; `depth` is null when the caller passed no params.
+int check_depth(svo_ctx *ctx, const uint32_t *depth, uint32_t max_depth) {
+    if (!depth) return svo_fail(ctx, SVO_ERR_ARG, "null params");
+    if (*depth < 1 || *depth > max_depth)
+        return svo_fail(ctx, SVO_ERR_ARG, "depth must be 1.." + std::to_string(max_depth) + " (got " + std::to_string(*depth) + ")");
+    return SVO_OK;
+}
+
+// The three list entry points: svo_nodes_build (chunked null), svo_cpu_octree_build (a single tree) and svo_world_build.
+int check_list(svo_ctx *ctx, const uint32_t *depth, const svo_chunk_build_params *chunked, bool world, const uint32_t *xyz, size_t n) {
+    int rc = check_depth(ctx, depth, 21);
+    if (rc) return rc;
+    if (chunked && !world && chunked->world_depth != 0) return svo_fail(ctx, SVO_ERR_ARG, "world_depth must be 0 for a single tree");
+    if (chunked && world && (chunked->world_depth < 1 || chunked->world_depth > 4 || chunked->world_depth >= *depth))
+        return svo_fail(ctx, SVO_ERR_ARG, "world_depth must be 1..4 and below depth (got " + std::to_string(chunked->world_depth) +
+                                              ", depth " + std::to_string(*depth) + ")");
+    if (n >= (1ull << 31)) return svo_fail(ctx, SVO_ERR_ARG, "at most 2^31 - 1 voxels per build");
+    if (!xyz && n) return svo_fail(ctx, SVO_ERR_ARG, "null coordinates");
     return SVO_OK;
 }
 
@@ -508,21 +524,70 @@ uint64_t word_limit(const svo_ctx *ctx, const svo_build_params *p) {
     return p->max_words ? std::min<uint64_t>(lim, p->max_words) : lim;
 }
 
-// Both entry points after their leaf pass: the other level passes, one read-back of the counts, the cap, the emit.
+// The front end of the list entry points: workspace for n voxels (chunked: and for runs_items chunk starts, cleared with
+// the counts), keys, sort, and the leaf pass, which keeps the last voxel of every run of equal keys in keys[2] /
+// leaf_colours and their number in counts[depth].
+int list_leaves(svo_ctx *ctx, const uint32_t *xyz, const uint32_t *colours, size_t n, uint32_t depth, uint32_t default_colour,
+                size_t runs_items) {
+    const uint32_t nt = svo_div_up(n, kTile);
+    int rc = ensure_state(ctx, n, std::max<uint64_t>(n, 256ull * nt), 256ull * nt);
+    if (rc) return rc;
+    svo_build_state *s = ctx->build.get();
+    if ((rc = svo_grow(ctx, &s->runs_items, runs_items, &s->runs))) return rc;
+    if ((rc = svo_grow_pinned(ctx, &s->runs_host_items, runs_items, &s->runs_host))) return rc;
+    HIP_TRY(ctx, hipEventRecord(s->ev[kEvStart], ctx->stream));
+    HIP_TRY(ctx, hipMemsetAsync(s->counts, 0, kCountSlots * sizeof(uint32_t), ctx->stream));
+    if (runs_items) HIP_TRY(ctx, hipMemsetAsync(s->runs, 0, runs_items * sizeof(uint32_t), ctx->stream));
+    build_keys_kernel<<<svo_div_up(n, kThreads), kThreads, 0, ctx->stream>>>(xyz, (uint32_t)n, depth, s->keys[0], s->vals[0],
+                                                                             s->counts + kErrSlot);
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, hipEventRecord(s->ev[kEvKeys], ctx->stream));
+    const uint32_t passes = (3 * depth + 7) / 8;
+    if ((rc = sort_passes(ctx, (uint32_t)n, passes))) return rc;
+    HIP_TRY(ctx, hipEventRecord(s->ev[kEvSort], ctx->stream));
+    LevelIn in{};
+    in.keys = s->keys[passes & 1];
+    in.vals = s->vals[passes & 1];
+    in.colours = colours;
+    in.colour = default_colour;
+    in.m_max = (uint32_t)n;
+    LevelOut out{};
+    out.keys = s->keys[2];
+    out.colours = s->leaf_colours;
+    out.cap = (uint32_t)s->items;
+    return level_pass<kDedupe>(ctx, in, out, n, s->counts + depth);
+}
+
+// Host bounds of the unique nodes per level, from the leaf level's: m_L <= m_{L+1} and m_L <= 8^L.
+void level_bounds(uint64_t bound[23], uint32_t depth, uint64_t leaf_bound) {
+    bound[depth] = leaf_bound;
+    for (uint32_t l = depth; l-- > 0;) bound[l] = std::min<uint64_t>(bound[l + 1], 1ull << (3 * l));
+}
+
+// The one read-back between the counting passes and the emit: the counts of all levels (and, chunked, the chunk starts)
+// into their pinned mirrors; fails on the keys kernel's range error word.
+int read_counts(svo_ctx *ctx, uint32_t depth, size_t runs_items) {
+    svo_build_state *s = ctx->build.get();
+    HIP_TRY(ctx, hipEventRecord(s->ev[kEvLevels], ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(s->counts_host, s->counts, kCountSlots * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+    if (runs_items) HIP_TRY(ctx, hipMemcpyAsync(s->runs_host, s->runs, runs_items * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipEventRecord(s->ev[kEvCounts], ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    if (s->counts_host[kErrSlot])
+        return svo_fail(ctx, SVO_ERR_ARG, "a voxel coordinate is outside [0, 2^depth) (depth " + std::to_string(depth) + ")");
+    return SVO_OK;
+}
+
+// Both word-tree entry points after their leaf pass: the other level passes, the read-back of the counts, the cap, the emit.
 int finish(svo_ctx *ctx, const svo_build_params *p, uint64_t leaf_bound, double t0, bool sorted, uint64_t *n_words_out) {
     svo_build_state *s = ctx->build.get();
     const uint32_t depth = p->depth;
-    uint64_t bound[23] = {};  // host bounds of the unique nodes per level
-    bound[depth] = std::min<uint64_t>(leaf_bound, s->items);
-    for (uint32_t l = depth; l-- > 0;) bound[l] = std::min<uint64_t>(bound[l + 1], 1ull << (3 * l));  // m_L <= 8^L
+    uint64_t bound[23] = {};
+    level_bounds(bound, depth, std::min<uint64_t>(leaf_bound, s->items));
     int rc = parent_passes(ctx, depth, 2, bound, nullptr, nullptr, 0);
     if (rc) return rc;
-    HIP_TRY(ctx, hipEventRecord(s->ev[3], ctx->stream));
-    HIP_TRY(ctx, hipMemcpyAsync(s->counts_host, s->counts, kCountSlots * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipEventRecord(s->ev[4], ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    if ((rc = read_counts(ctx, depth, 0))) return rc;
     const uint32_t *m = s->counts_host;
-    if (m[kErrSlot]) return svo_fail(ctx, SVO_ERR_ARG, "a voxel coordinate is outside [0, 2^depth) (depth " + std::to_string(depth) + ")");
     const uint64_t limit = word_limit(ctx, p);
     if (m[depth] > s->items)  // (dense: more solid cells than the cap has words)
         return svo_fail(ctx, SVO_ERR_CAP, std::to_string(m[depth]) + " leaves cannot fit in " + std::to_string(limit) + " words");
@@ -537,11 +602,11 @@ int finish(svo_ctx *ctx, const svo_build_params *p, uint64_t leaf_bound, double 
     // emit: behind every earlier write to the store, whichever context issued it
     rc = svo_store_order_after_write(ctx);
     if (rc) return rc;
-    HIP_TRY(ctx, hipEventRecord(s->ev[5], ctx->stream));
+    HIP_TRY(ctx, hipEventRecord(s->ev[kEvEmit], ctx->stream));
     HIP_TRY(ctx, hipMemsetD32Async((hipDeviceptr_t)ctx->nodes, (int)kEmptyWord, n_words, ctx->stream));
     rc = parent_passes(ctx, depth, 1, bound, ctx->nodes, base, n_words);
     if (rc) return rc;
-    HIP_TRY(ctx, hipEventRecord(s->ev[6], ctx->stream));
+    HIP_TRY(ctx, hipEventRecord(s->ev[kEvEmitEnd], ctx->stream));
     rc = svo_store_note_write(ctx);
     if (rc) return rc;
     *n_words_out = n_words;
@@ -607,68 +672,33 @@ namespace {
 
 constexpr uint64_t kDefaultMaxNodes = 256000000ull;  // procedural.rs:4
 
-// The chunk trees of n voxels: keys and sort as svo_nodes_build, the counting passes with the chunk runs
-// of every level, one read-back of the counts and runs, the caps, then (directory `dir` made when given) the emit into
-// one buffer, the mips and, chunk by chunk in id order, one copy into the pinned stage that take(id index, bytes, nodes)
-// consumes.  Nothing is created before every cap has been checked.
+// The chunk trees of n voxels: the list front end of svo_nodes_build, the counting passes with the chunk
+// runs of every level, one read-back of the counts and runs, the caps, then (the world's directory made when `world` is
+// given) the emit into one buffer, the mips and, chunk by chunk in id order, one copy into the pinned stage that
+// take(id index, bytes, nodes) consumes.  Nothing is created before every cap has been checked.
 template <class Take>
 int chunk_build(svo_ctx *ctx, const uint32_t *xyz, const uint32_t *colours, size_t n, const svo_chunk_build_params *p,
-                const std::string &dir, Take take) {
+                svo_world_writer *world, Take take) {
     const double t0 = svo_now_ms();
     const uint32_t depth = p->depth, wd = p->world_depth, cd = depth - wd, n_chunks = 1u << (3 * wd), row = n_chunks + 1;
     const uint64_t cap = std::min<uint64_t>(p->max_nodes ? p->max_nodes : kDefaultMaxNodes, 1ull << 31);
     HIP_TRY(ctx, hipSetDevice(ctx->device));
+    int rc;
     if (!n) {  // nothing to build: the empty world is its root alone
-        if (!dir.empty() && mkdir(dir.c_str(), 0777) != 0)
-            return svo_fail(ctx, errno == EEXIST ? SVO_ERR_ARG : SVO_ERR_STATE,
-                            errno == EEXIST ? "File already exists" : "cannot create " + dir + ": " + strerror(errno));
+        if (world && (rc = world->create())) return rc;
         if (ctx->build) memset(ctx->build->cms, 0, sizeof ctx->build->cms);
         return SVO_OK;
     }
-    const uint32_t nt = svo_div_up(n, kTile);
-    int rc = ensure_state(ctx, n, std::max<uint64_t>(n, 256ull * nt), 256ull * nt);
-    if (rc) return rc;
-    svo_build_state *s = ctx->build.get();
-    if (!s->cev[0])
-        for (hipEvent_t &e : s->cev) HIP_TRY(ctx, hipEventCreate(&e));
     const size_t runs_items = size_t(depth + 1) * row;
-    if ((rc = svo_grow(ctx, &s->runs_items, runs_items, &s->runs))) return rc;
-    if ((rc = svo_grow_pinned(ctx, &s->runs_host_items, runs_items, &s->runs_host))) return rc;
+    if ((rc = list_leaves(ctx, xyz, colours, n, depth, p->default_colour, runs_items))) return rc;
+    svo_build_state *s = ctx->build.get();
     memset(s->cms, 0, sizeof s->cms);
-
-    HIP_TRY(ctx, hipEventRecord(s->ev[0], ctx->stream));
-    HIP_TRY(ctx, hipMemsetAsync(s->counts, 0, kCountSlots * sizeof(uint32_t), ctx->stream));
-    HIP_TRY(ctx, hipMemsetAsync(s->runs, 0, runs_items * sizeof(uint32_t), ctx->stream));
-    build_keys_kernel<<<svo_div_up(n, kThreads), kThreads, 0, ctx->stream>>>(xyz, (uint32_t)n, depth, s->keys[0], s->vals[0],
-                                                                             s->counts + kErrSlot);
-    HIP_TRY(ctx, hipGetLastError());
-    HIP_TRY(ctx, hipEventRecord(s->ev[1], ctx->stream));
-    const uint32_t passes = (3 * depth + 7) / 8;
-    if ((rc = sort_passes(ctx, (uint32_t)n, passes))) return rc;
-    HIP_TRY(ctx, hipEventRecord(s->ev[2], ctx->stream));
-    LevelIn in{};
-    in.keys = s->keys[passes & 1];
-    in.vals = s->vals[passes & 1];
-    in.colours = colours;
-    in.colour = p->default_colour;
-    in.m_max = (uint32_t)n;
-    LevelOut out{};
-    out.keys = s->keys[2];
-    out.colours = s->leaf_colours;
-    out.cap = (uint32_t)s->items;
-    if ((rc = level_pass<kDedupe>(ctx, in, out, n, s->counts + depth))) return rc;
     uint64_t bound[23] = {};
-    bound[depth] = n;
-    for (uint32_t l = depth; l-- > 0;) bound[l] = std::min<uint64_t>(bound[l + 1], 1ull << (3 * l));
+    level_bounds(bound, depth, n);
     ChunkPlan plan{wd, n_chunks, nullptr, 0};
     if ((rc = parent_passes(ctx, depth, std::max(wd, 1u), bound, nullptr, nullptr, 0, &plan))) return rc;
-    HIP_TRY(ctx, hipEventRecord(s->ev[3], ctx->stream));
-    HIP_TRY(ctx, hipMemcpyAsync(s->counts_host, s->counts, kCountSlots * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipMemcpyAsync(s->runs_host, s->runs, runs_items * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipEventRecord(s->ev[4], ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    if ((rc = read_counts(ctx, depth, runs_items))) return rc;
     const uint32_t *m = s->counts_host;
-    if (m[kErrSlot]) return svo_fail(ctx, SVO_ERR_ARG, "a voxel coordinate is outside [0, 2^depth) (depth " + std::to_string(depth) + ")");
 
     // every chunk's local level bases (breadth-first: level 1 at 0, level L + 1 behind level L's groups) and its place
     const uint32_t stride = cd + 2;
@@ -686,12 +716,8 @@ int chunk_build(svo_ctx *ctx, const uint32_t *xyz, const uint32_t *colours, size
             b[L] = (uint32_t)at;
             at += 8 * count(wd + L - 1);
             if (at > cap) {
-                uint32_t cx = 0, cy = 0, cz = 0;
-                for (uint32_t k = 0; k < wd; k++) {
-                    cx |= (c >> (3 * k + 2) & 1u) << k;
-                    cy |= (c >> (3 * k + 1) & 1u) << k;
-                    cz |= (c >> (3 * k) & 1u) << k;
-                }
+                uint32_t cx, cy, cz;
+                morton_decode(c, wd, cx, cy, cz);
                 return svo_fail(ctx, SVO_ERR_CAP, "chunk (" + std::to_string(cx) + ", " + std::to_string(cy) + ", " + std::to_string(cz) +
                                                       ") needs more than " + std::to_string(cap) + " nodes (max_nodes " +
                                                       std::to_string(p->max_nodes) + ", 0 = 256 000 000; at most 2^31)");
@@ -706,37 +732,33 @@ int chunk_build(svo_ctx *ctx, const uint32_t *xyz, const uint32_t *colours, size
     if ((rc = svo_grow(ctx, &s->coff_items, coff.size(), &s->coff))) return rc;
     if ((rc = svo_grow(ctx, &s->node_items, total, &s->nodes))) return rc;
     if ((rc = svo_grow_pinned(ctx, &s->stage_bytes, largest * 8, &s->stage))) return rc;
-    if (!dir.empty() && mkdir(dir.c_str(), 0777) != 0)
-        return svo_fail(ctx, errno == EEXIST ? SVO_ERR_ARG : SVO_ERR_STATE,
-                        errno == EEXIST ? "File already exists" : "cannot create " + dir + ": " + strerror(errno));
+    if (world && (rc = world->create())) return rc;
 
     // emit and mips
     HIP_TRY(ctx, hipMemcpyAsync(s->cbase, cbase.data(), cbase.size() * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(ctx, hipMemcpyAsync(s->coff, coff.data(), coff.size() * sizeof(uint64_t), hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(ctx, hipEventRecord(s->cev[0], ctx->stream));
+    HIP_TRY(ctx, hipEventRecord(s->ev[kEvChunkEmit], ctx->stream));
     build_fill_kernel<<<std::max(std::min(svo_div_up(total, kThreads), 65536u), 1u), kThreads, 0, ctx->stream>>>(s->nodes, total);
     HIP_TRY(ctx, hipGetLastError());
     for (uint32_t l = 1; l <= depth; l++) bound[l] = m[l];
     plan.nodes = s->nodes;
     plan.n_nodes = total;
     if ((rc = parent_passes(ctx, depth, wd + 1, bound, nullptr, nullptr, 0, &plan))) return rc;
-    HIP_TRY(ctx, hipEventRecord(s->cev[1], ctx->stream));
+    HIP_TRY(ctx, hipEventRecord(s->ev[kEvChunkEmitEnd], ctx->stream));
     for (uint32_t l = depth - 1; l > wd; l--) {  // bottom-up; level `depth` is all leaves
         const uint32_t lanes = 8u * m[l - 1];
         build_mip_kernel<<<svo_div_up(lanes, kThreads), kThreads, 0, ctx->stream>>>(s->nodes, s->coff, s->cbase, s->runs + size_t(l - 1) * row,
                                                                                      n_chunks, stride, l - wd, lanes);
         HIP_TRY(ctx, hipGetLastError());
     }
-    HIP_TRY(ctx, hipEventRecord(s->cev[2], ctx->stream));
+    HIP_TRY(ctx, hipEventRecord(s->ev[kEvChunkMips], ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
 
     // chunks in id order: (cx * side + cy) * side + cz, chunk index = Morton code of (cx, cy, cz)
     const uint32_t side = 1u << wd;
     double copy_ms = 0, take_ms = 0;
     for (uint32_t id = 0; id < n_chunks; id++) {
-        const uint32_t cx = id / (side * side), cy = id / side % side, cz = id % side;
-        uint32_t c = 0;
-        for (uint32_t b = 0; b < wd; b++) c |= (cx >> b & 1u) << (3 * b + 2) | (cy >> b & 1u) << (3 * b + 1) | (cz >> b & 1u) << (3 * b);
+        const uint32_t c = (uint32_t)morton_encode(id / (side * side), id / side % side, id % side, wd);
         const uint64_t nodes = cbase[size_t(c) * stride + cd + 1];
         if (!nodes) continue;
         double t = svo_now_ms();
@@ -747,9 +769,7 @@ int chunk_build(svo_ctx *ctx, const uint32_t *xyz, const uint32_t *colours, size
         if ((rc = take(id, (const uint8_t *)s->stage, nodes))) return rc;
         take_ms += svo_now_ms() - t;
     }
-    const int first[6] = {0, 1, 2, 3, 0, 1}, last[6] = {1, 2, 3, 4, 1, 2};
-    for (int k = 0; k < 6; k++)
-        HIP_TRY(ctx, hipEventElapsedTime(&s->cms[k], k < 4 ? s->ev[first[k]] : s->cev[first[k]], k < 4 ? s->ev[last[k]] : s->cev[last[k]]));
+    for (int k = 0; k < 6; k++) HIP_TRY(ctx, hipEventElapsedTime(&s->cms[k], s->ev[kChunkSlots[k].first], s->ev[kChunkSlots[k].last]));
     s->cms[6] = float(copy_ms);
     s->cms[7] = float(take_ms);
     s->cms[8] = float(svo_now_ms() - t0);
@@ -766,64 +786,75 @@ void chunk_top_mip(const uint8_t *bytes, uint8_t rgb[3]) {
     rgb[2] = t >> 16 & 0xFFu;
 }
 
-int check_chunk_params(svo_ctx *ctx, const uint32_t *xyz, size_t n, const svo_chunk_build_params *p, bool world) {
-    if (!p) return svo_fail(ctx, SVO_ERR_ARG, "null params");
-    if (p->depth < 1 || p->depth > 21) return svo_fail(ctx, SVO_ERR_ARG, "depth must be 1..21 (got " + std::to_string(p->depth) + ")");
-    if (!world && p->world_depth != 0) return svo_fail(ctx, SVO_ERR_ARG, "world_depth must be 0 for a single tree");
-    if (world && (p->world_depth < 1 || p->world_depth > 4 || p->world_depth >= p->depth))
-        return svo_fail(ctx, SVO_ERR_ARG, "world_depth must be 1..4 and below depth (got " + std::to_string(p->world_depth) +
-                                              ", depth " + std::to_string(p->depth) + ")");
-    if (n >= (1ull << 31)) return svo_fail(ctx, SVO_ERR_ARG, "at most 2^31 - 1 voxels per build");
-    if (!xyz && n) return svo_fail(ctx, SVO_ERR_ARG, "null coordinates");
+}  // namespace
+
+// ---- the world writer (svo_ctx.h): the layout of a generated world's directory, for svo_world_build below and
+// svo_world_generate (svo_proc.hip) ----
+svo_world_writer::svo_world_writer(svo_ctx *ctx, svo_world *w, uint32_t world_depth)
+    : ctx(ctx), w(w), world_depth(world_depth), path(svo_world_path(w)) {}
+
+svo_world_writer::~svo_world_writer() { svo_cpu_octree_free(root); }
+
+int svo_world_writer::refuse_existing() {
+    if (path.empty()) return svo_fail(ctx, SVO_ERR_ARG, "world has no path");
+    struct stat st;
+    if (stat(path.c_str(), &st) == 0) return svo_fail(ctx, SVO_ERR_ARG, "File already exists");  // World::generate_world's words
     return SVO_OK;
 }
 
-}  // namespace
+int svo_world_writer::create() {
+    int rc = refuse_existing();
+    if (rc) return rc;
+    if (mkdir(path.c_str(), 0777) != 0) return svo_fail(ctx, SVO_ERR_STATE, "cannot create " + path + ": " + strerror(errno));
+    root = svo_cpu_octree_new(0);
+    return SVO_OK;
+}
+
+int svo_world_writer::add_chunk(uint32_t i, const void *bytes, uint64_t n_nodes) {
+    const uint32_t id = SVO_CHUNK_OFFSET / 2 + i, side = 1u << world_depth;
+    uint8_t top[3];
+    chunk_top_mip((const uint8_t *)bytes, top);
+    if (svo_world_write_chunk(w, id, bytes, n_nodes * 8, top) != 0)
+        return svo_fail(ctx, SVO_ERR_STATE, std::string("save: ") + svo_world_last_error(w));
+    const float voxel = 2.0f / float(side);
+    const float pos[3] = {float(i / (side * side)) * voxel - 1.0f, float(i / side % side) * voxel - 1.0f, float(i % side) * voxel - 1.0f};
+    svo_cpu_octree_put_in_block(root, pos, id, world_depth);
+    return SVO_OK;
+}
+
+int svo_world_writer::finish(float *mip_ms, float *save_ms) {
+    svo_world_insert(w, 0, root);  // (the world owns it from here)
+    root = nullptr;
+    double t = svo_now_ms();
+    if (svo_world_generate_mip_tree(w, 0, nullptr) != 0) return svo_fail(ctx, SVO_ERR_STATE, std::string("mips: ") + svo_world_last_error(w));
+    *mip_ms = float(svo_now_ms() - t);
+    t = svo_now_ms();
+    if (svo_world_save_chunk(w, 0) != 0) return svo_fail(ctx, SVO_ERR_STATE, std::string("save: ") + svo_world_last_error(w));
+    *save_ms = float(svo_now_ms() - t);
+    return SVO_OK;
+}
 
 extern "C" {
 
 int svo_nodes_build(svo_ctx *ctx, const uint32_t *xyz, const uint32_t *colours, size_t n, const svo_build_params *p,
                     uint64_t *n_words_out) {
     if (!ctx) return SVO_ERR_ARG;
-    int rc = check_common(ctx, p, 21, n_words_out);
+    if (n_words_out) *n_words_out = 0;
+    int rc = check_list(ctx, p ? &p->depth : nullptr, nullptr, false, xyz, n);
     if (rc) return rc;
-    if (n >= (1ull << 31)) return svo_fail(ctx, SVO_ERR_ARG, "at most 2^31 - 1 voxels per build");
-    if (!xyz && n) return svo_fail(ctx, SVO_ERR_ARG, "null coordinates");
     if (!n_words_out) return svo_fail(ctx, SVO_ERR_ARG, "null n_words_out");
     if ((rc = check_store(ctx))) return rc;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     if (!n) return build_empty(ctx, p, n_words_out);
     const double t0 = svo_now_ms();
-    const uint32_t depth = p->depth, nt = svo_div_up(n, kTile);
-    if ((rc = ensure_state(ctx, n, std::max<uint64_t>(n, 256ull * nt), 256ull * nt))) return rc;
-    svo_build_state *s = ctx->build.get();
-    HIP_TRY(ctx, hipEventRecord(s->ev[0], ctx->stream));
-    HIP_TRY(ctx, hipMemsetAsync(s->counts, 0, kCountSlots * sizeof(uint32_t), ctx->stream));
-    build_keys_kernel<<<svo_div_up(n, kThreads), kThreads, 0, ctx->stream>>>(xyz, (uint32_t)n, depth, s->keys[0], s->vals[0],
-                                                                             s->counts + kErrSlot);
-    HIP_TRY(ctx, hipGetLastError());
-    HIP_TRY(ctx, hipEventRecord(s->ev[1], ctx->stream));
-    const uint32_t passes = (3 * depth + 7) / 8;
-    if ((rc = sort_passes(ctx, (uint32_t)n, passes))) return rc;
-    HIP_TRY(ctx, hipEventRecord(s->ev[2], ctx->stream));
-    // leaf level: the last voxel of every run of equal keys
-    LevelIn in{};
-    in.keys = s->keys[passes & 1];
-    in.vals = s->vals[passes & 1];
-    in.colours = colours;
-    in.colour = p->default_colour;
-    in.m_max = (uint32_t)n;
-    LevelOut out{};
-    out.keys = s->keys[2];
-    out.colours = s->leaf_colours;
-    out.cap = (uint32_t)s->items;
-    if ((rc = level_pass<kDedupe>(ctx, in, out, n, s->counts + depth))) return rc;
+    if ((rc = list_leaves(ctx, xyz, colours, n, p->depth, p->default_colour, 0))) return rc;
     return finish(ctx, p, n, t0, true, n_words_out);
 }
 
 int svo_nodes_build_dense(svo_ctx *ctx, const uint32_t *grid, const svo_build_params *p, uint64_t *n_words_out) {
     if (!ctx) return SVO_ERR_ARG;
-    int rc = check_common(ctx, p, 10, n_words_out);
+    if (n_words_out) *n_words_out = 0;
+    int rc = check_depth(ctx, p ? &p->depth : nullptr, 10);
     if (rc) return rc;
     if (!grid) return svo_fail(ctx, SVO_ERR_ARG, "null grid");
     if (!n_words_out) return svo_fail(ctx, SVO_ERR_ARG, "null n_words_out");
@@ -837,10 +868,10 @@ int svo_nodes_build_dense(svo_ctx *ctx, const uint32_t *grid, const svo_build_pa
     const uint64_t room = std::max<uint64_t>(std::min(cells, word_limit(ctx, p)), 1);
     if ((rc = ensure_state(ctx, room, cells, 0))) return rc;
     svo_build_state *s = ctx->build.get();
-    HIP_TRY(ctx, hipEventRecord(s->ev[0], ctx->stream));
+    HIP_TRY(ctx, hipEventRecord(s->ev[kEvStart], ctx->stream));
     HIP_TRY(ctx, hipMemsetAsync(s->counts, 0, kCountSlots * sizeof(uint32_t), ctx->stream));
-    HIP_TRY(ctx, hipEventRecord(s->ev[1], ctx->stream));
-    HIP_TRY(ctx, hipEventRecord(s->ev[2], ctx->stream));
+    HIP_TRY(ctx, hipEventRecord(s->ev[kEvKeys], ctx->stream));
+    HIP_TRY(ctx, hipEventRecord(s->ev[kEvSort], ctx->stream));
     LevelIn in{};
     in.colours = grid;
     in.m_max = (uint32_t)cells;
@@ -858,13 +889,12 @@ int svo_build_timing(svo_ctx *ctx, float ms_out[SVO_BUILD_TIMES]) {
     if (!ctx->build) return svo_fail(ctx, SVO_ERR_STATE, "no tree built on this context yet");
     svo_build_state *s = ctx->build.get();
     if (!s->timed) {
-        const int first[5] = {0, 1, 2, 3, 5}, last[5] = {1, 2, 3, 4, 6};
         HIP_TRY(ctx, hipSetDevice(ctx->device));
-        HIP_TRY(ctx, hipEventSynchronize(s->ev[6]));
+        HIP_TRY(ctx, hipEventSynchronize(s->ev[kEvEmitEnd]));
         for (int k = 0; k < 5; k++) {
             s->ms[k] = 0.0f;
             if (k == 1 && !s->sorted) continue;  // (dense: no sort)
-            HIP_TRY(ctx, hipEventElapsedTime(&s->ms[k], s->ev[first[k]], s->ev[last[k]]));
+            HIP_TRY(ctx, hipEventElapsedTime(&s->ms[k], s->ev[kBuildSlots[k].first], s->ev[kBuildSlots[k].last]));
         }
         s->timed = true;
     }
@@ -877,10 +907,10 @@ int svo_cpu_octree_build(svo_ctx *ctx, const uint32_t *xyz, const uint32_t *colo
     if (!ctx) return SVO_ERR_ARG;
     if (!out) return svo_fail(ctx, SVO_ERR_ARG, "null output");
     *out = nullptr;
-    int rc = check_chunk_params(ctx, xyz, n, p, false);
+    int rc = check_list(ctx, p ? &p->depth : nullptr, p, false, xyz, n);
     if (rc) return rc;
     svo_cpu_octree *tree = nullptr;
-    rc = chunk_build(ctx, xyz, colours, n, p, std::string(), [&](uint32_t, const uint8_t *bytes, uint64_t nodes) -> int {
+    rc = chunk_build(ctx, xyz, colours, n, p, nullptr, [&](uint32_t, const uint8_t *bytes, uint64_t nodes) -> int {
         char why[128] = "";
         tree = svo_cpu_octree_from_bin(bytes, nodes * 8, why, sizeof why);
         if (!tree) return svo_fail(ctx, SVO_ERR_STATE, std::string("emitted tree rejected: ") + why);
@@ -900,42 +930,18 @@ int svo_cpu_octree_build(svo_ctx *ctx, const uint32_t *xyz, const uint32_t *colo
 int svo_world_build(svo_ctx *ctx, svo_world *w, const uint32_t *xyz, const uint32_t *colours, size_t n, const svo_chunk_build_params *p) {
     if (!ctx) return SVO_ERR_ARG;
     if (!w) return svo_fail(ctx, SVO_ERR_ARG, "null world");
-    int rc = check_chunk_params(ctx, xyz, n, p, true);
+    int rc = check_list(ctx, p ? &p->depth : nullptr, p, true, xyz, n);
     if (rc) return rc;
-    const std::string path = svo_world_path(w);
-    if (path.empty()) return svo_fail(ctx, SVO_ERR_ARG, "world has no path");
-    struct stat st;
-    if (stat(path.c_str(), &st) == 0) return svo_fail(ctx, SVO_ERR_ARG, "File already exists");  // World::generate_world's words
-    const uint32_t wd = p->world_depth, side = 1u << wd;
-    const float voxel = 2.0f / float(side);
-    svo_cpu_octree *root = svo_cpu_octree_new(0);
-    // as svo_world_generate: every non-empty chunk saved and kept as its top_mip, referenced from the root in id order
-    rc = chunk_build(ctx, xyz, colours, n, p, path, [&](uint32_t i, const uint8_t *bytes, uint64_t nodes) -> int {
-        const uint32_t id = SVO_CHUNK_OFFSET / 2 + i;
-        if (svo_world_write_chunk(w, id, bytes, nodes * 8) != 0)
-            return svo_fail(ctx, SVO_ERR_STATE, std::string("save: ") + svo_world_last_error(w));
-        uint8_t top[3];
-        chunk_top_mip(bytes, top);
-        svo_cpu_octree *chunk = svo_cpu_octree_new(0);
-        svo_cpu_octree_drop_nodes(chunk);
-        svo_cpu_octree_set_top_mip(chunk, top);
-        svo_world_insert(w, id, chunk);
-        const float pos[3] = {float(i / (side * side)) * voxel - 1.0f, float(i / side % side) * voxel - 1.0f, float(i % side) * voxel - 1.0f};
-        svo_cpu_octree_put_in_block(root, pos, id, wd);
-        return SVO_OK;
-    });
-    if (rc) {
-        svo_cpu_octree_free(root);
-        return rc;
-    }
-    const double t = svo_now_ms();
-    svo_world_insert(w, 0, root);
-    if (svo_world_generate_mip_tree(w, 0, nullptr) != 0 || svo_world_save_chunk(w, 0) != 0)
-        return svo_fail(ctx, SVO_ERR_STATE, std::string("root: ") + svo_world_last_error(w));
-    const float root_ms = float(svo_now_ms() - t);
+    svo_world_writer world(ctx, w, p->world_depth);
+    if ((rc = world.refuse_existing())) return rc;
+    rc = chunk_build(ctx, xyz, colours, n, p, &world,
+                     [&](uint32_t i, const uint8_t *bytes, uint64_t nodes) -> int { return world.add_chunk(i, bytes, nodes); });
+    if (rc) return rc;
+    float mip_ms = 0.0f, save_ms = 0.0f;
+    if ((rc = world.finish(&mip_ms, &save_ms))) return rc;
     if (ctx->build) {
-        ctx->build->cms[7] += root_ms;
-        ctx->build->cms[8] += root_ms;
+        ctx->build->cms[7] += mip_ms + save_ms;
+        ctx->build->cms[8] += mip_ms + save_ms;
     }
     return SVO_OK;
 }

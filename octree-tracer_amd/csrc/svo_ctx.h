@@ -1,6 +1,8 @@
 // svo_ctx.h -- the device context behind the opaque `svo_ctx` of include/svo_hip.h, and the host helpers of the files that
 // use it: svo_abi.cpp (trace / scan dispatch), svo_comm.cpp (RCCL frame gather) and the GPU tree passes (svo_proc.hip,
-// svo_build.hip, svo_adapt.hip).  Internal: not part of the boundary.
+// svo_build.hip, svo_adapt.hip).  Shared by the passes: svo_grow / svo_grow_pinned (workspaces), the builder's sort and scan,
+// svo_world_writer (a generated world's directory); svo_scan.h, svo_mip.h and svo_morton.h hold the device pieces.
+// Internal: not part of the boundary.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -172,13 +174,34 @@ void svo_comm_release(svo_ctx *ctx);
 // passes on the ctx stream; both use the builder's workspace
 int svo_build_sort_u32(svo_ctx *ctx, const uint32_t *in, uint32_t n, uint32_t *out);
 int svo_build_scan_u32(svo_ctx *ctx, uint32_t *a, uint32_t n);
-// svo_host.cpp (internal helpers of svo_world_generate and the chunk builder, svo_build.hip)
+// The one writer of a generated world's directory (svo_build.hip), for svo_world_build and
+// svo_world_generate: create() makes the directory and the empty root; add_chunk() writes <id>.bin (id = SVO_CHUNK_OFFSET
+// / 2 + i) from `bytes` in the <id>.bin layout, keeps the chunk in w as a node-less CpuOctree carrying its top_mip (the
+// mip of its root group) and references it from the root at i -> (x, y, z) * 2 / 2^world_depth - 1; finish() hands the
+// root to w as chunk 0, mips it on the host and saves 0.bin (*mip_ms, *save_ms: the host times of the two).  The root is
+// the writer's until finish(), so any early return frees it.  Failures are the context's (svo_fail).
+struct svo_world_writer {
+    svo_world_writer(svo_ctx *ctx, svo_world *w, uint32_t world_depth);
+    ~svo_world_writer();
+    int refuse_existing();  // SVO_ERR_ARG: the world has no path, or the path exists ("File already exists")
+    int create();           // refuse_existing(), then the directory
+    int add_chunk(uint32_t i, const void *bytes, uint64_t n_nodes);
+    int finish(float *mip_ms, float *save_ms);
+
+   private:
+    svo_ctx *ctx;
+    svo_world *w;
+    uint32_t world_depth;
+    std::string path;
+    svo_cpu_octree *root = nullptr;
+};
+// svo_host.cpp (what the writer and the two chunk producers need of the host model beyond include/svo_host.h)
 std::string svo_world_path(const svo_world *w);
-void svo_cpu_octree_drop_nodes(svo_cpu_octree *t);  // frees the nodes, keeps top_mip (world.rs:122)
 void svo_cpu_octree_set_top_mip(svo_cpu_octree *t, const uint8_t rgb[3]);
 void svo_cpu_octree_top_mip(const svo_cpu_octree *t, uint8_t rgb[3]);
-// <w's path>/<id>.bin from `len` bytes in the <id>.bin layout; 0 or -1 (svo_world_last_error says why)
-int svo_world_write_chunk(svo_world *w, uint32_t id, const void *bytes, size_t len);
+// <w's path>/<id>.bin from `len` bytes in the <id>.bin layout; the chunk stays in w without nodes, as its top_mip alone
+// (world.rs:122).  0 or -1 (svo_world_last_error says why)
+int svo_world_write_chunk(svo_world *w, uint32_t id, const void *bytes, size_t len, const uint8_t top_mip[3]);
 // svo_host.cpp (internal helpers of the device adaptive state): the octree's words, positions (3 floats per node) and hole
 // stack (bottom first) as they are; svo_octree_assign replaces all three and clears the dirty set
 size_t svo_octree_state(const svo_octree *o, const uint32_t **nodes, const float **positions, std::vector<uint32_t> &holes);

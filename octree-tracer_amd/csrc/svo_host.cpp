@@ -1205,20 +1205,23 @@ uint32_t svo_nodes_max_depth(const uint32_t *words, uint64_t n) {
 }  // extern "C"
 
 // ------------------------------------------------------------------------------------------
-// Internal helpers of svo_world_generate (svo_proc.hip); declared in csrc/svo_ctx.h, not part of the C ABI
+// Internal helpers of the world writer and the chunk producers (svo_build.hip, svo_proc.hip); declared in csrc/svo_ctx.h,
+// not part of the C ABI
 // ------------------------------------------------------------------------------------------
 std::string svo_world_path(const svo_world *w) { return w->path; }
-
-void svo_cpu_octree_drop_nodes(svo_cpu_octree *t) { std::vector<svo_cpu_octree::Node>().swap(t->nodes); }
 
 void svo_cpu_octree_set_top_mip(svo_cpu_octree *t, const uint8_t rgb[3]) { t->top_mip = Rgb{rgb[0], rgb[1], rgb[2]}; }
 void svo_cpu_octree_top_mip(const svo_cpu_octree *t, uint8_t rgb[3]) { rgb[0] = t->top_mip.r; rgb[1] = t->top_mip.g; rgb[2] = t->top_mip.b; }
 
-int svo_world_write_chunk(svo_world *w, uint32_t id, const void *bytes, size_t len) {
+int svo_world_write_chunk(svo_world *w, uint32_t id, const void *bytes, size_t len, const uint8_t top_mip[3]) {
     FILE *f = fopen(chunk_file(*w, id).c_str(), "wb");
     if (!f) return world_fail(w, "cannot create " + chunk_file(*w, id));
     const bool ok = fwrite(bytes, 1, len, f) == len;
-    return fclose(f) == 0 && ok ? 0 : world_fail(w, "short write to " + chunk_file(*w, id));
+    if (fclose(f) != 0 || !ok) return world_fail(w, "short write to " + chunk_file(*w, id));
+    svo_cpu_octree *chunk = svo_cpu_octree_new(0);
+    std::vector<svo_cpu_octree::Node>().swap(chunk->nodes);  // keep only top_mip in memory (world.rs:122)
+    svo_cpu_octree_set_top_mip(chunk, top_mip);
+    return svo_world_insert(w, id, chunk);
 }
 
 // The device adaptive state (svo_adapt.hip) uploads and restores the octree as it is: words, positions (three floats per

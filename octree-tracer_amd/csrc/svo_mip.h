@@ -2,7 +2,8 @@
 // (svo_build.hip) and the procedural world generator (svo_proc.hip).  A node is a uint2: x = pointer (interior: index of
 // its child group in the chunk; leaf: >= SVO_CHUNK_OFFSET), y = r | g << 8 | b << 16.  Levels run bottom-up, one launch
 // per level and one lane per node; a lane reads its child group (64 contiguous bytes) once and writes its own rgb word.
-// No atomics, no scratch.  Everything sits in an anonymous namespace, like svo_scan.h.
+// No atomics, no scratch.  mip_of is also the host's formula for a written chunk's top_mip (chunk_top_mip in
+// svo_build.hip, for svo_cpu_octree_build and svo_world_writer).  Everything sits in an anonymous namespace, like svo_scan.h.
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -1,0 +1,30 @@
+// svo_morton.h -- the one Morton convention of the GPU tree passes (svo_build.hip, svo_proc.hip), on the host and on the
+// device: bit b of x, y, z sits in key bits 3b + 2, 3b + 1, 3b, so three key bits are a child index x*4 + y*2 + z and
+// level 1 is in the top bits.  depth <= 21 (a key fits 63 bits).  Everything sits in an anonymous namespace, like
+// svo_scan.h.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+
+namespace {
+
+__host__ __device__ inline uint64_t morton_encode(uint32_t x, uint32_t y, uint32_t z, uint32_t depth) {
+    uint64_t k = 0;
+    for (uint32_t b = 0; b < depth; b++)
+        k |= uint64_t((x >> b) & 1u) << (3 * b + 2) | uint64_t((y >> b) & 1u) << (3 * b + 1) | uint64_t((z >> b) & 1u) << (3 * b);
+    return k;
+}
+
+// K: the key's own width (a kernel whose keys fit 32 bits decodes in 32-bit registers)
+template <typename K>
+__host__ __device__ inline void morton_decode(K k, uint32_t depth, uint32_t &x, uint32_t &y, uint32_t &z) {
+    x = y = z = 0;
+    for (uint32_t b = 0; b < depth; b++) {
+        z |= uint32_t((k >> (3 * b)) & 1u) << b;
+        y |= uint32_t((k >> (3 * b + 1)) & 1u) << b;
+        x |= uint32_t((k >> (3 * b + 2)) & 1u) << b;
+    }
+}
+
+}  // namespace

@@ -13,19 +13,20 @@
 //   mips       (svo_world_generate only) block leaves take their block's top_mip, then svo_mip.h's pass bottom-up
 //
 // All work runs on the context's stream.  Sizes come from the count pass; there are no atomics and no retries.
+// Shared with the tree builder: the tile shape and scans (svo_scan.h), the Morton convention (svo_morton.h), the mip pass
+// (svo_mip.h), svo_grow for the workspace and svo_world_writer for svo_world_generate's directory (svo_ctx.h; the writer
+// itself is in svo_build.hip).
 #include <hip/hip_runtime.h>
 
-#include <sys/stat.h>
-
-#include <cerrno>
 #include <cstring>
 #include <string>
 #include <vector>
 
 #include "svo_ctx.h"
 #include "svo_host.h"
-#include "svo_mip.h"   // (the world path mips its chunks on the device, as svo_world_build does)
-#include "svo_scan.h"  // (a level's mask bytes are scanned in tiles of kTile)
+#include "svo_mip.h"     // (the world path mips its chunks on the device, as svo_world_build does)
+#include "svo_morton.h"  // (lanes walk the cells in Morton order)
+#include "svo_scan.h"    // (a level's mask bytes are scanned in tiles of kTile)
 
 namespace {
 
@@ -156,15 +157,6 @@ struct ChunkGeom {
     uint32_t depth;    // chunk_depth
 };
 
-__device__ inline void morton_decode(uint32_t m, uint32_t depth, uint32_t &x, uint32_t &y, uint32_t &z) {
-    x = y = z = 0;
-    for (uint32_t b = 0; b < depth; b++) {
-        z |= ((m >> (3 * b)) & 1u) << b;
-        y |= ((m >> (3 * b + 1)) & 1u) << b;
-        x |= ((m >> (3 * b + 2)) & 1u) << b;
-    }
-}
-
 // class byte of one cell: 0 empty, 3 grass (nothing solid one voxel above), 1 stone (procedual.wgsl:189-201)
 __device__ inline uint32_t classify_cell(const ChunkGeom &g, uint32_t x, uint32_t y, uint32_t z) {
     // world = pos + (cell / 2^full) * 2; the product cell * (2 / 2^full) is the same exact value
@@ -274,14 +266,15 @@ uint64_t pad_tile(uint64_t n) { return (n + kTile - 1) / kTile * kTile; }
 
 }  // namespace
 
-// Per-context workspace of the generator (svo_ctx::proc), sized for the deepest chunk generated so far.
+// Per-context workspace of the generator (svo_ctx::proc).  The level buffers only grow (svo_grow): they have the room of
+// the deepest chunk generated so far, and a shallower chunk lays its levels out in the same memory.
 struct svo_proc_state {
     uint32_t depth = 0;               // chunk_depth the level buffers are laid out for
-    uint32_t alloc_depth = 0;         // chunk_depth they were allocated for (>= depth)
     uint8_t *cls = nullptr;           // 8^depth class bytes, Morton order
     uint8_t *masks = nullptr;         // levels 0 .. depth-1: child masks, each level zero-padded to whole tiles
     uint32_t *ranks = nullptr;        // levels 0 .. depth-1: exclusive ranks of the interior nodes
     uint32_t *tiles = nullptr;        // levels 0 .. depth-1: tile counts, then tile offsets
+    size_t cls_items = 0, mask_items = 0, rank_items = 0, tile_items = 0;  // room in each of the four
     uint32_t *totals = nullptr;       // interior nodes per level (device)
     uint32_t *totals_host = nullptr;  // (pinned)
     size_t mask_bytes = 0;
@@ -327,7 +320,7 @@ ChunkGeom geom_of(const svo_proc_params *p) {
     return g;
 }
 
-// workspace for chunks of `depth` levels (kept between calls; regrown for a deeper chunk)
+// workspace for chunks of `depth` levels (kept between calls; grown for a deeper chunk)
 int ensure_state(svo_ctx *ctx, uint32_t depth) {
     if (!ctx->proc) {
         ctx->proc = svo_workspace_new<svo_proc_state>();
@@ -338,14 +331,7 @@ int ensure_state(svo_ctx *ctx, uint32_t depth) {
     }
     svo_proc_state *s = ctx->proc.get();
     if (s->depth == depth) return SVO_OK;
-    if (s->alloc_depth < depth) {  // a shallower chunk reuses the buffers of a deeper one: every level fits
-        for (void *p : {(void *)s->cls, (void *)s->masks, (void *)s->ranks, (void *)s->tiles})
-            if (p) (void)hipFree(p);
-        s->cls = s->masks = nullptr;
-        s->ranks = s->tiles = nullptr;
-        s->alloc_depth = 0;
-        s->depth = 0;
-    }
+    s->depth = 0;  // (until the buffers have room for the new layout)
     uint64_t mb = 0, rb = 0, tb = 0;
     for (uint32_t l = 0; l < depth; l++) {
         const uint64_t n = pad_tile(1ull << (3 * l));
@@ -358,13 +344,11 @@ int ensure_state(svo_ctx *ctx, uint32_t depth) {
         tb += n / kTile;
     }
     s->mask_bytes = mb;
-    if (!s->cls) {
-        HIP_TRY(ctx, hipMalloc((void **)&s->cls, 1ull << (3 * depth)));
-        HIP_TRY(ctx, hipMalloc((void **)&s->masks, mb));
-        HIP_TRY(ctx, hipMalloc((void **)&s->ranks, rb * sizeof(uint32_t)));
-        HIP_TRY(ctx, hipMalloc((void **)&s->tiles, tb * sizeof(uint32_t)));
-    }
-    if (!s->alloc_depth) s->alloc_depth = depth;
+    int rc = svo_grow(ctx, &s->cls_items, (size_t)1 << (3 * depth), &s->cls);
+    if (!rc) rc = svo_grow(ctx, &s->mask_items, mb, &s->masks);
+    if (!rc) rc = svo_grow(ctx, &s->rank_items, rb, &s->ranks);
+    if (!rc) rc = svo_grow(ctx, &s->tile_items, tb, &s->tiles);
+    if (rc) return rc;
     s->depth = depth;
     return SVO_OK;
 }
@@ -417,12 +401,7 @@ int svo_proc_classify(svo_ctx *ctx, const svo_proc_params *params, uint8_t *cell
     // the reference's id order: id = x + side * y + side^2 * z (procedual.wgsl:160-170)
     for (uint32_t z = 0; z < side; z++)
         for (uint32_t y = 0; y < side; y++)
-            for (uint32_t x = 0; x < side; x++) {
-                uint32_t m = 0;
-                for (uint32_t b = 0; b < d; b++)
-                    m |= ((x >> b) & 1u) << (3 * b + 2) | ((y >> b) & 1u) << (3 * b + 1) | ((z >> b) & 1u) << (3 * b);
-                cells_out[x + side * y + side * side * z] = morton[m];
-            }
+            for (uint32_t x = 0; x < side; x++) cells_out[x + side * y + side * side * z] = morton[morton_encode(x, y, z, d)];
     return SVO_OK;
 }
 
@@ -492,6 +471,16 @@ int emit_chunk(svo_ctx *ctx, const svo_proc_params *params, double t0, uint64_t 
     return SVO_OK;
 }
 
+// The emitted chunk (and whatever the stream did to it since) into the pinned stage, grown to hold it; blocking.
+int read_stage(svo_ctx *ctx, size_t bytes) {
+    svo_proc_state *s = ctx->proc.get();
+    int rc = svo_grow_pinned(ctx, &s->stage_bytes, bytes, &s->stage);
+    if (rc) return rc;
+    HIP_TRY(ctx, hipMemcpyAsync(s->stage, s->out, bytes, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return SVO_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -509,9 +498,7 @@ int svo_proc_generate_chunk(svo_ctx *ctx, const svo_proc_params *params, svo_cpu
     svo_proc_state *s = ctx->proc.get();
     const size_t bytes = n_nodes * 8;
     const double t1 = svo_now_ms();
-    if ((rc = svo_grow_pinned(ctx, &s->stage_bytes, bytes, &s->stage))) return rc;
-    HIP_TRY(ctx, hipMemcpyAsync(s->stage, s->out, bytes, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    if ((rc = read_stage(ctx, bytes))) return rc;
     const double t2 = svo_now_ms();
     char why[128] = "";
     *out = svo_cpu_octree_from_bin(s->stage, bytes, why, sizeof why);
@@ -540,12 +527,9 @@ int svo_world_generate(svo_ctx *ctx, svo_world *w, uint32_t world_depth, uint32_
     if (chunk_depth < 2 || chunk_depth > 9) return svo_fail(ctx, SVO_ERR_ARG, "chunk_depth must be 2..9");
     for (uint32_t b = 1; b <= 8; b++)  // mips of block leaves need the blocks' top_mip (World::new, world.rs:19-58)
         if (!svo_world_chunk(w, b)) return svo_fail(ctx, SVO_ERR_STATE, "block " + std::to_string(b) + " is not loaded (insert blocks 1..8 first)");
-    const std::string path = svo_world_path(w);
-    if (path.empty()) return svo_fail(ctx, SVO_ERR_ARG, "world has no path");
-    if (mkdir(path.c_str(), 0777) != 0)
-        return svo_fail(ctx, errno == EEXIST ? SVO_ERR_ARG : SVO_ERR_STATE,
-                        errno == EEXIST ? "File already exists" : "cannot create " + path + ": " + strerror(errno));
-    auto world_fail = [&](const char *what) { return svo_fail(ctx, SVO_ERR_STATE, std::string(what) + ": " + svo_world_last_error(w)); };
+    svo_world_writer world(ctx, w, world_depth);  // (the directory is made before any GPU work)
+    int rc = world.create();
+    if (rc) return rc;
     float times[4] = {0, 0, 0, 0};  // GPU, read-back, mips, writes
     BlockMips blocks{};  // block leaves take their block's top_mip (as svo_world_generate_mip_tree does)
     for (uint32_t b = 1; b <= 8; b++) {
@@ -553,7 +537,6 @@ int svo_world_generate(svo_ctx *ctx, svo_world *w, uint32_t world_depth, uint32_
         svo_cpu_octree_top_mip(svo_world_chunk(w, b), rgb);
         blocks.rgb[b] = rgb[0] | rgb[1] << 8 | rgb[2] << 16;
     }
-    svo_cpu_octree *root = svo_cpu_octree_new(0);
     const uint32_t n = 1u << world_depth;
     const float voxel = 2.0f / float(n);
     uint32_t i = 0;
@@ -566,14 +549,9 @@ int svo_world_generate(svo_ctx *ctx, svo_world *w, uint32_t world_depth, uint32_
                 p.pos[2] = float(z) * voxel - 1.0f;
                 p.base_depth = world_depth;
                 p.chunk_depth = chunk_depth;
-                const uint32_t id = kChunkOffset / 2 + i;
                 uint64_t base[11], n_nodes = 0;
-                int rc = check_params(ctx, &p);
-                if (!rc) rc = emit_chunk(ctx, &p, svo_now_ms(), base, &n_nodes);
-                if (rc) {
-                    svo_cpu_octree_free(root);
-                    return rc;
-                }
+                if ((rc = check_params(ctx, &p))) return rc;
+                if ((rc = emit_chunk(ctx, &p, svo_now_ms(), base, &n_nodes))) return rc;
                 svo_proc_state *s = ctx->proc.get();
                 times[0] += s->ms[3];
                 if (!n_nodes) continue;
@@ -588,42 +566,21 @@ int svo_world_generate(svo_ctx *ctx, svo_world *w, uint32_t world_depth, uint32_
                 }
                 HIP_TRY(ctx, hipGetLastError());
                 HIP_TRY(ctx, hipEventRecord(s->mev[1], ctx->stream));
-                // one copy into the pinned stage; <id>.bin and top_mip come from there
+                // one copy into the pinned stage; the writer takes <id>.bin and top_mip from there
                 double t = svo_now_ms();
-                const size_t bytes = n_nodes * 8;
-                if ((rc = svo_grow_pinned(ctx, &s->stage_bytes, bytes, &s->stage))) {
-                    svo_cpu_octree_free(root);
-                    return rc;
-                }
-                HIP_TRY(ctx, hipMemcpyAsync(s->stage, s->out, bytes, hipMemcpyDeviceToHost, ctx->stream));
-                HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+                if ((rc = read_stage(ctx, n_nodes * 8))) return rc;
                 times[1] += float(svo_now_ms() - t);
                 float mip_ms = 0.0f;
                 HIP_TRY(ctx, hipEventElapsedTime(&mip_ms, s->mev[0], s->mev[1]));
                 times[2] += mip_ms;
                 t = svo_now_ms();
-                if (svo_world_write_chunk(w, id, s->stage, bytes) != 0) {
-                    svo_cpu_octree_free(root);
-                    return world_fail("save");
-                }
+                if ((rc = world.add_chunk(i, s->stage, n_nodes))) return rc;
                 times[3] += float(svo_now_ms() - t);
-                uint32_t top[8];  // top_mip: the mip of the root group
-                for (int c = 0; c < 8; c++) top[c] = reinterpret_cast<const uint32_t *>(s->stage)[2 * c + 1];
-                const uint32_t v = mip_of(top);
-                const uint8_t rgb[3] = {uint8_t(v), uint8_t(v >> 8), uint8_t(v >> 16)};
-                svo_cpu_octree *chunk = svo_cpu_octree_new(0);
-                svo_cpu_octree_drop_nodes(chunk);  // keep only top_mip in memory (world.rs:122)
-                svo_cpu_octree_set_top_mip(chunk, rgb);
-                svo_world_insert(w, id, chunk);
-                svo_cpu_octree_put_in_block(root, p.pos, id, world_depth);
             }
-    svo_world_insert(w, 0, root);
-    double t = svo_now_ms();
-    if (svo_world_generate_mip_tree(w, 0, nullptr) != 0) return world_fail("mips");
-    times[2] += float(svo_now_ms() - t);
-    t = svo_now_ms();
-    if (svo_world_save_chunk(w, 0) != 0) return world_fail("save");
-    times[3] += float(svo_now_ms() - t);
+    float mip_ms = 0.0f, save_ms = 0.0f;
+    if ((rc = world.finish(&mip_ms, &save_ms))) return rc;
+    times[2] += mip_ms;
+    times[3] += save_ms;
     memcpy(ctx->proc->ms + 6, times, sizeof times);
     return SVO_OK;
 }

@@ -1,6 +1,7 @@
 // svo_scan.h -- the scan pieces of the GPU tree passes (svo_proc.hip, svo_build.hip): the tile shape, a block-wide
 // exclusive scan and the one-block scan of the tile sums.  Everything sits in an anonymous namespace, so every pass file
-// that includes this header compiles its own copies, as it did when each file had its own.
+// that includes this header compiles its own copies, as it did when each file had its own.  The other shared device
+// pieces: svo_morton.h (the Morton convention), svo_mip.h (mip colours); the host ones are in svo_ctx.h.
 #pragma once
 #include <hip/hip_runtime.h>
 
