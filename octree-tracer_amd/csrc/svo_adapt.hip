@@ -28,12 +28,16 @@
 #include <vector>
 
 #include "svo_ctx.h"
-#include "svo_scan.h"  // (kThreads; tiles of kTile items for the expand's compactions)
+#include "svo_rules.h"  // (the walks, pointer classes and view rule the host path runs too)
+#include "svo_scan.h"   // (kThreads; tiles of kTile items for the expand's compactions)
 
 namespace {
 
+using svo_rules::leaf_word;
+using svo_rules::pos_offset;
+using svo_rules::Vec3;
+
 constexpr uint32_t kVoxelOff = SVO_VOXEL_OFFSET;
-constexpr uint32_t kChunkOff = SVO_CHUNK_OFFSET;
 constexpr uint32_t kNone = 0xFFFFFFFFu;
 constexpr uint32_t kFailed = 0xFFFFFFFEu;  // Chunk::rank of a chunk whose load failed in this pass (not resident)
 constexpr uint32_t kMaxTreeDepth = 31;     // pos_offset's 1 << depth
@@ -68,13 +72,7 @@ struct Status {
     uint32_t pad[2];
 };
 
-__device__ inline float3 pos_offset(uint32_t child, uint32_t depth) {  // svo_host.cpp / octree.rs:154-161, same rounding
-    const float d = float(1u << (depth & 31u));
-    return make_float3((float((child >> 2) & 1u) * 2.0f - 1.0f) / d, (float((child >> 1) & 1u) * 2.0f - 1.0f) / d,
-                       (float(child & 1u) * 2.0f - 1.0f) / d);
-}
-
-__device__ inline bool is_leaf(uint32_t w) { return (w >> 4) >= kVoxelOff; }
+__device__ inline bool is_leaf(uint32_t w) { return svo_rules::word_is_leaf(w); }
 
 __device__ inline uint32_t lower_bound(const uint32_t *a, uint32_t n, uint32_t v) {
     uint32_t lo = 0, hi = n;
@@ -96,17 +94,14 @@ __device__ inline uint32_t find_chunk(const Chunk *tab, uint32_t n, uint32_t id)
 
 __device__ inline void report(uint32_t *slot, uint32_t rank, uint32_t code) { atomicMin(slot, rank << 8 | code); }
 
-// Octree::find_voxel from the root with the `>=` rule, until stop(index, word): the stopping depth (0: the walk left
+// Octree::find_voxel from the root (svo_rules::descend), until stop(index, word): the stopping depth (0: the walk left
 // [0, len) or went deeper than 31 levels) and index.
 template <class Stop>
-__device__ inline uint32_t tree_walk(const uint32_t *nodes, uint32_t len, float3 p, Stop stop, uint32_t &at) {
+__device__ inline uint32_t tree_walk(const uint32_t *nodes, uint32_t len, Vec3 p, Stop stop, uint32_t &at) {
     uint32_t base = 0;
-    float cx = 0.0f, cy = 0.0f, cz = 0.0f;
+    Vec3 c;
     for (uint32_t depth = 1; depth <= kMaxTreeDepth; depth++) {
-        const uint32_t child = (p.x >= cx ? 4u : 0u) | (p.y >= cy ? 2u : 0u) | (p.z >= cz ? 1u : 0u);
-        const float3 o = pos_offset(child, depth);
-        cx += o.x; cy += o.y; cz += o.z;
-        at = base + child;
+        at = base + svo_rules::descend(p, c, depth);
         if (at >= len) return 0;
         const uint32_t w = nodes[at];
         if (stop(at, w)) return depth;
@@ -115,36 +110,35 @@ __device__ inline uint32_t tree_walk(const uint32_t *nodes, uint32_t len, float3
     return 0;
 }
 
-// World::find_voxel (svo_host.cpp world_locate) over the mirror, to max_depth: the mirror index of the node it ends on
-// (and its chunk's table slot), or kNone when it leaves the loaded chunks.  resident(slot) says whether an entered chunk counts as loaded.
+// The mirror as svo_rules::world_walk sees it: a chunk's handle is its table slot and the entry there, loaded once when
+// the walk enters the chunk; is_resident(slot) says whether an entered chunk counts as loaded.
 template <class Resident>
-__device__ inline uint32_t world_walk(const Chunk *tab, uint32_t n_tab, const uint2 *wn, float3 p, uint32_t max_depth,
-                                      Resident resident, uint32_t &code, uint32_t &slot) {
-    slot = find_chunk(tab, n_tab, 0u);
-    uint32_t base = 0;
-    float cx = 0.0f, cy = 0.0f, cz = 0.0f;
-    code = kErrWorld;
-    for (uint32_t depth = 1;; depth++) {
-        if (slot == kNone || !resident(slot)) return kNone;
-        const uint32_t child = (p.x >= cx ? 4u : 0u) | (p.y >= cy ? 2u : 0u) | (p.z >= cz ? 1u : 0u);
-        const float3 o = pos_offset(child, depth);
-        cx += o.x; cy += o.y; cz += o.z;
-        const Chunk c = tab[slot];
-        if (base + child >= c.count) return kNone;
-        const uint32_t at = c.first + base + child;
-        const uint32_t ptr = wn[at].x;
-        if (ptr == kChunkOff || depth == max_depth) {
-            code = kDone;
-            return at;
-        }
-        if (ptr > kChunkOff) {
-            slot = find_chunk(tab, n_tab, ptr - kChunkOff);
-            base = 0;
-        } else {
-            base = ptr;
-        }
-        if (depth >= 64) return kNone;  // cyclic chunk references
+struct MirrorChunks {
+    struct In {
+        uint32_t slot;
+        Chunk c;
+    };
+    const Chunk *tab;
+    uint32_t n_tab;
+    const uint2 *wn;
+    Resident is_resident;
+    __device__ In find(uint32_t id) const {
+        const uint32_t slot = find_chunk(tab, n_tab, id);
+        return {slot, slot != kNone ? tab[slot] : Chunk{}};
     }
+    __device__ bool resident(const In &in) const { return in.slot != kNone && is_resident(in.slot); }
+    __device__ uint32_t count(const In &in) const { return in.c.count; }
+    __device__ uint32_t pointer(const In &in, uint32_t i) const { return wn[in.c.first + i].x; }
+};
+
+// World::find_voxel over the mirror, to max_depth: the mirror index of the node it ends on (and its chunk's table slot),
+// or kNone when it leaves the loaded chunks (kErrWorld).
+template <class Resident>
+__device__ inline uint32_t world_walk(const Chunk *tab, uint32_t n_tab, const uint2 *wn, Vec3 p, uint32_t max_depth,
+                                      Resident resident, uint32_t &slot) {
+    const auto at = svo_rules::world_walk(MirrorChunks<Resident>{tab, n_tab, wn, resident}, p, max_depth);
+    slot = at.in.slot;
+    return at.ok ? at.in.c.first + at.index : kNone;
 }
 
 struct Tree {
@@ -153,8 +147,8 @@ struct Tree {
     uint32_t len;
 };
 
-__device__ inline float3 load_pos(const float *pos, uint32_t i) {
-    return make_float3(pos[3 * size_t(i)], pos[3 * size_t(i) + 1], pos[3 * size_t(i) + 2]);
+__device__ inline Vec3 load_pos(const float *pos, uint32_t i) {
+    return {pos[3 * size_t(i)], pos[3 * size_t(i) + 1], pos[3 * size_t(i) + 2]};
 }
 
 // ---- subdivide ----
@@ -170,7 +164,7 @@ __global__ __launch_bounds__(kThreads) void sub_plan_kernel(Tree t, const uint32
     if (node >= t.len) return report(&st->refuse, k, kErrRange);
     if (k > 0 && list[k - 1] == node) return report(&st->refuse, k, kErrDup);
     if (!is_leaf(t.nodes[node])) return;  // "Doubleup!" (adaptive.rs:32-35)
-    const float3 p = load_pos(t.pos, node);
+    const Vec3 p = load_pos(t.pos, node);
     uint32_t at = 0;
     const uint32_t vd = tree_walk(t.nodes, t.len, p, [](uint32_t, uint32_t w) { return is_leaf(w); }, at);
     if (!vd) return report(&st->err, k, kErrWalk);
@@ -180,16 +174,16 @@ __global__ __launch_bounds__(kThreads) void sub_plan_kernel(Tree t, const uint32
     }
     // a chunk loaded in this pass is resident for the entries after the one that loaded it
     auto resident = [&](uint32_t s) { const uint32_t r = tab[s].rank; return r == kNone || (r != kFailed && r < k); };
-    uint32_t code, slot;
-    const uint32_t wi = world_walk(tab, n_tab, wn, p, vd, resident, code, slot);
-    if (wi == kNone) return report(&st->err, k, code);
+    uint32_t slot;
+    const uint32_t wi = world_walk(tab, n_tab, wn, p, vd, resident, slot);
+    if (wi == kNone) return report(&st->err, k, kErrWorld);
     const uint32_t ptr = wn[wi].x;
     uint32_t first;
-    if (ptr < kChunkOff) {  // adaptive.rs:42-48
+    if (svo_rules::ptr_is_group(ptr)) {  // adaptive.rs:42-48
         if (ptr + 8u > tab[slot].count) return report(&st->err, k, kErrPast);
         first = tab[slot].first + ptr;
-    } else if (ptr > kChunkOff) {  // :49-58
-        const uint32_t id = ptr - kChunkOff, s = find_chunk(tab, n_tab, id);
+    } else if (svo_rules::ptr_is_chunk(ptr)) {  // :49-58
+        const uint32_t id = svo_rules::ptr_chunk_id(ptr), s = find_chunk(tab, n_tab, id);
         if (s == kNone) {  // not loaded: the lowest-ranked such entry loads it (the host takes the minimum) and is skipped
             const uint32_t q = atomicAdd(&st->n_req, 1u);
             req[2 * q] = id;
@@ -231,11 +225,11 @@ __global__ __launch_bounds__(kThreads) void sub_apply_kernel(Tree t, const uint3
     const uint32_t g = s < n_holes ? holes[n_holes - 1 - s] : t.len + 8u * (s - n_holes);
     if (g >= capacity || capacity - g < 8u) return report(&st->err, k, kErrRange);
     const uint32_t node = list[k], depth = (res[k] >> 8) + 1u, first = src[k];
-    const float3 p = load_pos(t.pos, node);
+    const Vec3 p = load_pos(t.pos, node);
     t.nodes[node] = g << 4;
     for (uint32_t i = 0; i < 8; i++) {
-        const float3 o = pos_offset(i, depth);
-        t.nodes[g + i] = (kVoxelOff + wn[first + i].y) << 4;
+        const Vec3 o = pos_offset(i, depth);
+        t.nodes[g + i] = leaf_word(wn[first + i].y);
         float *q = t.pos + 3 * size_t(g + i);
         q[0] = p.x + o.x;
         q[1] = p.y + o.y;
@@ -264,7 +258,7 @@ __global__ __launch_bounds__(kThreads) void unsub_plan_kernel(Tree t, const uint
     const uint32_t w = t.nodes[node];
     const bool first_of_run = k == 0 || list[k - 1] != node;  // a repeat sees the leaf its first occurrence left
     const bool collapse = !is_leaf(w) && first_of_run;
-    const float3 p = load_pos(t.pos, node);
+    const Vec3 p = load_pos(t.pos, node);
     if (collapse && p.x == 0.0f && p.y == 0.0f && p.z == 0.0f) return report(&st->err, k, kErrNoPos);
     // the host walks the tree after entries 0..k: a node on the path is a leaf if it was one after the subdivide pass or
     // is an interior entry of rank <= k (collapsed by then)
@@ -276,19 +270,19 @@ __global__ __launch_bounds__(kThreads) void unsub_plan_kernel(Tree t, const uint
     uint32_t at = 0;
     const uint32_t vd = tree_walk(t.nodes, t.len, p, stop, at);
     if (!vd) return report(&st->err, k, kErrWalk);
-    uint32_t code, slot;
-    const uint32_t wi = world_walk(tab, n_tab, wn, p, vd, [](uint32_t) { return true; }, code, slot);
-    if (wi == kNone) return report(&st->err, k, code);
+    uint32_t slot;
+    const uint32_t wi = world_walk(tab, n_tab, wn, p, vd, [](uint32_t) { return true; }, slot);
+    if (wi == kNone) return report(&st->err, k, kErrWorld);
     const uint2 wnode = wn[wi];
-    if (wnode.x > kChunkOff && wnode.x - kChunkOff >= kChunkOff / 2u) {  // adaptive.rs:104-110: streamed chunks are dropped
-        const uint32_t s = find_chunk(tab, n_tab, wnode.x - kChunkOff);
+    if (svo_rules::ptr_is_chunk(wnode.x) && svo_rules::chunk_is_streamed(svo_rules::ptr_chunk_id(wnode.x))) {  // adaptive.rs:104-110
+        const uint32_t s = find_chunk(tab, n_tab, svo_rules::ptr_chunk_id(wnode.x));
         if (s != kNone) {
             atomicMin(&rm[s], k);
             st->removals = 1;
         }
     }
     res[k] = (collapse ? kDone : kSkip) | vd << 8;
-    val[k] = (kVoxelOff + wnode.y) << 4;
+    val[k] = leaf_word(wnode.y);
     grp[k] = w >> 4;
     flag[k] = collapse ? 1u : 0u;
 }
@@ -299,10 +293,10 @@ __global__ __launch_bounds__(kThreads) void unsub_check_kernel(Tree t, const uin
                                                                const uint32_t *rm, Status *st) {
     const uint32_t k = blockIdx.x * kThreads + threadIdx.x;
     if (k >= n) return;
-    const float3 p = load_pos(t.pos, list[k]);
-    uint32_t code, slot;
-    const uint32_t wi = world_walk(tab, n_tab, wn, p, res[k] >> 8, [&](uint32_t s) { return rm[s] >= k; }, code, slot);
-    if (wi == kNone) report(&st->err, k, code);
+    const Vec3 p = load_pos(t.pos, list[k]);
+    uint32_t slot;
+    const uint32_t wi = world_walk(tab, n_tab, wn, p, res[k] >> 8, [&](uint32_t s) { return rm[s] >= k; }, slot);
+    if (wi == kNone) report(&st->err, k, kErrWorld);
 }
 
 __global__ __launch_bounds__(kThreads) void unsub_apply_kernel(Tree t, const uint32_t *list, uint32_t n, const uint32_t *res,
@@ -318,83 +312,78 @@ __global__ __launch_bounds__(kThreads) void unsub_apply_kernel(Tree t, const uin
 // A frontier entry is node index | depth << 27: an index is below 2^27 (SVO_VOXEL_OFFSET), a depth at most 31.
 constexpr uint32_t kDepthShift = 27, kIndexMask = (1u << kDepthShift) - 1u;
 
-// The initial frontier: every leaf of [0, len) with the depth of the walk to its position, in index order.  Tiles of
-// kTile words, kPer consecutive words per lane; the count kernel only tests the words, the emit kernel walks.
-__global__ __launch_bounds__(kThreads) void frontier_count_kernel(const uint32_t *nodes, uint32_t len, uint32_t *tile_sum) {
+// A stable compaction of the words in[0, n), in tiles of kTile with kPer consecutive words per lane: the count kernel sums
+// keep(word) per tile, tile_offsets_kernel scans the sums, and the emit kernel calls emit(i, word, rank) for every kept
+// word, which it holds in registers from the test on.
+template <class Keep>
+__global__ __launch_bounds__(kThreads) void compact_count_kernel(const uint32_t *in, uint32_t n, Keep keep, uint32_t *tile_sum) {
     const uint32_t i0 = blockIdx.x * kTile + threadIdx.x * kPer;
     uint32_t c = 0;
     for (uint32_t j = 0; j < kPer; j++)
-        if (i0 + j < len && is_leaf(nodes[i0 + j])) c++;
+        if (i0 + j < n && keep(in[i0 + j])) c++;
     uint32_t total;
     block_exclusive_scan<kThreads>(c, &total);
     if (threadIdx.x == 0) tile_sum[blockIdx.x] = total;
 }
 
-__global__ __launch_bounds__(kThreads) void frontier_emit_kernel(Tree t, const uint32_t *tile_off, uint32_t *out, uint32_t out_cap,
-                                                                 Status *st) {
+template <class Keep, class Emit>
+__global__ __launch_bounds__(kThreads) void compact_emit_kernel(const uint32_t *in, uint32_t n, Keep keep, Emit emit,
+                                                                const uint32_t *tile_off) {
     const uint32_t i0 = blockIdx.x * kTile + threadIdx.x * kPer;
-    uint32_t leaf = 0;
-    for (uint32_t j = 0; j < kPer; j++)
-        if (i0 + j < t.len && is_leaf(t.nodes[i0 + j])) leaf |= 1u << j;
-    uint32_t r = block_exclusive_scan<kThreads>(__popc(leaf), nullptr) + tile_off[blockIdx.x];
+    uint32_t w[kPer], kept = 0;
     for (uint32_t j = 0; j < kPer; j++) {
-        if (!((leaf >> j) & 1u)) continue;
-        const uint32_t i = i0 + j;
+        w[j] = i0 + j < n ? in[i0 + j] : 0u;
+        if (i0 + j < n && keep(w[j])) kept |= 1u << j;
+    }
+    uint32_t r = block_exclusive_scan<kThreads>(__popc(kept), nullptr) + tile_off[blockIdx.x];
+    for (uint32_t j = 0; j < kPer; j++)
+        if ((kept >> j) & 1u) emit(i0 + j, w[j], r++);
+}
+
+// The initial frontier: every leaf of [0, len) with the depth of the walk to its position, in index order.  The count
+// only tests the words, the emit walks.
+struct LeafWord {
+    __device__ bool operator()(uint32_t w) const { return is_leaf(w); }
+};
+
+struct EmitLeaf {
+    Tree t;
+    uint32_t *out, out_cap;
+    Status *st;
+    __device__ void operator()(uint32_t i, uint32_t, uint32_t r) const {
         uint32_t at = 0;
         const uint32_t d = tree_walk(t.nodes, t.len, load_pos(t.pos, i), [](uint32_t, uint32_t w) { return is_leaf(w); }, at);
         if (!d) report(&st->err, min(i, kMaxRank - 1u), kErrWalk);
         if (r < out_cap) out[r] = i | d << kDepthShift;  // (always: the counts come from the same words)
-        r++;
     }
-}
+};
 
-// svo_world_expand's rule for one frontier leaf (svo_host.cpp), operation by operation: deeper than max_depth never;
-// with a camera, only while 2^d * distance(camera, the leaf's cube) < lod_c (a NaN does not refine).
+// svo_world_expand's rule for one frontier leaf: deeper than max_depth never; with a camera, only while
+// svo_rules::lod_refines says so for the leaf's cube, centre +- half edge.
 struct View {
     float cam[3], lod_c;
     uint32_t max_depth, use_cam;
 };
 
-__device__ inline bool view_refines(const float *pos, uint32_t entry, const View &v) {
-    const uint32_t d = entry >> kDepthShift;
-    if (d >= v.max_depth) return false;
-    if (!v.use_cam) return true;
-    const float3 c = load_pos(pos, entry & kIndexMask);
-    const float h = 1.0f / float(1u << d);  // half edge of a depth-d cube
-    const float cc[3] = {c.x, c.y, c.z};
-    float d2 = 0.0f;
-    for (int k = 0; k < 3; k++) {
-        const float lo = cc[k] - h, hi = cc[k] + h;
-        const float dist = v.cam[k] < lo ? lo - v.cam[k] : (v.cam[k] > hi ? v.cam[k] - hi : 0.0f);
-        d2 += dist * dist;
+struct ViewRefines {
+    const float *pos;
+    View v;
+    __device__ bool operator()(uint32_t entry) const {
+        const uint32_t d = entry >> kDepthShift;
+        if (d >= v.max_depth) return false;
+        if (!v.use_cam) return true;
+        const Vec3 c = load_pos(pos, entry & kIndexMask);
+        const float h = 1.0f / float(1u << d);  // half edge of a depth-d cube
+        const float lo[3] = {c.x - h, c.y - h, c.z - h}, hi[3] = {c.x + h, c.y + h, c.z + h};
+        return svo_rules::lod_refines(v.cam, lo, hi, d, v.lod_c);
     }
-    return float(1u << d) * __fsqrt_rn(d2) < v.lod_c;
-}
+};
 
-__global__ __launch_bounds__(kThreads) void cand_count_kernel(const uint32_t *frontier, uint32_t n, const float *pos, View v,
-                                                              uint32_t *tile_sum) {
-    const uint32_t i0 = blockIdx.x * kTile + threadIdx.x * kPer;
-    uint32_t c = 0;
-    for (uint32_t j = 0; j < kPer; j++)
-        if (i0 + j < n && view_refines(pos, frontier[i0 + j], v)) c++;
-    uint32_t total;
-    block_exclusive_scan<kThreads>(c, &total);
-    if (threadIdx.x == 0) tile_sum[blockIdx.x] = total;
-}
-
-// the passing node indices, in frontier order, into list[0, total)
-__global__ __launch_bounds__(kThreads) void cand_emit_kernel(const uint32_t *frontier, uint32_t n, const float *pos, View v,
-                                                             const uint32_t *tile_off, uint32_t *list) {
-    const uint32_t i0 = blockIdx.x * kTile + threadIdx.x * kPer;
-    uint32_t e[kPer], pass = 0;
-    for (uint32_t j = 0; j < kPer; j++) {
-        e[j] = i0 + j < n ? frontier[i0 + j] : 0u;
-        if (i0 + j < n && view_refines(pos, e[j], v)) pass |= 1u << j;
-    }
-    uint32_t r = block_exclusive_scan<kThreads>(__popc(pass), nullptr) + tile_off[blockIdx.x];
-    for (uint32_t j = 0; j < kPer; j++)
-        if ((pass >> j) & 1u) list[r++] = e[j] & kIndexMask;  // (r < n: at most one index per frontier entry)
-}
+// the passing node indices, in frontier order, into list[0, total) (rank < n: at most one index per frontier entry)
+struct EmitCandidate {
+    uint32_t *list;
+    __device__ void operator()(uint32_t, uint32_t entry, uint32_t r) const { list[r] = entry & kIndexMask; }
+};
 
 // Success s (< limit) of the pass made the group at len_before + 8 s out of a leaf of depth d: its 8 slots, depth d + 1,
 // are entries [8 s, 8 s + 8) of the next frontier.  rank is the pass's scanned flag array.
@@ -462,6 +451,10 @@ struct svo_adapt_state {
 
 namespace {
 
+// the table is sorted by id, and an id is in it once
+bool by_id(const Chunk &x, const Chunk &y) { return x.id < y.id; }
+void table_insert(std::vector<Chunk> &tab, const Chunk &c) { tab.insert(std::upper_bound(tab.begin(), tab.end(), c, by_id), c); }
+
 // the table (and the rank array sized to it) to the device; blocking, so the host vector may change afterwards
 int upload_table(svo_ctx *ctx) {
     svo_adapt_state *a = ctx->adapt.get();
@@ -515,7 +508,7 @@ int rebuild_mirror(svo_ctx *ctx, size_t extra) {
     }
     for (const Chunk &c : old)
         if (c.rank == kFailed) a->tab.push_back(c);
-    std::sort(a->tab.begin(), a->tab.end(), [](const Chunk &x, const Chunk &y) { return x.id < y.id; });
+    std::sort(a->tab.begin(), a->tab.end(), by_id);
     return upload_table(ctx);
 }
 
@@ -525,14 +518,13 @@ int mirror_add(svo_ctx *ctx, uint32_t id, uint32_t rank) {
     const svo_cpu_octree *t = svo_world_chunk(a->world, id);
     const size_t cnt = svo_cpu_octree_len(t);
     if (a->wn_used + cnt > a->wn_cap) {
-        a->tab.push_back({id, 0, 0, rank});  // (the rebuild reads its nodes from the world and keeps the rank)
+        table_insert(a->tab, {id, 0, 0, rank});  // (the rebuild reads its nodes from the world and keeps the rank)
         return rebuild_mirror(ctx, 0);
     }
     int rc = put_chunk_nodes(ctx, t, (uint32_t)a->wn_used, cnt);
     if (rc) return rc;
-    a->tab.push_back({id, (uint32_t)a->wn_used, (uint32_t)cnt, rank});
+    table_insert(a->tab, {id, (uint32_t)a->wn_used, (uint32_t)cnt, rank});
     a->wn_used += cnt;
-    std::sort(a->tab.begin(), a->tab.end(), [](const Chunk &x, const Chunk &y) { return x.id < y.id; });
     return SVO_OK;
 }
 
@@ -573,6 +565,11 @@ int clear_status(svo_ctx *ctx) {
 
 Tree tree_of(svo_ctx *ctx) { return Tree{ctx->nodes, ctx->adapt->pos, ctx->adapt->len}; }
 
+// what a buffer of `have` items grows to for `want`: at least twice its size, so a run of growing levels reallocates rarely
+size_t grown(size_t have, size_t want) { return have >= want ? have : std::max(want, 2 * have); }
+// ... and the hole stack: twice what it needs, so the passes that follow push without growing it again
+size_t grown_stack(size_t have, size_t want) { return have >= want ? have : 2 * want; }
+
 // ---- the subdivide pass over the sorted list a->list[0][0, n) ----
 // Only the first `limit` successes in list order are applied (svo_adaptive_expand's word cap; kNone: all of them).
 int subdivide_pass(svo_ctx *ctx, uint32_t n, uint32_t limit, svo_adaptive_result *out) {
@@ -606,8 +603,7 @@ int subdivide_pass(svo_ctx *ctx, uint32_t n, uint32_t limit, svo_adaptive_result
                 out->chunks_loaded++;
                 if ((rc = mirror_add(ctx, id, rank))) return rc;
             } else {
-                a->tab.push_back({id, 0, 0, kFailed});
-                std::sort(a->tab.begin(), a->tab.end(), [](const Chunk &x, const Chunk &y) { return x.id < y.id; });
+                table_insert(a->tab, {id, 0, 0, kFailed});
             }
         }
         if ((rc = upload_table(ctx))) return rc;
@@ -667,17 +663,8 @@ int unsubdivide_pass(svo_ctx *ctx, uint32_t n, svo_adaptive_result *out) {
     if ((rc = read_status(ctx, a->flag + n))) return rc;
     if (a->st_host->err != kNone) return entry_fail(ctx, SVO_ERR_STATE, a->st_host->err, "unsubdivide");
     const uint32_t done = a->st_host->total;
-    if (size_t(a->n_holes) + done > a->hole_cap) {  // grow the hole stack, keeping its entries
-        uint32_t *bigger = nullptr;
-        const size_t cap = 2 * (size_t(a->n_holes) + done);
-        HIP_TRY(ctx, hipMalloc((void **)&bigger, cap * sizeof(uint32_t)));
-        if (a->n_holes)
-            HIP_TRY(ctx, hipMemcpyAsync(bigger, a->holes, a->n_holes * sizeof(uint32_t), hipMemcpyDeviceToDevice, ctx->stream));
-        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        (void)hipFree(a->holes);
-        a->holes = bigger;
-        a->hole_cap = cap;
-    }
+    const size_t hole_room = grown_stack(a->hole_cap, size_t(a->n_holes) + done);
+    if ((rc = svo_grow_keep(ctx, &a->hole_cap, hole_room, &a->holes, a->n_holes))) return rc;
     unsub_apply_kernel<<<grid, kThreads, 0, ctx->stream>>>(tree_of(ctx), list, n, a->res, a->val, a->src, a->flag, a->holes,
                                                            a->n_holes, (uint32_t)a->hole_cap);
     HIP_TRY(ctx, hipGetLastError());
@@ -712,8 +699,26 @@ bool forget_load_ranks(svo_adapt_state *a) {
     return changed;
 }
 
-// what a buffer of `have` items grows to for `want`: at least twice its size, so a run of growing levels reallocates rarely
-size_t grown(size_t have, size_t want) { return have >= want ? have : std::max(want, 2 * have); }
+// One stage of svo_adaptive_expand: the compaction of in[0, n) (its total into st->total), between the events ev[0] and
+// ev[1]; the status comes back, which waits for both, and their distance is added to expand_ms[stage].
+template <class Keep, class Emit>
+int timed_compaction(svo_ctx *ctx, int stage, const uint32_t *in, uint32_t n, Keep keep, Emit emit) {
+    svo_adapt_state *a = ctx->adapt.get();
+    const uint32_t nt = svo_div_up(n, kTile);
+    int rc = svo_grow(ctx, &a->tile_items, nt + 1, &a->tiles);
+    if (rc || (rc = clear_status(ctx))) return rc;
+    HIP_TRY(ctx, hipEventRecord(a->ev[0], ctx->stream));
+    compact_count_kernel<<<nt, kThreads, 0, ctx->stream>>>(in, n, keep, a->tiles);
+    tile_offsets_kernel<<<1, kTopThreads, 0, ctx->stream>>>(a->tiles, nt, nullptr, 0, &a->st->total);
+    compact_emit_kernel<<<nt, kThreads, 0, ctx->stream>>>(in, n, keep, emit, a->tiles);
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, hipEventRecord(a->ev[1], ctx->stream));
+    if ((rc = read_status(ctx, nullptr))) return rc;
+    float ms = 0.0f;
+    HIP_TRY(ctx, hipEventElapsedTime(&ms, a->ev[0], a->ev[1]));
+    a->expand_ms[stage] += ms;
+    return SVO_OK;
+}
 
 int check_attached(svo_ctx *ctx) {
     if (!ctx->adapt || !ctx->adapt->world) return svo_fail(ctx, SVO_ERR_STATE, "svo_adaptive_attach not called");
@@ -846,21 +851,10 @@ int svo_adaptive_expand(svo_ctx *ctx, uint32_t max_depth, const float cam[3], fl
     // the initial frontier: the leaves of [0, len) (at most len of them)
     uint32_t cur = 0, n_front = 0;
     if (a->len) {
-        const uint32_t nt = svo_div_up(a->len, kTile);
         if ((rc = svo_grow(ctx, &a->frontier_items[0], a->len, &a->frontier[0]))) return rc;
-        if ((rc = svo_grow(ctx, &a->tile_items, nt + 1, &a->tiles))) return rc;
-        if ((rc = clear_status(ctx))) return rc;
-        HIP_TRY(ctx, hipEventRecord(a->ev[0], ctx->stream));
-        frontier_count_kernel<<<nt, kThreads, 0, ctx->stream>>>(ctx->nodes, a->len, a->tiles);
-        tile_offsets_kernel<<<1, kTopThreads, 0, ctx->stream>>>(a->tiles, nt, nullptr, 0, &a->st->total);
-        frontier_emit_kernel<<<nt, kThreads, 0, ctx->stream>>>(tree_of(ctx), a->tiles, a->frontier[0], a->len, a->st);
-        HIP_TRY(ctx, hipGetLastError());
-        HIP_TRY(ctx, hipEventRecord(a->ev[1], ctx->stream));
-        if ((rc = read_status(ctx, nullptr))) return rc;
+        if ((rc = timed_compaction(ctx, 0, ctx->nodes, a->len, LeafWord{}, EmitLeaf{tree_of(ctx), a->frontier[0], a->len, a->st}))) return rc;
         if (a->st_host->err != kNone) return entry_fail(ctx, SVO_ERR_STATE, a->st_host->err, "expand: leaf");
         n_front = a->st_host->total;
-        HIP_TRY(ctx, hipEventElapsedTime(&ms, a->ev[0], a->ev[1]));
-        a->expand_ms[0] = ms;
     }
 
     // level by level; a level of 2^24 entries or more goes through the pass in consecutive slices (its rank packing)
@@ -874,7 +868,7 @@ int svo_adaptive_expand(svo_ctx *ctx, uint32_t max_depth, const float cam[3], fl
         if ((rc = svo_grow(ctx, &a->frontier_items[nxt], grown(a->frontier_items[nxt], next_max), &a->frontier[nxt]))) return rc;
         uint32_t n_next = 0;
         for (uint32_t lo = 0; lo < n_front && !full; lo += kMaxRank - 1u) {
-            const uint32_t n = std::min(n_front - lo, kMaxRank - 1u), nt = svo_div_up(n, kTile);
+            const uint32_t n = std::min(n_front - lo, kMaxRank - 1u);
             const uint32_t limit = (uint32_t)((cap > a->len ? cap - a->len : 0) / 8u);
             if (!limit) {
                 full = true;
@@ -884,18 +878,9 @@ int svo_adaptive_expand(svo_ctx *ctx, uint32_t max_depth, const float cam[3], fl
                                &a->flag)))
                 return rc;
             if ((rc = svo_grow(ctx, &a->req_items, 2 * a->items, &a->req))) return rc;
-            if ((rc = svo_grow(ctx, &a->tile_items, nt + 1, &a->tiles))) return rc;
-            if ((rc = clear_status(ctx))) return rc;
-            HIP_TRY(ctx, hipEventRecord(a->ev[0], ctx->stream));
-            cand_count_kernel<<<nt, kThreads, 0, ctx->stream>>>(a->frontier[cur] + lo, n, a->pos, view, a->tiles);
-            tile_offsets_kernel<<<1, kTopThreads, 0, ctx->stream>>>(a->tiles, nt, nullptr, 0, &a->st->total);
-            cand_emit_kernel<<<nt, kThreads, 0, ctx->stream>>>(a->frontier[cur] + lo, n, a->pos, view, a->tiles, a->list[0]);
-            HIP_TRY(ctx, hipGetLastError());
-            HIP_TRY(ctx, hipEventRecord(a->ev[1], ctx->stream));
-            if ((rc = read_status(ctx, nullptr))) return rc;
+            const uint32_t *front = a->frontier[cur] + lo;
+            if ((rc = timed_compaction(ctx, 1, front, n, ViewRefines{a->pos, view}, EmitCandidate{a->list[0]}))) return rc;
             const uint32_t n_cand = a->st_host->total;
-            HIP_TRY(ctx, hipEventElapsedTime(&ms, a->ev[0], a->ev[1]));
-            a->expand_ms[1] += ms;
             if (!n_cand) continue;
             const uint32_t len_before = a->len;
             svo_adaptive_result pass{};

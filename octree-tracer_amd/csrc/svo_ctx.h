@@ -1,7 +1,8 @@
 // svo_ctx.h -- the device context behind the opaque `svo_ctx` of include/svo_hip.h, and the host helpers of the files that
 // use it: svo_abi.cpp (trace / scan dispatch), svo_comm.cpp (RCCL frame gather) and the GPU tree passes (svo_proc.hip,
-// svo_build.hip, svo_adapt.hip).  Shared by the passes: svo_grow / svo_grow_pinned (workspaces), the builder's sort and scan,
-// svo_world_writer (a generated world's directory); svo_scan.h, svo_mip.h and svo_morton.h hold the device pieces.
+// svo_build.hip, svo_adapt.hip).  Shared by the passes: svo_grow / svo_grow_pinned / svo_grow_keep (workspaces), the builder's sort
+// and scan, svo_world_writer (a generated world's directory); svo_scan.h, svo_mip.h and svo_morton.h hold the device pieces,
+// svo_rules.h the walks and rules that svo_host.cpp and svo_adapt.hip both run.
 // Internal: not part of the boundary.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -162,6 +163,21 @@ template <typename... T>
 int svo_grow(svo_ctx *ctx, size_t *have, size_t want, T **...bufs) { return svo_grow_group(ctx, false, have, want, bufs...); }
 template <typename... T>
 int svo_grow_pinned(svo_ctx *ctx, size_t *have, size_t want, T **...bufs) { return svo_grow_group(ctx, true, have, want, bufs...); }
+
+// svo_grow for one device buffer whose first `keep` items stay: they are copied on the context's stream, which is waited
+// for before the old buffer is freed
+template <typename T>
+int svo_grow_keep(svo_ctx *ctx, size_t *have, size_t want, T **buf, size_t keep) {
+    if (*have >= want) return SVO_OK;
+    T *bigger = nullptr;
+    HIP_TRY(ctx, hipMalloc((void **)&bigger, want * sizeof(T)));
+    if (keep) HIP_TRY(ctx, hipMemcpyAsync(bigger, *buf, keep * sizeof(T), hipMemcpyDeviceToDevice, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    (void)hipFree(*buf);
+    *buf = bigger;
+    *have = want;
+    return SVO_OK;
+}
 
 // a write to the bound node store: enqueue it behind the store's last write (any context's), then record it, which makes
 // every context bound to the store rebuild its top table and schedule

@@ -13,8 +13,15 @@
 
 #include "svo_hip.h"
 #include "svo_host.h"
+#include "svo_rules.h"
 
 namespace {
+
+using svo_rules::descend;
+using svo_rules::leaf_word;
+using svo_rules::pos_offset;
+using svo_rules::Vec3;
+using svo_rules::word_is_leaf;
 
 constexpr uint32_t kVoxelOffset = SVO_VOXEL_OFFSET;
 constexpr uint32_t kChunkOffset = SVO_CHUNK_OFFSET;
@@ -23,19 +30,8 @@ struct Rgb {
     uint8_t r = 0, g = 0, b = 0;
     bool is_zero() const { return !(r | g | b); }
     uint32_t cpu_value() const { return (uint32_t(r) << 16) | (uint32_t(g) << 8) | b; }  // octree.rs:32-34
-    uint32_t gpu_word() const { return (kVoxelOffset + cpu_value()) << 4; }              // octree.rs:28-30
+    uint32_t gpu_word() const { return leaf_word(cpu_value()); }                         // octree.rs:28-30
 };
-
-struct Vec3 {
-    float x = 0, y = 0, z = 0;
-};
-
-// Octree::pos_offset (octree.rs:154-161)
-Vec3 pos_offset(uint32_t child, uint32_t depth) {
-    const float d = float(1u << depth);
-    return {(float((child >> 2) & 1u) * 2.0f - 1.0f) / d, (float((child >> 1) & 1u) * 2.0f - 1.0f) / d,
-            (float(child & 1u) * 2.0f - 1.0f) / d};
-}
 
 struct Located {
     size_t index;
@@ -50,10 +46,7 @@ Located locate(Vec3 p, int64_t max_depth, IsLeaf is_leaf, Next next) {
     size_t base = 0;
     Vec3 c;
     for (uint32_t depth = 1;; ++depth) {
-        const uint32_t child = (p.x >= c.x ? 4u : 0u) | (p.y >= c.y ? 2u : 0u) | (p.z >= c.z ? 1u : 0u);
-        const Vec3 o = pos_offset(child, depth);
-        c.x += o.x; c.y += o.y; c.z += o.z;
-        const size_t at = base + child;
+        const size_t at = base + descend(p, c, depth);
         if (is_leaf(at) || (max_depth >= 0 && int64_t(depth) == max_depth)) return {at, depth, c};
         base = next(at);
     }
@@ -486,7 +479,7 @@ size_t svo_octree_positions(const svo_octree *o, float *out, size_t cap) {
 }
 
 int svo_octree_subdivide(svo_octree *o, size_t node, const uint8_t mask_rgb[24], uint32_t depth) {
-    if ((o->nodes[node] >> 4) < kVoxelOffset) return -1;  // "Node already subdivided!" octree.rs:73-75
+    if (!word_is_leaf(o->nodes[node])) return -1;  // "Node already subdivided!" octree.rs:73-75
     const Vec3 c = o->positions[node];
     size_t first;
     if (!o->hole_stack.empty()) {  // reuse a freed group, octree.rs:78-84
@@ -522,7 +515,7 @@ int svo_octree_unsubdivide(svo_octree *o, size_t node) {
 void svo_octree_find_voxel(const svo_octree *o, const float pos[3], int64_t max_depth, uint64_t *index,
                            uint32_t *depth, float node_pos[3]) {
     const Located l = locate(
-        Vec3{pos[0], pos[1], pos[2]}, max_depth, [&](size_t i) { return (o->nodes[i] >> 4) >= kVoxelOffset; },
+        Vec3{pos[0], pos[1], pos[2]}, max_depth, [&](size_t i) { return word_is_leaf(o->nodes[i]); },
         [&](size_t i) { return size_t(o->nodes[i] >> 4); });
     if (index) *index = l.index;
     if (depth) *depth = l.depth;
@@ -575,38 +568,19 @@ struct svo_world {
 
 namespace {
 
-struct WorldLocated {
-    uint32_t chunk;
-    size_t index;
-    uint32_t depth;
-    Vec3 pos;
-    bool ok;
+// the loaded chunks as svo_rules::world_walk sees them
+struct WorldChunks {
+    const svo_world &w;
+    const svo_cpu_octree *find(uint32_t id) const { return w.get(id); }
+    bool resident(const svo_cpu_octree *t) const { return t != nullptr; }
+    size_t count(const svo_cpu_octree *t) const { return t->nodes.size(); }
+    uint32_t pointer(const svo_cpu_octree *t, uint32_t i) const { return t->nodes[i].pointer; }
 };
+using WorldLocated = svo_rules::WorldAt<const svo_cpu_octree *>;
 
-// World::find_voxel (world.rs:201-232): the `>=` walk, hopping into the referenced chunk's root group at a
-// block leaf.  The reference unwraps a missing chunk (panic); here ok = false.
+// World::find_voxel; a negative max_depth is no limit (the walk itself ends after 64 levels)
 WorldLocated world_locate(const svo_world &w, Vec3 p, int64_t max_depth) {
-    uint32_t chunk = 0;
-    size_t base = 0;
-    Vec3 c;
-    const svo_cpu_octree *cur = w.get(0);
-    for (uint32_t depth = 1;; ++depth) {
-        if (!cur) return {chunk, 0, depth, c, false};
-        const uint32_t child = (p.x >= c.x ? 4u : 0u) | (p.y >= c.y ? 2u : 0u) | (p.z >= c.z ? 1u : 0u);
-        const Vec3 o = pos_offset(child, depth);
-        c.x += o.x; c.y += o.y; c.z += o.z;
-        if (base + child >= cur->nodes.size()) return {chunk, base + child, depth, c, false};
-        const uint32_t ptr = cur->nodes[base + child].pointer;
-        if (ptr == kChunkOffset || (max_depth >= 0 && int64_t(depth) == max_depth)) return {chunk, base + child, depth, c, true};
-        if (ptr > kChunkOffset) {
-            chunk = ptr - kChunkOffset;
-            cur = w.get(chunk);
-            base = 0;
-        } else {
-            base = ptr;
-        }
-        if (depth >= 64) return {chunk, base, depth, c, false};  // cyclic chunk references
-    }
+    return svo_rules::world_walk(WorldChunks{w}, p, max_depth > 0 && max_depth <= 64 ? uint32_t(max_depth) : 0u);
 }
 
 // <id>.bin (world.rs:176-184, cpu_octree.rs:262-272): the reference dumps its Vec<Node> as raw memory.  Node is
@@ -646,7 +620,7 @@ int world_fail(svo_world *w, const std::string &msg) {
 // returns 1 subdivided, 0 skipped, -1 error
 int subdivide_one(svo_world *w, svo_octree *o, size_t node_index, uint64_t *loaded) {
     if (node_index >= o->nodes.size()) return world_fail(w, "node index past the octree");
-    if ((o->nodes[node_index] >> 4) < kVoxelOffset) return 0;  // "Doubleup!" :32-35
+    if (!word_is_leaf(o->nodes[node_index])) return 0;  // "Doubleup!" :32-35
     const Vec3 pos = o->positions[node_index];
     uint32_t voxel_depth = 0;
     {
@@ -658,11 +632,11 @@ int subdivide_one(svo_world *w, svo_octree *o, size_t node_index, uint64_t *load
     const svo_cpu_octree *chunk = w->get(l.chunk);
     const uint32_t ptr = chunk->nodes[l.index].pointer;
     uint8_t mask[24];
-    if (ptr < kChunkOffset) {  // :42-48
+    if (svo_rules::ptr_is_group(ptr)) {  // :42-48
         if (size_t(ptr) + 8 > chunk->nodes.size()) return world_fail(w, "child pointer past the chunk");
         svo_cpu_octree_get_node_mask(chunk, ptr, mask);
-    } else if (ptr > kChunkOffset) {  // :49-58
-        const uint32_t id = ptr - kChunkOffset;
+    } else if (svo_rules::ptr_is_chunk(ptr)) {  // :49-58
+        const uint32_t id = svo_rules::ptr_chunk_id(ptr);
         const svo_cpu_octree *block = w->get(id);
         if (!block) {
             // the reference starts an asynchronous load and retries when the node is listed again
@@ -737,9 +711,10 @@ int svo_world_generate_mip_tree(svo_world *w, uint32_t id, uint8_t top_mip[3]) {
     for (auto &n : t->nodes) {
         // every node of the array is reachable in a tree built by the loaders, so one linear pass equals
         // the reference's walk over reachable block leaves
-        if (n.pointer > kChunkOffset) {
-            const svo_cpu_octree *b = w->get(n.pointer - kChunkOffset);
-            if (!b) return world_fail(w, "block " + std::to_string(n.pointer - kChunkOffset) + " is not loaded");
+        if (svo_rules::ptr_is_chunk(n.pointer)) {
+            const uint32_t id = svo_rules::ptr_chunk_id(n.pointer);
+            const svo_cpu_octree *b = w->get(id);
+            if (!b) return world_fail(w, "block " + std::to_string(id) + " is not loaded");
             n.value = b->top_mip;
         }
     }
@@ -825,9 +800,9 @@ int64_t svo_adaptive_unsubdivide(svo_world *w, svo_octree *o, const uint32_t *li
         const WorldLocated l = world_locate(*w, pos, voxel_depth);
         if (!l.ok) return world_fail(w, "world walk left the loaded chunks (chunk " + std::to_string(l.chunk) + ")");
         const auto node = w->get(l.chunk)->nodes[l.index];
-        if (node.pointer > kChunkOffset) {  // :104-110: streamed chunks are dropped, blocks stay
-            const uint32_t id = node.pointer - kChunkOffset;
-            if (id >= kChunkOffset / 2) svo_world_remove(w, id);
+        if (svo_rules::ptr_is_chunk(node.pointer)) {  // :104-110: streamed chunks are dropped, blocks stay
+            const uint32_t id = svo_rules::ptr_chunk_id(node.pointer);
+            if (svo_rules::chunk_is_streamed(id)) svo_world_remove(w, id);
         }
         o->nodes[node_index] = node.value.gpu_word();  // :117
         o->touch(node_index);
@@ -845,7 +820,7 @@ uint64_t svo_world_expand(svo_world *w, svo_octree *o, uint32_t max_depth, const
     struct Leaf { size_t index; uint32_t depth; };
     std::vector<Leaf> frontier, next;
     for (size_t i = 0; i < o->nodes.size(); i++) {
-        if ((o->nodes[i] >> 4) < kVoxelOffset) continue;
+        if (!word_is_leaf(o->nodes[i])) continue;
         const Vec3 pos = o->positions[i];
         const float p[3] = {pos.x, pos.y, pos.z};
         uint32_t d = 0;
@@ -861,15 +836,8 @@ uint64_t svo_world_expand(svo_world *w, svo_octree *o, uint32_t max_depth, const
             if (lod_c > 0.0f && cam) {
                 const Vec3 c = o->positions[lf.index];
                 const float h = 1.0f / float(1u << lf.depth);  // half edge of a depth-d cube
-                float d2 = 0.0f;
-                const float cc[3] = {c.x, c.y, c.z};
-                for (int k = 0; k < 3; k++) {
-                    const float lo = cc[k] - h, hi = cc[k] + h;
-                    const float d = cam[k] < lo ? lo - cam[k] : (cam[k] > hi ? cam[k] - hi : 0.0f);
-                    d2 += d * d;
-                }
-                const float r = std::sqrt(d2);
-                if (!(float(1u << lf.depth) * r < lod_c)) continue;
+                const float lo[3] = {c.x - h, c.y - h, c.z - h}, hi[3] = {c.x + h, c.y + h, c.z + h};
+                if (!svo_rules::lod_refines(cam, lo, hi, lf.depth, lod_c)) continue;
             }
             const size_t before_holes = o->hole_stack.size();
             const size_t before = o->nodes.size();
@@ -956,28 +924,22 @@ struct Builder {
 
 uint32_t leaf_colour(uint32_t h) {
     const uint32_t r = 1 + (h & 0xFF) % 255, g = 1 + ((h >> 8) & 0xFF) % 255, b = 1 + ((h >> 16) & 0xFF) % 255;
-    return (kVoxelOffset + ((r << 16) | (g << 8) | b)) << 4;
+    return leaf_word((r << 16) | (g << 8) | b);
 }
-constexpr uint32_t kEmptyWord = kVoxelOffset << 4;
+constexpr uint32_t kEmptyWord = leaf_word(0);
 
-// distance from the LOD centre to the cube (x,y,z) of level `level` (cell size 2 / 2^level)
-float cube_distance(const float cam[3], uint32_t level, uint32_t x, uint32_t y, uint32_t z) {
-    const float s = 2.0f / float(1u << level);
-    const uint32_t c[3] = {x, y, z};
-    float d2 = 0;
-    for (int i = 0; i < 3; i++) {
-        const float lo = -1.0f + s * float(c[i]), hi = lo + s;
-        const float d = cam[i] < lo ? lo - cam[i] : (cam[i] > hi ? cam[i] - hi : 0.0f);
-        d2 += d * d;
-    }
-    return std::sqrt(d2);
-}
-
+// whether the generators split the cube (x, y, z) of level `level` (cell size 2 / 2^level) for the LOD centre p.cam
 bool lod_refine(const svo_terrain_params &p, uint32_t level, uint32_t x, uint32_t y, uint32_t z) {
     if (level >= p.max_depth) return false;
     if (level < p.min_depth) return true;
-    const float r = cube_distance(p.cam, level, x, y, z);
-    return float(1u << level) * r < p.lod_c;
+    const float s = 2.0f / float(1u << level);
+    const uint32_t c[3] = {x, y, z};
+    float lo[3], hi[3];
+    for (int i = 0; i < 3; i++) {
+        lo[i] = -1.0f + s * float(c[i]);
+        hi[i] = lo[i] + s;
+    }
+    return svo_rules::lod_refines(p.cam, lo, hi, level, p.lod_c);
 }
 
 struct Terrain {

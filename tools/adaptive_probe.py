@@ -24,9 +24,11 @@ import time
 import numpy as np
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+TOOLS = os.path.dirname(os.path.abspath(__file__))
+ROOT = os.path.dirname(TOOLS)
+sys.path[:0] = [ROOT, TOOLS]
 import __graft_entry__ as entry  # noqa: E402
+from expand_probe import state_digest  # noqa: E402
 
 BLOCKS = ("stone", "dirt", "grass", "wood", "leaf", "slate", "crystal", "glass")
 CAM, LOOK = (0.0, 0.25, -1.2), (0.0, -0.3, 1.0)  # above the island, looking in and down
@@ -140,6 +142,8 @@ def main():
                 and np.array_equal(a.hole_stack(), b.hole_stack()) and loops[0][4].chunk_ids() == loops[1][4].chunk_ids())
         say(f"# after {args.frames} frames: host and device words, positions, hole stacks and chunk sets equal: {same}; "
             f"length {len(a)}, holes {a.hole_count()}")
+        say(f"# the device copy's downloaded state (list sizes above vary from run to run with the scan's atomics; two runs "
+            f"with the same sizes must print the same digest): {state_digest(b)}")
         big = [r for r in rows if r[1] >= 1_000_000]
         if big:
             say(f"# frames at the 1 023 999-entry unsubdivide cap: {len(big)}; device step median "

@@ -14,6 +14,7 @@ and the two trees (words, positions, hole stacks, lengths, counts, chunk sets) m
     python tools/expand_probe.py [--out profiles/expand_probe.log] [--chunk-depth 9] [--expand-depth 12] [--lod 4096]
 """
 import argparse
+import hashlib
 import os
 import shutil
 import sys
@@ -48,6 +49,14 @@ def open_world(pkg, path, blocks):
 def monu9_world(pkg):
     z = np.load(os.path.join(ROOT, "tests", "golden", "monu9_vox.npz"))
     return pkg.adaptive.World(pkg.CpuOctree.from_voxels(int(z["size"][0]), z["xyzi"], z["palette"]))
+
+
+def state_digest(octree):
+    """What two builds of the library are compared by: the same inputs must give the same digest."""
+    h = hashlib.sha256()
+    for a in (octree.raw_data(), octree.positions(), octree.hole_stack()):
+        h.update(np.ascontiguousarray(a).tobytes())
+    return f"{len(octree)} words {h.hexdigest()[:32]}"
 
 
 def both_ways(pkg, say, name, make_world, size, max_depth, cam, lod_c, capacity, runs):
@@ -91,6 +100,7 @@ def both_ways(pkg, say, name, make_world, size, max_depth, cam, lod_c, capacity,
                 and np.array_equal(got.positions().view(np.uint32), octree.positions().view(np.uint32))
                 and np.array_equal(got.hole_stack(), octree.hole_stack()) and world.chunk_ids() == world_d.chunk_ids())
         say(f"               words, positions, hole stack, length, count and chunk set equal the host's: {same}")
+        say(f"               sha256 of the downloaded words, positions and hole stack: {state_digest(got)}")
         g.close()
         if not same:
             raise SystemExit(f"{name}: the device-expanded tree differs from the host's")
