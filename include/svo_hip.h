@@ -353,6 +353,44 @@ int svo_nodes_build_dense(svo_ctx *ctx, const uint32_t *grid, const svo_build_pa
 #define SVO_BUILD_TIMES 6
 int svo_build_timing(svo_ctx *ctx, float ms_out[SVO_BUILD_TIMES]);
 
+/* ---- a tree in the node buffer edited in place ----
+ * Inserts and removes voxels in the first n_words words of the node buffer without rebuilding the tree.  Inputs as
+ * svo_nodes_build: xyz n * 3 u32 and colours n u32 (0x00RRGGBB, the low 24 bits count) or NULL, DEVICE pointers on the
+ * ctx's device, every coordinate in [0, 2^depth).
+ * Afterwards the words [0, *n_words_out) are, bit for bit, what the host model makes of the same words with
+ * put(p, leaf, depth), p = cell / 2^depth * 2 - 1, applied once per distinct cell in ascending Morton-key order (the
+ * builder's key: child index x bit << 2 | y bit << 1 | z bit, level 1 in the top bits); of several voxels in one cell the
+ * last in input order wins.  leaf = (SVO_VOXEL_OFFSET + (colour & 0xFFFFFF)) << 4, so a colour-0 voxel writes the empty
+ * word: that is how a voxel is removed.  A leaf above `depth` on the way down is split into 8 EMPTY children -- the
+ * reference's put_in_voxel (cpu_octree.rs:100-111) does not carry the coarse leaf's colour down, and neither does this.
+ * Each new group is appended at the current end in the order the host creates them (by voxel, then by level), so
+ * *n_words_out = n_words + 8 * (groups created).  Written words have hit counter 0; every other word keeps all 32 bits,
+ * and nothing at or behind *n_words_out is touched.  The same words on every run and for any order of distinct cells.
+ * SVO_ERR_STATE, nothing written, when a cell is an interior node at `depth` (the tree is finer there than the edit; the
+ * host's put never ends on that input): svo_last_error names the input index of the first such voxel in key order.
+ * Replacing a subtree by a coarser leaf, pruning groups that became all-empty and reusing orphaned groups are not done.
+ * The other errors leave the node buffer untouched too, all decided by a read-only plan pass before any write:
+ * SVO_ERR_ARG for a bad depth, n >= 2^31, NULL xyz with n > 0, a coordinate outside [0, 2^depth) (checked on the device),
+ * or n_words not a positive multiple of 8 or above the capacity; SVO_ERR_CAP when the exact new length exceeds max_words,
+ * the capacity or 2^27; SVO_ERR_STATE without a node buffer (or for words whose pointers lead outside [0, n_words)).
+ * n == 0 succeeds and returns n_words.
+ * Runs on the ctx stream and blocks once, to read the counts and the status back; the writes are enqueued (a following
+ * svo_render on the stream sees the edit), ordered and recorded like svo_nodes_write, so every context sharing the buffer
+ * rebuilds its top table and schedule.  Inputs must stay valid until svo_sync.  SVO_OPT_TREE_DEPTH is the caller's to
+ * raise when depth exceeds it. */
+typedef struct svo_edit_params {
+    uint32_t depth;          /* 1..21: the level of the edited voxels */
+    uint32_t default_colour; /* used when colours == NULL */
+    uint64_t n_words;        /* the tree's current length: a multiple of 8, at least 8 */
+    uint64_t max_words;      /* 0 = the node buffer's capacity; never above SVO_VOXEL_OFFSET */
+} svo_edit_params;
+int svo_nodes_edit(svo_ctx *ctx, const uint32_t *xyz, const uint32_t *colours, size_t n, const svo_edit_params *p,
+                   uint64_t *n_words_out);
+/* Times (ms) of the last edit: [0] keys, [1] sort, [2] plan (leaf pass, walk, scan), [3] status read-back, [4] fill and
+ * link (device events; waits for the link), [5] host wall time of the call.  All 0 after an empty edit. */
+#define SVO_EDIT_TIMES 6
+int svo_edit_timing(svo_ctx *ctx, float ms_out[SVO_EDIT_TIMES]);
+
 /* ---- mip-coloured chunk trees and streamable worlds built on the GPU ----
  * Inputs as svo_nodes_build: xyz n * 3 u32 and colours n u32 (0x00RRGGBB) or NULL, DEVICE pointers on the ctx's device;
  * the last voxel of a cell wins; a colour-0 voxel is an empty leaf on a path that exists.  A chunk tree is the host

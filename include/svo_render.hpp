@@ -262,6 +262,21 @@ class Render {  // render.rs:3-285
         gpu_.poll_wait();  // the inputs may go away
         return n_words;
     }
+    // n voxels put into the first n_words words of the node buffer, in place (svo_nodes_edit): inputs as
+    // build_nodes, colour 0 removes a voxel; returns the new length.  Throws, with nothing written, for a cell the tree
+    // refines below depth.
+    uint64_t edit_nodes(uint64_t n_words, const uint32_t *xyz_dev, const uint32_t *colours_dev, size_t n, uint32_t depth,
+                        uint32_t colour = 0xFFFFFF, uint64_t max_words = 0) {
+        if (depth > declared_depth_) {
+            gpu_.set_option(SVO_OPT_TREE_DEPTH, depth);
+            declared_depth_ = depth;
+        }
+        const svo_edit_params p{depth, colour, n_words, max_words};
+        uint64_t new_words = 0;
+        gpu_.check(svo_nodes_edit(gpu_.ctx(), xyz_dev, colours_dev, n, &p, &new_words));
+        gpu_.poll_wait();  // the inputs may go away
+        return new_words;
+    }
     // the adaptive step on the GPU (svo_adaptive_*): attach once (SVO_OPT_SCAN_CLEARS_COUNTERS = 1, the
     // octree's words in the node buffer, `world` kept alive), then after each scan step() over the scan's own lists (or
     // explicit DEVICE lists); download() brings the host octree up to date

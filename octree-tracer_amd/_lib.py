@@ -56,6 +56,16 @@ class BuildParams(C.Structure):
     ]
 
 
+class EditParams(C.Structure):
+    """svo_edit_params: voxels put into a tree that is in the node buffer (include/svo_hip.h)."""
+    _fields_ = [
+        ("depth", C.c_uint32),
+        ("default_colour", C.c_uint32),
+        ("n_words", C.c_uint64),
+        ("max_words", C.c_uint64),
+    ]
+
+
 class ChunkBuildParams(C.Structure):
     """svo_chunk_build_params: a mip-coloured tree or a chunked world built on the GPU (include/svo_hip.h)."""
     _fields_ = [
@@ -89,6 +99,7 @@ DEVICE_SYMBOLS = [
     "svo_adaptive_attach", "svo_adaptive_step", "svo_adaptive_download", "svo_adaptive_length", "svo_adaptive_timing",
     "svo_adaptive_expand", "svo_adaptive_expand_timing",
     "svo_cpu_octree_build", "svo_world_build", "svo_world_build_timing",
+    "svo_nodes_edit", "svo_edit_timing",
 ]
 HOST_SYMBOLS = [
     "svo_cpu_octree_new", "svo_cpu_octree_free", "svo_cpu_octree_len", "svo_cpu_octree_load_file",
@@ -182,6 +193,8 @@ def lib():
     sig("svo_cpu_octree_build", C.c_int, vp, vp, vp, sz, C.POINTER(ChunkBuildParams), C.POINTER(vp))
     sig("svo_world_build", C.c_int, vp, vp, vp, vp, sz, C.POINTER(ChunkBuildParams))
     sig("svo_world_build_timing", C.c_int, vp, fp)
+    sig("svo_nodes_edit", C.c_int, vp, vp, vp, sz, C.POINTER(EditParams), C.POINTER(u64))
+    sig("svo_edit_timing", C.c_int, vp, fp)
     sig("svo_adaptive_attach", C.c_int, vp, vp, vp)
     sig("svo_adaptive_step", C.c_int, vp, vp, u32, vp, u32, C.POINTER(AdaptiveResult))
     sig("svo_adaptive_download", C.c_int, vp, vp)

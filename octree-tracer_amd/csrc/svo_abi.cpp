@@ -567,6 +567,7 @@ int svo_ctx_destroy(svo_ctx *ctx) {
     ctx->proc.reset();
     ctx->build.reset();
     ctx->adapt.reset();
+    ctx->edit.reset();
     release_store(ctx);
     if (ctx->top_table) (void)hipFree(ctx->top_table);
     if (ctx->status) (void)hipFree(ctx->status);

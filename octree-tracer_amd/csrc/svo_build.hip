@@ -25,7 +25,7 @@
 // The list entry points share one front end (check_list, list_leaves: keys, sort, leaf pass), level_bounds and
 // read_counts.  Shared with the other passes: the tile shape and scans (svo_scan.h), the Morton convention
 // (svo_morton.h), mip_of and the mip pass (svo_mip.h), svo_grow (svo_ctx.h).  This file also holds what the others
-// borrow: svo_build_sort_u32 / svo_build_scan_u32 (svo_adapt.hip) and svo_world_writer, the one place that lays out a
+// borrow: svo_build_sort_u32 / svo_build_scan_u32 (svo_adapt.hip), svo_build_list_leaves (svo_edit.hip) and svo_world_writer, the one place that lays out a
 // generated world's directory (svo_world_build here, svo_world_generate in svo_proc.hip).
 #include <hip/hip_runtime.h>
 
@@ -185,6 +185,7 @@ struct LevelIn {
 struct LevelOut {
     uint64_t *keys;     // compacted keys, one per run
     uint32_t *colours;  // kDedupe / kDense: the leaf colour of each
+    uint32_t *index;    // kDedupe: the input index of each (null: not kept)
     uint32_t cap;       // room in keys / colours
     // emit (kParent only; words null: counting pass)
     uint32_t *words;
@@ -276,6 +277,7 @@ __global__ __launch_bounds__(kThreads) void build_compact_kernel(LevelIn in, con
             if (r < out.cap) {
                 out.keys[r] = M == kParent || M == kChunk ? k[j] >> 3 : (M == kDense ? k[j] & 0xFFFFFFFFu : k[j]);
                 if (M == kDedupe) out.colours[r] = (in.colours ? in.colours[in.vals[i]] : in.colour) & 0xFFFFFFu;
+                if (M == kDedupe && out.index) out.index[r] = in.vals[i];
                 if (M == kDense) out.colours[r] = uint32_t(k[j] >> 32) & 0xFFFFFFu;
             }
             r++;
@@ -526,9 +528,9 @@ uint64_t word_limit(const svo_ctx *ctx, const svo_build_params *p) {
 
 // The front end of the list entry points: workspace for n voxels (chunked: and for runs_items chunk starts, cleared with
 // the counts), keys, sort, and the leaf pass, which keeps the last voxel of every run of equal keys in keys[2] /
-// leaf_colours and their number in counts[depth].
+// leaf_colours and their number in counts[depth]; with keep_index also their input indices, in the sort's spare vals buffer.
 int list_leaves(svo_ctx *ctx, const uint32_t *xyz, const uint32_t *colours, size_t n, uint32_t depth, uint32_t default_colour,
-                size_t runs_items) {
+                size_t runs_items, bool keep_index = false) {
     const uint32_t nt = svo_div_up(n, kTile);
     int rc = ensure_state(ctx, n, std::max<uint64_t>(n, 256ull * nt), 256ull * nt);
     if (rc) return rc;
@@ -554,6 +556,7 @@ int list_leaves(svo_ctx *ctx, const uint32_t *xyz, const uint32_t *colours, size
     LevelOut out{};
     out.keys = s->keys[2];
     out.colours = s->leaf_colours;
+    out.index = keep_index ? s->vals[(passes & 1) ^ 1] : nullptr;
     out.cap = (uint32_t)s->items;
     return level_pass<kDedupe>(ctx, in, out, n, s->counts + depth);
 }
@@ -666,6 +669,38 @@ int svo_build_scan_u32(svo_ctx *ctx, uint32_t *a, uint32_t n) {
     int rc = ensure_state(ctx, 0, n, 0);
     if (rc) return rc;
     return scan_u32(ctx, a, n);
+}
+
+// The list front end for other passes (svo_edit.hip): the argument checks of the list entry points, then keys, sort and
+// the leaf pass.  The events are the builder's own, so the times of a build still in flight are taken first.
+int svo_build_check_list(svo_ctx *ctx, const uint32_t *depth, const uint32_t *xyz, size_t n) {
+    return check_list(ctx, depth, nullptr, false, xyz, n);
+}
+
+int svo_build_list_leaves(svo_ctx *ctx, const uint32_t *xyz, const uint32_t *colours, size_t n, uint32_t depth,
+                          uint32_t default_colour, svo_build_leaves *out) {
+    if (ctx->build && !ctx->build->timed) {
+        float ms[SVO_BUILD_TIMES];
+        int rc = svo_build_timing(ctx, ms);
+        if (rc) return rc;
+    }
+    int rc = list_leaves(ctx, xyz, colours, n, depth, default_colour, 0, true);
+    if (rc) return rc;
+    svo_build_state *s = ctx->build.get();
+    const uint32_t a = ((3 * depth + 7) / 8) & 1;  // the sort's result was in keys[a] / vals[a]: free again, like keys[a ^ 1]
+    out->keys = s->keys[2];
+    out->colours = s->leaf_colours;
+    out->index = s->vals[a ^ 1];
+    out->count = s->counts + depth;
+    out->range_err = s->counts + kErrSlot;
+    out->spare32 = s->vals[a];
+    out->spare64[0] = s->keys[0];
+    out->spare64[1] = s->keys[1];
+    out->items = s->items;
+    out->ev_start = s->ev[kEvStart];
+    out->ev_keys = s->ev[kEvKeys];
+    out->ev_sort = s->ev[kEvSort];
+    return SVO_OK;
 }
 
 namespace {

@@ -1,6 +1,6 @@
 // svo_ctx.h -- the device context behind the opaque `svo_ctx` of include/svo_hip.h, and the host helpers of the files that
 // use it: svo_abi.cpp (trace / scan dispatch), svo_comm.cpp (RCCL frame gather) and the GPU tree passes (svo_proc.hip,
-// svo_build.hip, svo_adapt.hip).  Shared by the passes: svo_grow / svo_grow_pinned / svo_grow_keep (workspaces), the builder's sort
+// svo_build.hip, svo_edit.hip, svo_adapt.hip).  Shared by the passes: svo_grow / svo_grow_pinned / svo_grow_keep (workspaces), the builder's sort
 // and scan, svo_world_writer (a generated world's directory); svo_scan.h, svo_mip.h and svo_morton.h hold the device pieces,
 // svo_rules.h the walks and rules that svo_host.cpp and svo_adapt.hip both run.
 // Internal: not part of the boundary.
@@ -39,6 +39,7 @@ struct svo_node_store {
 struct svo_proc_state;
 struct svo_build_state;
 struct svo_adapt_state;
+struct svo_edit_state;
 template <typename T>
 using svo_workspace = std::unique_ptr<T, void (*)(T *)>;
 template <typename T>
@@ -119,6 +120,7 @@ struct svo_ctx {
     svo_workspace<svo_proc_state> proc{nullptr, nullptr};    // procedural generator's workspace (svo_proc.hip)
     svo_workspace<svo_build_state> build{nullptr, nullptr};  // tree builder's workspace (svo_build.hip)
     svo_workspace<svo_adapt_state> adapt{nullptr, nullptr};  // device adaptive state (svo_adapt.hip)
+    svo_workspace<svo_edit_state> edit{nullptr, nullptr};    // in-place edits' workspace (svo_edit.hip)
     std::string err;
 };
 
@@ -190,6 +192,23 @@ void svo_comm_release(svo_ctx *ctx);
 // passes on the ctx stream; both use the builder's workspace
 int svo_build_sort_u32(svo_ctx *ctx, const uint32_t *in, uint32_t n, uint32_t *out);
 int svo_build_scan_u32(svo_ctx *ctx, uint32_t *a, uint32_t n);
+// the front end of the builder's list entry points, for other passes over a voxel list (svo_edit.hip): the checks of
+// depth (null: no params), n and xyz with the builder's messages, then keys, the stable sort and the leaf pass on the ctx
+// stream.  Everything in svo_build_leaves lives in the builder's workspace and holds until the next call that uses it.
+struct svo_build_leaves {
+    const uint64_t *keys;       // the distinct cells' Morton keys, ascending (svo_morton.h)
+    const uint32_t *colours;    // their colours (24 bits): of several voxels in one cell the last in input order
+    const uint32_t *index;      // that voxel's input index
+    const uint32_t *count;      // device word: how many there are
+    const uint32_t *range_err;  // device word: non-zero when a coordinate was outside [0, 2^depth)
+    uint32_t *spare32;          // `items` u32 and twice `items` u64 that the front end no longer needs
+    uint64_t *spare64[2];
+    size_t items;               // >= n
+    hipEvent_t ev_start, ev_keys, ev_sort;  // recorded before the keys kernel, after it, after the sort
+};
+int svo_build_check_list(svo_ctx *ctx, const uint32_t *depth, const uint32_t *xyz, size_t n);
+int svo_build_list_leaves(svo_ctx *ctx, const uint32_t *xyz, const uint32_t *colours, size_t n, uint32_t depth,
+                          uint32_t default_colour, svo_build_leaves *out);
 // The one writer of a generated world's directory (svo_build.hip), for svo_world_build and
 // svo_world_generate: create() makes the directory and the empty root; add_chunk() writes <id>.bin (id = SVO_CHUNK_OFFSET
 // / 2 + i) from `bytes` in the <id>.bin layout, keeps the chunk in w as a node-less CpuOctree carrying its top_mip (the

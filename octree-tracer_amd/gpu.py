@@ -56,6 +56,13 @@ class Gpu:
         self.check(lib().svo_build_timing(self._h, ms))
         return list(ms)
 
+    def edit_timing(self):
+        """ms of the last Render.edit_nodes: keys, sort, plan, status read-back, fill and link (device events), host wall
+        time of the call (svo_edit_timing)"""
+        ms = (C.c_float * 6)()
+        self.check(lib().svo_edit_timing(self._h, ms))
+        return list(ms)
+
     def world_build_timing(self):
         """ms of the last CpuOctree.build / World.build_world: keys, sort, levels, count read-back, emit, mips (device
         events), chunk read-back, chunk files and root (CpuOctree.build: the tree), host wall time of the call

@@ -4,7 +4,7 @@ import ctypes as C
 import numpy as np
 import torch
 
-from ._lib import BuildParams, Uniforms, lib
+from ._lib import BuildParams, EditParams, Uniforms, lib
 from .camera import camera_matrices
 
 F_PAUSE_ADAPTIVE, F_SHOW_STEPS, F_SHOW_HITS, F_SHADOWS, F_MISC_BOOL = 1, 2, 4, 8, 16
@@ -107,6 +107,37 @@ class Render:
         torch.cuda.current_stream(dev).synchronize()  # the inputs were made on torch's stream
         rc = lib().svo_nodes_build(self.gpu._h, xyz.data_ptr() if n else None, col.data_ptr() if col is not None and n else None, n,
                                    C.byref(p), C.byref(out))
+        self.gpu.check(rc)
+        self.gpu.sync()  # (the inputs may be released by the caller)
+        self.node_length = out.value
+        return out.value
+
+    def edit_nodes(self, coords, depth, colours=None, colour=0xFFFFFF, max_words=None):
+        """Put voxels into the tree that is in the node buffer, in place (svo_nodes_edit): what put_in_voxel
+        per distinct cell makes of the first node_length words; colour 0 removes a voxel; a coarser leaf on the way is split
+        into empty children.  Inputs as build_nodes.  A cell the tree refines below `depth` raises SvoError and nothing is
+        written.  Returns the new length (node_length)."""
+        dev = torch.device("cuda", self.gpu.device)
+        xyz = _device_u32(coords, dev, clamp=True)
+        if xyz.dim() != 2 or xyz.shape[1] != 3:
+            raise ValueError(f"coords must be (N, 3), got {tuple(xyz.shape)}")
+        n = xyz.shape[0]
+        col = None
+        if colours is not None:
+            col = _device_u32(colours, dev, mask=0xFFFFFF).reshape(-1)
+            if col.numel() != n:
+                raise ValueError(f"{col.numel()} colours for {n} voxels")
+        depth = int(depth)
+        self._declare_depth(depth)
+        p = EditParams()
+        p.depth = max(0, depth)
+        p.default_colour = int(colour) & 0xFFFFFF
+        p.n_words = int(self.node_length)
+        p.max_words = int(max_words or 0)
+        out = C.c_uint64()
+        torch.cuda.current_stream(dev).synchronize()  # the inputs were made on torch's stream
+        rc = lib().svo_nodes_edit(self.gpu._h, xyz.data_ptr() if n else None, col.data_ptr() if col is not None and n else None, n,
+                                  C.byref(p), C.byref(out))
         self.gpu.check(rc)
         self.gpu.sync()  # (the inputs may be released by the caller)
         self.node_length = out.value
