@@ -368,7 +368,8 @@ int svo_build_timing(svo_ctx *ctx, float ms_out[SVO_BUILD_TIMES]);
  * and nothing at or behind *n_words_out is touched.  The same words on every run and for any order of distinct cells.
  * SVO_ERR_STATE, nothing written, when a cell is an interior node at `depth` (the tree is finer there than the edit; the
  * host's put never ends on that input): svo_last_error names the input index of the first such voxel in key order.
- * Replacing a subtree by a coarser leaf, pruning groups that became all-empty and reusing orphaned groups are not done.
+ * Replacing a subtree by a coarser leaf and reusing free groups are not done; groups that became all-empty or were cut
+ * off are pruned and dropped afterwards, by svo_nodes_compact.
  * The other errors leave the node buffer untouched too, all decided by a read-only plan pass before any write:
  * SVO_ERR_ARG for a bad depth, n >= 2^31, NULL xyz with n > 0, a coordinate outside [0, 2^depth) (checked on the device),
  * or n_words not a positive multiple of 8 or above the capacity; SVO_ERR_CAP when the exact new length exceeds max_words,
@@ -390,6 +391,42 @@ int svo_nodes_edit(svo_ctx *ctx, const uint32_t *xyz, const uint32_t *colours, s
  * link (device events; waits for the link), [5] host wall time of the call.  All 0 after an empty edit. */
 #define SVO_EDIT_TIMES 6
 int svo_edit_timing(svo_ctx *ctx, float ms_out[SVO_EDIT_TIMES]);
+
+/* ---- the tree in the node buffer compacted in place ----
+ * Reads the first n_words words of the node buffer as a tree rooted at group 0.  E = SVO_VOXEL_OFFSET << 4 is the empty
+ * word; a word is interior when word >> 4 < SVO_VOXEL_OFFSET.
+ * flags == 0: the words [0, *n_words_out) become, bit for bit, what the host's svo_nodes_relayout(words, n_words, 32, out,
+ * perm) returns: the reachable groups in breadth-first order, each level in the order of its parents, pointers rewritten,
+ * the low 4 bits (hit counters) of every word kept, unreachable groups dropped.  perm_out_dev (DEVICE, at least n_words
+ * u32, or NULL): perm[new word] = old word for [0, *n_words_out); nothing behind *n_words_out is written in it.
+ * SVO_COMPACT_PRUNE_EMPTY: a group is dead when each of its 8 words, counter ignored, is E or an interior word whose group
+ * is dead; the root group is never dead.  An interior word pointing at a dead group becomes exactly E (counter 0), dead
+ * groups are dropped, and the rest is as above, applied to the pruned tree.  Pruning a pruned, canonical tree returns it
+ * unchanged.
+ * Afterwards the words [*n_words_out, n_words) hold E, no word at or behind n_words is touched, *n_words_out <= n_words,
+ * and the result is the same on every run (no atomics: the order is the contract).
+ * Errors are decided before any write and leave the node buffer and perm_out_dev as they were.  SVO_ERR_ARG: NULL p or
+ * n_words_out, unknown flag bits, n_words not a positive multiple of 8 or above the capacity.  SVO_ERR_STATE, the cause in
+ * svo_last_error ("malformed tree: ..." for the last four): no node buffer; a device adaptive state attached to the
+ * context (svo_adaptive_attach: its positions and hole stack index the old layout); an interior pointer that is not a
+ * multiple of 8 or with pointer + 8 > n_words; a tree deeper than 31 levels; a group reached twice.  Of several causes
+ * the first in this order is reported: NULL p or n_words_out, flag bits, no node buffer, an attached adaptive state (both
+ * SVO_ERR_STATE, before n_words is looked at: without a buffer there is no capacity to hold it against), n_words, the tree.
+ * Runs on the ctx stream and blocks once per level of the tree (a count is read back) and once before the emit; the
+ * copy back is enqueued (a following svo_render on the stream sees the compacted tree), ordered and recorded like
+ * svo_nodes_write, so every context sharing the buffer rebuilds its top table and schedule. */
+#define SVO_COMPACT_PRUNE_EMPTY 1u
+typedef struct svo_compact_params {
+    uint32_t flags;    /* 0 or SVO_COMPACT_PRUNE_EMPTY */
+    uint32_t reserved;
+    uint64_t n_words;  /* the tree's current length: a multiple of 8, at least 8 */
+} svo_compact_params;
+int svo_nodes_compact(svo_ctx *ctx, const svo_compact_params *p, uint32_t *perm_out_dev /* may be null */, uint64_t *n_words_out);
+/* Times (ms) of the last compaction: [0] discover (with its per-level read-backs), [1] check, [2] prune, [3] emit,
+ * [4] copy back (device events; waits for the copy), [5] host wall time of the call.  A refused call leaves the times
+ * of the last compaction that ran. */
+#define SVO_COMPACT_TIMES 6
+int svo_compact_timing(svo_ctx *ctx, float ms_out[SVO_COMPACT_TIMES]);
 
 /* ---- mip-coloured chunk trees and streamable worlds built on the GPU ----
  * Inputs as svo_nodes_build: xyz n * 3 u32 and colours n u32 (0x00RRGGBB) or NULL, DEVICE pointers on the ctx's device;

@@ -277,6 +277,17 @@ class Render {  // render.rs:3-285
         gpu_.poll_wait();  // the inputs may go away
         return new_words;
     }
+    // the first n_words words of the node buffer compacted in place (svo_nodes_compact): unreachable groups
+    // dropped, with `prune` also the groups that hold nothing, the rest in the builder's breadth-first order; returns the
+    // new length.  perm_dev (device, n_words u32, or null): perm[new word] = old word.  Throws, with nothing written, for
+    // a malformed tree or with a device adaptive state attached.
+    uint64_t compact_nodes(uint64_t n_words, bool prune = true, uint32_t *perm_dev = nullptr) {
+        const svo_compact_params p{prune ? SVO_COMPACT_PRUNE_EMPTY : 0u, 0u, n_words};
+        uint64_t new_words = 0;
+        gpu_.check(svo_nodes_compact(gpu_.ctx(), &p, perm_dev, &new_words));
+        gpu_.poll_wait();
+        return new_words;
+    }
     // the adaptive step on the GPU (svo_adaptive_*): attach once (SVO_OPT_SCAN_CLEARS_COUNTERS = 1, the
     // octree's words in the node buffer, `world` kept alive), then after each scan step() over the scan's own lists (or
     // explicit DEVICE lists); download() brings the host octree up to date

@@ -66,6 +66,15 @@ class EditParams(C.Structure):
     ]
 
 
+class CompactParams(C.Structure):
+    """svo_compact_params: the tree in the node buffer compacted in place (include/svo_hip.h)."""
+    _fields_ = [
+        ("flags", C.c_uint32),
+        ("reserved", C.c_uint32),
+        ("n_words", C.c_uint64),
+    ]
+
+
 class ChunkBuildParams(C.Structure):
     """svo_chunk_build_params: a mip-coloured tree or a chunked world built on the GPU (include/svo_hip.h)."""
     _fields_ = [
@@ -100,6 +109,7 @@ DEVICE_SYMBOLS = [
     "svo_adaptive_expand", "svo_adaptive_expand_timing",
     "svo_cpu_octree_build", "svo_world_build", "svo_world_build_timing",
     "svo_nodes_edit", "svo_edit_timing",
+    "svo_nodes_compact", "svo_compact_timing",
 ]
 HOST_SYMBOLS = [
     "svo_cpu_octree_new", "svo_cpu_octree_free", "svo_cpu_octree_len", "svo_cpu_octree_load_file",
@@ -195,6 +205,8 @@ def lib():
     sig("svo_world_build_timing", C.c_int, vp, fp)
     sig("svo_nodes_edit", C.c_int, vp, vp, vp, sz, C.POINTER(EditParams), C.POINTER(u64))
     sig("svo_edit_timing", C.c_int, vp, fp)
+    sig("svo_nodes_compact", C.c_int, vp, C.POINTER(CompactParams), vp, C.POINTER(u64))
+    sig("svo_compact_timing", C.c_int, vp, fp)
     sig("svo_adaptive_attach", C.c_int, vp, vp, vp)
     sig("svo_adaptive_step", C.c_int, vp, vp, u32, vp, u32, C.POINTER(AdaptiveResult))
     sig("svo_adaptive_download", C.c_int, vp, vp)

@@ -568,6 +568,7 @@ int svo_ctx_destroy(svo_ctx *ctx) {
     ctx->build.reset();
     ctx->adapt.reset();
     ctx->edit.reset();
+    ctx->compact.reset();
     release_store(ctx);
     if (ctx->top_table) (void)hipFree(ctx->top_table);
     if (ctx->status) (void)hipFree(ctx->status);

@@ -1,0 +1,307 @@
+// svo_compact.hip -- the tree in the node buffer compacted in place: unreachable groups dropped, with
+// SVO_COMPACT_PRUNE_EMPTY also the groups that hold nothing, the rest in the canonical breadth-first order of the
+// builder (svo_nodes_relayout(words, n, 32, ...) of the host).  Scans instead of atomics, so the words do not depend on
+// the run.  Every kernel gives 8 lanes to a group, one word per lane: a wave64 handles 8 groups, a group is one 32-byte
+// read, and its interior mask is its byte of the wave's ballot.
+//
+//   discover  top-down, one launch set per level: the frontier (old group starts, order[off .. off + F)) counts its
+//             interior words per group, an exclusive scan of the counts (the builder's scan) gives every group the place
+//             of its first child in the next frontier, and the scatter appends the children behind the frontier at
+//             scan + (interior lanes below), which keeps the order of the parents.  first_child[k] = the index in `order`
+//             of group k's first interior child.  A pointer that is no multiple of 8 or leaves the words sets a status
+//             word; the next frontier's size comes back with the status, once per level
+//   check     new_of[order[k] / 8] = k by plain stores, then a launch of its own tests new_of[order[k] / 8] == k: of two
+//             groups k that share an old group one store wins and the other k sees it, whichever it is
+//   prune     bottom-up, one launch per level: live[k] = any word is a non-empty leaf or an interior word whose child
+//             is live; live[0] = 1.  Without the flag every group is live
+//   emit      one exclusive scan of live over all of order gives every live group its new number (level-major, and a
+//             live group's ancestors are live: still breadth-first).  The groups are written into a workspace image, not
+//             into the node buffer they are read from; the optional perm is written here
+//   copy back one device-to-device copy of the image and one fill of the freed tail with the empty word
+//
+// Every error is decided before the emit, so it leaves the node buffer and the perm as they were.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "svo_ctx.h"
+#include "svo_scan.h"  // (kThreads)
+
+namespace {
+
+constexpr uint32_t kEmptyWord = SVO_VOXEL_OFFSET << 4;
+constexpr uint64_t kMaxWords = SVO_VOXEL_OFFSET;  // 2^27: no pointer reaches further
+constexpr uint32_t kMaxLevels = 31;               // as svo_nodes_relayout and svo_nodes_max_depth
+enum Status { kStAlign, kStRange, kStNext, kStDup, kStLive, kStWords };  // the words read back
+
+// What the 8 lanes of a group know of it.  Every lane of the wave must get here: the mask is a ballot.
+struct GroupLane {
+    uint32_t word, pointer;
+    bool interior;
+    uint32_t mask;   // the group's interior lanes, bit c = child c
+    uint32_t below;  // how many of them are below this lane
+};
+
+__device__ inline GroupLane group_lane(const uint32_t *words, const uint32_t *order, uint32_t k, uint32_t c, bool valid) {
+    GroupLane g;
+    g.word = valid ? words[order[k] + c] : kEmptyWord;
+    g.pointer = g.word >> 4;
+    g.interior = valid && g.pointer < SVO_VOXEL_OFFSET;
+    const uint64_t all = __ballot(g.interior);
+    g.mask = uint32_t(all >> (__lane_id() & ~7u)) & 0xFFu;
+    g.below = __popc(g.mask & ((1u << c) - 1u));
+    return g;
+}
+
+// The frontier order[0, n) (the caller passes order + off): count[k] = interior words of group k; the pointers are checked.
+__global__ __launch_bounds__(kThreads) void compact_count_kernel(const uint32_t *words, uint32_t n_words, const uint32_t *order,
+                                                                 uint32_t n, uint32_t *count, uint32_t *status) {
+    const uint32_t i = blockIdx.x * kThreads + threadIdx.x, k = i >> 3, c = i & 7u;
+    const GroupLane g = group_lane(words, order, k, c, k < n);
+    if (g.interior) {  // (every writer stores the same value)
+        if (g.pointer & 7u) status[kStAlign] = 1u;
+        else if (g.pointer + 8u > n_words) status[kStRange] = 1u;
+    }
+    if (k < n && c == 0) count[k] = __popc(g.mask);
+}
+
+// The frontier order[off, off + n) and the exclusive scan of its counts: the children go behind it, in the parents' order.
+__global__ __launch_bounds__(kThreads) void compact_scatter_kernel(const uint32_t *words, uint32_t *order, uint32_t off, uint32_t n,
+                                                                   const uint32_t *scan, uint32_t *first_child, uint32_t cap,
+                                                                   uint32_t *status) {
+    const uint32_t i = blockIdx.x * kThreads + threadIdx.x, k = i >> 3, c = i & 7u;
+    const GroupLane g = group_lane(words, order + off, k, c, k < n);
+    if (k >= n) return;
+    const uint32_t first = off + n + scan[k];
+    if (g.interior && first + g.below < cap) order[first + g.below] = g.pointer;  // (more than cap: a group reached twice, refused on the host)
+    if (c == 0) {
+        first_child[off + k] = first;
+        if (k == n - 1) status[kStNext] = scan[k] + __popc(g.mask);
+    }
+}
+
+__global__ __launch_bounds__(kThreads) void compact_mark_kernel(const uint32_t *order, uint32_t n, uint32_t *new_of) {
+    const uint32_t k = blockIdx.x * kThreads + threadIdx.x;
+    if (k < n) new_of[order[k] >> 3] = k;
+}
+
+__global__ __launch_bounds__(kThreads) void compact_check_kernel(const uint32_t *order, uint32_t n, const uint32_t *new_of,
+                                                                 uint32_t *status) {
+    const uint32_t k = blockIdx.x * kThreads + threadIdx.x;
+    if (k < n && new_of[order[k] >> 3] != k) status[kStDup] = 1u;
+}
+
+// The level order[off, off + n), behind the launches of the levels below it.
+__global__ __launch_bounds__(kThreads) void compact_live_kernel(const uint32_t *words, const uint32_t *order, uint32_t off, uint32_t n,
+                                                                const uint32_t *first_child, uint32_t *live) {
+    const uint32_t i = blockIdx.x * kThreads + threadIdx.x, k = i >> 3, c = i & 7u;
+    const bool valid = k < n;
+    const GroupLane g = group_lane(words, order + off, k, c, valid);
+    const bool keeps = valid && (g.interior ? live[first_child[off + k] + g.below] != 0u : g.pointer != SVO_VOXEL_OFFSET);
+    const uint32_t any = uint32_t(__ballot(keeps) >> (__lane_id() & ~7u)) & 0xFFu;
+    if (valid && c == 0) live[off + k] = (any || off + k == 0) ? 1u : 0u;
+}
+
+__global__ void compact_total_kernel(const uint32_t *number, const uint32_t *live, uint32_t n, uint32_t *status) {
+    status[kStLive] = number[n - 1] + live[n - 1];
+}
+
+__global__ __launch_bounds__(kThreads) void compact_emit_kernel(const uint32_t *words, const uint32_t *order, uint32_t n,
+                                                                const uint32_t *first_child, const uint32_t *live,
+                                                                const uint32_t *number, uint32_t n_out, uint32_t *image, uint32_t *perm) {
+    const uint32_t i = blockIdx.x * kThreads + threadIdx.x, k = i >> 3, c = i & 7u;
+    const bool valid = k < n;
+    const GroupLane g = group_lane(words, order, k, c, valid);
+    if (!valid || !live[k]) return;
+    uint32_t out = g.word;
+    if (g.interior) {
+        const uint32_t child = first_child[k] + g.below;
+        out = live[child] ? ((8u * number[child]) << 4 | (g.word & 15u)) : kEmptyWord;
+    }
+    const uint32_t at = 8u * number[k] + c;
+    if (at < n_out) {  // (always: n_out is the scan's total)
+        image[at] = out;
+        if (perm) perm[at] = order[k] + c;
+    }
+}
+
+enum Ev { kEvStart, kEvDiscover, kEvCheck, kEvPrune, kEvEmit, kEvEnd, kEvs };
+
+}  // namespace
+
+// Per-context workspace of the compaction (svo_ctx::compact): the image and five u32 per group.
+struct svo_compact_state {
+    uint32_t *image = nullptr;  // the compacted words before they are copied back
+    size_t image_items = 0;
+    uint32_t *order = nullptr, *first_child = nullptr, *new_of = nullptr, *live = nullptr, *number = nullptr;
+    size_t group_items = 0;
+    uint32_t *status = nullptr, *status_host = nullptr;  // kStWords words (device / pinned)
+    hipEvent_t ev[kEvs] = {};
+    bool timed = true;
+    float ms[SVO_COMPACT_TIMES] = {};
+
+    ~svo_compact_state() {
+        for (uint32_t *p : {image, order, first_child, new_of, live, number, status})
+            if (p) (void)hipFree(p);
+        if (status_host) (void)hipHostFree(status_host);
+        for (hipEvent_t e : ev)
+            if (e) (void)hipEventDestroy(e);
+    }
+};
+
+namespace {
+
+int ensure_state(svo_ctx *ctx, size_t words, size_t groups) {
+    if (!ctx->compact) {  // the context gets the state only when all of it exists (a failure frees what there is)
+        svo_workspace<svo_compact_state> fresh = svo_workspace_new<svo_compact_state>();
+        for (hipEvent_t &e : fresh->ev) HIP_TRY(ctx, hipEventCreate(&e));
+        HIP_TRY(ctx, hipHostMalloc((void **)&fresh->status_host, kStWords * sizeof(uint32_t), hipHostMallocDefault));
+        HIP_TRY(ctx, hipMalloc((void **)&fresh->status, kStWords * sizeof(uint32_t)));
+        ctx->compact = std::move(fresh);
+    }
+    svo_compact_state *s = ctx->compact.get();
+    int rc = svo_grow(ctx, &s->image_items, words, &s->image);
+    if (!rc) rc = svo_grow(ctx, &s->group_items, groups, &s->order, &s->first_child, &s->new_of, &s->live, &s->number);
+    return rc;
+}
+
+int read_status(svo_ctx *ctx) {
+    svo_compact_state *s = ctx->compact.get();
+    HIP_TRY(ctx, hipMemcpyAsync(s->status_host, s->status, kStWords * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return SVO_OK;
+}
+
+int malformed(svo_ctx *ctx, const std::string &why) { return svo_fail(ctx, SVO_ERR_STATE, "malformed tree: " + why); }
+
+}  // namespace
+
+extern "C" {
+
+int svo_nodes_compact(svo_ctx *ctx, const svo_compact_params *p, uint32_t *perm_out_dev, uint64_t *n_words_out) {
+    if (!ctx) return SVO_ERR_ARG;
+    if (n_words_out) *n_words_out = 0;
+    if (!p) return svo_fail(ctx, SVO_ERR_ARG, "null params");
+    if (!n_words_out) return svo_fail(ctx, SVO_ERR_ARG, "null n_words_out");
+    if (p->flags & ~SVO_COMPACT_PRUNE_EMPTY) return svo_fail(ctx, SVO_ERR_ARG, "unknown flag bits " + std::to_string(p->flags));
+    if (!ctx->store) return svo_fail(ctx, SVO_ERR_STATE, "svo_nodes_alloc / svo_nodes_bind_device not called");
+    if (ctx->adapt)
+        return svo_fail(ctx, SVO_ERR_STATE, "a device adaptive state is attached: its positions and hole stack index the layout "
+                                            "that a compaction replaces");
+    if (p->n_words < 8 || p->n_words % 8 || p->n_words > ctx->capacity)
+        return svo_fail(ctx, SVO_ERR_ARG, "n_words must be a positive multiple of 8 within the node buffer's capacity (got " +
+                                              std::to_string(p->n_words) + ", capacity " + std::to_string(ctx->capacity) + ")");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const double t0 = svo_now_ms();
+    // no pointer reaches a group behind 2^27, so the words behind it hold no reachable group
+    const uint32_t n_words = (uint32_t)std::min<uint64_t>(p->n_words, kMaxWords), cap = n_words / 8;
+    int rc = ensure_state(ctx, n_words, cap);
+    if (rc) return rc;
+    svo_compact_state *s = ctx->compact.get();
+    if (!s->timed) {  // the events are recorded again below: the last compaction's times are taken first, so that a refused
+        float ms[SVO_COMPACT_TIMES];  // call leaves svo_compact_timing with the times of the last one that ran
+        if ((rc = svo_compact_timing(ctx, ms))) return rc;
+    }
+    const uint32_t *st = s->status_host;
+    const bool prune = p->flags & SVO_COMPACT_PRUNE_EMPTY;
+
+    // the passes read the words: behind every earlier write to the store, whichever context issued it
+    if ((rc = svo_store_order_after_write(ctx))) return rc;
+    HIP_TRY(ctx, hipEventRecord(s->ev[kEvStart], ctx->stream));
+    HIP_TRY(ctx, hipMemsetAsync(s->status, 0, kStWords * sizeof(uint32_t), ctx->stream));
+    HIP_TRY(ctx, hipMemsetAsync(s->order, 0, sizeof(uint32_t), ctx->stream));  // level 1: group 0
+
+    // discover
+    std::vector<uint32_t> level_off;
+    uint32_t off = 0, n = 1;
+    for (uint32_t level = 1;; level++) {
+        level_off.push_back(off);
+        const uint32_t grid = svo_div_up(8ull * n, kThreads);
+        compact_count_kernel<<<grid, kThreads, 0, ctx->stream>>>(ctx->nodes, n_words, s->order + off, n, s->number, s->status);
+        HIP_TRY(ctx, hipGetLastError());
+        if ((rc = svo_build_scan_u32(ctx, s->number, n))) return rc;
+        compact_scatter_kernel<<<grid, kThreads, 0, ctx->stream>>>(ctx->nodes, s->order, off, n, s->number, s->first_child, cap, s->status);
+        HIP_TRY(ctx, hipGetLastError());
+        if ((rc = read_status(ctx))) return rc;
+        if (st[kStAlign]) return malformed(ctx, "an interior pointer at level " + std::to_string(level) + " is not a multiple of 8");
+        if (st[kStRange])
+            return malformed(ctx, "an interior pointer at level " + std::to_string(level) + " leaves the first n_words = " +
+                                      std::to_string(p->n_words) + " words");
+        const uint32_t next = st[kStNext];
+        if (uint64_t(off) + n + next > cap)
+            return malformed(ctx, "a group is reached twice (level " + std::to_string(level + 1) + " brings the groups reached to " +
+                                      std::to_string(uint64_t(off) + n + next) + ", more than n_words / 8)");
+        off += n;
+        if (!next) break;
+        if (level == kMaxLevels) return malformed(ctx, "the tree is deeper than " + std::to_string(kMaxLevels) + " levels");
+        n = next;
+    }
+    const uint32_t total = off, n_levels = (uint32_t)level_off.size();
+    level_off.push_back(total);
+    HIP_TRY(ctx, hipEventRecord(s->ev[kEvDiscover], ctx->stream));
+
+    // check
+    const uint32_t group_grid = svo_div_up(total, kThreads), word_grid = svo_div_up(8ull * total, kThreads);
+    compact_mark_kernel<<<group_grid, kThreads, 0, ctx->stream>>>(s->order, total, s->new_of);
+    compact_check_kernel<<<group_grid, kThreads, 0, ctx->stream>>>(s->order, total, s->new_of, s->status);
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, hipEventRecord(s->ev[kEvCheck], ctx->stream));
+
+    // prune
+    if (prune) {
+        for (uint32_t l = n_levels; l-- > 0;) {
+            const uint32_t m = level_off[l + 1] - level_off[l];
+            compact_live_kernel<<<svo_div_up(8ull * m, kThreads), kThreads, 0, ctx->stream>>>(ctx->nodes, s->order, level_off[l], m,
+                                                                                             s->first_child, s->live);
+        }
+        HIP_TRY(ctx, hipGetLastError());
+    } else {
+        HIP_TRY(ctx, hipMemsetD32Async((hipDeviceptr_t)s->live, 1, total, ctx->stream));
+    }
+    HIP_TRY(ctx, hipEventRecord(s->ev[kEvPrune], ctx->stream));
+
+    // emit
+    HIP_TRY(ctx, hipMemcpyAsync(s->number, s->live, total * sizeof(uint32_t), hipMemcpyDeviceToDevice, ctx->stream));
+    if ((rc = svo_build_scan_u32(ctx, s->number, total))) return rc;
+    compact_total_kernel<<<1, 1, 0, ctx->stream>>>(s->number, s->live, total, s->status);
+    HIP_TRY(ctx, hipGetLastError());
+    if ((rc = read_status(ctx))) return rc;
+    if (st[kStDup]) return malformed(ctx, "a group is reached twice");
+    const uint32_t n_out = 8u * st[kStLive];
+    if (!n_out || n_out > n_words) return svo_fail(ctx, SVO_ERR_HIP, "the live groups' scan is out of range");  // (never: live[0] = 1)
+    compact_emit_kernel<<<word_grid, kThreads, 0, ctx->stream>>>(ctx->nodes, s->order, total, s->first_child, s->live, s->number, n_out,
+                                                                s->image, perm_out_dev);
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, hipEventRecord(s->ev[kEvEmit], ctx->stream));
+
+    // copy back: behind every earlier write to the store (another context may have written while this one waited)
+    if ((rc = svo_store_order_after_write(ctx))) return rc;
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->nodes, s->image, size_t(n_out) * sizeof(uint32_t), hipMemcpyDeviceToDevice, ctx->stream));
+    if (p->n_words > n_out)
+        HIP_TRY(ctx, hipMemsetD32Async((hipDeviceptr_t)(ctx->nodes + n_out), (int)kEmptyWord, p->n_words - n_out, ctx->stream));
+    HIP_TRY(ctx, hipEventRecord(s->ev[kEvEnd], ctx->stream));
+    if ((rc = svo_store_note_write(ctx))) return rc;
+    *n_words_out = n_out;
+    s->ms[5] = float(svo_now_ms() - t0);
+    s->timed = false;  // (the copy is still in flight: svo_compact_timing reads the events)
+    return SVO_OK;
+}
+
+int svo_compact_timing(svo_ctx *ctx, float ms_out[SVO_COMPACT_TIMES]) {
+    if (!ctx || !ms_out) return SVO_ERR_ARG;
+    if (!ctx->compact) return svo_fail(ctx, SVO_ERR_STATE, "no tree compacted on this context yet");
+    svo_compact_state *s = ctx->compact.get();
+    if (!s->timed) {
+        HIP_TRY(ctx, hipSetDevice(ctx->device));
+        HIP_TRY(ctx, hipEventSynchronize(s->ev[kEvEnd]));
+        for (int k = 0; k < 5; k++) HIP_TRY(ctx, hipEventElapsedTime(&s->ms[k], s->ev[k], s->ev[k + 1]));
+        s->timed = true;
+    }
+    memcpy(ms_out, s->ms, sizeof s->ms);
+    return SVO_OK;
+}
+
+}  // extern "C"

@@ -63,6 +63,13 @@ class Gpu:
         self.check(lib().svo_edit_timing(self._h, ms))
         return list(ms)
 
+    def compact_timing(self):
+        """ms of the last Render.compact_nodes: discover, check, prune, emit, copy back (device events), host wall time
+        of the call (svo_compact_timing)"""
+        ms = (C.c_float * 6)()
+        self.check(lib().svo_compact_timing(self._h, ms))
+        return list(ms)
+
     def world_build_timing(self):
         """ms of the last CpuOctree.build / World.build_world: keys, sort, levels, count read-back, emit, mips (device
         events), chunk read-back, chunk files and root (CpuOctree.build: the tree), host wall time of the call

@@ -4,7 +4,7 @@ import ctypes as C
 import numpy as np
 import torch
 
-from ._lib import BuildParams, EditParams, Uniforms, lib
+from ._lib import BuildParams, CompactParams, EditParams, Uniforms, lib
 from .camera import camera_matrices
 
 F_PAUSE_ADAPTIVE, F_SHOW_STEPS, F_SHOW_HITS, F_SHADOWS, F_MISC_BOOL = 1, 2, 4, 8, 16
@@ -142,6 +142,25 @@ class Render:
         self.gpu.sync()  # (the inputs may be released by the caller)
         self.node_length = out.value
         return out.value
+
+    def compact_nodes(self, prune=True, with_perm=False):
+        """Compact the first node_length words of the node buffer in place (svo_nodes_compact): unreachable
+        groups go, with `prune` also the groups that hold nothing (a word pointing at one becomes the empty word), and
+        the rest comes out in the builder's breadth-first order; the freed tail holds the empty word.  Raises SvoError,
+        with nothing written, for a malformed tree or with a device adaptive state attached.  Sets node_length to the new
+        length and returns it; with_perm: (length, perm) with perm[new word] = old word as a device int32 tensor."""
+        dev = torch.device("cuda", self.gpu.device)
+        p = CompactParams()
+        p.flags = 1 if prune else 0
+        p.n_words = int(self.node_length)
+        perm = torch.empty(max(int(self.node_length), 1), dtype=torch.int32, device=dev) if with_perm else None
+        out = C.c_uint64()
+        if with_perm:
+            torch.cuda.current_stream(dev).synchronize()  # the tensor was made on torch's stream
+        self.gpu.check(lib().svo_nodes_compact(self.gpu._h, C.byref(p), perm.data_ptr() if with_perm else None, C.byref(out)))
+        self.gpu.sync()
+        self.node_length = out.value
+        return (out.value, perm[: out.value]) if with_perm else out.value
 
     def build_nodes_dense(self, grid, max_words=None):
         """Build the tree of a dense (side, side, side) colour grid indexed [x, y, z] (non-zero = voxel, low 24 bits the
