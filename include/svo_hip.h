@@ -428,6 +428,53 @@ int svo_nodes_compact(svo_ctx *ctx, const svo_compact_params *p, uint32_t *perm_
 #define SVO_COMPACT_TIMES 6
 int svo_compact_timing(svo_ctx *ctx, float ms_out[SVO_COMPACT_TIMES]);
 
+/* ---- the voxels of the tree in the node buffer listed on the device ----
+ * The inverse of svo_nodes_build.  Reads the first n_words words of the node buffer as a tree rooted at group 0.
+ * E = SVO_VOXEL_OFFSET << 4; a word is interior when word >> 4 < SVO_VOXEL_OFFSET and a *voxel* when word >> 4 >
+ * SVO_VOXEL_OFFSET; the low 4 bits (hit counters) never matter.  The root group's words are level 1, the words of the
+ * group an interior word at level l points at are level l + 1, and the child index is x * 4 + y * 2 + z.  A voxel word
+ * reached at level l is a cube whose minimum corner on the `depth` grid is cell << (depth - l).
+ * flags == 0: one entry per voxel word reachable from group 0: xyz (3 u32) its minimum corner on the `depth` grid, value =
+ * (word >> 4) - SVO_VOXEL_OFFSET (the 24-bit colour of built and edited trees), level = l (written when level_out_dev is
+ * not NULL).  The entries come in ascending Morton key of xyz at `depth` (the builder's key); the cubes are disjoint, so
+ * that is the depth-first order of the tree by child index and the order is total.  The output does not depend on where
+ * the groups sit in the buffer: a tree in put order, its compacted form and its canonical rebuild list identically, byte
+ * for byte, on every run (no atomics: the order is the contract).
+ * SVO_LIST_EXPAND: a voxel at level l < depth is replaced by its 8^(depth - l) cells of the `depth` grid, all with its
+ * value and level = depth, in Morton order: the result is a list that svo_nodes_build accepts at `depth`.
+ * xyz_out_dev == NULL is a count query: *n_out gets the number of entries, nothing else is written and max_voxels is
+ * ignored.  Otherwise xyz_out_dev (3 * max_voxels u32), value_out_dev (max_voxels u32) and level_out_dev (max_voxels u32,
+ * or NULL) are DEVICE pointers of which only the entries [0, *n_out) are written.  The node buffer is never written.
+ * Errors are decided before any write to the outputs and leave them and *n_out as they were.  SVO_ERR_ARG: NULL p or
+ * n_out; unknown flag bits; depth outside 1..21; NULL value_out_dev with xyz_out_dev given; n_words not a positive
+ * multiple of 8 or above the capacity; a voxel or an interior word at a level deeper than `depth` (svo_last_error names
+ * the deepest such level).  SVO_ERR_STATE: no node buffer; and the "malformed tree: ..." causes of svo_nodes_compact with
+ * its wording: an interior pointer that is not a multiple of 8 or with pointer + 8 > n_words, a tree deeper than 31
+ * levels, a group reached twice.  SVO_ERR_CAP, with the exact count in svo_last_error: more entries than max_voxels
+ * (not for a count query), or 2^31 or more (also for a count query).  Counts are 64 bits wide: the cubes of a tree are
+ * disjoint, so an expanded count is at most 8^21 = 2^63 and does not wrap; one level-1 voxel expanded at depth 21 is 2^60
+ * entries and SVO_ERR_CAP.  Of several causes the first in this order is reported: NULL p, NULL n_out, flag bits, depth,
+ * value_out_dev, no node buffer, n_words, the malformed-tree causes in svo_nodes_compact's order, the level deeper than
+ * `depth`, the count.  A device adaptive state attached to the context is no obstacle: the call only reads, and free
+ * groups are unreachable.
+ * Runs on the ctx stream behind the store's last write, whichever context issued it, and records no write of its own.
+ * Blocks once per level of the tree and once for the counts; the fill is enqueued (svo_sync before the outputs are read
+ * on another stream). */
+#define SVO_LIST_EXPAND 1u
+typedef struct svo_list_params {
+    uint32_t flags;       /* 0 or SVO_LIST_EXPAND */
+    uint32_t depth;       /* 1..21: the grid the coordinates are given on */
+    uint64_t n_words;     /* the tree: words [0, n_words) of the node buffer, rooted at group 0 */
+    uint64_t max_voxels;  /* room in the output arrays, in entries */
+} svo_list_params;
+int svo_nodes_list_voxels(svo_ctx *ctx, const svo_list_params *p, uint32_t *xyz_out_dev, uint32_t *value_out_dev,
+                          uint32_t *level_out_dev /* may be null */, uint64_t *n_out);
+/* Times (ms) of the last listing: [0] discover (with its per-level read-backs), [1] count (with its read-back), [2] offsets,
+ * [3] emit (device events; waits for the emit; 0 for a count query), [4] host wall time of the call.  A refused call
+ * leaves the times of the last listing that ran. */
+#define SVO_LIST_TIMES 5
+int svo_list_timing(svo_ctx *ctx, float ms_out[SVO_LIST_TIMES]);
+
 /* ---- mip-coloured chunk trees and streamable worlds built on the GPU ----
  * Inputs as svo_nodes_build: xyz n * 3 u32 and colours n u32 (0x00RRGGBB) or NULL, DEVICE pointers on the ctx's device;
  * the last voxel of a cell wins; a colour-0 voxel is an empty leaf on a path that exists.  A chunk tree is the host

@@ -288,6 +288,19 @@ class Render {  // render.rs:3-285
         gpu_.poll_wait();
         return new_words;
     }
+    // the voxels of the tree in the first n_words words of the node buffer listed on the GPU (svo_nodes_list_voxels,
+    // DESIGN.md 18), the inverse of build_nodes: xyz_dev (3 * max_voxels u32), values_dev (max_voxels) and levels_dev
+    // (max_voxels, or null) are DEVICE pointers; entries in ascending Morton order on the `depth` grid, with `expand` a
+    // leaf above depth as its cells; returns the entry count.  xyz_dev null: the count alone.  Throws, with nothing
+    // written, for a tree deeper than depth, a malformed tree or more entries than max_voxels.
+    uint64_t list_voxels(uint64_t n_words, uint32_t depth, uint32_t *xyz_dev, uint32_t *values_dev, uint64_t max_voxels,
+                         bool expand = false, uint32_t *levels_dev = nullptr) {
+        const svo_list_params p{expand ? SVO_LIST_EXPAND : 0u, depth, n_words, max_voxels};
+        uint64_t n = 0;
+        gpu_.check(svo_nodes_list_voxels(gpu_.ctx(), &p, xyz_dev, values_dev, levels_dev, &n));
+        gpu_.poll_wait();
+        return n;
+    }
     // the adaptive step on the GPU (svo_adaptive_*): attach once (SVO_OPT_SCAN_CLEARS_COUNTERS = 1, the
     // octree's words in the node buffer, `world` kept alive), then after each scan step() over the scan's own lists (or
     // explicit DEVICE lists); download() brings the host octree up to date

@@ -75,6 +75,16 @@ class CompactParams(C.Structure):
     ]
 
 
+class ListParams(C.Structure):
+    """svo_list_params: the voxels of the tree in the node buffer listed on the device (include/svo_hip.h)."""
+    _fields_ = [
+        ("flags", C.c_uint32),
+        ("depth", C.c_uint32),
+        ("n_words", C.c_uint64),
+        ("max_voxels", C.c_uint64),
+    ]
+
+
 class ChunkBuildParams(C.Structure):
     """svo_chunk_build_params: a mip-coloured tree or a chunked world built on the GPU (include/svo_hip.h)."""
     _fields_ = [
@@ -110,6 +120,7 @@ DEVICE_SYMBOLS = [
     "svo_cpu_octree_build", "svo_world_build", "svo_world_build_timing",
     "svo_nodes_edit", "svo_edit_timing",
     "svo_nodes_compact", "svo_compact_timing",
+    "svo_nodes_list_voxels", "svo_list_timing",
 ]
 HOST_SYMBOLS = [
     "svo_cpu_octree_new", "svo_cpu_octree_free", "svo_cpu_octree_len", "svo_cpu_octree_load_file",
@@ -207,6 +218,8 @@ def lib():
     sig("svo_edit_timing", C.c_int, vp, fp)
     sig("svo_nodes_compact", C.c_int, vp, C.POINTER(CompactParams), vp, C.POINTER(u64))
     sig("svo_compact_timing", C.c_int, vp, fp)
+    sig("svo_nodes_list_voxels", C.c_int, vp, C.POINTER(ListParams), vp, vp, vp, C.POINTER(u64))
+    sig("svo_list_timing", C.c_int, vp, fp)
     sig("svo_adaptive_attach", C.c_int, vp, vp, vp)
     sig("svo_adaptive_step", C.c_int, vp, vp, u32, vp, u32, C.POINTER(AdaptiveResult))
     sig("svo_adaptive_download", C.c_int, vp, vp)

@@ -569,6 +569,7 @@ int svo_ctx_destroy(svo_ctx *ctx) {
     ctx->adapt.reset();
     ctx->edit.reset();
     ctx->compact.reset();
+    ctx->list.reset();
     release_store(ctx);
     if (ctx->top_table) (void)hipFree(ctx->top_table);
     if (ctx->status) (void)hipFree(ctx->status);

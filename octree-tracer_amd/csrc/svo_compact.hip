@@ -28,33 +28,15 @@
 #include <vector>
 
 #include "svo_ctx.h"
-#include "svo_scan.h"  // (kThreads)
+#include "svo_group.h"  // (group_lane: 8 lanes per group)
+#include "svo_scan.h"   // (kThreads)
 
 namespace {
 
-constexpr uint32_t kEmptyWord = SVO_VOXEL_OFFSET << 4;
 constexpr uint64_t kMaxWords = SVO_VOXEL_OFFSET;  // 2^27: no pointer reaches further
 constexpr uint32_t kMaxLevels = 31;               // as svo_nodes_relayout and svo_nodes_max_depth
-enum Status { kStAlign, kStRange, kStNext, kStDup, kStLive, kStWords };  // the words read back
-
-// What the 8 lanes of a group know of it.  Every lane of the wave must get here: the mask is a ballot.
-struct GroupLane {
-    uint32_t word, pointer;
-    bool interior;
-    uint32_t mask;   // the group's interior lanes, bit c = child c
-    uint32_t below;  // how many of them are below this lane
-};
-
-__device__ inline GroupLane group_lane(const uint32_t *words, const uint32_t *order, uint32_t k, uint32_t c, bool valid) {
-    GroupLane g;
-    g.word = valid ? words[order[k] + c] : kEmptyWord;
-    g.pointer = g.word >> 4;
-    g.interior = valid && g.pointer < SVO_VOXEL_OFFSET;
-    const uint64_t all = __ballot(g.interior);
-    g.mask = uint32_t(all >> (__lane_id() & ~7u)) & 0xFFu;
-    g.below = __popc(g.mask & ((1u << c) - 1u));
-    return g;
-}
+// the words read back: the discovery's (svo_ctx.h), then the compaction's own
+enum Status { kStAlign = SVO_WALK_ALIGN, kStRange = SVO_WALK_RANGE, kStNext = SVO_WALK_NEXT, kStDup = SVO_WALK_DUP, kStLive = SVO_WALK_STATUS, kStWords };
 
 // The frontier order[0, n) (the caller passes order + off): count[k] = interior words of group k; the pointers are checked.
 __global__ __launch_bounds__(kThreads) void compact_count_kernel(const uint32_t *words, uint32_t n_words, const uint32_t *order,
@@ -168,16 +150,66 @@ int ensure_state(svo_ctx *ctx, size_t words, size_t groups) {
     return rc;
 }
 
-int read_status(svo_ctx *ctx) {
-    svo_compact_state *s = ctx->compact.get();
-    HIP_TRY(ctx, hipMemcpyAsync(s->status_host, s->status, kStWords * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+int read_status(svo_ctx *ctx, uint32_t *host, const uint32_t *dev, size_t words) {
+    HIP_TRY(ctx, hipMemcpyAsync(host, dev, words * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return SVO_OK;
+}
+int read_status(svo_ctx *ctx) {
+    svo_compact_state *s = ctx->compact.get();
+    return read_status(ctx, s->status_host, s->status, kStWords);
 }
 
 int malformed(svo_ctx *ctx, const std::string &why) { return svo_fail(ctx, SVO_ERR_STATE, "malformed tree: " + why); }
 
 }  // namespace
+
+// The discovery and the check of the tree in the first n_words_in words of the node buffer, for the compaction and for
+// svo_list.hip, on the ctx stream into the caller's workspace (svo_ctx.h).  Blocks once per level.
+int svo_tree_discover(svo_ctx *ctx, uint64_t n_words_in, svo_tree_walk *w, hipEvent_t discovered) {
+    // no pointer reaches a group behind 2^27, so the words behind it hold no reachable group
+    const uint32_t n_words = (uint32_t)std::min<uint64_t>(n_words_in, kMaxWords), cap = n_words / 8;
+    const uint32_t *st = w->status_host;
+    int rc;
+    HIP_TRY(ctx, hipMemsetAsync(w->order, 0, sizeof(uint32_t), ctx->stream));  // level 1: group 0
+
+    // discover
+    std::vector<uint32_t> &level_off = w->level_off;
+    level_off.clear();
+    uint32_t off = 0, n = 1;
+    for (uint32_t level = 1;; level++) {
+        level_off.push_back(off);
+        const uint32_t grid = svo_div_up(8ull * n, kThreads);
+        compact_count_kernel<<<grid, kThreads, 0, ctx->stream>>>(ctx->nodes, n_words, w->order + off, n, w->scan, w->status);
+        HIP_TRY(ctx, hipGetLastError());
+        if ((rc = svo_build_scan_u32(ctx, w->scan, n))) return rc;
+        compact_scatter_kernel<<<grid, kThreads, 0, ctx->stream>>>(ctx->nodes, w->order, off, n, w->scan, w->first_child, cap, w->status);
+        HIP_TRY(ctx, hipGetLastError());
+        if ((rc = read_status(ctx, w->status_host, w->status, w->status_words))) return rc;
+        if (st[kStAlign]) return malformed(ctx, "an interior pointer at level " + std::to_string(level) + " is not a multiple of 8");
+        if (st[kStRange])
+            return malformed(ctx, "an interior pointer at level " + std::to_string(level) + " leaves the first n_words = " +
+                                      std::to_string(n_words_in) + " words");
+        const uint32_t next = st[kStNext];
+        if (uint64_t(off) + n + next > cap)
+            return malformed(ctx, "a group is reached twice (level " + std::to_string(level + 1) + " brings the groups reached to " +
+                                      std::to_string(uint64_t(off) + n + next) + ", more than n_words / 8)");
+        off += n;
+        if (!next) break;
+        if (level == kMaxLevels) return malformed(ctx, "the tree is deeper than " + std::to_string(kMaxLevels) + " levels");
+        n = next;
+    }
+    const uint32_t total = off;
+    level_off.push_back(total);
+    if (discovered) HIP_TRY(ctx, hipEventRecord(discovered, ctx->stream));
+
+    // check (the verdict is in status[SVO_WALK_DUP] at the caller's next read-back)
+    const uint32_t group_grid = svo_div_up(total, kThreads);
+    compact_mark_kernel<<<group_grid, kThreads, 0, ctx->stream>>>(w->order, total, w->new_of);
+    compact_check_kernel<<<group_grid, kThreads, 0, ctx->stream>>>(w->order, total, w->new_of, w->status);
+    HIP_TRY(ctx, hipGetLastError());
+    return SVO_OK;
+}
 
 extern "C" {
 
@@ -212,42 +244,12 @@ int svo_nodes_compact(svo_ctx *ctx, const svo_compact_params *p, uint32_t *perm_
     if ((rc = svo_store_order_after_write(ctx))) return rc;
     HIP_TRY(ctx, hipEventRecord(s->ev[kEvStart], ctx->stream));
     HIP_TRY(ctx, hipMemsetAsync(s->status, 0, kStWords * sizeof(uint32_t), ctx->stream));
-    HIP_TRY(ctx, hipMemsetAsync(s->order, 0, sizeof(uint32_t), ctx->stream));  // level 1: group 0
-
-    // discover
-    std::vector<uint32_t> level_off;
-    uint32_t off = 0, n = 1;
-    for (uint32_t level = 1;; level++) {
-        level_off.push_back(off);
-        const uint32_t grid = svo_div_up(8ull * n, kThreads);
-        compact_count_kernel<<<grid, kThreads, 0, ctx->stream>>>(ctx->nodes, n_words, s->order + off, n, s->number, s->status);
-        HIP_TRY(ctx, hipGetLastError());
-        if ((rc = svo_build_scan_u32(ctx, s->number, n))) return rc;
-        compact_scatter_kernel<<<grid, kThreads, 0, ctx->stream>>>(ctx->nodes, s->order, off, n, s->number, s->first_child, cap, s->status);
-        HIP_TRY(ctx, hipGetLastError());
-        if ((rc = read_status(ctx))) return rc;
-        if (st[kStAlign]) return malformed(ctx, "an interior pointer at level " + std::to_string(level) + " is not a multiple of 8");
-        if (st[kStRange])
-            return malformed(ctx, "an interior pointer at level " + std::to_string(level) + " leaves the first n_words = " +
-                                      std::to_string(p->n_words) + " words");
-        const uint32_t next = st[kStNext];
-        if (uint64_t(off) + n + next > cap)
-            return malformed(ctx, "a group is reached twice (level " + std::to_string(level + 1) + " brings the groups reached to " +
-                                      std::to_string(uint64_t(off) + n + next) + ", more than n_words / 8)");
-        off += n;
-        if (!next) break;
-        if (level == kMaxLevels) return malformed(ctx, "the tree is deeper than " + std::to_string(kMaxLevels) + " levels");
-        n = next;
-    }
-    const uint32_t total = off, n_levels = (uint32_t)level_off.size();
-    level_off.push_back(total);
-    HIP_TRY(ctx, hipEventRecord(s->ev[kEvDiscover], ctx->stream));
-
-    // check
-    const uint32_t group_grid = svo_div_up(total, kThreads), word_grid = svo_div_up(8ull * total, kThreads);
-    compact_mark_kernel<<<group_grid, kThreads, 0, ctx->stream>>>(s->order, total, s->new_of);
-    compact_check_kernel<<<group_grid, kThreads, 0, ctx->stream>>>(s->order, total, s->new_of, s->status);
-    HIP_TRY(ctx, hipGetLastError());
+    // discover and check
+    svo_tree_walk walk{s->order, s->first_child, s->new_of, s->number, s->status, s->status_host, kStWords, {}};
+    if ((rc = svo_tree_discover(ctx, p->n_words, &walk, s->ev[kEvDiscover]))) return rc;
+    const std::vector<uint32_t> &level_off = walk.level_off;
+    const uint32_t n_levels = (uint32_t)level_off.size() - 1, total = level_off[n_levels];
+    const uint32_t word_grid = svo_div_up(8ull * total, kThreads);
     HIP_TRY(ctx, hipEventRecord(s->ev[kEvCheck], ctx->stream));
 
     // prune

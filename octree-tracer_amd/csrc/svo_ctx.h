@@ -1,6 +1,6 @@
 // svo_ctx.h -- the device context behind the opaque `svo_ctx` of include/svo_hip.h, and the host helpers of the files that
 // use it: svo_abi.cpp (trace / scan dispatch), svo_comm.cpp (RCCL frame gather) and the GPU tree passes (svo_proc.hip,
-// svo_build.hip, svo_edit.hip, svo_compact.hip, svo_adapt.hip).  Shared by the passes: svo_grow / svo_grow_pinned / svo_grow_keep (workspaces), the builder's sort
+// svo_build.hip, svo_edit.hip, svo_compact.hip, svo_list.hip, svo_adapt.hip).  Shared by the passes: svo_grow / svo_grow_pinned / svo_grow_keep (workspaces), the builder's sort
 // and scan, svo_world_writer (a generated world's directory); svo_scan.h, svo_mip.h and svo_morton.h hold the device pieces,
 // svo_rules.h the walks and rules that svo_host.cpp and svo_adapt.hip both run.
 // Internal: not part of the boundary.
@@ -41,6 +41,7 @@ struct svo_build_state;
 struct svo_adapt_state;
 struct svo_edit_state;
 struct svo_compact_state;
+struct svo_list_state;
 template <typename T>
 using svo_workspace = std::unique_ptr<T, void (*)(T *)>;
 template <typename T>
@@ -123,6 +124,7 @@ struct svo_ctx {
     svo_workspace<svo_adapt_state> adapt{nullptr, nullptr};  // device adaptive state (svo_adapt.hip)
     svo_workspace<svo_edit_state> edit{nullptr, nullptr};    // in-place edits' workspace (svo_edit.hip)
     svo_workspace<svo_compact_state> compact{nullptr, nullptr};  // compaction's workspace (svo_compact.hip)
+    svo_workspace<svo_list_state> list{nullptr, nullptr};  // voxel listing's workspace (svo_list.hip)
     std::string err;
 };
 
@@ -211,6 +213,23 @@ struct svo_build_leaves {
 int svo_build_check_list(svo_ctx *ctx, const uint32_t *depth, const uint32_t *xyz, size_t n);
 int svo_build_list_leaves(svo_ctx *ctx, const uint32_t *xyz, const uint32_t *colours, size_t n, uint32_t depth,
                           uint32_t default_colour, svo_build_leaves *out);
+// svo_compact.hip
+// The discovery of the tree in the first n_words words of the node buffer, for the
+// compaction and the voxel listing (svo_list.hip), on the ctx stream.  The caller owns the workspace: order, first_child,
+// new_of and scan of n_words / 8 u32 each, and status words (device / pinned mirror) that it has zeroed on the stream;
+// the first SVO_WALK_STATUS of them are the discovery's, status_words of them come back once per level.  Afterwards
+// order[level_off[l], level_off[l + 1]) holds the old group starts of level l + 1 in the order of their parents,
+// first_child[k] the index in order of group k's first interior child, and level_off has one entry per level and the
+// total.  `discovered` (or null) is recorded before the check; the check's verdict is status[SVO_WALK_DUP] at the
+// caller's next read-back.  Malformed trees are refused here with the compaction's messages (SVO_ERR_STATE).
+enum { SVO_WALK_ALIGN, SVO_WALK_RANGE, SVO_WALK_NEXT, SVO_WALK_DUP, SVO_WALK_STATUS };
+struct svo_tree_walk {
+    uint32_t *order, *first_child, *new_of, *scan;
+    uint32_t *status, *status_host;
+    size_t status_words;
+    std::vector<uint32_t> level_off;
+};
+int svo_tree_discover(svo_ctx *ctx, uint64_t n_words, svo_tree_walk *w, hipEvent_t discovered);
 // The one writer of a generated world's directory (svo_build.hip), for svo_world_build and
 // svo_world_generate: create() makes the directory and the empty root; add_chunk() writes <id>.bin (id = SVO_CHUNK_OFFSET
 // / 2 + i) from `bytes` in the <id>.bin layout, keeps the chunk in w as a node-less CpuOctree carrying its top_mip (the

@@ -1,0 +1,351 @@
+// svo_list.hip -- the voxels of the tree in the node buffer listed on the device: the inverse of the
+// builder.  One entry per voxel word reachable from group 0, in ascending Morton order of its minimum corner on the
+// `depth` grid, which is the depth-first order of the tree by child index; with SVO_LIST_EXPAND a voxel above `depth`
+// becomes its cells of the `depth` grid.  No sort and no atomics: counts bottom-up, offsets top-down, so the list does
+// not depend on where the groups sit in the buffer or on the run.  Every tree kernel gives 8 lanes to a group, one
+// word per lane (svo_group.h); sums and prefixes over a group are cross-lane operations inside its 8-lane segment.
+//
+//   discover  svo_tree_discover (svo_compact.hip): order, first_child, the levels; pointer checks, the reached-twice check
+//   count     bottom-up, one launch per level: cnt[k] = sum over the group's words of the entries a voxel gives (1, or
+//             8^(depth - level) with expand), cnt[child] for an interior word, 0 for the empty word; rcnt[k] the same
+//             for the voxels above `depth` that the expansion handles as records.  A level below `depth` only notes
+//             whether it holds anything.  cnt[0], rcnt[0], those notes and the check's verdict come back in one copy:
+//             the last point of failure
+//   offsets   top-down, one launch per level: an exclusive prefix over the 8 lanes gives every word its start; an
+//             interior word hands it to its child group with the child's Morton prefix (a leading 1, then 3 bits per
+//             level: the level is the position of that 1)
+//   emit      one launch over all groups: a voxel lane writes its entry at its start, or, expanded and above `depth`, its
+//             record (start, key, value) at its record start: the records are sorted by start.  A second launch, one
+//             lane per output entry, finds the record that covers the entry by binary search and writes the cell whose
+//             Morton suffix is the entry's distance from the record's start
+//
+// Every error is decided before the offsets, so it leaves the outputs as they were.  The node buffer is only read.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "svo_ctx.h"
+#include "svo_group.h"   // (group_lane: 8 lanes per group)
+#include "svo_morton.h"  // (morton_decode)
+#include "svo_scan.h"    // (kThreads)
+
+namespace {
+
+constexpr uint64_t kMaxWords = SVO_VOXEL_OFFSET;  // 2^27: no pointer reaches further
+constexpr uint64_t kMaxEntries = 1ull << 31;
+// the words read back: the discovery's (svo_ctx.h), the root's counts, one note per level below `depth`
+enum Status { kStCountLo = SVO_WALK_STATUS, kStCountHi, kStRecords, kStPad, kStDeep, kStWords = kStDeep + 32 };
+
+// the level of the words of a group with Morton prefix `key`, or of a word with cell key `key`, minus one
+__device__ inline uint32_t key_bits(uint64_t key) { return (63u - (uint32_t)__clzll((long long)key)) / 3u; }
+
+// What a word adds to its group's entry and record counts; `leaf` entries per voxel of this level, `coarse`: such a
+// voxel is a record.  Every lane of the wave must get here with group_lane's result.
+struct Share {
+    bool voxel;
+    uint64_t entries;
+    uint32_t records;
+};
+
+__device__ inline Share word_share(const GroupLane &g, bool valid, uint32_t child, uint64_t leaf, uint32_t coarse, const uint64_t *cnt,
+                                   const uint32_t *rcnt) {
+    Share s;
+    s.voxel = valid && g.pointer > SVO_VOXEL_OFFSET;
+    s.entries = s.voxel ? leaf : 0u;
+    s.records = s.voxel ? coarse : 0u;
+    if (g.interior) {  // (valid)
+        s.entries = cnt[child];
+        s.records = rcnt[child];
+    }
+    return s;
+}
+
+// exclusive prefix of v over the 8 lanes of a group
+__device__ inline uint32_t prefix8(uint32_t v, uint32_t c) {
+    uint32_t inc = v;
+    for (uint32_t d = 1; d < 8; d <<= 1) {
+        const uint32_t t = __shfl_up(inc, d, 8);
+        if (c >= d) inc += t;
+    }
+    return inc - v;
+}
+
+// The level order[off, off + n), behind the launches of the levels below it.  With `deep` the level lies below `depth`:
+// it counts nothing and notes whether it holds a voxel or an interior word (every writer stores the same value).
+__global__ __launch_bounds__(kThreads) void list_count_kernel(const uint32_t *words, const uint32_t *order, uint32_t off, uint32_t n,
+                                                              const uint32_t *first_child, uint64_t leaf, uint32_t coarse,
+                                                              uint64_t *cnt, uint32_t *rcnt, uint32_t *deep) {
+    const uint32_t i = blockIdx.x * kThreads + threadIdx.x, k = i >> 3, c = i & 7u;
+    const bool valid = k < n;
+    const GroupLane g = group_lane(words, order + off, k, c, valid);
+    uint64_t v = 0;
+    uint32_t r = 0;
+    if (deep) {
+        if (valid && g.pointer != SVO_VOXEL_OFFSET) *deep = 1u;
+    } else {
+        const Share s = word_share(g, valid, g.interior ? first_child[off + k] + g.below : 0u, leaf, coarse, cnt, rcnt);
+        v = s.entries;
+        r = s.records;
+    }
+    for (uint32_t d = 1; d < 8; d <<= 1) {
+        v += __shfl_xor(v, d, 8);
+        r += __shfl_xor(r, d, 8);
+    }
+    if (valid && c == 0) {
+        cnt[off + k] = v;
+        rcnt[off + k] = r;
+    }
+}
+
+// the root's counts into the status words; its start, record start and Morton prefix
+__global__ void list_root_kernel(const uint64_t *cnt, const uint32_t *rcnt, uint32_t *status, uint32_t *start, uint32_t *rstart,
+                                 uint64_t *key) {
+    status[kStCountLo] = uint32_t(cnt[0]);
+    status[kStCountHi] = uint32_t(cnt[0] >> 32);
+    status[kStRecords] = rcnt[0];
+    start[0] = 0u;
+    rstart[0] = 0u;
+    key[0] = 1u;
+}
+
+// The level order[off, off + n), behind the launch of the level above it: the groups below get their starts and prefixes.
+__global__ __launch_bounds__(kThreads) void list_offsets_kernel(const uint32_t *words, const uint32_t *order, uint32_t off, uint32_t n,
+                                                                const uint32_t *first_child, uint64_t leaf, uint32_t coarse,
+                                                                const uint64_t *cnt, const uint32_t *rcnt, uint32_t *start,
+                                                                uint32_t *rstart, uint64_t *key) {
+    const uint32_t i = blockIdx.x * kThreads + threadIdx.x, k = i >> 3, c = i & 7u;
+    const bool valid = k < n;
+    const GroupLane g = group_lane(words, order + off, k, c, valid);
+    const uint32_t child = g.interior ? first_child[off + k] + g.below : 0u;
+    const Share s = word_share(g, valid, child, leaf, coarse, cnt, rcnt);
+    const uint32_t at = prefix8(uint32_t(s.entries), c), rat = prefix8(s.records, c);  // (the total is below 2^31)
+    if (g.interior) {
+        start[child] = start[off + k] + at;
+        rstart[child] = rstart[off + k] + rat;
+        key[child] = key[off + k] << 3 | c;
+    }
+}
+
+struct ListOut {
+    uint32_t *xyz, *value, *level;  // level may be null
+    uint32_t n;                     // entries
+    uint32_t *rec_start, *rec_value;
+    uint64_t *rec_key;
+    uint32_t n_rec;
+};
+
+__device__ inline void write_entry(const ListOut &out, uint32_t at, uint64_t cell, uint32_t bits, uint32_t depth, uint32_t value,
+                                   uint32_t level) {
+    uint32_t x, y, z;
+    morton_decode<uint64_t>(cell, bits, x, y, z);
+    const uint32_t shift = depth - bits;
+    out.xyz[3ull * at] = x << shift;
+    out.xyz[3ull * at + 1] = y << shift;
+    out.xyz[3ull * at + 2] = z << shift;
+    out.value[at] = value;
+    if (out.level) out.level[at] = level;
+}
+
+// All groups of the levels 1..depth, order[0, n).
+__global__ __launch_bounds__(kThreads) void list_emit_kernel(const uint32_t *words, const uint32_t *order, uint32_t n,
+                                                             const uint32_t *first_child, const uint64_t *cnt, const uint32_t *rcnt,
+                                                             const uint32_t *start, const uint32_t *rstart, const uint64_t *key,
+                                                             uint32_t depth, bool expand, ListOut out) {
+    const uint32_t i = blockIdx.x * kThreads + threadIdx.x, k = i >> 3, c = i & 7u;
+    const bool valid = k < n;
+    const GroupLane g = group_lane(words, order, k, c, valid);
+    const uint64_t prefix = valid ? key[k] : 1u;
+    const uint32_t level = min(key_bits(prefix) + 1u, depth);  // (at most depth: deeper groups are not launched)
+    const bool coarse = expand && level < depth;
+    const Share s = word_share(g, valid, g.interior ? first_child[k] + g.below : 0u, expand ? 1ull << 3u * (depth - level) : 1ull,
+                               coarse ? 1u : 0u, cnt, rcnt);
+    const uint32_t at = prefix8(uint32_t(s.entries), c), rat = prefix8(s.records, c);
+    if (!s.voxel) return;
+    const uint64_t cell = prefix << 3 | c;
+    const uint32_t value = g.pointer - SVO_VOXEL_OFFSET;
+    if (coarse) {
+        const uint32_t j = rstart[k] + rat;
+        if (j < out.n_rec) {  // (always: n_rec is the root's count)
+            out.rec_start[j] = start[k] + at;
+            out.rec_value[j] = value;
+            out.rec_key[j] = cell;
+        }
+    } else if (start[k] + at < out.n) {  // (always: n is the root's count)
+        write_entry(out, start[k] + at, cell ^ (1ull << 3u * level), level, depth, value, level);
+    }
+}
+
+// One lane per output entry: the cells of the records.  An entry that no record covers is a voxel at `depth`, written above.
+__global__ __launch_bounds__(kThreads) void list_expand_kernel(uint32_t depth, ListOut out) {
+    const uint32_t i = blockIdx.x * kThreads + threadIdx.x;
+    if (i >= out.n) return;
+    uint32_t lo = 0, hi = out.n_rec;  // the last record with rec_start <= i is lo - 1
+    while (lo < hi) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (out.rec_start[mid] <= i) lo = mid + 1;
+        else hi = mid;
+    }
+    if (!lo) return;
+    const uint64_t cell = out.rec_key[lo - 1];
+    const uint32_t level = key_bits(cell), below = 3u * (depth - level), suffix = i - out.rec_start[lo - 1];
+    if (suffix >= 1ull << below) return;
+    write_entry(out, i, (cell ^ (1ull << 3u * level)) << below | suffix, depth, depth, out.rec_value[lo - 1], depth);
+}
+
+enum Ev { kEvStart, kEvDiscover, kEvCount, kEvOffsets, kEvEmit, kEvs };
+
+}  // namespace
+
+// Per-context workspace of the listing (svo_ctx::list): eleven u32 per group, four per record.
+struct svo_list_state {
+    uint32_t *order = nullptr, *first_child = nullptr, *new_of = nullptr, *scan = nullptr;  // the discovery's
+    uint32_t *rcnt = nullptr, *start = nullptr, *rstart = nullptr;
+    uint64_t *cnt = nullptr, *key = nullptr;
+    size_t group_items = 0;
+    uint32_t *rec_start = nullptr, *rec_value = nullptr;
+    uint64_t *rec_key = nullptr;
+    size_t rec_items = 0;
+    uint32_t *status = nullptr, *status_host = nullptr;  // kStWords words (device / pinned)
+    hipEvent_t ev[kEvs] = {};
+    bool timed = true;
+    float ms[SVO_LIST_TIMES] = {};
+
+    ~svo_list_state() {
+        for (void *p : {(void *)order, (void *)first_child, (void *)new_of, (void *)scan, (void *)rcnt, (void *)start, (void *)rstart,
+                        (void *)cnt, (void *)key, (void *)rec_start, (void *)rec_value, (void *)rec_key, (void *)status})
+            if (p) (void)hipFree(p);
+        if (status_host) (void)hipHostFree(status_host);
+        for (hipEvent_t e : ev)
+            if (e) (void)hipEventDestroy(e);
+    }
+};
+
+namespace {
+
+int ensure_state(svo_ctx *ctx, size_t groups) {
+    if (!ctx->list) {  // the context gets the state only when all of it exists (a failure frees what there is)
+        svo_workspace<svo_list_state> fresh = svo_workspace_new<svo_list_state>();
+        for (hipEvent_t &e : fresh->ev) HIP_TRY(ctx, hipEventCreate(&e));
+        HIP_TRY(ctx, hipHostMalloc((void **)&fresh->status_host, kStWords * sizeof(uint32_t), hipHostMallocDefault));
+        HIP_TRY(ctx, hipMalloc((void **)&fresh->status, kStWords * sizeof(uint32_t)));
+        ctx->list = std::move(fresh);
+    }
+    svo_list_state *s = ctx->list.get();
+    return svo_grow(ctx, &s->group_items, groups, &s->order, &s->first_child, &s->new_of, &s->scan, &s->rcnt, &s->start, &s->rstart,
+                    &s->cnt, &s->key);
+}
+
+}  // namespace
+
+extern "C" {
+
+int svo_nodes_list_voxels(svo_ctx *ctx, const svo_list_params *p, uint32_t *xyz_out_dev, uint32_t *value_out_dev,
+                          uint32_t *level_out_dev, uint64_t *n_out) {
+    if (!ctx) return SVO_ERR_ARG;
+    if (!p) return svo_fail(ctx, SVO_ERR_ARG, "null params");
+    if (!n_out) return svo_fail(ctx, SVO_ERR_ARG, "null n_out");
+    if (p->flags & ~SVO_LIST_EXPAND) return svo_fail(ctx, SVO_ERR_ARG, "unknown flag bits " + std::to_string(p->flags));
+    if (p->depth < 1 || p->depth > 21) return svo_fail(ctx, SVO_ERR_ARG, "depth must be 1..21 (got " + std::to_string(p->depth) + ")");
+    if (xyz_out_dev && !value_out_dev) return svo_fail(ctx, SVO_ERR_ARG, "null value_out_dev with xyz_out_dev given");
+    if (!ctx->store) return svo_fail(ctx, SVO_ERR_STATE, "svo_nodes_alloc / svo_nodes_bind_device not called");
+    if (p->n_words < 8 || p->n_words % 8 || p->n_words > ctx->capacity)
+        return svo_fail(ctx, SVO_ERR_ARG, "n_words must be a positive multiple of 8 within the node buffer's capacity (got " +
+                                              std::to_string(p->n_words) + ", capacity " + std::to_string(ctx->capacity) + ")");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const double t0 = svo_now_ms();
+    const uint32_t n_words = (uint32_t)std::min<uint64_t>(p->n_words, kMaxWords), depth = p->depth;
+    const bool expand = p->flags & SVO_LIST_EXPAND;
+    int rc = ensure_state(ctx, n_words / 8);
+    if (rc) return rc;
+    svo_list_state *s = ctx->list.get();
+    if (!s->timed) {  // the events are recorded again below: the last listing's times are taken first, so that a refused
+        float ms[SVO_LIST_TIMES];  // call leaves svo_list_timing with the times of the last one that ran
+        if ((rc = svo_list_timing(ctx, ms))) return rc;
+    }
+    const uint32_t *st = s->status_host;
+
+    // the passes read the words: behind every earlier write to the store, whichever context issued it
+    if ((rc = svo_store_order_after_write(ctx))) return rc;
+    HIP_TRY(ctx, hipEventRecord(s->ev[kEvStart], ctx->stream));
+    HIP_TRY(ctx, hipMemsetAsync(s->status, 0, kStWords * sizeof(uint32_t), ctx->stream));
+
+    // discover and check
+    svo_tree_walk walk{s->order, s->first_child, s->new_of, s->scan, s->status, s->status_host, kStWords, {}};
+    if ((rc = svo_tree_discover(ctx, p->n_words, &walk, s->ev[kEvDiscover]))) return rc;
+    const std::vector<uint32_t> &level_off = walk.level_off;  // level l: order[level_off[l - 1], level_off[l])
+    const uint32_t n_levels = (uint32_t)level_off.size() - 1, listed = std::min(n_levels, depth);
+    const auto leaf = [&](uint32_t level) { return expand ? 1ull << 3u * (depth - level) : 1ull; };
+    const auto coarse = [&](uint32_t level) { return expand && level < depth ? 1u : 0u; };
+
+    // count
+    for (uint32_t l = n_levels; l >= 1; l--) {
+        const uint32_t off = level_off[l - 1], m = level_off[l] - off;
+        const bool deep = l > depth;
+        list_count_kernel<<<svo_div_up(8ull * m, kThreads), kThreads, 0, ctx->stream>>>(
+            ctx->nodes, s->order, off, m, s->first_child, deep ? 0ull : leaf(l), deep ? 0u : coarse(l), s->cnt, s->rcnt,
+            deep ? s->status + kStDeep + l : nullptr);
+    }
+    list_root_kernel<<<1, 1, 0, ctx->stream>>>(s->cnt, s->rcnt, s->status, s->start, s->rstart, s->key);
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, hipMemcpyAsync(s->status_host, s->status, kStWords * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    if (st[SVO_WALK_DUP]) return svo_fail(ctx, SVO_ERR_STATE, "malformed tree: a group is reached twice");
+    for (uint32_t l = n_levels; l > depth; l--)
+        if (st[kStDeep + l])
+            return svo_fail(ctx, SVO_ERR_ARG, "the tree holds a voxel or an interior word at level " + std::to_string(l) +
+                                                  ", deeper than depth = " + std::to_string(depth));
+    const uint64_t count = uint64_t(st[kStCountHi]) << 32 | st[kStCountLo];
+    const uint32_t n_rec = st[kStRecords];
+    if (count >= kMaxEntries) return svo_fail(ctx, SVO_ERR_CAP, "the list has " + std::to_string(count) + " entries, 2^31 or more");
+    if (xyz_out_dev && count > p->max_voxels)
+        return svo_fail(ctx, SVO_ERR_CAP, "the list has " + std::to_string(count) + " entries, more than max_voxels = " +
+                                              std::to_string(p->max_voxels));
+    HIP_TRY(ctx, hipEventRecord(s->ev[kEvCount], ctx->stream));
+
+    if (xyz_out_dev && count) {
+        if ((rc = svo_grow(ctx, &s->rec_items, (size_t)n_rec, &s->rec_start, &s->rec_value, &s->rec_key))) return rc;
+        // offsets: the levels that have listed levels below them
+        for (uint32_t l = 1; l < listed; l++) {
+            const uint32_t off = level_off[l - 1], m = level_off[l] - off;
+            list_offsets_kernel<<<svo_div_up(8ull * m, kThreads), kThreads, 0, ctx->stream>>>(
+                ctx->nodes, s->order, off, m, s->first_child, leaf(l), coarse(l), s->cnt, s->rcnt, s->start, s->rstart, s->key);
+        }
+        HIP_TRY(ctx, hipGetLastError());
+        HIP_TRY(ctx, hipEventRecord(s->ev[kEvOffsets], ctx->stream));
+
+        // emit
+        const ListOut out{xyz_out_dev, value_out_dev, level_out_dev, (uint32_t)count, s->rec_start, s->rec_value, s->rec_key, n_rec};
+        const uint32_t m = level_off[listed];
+        list_emit_kernel<<<svo_div_up(8ull * m, kThreads), kThreads, 0, ctx->stream>>>(ctx->nodes, s->order, m, s->first_child, s->cnt,
+                                                                                       s->rcnt, s->start, s->rstart, s->key, depth, expand,
+                                                                                       out);
+        if (n_rec) list_expand_kernel<<<svo_div_up(count, kThreads), kThreads, 0, ctx->stream>>>(depth, out);
+        HIP_TRY(ctx, hipGetLastError());
+    } else {
+        HIP_TRY(ctx, hipEventRecord(s->ev[kEvOffsets], ctx->stream));
+    }
+    HIP_TRY(ctx, hipEventRecord(s->ev[kEvEmit], ctx->stream));
+    *n_out = count;
+    s->ms[4] = float(svo_now_ms() - t0);
+    s->timed = false;  // (the emit is still in flight: svo_list_timing reads the events)
+    return SVO_OK;
+}
+
+int svo_list_timing(svo_ctx *ctx, float ms_out[SVO_LIST_TIMES]) {
+    if (!ctx || !ms_out) return SVO_ERR_ARG;
+    if (!ctx->list) return svo_fail(ctx, SVO_ERR_STATE, "no tree listed on this context yet");
+    svo_list_state *s = ctx->list.get();
+    if (!s->timed) {
+        HIP_TRY(ctx, hipSetDevice(ctx->device));
+        HIP_TRY(ctx, hipEventSynchronize(s->ev[kEvEmit]));
+        for (int k = 0; k < 4; k++) HIP_TRY(ctx, hipEventElapsedTime(&s->ms[k], s->ev[k], s->ev[k + 1]));
+        s->timed = true;
+    }
+    memcpy(ms_out, s->ms, sizeof s->ms);
+    return SVO_OK;
+}
+
+}  // extern "C"

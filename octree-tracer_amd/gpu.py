@@ -70,6 +70,13 @@ class Gpu:
         self.check(lib().svo_compact_timing(self._h, ms))
         return list(ms)
 
+    def list_timing(self):
+        """ms of the last Render.list_voxels call into the library (its fill, or its count query when the list was empty
+        or refused): discover, count, offsets, emit (device events), host wall time of the call (svo_list_timing)"""
+        ms = (C.c_float * 5)()
+        self.check(lib().svo_list_timing(self._h, ms))
+        return list(ms)
+
     def world_build_timing(self):
         """ms of the last CpuOctree.build / World.build_world: keys, sort, levels, count read-back, emit, mips (device
         events), chunk read-back, chunk files and root (CpuOctree.build: the tree), host wall time of the call

@@ -4,7 +4,7 @@ import ctypes as C
 import numpy as np
 import torch
 
-from ._lib import BuildParams, CompactParams, EditParams, Uniforms, lib
+from ._lib import BuildParams, CompactParams, EditParams, ListParams, Uniforms, lib
 from .camera import camera_matrices
 
 F_PAUSE_ADAPTIVE, F_SHOW_STEPS, F_SHOW_HITS, F_SHADOWS, F_MISC_BOOL = 1, 2, 4, 8, 16
@@ -161,6 +161,34 @@ class Render:
         self.gpu.sync()
         self.node_length = out.value
         return (out.value, perm[: out.value]) if with_perm else out.value
+
+    def list_voxels(self, depth=None, expand=False, with_levels=False):
+        """The voxels of the tree in the first node_length words of the node buffer, listed on the GPU (svo_nodes_list_voxels,
+        DESIGN.md 18): the inverse of build_nodes.  Returns (coords, colours), device tensors (N, 3) int32 and N int32 ready
+        for build_nodes, edit_nodes, CpuOctree.build and World.build_world: one entry per coloured leaf, coords its minimum
+        corner on the `depth` grid, in ascending Morton order, the same for any layout of the same tree.  expand: a leaf above
+        `depth` becomes its cells of the `depth` grid.  with_levels: (coords, colours, levels), the level each leaf was
+        found at (`depth` for expanded cells).  depth=None: the depth declared for this tree (16 unless a build, an edit
+        or from_world raised it).  Raises SvoError for a tree deeper than `depth`, a malformed tree or 2^31 entries or
+        more.  The node buffer is only read."""
+        dev = torch.device("cuda", self.gpu.device)
+        p = ListParams()
+        p.flags = 1 if expand else 0
+        p.depth = max(0, int(getattr(self, "_declared_depth", 16) if depth is None else depth))
+        p.n_words = int(self.node_length)
+        n = C.c_uint64()
+        self.gpu.check(lib().svo_nodes_list_voxels(self.gpu._h, C.byref(p), None, None, None, C.byref(n)))  # the count
+        count = n.value
+        coords = torch.empty((count, 3), dtype=torch.int32, device=dev)
+        colours = torch.empty(count, dtype=torch.int32, device=dev)
+        levels = torch.empty(count, dtype=torch.int32, device=dev) if with_levels else None
+        if count:
+            p.max_voxels = count
+            torch.cuda.current_stream(dev).synchronize()  # the tensors were made on torch's stream
+            self.gpu.check(lib().svo_nodes_list_voxels(self.gpu._h, C.byref(p), coords.data_ptr(), colours.data_ptr(),
+                                                       levels.data_ptr() if with_levels else None, C.byref(n)))
+            self.gpu.sync()
+        return (coords, colours, levels) if with_levels else (coords, colours)
 
     def build_nodes_dense(self, grid, max_words=None):
         """Build the tree of a dense (side, side, side) colour grid indexed [x, y, z] (non-zero = voxel, low 24 bits the

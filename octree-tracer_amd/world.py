@@ -66,6 +66,15 @@ class World:
             gpu.check(lib().svo_world_build(gpu._h, w._h, xyz, col, n, C.byref(p)))
         return World.load_world(path)
 
+    @staticmethod
+    def save_nodes(path, render, depth, world_depth=1):
+        """Save the tree in `render`'s node buffer as a new streamable world in directory `path` (which must not exist):
+        Render.list_voxels(depth, expand=True) followed by build_world of that list; nothing but the chunk
+        files leaves the device.  A tree deeper than `depth` raises SvoError and nothing is created.  Returns
+        World.load_world(path)."""
+        coords, colours = render.list_voxels(depth, expand=True)
+        return World.build_world(path, render.gpu, coords, depth, colours, world_depth)
+
     def __del__(self):
         if getattr(self, "_h", None) and lib is not None:  # (module globals are gone at interpreter exit)
             lib().svo_world_free(self._h)
