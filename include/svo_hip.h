@@ -475,6 +475,53 @@ int svo_nodes_list_voxels(svo_ctx *ctx, const svo_list_params *p, uint32_t *xyz_
 #define SVO_LIST_TIMES 5
 int svo_list_timing(svo_ctx *ctx, float ms_out[SVO_LIST_TIMES]);
 
+/* ---- the tree in the node buffer sampled on the device ----
+ * What is at a cell of the `depth` grid, read from the first n_words words of the node buffer as a tree rooted at group 0;
+ * coordinates, child index and levels are those of svo_nodes_build, svo_nodes_edit and svo_nodes_list_voxels.  For the
+ * cell (x, y, z):
+ *     if x, y or z >= 2^depth:           value SVO_SAMPLE_OUTSIDE, level 0, index 0xFFFFFFFF
+ *     group = 0
+ *     for l = 1 .. depth:
+ *         i = group + (x bit << 2 | y bit << 1 | z bit), the bit depth - l of each coordinate
+ *         ptr = words[i] >> 4                          (the hit counter never matters)
+ *         if ptr >= SVO_VOXEL_OFFSET:    value ptr - SVO_VOXEL_OFFSET, level l, index i     (0: empty)
+ *         if l == depth:                 value SVO_SAMPLE_FINER, level l, index i           (the pointer is not looked at)
+ *         if ptr % 8 != 0 or ptr + 8 > n_words:  value SVO_SAMPLE_BROKEN, level l, index i
+ *         group = ptr
+ * A value is below 2^27, so no mark collides with one, and bit 31 is never set.  index is the word the walk stopped on:
+ * for a leaf the number in a hit record's `value`, and the address svo_nodes_scatter takes.  No pointer is followed
+ * before it passed the check, and the depth bound ends the walk on a cyclic tree.
+ * svo_nodes_sample: xyz_dev holds n * 3 u32, interleaved as the builder takes them, in any order, duplicates included;
+ * entry k of value_out_dev, level_out_dev and index_out_dev (n u32 each; the last two may be NULL) gets cell k's result.
+ * svo_nodes_sample_dense: the cells [origin, origin + size) of the grid; grid_out_dev[(i * size[1] + j) * size[2] + k]
+ * gets the value of cell origin + (i, j, k), which is svo_nodes_build_dense's [x][y][z] layout: the whole grid of a
+ * dense-built tree samples to grid & 0xFFFFFF.  A size with a 0 succeeds and writes nothing; so does n == 0.
+ * All pointers but p, origin and size are DEVICE pointers.  Both calls only read the node buffer, run on the ctx stream
+ * behind the store's last write, whichever context issued it, record no write and DO NOT BLOCK: nothing is read back,
+ * everything the device finds out is in the marks, and inputs and outputs must stay valid until svo_sync.  Only the n or
+ * size[0] * size[1] * size[2] entries are written.  No atomics: the same bytes on every run and for every layout of the
+ * same tree, but for index, which names a place.  A device adaptive state attached to the context is no obstacle.
+ * Errors are decided on the host from the arguments before anything is enqueued; the first in this order is reported:
+ * SVO_ERR_ARG: NULL p; non-zero flags; depth outside 1..21; NULL xyz_dev or value_out_dev with n > 0, n >= 2^31, NULL
+ * origin, size or grid_out_dev, a box with origin + size > 2^depth on an axis or with 2^31 cells or more.  SVO_ERR_STATE:
+ * no node buffer.  SVO_ERR_ARG: n_words not a positive multiple of 8 or above the capacity. */
+#define SVO_SAMPLE_FINER   (1u << 28)  /* the tree is interior at `depth` in this cell */
+#define SVO_SAMPLE_OUTSIDE (1u << 29)  /* a coordinate >= 2^depth */
+#define SVO_SAMPLE_BROKEN  (1u << 30)  /* the path met a pointer that is unaligned or leaves [0, n_words) */
+typedef struct svo_sample_params {
+    uint32_t flags;    /* 0 */
+    uint32_t depth;    /* 1..21: the grid the cells are given on */
+    uint64_t n_words;  /* the tree: words [0, n_words) of the node buffer, rooted at group 0 */
+} svo_sample_params;
+int svo_nodes_sample(svo_ctx *ctx, const svo_sample_params *p, const uint32_t *xyz_dev, size_t n,
+                     uint32_t *value_out_dev, uint32_t *level_out_dev /* may be null */, uint32_t *index_out_dev /* may be null */);
+int svo_nodes_sample_dense(svo_ctx *ctx, const svo_sample_params *p, const uint32_t origin[3], const uint32_t size[3],
+                           uint32_t *grid_out_dev);
+/* Times (ms) of the last sampling call that ran: [0] the kernel (device events; waits for it), [1] host wall time of the
+ * call.  A refused call, and one with nothing to do, leaves them. */
+#define SVO_SAMPLE_TIMES 2
+int svo_sample_timing(svo_ctx *ctx, float ms_out[SVO_SAMPLE_TIMES]);
+
 /* ---- mip-coloured chunk trees and streamable worlds built on the GPU ----
  * Inputs as svo_nodes_build: xyz n * 3 u32 and colours n u32 (0x00RRGGBB) or NULL, DEVICE pointers on the ctx's device;
  * the last voxel of a cell wins; a colour-0 voxel is an empty leaf on a path that exists.  A chunk tree is the host

@@ -301,6 +301,24 @@ class Render {  // render.rs:3-285
         gpu_.poll_wait();
         return n;
     }
+    // what the tree in the first n_words words of the node buffer holds at n cells of the `depth` grid, looked up on the
+    // GPU (svo_nodes_sample): xyz_dev (3 * n u32, as build_nodes takes them), values_dev (n u32) and
+    // levels_dev, indices_dev (n u32 each, or null) are DEVICE pointers; a value is the leaf's, 0 for empty, or one of
+    // SVO_SAMPLE_FINER, SVO_SAMPLE_OUTSIDE, SVO_SAMPLE_BROKEN.  The node buffer is only read.
+    void sample_voxels(uint64_t n_words, uint32_t depth, const uint32_t *xyz_dev, size_t n, uint32_t *values_dev,
+                       uint32_t *levels_dev = nullptr, uint32_t *indices_dev = nullptr) {
+        const svo_sample_params p{0u, depth, n_words};
+        gpu_.check(svo_nodes_sample(gpu_.ctx(), &p, xyz_dev, n, values_dev, levels_dev, indices_dev));
+        gpu_.poll_wait();  // the inputs may go away
+    }
+    // the cells [origin, origin + size) of the `depth` grid as a dense array indexed [x][y][z], z fastest, like
+    // build_nodes_dense's grid (svo_nodes_sample_dense): grid_dev holds size[0] * size[1] * size[2] u32
+    // of DEVICE memory.  Throws for a box that leaves the grid or has 2^31 cells or more.
+    void sample_dense(uint64_t n_words, uint32_t depth, const uint32_t origin[3], const uint32_t size[3], uint32_t *grid_dev) {
+        const svo_sample_params p{0u, depth, n_words};
+        gpu_.check(svo_nodes_sample_dense(gpu_.ctx(), &p, origin, size, grid_dev));
+        gpu_.poll_wait();
+    }
     // the adaptive step on the GPU (svo_adaptive_*): attach once (SVO_OPT_SCAN_CLEARS_COUNTERS = 1, the
     // octree's words in the node buffer, `world` kept alive), then after each scan step() over the scan's own lists (or
     // explicit DEVICE lists); download() brings the host octree up to date

@@ -22,6 +22,7 @@ from .cpu_octree import CHUNK_OFFSET, CpuOctree
 from .camera import Character, Settings, camera_matrices
 from .gpu import Gpu
 from .render import Render, HIT_DTYPE, F_PAUSE_ADAPTIVE, F_SHOW_STEPS, F_SHOW_HITS, F_SHADOWS, F_MISC_BOOL
+from .render import SAMPLE_FINER, SAMPLE_OUTSIDE, SAMPLE_BROKEN
 from .compute import Compute
 from .world import World
 from .procedural import Procedural
@@ -31,4 +32,4 @@ from . import sharding
 from . import adaptive
 
 __all__ = ["Gpu", "Render", "Compute", "Octree", "CpuOctree", "Voxel", "World", "Procedural", "Uniforms", "Character", "Settings",
-           "SvoError", "VOXEL_OFFSET", "CHUNK_OFFSET", "HIT_DTYPE", "create_node", "camera_matrices", "scenes", "sharding", "adaptive", "procedural"]
+           "SvoError", "SAMPLE_FINER", "SAMPLE_OUTSIDE", "SAMPLE_BROKEN", "VOXEL_OFFSET", "CHUNK_OFFSET", "HIT_DTYPE", "create_node", "camera_matrices", "scenes", "sharding", "adaptive", "procedural"]

@@ -85,6 +85,15 @@ class ListParams(C.Structure):
     ]
 
 
+class SampleParams(C.Structure):
+    """svo_sample_params: the tree in the node buffer sampled on the device (include/svo_hip.h)."""
+    _fields_ = [
+        ("flags", C.c_uint32),
+        ("depth", C.c_uint32),
+        ("n_words", C.c_uint64),
+    ]
+
+
 class ChunkBuildParams(C.Structure):
     """svo_chunk_build_params: a mip-coloured tree or a chunked world built on the GPU (include/svo_hip.h)."""
     _fields_ = [
@@ -121,6 +130,7 @@ DEVICE_SYMBOLS = [
     "svo_nodes_edit", "svo_edit_timing",
     "svo_nodes_compact", "svo_compact_timing",
     "svo_nodes_list_voxels", "svo_list_timing",
+    "svo_nodes_sample", "svo_nodes_sample_dense", "svo_sample_timing",
 ]
 HOST_SYMBOLS = [
     "svo_cpu_octree_new", "svo_cpu_octree_free", "svo_cpu_octree_len", "svo_cpu_octree_load_file",
@@ -220,6 +230,9 @@ def lib():
     sig("svo_compact_timing", C.c_int, vp, fp)
     sig("svo_nodes_list_voxels", C.c_int, vp, C.POINTER(ListParams), vp, vp, vp, C.POINTER(u64))
     sig("svo_list_timing", C.c_int, vp, fp)
+    sig("svo_nodes_sample", C.c_int, vp, C.POINTER(SampleParams), vp, C.c_size_t, vp, vp, vp)
+    sig("svo_nodes_sample_dense", C.c_int, vp, C.POINTER(SampleParams), C.POINTER(u32), C.POINTER(u32), vp)
+    sig("svo_sample_timing", C.c_int, vp, fp)
     sig("svo_adaptive_attach", C.c_int, vp, vp, vp)
     sig("svo_adaptive_step", C.c_int, vp, vp, u32, vp, u32, C.POINTER(AdaptiveResult))
     sig("svo_adaptive_download", C.c_int, vp, vp)

@@ -1,4 +1,4 @@
-// svo_morton.h -- the one Morton convention of the GPU tree passes (svo_build.hip, svo_proc.hip), on the host and on the
+// svo_morton.h -- the one Morton convention of the GPU tree passes (svo_build.hip, svo_proc.hip, svo_sample.hip), on the host and on the
 // device: bit b of x, y, z sits in key bits 3b + 2, 3b + 1, 3b, so three key bits are a child index x*4 + y*2 + z and
 // level 1 is in the top bits.  depth <= 21 (a key fits 63 bits).  Everything sits in an anonymous namespace, like
 // svo_scan.h.
@@ -14,6 +14,11 @@ __host__ __device__ inline uint64_t morton_encode(uint32_t x, uint32_t y, uint32
     for (uint32_t b = 0; b < depth; b++)
         k |= uint64_t((x >> b) & 1u) << (3 * b + 2) | uint64_t((y >> b) & 1u) << (3 * b + 1) | uint64_t((z >> b) & 1u) << (3 * b);
     return k;
+}
+
+// the child index of the cell (x, y, z) on the level whose bit of the coordinates is b: the key's bits 3b + 2 .. 3b
+__host__ __device__ inline uint32_t morton_child(uint32_t x, uint32_t y, uint32_t z, uint32_t b) {
+    return ((x >> b) & 1u) << 2 | ((y >> b) & 1u) << 1 | ((z >> b) & 1u);
 }
 
 // K: the key's own width (a kernel whose keys fit 32 bits decodes in 32-bit registers)

@@ -77,6 +77,13 @@ class Gpu:
         self.check(lib().svo_list_timing(self._h, ms))
         return list(ms)
 
+    def sample_timing(self):
+        """ms of the last Render.sample_voxels / sample_dense call that ran: the kernel (device events), host wall time of
+        the call (svo_sample_timing)"""
+        ms = (C.c_float * 2)()
+        self.check(lib().svo_sample_timing(self._h, ms))
+        return list(ms)
+
     def world_build_timing(self):
         """ms of the last CpuOctree.build / World.build_world: keys, sort, levels, count read-back, emit, mips (device
         events), chunk read-back, chunk files and root (CpuOctree.build: the tree), host wall time of the call

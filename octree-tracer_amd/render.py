@@ -4,13 +4,16 @@ import ctypes as C
 import numpy as np
 import torch
 
-from ._lib import BuildParams, CompactParams, EditParams, ListParams, Uniforms, lib
+from ._lib import BuildParams, CompactParams, EditParams, ListParams, SampleParams, Uniforms, lib
 from .camera import camera_matrices
 
 F_PAUSE_ADAPTIVE, F_SHOW_STEPS, F_SHOW_HITS, F_SHADOWS, F_MISC_BOOL = 1, 2, 4, 8, 16
 HIT_DTYPE = np.dtype([("value", "<u4"), ("t", "<f4"), ("info", "<u4"), ("normal_bits", "<u4")])
 DEFAULT_NODE_CAPACITY = 10_000_000  # render.rs:53
 EMPTY_WORD = (1 << 27) << 4  # an empty slot: (VOXEL_OFFSET + colour 0) << 4
+# what sample_voxels / sample_dense return in place of a value (svo_hip.h): the tree is interior at `depth` in the cell; a
+# coordinate is outside the grid; the path met a pointer that is unaligned or leaves the tree's words
+SAMPLE_FINER, SAMPLE_OUTSIDE, SAMPLE_BROKEN = 1 << 28, 1 << 29, 1 << 30
 
 
 class Render:
@@ -189,6 +192,56 @@ class Render:
                                                        levels.data_ptr() if with_levels else None, C.byref(n)))
             self.gpu.sync()
         return (coords, colours, levels) if with_levels else (coords, colours)
+
+    def _sample_params(self, depth):
+        p = SampleParams()
+        p.depth = max(0, int(getattr(self, "_declared_depth", 16) if depth is None else depth))
+        p.n_words = int(self.node_length)
+        return p
+
+    def sample_voxels(self, coords, depth=None, with_levels=False, with_indices=False):
+        """What the tree in the first node_length words of the node buffer holds at cells of the `depth` grid, looked up on
+        the GPU (svo_nodes_sample).  coords as build_nodes takes them, in any order.  Returns an int32 device
+        tensor of N values: the leaf's value (its 24-bit colour in built and edited trees, 0 for empty), SAMPLE_FINER where
+        the tree is refined below `depth`, SAMPLE_OUTSIDE for a coordinate outside [0, 2^depth) (a negative one included),
+        SAMPLE_BROKEN where the path met a bad pointer.  with_levels: also the level the walk stopped on; with_indices: also
+        the index of the word it stopped on (as in a hit record; -1 for OUTSIDE); in that order.  depth=None: the depth
+        declared for this tree, as in list_voxels.  The node buffer is only read."""
+        dev = torch.device("cuda", self.gpu.device)
+        xyz = _device_u32(coords, dev, clamp=True)
+        if xyz.dim() != 2 or xyz.shape[1] != 3:
+            raise ValueError(f"coords must be (N, 3), got {tuple(xyz.shape)}")
+        n = xyz.shape[0]
+        p = self._sample_params(depth)
+        values = torch.empty(n, dtype=torch.int32, device=dev)
+        levels = torch.empty(n, dtype=torch.int32, device=dev) if with_levels else None
+        indices = torch.empty(n, dtype=torch.int32, device=dev) if with_indices else None
+        torch.cuda.current_stream(dev).synchronize()  # the tensors were made on torch's stream
+        self.gpu.check(lib().svo_nodes_sample(self.gpu._h, C.byref(p), xyz.data_ptr() if n else None, n, values.data_ptr() if n else None,
+                                              levels.data_ptr() if with_levels and n else None,
+                                              indices.data_ptr() if with_indices and n else None))
+        self.gpu.sync()  # (the inputs may be released by the caller)
+        out = (values,) + ((levels,) if with_levels else ()) + ((indices,) if with_indices else ())
+        return out if len(out) > 1 else values
+
+    def sample_dense(self, origin, size, depth=None):
+        """The cells [origin, origin + size) of the `depth` grid as a dense int32 device tensor of shape `size`, indexed
+        [x, y, z] like build_nodes_dense's grid, read from the tree on the GPU (svo_nodes_sample_dense):
+        values and marks as sample_voxels gives them.  The whole grid of a dense-built tree comes back as grid & 0xFFFFFF.
+        Raises SvoError for a box that leaves the grid or has 2^31 cells or more.  The node buffer is only read."""
+        dev = torch.device("cuda", self.gpu.device)
+        o, s = [int(v) for v in origin], [int(v) for v in size]
+        if len(o) != 3 or len(s) != 3 or min(o + s) < 0 or max(o + s) >= 1 << 32:
+            raise ValueError(f"origin and size must be 3 values in [0, 2^32) each, got {o} and {s}")
+        p = self._sample_params(depth)
+        # a box the call will refuse gets no memory first: the library decides and words the refusal
+        fits = 1 <= p.depth <= 21 and all(a + b <= 1 << p.depth for a, b in zip(o, s)) and s[0] * s[1] * s[2] < 1 << 31
+        grid = torch.empty(s if fits else (0,), dtype=torch.int32, device=dev)
+        room = grid if grid.numel() else torch.empty(1, dtype=torch.int32, device=dev)  # (nothing is written to it)
+        torch.cuda.current_stream(dev).synchronize()  # the tensors were made on torch's stream
+        self.gpu.check(lib().svo_nodes_sample_dense(self.gpu._h, C.byref(p), (C.c_uint32 * 3)(*o), (C.c_uint32 * 3)(*s), room.data_ptr()))
+        self.gpu.sync()
+        return grid
 
     def build_nodes_dense(self, grid, max_words=None):
         """Build the tree of a dense (side, side, side) colour grid indexed [x, y, z] (non-zero = voxel, low 24 bits the
