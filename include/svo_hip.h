@@ -522,6 +522,56 @@ int svo_nodes_sample_dense(svo_ctx *ctx, const svo_sample_params *p, const uint3
 #define SVO_SAMPLE_TIMES 2
 int svo_sample_timing(svo_ctx *ctx, float ms_out[SVO_SAMPLE_TIMES]);
 
+/* ---- triangle meshes voxelised on the GPU ----
+ * Conservative voxelisation of a triangle mesh on the 2^depth grid into the voxel list that svo_nodes_build,
+ * svo_nodes_edit, svo_cpu_octree_build and svo_world_build take.  The geometry is exact.  A quantised coordinate q lies
+ * in [0, 2^(depth + SVO_VOX_SUBBITS)); the vertex stands at (q + 1/2) / 64 cells, so no vertex ever lies on a cell
+ * boundary and a wall modelled exactly on a grid plane falls on one side of it and is one cell thick.  Cell c is the
+ * closed cube [c, c + 1]^3.  There is one entry (t, c) iff the closed triangle t meets the closed cube c; a triangle
+ * that is a segment or a point counts too.  The test is done in integers, in doubled units (vertex 2q + 1, a level-l
+ * cell [c * S, (c + 1) * S] with S = 2^(depth - l + 7)), with the 13 separating axes of a triangle and a box (3 box
+ * axes, the plane, 9 edge x axis products) and every comparison strict; no float takes part.
+ * Entries come in ascending triangle index and, within a triangle, in ascending Morton key of the cell at `depth`
+ * (csrc/svo_morton.h: the builder's key).  xyz is the cell, colour the triangle's colour & 0xFFFFFF (default_colour when
+ * tri_colours_dev is NULL), tri the triangle's index.  A cell touched by several triangles appears once per triangle:
+ * fed to svo_nodes_build or svo_nodes_edit, where the last in input order wins, THE HIGHEST TRIANGLE INDEX COLOURS A
+ * SHARED CELL.  No atomics: the same bytes on every run.
+ * xyz_out_dev == NULL is a count query: *n_out gets the number of entries, nothing else is written and max_voxels is
+ * ignored.  Otherwise xyz_out_dev (3 * max_voxels u32), colour_out_dev (max_voxels u32) and tri_out_dev (max_voxels u32,
+ * or NULL) get the entries [0, *n_out) and nothing behind them.  n_tris == 0 succeeds with *n_out = 0.
+ * All pointers but p and n_out are DEVICE pointers on the ctx's device.  The call needs no node buffer and never touches
+ * one.  Runs on the ctx stream; blocks once per level to read that level's pair count; the last level's fill is
+ * enqueued: inputs and outputs must stay valid until svo_sync.
+ * A refused call leaves the outputs and *n_out as they were.  Of several causes the first in this order is reported.
+ * SVO_ERR_ARG: NULL p or n_out; non-zero flags; depth outside 1..21; n_tris >= 2^31; NULL vq_dev or tri_dev with
+ * n_tris > 0; NULL colour_out_dev with xyz_out_dev given; checked on the device: a vertex index >= n_vertices or a
+ * coordinate >= 2^(depth + 6) (svo_last_error names the first triangle this applies to).  SVO_ERR_CAP: the pair count
+ * passes max_voxels, or reaches 2^31 (also in a count query).  The pairs (triangle, cell) are refined one level at a time
+ * and their number never decreases from a level to the next (every overlapping cell has an overlapping child), so the
+ * refusal comes at the first level that exceeds the cap, names that level and its pair count, and no wider level is
+ * allocated. */
+typedef struct svo_voxelize_params {
+    uint32_t depth;          /* 1..21: the grid is 2^depth cells a side */
+    uint32_t flags;          /* must be 0 */
+    uint32_t default_colour; /* used when tri_colours == NULL */
+    uint32_t n_vertices;
+    uint64_t max_voxels;     /* capacity of the outputs, in entries; ignored by a count query */
+} svo_voxelize_params;
+#define SVO_VOX_SUBBITS 6
+int svo_mesh_voxelize(svo_ctx *ctx, const svo_voxelize_params *p,
+                      const uint32_t *vq_dev,          /* n_vertices * 3 quantised coordinates */
+                      const uint32_t *tri_dev,         /* n_tris * 3 vertex indices */
+                      const uint32_t *tri_colours_dev, /* n_tris x 0x00RRGGBB, or NULL */
+                      size_t n_tris,
+                      uint32_t *xyz_out_dev, uint32_t *colour_out_dev, uint32_t *tri_out_dev /* may be NULL */,
+                      uint64_t *n_out);
+/* Times (ms) of the last voxelisation that ran: [0] setup (the vertex check and the triangles' gather), [1] the levels
+ * 1 .. depth - 1 (test, scan, scatter and one read-back each), [2] the last level's test and scan (with its read-back),
+ * [3] emit (device events; waits for the emit; 0 for a count query), [4] host wall time of the call.  A refused call
+ * leaves the times of the last voxelisation that ran. */
+#define SVO_VOXELIZE_TIMES 5
+int svo_voxelize_timing(svo_ctx *ctx, float ms_out[SVO_VOXELIZE_TIMES]);
+
 /* ---- mip-coloured chunk trees and streamable worlds built on the GPU ----
  * Inputs as svo_nodes_build: xyz n * 3 u32 and colours n u32 (0x00RRGGBB) or NULL, DEVICE pointers on the ctx's device;
  * the last voxel of a cell wins; a colour-0 voxel is an empty leaf on a path that exists.  A chunk tree is the host

@@ -301,6 +301,22 @@ class Render {  // render.rs:3-285
         gpu_.poll_wait();
         return n;
     }
+    // a triangle mesh voxelised on the GPU, conservatively and exactly (svo_mesh_voxelize): vq_dev
+    // (3 * n_vertices quantised coordinates, 64 per cell of the 2^depth grid), tri_dev (3 * n_tris vertex indices),
+    // tri_colours_dev (n_tris x 0x00RRGGBB, or null: `colour`) and the outputs xyz_dev (3 * max_voxels u32), colours_dev
+    // (max_voxels) and tris_dev (max_voxels, or null) are DEVICE pointers; one entry per triangle and cell that meet,
+    // triangles in order, cells in Morton order: a list that build_nodes and edit_nodes take, in which the highest triangle
+    // index colours a shared cell.  Returns the entry count; xyz_dev null: the count alone.  Needs no node buffer.  Throws,
+    // with nothing written, for a bad vertex index or coordinate or more entries than max_voxels.
+    uint64_t voxelize_mesh(const uint32_t *vq_dev, uint32_t n_vertices, const uint32_t *tri_dev, size_t n_tris, uint32_t depth,
+                           uint32_t *xyz_dev, uint32_t *colours_dev, uint64_t max_voxels, const uint32_t *tri_colours_dev = nullptr,
+                           uint32_t colour = 0xFFFFFF, uint32_t *tris_dev = nullptr) {
+        const svo_voxelize_params p{depth, 0u, colour, n_vertices, max_voxels};
+        uint64_t n = 0;
+        gpu_.check(svo_mesh_voxelize(gpu_.ctx(), &p, vq_dev, tri_dev, tri_colours_dev, n_tris, xyz_dev, colours_dev, tris_dev, &n));
+        gpu_.poll_wait();  // the inputs may go away
+        return n;
+    }
     // what the tree in the first n_words words of the node buffer holds at n cells of the `depth` grid, looked up on the
     // GPU (svo_nodes_sample): xyz_dev (3 * n u32, as build_nodes takes them), values_dev (n u32) and
     // levels_dev, indices_dev (n u32 each, or null) are DEVICE pointers; a value is the leaf's, 0 for empty, or one of

@@ -12,6 +12,7 @@ C ABI of libsvo_hip.so:
     procedural.Procedural <- src/procedural.rs Procedural {generate_chunk} (deterministic: DESIGN.md 11)
     adaptive           <- src/adaptive.rs  process_subdivision / process_unsubdivision
     scenes             deterministic benchmark scene generators (no reference counterpart)
+    mesh               triangle meshes voxelised on the GPU into voxel lists, a Wavefront reader, mesh generators (no reference counterpart)
 The package directory name contains a hyphen; import it through __graft_entry__.load_package(),
 which registers it as module `octree_tracer_amd`.
 """
@@ -28,8 +29,9 @@ from .world import World
 from .procedural import Procedural
 from . import procedural
 from . import scenes
+from . import mesh
 from . import sharding
 from . import adaptive
 
 __all__ = ["Gpu", "Render", "Compute", "Octree", "CpuOctree", "Voxel", "World", "Procedural", "Uniforms", "Character", "Settings",
-           "SvoError", "SAMPLE_FINER", "SAMPLE_OUTSIDE", "SAMPLE_BROKEN", "VOXEL_OFFSET", "CHUNK_OFFSET", "HIT_DTYPE", "create_node", "camera_matrices", "scenes", "sharding", "adaptive", "procedural"]
+           "SvoError", "SAMPLE_FINER", "SAMPLE_OUTSIDE", "SAMPLE_BROKEN", "VOXEL_OFFSET", "CHUNK_OFFSET", "HIT_DTYPE", "create_node", "camera_matrices", "scenes", "mesh", "sharding", "adaptive", "procedural"]

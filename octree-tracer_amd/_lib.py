@@ -94,6 +94,17 @@ class SampleParams(C.Structure):
     ]
 
 
+class VoxelizeParams(C.Structure):
+    """svo_voxelize_params: a triangle mesh voxelised on the device (include/svo_hip.h)."""
+    _fields_ = [
+        ("depth", C.c_uint32),
+        ("flags", C.c_uint32),
+        ("default_colour", C.c_uint32),
+        ("n_vertices", C.c_uint32),
+        ("max_voxels", C.c_uint64),
+    ]
+
+
 class ChunkBuildParams(C.Structure):
     """svo_chunk_build_params: a mip-coloured tree or a chunked world built on the GPU (include/svo_hip.h)."""
     _fields_ = [
@@ -131,6 +142,7 @@ DEVICE_SYMBOLS = [
     "svo_nodes_compact", "svo_compact_timing",
     "svo_nodes_list_voxels", "svo_list_timing",
     "svo_nodes_sample", "svo_nodes_sample_dense", "svo_sample_timing",
+    "svo_mesh_voxelize", "svo_voxelize_timing",
 ]
 HOST_SYMBOLS = [
     "svo_cpu_octree_new", "svo_cpu_octree_free", "svo_cpu_octree_len", "svo_cpu_octree_load_file",
@@ -233,6 +245,8 @@ def lib():
     sig("svo_nodes_sample", C.c_int, vp, C.POINTER(SampleParams), vp, C.c_size_t, vp, vp, vp)
     sig("svo_nodes_sample_dense", C.c_int, vp, C.POINTER(SampleParams), C.POINTER(u32), C.POINTER(u32), vp)
     sig("svo_sample_timing", C.c_int, vp, fp)
+    sig("svo_mesh_voxelize", C.c_int, vp, C.POINTER(VoxelizeParams), vp, vp, vp, sz, vp, vp, vp, C.POINTER(u64))
+    sig("svo_voxelize_timing", C.c_int, vp, fp)
     sig("svo_adaptive_attach", C.c_int, vp, vp, vp)
     sig("svo_adaptive_step", C.c_int, vp, vp, u32, vp, u32, C.POINTER(AdaptiveResult))
     sig("svo_adaptive_download", C.c_int, vp, vp)

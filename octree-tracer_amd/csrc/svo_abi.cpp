@@ -571,6 +571,7 @@ int svo_ctx_destroy(svo_ctx *ctx) {
     ctx->compact.reset();
     ctx->list.reset();
     ctx->sample.reset();
+    ctx->voxelize.reset();
     release_store(ctx);
     if (ctx->top_table) (void)hipFree(ctx->top_table);
     if (ctx->status) (void)hipFree(ctx->status);

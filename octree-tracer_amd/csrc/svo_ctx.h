@@ -1,6 +1,6 @@
 // svo_ctx.h -- the device context behind the opaque `svo_ctx` of include/svo_hip.h, and the host helpers of the files that
 // use it: svo_abi.cpp (trace / scan dispatch), svo_comm.cpp (RCCL frame gather) and the GPU tree passes (svo_proc.hip,
-// svo_build.hip, svo_edit.hip, svo_compact.hip, svo_list.hip, svo_sample.hip, svo_adapt.hip).  Shared by the passes: svo_grow / svo_grow_pinned / svo_grow_keep (workspaces), the builder's sort
+// svo_build.hip, svo_edit.hip, svo_compact.hip, svo_list.hip, svo_sample.hip, svo_voxelize.hip, svo_adapt.hip).  Shared by the passes: svo_grow / svo_grow_pinned / svo_grow_keep (workspaces), the builder's sort
 // and scan, svo_world_writer (a generated world's directory); svo_scan.h, svo_mip.h and svo_morton.h hold the device pieces,
 // svo_rules.h the walks and rules that svo_host.cpp and svo_adapt.hip both run.
 // Internal: not part of the boundary.
@@ -43,6 +43,7 @@ struct svo_edit_state;
 struct svo_compact_state;
 struct svo_list_state;
 struct svo_sample_state;
+struct svo_voxelize_state;
 template <typename T>
 using svo_workspace = std::unique_ptr<T, void (*)(T *)>;
 template <typename T>
@@ -127,6 +128,7 @@ struct svo_ctx {
     svo_workspace<svo_compact_state> compact{nullptr, nullptr};  // compaction's workspace (svo_compact.hip)
     svo_workspace<svo_list_state> list{nullptr, nullptr};  // voxel listing's workspace (svo_list.hip)
     svo_workspace<svo_sample_state> sample{nullptr, nullptr};  // sampling's events and times (svo_sample.hip)
+    svo_workspace<svo_voxelize_state> voxelize{nullptr, nullptr};  // mesh voxeliser's workspace (svo_voxelize.hip)
     std::string err;
 };
 

@@ -84,6 +84,14 @@ class Gpu:
         self.check(lib().svo_sample_timing(self._h, ms))
         return list(ms)
 
+    def voxelize_timing(self):
+        """ms of the last mesh.voxelize call into the library that ran (its fill, or its count query when the list was
+        empty): setup, the levels above the last, the last level's test and scan, emit (device events), host wall time of
+        the call (svo_voxelize_timing)"""
+        ms = (C.c_float * 5)()
+        self.check(lib().svo_voxelize_timing(self._h, ms))
+        return list(ms)
+
     def world_build_timing(self):
         """ms of the last CpuOctree.build / World.build_world: keys, sort, levels, count read-back, emit, mips (device
         events), chunk read-back, chunk files and root (CpuOctree.build: the tree), host wall time of the call

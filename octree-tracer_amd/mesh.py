@@ -1,0 +1,175 @@
+"""Triangle meshes on their way into the node buffer (no reference counterpart): the GPU voxeliser behind
+svo_mesh_voxelize, the quantisation it works on, a minimal Wavefront reader and two deterministic mesh generators.
+
+    quantize_vertices  world coordinates in [-1, 1) -> the voxeliser's integer coordinates, 64 per cell
+    voxelize           mesh -> device voxel list (coords, colours[, triangles]) for build_nodes, edit_nodes, CpuOctree.build
+                       and World.build_world: one entry per (triangle, cell) that meet, triangles in order, cells in
+                       Morton order; the highest triangle index colours a shared cell
+    load_obj           v / f lines of a Wavefront file
+    fit_to_cube        uniform scale and centring into the cube
+    icosphere, torus   generators for tests and tools/voxelize_probe.py
+"""
+import ctypes as C
+
+import numpy as np
+import torch
+
+from ._lib import VoxelizeParams, lib
+
+SUBBITS = 6  # SVO_VOX_SUBBITS: a cell is 64 quantised steps wide
+
+
+def quantize_vertices(vertices, depth):
+    """q = floor((v + 1) * 2^(depth + 5)) in float64, which is exact for float32 and float64 input: the vertex then
+    stands at (q + 1/2) / 64 cells of the 2^depth grid, in the convention p = cell / 2^depth * 2 - 1.  vertices: (N, 3)
+    floats in [-1, 1), numpy (returns int64 numpy) or a torch tensor (returns an int64 tensor on its device).  Raises
+    ValueError for a vertex outside the cube; a float64 so close to the far face that v + 1 rounds to 2 counts as outside."""
+    depth = int(depth)
+    if not 1 <= depth <= 21:
+        raise ValueError(f"depth must be 1..21 (got {depth})")
+    scale = float(1 << (depth + SUBBITS - 1))
+    tensor = isinstance(vertices, torch.Tensor)
+    v = vertices.to(torch.float64) if tensor else np.asarray(vertices, dtype=np.float64)
+    if not bool(((v >= -1.0) & (v + 1.0 < 2.0)).all()):  # (NaN included)
+        raise ValueError("a vertex lies outside the cube [-1, 1)")
+    q = (v + 1.0) * scale
+    return torch.floor(q).to(torch.int64) if tensor else np.floor(q).astype(np.int64)
+
+
+def _as_u32(a, dev, what, clamp):
+    """an integer array as a contiguous int32 device tensor of u32 bit patterns; clamp: values outside [0, 2^31) become -1 or
+    2^31 - 1, which the device's range checks refuse at any depth"""
+    t = a if isinstance(a, torch.Tensor) else torch.as_tensor(np.ascontiguousarray(a))
+    if t.dtype.is_floating_point or t.dtype.is_complex or t.dtype == torch.bool:
+        raise TypeError(f"{what}: integer input expected, got {t.dtype}")
+    t = t.to(dev)
+    if t.dtype != torch.int32:
+        t = t.to(torch.int64)
+        t = t.clamp(-1, 2**31 - 1) if clamp else t & 0xFFFFFF
+    return t.to(torch.int32).contiguous()
+
+
+def voxelize(gpu, vertices, triangles, depth, colours=None, colour=0xFFFFFF, with_triangles=False, quantized=False):
+    """Voxelise a triangle mesh on the GPU, conservatively and exactly (svo_mesh_voxelize).  vertices: (V, 3)
+    floats in [-1, 1) (quantize_vertices is applied), or with quantized=True its integers; triangles: (T, 3) vertex
+    indices; colours: T values 0x00RRGGBB or None (every triangle `colour`); numpy or torch tensors.  Returns device
+    tensors (coords (N, 3) int32, colours (N) int32[, triangles (N) int32]): one entry per triangle and cell of the
+    2^depth grid that meet, in ascending triangle index and Morton order within a triangle.  A count query and then a fill,
+    like Render.list_voxels.  Raises SvoError for a bad vertex index or coordinate and for 2^31 entries or more."""
+    dev = torch.device("cuda", gpu.device)
+    depth = int(depth)
+    vq = _as_u32(vertices if quantized else quantize_vertices(vertices, depth), dev, "vertices", clamp=True)
+    tri = _as_u32(triangles, dev, "triangles", clamp=True)
+    if vq.dim() != 2 or vq.shape[1] != 3:
+        raise ValueError(f"vertices must be (V, 3), got {tuple(vq.shape)}")
+    if tri.dim() != 2 or tri.shape[1] != 3:
+        raise ValueError(f"triangles must be (T, 3), got {tuple(tri.shape)}")
+    n_tris = tri.shape[0]
+    col = None
+    if colours is not None:
+        col = _as_u32(colours, dev, "colours", clamp=False).reshape(-1)
+        if col.numel() != n_tris:
+            raise ValueError(f"{col.numel()} colours for {n_tris} triangles")
+    p = VoxelizeParams()
+    p.depth = max(0, depth)
+    p.default_colour = int(colour) & 0xFFFFFF
+    p.n_vertices = vq.shape[0]
+    args = (vq.data_ptr() if vq.numel() else None, tri.data_ptr() if n_tris else None,
+            col.data_ptr() if col is not None and n_tris else None, n_tris)
+    n = C.c_uint64()
+    torch.cuda.current_stream(dev).synchronize()  # the inputs were made on torch's stream
+    gpu.check(lib().svo_mesh_voxelize(gpu._h, C.byref(p), *args, None, None, None, C.byref(n)))  # the count
+    count = n.value
+    coords = torch.empty((count, 3), dtype=torch.int32, device=dev)
+    out_colours = torch.empty(count, dtype=torch.int32, device=dev)
+    out_tris = torch.empty(count, dtype=torch.int32, device=dev) if with_triangles else None
+    if count:
+        p.max_voxels = count
+        torch.cuda.current_stream(dev).synchronize()  # the tensors were made on torch's stream
+        gpu.check(lib().svo_mesh_voxelize(gpu._h, C.byref(p), *args, coords.data_ptr(), out_colours.data_ptr(),
+                                          out_tris.data_ptr() if with_triangles else None, C.byref(n)))
+    gpu.sync()  # (the inputs may be released by the caller)
+    return (coords, out_colours, out_tris) if with_triangles else (coords, out_colours)
+
+
+def load_obj(path):
+    """A minimal Wavefront reader: `v x y z [r g b]` and `f` with i, i/j, i/j/k and i//k (negative indices count back from
+    the last vertex read so far); polygons are fan-triangulated; everything else is ignored.  Returns (vertices (V, 3)
+    float32, triangles (T, 3) int32, vertex_rgb (V, 3) float32 or None when not every vertex carries a colour)."""
+    vertices, rgb, triangles = [], [], []
+    with open(path) as f:
+        for number, line in enumerate(f, 1):
+            part = line.split("#", 1)[0].split()
+            if not part:
+                continue
+            if part[0] == "v":
+                if len(part) < 4:
+                    raise ValueError(f"{path}:{number}: a vertex needs three coordinates")
+                vertices.append([float(x) for x in part[1:4]])
+                rgb.append([float(x) for x in part[4:7]] if len(part) >= 7 else None)
+            elif part[0] == "f":
+                corner = []
+                for word in part[1:]:
+                    i = int(word.split("/", 1)[0])
+                    i = i - 1 if i > 0 else len(vertices) + i
+                    if i < 0 or i >= len(vertices):
+                        raise ValueError(f"{path}:{number}: vertex index {word} outside the {len(vertices)} vertices read so far")
+                    corner.append(i)
+                if len(corner) < 3:
+                    raise ValueError(f"{path}:{number}: a face needs three vertices")
+                triangles += [[corner[0], corner[k], corner[k + 1]] for k in range(1, len(corner) - 1)]
+    v = np.array(vertices, dtype=np.float32).reshape(-1, 3)
+    t = np.array(triangles, dtype=np.int32).reshape(-1, 3)
+    colours = np.array(rgb, dtype=np.float32).reshape(-1, 3) if rgb and all(c is not None for c in rgb) else None
+    return v, t, colours
+
+
+def fit_to_cube(vertices, margin=0.02):
+    """The vertices scaled uniformly and centred so that their bounding box's longest side spans [-1 + margin, 1 - margin]
+    (float64 in, float64 out; float32 otherwise)."""
+    v = np.asarray(vertices)
+    v = v.astype(np.float64 if v.dtype == np.float64 else np.float32)
+    if v.size == 0:
+        return v
+    lo, hi = v.min(axis=0), v.max(axis=0)
+    extent = float((hi - lo).max())
+    scale = (1.0 - margin) * 2.0 / extent if extent > 0 else 1.0
+    return ((v - (lo + hi) / 2) * scale).astype(v.dtype)
+
+
+def icosphere(subdivisions=2, radius=0.8, centre=(0.0, 0.0, 0.0)):
+    """An icosahedron subdivided `subdivisions` times onto the sphere: (vertices float32, triangles int32) with
+    20 * 4^subdivisions triangles, the same arrays on every run."""
+    g = (1.0 + 5.0 ** 0.5) / 2.0
+    v = [(-1, g, 0), (1, g, 0), (-1, -g, 0), (1, -g, 0), (0, -1, g), (0, 1, g), (0, -1, -g), (0, 1, -g),
+         (g, 0, -1), (g, 0, 1), (-g, 0, -1), (-g, 0, 1)]
+    v = np.array(v, dtype=np.float64)
+    v /= np.linalg.norm(v, axis=1, keepdims=True)
+    t = np.array([(0, 11, 5), (0, 5, 1), (0, 1, 7), (0, 7, 10), (0, 10, 11), (1, 5, 9), (5, 11, 4), (11, 10, 2), (10, 7, 6), (7, 1, 8),
+                  (3, 9, 4), (3, 4, 2), (3, 2, 6), (3, 6, 8), (3, 8, 9), (4, 9, 5), (2, 4, 11), (6, 2, 10), (8, 6, 7), (9, 8, 1)], dtype=np.int64)
+    for _ in range(int(subdivisions)):
+        # one new vertex per edge, in the order of the edges' (low, high) vertex pairs
+        ends = np.sort(np.stack([t, np.roll(t, -1, axis=1)], axis=-1).reshape(-1, 2), axis=1)
+        edge, mid = np.unique(ends[:, 0] * len(v) + ends[:, 1], return_inverse=True)
+        new = v[edge // len(v)] + v[edge % len(v)]
+        mid = mid.reshape(-1, 3) + len(v)  # per triangle: the midpoints of ab, bc, ca
+        v = np.concatenate([v, new / np.linalg.norm(new, axis=1, keepdims=True)])
+        a, b, c, ab, bc, ca = t[:, 0], t[:, 1], t[:, 2], mid[:, 0], mid[:, 1], mid[:, 2]
+        t = np.stack([np.stack(x, axis=-1) for x in ((a, ab, ca), (b, bc, ab), (c, ca, bc), (ab, bc, ca))], axis=1).reshape(-1, 3)
+    vertices = v * float(radius) + np.array(centre, dtype=np.float64)
+    return vertices.astype(np.float32), t.astype(np.int32)
+
+
+def torus(nu=24, nv=12, R=0.6, r=0.2, centre=(0.0, 0.0, 0.0)):
+    """A torus around the y axis, nu segments around the axis and nv around the tube: (vertices float32, triangles int32)
+    with 2 * nu * nv triangles, the same arrays on every run."""
+    u = np.arange(nu, dtype=np.float64) * (2 * np.pi / nu)
+    w = np.arange(nv, dtype=np.float64) * (2 * np.pi / nv)
+    uu, ww = np.meshgrid(u, w, indexing="ij")
+    ring = R + r * np.cos(ww)
+    vertices = np.stack([ring * np.cos(uu), r * np.sin(ww), ring * np.sin(uu)], axis=-1).reshape(-1, 3) + np.array(centre, dtype=np.float64)
+    i, j = np.meshgrid(np.arange(nu), np.arange(nv), indexing="ij")
+    a, b = i * nv + j, ((i + 1) % nu) * nv + j
+    c, d = ((i + 1) % nu) * nv + (j + 1) % nv, i * nv + (j + 1) % nv
+    triangles = np.stack([np.stack([a, b, c], -1), np.stack([a, c, d], -1)], axis=2).reshape(-1, 3)
+    return vertices.astype(np.float32), triangles.astype(np.int32)

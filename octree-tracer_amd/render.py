@@ -91,6 +91,22 @@ class Render:
         self.build_nodes(coords, depth, colours)
         return self
 
+    @classmethod
+    def from_mesh(cls, gpu, size, vertices, triangles, depth, colours=None, capacity=None):
+        """A Render whose tree is a triangle mesh voxelised and built on the GPU (build_nodes_mesh)."""
+        self = cls(gpu, size, np.full(8, EMPTY_WORD, dtype=np.uint32), capacity)
+        self.build_nodes_mesh(vertices, triangles, depth, colours)
+        return self
+
+    def build_nodes_mesh(self, vertices, triangles, depth, colours=None, colour=0xFFFFFF, max_words=None, quantized=False):
+        """Voxelise a triangle mesh on the GPU (mesh.voxelize) and build the tree of its cells into the node
+        buffer from word 0 (build_nodes).  vertices: (V, 3) floats in [-1, 1), or with quantized=True the integers of
+        mesh.quantize_vertices; triangles: (T, 3) vertex indices; colours: T values 0x00RRGGBB or None (every triangle
+        `colour`).  The highest triangle index colours a cell that several triangles touch.  Returns the word count."""
+        from .mesh import voxelize
+        coords, cell_colours = voxelize(self.gpu, vertices, triangles, depth, colours, colour, quantized=quantized)
+        return self.build_nodes(coords, depth, cell_colours, max_words=max_words)
+
     def build_nodes(self, coords, depth, colours=None, colour=0xFFFFFF, max_words=None):
         """Build the tree of a voxel list on the GPU into the node buffer from word 0 (svo_nodes_build).
         coords: (N, 3) integer cells in [0, 2^depth), a torch tensor on this context's device or numpy (copied there);
