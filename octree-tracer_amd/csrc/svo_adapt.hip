@@ -403,49 +403,45 @@ struct svo_adapt_state {
     svo_world *world = nullptr;
     uint32_t *nodes_at_attach = nullptr;  // the node buffer the state belongs to
     size_t capacity = 0;                  // the node buffer's at attach
-    float *pos = nullptr;                 // 3 per node
+    svo_dev<float> pos;                   // 3 per node
     size_t pos_items = 0;
-    uint32_t *holes = nullptr;
+    svo_dev<uint32_t> holes;
     size_t hole_cap = 0;
     uint32_t n_holes = 0;
     uint32_t len = 0;
     // world mirror: nodes {pointer, rgb} of every resident chunk, concatenated; table sorted by id
-    uint2 *wn = nullptr;
+    svo_dev<uint2> wn;
     size_t wn_cap = 0, wn_used = 0;
     std::vector<Chunk> tab;
-    Chunk *tab_dev = nullptr;
+    svo_dev<Chunk> tab_dev;
     size_t tab_cap = 0;
-    uint32_t *rm = nullptr;  // per table slot: lowest unsubdivide rank that drops it
+    svo_dev<uint32_t> rm;  // per table slot: lowest unsubdivide rank that drops it
     size_t rm_cap = 0;
     // per-entry workspace
-    uint32_t *list[2] = {};  // sorted subdivide / unsubdivide lists
-    uint32_t *res = nullptr, *src = nullptr, *val = nullptr, *flag = nullptr;
+    svo_dev<uint32_t> list[2];  // sorted subdivide / unsubdivide lists
+    svo_dev<uint32_t> res, src, val, flag;
     size_t items = 0;
-    uint32_t *req = nullptr;  // 2 per entry
+    svo_dev<uint32_t> req;  // 2 per entry
     size_t req_items = 0;
-    uint32_t *bits = nullptr;
+    svo_dev<uint32_t> bits;
     size_t bit_words = 0;
-    Status *st = nullptr, *st_host = nullptr;
-    uint32_t *counts_host = nullptr;  // (pinned) scan list counts
+    svo_mirrored<Status> st;                // one Status
+    svo_pinned<uint32_t> counts_host;     // scan list counts
     std::vector<uint32_t> removed;
-    hipEvent_t ev[4] = {};  // start, sorted, subdivided, unsubdivided
+    svo_events<4> ev;  // start, sorted, subdivided, unsubdivided
     float ms[SVO_ADAPT_TIMES] = {};
     // svo_adaptive_expand: this level's frontier and the next one's, the compactions' tile sums
-    uint32_t *frontier[2] = {};
+    svo_dev<uint32_t> frontier[2];
     size_t frontier_items[2] = {};
-    uint32_t *tiles = nullptr;
+    svo_dev<uint32_t> tiles;
     size_t tile_items = 0;
     float expand_ms[SVO_ADAPT_EXPAND_TIMES] = {};
 
-    ~svo_adapt_state() {
-        for (void *p : {(void *)pos, (void *)holes, (void *)wn, (void *)tab_dev, (void *)rm, (void *)list[0], (void *)list[1],
-                        (void *)res, (void *)src, (void *)val, (void *)flag, (void *)req, (void *)bits, (void *)st, (void *)frontier[0],
-                        (void *)frontier[1], (void *)tiles})
-            if (p) (void)hipFree(p);
-        for (void *p : {(void *)st_host, (void *)counts_host})
-            if (p) (void)hipHostFree(p);
-        for (hipEvent_t e : ev)
-            if (e) (void)hipEventDestroy(e);
+    int create(svo_ctx *ctx) {
+        HIP_TRY(ctx, ev.create());
+        if (int rc = st.alloc(ctx, 1)) return rc;
+        HIP_TRY(ctx, hipHostMalloc((void **)&counts_host.p, 2 * sizeof(uint32_t), hipHostMallocDefault));
+        return SVO_OK;
     }
 };
 
@@ -549,17 +545,15 @@ int entry_fail(svo_ctx *ctx, int code, uint32_t packed, const char *pass) {
 
 int read_status(svo_ctx *ctx, const uint32_t *total_dev) {
     svo_adapt_state *a = ctx->adapt.get();
-    if (total_dev) HIP_TRY(ctx, hipMemcpyAsync(&a->st->total, total_dev, sizeof(uint32_t), hipMemcpyDeviceToDevice, ctx->stream));
-    HIP_TRY(ctx, hipMemcpyAsync(a->st_host, a->st, sizeof(Status), hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    return SVO_OK;
+    if (total_dev) HIP_TRY(ctx, hipMemcpyAsync(&a->st.dev->total, total_dev, sizeof(uint32_t), hipMemcpyDeviceToDevice, ctx->stream));
+    return a->st.read(ctx);
 }
 
 int clear_status(svo_ctx *ctx) {
     Status s{};
     s.refuse = s.err = kNone;
-    *ctx->adapt->st_host = s;
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->adapt->st, ctx->adapt->st_host, sizeof(Status), hipMemcpyHostToDevice, ctx->stream));
+    *ctx->adapt->st.host() = s;
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->adapt->st.dev, ctx->adapt->st.host(), sizeof(Status), hipMemcpyHostToDevice, ctx->stream));
     return SVO_OK;
 }
 
@@ -581,10 +575,10 @@ int subdivide_pass(svo_ctx *ctx, uint32_t n, uint32_t limit, svo_adaptive_result
     for (int round = 0;; round++) {
         if ((rc = clear_status(ctx))) return rc;
         sub_plan_kernel<<<grid, kThreads, 0, ctx->stream>>>(tree_of(ctx), list, n, a->tab_dev, (uint32_t)a->tab.size(), a->wn,
-                                                            a->res, a->src, a->flag, a->req, a->st);
+                                                            a->res, a->src, a->flag, a->req, a->st.dev);
         HIP_TRY(ctx, hipGetLastError());
         if ((rc = read_status(ctx, nullptr))) return rc;
-        const Status s = *a->st_host;
+        const Status s = *a->st.host();
         if (s.refuse != kNone) return entry_fail(ctx, SVO_ERR_STATE, s.refuse, "subdivide");
         if (!s.n_req) {
             if (s.err != kNone) return entry_fail(ctx, SVO_ERR_STATE, s.err, "subdivide");
@@ -613,11 +607,11 @@ int subdivide_pass(svo_ctx *ctx, uint32_t n, uint32_t limit, svo_adaptive_result
     if ((rc = svo_build_scan_u32(ctx, a->flag, n + 1))) return rc;
     if (a->n_holes)
         sub_popped_kernel<<<svo_div_up(std::min(n, a->n_holes), kThreads), kThreads, 0, ctx->stream>>>(a->holes, a->n_holes, list, n,
-                                                                                                       a->flag + n, a->st);
+                                                                                                       a->flag + n, a->st.dev);
     HIP_TRY(ctx, hipGetLastError());
     if ((rc = read_status(ctx, a->flag + n))) return rc;
-    const uint32_t done = std::min(a->st_host->total, limit);
-    if (a->st_host->popped_hit)
+    const uint32_t done = std::min(a->st.host()->total, limit);
+    if (a->st.host()->popped_hit)
         return svo_fail(ctx, SVO_ERR_STATE, "subdivide: an entry lies in a hole group this pass reuses (this list needs the sequential "
                                             "host path, svo_adaptive_subdivide)");
     const uint32_t pops = std::min(done, a->n_holes);
@@ -627,7 +621,7 @@ int subdivide_pass(svo_ctx *ctx, uint32_t n, uint32_t limit, svo_adaptive_result
                                               " words, over the node buffer's capacity of " + std::to_string(ctx->capacity));
     if (done) {
         sub_apply_kernel<<<grid, kThreads, 0, ctx->stream>>>(tree_of(ctx), list, n, a->res, a->src, a->flag, a->holes, a->n_holes,
-                                                             a->wn, (uint32_t)ctx->capacity, limit, a->st);
+                                                             a->wn, (uint32_t)ctx->capacity, limit, a->st.dev);
         HIP_TRY(ctx, hipGetLastError());
     }
     a->n_holes -= pops;
@@ -648,21 +642,21 @@ int unsubdivide_pass(svo_ctx *ctx, uint32_t n, svo_adaptive_result *out) {
     if ((rc = clear_status(ctx))) return rc;
     unsub_mark_kernel<<<grid, kThreads, 0, ctx->stream>>>(list, n, a->len, a->bits);
     unsub_plan_kernel<<<grid, kThreads, 0, ctx->stream>>>(tree_of(ctx), list, n, a->bits, a->tab_dev, (uint32_t)a->tab.size(),
-                                                          a->wn, a->res, a->val, a->src, a->flag, a->rm, a->st);
+                                                          a->wn, a->res, a->val, a->src, a->flag, a->rm, a->st.dev);
     HIP_TRY(ctx, hipGetLastError());
     if ((rc = read_status(ctx, nullptr))) return rc;
-    if (a->st_host->err != kNone) return entry_fail(ctx, SVO_ERR_STATE, a->st_host->err, "unsubdivide");
-    const bool removals = a->st_host->removals != 0;
+    if (a->st.host()->err != kNone) return entry_fail(ctx, SVO_ERR_STATE, a->st.host()->err, "unsubdivide");
+    const bool removals = a->st.host()->removals != 0;
     if (removals) {
         unsub_check_kernel<<<grid, kThreads, 0, ctx->stream>>>(tree_of(ctx), list, n, a->res, a->tab_dev, (uint32_t)a->tab.size(),
-                                                               a->wn, a->rm, a->st);
+                                                               a->wn, a->rm, a->st.dev);
         HIP_TRY(ctx, hipGetLastError());
     }
     HIP_TRY(ctx, hipMemsetAsync(a->flag + n, 0, sizeof(uint32_t), ctx->stream));
     if ((rc = svo_build_scan_u32(ctx, a->flag, n + 1))) return rc;
     if ((rc = read_status(ctx, a->flag + n))) return rc;
-    if (a->st_host->err != kNone) return entry_fail(ctx, SVO_ERR_STATE, a->st_host->err, "unsubdivide");
-    const uint32_t done = a->st_host->total;
+    if (a->st.host()->err != kNone) return entry_fail(ctx, SVO_ERR_STATE, a->st.host()->err, "unsubdivide");
+    const uint32_t done = a->st.host()->total;
     const size_t hole_room = grown_stack(a->hole_cap, size_t(a->n_holes) + done);
     if ((rc = svo_grow_keep(ctx, &a->hole_cap, hole_room, &a->holes, a->n_holes))) return rc;
     unsub_apply_kernel<<<grid, kThreads, 0, ctx->stream>>>(tree_of(ctx), list, n, a->res, a->val, a->src, a->flag, a->holes,
@@ -709,7 +703,7 @@ int timed_compaction(svo_ctx *ctx, int stage, const uint32_t *in, uint32_t n, Ke
     if (rc || (rc = clear_status(ctx))) return rc;
     HIP_TRY(ctx, hipEventRecord(a->ev[0], ctx->stream));
     compact_count_kernel<<<nt, kThreads, 0, ctx->stream>>>(in, n, keep, a->tiles);
-    tile_offsets_kernel<<<1, kTopThreads, 0, ctx->stream>>>(a->tiles, nt, nullptr, 0, &a->st->total);
+    tile_offsets_kernel<<<1, kTopThreads, 0, ctx->stream>>>(a->tiles, nt, nullptr, 0, &a->st.dev->total);
     compact_emit_kernel<<<nt, kThreads, 0, ctx->stream>>>(in, n, keep, emit, a->tiles);
     HIP_TRY(ctx, hipGetLastError());
     HIP_TRY(ctx, hipEventRecord(a->ev[1], ctx->stream));
@@ -742,17 +736,10 @@ int svo_adaptive_attach(svo_ctx *ctx, svo_world *w, const svo_octree *o) {
     const size_t len = svo_octree_state(o, &nodes, &pos, holes);
     if (len > ctx->capacity || len > kVoxelOff) return svo_fail(ctx, SVO_ERR_CAP, "the octree is longer than the node buffer");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    if (!ctx->adapt) {
-        ctx->adapt = svo_workspace_new<svo_adapt_state>();
-        svo_adapt_state *a = ctx->adapt.get();
-        for (hipEvent_t &e : a->ev) HIP_TRY(ctx, hipEventCreate(&e));
-        HIP_TRY(ctx, hipMalloc((void **)&a->st, sizeof(Status)));
-        HIP_TRY(ctx, hipHostMalloc((void **)&a->st_host, sizeof(Status), hipHostMallocDefault));
-        HIP_TRY(ctx, hipHostMalloc((void **)&a->counts_host, 2 * sizeof(uint32_t), hipHostMallocDefault));
-    }
+    int rc = svo_workspace_ensure(ctx, ctx->adapt);
+    if (rc) return rc;
     svo_adapt_state *a = ctx->adapt.get();
     a->world = nullptr;  // (attached only once everything is up)
-    int rc;
     if ((rc = svo_grow(ctx, &a->pos_items, 3 * ctx->capacity, &a->pos))) return rc;
     a->capacity = ctx->capacity;
     if ((rc = svo_grow(ctx, &a->hole_cap, std::max<size_t>(holes.size() + kListCap, ctx->capacity / 8 + 1), &a->holes))) return rc;
@@ -852,9 +839,9 @@ int svo_adaptive_expand(svo_ctx *ctx, uint32_t max_depth, const float cam[3], fl
     uint32_t cur = 0, n_front = 0;
     if (a->len) {
         if ((rc = svo_grow(ctx, &a->frontier_items[0], a->len, &a->frontier[0]))) return rc;
-        if ((rc = timed_compaction(ctx, 0, ctx->nodes, a->len, LeafWord{}, EmitLeaf{tree_of(ctx), a->frontier[0], a->len, a->st}))) return rc;
-        if (a->st_host->err != kNone) return entry_fail(ctx, SVO_ERR_STATE, a->st_host->err, "expand: leaf");
-        n_front = a->st_host->total;
+        if ((rc = timed_compaction(ctx, 0, ctx->nodes, a->len, LeafWord{}, EmitLeaf{tree_of(ctx), a->frontier[0], a->len, a->st.dev}))) return rc;
+        if (a->st.host()->err != kNone) return entry_fail(ctx, SVO_ERR_STATE, a->st.host()->err, "expand: leaf");
+        n_front = a->st.host()->total;
     }
 
     // level by level; a level of 2^24 entries or more goes through the pass in consecutive slices (its rank packing)
@@ -880,7 +867,7 @@ int svo_adaptive_expand(svo_ctx *ctx, uint32_t max_depth, const float cam[3], fl
             if ((rc = svo_grow(ctx, &a->req_items, 2 * a->items, &a->req))) return rc;
             const uint32_t *front = a->frontier[cur] + lo;
             if ((rc = timed_compaction(ctx, 1, front, n, ViewRefines{a->pos, view}, EmitCandidate{a->list[0]}))) return rc;
-            const uint32_t n_cand = a->st_host->total;
+            const uint32_t n_cand = a->st.host()->total;
             if (!n_cand) continue;
             const uint32_t len_before = a->len;
             svo_adaptive_result pass{};

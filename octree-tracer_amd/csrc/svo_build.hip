@@ -44,8 +44,6 @@
 
 namespace {
 
-constexpr uint32_t kEmptyWord = SVO_VOXEL_OFFSET << 4;
-constexpr uint64_t kMaxWords = SVO_VOXEL_OFFSET;  // 2^27: pointers and colours must stay apart
 constexpr int kErrSlot = 24;                      // counts[0..21]: nodes per level; counts[24]: range error
 constexpr int kCountSlots = 32;
 
@@ -340,40 +338,33 @@ constexpr Slot kChunkSlots[6] = {{kEvStart, kEvKeys},    {kEvKeys, kEvSort},    
 // context.  keys[0] / keys[1] and vals[0] / vals[1] are the sort's ping-pong buffers, later the level passes'
 // (keys[0], keys[1] by turns); keys[2] / leaf_colours hold the leaf level from the level pass to the emit.
 struct svo_build_state {
-    uint64_t *keys[3] = {};
-    uint32_t *vals[2] = {};
-    uint32_t *leaf_colours = nullptr;
-    size_t items = 0;           // room in every one of them
-    uint32_t *hist = nullptr;   // the sort's digit counts, 256 per tile
+    svo_dev<uint64_t> keys[3];
+    svo_dev<uint32_t> vals[2];
+    svo_dev<uint32_t> leaf_colours;
+    size_t items = 0;         // room in every one of them
+    svo_dev<uint32_t> hist;   // the sort's digit counts, 256 per tile
     size_t hist_items = 0;
-    uint32_t *tiles = nullptr;  // tile sums / offsets of a scan
+    svo_dev<uint32_t> tiles;  // tile sums / offsets of a scan
     size_t tile_items = 0;
-    uint32_t *counts = nullptr;       // kCountSlots words (device): unique nodes per level, error word
-    uint32_t *counts_host = nullptr;  // (pinned)
-    hipEvent_t ev[kEvs] = {};
-    bool sorted = false, timed = true;  // the last build sorted / its device times are in ms
-    float ms[SVO_BUILD_TIMES] = {};
+    svo_mirrored<> counts;      // kCountSlots words: unique nodes per level, error word
+    svo_pass_timer<kEvs, SVO_BUILD_TIMES> timer;  // (spans: kBuildSlots, the sort's only when the last build sorted)
     // chunk trees (svo_world_build, svo_cpu_octree_build)
-    uint32_t *runs = nullptr, *runs_host = nullptr;  // per level 0..21: n_chunks + 1 chunk starts (device / pinned)
+    svo_dev<uint32_t> runs;  // per level 0..21: n_chunks + 1 chunk starts, and their pinned mirror
+    svo_pinned<uint32_t> runs_host;
     size_t runs_items = 0, runs_host_items = 0;
-    uint32_t *cbase = nullptr;  // per chunk: chunk-local level bases 1 .. chunk_depth + 1 (the last = its node count)
+    svo_dev<uint32_t> cbase;  // per chunk: chunk-local level bases 1 .. chunk_depth + 1 (the last = its node count)
     size_t cbase_items = 0;
-    uint64_t *coff = nullptr;   // per chunk: its first node in `nodes`
+    svo_dev<uint64_t> coff;   // per chunk: its first node in `nodes`
     size_t coff_items = 0;
-    uint2 *nodes = nullptr;     // every chunk's nodes, one chunk after another
+    svo_dev<uint2> nodes;     // every chunk's nodes, one chunk after another
     size_t node_items = 0;
-    void *stage = nullptr;      // pinned: one chunk's bytes on their way to a file or a CpuOctree
+    svo_pinned<void> stage;   // one chunk's bytes on their way to a file or a CpuOctree
     size_t stage_bytes = 0;
     float cms[SVO_WORLD_BUILD_TIMES] = {};
 
-    ~svo_build_state() {
-        for (void *p : {(void *)keys[0], (void *)keys[1], (void *)keys[2], (void *)vals[0], (void *)vals[1], (void *)leaf_colours,
-                        (void *)hist, (void *)tiles, (void *)counts, (void *)runs, (void *)cbase, (void *)coff, (void *)nodes})
-            if (p) (void)hipFree(p);
-        for (void *p : {(void *)counts_host, (void *)runs_host, stage})
-            if (p) (void)hipHostFree(p);
-        for (hipEvent_t e : ev)
-            if (e) (void)hipEventDestroy(e);
+    int create(svo_ctx *ctx) {
+        HIP_TRY(ctx, timer.create());
+        return counts.alloc(ctx, kCountSlots);
     }
 };
 
@@ -381,14 +372,10 @@ namespace {
 
 // workspace for `items` keys (and the tile sums of scans over at most `scan_items` items)
 int ensure_state(svo_ctx *ctx, size_t items, size_t scan_items, size_t hist_items) {
-    if (!ctx->build) {
-        ctx->build = svo_workspace_new<svo_build_state>();
-        for (hipEvent_t &e : ctx->build->ev) HIP_TRY(ctx, hipEventCreate(&e));
-        HIP_TRY(ctx, hipHostMalloc((void **)&ctx->build->counts_host, kCountSlots * sizeof(uint32_t), hipHostMallocDefault));
-        HIP_TRY(ctx, hipMalloc((void **)&ctx->build->counts, kCountSlots * sizeof(uint32_t)));
-    }
+    int rc = svo_workspace_ensure(ctx, ctx->build);
+    if (rc) return rc;
     svo_build_state *s = ctx->build.get();
-    int rc = svo_grow(ctx, &s->items, items, &s->keys[0], &s->keys[1], &s->keys[2], &s->vals[0], &s->vals[1], &s->leaf_colours);
+    rc = svo_grow(ctx, &s->items, items, &s->keys[0], &s->keys[1], &s->keys[2], &s->vals[0], &s->vals[1], &s->leaf_colours);
     if (!rc) rc = svo_grow(ctx, &s->hist_items, hist_items, &s->hist);
     if (!rc) rc = svo_grow(ctx, &s->tile_items, (size_t)svo_div_up(scan_items, kTile) + 1, &s->tiles);
     return rc;
@@ -399,7 +386,7 @@ int scan_u32(svo_ctx *ctx, uint32_t *a, uint32_t n) {
     svo_build_state *s = ctx->build.get();
     const uint32_t nt = svo_div_up(n, kTile);
     build_sum_kernel<<<nt, kThreads, 0, ctx->stream>>>(a, n, s->tiles);
-    tile_offsets_kernel<<<1, kTopThreads, 0, ctx->stream>>>(s->tiles, nt, nullptr, 0, s->counts + kErrSlot + 1);
+    tile_offsets_kernel<<<1, kTopThreads, 0, ctx->stream>>>(s->tiles, nt, nullptr, 0, s->counts.dev + kErrSlot + 1);
     build_add_kernel<<<nt, kThreads, 0, ctx->stream>>>(a, n, s->tiles);
     HIP_TRY(ctx, hipGetLastError());
     return SVO_OK;
@@ -453,7 +440,7 @@ int parent_passes(svo_ctx *ctx, uint32_t depth, uint32_t stop, const uint64_t *b
         LevelIn in{};
         in.keys = src;
         in.vals = l == depth ? s->leaf_colours : nullptr;
-        in.m_dev = s->counts + l;
+        in.m_dev = s->counts.dev + l;
         in.m_max = (uint32_t)s->items;
         LevelOut out{};
         out.keys = s->keys[turn];
@@ -470,7 +457,7 @@ int parent_passes(svo_ctx *ctx, uint32_t depth, uint32_t stop, const uint64_t *b
             const uint32_t wd = plan->world_depth, row = plan->n_chunks + 1;
             if (!plan->nodes && l < depth && l >= wd) {
                 build_runs_kernel<<<std::max(svo_div_up(bound[l], kThreads), 1u), kThreads, 0, ctx->stream>>>(
-                    src, s->counts + l, in.m_max, 3 * (l - wd), plan->n_chunks, s->runs + size_t(l) * row);
+                    src, s->counts.dev + l, in.m_max, 3 * (l - wd), plan->n_chunks, s->runs + size_t(l) * row);
                 HIP_TRY(ctx, hipGetLastError());
             }
             if (plan->nodes) {
@@ -485,9 +472,9 @@ int parent_passes(svo_ctx *ctx, uint32_t depth, uint32_t stop, const uint64_t *b
                 out.stride = depth - wd + 2;
                 out.last = l == depth;
             }
-            rc = level_pass<kChunk>(ctx, in, out, bound[l], s->counts + l - 1);
+            rc = level_pass<kChunk>(ctx, in, out, bound[l], s->counts.dev + l - 1);
         } else {
-            rc = level_pass<kParent>(ctx, in, out, bound[l], s->counts + l - 1);
+            rc = level_pass<kParent>(ctx, in, out, bound[l], s->counts.dev + l - 1);
         }
         if (rc) return rc;
         src = s->keys[turn];
@@ -498,9 +485,7 @@ int parent_passes(svo_ctx *ctx, uint32_t depth, uint32_t stop, const uint64_t *b
 // The parameters every build has; `depth` is null when the caller passed no params.
 int check_depth(svo_ctx *ctx, const uint32_t *depth, uint32_t max_depth) {
     if (!depth) return svo_fail(ctx, SVO_ERR_ARG, "null params");
-    if (*depth < 1 || *depth > max_depth)
-        return svo_fail(ctx, SVO_ERR_ARG, "depth must be 1.." + std::to_string(max_depth) + " (got " + std::to_string(*depth) + ")");
-    return SVO_OK;
+    return svo_check_depth(ctx, *depth, max_depth);
 }
 
 // The three list entry points: svo_nodes_build (chunked null), svo_cpu_octree_build (a single tree) and svo_world_build.
@@ -513,11 +498,6 @@ int check_list(svo_ctx *ctx, const uint32_t *depth, const svo_chunk_build_params
                                               ", depth " + std::to_string(*depth) + ")");
     if (n >= (1ull << 31)) return svo_fail(ctx, SVO_ERR_ARG, "at most 2^31 - 1 voxels per build");
     if (!xyz && n) return svo_fail(ctx, SVO_ERR_ARG, "null coordinates");
-    return SVO_OK;
-}
-
-int check_store(svo_ctx *ctx) {
-    if (!ctx->store) return svo_fail(ctx, SVO_ERR_STATE, "svo_nodes_alloc / svo_nodes_bind_device not called");
     return SVO_OK;
 }
 
@@ -537,16 +517,16 @@ int list_leaves(svo_ctx *ctx, const uint32_t *xyz, const uint32_t *colours, size
     svo_build_state *s = ctx->build.get();
     if ((rc = svo_grow(ctx, &s->runs_items, runs_items, &s->runs))) return rc;
     if ((rc = svo_grow_pinned(ctx, &s->runs_host_items, runs_items, &s->runs_host))) return rc;
-    HIP_TRY(ctx, hipEventRecord(s->ev[kEvStart], ctx->stream));
-    HIP_TRY(ctx, hipMemsetAsync(s->counts, 0, kCountSlots * sizeof(uint32_t), ctx->stream));
+    HIP_TRY(ctx, s->timer.mark(ctx, kEvStart));
+    HIP_TRY(ctx, s->counts.zero(ctx));
     if (runs_items) HIP_TRY(ctx, hipMemsetAsync(s->runs, 0, runs_items * sizeof(uint32_t), ctx->stream));
     build_keys_kernel<<<svo_div_up(n, kThreads), kThreads, 0, ctx->stream>>>(xyz, (uint32_t)n, depth, s->keys[0], s->vals[0],
-                                                                             s->counts + kErrSlot);
+                                                                             s->counts.dev + kErrSlot);
     HIP_TRY(ctx, hipGetLastError());
-    HIP_TRY(ctx, hipEventRecord(s->ev[kEvKeys], ctx->stream));
+    HIP_TRY(ctx, s->timer.mark(ctx, kEvKeys));
     const uint32_t passes = (3 * depth + 7) / 8;
     if ((rc = sort_passes(ctx, (uint32_t)n, passes))) return rc;
-    HIP_TRY(ctx, hipEventRecord(s->ev[kEvSort], ctx->stream));
+    HIP_TRY(ctx, s->timer.mark(ctx, kEvSort));
     LevelIn in{};
     in.keys = s->keys[passes & 1];
     in.vals = s->vals[passes & 1];
@@ -558,7 +538,7 @@ int list_leaves(svo_ctx *ctx, const uint32_t *xyz, const uint32_t *colours, size
     out.colours = s->leaf_colours;
     out.index = keep_index ? s->vals[(passes & 1) ^ 1] : nullptr;
     out.cap = (uint32_t)s->items;
-    return level_pass<kDedupe>(ctx, in, out, n, s->counts + depth);
+    return level_pass<kDedupe>(ctx, in, out, n, s->counts.dev + depth);
 }
 
 // Host bounds of the unique nodes per level, from the leaf level's: m_L <= m_{L+1} and m_L <= 8^L.
@@ -571,12 +551,12 @@ void level_bounds(uint64_t bound[23], uint32_t depth, uint64_t leaf_bound) {
 // into their pinned mirrors; fails on the keys kernel's range error word.
 int read_counts(svo_ctx *ctx, uint32_t depth, size_t runs_items) {
     svo_build_state *s = ctx->build.get();
-    HIP_TRY(ctx, hipEventRecord(s->ev[kEvLevels], ctx->stream));
-    HIP_TRY(ctx, hipMemcpyAsync(s->counts_host, s->counts, kCountSlots * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, s->timer.mark(ctx, kEvLevels));
+    HIP_TRY(ctx, s->counts.copy(ctx));
     if (runs_items) HIP_TRY(ctx, hipMemcpyAsync(s->runs_host, s->runs, runs_items * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipEventRecord(s->ev[kEvCounts], ctx->stream));
+    HIP_TRY(ctx, s->timer.mark(ctx, kEvCounts));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    if (s->counts_host[kErrSlot])
+    if (s->counts.host()[kErrSlot])
         return svo_fail(ctx, SVO_ERR_ARG, "a voxel coordinate is outside [0, 2^depth) (depth " + std::to_string(depth) + ")");
     return SVO_OK;
 }
@@ -590,7 +570,7 @@ int finish(svo_ctx *ctx, const svo_build_params *p, uint64_t leaf_bound, double 
     int rc = parent_passes(ctx, depth, 2, bound, nullptr, nullptr, 0);
     if (rc) return rc;
     if ((rc = read_counts(ctx, depth, 0))) return rc;
-    const uint32_t *m = s->counts_host;
+    const uint32_t *m = s->counts.host();
     const uint64_t limit = word_limit(ctx, p);
     if (m[depth] > s->items)  // (dense: more solid cells than the cap has words)
         return svo_fail(ctx, SVO_ERR_CAP, std::to_string(m[depth]) + " leaves cannot fit in " + std::to_string(limit) + " words");
@@ -605,17 +585,20 @@ int finish(svo_ctx *ctx, const svo_build_params *p, uint64_t leaf_bound, double 
     // emit: behind every earlier write to the store, whichever context issued it
     rc = svo_store_order_after_write(ctx);
     if (rc) return rc;
-    HIP_TRY(ctx, hipEventRecord(s->ev[kEvEmit], ctx->stream));
+    HIP_TRY(ctx, s->timer.mark(ctx, kEvEmit));
     HIP_TRY(ctx, hipMemsetD32Async((hipDeviceptr_t)ctx->nodes, (int)kEmptyWord, n_words, ctx->stream));
     rc = parent_passes(ctx, depth, 1, bound, ctx->nodes, base, n_words);
     if (rc) return rc;
-    HIP_TRY(ctx, hipEventRecord(s->ev[kEvEmitEnd], ctx->stream));
+    HIP_TRY(ctx, s->timer.mark(ctx, kEvEmitEnd));
     rc = svo_store_note_write(ctx);
     if (rc) return rc;
     *n_words_out = n_words;
-    s->ms[5] = float(svo_now_ms() - t0);
-    s->sorted = sorted;
-    s->timed = false;  // (the emit is still in flight: svo_build_timing reads the events)
+    for (int k = 0; k < 5; k++) {  // (dense: no sort)
+        const bool none = k == 1 && !sorted;
+        s->timer.span[k][0] = none ? nullptr : s->timer.ev[kBuildSlots[k].first];
+        s->timer.span[k][1] = none ? nullptr : s->timer.ev[kBuildSlots[k].last];
+    }
+    s->timer.finish(t0);
     return SVO_OK;
 }
 
@@ -627,10 +610,7 @@ int build_empty(svo_ctx *ctx, const svo_build_params *p, uint64_t *n_words_out) 
     HIP_TRY(ctx, hipMemsetD32Async((hipDeviceptr_t)ctx->nodes, (int)kEmptyWord, 8, ctx->stream));
     rc = svo_store_note_write(ctx);
     if (rc) return rc;
-    if (ctx->build) {
-        memset(ctx->build->ms, 0, sizeof ctx->build->ms);
-        ctx->build->timed = true;
-    }
+    if (ctx->build) ctx->build->timer.none();
     *n_words_out = 8;
     return SVO_OK;
 }
@@ -679,27 +659,24 @@ int svo_build_check_list(svo_ctx *ctx, const uint32_t *depth, const uint32_t *xy
 
 int svo_build_list_leaves(svo_ctx *ctx, const uint32_t *xyz, const uint32_t *colours, size_t n, uint32_t depth,
                           uint32_t default_colour, svo_build_leaves *out) {
-    if (ctx->build && !ctx->build->timed) {
-        float ms[SVO_BUILD_TIMES];
-        int rc = svo_build_timing(ctx, ms);
-        if (rc) return rc;
-    }
-    int rc = list_leaves(ctx, xyz, colours, n, depth, default_colour, 0, true);
+    int rc = ctx->build ? ctx->build->timer.begin(ctx) : SVO_OK;
+    if (rc) return rc;
+    rc = list_leaves(ctx, xyz, colours, n, depth, default_colour, 0, true);
     if (rc) return rc;
     svo_build_state *s = ctx->build.get();
     const uint32_t a = ((3 * depth + 7) / 8) & 1;  // the sort's result was in keys[a] / vals[a]: free again, like keys[a ^ 1]
     out->keys = s->keys[2];
     out->colours = s->leaf_colours;
     out->index = s->vals[a ^ 1];
-    out->count = s->counts + depth;
-    out->range_err = s->counts + kErrSlot;
+    out->count = s->counts.dev + depth;
+    out->range_err = s->counts.dev + kErrSlot;
     out->spare32 = s->vals[a];
     out->spare64[0] = s->keys[0];
     out->spare64[1] = s->keys[1];
     out->items = s->items;
-    out->ev_start = s->ev[kEvStart];
-    out->ev_keys = s->ev[kEvKeys];
-    out->ev_sort = s->ev[kEvSort];
+    out->ev_start = s->timer.ev[kEvStart];
+    out->ev_keys = s->timer.ev[kEvKeys];
+    out->ev_sort = s->timer.ev[kEvSort];
     return SVO_OK;
 }
 
@@ -733,7 +710,7 @@ int chunk_build(svo_ctx *ctx, const uint32_t *xyz, const uint32_t *colours, size
     ChunkPlan plan{wd, n_chunks, nullptr, 0};
     if ((rc = parent_passes(ctx, depth, std::max(wd, 1u), bound, nullptr, nullptr, 0, &plan))) return rc;
     if ((rc = read_counts(ctx, depth, runs_items))) return rc;
-    const uint32_t *m = s->counts_host;
+    const uint32_t *m = s->counts.host();
 
     // every chunk's local level bases (breadth-first: level 1 at 0, level L + 1 behind level L's groups) and its place
     const uint32_t stride = cd + 2;
@@ -772,21 +749,21 @@ int chunk_build(svo_ctx *ctx, const uint32_t *xyz, const uint32_t *colours, size
     // emit and mips
     HIP_TRY(ctx, hipMemcpyAsync(s->cbase, cbase.data(), cbase.size() * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(ctx, hipMemcpyAsync(s->coff, coff.data(), coff.size() * sizeof(uint64_t), hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(ctx, hipEventRecord(s->ev[kEvChunkEmit], ctx->stream));
+    HIP_TRY(ctx, s->timer.mark(ctx, kEvChunkEmit));
     build_fill_kernel<<<std::max(std::min(svo_div_up(total, kThreads), 65536u), 1u), kThreads, 0, ctx->stream>>>(s->nodes, total);
     HIP_TRY(ctx, hipGetLastError());
     for (uint32_t l = 1; l <= depth; l++) bound[l] = m[l];
     plan.nodes = s->nodes;
     plan.n_nodes = total;
     if ((rc = parent_passes(ctx, depth, wd + 1, bound, nullptr, nullptr, 0, &plan))) return rc;
-    HIP_TRY(ctx, hipEventRecord(s->ev[kEvChunkEmitEnd], ctx->stream));
+    HIP_TRY(ctx, s->timer.mark(ctx, kEvChunkEmitEnd));
     for (uint32_t l = depth - 1; l > wd; l--) {  // bottom-up; level `depth` is all leaves
         const uint32_t lanes = 8u * m[l - 1];
         build_mip_kernel<<<svo_div_up(lanes, kThreads), kThreads, 0, ctx->stream>>>(s->nodes, s->coff, s->cbase, s->runs + size_t(l - 1) * row,
                                                                                      n_chunks, stride, l - wd, lanes);
         HIP_TRY(ctx, hipGetLastError());
     }
-    HIP_TRY(ctx, hipEventRecord(s->ev[kEvChunkMips], ctx->stream));
+    HIP_TRY(ctx, s->timer.mark(ctx, kEvChunkMips));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
 
     // chunks in id order: (cx * side + cy) * side + cz, chunk index = Morton code of (cx, cy, cz)
@@ -801,10 +778,10 @@ int chunk_build(svo_ctx *ctx, const uint32_t *xyz, const uint32_t *colours, size
         HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
         copy_ms += svo_now_ms() - t;
         t = svo_now_ms();
-        if ((rc = take(id, (const uint8_t *)s->stage, nodes))) return rc;
+        if ((rc = take(id, (const uint8_t *)s->stage.get(), nodes))) return rc;
         take_ms += svo_now_ms() - t;
     }
-    for (int k = 0; k < 6; k++) HIP_TRY(ctx, hipEventElapsedTime(&s->cms[k], s->ev[kChunkSlots[k].first], s->ev[kChunkSlots[k].last]));
+    for (int k = 0; k < 6; k++) HIP_TRY(ctx, hipEventElapsedTime(&s->cms[k], s->timer.ev[kChunkSlots[k].first], s->timer.ev[kChunkSlots[k].last]));
     s->cms[6] = float(copy_ms);
     s->cms[7] = float(take_ms);
     s->cms[8] = float(svo_now_ms() - t0);
@@ -878,7 +855,7 @@ int svo_nodes_build(svo_ctx *ctx, const uint32_t *xyz, const uint32_t *colours, 
     int rc = check_list(ctx, p ? &p->depth : nullptr, nullptr, false, xyz, n);
     if (rc) return rc;
     if (!n_words_out) return svo_fail(ctx, SVO_ERR_ARG, "null n_words_out");
-    if ((rc = check_store(ctx))) return rc;
+    if ((rc = svo_check_store(ctx))) return rc;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     if (!n) return build_empty(ctx, p, n_words_out);
     const double t0 = svo_now_ms();
@@ -893,7 +870,7 @@ int svo_nodes_build_dense(svo_ctx *ctx, const uint32_t *grid, const svo_build_pa
     if (rc) return rc;
     if (!grid) return svo_fail(ctx, SVO_ERR_ARG, "null grid");
     if (!n_words_out) return svo_fail(ctx, SVO_ERR_ARG, "null n_words_out");
-    if ((rc = check_store(ctx))) return rc;
+    if ((rc = svo_check_store(ctx))) return rc;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const double t0 = svo_now_ms();
     const uint32_t depth = p->depth;
@@ -903,10 +880,10 @@ int svo_nodes_build_dense(svo_ctx *ctx, const uint32_t *grid, const svo_build_pa
     const uint64_t room = std::max<uint64_t>(std::min(cells, word_limit(ctx, p)), 1);
     if ((rc = ensure_state(ctx, room, cells, 0))) return rc;
     svo_build_state *s = ctx->build.get();
-    HIP_TRY(ctx, hipEventRecord(s->ev[kEvStart], ctx->stream));
-    HIP_TRY(ctx, hipMemsetAsync(s->counts, 0, kCountSlots * sizeof(uint32_t), ctx->stream));
-    HIP_TRY(ctx, hipEventRecord(s->ev[kEvKeys], ctx->stream));
-    HIP_TRY(ctx, hipEventRecord(s->ev[kEvSort], ctx->stream));
+    HIP_TRY(ctx, s->timer.mark(ctx, kEvStart));
+    HIP_TRY(ctx, s->counts.zero(ctx));
+    HIP_TRY(ctx, s->timer.mark(ctx, kEvKeys));
+    HIP_TRY(ctx, s->timer.mark(ctx, kEvSort));
     LevelIn in{};
     in.colours = grid;
     in.m_max = (uint32_t)cells;
@@ -915,26 +892,14 @@ int svo_nodes_build_dense(svo_ctx *ctx, const uint32_t *grid, const svo_build_pa
     out.keys = s->keys[2];
     out.colours = s->leaf_colours;
     out.cap = (uint32_t)s->items;
-    if ((rc = level_pass<kDense>(ctx, in, out, cells, s->counts + depth))) return rc;
+    if ((rc = level_pass<kDense>(ctx, in, out, cells, s->counts.dev + depth))) return rc;
     return finish(ctx, p, cells, t0, false, n_words_out);
 }
 
 int svo_build_timing(svo_ctx *ctx, float ms_out[SVO_BUILD_TIMES]) {
     if (!ctx || !ms_out) return SVO_ERR_ARG;
     if (!ctx->build) return svo_fail(ctx, SVO_ERR_STATE, "no tree built on this context yet");
-    svo_build_state *s = ctx->build.get();
-    if (!s->timed) {
-        HIP_TRY(ctx, hipSetDevice(ctx->device));
-        HIP_TRY(ctx, hipEventSynchronize(s->ev[kEvEmitEnd]));
-        for (int k = 0; k < 5; k++) {
-            s->ms[k] = 0.0f;
-            if (k == 1 && !s->sorted) continue;  // (dense: no sort)
-            HIP_TRY(ctx, hipEventElapsedTime(&s->ms[k], s->ev[kBuildSlots[k].first], s->ev[kBuildSlots[k].last]));
-        }
-        s->timed = true;
-    }
-    memcpy(ms_out, ctx->build->ms, sizeof ctx->build->ms);
-    return SVO_OK;
+    return ctx->build->timer.read(ctx, ms_out);
 }
 
 int svo_cpu_octree_build(svo_ctx *ctx, const uint32_t *xyz, const uint32_t *colours, size_t n, const svo_chunk_build_params *p,

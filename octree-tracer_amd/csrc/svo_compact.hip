@@ -23,17 +23,15 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <cstring>
 #include <string>
 #include <vector>
 
 #include "svo_ctx.h"
-#include "svo_group.h"  // (group_lane: 8 lanes per group)
+#include "svo_group.h"  // (group_lane: 8 lanes per group; kMaxWords)
 #include "svo_scan.h"   // (kThreads)
 
 namespace {
 
-constexpr uint64_t kMaxWords = SVO_VOXEL_OFFSET;  // 2^27: no pointer reaches further
 constexpr uint32_t kMaxLevels = 31;               // as svo_nodes_relayout and svo_nodes_max_depth
 // the words read back: the discovery's (svo_ctx.h), then the compaction's own
 enum Status { kStAlign = SVO_WALK_ALIGN, kStRange = SVO_WALK_RANGE, kStNext = SVO_WALK_NEXT, kStDup = SVO_WALK_DUP, kStLive = SVO_WALK_STATUS, kStWords };
@@ -116,48 +114,28 @@ enum Ev { kEvStart, kEvDiscover, kEvCheck, kEvPrune, kEvEmit, kEvEnd, kEvs };
 
 // Per-context workspace of the compaction (svo_ctx::compact): the image and five u32 per group.
 struct svo_compact_state {
-    uint32_t *image = nullptr;  // the compacted words before they are copied back
+    svo_dev<uint32_t> image;  // the compacted words before they are copied back
     size_t image_items = 0;
-    uint32_t *order = nullptr, *first_child = nullptr, *new_of = nullptr, *live = nullptr, *number = nullptr;
+    svo_dev<uint32_t> order, first_child, new_of, live, number;
     size_t group_items = 0;
-    uint32_t *status = nullptr, *status_host = nullptr;  // kStWords words (device / pinned)
-    hipEvent_t ev[kEvs] = {};
-    bool timed = true;
-    float ms[SVO_COMPACT_TIMES] = {};
+    svo_mirrored<> status;  // kStWords words
+    svo_pass_timer<kEvs, SVO_COMPACT_TIMES> timer;
 
-    ~svo_compact_state() {
-        for (uint32_t *p : {image, order, first_child, new_of, live, number, status})
-            if (p) (void)hipFree(p);
-        if (status_host) (void)hipHostFree(status_host);
-        for (hipEvent_t e : ev)
-            if (e) (void)hipEventDestroy(e);
+    int create(svo_ctx *ctx) {
+        HIP_TRY(ctx, timer.create());
+        return status.alloc(ctx, kStWords);
     }
 };
 
 namespace {
 
 int ensure_state(svo_ctx *ctx, size_t words, size_t groups) {
-    if (!ctx->compact) {  // the context gets the state only when all of it exists (a failure frees what there is)
-        svo_workspace<svo_compact_state> fresh = svo_workspace_new<svo_compact_state>();
-        for (hipEvent_t &e : fresh->ev) HIP_TRY(ctx, hipEventCreate(&e));
-        HIP_TRY(ctx, hipHostMalloc((void **)&fresh->status_host, kStWords * sizeof(uint32_t), hipHostMallocDefault));
-        HIP_TRY(ctx, hipMalloc((void **)&fresh->status, kStWords * sizeof(uint32_t)));
-        ctx->compact = std::move(fresh);
-    }
+    int rc = svo_workspace_ensure(ctx, ctx->compact);
+    if (rc) return rc;
     svo_compact_state *s = ctx->compact.get();
-    int rc = svo_grow(ctx, &s->image_items, words, &s->image);
+    rc = svo_grow(ctx, &s->image_items, words, &s->image);
     if (!rc) rc = svo_grow(ctx, &s->group_items, groups, &s->order, &s->first_child, &s->new_of, &s->live, &s->number);
     return rc;
-}
-
-int read_status(svo_ctx *ctx, uint32_t *host, const uint32_t *dev, size_t words) {
-    HIP_TRY(ctx, hipMemcpyAsync(host, dev, words * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    return SVO_OK;
-}
-int read_status(svo_ctx *ctx) {
-    svo_compact_state *s = ctx->compact.get();
-    return read_status(ctx, s->status_host, s->status, kStWords);
 }
 
 int malformed(svo_ctx *ctx, const std::string &why) { return svo_fail(ctx, SVO_ERR_STATE, "malformed tree: " + why); }
@@ -169,7 +147,7 @@ int malformed(svo_ctx *ctx, const std::string &why) { return svo_fail(ctx, SVO_E
 int svo_tree_discover(svo_ctx *ctx, uint64_t n_words_in, svo_tree_walk *w, hipEvent_t discovered) {
     // no pointer reaches a group behind 2^27, so the words behind it hold no reachable group
     const uint32_t n_words = (uint32_t)std::min<uint64_t>(n_words_in, kMaxWords), cap = n_words / 8;
-    const uint32_t *st = w->status_host;
+    const uint32_t *st = w->status.host();
     int rc;
     HIP_TRY(ctx, hipMemsetAsync(w->order, 0, sizeof(uint32_t), ctx->stream));  // level 1: group 0
 
@@ -180,12 +158,12 @@ int svo_tree_discover(svo_ctx *ctx, uint64_t n_words_in, svo_tree_walk *w, hipEv
     for (uint32_t level = 1;; level++) {
         level_off.push_back(off);
         const uint32_t grid = svo_div_up(8ull * n, kThreads);
-        compact_count_kernel<<<grid, kThreads, 0, ctx->stream>>>(ctx->nodes, n_words, w->order + off, n, w->scan, w->status);
+        compact_count_kernel<<<grid, kThreads, 0, ctx->stream>>>(ctx->nodes, n_words, w->order + off, n, w->scan, w->status.dev);
         HIP_TRY(ctx, hipGetLastError());
         if ((rc = svo_build_scan_u32(ctx, w->scan, n))) return rc;
-        compact_scatter_kernel<<<grid, kThreads, 0, ctx->stream>>>(ctx->nodes, w->order, off, n, w->scan, w->first_child, cap, w->status);
+        compact_scatter_kernel<<<grid, kThreads, 0, ctx->stream>>>(ctx->nodes, w->order, off, n, w->scan, w->first_child, cap, w->status.dev);
         HIP_TRY(ctx, hipGetLastError());
-        if ((rc = read_status(ctx, w->status_host, w->status, w->status_words))) return rc;
+        if ((rc = w->status.read(ctx))) return rc;
         if (st[kStAlign]) return malformed(ctx, "an interior pointer at level " + std::to_string(level) + " is not a multiple of 8");
         if (st[kStRange])
             return malformed(ctx, "an interior pointer at level " + std::to_string(level) + " leaves the first n_words = " +
@@ -206,7 +184,7 @@ int svo_tree_discover(svo_ctx *ctx, uint64_t n_words_in, svo_tree_walk *w, hipEv
     // check (the verdict is in status[SVO_WALK_DUP] at the caller's next read-back)
     const uint32_t group_grid = svo_div_up(total, kThreads);
     compact_mark_kernel<<<group_grid, kThreads, 0, ctx->stream>>>(w->order, total, w->new_of);
-    compact_check_kernel<<<group_grid, kThreads, 0, ctx->stream>>>(w->order, total, w->new_of, w->status);
+    compact_check_kernel<<<group_grid, kThreads, 0, ctx->stream>>>(w->order, total, w->new_of, w->status.dev);
     HIP_TRY(ctx, hipGetLastError());
     return SVO_OK;
 }
@@ -218,39 +196,33 @@ int svo_nodes_compact(svo_ctx *ctx, const svo_compact_params *p, uint32_t *perm_
     if (n_words_out) *n_words_out = 0;
     if (!p) return svo_fail(ctx, SVO_ERR_ARG, "null params");
     if (!n_words_out) return svo_fail(ctx, SVO_ERR_ARG, "null n_words_out");
-    if (p->flags & ~SVO_COMPACT_PRUNE_EMPTY) return svo_fail(ctx, SVO_ERR_ARG, "unknown flag bits " + std::to_string(p->flags));
-    if (!ctx->store) return svo_fail(ctx, SVO_ERR_STATE, "svo_nodes_alloc / svo_nodes_bind_device not called");
+    int rc = svo_check_flags(ctx, p->flags, SVO_COMPACT_PRUNE_EMPTY);
+    if (rc || (rc = svo_check_store(ctx))) return rc;
     if (ctx->adapt)
         return svo_fail(ctx, SVO_ERR_STATE, "a device adaptive state is attached: its positions and hole stack index the layout "
                                             "that a compaction replaces");
-    if (p->n_words < 8 || p->n_words % 8 || p->n_words > ctx->capacity)
-        return svo_fail(ctx, SVO_ERR_ARG, "n_words must be a positive multiple of 8 within the node buffer's capacity (got " +
-                                              std::to_string(p->n_words) + ", capacity " + std::to_string(ctx->capacity) + ")");
+    if ((rc = svo_check_n_words(ctx, p->n_words))) return rc;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const double t0 = svo_now_ms();
     // no pointer reaches a group behind 2^27, so the words behind it hold no reachable group
     const uint32_t n_words = (uint32_t)std::min<uint64_t>(p->n_words, kMaxWords), cap = n_words / 8;
-    int rc = ensure_state(ctx, n_words, cap);
-    if (rc) return rc;
+    if ((rc = ensure_state(ctx, n_words, cap))) return rc;
     svo_compact_state *s = ctx->compact.get();
-    if (!s->timed) {  // the events are recorded again below: the last compaction's times are taken first, so that a refused
-        float ms[SVO_COMPACT_TIMES];  // call leaves svo_compact_timing with the times of the last one that ran
-        if ((rc = svo_compact_timing(ctx, ms))) return rc;
-    }
-    const uint32_t *st = s->status_host;
+    if ((rc = s->timer.begin(ctx))) return rc;
+    const uint32_t *st = s->status.host();
     const bool prune = p->flags & SVO_COMPACT_PRUNE_EMPTY;
 
     // the passes read the words: behind every earlier write to the store, whichever context issued it
     if ((rc = svo_store_order_after_write(ctx))) return rc;
-    HIP_TRY(ctx, hipEventRecord(s->ev[kEvStart], ctx->stream));
-    HIP_TRY(ctx, hipMemsetAsync(s->status, 0, kStWords * sizeof(uint32_t), ctx->stream));
+    HIP_TRY(ctx, s->timer.mark(ctx, kEvStart));
+    HIP_TRY(ctx, s->status.zero(ctx));
     // discover and check
-    svo_tree_walk walk{s->order, s->first_child, s->new_of, s->number, s->status, s->status_host, kStWords, {}};
-    if ((rc = svo_tree_discover(ctx, p->n_words, &walk, s->ev[kEvDiscover]))) return rc;
+    svo_tree_walk walk{s->order, s->first_child, s->new_of, s->number, s->status, {}};
+    if ((rc = svo_tree_discover(ctx, p->n_words, &walk, s->timer.ev[kEvDiscover]))) return rc;
     const std::vector<uint32_t> &level_off = walk.level_off;
     const uint32_t n_levels = (uint32_t)level_off.size() - 1, total = level_off[n_levels];
     const uint32_t word_grid = svo_div_up(8ull * total, kThreads);
-    HIP_TRY(ctx, hipEventRecord(s->ev[kEvCheck], ctx->stream));
+    HIP_TRY(ctx, s->timer.mark(ctx, kEvCheck));
 
     // prune
     if (prune) {
@@ -263,47 +235,38 @@ int svo_nodes_compact(svo_ctx *ctx, const svo_compact_params *p, uint32_t *perm_
     } else {
         HIP_TRY(ctx, hipMemsetD32Async((hipDeviceptr_t)s->live, 1, total, ctx->stream));
     }
-    HIP_TRY(ctx, hipEventRecord(s->ev[kEvPrune], ctx->stream));
+    HIP_TRY(ctx, s->timer.mark(ctx, kEvPrune));
 
     // emit
     HIP_TRY(ctx, hipMemcpyAsync(s->number, s->live, total * sizeof(uint32_t), hipMemcpyDeviceToDevice, ctx->stream));
     if ((rc = svo_build_scan_u32(ctx, s->number, total))) return rc;
-    compact_total_kernel<<<1, 1, 0, ctx->stream>>>(s->number, s->live, total, s->status);
+    compact_total_kernel<<<1, 1, 0, ctx->stream>>>(s->number, s->live, total, s->status.dev);
     HIP_TRY(ctx, hipGetLastError());
-    if ((rc = read_status(ctx))) return rc;
+    if ((rc = s->status.read(ctx))) return rc;
     if (st[kStDup]) return malformed(ctx, "a group is reached twice");
     const uint32_t n_out = 8u * st[kStLive];
     if (!n_out || n_out > n_words) return svo_fail(ctx, SVO_ERR_HIP, "the live groups' scan is out of range");  // (never: live[0] = 1)
     compact_emit_kernel<<<word_grid, kThreads, 0, ctx->stream>>>(ctx->nodes, s->order, total, s->first_child, s->live, s->number, n_out,
                                                                 s->image, perm_out_dev);
     HIP_TRY(ctx, hipGetLastError());
-    HIP_TRY(ctx, hipEventRecord(s->ev[kEvEmit], ctx->stream));
+    HIP_TRY(ctx, s->timer.mark(ctx, kEvEmit));
 
     // copy back: behind every earlier write to the store (another context may have written while this one waited)
     if ((rc = svo_store_order_after_write(ctx))) return rc;
     HIP_TRY(ctx, hipMemcpyAsync(ctx->nodes, s->image, size_t(n_out) * sizeof(uint32_t), hipMemcpyDeviceToDevice, ctx->stream));
     if (p->n_words > n_out)
         HIP_TRY(ctx, hipMemsetD32Async((hipDeviceptr_t)(ctx->nodes + n_out), (int)kEmptyWord, p->n_words - n_out, ctx->stream));
-    HIP_TRY(ctx, hipEventRecord(s->ev[kEvEnd], ctx->stream));
+    HIP_TRY(ctx, s->timer.mark(ctx, kEvEnd));
     if ((rc = svo_store_note_write(ctx))) return rc;
     *n_words_out = n_out;
-    s->ms[5] = float(svo_now_ms() - t0);
-    s->timed = false;  // (the copy is still in flight: svo_compact_timing reads the events)
+    s->timer.finish(t0);
     return SVO_OK;
 }
 
 int svo_compact_timing(svo_ctx *ctx, float ms_out[SVO_COMPACT_TIMES]) {
     if (!ctx || !ms_out) return SVO_ERR_ARG;
     if (!ctx->compact) return svo_fail(ctx, SVO_ERR_STATE, "no tree compacted on this context yet");
-    svo_compact_state *s = ctx->compact.get();
-    if (!s->timed) {
-        HIP_TRY(ctx, hipSetDevice(ctx->device));
-        HIP_TRY(ctx, hipEventSynchronize(s->ev[kEvEnd]));
-        for (int k = 0; k < 5; k++) HIP_TRY(ctx, hipEventElapsedTime(&s->ms[k], s->ev[k], s->ev[k + 1]));
-        s->timed = true;
-    }
-    memcpy(ms_out, s->ms, sizeof s->ms);
-    return SVO_OK;
+    return ctx->compact->timer.read(ctx, ms_out);
 }
 
 }  // extern "C"

@@ -1,14 +1,19 @@
 // svo_ctx.h -- the device context behind the opaque `svo_ctx` of include/svo_hip.h, and the host helpers of the files that
 // use it: svo_abi.cpp (trace / scan dispatch), svo_comm.cpp (RCCL frame gather) and the GPU tree passes (svo_proc.hip,
-// svo_build.hip, svo_edit.hip, svo_compact.hip, svo_list.hip, svo_sample.hip, svo_voxelize.hip, svo_adapt.hip).  Shared by the passes: svo_grow / svo_grow_pinned / svo_grow_keep (workspaces), the builder's sort
-// and scan, svo_world_writer (a generated world's directory); svo_scan.h, svo_mip.h and svo_morton.h hold the device pieces,
-// svo_rules.h the walks and rules that svo_host.cpp and svo_adapt.hip both run.
+// svo_build.hip, svo_edit.hip, svo_compact.hip, svo_list.hip, svo_sample.hip, svo_voxelize.hip, svo_adapt.hip).  Shared by
+// the passes, as their host frame: svo_dev / svo_pinned / svo_events (owning members of a pass's state), svo_grow /
+// svo_grow_pinned / svo_grow_keep (workspaces), svo_mirrored (device words with a pinned mirror), svo_pass_timer (events
+// and times), svo_workspace_ensure (creation) and the svo_check_* argument checks; then the builder's sort and scan and
+// svo_world_writer (a generated world's directory).  svo_scan.h, svo_group.h, svo_mip.h and svo_morton.h hold the device
+// pieces, svo_rules.h the walks and rules that svo_host.cpp and svo_adapt.hip both run.
 // Internal: not part of the boundary.
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <chrono>
 #include <cstdint>
+#include <cstring>
 #include <memory>
 #include <string>
 #include <type_traits>
@@ -34,8 +39,8 @@ struct svo_node_store {
     hipStream_t last_writer = nullptr; // that stream: other streams wait for the event before they read
 };
 
-// The workspace of a GPU pass, kept per context and freed by its destructor.  Its type is complete only in the pass's own
-// file, so the deleter is bound there, by svo_workspace_new.
+// The workspace of a GPU pass, kept per context and freed with it (svo_ctx_destroy), member by member.  Its type is
+// complete only in the pass's own file, so the deleter is bound there, by svo_workspace_new.
 struct svo_proc_state;
 struct svo_build_state;
 struct svo_adapt_state;
@@ -151,9 +156,55 @@ inline double svo_now_ms() {
 // blocks of `per` items that cover n
 inline uint32_t svo_div_up(uint64_t n, uint64_t per) { return (uint32_t)((n + per - 1) / per); }
 
+// ---- the host frame of a GPU pass: owning members, status words, the timer, creation, shared checks ----
+
+// One device (or pinned host) allocation: freed with its owner, moved but not copied, a T* wherever one is wanted.
+template <typename T, bool kPinned>
+struct svo_mem {
+    T *p = nullptr;
+    svo_mem() = default;
+    svo_mem(svo_mem &&o) noexcept : p(o.p) { o.p = nullptr; }
+    svo_mem &operator=(svo_mem &&o) noexcept {
+        std::swap(p, o.p);
+        return *this;
+    }
+    ~svo_mem() { reset(); }
+    void reset() {
+        if (p) (void)(kPinned ? hipHostFree(p) : hipFree(p));
+        p = nullptr;
+    }
+    T *get() const { return p; }
+    operator T *() const { return p; }
+    T *operator->() const { return p; }
+};
+template <typename T>
+using svo_dev = svo_mem<T, false>;
+template <typename T>
+using svo_pinned = svo_mem<T, true>;
+
+// N events, created together and destroyed with their owner.
+template <int N>
+struct svo_events {
+    hipEvent_t e[N] = {};
+    svo_events() = default;
+    svo_events(const svo_events &) = delete;
+    svo_events &operator=(const svo_events &) = delete;
+    ~svo_events() {
+        for (hipEvent_t x : e)
+            if (x) (void)hipEventDestroy(x);
+    }
+    hipError_t create() {
+        for (hipEvent_t &x : e)
+            if (hipError_t err = hipEventCreate(&x)) return err;
+        return hipSuccess;
+    }
+    hipEvent_t operator[](int k) const { return e[k]; }
+};
+
 // Grows a group of buffers to `want` items of its own type each (a void buffer counts bytes): when *have < want, waits
 // for the context's stream, frees all of them and allocates them again; *have becomes `want` only when every allocation
-// succeeded.  svo_grow allocates device memory, svo_grow_pinned pinned host memory.
+// succeeded.  svo_grow allocates device memory, for raw pointers (the context's own buffers) or owning members;
+// svo_grow_pinned pinned host memory, for owning members.
 template <typename... T>
 int svo_grow_group(svo_ctx *ctx, bool pinned, size_t *have, size_t want, T **...bufs) {
     if (*have >= want) return SVO_OK;
@@ -172,20 +223,122 @@ int svo_grow_group(svo_ctx *ctx, bool pinned, size_t *have, size_t want, T **...
 template <typename... T>
 int svo_grow(svo_ctx *ctx, size_t *have, size_t want, T **...bufs) { return svo_grow_group(ctx, false, have, want, bufs...); }
 template <typename... T>
-int svo_grow_pinned(svo_ctx *ctx, size_t *have, size_t want, T **...bufs) { return svo_grow_group(ctx, true, have, want, bufs...); }
+int svo_grow(svo_ctx *ctx, size_t *have, size_t want, svo_dev<T> *...bufs) { return svo_grow_group(ctx, false, have, want, &bufs->p...); }
+template <typename... T>
+int svo_grow_pinned(svo_ctx *ctx, size_t *have, size_t want, svo_pinned<T> *...bufs) { return svo_grow_group(ctx, true, have, want, &bufs->p...); }
 
 // svo_grow for one device buffer whose first `keep` items stay: they are copied on the context's stream, which is waited
 // for before the old buffer is freed
 template <typename T>
-int svo_grow_keep(svo_ctx *ctx, size_t *have, size_t want, T **buf, size_t keep) {
+int svo_grow_keep(svo_ctx *ctx, size_t *have, size_t want, svo_dev<T> *buf, size_t keep) {
     if (*have >= want) return SVO_OK;
-    T *bigger = nullptr;
-    HIP_TRY(ctx, hipMalloc((void **)&bigger, want * sizeof(T)));
+    svo_dev<T> bigger;
+    HIP_TRY(ctx, hipMalloc((void **)&bigger.p, want * sizeof(T)));
     if (keep) HIP_TRY(ctx, hipMemcpyAsync(bigger, *buf, keep * sizeof(T), hipMemcpyDeviceToDevice, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    (void)hipFree(*buf);
-    *buf = bigger;
+    *buf = std::move(bigger);  // (a swap: the old buffer goes with `bigger`)
     *have = want;
+    return SVO_OK;
+}
+
+// n items on the device that kernels write, and their pinned mirror that the host reads after read().
+template <typename T = uint32_t>
+struct svo_mirrored {
+    svo_dev<T> dev;
+    svo_pinned<T> mirror;
+    size_t n = 0;
+    int alloc(svo_ctx *ctx, size_t items) {
+        HIP_TRY(ctx, hipHostMalloc((void **)&mirror.p, items * sizeof(T), hipHostMallocDefault));
+        HIP_TRY(ctx, hipMalloc((void **)&dev.p, items * sizeof(T)));
+        n = items;
+        return SVO_OK;
+    }
+    hipError_t zero(svo_ctx *ctx) { return hipMemsetAsync(dev, 0, n * sizeof(T), ctx->stream); }
+    // the first `items` of them (all by default) into the mirror: enqueued by copy(), there after read()
+    hipError_t copy(svo_ctx *ctx, size_t items = ~size_t(0)) {
+        return hipMemcpyAsync(mirror, dev, std::min(items, n) * sizeof(T), hipMemcpyDeviceToHost, ctx->stream);
+    }
+    int read(svo_ctx *ctx, size_t items = ~size_t(0)) {
+        HIP_TRY(ctx, copy(ctx, items));
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        return SVO_OK;
+    }
+    T *host() const { return mirror; }
+};
+
+// The events of a pass and the times read from them: ms[k] is the time from span[k][0] to span[k][1] (a null span: 0 ms),
+// the last slot the host's wall time.  The spans are consecutive events unless the pass sets others; the last span ends
+// at the pass's last event.  Between finish() and read() the times are pending: begin() takes them before a new run
+// records the events again, so a refused call leaves the times of the last run that completed.
+template <int kEvents, int kTimes>
+struct svo_pass_timer {
+    svo_events<kEvents> ev;
+    hipEvent_t span[kTimes - 1][2] = {};
+    bool timed = true;
+    float ms[kTimes] = {};
+
+    hipError_t create() {
+        const hipError_t err = ev.create();
+        for (int k = 0; k < kTimes - 1 && k + 1 < kEvents; k++) span[k][0] = ev[k], span[k][1] = ev[k + 1];
+        return err;
+    }
+    int begin(svo_ctx *ctx) {
+        float unused[kTimes];
+        return timed ? SVO_OK : read(ctx, unused);
+    }
+    hipError_t mark(svo_ctx *ctx, int k) { return hipEventRecord(ev[k], ctx->stream); }
+    void finish(double t0) {
+        ms[kTimes - 1] = float(svo_now_ms() - t0);
+        timed = false;  // (the pass is still in flight: read() waits for the events)
+    }
+    void none() {  // a run that had nothing to do
+        memset(ms, 0, sizeof ms);
+        timed = true;
+    }
+    int read(svo_ctx *ctx, float *ms_out) {
+        if (!timed) {
+            HIP_TRY(ctx, hipSetDevice(ctx->device));
+            HIP_TRY(ctx, hipEventSynchronize(span[kTimes - 2][1]));
+            for (int k = 0; k < kTimes - 1; k++) {
+                ms[k] = 0.0f;
+                if (span[k][0]) HIP_TRY(ctx, hipEventElapsedTime(&ms[k], span[k][0], span[k][1]));
+            }
+            timed = true;
+        }
+        memcpy(ms_out, ms, sizeof ms);
+        return SVO_OK;
+    }
+};
+
+// A pass's state comes to the context only when all of it exists: S::create(ctx) makes the events and the fixed
+// allocations, and a failure half way frees what there is and leaves the slot null.
+template <typename S>
+int svo_workspace_ensure(svo_ctx *ctx, svo_workspace<S> &slot) {
+    if (slot) return SVO_OK;
+    svo_workspace<S> fresh = svo_workspace_new<S>();
+    if (int rc = fresh->create(ctx)) return rc;
+    slot = std::move(fresh);
+    return SVO_OK;
+}
+
+// The argument checks that the passes over the node buffer share, with one message each.
+inline int svo_check_store(svo_ctx *ctx) {
+    if (!ctx->store) return svo_fail(ctx, SVO_ERR_STATE, "svo_nodes_alloc / svo_nodes_bind_device not called");
+    return SVO_OK;
+}
+inline int svo_check_n_words(svo_ctx *ctx, uint64_t n_words) {
+    if (n_words < 8 || n_words % 8 || n_words > ctx->capacity)
+        return svo_fail(ctx, SVO_ERR_ARG, "n_words must be a positive multiple of 8 within the node buffer's capacity (got " +
+                                              std::to_string(n_words) + ", capacity " + std::to_string(ctx->capacity) + ")");
+    return SVO_OK;
+}
+inline int svo_check_depth(svo_ctx *ctx, uint32_t depth, uint32_t max) {
+    if (depth < 1 || depth > max)
+        return svo_fail(ctx, SVO_ERR_ARG, "depth must be 1.." + std::to_string(max) + " (got " + std::to_string(depth) + ")");
+    return SVO_OK;
+}
+inline int svo_check_flags(svo_ctx *ctx, uint32_t flags, uint32_t known) {
+    if (flags & ~known) return svo_fail(ctx, SVO_ERR_ARG, "unknown flag bits " + std::to_string(flags));
     return SVO_OK;
 }
 
@@ -220,8 +373,8 @@ int svo_build_list_leaves(svo_ctx *ctx, const uint32_t *xyz, const uint32_t *col
 // svo_compact.hip
 // The discovery of the tree in the first n_words words of the node buffer, for the
 // compaction and the voxel listing (svo_list.hip), on the ctx stream.  The caller owns the workspace: order, first_child,
-// new_of and scan of n_words / 8 u32 each, and status words (device / pinned mirror) that it has zeroed on the stream;
-// the first SVO_WALK_STATUS of them are the discovery's, status_words of them come back once per level.  Afterwards
+// new_of and scan of n_words / 8 u32 each, and status words that it has zeroed on the stream; the first SVO_WALK_STATUS
+// of them are the discovery's, and all of them come back once per level.  Afterwards
 // order[level_off[l], level_off[l + 1]) holds the old group starts of level l + 1 in the order of their parents,
 // first_child[k] the index in order of group k's first interior child, and level_off has one entry per level and the
 // total.  `discovered` (or null) is recorded before the check; the check's verdict is status[SVO_WALK_DUP] at the
@@ -229,8 +382,7 @@ int svo_build_list_leaves(svo_ctx *ctx, const uint32_t *xyz, const uint32_t *col
 enum { SVO_WALK_ALIGN, SVO_WALK_RANGE, SVO_WALK_NEXT, SVO_WALK_DUP, SVO_WALK_STATUS };
 struct svo_tree_walk {
     uint32_t *order, *first_child, *new_of, *scan;
-    uint32_t *status, *status_host;
-    size_t status_words;
+    svo_mirrored<> &status;
     std::vector<uint32_t> level_off;
 };
 int svo_tree_discover(svo_ctx *ctx, uint64_t n_words, svo_tree_walk *w, hipEvent_t discovered);

@@ -27,12 +27,10 @@
 
 #include "svo_ctx.h"
 #include "svo_morton.h"  // (the key's convention; the refused voxel's cell)
-#include "svo_scan.h"    // (kThreads, block_exclusive_scan, input_count)
+#include "svo_scan.h"    // (kThreads, block_exclusive_scan, input_count; svo_group.h: kEmptyWord, kMaxWords)
 
 namespace {
 
-constexpr uint32_t kEmptyWord = SVO_VOXEL_OFFSET << 4;
-constexpr uint64_t kMaxWords = SVO_VOXEL_OFFSET;  // 2^27: pointers and colours must stay apart
 constexpr uint32_t kNone = 0xFFFFFFFFu;
 constexpr uint32_t kMalformed = 1u << 31;  // in a block's first untakeable voxel: its walk left the tree
 enum Status { kStCount, kStRange, kStGroups, kStBad, kStIndex, kStKeyLo, kStKeyHi, kStWords };  // the words read back
@@ -155,34 +153,16 @@ enum Ev { kEvPlan, kEvRead, kEvFill, kEvEnd, kEvs };
 
 // Per-context workspace of the edit (svo_ctx::edit).  The per-voxel arrays live in the builder's workspace, in the sort
 // buffers its front end no longer needs (svo_build_leaves::spare32 / spare64); what is the edit's own is the status words
-// and the events.
+// and the events.  The first three spans of its times run between the builder's events, which the front end hands out.
 struct svo_edit_state {
-    uint32_t *status = nullptr, *status_host = nullptr;  // kStWords words (device / pinned)
-    hipEvent_t ev[kEvs] = {};
-    hipEvent_t ev_start = nullptr, ev_keys = nullptr, ev_sort = nullptr;  // the builder's, of the last edit's front end
-    bool timed = true;
-    float ms[SVO_EDIT_TIMES] = {};
+    svo_mirrored<> status;  // kStWords words
+    svo_pass_timer<kEvs, SVO_EDIT_TIMES> timer;
 
-    ~svo_edit_state() {
-        if (status) (void)hipFree(status);
-        if (status_host) (void)hipHostFree(status_host);
-        for (hipEvent_t e : ev)
-            if (e) (void)hipEventDestroy(e);
+    int create(svo_ctx *ctx) {
+        HIP_TRY(ctx, timer.create());
+        return status.alloc(ctx, kStWords);
     }
 };
-
-namespace {
-
-int ensure_state(svo_ctx *ctx) {
-    if (ctx->edit) return SVO_OK;
-    ctx->edit = svo_workspace_new<svo_edit_state>();
-    for (hipEvent_t &e : ctx->edit->ev) HIP_TRY(ctx, hipEventCreate(&e));
-    HIP_TRY(ctx, hipHostMalloc((void **)&ctx->edit->status_host, kStWords * sizeof(uint32_t), hipHostMallocDefault));
-    HIP_TRY(ctx, hipMalloc((void **)&ctx->edit->status, kStWords * sizeof(uint32_t)));
-    return SVO_OK;
-}
-
-}  // namespace
 
 extern "C" {
 
@@ -192,20 +172,17 @@ int svo_nodes_edit(svo_ctx *ctx, const uint32_t *xyz, const uint32_t *colours, s
     int rc = svo_build_check_list(ctx, p ? &p->depth : nullptr, xyz, n);
     if (rc) return rc;
     if (!n_words_out) return svo_fail(ctx, SVO_ERR_ARG, "null n_words_out");
-    if (!ctx->store) return svo_fail(ctx, SVO_ERR_STATE, "svo_nodes_alloc / svo_nodes_bind_device not called");
-    if (p->n_words < 8 || p->n_words % 8 || p->n_words > ctx->capacity)
-        return svo_fail(ctx, SVO_ERR_ARG, "n_words must be a positive multiple of 8 within the node buffer's capacity (got " +
-                                              std::to_string(p->n_words) + ", capacity " + std::to_string(ctx->capacity) + ")");
+    if ((rc = svo_check_store(ctx)) || (rc = svo_check_n_words(ctx, p->n_words))) return rc;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    if ((rc = ensure_state(ctx))) return rc;
+    if ((rc = svo_workspace_ensure(ctx, ctx->edit))) return rc;
     svo_edit_state *s = ctx->edit.get();
     if (!n) {  // nothing to edit
-        memset(s->ms, 0, sizeof s->ms);
-        s->timed = true;
+        s->timer.none();
         *n_words_out = p->n_words;
         return SVO_OK;
     }
     const double t0 = svo_now_ms();
+    if ((rc = s->timer.begin(ctx))) return rc;  // (before the front end records the builder's events again)
     const uint32_t depth = p->depth, n_words = (uint32_t)std::min<uint64_t>(p->n_words, kMaxWords), bound = (uint32_t)n;
     svo_build_leaves lv{};
     if ((rc = svo_build_list_leaves(ctx, xyz, colours, n, depth, p->default_colour, &lv))) return rc;
@@ -218,14 +195,14 @@ int svo_nodes_edit(svo_ctx *ctx, const uint32_t *xyz, const uint32_t *colours, s
     HIP_TRY(ctx, hipGetLastError());
     if ((rc = svo_build_scan_u32(ctx, start, bound))) return rc;
     edit_status_kernel<<<1, kTopThreads, 0, ctx->stream>>>(bad, n_blocks, lv.count, bound, lv.range_err, depth, lvl, start, lv.keys,
-                                                          lv.index, s->status);
+                                                          lv.index, s->status.dev);
     HIP_TRY(ctx, hipGetLastError());
-    HIP_TRY(ctx, hipEventRecord(s->ev[kEvPlan], ctx->stream));
-    HIP_TRY(ctx, hipMemcpyAsync(s->status_host, s->status, kStWords * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipEventRecord(s->ev[kEvRead], ctx->stream));
+    HIP_TRY(ctx, s->timer.mark(ctx, kEvPlan));
+    HIP_TRY(ctx, s->status.copy(ctx));
+    HIP_TRY(ctx, s->timer.mark(ctx, kEvRead));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
 
-    const uint32_t *st = s->status_host;
+    const uint32_t *st = s->status.host();
     if (st[kStRange])
         return svo_fail(ctx, SVO_ERR_ARG, "a voxel coordinate is outside [0, 2^depth) (depth " + std::to_string(depth) + ")");
     if (st[kStBad]) {
@@ -249,37 +226,27 @@ int svo_nodes_edit(svo_ctx *ctx, const uint32_t *xyz, const uint32_t *colours, s
                                               ", over the limit of " + std::to_string(limit) + " (max_words, the node buffer's capacity, 2^27)");
 
     if ((rc = svo_store_order_after_write(ctx))) return rc;
-    HIP_TRY(ctx, hipEventRecord(s->ev[kEvFill], ctx->stream));
+    HIP_TRY(ctx, s->timer.mark(ctx, kEvFill));
     if (new_words > p->n_words)
         HIP_TRY(ctx, hipMemsetD32Async((hipDeviceptr_t)(ctx->nodes + p->n_words), (int)kEmptyWord, new_words - p->n_words, ctx->stream));
     edit_link_kernel<<<svo_div_up(st[kStCount], kThreads), kThreads, 0, ctx->stream>>>(ctx->nodes, n_words, (uint32_t)new_words, lv.keys,
                                                                                       lv.colours, st[kStCount], depth, lvl, start, at);
     HIP_TRY(ctx, hipGetLastError());
-    HIP_TRY(ctx, hipEventRecord(s->ev[kEvEnd], ctx->stream));
+    HIP_TRY(ctx, s->timer.mark(ctx, kEvEnd));
     if ((rc = svo_store_note_write(ctx))) return rc;
     *n_words_out = new_words;
-    s->ev_start = lv.ev_start;
-    s->ev_keys = lv.ev_keys;
-    s->ev_sort = lv.ev_sort;
-    s->ms[5] = float(svo_now_ms() - t0);
-    s->timed = false;  // (the link is still in flight: svo_edit_timing reads the events)
+    const svo_events<kEvs> &ev = s->timer.ev;
+    const hipEvent_t span[SVO_EDIT_TIMES - 1][2] = {
+        {lv.ev_start, lv.ev_keys}, {lv.ev_keys, lv.ev_sort}, {lv.ev_sort, ev[kEvPlan]}, {ev[kEvPlan], ev[kEvRead]}, {ev[kEvFill], ev[kEvEnd]}};
+    memcpy(s->timer.span, span, sizeof span);
+    s->timer.finish(t0);
     return SVO_OK;
 }
 
 int svo_edit_timing(svo_ctx *ctx, float ms_out[SVO_EDIT_TIMES]) {
     if (!ctx || !ms_out) return SVO_ERR_ARG;
     if (!ctx->edit) return svo_fail(ctx, SVO_ERR_STATE, "no tree edited on this context yet");
-    svo_edit_state *s = ctx->edit.get();
-    if (!s->timed) {
-        HIP_TRY(ctx, hipSetDevice(ctx->device));
-        HIP_TRY(ctx, hipEventSynchronize(s->ev[kEvEnd]));
-        const hipEvent_t span[5][2] = {{s->ev_start, s->ev_keys}, {s->ev_keys, s->ev_sort}, {s->ev_sort, s->ev[kEvPlan]},
-                                       {s->ev[kEvPlan], s->ev[kEvRead]}, {s->ev[kEvFill], s->ev[kEvEnd]}};
-        for (int k = 0; k < 5; k++) HIP_TRY(ctx, hipEventElapsedTime(&s->ms[k], span[k][0], span[k][1]));
-        s->timed = true;
-    }
-    memcpy(ms_out, s->ms, sizeof s->ms);
-    return SVO_OK;
+    return ctx->edit->timer.read(ctx, ms_out);
 }
 
 }  // extern "C"

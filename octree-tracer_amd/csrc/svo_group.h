@@ -1,6 +1,7 @@
-// svo_group.h -- what the passes that walk the tree in the node buffer (svo_compact.hip, svo_list.hip) share on the
-// device: 8 lanes per group, one word per lane, so a wave64 handles 8 groups, a group is one 32-byte read and its
-// interior mask is its byte of the wave's ballot.  Everything sits in an anonymous namespace, like svo_scan.h.
+// svo_group.h -- the constants of the tree passes, and what those that walk the tree in the node buffer
+// (svo_compact.hip, svo_list.hip) share on the device: 8 lanes per group, one word per lane, so a wave64 handles 8
+// groups, a group is one 32-byte read and its interior mask is its byte of the wave's ballot.  Everything sits in an
+// anonymous namespace, like svo_scan.h, which includes this header.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -10,7 +11,9 @@
 
 namespace {
 
+constexpr uint32_t kThreads = 256;  // per workgroup, in every tree pass
 constexpr uint32_t kEmptyWord = SVO_VOXEL_OFFSET << 4;
+constexpr uint64_t kMaxWords = SVO_VOXEL_OFFSET;  // 2^27: no pointer reaches further, and pointers and colours stay apart
 
 // What the 8 lanes of a group know of it.  Every lane of the wave must get here: the mask is a ballot.
 struct GroupLane {

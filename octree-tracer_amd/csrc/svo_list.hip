@@ -23,18 +23,16 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <cstring>
 #include <string>
 #include <vector>
 
 #include "svo_ctx.h"
-#include "svo_group.h"   // (group_lane: 8 lanes per group)
+#include "svo_group.h"   // (group_lane: 8 lanes per group; kMaxWords)
 #include "svo_morton.h"  // (morton_decode)
 #include "svo_scan.h"    // (kThreads)
 
 namespace {
 
-constexpr uint64_t kMaxWords = SVO_VOXEL_OFFSET;  // 2^27: no pointer reaches further
 constexpr uint64_t kMaxEntries = 1ull << 31;
 // the words read back: the discovery's (svo_ctx.h), the root's counts, one note per level below `depth`
 enum Status { kStCountLo = SVO_WALK_STATUS, kStCountHi, kStRecords, kStPad, kStDeep, kStWords = kStDeep + 32 };
@@ -201,38 +199,26 @@ enum Ev { kEvStart, kEvDiscover, kEvCount, kEvOffsets, kEvEmit, kEvs };
 
 // Per-context workspace of the listing (svo_ctx::list): eleven u32 per group, four per record.
 struct svo_list_state {
-    uint32_t *order = nullptr, *first_child = nullptr, *new_of = nullptr, *scan = nullptr;  // the discovery's
-    uint32_t *rcnt = nullptr, *start = nullptr, *rstart = nullptr;
-    uint64_t *cnt = nullptr, *key = nullptr;
+    svo_dev<uint32_t> order, first_child, new_of, scan;  // the discovery's
+    svo_dev<uint32_t> rcnt, start, rstart;
+    svo_dev<uint64_t> cnt, key;
     size_t group_items = 0;
-    uint32_t *rec_start = nullptr, *rec_value = nullptr;
-    uint64_t *rec_key = nullptr;
+    svo_dev<uint32_t> rec_start, rec_value;
+    svo_dev<uint64_t> rec_key;
     size_t rec_items = 0;
-    uint32_t *status = nullptr, *status_host = nullptr;  // kStWords words (device / pinned)
-    hipEvent_t ev[kEvs] = {};
-    bool timed = true;
-    float ms[SVO_LIST_TIMES] = {};
+    svo_mirrored<> status;  // kStWords words
+    svo_pass_timer<kEvs, SVO_LIST_TIMES> timer;
 
-    ~svo_list_state() {
-        for (void *p : {(void *)order, (void *)first_child, (void *)new_of, (void *)scan, (void *)rcnt, (void *)start, (void *)rstart,
-                        (void *)cnt, (void *)key, (void *)rec_start, (void *)rec_value, (void *)rec_key, (void *)status})
-            if (p) (void)hipFree(p);
-        if (status_host) (void)hipHostFree(status_host);
-        for (hipEvent_t e : ev)
-            if (e) (void)hipEventDestroy(e);
+    int create(svo_ctx *ctx) {
+        HIP_TRY(ctx, timer.create());
+        return status.alloc(ctx, kStWords);
     }
 };
 
 namespace {
 
 int ensure_state(svo_ctx *ctx, size_t groups) {
-    if (!ctx->list) {  // the context gets the state only when all of it exists (a failure frees what there is)
-        svo_workspace<svo_list_state> fresh = svo_workspace_new<svo_list_state>();
-        for (hipEvent_t &e : fresh->ev) HIP_TRY(ctx, hipEventCreate(&e));
-        HIP_TRY(ctx, hipHostMalloc((void **)&fresh->status_host, kStWords * sizeof(uint32_t), hipHostMallocDefault));
-        HIP_TRY(ctx, hipMalloc((void **)&fresh->status, kStWords * sizeof(uint32_t)));
-        ctx->list = std::move(fresh);
-    }
+    if (int rc = svo_workspace_ensure(ctx, ctx->list)) return rc;
     svo_list_state *s = ctx->list.get();
     return svo_grow(ctx, &s->group_items, groups, &s->order, &s->first_child, &s->new_of, &s->scan, &s->rcnt, &s->start, &s->rstart,
                     &s->cnt, &s->key);
@@ -247,34 +233,27 @@ int svo_nodes_list_voxels(svo_ctx *ctx, const svo_list_params *p, uint32_t *xyz_
     if (!ctx) return SVO_ERR_ARG;
     if (!p) return svo_fail(ctx, SVO_ERR_ARG, "null params");
     if (!n_out) return svo_fail(ctx, SVO_ERR_ARG, "null n_out");
-    if (p->flags & ~SVO_LIST_EXPAND) return svo_fail(ctx, SVO_ERR_ARG, "unknown flag bits " + std::to_string(p->flags));
-    if (p->depth < 1 || p->depth > 21) return svo_fail(ctx, SVO_ERR_ARG, "depth must be 1..21 (got " + std::to_string(p->depth) + ")");
+    int rc = svo_check_flags(ctx, p->flags, SVO_LIST_EXPAND);
+    if (rc || (rc = svo_check_depth(ctx, p->depth, 21))) return rc;
     if (xyz_out_dev && !value_out_dev) return svo_fail(ctx, SVO_ERR_ARG, "null value_out_dev with xyz_out_dev given");
-    if (!ctx->store) return svo_fail(ctx, SVO_ERR_STATE, "svo_nodes_alloc / svo_nodes_bind_device not called");
-    if (p->n_words < 8 || p->n_words % 8 || p->n_words > ctx->capacity)
-        return svo_fail(ctx, SVO_ERR_ARG, "n_words must be a positive multiple of 8 within the node buffer's capacity (got " +
-                                              std::to_string(p->n_words) + ", capacity " + std::to_string(ctx->capacity) + ")");
+    if ((rc = svo_check_store(ctx)) || (rc = svo_check_n_words(ctx, p->n_words))) return rc;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const double t0 = svo_now_ms();
     const uint32_t n_words = (uint32_t)std::min<uint64_t>(p->n_words, kMaxWords), depth = p->depth;
     const bool expand = p->flags & SVO_LIST_EXPAND;
-    int rc = ensure_state(ctx, n_words / 8);
-    if (rc) return rc;
+    if ((rc = ensure_state(ctx, n_words / 8))) return rc;
     svo_list_state *s = ctx->list.get();
-    if (!s->timed) {  // the events are recorded again below: the last listing's times are taken first, so that a refused
-        float ms[SVO_LIST_TIMES];  // call leaves svo_list_timing with the times of the last one that ran
-        if ((rc = svo_list_timing(ctx, ms))) return rc;
-    }
-    const uint32_t *st = s->status_host;
+    if ((rc = s->timer.begin(ctx))) return rc;
+    const uint32_t *st = s->status.host();
 
     // the passes read the words: behind every earlier write to the store, whichever context issued it
     if ((rc = svo_store_order_after_write(ctx))) return rc;
-    HIP_TRY(ctx, hipEventRecord(s->ev[kEvStart], ctx->stream));
-    HIP_TRY(ctx, hipMemsetAsync(s->status, 0, kStWords * sizeof(uint32_t), ctx->stream));
+    HIP_TRY(ctx, s->timer.mark(ctx, kEvStart));
+    HIP_TRY(ctx, s->status.zero(ctx));
 
     // discover and check
-    svo_tree_walk walk{s->order, s->first_child, s->new_of, s->scan, s->status, s->status_host, kStWords, {}};
-    if ((rc = svo_tree_discover(ctx, p->n_words, &walk, s->ev[kEvDiscover]))) return rc;
+    svo_tree_walk walk{s->order, s->first_child, s->new_of, s->scan, s->status, {}};
+    if ((rc = svo_tree_discover(ctx, p->n_words, &walk, s->timer.ev[kEvDiscover]))) return rc;
     const std::vector<uint32_t> &level_off = walk.level_off;  // level l: order[level_off[l - 1], level_off[l])
     const uint32_t n_levels = (uint32_t)level_off.size() - 1, listed = std::min(n_levels, depth);
     const auto leaf = [&](uint32_t level) { return expand ? 1ull << 3u * (depth - level) : 1ull; };
@@ -286,12 +265,11 @@ int svo_nodes_list_voxels(svo_ctx *ctx, const svo_list_params *p, uint32_t *xyz_
         const bool deep = l > depth;
         list_count_kernel<<<svo_div_up(8ull * m, kThreads), kThreads, 0, ctx->stream>>>(
             ctx->nodes, s->order, off, m, s->first_child, deep ? 0ull : leaf(l), deep ? 0u : coarse(l), s->cnt, s->rcnt,
-            deep ? s->status + kStDeep + l : nullptr);
+            deep ? s->status.dev + kStDeep + l : nullptr);
     }
-    list_root_kernel<<<1, 1, 0, ctx->stream>>>(s->cnt, s->rcnt, s->status, s->start, s->rstart, s->key);
+    list_root_kernel<<<1, 1, 0, ctx->stream>>>(s->cnt, s->rcnt, s->status.dev, s->start, s->rstart, s->key);
     HIP_TRY(ctx, hipGetLastError());
-    HIP_TRY(ctx, hipMemcpyAsync(s->status_host, s->status, kStWords * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    if ((rc = s->status.read(ctx))) return rc;
     if (st[SVO_WALK_DUP]) return svo_fail(ctx, SVO_ERR_STATE, "malformed tree: a group is reached twice");
     for (uint32_t l = n_levels; l > depth; l--)
         if (st[kStDeep + l])
@@ -303,7 +281,7 @@ int svo_nodes_list_voxels(svo_ctx *ctx, const svo_list_params *p, uint32_t *xyz_
     if (xyz_out_dev && count > p->max_voxels)
         return svo_fail(ctx, SVO_ERR_CAP, "the list has " + std::to_string(count) + " entries, more than max_voxels = " +
                                               std::to_string(p->max_voxels));
-    HIP_TRY(ctx, hipEventRecord(s->ev[kEvCount], ctx->stream));
+    HIP_TRY(ctx, s->timer.mark(ctx, kEvCount));
 
     if (xyz_out_dev && count) {
         if ((rc = svo_grow(ctx, &s->rec_items, (size_t)n_rec, &s->rec_start, &s->rec_value, &s->rec_key))) return rc;
@@ -314,7 +292,7 @@ int svo_nodes_list_voxels(svo_ctx *ctx, const svo_list_params *p, uint32_t *xyz_
                 ctx->nodes, s->order, off, m, s->first_child, leaf(l), coarse(l), s->cnt, s->rcnt, s->start, s->rstart, s->key);
         }
         HIP_TRY(ctx, hipGetLastError());
-        HIP_TRY(ctx, hipEventRecord(s->ev[kEvOffsets], ctx->stream));
+        HIP_TRY(ctx, s->timer.mark(ctx, kEvOffsets));
 
         // emit
         const ListOut out{xyz_out_dev, value_out_dev, level_out_dev, (uint32_t)count, s->rec_start, s->rec_value, s->rec_key, n_rec};
@@ -325,27 +303,18 @@ int svo_nodes_list_voxels(svo_ctx *ctx, const svo_list_params *p, uint32_t *xyz_
         if (n_rec) list_expand_kernel<<<svo_div_up(count, kThreads), kThreads, 0, ctx->stream>>>(depth, out);
         HIP_TRY(ctx, hipGetLastError());
     } else {
-        HIP_TRY(ctx, hipEventRecord(s->ev[kEvOffsets], ctx->stream));
+        HIP_TRY(ctx, s->timer.mark(ctx, kEvOffsets));
     }
-    HIP_TRY(ctx, hipEventRecord(s->ev[kEvEmit], ctx->stream));
+    HIP_TRY(ctx, s->timer.mark(ctx, kEvEmit));
     *n_out = count;
-    s->ms[4] = float(svo_now_ms() - t0);
-    s->timed = false;  // (the emit is still in flight: svo_list_timing reads the events)
+    s->timer.finish(t0);
     return SVO_OK;
 }
 
 int svo_list_timing(svo_ctx *ctx, float ms_out[SVO_LIST_TIMES]) {
     if (!ctx || !ms_out) return SVO_ERR_ARG;
     if (!ctx->list) return svo_fail(ctx, SVO_ERR_STATE, "no tree listed on this context yet");
-    svo_list_state *s = ctx->list.get();
-    if (!s->timed) {
-        HIP_TRY(ctx, hipSetDevice(ctx->device));
-        HIP_TRY(ctx, hipEventSynchronize(s->ev[kEvEmit]));
-        for (int k = 0; k < 4; k++) HIP_TRY(ctx, hipEventElapsedTime(&s->ms[k], s->ev[k], s->ev[k + 1]));
-        s->timed = true;
-    }
-    memcpy(ms_out, s->ms, sizeof s->ms);
-    return SVO_OK;
+    return ctx->list->timer.read(ctx, ms_out);
 }
 
 }  // extern "C"

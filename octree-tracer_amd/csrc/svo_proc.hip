@@ -269,34 +269,28 @@ uint64_t pad_tile(uint64_t n) { return (n + kTile - 1) / kTile * kTile; }
 // Per-context workspace of the generator (svo_ctx::proc).  The level buffers only grow (svo_grow): they have the room of
 // the deepest chunk generated so far, and a shallower chunk lays its levels out in the same memory.
 struct svo_proc_state {
-    uint32_t depth = 0;               // chunk_depth the level buffers are laid out for
-    uint8_t *cls = nullptr;           // 8^depth class bytes, Morton order
-    uint8_t *masks = nullptr;         // levels 0 .. depth-1: child masks, each level zero-padded to whole tiles
-    uint32_t *ranks = nullptr;        // levels 0 .. depth-1: exclusive ranks of the interior nodes
-    uint32_t *tiles = nullptr;        // levels 0 .. depth-1: tile counts, then tile offsets
+    uint32_t depth = 0;       // chunk_depth the level buffers are laid out for
+    svo_dev<uint8_t> cls;     // 8^depth class bytes, Morton order
+    svo_dev<uint8_t> masks;   // levels 0 .. depth-1: child masks, each level zero-padded to whole tiles
+    svo_dev<uint32_t> ranks;  // levels 0 .. depth-1: exclusive ranks of the interior nodes
+    svo_dev<uint32_t> tiles;  // levels 0 .. depth-1: tile counts, then tile offsets
     size_t cls_items = 0, mask_items = 0, rank_items = 0, tile_items = 0;  // room in each of the four
-    uint32_t *totals = nullptr;       // interior nodes per level (device)
-    uint32_t *totals_host = nullptr;  // (pinned)
+    svo_mirrored<> totals;      // interior nodes per level
     size_t mask_bytes = 0;
     uint64_t mask_off[10] = {}, rank_off[10] = {}, tile_off[10] = {};
     uint32_t n_tiles[10] = {};
-    uint4 *out = nullptr;  // emitted nodes, 8 bytes each
+    svo_dev<uint4> out;  // emitted nodes, 8 bytes each
     size_t out_items = 0;
-    uint8_t *stage = nullptr;  // pinned read-back buffer
+    svo_pinned<uint8_t> stage;  // read-back buffer
     size_t stage_bytes = 0;
-    hipEvent_t ev[4] = {};
-    hipEvent_t mev[2] = {};  // svo_world_generate: around a chunk's device mips
+    svo_events<4> ev;
+    svo_events<2> mev;  // svo_world_generate: around a chunk's device mips
     float ms[SVO_PROC_TIMES] = {};
 
-    ~svo_proc_state() {
-        for (void *p : {(void *)cls, (void *)masks, (void *)ranks, (void *)tiles, (void *)totals, (void *)out})
-            if (p) (void)hipFree(p);
-        if (totals_host) (void)hipHostFree(totals_host);
-        if (stage) (void)hipHostFree(stage);
-        for (hipEvent_t e : ev)
-            if (e) (void)hipEventDestroy(e);
-        for (hipEvent_t e : mev)
-            if (e) (void)hipEventDestroy(e);
+    int create(svo_ctx *ctx) {
+        HIP_TRY(ctx, ev.create());
+        HIP_TRY(ctx, mev.create());
+        return totals.alloc(ctx, 16);
     }
 };
 
@@ -322,13 +316,7 @@ ChunkGeom geom_of(const svo_proc_params *p) {
 
 // workspace for chunks of `depth` levels (kept between calls; grown for a deeper chunk)
 int ensure_state(svo_ctx *ctx, uint32_t depth) {
-    if (!ctx->proc) {
-        ctx->proc = svo_workspace_new<svo_proc_state>();
-        for (hipEvent_t &e : ctx->proc->ev) HIP_TRY(ctx, hipEventCreate(&e));
-        for (hipEvent_t &e : ctx->proc->mev) HIP_TRY(ctx, hipEventCreate(&e));
-        HIP_TRY(ctx, hipHostMalloc((void **)&ctx->proc->totals_host, 16 * sizeof(uint32_t), hipHostMallocDefault));
-        HIP_TRY(ctx, hipMalloc((void **)&ctx->proc->totals, 16 * sizeof(uint32_t)));
-    }
+    if (int rc = svo_workspace_ensure(ctx, ctx->proc)) return rc;
     svo_proc_state *s = ctx->proc.get();
     if (s->depth == depth) return SVO_OK;
     s->depth = 0;  // (until the buffers have room for the new layout)
@@ -434,19 +422,18 @@ int emit_chunk(svo_ctx *ctx, const svo_proc_params *params, double t0, uint64_t 
         const uint8_t *m = s->masks + s->mask_off[l];
         uint32_t *tiles = s->tiles + s->tile_off[l];
         proc_tile_count_kernel<<<s->n_tiles[l], 256, 0, ctx->stream>>>(m, tiles);
-        tile_offsets_kernel<<<1, kTopThreads, 0, ctx->stream>>>(tiles, s->n_tiles[l], nullptr, 0, s->totals + l);
+        tile_offsets_kernel<<<1, kTopThreads, 0, ctx->stream>>>(tiles, s->n_tiles[l], nullptr, 0, s->totals.dev + l);
         proc_tile_rank_kernel<<<s->n_tiles[l], 256, 0, ctx->stream>>>(m, tiles, s->ranks + s->rank_off[l]);
         HIP_TRY(ctx, hipGetLastError());
     }
     HIP_TRY(ctx, hipEventRecord(s->ev[2], ctx->stream));
-    HIP_TRY(ctx, hipMemcpyAsync(s->totals_host, s->totals, depth * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    if ((rc = s->totals.read(ctx, depth))) return rc;
 
     // breadth-first bases: level 1 (the root group) at 0, level L+1 behind level L's 8 * interior(L-1) nodes
     base[0] = base[1] = 0;
-    for (uint32_t l = 1; l <= depth; l++) base[l + 1] = base[l] + 8ull * s->totals_host[l - 1];
+    for (uint32_t l = 1; l <= depth; l++) base[l + 1] = base[l] + 8ull * s->totals.host()[l - 1];
     const uint64_t n_nodes = base[depth + 1];
-    if (s->totals_host[0] == 0) {  // no solid cell: the reference's "len <= 8 -> None" (procedural.rs:167)
+    if (s->totals.host()[0] == 0) {  // no solid cell: the reference's "len <= 8 -> None" (procedural.rs:167)
         s->ms[0] = s->ms[1] = s->ms[2] = s->ms[4] = s->ms[5] = 0.0f;
         s->ms[3] = float(svo_now_ms() - t0);
         return SVO_OK;
@@ -556,7 +543,7 @@ int svo_world_generate(svo_ctx *ctx, svo_world *w, uint32_t world_depth, uint32_
                 times[0] += s->ms[3];
                 if (!n_nodes) continue;
                 // mips on the device: block leaves first, then the interior levels bottom-up
-                uint2 *nodes = reinterpret_cast<uint2 *>(s->out);
+                uint2 *nodes = reinterpret_cast<uint2 *>(s->out.get());
                 HIP_TRY(ctx, hipEventRecord(s->mev[0], ctx->stream));
                 const uint32_t leaves = uint32_t(base[chunk_depth + 1] - base[chunk_depth]);
                 proc_block_mips_kernel<<<svo_div_up(leaves, 256), 256, 0, ctx->stream>>>(nodes, (uint32_t)base[chunk_depth], leaves, blocks);

@@ -18,16 +18,14 @@
 // branch on its caller.
 #include <hip/hip_runtime.h>
 
-#include <cstring>
 #include <string>
 
 #include "svo_ctx.h"
-#include "svo_group.h"   // (kEmptyWord)
+#include "svo_group.h"   // (kThreads, kEmptyWord; not svo_scan.h: this file needs none of its kernels)
 #include "svo_morton.h"  // (morton_child)
 
 namespace {
 
-constexpr uint32_t kThreads = 256;  // per workgroup, as in the other tree passes (svo_scan.h, whose kernels this file does not need)
 constexpr uint64_t kMaxCells = 1ull << 31;
 constexpr uint32_t kRun = 4;             // bricks along z per wave
 constexpr uint32_t kSettled = 0xFFFFFFFFu;  // in Brick::group: every cell of the brick has Brick::value
@@ -127,13 +125,11 @@ __global__ __launch_bounds__(kThreads) void sample_dense_kernel(const uint32_t *
 
 // Per-context state of the sampling (svo_ctx::sample): the events around the last kernel and its times.
 struct svo_sample_state {
-    hipEvent_t ev[2] = {};
-    bool timed = true;
-    float ms[SVO_SAMPLE_TIMES] = {};
+    svo_pass_timer<2, SVO_SAMPLE_TIMES> timer;
 
-    ~svo_sample_state() {
-        for (hipEvent_t e : ev)
-            if (e) (void)hipEventDestroy(e);
+    int create(svo_ctx *ctx) {
+        HIP_TRY(ctx, timer.create());
+        return SVO_OK;
     }
 };
 
@@ -142,40 +138,27 @@ namespace {
 // The checks both calls share behind their own arguments' (the contract's causes 1 to 3 come before, 5 and 6 after).
 int check_params(svo_ctx *ctx, const svo_sample_params *p) {
     if (!p) return svo_fail(ctx, SVO_ERR_ARG, "null params");
-    if (p->flags) return svo_fail(ctx, SVO_ERR_ARG, "unknown flag bits " + std::to_string(p->flags));
-    if (p->depth < 1 || p->depth > 21) return svo_fail(ctx, SVO_ERR_ARG, "depth must be 1..21 (got " + std::to_string(p->depth) + ")");
-    return SVO_OK;
+    if (int rc = svo_check_flags(ctx, p->flags, 0)) return rc;
+    return svo_check_depth(ctx, p->depth, 21);
 }
 
 int check_tree(svo_ctx *ctx, const svo_sample_params *p) {
-    if (!ctx->store) return svo_fail(ctx, SVO_ERR_STATE, "svo_nodes_alloc / svo_nodes_bind_device not called");
-    if (p->n_words < 8 || p->n_words % 8 || p->n_words > ctx->capacity)
-        return svo_fail(ctx, SVO_ERR_ARG, "n_words must be a positive multiple of 8 within the node buffer's capacity (got " +
-                                              std::to_string(p->n_words) + ", capacity " + std::to_string(ctx->capacity) + ")");
-    return SVO_OK;
-}
-
-int ensure_state(svo_ctx *ctx) {
-    if (ctx->sample) return SVO_OK;
-    svo_workspace<svo_sample_state> fresh = svo_workspace_new<svo_sample_state>();
-    for (hipEvent_t &e : fresh->ev) HIP_TRY(ctx, hipEventCreate(&e));
-    ctx->sample = std::move(fresh);
-    return SVO_OK;
+    if (int rc = svo_check_store(ctx)) return rc;
+    return svo_check_n_words(ctx, p->n_words);
 }
 
 // The kernel behind every earlier write to the store, whichever context issued it, between the two events.
 template <typename Launch>
 int run_timed(svo_ctx *ctx, double t0, Launch launch) {
-    int rc = ensure_state(ctx);
+    int rc = svo_workspace_ensure(ctx, ctx->sample);
     if (rc) return rc;
     svo_sample_state *s = ctx->sample.get();
     if ((rc = svo_store_order_after_write(ctx))) return rc;
-    HIP_TRY(ctx, hipEventRecord(s->ev[0], ctx->stream));
+    HIP_TRY(ctx, s->timer.mark(ctx, 0));
     launch();
     HIP_TRY(ctx, hipGetLastError());
-    HIP_TRY(ctx, hipEventRecord(s->ev[1], ctx->stream));
-    s->ms[1] = float(svo_now_ms() - t0);
-    s->timed = false;  // (the kernel is in flight: svo_sample_timing reads the events)
+    HIP_TRY(ctx, s->timer.mark(ctx, 1));
+    s->timer.finish(t0);
     return SVO_OK;
 }
 
@@ -240,15 +223,7 @@ int svo_nodes_sample_dense(svo_ctx *ctx, const svo_sample_params *p, const uint3
 int svo_sample_timing(svo_ctx *ctx, float ms_out[SVO_SAMPLE_TIMES]) {
     if (!ctx || !ms_out) return SVO_ERR_ARG;
     if (!ctx->sample) return svo_fail(ctx, SVO_ERR_STATE, "no tree sampled on this context yet");
-    svo_sample_state *s = ctx->sample.get();
-    if (!s->timed) {
-        HIP_TRY(ctx, hipSetDevice(ctx->device));
-        HIP_TRY(ctx, hipEventSynchronize(s->ev[1]));
-        HIP_TRY(ctx, hipEventElapsedTime(&s->ms[0], s->ev[0], s->ev[1]));
-        s->timed = true;
-    }
-    memcpy(ms_out, s->ms, sizeof s->ms);
-    return SVO_OK;
+    return ctx->sample->timer.read(ctx, ms_out);
 }
 
 }  // extern "C"

@@ -7,9 +7,10 @@
 
 #include <cstdint>
 
+#include "svo_group.h"  // (kThreads)
+
 namespace {
 
-constexpr uint32_t kThreads = 256;
 constexpr uint32_t kPer = 16;                // items per thread of a tile
 constexpr uint32_t kTile = kThreads * kPer;  // items per tile
 constexpr uint32_t kTopThreads = 1024;       // threads of the one block that scans the tile sums

@@ -295,43 +295,23 @@ enum Ev { kEvStart, kEvSetup, kEvRefine, kEvCount, kEvEmit, kEvs };
 // Per-context workspace of the voxeliser (svo_ctx::voxelize): nine i32 per triangle, two pair arrays of twelve bytes per
 // pair that take turns, one mask byte per pair, one u32 per tile.
 struct svo_voxelize_state {
-    int32_t *tv = nullptr;
+    svo_dev<int32_t> tv;
     size_t tri_items = 0;  // (i32: nine per triangle)
-    uint32_t *pair_tri[2] = {};
-    uint64_t *pair_cell[2] = {};
+    svo_dev<uint32_t> pair_tri[2];
+    svo_dev<uint64_t> pair_cell[2];
     size_t pair_items[2] = {};
-    uint8_t *mask = nullptr;
+    svo_dev<uint8_t> mask;
     size_t mask_items = 0;
-    uint32_t *tiles = nullptr;
+    svo_dev<uint32_t> tiles;
     size_t tile_items = 0;
-    uint32_t *status = nullptr, *status_host = nullptr;  // kStWords words (device / pinned)
-    hipEvent_t ev[kEvs] = {};
-    bool timed = true;
-    float ms[SVO_VOXELIZE_TIMES] = {};
+    svo_mirrored<> status;  // kStWords words
+    svo_pass_timer<kEvs, SVO_VOXELIZE_TIMES> timer;
 
-    ~svo_voxelize_state() {
-        for (void *p : {(void *)tv, (void *)pair_tri[0], (void *)pair_tri[1], (void *)pair_cell[0], (void *)pair_cell[1], (void *)mask,
-                        (void *)tiles, (void *)status})
-            if (p) (void)hipFree(p);
-        if (status_host) (void)hipHostFree(status_host);
-        for (hipEvent_t e : ev)
-            if (e) (void)hipEventDestroy(e);
+    int create(svo_ctx *ctx) {
+        HIP_TRY(ctx, timer.create());
+        return status.alloc(ctx, kStWords);
     }
 };
-
-namespace {
-
-int ensure_state(svo_ctx *ctx) {
-    if (ctx->voxelize) return SVO_OK;  // the context gets the state only when all of it exists (a failure frees what there is)
-    svo_workspace<svo_voxelize_state> fresh = svo_workspace_new<svo_voxelize_state>();
-    for (hipEvent_t &e : fresh->ev) HIP_TRY(ctx, hipEventCreate(&e));
-    HIP_TRY(ctx, hipHostMalloc((void **)&fresh->status_host, kStWords * sizeof(uint32_t), hipHostMallocDefault));
-    HIP_TRY(ctx, hipMalloc((void **)&fresh->status, kStWords * sizeof(uint32_t)));
-    ctx->voxelize = std::move(fresh);
-    return SVO_OK;
-}
-
-}  // namespace
 
 extern "C" {
 
@@ -341,8 +321,8 @@ int svo_mesh_voxelize(svo_ctx *ctx, const svo_voxelize_params *p, const uint32_t
     if (!ctx) return SVO_ERR_ARG;
     if (!p) return svo_fail(ctx, SVO_ERR_ARG, "null params");
     if (!n_out) return svo_fail(ctx, SVO_ERR_ARG, "null n_out");
-    if (p->flags) return svo_fail(ctx, SVO_ERR_ARG, "unknown flag bits " + std::to_string(p->flags));
-    if (p->depth < 1 || p->depth > 21) return svo_fail(ctx, SVO_ERR_ARG, "depth must be 1..21 (got " + std::to_string(p->depth) + ")");
+    int rc = svo_check_flags(ctx, p->flags, 0);
+    if (rc || (rc = svo_check_depth(ctx, p->depth, 21))) return rc;
     if (n_tris >= kMaxEntries) return svo_fail(ctx, SVO_ERR_ARG, "n_tris must be below 2^31 (got " + std::to_string(n_tris) + ")");
     if (n_tris && !vq_dev) return svo_fail(ctx, SVO_ERR_ARG, "null vq_dev");
     if (n_tris && !tri_dev) return svo_fail(ctx, SVO_ERR_ARG, "null tri_dev");
@@ -354,14 +334,10 @@ int svo_mesh_voxelize(svo_ctx *ctx, const svo_voxelize_params *p, const uint32_t
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const double t0 = svo_now_ms();
     const uint32_t depth = p->depth, n = (uint32_t)n_tris;
-    int rc = ensure_state(ctx);
-    if (rc) return rc;
+    if ((rc = svo_workspace_ensure(ctx, ctx->voxelize))) return rc;
     svo_voxelize_state *s = ctx->voxelize.get();
-    if (!s->timed) {  // the events are recorded again below: the last run's times are taken first, so that a refused call
-        float ms[SVO_VOXELIZE_TIMES];  // leaves svo_voxelize_timing with the times of the last one that ran
-        if ((rc = svo_voxelize_timing(ctx, ms))) return rc;
-    }
-    const uint32_t *st = s->status_host;
+    if ((rc = s->timer.begin(ctx))) return rc;
+    const uint32_t *st = s->status.host();
     const uint64_t cap = xyz_out_dev ? std::min<uint64_t>(p->max_voxels, kMaxEntries - 1) : kMaxEntries - 1;
 
     // setup: the check, the gather, the root pairs
@@ -369,26 +345,25 @@ int svo_mesh_voxelize(svo_ctx *ctx, const svo_voxelize_params *p, const uint32_t
     if ((rc = svo_grow(ctx, &s->tri_items, 9 * (size_t)n, &s->tv))) return rc;
     if ((rc = svo_grow(ctx, &s->pair_items[0], (size_t)n, &s->pair_tri[0], &s->pair_cell[0]))) return rc;
     if ((rc = svo_grow(ctx, &s->tile_items, (size_t)n_blocks, &s->tiles))) return rc;
-    HIP_TRY(ctx, hipEventRecord(s->ev[kEvStart], ctx->stream));
+    HIP_TRY(ctx, s->timer.mark(ctx, kEvStart));
     vox_setup_kernel<<<n_blocks, kThreads, 0, ctx->stream>>>(vq_dev, p->n_vertices, tri_dev, n, depth, s->tv, s->pair_tri[0],
                                                              s->pair_cell[0], s->tiles);
-    vox_bad_kernel<<<1, kTopThreads, 0, ctx->stream>>>(s->tiles, n_blocks, s->status);
+    vox_bad_kernel<<<1, kTopThreads, 0, ctx->stream>>>(s->tiles, n_blocks, s->status.dev);
     HIP_TRY(ctx, hipGetLastError());
-    HIP_TRY(ctx, hipEventRecord(s->ev[kEvSetup], ctx->stream));
+    HIP_TRY(ctx, s->timer.mark(ctx, kEvSetup));
 
     uint32_t m = n, cur = 0;  // the pairs of level l - 1: pair_*[cur][0, m)
     for (uint32_t l = 1; l <= depth; l++) {
-        if (l == depth) HIP_TRY(ctx, hipEventRecord(s->ev[kEvRefine], ctx->stream));
+        if (l == depth) HIP_TRY(ctx, s->timer.mark(ctx, kEvRefine));
         const uint32_t n_tiles = svo_div_up(m, kTile), hs = depth - l + SVO_VOX_SUBBITS;
         if ((rc = svo_grow(ctx, &s->mask_items, size_t(n_tiles) * kTile, &s->mask))) return rc;
         if ((rc = svo_grow(ctx, &s->tile_items, (size_t)n_tiles, &s->tiles))) return rc;
         vox_test_kernel<<<svo_div_up(m, kThreads), kThreads, 0, ctx->stream>>>(s->tv, s->pair_tri[cur], s->pair_cell[cur], m, hs, s->mask);
         vox_sum_kernel<<<n_tiles, kThreads, 0, ctx->stream>>>(s->mask, m, s->tiles);
-        vox_total_kernel<<<1, kTopThreads, 0, ctx->stream>>>(s->tiles, n_tiles, s->status);
-        tile_offsets_kernel<<<1, kTopThreads, 0, ctx->stream>>>(s->tiles, n_tiles, nullptr, 0, s->status + kStTotal32);
+        vox_total_kernel<<<1, kTopThreads, 0, ctx->stream>>>(s->tiles, n_tiles, s->status.dev);
+        tile_offsets_kernel<<<1, kTopThreads, 0, ctx->stream>>>(s->tiles, n_tiles, nullptr, 0, s->status.dev + kStTotal32);
         HIP_TRY(ctx, hipGetLastError());
-        HIP_TRY(ctx, hipMemcpyAsync(s->status_host, s->status, kStWords * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        if ((rc = s->status.read(ctx))) return rc;
         if (l == 1 && st[kStBad] != kNoBad)
             return svo_fail(ctx, SVO_ERR_ARG, "triangle " + std::to_string(st[kStBad] >> 1) +
                                                   (st[kStBad] & 1u ? " has a coordinate outside [0, 2^(depth + 6) = " +
@@ -413,7 +388,7 @@ int svo_mesh_voxelize(svo_ctx *ctx, const svo_voxelize_params *p, const uint32_t
             cur = next;
             continue;
         }
-        HIP_TRY(ctx, hipEventRecord(s->ev[kEvCount], ctx->stream));
+        HIP_TRY(ctx, s->timer.mark(ctx, kEvCount));
         if (xyz_out_dev && count) {
             out.xyz = xyz_out_dev;
             out.colour = colour_out_dev;
@@ -423,26 +398,17 @@ int svo_mesh_voxelize(svo_ctx *ctx, const svo_voxelize_params *p, const uint32_t
             vox_scatter_kernel<true><<<n_tiles, kThreads, 0, ctx->stream>>>(s->pair_tri[cur], s->pair_cell[cur], s->mask, m, s->tiles, out);
             HIP_TRY(ctx, hipGetLastError());
         }
-        HIP_TRY(ctx, hipEventRecord(s->ev[kEvEmit], ctx->stream));
+        HIP_TRY(ctx, s->timer.mark(ctx, kEvEmit));
         *n_out = count;
     }
-    s->ms[4] = float(svo_now_ms() - t0);
-    s->timed = false;  // (the emit is still in flight: svo_voxelize_timing reads the events)
+    s->timer.finish(t0);
     return SVO_OK;
 }
 
 int svo_voxelize_timing(svo_ctx *ctx, float ms_out[SVO_VOXELIZE_TIMES]) {
     if (!ctx || !ms_out) return SVO_ERR_ARG;
     if (!ctx->voxelize) return svo_fail(ctx, SVO_ERR_STATE, "no mesh voxelised on this context yet");
-    svo_voxelize_state *s = ctx->voxelize.get();
-    if (!s->timed) {
-        HIP_TRY(ctx, hipSetDevice(ctx->device));
-        HIP_TRY(ctx, hipEventSynchronize(s->ev[kEvEmit]));
-        for (int k = 0; k < 4; k++) HIP_TRY(ctx, hipEventElapsedTime(&s->ms[k], s->ev[k], s->ev[k + 1]));
-        s->timed = true;
-    }
-    memcpy(ms_out, s->ms, sizeof s->ms);
-    return SVO_OK;
+    return ctx->voxelize->timer.read(ctx, ms_out);
 }
 
 }  // extern "C"

@@ -49,56 +49,47 @@ class Gpu:
         self.check(lib().svo_last_render_ms(self._h, C.byref(ms)))
         return ms.value
 
+    def _timing(self, fn, n):
+        ms = (C.c_float * n)()
+        self.check(fn(self._h, ms))
+        return list(ms)
+
     def build_timing(self):
         """ms of the last Render.build_nodes / build_nodes_dense: keys, sort, levels, count read-back, emit (device events),
         host wall time of the call (svo_build_timing)"""
-        ms = (C.c_float * 6)()
-        self.check(lib().svo_build_timing(self._h, ms))
-        return list(ms)
+        return self._timing(lib().svo_build_timing, 6)
 
     def edit_timing(self):
         """ms of the last Render.edit_nodes: keys, sort, plan, status read-back, fill and link (device events), host wall
         time of the call (svo_edit_timing)"""
-        ms = (C.c_float * 6)()
-        self.check(lib().svo_edit_timing(self._h, ms))
-        return list(ms)
+        return self._timing(lib().svo_edit_timing, 6)
 
     def compact_timing(self):
         """ms of the last Render.compact_nodes: discover, check, prune, emit, copy back (device events), host wall time
         of the call (svo_compact_timing)"""
-        ms = (C.c_float * 6)()
-        self.check(lib().svo_compact_timing(self._h, ms))
-        return list(ms)
+        return self._timing(lib().svo_compact_timing, 6)
 
     def list_timing(self):
         """ms of the last Render.list_voxels call into the library (its fill, or its count query when the list was empty
         or refused): discover, count, offsets, emit (device events), host wall time of the call (svo_list_timing)"""
-        ms = (C.c_float * 5)()
-        self.check(lib().svo_list_timing(self._h, ms))
-        return list(ms)
+        return self._timing(lib().svo_list_timing, 5)
 
     def sample_timing(self):
         """ms of the last Render.sample_voxels / sample_dense call that ran: the kernel (device events), host wall time of
         the call (svo_sample_timing)"""
-        ms = (C.c_float * 2)()
-        self.check(lib().svo_sample_timing(self._h, ms))
-        return list(ms)
+        return self._timing(lib().svo_sample_timing, 2)
 
     def voxelize_timing(self):
         """ms of the last mesh.voxelize call into the library that ran (its fill, or its count query when the list was
         empty): setup, the levels above the last, the last level's test and scan, emit (device events), host wall time of
         the call (svo_voxelize_timing)"""
-        ms = (C.c_float * 5)()
-        self.check(lib().svo_voxelize_timing(self._h, ms))
-        return list(ms)
+        return self._timing(lib().svo_voxelize_timing, 5)
 
     def world_build_timing(self):
         """ms of the last CpuOctree.build / World.build_world: keys, sort, levels, count read-back, emit, mips (device
         events), chunk read-back, chunk files and root (CpuOctree.build: the tree), host wall time of the call
         (svo_world_build_timing)"""
-        ms = (C.c_float * 9)()
-        self.check(lib().svo_world_build_timing(self._h, ms))
-        return list(ms)
+        return self._timing(lib().svo_world_build_timing, 9)
 
     def strip_classes(self, n_strips):
         """class byte per 64-pixel block of the last pixel frame that ran the culling pass (0xFF = culled); diagnostics"""

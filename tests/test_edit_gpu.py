@@ -250,6 +250,25 @@ def test_errors_write_nothing(pkg, render, egpu, base6):
         fresh.close()
 
 
+def test_timing_keeps_the_last_edit_that_ran(pkg, render, egpu, base6):
+    import torch
+    coords, base = base6
+    rng = np.random.default_rng(77)
+    ec, ecol = edit_voxels(rng, 7, 3000, coords, 1)
+    set_base(render, base)
+    assert render.edit_nodes(ec, 7, ecol) > base.size  # (its times are not fetched)
+    # a refused call records the front end's events again: the accepted edit's times are taken before it does
+    set_base(render, base)
+    refused = torch.tensor(np.array([[15, 15, 15], coords[7] >> 2, [0, 15, 0]]), dtype=torch.int32,
+                           device=torch.device("cuda", egpu.device))
+    assert raw_edit(pkg, egpu, refused, 4, base.size)[0] == ERR_STATE
+    ms = egpu.edit_timing()
+    assert len(ms) == 6 and all(t >= 0 for t in ms) and ms[1] > 0 and ms[5] > 0
+    assert ms == egpu.edit_timing()
+    assert raw_edit(pkg, egpu, refused, 4, base.size)[0] == ERR_STATE
+    assert ms == egpu.edit_timing()
+
+
 def frame(pkg, r, u):
     set_uniforms_from_oracle(r, u)
     got = pkg.render.hits_to_numpy(r.render())
