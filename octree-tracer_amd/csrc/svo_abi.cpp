@@ -36,42 +36,56 @@ int bind(svo_ctx *ctx) {
 // ---- node store (svo_ctx.h) ----
 // Reads issued by this context from now on come after the store's last write, whichever context's stream it ran on.
 int order_after_last_write(svo_ctx *ctx) {
-    svo_node_store *st = ctx->store;
-    if (st->last_write && st->last_writer != ctx->stream) HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, st->last_write, 0));
+    svo_node_store *st = ctx->store.get();
+    if (st->last_write[0] && st->last_writer != ctx->stream) HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, st->last_write[0], 0));
     return SVO_OK;
 }
 
 // A write to the store's words has been enqueued on this context's stream (or, `on_stream` false, may happen behind
 // the library's back through a pointer the caller holds): every context bound to the store rebuilds what it derived.
 int note_write(svo_ctx *ctx, bool on_stream) {
-    svo_node_store *st = ctx->store;
+    svo_node_store *st = ctx->store.get();
     st->version++;
     if (on_stream) {
-        if (!st->last_write) HIP_TRY(ctx, hipEventCreateWithFlags(&st->last_write, hipEventDisableTiming));
-        HIP_TRY(ctx, hipEventRecord(st->last_write, ctx->stream));
+        HIP_TRY(ctx, st->last_write.create(hipEventDisableTiming));  // (the first time)
+        HIP_TRY(ctx, hipEventRecord(st->last_write[0], ctx->stream));
         st->last_writer = ctx->stream;
     }
     return SVO_OK;
 }
 
 void release_store(svo_ctx *ctx) {
-    svo_node_store *st = ctx->store;
-    ctx->store = nullptr;
+    ctx->store.reset();  // (the store goes with its last context)
     ctx->nodes = nullptr;
     ctx->capacity = 0;
     ctx->top_version = 0;
-    if (!st || --st->refs > 0) return;
-    (void)hipSetDevice(st->device);
-    if (st->nodes && st->owned) (void)hipFree(st->nodes);
-    if (st->last_write) (void)hipEventDestroy(st->last_write);
-    delete st;
 }
 
-void adopt_store(svo_ctx *ctx, svo_node_store *st) {
-    ctx->store = st;
-    ctx->nodes = st->nodes;
-    ctx->capacity = st->capacity;
+void adopt_store(svo_ctx *ctx, std::shared_ptr<svo_node_store> st) {
+    ctx->store = std::move(st);
+    ctx->nodes = ctx->store->nodes;
+    ctx->capacity = ctx->store->capacity;
     ctx->top_version = 0;
+}
+
+// The context leaves its store for a new one of capacity_words words: the caller's, or (null) words allocated here
+// that go with the store.  The stream is waited for first; a failure leaves the context without a store.
+int adopt_new_store(svo_ctx *ctx, uint32_t *device_words, size_t capacity_words) {
+    if (capacity_words < 8 || capacity_words > (size_t)SVO_VOXEL_OFFSET)
+        return svo_fail(ctx, SVO_ERR_ARG, "capacity_words must be in [8, 2^27]");
+    int rc = bind(ctx);
+    if (rc) return rc;
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    release_store(ctx);  // (contexts that share the old store keep it alive)
+    std::shared_ptr<svo_node_store> st(new (std::nothrow) svo_node_store());
+    if (!st) return svo_fail(ctx, SVO_ERR_HIP, "out of host memory");
+    st->device = ctx->device;
+    st->nodes = device_words;
+    st->capacity = capacity_words;
+    st->owned = !device_words;
+    if (st->owned) HIP_TRY(ctx, hipMalloc((void **)&st->nodes, capacity_words * sizeof(uint32_t)));
+    adopt_store(ctx, std::move(st));
+    return SVO_OK;
 }
 
 int ensure_top_table(svo_ctx *ctx) {
@@ -162,23 +176,23 @@ int schedule_before(svo_ctx *ctx, svo_ctx::Sched &sc, const svo::FrameFacts &f, 
             for (uint32_t k = 0; k <= 8; k++) w[k] = k * 8192u;
             return w;
         }();
-        HIP_TRY(ctx, hipMemcpyAsync(sc.buf.balance, equal_shares.data(), sizeof(equal_shares), hipMemcpyHostToDevice, ctx->stream));
+        HIP_TRY(ctx, hipMemcpyAsync(sc.balance, equal_shares.data(), sizeof(equal_shares), hipMemcpyHostToDevice, ctx->stream));
     }
-    a.balance = plan.feed_balance ? sc.buf.balance : nullptr;
+    a.balance = plan.feed_balance ? sc.balance : nullptr;
     a.order_cap = svo::order_list_cap(n_strips);
     if (f.filtered) {
         // slots without a ray (secondary rays of pixels that hit nothing): this frame's lists leave out the strips
         // that consist of nothing else, ordered by the costs of an earlier frame when there are any
         // (likewise for pixel frames seen from outside the cube: strips of sky are culled before the trace, their zero
         // records written by the culling pass)
-        const uint8_t *prev = plan.prior_costs ? sc.buf.cost : nullptr;
+        const uint8_t *prev = plan.prior_costs ? sc.cost : nullptr;
         if (a.skip)
-            HIP_TRY(ctx, svo::launch_schedule_skipping(a, prev, sc.buf.cls_now, sc.buf.order, n_strips, a.order_cap, ctx->stream));
+            HIP_TRY(ctx, svo::launch_schedule_skipping(a, prev, sc.cls_now, sc.order, n_strips, a.order_cap, ctx->stream));
         else
-            HIP_TRY(ctx, svo::launch_schedule_culling(a, prev, sc.buf.cls_now, sc.buf.order, n_strips, a.order_cap, ctx->stream));
-        a.order = sc.buf.order;
+            HIP_TRY(ctx, svo::launch_schedule_culling(a, prev, sc.cls_now, sc.order, n_strips, a.order_cap, ctx->stream));
+        a.order = sc.order;
     } else if (plan.stored_lists) {
-        a.order = sc.buf.order;
+        a.order = sc.order;
     }
     return SVO_OK;
 }
@@ -192,7 +206,7 @@ int schedule_after(svo_ctx *ctx, svo_ctx::Sched &sc, svo::FrameFacts &f, const s
                    memcmp(&sc.built_uniforms, &ctx->uniforms, sizeof(svo_uniforms)) == 0;
     f.moving = sc.have_prev && memcmp(&sc.prev_uniforms, &ctx->uniforms, sizeof(svo_uniforms)) != 0;
     const svo::PostPlan plan = svo::plan_after_trace(sc.state, f);
-    HIP_TRY(ctx, svo::launch_post(a, li, plan, sc.buf, ctx->stream));
+    HIP_TRY(ctx, svo::launch_post(a, li, plan, sc.buf(), ctx->stream));
     sc.prev_uniforms = ctx->uniforms;
     sc.have_prev = true;
     if (plan.rebuild) {
@@ -262,13 +276,12 @@ int trace_launch(svo_ctx *ctx, const svo::WorkDesc &work, const float *rays, svo
     li.occupancy = ctx->occupancy;
     if (stack && ctx->defer_items < wd.n_items) {
         HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        if (ctx->defer_buf) (void)hipFree(ctx->defer_buf);
-        ctx->defer_buf = nullptr;
+        ctx->defer_buf.reset();
         ctx->frame_parity = 0;
         ctx->defer_items = 0;
         size_t want = wd.n_items < (1u << 16) ? (1u << 16) : wd.n_items;
         // layout: claim counters | list A: count + items | list B: count + items
-        HIP_TRY(ctx, hipMalloc((void **)&ctx->defer_buf, (svo::kCounterWords + 2 * (want + 1)) * sizeof(uint32_t)));
+        HIP_TRY(ctx, hipMalloc((void **)&ctx->defer_buf.p, (svo::kCounterWords + 2 * (want + 1)) * sizeof(uint32_t)));
         HIP_TRY(ctx, hipMemsetAsync(ctx->defer_buf, 0, (svo::kCounterWords + 2 * (want + 1)) * sizeof(uint32_t), ctx->stream));
         ctx->defer_items = want;
     }
@@ -281,10 +294,10 @@ int trace_launch(svo_ctx *ctx, const svo::WorkDesc &work, const float *rays, svo
     }
     const size_t slot = ctx->ev_slots ? (ctx->ev_count % ctx->ev_slots) : 0;
     const bool timed = ctx->ev_slots && opt.sched_slot == 0;  // the timing ring records the primary trace launches
-    if (timed) HIP_TRY(ctx, hipEventRecord(ctx->ev[2 * slot], ctx->stream));
+    if (timed) HIP_TRY(ctx, hipEventRecord(ctx->ev[slot][0], ctx->stream));
     HIP_TRY(ctx, svo::launch_trace(a, li, ctx->stream));
     if (timed) {
-        HIP_TRY(ctx, hipEventRecord(ctx->ev[2 * slot + 1], ctx->stream));
+        HIP_TRY(ctx, hipEventRecord(ctx->ev[slot][1], ctx->stream));
         ctx->ev_count++;
     }
     if (!stack) return SVO_OK;
@@ -326,41 +339,41 @@ int trace_common(svo_ctx *ctx, const svo::WorkDesc &work, const float *rays, svo
     const uint32_t f = ctx->uniforms.flags;
     const bool shadows = (f & SVO_F_SHADOWS) && !(f & SVO_F_SHOW_STEPS) && !(f & SVO_F_SHOW_HITS);
     if (!hits) {
-        rc = svo_grow(ctx, &ctx->shade_hits_bytes, n * sizeof(svo_hit), &ctx->shade_hits);
+        rc = svo_grow(ctx, &ctx->shade_hits_items, n, &ctx->shade_hits);
         if (rc) return rc;
-        hits = (svo_hit *)ctx->shade_hits;
+        hits = ctx->shade_hits;
     }
     const bool fused = shadows && fuse_shadow_rays(ctx);
     TraceOpts primary;
     if (fused) {
-        rc = svo_grow(ctx, &ctx->shade_shadow_bytes, n * sizeof(svo_hit), &ctx->shade_shadow);
+        rc = svo_grow(ctx, &ctx->shade_shadow_items, n, &ctx->shade_shadow);
         if (rc) return rc;
-        primary.shadow_out = (svo_hit *)ctx->shade_shadow;
+        primary.shadow_out = ctx->shade_shadow;
     } else {
-        rc = svo_grow(ctx, &ctx->shade_aux_bytes, n * sizeof(float), &ctx->shade_aux);
+        rc = svo_grow(ctx, &ctx->shade_aux_items, n, &ctx->shade_aux);
         if (rc) return rc;
-        primary.aux_t = (float *)ctx->shade_aux;
+        primary.aux_t = ctx->shade_aux;
     }
     rc = trace_launch(ctx, work, nullptr, hits, primary);
     if (rc) return rc;
     const svo::TraceArgs a = trace_args(ctx, work, hits);
     if (shadows && !fused) {
-        rc = svo_grow(ctx, &ctx->shade_rays_bytes, n * 6 * sizeof(float), &ctx->shade_rays);
+        rc = svo_grow(ctx, &ctx->shade_rays_items, n * 6, &ctx->shade_rays);
         if (rc) return rc;
-        rc = svo_grow(ctx, &ctx->shade_shadow_bytes, n * sizeof(svo_hit), &ctx->shade_shadow);
+        rc = svo_grow(ctx, &ctx->shade_shadow_items, n, &ctx->shade_shadow);
         if (rc) return rc;
-        rc = svo_grow(ctx, &ctx->shade_skip_bytes, n, &ctx->shade_skip);
+        rc = svo_grow(ctx, &ctx->shade_skip_items, n, &ctx->shade_skip);
         if (rc) return rc;
-        HIP_TRY(ctx, svo::launch_secondary_gen(a, (const float *)ctx->shade_aux, (float *)ctx->shade_rays, (uint8_t *)ctx->shade_skip,
-                                               (svo_hit *)ctx->shade_shadow, 0u, 1u, (uint32_t)n, ctx->stream));
+        HIP_TRY(ctx, svo::launch_secondary_gen(a, ctx->shade_aux, ctx->shade_rays, ctx->shade_skip, ctx->shade_shadow, 0u, 1u,
+                                               (uint32_t)n, ctx->stream));
         TraceOpts shadow;
         shadow.count_rays = true;
         shadow.sched_slot = 1;
-        shadow.skip = (const uint8_t *)ctx->shade_skip;
-        rc = trace_launch(ctx, ray_work(n), (const float *)ctx->shade_rays, (svo_hit *)ctx->shade_shadow, shadow);
+        shadow.skip = ctx->shade_skip;
+        rc = trace_launch(ctx, ray_work(n), ctx->shade_rays, ctx->shade_shadow, shadow);
         if (rc) return rc;
     }
-    HIP_TRY(ctx, svo::launch_shade(a, shadows ? (const svo_hit *)ctx->shade_shadow : nullptr, rgba, ctx->stream));
+    HIP_TRY(ctx, svo::launch_shade(a, shadows ? ctx->shade_shadow.get() : nullptr, rgba, ctx->stream));
     return SVO_OK;
 }
 
@@ -375,35 +388,35 @@ int trace_secondary(svo_ctx *ctx, const svo::WorkDesc &work, uint32_t n_secondar
     const size_t n = (size_t)work.n_rects * work.w * work.h;
     if (n * n_secondary > (1u << 26)) return svo_fail(ctx, SVO_ERR_ARG, "too many secondary rays for one call");
     if (!primary) {
-        rc = svo_grow(ctx, &ctx->shade_hits_bytes, n * sizeof(svo_hit), &ctx->shade_hits);
+        rc = svo_grow(ctx, &ctx->shade_hits_items, n, &ctx->shade_hits);
         if (rc) return rc;
-        primary = (svo_hit *)ctx->shade_hits;
+        primary = ctx->shade_hits;
     }
-    rc = svo_grow(ctx, &ctx->shade_aux_bytes, n * sizeof(float), &ctx->shade_aux);
+    rc = svo_grow(ctx, &ctx->shade_aux_items, n, &ctx->shade_aux);
     if (rc) return rc;
-    rc = svo_grow(ctx, &ctx->shade_rays_bytes, n * n_secondary * 6 * sizeof(float), &ctx->shade_rays);
+    rc = svo_grow(ctx, &ctx->shade_rays_items, n * n_secondary * 6, &ctx->shade_rays);
     if (rc) return rc;
     // ray 0, the shadow ray, can run inside the primary launch (its records go straight to the first set)
     const bool debug_view = (ctx->uniforms.flags & SVO_F_PAUSE_ADAPTIVE) && (ctx->uniforms.flags & SVO_F_SHOW_HITS);
     const bool fused = !debug_view && fuse_shadow_rays(ctx);
     const uint32_t k_first = fused ? 1u : 0u;
     TraceOpts popt;
-    popt.aux_t = (float *)ctx->shade_aux;
+    popt.aux_t = ctx->shade_aux;
     if (fused) popt.shadow_out = secondary;
     rc = trace_launch(ctx, work, nullptr, primary, popt);
     if (rc) return rc;
     if (k_first == n_secondary) return SVO_OK;
     const svo::TraceArgs a = trace_args(ctx, work, primary);
-    rc = svo_grow(ctx, &ctx->shade_skip_bytes, n * n_secondary, &ctx->shade_skip);
+    rc = svo_grow(ctx, &ctx->shade_skip_items, n * n_secondary, &ctx->shade_skip);
     if (rc) return rc;
     svo_hit *rest = secondary + (size_t)k_first * n;
-    HIP_TRY(ctx, svo::launch_secondary_gen(a, (const float *)ctx->shade_aux, (float *)ctx->shade_rays, (uint8_t *)ctx->shade_skip, rest,
-                                           k_first, n_secondary, (uint32_t)n, ctx->stream));
+    HIP_TRY(ctx, svo::launch_secondary_gen(a, ctx->shade_aux, ctx->shade_rays, ctx->shade_skip, rest, k_first, n_secondary,
+                                           (uint32_t)n, ctx->stream));
     TraceOpts sopt;
     sopt.count_rays = true;  // like the shadow ray, which passes primary = true (shader.wgsl:276)
     sopt.sched_slot = 1;
-    sopt.skip = (const uint8_t *)ctx->shade_skip;
-    return trace_launch(ctx, ray_work(n * (n_secondary - k_first)), (const float *)ctx->shade_rays, rest, sopt);
+    sopt.skip = ctx->shade_skip;
+    return trace_launch(ctx, ray_work(n * (n_secondary - k_first)), ctx->shade_rays, rest, sopt);
 }
 
 // pixel blocks of 2^bw_log2 x 64 / 2^bw_log2 over a w x h rectangle
@@ -456,6 +469,14 @@ int make_rect_work(svo_ctx *ctx, uint32_t width, uint32_t height, uint32_t x0, u
     return SVO_OK;
 }
 
+// the time of the timing ring's launch number `launch` (it waits for the launch to end)
+int timed_launch_ms(svo_ctx *ctx, size_t launch, float *ms) {
+    const svo_events<2> &pair = ctx->ev[launch % ctx->ev_slots];
+    HIP_TRY(ctx, hipEventSynchronize(pair[1]));
+    HIP_TRY(ctx, hipEventElapsedTime(ms, pair[0], pair[1]));
+    return SVO_OK;
+}
+
 }  // namespace
 
 int svo_store_order_after_write(svo_ctx *ctx) { return order_after_last_write(ctx); }
@@ -467,18 +488,12 @@ hipError_t svo_ctx::Sched::alloc(uint32_t n_strips) {
     const uint32_t want = n_strips < 4096u ? 4096u : n_strips;
     const size_t cls_bytes = want + 32 + svo::kOrderHistWords * sizeof(uint32_t);  // class bytes, then the chunk histograms
     const size_t order_words = 8 + 8 * (svo::order_list_cap(want) + 8);  // 8 lengths, 8 lists (and 8 spare entries each)
-    hipError_t e = hipMalloc((void **)&buf.cost, cls_bytes);
-    if (e == hipSuccess) e = hipMalloc((void **)&buf.cls_now, cls_bytes);
-    if (e == hipSuccess) e = hipMalloc((void **)&buf.order, order_words * sizeof(uint32_t));
-    if (e == hipSuccess) e = hipMalloc((void **)&buf.balance, svo::kBalanceWords * sizeof(uint32_t));
+    hipError_t e = hipMalloc((void **)&cost.p, cls_bytes);
+    if (e == hipSuccess) e = hipMalloc((void **)&cls_now.p, cls_bytes);
+    if (e == hipSuccess) e = hipMalloc((void **)&order.p, order_words * sizeof(uint32_t));
+    if (e == hipSuccess) e = hipMalloc((void **)&balance.p, svo::kBalanceWords * sizeof(uint32_t));
     if (e == hipSuccess) cap = want;
     return e;
-}
-
-void svo_ctx::Sched::release() {
-    for (void *p : {(void *)buf.cost, (void *)buf.cls_now, (void *)buf.order, (void *)buf.balance})
-        if (p) (void)hipFree(p);
-    *this = Sched{};
 }
 
 extern "C" {
@@ -545,10 +560,10 @@ int svo_ctx_create(int hip_device, svo_ctx **out) {
     if (e == hipSuccess) e = hipGetDeviceProperties(&prop, hip_device);
     if (e == hipSuccess) {
         ctx->num_cus = prop.multiProcessorCount;
-        e = hipStreamCreateWithFlags(&ctx->own_stream, hipStreamNonBlocking);
+        e = ctx->own_stream.create();
     }
-    if (e == hipSuccess) e = hipMalloc((void **)&ctx->top_table, (svo::kTopEntries + svo::kTopAuxEntries) * sizeof(uint32_t));
-    if (e == hipSuccess) e = hipMalloc((void **)&ctx->status, sizeof(uint32_t));
+    if (e == hipSuccess) e = hipMalloc((void **)&ctx->top_table.p, (svo::kTopEntries + svo::kTopAuxEntries) * sizeof(uint32_t));
+    if (e == hipSuccess) e = hipMalloc((void **)&ctx->status.p, sizeof(uint32_t));
     if (e == hipSuccess) e = hipMemset(ctx->status, 0, sizeof(uint32_t));
     if (e != hipSuccess) {
         svo_ctx_destroy(ctx);
@@ -559,31 +574,13 @@ int svo_ctx_create(int hip_device, svo_ctx **out) {
     return SVO_OK;
 }
 
+// (safe with a context that svo_ctx_create has built half: members that hold nothing free nothing)
 int svo_ctx_destroy(svo_ctx *ctx) {
     if (!ctx) return SVO_OK;
     (void)hipSetDevice(ctx->device);
     if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
     svo_comm_release(ctx);
-    ctx->proc.reset();
-    ctx->build.reset();
-    ctx->adapt.reset();
-    ctx->edit.reset();
-    ctx->compact.reset();
-    ctx->list.reset();
-    ctx->sample.reset();
-    ctx->voxelize.reset();
-    release_store(ctx);
-    if (ctx->top_table) (void)hipFree(ctx->top_table);
-    if (ctx->status) (void)hipFree(ctx->status);
-    if (ctx->defer_buf) (void)hipFree(ctx->defer_buf);
-    for (auto &sc : ctx->sched) sc.release();
-    for (void *p : {ctx->shade_hits, ctx->shade_aux, ctx->shade_rays, ctx->shade_shadow, ctx->shade_skip, ctx->scatter_buf})
-        if (p) (void)hipFree(p);
-    if (ctx->scan_sub) (void)hipFree(ctx->scan_sub);  // scan_unsub is the second half of the same allocation
-    if (ctx->stage) (void)hipFree(ctx->stage);
-    for (hipEvent_t e : ctx->ev) (void)hipEventDestroy(e);
-    if (ctx->own_stream) (void)hipStreamDestroy(ctx->own_stream);
-    delete ctx;
+    delete ctx;  // members in reverse order, the streams last (svo_ctx.h)
     return SVO_OK;
 }
 
@@ -608,10 +605,10 @@ int svo_set_option(svo_ctx *ctx, int option, int64_t value) {
             int rc = bind(ctx);
             if (rc) return rc;
             HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-            while (ctx->ev.size() < 2 * (size_t)value) {
-                hipEvent_t e;
-                HIP_TRY(ctx, hipEventCreate(&e));
-                ctx->ev.push_back(e);
+            while (ctx->ev.size() < (size_t)value) {
+                svo_events<2> pair;
+                HIP_TRY(ctx, pair.create());
+                ctx->ev.push_back(std::move(pair));
             }
             ctx->ev_slots = (size_t)value;
             ctx->ev_count = 0;
@@ -703,24 +700,8 @@ int svo_sync(svo_ctx *ctx) {
 
 int svo_nodes_alloc(svo_ctx *ctx, size_t capacity_words) {
     if (!ctx) return SVO_ERR_ARG;
-    if (capacity_words < 8 || capacity_words > (size_t)SVO_VOXEL_OFFSET)
-        return svo_fail(ctx, SVO_ERR_ARG, "capacity_words must be in [8, 2^27]");
-    int rc = bind(ctx);
+    int rc = adopt_new_store(ctx, nullptr, capacity_words);
     if (rc) return rc;
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    release_store(ctx);  // (contexts that share the old store keep it alive)
-    uint32_t *words = nullptr;
-    HIP_TRY(ctx, hipMalloc((void **)&words, capacity_words * sizeof(uint32_t)));
-    svo_node_store *st = new (std::nothrow) svo_node_store();
-    if (!st) {
-        (void)hipFree(words);
-        return svo_fail(ctx, SVO_ERR_HIP, "out of host memory");
-    }
-    st->device = ctx->device;
-    st->nodes = words;
-    st->capacity = capacity_words;
-    st->owned = true;
-    adopt_store(ctx, st);
     // Octree::expanded zero-fills the tail (octree.rs:143-148)
     HIP_TRY(ctx, hipMemsetAsync(ctx->nodes, 0, capacity_words * sizeof(uint32_t), ctx->stream));
     return note_write(ctx, true);
@@ -728,20 +709,7 @@ int svo_nodes_alloc(svo_ctx *ctx, size_t capacity_words) {
 
 int svo_nodes_bind_device(svo_ctx *ctx, uint32_t *device_words, size_t capacity_words) {
     if (!ctx || !device_words) return SVO_ERR_ARG;
-    if (capacity_words < 8 || capacity_words > (size_t)SVO_VOXEL_OFFSET)
-        return svo_fail(ctx, SVO_ERR_ARG, "capacity_words must be in [8, 2^27]");
-    int rc = bind(ctx);
-    if (rc) return rc;
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    release_store(ctx);
-    svo_node_store *st = new (std::nothrow) svo_node_store();
-    if (!st) return svo_fail(ctx, SVO_ERR_HIP, "out of host memory");
-    st->device = ctx->device;
-    st->nodes = device_words;
-    st->capacity = capacity_words;
-    st->owned = false;
-    adopt_store(ctx, st);
-    return SVO_OK;
+    return adopt_new_store(ctx, device_words, capacity_words);
 }
 
 int svo_nodes_share(svo_ctx *ctx, svo_ctx *owner) {
@@ -753,7 +721,6 @@ int svo_nodes_share(svo_ctx *ctx, svo_ctx *owner) {
     if (rc) return rc;
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     release_store(ctx);
-    owner->store->refs++;
     adopt_store(ctx, owner->store);
     return SVO_OK;
 }
@@ -792,9 +759,9 @@ int svo_nodes_scatter(svo_ctx *ctx, const uint32_t *indices, const uint32_t *hos
     if (rc || n == 0) return rc;
     rc = order_after_last_write(ctx);  // a shared store: writes land in the order they were issued, whichever context issued them
     if (rc) return rc;
-    rc = svo_grow(ctx, &ctx->scatter_bytes, 2 * n * sizeof(uint32_t), &ctx->scatter_buf);
+    rc = svo_grow(ctx, &ctx->scatter_items, 2 * n, &ctx->scatter_buf);
     if (rc) return rc;
-    uint32_t *d_idx = (uint32_t *)ctx->scatter_buf, *d_val = d_idx + n;
+    uint32_t *d_idx = ctx->scatter_buf, *d_val = d_idx + n;
     HIP_TRY(ctx, hipMemcpyAsync(d_idx, indices, n * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(ctx, hipMemcpyAsync(d_val, host_words, n * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(ctx, svo::launch_scatter(ctx->nodes, (uint32_t)ctx->capacity, d_idx, d_val, (uint32_t)n, ctx->stream));
@@ -854,8 +821,8 @@ int svo_render_host(svo_ctx *ctx, uint32_t width, uint32_t height, uint32_t x0, 
     if (rc) return rc;
     rc = svo_grow(ctx, &ctx->stage_bytes, n * (sizeof(svo_hit) + sizeof(uint32_t)), &ctx->stage);
     if (rc) return rc;
-    svo_hit *dh = (svo_hit *)ctx->stage;
-    uint32_t *dc = (uint32_t *)((char *)ctx->stage + n * sizeof(svo_hit));
+    svo_hit *dh = (svo_hit *)ctx->stage.get();
+    uint32_t *dc = (uint32_t *)(ctx->stage + n * sizeof(svo_hit));
     rc = trace_common(ctx, work, nullptr, dh, rgba_out ? dc : nullptr);
     if (rc) return rc;
     if (hits_out) HIP_TRY(ctx, hipMemcpyAsync(hits_out, dh, n * sizeof(svo_hit), hipMemcpyDeviceToHost, ctx->stream));
@@ -949,10 +916,7 @@ int svo_last_render_ms(svo_ctx *ctx, float *ms) {
     if (!ctx->ev_slots || !ctx->ev_count) return svo_fail(ctx, SVO_ERR_STATE, "no timed launch (set SVO_OPT_TIMING first)");
     int rc = bind(ctx);
     if (rc) return rc;
-    const size_t slot = (ctx->ev_count - 1) % ctx->ev_slots;
-    HIP_TRY(ctx, hipEventSynchronize(ctx->ev[2 * slot + 1]));
-    HIP_TRY(ctx, hipEventElapsedTime(ms, ctx->ev[2 * slot], ctx->ev[2 * slot + 1]));
-    return SVO_OK;
+    return timed_launch_ms(ctx, ctx->ev_count - 1, ms);
 }
 
 int svo_timing_collect(svo_ctx *ctx, float *ms_out, size_t cap, size_t *n_out) {
@@ -964,11 +928,8 @@ int svo_timing_collect(svo_ctx *ctx, float *ms_out, size_t cap, size_t *n_out) {
     size_t n = ctx->ev_count < ctx->ev_slots ? ctx->ev_count : ctx->ev_slots;
     if (n > cap) n = cap;
     const size_t first = ctx->ev_count - n;
-    for (size_t i = 0; i < n; i++) {
-        const size_t slot = (first + i) % ctx->ev_slots;
-        HIP_TRY(ctx, hipEventSynchronize(ctx->ev[2 * slot + 1]));
-        HIP_TRY(ctx, hipEventElapsedTime(&ms_out[i], ctx->ev[2 * slot], ctx->ev[2 * slot + 1]));
-    }
+    for (size_t i = 0; i < n; i++)
+        if ((rc = timed_launch_ms(ctx, first + i, &ms_out[i]))) return rc;
     *n_out = n;
     ctx->ev_count = 0;
     return SVO_OK;
@@ -987,11 +948,11 @@ int svo_diag_gather(svo_ctx *ctx, uint32_t stride_bytes, uint32_t n_loads) {
 int svo_diag_strip_classes(svo_ctx *ctx, uint8_t *host_out, size_t n_strips) {
     if (!ctx || (!host_out && n_strips)) return SVO_ERR_ARG;
     const svo_ctx::Sched &sc = ctx->sched[0];
-    if (!sc.buf.cls_now || !sc.state.order_filtered) return svo_fail(ctx, SVO_ERR_STATE, "the last pixel frame was traced without a culling pass");
+    if (!sc.cls_now || !sc.state.order_filtered) return svo_fail(ctx, SVO_ERR_STATE, "the last pixel frame was traced without a culling pass");
     if (n_strips > sc.cap) return svo_fail(ctx, SVO_ERR_ARG, "more strips than the last frame had");
     int rc = bind(ctx);
     if (rc || n_strips == 0) return rc;
-    HIP_TRY(ctx, hipMemcpyAsync(host_out, sc.buf.cls_now, n_strips, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(host_out, sc.cls_now, n_strips, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return SVO_OK;
 }
@@ -1001,33 +962,30 @@ int svo_scan_dispatch(svo_ctx *ctx, uint32_t node_length) {
     if (!ctx->nodes) return svo_fail(ctx, SVO_ERR_STATE, "svo_nodes_alloc not called");
     int rc = bind(ctx);
     if (rc) return rc;
-    if (!ctx->scan_sub) {
+    if (!ctx->scan_lists) {
         // Compute::new: two lists of 1 024 000 words, zero-initialised (compute.rs:46-64)
         // (one allocation for both, so that a failure cannot leave half of the pair behind)
-        uint32_t *lists = nullptr;
-        HIP_TRY(ctx, hipMalloc((void **)&lists, 2 * kScanCapacity * sizeof(uint32_t)));
-        ctx->scan_sub = lists;
-        ctx->scan_unsub = lists + kScanCapacity;
+        HIP_TRY(ctx, hipMalloc((void **)&ctx->scan_lists.p, 2 * kScanCapacity * sizeof(uint32_t)));
         ctx->scan_capacity = kScanCapacity;
-        HIP_TRY(ctx, hipMemsetAsync(ctx->scan_sub, 0, sizeof(uint32_t), ctx->stream));
-        HIP_TRY(ctx, hipMemsetAsync(ctx->scan_unsub, 0, sizeof(uint32_t), ctx->stream));
+        HIP_TRY(ctx, hipMemsetAsync(ctx->scan_sub(), 0, sizeof(uint32_t), ctx->stream));
+        HIP_TRY(ctx, hipMemsetAsync(ctx->scan_unsub(), 0, sizeof(uint32_t), ctx->stream));
     }
     uint32_t n = node_length < ctx->capacity ? node_length : (uint32_t)ctx->capacity;
     rc = order_after_last_write(ctx);  // (the scan reads -- and with SCAN_CLEARS_COUNTERS writes -- the words of a possibly shared store)
     if (rc) return rc;
-    HIP_TRY(ctx, svo::launch_scan(ctx->nodes, n, node_length, ctx->scan_sub, ctx->scan_unsub,
+    HIP_TRY(ctx, svo::launch_scan(ctx->nodes, n, node_length, ctx->scan_sub(), ctx->scan_unsub(),
                                   (uint32_t)ctx->scan_capacity, ctx->scan_clears, ctx->stream));
     return SVO_OK;
 }
 
 int svo_scan_read(svo_ctx *ctx, uint32_t *sub, uint32_t *n_sub, uint32_t *unsub, uint32_t *n_unsub, size_t capacity) {
     if (!ctx || !sub || !unsub || !n_sub || !n_unsub || capacity < 1) return SVO_ERR_ARG;
-    if (!ctx->scan_sub) return svo_fail(ctx, SVO_ERR_STATE, "svo_scan_dispatch not called");
+    if (!ctx->scan_lists) return svo_fail(ctx, SVO_ERR_STATE, "svo_scan_dispatch not called");
     int rc = bind(ctx);
     if (rc) return rc;
     uint32_t counts[2] = {0, 0};
-    HIP_TRY(ctx, hipMemcpyAsync(&counts[0], ctx->scan_sub, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipMemcpyAsync(&counts[1], ctx->scan_unsub, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(&counts[0], ctx->scan_sub(), sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(&counts[1], ctx->scan_unsub(), sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     // adaptive.rs:22,86: len = min(count, MAX - 1)
     uint32_t ls = counts[0] < ctx->scan_capacity - 1 ? counts[0] : (uint32_t)ctx->scan_capacity - 1;
@@ -1036,11 +994,11 @@ int svo_scan_read(svo_ctx *ctx, uint32_t *sub, uint32_t *n_sub, uint32_t *unsub,
     if (lu + 1 > capacity) lu = (uint32_t)capacity - 1;
     sub[0] = ls;
     unsub[0] = lu;
-    if (ls) HIP_TRY(ctx, hipMemcpyAsync(sub + 1, ctx->scan_sub + 1, ls * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-    if (lu) HIP_TRY(ctx, hipMemcpyAsync(unsub + 1, ctx->scan_unsub + 1, lu * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+    if (ls) HIP_TRY(ctx, hipMemcpyAsync(sub + 1, ctx->scan_sub() + 1, ls * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+    if (lu) HIP_TRY(ctx, hipMemcpyAsync(unsub + 1, ctx->scan_unsub() + 1, lu * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
     // adaptive.rs:23,87: reset the atomic counter
-    HIP_TRY(ctx, hipMemsetAsync(ctx->scan_sub, 0, sizeof(uint32_t), ctx->stream));
-    HIP_TRY(ctx, hipMemsetAsync(ctx->scan_unsub, 0, sizeof(uint32_t), ctx->stream));
+    HIP_TRY(ctx, hipMemsetAsync(ctx->scan_sub(), 0, sizeof(uint32_t), ctx->stream));
+    HIP_TRY(ctx, hipMemsetAsync(ctx->scan_unsub(), 0, sizeof(uint32_t), ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     *n_sub = ls;
     *n_unsub = lu;

@@ -775,17 +775,17 @@ int svo_adaptive_step(svo_ctx *ctx, const uint32_t *d_sub, uint32_t n_sub, const
     if ((rc = svo_store_order_after_write(ctx))) return rc;
     HIP_TRY(ctx, hipEventRecord(a->ev[0], ctx->stream));
     if (!d_sub) {  // the scan's own lists, clamped like svo_scan_read (adaptive.rs:22,86), their counters reset
-        if (!ctx->scan_sub) return svo_fail(ctx, SVO_ERR_STATE, "svo_scan_dispatch not called");
-        HIP_TRY(ctx, hipMemcpyAsync(&a->counts_host[0], ctx->scan_sub, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-        HIP_TRY(ctx, hipMemcpyAsync(&a->counts_host[1], ctx->scan_unsub, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+        if (!ctx->scan_lists) return svo_fail(ctx, SVO_ERR_STATE, "svo_scan_dispatch not called");
+        HIP_TRY(ctx, hipMemcpyAsync(&a->counts_host[0], ctx->scan_sub(), sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(ctx, hipMemcpyAsync(&a->counts_host[1], ctx->scan_unsub(), sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
         HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
         const uint32_t lim = (uint32_t)ctx->scan_capacity - 1;
         n_sub = std::min(a->counts_host[0], lim);
         n_unsub = std::min(a->counts_host[1], lim);
-        d_sub = ctx->scan_sub + 1;
-        d_unsub = ctx->scan_unsub + 1;
-        HIP_TRY(ctx, hipMemsetAsync(ctx->scan_sub, 0, sizeof(uint32_t), ctx->stream));
-        HIP_TRY(ctx, hipMemsetAsync(ctx->scan_unsub, 0, sizeof(uint32_t), ctx->stream));
+        d_sub = ctx->scan_sub() + 1;
+        d_unsub = ctx->scan_unsub() + 1;
+        HIP_TRY(ctx, hipMemsetAsync(ctx->scan_sub(), 0, sizeof(uint32_t), ctx->stream));
+        HIP_TRY(ctx, hipMemsetAsync(ctx->scan_unsub(), 0, sizeof(uint32_t), ctx->stream));
     }
     if (n_sub >= kMaxRank || n_unsub >= kMaxRank) return svo_fail(ctx, SVO_ERR_ARG, "at most 2^24 - 1 entries per list");
     const size_t items = std::max<size_t>(std::max(n_sub, n_unsub), 1) + 1;

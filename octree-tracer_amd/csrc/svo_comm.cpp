@@ -80,6 +80,8 @@ int fail_nccl(svo_ctx *ctx, Rccl *r, ncclResult_t e, const char *what) {
     return SVO_ERR_COMM;
 }
 
+enum { kReady, kDone };  // svo_ctx::comm_ev
+
 static_assert(sizeof(ncclUniqueId) == SVO_COMM_ID_BYTES, "SVO_COMM_ID_BYTES must be the size of ncclUniqueId");
 
 int drop_comm(svo_ctx *ctx, Rccl *r) {
@@ -89,11 +91,8 @@ int drop_comm(svo_ctx *ctx, Rccl *r) {
     ncclResult_t e = r->CommDestroy((ncclComm_t)ctx->comm);
     ctx->comm = nullptr;
     ctx->comm_world = ctx->comm_rank = 0;
-    if (ctx->comm_ready) (void)hipEventDestroy(ctx->comm_ready);
-    if (ctx->comm_done) (void)hipEventDestroy(ctx->comm_done);
-    if (ctx->comm_stream) (void)hipStreamDestroy(ctx->comm_stream);
-    ctx->comm_ready = ctx->comm_done = nullptr;
-    ctx->comm_stream = nullptr;
+    ctx->comm_ev.reset();
+    ctx->comm_stream.reset();
     ctx->gathers_issued = false;
     return e == ncclSuccess ? SVO_OK : fail_nccl(ctx, r, e, "ncclCommDestroy");
 }
@@ -102,16 +101,15 @@ int drop_comm(svo_ctx *ctx, Rccl *r) {
 // travel: ordered behind everything enqueued on the context's stream so far; svo_gather_wait orders the other way.
 int comm_stream_ready(svo_ctx *ctx) {
     hipError_t e = hipSetDevice(ctx->device);
-    if (e == hipSuccess && !ctx->comm_stream) e = hipStreamCreateWithFlags(&ctx->comm_stream, hipStreamNonBlocking);
-    if (e == hipSuccess && !ctx->comm_ready) e = hipEventCreateWithFlags(&ctx->comm_ready, hipEventDisableTiming);
-    if (e == hipSuccess && !ctx->comm_done) e = hipEventCreateWithFlags(&ctx->comm_done, hipEventDisableTiming);
-    if (e == hipSuccess) e = hipEventRecord(ctx->comm_ready, ctx->stream);
-    if (e == hipSuccess) e = hipStreamWaitEvent(ctx->comm_stream, ctx->comm_ready, 0);
+    if (e == hipSuccess && !ctx->comm_stream) e = ctx->comm_stream.create();
+    if (e == hipSuccess) e = ctx->comm_ev.create(hipEventDisableTiming);  // (the first time)
+    if (e == hipSuccess) e = hipEventRecord(ctx->comm_ev[kReady], ctx->stream);
+    if (e == hipSuccess) e = hipStreamWaitEvent(ctx->comm_stream, ctx->comm_ev[kReady], 0);
     return e == hipSuccess ? SVO_OK : svo_fail_hip(ctx, e, "communication stream set-up");
 }
 
 int comm_stream_done(svo_ctx *ctx) {
-    hipError_t e = hipEventRecord(ctx->comm_done, ctx->comm_stream);
+    hipError_t e = hipEventRecord(ctx->comm_ev[kDone], ctx->comm_stream);
     ctx->gathers_issued = true;
     return e == hipSuccess ? SVO_OK : svo_fail_hip(ctx, e, "hipEventRecord");
 }
@@ -247,7 +245,7 @@ int svo_gather_wait(svo_ctx *ctx) {
     if (!ctx) return SVO_ERR_ARG;
     if (!ctx->gathers_issued) return SVO_OK;
     hipError_t e = hipSetDevice(ctx->device);
-    if (e == hipSuccess) e = hipStreamWaitEvent(ctx->stream, ctx->comm_done, 0);
+    if (e == hipSuccess) e = hipStreamWaitEvent(ctx->stream, ctx->comm_ev[kDone], 0);
     return e == hipSuccess ? SVO_OK : svo_fail_hip(ctx, e, "hipStreamWaitEvent");
 }
 

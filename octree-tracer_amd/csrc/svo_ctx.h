@@ -1,11 +1,12 @@
 // svo_ctx.h -- the device context behind the opaque `svo_ctx` of include/svo_hip.h, and the host helpers of the files that
 // use it: svo_abi.cpp (trace / scan dispatch), svo_comm.cpp (RCCL frame gather) and the GPU tree passes (svo_proc.hip,
-// svo_build.hip, svo_edit.hip, svo_compact.hip, svo_list.hip, svo_sample.hip, svo_voxelize.hip, svo_adapt.hip).  Shared by
-// the passes, as their host frame: svo_dev / svo_pinned / svo_events (owning members of a pass's state), svo_grow /
-// svo_grow_pinned / svo_grow_keep (workspaces), svo_mirrored (device words with a pinned mirror), svo_pass_timer (events
-// and times), svo_workspace_ensure (creation) and the svo_check_* argument checks; then the builder's sort and scan and
-// svo_world_writer (a generated world's directory).  svo_scan.h, svo_group.h, svo_mip.h and svo_morton.h hold the device
-// pieces, svo_rules.h the walks and rules that svo_host.cpp and svo_adapt.hip both run.
+// svo_build.hip, svo_edit.hip, svo_compact.hip, svo_list.hip, svo_sample.hip, svo_voxelize.hip, svo_adapt.hip).  One rule
+// of ownership for the context, the node store and every pass's state: a member owns what it holds, as svo_dev /
+// svo_pinned (an allocation), svo_events (events) or svo_stream (a stream).  The passes share the rest as their host
+// frame: svo_grow / svo_grow_pinned / svo_grow_keep (workspaces), svo_mirrored (device words with a pinned mirror),
+// svo_pass_timer (events and times), svo_workspace_ensure (creation) and the svo_check_* argument checks; then the
+// builder's sort and scan and svo_world_writer (a generated world's directory).  svo_scan.h, svo_group.h, svo_mip.h and
+// svo_morton.h hold the device pieces, svo_rules.h the walks and rules that svo_host.cpp and svo_adapt.hip both run.
 // Internal: not part of the boundary.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -24,22 +25,92 @@
 #include "svo_hip.h"
 #include "svo_host.h"
 
+// ---- owning members: what the context, the node store and the passes' states hold their resources in ----
+
+// One device (or pinned host) allocation: freed with its owner, moved but not copied, a T* wherever one is wanted.
+template <typename T, bool kPinned>
+struct svo_mem {
+    T *p = nullptr;
+    svo_mem() = default;
+    svo_mem(svo_mem &&o) noexcept : p(o.p) { o.p = nullptr; }
+    svo_mem &operator=(svo_mem &&o) noexcept {
+        std::swap(p, o.p);
+        return *this;
+    }
+    ~svo_mem() { reset(); }
+    void reset() {
+        if (p) (void)(kPinned ? hipHostFree(p) : hipFree(p));
+        p = nullptr;
+    }
+    T *get() const { return p; }
+    operator T *() const { return p; }
+    T *operator->() const { return p; }
+};
+template <typename T>
+using svo_dev = svo_mem<T, false>;
+template <typename T>
+using svo_pinned = svo_mem<T, true>;
+
+// N events, destroyed with their owner (or by reset()), moved but not copied.  create() makes the ones that are not
+// there yet, with `flags` (hipEventDisableTiming for events that only order streams: they are cheaper to record).
+template <int N>
+struct svo_events {
+    hipEvent_t e[N] = {};
+    svo_events() = default;
+    svo_events(svo_events &&o) noexcept {
+        for (int k = 0; k < N; k++) e[k] = o.e[k], o.e[k] = nullptr;
+    }
+    svo_events &operator=(const svo_events &) = delete;
+    ~svo_events() { reset(); }
+    void reset() {
+        for (hipEvent_t &x : e) {
+            if (x) (void)hipEventDestroy(x);
+            x = nullptr;
+        }
+    }
+    hipError_t create(unsigned flags = hipEventDefault) {
+        for (hipEvent_t &x : e)
+            if (!x)
+                if (hipError_t err = flags ? hipEventCreateWithFlags(&x, flags) : hipEventCreate(&x)) return err;
+        return hipSuccess;
+    }
+    hipEvent_t operator[](int k) const { return e[k]; }
+};
+
+// A non-blocking stream, destroyed with its owner (or by reset()).
+struct svo_stream {
+    hipStream_t s = nullptr;
+    svo_stream() = default;
+    svo_stream(const svo_stream &) = delete;
+    svo_stream &operator=(const svo_stream &) = delete;
+    ~svo_stream() { reset(); }
+    void reset() {
+        if (s) (void)hipStreamDestroy(s);
+        s = nullptr;
+    }
+    hipError_t create() { return hipStreamCreateWithFlags(&s, hipStreamNonBlocking); }
+    operator hipStream_t() const { return s; }
+};
+
 // The device node buffer (render.rs:53-61) and what is derived from it.  Several contexts can trace from one store
 // (svo_nodes_share: frames in flight on several streams): they share the words, the generation counter that tells every
 // one of them when its own top table and strip schedule are stale, and the event that orders their reads behind the
-// last write, whichever context issued it.
+// last write, whichever context issued it.  Every context bound to it holds a reference; it goes with the last one.
 struct svo_node_store {
     int device = 0;
     uint32_t *nodes = nullptr;
     size_t capacity = 0;
-    bool owned = false;          // allocated by svo_nodes_alloc (freed with the last reference)
-    int refs = 1;
+    bool owned = false;          // allocated by svo_nodes_alloc (freed with the store)
     uint64_t version = 1;        // bumped whenever the words may have changed
-    hipEvent_t last_write = nullptr;   // recorded on the writing context's stream after every write
+    svo_events<1> last_write;    // recorded on the writing context's stream after every write (made by the first)
     hipStream_t last_writer = nullptr; // that stream: other streams wait for the event before they read
+    ~svo_node_store() {  // (then last_write, on the same device)
+        (void)hipSetDevice(device);
+        if (nodes && owned) (void)hipFree(nodes);
+    }
 };
 
-// The workspace of a GPU pass, kept per context and freed with it (svo_ctx_destroy), member by member.  Its type is
+// The workspace of a GPU pass, kept per context and freed with it, member by member.  Its type is
 // complete only in the pass's own file, so the deleter is bound there, by svo_workspace_new.
 struct svo_proc_state;
 struct svo_build_state;
@@ -56,32 +127,36 @@ svo_workspace<T> svo_workspace_new() {
     return svo_workspace<T>(new T(), [](T *p) { delete p; });
 }
 
+// Every resource is a member that owns it, and svo_ctx_destroy only deletes the context.  The order of the members
+// matters: they go in reverse, so the two streams stand first and outlive everything that may still be ordered on them.
 struct svo_ctx {
+    svo_stream own_stream;
+    svo_stream comm_stream;      // the gathers run here, ordered against `stream` by the two events of comm_ev
     int device = 0;
     int num_cus = 256;
-    hipStream_t own_stream = nullptr;
-    hipStream_t stream = nullptr;
+    hipStream_t stream = nullptr;  // own_stream, or the caller's (svo_ctx_set_stream)
     // node buffer (render.rs:53-61): `nodes` / `capacity` mirror the store this context is bound to
-    svo_node_store *store = nullptr;
+    std::shared_ptr<svo_node_store> store;
     uint32_t *nodes = nullptr;
     size_t capacity = 0;
     uint64_t top_version = 0;    // store version this context's top table was built from (0: none)
-    uint32_t *top_table = nullptr;
+    svo_dev<uint32_t> top_table;
     int cull_mode = 2;           // SVO_OPT_CULL
     bool cam_shortcut = true;    // SVO_OPT_CAMERA_SHORTCUT
     void *comm = nullptr;        // ncclComm_t (svo_comm.cpp); world size and rank of this context in it
     int comm_world = 0, comm_rank = 0;
-    hipStream_t comm_stream = nullptr;  // the gathers run here, ordered against `stream` by the two events
-    hipEvent_t comm_ready = nullptr, comm_done = nullptr;
+    svo_events<2> comm_ev;       // ready and done (svo_comm.cpp), made with the stream, without timing
     bool gathers_issued = false;
-    uint32_t *status = nullptr;        // device error word
-    uint32_t *defer_buf = nullptr;     // {strip counter, deferred count, deferred item indices...}
+    svo_dev<uint32_t> status;          // device error word
+    svo_dev<uint32_t> defer_buf;       // {strip counter, deferred count, deferred item indices...}
     size_t defer_items = 0;
-    // scan lists (compute.rs:46-64): slot 0 = count
-    uint32_t *scan_sub = nullptr, *scan_unsub = nullptr;
+    // scan lists (compute.rs:46-64): slot 0 = count.  One allocation, the subdivide list in its first half
+    svo_dev<uint32_t> scan_lists;
     size_t scan_capacity = 0;
-    // host staging for svo_render_host
-    void *stage = nullptr;
+    uint32_t *scan_sub() const { return scan_lists; }
+    uint32_t *scan_unsub() const { return scan_lists + scan_capacity; }
+    // device staging for svo_render_host
+    svo_dev<char> stage;
     size_t stage_bytes = 0;
     svo_uniforms uniforms{};
     bool have_uniforms = false;
@@ -92,16 +167,18 @@ struct svo_ctx {
     uint32_t refill_min = 32;  // (round 5: 16 until the schedule's locality work; profiles/r05_refill_sweep.log)
     bool scan_clears = false;
     int fused_shadows = 2;  // 0: off, 1: on, 2: automatic (see fuse_shadow_rays)
-    void *scatter_buf = nullptr;
-    size_t scatter_bytes = 0;
+    svo_dev<uint32_t> scatter_buf;  // svo_nodes_scatter: indices, then values
+    size_t scatter_items = 0;
     uint32_t block_w_log2 = 3;  // 64-pixel blocks of 8x8
     uint32_t tree_depth = 16;  // caller's bound on the octree depth (the reference's Settings.octree_depth)
     // scheduling feedback (strip order from an earlier frame of the same work layout); slot 1: shadow rays.  What is decided per
     // frame is svo_sched.h's; svo_abi.cpp's trace_launch measures its facts and runs the launches.
     struct Sched {
         svo::SchedState state;
-        svo::SchedBuffers buf{};  // for up to `cap` strips
+        svo_dev<uint8_t> cost, cls_now;  // for up to `cap` strips: svo::SchedBuffers says what they hold
+        svo_dev<uint32_t> order, balance;
         size_t cap = 0;
+        svo::SchedBuffers buf() const { return {cost, cls_now, order, balance}; }
         svo::WorkDesc key{};  // the work layout of the costs
         // what the schedule was measured on: while camera and tree stay the same it stays exact and is not rebuilt
         svo_uniforms built_uniforms{};
@@ -110,7 +187,7 @@ struct svo_ctx {
         svo_uniforms prev_uniforms{};
         bool have_prev = false;
         hipError_t alloc(uint32_t n_strips);  // frees what there is and starts the slot over (svo_abi.cpp)
-        void release();
+        void release() { *this = Sched{}; }  // (the buffers go with the temporary)
     };
     Sched sched[2];
     bool list_balance = true;  // unless SVO_NO_LIST_BALANCE is set (A/B switch of the list-share feedback, svo_kernels.hip: balance_step)
@@ -119,12 +196,14 @@ struct svo_ctx {
     uint32_t sched_period = 2;  // frames between schedule rebuilds (tools/perf_probe.py --motion: 2 keeps the gain under camera motion)
     int frame_parity = 0;
     // shading pass scratch (svo_render with rgba_out)
-    void *shade_hits = nullptr, *shade_aux = nullptr, *shade_rays = nullptr, *shade_shadow = nullptr, *shade_skip = nullptr;
-    size_t shade_hits_bytes = 0, shade_aux_bytes = 0, shade_rays_bytes = 0, shade_shadow_bytes = 0, shade_skip_bytes = 0;
+    svo_dev<svo_hit> shade_hits, shade_shadow;
+    svo_dev<float> shade_aux, shade_rays;
+    svo_dev<uint8_t> shade_skip;
+    size_t shade_hits_items = 0, shade_aux_items = 0, shade_rays_items = 0, shade_shadow_items = 0, shade_skip_items = 0;
     uint32_t *debug_buf = nullptr;  // caller-provided device buffer for the per-wave timeline (diagnostics)
     uint32_t strip_items = 64;
     // launch timing: a ring of (start, stop) event pairs recorded around trace launches
-    std::vector<hipEvent_t> ev;  // 2 per slot
+    std::vector<svo_events<2>> ev;  // one pair per slot; only ever added to
     size_t ev_slots = 0, ev_count = 0;
     svo_workspace<svo_proc_state> proc{nullptr, nullptr};    // procedural generator's workspace (svo_proc.hip)
     svo_workspace<svo_build_state> build{nullptr, nullptr};  // tree builder's workspace (svo_build.hip)
@@ -156,55 +235,11 @@ inline double svo_now_ms() {
 // blocks of `per` items that cover n
 inline uint32_t svo_div_up(uint64_t n, uint64_t per) { return (uint32_t)((n + per - 1) / per); }
 
-// ---- the host frame of a GPU pass: owning members, status words, the timer, creation, shared checks ----
-
-// One device (or pinned host) allocation: freed with its owner, moved but not copied, a T* wherever one is wanted.
-template <typename T, bool kPinned>
-struct svo_mem {
-    T *p = nullptr;
-    svo_mem() = default;
-    svo_mem(svo_mem &&o) noexcept : p(o.p) { o.p = nullptr; }
-    svo_mem &operator=(svo_mem &&o) noexcept {
-        std::swap(p, o.p);
-        return *this;
-    }
-    ~svo_mem() { reset(); }
-    void reset() {
-        if (p) (void)(kPinned ? hipHostFree(p) : hipFree(p));
-        p = nullptr;
-    }
-    T *get() const { return p; }
-    operator T *() const { return p; }
-    T *operator->() const { return p; }
-};
-template <typename T>
-using svo_dev = svo_mem<T, false>;
-template <typename T>
-using svo_pinned = svo_mem<T, true>;
-
-// N events, created together and destroyed with their owner.
-template <int N>
-struct svo_events {
-    hipEvent_t e[N] = {};
-    svo_events() = default;
-    svo_events(const svo_events &) = delete;
-    svo_events &operator=(const svo_events &) = delete;
-    ~svo_events() {
-        for (hipEvent_t x : e)
-            if (x) (void)hipEventDestroy(x);
-    }
-    hipError_t create() {
-        for (hipEvent_t &x : e)
-            if (hipError_t err = hipEventCreate(&x)) return err;
-        return hipSuccess;
-    }
-    hipEvent_t operator[](int k) const { return e[k]; }
-};
+// ---- the host frame of a GPU pass: workspaces, status words, the timer, creation, shared checks ----
 
 // Grows a group of buffers to `want` items of its own type each (a void buffer counts bytes): when *have < want, waits
 // for the context's stream, frees all of them and allocates them again; *have becomes `want` only when every allocation
-// succeeded.  svo_grow allocates device memory, for raw pointers (the context's own buffers) or owning members;
-// svo_grow_pinned pinned host memory, for owning members.
+// succeeded.  svo_grow allocates device memory, svo_grow_pinned pinned host memory.
 template <typename... T>
 int svo_grow_group(svo_ctx *ctx, bool pinned, size_t *have, size_t want, T **...bufs) {
     if (*have >= want) return SVO_OK;
@@ -220,8 +255,6 @@ int svo_grow_group(svo_ctx *ctx, bool pinned, size_t *have, size_t want, T **...
     *have = want;
     return SVO_OK;
 }
-template <typename... T>
-int svo_grow(svo_ctx *ctx, size_t *have, size_t want, T **...bufs) { return svo_grow_group(ctx, false, have, want, bufs...); }
 template <typename... T>
 int svo_grow(svo_ctx *ctx, size_t *have, size_t want, svo_dev<T> *...bufs) { return svo_grow_group(ctx, false, have, want, &bufs->p...); }
 template <typename... T>

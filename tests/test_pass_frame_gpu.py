@@ -1,10 +1,12 @@
 """The host frame the GPU tree passes share (csrc/svo_ctx.h): one context runs every pass that keeps a
 workspace, hands out each pass's times and is closed, which is where all of its owning members are released together;
-a second context then builds the same tree."""
+a second context then builds the same tree.  Likewise the context's own members: its scratch grows, is reused and goes
+with it, and a shared node store goes with the last context that holds it, whichever that is."""
 import numpy as np
 import pytest
 
 import build_ref as B
+from conftest import assert_hits_equal, set_uniforms_from_oracle
 
 pytestmark = pytest.mark.gpu
 
@@ -54,3 +56,169 @@ def test_every_pass_on_one_context_then_close(pkg):
         assert np.array_equal(render.read_nodes(), built)
     finally:
         second.close()
+
+
+def _frames(pkg, gpu, render, n=2):
+    """The records of the n-th frame in a row (from the second on the trace claims from stored lists)."""
+    for _ in range(n):
+        hits = render.render()
+        gpu.sync()  # (a lane runs on a stream of its own: torch's copy below would not wait for it)
+    return pkg.render.hits_to_numpy(hits)
+
+
+def test_context_buffers_grow_are_reused_and_go_with_the_context(pkg, O, monu9_words):
+    """One context renders 320x192, 512x520 and 320x192 again.  512x520 is 4160 strips and 266 240 items, above the
+    schedule slot's floor of 4096 strips and the deferred-ray buffer's floor of 65 536 items: both regrow once, and so
+    does every shading scratch buffer; the third size runs in what the second left.  Then the timing ring, the scatter
+    buffer and the scan lists, and a second context after the first is closed."""
+    import torch
+    if not torch.cuda.is_available():
+        pytest.skip("no GPU")
+    words = monu9_words
+    cap = words.size + 1024
+    refs = {}
+
+    def ref(size):  # (computed once per size)
+        if size not in refs:
+            u = O.make_uniforms(width=size[0], height=size[1], flags=O.F_PAUSE_ADAPTIVE | O.F_SHADOWS)
+            want8 = np.floor(np.clip(O.shade_frame(words, u, threads=8), 0, 1) * 255.0 + 0.5).astype(np.int32)
+            refs[size] = (u, O.trace_frame(words, u, threads=8), want8, O.secondary_frame(words, u, 2, threads=8))
+        return refs[size]
+
+    def shaded_ok(img, want8, what):  # test_shaded_frame's bar
+        diff = np.abs(img.astype(np.int32) - want8)
+        assert diff[..., 3].max() == 0 and (img[..., 3] == 128).all(), what
+        assert diff.max() <= 1, f"{what}: colour off by {diff.max()}"
+        assert (diff == 0).mean() > 0.98, what
+        assert img[..., :3].any(), what
+
+    first = pkg.Gpu(0)
+    try:
+        first.set_option(pkg.gpu.OPT_VARIANT, pkg.gpu.VARIANT_STACK)
+        render = pkg.Render(first, (320, 192), words, capacity=cap)
+        first_frame = None
+        for step, size in enumerate(((320, 192), (512, 520), (320, 192))):
+            W, H = size
+            what = f"size {step}: {W}x{H}"
+            u, want, want8, (oprim, osec) = ref(size)
+            set_uniforms_from_oracle(render, u)
+            got = _frames(pkg, first, render)
+            assert_hits_equal(got, want, what)
+            if first_frame is None:
+                first_frame = got.copy()
+            for fused in (0, 1):  # 0: aux, ray, skip and shadow scratch, schedule slot 1; 1: the shadow records alone
+                first.set_option(pkg.gpu.OPT_FUSED_SHADOWS, fused)
+                for _ in range(2):
+                    hits, img = render.render_host(rgba=True)
+                assert_hits_equal(hits, want, f"{what}: records under shading, fused {fused}")
+                shaded_ok(img, want8, f"{what}: shaded frame, fused {fused}")
+                # the image alone: the records stay in the context's scratch
+                rgba = render.alloc_rgba(W * H)
+                first.check(pkg._lib.lib().svo_render(first._h, W, H, 0, 0, W, H, None, rgba.data_ptr()))
+                first.sync()
+                assert np.array_equal(rgba.cpu().numpy().view(np.uint8).reshape(H, W, 4), img), f"{what}: image without records, fused {fused}"
+                for _ in range(2):
+                    prim, sec = render.render_secondary(2)
+                    first.sync()
+                assert_hits_equal(pkg.render.hits_to_numpy(prim), oprim, f"{what}: primary records of the secondary call, fused {fused}")
+                assert_hits_equal(pkg.render.hits_to_numpy(sec).reshape(2, H, W), osec, f"{what}: secondary rays, fused {fused}")
+            first.set_option(pkg.gpu.OPT_FUSED_SHADOWS, 2)
+            assert_hits_equal(render.render_host(), _frames(pkg, first, render, 1), f"{what}: render_host")
+
+        # the timing ring: only ever longer, restarted by every change
+        for slots, frames in ((2, 5), (4, 3)):
+            first.set_option(pkg.gpu.OPT_TIMING, slots)
+            _frames(pkg, first, render, frames)
+            ms = first.timing_collect()
+            assert ms.size == min(slots, frames) and (ms > 0).all(), (slots, frames, ms)
+        first.set_option(pkg.gpu.OPT_TIMING, 0)
+        with pytest.raises(pkg.SvoError):
+            first.timing_collect()
+
+        # the scatter buffer, grown once: into the spare words behind the tree
+        rng = np.random.default_rng(7)
+        tail = np.zeros(1024, dtype=np.uint32)
+        for n in (8, 64):
+            idx = rng.choice(1024, n, replace=False).astype(np.uint32)
+            vals = rng.integers(0, 1 << 32, n, dtype=np.uint64).astype(np.uint32)
+            render.scatter_nodes(idx + words.size, vals)
+            tail[idx] = vals
+            assert np.array_equal(render.read_nodes(1024, words.size), tail), f"scatter of {n} words"
+
+        # the scan lists, as test_scan_kernel compares them
+        now = render.read_nodes(cap)
+        assert np.array_equal(now[:words.size], words)
+        compute = pkg.Compute(first, render)
+        compute.update(cap)
+        sub, unsub = compute.read_lists()
+        osub, ounsub = O.scan(now, node_length=cap)
+        assert osub[0] > 0 and ounsub[0] > 0
+        assert sorted(sub.tolist()) == osub[1:1 + osub[0]].tolist()
+        assert sorted(unsub.tolist()) == ounsub[1:1 + ounsub[0]].tolist()
+    finally:
+        first.close()
+
+    second = pkg.Gpu(0)
+    try:
+        second.set_option(pkg.gpu.OPT_VARIANT, pkg.gpu.VARIANT_STACK)
+        render = pkg.Render(second, (320, 192), words, capacity=cap)
+        set_uniforms_from_oracle(render, ref((320, 192))[0])
+        assert_hits_equal(_frames(pkg, second, render, 1), first_frame, "second context")
+    finally:
+        second.close()
+
+
+def test_shared_node_store_outlives_its_contexts_in_either_order(pkg, O, small_words, monu9_words):
+    """The store goes with the last context bound to it: lanes go on tracing after the owner's context is closed, and
+    the owner after its lane's."""
+    import torch
+    if not torch.cuda.is_available():
+        pytest.skip("no GPU")
+    cap = max(monu9_words.size, small_words.size)
+    u = O.make_uniforms(width=320, height=192, flags=O.F_PAUSE_ADAPTIVE)
+    want = O.trace_frame(monu9_words, u, threads=8)
+    opened = []
+
+    def context(stream=None):
+        g = pkg.Gpu(0, stream=stream.cuda_stream if stream is not None else None)
+        opened.append(g)
+        g.set_option(pkg.gpu.OPT_VARIANT, pkg.gpu.VARIANT_STACK)
+        return g
+
+    def lane_of(owner):
+        g = context(torch.cuda.Stream())
+        lane = pkg.Render.share_nodes(g, owner)
+        set_uniforms_from_oracle(lane, u)
+        return g, lane
+
+    try:
+        # the owner goes first, then one lane, then the other
+        g0 = context()
+        owner = pkg.Render(g0, (320, 192), monu9_words, capacity=cap)
+        set_uniforms_from_oracle(owner, u)
+        ga, lane_a = lane_of(owner)
+        gb, lane_b = lane_of(owner)
+        for g, r, what in ((g0, owner, "owner"), (ga, lane_a, "lane A"), (gb, lane_b, "lane B")):
+            assert_hits_equal(_frames(pkg, g, r), want, what)
+        g0.close()
+        assert_hits_equal(_frames(pkg, ga, lane_a), want, "lane A after the owner's context is closed")
+        assert_hits_equal(_frames(pkg, gb, lane_b), want, "lane B after the owner's context is closed")
+        ga.close()
+        assert_hits_equal(_frames(pkg, gb, lane_b), want, "lane B after lane A's context is closed")
+        gb.close()
+
+        # the lane goes first
+        g0 = context()
+        owner = pkg.Render(g0, (320, 192), monu9_words, capacity=cap)
+        set_uniforms_from_oracle(owner, u)
+        ga, lane_a = lane_of(owner)
+        assert_hits_equal(_frames(pkg, ga, lane_a), want, "lane")
+        ga.close()
+        assert_hits_equal(_frames(pkg, g0, owner), want, "owner after the lane's context is closed")
+        padded = np.zeros(cap, dtype=np.uint32)
+        padded[:small_words.size] = small_words
+        owner.write_nodes(padded)
+        assert_hits_equal(_frames(pkg, g0, owner), O.trace_frame(padded, u, threads=8), "owner after its upload")
+    finally:
+        for g in opened:
+            g.close()
