@@ -127,38 +127,147 @@ class AdaptiveResult(C.Structure):
     ]
 
 
-DEVICE_SYMBOLS = [
-    "svo_device_count", "svo_buffer_alloc", "svo_buffer_free", "svo_buffer_read", "svo_ctx_create", "svo_ctx_destroy", "svo_ctx_set_stream", "svo_set_option", "svo_last_error", "svo_sync",
-    "svo_nodes_alloc", "svo_nodes_bind_device", "svo_nodes_write", "svo_nodes_scatter", "svo_nodes_read", "svo_nodes_device_ptr", "svo_nodes_share", "svo_nodes_invalidate",
-    "svo_comm_unique_id", "svo_comm_init_rank", "svo_comm_init_all", "svo_comm_destroy", "svo_gather_frame", "svo_gather_frame_all", "svo_gather_wait",
-    "svo_set_uniforms", "svo_render", "svo_render_host", "svo_render_tiles", "svo_render_secondary", "svo_render_tiles_secondary", "svo_assemble_tiles", "svo_assemble_tiles_packed", "svo_assemble_tiles_rgba", "svo_pack_records", "svo_trace_rays",
-    "svo_last_render_ms", "svo_timing_collect", "svo_diag_gather", "svo_diag_strip_classes", "svo_scan_dispatch", "svo_scan_read",
-    "svo_proc_generate_chunk", "svo_world_generate", "svo_proc_sdf", "svo_proc_classify", "svo_proc_timing",
-    "svo_nodes_build", "svo_nodes_build_dense", "svo_buffer_write", "svo_build_timing",
-    "svo_adaptive_attach", "svo_adaptive_step", "svo_adaptive_download", "svo_adaptive_length", "svo_adaptive_timing",
-    "svo_adaptive_expand", "svo_adaptive_expand_timing",
-    "svo_cpu_octree_build", "svo_world_build", "svo_world_build_timing",
-    "svo_nodes_edit", "svo_edit_timing",
-    "svo_nodes_compact", "svo_compact_timing",
-    "svo_nodes_list_voxels", "svo_list_timing",
-    "svo_nodes_sample", "svo_nodes_sample_dense", "svo_sample_timing",
-    "svo_mesh_voxelize", "svo_voxelize_timing",
-]
-HOST_SYMBOLS = [
-    "svo_cpu_octree_new", "svo_cpu_octree_free", "svo_cpu_octree_len", "svo_cpu_octree_load_file",
-    "svo_cpu_octree_load_vox", "svo_cpu_octree_load_rsvo", "svo_cpu_octree_from_voxels",
-    "svo_cpu_octree_put_in_voxel", "svo_cpu_octree_put_in_block", "svo_cpu_octree_find_voxel",
-    "svo_cpu_octree_get_node_mask", "svo_cpu_octree_to_octree", "svo_cpu_octree_raw",
-    "svo_cpu_octree_generate_mips", "svo_vox_parse", "svo_vox_write", "svo_rsvo_write",
-    "svo_octree_new", "svo_octree_from_words", "svo_octree_free", "svo_octree_len", "svo_octree_raw_data",
-    "svo_octree_get_node", "svo_octree_subdivide", "svo_octree_unsubdivide", "svo_octree_find_voxel",
-    "svo_octree_expanded", "svo_octree_pos_offset", "svo_octree_holes", "svo_octree_set_node", "svo_octree_position", "svo_octree_hole_stack", "svo_octree_positions", "svo_octree_take_dirty", "svo_camera_matrices",
-    "svo_world_new", "svo_world_free", "svo_world_last_error", "svo_world_insert", "svo_world_remove",
-    "svo_world_chunk", "svo_world_chunk_ids", "svo_world_find_voxel", "svo_world_generate_mip_tree",
-    "svo_world_save_chunk", "svo_world_load_chunk", "svo_world_load", "svo_cpu_octree_bin", "svo_cpu_octree_from_bin",
-    "svo_adaptive_subdivide", "svo_adaptive_unsubdivide", "svo_world_expand",
-    "svo_gen_terrain", "svo_gen_terrain_height", "svo_gen_fractal", "svo_gen_random", "svo_nodes_max_depth", "svo_nodes_relayout",
-]
+vp, sz, u32, u64, i64, f32 = C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint64, C.c_int64, C.c_float
+cp = C.c_char_p
+fp = C.POINTER(C.c_float)
+
+# the device boundary (include/svo_hip.h): name -> (result, argument types)
+DEVICE_SIGNATURES = {
+    "svo_device_count": (C.c_int, ()),
+    "svo_buffer_alloc": (C.c_int, (vp, sz, C.POINTER(vp))),
+    "svo_buffer_free": (C.c_int, (vp, vp)),
+    "svo_buffer_read": (C.c_int, (vp, vp, vp, sz)),
+    "svo_ctx_create": (C.c_int, (C.c_int, C.POINTER(vp))),
+    "svo_ctx_destroy": (C.c_int, (vp,)),
+    "svo_ctx_set_stream": (C.c_int, (vp, vp, C.c_int)),
+    "svo_set_option": (C.c_int, (vp, C.c_int, i64)),
+    "svo_last_error": (cp, (vp,)),
+    "svo_sync": (C.c_int, (vp,)),
+    "svo_nodes_alloc": (C.c_int, (vp, sz)),
+    "svo_nodes_bind_device": (C.c_int, (vp, vp, sz)),
+    "svo_nodes_write": (C.c_int, (vp, sz, vp, sz)),
+    "svo_nodes_scatter": (C.c_int, (vp, vp, vp, sz)),
+    "svo_nodes_read": (C.c_int, (vp, sz, vp, sz)),
+    "svo_nodes_device_ptr": (C.c_int, (vp, C.POINTER(vp), C.POINTER(sz))),
+    "svo_nodes_share": (C.c_int, (vp, vp)),
+    "svo_nodes_invalidate": (C.c_int, (vp,)),
+    "svo_comm_unique_id": (C.c_int, (vp,)),
+    "svo_comm_init_rank": (C.c_int, (vp, vp, C.c_int, C.c_int)),
+    "svo_comm_init_all": (C.c_int, (C.c_int, C.POINTER(vp))),
+    "svo_comm_destroy": (C.c_int, (vp,)),
+    "svo_gather_frame": (C.c_int, (vp, vp, sz, vp, C.c_int)),
+    "svo_gather_wait": (C.c_int, (vp,)),
+    "svo_gather_frame_all": (C.c_int, (C.c_int, C.POINTER(vp), C.POINTER(vp), sz, vp, C.c_int)),
+    "svo_set_uniforms": (C.c_int, (vp, C.POINTER(Uniforms))),
+    "svo_render": (C.c_int, (vp, u32, u32, u32, u32, u32, u32, vp, vp)),
+    "svo_render_host": (C.c_int, (vp, u32, u32, u32, u32, u32, u32, vp, vp)),
+    "svo_render_tiles": (C.c_int, (vp, u32, u32, u32, u32, u32, u32, vp, vp)),
+    "svo_render_secondary": (C.c_int, (vp, u32, u32, u32, u32, u32, u32, u32, vp, vp)),
+    "svo_render_tiles_secondary": (C.c_int, (vp, u32, u32, u32, u32, u32, u32, u32, vp, vp)),
+    "svo_assemble_tiles": (C.c_int, (vp, vp, u32, u32, u32, u32, u32, u32, vp)),
+    "svo_assemble_tiles_packed": (C.c_int, (vp, vp, u32, u32, u32, u32, u32, u32, vp)),
+    "svo_assemble_tiles_rgba": (C.c_int, (vp, vp, u32, u32, u32, u32, u32, u32, vp)),
+    "svo_pack_records": (C.c_int, (vp, vp, sz, vp)),
+    "svo_trace_rays": (C.c_int, (vp, vp, sz, vp)),
+    "svo_last_render_ms": (C.c_int, (vp, fp)),
+    "svo_timing_collect": (C.c_int, (vp, fp, sz, C.POINTER(sz))),
+    "svo_diag_gather": (C.c_int, (vp, u32, u32)),
+    "svo_diag_strip_classes": (C.c_int, (vp, vp, sz)),
+    "svo_scan_dispatch": (C.c_int, (vp, u32)),
+    "svo_scan_read": (C.c_int, (vp, vp, C.POINTER(u32), vp, C.POINTER(u32), sz)),
+    "svo_proc_generate_chunk": (C.c_int, (vp, C.POINTER(ProcParams), C.POINTER(vp))),
+    "svo_world_generate": (C.c_int, (vp, vp, u32, u32)),
+    "svo_proc_sdf": (C.c_int, (vp, vp, sz, vp)),
+    "svo_proc_classify": (C.c_int, (vp, C.POINTER(ProcParams), vp)),
+    "svo_proc_timing": (C.c_int, (vp, fp)),
+    "svo_nodes_build": (C.c_int, (vp, vp, vp, sz, C.POINTER(BuildParams), C.POINTER(u64))),
+    "svo_nodes_build_dense": (C.c_int, (vp, vp, C.POINTER(BuildParams), C.POINTER(u64))),
+    "svo_buffer_write": (C.c_int, (vp, vp, vp, sz)),
+    "svo_build_timing": (C.c_int, (vp, fp)),
+    "svo_cpu_octree_build": (C.c_int, (vp, vp, vp, sz, C.POINTER(ChunkBuildParams), C.POINTER(vp))),
+    "svo_world_build": (C.c_int, (vp, vp, vp, vp, sz, C.POINTER(ChunkBuildParams))),
+    "svo_world_build_timing": (C.c_int, (vp, fp)),
+    "svo_nodes_edit": (C.c_int, (vp, vp, vp, sz, C.POINTER(EditParams), C.POINTER(u64))),
+    "svo_edit_timing": (C.c_int, (vp, fp)),
+    "svo_nodes_compact": (C.c_int, (vp, C.POINTER(CompactParams), vp, C.POINTER(u64))),
+    "svo_compact_timing": (C.c_int, (vp, fp)),
+    "svo_nodes_list_voxels": (C.c_int, (vp, C.POINTER(ListParams), vp, vp, vp, C.POINTER(u64))),
+    "svo_list_timing": (C.c_int, (vp, fp)),
+    "svo_nodes_sample": (C.c_int, (vp, C.POINTER(SampleParams), vp, sz, vp, vp, vp)),
+    "svo_nodes_sample_dense": (C.c_int, (vp, C.POINTER(SampleParams), C.POINTER(u32), C.POINTER(u32), vp)),
+    "svo_sample_timing": (C.c_int, (vp, fp)),
+    "svo_mesh_voxelize": (C.c_int, (vp, C.POINTER(VoxelizeParams), vp, vp, vp, sz, vp, vp, vp, C.POINTER(u64))),
+    "svo_voxelize_timing": (C.c_int, (vp, fp)),
+    "svo_adaptive_attach": (C.c_int, (vp, vp, vp)),
+    "svo_adaptive_step": (C.c_int, (vp, vp, u32, vp, u32, C.POINTER(AdaptiveResult))),
+    "svo_adaptive_download": (C.c_int, (vp, vp)),
+    "svo_adaptive_length": (C.c_int, (vp, C.POINTER(u64))),
+    "svo_adaptive_timing": (C.c_int, (vp, fp)),
+    "svo_adaptive_expand": (C.c_int, (vp, u32, fp, f32, u64, C.POINTER(AdaptiveResult))),
+    "svo_adaptive_expand_timing": (C.c_int, (vp, fp)),
+}
+# the host data model (include/svo_host.h): name -> (result, argument types)
+HOST_SIGNATURES = {
+    "svo_cpu_octree_new": (vp, (C.c_uint8,)),
+    "svo_cpu_octree_free": (None, (vp,)),
+    "svo_cpu_octree_len": (sz, (vp,)),
+    "svo_cpu_octree_load_file": (vp, (cp, u32, cp, sz)),
+    "svo_cpu_octree_load_vox": (vp, (cp, sz, cp, sz)),
+    "svo_cpu_octree_load_rsvo": (vp, (cp, sz, u32, cp, sz)),
+    "svo_cpu_octree_from_voxels": (vp, (u32, vp, sz, vp, cp, sz)),
+    "svo_cpu_octree_put_in_voxel": (None, (vp, fp, C.POINTER(C.c_uint8), u32)),
+    "svo_cpu_octree_put_in_block": (None, (vp, fp, u32, u32)),
+    "svo_cpu_octree_find_voxel": (None, (vp, fp, i64, C.POINTER(u64), C.POINTER(u32), fp)),
+    "svo_cpu_octree_get_node_mask": (None, (vp, sz, C.POINTER(C.c_uint8))),
+    "svo_cpu_octree_to_octree": (None, (vp, vp)),
+    "svo_cpu_octree_raw": (None, (vp, vp, vp)),
+    "svo_cpu_octree_generate_mips": (None, (vp, C.POINTER(C.c_uint8))),
+    "svo_vox_parse": (i64, (cp, sz, C.POINTER(u32), vp, sz, vp, cp, sz)),
+    "svo_vox_write": (sz, (u32, vp, sz, vp, vp, sz)),
+    "svo_rsvo_write": (sz, (vp, vp, sz)),
+    "svo_octree_new": (vp, (C.POINTER(C.c_uint8),)),
+    "svo_octree_from_words": (vp, (vp, sz)),
+    "svo_octree_free": (None, (vp,)),
+    "svo_octree_len": (sz, (vp,)),
+    "svo_octree_raw_data": (vp, (vp,)),
+    "svo_octree_get_node": (u32, (vp, sz)),
+    "svo_octree_subdivide": (C.c_int, (vp, sz, C.POINTER(C.c_uint8), u32)),
+    "svo_octree_unsubdivide": (C.c_int, (vp, sz)),
+    "svo_octree_find_voxel": (None, (vp, fp, i64, C.POINTER(u64), C.POINTER(u32), fp)),
+    "svo_octree_expanded": (C.c_int, (vp, sz, vp)),
+    "svo_octree_pos_offset": (None, (u32, u32, fp)),
+    "svo_octree_holes": (sz, (vp,)),
+    "svo_octree_set_node": (None, (vp, sz, u32)),
+    "svo_octree_position": (None, (vp, sz, fp)),
+    "svo_octree_hole_stack": (sz, (vp, vp, sz)),
+    "svo_octree_positions": (sz, (vp, vp, sz)),
+    "svo_octree_take_dirty": (sz, (vp, vp, vp, sz)),
+    "svo_world_new": (vp, (cp,)),
+    "svo_world_free": (None, (vp,)),
+    "svo_world_last_error": (cp, (vp,)),
+    "svo_world_insert": (C.c_int, (vp, u32, vp)),
+    "svo_world_remove": (C.c_int, (vp, u32)),
+    "svo_world_chunk": (vp, (vp, u32)),
+    "svo_world_chunk_ids": (sz, (vp, vp, sz)),
+    "svo_world_find_voxel": (C.c_int, (vp, fp, i64, C.POINTER(u32), C.POINTER(u64), C.POINTER(u32), fp)),
+    "svo_world_generate_mip_tree": (C.c_int, (vp, u32, C.POINTER(C.c_uint8))),
+    "svo_world_save_chunk": (C.c_int, (vp, u32)),
+    "svo_world_load_chunk": (C.c_int, (vp, u32)),
+    "svo_world_load": (vp, (cp, cp, sz)),
+    "svo_cpu_octree_bin": (sz, (vp, vp, sz)),
+    "svo_cpu_octree_from_bin": (vp, (cp, sz, cp, sz)),
+    "svo_adaptive_subdivide": (i64, (vp, vp, vp, sz, C.POINTER(u64))),
+    "svo_adaptive_unsubdivide": (i64, (vp, vp, vp, sz)),
+    "svo_world_expand": (u64, (vp, vp, u32, fp, f32, u64)),
+    "svo_camera_matrices": (None, (fp, fp, f32, f32, f32, fp, fp)),
+    "svo_gen_terrain": (u64, (C.POINTER(TerrainParams), vp, u64)),
+    "svo_gen_terrain_height": (C.c_int32, (u32, u32, u32, u32)),
+    "svo_gen_fractal": (u64, (C.POINTER(TerrainParams), vp, u64)),
+    "svo_gen_random": (u64, (u32, u32, f32, f32, u64, vp, u64)),
+    "svo_nodes_max_depth": (u32, (vp, u64)),
+    "svo_nodes_relayout": (u64, (vp, u64, u32, vp, vp)),
+}
+DEVICE_SYMBOLS, HOST_SYMBOLS = list(DEVICE_SIGNATURES), list(HOST_SIGNATURES)
 
 _lib = None
 
@@ -172,147 +281,11 @@ def lib():
             f"{LIB_PATH} is missing: build it with `make -C octree-tracer_amd/csrc` "
             "(or __graft_entry__.build()); there is no CPU fallback")
     L = C.CDLL(LIB_PATH)
-    vp, sz, u32, u64, i64, f32 = C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint64, C.c_int64, C.c_float
-    cp = C.c_char_p
-    fp = C.POINTER(C.c_float)
-
-    def sig(name, res, *args):
-        fn = getattr(L, name)
-        fn.restype = res
-        fn.argtypes = list(args)
-
-    # device boundary (include/svo_hip.h)
-    sig("svo_device_count", C.c_int)
-    sig("svo_buffer_alloc", C.c_int, vp, sz, C.POINTER(vp))
-    sig("svo_buffer_free", C.c_int, vp, vp)
-    sig("svo_buffer_read", C.c_int, vp, vp, vp, sz)
-    sig("svo_ctx_create", C.c_int, C.c_int, C.POINTER(vp))
-    sig("svo_ctx_destroy", C.c_int, vp)
-    sig("svo_ctx_set_stream", C.c_int, vp, vp, C.c_int)
-    sig("svo_set_option", C.c_int, vp, C.c_int, i64)
-    sig("svo_last_error", cp, vp)
-    sig("svo_sync", C.c_int, vp)
-    sig("svo_nodes_alloc", C.c_int, vp, sz)
-    sig("svo_nodes_bind_device", C.c_int, vp, vp, sz)
-    sig("svo_nodes_write", C.c_int, vp, sz, vp, sz)
-    sig("svo_nodes_scatter", C.c_int, vp, vp, vp, sz)
-    sig("svo_nodes_read", C.c_int, vp, sz, vp, sz)
-    sig("svo_nodes_device_ptr", C.c_int, vp, C.POINTER(vp), C.POINTER(sz))
-    sig("svo_nodes_share", C.c_int, vp, vp)
-    sig("svo_nodes_invalidate", C.c_int, vp)
-    sig("svo_comm_unique_id", C.c_int, vp)
-    sig("svo_comm_init_rank", C.c_int, vp, vp, C.c_int, C.c_int)
-    sig("svo_comm_init_all", C.c_int, C.c_int, C.POINTER(vp))
-    sig("svo_comm_destroy", C.c_int, vp)
-    sig("svo_gather_frame", C.c_int, vp, vp, sz, vp, C.c_int)
-    sig("svo_gather_wait", C.c_int, vp)
-    sig("svo_gather_frame_all", C.c_int, C.c_int, C.POINTER(vp), C.POINTER(vp), sz, vp, C.c_int)
-    sig("svo_set_uniforms", C.c_int, vp, C.POINTER(Uniforms))
-    sig("svo_render", C.c_int, vp, u32, u32, u32, u32, u32, u32, vp, vp)
-    sig("svo_render_host", C.c_int, vp, u32, u32, u32, u32, u32, u32, vp, vp)
-    sig("svo_render_tiles", C.c_int, vp, u32, u32, u32, u32, u32, u32, vp, vp)
-    sig("svo_render_secondary", C.c_int, vp, u32, u32, u32, u32, u32, u32, u32, vp, vp)
-    sig("svo_render_tiles_secondary", C.c_int, vp, u32, u32, u32, u32, u32, u32, u32, vp, vp)
-    sig("svo_assemble_tiles", C.c_int, vp, vp, u32, u32, u32, u32, u32, u32, vp)
-    sig("svo_assemble_tiles_packed", C.c_int, vp, vp, u32, u32, u32, u32, u32, u32, vp)
-    sig("svo_assemble_tiles_rgba", C.c_int, vp, vp, u32, u32, u32, u32, u32, u32, vp)
-    sig("svo_pack_records", C.c_int, vp, vp, sz, vp)
-    sig("svo_trace_rays", C.c_int, vp, vp, sz, vp)
-    sig("svo_last_render_ms", C.c_int, vp, fp)
-    sig("svo_timing_collect", C.c_int, vp, fp, sz, C.POINTER(sz))
-    sig("svo_diag_gather", C.c_int, vp, u32, u32)
-    sig("svo_diag_strip_classes", C.c_int, vp, vp, sz)
-    sig("svo_scan_dispatch", C.c_int, vp, u32)
-    sig("svo_scan_read", C.c_int, vp, vp, C.POINTER(u32), vp, C.POINTER(u32), sz)
-    sig("svo_proc_generate_chunk", C.c_int, vp, C.POINTER(ProcParams), C.POINTER(vp))
-    sig("svo_world_generate", C.c_int, vp, vp, u32, u32)
-    sig("svo_proc_sdf", C.c_int, vp, vp, sz, vp)
-    sig("svo_proc_classify", C.c_int, vp, C.POINTER(ProcParams), vp)
-    sig("svo_proc_timing", C.c_int, vp, fp)
-    sig("svo_nodes_build", C.c_int, vp, vp, vp, sz, C.POINTER(BuildParams), C.POINTER(u64))
-    sig("svo_nodes_build_dense", C.c_int, vp, vp, C.POINTER(BuildParams), C.POINTER(u64))
-    sig("svo_buffer_write", C.c_int, vp, vp, vp, sz)
-    sig("svo_build_timing", C.c_int, vp, fp)
-    sig("svo_cpu_octree_build", C.c_int, vp, vp, vp, sz, C.POINTER(ChunkBuildParams), C.POINTER(vp))
-    sig("svo_world_build", C.c_int, vp, vp, vp, vp, sz, C.POINTER(ChunkBuildParams))
-    sig("svo_world_build_timing", C.c_int, vp, fp)
-    sig("svo_nodes_edit", C.c_int, vp, vp, vp, sz, C.POINTER(EditParams), C.POINTER(u64))
-    sig("svo_edit_timing", C.c_int, vp, fp)
-    sig("svo_nodes_compact", C.c_int, vp, C.POINTER(CompactParams), vp, C.POINTER(u64))
-    sig("svo_compact_timing", C.c_int, vp, fp)
-    sig("svo_nodes_list_voxels", C.c_int, vp, C.POINTER(ListParams), vp, vp, vp, C.POINTER(u64))
-    sig("svo_list_timing", C.c_int, vp, fp)
-    sig("svo_nodes_sample", C.c_int, vp, C.POINTER(SampleParams), vp, C.c_size_t, vp, vp, vp)
-    sig("svo_nodes_sample_dense", C.c_int, vp, C.POINTER(SampleParams), C.POINTER(u32), C.POINTER(u32), vp)
-    sig("svo_sample_timing", C.c_int, vp, fp)
-    sig("svo_mesh_voxelize", C.c_int, vp, C.POINTER(VoxelizeParams), vp, vp, vp, sz, vp, vp, vp, C.POINTER(u64))
-    sig("svo_voxelize_timing", C.c_int, vp, fp)
-    sig("svo_adaptive_attach", C.c_int, vp, vp, vp)
-    sig("svo_adaptive_step", C.c_int, vp, vp, u32, vp, u32, C.POINTER(AdaptiveResult))
-    sig("svo_adaptive_download", C.c_int, vp, vp)
-    sig("svo_adaptive_length", C.c_int, vp, C.POINTER(u64))
-    sig("svo_adaptive_timing", C.c_int, vp, fp)
-    sig("svo_adaptive_expand", C.c_int, vp, u32, fp, f32, u64, C.POINTER(AdaptiveResult))
-    sig("svo_adaptive_expand_timing", C.c_int, vp, fp)
-    # host data model (include/svo_host.h)
-    sig("svo_cpu_octree_new", vp, C.c_uint8)
-    sig("svo_cpu_octree_free", None, vp)
-    sig("svo_cpu_octree_len", sz, vp)
-    sig("svo_cpu_octree_load_file", vp, cp, u32, cp, sz)
-    sig("svo_cpu_octree_load_vox", vp, cp, sz, cp, sz)
-    sig("svo_cpu_octree_load_rsvo", vp, cp, sz, u32, cp, sz)
-    sig("svo_cpu_octree_from_voxels", vp, u32, vp, sz, vp, cp, sz)
-    sig("svo_cpu_octree_put_in_voxel", None, vp, fp, C.POINTER(C.c_uint8), u32)
-    sig("svo_cpu_octree_put_in_block", None, vp, fp, u32, u32)
-    sig("svo_cpu_octree_find_voxel", None, vp, fp, i64, C.POINTER(u64), C.POINTER(u32), fp)
-    sig("svo_cpu_octree_get_node_mask", None, vp, sz, C.POINTER(C.c_uint8))
-    sig("svo_cpu_octree_to_octree", None, vp, vp)
-    sig("svo_cpu_octree_raw", None, vp, vp, vp)
-    sig("svo_cpu_octree_generate_mips", None, vp, C.POINTER(C.c_uint8))
-    sig("svo_vox_parse", i64, cp, sz, C.POINTER(u32), vp, sz, vp, cp, sz)
-    sig("svo_vox_write", sz, u32, vp, sz, vp, vp, sz)
-    sig("svo_rsvo_write", sz, vp, vp, sz)
-    sig("svo_octree_new", vp, C.POINTER(C.c_uint8))
-    sig("svo_octree_from_words", vp, vp, sz)
-    sig("svo_octree_free", None, vp)
-    sig("svo_octree_len", sz, vp)
-    sig("svo_octree_raw_data", vp, vp)
-    sig("svo_octree_get_node", u32, vp, sz)
-    sig("svo_octree_subdivide", C.c_int, vp, sz, C.POINTER(C.c_uint8), u32)
-    sig("svo_octree_unsubdivide", C.c_int, vp, sz)
-    sig("svo_octree_find_voxel", None, vp, fp, i64, C.POINTER(u64), C.POINTER(u32), fp)
-    sig("svo_octree_expanded", C.c_int, vp, sz, vp)
-    sig("svo_octree_pos_offset", None, u32, u32, fp)
-    sig("svo_octree_holes", sz, vp)
-    sig("svo_octree_set_node", None, vp, sz, u32)
-    sig("svo_octree_position", None, vp, sz, fp)
-    sig("svo_octree_hole_stack", sz, vp, vp, sz)
-    sig("svo_octree_positions", sz, vp, vp, sz)
-    sig("svo_octree_take_dirty", sz, vp, vp, vp, sz)
-    sig("svo_world_new", vp, cp)
-    sig("svo_world_free", None, vp)
-    sig("svo_world_last_error", cp, vp)
-    sig("svo_world_insert", C.c_int, vp, u32, vp)
-    sig("svo_world_remove", C.c_int, vp, u32)
-    sig("svo_world_chunk", vp, vp, u32)
-    sig("svo_world_chunk_ids", sz, vp, vp, sz)
-    sig("svo_world_find_voxel", C.c_int, vp, fp, i64, C.POINTER(u32), C.POINTER(u64), C.POINTER(u32), fp)
-    sig("svo_world_generate_mip_tree", C.c_int, vp, u32, C.POINTER(C.c_uint8))
-    sig("svo_world_save_chunk", C.c_int, vp, u32)
-    sig("svo_world_load_chunk", C.c_int, vp, u32)
-    sig("svo_world_load", vp, cp, cp, sz)
-    sig("svo_cpu_octree_bin", sz, vp, vp, sz)
-    sig("svo_cpu_octree_from_bin", vp, cp, sz, cp, sz)
-    sig("svo_adaptive_subdivide", i64, vp, vp, vp, sz, C.POINTER(u64))
-    sig("svo_adaptive_unsubdivide", i64, vp, vp, vp, sz)
-    sig("svo_world_expand", u64, vp, vp, u32, fp, f32, u64)
-    sig("svo_camera_matrices", None, fp, fp, f32, f32, f32, fp, fp)
-    sig("svo_gen_terrain", u64, C.POINTER(TerrainParams), vp, u64)
-    sig("svo_gen_terrain_height", C.c_int32, u32, u32, u32, u32)
-    sig("svo_gen_fractal", u64, C.POINTER(TerrainParams), vp, u64)
-    sig("svo_gen_random", u64, u32, u32, f32, f32, u64, vp, u64)
-    sig("svo_nodes_max_depth", u32, vp, u64)
-    sig("svo_nodes_relayout", u64, vp, u64, u32, vp, vp)
+    for table in (DEVICE_SIGNATURES, HOST_SIGNATURES):
+        for name, (res, args) in table.items():
+            fn = getattr(L, name)
+            fn.restype = res
+            fn.argtypes = list(args)
     _lib = L
     return L
 

@@ -8,6 +8,7 @@ import ctypes as C
 import numpy as np
 import torch
 
+from ._device import wait_for_torch
 from ._lib import AdaptiveResult, lib
 from .gpu import OPT_SCAN_CLEARS_COUNTERS
 from .world import World as _World
@@ -43,7 +44,7 @@ def process_unsubdivision(compute_lists, octree, world):
 
 def _device_list(gpu, nodes):
     """A node list as a contiguous 32-bit tensor on the context's device (torch has no uint32: int32 carries the bits)."""
-    dev = torch.device("cuda", gpu.device)
+    dev = gpu.torch_device
     if isinstance(nodes, torch.Tensor):
         t = nodes.to(dev).reshape(-1)
         if t.dtype != torch.int32:
@@ -73,7 +74,7 @@ class DeviceAdaptive:
         else:
             s = _device_list(self.gpu, sub if sub is not None else [])
             u = _device_list(self.gpu, unsub if unsub is not None else [])
-            torch.cuda.current_stream(s.device).synchronize()  # the lists were made on torch's stream
+            wait_for_torch(self.gpu)
             # (an empty list still needs a device pointer: both or neither)
             ps = s.data_ptr() if s.numel() else u.data_ptr() if u.numel() else self._dummy().data_ptr()
             pu = u.data_ptr() if u.numel() else ps
@@ -100,13 +101,12 @@ class DeviceAdaptive:
 
     def expand_timing(self):
         """Of the last expand: ms listing the leaves, choosing candidates, subdividing (device events), host wall ms, levels."""
-        out = (C.c_float * 5)()
-        self.gpu.check(lib().svo_adaptive_expand_timing(self.gpu._h, out))
-        return list(out[:4]) + [int(out[4])]
+        out = self.gpu._timing(lib().svo_adaptive_expand_timing, 5)
+        return out[:4] + [int(out[4])]
 
     def _dummy(self):
         if getattr(self, "_one", None) is None:
-            self._one = torch.zeros(1, dtype=torch.int32, device=torch.device("cuda", self.gpu.device))
+            self._one = torch.zeros(1, dtype=torch.int32, device=self.gpu.torch_device)
         return self._one
 
     def download(self):
@@ -116,9 +116,7 @@ class DeviceAdaptive:
 
     def timing(self):
         """ms of the last step: sort, subdivide, unsubdivide (device events), host wall time."""
-        out = (C.c_float * 4)()
-        self.gpu.check(lib().svo_adaptive_timing(self.gpu._h, out))
-        return list(out)
+        return self.gpu._timing(lib().svo_adaptive_timing, 4)
 
 
 class AdaptiveLoop:

@@ -3,7 +3,8 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import lib
+from ._device import voxel_list, wait_for_torch
+from ._lib import ChunkBuildParams, lib
 from .octree import Octree, Voxel
 
 CHUNK_OFFSET = 2147483648  # cpu_octree.rs:3
@@ -56,8 +57,8 @@ class CpuOctree:
         voxel (None: `colour`); the last voxel of a cell wins.  Torch tensors on gpu's device or numpy arrays.  None for
         no voxels; a tree of more than max_nodes nodes (default 256 000 000) raises SvoError."""
         out = C.c_void_p()
-        with _chunk_inputs(gpu, coords, depth, colours, colour, 0, max_nodes) as (xyz, col, n, p):
-            gpu.check(lib().svo_cpu_octree_build(gpu._h, xyz, col, n, C.byref(p), C.byref(out)))
+        (xyz, col, n, p), tensors = _chunk_inputs(gpu, coords, depth, colours, colour, 0, max_nodes)  # (the tensors: held across the call)
+        gpu.check(lib().svo_cpu_octree_build(gpu._h, xyz, col, n, C.byref(p), C.byref(out)))
         return cls(_handle=out.value) if out.value else None
 
     def __del__(self):
@@ -128,38 +129,17 @@ class CpuOctree:
         return buf.tobytes()
 
 
-class _chunk_inputs:
-    """Device pointers and svo_chunk_build_params of a chunk build, as Render.build_nodes prepares them; the tensors
-    live until the with-block ends."""
-
-    def __init__(self, gpu, coords, depth, colours, colour, world_depth, max_nodes):
-        import torch
-        from ._lib import ChunkBuildParams
-        from .render import _device_u32
-        dev = torch.device("cuda", gpu.device)
-        self.xyz = _device_u32(coords, dev, clamp=True)
-        if self.xyz.dim() != 2 or self.xyz.shape[1] != 3:
-            raise ValueError(f"coords must be (N, 3), got {tuple(self.xyz.shape)}")
-        self.n = self.xyz.shape[0]
-        self.col = None
-        if colours is not None:
-            self.col = _device_u32(colours, dev, mask=0xFFFFFF).reshape(-1)
-            if self.col.numel() != self.n:
-                raise ValueError(f"{self.col.numel()} colours for {self.n} voxels")
-        p = ChunkBuildParams()
-        p.depth = max(0, int(depth))
-        p.world_depth = max(0, int(world_depth))
-        p.default_colour = int(colour) & 0xFFFFFF
-        p.max_nodes = int(max_nodes or 0)
-        self.p = p
-        torch.cuda.current_stream(dev).synchronize()  # the inputs were made on torch's stream
-
-    def __enter__(self):
-        n = self.n
-        return (self.xyz.data_ptr() if n else None, self.col.data_ptr() if self.col is not None and n else None, n, self.p)
-
-    def __exit__(self, *exc):
-        return False
+def _chunk_inputs(gpu, coords, depth, colours, colour, world_depth, max_nodes):
+    """((coords pointer, colours pointer, n, svo_chunk_build_params), tensors) of a chunk build, the list as
+    Render.build_nodes prepares it; the caller holds `tensors` in a local until its call has returned."""
+    xyz, col, n, xyz_ptr, col_ptr = voxel_list(gpu, coords, colours)
+    p = ChunkBuildParams()
+    p.depth = max(0, int(depth))
+    p.world_depth = max(0, int(world_depth))
+    p.default_colour = int(colour) & 0xFFFFFF
+    p.max_nodes = int(max_nodes or 0)
+    wait_for_torch(gpu)
+    return (xyz_ptr, col_ptr, n, p), (xyz, col)
 
 
 def vox_parse(data: bytes):

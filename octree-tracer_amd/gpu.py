@@ -2,6 +2,8 @@
 HIP context handle from the C ABI."""
 import ctypes as C
 
+import torch
+
 from ._lib import SvoError, lib
 
 OPT_VARIANT, OPT_TIMING, OPT_GRID_BLOCKS, OPT_REFILL_MIN, OPT_STRIP_ITEMS, OPT_DYNAMIC_STRIPS, OPT_PRIO_STEPS, OPT_DEBUG_BUFFER, OPT_SCHEDULE, OPT_TREE_DEPTH, OPT_BLOCK_SHAPE, OPT_SCAN_CLEARS_COUNTERS, OPT_FUSED_SHADOWS, OPT_PAIR_TABLE, OPT_CULL, OPT_CAMERA_SHORTCUT, OPT_SCHEDULE_MOTION = range(17)
@@ -17,9 +19,10 @@ class Gpu:
             raise SvoError(f"svo_ctx_create(device={device}) failed with status {rc} (no usable HIP device?)")
         self._h = h
         self.device = device
+        self.torch_device = torch.device("cuda", device)  # where tensors handed to this context live (made once: the wrappers ask per call)
+        self.tree_depth = 16  # what SVO_OPT_TREE_DEPTH holds: the library's default until set_option is told another
         # torch allocates and copies on its current stream: launch there so tensors handed to the
         # C ABI are ordered with the kernels that read or write them
-        import torch
         self.set_stream(stream if stream is not None else torch.cuda.current_stream(device).cuda_stream)
 
     @classmethod
@@ -39,6 +42,15 @@ class Gpu:
 
     def set_option(self, option, value):
         self.check(lib().svo_set_option(self._h, option, int(value)))
+        if option == OPT_TREE_DEPTH:
+            self.tree_depth = int(value)
+
+    def declare_depth(self, depth, most=21):
+        """The trace kernels must know how deep the tree goes (SVO_OPT_TREE_DEPTH): a depth in 1..most above the one this
+        context holds raises it; nothing here ever lowers it, whoever set it -- the caller or any Render on this context.
+        most: 21, the deepest tree a build or an edit makes."""
+        if 1 <= depth <= most and depth > self.tree_depth:
+            self.set_option(OPT_TREE_DEPTH, depth)
 
     def sync(self):
         """device.poll(Maintain::Wait)"""

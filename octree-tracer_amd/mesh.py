@@ -14,6 +14,7 @@ import ctypes as C
 import numpy as np
 import torch
 
+from ._device import device_u32, voxel_list, wait_for_torch
 from ._lib import VoxelizeParams, lib
 
 SUBBITS = 6  # SVO_VOX_SUBBITS: a cell is 64 quantised steps wide
@@ -36,19 +37,6 @@ def quantize_vertices(vertices, depth):
     return torch.floor(q).to(torch.int64) if tensor else np.floor(q).astype(np.int64)
 
 
-def _as_u32(a, dev, what, clamp):
-    """an integer array as a contiguous int32 device tensor of u32 bit patterns; clamp: values outside [0, 2^31) become -1 or
-    2^31 - 1, which the device's range checks refuse at any depth"""
-    t = a if isinstance(a, torch.Tensor) else torch.as_tensor(np.ascontiguousarray(a))
-    if t.dtype.is_floating_point or t.dtype.is_complex or t.dtype == torch.bool:
-        raise TypeError(f"{what}: integer input expected, got {t.dtype}")
-    t = t.to(dev)
-    if t.dtype != torch.int32:
-        t = t.to(torch.int64)
-        t = t.clamp(-1, 2**31 - 1) if clamp else t & 0xFFFFFF
-    return t.to(torch.int32).contiguous()
-
-
 def voxelize(gpu, vertices, triangles, depth, colours=None, colour=0xFFFFFF, with_triangles=False, quantized=False):
     """Voxelise a triangle mesh on the GPU, conservatively and exactly (svo_mesh_voxelize).  vertices: (V, 3)
     floats in [-1, 1) (quantize_vertices is applied), or with quantized=True its integers; triangles: (T, 3) vertex
@@ -56,28 +44,19 @@ def voxelize(gpu, vertices, triangles, depth, colours=None, colour=0xFFFFFF, wit
     tensors (coords (N, 3) int32, colours (N) int32[, triangles (N) int32]): one entry per triangle and cell of the
     2^depth grid that meet, in ascending triangle index and Morton order within a triangle.  A count query and then a fill,
     like Render.list_voxels.  Raises SvoError for a bad vertex index or coordinate and for 2^31 entries or more."""
-    dev = torch.device("cuda", gpu.device)
+    dev = gpu.torch_device
     depth = int(depth)
-    vq = _as_u32(vertices if quantized else quantize_vertices(vertices, depth), dev, "vertices", clamp=True)
-    tri = _as_u32(triangles, dev, "triangles", clamp=True)
+    vq = device_u32(vertices if quantized else quantize_vertices(vertices, depth), dev, clamp=True, what="vertices")
     if vq.dim() != 2 or vq.shape[1] != 3:
         raise ValueError(f"vertices must be (V, 3), got {tuple(vq.shape)}")
-    if tri.dim() != 2 or tri.shape[1] != 3:
-        raise ValueError(f"triangles must be (T, 3), got {tuple(tri.shape)}")
-    n_tris = tri.shape[0]
-    col = None
-    if colours is not None:
-        col = _as_u32(colours, dev, "colours", clamp=False).reshape(-1)
-        if col.numel() != n_tris:
-            raise ValueError(f"{col.numel()} colours for {n_tris} triangles")
+    tri, col, n_tris, tri_ptr, col_ptr = voxel_list(gpu, triangles, colours, noun="triangles", what="triangles", rows="T")
     p = VoxelizeParams()
     p.depth = max(0, depth)
     p.default_colour = int(colour) & 0xFFFFFF
     p.n_vertices = vq.shape[0]
-    args = (vq.data_ptr() if vq.numel() else None, tri.data_ptr() if n_tris else None,
-            col.data_ptr() if col is not None and n_tris else None, n_tris)
+    args = (vq.data_ptr() if vq.numel() else None, tri_ptr, col_ptr, n_tris)
     n = C.c_uint64()
-    torch.cuda.current_stream(dev).synchronize()  # the inputs were made on torch's stream
+    wait_for_torch(gpu)
     gpu.check(lib().svo_mesh_voxelize(gpu._h, C.byref(p), *args, None, None, None, C.byref(n)))  # the count
     count = n.value
     coords = torch.empty((count, 3), dtype=torch.int32, device=dev)
@@ -85,7 +64,7 @@ def voxelize(gpu, vertices, triangles, depth, colours=None, colour=0xFFFFFF, wit
     out_tris = torch.empty(count, dtype=torch.int32, device=dev) if with_triangles else None
     if count:
         p.max_voxels = count
-        torch.cuda.current_stream(dev).synchronize()  # the tensors were made on torch's stream
+        wait_for_torch(gpu)
         gpu.check(lib().svo_mesh_voxelize(gpu._h, C.byref(p), *args, coords.data_ptr(), out_colours.data_ptr(),
                                           out_tris.data_ptr() if with_triangles else None, C.byref(n)))
     gpu.sync()  # (the inputs may be released by the caller)

@@ -69,9 +69,7 @@ class Procedural:
 
     def timing(self):
         """ms of the last generate_chunk / generate_world phases (svo_proc_timing), by name"""
-        buf = (C.c_float * len(TIMES))()
-        self.gpu.check(lib().svo_proc_timing(self.gpu._h, buf))
-        return dict(zip(TIMES, list(buf)))
+        return dict(zip(TIMES, self.gpu._timing(lib().svo_proc_timing, len(TIMES))))
 
 
 __all__ = ["Procedural", "chunk_layout", "MAX_NODES", "SvoError"]

@@ -4,6 +4,8 @@ import ctypes as C
 import numpy as np
 import torch
 
+from . import sharding
+from ._device import device_u32, voxel_list, wait_for_torch
 from ._lib import BuildParams, CompactParams, EditParams, ListParams, SampleParams, Uniforms, lib
 from .camera import camera_matrices
 
@@ -71,7 +73,7 @@ class Render:
         from .gpu import OPT_SCAN_CLEARS_COUNTERS
         octree = world.root_octree()
         self = cls(gpu, size, octree.raw_data(), capacity)
-        self._declare_depth(max_depth)
+        gpu.declare_depth(max_depth)
         gpu.set_option(OPT_SCAN_CLEARS_COUNTERS, 1)
         device = DeviceAdaptive(gpu, self, octree, world)
         device.expand(max_depth, cam=cam, lod_c=lod_c)
@@ -111,22 +113,11 @@ class Render:
         """Build the tree of a voxel list on the GPU into the node buffer from word 0 (svo_nodes_build).
         coords: (N, 3) integer cells in [0, 2^depth), a torch tensor on this context's device or numpy (copied there);
         colours: N values 0x00RRGGBB or None (every voxel `colour`).  Returns the word count."""
-        dev = torch.device("cuda", self.gpu.device)
-        xyz = _device_u32(coords, dev, clamp=True)
-        if xyz.dim() != 2 or xyz.shape[1] != 3:
-            raise ValueError(f"coords must be (N, 3), got {tuple(xyz.shape)}")
-        n = xyz.shape[0]
-        col = None
-        if colours is not None:
-            col = _device_u32(colours, dev, mask=0xFFFFFF).reshape(-1)
-            if col.numel() != n:
-                raise ValueError(f"{col.numel()} colours for {n} voxels")
+        xyz, col, n, xyz_ptr, col_ptr = voxel_list(self.gpu, coords, colours)
         p = self._build_params(depth, colour, max_words)
         out = C.c_uint64()
-        torch.cuda.current_stream(dev).synchronize()  # the inputs were made on torch's stream
-        rc = lib().svo_nodes_build(self.gpu._h, xyz.data_ptr() if n else None, col.data_ptr() if col is not None and n else None, n,
-                                   C.byref(p), C.byref(out))
-        self.gpu.check(rc)
+        wait_for_torch(self.gpu)
+        self.gpu.check(lib().svo_nodes_build(self.gpu._h, xyz_ptr, col_ptr, n, C.byref(p), C.byref(out)))
         self.gpu.sync()  # (the inputs may be released by the caller)
         self.node_length = out.value
         return out.value
@@ -136,28 +127,17 @@ class Render:
         per distinct cell makes of the first node_length words; colour 0 removes a voxel; a coarser leaf on the way is split
         into empty children.  Inputs as build_nodes.  A cell the tree refines below `depth` raises SvoError and nothing is
         written.  Returns the new length (node_length)."""
-        dev = torch.device("cuda", self.gpu.device)
-        xyz = _device_u32(coords, dev, clamp=True)
-        if xyz.dim() != 2 or xyz.shape[1] != 3:
-            raise ValueError(f"coords must be (N, 3), got {tuple(xyz.shape)}")
-        n = xyz.shape[0]
-        col = None
-        if colours is not None:
-            col = _device_u32(colours, dev, mask=0xFFFFFF).reshape(-1)
-            if col.numel() != n:
-                raise ValueError(f"{col.numel()} colours for {n} voxels")
+        xyz, col, n, xyz_ptr, col_ptr = voxel_list(self.gpu, coords, colours)
         depth = int(depth)
-        self._declare_depth(depth)
+        self.gpu.declare_depth(depth)
         p = EditParams()
         p.depth = max(0, depth)
         p.default_colour = int(colour) & 0xFFFFFF
         p.n_words = int(self.node_length)
         p.max_words = int(max_words or 0)
         out = C.c_uint64()
-        torch.cuda.current_stream(dev).synchronize()  # the inputs were made on torch's stream
-        rc = lib().svo_nodes_edit(self.gpu._h, xyz.data_ptr() if n else None, col.data_ptr() if col is not None and n else None, n,
-                                  C.byref(p), C.byref(out))
-        self.gpu.check(rc)
+        wait_for_torch(self.gpu)
+        self.gpu.check(lib().svo_nodes_edit(self.gpu._h, xyz_ptr, col_ptr, n, C.byref(p), C.byref(out)))
         self.gpu.sync()  # (the inputs may be released by the caller)
         self.node_length = out.value
         return out.value
@@ -168,14 +148,13 @@ class Render:
         the rest comes out in the builder's breadth-first order; the freed tail holds the empty word.  Raises SvoError,
         with nothing written, for a malformed tree or with a device adaptive state attached.  Sets node_length to the new
         length and returns it; with_perm: (length, perm) with perm[new word] = old word as a device int32 tensor."""
-        dev = torch.device("cuda", self.gpu.device)
         p = CompactParams()
         p.flags = 1 if prune else 0
         p.n_words = int(self.node_length)
-        perm = torch.empty(max(int(self.node_length), 1), dtype=torch.int32, device=dev) if with_perm else None
+        perm = torch.empty(max(int(self.node_length), 1), dtype=torch.int32, device=self.gpu.torch_device) if with_perm else None
         out = C.c_uint64()
         if with_perm:
-            torch.cuda.current_stream(dev).synchronize()  # the tensor was made on torch's stream
+            wait_for_torch(self.gpu)
         self.gpu.check(lib().svo_nodes_compact(self.gpu._h, C.byref(p), perm.data_ptr() if with_perm else None, C.byref(out)))
         self.gpu.sync()
         self.node_length = out.value
@@ -190,10 +169,10 @@ class Render:
         found at (`depth` for expanded cells).  depth=None: the depth declared for this tree (16 unless a build, an edit
         or from_world raised it).  Raises SvoError for a tree deeper than `depth`, a malformed tree or 2^31 entries or
         more.  The node buffer is only read."""
-        dev = torch.device("cuda", self.gpu.device)
+        dev = self.gpu.torch_device
         p = ListParams()
         p.flags = 1 if expand else 0
-        p.depth = max(0, int(getattr(self, "_declared_depth", 16) if depth is None else depth))
+        p.depth = max(0, int(self.gpu.tree_depth if depth is None else depth))
         p.n_words = int(self.node_length)
         n = C.c_uint64()
         self.gpu.check(lib().svo_nodes_list_voxels(self.gpu._h, C.byref(p), None, None, None, C.byref(n)))  # the count
@@ -203,7 +182,7 @@ class Render:
         levels = torch.empty(count, dtype=torch.int32, device=dev) if with_levels else None
         if count:
             p.max_voxels = count
-            torch.cuda.current_stream(dev).synchronize()  # the tensors were made on torch's stream
+            wait_for_torch(self.gpu)
             self.gpu.check(lib().svo_nodes_list_voxels(self.gpu._h, C.byref(p), coords.data_ptr(), colours.data_ptr(),
                                                        levels.data_ptr() if with_levels else None, C.byref(n)))
             self.gpu.sync()
@@ -211,7 +190,7 @@ class Render:
 
     def _sample_params(self, depth):
         p = SampleParams()
-        p.depth = max(0, int(getattr(self, "_declared_depth", 16) if depth is None else depth))
+        p.depth = max(0, int(self.gpu.tree_depth if depth is None else depth))
         p.n_words = int(self.node_length)
         return p
 
@@ -223,17 +202,14 @@ class Render:
         SAMPLE_BROKEN where the path met a bad pointer.  with_levels: also the level the walk stopped on; with_indices: also
         the index of the word it stopped on (as in a hit record; -1 for OUTSIDE); in that order.  depth=None: the depth
         declared for this tree, as in list_voxels.  The node buffer is only read."""
-        dev = torch.device("cuda", self.gpu.device)
-        xyz = _device_u32(coords, dev, clamp=True)
-        if xyz.dim() != 2 or xyz.shape[1] != 3:
-            raise ValueError(f"coords must be (N, 3), got {tuple(xyz.shape)}")
-        n = xyz.shape[0]
+        dev = self.gpu.torch_device
+        xyz, _, n, xyz_ptr, _ = voxel_list(self.gpu, coords)
         p = self._sample_params(depth)
         values = torch.empty(n, dtype=torch.int32, device=dev)
         levels = torch.empty(n, dtype=torch.int32, device=dev) if with_levels else None
         indices = torch.empty(n, dtype=torch.int32, device=dev) if with_indices else None
-        torch.cuda.current_stream(dev).synchronize()  # the tensors were made on torch's stream
-        self.gpu.check(lib().svo_nodes_sample(self.gpu._h, C.byref(p), xyz.data_ptr() if n else None, n, values.data_ptr() if n else None,
+        wait_for_torch(self.gpu)
+        self.gpu.check(lib().svo_nodes_sample(self.gpu._h, C.byref(p), xyz_ptr, n, values.data_ptr() if n else None,
                                               levels.data_ptr() if with_levels and n else None,
                                               indices.data_ptr() if with_indices and n else None))
         self.gpu.sync()  # (the inputs may be released by the caller)
@@ -245,7 +221,7 @@ class Render:
         [x, y, z] like build_nodes_dense's grid, read from the tree on the GPU (svo_nodes_sample_dense):
         values and marks as sample_voxels gives them.  The whole grid of a dense-built tree comes back as grid & 0xFFFFFF.
         Raises SvoError for a box that leaves the grid or has 2^31 cells or more.  The node buffer is only read."""
-        dev = torch.device("cuda", self.gpu.device)
+        dev = self.gpu.torch_device
         o, s = [int(v) for v in origin], [int(v) for v in size]
         if len(o) != 3 or len(s) != 3 or min(o + s) < 0 or max(o + s) >= 1 << 32:
             raise ValueError(f"origin and size must be 3 values in [0, 2^32) each, got {o} and {s}")
@@ -254,7 +230,7 @@ class Render:
         fits = 1 <= p.depth <= 21 and all(a + b <= 1 << p.depth for a, b in zip(o, s)) and s[0] * s[1] * s[2] < 1 << 31
         grid = torch.empty(s if fits else (0,), dtype=torch.int32, device=dev)
         room = grid if grid.numel() else torch.empty(1, dtype=torch.int32, device=dev)  # (nothing is written to it)
-        torch.cuda.current_stream(dev).synchronize()  # the tensors were made on torch's stream
+        wait_for_torch(self.gpu)
         self.gpu.check(lib().svo_nodes_sample_dense(self.gpu._h, C.byref(p), (C.c_uint32 * 3)(*o), (C.c_uint32 * 3)(*s), room.data_ptr()))
         self.gpu.sync()
         return grid
@@ -262,30 +238,22 @@ class Render:
     def build_nodes_dense(self, grid, max_words=None):
         """Build the tree of a dense (side, side, side) colour grid indexed [x, y, z] (non-zero = voxel, low 24 bits the
         colour; side = 2^depth, depth 1..10) on the GPU (svo_nodes_build_dense).  Returns the word count."""
-        dev = torch.device("cuda", self.gpu.device)
-        g = _device_u32(grid, dev, cells=True)
+        g = device_u32(grid, self.gpu.torch_device, cells=True)
         side = g.shape[0] if g.dim() == 3 else 0
         depth = side.bit_length() - 1
         if g.dim() != 3 or tuple(g.shape) != (side,) * 3 or side != 1 << depth:
             raise ValueError(f"grid must be (side, side, side) with side a power of two, got {tuple(g.shape)}")
         p = self._build_params(depth, 0, max_words)
         out = C.c_uint64()
-        torch.cuda.current_stream(dev).synchronize()
+        wait_for_torch(self.gpu)
         self.gpu.check(lib().svo_nodes_build_dense(self.gpu._h, g.data_ptr(), C.byref(p), C.byref(out)))
         self.gpu.sync()
         self.node_length = out.value
         return out.value
 
-    def _declare_depth(self, depth):
-        # the trace kernels must know how deep the tree goes (SVO_OPT_TREE_DEPTH; raised, never lowered)
-        if 1 <= depth <= 21 and depth > getattr(self, "_declared_depth", 16):
-            from .gpu import OPT_TREE_DEPTH
-            self.gpu.set_option(OPT_TREE_DEPTH, depth)
-            self._declared_depth = depth
-
     def _build_params(self, depth, colour, max_words):
         depth = int(depth)
-        self._declare_depth(depth)
+        self.gpu.declare_depth(depth)
         p = BuildParams()
         p.depth = max(0, depth)
         p.default_colour = int(colour) & 0xFFFFFF
@@ -325,13 +293,10 @@ class Render:
         """render.rs:191-215: camera = proj * look_at_rh; upload the uniforms."""
         w, h = self.size
         # Settings.octree_depth (app.rs:24) is the depth the adaptive loop refines to: a tree may reach it, so it is declared to the
-        # library when it exceeds the default kernel's 16 levels (SVO_OPT_TREE_DEPTH; never lowered here -- ADVICE r4: a deeper
-        # scene used to fail only at svo_sync)
+        # library when it exceeds what the context holds (ADVICE r4: a deeper scene used to fail only at svo_sync); any depth,
+        # the library words the refusal of one the option does not take
         depth = int(getattr(settings, "octree_depth", 0) or 0)
-        if depth > 16 and depth > getattr(self, "_declared_depth", 16):
-            from .gpu import OPT_TREE_DEPTH
-            self.gpu.set_option(OPT_TREE_DEPTH, depth)
-            self._declared_depth = depth
+        self.gpu.declare_depth(depth, most=depth)
         cam, inv = camera_matrices(character.pos, character.look, settings.fov, w, h)
         self.uniforms.camera[:] = cam.tolist()
         self.uniforms.camera_inverse[:] = inv.tolist()
@@ -345,11 +310,14 @@ class Render:
         dev = device if device is not None else f"cuda:{self.gpu.device}"
         return torch.empty((n_pixels, 4), dtype=torch.int32, device=dev)
 
+    def _rect(self, tile):
+        """(frame w, h, x0, y0, w, h) of `tile`; None: the whole frame"""
+        return self.size + (tuple(tile) if tile is not None else (0, 0) + self.size)
+
     def render(self, hits=None, tile=None, rgba=None):
         """Trace every pixel of the frame (or of tile=(x0, y0, w, h)); asynchronous.  Returns the
         device tensor of hit records (n_pixels x 4 int32 = svo_hit)."""
-        w, h = self.size
-        x0, y0, tw, th = tile if tile is not None else (0, 0, w, h)
+        w, h, x0, y0, tw, th = self._rect(tile)
         if hits is None:
             hits = self.alloc_hits(tw * th)
         self.gpu.check(lib().svo_render(self.gpu._h, w, h, x0, y0, tw, th, hits.data_ptr(),
@@ -359,8 +327,7 @@ class Render:
     def render_tiles(self, tile_w, tile_h, first_tile, tile_stride, hits=None, rgba=None):
         """This rank's tiles (first_tile, first_tile + tile_stride, ...), contiguous in that order."""
         w, h = self.size
-        n_tiles_total = (w // tile_w) * (h // tile_h)
-        n_mine = max(0, (n_tiles_total - first_tile + tile_stride - 1) // tile_stride)
+        n_mine = sharding.local_tile_count(w, h, tile_w, tile_h, first_tile, tile_stride)
         if hits is None:
             hits = self.alloc_hits(n_mine * tile_w * tile_h)
         self.gpu.check(lib().svo_render_tiles(self.gpu._h, w, h, tile_w, tile_h, first_tile, tile_stride,
@@ -370,8 +337,7 @@ class Render:
     def render_secondary(self, n_secondary, tile=None, hits=None, secondary=None):
         """Primary rays plus n_secondary rays per hit pixel (svo_render_secondary): returns (primary records,
         secondary records [n_secondary * n_pixels, ray-major]) as device tensors; asynchronous."""
-        w, h = self.size
-        x0, y0, tw, th = tile if tile is not None else (0, 0, w, h)
+        w, h, x0, y0, tw, th = self._rect(tile)
         if hits is None:
             hits = self.alloc_hits(tw * th)
         if secondary is None:
@@ -383,8 +349,7 @@ class Render:
     def render_tiles_secondary(self, tile_w, tile_h, first_tile, tile_stride, n_secondary, hits=None, secondary=None):
         """render_tiles with secondary rays: this rank's tiles, contiguous; secondary ray-major over them."""
         w, h = self.size
-        n_tiles_total = (w // tile_w) * (h // tile_h)
-        n_mine = max(0, (n_tiles_total - first_tile + tile_stride - 1) // tile_stride)
+        n_mine = sharding.local_tile_count(w, h, tile_w, tile_h, first_tile, tile_stride)
         if hits is None:
             hits = self.alloc_hits(n_mine * tile_w * tile_h)
         if secondary is None:
@@ -424,8 +389,7 @@ class Render:
     def render_host(self, tile=None, rgba=False):
         """Blocking variant with host results: hit records (numpy structured array, tile-local row-major)
         and, with rgba=True, also the shaded RGBA8 image of fs_main (uint8 [h, w, 4])."""
-        w, h = self.size
-        x0, y0, tw, th = tile if tile is not None else (0, 0, w, h)
+        w, h, x0, y0, tw, th = self._rect(tile)
         out = np.empty((th, tw), dtype=HIT_DTYPE)
         img = np.empty((th, tw), dtype=np.uint32) if rgba else None
         self.gpu.check(lib().svo_render_host(self.gpu._h, w, h, x0, y0, tw, th, out.ctypes.data,
@@ -443,25 +407,6 @@ class Render:
             hits = self.alloc_hits(n, rays.device)
         self.gpu.check(lib().svo_trace_rays(self.gpu._h, rays.data_ptr(), n, hits.data_ptr()))
         return hits
-
-
-def _device_u32(a, dev, clamp=False, mask=None, cells=False):
-    """An integer array as a contiguous int32 tensor on `dev` holding u32 bit patterns.  clamp: values outside [0, 2^31)
-    become -1 or 2^31 - 1, out of range for any depth, so the device's range check still sees them; mask: keep those bits;
-    cells: a wide value stays non-zero iff it was (its low 24 bits kept)."""
-    t = a if isinstance(a, torch.Tensor) else torch.as_tensor(np.ascontiguousarray(a))
-    if t.dtype.is_floating_point or t.dtype.is_complex or t.dtype == torch.bool:
-        raise TypeError(f"integer input expected, got {t.dtype}")
-    t = t.to(dev)
-    if t.dtype != torch.int32 or mask is not None:
-        t = t.to(torch.int64)
-        if mask is not None:
-            t = t & mask
-        elif clamp:
-            t = t.clamp(-1, 2**31 - 1)
-        elif cells:
-            t = torch.where(t != 0, (t & 0xFFFFFF) | (1 << 24), 0)
-    return t.to(torch.int32).contiguous()
 
 
 def hits_to_numpy(hits):

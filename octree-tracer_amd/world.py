@@ -62,8 +62,8 @@ class World:
         SvoError and nothing is created.  Returns World.load_world(path)."""
         from .cpu_octree import _chunk_inputs
         w = World(path)
-        with _chunk_inputs(gpu, coords, depth, colours, colour, world_depth, max_nodes) as (xyz, col, n, p):
-            gpu.check(lib().svo_world_build(gpu._h, w._h, xyz, col, n, C.byref(p)))
+        (xyz, col, n, p), tensors = _chunk_inputs(gpu, coords, depth, colours, colour, world_depth, max_nodes)  # (the tensors: held across the call)
+        gpu.check(lib().svo_world_build(gpu._h, w._h, xyz, col, n, C.byref(p)))
         return World.load_world(path)
 
     @staticmethod

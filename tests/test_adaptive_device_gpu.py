@@ -1,36 +1,14 @@
 """The adaptive step on the GPU (svo_adaptive_step) against the host path it replaces:
 svo_adaptive_subdivide(sorted(sub)) then svo_adaptive_unsubdivide(sorted(unsub)), bit for bit."""
-import os
 
 import numpy as np
 import pytest
 
-from conftest import GOLDEN, load_vox_fixture
+from pass_frame import assert_octrees_equal, monu9_world, write_blocks
 
 pytestmark = pytest.mark.gpu
 
 VOXEL_OFFSET = 1 << 27  # octree.rs:5: words at or above VOXEL_OFFSET << 4 are leaves
-BLOCKS = ("stone", "dirt", "grass", "wood", "leaf", "slate", "crystal", "glass")
-
-
-def write_blocks(pkg, d):
-    z = np.load(os.path.join(GOLDEN, "blocks_vox.npz"))
-    os.makedirs(d)
-    for name in BLOCKS:
-        with open(os.path.join(d, name + ".vox"), "wb") as f:
-            f.write(pkg.cpu_octree.vox_write(16, z[name + "_xyzi"], z[name + "_palette"]))
-
-
-def assert_octrees_equal(a, b, what=""):
-    assert len(a) == len(b), f"{what}: lengths {len(a)} != {len(b)}"
-    assert np.array_equal(a.raw_data(), b.raw_data()), f"{what}: words differ"
-    assert np.array_equal(a.positions().view(np.uint32), b.positions().view(np.uint32)), f"{what}: positions differ"
-    assert np.array_equal(a.hole_stack(), b.hole_stack()), f"{what}: hole stacks differ"
-
-
-def monu9_world(pkg):
-    size, xyzi, pal, _, _ = load_vox_fixture("monu9")
-    return pkg.adaptive.World(pkg.CpuOctree.from_voxels(size, xyzi, pal))
 
 
 def make_loop(pkg, world, octree, on_device, capacity=200_000, size=(160, 96)):

@@ -9,6 +9,7 @@ import pytest
 
 import build_ref as B
 from conftest import GOLDEN, assert_hits_equal, set_uniforms_from_oracle
+from pass_frame import assert_words, own_gpu  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -17,30 +18,13 @@ ERR_ARG, ERR_STATE, ERR_CAP = -1, -3, -6
 
 
 @pytest.fixture(scope="module")
-def bgpu(pkg):
-    """a context of this module's own: the depth-21 builds raise its SVO_OPT_TREE_DEPTH"""
-    import torch
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    g = pkg.Gpu(0)
-    yield g
-    g.close()
-
-
-@pytest.fixture(scope="module")
-def render(pkg, bgpu):
-    return pkg.Render(bgpu, (64, 64), np.full(8, B.EMPTY, dtype=np.uint32), capacity=CAPACITY)
+def render(pkg, own_gpu):
+    return pkg.Render(own_gpu, (64, 64), np.full(8, B.EMPTY, dtype=np.uint32), capacity=CAPACITY)
 
 
 def gpu_build(render, coords, depth, colours=None, **kw):
     n = render.build_nodes(coords, depth, colours, **kw)
     return render.read_nodes(n)
-
-
-def assert_words(got, want, what):
-    assert got.size == want.size, f"{what}: {got.size} words, want {want.size}"
-    bad = np.flatnonzero(got != want)
-    assert bad.size == 0, f"{what}: {bad.size} words differ, first at {bad[:5]}: got {got[bad[:5]]} want {want[bad[:5]]}"
 
 
 def height_field(seed, depth, side, origin=(0, 0)):
@@ -87,7 +71,7 @@ def test_random_sets_match_numpy(render, depth):
         assert_words(got, B.build(coords, depth, None, colour=0xABCDEF), f"depth {depth}, n {n}, one colour")
 
 
-def test_millions_of_voxels_match_numpy(render, bgpu):
+def test_millions_of_voxels_match_numpy(render, own_gpu):
     """every radix pass and multi-tile scans: 4 M voxels clustered in a 256^3 block of a depth-16 cube"""
     rng = np.random.default_rng(5)
     n = 4_000_000
@@ -96,7 +80,7 @@ def test_millions_of_voxels_match_numpy(render, bgpu):
     colours = rng.integers(0, 1 << 24, n)
     got = gpu_build(render, coords, 16, colours)
     assert_words(got, B.build(coords, 16, colours), "4 M voxels")
-    ms = bgpu.build_timing()
+    ms = own_gpu.build_timing()
     assert len(ms) == 6 and all(t >= 0 for t in ms) and ms[1] > 0
 
 
@@ -138,29 +122,29 @@ def raw_build(pkg, gpu, xyz, depth, max_words=0, n=None):
     return rc, out.value
 
 
-def test_errors_leave_the_node_buffer_untouched(pkg, render, bgpu):
+def test_errors_leave_the_node_buffer_untouched(pkg, render, own_gpu):
     import torch
     sentinel = np.arange(0xDEAD0000, 0xDEAD0000 + 4096, dtype=np.uint32)
     render.write_nodes(sentinel)
-    dev = torch.device("cuda", bgpu.device)
+    dev = torch.device("cuda", own_gpu.device)
     ok = torch.tensor([[1, 2, 3], [7, 7, 7]], dtype=torch.int32, device=dev)
     bad = torch.tensor([[1, 2, 3], [8, 0, 0]], dtype=torch.int32, device=dev)
     neg = torch.tensor([[1, 2, 3], [0, -1, 0]], dtype=torch.int32, device=dev)
-    assert raw_build(pkg, bgpu, bad, 3)[0] == ERR_ARG
-    assert "outside" in pkg._lib.lib().svo_last_error(bgpu._h).decode()
-    assert raw_build(pkg, bgpu, neg, 3)[0] == ERR_ARG
-    assert raw_build(pkg, bgpu, ok, 0)[0] == ERR_ARG
-    assert raw_build(pkg, bgpu, ok, 22)[0] == ERR_ARG
-    assert raw_build(pkg, bgpu, None, 3, n=5)[0] == ERR_ARG
-    assert raw_build(pkg, bgpu, ok, 3, n=1 << 31)[0] == ERR_ARG
-    assert raw_build(pkg, bgpu, ok, 3, max_words=23)[0] == ERR_CAP  # needs 8 + 8 * 2 + 8 * 2 = 40
-    assert raw_build(pkg, bgpu, ok[:0], 3, max_words=7)[0] == ERR_CAP
+    assert raw_build(pkg, own_gpu, bad, 3)[0] == ERR_ARG
+    assert "outside" in pkg._lib.lib().svo_last_error(own_gpu._h).decode()
+    assert raw_build(pkg, own_gpu, neg, 3)[0] == ERR_ARG
+    assert raw_build(pkg, own_gpu, ok, 0)[0] == ERR_ARG
+    assert raw_build(pkg, own_gpu, ok, 22)[0] == ERR_ARG
+    assert raw_build(pkg, own_gpu, None, 3, n=5)[0] == ERR_ARG
+    assert raw_build(pkg, own_gpu, ok, 3, n=1 << 31)[0] == ERR_ARG
+    assert raw_build(pkg, own_gpu, ok, 3, max_words=23)[0] == ERR_CAP  # needs 8 + 8 * 2 + 8 * 2 = 40
+    assert raw_build(pkg, own_gpu, ok[:0], 3, max_words=7)[0] == ERR_CAP
     with pytest.raises(pkg.SvoError):
         render.build_nodes(bad, 3)
     with pytest.raises(pkg.SvoError):
         render.build_nodes_dense(np.ones((4, 4, 4), dtype=np.uint32), max_words=16)
     assert np.array_equal(render.read_nodes(sentinel.size), sentinel)
-    assert raw_build(pkg, bgpu, ok, 3, max_words=40) == (0, 40)
+    assert raw_build(pkg, own_gpu, ok, 3, max_words=40) == (0, 40)
     fresh = pkg.Gpu(0)
     try:
         assert raw_build(pkg, fresh, ok, 3)[0] == ERR_STATE
@@ -168,12 +152,12 @@ def test_errors_leave_the_node_buffer_untouched(pkg, render, bgpu):
         fresh.close()
 
 
-def test_torch_and_numpy_inputs_give_the_same_words(render, bgpu):
+def test_torch_and_numpy_inputs_give_the_same_words(render, own_gpu):
     import torch
     rng = np.random.default_rng(3)
     coords, colours = random_case(rng, 10, 20000)
     want = B.build(coords, 10, colours)
-    dev = torch.device("cuda", bgpu.device)
+    dev = torch.device("cuda", own_gpu.device)
     for c in (coords, coords.astype(np.int32), coords.astype(np.uint32),
               torch.from_numpy(coords).to(dev), torch.from_numpy(coords).to(dev, torch.int32)):
         for col in (colours, torch.from_numpy(colours).to(dev), torch.from_numpy(colours & 0xFFFFFF).to(dev, torch.int32)):
@@ -187,10 +171,10 @@ def frame(pkg, O, r, u):
     return got
 
 
-def test_built_trees_trace_like_the_oracle(pkg, O, bgpu, monu9_words):
+def test_built_trees_trace_like_the_oracle(pkg, O, own_gpu, monu9_words):
     (label, size, xyzi, pal), = B.fixture_models(GOLDEN, "monu9")
     coords, colours, depth = B.vox_voxels(size, xyzi, pal)
-    r = pkg.Render.from_voxels(bgpu, (96, 96), coords, depth, colours, capacity=8_000_000)
+    r = pkg.Render.from_voxels(own_gpu, (96, 96), coords, depth, colours, capacity=8_000_000)
     words = r.read_nodes()
     u = O.make_uniforms(width=96, height=96, flags=O.F_PAUSE_ADAPTIVE)
     got = frame(pkg, O, r, u)
@@ -217,9 +201,9 @@ def test_built_trees_trace_like_the_oracle(pkg, O, bgpu, monu9_words):
     assert (want["info"] >> 16 & 1).sum() > 500
 
 
-def test_replacing_the_tree_through_either_sharing_context(pkg, O, bgpu, small_words):
+def test_replacing_the_tree_through_either_sharing_context(pkg, O, own_gpu, small_words):
     a = np.asarray(small_words)
-    r1 = pkg.Render(bgpu, (80, 80), a, capacity=2_000_000)
+    r1 = pkg.Render(own_gpu, (80, 80), a, capacity=2_000_000)
     g2 = pkg.Gpu(0)
     try:
         r2 = pkg.Render.share_nodes(g2, r1)

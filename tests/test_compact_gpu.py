@@ -10,46 +10,29 @@ import pytest
 
 import build_ref as B
 import compact_ref as K
-import edit_ref as E
 from conftest import GOLDEN, assert_hits_equal, load_vox_fixture
+from pass_frame import SENTINEL, SentinelOut, assert_words, own_gpu, tree7_base  # noqa: F401
 from test_compact_host import malformed_cases, orphaned, survivors
-from test_edit_gpu import CAPACITY, PAD, ROOT, assert_words, edit_voxels, frame, monu9_edits, poison, set_base
+from test_edit_gpu import CAPACITY, PAD, ROOT, frame, monu9_edits, poison, set_base
 
 pytestmark = pytest.mark.gpu
 
 ERR_ARG, ERR_STATE = -1, -3
 PRUNE = 1
-SENTINEL = 0x5EA70000  # what a perm buffer holds where nothing was written
 
 
 @pytest.fixture(scope="module")
-def cgpu(pkg):
-    """a context of this module's own: the depth-21 edit raises its SVO_OPT_TREE_DEPTH"""
-    import torch
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    g = pkg.Gpu(0)
-    yield g
-    g.close()
-
-
-@pytest.fixture(scope="module")
-def render(pkg, cgpu):
-    return pkg.Render(cgpu, (64, 64), ROOT, capacity=CAPACITY)
+def render(pkg, own_gpu):
+    return pkg.Render(own_gpu, (64, 64), ROOT, capacity=CAPACITY)
 
 
 @pytest.fixture(scope="module")
 def tree7():
-    """10 000 random voxels at depth 7 (the two lowest levels have more than 4 096 groups, a scan tile, and group counts
-    that fill no whole wave) edited with 4 097 voxels of which a fifth are removed: A, B, the canonical base, the edited
-    words in put order and the references of both flag settings, computed once"""
-    rng = np.random.default_rng(70)
-    a = rng.integers(0, 128, (10000, 3)), rng.integers(1, 1 << 24, 10000)
-    b = edit_voxels(rng, 7, 4097, a[0], 0)
-    base = B.build(a[0], 7, a[1])
-    words = E.edit(base, base.size, b[0], 7, b[1])
-    return {"a": a, "b": b, "base": base, "words": words, False: K.compact(words, words.size, False),
-            True: K.compact(words, words.size, True)}
+    """pass_frame.tree7_base (A, B, the canonical base, the edited words in put order) and the references of both flag
+    settings, computed once"""
+    t = tree7_base()
+    words = t["words"]
+    return {**t, False: K.compact(words, words.size, False), True: K.compact(words, words.size, True)}
 
 
 def raw_compact(pkg, gpu, flags, n_words, perm=None, params=True, out=True):
@@ -63,10 +46,7 @@ def raw_compact(pkg, gpu, flags, n_words, perm=None, params=True, out=True):
 
 
 def sentinel_perm(gpu, n):
-    import torch
-    t = torch.full((n,), SENTINEL, dtype=torch.int32, device=torch.device("cuda", gpu.device))
-    torch.cuda.current_stream(t.device).synchronize()
-    return t
+    return SentinelOut(gpu, [n]).t[0]
 
 
 def check_compact(pkg, render, words, prune, what, want=None):
@@ -175,18 +155,18 @@ def test_every_run_and_counters(pkg, render, tree7):
     check_compact(pkg, render, counted, True, "counters, pruned", (want, perm))
 
 
-def test_errors_write_nothing(pkg, render, cgpu, tree7):
-    last_error = lambda g=cgpu: pkg._lib.lib().svo_last_error(g._h).decode()  # noqa: E731
+def test_errors_write_nothing(pkg, render, own_gpu, tree7):
+    last_error = lambda g=own_gpu: pkg._lib.lib().svo_last_error(g._h).decode()  # noqa: E731
     base = tree7["base"]
     set_base(render, base)
     before = render.read_nodes(base.size + PAD)
-    perm = sentinel_perm(cgpu, base.size)
+    perm = sentinel_perm(own_gpu, base.size)
     for kw in (dict(params=False), dict(out=False)):
-        assert raw_compact(pkg, cgpu, 0, base.size, perm, **kw)[0] == ERR_ARG and "null" in last_error()
-    assert raw_compact(pkg, cgpu, 2, base.size, perm)[0] == ERR_ARG and "flag" in last_error()
-    assert raw_compact(pkg, cgpu, 1 | 1 << 31, base.size, perm)[0] == ERR_ARG
+        assert raw_compact(pkg, own_gpu, 0, base.size, perm, **kw)[0] == ERR_ARG and "null" in last_error()
+    assert raw_compact(pkg, own_gpu, 2, base.size, perm)[0] == ERR_ARG and "flag" in last_error()
+    assert raw_compact(pkg, own_gpu, 1 | 1 << 31, base.size, perm)[0] == ERR_ARG
     for n in (0, 12, base.size + 4, CAPACITY + 8):
-        assert raw_compact(pkg, cgpu, PRUNE, n, perm) == (ERR_ARG, 0) and "n_words" in last_error()
+        assert raw_compact(pkg, own_gpu, PRUNE, n, perm) == (ERR_ARG, 0) and "n_words" in last_error()
     assert np.array_equal(render.read_nodes(base.size + PAD), before)
 
     causes = {"a pointer with pointer + 8 > n_words": "leaves the first n_words", "an unaligned pointer": "not a multiple of 8",
@@ -197,7 +177,7 @@ def test_errors_write_nothing(pkg, render, cgpu, tree7):
         set_base(render, words)
         before = render.read_nodes(words.size + PAD)
         for flags in (0, PRUNE):
-            assert raw_compact(pkg, cgpu, flags, words.size, perm) == (ERR_STATE, 0), name
+            assert raw_compact(pkg, own_gpu, flags, words.size, perm) == (ERR_STATE, 0), name
             assert "malformed tree: " in last_error() and causes[name] in last_error(), f"{name}: {last_error()}"
         with pytest.raises(pkg.SvoError):
             render.compact_nodes()
@@ -273,18 +253,18 @@ def test_compacted_trees_trace_like_the_oracle(pkg, O):
         g1.close()
 
 
-def test_timing(pkg, render, cgpu, tree7):
+def test_timing(pkg, render, own_gpu, tree7):
     set_base(render, tree7["words"])
     render.compact_nodes()
-    ms = cgpu.compact_timing()
+    ms = own_gpu.compact_timing()
     assert len(ms) == 6 and all(t >= 0 for t in ms) and ms[5] > 0
-    assert ms == cgpu.compact_timing()
+    assert ms == own_gpu.compact_timing()
     # a refused call in between leaves the times of the last compaction that ran, whether they were fetched or not
     render.compact_nodes()
     words = malformed_cases()["two parents sharing one group"]
     set_base(render, words)
-    assert raw_compact(pkg, cgpu, PRUNE, words.size)[0] == ERR_STATE
-    after = cgpu.compact_timing()
+    assert raw_compact(pkg, own_gpu, PRUNE, words.size)[0] == ERR_STATE
+    after = own_gpu.compact_timing()
     assert len(after) == 6 and all(t >= 0 for t in after) and after[5] > 0
-    assert raw_compact(pkg, cgpu, PRUNE, words.size)[0] == ERR_STATE
-    assert after == cgpu.compact_timing()
+    assert raw_compact(pkg, own_gpu, PRUNE, words.size)[0] == ERR_STATE
+    assert after == own_gpu.compact_timing()

@@ -10,6 +10,7 @@ import pytest
 import build_ref as B
 import edit_ref as E
 from conftest import GOLDEN, assert_hits_equal, load_vox_fixture, set_uniforms_from_oracle
+from pass_frame import assert_words, own_gpu  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -20,19 +21,8 @@ ROOT = np.full(8, B.EMPTY, dtype=np.uint32)
 
 
 @pytest.fixture(scope="module")
-def egpu(pkg):
-    """a context of this module's own: the depth-21 edits raise its SVO_OPT_TREE_DEPTH"""
-    import torch
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    g = pkg.Gpu(0)
-    yield g
-    g.close()
-
-
-@pytest.fixture(scope="module")
-def render(pkg, egpu):
-    return pkg.Render(egpu, (64, 64), ROOT, capacity=CAPACITY)
+def render(pkg, own_gpu):
+    return pkg.Render(own_gpu, (64, 64), ROOT, capacity=CAPACITY)
 
 
 @pytest.fixture(scope="module")
@@ -52,12 +42,6 @@ def set_base(render, base, growth=0):
     """the base in the node buffer, with poison over the words an edit of `growth` new words may take and PAD more"""
     render.write_nodes(np.concatenate([base, poison(growth + PAD)]))
     render.node_length = base.size
-
-
-def assert_words(got, want, what):
-    assert got.size == want.size, f"{what}: {got.size} words, want {want.size}"
-    bad = np.flatnonzero(got != want)
-    assert bad.size == 0, f"{what}: {bad.size} words differ, first at {bad[:5]}: got {got[bad[:5]]} want {want[bad[:5]]}"
 
 
 def check_edit(render, base, coords, depth, colours, what, **kw):
@@ -171,18 +155,18 @@ def test_untouched_words_keep_their_counters(render, base6):
     assert kept.sum() > base.size // 2 and (want[: base.size][~kept] & 15 == 0).all()
 
 
-def test_torch_and_numpy_inputs(render, egpu, base6):
+def test_torch_and_numpy_inputs(render, own_gpu, base6):
     import torch
     coords, base = base6
     rng = np.random.default_rng(5)
     ec, ecol = edit_voxels(rng, 7, 3000, coords, 1)
     want = E.edit(base, base.size, ec, 7, ecol)
-    dev = torch.device("cuda", egpu.device)
+    dev = torch.device("cuda", own_gpu.device)
     for c, col in ((ec.astype(np.int32), ecol), (torch.from_numpy(ec).to(dev), torch.from_numpy(ecol).to(dev)),
                    (torch.from_numpy(ec).to(dev, torch.int32), torch.from_numpy(ecol & 0xFFFFFF).to(dev, torch.int32))):
         set_base(render, base)
         assert_words(render.read_nodes(render.edit_nodes(c, 7, col)), want, f"{type(c)} {c.dtype}")
-    ms = egpu.edit_timing()
+    ms = own_gpu.edit_timing()
     assert len(ms) == 6 and all(t >= 0 for t in ms) and ms[1] > 0 and ms[5] > 0
 
 
@@ -196,13 +180,13 @@ def raw_edit(pkg, gpu, xyz, depth, n_words, max_words=0, n=None):
     return rc, out.value
 
 
-def test_errors_write_nothing(pkg, render, egpu, base6):
+def test_errors_write_nothing(pkg, render, own_gpu, base6):
     import torch
     coords, base = base6
     set_base(render, base)
     before = render.read_nodes(base.size + PAD)
-    dev = torch.device("cuda", egpu.device)
-    last_error = lambda: pkg._lib.lib().svo_last_error(egpu._h).decode()  # noqa: E731
+    dev = torch.device("cuda", own_gpu.device)
+    last_error = lambda: pkg._lib.lib().svo_last_error(own_gpu._h).decode()  # noqa: E731
     t = lambda a: torch.tensor(a, dtype=torch.int32, device=dev)  # noqa: E731
 
     # depth 4 into a region the depth-6 base refines: refused, naming the voxel
@@ -211,37 +195,37 @@ def test_errors_write_nothing(pkg, render, egpu, base6):
     with pytest.raises(E.Refused) as e:
         E.edit(base, base.size, refused, 4)
     assert e.value.index == 1
-    assert raw_edit(pkg, egpu, t(refused), 4, base.size)[0] == ERR_STATE
+    assert raw_edit(pkg, own_gpu, t(refused), 4, base.size)[0] == ERR_STATE
     assert "voxel 1 " in last_error() and "interior" in last_error()
     with pytest.raises(pkg.SvoError):
         render.edit_nodes(refused, 4)
     assert render.node_length == base.size
 
     ok = t([[1, 2, 3], [63, 63, 63]])
-    assert raw_edit(pkg, egpu, t([[1, 2, 3], [64, 0, 0]]), 6, base.size)[0] == ERR_ARG
+    assert raw_edit(pkg, own_gpu, t([[1, 2, 3], [64, 0, 0]]), 6, base.size)[0] == ERR_ARG
     assert "outside" in last_error()
-    assert raw_edit(pkg, egpu, t([[1, 2, 3], [0, -1, 0]]), 6, base.size)[0] == ERR_ARG
-    assert raw_edit(pkg, egpu, ok, 0, base.size)[0] == ERR_ARG
-    assert raw_edit(pkg, egpu, ok, 22, base.size)[0] == ERR_ARG
-    assert raw_edit(pkg, egpu, ok, 6, 12)[0] == ERR_ARG
-    assert raw_edit(pkg, egpu, ok, 6, 0)[0] == ERR_ARG
-    assert raw_edit(pkg, egpu, ok, 6, CAPACITY + 8)[0] == ERR_ARG
-    assert raw_edit(pkg, egpu, None, 6, base.size, n=5)[0] == ERR_ARG
-    assert raw_edit(pkg, egpu, ok, 6, base.size, n=1 << 31)[0] == ERR_ARG
+    assert raw_edit(pkg, own_gpu, t([[1, 2, 3], [0, -1, 0]]), 6, base.size)[0] == ERR_ARG
+    assert raw_edit(pkg, own_gpu, ok, 0, base.size)[0] == ERR_ARG
+    assert raw_edit(pkg, own_gpu, ok, 22, base.size)[0] == ERR_ARG
+    assert raw_edit(pkg, own_gpu, ok, 6, 12)[0] == ERR_ARG
+    assert raw_edit(pkg, own_gpu, ok, 6, 0)[0] == ERR_ARG
+    assert raw_edit(pkg, own_gpu, ok, 6, CAPACITY + 8)[0] == ERR_ARG
+    assert raw_edit(pkg, own_gpu, None, 6, base.size, n=5)[0] == ERR_ARG
+    assert raw_edit(pkg, own_gpu, ok, 6, base.size, n=1 << 31)[0] == ERR_ARG
     # the cap: one group short fails, exactly reached succeeds (below)
     grow = np.array([[63, 63, 63], [62, 1, 60]])
     want = E.edit(base, base.size, grow, 6)
     assert want.size >= base.size + 16
-    assert raw_edit(pkg, egpu, t(grow), 6, base.size, max_words=want.size - 8)[0] == ERR_CAP
+    assert raw_edit(pkg, own_gpu, t(grow), 6, base.size, max_words=want.size - 8)[0] == ERR_CAP
     assert str(want.size) in last_error()
     with pytest.raises(pkg.SvoError):
         render.edit_nodes(grow, 6, max_words=want.size - 8)
-    assert raw_edit(pkg, egpu, ok[:0], 6, base.size) == (0, base.size)  # nothing to edit
+    assert raw_edit(pkg, own_gpu, ok[:0], 6, base.size) == (0, base.size)  # nothing to edit
     assert render.edit_nodes(np.zeros((0, 3), dtype=np.int64), 6) == base.size
     assert render.node_length == base.size
     assert np.array_equal(render.read_nodes(base.size + PAD), before)
 
-    assert raw_edit(pkg, egpu, t(grow), 6, base.size, max_words=want.size) == (0, want.size)
+    assert raw_edit(pkg, own_gpu, t(grow), 6, base.size, max_words=want.size) == (0, want.size)
     assert_words(render.read_nodes(want.size), want, "the cap exactly reached")
     fresh = pkg.Gpu(0)
     try:
@@ -250,7 +234,7 @@ def test_errors_write_nothing(pkg, render, egpu, base6):
         fresh.close()
 
 
-def test_timing_keeps_the_last_edit_that_ran(pkg, render, egpu, base6):
+def test_timing_keeps_the_last_edit_that_ran(pkg, render, own_gpu, base6):
     import torch
     coords, base = base6
     rng = np.random.default_rng(77)
@@ -260,13 +244,13 @@ def test_timing_keeps_the_last_edit_that_ran(pkg, render, egpu, base6):
     # a refused call records the front end's events again: the accepted edit's times are taken before it does
     set_base(render, base)
     refused = torch.tensor(np.array([[15, 15, 15], coords[7] >> 2, [0, 15, 0]]), dtype=torch.int32,
-                           device=torch.device("cuda", egpu.device))
-    assert raw_edit(pkg, egpu, refused, 4, base.size)[0] == ERR_STATE
-    ms = egpu.edit_timing()
+                           device=torch.device("cuda", own_gpu.device))
+    assert raw_edit(pkg, own_gpu, refused, 4, base.size)[0] == ERR_STATE
+    ms = own_gpu.edit_timing()
     assert len(ms) == 6 and all(t >= 0 for t in ms) and ms[1] > 0 and ms[5] > 0
-    assert ms == egpu.edit_timing()
-    assert raw_edit(pkg, egpu, refused, 4, base.size)[0] == ERR_STATE
-    assert ms == egpu.edit_timing()
+    assert ms == own_gpu.edit_timing()
+    assert raw_edit(pkg, own_gpu, refused, 4, base.size)[0] == ERR_STATE
+    assert ms == own_gpu.edit_timing()
 
 
 def frame(pkg, r, u):

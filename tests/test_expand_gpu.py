@@ -5,25 +5,13 @@ import os
 import numpy as np
 import pytest
 
-from conftest import GOLDEN, assert_hits_equal, load_vox_fixture, set_uniforms_from_oracle
+from conftest import GOLDEN, assert_hits_equal, set_uniforms_from_oracle
+from pass_frame import assert_octrees_equal, monu9_world, write_blocks
 
 pytestmark = pytest.mark.gpu
 
 VOXEL_OFFSET = 1 << 27
-BLOCKS = ("stone", "dirt", "grass", "wood", "leaf", "slate", "crystal", "glass")
 SIZE = (96, 64)
-
-
-def assert_octrees_equal(a, b, what=""):
-    assert len(a) == len(b), f"{what}: lengths {len(a)} != {len(b)}"
-    assert np.array_equal(a.raw_data(), b.raw_data()), f"{what}: words differ"
-    assert np.array_equal(a.positions().view(np.uint32), b.positions().view(np.uint32)), f"{what}: positions differ"
-    assert np.array_equal(a.hole_stack(), b.hole_stack()), f"{what}: hole stacks differ"
-
-
-def monu9_world(pkg):
-    size, xyzi, pal, _, _ = load_vox_fixture("monu9")
-    return pkg.adaptive.World(pkg.CpuOctree.from_voxels(size, xyzi, pal))
 
 
 def attach(pkg, world, octree, capacity):
@@ -84,14 +72,6 @@ def test_cap_is_the_capacity(pkg, gpu, max_words):
     """No max_words, or one above the capacity: the node buffer's capacity is where expansion stops, without an error."""
     counts, _, oa = check_expand(pkg, lambda: monu9_world(pkg), 6, max_words=max_words, capacity=4001)
     assert len(oa) == 4000 and counts[0] == 499
-
-
-def write_blocks(pkg, d):
-    z = np.load(os.path.join(GOLDEN, "blocks_vox.npz"))
-    os.makedirs(d)
-    for name in BLOCKS:
-        with open(os.path.join(d, name + ".vox"), "wb") as f:
-            f.write(pkg.cpu_octree.vox_write(16, z[name + "_xyzi"], z[name + "_palette"]))
 
 
 def test_streamed_world_loads_chunks(pkg, gpu, tmp_path):

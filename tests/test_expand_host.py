@@ -8,7 +8,8 @@ import re
 import numpy as np
 import pytest
 
-from conftest import ROOT, load_vox_fixture
+from conftest import ROOT
+from pass_frame import monu9_world
 
 VOXEL_OFFSET = 1 << 27
 
@@ -21,11 +22,6 @@ CASES = [
     (6, None, 0.0, 4001),   # the cap cuts a level
     (7, (0.1, 0.2, -1.5), 12.0, 300),
 ]
-
-
-def monu9_world(pkg):
-    size, xyzi, pal, _, _ = load_vox_fixture("monu9")
-    return pkg.adaptive.World(pkg.CpuOctree.from_voxels(size, xyzi, pal))
 
 
 def refines(pos, depth, cam, lod_c):

@@ -10,66 +10,40 @@ import numpy as np
 import pytest
 
 import build_ref as B
-import edit_ref as E
 import list_ref as L
+from pass_frame import SLACK, SentinelOut, last_error, monu9_world, own_gpu, tree7_base  # noqa: F401
 from test_compact_host import malformed_cases, orphaned, survivors
-from test_edit_gpu import CAPACITY, PAD, ROOT, edit_voxels, frame, poison, set_base
-from test_expand_gpu import monu9_world
+from test_edit_gpu import CAPACITY, PAD, ROOT, frame, poison, set_base
 from test_list_host import full_root, mixed_levels, one_leaf_root, voxel_list
 
 pytestmark = pytest.mark.gpu
 
 ERR_ARG, ERR_STATE, ERR_CAP = -1, -3, -6
 EXPAND = 1
-SENTINEL = 0x5EA70000  # what the outputs hold where nothing was written
-SLACK = 64             # entries behind the list that must keep the sentinel
 
 
 @pytest.fixture(scope="module")
-def lgpu(pkg):
-    """a context of this module's own: the depth-21 tree raises its SVO_OPT_TREE_DEPTH"""
-    import torch
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    g = pkg.Gpu(0)
-    yield g
-    g.close()
-
-
-@pytest.fixture(scope="module")
-def render(pkg, lgpu):
-    return pkg.Render(lgpu, (64, 64), ROOT, capacity=CAPACITY)
+def render(pkg, own_gpu):
+    return pkg.Render(own_gpu, (64, 64), ROOT, capacity=CAPACITY)
 
 
 @pytest.fixture(scope="module")
 def tree7():
-    """test_compact_gpu's tree7: 10 000 random voxels at depth 7 edited with 4 097 voxels of which a fifth are removed;
-    the base, the edited words in put order, both lists' references and the surviving voxels, computed once"""
-    rng = np.random.default_rng(70)
-    a = rng.integers(0, 128, (10000, 3)), rng.integers(1, 1 << 24, 10000)
-    b = edit_voxels(rng, 7, 4097, a[0], 0)
-    base = B.build(a[0], 7, a[1])
-    words = E.edit(base, base.size, b[0], 7, b[1])
-    return {"a": a, "b": b, "base": base, "words": words, "base list": L.list_voxels(base, base.size, 7),
-            "list": L.list_voxels(words, words.size, 7), "left": survivors(7, a, b)}
+    """pass_frame.tree7_base (the base, the edited words in put order) with both lists' references and the surviving
+    voxels, computed once"""
+    t = tree7_base()
+    base, words = t["base"], t["words"]
+    return {**t, "base list": L.list_voxels(base, base.size, 7), "list": L.list_voxels(words, words.size, 7),
+            "left": survivors(7, t["a"], t["b"])}
 
 
-class Out:
+class Out(SentinelOut):
     """sentinel-filled device outputs of `room` entries"""
 
     def __init__(self, gpu, room, levels=True):
-        import torch
-        dev = torch.device("cuda", gpu.device)
-        full = lambda *shape: torch.full(shape, SENTINEL, dtype=torch.int32, device=dev)  # noqa: E731
-        self.xyz, self.value, self.level = full(room, 3), full(room), full(room) if levels else None
+        super().__init__(gpu, [(room, 3), room, room if levels else None])
+        self.xyz, self.value, self.level = self.t
         self.room = room
-        torch.cuda.current_stream(dev).synchronize()
-
-    def host(self):
-        return tuple(t.cpu().numpy().view(np.uint32) for t in (self.xyz, self.value, self.level) if t is not None)
-
-    def untouched_from(self, n):
-        return all((a[n:] == SENTINEL).all() for a in self.host())
 
 
 def raw_list(pkg, gpu, flags, depth, n_words, out=None, max_voxels=None, params=True, n_out=True, value=True):
@@ -83,10 +57,6 @@ def raw_list(pkg, gpu, flags, depth, n_words, out=None, max_voxels=None, params=
         out.level.data_ptr() if out is not None and out.level is not None else None, C.byref(n) if n_out else None)
     gpu.sync()
     return rc, n.value
-
-
-def last_error(pkg, gpu):
-    return pkg._lib.lib().svo_last_error(gpu._h).decode()
 
 
 def check_list(pkg, render, words, depth, expand, what, want=None, loaded=False):
@@ -183,7 +153,7 @@ def value_image(hits, words):
     return np.where(v < words.size, (words[np.minimum(v, words.size - 1)] >> 4).astype(np.int64), v + (1 << 32))
 
 
-def test_mixed_levels_native_and_expanded(pkg, render, lgpu, O):
+def test_mixed_levels_native_and_expanded(pkg, render, own_gpu, O):
     mixed = mixed_levels()
     native = check_list(pkg, render, mixed, 6, False, "mixed levels")
     assert set(native[2].tolist()) == {2, 3, 4, 5, 6}
@@ -213,14 +183,14 @@ def test_mixed_levels_native_and_expanded(pkg, render, lgpu, O):
     assert np.array_equal(render.read_nodes(8), one)
 
 
-def test_errors_write_nothing(pkg, render, lgpu, tree7):
+def test_errors_write_nothing(pkg, render, own_gpu, tree7):
     base = tree7["base"]
     set_base(render, base)
     before = render.read_nodes(base.size + PAD)
     count = tree7["base list"][1].size
-    out = Out(lgpu, count + SLACK)
-    refused = lambda code, part, *a, **kw: (raw_list(pkg, lgpu, *a, **kw) == (code, 12345)  # noqa: E731
-                                            and part in last_error(pkg, lgpu))
+    out = Out(own_gpu, count + SLACK)
+    refused = lambda code, part, *a, **kw: (raw_list(pkg, own_gpu, *a, **kw) == (code, 12345)  # noqa: E731
+                                            and part in last_error(pkg, own_gpu))
     assert refused(ERR_ARG, "null", 0, 7, base.size, out, params=False)
     assert refused(ERR_ARG, "null", 0, 7, base.size, out, n_out=False)
     assert refused(ERR_ARG, "flag", 2, 7, base.size, out)
@@ -238,14 +208,14 @@ def test_errors_write_nothing(pkg, render, lgpu, tree7):
         render.list_voxels(3)
     # room for one entry less than there are; a count query does not look at max_voxels
     assert refused(ERR_CAP, f"{count} entries", 0, 7, base.size, out, max_voxels=count - 1)
-    assert raw_list(pkg, lgpu, 0, 7, base.size, max_voxels=0) == (0, count)
+    assert raw_list(pkg, own_gpu, 0, 7, base.size, max_voxels=0) == (0, count)
     assert out.untouched_from(0)
     assert np.array_equal(render.read_nodes(base.size + PAD), before)
     # a level-1 voxel expanded at depth 21: 8^20 cells, counted in 64 bits
     set_base(render, one_leaf_root())
     assert refused(ERR_CAP, f"{8 ** 20} entries", EXPAND, 21, 8, out)
     assert refused(ERR_CAP, f"{8 ** 20} entries", EXPAND, 21, 8)
-    assert raw_list(pkg, lgpu, 0, 21, 8) == (0, 1)
+    assert raw_list(pkg, own_gpu, 0, 21, 8) == (0, 1)
     assert refused(ERR_CAP, f"{8 ** 11} entries", EXPAND, 12, 8)  # 2^33: the low 32 bits are 0
 
     causes = {"a pointer with pointer + 8 > n_words": "leaves the first n_words", "an unaligned pointer": "not a multiple of 8",
@@ -257,8 +227,8 @@ def test_errors_write_nothing(pkg, render, lgpu, tree7):
         before = render.read_nodes(words.size + PAD)
         for flags in (0, EXPAND):
             for o in (out, None):
-                assert raw_list(pkg, lgpu, flags, 21, words.size, o) == (ERR_STATE, 12345), name
-                assert "malformed tree: " in last_error(pkg, lgpu) and causes[name] in last_error(pkg, lgpu), f"{name}: {last_error(pkg, lgpu)}"
+                assert raw_list(pkg, own_gpu, flags, 21, words.size, o) == (ERR_STATE, 12345), name
+                assert "malformed tree: " in last_error(pkg, own_gpu) and causes[name] in last_error(pkg, own_gpu), f"{name}: {last_error(pkg, own_gpu)}"
         with pytest.raises(pkg.SvoError):
             render.list_voxels(21)
         assert np.array_equal(render.read_nodes(words.size + PAD), before), name
@@ -271,22 +241,22 @@ def test_errors_write_nothing(pkg, render, lgpu, tree7):
         fresh.close()
 
 
-def test_timing(pkg, render, lgpu, tree7):
+def test_timing(pkg, render, own_gpu, tree7):
     set_base(render, tree7["base"])
     render.list_voxels(7)
-    ms = lgpu.list_timing()
+    ms = own_gpu.list_timing()
     assert len(ms) == 5 and all(t >= 0 for t in ms) and ms[4] > 0
-    assert ms == lgpu.list_timing()
-    assert raw_list(pkg, lgpu, 0, 3, tree7["base"].size)[0] == ERR_ARG  # a refused call leaves the times
-    assert ms == lgpu.list_timing()
+    assert ms == own_gpu.list_timing()
+    assert raw_list(pkg, own_gpu, 0, 3, tree7["base"].size)[0] == ERR_ARG  # a refused call leaves the times
+    assert ms == own_gpu.list_timing()
 
 
-def test_an_edit_through_a_sharing_context_is_seen(pkg, render, lgpu, tree7):
+def test_an_edit_through_a_sharing_context_is_seen(pkg, render, own_gpu, tree7):
     g2 = pkg.Gpu(0)
     try:
         base = tree7["base"]
         set_base(render, base, 8 * 4097 * 7)
-        lgpu.sync()
+        own_gpu.sync()
         r2 = pkg.Render.share_nodes(g2, render)
         b = tree7["b"]
         import torch
@@ -330,14 +300,14 @@ def test_a_device_adaptive_state_is_no_obstacle(pkg):
         g.close()
 
 
-def test_save_nodes_equals_build_world_of_the_surviving_voxels(pkg, render, lgpu, tree7, tmp_path):
+def test_save_nodes_equals_build_world_of_the_surviving_voxels(pkg, render, own_gpu, tree7, tmp_path):
     set_base(render, tree7["words"])
     before = render.read_nodes(tree7["words"].size + PAD)
     saved, built = str(tmp_path / "saved"), str(tmp_path / "built")
     world = pkg.World.save_nodes(saved, render, 7, world_depth=1)
     assert world.chunk_ids()
     coords, colours = tree7["left"]
-    pkg.World.build_world(built, lgpu, coords, 7, colours, world_depth=1)
+    pkg.World.build_world(built, own_gpu, coords, 7, colours, world_depth=1)
     files = sorted(os.listdir(built))
     assert files == sorted(os.listdir(saved)) and "0.bin" in files and len(files) > 1
     for name in files:

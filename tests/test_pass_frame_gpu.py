@@ -1,7 +1,9 @@
 """The host frame the GPU tree passes share (csrc/svo_ctx.h): one context runs every pass that keeps a
 workspace, hands out each pass's times and is closed, which is where all of its owning members are released together;
 a second context then builds the same tree.  Likewise the context's own members: its scratch grows, is reused and goes
-with it, and a shared node store goes with the last context that holds it, whichever that is."""
+with it, and a shared node store goes with the last context that holds it, whichever that is.  And the frame above the C
+ABI (octree-tracer_amd/_device.py): the declared depth is the context's and no Render lowers it; a voxel
+list builds the same tree whichever way it comes in."""
 import numpy as np
 import pytest
 
@@ -222,3 +224,74 @@ def test_shared_node_store_outlives_its_contexts_in_either_order(pkg, O, small_w
     finally:
         for g in opened:
             g.close()
+
+
+DEEP = B.build([[0, 0, 0]], 20)  # one voxel at depth 20: 160 words
+
+
+def _deep_frame(pkg, gpu, render, octree_depth):
+    """update() with Settings.octree_depth, then one 8x8 frame from 1e-5 inside the cube's low corner, looking at the
+    voxel there (the oracle finds it with two of these rays): they go down all 20 levels, which svo_sync refuses under a
+    lower SVO_OPT_TREE_DEPTH.  Returns the records."""
+    render.set_flags(pause_adaptive=True, shadows=False)
+    render.update(pkg.Settings(octree_depth=octree_depth), pkg.Character(pos=(-0.99999,) * 3, look=(-1.0, -1.0, -1.0)))
+    hits = render.render()
+    gpu.sync()
+    got = pkg.render.hits_to_numpy(hits)
+    assert (got["info"] >> 16 & 1).any(), "no ray of the frame hit the depth-20 voxel: the frame does not test the depth"
+    return got
+
+
+def test_a_render_does_not_lower_the_depth_its_gpu_holds(pkg):
+    import torch
+    if not torch.cuda.is_available():
+        pytest.skip("no GPU")
+    gpu = pkg.Gpu(0)
+    try:
+        assert gpu.tree_depth == 16
+        gpu.set_option(pkg.gpu.OPT_TREE_DEPTH, 20)
+        render = pkg.Render(gpu, (8, 8), DEEP, capacity=1024)
+        assert DEEP.size == 160 and gpu.tree_depth == 20
+        _deep_frame(pkg, gpu, render, 18)
+        assert gpu.tree_depth == 20
+        _deep_frame(pkg, gpu, render, 21)  # (raising is still the wrapper's to do)
+        assert gpu.tree_depth == 21
+    finally:
+        gpu.close()
+
+
+def test_a_second_render_on_the_gpu_does_not_lower_it_either(pkg):
+    import torch
+    if not torch.cuda.is_available():
+        pytest.skip("no GPU")
+    gpu = pkg.Gpu(0)
+    try:
+        first = pkg.Render(gpu, (8, 8), ROOT, capacity=1024)
+        assert first.build_nodes([[0, 0, 0]], 20) == DEEP.size and gpu.tree_depth == 20
+        second = pkg.Render(gpu, (8, 8), DEEP, capacity=1024)
+        _deep_frame(pkg, gpu, second, 17)
+        assert gpu.tree_depth == 20
+    finally:
+        gpu.close()
+
+
+def test_a_voxel_list_builds_the_same_tree_however_it_comes_in(pkg):
+    import torch
+    if not torch.cuda.is_available():
+        pytest.skip("no GPU")
+    rng = np.random.default_rng(21)
+    coords, colours = rng.integers(0, 32, (64, 3)), rng.integers(1, 1 << 24, 64)
+    want = B.build(coords, 5, colours)
+    gpu = pkg.Gpu(0)
+    try:
+        render = pkg.Render(gpu, (8, 8), ROOT, capacity=4096)
+        forms = {"numpy int64": (coords.astype(np.int64), colours.astype(np.int64)),
+                 "torch int32 on the device": (torch.as_tensor(coords, dtype=torch.int32, device=gpu.torch_device),
+                                               torch.as_tensor(colours, dtype=torch.int32, device=gpu.torch_device)),
+                 "torch int64 on the CPU": (torch.as_tensor(coords, dtype=torch.int64), torch.as_tensor(colours, dtype=torch.int64))}
+        for what, (xyz, col) in forms.items():
+            render.write_nodes(ROOT)
+            assert render.build_nodes(xyz, 5, col) == want.size, what
+            assert render.read_nodes(want.size).tobytes() == want.tobytes(), what
+    finally:
+        gpu.close()

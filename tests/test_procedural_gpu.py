@@ -7,13 +7,13 @@ import numpy as np
 import pytest
 
 import proc_ref as R
-from conftest import GOLDEN, assert_hits_equal, set_uniforms_from_oracle
+from conftest import assert_hits_equal, set_uniforms_from_oracle
+from pass_frame import write_blocks
 
 pytestmark = pytest.mark.gpu
 
 F = np.float32
 CO = R.CHUNK_OFFSET
-BLOCKS = ("stone", "dirt", "grass", "wood", "leaf", "slate", "crystal", "glass")
 CHUNKS_1 = [pos for _, _, pos in R.chunk_layout(1)]  # the 8 chunks of a world_depth 1 world
 
 
@@ -149,14 +149,6 @@ def test_node_cap_is_an_error_and_the_context_stays_usable(pkg, O, gpu, proc):
     got = pkg.render.hits_to_numpy(render.render())
     gpu.sync()
     assert_hits_equal(got, O.trace_frame(words, u, threads=4), "frame after a refused chunk")
-
-
-def write_blocks(pkg, d):
-    z = np.load(os.path.join(GOLDEN, "blocks_vox.npz"))
-    os.makedirs(d)
-    for name in BLOCKS:
-        with open(os.path.join(d, name + ".vox"), "wb") as f:
-            f.write(pkg.cpu_octree.vox_write(16, z[name + "_xyzi"], z[name + "_palette"]))
 
 
 def test_generate_world_end_to_end(pkg, O, gpu, proc, ref_cls6, tmp_path):

@@ -15,51 +15,32 @@ import numpy as np
 import pytest
 
 import build_ref as B
-import edit_ref as E
 import list_ref as L
 import sample_ref as S
+from pass_frame import SLACK, SentinelOut, last_error, monu9_world, own_gpu, tree7_base  # noqa: F401
 from test_compact_host import malformed_cases
-from test_edit_gpu import CAPACITY, PAD, ROOT, edit_voxels, poison, set_base
-from test_expand_gpu import monu9_world
+from test_edit_gpu import CAPACITY, PAD, ROOT, poison, set_base
 from test_list_host import full_root, mixed_levels, one_leaf_root
 from test_sample_host import BOXES, DEEP_CELL, deep_cells
 
 pytestmark = pytest.mark.gpu
 
 ERR_ARG, ERR_STATE = -1, -3
-SENTINEL = 0x5EA70000  # what the outputs hold where nothing was written
-SLACK = 64             # entries behind the outputs that must keep the sentinel
 WHOLE7 = ((0, 0, 0), (128, 128, 128))
 
 
 @pytest.fixture(scope="module")
-def sgpu(pkg):
-    """a context of this module's own: the depth-21 tree raises its SVO_OPT_TREE_DEPTH"""
-    import torch
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    g = pkg.Gpu(0)
-    yield g
-    g.close()
-
-
-@pytest.fixture(scope="module")
-def render(pkg, sgpu):
-    return pkg.Render(sgpu, (64, 64), ROOT, capacity=CAPACITY)
+def render(pkg, own_gpu):
+    return pkg.Render(own_gpu, (64, 64), ROOT, capacity=CAPACITY)
 
 
 @pytest.fixture(scope="module")
 def tree7():
-    """test_list_gpu's tree7, recomputed: 10 000 random voxels at depth 7 edited with 4 097 voxels of which a fifth are
-    removed; the base, the edited words in put order, their list, and the rule over every cell of the 128^3 grid"""
-    rng = np.random.default_rng(70)
-    a = rng.integers(0, 128, (10000, 3)), rng.integers(1, 1 << 24, 10000)
-    b = edit_voxels(rng, 7, 4097, a[0], 0)
-    base = B.build(a[0], 7, a[1])
-    words = E.edit(base, base.size, b[0], 7, b[1])
-    cells = S.box_cells(*WHOLE7)
-    return {"a": a, "b": b, "base": base, "words": words, "list": L.list_voxels(words, words.size, 7), "cells": cells,
-            "whole": S.sample(words, words.size, cells, 7)}
+    """pass_frame.tree7_base (the base, the edited words in put order) with the words' list and the rule over every cell
+    of the 128^3 grid, computed once"""
+    t = tree7_base()
+    words, cells = t["words"], S.box_cells(*WHOLE7)
+    return {**t, "list": L.list_voxels(words, words.size, 7), "cells": cells, "whole": S.sample(words, words.size, cells, 7)}
 
 
 def device_cells(gpu, cells):
@@ -71,24 +52,15 @@ def device_cells(gpu, cells):
     return t
 
 
-class Out:
-    """sentinel-filled device outputs of `n` entries and SLACK more"""
+class Out(SentinelOut):
+    """`arrays` sentinel-filled device outputs of `n` entries and SLACK more"""
 
     def __init__(self, gpu, n, arrays=3):
-        import torch
-        dev = torch.device("cuda", gpu.device)
+        super().__init__(gpu, [n + SLACK] * arrays)
         self.n = n
-        self.t = [torch.full((n + SLACK,), SENTINEL, dtype=torch.int32, device=dev) for _ in range(arrays)]
-        torch.cuda.current_stream(dev).synchronize()
 
     def ptr(self, k):
         return self.t[k].data_ptr() if k < len(self.t) else None
-
-    def host(self):
-        return [t.cpu().numpy().view(np.uint32) for t in self.t]
-
-    def untouched_from(self, n):
-        return all((a[n:] == SENTINEL).all() for a in self.host())
 
 
 def raw_sample(pkg, gpu, depth, n_words, xyz, n, out, flags=0, params=True, give_xyz=True, give_value=True):
@@ -107,10 +79,6 @@ def raw_dense(pkg, gpu, depth, n_words, origin, size, out, flags=0, params=True,
                                                (C.c_uint32 * 3)(*size) if give_size else None, out.ptr(0) if give_grid else None)
     gpu.sync()
     return rc
-
-
-def last_error(pkg, gpu):
-    return pkg._lib.lib().svo_last_error(gpu._h).decode()
 
 
 def assert_same(got, want, what, name):
@@ -335,48 +303,48 @@ def test_malformed_trees(pkg, render):
     assert broken == 2  # the two pointer cases
 
 
-def test_errors_enqueue_nothing(pkg, render, sgpu, tree7):
+def test_errors_enqueue_nothing(pkg, render, own_gpu, tree7):
     base = tree7["base"]
     set_base(render, base)
     before = render.read_nodes(base.size + PAD)
     n = 100
-    xyz = device_cells(sgpu, tree7["cells"][:n])
-    out = Out(sgpu, n)
+    xyz = device_cells(own_gpu, tree7["cells"][:n])
+    out = Out(own_gpu, n)
     size = base.size
 
     def refused(gpu, code, part, rc):
         return rc == code and part in last_error(pkg, gpu)
 
-    pts = lambda *a, **kw: raw_sample(pkg, sgpu, *a, **kw)  # noqa: E731
-    box = lambda *a, **kw: raw_dense(pkg, sgpu, *a, **kw)  # noqa: E731
+    pts = lambda *a, **kw: raw_sample(pkg, own_gpu, *a, **kw)  # noqa: E731
+    box = lambda *a, **kw: raw_dense(pkg, own_gpu, *a, **kw)  # noqa: E731
     o, s = (1, 2, 3), (4, 5, 5)
     # 1. null params (before everything else that is wrong)
-    assert refused(sgpu, ERR_ARG, "null params", pts(0, 12, xyz, n, out, flags=1, params=False, give_xyz=False))
-    assert refused(sgpu, ERR_ARG, "null params", box(0, 12, o, s, out, flags=1, params=False, give_grid=False))
+    assert refused(own_gpu, ERR_ARG, "null params", pts(0, 12, xyz, n, out, flags=1, params=False, give_xyz=False))
+    assert refused(own_gpu, ERR_ARG, "null params", box(0, 12, o, s, out, flags=1, params=False, give_grid=False))
     # 2. flags (before the depth)
     for flags in (1, 1 << 31):
-        assert refused(sgpu, ERR_ARG, "flag", pts(0, size, xyz, n, out, flags=flags))
-        assert refused(sgpu, ERR_ARG, "flag", box(22, size, o, s, out, flags=flags))
+        assert refused(own_gpu, ERR_ARG, "flag", pts(0, size, xyz, n, out, flags=flags))
+        assert refused(own_gpu, ERR_ARG, "flag", box(22, size, o, s, out, flags=flags))
     # 3. depth (before the arguments)
     for depth in (0, 22):
-        assert refused(sgpu, ERR_ARG, "depth", pts(depth, size, xyz, n, out, give_xyz=False))
-        assert refused(sgpu, ERR_ARG, "depth", box(depth, size, o, s, out, give_origin=False))
+        assert refused(own_gpu, ERR_ARG, "depth", pts(depth, size, xyz, n, out, give_xyz=False))
+        assert refused(own_gpu, ERR_ARG, "depth", box(depth, size, o, s, out, give_origin=False))
     # 4. the arguments (before the tree)
-    assert refused(sgpu, ERR_ARG, "xyz_dev", pts(7, 12, xyz, n, out, give_xyz=False))
-    assert refused(sgpu, ERR_ARG, "value_out_dev", pts(7, 12, xyz, n, out, give_value=False))
-    assert refused(sgpu, ERR_ARG, "2^31", pts(7, 12, xyz, 1 << 31, out))
-    assert refused(sgpu, ERR_ARG, "2^31", pts(7, size, xyz, (1 << 40) + 5, out))
-    assert refused(sgpu, ERR_ARG, "origin", box(7, 12, o, s, out, give_origin=False))
-    assert refused(sgpu, ERR_ARG, "size", box(7, 12, o, s, out, give_size=False))
-    assert refused(sgpu, ERR_ARG, "grid_out_dev", box(7, 12, o, s, out, give_grid=False))
+    assert refused(own_gpu, ERR_ARG, "xyz_dev", pts(7, 12, xyz, n, out, give_xyz=False))
+    assert refused(own_gpu, ERR_ARG, "value_out_dev", pts(7, 12, xyz, n, out, give_value=False))
+    assert refused(own_gpu, ERR_ARG, "2^31", pts(7, 12, xyz, 1 << 31, out))
+    assert refused(own_gpu, ERR_ARG, "2^31", pts(7, size, xyz, (1 << 40) + 5, out))
+    assert refused(own_gpu, ERR_ARG, "origin", box(7, 12, o, s, out, give_origin=False))
+    assert refused(own_gpu, ERR_ARG, "size", box(7, 12, o, s, out, give_size=False))
+    assert refused(own_gpu, ERR_ARG, "grid_out_dev", box(7, 12, o, s, out, give_grid=False))
     for origin, sz in (((120, 0, 0), (9, 1, 1)), ((0, 128, 0), (1, 1, 1)), ((0, 0, 0xFFFFFFFF), (1, 1, 2)), ((0, 0, 0), (1, 129, 1))):
-        assert refused(sgpu, ERR_ARG, "leaves the grid", box(7, 12, origin, sz, out))
-    assert refused(sgpu, ERR_ARG, "2^31 or more", box(21, 12, (0, 0, 0), (2048, 1024, 1024), out))
+        assert refused(own_gpu, ERR_ARG, "leaves the grid", box(7, 12, origin, sz, out))
+    assert refused(own_gpu, ERR_ARG, "2^31 or more", box(21, 12, (0, 0, 0), (2048, 1024, 1024), out))
     # 6. n_words
     for bad in (0, 12, size + 4, CAPACITY + 8):
-        assert refused(sgpu, ERR_ARG, "n_words", pts(7, bad, xyz, n, out))
-        assert refused(sgpu, ERR_ARG, "n_words", box(7, bad, o, s, out))
-        assert refused(sgpu, ERR_ARG, "n_words", pts(7, bad, xyz, 0, out))  # (also with nothing to do)
+        assert refused(own_gpu, ERR_ARG, "n_words", pts(7, bad, xyz, n, out))
+        assert refused(own_gpu, ERR_ARG, "n_words", box(7, bad, o, s, out))
+        assert refused(own_gpu, ERR_ARG, "n_words", pts(7, bad, xyz, 0, out))  # (also with nothing to do)
     with pytest.raises(pkg.SvoError):
         render.sample_dense((120, 0, 0), (9, 1, 1), 7)
     with pytest.raises(pkg.SvoError):
@@ -399,13 +367,13 @@ def test_errors_enqueue_nothing(pkg, render, sgpu, tree7):
     assert out.untouched_from(0)
 
 
-def test_an_edit_through_a_sharing_context_is_seen(pkg, render, sgpu, tree7):
+def test_an_edit_through_a_sharing_context_is_seen(pkg, render, own_gpu, tree7):
     import torch
     g2 = pkg.Gpu(0)
     try:
         base = tree7["base"]
         set_base(render, base, 8 * 4097 * 7)
-        sgpu.sync()
+        own_gpu.sync()
         r2 = pkg.Render.share_nodes(g2, render)
         b = tree7["b"]
         dev = torch.device("cuda", 0)

@@ -12,44 +12,23 @@ import pytest
 import build_ref as B
 import edit_ref as E
 import voxelize_ref as V
+from pass_frame import SENTINEL, SLACK, SentinelOut, last_error, own_gpu  # noqa: F401
 from test_edit_gpu import CAPACITY, PAD, ROOT, poison, set_base
 from test_voxelize_host import planar_quad, random_mesh
 
 pytestmark = pytest.mark.gpu
 
 ERR_ARG, ERR_STATE, ERR_CAP = -1, -3, -6
-SENTINEL = 0x5EA70000  # what the outputs hold where nothing was written
-SLACK = 64             # entries behind the list that must keep the sentinel
 TOP21 = 1 << 27        # quantised coordinates of depth 21 lie below this
 
 
-@pytest.fixture(scope="module")
-def vgpu(pkg):
-    """a context of this module's own"""
-    import torch
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    g = pkg.Gpu(0)
-    yield g
-    g.close()
-
-
-class Out:
+class Out(SentinelOut):
     """sentinel-filled device outputs of `room` entries"""
 
     def __init__(self, gpu, room):
-        import torch
-        dev = torch.device("cuda", gpu.device)
-        full = lambda *shape: torch.full(shape, SENTINEL, dtype=torch.int32, device=dev)  # noqa: E731
-        self.xyz, self.colour, self.tri = full(room, 3), full(room), full(room)
+        super().__init__(gpu, [(room, 3), room, room])
+        self.xyz, self.colour, self.tri = self.t
         self.room = room
-        torch.cuda.current_stream(dev).synchronize()
-
-    def host(self):
-        return tuple(t.cpu().numpy().view(np.uint32) for t in (self.xyz, self.colour, self.tri))
-
-    def untouched_from(self, n):
-        return all((a[n:] == SENTINEL).all() for a in self.host())
 
 
 class Mesh:
@@ -80,10 +59,6 @@ def raw_voxelize(pkg, gpu, mesh, depth, out=None, max_voxels=None, params=True, 
     return rc, n.value
 
 
-def last_error(pkg, gpu):
-    return pkg._lib.lib().svo_last_error(gpu._h).decode()
-
-
 def check_mesh(pkg, gpu, vq, tris, depth, colours, what, want=None, colour=0xFFFFFF):
     """the mesh's list on the GPU == the reference; the count query agrees and writes nothing; nothing is written behind
     n.  Returns the list's three host arrays."""
@@ -105,27 +80,27 @@ def check_mesh(pkg, gpu, vq, tris, depth, colours, what, want=None, colour=0xFFF
     return tuple(g[:n] for g in got)
 
 
-def test_depth_1_single_triangles(pkg, vgpu):
+def test_depth_1_single_triangles(pkg, own_gpu):
     cases = {"inside an octant": ([[70, 70, 70], [100, 80, 75], [80, 110, 90]], 1),
              # the edge from (0, 1, 2) to (127, 126, 125) passes through the grid's centre, a point of all eight closed cubes
              "through all eight octants": ([[0, 1, 2], [127, 126, 125], [100, 5, 60]], 8),
              "a point": ([[5, 5, 5]] * 3, 1),
              "a segment": ([[5, 5, 5], [120, 5, 5], [120, 5, 5]], 2)}
     for name, (vq, cells) in cases.items():
-        xyz, colour, tri = check_mesh(pkg, vgpu, vq, [[0, 1, 2]], 1, None, name, colour=0x123456)
+        xyz, colour, tri = check_mesh(pkg, own_gpu, vq, [[0, 1, 2]], 1, None, name, colour=0x123456)
         assert len(xyz) == cells and (colour == 0x123456).all() and (tri == 0).all(), name
-    xyz, _, tri = check_mesh(pkg, vgpu, sum((c[0] for c in cases.values()), []), np.arange(12).reshape(4, 3), 1, [1, 2, 3, 4], "all four")
+    xyz, _, tri = check_mesh(pkg, own_gpu, sum((c[0] for c in cases.values()), []), np.arange(12).reshape(4, 3), 1, [1, 2, 3, 4], "all four")
     assert np.bincount(tri).tolist() == [1, 8, 1, 2]
 
 
 @pytest.mark.parametrize("depth", [2, 3])
-def test_random_and_degenerate_triangles(pkg, vgpu, depth):
+def test_random_and_degenerate_triangles(pkg, own_gpu, depth):
     vq, tris, colours = random_mesh(100 + depth, depth, 50)
     quad = planar_quad(depth)
     tris = np.concatenate([tris, quad[1] + len(vq)])
     vq = np.concatenate([vq, quad[0]])
     colours = np.concatenate([colours, [0xFF000005, 6]])  # (the high byte is masked away)
-    xyz, colour, tri = check_mesh(pkg, vgpu, vq, tris, depth, colours, f"depth {depth}")
+    xyz, colour, tri = check_mesh(pkg, own_gpu, vq, tris, depth, colours, f"depth {depth}")
     assert set(tri.tolist()) == set(range(52))
     wall = xyz[tri >= 50]
     assert len(wall) >= 9 and (wall[:, 1] == 2).all()  # the quad on the grid plane y = 2 is one cell thick
@@ -140,16 +115,16 @@ def one_cell_triangles(seed, depth, n):
 
 
 @pytest.mark.parametrize("n", [4095, 4096, 4097])
-def test_triangle_counts_around_the_scans_tile(pkg, vgpu, n):
+def test_triangle_counts_around_the_scans_tile(pkg, own_gpu, n):
     vq, tris, cells = one_cell_triangles(n, 5, n)
     colours = np.arange(1, n + 1)
-    xyz, colour, tri = check_mesh(pkg, vgpu, vq, tris, 5, colours, f"{n} one-cell triangles")
+    xyz, colour, tri = check_mesh(pkg, own_gpu, vq, tris, 5, colours, f"{n} one-cell triangles")
     assert np.array_equal(xyz, cells) and np.array_equal(tri, np.arange(n)) and np.array_equal(colour, colours)
 
 
-def test_a_levels_pairs_span_several_tiles(pkg, vgpu):
+def test_a_levels_pairs_span_several_tiles(pkg, own_gpu):
     vq, tris, colours = random_mesh(8, 8, 10000, n_vertices=6000, extent=200)
-    xyz, colour, tri = check_mesh(pkg, vgpu, vq, tris, 8, colours, "10 000 small triangles at depth 8")
+    xyz, colour, tri = check_mesh(pkg, own_gpu, vq, tris, 8, colours, "10 000 small triangles at depth 8")
     assert len(tri) > 5 * 4096
 
 
@@ -173,17 +148,17 @@ def last_wins(xyz, colour, depth):
 
 
 @pytest.mark.parametrize("name", ["icosphere", "torus"])
-def test_depth_7_meshes_and_their_trees(pkg, vgpu, meshes7, name):
+def test_depth_7_meshes_and_their_trees(pkg, own_gpu, meshes7, name):
     m = meshes7[name]
     want = m["list"]
-    check_mesh(pkg, vgpu, m["vq"], m["t"], 7, m["colours"], name, want)
+    check_mesh(pkg, own_gpu, m["vq"], m["t"], 7, m["colours"], name, want)
     # the public call, from float vertices, with the triangle indices
-    coords, colours, tris = pkg.mesh.voxelize(vgpu, m["v"], m["t"], 7, m["colours"], with_triangles=True)
+    coords, colours, tris = pkg.mesh.voxelize(own_gpu, m["v"], m["t"], 7, m["colours"], with_triangles=True)
     assert coords.dtype == colours.dtype == tris.dtype and coords.dtype.is_signed and coords.shape == (len(want[1]), 3)
     for got, w in zip((coords, colours, tris), want):
         assert np.array_equal(got.cpu().numpy().view(np.uint32), w)
     # voxelise and build: the words of the reference list's tree
-    render = pkg.Render.from_mesh(vgpu, (64, 64), m["v"], m["t"], 7, m["colours"], capacity=CAPACITY)
+    render = pkg.Render.from_mesh(own_gpu, (64, 64), m["v"], m["t"], 7, m["colours"], capacity=CAPACITY)
     words = B.build(want[0], 7, want[1])
     assert render.node_length == words.size and np.array_equal(render.read_nodes(), words)
     assert render.build_nodes_mesh(m["vq"], m["t"], 7, m["colours"], quantized=True) == words.size
@@ -202,59 +177,59 @@ def test_depth_7_meshes_and_their_trees(pkg, vgpu, meshes7, name):
     assert np.array_equal(render.read_nodes(), edited)
 
 
-def test_depth_21_next_to_the_far_corner(pkg, vgpu):
+def test_depth_21_next_to_the_far_corner(pkg, own_gpu):
     vq = [[TOP21 - 1 - 64 * 300, TOP21 - 10, TOP21 - 20], [TOP21 - 1, TOP21 - 5, TOP21 - 70], [TOP21 - 64 * 150, TOP21 - 3, TOP21 - 30]]
-    xyz, colour, tri = check_mesh(pkg, vgpu, vq, [[0, 1, 2]], 21, [0xABCDEF], "depth-21 sliver")
+    xyz, colour, tri = check_mesh(pkg, own_gpu, vq, [[0, 1, 2]], 21, [0xABCDEF], "depth-21 sliver")
     assert 300 <= len(xyz) < 2000 and xyz.max() == (1 << 21) - 1 and xyz.min() >= (1 << 21) - 302
 
 
-def test_the_cap_stops_the_corner_to_corner_sliver_at_its_level(pkg, vgpu):
+def test_the_cap_stops_the_corner_to_corner_sliver_at_its_level(pkg, own_gpu):
     vq = [[0, 0, 0], [TOP21 - 1, TOP21 - 1, TOP21 - 1], [TOP21 - 1, TOP21 - 1, TOP21 - 2]]
     stopped = V.voxelize(vq, [[0, 1, 2]], 21, cap=4096)
     assert isinstance(stopped, V.Stopped) and stopped.count > 4096
-    mesh = Mesh(vgpu, vq, [[0, 1, 2]])
-    out = Out(vgpu, 4096 + SLACK)
-    assert raw_voxelize(pkg, vgpu, mesh, 21, out, max_voxels=4096) == (ERR_CAP, 12345)
-    found = re.search(r"level (\d+) has (\d+) ", last_error(pkg, vgpu))
-    assert found and (int(found.group(1)), int(found.group(2))) == (stopped.level, stopped.count), last_error(pkg, vgpu)
-    assert "max_voxels = 4096" in last_error(pkg, vgpu)
+    mesh = Mesh(own_gpu, vq, [[0, 1, 2]])
+    out = Out(own_gpu, 4096 + SLACK)
+    assert raw_voxelize(pkg, own_gpu, mesh, 21, out, max_voxels=4096) == (ERR_CAP, 12345)
+    found = re.search(r"level (\d+) has (\d+) ", last_error(pkg, own_gpu))
+    assert found and (int(found.group(1)), int(found.group(2))) == (stopped.level, stopped.count), last_error(pkg, own_gpu)
+    assert "max_voxels = 4096" in last_error(pkg, own_gpu)
     assert out.untouched_from(0)
 
 
-def test_count_query_runs_and_no_triangles(pkg, vgpu, meshes7):
+def test_count_query_runs_and_no_triangles(pkg, own_gpu, meshes7):
     m = meshes7["torus"]
-    mesh = Mesh(vgpu, m["vq"], m["t"], m["colours"])
+    mesh = Mesh(own_gpu, m["vq"], m["t"], m["colours"])
     count = len(m["list"][1])
-    assert raw_voxelize(pkg, vgpu, mesh, 7, max_voxels=0) == (0, count)  # a count query does not look at max_voxels
+    assert raw_voxelize(pkg, own_gpu, mesh, 7, max_voxels=0) == (0, count)  # a count query does not look at max_voxels
     runs = []
     for _ in range(2):
-        out = Out(vgpu, count + SLACK)
-        assert raw_voxelize(pkg, vgpu, mesh, 7, out) == (0, count)
+        out = Out(own_gpu, count + SLACK)
+        assert raw_voxelize(pkg, own_gpu, mesh, 7, out) == (0, count)
         runs.append(out.host())
     assert all(a.tobytes() == b.tobytes() for a, b in zip(*runs))
     # without the triangle output
-    out = Out(vgpu, count + SLACK)
-    assert raw_voxelize(pkg, vgpu, mesh, 7, out, tri_out=False) == (0, count)
+    out = Out(own_gpu, count + SLACK)
+    assert raw_voxelize(pkg, own_gpu, mesh, 7, out, tri_out=False) == (0, count)
     assert np.array_equal(out.host()[0][:count], m["list"][0]) and (out.host()[2] == SENTINEL).all()
     # no triangles: success with 0, with and without outputs, with and without vertices
     for vq in (m["vq"], np.zeros((0, 3))):
-        empty = Mesh(vgpu, vq, np.zeros((0, 3)))
-        out = Out(vgpu, SLACK)
-        assert raw_voxelize(pkg, vgpu, empty, 7, out) == (0, 0) and raw_voxelize(pkg, vgpu, empty, 7) == (0, 0)
+        empty = Mesh(own_gpu, vq, np.zeros((0, 3)))
+        out = Out(own_gpu, SLACK)
+        assert raw_voxelize(pkg, own_gpu, empty, 7, out) == (0, 0) and raw_voxelize(pkg, own_gpu, empty, 7) == (0, 0)
         assert out.untouched_from(0)
-    coords, colours, tris = pkg.mesh.voxelize(vgpu, m["v"], np.zeros((0, 3), dtype=np.int32), 7, with_triangles=True)
+    coords, colours, tris = pkg.mesh.voxelize(own_gpu, m["v"], np.zeros((0, 3), dtype=np.int32), 7, with_triangles=True)
     assert coords.shape == (0, 3) and colours.shape == (0,) and tris.shape == (0,)
 
 
-def test_errors_in_their_order_write_nothing(pkg, vgpu, meshes7):
+def test_errors_in_their_order_write_nothing(pkg, own_gpu, meshes7):
     m = meshes7["icosphere"]
     count = len(m["list"][1])
-    mesh = Mesh(vgpu, m["vq"], m["t"], m["colours"])
-    out = Out(vgpu, count + SLACK)
+    mesh = Mesh(own_gpu, m["vq"], m["t"], m["colours"])
+    out = Out(own_gpu, count + SLACK)
 
     def refused(code, part, mesh=mesh, depth=7, **kw):
-        got = raw_voxelize(pkg, vgpu, mesh, depth, kw.pop("out", out), **kw)
-        return got == (code, 12345) and part in last_error(pkg, vgpu)
+        got = raw_voxelize(pkg, own_gpu, mesh, depth, kw.pop("out", out), **kw)
+        return got == (code, 12345) and part in last_error(pkg, own_gpu)
 
     # every cause alone, then with the next one in the contract's order: the earlier one is reported
     assert refused(ERR_ARG, "null params", params=False)
@@ -277,7 +252,7 @@ def test_errors_in_their_order_write_nothing(pkg, vgpu, meshes7):
     tris = m["t"].copy()
     tris[7, 1] = len(m["vq"])
     tris[3, 2] = 0x7FFFFFFF
-    bad_index = Mesh(vgpu, m["vq"], tris, m["colours"])
+    bad_index = Mesh(own_gpu, m["vq"], tris, m["colours"])
     assert refused(ERR_ARG, "triangle 3 has a vertex index", mesh=bad_index)
     assert refused(ERR_ARG, "triangle 3 has a vertex index", mesh=bad_index, out=None)
     assert refused(ERR_ARG, "colour_out_dev", mesh=bad_index, colour_out=False)
@@ -285,41 +260,41 @@ def test_errors_in_their_order_write_nothing(pkg, vgpu, meshes7):
     vq = m["vq"].copy()
     vq[m["t"][5, 0], 2] = 1 << 13  # = 2^(depth + 6): the first coordinate outside
     at = int(np.flatnonzero((m["t"] == m["t"][5, 0]).any(axis=1)).min())
-    assert refused(ERR_ARG, f"triangle {at} has a coordinate", mesh=Mesh(vgpu, vq, m["t"], m["colours"]))
+    assert refused(ERR_ARG, f"triangle {at} has a coordinate", mesh=Mesh(own_gpu, vq, m["t"], m["colours"]))
     vq[m["t"][5, 0], 2] = (1 << 13) - 1
-    assert raw_voxelize(pkg, vgpu, Mesh(vgpu, vq, m["t"]), 7)[0] == 0
+    assert raw_voxelize(pkg, own_gpu, Mesh(own_gpu, vq, m["t"]), 7)[0] == 0
     tris = m["t"].copy()
     tris[at + 1] = len(m["vq"]) + 5
     vq[m["t"][5, 0], 0] = 0xFFFFFFFF
-    assert refused(ERR_ARG, f"triangle {at} has a coordinate", mesh=Mesh(vgpu, vq, tris))
+    assert refused(ERR_ARG, f"triangle {at} has a coordinate", mesh=Mesh(own_gpu, vq, tris))
     with pytest.raises(pkg.SvoError):
-        pkg.mesh.voxelize(vgpu, vq, tris, 7, quantized=True)
+        pkg.mesh.voxelize(own_gpu, vq, tris, 7, quantized=True)
     with pytest.raises(ValueError):
-        pkg.mesh.voxelize(vgpu, m["v"] * 2, m["t"], 7)
+        pkg.mesh.voxelize(own_gpu, m["v"] * 2, m["t"], 7)
     # room for one entry less than there are
     assert refused(ERR_CAP, f"level 7 has {count} ", max_voxels=count - 1)
     assert refused(ERR_CAP, "level ", max_voxels=0)
     assert out.untouched_from(0)
-    assert raw_voxelize(pkg, vgpu, mesh, 7, out, max_voxels=count) == (0, count) and out.untouched_from(count)
+    assert raw_voxelize(pkg, own_gpu, mesh, 7, out, max_voxels=count) == (0, count) and out.untouched_from(count)
 
 
-def test_the_node_buffer_is_never_touched_and_timing(pkg, vgpu, meshes7):
-    render = pkg.Render(vgpu, (64, 64), ROOT, capacity=CAPACITY)
+def test_the_node_buffer_is_never_touched_and_timing(pkg, own_gpu, meshes7):
+    render = pkg.Render(own_gpu, (64, 64), ROOT, capacity=CAPACITY)
     rng = np.random.default_rng(3)
     base = B.build(rng.integers(0, 64, (2000, 3)), 6, rng.integers(1, 1 << 24, 2000))
     set_base(render, base)
     before = render.read_nodes(base.size + PAD)
     assert np.array_equal(before[base.size:], poison(PAD))
     m = meshes7["icosphere"]
-    coords, colours = pkg.mesh.voxelize(vgpu, m["v"], m["t"], 7, m["colours"])
+    coords, colours = pkg.mesh.voxelize(own_gpu, m["v"], m["t"], 7, m["colours"])
     assert np.array_equal(coords.cpu().numpy().view(np.uint32), m["list"][0])
     assert np.array_equal(render.read_nodes(base.size + PAD), before) and render.node_length == base.size
-    ms = vgpu.voxelize_timing()
+    ms = own_gpu.voxelize_timing()
     assert len(ms) == 5 and all(t >= 0 for t in ms) and ms[4] > 0 and ms[3] > 0
-    assert ms == vgpu.voxelize_timing()
-    assert raw_voxelize(pkg, vgpu, Mesh(vgpu, m["vq"], m["t"]), 0)[0] == ERR_ARG  # a refused call leaves the times
-    assert raw_voxelize(pkg, vgpu, Mesh(vgpu, m["vq"], m["t"]), 7, Out(vgpu, 8), max_voxels=8)[0] == ERR_CAP
-    assert ms == vgpu.voxelize_timing()
+    assert ms == own_gpu.voxelize_timing()
+    assert raw_voxelize(pkg, own_gpu, Mesh(own_gpu, m["vq"], m["t"]), 0)[0] == ERR_ARG  # a refused call leaves the times
+    assert raw_voxelize(pkg, own_gpu, Mesh(own_gpu, m["vq"], m["t"]), 7, Out(own_gpu, 8), max_voxels=8)[0] == ERR_CAP
+    assert ms == own_gpu.voxelize_timing()
     # a context with no node buffer voxelises; one that has not, has no times
     fresh = pkg.Gpu(0)
     try:

@@ -8,7 +8,8 @@ import numpy as np
 import pytest
 
 import world_build_ref as R
-from test_adaptive_device_gpu import assert_octrees_equal, make_loop, run_frames, write_blocks
+from pass_frame import assert_octrees_equal, write_blocks
+from test_adaptive_device_gpu import make_loop, run_frames
 
 pytestmark = pytest.mark.gpu
 

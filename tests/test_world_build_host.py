@@ -9,6 +9,7 @@ import pytest
 import build_ref as B
 import world_build_ref as R
 from conftest import GOLDEN
+from pass_frame import write_blocks
 
 
 def test_entry_points_are_exported_with_signatures(pkg):
@@ -87,15 +88,6 @@ def test_world_reference_splits_into_chunk_trees(pkg):
         ptr, rgb, t = R.tree(cells[sel] & ((1 << cd) - 1), cd, col[sel])
         assert data == R.to_bin(ptr, rgb) and np.array_equal(top, t)
         assert pkg.CpuOctree.from_bin(data).bin() == data
-
-
-def write_blocks(pkg, d):
-    """blocks/<name>.vox of the 8 block fixtures, as World.new reads them; returns the directory"""
-    z = np.load(f"{GOLDEN}/blocks_vox.npz")
-    d.mkdir()
-    for name in B.BLOCKS:
-        (d / f"{name}.vox").write_bytes(pkg.cpu_octree.vox_write(16, z[name + "_xyzi"], z[name + "_palette"]))
-    return str(d)
 
 
 @pytest.mark.gpu
