@@ -276,13 +276,12 @@ int trace_launch(svo_ctx *ctx, const svo::WorkDesc &work, const float *rays, svo
     li.occupancy = ctx->occupancy;
     if (stack && ctx->defer_items < wd.n_items) {
         HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        ctx->defer_buf.reset();
         ctx->frame_parity = 0;
         ctx->defer_items = 0;
         size_t want = wd.n_items < (1u << 16) ? (1u << 16) : wd.n_items;
         // layout: claim counters | list A: count + items | list B: count + items
-        HIP_TRY(ctx, hipMalloc((void **)&ctx->defer_buf.p, (svo::kCounterWords + 2 * (want + 1)) * sizeof(uint32_t)));
-        HIP_TRY(ctx, hipMemsetAsync(ctx->defer_buf, 0, (svo::kCounterWords + 2 * (want + 1)) * sizeof(uint32_t), ctx->stream));
+        HIP_TRY(ctx, ctx->defer_buf.alloc(svo::kCounterWords + 2 * (want + 1)));
+        HIP_TRY(ctx, hipMemsetAsync(ctx->defer_buf, 0, ctx->defer_buf.size() * sizeof(uint32_t), ctx->stream));
         ctx->defer_items = want;
     }
     li.counters = ctx->defer_buf;  // (strips are always claimed dynamically)
@@ -339,18 +338,18 @@ int trace_common(svo_ctx *ctx, const svo::WorkDesc &work, const float *rays, svo
     const uint32_t f = ctx->uniforms.flags;
     const bool shadows = (f & SVO_F_SHADOWS) && !(f & SVO_F_SHOW_STEPS) && !(f & SVO_F_SHOW_HITS);
     if (!hits) {
-        rc = svo_grow(ctx, &ctx->shade_hits_items, n, &ctx->shade_hits);
+        rc = svo_grow(ctx, n, &ctx->shade_hits);
         if (rc) return rc;
         hits = ctx->shade_hits;
     }
     const bool fused = shadows && fuse_shadow_rays(ctx);
     TraceOpts primary;
     if (fused) {
-        rc = svo_grow(ctx, &ctx->shade_shadow_items, n, &ctx->shade_shadow);
+        rc = svo_grow(ctx, n, &ctx->shade_shadow);
         if (rc) return rc;
         primary.shadow_out = ctx->shade_shadow;
     } else {
-        rc = svo_grow(ctx, &ctx->shade_aux_items, n, &ctx->shade_aux);
+        rc = svo_grow(ctx, n, &ctx->shade_aux);
         if (rc) return rc;
         primary.aux_t = ctx->shade_aux;
     }
@@ -358,11 +357,11 @@ int trace_common(svo_ctx *ctx, const svo::WorkDesc &work, const float *rays, svo
     if (rc) return rc;
     const svo::TraceArgs a = trace_args(ctx, work, hits);
     if (shadows && !fused) {
-        rc = svo_grow(ctx, &ctx->shade_rays_items, n * 6, &ctx->shade_rays);
+        rc = svo_grow(ctx, n * 6, &ctx->shade_rays);
         if (rc) return rc;
-        rc = svo_grow(ctx, &ctx->shade_shadow_items, n, &ctx->shade_shadow);
+        rc = svo_grow(ctx, n, &ctx->shade_shadow);
         if (rc) return rc;
-        rc = svo_grow(ctx, &ctx->shade_skip_items, n, &ctx->shade_skip);
+        rc = svo_grow(ctx, n, &ctx->shade_skip);
         if (rc) return rc;
         HIP_TRY(ctx, svo::launch_secondary_gen(a, ctx->shade_aux, ctx->shade_rays, ctx->shade_skip, ctx->shade_shadow, 0u, 1u,
                                                (uint32_t)n, ctx->stream));
@@ -388,13 +387,13 @@ int trace_secondary(svo_ctx *ctx, const svo::WorkDesc &work, uint32_t n_secondar
     const size_t n = (size_t)work.n_rects * work.w * work.h;
     if (n * n_secondary > (1u << 26)) return svo_fail(ctx, SVO_ERR_ARG, "too many secondary rays for one call");
     if (!primary) {
-        rc = svo_grow(ctx, &ctx->shade_hits_items, n, &ctx->shade_hits);
+        rc = svo_grow(ctx, n, &ctx->shade_hits);
         if (rc) return rc;
         primary = ctx->shade_hits;
     }
-    rc = svo_grow(ctx, &ctx->shade_aux_items, n, &ctx->shade_aux);
+    rc = svo_grow(ctx, n, &ctx->shade_aux);
     if (rc) return rc;
-    rc = svo_grow(ctx, &ctx->shade_rays_items, n * n_secondary * 6, &ctx->shade_rays);
+    rc = svo_grow(ctx, n * n_secondary * 6, &ctx->shade_rays);
     if (rc) return rc;
     // ray 0, the shadow ray, can run inside the primary launch (its records go straight to the first set)
     const bool debug_view = (ctx->uniforms.flags & SVO_F_PAUSE_ADAPTIVE) && (ctx->uniforms.flags & SVO_F_SHOW_HITS);
@@ -407,7 +406,7 @@ int trace_secondary(svo_ctx *ctx, const svo::WorkDesc &work, uint32_t n_secondar
     if (rc) return rc;
     if (k_first == n_secondary) return SVO_OK;
     const svo::TraceArgs a = trace_args(ctx, work, primary);
-    rc = svo_grow(ctx, &ctx->shade_skip_items, n * n_secondary, &ctx->shade_skip);
+    rc = svo_grow(ctx, n * n_secondary, &ctx->shade_skip);
     if (rc) return rc;
     svo_hit *rest = secondary + (size_t)k_first * n;
     HIP_TRY(ctx, svo::launch_secondary_gen(a, ctx->shade_aux, ctx->shade_rays, ctx->shade_skip, rest, k_first, n_secondary,
@@ -488,10 +487,10 @@ hipError_t svo_ctx::Sched::alloc(uint32_t n_strips) {
     const uint32_t want = n_strips < 4096u ? 4096u : n_strips;
     const size_t cls_bytes = want + 32 + svo::kOrderHistWords * sizeof(uint32_t);  // class bytes, then the chunk histograms
     const size_t order_words = 8 + 8 * (svo::order_list_cap(want) + 8);  // 8 lengths, 8 lists (and 8 spare entries each)
-    hipError_t e = hipMalloc((void **)&cost.p, cls_bytes);
-    if (e == hipSuccess) e = hipMalloc((void **)&cls_now.p, cls_bytes);
-    if (e == hipSuccess) e = hipMalloc((void **)&order.p, order_words * sizeof(uint32_t));
-    if (e == hipSuccess) e = hipMalloc((void **)&balance.p, svo::kBalanceWords * sizeof(uint32_t));
+    hipError_t e = cost.alloc(cls_bytes);
+    if (e == hipSuccess) e = cls_now.alloc(cls_bytes);
+    if (e == hipSuccess) e = order.alloc(order_words);
+    if (e == hipSuccess) e = balance.alloc(svo::kBalanceWords);
     if (e == hipSuccess) cap = want;
     return e;
 }
@@ -562,8 +561,8 @@ int svo_ctx_create(int hip_device, svo_ctx **out) {
         ctx->num_cus = prop.multiProcessorCount;
         e = ctx->own_stream.create();
     }
-    if (e == hipSuccess) e = hipMalloc((void **)&ctx->top_table.p, (svo::kTopEntries + svo::kTopAuxEntries) * sizeof(uint32_t));
-    if (e == hipSuccess) e = hipMalloc((void **)&ctx->status.p, sizeof(uint32_t));
+    if (e == hipSuccess) e = ctx->top_table.alloc(svo::kTopEntries + svo::kTopAuxEntries);
+    if (e == hipSuccess) e = ctx->status.alloc(1);
     if (e == hipSuccess) e = hipMemset(ctx->status, 0, sizeof(uint32_t));
     if (e != hipSuccess) {
         svo_ctx_destroy(ctx);
@@ -759,7 +758,7 @@ int svo_nodes_scatter(svo_ctx *ctx, const uint32_t *indices, const uint32_t *hos
     if (rc || n == 0) return rc;
     rc = order_after_last_write(ctx);  // a shared store: writes land in the order they were issued, whichever context issued them
     if (rc) return rc;
-    rc = svo_grow(ctx, &ctx->scatter_items, 2 * n, &ctx->scatter_buf);
+    rc = svo_grow(ctx, 2 * n, &ctx->scatter_buf);
     if (rc) return rc;
     uint32_t *d_idx = ctx->scatter_buf, *d_val = d_idx + n;
     HIP_TRY(ctx, hipMemcpyAsync(d_idx, indices, n * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
@@ -819,7 +818,7 @@ int svo_render_host(svo_ctx *ctx, uint32_t width, uint32_t height, uint32_t x0, 
     size_t n = (size_t)tile_w * tile_h;
     rc = bind(ctx);
     if (rc) return rc;
-    rc = svo_grow(ctx, &ctx->stage_bytes, n * (sizeof(svo_hit) + sizeof(uint32_t)), &ctx->stage);
+    rc = svo_grow(ctx, n * (sizeof(svo_hit) + sizeof(uint32_t)), &ctx->stage);
     if (rc) return rc;
     svo_hit *dh = (svo_hit *)ctx->stage.get();
     uint32_t *dc = (uint32_t *)(ctx->stage + n * sizeof(svo_hit));
@@ -965,7 +964,7 @@ int svo_scan_dispatch(svo_ctx *ctx, uint32_t node_length) {
     if (!ctx->scan_lists) {
         // Compute::new: two lists of 1 024 000 words, zero-initialised (compute.rs:46-64)
         // (one allocation for both, so that a failure cannot leave half of the pair behind)
-        HIP_TRY(ctx, hipMalloc((void **)&ctx->scan_lists.p, 2 * kScanCapacity * sizeof(uint32_t)));
+        HIP_TRY(ctx, ctx->scan_lists.alloc(2 * kScanCapacity));
         ctx->scan_capacity = kScanCapacity;
         HIP_TRY(ctx, hipMemsetAsync(ctx->scan_sub(), 0, sizeof(uint32_t), ctx->stream));
         HIP_TRY(ctx, hipMemsetAsync(ctx->scan_unsub(), 0, sizeof(uint32_t), ctx->stream));

@@ -404,27 +404,20 @@ struct svo_adapt_state {
     uint32_t *nodes_at_attach = nullptr;  // the node buffer the state belongs to
     size_t capacity = 0;                  // the node buffer's at attach
     svo_dev<float> pos;                   // 3 per node
-    size_t pos_items = 0;
     svo_dev<uint32_t> holes;
-    size_t hole_cap = 0;
     uint32_t n_holes = 0;
     uint32_t len = 0;
     // world mirror: nodes {pointer, rgb} of every resident chunk, concatenated; table sorted by id
     svo_dev<uint2> wn;
-    size_t wn_cap = 0, wn_used = 0;
+    size_t wn_used = 0;  // nodes of the mirror in use
     std::vector<Chunk> tab;
     svo_dev<Chunk> tab_dev;
-    size_t tab_cap = 0;
     svo_dev<uint32_t> rm;  // per table slot: lowest unsubdivide rank that drops it
-    size_t rm_cap = 0;
     // per-entry workspace
     svo_dev<uint32_t> list[2];  // sorted subdivide / unsubdivide lists
     svo_dev<uint32_t> res, src, val, flag;
-    size_t items = 0;
-    svo_dev<uint32_t> req;  // 2 per entry
-    size_t req_items = 0;
+    svo_dev<uint32_t> req;  // 2 per entry (grow_entries)
     svo_dev<uint32_t> bits;
-    size_t bit_words = 0;
     svo_mirrored<Status> st;                // one Status
     svo_pinned<uint32_t> counts_host;     // scan list counts
     std::vector<uint32_t> removed;
@@ -432,15 +425,13 @@ struct svo_adapt_state {
     float ms[SVO_ADAPT_TIMES] = {};
     // svo_adaptive_expand: this level's frontier and the next one's, the compactions' tile sums
     svo_dev<uint32_t> frontier[2];
-    size_t frontier_items[2] = {};
     svo_dev<uint32_t> tiles;
-    size_t tile_items = 0;
     float expand_ms[SVO_ADAPT_EXPAND_TIMES] = {};
 
     int create(svo_ctx *ctx) {
         HIP_TRY(ctx, ev.create());
         if (int rc = st.alloc(ctx, 1)) return rc;
-        HIP_TRY(ctx, hipHostMalloc((void **)&counts_host.p, 2 * sizeof(uint32_t), hipHostMallocDefault));
+        HIP_TRY(ctx, counts_host.alloc(2));
         return SVO_OK;
     }
 };
@@ -454,9 +445,9 @@ void table_insert(std::vector<Chunk> &tab, const Chunk &c) { tab.insert(std::upp
 // the table (and the rank array sized to it) to the device; blocking, so the host vector may change afterwards
 int upload_table(svo_ctx *ctx) {
     svo_adapt_state *a = ctx->adapt.get();
-    int rc = svo_grow(ctx, &a->tab_cap, std::max<size_t>(a->tab.size(), 16), &a->tab_dev);
+    int rc = svo_grow(ctx, std::max<size_t>(a->tab.size(), 16), &a->tab_dev);
     if (rc) return rc;
-    if ((rc = svo_grow(ctx, &a->rm_cap, std::max<size_t>(a->tab.size(), 16), &a->rm))) return rc;
+    if ((rc = svo_grow(ctx, std::max<size_t>(a->tab.size(), 16), &a->rm))) return rc;
     if (!a->tab.empty())
         HIP_TRY(ctx, hipMemcpyAsync(a->tab_dev, a->tab.data(), a->tab.size() * sizeof(Chunk), hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
@@ -486,8 +477,8 @@ int rebuild_mirror(svo_ctx *ctx, size_t extra) {
     size_t total = 0;
     for (uint32_t id : ids) total += svo_cpu_octree_len(svo_world_chunk(a->world, id));
     if (total + extra >= kNone) return svo_fail(ctx, SVO_ERR_CAP, "the world mirror would pass 2^32 nodes");
-    if (a->wn_cap < total + extra) {
-        const int rc = svo_grow(ctx, &a->wn_cap, std::min<size_t>(2 * (total + extra) + 4096, kNone - 1), &a->wn);
+    if (a->wn.size() < total + extra) {
+        const int rc = svo_grow(ctx, std::min<size_t>(2 * (total + extra) + 4096, kNone - 1), &a->wn);
         if (rc) return rc;
     }
     a->wn_used = 0;
@@ -513,7 +504,7 @@ int mirror_add(svo_ctx *ctx, uint32_t id, uint32_t rank) {
     svo_adapt_state *a = ctx->adapt.get();
     const svo_cpu_octree *t = svo_world_chunk(a->world, id);
     const size_t cnt = svo_cpu_octree_len(t);
-    if (a->wn_used + cnt > a->wn_cap) {
+    if (a->wn_used + cnt > a->wn.size()) {
         table_insert(a->tab, {id, 0, 0, rank});  // (the rebuild reads its nodes from the world and keeps the rank)
         return rebuild_mirror(ctx, 0);
     }
@@ -563,6 +554,14 @@ Tree tree_of(svo_ctx *ctx) { return Tree{ctx->nodes, ctx->adapt->pos, ctx->adapt
 size_t grown(size_t have, size_t want) { return have >= want ? have : std::max(want, 2 * have); }
 // ... and the hole stack: twice what it needs, so the passes that follow push without growing it again
 size_t grown_stack(size_t have, size_t want) { return have >= want ? have : 2 * want; }
+
+// the per-entry workspace for `items` entries, and req's two words for each; flag is allocated last, so its size is
+// the room of all of them
+int grow_entries(svo_ctx *ctx, size_t items) {
+    svo_adapt_state *a = ctx->adapt.get();
+    const int rc = svo_grow(ctx, items, &a->list[0], &a->list[1], &a->res, &a->src, &a->val, &a->flag);
+    return rc ? rc : svo_grow(ctx, 2 * items, &a->req);
+}
 
 // ---- the subdivide pass over the sorted list a->list[0][0, n) ----
 // Only the first `limit` successes in list order are applied (svo_adaptive_expand's word cap; kNone: all of them).
@@ -636,9 +635,9 @@ int unsubdivide_pass(svo_ctx *ctx, uint32_t n, svo_adaptive_result *out) {
     const uint32_t *list = a->list[1], grid = svo_div_up(n, kThreads);
     int rc;
     const size_t words = (a->len + 31) / 32;
-    if ((rc = svo_grow(ctx, &a->bit_words, std::max<size_t>(words, 1), &a->bits))) return rc;
+    if ((rc = svo_grow(ctx, std::max<size_t>(words, 1), &a->bits))) return rc;
     HIP_TRY(ctx, hipMemsetAsync(a->bits, 0, words * sizeof(uint32_t), ctx->stream));
-    HIP_TRY(ctx, hipMemsetAsync(a->rm, 0xFF, a->rm_cap * sizeof(uint32_t), ctx->stream));
+    HIP_TRY(ctx, hipMemsetAsync(a->rm, 0xFF, a->rm.size() * sizeof(uint32_t), ctx->stream));
     if ((rc = clear_status(ctx))) return rc;
     unsub_mark_kernel<<<grid, kThreads, 0, ctx->stream>>>(list, n, a->len, a->bits);
     unsub_plan_kernel<<<grid, kThreads, 0, ctx->stream>>>(tree_of(ctx), list, n, a->bits, a->tab_dev, (uint32_t)a->tab.size(),
@@ -657,10 +656,10 @@ int unsubdivide_pass(svo_ctx *ctx, uint32_t n, svo_adaptive_result *out) {
     if ((rc = read_status(ctx, a->flag + n))) return rc;
     if (a->st.host()->err != kNone) return entry_fail(ctx, SVO_ERR_STATE, a->st.host()->err, "unsubdivide");
     const uint32_t done = a->st.host()->total;
-    const size_t hole_room = grown_stack(a->hole_cap, size_t(a->n_holes) + done);
-    if ((rc = svo_grow_keep(ctx, &a->hole_cap, hole_room, &a->holes, a->n_holes))) return rc;
+    const size_t hole_room = grown_stack(a->holes.size(), size_t(a->n_holes) + done);
+    if ((rc = svo_grow_keep(ctx, hole_room, &a->holes, a->n_holes))) return rc;
     unsub_apply_kernel<<<grid, kThreads, 0, ctx->stream>>>(tree_of(ctx), list, n, a->res, a->val, a->src, a->flag, a->holes,
-                                                           a->n_holes, (uint32_t)a->hole_cap);
+                                                           a->n_holes, (uint32_t)a->holes.size());
     HIP_TRY(ctx, hipGetLastError());
     a->n_holes += done;
     out->n_unsub = done;
@@ -699,7 +698,7 @@ template <class Keep, class Emit>
 int timed_compaction(svo_ctx *ctx, int stage, const uint32_t *in, uint32_t n, Keep keep, Emit emit) {
     svo_adapt_state *a = ctx->adapt.get();
     const uint32_t nt = svo_div_up(n, kTile);
-    int rc = svo_grow(ctx, &a->tile_items, nt + 1, &a->tiles);
+    int rc = svo_grow(ctx, nt + 1, &a->tiles);
     if (rc || (rc = clear_status(ctx))) return rc;
     HIP_TRY(ctx, hipEventRecord(a->ev[0], ctx->stream));
     compact_count_kernel<<<nt, kThreads, 0, ctx->stream>>>(in, n, keep, a->tiles);
@@ -740,9 +739,9 @@ int svo_adaptive_attach(svo_ctx *ctx, svo_world *w, const svo_octree *o) {
     if (rc) return rc;
     svo_adapt_state *a = ctx->adapt.get();
     a->world = nullptr;  // (attached only once everything is up)
-    if ((rc = svo_grow(ctx, &a->pos_items, 3 * ctx->capacity, &a->pos))) return rc;
+    if ((rc = svo_grow(ctx, 3 * ctx->capacity, &a->pos))) return rc;
     a->capacity = ctx->capacity;
-    if ((rc = svo_grow(ctx, &a->hole_cap, std::max<size_t>(holes.size() + kListCap, ctx->capacity / 8 + 1), &a->holes))) return rc;
+    if ((rc = svo_grow(ctx, std::max<size_t>(holes.size() + kListCap, ctx->capacity / 8 + 1), &a->holes))) return rc;
     // (the order behind the store's last write: the plan kernels read the words)
     if ((rc = svo_store_order_after_write(ctx))) return rc;
     if (len) HIP_TRY(ctx, hipMemcpyAsync(a->pos, pos, 3 * len * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
@@ -788,9 +787,7 @@ int svo_adaptive_step(svo_ctx *ctx, const uint32_t *d_sub, uint32_t n_sub, const
         HIP_TRY(ctx, hipMemsetAsync(ctx->scan_unsub(), 0, sizeof(uint32_t), ctx->stream));
     }
     if (n_sub >= kMaxRank || n_unsub >= kMaxRank) return svo_fail(ctx, SVO_ERR_ARG, "at most 2^24 - 1 entries per list");
-    const size_t items = std::max<size_t>(std::max(n_sub, n_unsub), 1) + 1;
-    if ((rc = svo_grow(ctx, &a->items, items, &a->list[0], &a->list[1], &a->res, &a->src, &a->val, &a->flag))) return rc;
-    if ((rc = svo_grow(ctx, &a->req_items, 2 * items, &a->req))) return rc;
+    if ((rc = grow_entries(ctx, std::max<size_t>(std::max(n_sub, n_unsub), 1) + 1))) return rc;
     if ((rc = svo_build_sort_u32(ctx, d_sub, n_sub, a->list[0]))) return rc;
     if ((rc = svo_build_sort_u32(ctx, d_unsub, n_unsub, a->list[1]))) return rc;
     HIP_TRY(ctx, hipEventRecord(a->ev[1], ctx->stream));
@@ -838,7 +835,7 @@ int svo_adaptive_expand(svo_ctx *ctx, uint32_t max_depth, const float cam[3], fl
     // the initial frontier: the leaves of [0, len) (at most len of them)
     uint32_t cur = 0, n_front = 0;
     if (a->len) {
-        if ((rc = svo_grow(ctx, &a->frontier_items[0], a->len, &a->frontier[0]))) return rc;
+        if ((rc = svo_grow(ctx, a->len, &a->frontier[0]))) return rc;
         if ((rc = timed_compaction(ctx, 0, ctx->nodes, a->len, LeafWord{}, EmitLeaf{tree_of(ctx), a->frontier[0], a->len, a->st.dev}))) return rc;
         if (a->st.host()->err != kNone) return entry_fail(ctx, SVO_ERR_STATE, a->st.host()->err, "expand: leaf");
         n_front = a->st.host()->total;
@@ -852,7 +849,7 @@ int svo_adaptive_expand(svo_ctx *ctx, uint32_t max_depth, const float cam[3], fl
         const uint32_t nxt = cur ^ 1u;
         const uint64_t room = cap > a->len ? cap - a->len : 0;
         const size_t next_max = std::max<uint64_t>(std::min<uint64_t>(8ull * n_front, room), 8);  // 8 slots per success
-        if ((rc = svo_grow(ctx, &a->frontier_items[nxt], grown(a->frontier_items[nxt], next_max), &a->frontier[nxt]))) return rc;
+        if ((rc = svo_grow(ctx, grown(a->frontier[nxt].size(), next_max), &a->frontier[nxt]))) return rc;
         uint32_t n_next = 0;
         for (uint32_t lo = 0; lo < n_front && !full; lo += kMaxRank - 1u) {
             const uint32_t n = std::min(n_front - lo, kMaxRank - 1u);
@@ -861,10 +858,7 @@ int svo_adaptive_expand(svo_ctx *ctx, uint32_t max_depth, const float cam[3], fl
                 full = true;
                 break;
             }
-            if ((rc = svo_grow(ctx, &a->items, grown(a->items, size_t(n) + 1), &a->list[0], &a->list[1], &a->res, &a->src, &a->val,
-                               &a->flag)))
-                return rc;
-            if ((rc = svo_grow(ctx, &a->req_items, 2 * a->items, &a->req))) return rc;
+            if ((rc = grow_entries(ctx, grown(a->flag.size(), size_t(n) + 1)))) return rc;
             const uint32_t *front = a->frontier[cur] + lo;
             if ((rc = timed_compaction(ctx, 1, front, n, ViewRefines{a->pos, view}, EmitCandidate{a->list[0]}))) return rc;
             const uint32_t n_cand = a->st.host()->total;

@@ -341,25 +341,18 @@ struct svo_build_state {
     svo_dev<uint64_t> keys[3];
     svo_dev<uint32_t> vals[2];
     svo_dev<uint32_t> leaf_colours;
-    size_t items = 0;         // room in every one of them
+    size_t items() const { return leaf_colours.size(); }  // room in every one of them (the last one allocated)
     svo_dev<uint32_t> hist;   // the sort's digit counts, 256 per tile
-    size_t hist_items = 0;
     svo_dev<uint32_t> tiles;  // tile sums / offsets of a scan
-    size_t tile_items = 0;
     svo_mirrored<> counts;      // kCountSlots words: unique nodes per level, error word
     svo_pass_timer<kEvs, SVO_BUILD_TIMES> timer;  // (spans: kBuildSlots, the sort's only when the last build sorted)
     // chunk trees (svo_world_build, svo_cpu_octree_build)
     svo_dev<uint32_t> runs;  // per level 0..21: n_chunks + 1 chunk starts, and their pinned mirror
     svo_pinned<uint32_t> runs_host;
-    size_t runs_items = 0, runs_host_items = 0;
     svo_dev<uint32_t> cbase;  // per chunk: chunk-local level bases 1 .. chunk_depth + 1 (the last = its node count)
-    size_t cbase_items = 0;
     svo_dev<uint64_t> coff;   // per chunk: its first node in `nodes`
-    size_t coff_items = 0;
     svo_dev<uint2> nodes;     // every chunk's nodes, one chunk after another
-    size_t node_items = 0;
     svo_pinned<void> stage;   // one chunk's bytes on their way to a file or a CpuOctree
-    size_t stage_bytes = 0;
     float cms[SVO_WORLD_BUILD_TIMES] = {};
 
     int create(svo_ctx *ctx) {
@@ -375,9 +368,9 @@ int ensure_state(svo_ctx *ctx, size_t items, size_t scan_items, size_t hist_item
     int rc = svo_workspace_ensure(ctx, ctx->build);
     if (rc) return rc;
     svo_build_state *s = ctx->build.get();
-    rc = svo_grow(ctx, &s->items, items, &s->keys[0], &s->keys[1], &s->keys[2], &s->vals[0], &s->vals[1], &s->leaf_colours);
-    if (!rc) rc = svo_grow(ctx, &s->hist_items, hist_items, &s->hist);
-    if (!rc) rc = svo_grow(ctx, &s->tile_items, (size_t)svo_div_up(scan_items, kTile) + 1, &s->tiles);
+    rc = svo_grow(ctx, items, &s->keys[0], &s->keys[1], &s->keys[2], &s->vals[0], &s->vals[1], &s->leaf_colours);
+    if (!rc) rc = svo_grow(ctx, hist_items, &s->hist);
+    if (!rc) rc = svo_grow(ctx, (size_t)svo_div_up(scan_items, kTile) + 1, &s->tiles);
     return rc;
 }
 
@@ -441,10 +434,10 @@ int parent_passes(svo_ctx *ctx, uint32_t depth, uint32_t stop, const uint64_t *b
         in.keys = src;
         in.vals = l == depth ? s->leaf_colours : nullptr;
         in.m_dev = s->counts.dev + l;
-        in.m_max = (uint32_t)s->items;
+        in.m_max = (uint32_t)s->items();
         LevelOut out{};
         out.keys = s->keys[turn];
-        out.cap = (uint32_t)s->items;
+        out.cap = (uint32_t)s->items();
         out.words = words;
         if (words) {
             out.base = (uint32_t)base[l];
@@ -515,8 +508,8 @@ int list_leaves(svo_ctx *ctx, const uint32_t *xyz, const uint32_t *colours, size
     int rc = ensure_state(ctx, n, std::max<uint64_t>(n, 256ull * nt), 256ull * nt);
     if (rc) return rc;
     svo_build_state *s = ctx->build.get();
-    if ((rc = svo_grow(ctx, &s->runs_items, runs_items, &s->runs))) return rc;
-    if ((rc = svo_grow_pinned(ctx, &s->runs_host_items, runs_items, &s->runs_host))) return rc;
+    if ((rc = svo_grow(ctx, runs_items, &s->runs))) return rc;
+    if ((rc = svo_grow_pinned(ctx, runs_items, &s->runs_host))) return rc;
     HIP_TRY(ctx, s->timer.mark(ctx, kEvStart));
     HIP_TRY(ctx, s->counts.zero(ctx));
     if (runs_items) HIP_TRY(ctx, hipMemsetAsync(s->runs, 0, runs_items * sizeof(uint32_t), ctx->stream));
@@ -537,7 +530,7 @@ int list_leaves(svo_ctx *ctx, const uint32_t *xyz, const uint32_t *colours, size
     out.keys = s->keys[2];
     out.colours = s->leaf_colours;
     out.index = keep_index ? s->vals[(passes & 1) ^ 1] : nullptr;
-    out.cap = (uint32_t)s->items;
+    out.cap = (uint32_t)s->items();
     return level_pass<kDedupe>(ctx, in, out, n, s->counts.dev + depth);
 }
 
@@ -566,13 +559,13 @@ int finish(svo_ctx *ctx, const svo_build_params *p, uint64_t leaf_bound, double 
     svo_build_state *s = ctx->build.get();
     const uint32_t depth = p->depth;
     uint64_t bound[23] = {};
-    level_bounds(bound, depth, std::min<uint64_t>(leaf_bound, s->items));
+    level_bounds(bound, depth, std::min<uint64_t>(leaf_bound, s->items()));
     int rc = parent_passes(ctx, depth, 2, bound, nullptr, nullptr, 0);
     if (rc) return rc;
     if ((rc = read_counts(ctx, depth, 0))) return rc;
     const uint32_t *m = s->counts.host();
     const uint64_t limit = word_limit(ctx, p);
-    if (m[depth] > s->items)  // (dense: more solid cells than the cap has words)
+    if (m[depth] > s->items())  // (dense: more solid cells than the cap has words)
         return svo_fail(ctx, SVO_ERR_CAP, std::to_string(m[depth]) + " leaves cannot fit in " + std::to_string(limit) + " words");
     // breadth-first bases: level 1 (the root group) at 0, level L+1 behind level L's 8 * m_{L-1} words
     uint64_t base[23] = {0, 0};
@@ -673,7 +666,7 @@ int svo_build_list_leaves(svo_ctx *ctx, const uint32_t *xyz, const uint32_t *col
     out->spare32 = s->vals[a];
     out->spare64[0] = s->keys[0];
     out->spare64[1] = s->keys[1];
-    out->items = s->items;
+    out->items = s->items();
     out->ev_start = s->timer.ev[kEvStart];
     out->ev_keys = s->timer.ev[kEvKeys];
     out->ev_sort = s->timer.ev[kEvSort];
@@ -740,10 +733,10 @@ int chunk_build(svo_ctx *ctx, const uint32_t *xyz, const uint32_t *colours, size
         total += at;
         largest = std::max(largest, at);
     }
-    if ((rc = svo_grow(ctx, &s->cbase_items, cbase.size(), &s->cbase))) return rc;
-    if ((rc = svo_grow(ctx, &s->coff_items, coff.size(), &s->coff))) return rc;
-    if ((rc = svo_grow(ctx, &s->node_items, total, &s->nodes))) return rc;
-    if ((rc = svo_grow_pinned(ctx, &s->stage_bytes, largest * 8, &s->stage))) return rc;
+    if ((rc = svo_grow(ctx, cbase.size(), &s->cbase))) return rc;
+    if ((rc = svo_grow(ctx, coff.size(), &s->coff))) return rc;
+    if ((rc = svo_grow(ctx, total, &s->nodes))) return rc;
+    if ((rc = svo_grow_pinned(ctx, largest * 8, &s->stage))) return rc;
     if (world && (rc = world->create())) return rc;
 
     // emit and mips
@@ -891,7 +884,7 @@ int svo_nodes_build_dense(svo_ctx *ctx, const uint32_t *grid, const svo_build_pa
     LevelOut out{};
     out.keys = s->keys[2];
     out.colours = s->leaf_colours;
-    out.cap = (uint32_t)s->items;
+    out.cap = (uint32_t)s->items();
     if ((rc = level_pass<kDense>(ctx, in, out, cells, s->counts.dev + depth))) return rc;
     return finish(ctx, p, cells, t0, false, n_words_out);
 }

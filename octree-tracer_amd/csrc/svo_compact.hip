@@ -115,9 +115,7 @@ enum Ev { kEvStart, kEvDiscover, kEvCheck, kEvPrune, kEvEmit, kEvEnd, kEvs };
 // Per-context workspace of the compaction (svo_ctx::compact): the image and five u32 per group.
 struct svo_compact_state {
     svo_dev<uint32_t> image;  // the compacted words before they are copied back
-    size_t image_items = 0;
     svo_dev<uint32_t> order, first_child, new_of, live, number;
-    size_t group_items = 0;
     svo_mirrored<> status;  // kStWords words
     svo_pass_timer<kEvs, SVO_COMPACT_TIMES> timer;
 
@@ -133,8 +131,8 @@ int ensure_state(svo_ctx *ctx, size_t words, size_t groups) {
     int rc = svo_workspace_ensure(ctx, ctx->compact);
     if (rc) return rc;
     svo_compact_state *s = ctx->compact.get();
-    rc = svo_grow(ctx, &s->image_items, words, &s->image);
-    if (!rc) rc = svo_grow(ctx, &s->group_items, groups, &s->order, &s->first_child, &s->new_of, &s->live, &s->number);
+    rc = svo_grow(ctx, words, &s->image);
+    if (!rc) rc = svo_grow(ctx, groups, &s->order, &s->first_child, &s->new_of, &s->live, &s->number);
     return rc;
 }
 

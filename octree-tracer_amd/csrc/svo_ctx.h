@@ -2,11 +2,12 @@
 // use it: svo_abi.cpp (trace / scan dispatch), svo_comm.cpp (RCCL frame gather) and the GPU tree passes (svo_proc.hip,
 // svo_build.hip, svo_edit.hip, svo_compact.hip, svo_list.hip, svo_sample.hip, svo_voxelize.hip, svo_adapt.hip).  One rule
 // of ownership for the context, the node store and every pass's state: a member owns what it holds, as svo_dev /
-// svo_pinned (an allocation), svo_events (events) or svo_stream (a stream).  The passes share the rest as their host
-// frame: svo_grow / svo_grow_pinned / svo_grow_keep (workspaces), svo_mirrored (device words with a pinned mirror),
-// svo_pass_timer (events and times), svo_workspace_ensure (creation) and the svo_check_* argument checks; then the
-// builder's sort and scan and svo_world_writer (a generated world's directory).  svo_scan.h, svo_group.h, svo_mip.h and
-// svo_morton.h hold the device pieces, svo_rules.h the walks and rules that svo_host.cpp and svo_adapt.hip both run.
+// svo_pinned (an allocation and its size), svo_events (events) or svo_stream (a stream).  The passes share the rest as
+// their host frame: svo_grow / svo_grow_pinned / svo_grow_keep (workspaces, by the buffers' own sizes), svo_mirrored
+// (device words with a pinned mirror), svo_pass_timer (events and times), svo_workspace_ensure (creation) and the
+// svo_check_* argument checks; then the builder's sort and scan and svo_world_writer (a generated world's directory).
+// svo_scan.h, svo_group.h, svo_mip.h and svo_morton.h hold the device pieces, svo_rules.h the walks and rules that
+// svo_host.cpp and svo_adapt.hip both run.
 // Internal: not part of the boundary.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -27,21 +28,35 @@
 
 // ---- owning members: what the context, the node store and the passes' states hold their resources in ----
 
-// One device (or pinned host) allocation: freed with its owner, moved but not copied, a T* wherever one is wanted.
+// One device (or pinned host) allocation and its size: freed with its owner, moved but not copied, a T* wherever one is
+// wanted.  size() is the room in items (in bytes of a void buffer); alloc() is the one place that allocates.
 template <typename T, bool kPinned>
 struct svo_mem {
     T *p = nullptr;
+    size_t n = 0;
     svo_mem() = default;
-    svo_mem(svo_mem &&o) noexcept : p(o.p) { o.p = nullptr; }
+    svo_mem(svo_mem &&o) noexcept : p(o.p), n(o.n) { o.p = nullptr, o.n = 0; }
     svo_mem &operator=(svo_mem &&o) noexcept {
         std::swap(p, o.p);
+        std::swap(n, o.n);
         return *this;
     }
     ~svo_mem() { reset(); }
     void reset() {
         if (p) (void)(kPinned ? hipHostFree(p) : hipFree(p));
         p = nullptr;
+        n = 0;
     }
+    // frees what there is, then room for `items`; size() says so only when the allocation succeeded
+    hipError_t alloc(size_t items) {
+        reset();
+        const size_t bytes = items * sizeof(std::conditional_t<std::is_void<T>::value, char, T>);
+        const hipError_t e = kPinned ? hipHostMalloc((void **)&p, bytes, hipHostMallocDefault) : hipMalloc((void **)&p, bytes);
+        if (e == hipSuccess) n = items;
+        else p = nullptr;
+        return e;
+    }
+    size_t size() const { return n; }
     T *get() const { return p; }
     operator T *() const { return p; }
     T *operator->() const { return p; }
@@ -149,15 +164,14 @@ struct svo_ctx {
     bool gathers_issued = false;
     svo_dev<uint32_t> status;          // device error word
     svo_dev<uint32_t> defer_buf;       // {strip counter, deferred count, deferred item indices...}
-    size_t defer_items = 0;
+    size_t defer_items = 0;            // rays per deferred list (the allocation: kCounterWords + 2 * (defer_items + 1) words)
     // scan lists (compute.rs:46-64): slot 0 = count.  One allocation, the subdivide list in its first half
     svo_dev<uint32_t> scan_lists;
-    size_t scan_capacity = 0;
+    size_t scan_capacity = 0;  // words per list: where the second list starts
     uint32_t *scan_sub() const { return scan_lists; }
     uint32_t *scan_unsub() const { return scan_lists + scan_capacity; }
     // device staging for svo_render_host
     svo_dev<char> stage;
-    size_t stage_bytes = 0;
     svo_uniforms uniforms{};
     bool have_uniforms = false;
     // options
@@ -168,7 +182,6 @@ struct svo_ctx {
     bool scan_clears = false;
     int fused_shadows = 2;  // 0: off, 1: on, 2: automatic (see fuse_shadow_rays)
     svo_dev<uint32_t> scatter_buf;  // svo_nodes_scatter: indices, then values
-    size_t scatter_items = 0;
     uint32_t block_w_log2 = 3;  // 64-pixel blocks of 8x8
     uint32_t tree_depth = 16;  // caller's bound on the octree depth (the reference's Settings.octree_depth)
     // scheduling feedback (strip order from an earlier frame of the same work layout); slot 1: shadow rays.  What is decided per
@@ -177,7 +190,7 @@ struct svo_ctx {
         svo::SchedState state;
         svo_dev<uint8_t> cost, cls_now;  // for up to `cap` strips: svo::SchedBuffers says what they hold
         svo_dev<uint32_t> order, balance;
-        size_t cap = 0;
+        size_t cap = 0;  // strips the buffers were sized for
         svo::SchedBuffers buf() const { return {cost, cls_now, order, balance}; }
         svo::WorkDesc key{};  // the work layout of the costs
         // what the schedule was measured on: while camera and tree stay the same it stays exact and is not rebuilt
@@ -199,7 +212,6 @@ struct svo_ctx {
     svo_dev<svo_hit> shade_hits, shade_shadow;
     svo_dev<float> shade_aux, shade_rays;
     svo_dev<uint8_t> shade_skip;
-    size_t shade_hits_items = 0, shade_aux_items = 0, shade_rays_items = 0, shade_shadow_items = 0, shade_skip_items = 0;
     uint32_t *debug_buf = nullptr;  // caller-provided device buffer for the per-wave timeline (diagnostics)
     uint32_t strip_items = 64;
     // launch timing: a ring of (start, stop) event pairs recorded around trace launches
@@ -237,40 +249,34 @@ inline uint32_t svo_div_up(uint64_t n, uint64_t per) { return (uint32_t)((n + pe
 
 // ---- the host frame of a GPU pass: workspaces, status words, the timer, creation, shared checks ----
 
-// Grows a group of buffers to `want` items of its own type each (a void buffer counts bytes): when *have < want, waits
-// for the context's stream, frees all of them and allocates them again; *have becomes `want` only when every allocation
-// succeeded.  svo_grow allocates device memory, svo_grow_pinned pinned host memory.
-template <typename... T>
-int svo_grow_group(svo_ctx *ctx, bool pinned, size_t *have, size_t want, T **...bufs) {
-    if (*have >= want) return SVO_OK;
-    const std::pair<void **, size_t> group[] = {{(void **)bufs, sizeof(std::conditional_t<std::is_void<T>::value, char, T>)}...};
+// Grows a group of buffers to `want` items of its own type each (a void buffer counts bytes): when one of them is
+// smaller, waits for the context's stream, frees all of them and allocates them again.  A failure half way leaves the
+// rest empty, so the next call starts over.  svo_grow takes device buffers, svo_grow_pinned pinned host buffers.
+template <bool kPinned, typename... T>
+int svo_grow_group(svo_ctx *ctx, size_t want, svo_mem<T, kPinned> *...bufs) {
+    if (std::min({bufs->size()...}) >= want) return SVO_OK;
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    for (auto &b : group) {
-        if (*b.first) (void)(pinned ? hipHostFree(*b.first) : hipFree(*b.first));
-        *b.first = nullptr;
-    }
-    *have = 0;
-    for (auto &b : group)
-        HIP_TRY(ctx, pinned ? hipHostMalloc(b.first, want * b.second, hipHostMallocDefault) : hipMalloc(b.first, want * b.second));
-    *have = want;
+    (bufs->reset(), ...);
+    hipError_t group_alloc = hipSuccess;  // (the first failure ends the fold)
+    (void)(... && ((group_alloc = bufs->alloc(want)) == hipSuccess));
+    HIP_TRY(ctx, group_alloc);
     return SVO_OK;
 }
 template <typename... T>
-int svo_grow(svo_ctx *ctx, size_t *have, size_t want, svo_dev<T> *...bufs) { return svo_grow_group(ctx, false, have, want, &bufs->p...); }
+int svo_grow(svo_ctx *ctx, size_t want, svo_dev<T> *...bufs) { return svo_grow_group(ctx, want, bufs...); }
 template <typename... T>
-int svo_grow_pinned(svo_ctx *ctx, size_t *have, size_t want, svo_pinned<T> *...bufs) { return svo_grow_group(ctx, true, have, want, &bufs->p...); }
+int svo_grow_pinned(svo_ctx *ctx, size_t want, svo_pinned<T> *...bufs) { return svo_grow_group(ctx, want, bufs...); }
 
 // svo_grow for one device buffer whose first `keep` items stay: they are copied on the context's stream, which is waited
 // for before the old buffer is freed
 template <typename T>
-int svo_grow_keep(svo_ctx *ctx, size_t *have, size_t want, svo_dev<T> *buf, size_t keep) {
-    if (*have >= want) return SVO_OK;
+int svo_grow_keep(svo_ctx *ctx, size_t want, svo_dev<T> *buf, size_t keep) {
+    if (buf->size() >= want) return SVO_OK;
     svo_dev<T> bigger;
-    HIP_TRY(ctx, hipMalloc((void **)&bigger.p, want * sizeof(T)));
+    HIP_TRY(ctx, bigger.alloc(want));
     if (keep) HIP_TRY(ctx, hipMemcpyAsync(bigger, *buf, keep * sizeof(T), hipMemcpyDeviceToDevice, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     *buf = std::move(bigger);  // (a swap: the old buffer goes with `bigger`)
-    *have = want;
     return SVO_OK;
 }
 
@@ -279,17 +285,15 @@ template <typename T = uint32_t>
 struct svo_mirrored {
     svo_dev<T> dev;
     svo_pinned<T> mirror;
-    size_t n = 0;
     int alloc(svo_ctx *ctx, size_t items) {
-        HIP_TRY(ctx, hipHostMalloc((void **)&mirror.p, items * sizeof(T), hipHostMallocDefault));
-        HIP_TRY(ctx, hipMalloc((void **)&dev.p, items * sizeof(T)));
-        n = items;
+        HIP_TRY(ctx, mirror.alloc(items));
+        HIP_TRY(ctx, dev.alloc(items));
         return SVO_OK;
     }
-    hipError_t zero(svo_ctx *ctx) { return hipMemsetAsync(dev, 0, n * sizeof(T), ctx->stream); }
+    hipError_t zero(svo_ctx *ctx) { return hipMemsetAsync(dev, 0, dev.size() * sizeof(T), ctx->stream); }
     // the first `items` of them (all by default) into the mirror: enqueued by copy(), there after read()
     hipError_t copy(svo_ctx *ctx, size_t items = ~size_t(0)) {
-        return hipMemcpyAsync(mirror, dev, std::min(items, n) * sizeof(T), hipMemcpyDeviceToHost, ctx->stream);
+        return hipMemcpyAsync(mirror, dev, std::min(items, dev.size()) * sizeof(T), hipMemcpyDeviceToHost, ctx->stream);
     }
     int read(svo_ctx *ctx, size_t items = ~size_t(0)) {
         HIP_TRY(ctx, copy(ctx, items));

@@ -202,10 +202,8 @@ struct svo_list_state {
     svo_dev<uint32_t> order, first_child, new_of, scan;  // the discovery's
     svo_dev<uint32_t> rcnt, start, rstart;
     svo_dev<uint64_t> cnt, key;
-    size_t group_items = 0;
     svo_dev<uint32_t> rec_start, rec_value;
     svo_dev<uint64_t> rec_key;
-    size_t rec_items = 0;
     svo_mirrored<> status;  // kStWords words
     svo_pass_timer<kEvs, SVO_LIST_TIMES> timer;
 
@@ -220,7 +218,7 @@ namespace {
 int ensure_state(svo_ctx *ctx, size_t groups) {
     if (int rc = svo_workspace_ensure(ctx, ctx->list)) return rc;
     svo_list_state *s = ctx->list.get();
-    return svo_grow(ctx, &s->group_items, groups, &s->order, &s->first_child, &s->new_of, &s->scan, &s->rcnt, &s->start, &s->rstart,
+    return svo_grow(ctx, groups, &s->order, &s->first_child, &s->new_of, &s->scan, &s->rcnt, &s->start, &s->rstart,
                     &s->cnt, &s->key);
 }
 
@@ -284,7 +282,7 @@ int svo_nodes_list_voxels(svo_ctx *ctx, const svo_list_params *p, uint32_t *xyz_
     HIP_TRY(ctx, s->timer.mark(ctx, kEvCount));
 
     if (xyz_out_dev && count) {
-        if ((rc = svo_grow(ctx, &s->rec_items, (size_t)n_rec, &s->rec_start, &s->rec_value, &s->rec_key))) return rc;
+        if ((rc = svo_grow(ctx, (size_t)n_rec, &s->rec_start, &s->rec_value, &s->rec_key))) return rc;
         // offsets: the levels that have listed levels below them
         for (uint32_t l = 1; l < listed; l++) {
             const uint32_t off = level_off[l - 1], m = level_off[l] - off;

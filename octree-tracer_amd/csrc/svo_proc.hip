@@ -274,15 +274,12 @@ struct svo_proc_state {
     svo_dev<uint8_t> masks;   // levels 0 .. depth-1: child masks, each level zero-padded to whole tiles
     svo_dev<uint32_t> ranks;  // levels 0 .. depth-1: exclusive ranks of the interior nodes
     svo_dev<uint32_t> tiles;  // levels 0 .. depth-1: tile counts, then tile offsets
-    size_t cls_items = 0, mask_items = 0, rank_items = 0, tile_items = 0;  // room in each of the four
     svo_mirrored<> totals;      // interior nodes per level
-    size_t mask_bytes = 0;
+    size_t mask_bytes = 0;  // of `masks`, in use by the layout of `depth`
     uint64_t mask_off[10] = {}, rank_off[10] = {}, tile_off[10] = {};
     uint32_t n_tiles[10] = {};
     svo_dev<uint4> out;  // emitted nodes, 8 bytes each
-    size_t out_items = 0;
     svo_pinned<uint8_t> stage;  // read-back buffer
-    size_t stage_bytes = 0;
     svo_events<4> ev;
     svo_events<2> mev;  // svo_world_generate: around a chunk's device mips
     float ms[SVO_PROC_TIMES] = {};
@@ -332,10 +329,10 @@ int ensure_state(svo_ctx *ctx, uint32_t depth) {
         tb += n / kTile;
     }
     s->mask_bytes = mb;
-    int rc = svo_grow(ctx, &s->cls_items, (size_t)1 << (3 * depth), &s->cls);
-    if (!rc) rc = svo_grow(ctx, &s->mask_items, mb, &s->masks);
-    if (!rc) rc = svo_grow(ctx, &s->rank_items, rb, &s->ranks);
-    if (!rc) rc = svo_grow(ctx, &s->tile_items, tb, &s->tiles);
+    int rc = svo_grow(ctx, (size_t)1 << (3 * depth), &s->cls);
+    if (!rc) rc = svo_grow(ctx, mb, &s->masks);
+    if (!rc) rc = svo_grow(ctx, rb, &s->ranks);
+    if (!rc) rc = svo_grow(ctx, tb, &s->tiles);
     if (rc) return rc;
     s->depth = depth;
     return SVO_OK;
@@ -361,8 +358,8 @@ int svo_proc_sdf(svo_ctx *ctx, const float *xyz, size_t n, float *out) {
     if (n > (1ull << 28)) return svo_fail(ctx, SVO_ERR_ARG, "at most 2^28 points per call");
     if (!n) return SVO_OK;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    float *d = nullptr;
-    HIP_TRY(ctx, hipMalloc((void **)&d, n * 4 * sizeof(float)));
+    svo_dev<float> d;  // the points, then the distances
+    HIP_TRY(ctx, d.alloc(n * 4));
     hipError_t e = hipMemcpyAsync(d, xyz, n * 3 * sizeof(float), hipMemcpyHostToDevice, ctx->stream);
     if (e == hipSuccess) {
         proc_sdf_kernel<<<svo_div_up(n, 256), 256, 0, ctx->stream>>>(d, (uint32_t)n, d + 3 * n);
@@ -370,7 +367,6 @@ int svo_proc_sdf(svo_ctx *ctx, const float *xyz, size_t n, float *out) {
     }
     if (e == hipSuccess) e = hipMemcpyAsync(out, d + 3 * n, n * sizeof(float), hipMemcpyDeviceToHost, ctx->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    (void)hipFree(d);
     return e == hipSuccess ? SVO_OK : svo_fail_hip(ctx, e, "svo_proc_sdf");
 }
 
@@ -442,7 +438,7 @@ int emit_chunk(svo_ctx *ctx, const svo_proc_params *params, double t0, uint64_t 
         return svo_fail(ctx, SVO_ERR_CAP, "chunk needs " + std::to_string(n_nodes) + " nodes, over max_nodes = " +
                                               std::to_string(max_nodes) + " (the reference panics here, procedural.rs:171-172)");
     const size_t bytes = n_nodes * 8;
-    if ((rc = svo_grow(ctx, &s->out_items, bytes / sizeof(uint4), &s->out))) return rc;
+    if ((rc = svo_grow(ctx, bytes / sizeof(uint4), &s->out))) return rc;
     for (uint32_t l = 1; l <= depth; l++) {
         const uint32_t n_par = 1u << (3 * (l - 1));
         const bool last = l == depth;
@@ -461,7 +457,7 @@ int emit_chunk(svo_ctx *ctx, const svo_proc_params *params, double t0, uint64_t 
 // The emitted chunk (and whatever the stream did to it since) into the pinned stage, grown to hold it; blocking.
 int read_stage(svo_ctx *ctx, size_t bytes) {
     svo_proc_state *s = ctx->proc.get();
-    int rc = svo_grow_pinned(ctx, &s->stage_bytes, bytes, &s->stage);
+    int rc = svo_grow_pinned(ctx, bytes, &s->stage);
     if (rc) return rc;
     HIP_TRY(ctx, hipMemcpyAsync(s->stage, s->out, bytes, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));

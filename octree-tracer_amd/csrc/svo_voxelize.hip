@@ -295,15 +295,11 @@ enum Ev { kEvStart, kEvSetup, kEvRefine, kEvCount, kEvEmit, kEvs };
 // Per-context workspace of the voxeliser (svo_ctx::voxelize): nine i32 per triangle, two pair arrays of twelve bytes per
 // pair that take turns, one mask byte per pair, one u32 per tile.
 struct svo_voxelize_state {
-    svo_dev<int32_t> tv;
-    size_t tri_items = 0;  // (i32: nine per triangle)
+    svo_dev<int32_t> tv;  // (i32: nine per triangle)
     svo_dev<uint32_t> pair_tri[2];
     svo_dev<uint64_t> pair_cell[2];
-    size_t pair_items[2] = {};
     svo_dev<uint8_t> mask;
-    size_t mask_items = 0;
     svo_dev<uint32_t> tiles;
-    size_t tile_items = 0;
     svo_mirrored<> status;  // kStWords words
     svo_pass_timer<kEvs, SVO_VOXELIZE_TIMES> timer;
 
@@ -342,9 +338,9 @@ int svo_mesh_voxelize(svo_ctx *ctx, const svo_voxelize_params *p, const uint32_t
 
     // setup: the check, the gather, the root pairs
     const uint32_t n_blocks = svo_div_up(n, kThreads);
-    if ((rc = svo_grow(ctx, &s->tri_items, 9 * (size_t)n, &s->tv))) return rc;
-    if ((rc = svo_grow(ctx, &s->pair_items[0], (size_t)n, &s->pair_tri[0], &s->pair_cell[0]))) return rc;
-    if ((rc = svo_grow(ctx, &s->tile_items, (size_t)n_blocks, &s->tiles))) return rc;
+    if ((rc = svo_grow(ctx, 9 * (size_t)n, &s->tv))) return rc;
+    if ((rc = svo_grow(ctx, (size_t)n, &s->pair_tri[0], &s->pair_cell[0]))) return rc;
+    if ((rc = svo_grow(ctx, (size_t)n_blocks, &s->tiles))) return rc;
     HIP_TRY(ctx, s->timer.mark(ctx, kEvStart));
     vox_setup_kernel<<<n_blocks, kThreads, 0, ctx->stream>>>(vq_dev, p->n_vertices, tri_dev, n, depth, s->tv, s->pair_tri[0],
                                                              s->pair_cell[0], s->tiles);
@@ -356,8 +352,8 @@ int svo_mesh_voxelize(svo_ctx *ctx, const svo_voxelize_params *p, const uint32_t
     for (uint32_t l = 1; l <= depth; l++) {
         if (l == depth) HIP_TRY(ctx, s->timer.mark(ctx, kEvRefine));
         const uint32_t n_tiles = svo_div_up(m, kTile), hs = depth - l + SVO_VOX_SUBBITS;
-        if ((rc = svo_grow(ctx, &s->mask_items, size_t(n_tiles) * kTile, &s->mask))) return rc;
-        if ((rc = svo_grow(ctx, &s->tile_items, (size_t)n_tiles, &s->tiles))) return rc;
+        if ((rc = svo_grow(ctx, size_t(n_tiles) * kTile, &s->mask))) return rc;
+        if ((rc = svo_grow(ctx, (size_t)n_tiles, &s->tiles))) return rc;
         vox_test_kernel<<<svo_div_up(m, kThreads), kThreads, 0, ctx->stream>>>(s->tv, s->pair_tri[cur], s->pair_cell[cur], m, hs, s->mask);
         vox_sum_kernel<<<n_tiles, kThreads, 0, ctx->stream>>>(s->mask, m, s->tiles);
         vox_total_kernel<<<1, kTopThreads, 0, ctx->stream>>>(s->tiles, n_tiles, s->status.dev);
@@ -379,7 +375,7 @@ int svo_mesh_voxelize(svo_ctx *ctx, const svo_voxelize_params *p, const uint32_t
         out.room = (uint32_t)count;
         if (l < depth) {
             const uint32_t next = cur ^ 1u;
-            if ((rc = svo_grow(ctx, &s->pair_items[next], (size_t)count, &s->pair_tri[next], &s->pair_cell[next]))) return rc;
+            if ((rc = svo_grow(ctx, (size_t)count, &s->pair_tri[next], &s->pair_cell[next]))) return rc;
             out.pair_tri = s->pair_tri[next];
             out.pair_cell = s->pair_cell[next];
             vox_scatter_kernel<false><<<n_tiles, kThreads, 0, ctx->stream>>>(s->pair_tri[cur], s->pair_cell[cur], s->mask, m, s->tiles, out);

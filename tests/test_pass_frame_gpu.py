@@ -8,7 +8,13 @@ import numpy as np
 import pytest
 
 import build_ref as B
+import compact_ref as C
+import edit_ref as E
+import list_ref as L
+import sample_ref as S
+import voxelize_ref as V
 from conftest import assert_hits_equal, set_uniforms_from_oracle
+from pass_frame import assert_words
 
 pytestmark = pytest.mark.gpu
 
@@ -58,6 +64,64 @@ def test_every_pass_on_one_context_then_close(pkg):
         assert np.array_equal(render.read_nodes(), built)
     finally:
         second.close()
+
+
+def _pass_case(pkg, seed, n, depth, subdivisions):
+    """n random voxels at `depth` (distinct when seed is odd), an edit that removes an eighth of them and puts as many,
+    cells to sample and an icosphere, with every pass's reference result"""
+    rng = np.random.default_rng(seed)
+    side = 1 << depth
+    cells = rng.choice(side ** 3, n, replace=False) if seed & 1 else rng.integers(0, side ** 3, n)
+    coords = np.stack(np.unravel_index(cells, (side,) * 3), axis=1)
+    colours = rng.integers(1, 1 << 24, n)
+    ec = np.concatenate([coords[:n // 8], rng.integers(0, side, (n // 8, 3))])  # an eighth goes, as many come
+    ecol = np.concatenate([np.zeros(n // 8, dtype=np.int64), rng.integers(1, 1 << 24, n // 8)])
+    built = B.build(coords, depth, colours)
+    edited = E.edit(built, built.size, ec, depth, ecol)
+    compacted = C.compact(edited, edited.size, True)[0]
+    listed = L.list_voxels(compacted, compacted.size, depth)
+    probes = np.concatenate([listed[0].astype(np.int64), rng.integers(0, side + 2, (64, 3))])
+    v, t = pkg.mesh.icosphere(subdivisions, 0.5)
+    return {"depth": depth, "coords": coords, "colours": colours, "edit": (ec, ecol), "built": built, "edited": edited,
+            "compacted": compacted, "listed": listed, "probes": probes, "sampled": S.sample(compacted, compacted.size, probes, depth)[0],
+            "mesh": (v, t), "voxelized": V.voxelize(pkg.mesh.quantize_vertices(v, depth), t, depth)}
+
+
+def test_pass_workspaces_grow_and_shrink_back_on_one_context(pkg):
+    """One context builds, edits, compacts, lists, samples and voxelises a small input (40 voxels at depth 4, an
+    icosahedron), then one that passes a scan tile of 4096 items in voxels, groups and triangle-cell pairs (5000 distinct
+    voxels and icosphere(3) at depth 6), so the grouped buffers and the tile sums reallocate, then the small one again
+    in the larger buffers.  Every result is its reference's."""
+    import torch
+    if not torch.cuda.is_available():
+        pytest.skip("no GPU")
+    small, large = _pass_case(pkg, 40, 40, 4, 0), _pass_case(pkg, 41, 5000, 6, 3)
+    assert large["built"].size // 8 > 4096 and large["voxelized"][1].size > 4096 > small["voxelized"][1].size
+
+    def u32(tensor):
+        return tensor.cpu().numpy().view(np.uint32)
+
+    gpu = pkg.Gpu(0)
+    try:
+        render = pkg.Render(gpu, (8, 8), ROOT, capacity=1 << 18)
+        for step, case in enumerate((small, large, small)):
+            what, depth = f"input {step}", case["depth"]
+            render.write_nodes(ROOT)
+            assert render.build_nodes(case["coords"], depth, case["colours"]) == case["built"].size, what
+            assert_words(render.read_nodes(), case["built"], f"{what}: built")
+            assert render.edit_nodes(case["edit"][0], depth, case["edit"][1]) == case["edited"].size, what
+            assert_words(render.read_nodes(), case["edited"], f"{what}: edited")
+            assert render.compact_nodes() == case["compacted"].size, what
+            assert_words(render.read_nodes(), case["compacted"], f"{what}: compacted")
+            coords, colours, levels = render.list_voxels(depth, with_levels=True)
+            for got, want in zip((coords, colours, levels), case["listed"]):
+                assert np.array_equal(u32(got), want), f"{what}: listed"
+            assert np.array_equal(u32(render.sample_voxels(case["probes"], depth)), case["sampled"]), f"{what}: sampled"
+            got = pkg.mesh.voxelize(gpu, *case["mesh"], depth, with_triangles=True)
+            for g, want in zip(got, case["voxelized"]):
+                assert np.array_equal(u32(g), want), f"{what}: voxelised"
+    finally:
+        gpu.close()
 
 
 def _frames(pkg, gpu, render, n=2):
