@@ -141,6 +141,10 @@ typedef enum svo_option {
                                 for strips with one such strip among their 24 neighbours: 3 - 5 % off a moving camera's frame).  When the
                                 camera comes to rest the lists are rebuilt once more from the classes as measured.
                                 Results do not depend on it. */
+    SVO_OPT_STATIC_DEAL = 17, /* resting views (same camera, tree and layout, plain pixel frames of the STACK variant, lists settled):
+                                which wave traces which strips is written down once and replayed without claims, then improved from
+                                per-wave time stamps over 16 frames; a view whose replay never beat its claims goes back to claiming.
+                                1 (default) on, 0 off.  Results do not depend on it. */
     SVO_OPT_PRIO_STEPS = 6   /* accepted and ignored: raising the issue priority of waves with old rays measured no effect and
                                 left the kernel */
 } svo_option;
@@ -279,6 +283,15 @@ int svo_diag_gather(svo_ctx *ctx, uint32_t stride_bytes, uint32_t n_loads);
  * the last pixel frame that ran the pass (block b of a width x height rectangle, 8x8 blocks row-major; 0xFF = culled: the pass
  * wrote the block's all-zero records and the trace never claimed it).  Blocking; SVO_ERR_STATE when that frame ran without it. */
 int svo_diag_strip_classes(svo_ctx *ctx, uint8_t *host_out, size_t n_strips);
+
+/* Diagnostic for the static deal (SVO_OPT_STATIC_DEAL), read-only and blocking.  status_out: frames traced by the replay kernel,
+ * seeds asked for by the host, seeds and strips moved on the device, learning frames stepped since the last seed (16: over),
+ * verdict (0 learning, 1 replay, 2 claims), table seeded (0/1), host knows "claims" (0/1), rows, entries per row, best replayed
+ * frame (10 ns ticks: all waves; the sampled workgroups), the claiming kernel's last frame, the last stepped frame and its
+ * moves, frames that still get a step.  table_out / stamps_out (or NULL): the first table_words words of the table (rows x
+ * entries per row, 0xFFFFFFFF behind a row's last strip) and the first stamps_words of the per-wave stamps (2 per row). */
+int svo_diag_deal(svo_ctx *ctx, uint32_t status_out[16], uint32_t *table_out, size_t table_words, uint32_t *stamps_out,
+                  size_t stamps_words);
 
 /* Counter scan (compute.wgsl).  Lists hold `capacity` words: slot 0 = count, slots 1.. = indices. */
 int svo_scan_dispatch(svo_ctx *ctx, uint32_t node_length);

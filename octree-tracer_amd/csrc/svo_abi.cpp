@@ -197,16 +197,86 @@ int schedule_before(svo_ctx *ctx, svo_ctx::Sched &sc, const svo::FrameFacts &f, 
     return SVO_OK;
 }
 
+// A resting view's static deal, before the trace (svo_deal.h: deal_before_trace): the frame's facts, the buffers and the seed when
+// the plan asks for one, and the table in the launch arguments when the replay kernel traces this frame.  Called with the launch
+// as it will be made, after schedule_before.
+int deal_before(svo_ctx *ctx, svo_ctx::Sched &sc, const svo::FrameFacts &ff, svo::TraceArgs &a, const svo::LaunchInfo &li, int sched_slot,
+                svo::DealPlan &plan) {
+    svo_ctx::Sched::DealBuffers &db = sc.deal;
+    svo::DealFacts f;
+    f.enabled = ctx->static_deal;
+    f.plain_static = sched_slot == 0 && a.work.mode != 2 && a.hits && !a.skip && !a.count_nodes && !a.shadow_hits && !a.debug && !li.deep_stack;
+    f.stored_lists = ff.schedule && !ff.filtered && a.order != nullptr && a.balance != nullptr;
+    f.at_rest = sc.built_nodes_version == ctx->store->version && memcmp(&sc.built_uniforms, &ctx->uniforms, sizeof(svo_uniforms)) == 0;
+    f.balance_frames = sc.state.balance_frames;
+    if (f.enabled && f.plain_static && f.stored_lists && f.at_rest) {
+        svo::LaunchInfo ask = li;
+        ask.blocks_out = &f.grid_blocks;
+        HIP_TRY(ctx, svo::launch_trace(a, ask, ctx->stream));
+        f.row_cap = svo::deal_row_cap(a.order_cap, f.grid_blocks);
+    }
+    if (db.seen_pending && hipEventQuery(db.seen_ev[0]) == hipSuccess) {  // (never waited for: not there yet = not seen yet)
+        db.seen_pending = false;
+        f.seen_fresh = true;
+        f.seen_step = db.seen[svo::kDealStep];
+        f.seen_verdict = db.seen[svo::kDealVerdict];
+    }
+    (void)hipGetLastError();  // (hipErrorNotReady is no error)
+    const bool claimed_before = !db.last_replayed;
+    plan = svo::deal_before_trace(db.state, f);
+    db.last_replayed = plan.replay;
+    if (plan.seed) {
+        const size_t rows = (size_t)f.grid_blocks * 4;
+        if (int rc = svo_grow(ctx, rows * f.row_cap, &db.table)) return rc;
+        if (int rc = svo_grow(ctx, rows, &db.len)) return rc;
+        if (int rc = svo_grow(ctx, svo::deal_log_words(f.grid_blocks), &db.log)) return rc;
+        if (int rc = svo_grow(ctx, sc.order.size(), &db.lists)) return rc;
+        if (db.stamps.size() < 2 * rows) {
+            if (int rc = svo_grow(ctx, 2 * rows, &db.stamps)) return rc;
+            HIP_TRY(ctx, hipMemsetAsync(db.stamps, 0, db.stamps.size() * sizeof(uint32_t), ctx->stream));
+        }
+        if (!db.words) {
+            HIP_TRY(ctx, db.words.alloc(svo::kDealStateWords));
+            HIP_TRY(ctx, db.seen.alloc(svo::kDealStateWords));
+            HIP_TRY(ctx, db.seen_ev.create(hipEventDisableTiming));
+            HIP_TRY(ctx, hipMemsetAsync(db.words, 0, svo::kDealStateWords * sizeof(uint32_t), ctx->stream));
+            memset(db.seen, 0, svo::kDealStateWords * sizeof(uint32_t));
+        }
+        HIP_TRY(ctx, svo::launch_deal_seed(db.view(a.order_cap, ctx->deal_pairs_div), sc.order, claimed_before ? sc.balance.get() : nullptr, ctx->stream));
+    }
+    if (plan.replay) {
+        a.deal_table = db.table;
+        a.deal_row_cap = db.state.row_cap;
+        a.deal_stamps = db.stamps;
+    }
+    return SVO_OK;
+}
+
 // After a STACK trace (svo_sched.h: plan_after_trace): the post pass -- deferred rays, counter re-arm, and what the plan measures
-// and builds for the next frames.
+// and builds for the next frames; then the deal's step on a learning frame, and its compare when the lists were rebuilt.
 int schedule_after(svo_ctx *ctx, svo_ctx::Sched &sc, svo::FrameFacts &f, const svo::TraceArgs &a, const svo::LaunchInfo &li,
-                   int sched_slot) {
+                   int sched_slot, const svo::DealPlan &deal) {
     // (caller-supplied rays cannot be compared: they always count as moving)
     f.same_input = (a.work.mode != 2 || sched_slot == 1) && sc.built_nodes_version == ctx->store->version &&
                    memcmp(&sc.built_uniforms, &ctx->uniforms, sizeof(svo_uniforms)) == 0;
     f.moving = sc.have_prev && memcmp(&sc.prev_uniforms, &ctx->uniforms, sizeof(svo_uniforms)) != 0;
-    const svo::PostPlan plan = svo::plan_after_trace(sc.state, f);
+    svo::PostPlan plan = svo::plan_after_trace(sc.state, f);
+    // a replayed frame's times are its deal's, not its lists': they do not step the shares (the lists the schedule's backstop
+    // rebuilds from the same input are then the same lists, and the deal is kept)
+    if (deal.replay) plan.balance_update = 0u;
     HIP_TRY(ctx, svo::launch_post(a, li, plan, sc.buf(), ctx->stream));
+    if (sched_slot == 0) {
+        svo_ctx::Sched::DealBuffers &db = sc.deal;
+        const svo::Deal view = db.view(a.order_cap, ctx->deal_pairs_div);
+        if (deal.step) HIP_TRY(ctx, svo::launch_deal_step(view, sc.balance, ctx->stream));
+        bool mirror = false;
+        if (svo::deal_after_post(db.state, deal, plan.build_lists, mirror)) HIP_TRY(ctx, svo::launch_deal_compare(view, sc.order, ctx->stream));
+        if (mirror) {
+            HIP_TRY(ctx, hipMemcpyAsync(db.seen, db.words, svo::kDealStateWords * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+            HIP_TRY(ctx, hipEventRecord(db.seen_ev[0], ctx->stream));
+            db.seen_pending = true;
+        }
+    }
     sc.prev_uniforms = ctx->uniforms;
     sc.have_prev = true;
     if (plan.rebuild) {
@@ -291,6 +361,11 @@ int trace_launch(svo_ctx *ctx, const svo::WorkDesc &work, const float *rays, svo
         li.defer = lists + (ctx->frame_parity ? stride : 0);
         li.next_defer_count = lists + (ctx->frame_parity ? 0 : stride);
     }
+    svo::DealPlan deal;
+    if (stack) {
+        rc = deal_before(ctx, sc, f, a, li, opt.sched_slot, deal);
+        if (rc) return rc;
+    }
     const size_t slot = ctx->ev_slots ? (ctx->ev_count % ctx->ev_slots) : 0;
     const bool timed = ctx->ev_slots && opt.sched_slot == 0;  // the timing ring records the primary trace launches
     if (timed) HIP_TRY(ctx, hipEventRecord(ctx->ev[slot][0], ctx->stream));
@@ -300,7 +375,7 @@ int trace_launch(svo_ctx *ctx, const svo::WorkDesc &work, const float *rays, svo
         ctx->ev_count++;
     }
     if (!stack) return SVO_OK;
-    rc = schedule_after(ctx, sc, f, a, li, opt.sched_slot);  // deferred rays, scheduling feedback for the next frames, counter re-arm
+    rc = schedule_after(ctx, sc, f, a, li, opt.sched_slot, deal);  // deferred rays, scheduling feedback for the next frames, counter re-arm
     if (rc) return rc;
     ctx->frame_parity ^= 1;
     return SVO_OK;
@@ -554,6 +629,10 @@ int svo_ctx_create(int hip_device, svo_ctx **out) {
     if (!ctx) return SVO_ERR_HIP;
     ctx->device = hip_device;
     ctx->list_balance = getenv("SVO_NO_LIST_BALANCE") == nullptr;
+    if (const char *div = getenv("SVO_DEAL_PAIRS_DIV")) {  // (A/B switch of the deal's step: pairs = a list's waves / this)
+        const long v = strtol(div, nullptr, 10);
+        if (v >= 2 && v <= 1024) ctx->deal_pairs_div = (uint32_t)v;
+    }
     hipError_t e = hipSetDevice(hip_device);
     hipDeviceProp_t prop;
     if (e == hipSuccess) e = hipGetDeviceProperties(&prop, hip_device);
@@ -668,6 +747,10 @@ int svo_set_option(svo_ctx *ctx, int option, int64_t value) {
         case SVO_OPT_PRIO_STEPS:
             if (value < 0 || value > 255) return svo_fail(ctx, SVO_ERR_ARG, "prio_steps must be 0..255");
             return SVO_OK;  // (no longer used)
+        case SVO_OPT_STATIC_DEAL:
+            if (value < 0 || value > 1) return svo_fail(ctx, SVO_ERR_ARG, "static deal: 0 (off) or 1 (on)");
+            ctx->static_deal = value != 0;  // (off: the next frame drops the table, svo_deal.h)
+            return SVO_OK;
         default:
             return svo_fail(ctx, SVO_ERR_ARG, "unknown option");
     }
@@ -941,6 +1024,25 @@ int svo_diag_gather(svo_ctx *ctx, uint32_t stride_bytes, uint32_t n_loads) {
     int rc = bind(ctx);
     if (rc) return rc;
     HIP_TRY(ctx, svo::launch_diag_gather(ctx->nodes, (uint32_t)ctx->capacity, stride_bytes / 4, n_loads, ctx->status, ctx->stream));
+    return SVO_OK;
+}
+
+int svo_diag_deal(svo_ctx *ctx, uint32_t status_out[16], uint32_t *table_out, size_t table_words, uint32_t *stamps_out, size_t stamps_words) {
+    if (!ctx || !status_out) return SVO_ERR_ARG;
+    int rc = bind(ctx);
+    if (rc) return rc;
+    const svo_ctx::Sched::DealBuffers &db = ctx->sched[0].deal;
+    uint32_t words[svo::kDealStateWords] = {};
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    if (db.words) HIP_TRY(ctx, hipMemcpy(words, db.words, sizeof words, hipMemcpyDeviceToHost));
+    const uint32_t rows = db.state.seeded ? db.state.grid_blocks * 4u : 0u;
+    const uint32_t out[16] = {(uint32_t)db.state.replayed, (uint32_t)db.state.seeds, words[svo::kDealSeeds], words[svo::kDealMoves],
+                              words[svo::kDealStep], words[svo::kDealVerdict], db.state.seeded, db.state.claims, rows, db.state.row_cap,
+                              words[svo::kDealBestTime], words[svo::kDealBestSample], words[svo::kDealClaimTime], words[svo::kDealLastTime],
+                              words[svo::kDealLastMoves], db.state.learn_left};
+    memcpy(status_out, out, sizeof out);
+    if (table_out && rows) HIP_TRY(ctx, hipMemcpy(table_out, db.table, std::min(table_words, (size_t)rows * db.state.row_cap) * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (stamps_out && rows) HIP_TRY(ctx, hipMemcpy(stamps_out, db.stamps, std::min(stamps_words, (size_t)rows * 2) * sizeof(uint32_t), hipMemcpyDeviceToHost));
     return SVO_OK;
 }
 

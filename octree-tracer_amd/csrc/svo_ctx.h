@@ -22,6 +22,7 @@
 #include <utility>
 #include <vector>
 
+#include "svo_deal.h"
 #include "svo_device.h"
 #include "svo_hip.h"
 #include "svo_host.h"
@@ -76,6 +77,10 @@ struct svo_events {
         for (int k = 0; k < N; k++) e[k] = o.e[k], o.e[k] = nullptr;
     }
     svo_events &operator=(const svo_events &) = delete;
+    svo_events &operator=(svo_events &&o) noexcept {
+        for (int k = 0; k < N; k++) std::swap(e[k], o.e[k]);
+        return *this;
+    }
     ~svo_events() { reset(); }
     void reset() {
         for (hipEvent_t &x : e) {
@@ -199,10 +204,27 @@ struct svo_ctx {
         // camera motion (SVO_OPT_SCHEDULE_MOTION): the uniforms of the previous frame
         svo_uniforms prev_uniforms{};
         bool have_prev = false;
+        // a resting view's static deal (svo_deal.h; slot 0 only): the table the replay kernel reads, its rows' lengths, the steps' move log, the lists
+        // it was seeded from, the waves' stamps and the state words, with a pinned copy of those that the host looks at when
+        // it has arrived (seen_ev) and never waits for
+        struct DealBuffers {
+            svo::DealState state;
+            svo_dev<uint32_t> table, len, log, lists, stamps, words;
+            svo_pinned<uint32_t> seen;
+            svo_events<1> seen_ev;
+            bool seen_pending = false;
+            bool last_replayed = false;  // the frame before this one was traced by the replay kernel
+            svo::Deal view(uint32_t order_cap, uint32_t pairs_div) const {
+                return {table, len, log, lists, stamps, words, state.row_cap, state.grid_blocks, order_cap, pairs_div};
+            }
+        };
+        DealBuffers deal;
         hipError_t alloc(uint32_t n_strips);  // frees what there is and starts the slot over (svo_abi.cpp)
         void release() { *this = Sched{}; }  // (the buffers go with the temporary)
     };
     Sched sched[2];
+    bool static_deal = true;   // SVO_OPT_STATIC_DEAL
+    uint32_t deal_pairs_div = svo::kDealPairsDiv;  // (SVO_DEAL_PAIRS_DIV: the sweep of tools/deal_probe.py)
     bool list_balance = true;  // unless SVO_NO_LIST_BALANCE is set (A/B switch of the list-share feedback, svo_kernels.hip: balance_step)
     uint32_t motion_floor = 0x1204;  // SVO_OPT_SCHEDULE_MOTION: class floor | radius << 8 | min_count << 12; 0 = off
     bool schedule = true;

@@ -68,6 +68,11 @@ struct TraceArgs {
                                 // records when its first wave started (kBalanceStart) and when a sample of every list's workgroups ended, 10 ns ticks
     svo_hit *shadow_hits;       // STACK, optional (fused shadow rays): the lane that finishes a primary ray with a hit goes on with that
                                 // pixel's shadow ray (shader.wgsl:275-280) and writes its record here; pixels without one get zeros
+    // STACK, optional (a resting view's static deal, svo_deal.h): non-null = the replay kernel traces this frame, wave w the strips of
+    // row w of the table (deal_row_cap entries a row, 0xFFFFFFFF behind the last) and leaves two stamps in slot w of deal_stamps
+    const uint32_t *deal_table;
+    uint32_t deal_row_cap;
+    uint32_t *deal_stamps;      // per wave: when it began its last strip, when it ended (10 ns ticks)
 };
 
 struct LaunchInfo {
@@ -80,6 +85,7 @@ struct LaunchInfo {
     uint32_t *counters;      // STACK: kCounterWords claim-counter words, zero when a frame starts
     uint32_t *defer;         // STACK: this frame's deferred list: count, then one slot per item handed to RESTART
     uint32_t *next_defer_count;  // STACK: count word of the other list (lists alternate between frames)
+    uint32_t *blocks_out;    // STACK, optional (host): launch nothing, only say how many workgroups this frame's trace kernel gets
 };
 
 hipError_t launch_build_top_table(const uint32_t *nodes, uint32_t n_words, uint32_t *top_table,
@@ -117,6 +123,14 @@ struct SchedBuffers {
 hipError_t launch_post(const TraceArgs &args, const LaunchInfo &li, const PostPlan &plan, const SchedBuffers &buf, hipStream_t stream);
 // svo_sched.hip: launch_post's list build (args.order_cap entries per list, shares from args.balance)
 hipError_t launch_build_lists(const TraceArgs &args, uint32_t motion_floor, const SchedBuffers &buf, hipStream_t stream);
+
+// svo_deal.hip: a resting view's static deal (svo_deal.h), one workgroup each on `stream`: seed the table from the stored lists (bal: the
+// balance words the claiming kernel left the frame before);
+// step it after a replayed frame (bal: the schedule's balance words); re-seed it if the rebuilt lists are not the ones it came from
+struct Deal;
+hipError_t launch_deal_seed(const Deal &d, const uint32_t *order, const uint32_t *bal, hipStream_t stream);
+hipError_t launch_deal_step(const Deal &d, const uint32_t *bal, hipStream_t stream);
+hipError_t launch_deal_compare(const Deal &d, const uint32_t *order, hipStream_t stream);
 
 // explicit rays with a skip mask (args.skip): this frame's strip lists without the strips that hold no ray (classes from `prev`, or
 // screen order)

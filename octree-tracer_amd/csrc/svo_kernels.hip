@@ -315,9 +315,13 @@ struct StackLds {
 #endif
 
 // CNT: hit counters live (adaptive mode, shader.wgsl:157-161), see step 3a in the loop.
-template <int BLOCK, int NS, int K, bool GE, bool DBG, bool CNT, bool SHD>
-__global__ __launch_bounds__(BLOCK, NS > 12 ? 4 : (CNT ? SVO_WAVES_PER_SIMD_CNT : ((SHD || (DBG && SVO_DBG_LIGHT == 0)) ? 6 : SVO_WAVES_PER_SIMD))) void trace_stack_kernel(TraceArgs a, uint32_t strip_items,
-                                                               uint32_t *work_counter, uint32_t *defer) {
+// The body of both trace kernels (they follow it): trace_stack_kernel claims its strips from the lists' counters, REPLAY = false;
+// trace_stack_replay_kernel reads them from the wave's row of a deal table (svo_deal.h), REPLAY = true -- the claim code
+// (the reserved first entry, the atomics, the probe of the 64 counters, entry_of and home) is compiled out, work_counter is not read,
+// and the wave leaves two time stamps for the deal's step.  Everything else is the same text.
+template <int BLOCK, int NS, int K, bool GE, bool DBG, bool CNT, bool SHD, bool REPLAY>
+__device__ __forceinline__ void trace_stack_body(const TraceArgs &a, uint32_t strip_items, uint32_t *work_counter, uint32_t *defer) {
+    static_assert(!REPLAY || (!DBG && !CNT && !SHD), "the replay kernel exists for the plain static frame only");
     constexpr bool DBGH = DBG && SVO_DBG_LIGHT == 0;  // the timeline build's phase clocks and tallies (the light build keeps the time stamps only)
     constexpr int D = kPathBits;
     constexpr int SBASE = K + 2;       // first level kept on the LDS stack
@@ -515,7 +519,8 @@ __global__ __launch_bounds__(BLOCK, NS > 12 ? 4 : (CNT ? SVO_WAVES_PER_SIMD_CNT 
     // (Wave-uniform state, kept small -- the kernel sits at the limit of its scalar registers, and what does not fit there
     // ends up in scratch memory, inside the hot loop: `next` == 0xFFFFFFFE says that a claim is in flight, 0xFFFFFFFF that
     // the frame has no more strips for this wave.  The stealing code exists once, in the refill step.)
-    uint32_t home = (blockIdx.x % kShards) * kSubs + (blockIdx.x / kShards) % kSubs;  // the claim counter (list * kSubs + counter) this wave draws from
+    // (REPLAY: home is the position in the wave's row of the entry asked for last, pend that entry itself, wave-uniform)
+    uint32_t home = REPLAY ? 0u : (blockIdx.x % kShards) * kSubs + (blockIdx.x / kShards) % kSubs;  // the claim counter (list * kSubs + counter) this wave draws from
     uint32_t pend = 0;                // lane 0: what the atomic returned
     uint32_t next, strip_end;
     auto entry_of = [=](uint32_t sh, uint32_t k) -> uint32_t {  // strip behind entry k of list sh (0xFFFFFFFF: past the end)
@@ -526,7 +531,17 @@ __global__ __launch_bounds__(BLOCK, NS > 12 ? 4 : (CNT ? SVO_WAVES_PER_SIMD_CNT 
         const uint32_t cand = (((k >> 4) * kShards + sh) << 4) | (k & 15u);
         return cand < n_strips ? cand : 0xFFFFFFFFu;
     };
-    {
+    // the wave's row of the deal table: strips in the order it traces them, 0xFFFFFFFF behind the last (read-only for the launch)
+    // (the load is all the caller pays for: like a claim's answer, the entry is looked at -- readfirstlane -- only when it is needed)
+    auto row_entry = [=](uint32_t j) -> uint32_t {
+        const TraceArgs &fa = fresh_args();
+        return fa.deal_table[wave_id * fa.deal_row_cap + j];
+    };
+    if (REPLAY) {
+        const uint32_t s0 = __builtin_amdgcn_readfirstlane(row_entry(0u));
+        next = s0 != 0xFFFFFFFFu ? s0 * strip_items : 0xFFFFFFFFu;  // (an empty row: the frame has nothing for this wave)
+        strip_end = s0 != 0xFFFFFFFFu ? min(next + strip_items, n_items) : 0xFFFFFFFFu;
+    } else {
         const uint32_t my_rank = (blockIdx.x / kShards) * (uint32_t)(BLOCK / 64) + __builtin_amdgcn_readfirstlane(tid >> 6);  // among the waves that start on my list
         const uint32_t s0 = __builtin_amdgcn_readfirstlane(entry_of(blockIdx.x % kShards, my_rank));
         if (s0 != 0xFFFFFFFFu) {
@@ -934,14 +949,15 @@ __global__ __launch_bounds__(BLOCK, NS > 12 ? 4 : (CNT ? SVO_WAVES_PER_SIMD_CNT 
                     dbg_desc_rounds += (uint32_t)(__builtin_amdgcn_s_memtime() - c_w0);
                 }
                 uint32_t lst = home / kSubs;
-                uint32_t s = entry_of(lst, __builtin_amdgcn_readfirstlane(pend) * kSubs + home % kSubs + ((gridDim.x + kShards - 1u - lst) / kShards) * (uint32_t)(BLOCK / 64));
+                // (REPLAY: the answer is the row's next entry, asked for when the last strip became pool rays; nothing to probe or steal)
+                uint32_t s = REPLAY ? pend : entry_of(lst, __builtin_amdgcn_readfirstlane(pend) * kSubs + home % kSubs + ((gridDim.x + kShards - 1u - lst) / kShards) * (uint32_t)(BLOCK / 64));
                 // The home counter ran out: lane i looks at counter i -- one load for all 64 -- and the wave draws from the first
                 // counter that still has entries, starting behind its own (the other counters of its list, then list by list), and
                 // makes that counter its home: later claims from it are issued ahead of time again (frames whose lists differ
                 // much in length -- secondary rays of the pixels that hit something -- would otherwise pay two round trips per
                 // strip).  Probing the counters one atomic after the other would cost a finished wave 64 round trips to find
                 // out that the frame is over.
-                while (s == 0xFFFFFFFFu) {
+                while (!REPLAY && s == 0xFFFFFFFFu) {
                     if (DBG && !DBGH && lane == 0u) dbg_desc_iters += 1u;  // (light timeline build, slot 12: probes of the 64 claim counters)
                     const uint32_t l = lane / kSubs;
                     const uint32_t cv = __hip_atomic_load(work_counter + lane * kShardStride, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -966,7 +982,7 @@ __global__ __launch_bounds__(BLOCK, NS > 12 ? 4 : (CNT ? SVO_WAVES_PER_SIMD_CNT 
                 // the counters advance together and the list is consumed front to back, as with one counter (waves tied to one
                 // counter let the counters drift apart: a group of waves that got long strips leaves its share of the list's
                 // front -- long strips -- for the end; 4K frames with fused shadow rays lost 25 %)
-                home = (home & ~(kSubs - 1u)) | ((home + 1u) & (kSubs - 1u));
+                if (!REPLAY) home = (home & ~(kSubs - 1u)) | ((home + 1u) & (kSubs - 1u));
                 s = __builtin_amdgcn_readfirstlane(s);
                 next = s != 0xFFFFFFFFu ? s * strip_items : 0xFFFFFFFFu;
                 strip_end = s != 0xFFFFFFFFu ? min(next + strip_items, n_items) : 0xFFFFFFFFu;
@@ -985,6 +1001,9 @@ __global__ __launch_bounds__(BLOCK, NS > 12 ? 4 : (CNT ? SVO_WAVES_PER_SIMD_CNT 
                     const uint64_t c_g0 = DBGH ? __builtin_amdgcn_s_memtime() : 0ull;
                     // -- generate the next (up to) 64 rays, all lanes --
                     const TraceArgs &a = fresh_args();  // (shadows the parameter: see fresh_args)
+                    // (REPLAY, stamp 0 of the wave's slot: when it began to generate a strip -- the last one written is its last strip's;
+                    // a plain store, like the end stamp below)
+                    if (REPLAY && lane == 0u) a.deal_stamps[2u * wave_id] = (uint32_t)__builtin_amdgcn_s_memrealtime();
                     const uint32_t q = next + lane;
                     bool alive = false;
                     float gp0 = 0, gp1 = 0, gp2 = 0, gd0 = 1, gd1 = 1, gd2 = 1, gdist = 0;
@@ -1040,7 +1059,12 @@ __global__ __launch_bounds__(BLOCK, NS > 12 ? 4 : (CNT ? SVO_WAVES_PER_SIMD_CNT 
                     pool_i = 0u;
                     next += min(64u, strip_end - next);
                     if (next >= strip_end) {
-                        if (lane == 0) pend = atomicAdd(work_counter + home * kShardStride, 1u);
+                        if (REPLAY) {
+                            home += 1u;
+                            pend = row_entry(home);
+                        } else if (lane == 0) {
+                            pend = atomicAdd(work_counter + home * kShardStride, 1u);
+                        }
 #ifdef SVO_PROBE_CLAIM_LATENCY   // (light timeline build: how long a claim's answer takes under the kernel's own load, slot 15)
                         if (DBG) {
                             const uint64_t c_a0 = __builtin_amdgcn_s_memtime();
@@ -1283,6 +1307,8 @@ __global__ __launch_bounds__(BLOCK, NS > 12 ? 4 : (CNT ? SVO_WAVES_PER_SIMD_CNT 
         // side, 11 ns apiece, and 7168 waves adding to 8 words at their exit held the END of the kernel up by 10 us)
         if (bal != nullptr && tid == 0u && blockIdx.x < kBalanceSlots) bal[kBalanceHead + blockIdx.x] = (uint32_t)__builtin_amdgcn_s_memrealtime();
         if (bal != nullptr && tid == 0u && blockIdx.x == 0u) bal[kBalanceStamps] = gridDim.x;  // (how many stamps this launch leaves)
+        // (REPLAY, stamp 1 of the wave's slot: when the wave ended -- what the deal's step ranks the waves of a list by)
+        if (REPLAY && lane == 0u) fresh_args().deal_stamps[2u * wave_id + 1u] = (uint32_t)__builtin_amdgcn_s_memrealtime();
     }
     if (DBG && lane == 0) {
         uint64_t t_end = __builtin_amdgcn_s_memrealtime();
@@ -1304,6 +1330,19 @@ __global__ __launch_bounds__(BLOCK, NS > 12 ? 4 : (CNT ? SVO_WAVES_PER_SIMD_CNT 
         d[6] = dbg_refills;
         d[7] = dbg_gens;
     }
+}
+
+template <int BLOCK, int NS, int K, bool GE, bool DBG, bool CNT, bool SHD>
+__global__ __launch_bounds__(BLOCK, NS > 12 ? 4 : (CNT ? SVO_WAVES_PER_SIMD_CNT : ((SHD || (DBG && SVO_DBG_LIGHT == 0)) ? 6 : SVO_WAVES_PER_SIMD))) void trace_stack_kernel(TraceArgs a, uint32_t strip_items,
+                                                               uint32_t *work_counter, uint32_t *defer) {
+    trace_stack_body<BLOCK, NS, K, GE, DBG, CNT, SHD, false>(a, strip_items, work_counter, defer);
+}
+
+// The replay twin of the default instantiation (DBG = CNT = SHD = false): a resting view's strips from a.deal_table, no claims.
+// (TraceArgs stays the first parameter: fresh_args reads it from the start of the kernarg segment.)
+template <int BLOCK, int NS, int K, bool GE>
+__global__ __launch_bounds__(BLOCK, SVO_WAVES_PER_SIMD) void trace_stack_replay_kernel(TraceArgs a, uint32_t strip_items, uint32_t *defer) {
+    trace_stack_body<BLOCK, NS, K, GE, false, false, false, true>(a, strip_items, nullptr, defer);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1725,6 +1764,20 @@ static hipError_t launch_stack(const TraceArgs &args, const LaunchInfo &li, hipS
     uint32_t n_strips = (args.work.n_items + strip_items - 1) / strip_items;
     uint32_t need = (n_strips + (kStackBlock / 64) - 1) / (kStackBlock / 64);
     if (blocks > need) blocks = need;
+    if (li.blocks_out) {  // (the caller only asks what grid this frame would get: svo_abi.cpp sizes and seeds the deal table from it)
+        *li.blocks_out = blocks;
+        return hipSuccess;
+    }
+    if (args.deal_table != nullptr) {
+        // the replay twin: same grid, same LDS, same occupancy slot as the default instantiation whose claims it replaces
+        if constexpr (NS == kStackLevels) {
+            if (shd || args.count_nodes || args.debug) return hipErrorInvalidValue;
+            hipLaunchKernelGGL((trace_stack_replay_kernel<kStackBlock, NS, kTopLevels, GE>), dim3(blocks), dim3(kStackBlock), lds_bytes, stream, args,
+                               strip_items, li.defer);
+            return hipGetLastError();
+        }
+        return hipErrorInvalidValue;
+    }
     hipLaunchKernelGGL(kern, dim3(blocks), dim3(kStackBlock), lds_bytes, stream, args, strip_items, li.counters, li.defer);
     return hipGetLastError();
 }

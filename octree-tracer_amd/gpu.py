@@ -6,7 +6,7 @@ import torch
 
 from ._lib import SvoError, lib
 
-OPT_VARIANT, OPT_TIMING, OPT_GRID_BLOCKS, OPT_REFILL_MIN, OPT_STRIP_ITEMS, OPT_DYNAMIC_STRIPS, OPT_PRIO_STEPS, OPT_DEBUG_BUFFER, OPT_SCHEDULE, OPT_TREE_DEPTH, OPT_BLOCK_SHAPE, OPT_SCAN_CLEARS_COUNTERS, OPT_FUSED_SHADOWS, OPT_PAIR_TABLE, OPT_CULL, OPT_CAMERA_SHORTCUT, OPT_SCHEDULE_MOTION = range(17)
+OPT_VARIANT, OPT_TIMING, OPT_GRID_BLOCKS, OPT_REFILL_MIN, OPT_STRIP_ITEMS, OPT_DYNAMIC_STRIPS, OPT_PRIO_STEPS, OPT_DEBUG_BUFFER, OPT_SCHEDULE, OPT_TREE_DEPTH, OPT_BLOCK_SHAPE, OPT_SCAN_CLEARS_COUNTERS, OPT_FUSED_SHADOWS, OPT_PAIR_TABLE, OPT_CULL, OPT_CAMERA_SHORTCUT, OPT_SCHEDULE_MOTION, OPT_STATIC_DEAL = range(18)
 VARIANT_RESTART, VARIANT_STACK = 0, 1
 
 
@@ -108,6 +108,29 @@ class Gpu:
         import numpy as np
         out = np.zeros(n_strips, dtype=np.uint8)
         self.check(lib().svo_diag_strip_classes(self._h, out.ctypes.data_as(C.c_void_p), n_strips))
+        return out
+
+    DEAL_STATUS = ("replayed", "seeds", "device_seeds", "moves", "step", "verdict", "seeded", "claims", "rows", "row_cap",
+                   "best_ticks", "best_sample_ticks", "claim_ticks", "last_ticks", "last_moves", "learn_left")
+
+    def deal_status(self, table=False, stamps=False):
+        """the static deal of the context's resting view (OPT_STATIC_DEAL), read-only: a dict of DEAL_STATUS (svo_diag_deal),
+        with the device table (rows x row_cap strip numbers, 0xFFFFFFFF behind a row's last) and the per-wave stamps (began
+        its last strip, ended: 10 ns ticks) when asked for; diagnostics"""
+        import numpy as np
+        st = np.zeros(16, dtype=np.uint32)
+        self.check(lib().svo_diag_deal(self._h, st.ctypes.data_as(C.c_void_p), None, 0, None, 0))
+        out = dict(zip(self.DEAL_STATUS, (int(v) for v in st)))
+        rows, cap = out["rows"], out["row_cap"]
+        tab = np.zeros((rows, cap), dtype=np.uint32) if table else None
+        stp = np.zeros((rows, 2), dtype=np.uint32) if stamps else None
+        if rows and (table or stamps):
+            self.check(lib().svo_diag_deal(self._h, st.ctypes.data_as(C.c_void_p), tab.ctypes.data_as(C.c_void_p) if table else None,
+                                           tab.size if table else 0, stp.ctypes.data_as(C.c_void_p) if stamps else None, stp.size if stamps else 0))
+        if table:
+            out["table"] = tab
+        if stamps:
+            out["stamps"] = stp
         return out
 
     def timing_collect(self, cap=65536):
