@@ -585,6 +585,108 @@ int svo_mesh_voxelize(svo_ctx *ctx, const svo_voxelize_params *p,
 #define SVO_VOXELIZE_TIMES 5
 int svo_voxelize_timing(svo_ctx *ctx, float ms_out[SVO_VOXELIZE_TIMES]);
 
+/* ---- voxel structures scattered over the tree in the node buffer ----
+ * Three calls that together populate a terrain without the tree leaving the device: where the ground is in every
+ * column of a rectangle (svo_nodes_column_tops), which columns get a structure (svo_structures_sites), and the voxel
+ * list of a structure stamped at every site (svo_structures_stamp), which svo_nodes_edit takes as it is.
+ *
+ * svo_nodes_column_tops: the highest occupied cell of each column of the `depth` grid, by the rule of svo_nodes_sample.
+ * For the column (x, z) = (origin_xz[0] + i, origin_xz[1] + k), i < size_xz[0], k < size_xz[1]:
+ *     for y = y_hi - 1 down to y_lo:
+ *         v = the value svo_nodes_sample gives the cell (x, y, z) at `depth`
+ *         if v != 0:  top = y, value = v, done
+ *     top = SVO_TOP_NONE, value = 0
+ * so value is a colour, SVO_SAMPLE_FINER (the tree is interior at `depth` there: occupied, and said so) or
+ * SVO_SAMPLE_BROKEN.  Hit counters never matter.  A leaf above `depth` covers a run of the column's cells: y_hi and y_lo
+ * may cut through it, and top is then the highest of its cells below y_hi.  top_out_dev[i * size_xz[1] + k] and, unless
+ * it is NULL, value_out_dev[i * size_xz[1] + k] get the column's result (z runs fastest, as in svo_nodes_sample_dense);
+ * only these size_xz[0] * size_xz[1] entries are written.  A size with a 0 succeeds and writes nothing.
+ * The outputs are DEVICE pointers.  The call only reads the node buffer, runs on the ctx stream behind the store's last
+ * write, whichever context issued it, records no write and DOES NOT BLOCK: outputs must stay valid until svo_sync.  No
+ * atomics: the same bytes on every run and for every layout of the same tree.  No pointer is followed before it passed
+ * svo_nodes_sample's check, and the depth bound ends every walk on a cyclic tree.  A device adaptive state attached to the
+ * context is no obstacle.
+ * Errors are decided on the host from the arguments before anything is enqueued; the first in this order is reported:
+ * SVO_ERR_ARG: NULL p; NULL origin_xz, size_xz or top_out_dev; non-zero flags; depth outside 1..21; y_lo >= y_hi or
+ * y_hi > 2^depth; a rectangle with origin + size > 2^depth on an axis; 2^31 columns or more.  SVO_ERR_STATE: no node
+ * buffer.  SVO_ERR_ARG: n_words not a positive multiple of 8 or above the capacity. */
+#define SVO_TOP_NONE 0xFFFFFFFFu /* nothing in the column within [y_lo, y_hi) */
+typedef struct svo_tops_params {
+    uint32_t flags;    /* 0 */
+    uint32_t depth;    /* 1..21: the grid the columns stand on */
+    uint64_t n_words;  /* the tree: words [0, n_words) of the node buffer, rooted at group 0 */
+    uint32_t y_lo;     /* the search covers y_lo <= y < y_hi <= 2^depth */
+    uint32_t y_hi;
+} svo_tops_params;
+int svo_nodes_column_tops(svo_ctx *ctx, const svo_tops_params *p, const uint32_t origin_xz[2], const uint32_t size_xz[2],
+                          uint32_t *top_out_dev, uint32_t *value_out_dev /* may be null */);
+
+/* svo_structures_sites: the columns of a rectangle that get a structure, from the two arrays svo_nodes_column_tops wrote
+ * for it (top_dev, value_dev: DEVICE, size_xz[0] * size_xz[1] u32 each, z fastest).  With lowbias32(v): v ^= v >> 16,
+ * v *= 0x7feb352d, v ^= v >> 15, v *= 0x846ca68b, v ^= v >> 16 in wrapping u32 arithmetic, and
+ * h = lowbias32(lowbias32(x + seed) ^ z) for the column (x, z) = origin_xz + (i, k), the column is a site iff
+ *     top != SVO_TOP_NONE,  value < 2^27 (neither FINER nor BROKEN),  on_value == 0 or value == on_value,  h % one_in == 0.
+ * value_dev may be NULL when on_value == 0; the two tests on value are then skipped.  A site's origin is the three int32
+ * (x, top + lift, z), its rotation lowbias32(h + 0x9E3779B9) >> 30 with SVO_SITES_ROTATE and 0 without.  The sites come
+ * in the order of the arrays (x, then z).
+ * origins_out_dev == NULL is a count query: *n_out gets the number of sites, nothing else is written and max_sites is
+ * ignored.  Otherwise origins_out_dev (3 * max_sites int32) and rots_out_dev (max_sites u32, or NULL) are DEVICE pointers
+ * that get the entries [0, *n_out) and nothing behind them.  An empty rectangle succeeds with *n_out = 0.
+ * The call needs no node buffer.  Runs on the ctx stream, blocks once to read the count; the fill is enqueued: inputs and
+ * outputs must stay valid until svo_sync.  Scans and no atomics: the same bytes on every run.
+ * A refused call leaves the outputs and *n_out as they were; the first cause in this order is reported.  SVO_ERR_ARG: NULL
+ * p or n_out; flag bits other than SVO_SITES_ROTATE; one_in == 0; NULL origin_xz or size_xz; an origin or a size of 2^31
+ * or more on an axis, or 2^31 columns or more; NULL top_dev with columns to read; NULL value_dev with on_value != 0.
+ * SVO_ERR_CAP, with the exact count in svo_last_error: more sites than max_sites (not for a count query). */
+#define SVO_SITES_ROTATE 1u
+typedef struct svo_sites_params {
+    uint32_t flags;      /* 0 or SVO_SITES_ROTATE */
+    uint32_t seed;
+    uint32_t one_in;     /* >= 1: one column in one_in is picked, by the hash */
+    uint32_t on_value;   /* 0, or the only value of a column's top that takes a structure */
+    int32_t lift;        /* added to top: 1 stands the structure's y = 0 layer on the ground */
+    uint32_t reserved;   /* 0 */
+    uint64_t max_sites;  /* room in the outputs, in sites; ignored by a count query */
+} svo_sites_params;
+int svo_structures_sites(svo_ctx *ctx, const svo_sites_params *p, const uint32_t *top_dev, const uint32_t *value_dev /* may be null */,
+                         const uint32_t origin_xz[2], const uint32_t size_xz[2], int32_t *origins_out_dev,
+                         uint32_t *rots_out_dev /* may be null */, uint64_t *n_out);
+
+/* svo_structures_stamp: k placements of a structure of m voxels as one voxel list.  offsets_dev (m * 3 int32) and
+ * colours_dev (m u32) are the structure (svo_structure_load), origins_dev (k * 3 int32) and rots_dev (k u32, or NULL: all
+ * 0) the placements (svo_structures_sites); all DEVICE pointers.  The entry (p, v) has the cell
+ *     origins[p] + R^rots[p](offsets[v]),   R (dx, dy, dz) = (dz, dy, -dx): a quarter turn about +y,
+ * and exists iff that cell lies in [0, 2^depth)^3: everything else is clipped, and a placement wholly outside gives
+ * nothing.  The entries come placement by placement and, within a placement, in the structure's order: fed to
+ * svo_nodes_edit, where the last in input order wins, A LATER PLACEMENT WINS A SHARED CELL.  xyz is the cell, colour
+ * colours[v] as it is (svo_nodes_edit masks it to 24 bits; 0 removes the cell), placement p.
+ * xyz_out_dev == NULL is a count query: *n_out gets the number of entries, nothing else is written and max_voxels is
+ * ignored.  Otherwise xyz_out_dev (3 * max_voxels u32), colour_out_dev (max_voxels u32) and placement_out_dev (max_voxels
+ * u32, or NULL) get the entries [0, *n_out) and nothing behind them.  k == 0 or m == 0 succeeds with *n_out = 0.
+ * The call needs no node buffer.  Runs on the ctx stream, blocks once to read the count and the device's checks; the fill
+ * is enqueued: inputs and outputs must stay valid until svo_sync.  Scans and no atomics: the same bytes on every run.
+ * A refused call leaves the outputs and *n_out as they were; the first cause in this order is reported.  SVO_ERR_ARG: NULL
+ * p or n_out; non-zero flags; depth outside 1..21; k * m >= 2^31 (decided in 64 bits before any launch); NULL offsets_dev,
+ * colours_dev or origins_dev with k * m > 0; NULL colour_out_dev with xyz_out_dev given; checked on the device, the lowest
+ * index named in svo_last_error: a placement with an origin component outside [-2^22, 2^22), else a placement with a
+ * rotation >= 4, else a voxel with an offset component outside (-2^22, 2^22).  SVO_ERR_CAP, with the exact count in
+ * svo_last_error: more entries than max_voxels (not for a count query). */
+typedef struct svo_stamp_params {
+    uint32_t flags;       /* 0 */
+    uint32_t depth;       /* 1..21: the grid the cells are clipped to */
+    uint64_t max_voxels;  /* room in the outputs, in entries; ignored by a count query */
+} svo_stamp_params;
+int svo_structures_stamp(svo_ctx *ctx, const svo_stamp_params *p, const int32_t *offsets_dev, const uint32_t *colours_dev, size_t m,
+                         const int32_t *origins_dev, const uint32_t *rots_dev /* may be null */, size_t k,
+                         uint32_t *xyz_out_dev, uint32_t *colour_out_dev, uint32_t *placement_out_dev /* may be null */,
+                         uint64_t *n_out);
+/* Times (ms) of the last of the three calls that ran on the context: [0] count (column tops: the kernel; sites and
+ * stamp: the checks, the flags' sums and their scan, with the read-back), [1] fill (device events; waits for it; 0 for
+ * column tops and for a count query), [2] host wall time of the call.  A refused call, and one with nothing to do,
+ * leaves them. */
+#define SVO_STRUCTURE_TIMES 3
+int svo_structure_timing(svo_ctx *ctx, float ms_out[SVO_STRUCTURE_TIMES]);
+
 /* ---- mip-coloured chunk trees and streamable worlds built on the GPU ----
  * Inputs as svo_nodes_build: xyz n * 3 u32 and colours n u32 (0x00RRGGBB) or NULL, DEVICE pointers on the ctx's device;
  * the last voxel of a cell wins; a colour-0 voxel is an empty leaf on a path that exists.  A chunk tree is the host

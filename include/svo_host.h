@@ -6,7 +6,7 @@
  * Reference counterparts (file:line under /root/reference/src):
  *   svo_cpu_octree_*      CpuOctree (cpu_octree.rs:17-273): new/add_voxels :23-45, find_voxel
  *                         :48-76, put_in_voxel :100-111, load_file :113-125, .rsvo :128-175,
- *                         .vox :177-210, to_octree :233-252; World::generate_mip_tree
+ *                         .vox :177-210, load_structure :213-230, to_octree :233-252; World::generate_mip_tree
  *                         (world.rs:234-336)
  *   svo_octree_*          Octree (octree.rs:43-162): new :51-66, subdivide :72-93, unsubdivide
  *                         :95-110, find_voxel :113-141, expanded :143-148, pos_offset :154-161
@@ -63,6 +63,16 @@ int64_t svo_vox_parse(const uint8_t *data, size_t len, uint32_t size[3], uint8_t
 /* write a minimal .vox (SIZE, XYZI, RGBA); returns bytes needed/written */
 size_t svo_vox_write(uint32_t size, const uint8_t *xyzi, size_t n_voxels, const uint32_t *palette256, uint8_t *out,
                      size_t cap);
+/* the same for a model of any size (size[3] as the SIZE chunk holds it) */
+size_t svo_vox_write_box(const uint32_t size[3], const uint8_t *xyzi, size_t n_voxels, const uint32_t *palette256, uint8_t *out,
+                         size_t cap);
+/* CpuOctree::load_structure (cpu_octree.rs:213-230): model 0 of a .vox of any size, read from `path` or, with path NULL,
+ * from `data`, as a structure for svo_structures_stamp.  Per voxel, in file order: offsets (3 int32) = (size.x / 2 - x, z,
+ * y - size.y / 2) in integer division, index = voxel.i + 1 with voxel.i = file colour index - 1 (the loader's convention:
+ * a file index of 0 counts as 1), colours = 0x00RRGGBB of palette[voxel.i], as svo_cpu_octree_load_vox resolves it.
+ * Returns the voxel count, or -1 (err says why); the outputs (each optional) are filled when cap >= the count. */
+int64_t svo_structure_load(const char *path, const uint8_t *data, size_t len, int32_t *offsets, uint32_t *index,
+                           uint32_t *colours, size_t cap, char *err, size_t errlen);
 /* serialise a CpuOctree as an .rsvo child-mask stream (inverse of load_rsvo); returns bytes */
 size_t svo_rsvo_write(const svo_cpu_octree *t, uint8_t *out, size_t cap);
 

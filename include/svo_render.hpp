@@ -62,6 +62,21 @@ class Gpu {  // gpu.rs:3-50 (wgpu instance/adapter/device/queue -> one HIP conte
     svo_ctx *ctx_ = nullptr;
 };
 
+// `words` u32 of device memory for the length of a call (svo_buffer_alloc), freed with the object
+class Scratch {
+  public:
+    Scratch(const Gpu &gpu, uint64_t words) : gpu_(gpu) { gpu.check(svo_buffer_alloc(gpu.ctx(), size_t(words) * 4, &p_)); }
+    ~Scratch() { (void)svo_buffer_free(gpu_.ctx(), p_); }
+    Scratch(const Scratch &) = delete;
+    Scratch &operator=(const Scratch &) = delete;
+    uint32_t *u32() const { return static_cast<uint32_t *>(p_); }
+    int32_t *i32() const { return static_cast<int32_t *>(p_); }
+
+  private:
+    const Gpu &gpu_;
+    void *p_ = nullptr;
+};
+
 class CpuOctree {  // cpu_octree.rs:17-273
   public:
     explicit CpuOctree(uint8_t mask = 0) : t_(svo_cpu_octree_new(mask)) {}
@@ -334,6 +349,70 @@ class Render {  // render.rs:3-285
         const svo_sample_params p{0u, depth, n_words};
         gpu_.check(svo_nodes_sample_dense(gpu_.ctx(), &p, origin, size, grid_dev));
         gpu_.poll_wait();
+    }
+    // the highest occupied cell of each column of a rectangle of the `depth` grid (svo_nodes_column_tops):
+    // tops_dev and values_dev (or null) hold size_xz[0] * size_xz[1] u32 of DEVICE memory, z fastest; a top is the y of
+    // the first cell from y_hi - 1 down to y_lo that sample_voxels gives a value other than 0, or SVO_TOP_NONE.  y_hi 0:
+    // the whole height.  The node buffer is only read.
+    void column_tops(uint64_t n_words, uint32_t depth, const uint32_t origin_xz[2], const uint32_t size_xz[2], uint32_t *tops_dev,
+                     uint32_t *values_dev = nullptr, uint32_t y_lo = 0, uint32_t y_hi = 0) {
+        const svo_tops_params p{0u, depth, n_words, y_lo, y_hi ? y_hi : depth < 32 ? 1u << depth : 0u};
+        gpu_.check(svo_nodes_column_tops(gpu_.ctx(), &p, origin_xz, size_xz, tops_dev, values_dev));
+        gpu_.poll_wait();
+    }
+    // the columns of that rectangle that get a structure (svo_structures_sites), from the two arrays
+    // column_tops wrote: origins_dev (3 * max_sites int32: x, top + lift, z) and rots_dev (max_sites u32, or null) are
+    // DEVICE pointers; returns the site count.  origins_dev null: the count alone.
+    uint64_t structure_sites(const uint32_t *tops_dev, const uint32_t *values_dev, const uint32_t origin_xz[2], const uint32_t size_xz[2],
+                             uint32_t one_in, int32_t *origins_dev, uint32_t *rots_dev, uint64_t max_sites, uint32_t seed = 0,
+                             uint32_t on_value = 0, int32_t lift = 1, bool rotate = true) {
+        const svo_sites_params p{rotate ? SVO_SITES_ROTATE : 0u, seed, one_in, on_value, lift, 0u, max_sites};
+        uint64_t n = 0;
+        gpu_.check(svo_structures_sites(gpu_.ctx(), &p, tops_dev, values_dev, origin_xz, size_xz, origins_dev, rots_dev, &n));
+        gpu_.poll_wait();
+        return n;
+    }
+    // k placements of a structure of m voxels as one voxel list (svo_structures_stamp): offsets_dev (3 * m
+    // int32), colours_dev (m), origins_dev (3 * k int32), rots_dev (k quarter turns about +y, or null) and the outputs
+    // xyz_dev (3 * max_voxels u32), out_colours_dev (max_voxels) and placements_dev (max_voxels, or null) are DEVICE
+    // pointers; cells outside the `depth` grid are clipped; a list that edit_nodes takes, in which a later placement wins
+    // a shared cell.  Returns the entry count; xyz_dev null: the count alone.
+    uint64_t stamp_structures(const int32_t *offsets_dev, const uint32_t *colours_dev, size_t m, const int32_t *origins_dev,
+                              const uint32_t *rots_dev, size_t k, uint32_t depth, uint32_t *xyz_dev, uint32_t *out_colours_dev,
+                              uint64_t max_voxels, uint32_t *placements_dev = nullptr) {
+        const svo_stamp_params p{0u, depth, max_voxels};
+        uint64_t n = 0;
+        gpu_.check(svo_structures_stamp(gpu_.ctx(), &p, offsets_dev, colours_dev, m, origins_dev, rots_dev, k, xyz_dev, out_colours_dev,
+                                        placements_dev, &n));
+        gpu_.poll_wait();  // the inputs may go away
+        return n;
+    }
+    // stamp_structures, then edit_nodes with the list (held in device memory of this call's own): the structure put into
+    // the first n_words words of the tree at every origin.  Returns the new length.
+    uint64_t place_structures(uint64_t n_words, const int32_t *offsets_dev, const uint32_t *colours_dev, size_t m, const int32_t *origins_dev,
+                              const uint32_t *rots_dev, size_t k, uint32_t depth, uint64_t max_words = 0) {
+        const uint64_t n = stamp_structures(offsets_dev, colours_dev, m, origins_dev, rots_dev, k, depth, nullptr, nullptr, 0);
+        if (!n) return n_words;
+        Scratch xyz(gpu_, 3 * n), colours(gpu_, n);
+        stamp_structures(offsets_dev, colours_dev, m, origins_dev, rots_dev, k, depth, xyz.u32(), colours.u32(), n);
+        return edit_nodes(n_words, xyz.u32(), colours.u32(), n, depth, 0xFFFFFF, max_words);
+    }
+    // a structure scattered over the ground of a rectangle without the tree leaving the device: column_tops, then
+    // structure_sites, then place_structures.  Returns the new length; *n_sites (or null) gets the number of sites.
+    uint64_t scatter_structures(uint64_t n_words, const int32_t *offsets_dev, const uint32_t *colours_dev, size_t m,
+                                const uint32_t origin_xz[2], const uint32_t size_xz[2], uint32_t depth, uint32_t one_in, uint32_t seed = 0,
+                                uint32_t on_value = 0, int32_t lift = 1, bool rotate = true, uint64_t *n_sites = nullptr) {
+        const uint64_t columns = uint64_t(size_xz[0]) * size_xz[1];
+        if (n_sites) *n_sites = 0;
+        if (!columns) return n_words;
+        Scratch tops(gpu_, columns), values(gpu_, columns);
+        column_tops(n_words, depth, origin_xz, size_xz, tops.u32(), values.u32());
+        const uint64_t k = structure_sites(tops.u32(), values.u32(), origin_xz, size_xz, one_in, nullptr, nullptr, 0, seed, on_value, lift, rotate);
+        if (n_sites) *n_sites = k;
+        if (!k) return n_words;
+        Scratch origins(gpu_, 3 * k), rots(gpu_, k);
+        structure_sites(tops.u32(), values.u32(), origin_xz, size_xz, one_in, origins.i32(), rots.u32(), k, seed, on_value, lift, rotate);
+        return place_structures(n_words, offsets_dev, colours_dev, m, origins.i32(), rots.u32(), k, depth);
     }
     // the adaptive step on the GPU (svo_adaptive_*): attach once (SVO_OPT_SCAN_CLEARS_COUNTERS = 1, the
     // octree's words in the node buffer, `world` kept alive), then after each scan step() over the scan's own lists (or

@@ -13,6 +13,7 @@ C ABI of libsvo_hip.so:
     adaptive           <- src/adaptive.rs  process_subdivision / process_unsubdivision
     scenes             deterministic benchmark scene generators (no reference counterpart)
     mesh               triangle meshes voxelised on the GPU into voxel lists, a Wavefront reader, mesh generators (no reference counterpart)
+    structure.Structure <- src/cpu_octree.rs CpuOctree::load_structure: a .vox model as offsets, block indices and colours
 The package directory name contains a hyphen; import it through __graft_entry__.load_package(),
 which registers it as module `octree_tracer_amd`.
 """
@@ -23,15 +24,17 @@ from .cpu_octree import CHUNK_OFFSET, CpuOctree
 from .camera import Character, Settings, camera_matrices
 from .gpu import Gpu
 from .render import Render, HIT_DTYPE, F_PAUSE_ADAPTIVE, F_SHOW_STEPS, F_SHOW_HITS, F_SHADOWS, F_MISC_BOOL
-from .render import SAMPLE_FINER, SAMPLE_OUTSIDE, SAMPLE_BROKEN
+from .render import SAMPLE_FINER, SAMPLE_OUTSIDE, SAMPLE_BROKEN, TOP_NONE
+from .structure import Structure, load_structure
 from .compute import Compute
 from .world import World
 from .procedural import Procedural
 from . import procedural
 from . import scenes
 from . import mesh
+from . import structure
 from . import sharding
 from . import adaptive
 
 __all__ = ["Gpu", "Render", "Compute", "Octree", "CpuOctree", "Voxel", "World", "Procedural", "Uniforms", "Character", "Settings",
-           "SvoError", "SAMPLE_FINER", "SAMPLE_OUTSIDE", "SAMPLE_BROKEN", "VOXEL_OFFSET", "CHUNK_OFFSET", "HIT_DTYPE", "create_node", "camera_matrices", "scenes", "mesh", "sharding", "adaptive", "procedural"]
+           "SvoError", "SAMPLE_FINER", "SAMPLE_OUTSIDE", "SAMPLE_BROKEN", "TOP_NONE", "Structure", "load_structure", "VOXEL_OFFSET", "CHUNK_OFFSET", "HIT_DTYPE", "create_node", "camera_matrices", "scenes", "mesh", "structure", "sharding", "adaptive", "procedural"]

@@ -4,13 +4,15 @@ import numpy as np
 import torch
 
 
-def device_u32(a, dev, clamp=False, mask=None, cells=False, what=None):
+def device_u32(a, dev, clamp=False, mask=None, cells=False, what=None, signed=False):
     """An integer array (numpy or torch, any integer dtype) as a contiguous int32 tensor on `dev` holding u32 bit patterns.
     clamp: values outside [0, 2^31) become -1 or 2^31 - 1, out of range for any depth, so the device's range checks still
     see them; mask: keep those bits, whatever the dtype -- colours are masked to 24 bits here for every caller, which for
     an int32 colour tensor with bits above 23 handed to mesh.voxelize used to happen on the device only (the kernels mask
     again, the result is the same); cells: a wide value stays non-zero iff it was (its low 24 bits kept).  An int32 input
-    is taken as it is unless `mask` is given.  what: the argument's name, put in front of the TypeError's text."""
+    is taken as it is unless `mask` is given.  signed: the values are int32 numbers (a structure's offsets, placements'
+    origins), and one outside int32 becomes its nearest bound, out of range for the device's checks.  what: the
+    argument's name, put in front of the TypeError's text."""
     t = a if isinstance(a, torch.Tensor) else torch.as_tensor(np.ascontiguousarray(a))
     if t.dtype.is_floating_point or t.dtype.is_complex or t.dtype == torch.bool:
         raise TypeError(f"{what + ': ' if what else ''}integer input expected, got {t.dtype}")
@@ -21,6 +23,8 @@ def device_u32(a, dev, clamp=False, mask=None, cells=False, what=None):
             t = t & mask
         elif clamp:
             t = t.clamp(-1, 2**31 - 1)
+        elif signed:
+            t = t.clamp(-2**31, 2**31 - 1)
         elif cells:
             t = torch.where(t != 0, (t & 0xFFFFFF) | (1 << 24), 0)
     return t.to(torch.int32).contiguous()

@@ -105,6 +105,39 @@ class VoxelizeParams(C.Structure):
     ]
 
 
+class TopsParams(C.Structure):
+    """svo_tops_params: the highest occupied cell of each column of the tree in the node buffer (include/svo_hip.h)."""
+    _fields_ = [
+        ("flags", C.c_uint32),
+        ("depth", C.c_uint32),
+        ("n_words", C.c_uint64),
+        ("y_lo", C.c_uint32),
+        ("y_hi", C.c_uint32),
+    ]
+
+
+class SitesParams(C.Structure):
+    """svo_sites_params: the columns that get a structure (include/svo_hip.h)."""
+    _fields_ = [
+        ("flags", C.c_uint32),
+        ("seed", C.c_uint32),
+        ("one_in", C.c_uint32),
+        ("on_value", C.c_uint32),
+        ("lift", C.c_int32),
+        ("reserved", C.c_uint32),
+        ("max_sites", C.c_uint64),
+    ]
+
+
+class StampParams(C.Structure):
+    """svo_stamp_params: placements x structure -> a voxel list (include/svo_hip.h)."""
+    _fields_ = [
+        ("flags", C.c_uint32),
+        ("depth", C.c_uint32),
+        ("max_voxels", C.c_uint64),
+    ]
+
+
 class ChunkBuildParams(C.Structure):
     """svo_chunk_build_params: a mip-coloured tree or a chunked world built on the GPU (include/svo_hip.h)."""
     _fields_ = [
@@ -199,6 +232,10 @@ DEVICE_SIGNATURES = {
     "svo_sample_timing": (C.c_int, (vp, fp)),
     "svo_mesh_voxelize": (C.c_int, (vp, C.POINTER(VoxelizeParams), vp, vp, vp, sz, vp, vp, vp, C.POINTER(u64))),
     "svo_voxelize_timing": (C.c_int, (vp, fp)),
+    "svo_nodes_column_tops": (C.c_int, (vp, C.POINTER(TopsParams), C.POINTER(u32), C.POINTER(u32), vp, vp)),
+    "svo_structures_sites": (C.c_int, (vp, C.POINTER(SitesParams), vp, vp, C.POINTER(u32), C.POINTER(u32), vp, vp, C.POINTER(u64))),
+    "svo_structures_stamp": (C.c_int, (vp, C.POINTER(StampParams), vp, vp, sz, vp, vp, sz, vp, vp, vp, C.POINTER(u64))),
+    "svo_structure_timing": (C.c_int, (vp, fp)),
     "svo_adaptive_attach": (C.c_int, (vp, vp, vp)),
     "svo_adaptive_step": (C.c_int, (vp, vp, u32, vp, u32, C.POINTER(AdaptiveResult))),
     "svo_adaptive_download": (C.c_int, (vp, vp)),
@@ -225,6 +262,8 @@ HOST_SIGNATURES = {
     "svo_cpu_octree_generate_mips": (None, (vp, C.POINTER(C.c_uint8))),
     "svo_vox_parse": (i64, (cp, sz, C.POINTER(u32), vp, sz, vp, cp, sz)),
     "svo_vox_write": (sz, (u32, vp, sz, vp, vp, sz)),
+    "svo_vox_write_box": (sz, (C.POINTER(u32), vp, sz, vp, vp, sz)),
+    "svo_structure_load": (i64, (cp, cp, sz, vp, vp, vp, sz, cp, sz)),
     "svo_rsvo_write": (sz, (vp, vp, sz)),
     "svo_octree_new": (vp, (C.POINTER(C.c_uint8),)),
     "svo_octree_from_words": (vp, (vp, sz)),

@@ -155,9 +155,11 @@ def vox_parse(data: bytes):
 
 
 def vox_write(size, xyzi, palette):
+    """A minimal .vox of one model: size a side length (a cube) or the three of the SIZE chunk (x, y, z)."""
     xyzi = np.ascontiguousarray(xyzi, dtype=np.uint8)
     palette = np.ascontiguousarray(palette, dtype=np.uint32)
-    n = lib().svo_vox_write(size, xyzi.ctypes.data, xyzi.shape[0], palette.ctypes.data, None, 0)
+    box = (C.c_uint32 * 3)(*([int(size)] * 3 if np.ndim(size) == 0 else [int(v) for v in size]))
+    n = lib().svo_vox_write_box(box, xyzi.ctypes.data, xyzi.shape[0], palette.ctypes.data, None, 0)
     buf = np.empty(n, dtype=np.uint8)
-    lib().svo_vox_write(size, xyzi.ctypes.data, xyzi.shape[0], palette.ctypes.data, buf.ctypes.data, n)
+    lib().svo_vox_write_box(box, xyzi.ctypes.data, xyzi.shape[0], palette.ctypes.data, buf.ctypes.data, n)
     return buf.tobytes()

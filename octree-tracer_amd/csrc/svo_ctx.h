@@ -1,11 +1,12 @@
 // svo_ctx.h -- the device context behind the opaque `svo_ctx` of include/svo_hip.h, and the host helpers of the files that
 // use it: svo_abi.cpp (trace / scan dispatch), svo_comm.cpp (RCCL frame gather) and the GPU tree passes (svo_proc.hip,
-// svo_build.hip, svo_edit.hip, svo_compact.hip, svo_list.hip, svo_sample.hip, svo_voxelize.hip, svo_adapt.hip).  One rule
-// of ownership for the context, the node store and every pass's state: a member owns what it holds, as svo_dev /
-// svo_pinned (an allocation and its size), svo_events (events) or svo_stream (a stream).  The passes share the rest as
-// their host frame: svo_grow / svo_grow_pinned / svo_grow_keep (workspaces, by the buffers' own sizes), svo_mirrored
-// (device words with a pinned mirror), svo_pass_timer (events and times), svo_workspace_ensure (creation) and the
-// svo_check_* argument checks; then the builder's sort and scan and svo_world_writer (a generated world's directory).
+// svo_build.hip, svo_edit.hip, svo_compact.hip, svo_list.hip, svo_sample.hip, svo_voxelize.hip, svo_structure.hip,
+// svo_adapt.hip).  One rule of ownership for the context, the node store and every pass's state: a member owns what it
+// holds, as svo_dev / svo_pinned (an allocation and its size), svo_events (events) or svo_stream (a stream).  The passes
+// share the rest as their host frame: svo_grow / svo_grow_pinned / svo_grow_keep (workspaces, by the buffers' own
+// sizes), svo_mirrored (device words with a pinned mirror), svo_pass_timer (events and times), svo_workspace_ensure
+// (creation) and the svo_check_* argument checks; then the builder's sort and scan and svo_world_writer (a generated
+// world's directory).
 // svo_scan.h, svo_group.h, svo_mip.h and svo_morton.h hold the device pieces, svo_rules.h the walks and rules that
 // svo_host.cpp and svo_adapt.hip both run.
 // Internal: not part of the boundary.
@@ -140,6 +141,7 @@ struct svo_compact_state;
 struct svo_list_state;
 struct svo_sample_state;
 struct svo_voxelize_state;
+struct svo_structure_state;
 template <typename T>
 using svo_workspace = std::unique_ptr<T, void (*)(T *)>;
 template <typename T>
@@ -247,6 +249,7 @@ struct svo_ctx {
     svo_workspace<svo_list_state> list{nullptr, nullptr};  // voxel listing's workspace (svo_list.hip)
     svo_workspace<svo_sample_state> sample{nullptr, nullptr};  // sampling's events and times (svo_sample.hip)
     svo_workspace<svo_voxelize_state> voxelize{nullptr, nullptr};  // mesh voxeliser's workspace (svo_voxelize.hip)
+    svo_workspace<svo_structure_state> structure{nullptr, nullptr};  // structure scattering's workspace (svo_structure.hip)
     std::string err;
 };
 

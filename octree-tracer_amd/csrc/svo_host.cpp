@@ -188,6 +188,16 @@ svo_cpu_octree *tree_from_voxels(uint32_t size, const uint8_t *xyzi, size_t n, c
     return t;
 }
 
+bool read_file(const std::string &path, std::vector<uint8_t> &buf) {
+    FILE *f = fopen(path.c_str(), "rb");
+    if (!f) return false;
+    uint8_t tmp[65536];
+    size_t got;
+    while ((got = fread(tmp, 1, sizeof tmp, f)) > 0) buf.insert(buf.end(), tmp, tmp + got);
+    fclose(f);
+    return true;
+}
+
 void average_children(const svo_cpu_octree &t, size_t first_child, Rgb &dst) {
     // world.rs:311-328: mean of the non-(0,0,0) children, `as u8` (saturating, NaN -> 0), max 1
     float sum[3] = {0, 0, 0}, div = 0;
@@ -270,13 +280,8 @@ svo_cpu_octree *svo_cpu_octree_load_rsvo(const uint8_t *data, size_t len, uint32
 
 svo_cpu_octree *svo_cpu_octree_load_file(const char *path, uint32_t octree_depth, char *err, size_t errlen) {
     std::string p(path ? path : "");
-    FILE *f = fopen(p.c_str(), "rb");
-    if (!f) { put_err(err, errlen, "cannot open " + p); return nullptr; }
     std::vector<uint8_t> buf;
-    uint8_t tmp[65536];
-    size_t got;
-    while ((got = fread(tmp, 1, sizeof tmp, f)) > 0) buf.insert(buf.end(), tmp, tmp + got);
-    fclose(f);
+    if (!read_file(p, buf)) { put_err(err, errlen, "cannot open " + p); return nullptr; }
     const size_t dot = p.find_last_of('.');
     const std::string ext = dot == std::string::npos ? "" : p.substr(dot + 1);
     if (ext == "rsvo") return svo_cpu_octree_load_rsvo(buf.data(), buf.size(), octree_depth, err, errlen);
@@ -354,6 +359,12 @@ int64_t svo_vox_parse(const uint8_t *data, size_t len, uint32_t size[3], uint8_t
 
 size_t svo_vox_write(uint32_t size, const uint8_t *xyzi, size_t n_voxels, const uint32_t *palette256, uint8_t *out,
                      size_t cap) {
+    const uint32_t cube[3] = {size, size, size};
+    return svo_vox_write_box(cube, xyzi, n_voxels, palette256, out, cap);
+}
+
+size_t svo_vox_write_box(const uint32_t size[3], const uint8_t *xyzi, size_t n_voxels, const uint32_t *palette256, uint8_t *out,
+                         size_t cap) {
     const size_t size_chunk = 12 + 12, xyzi_chunk = 12 + 4 + 4 * n_voxels, rgba_chunk = 12 + 1024;
     const size_t total = 8 + 12 + size_chunk + xyzi_chunk + rgba_chunk;
     if (!out || cap < total) return total;
@@ -361,12 +372,44 @@ size_t svo_vox_write(uint32_t size, const uint8_t *xyzi, size_t n_voxels, const 
     memcpy(p, "VOX ", 4); put32(p + 4, 150); p += 8;
     memcpy(p, "MAIN", 4); put32(p + 4, 0); put32(p + 8, uint32_t(size_chunk + xyzi_chunk + rgba_chunk)); p += 12;
     memcpy(p, "SIZE", 4); put32(p + 4, 12); put32(p + 8, 0);
-    put32(p + 12, size); put32(p + 16, size); put32(p + 20, size); p += size_chunk;
+    put32(p + 12, size[0]); put32(p + 16, size[1]); put32(p + 20, size[2]); p += size_chunk;
     memcpy(p, "XYZI", 4); put32(p + 4, uint32_t(4 + 4 * n_voxels)); put32(p + 8, 0); put32(p + 12, uint32_t(n_voxels));
     memcpy(p + 16, xyzi, 4 * n_voxels); p += xyzi_chunk;
     memcpy(p, "RGBA", 4); put32(p + 4, 1024); put32(p + 8, 0);
     for (int i = 0; i < 256; i++) put32(p + 12 + 4 * i, palette256[i]);
     return total;
+}
+
+// CpuOctree::load_structure (cpu_octree.rs:213-230): model 0 of a .vox of any size as offsets from the model's foot.  The
+// index convention is tree_from_voxels': voxel.i = file colour index - 1 (0 for a file index of 0), so index = voxel.i + 1
+// and the colour is palette[voxel.i], its r g b bytes as 0x00RRGGBB.
+int64_t svo_structure_load(const char *path, const uint8_t *data, size_t len, int32_t *offsets, uint32_t *index, uint32_t *colours,
+                           size_t cap, char *err, size_t errlen) {
+    std::vector<uint8_t> buf;
+    if (path) {
+        if (!read_file(path, buf)) { put_err(err, errlen, std::string("cannot open ") + path); return -1; }
+        data = buf.data();
+        len = buf.size();
+    }
+    if (!data) { put_err(err, errlen, "neither a path nor bytes"); return -1; }
+    VoxFile v;
+    std::string why;
+    if (!parse_vox(data, len, v, why)) { put_err(err, errlen, why); return -1; }
+    const size_t n = v.xyzi.size() / 4;
+    if (cap < n) return int64_t(n);
+    const int32_t half_x = int32_t(v.size[0]) / 2, half_y = int32_t(v.size[1]) / 2;
+    for (size_t k = 0; k < n; k++) {
+        const uint8_t *q = v.xyzi.data() + 4 * k;
+        const uint32_t i = q[3] ? q[3] - 1u : 0u, rgba = v.palette[i];
+        if (offsets) {
+            offsets[3 * k] = half_x - int32_t(q[0]);
+            offsets[3 * k + 1] = int32_t(q[2]);
+            offsets[3 * k + 2] = int32_t(q[1]) - half_y;
+        }
+        if (index) index[k] = i + 1u;
+        if (colours) colours[k] = (rgba & 0xFFu) << 16 | (rgba >> 8 & 0xFFu) << 8 | (rgba >> 16 & 0xFFu);
+    }
+    return int64_t(n);
 }
 
 size_t svo_rsvo_write(const svo_cpu_octree *t, uint8_t *out, size_t cap) {
@@ -599,16 +642,6 @@ svo_cpu_octree *tree_from_bin(const uint8_t *d, size_t len) {
         t->nodes[i] = {le32(n), Rgb{n[4], n[5], n[6]}};
     }
     return t;
-}
-
-bool read_file(const std::string &p, std::vector<uint8_t> &buf) {
-    FILE *f = fopen(p.c_str(), "rb");
-    if (!f) return false;
-    uint8_t tmp[65536];
-    size_t got;
-    while ((got = fread(tmp, 1, sizeof tmp, f)) > 0) buf.insert(buf.end(), tmp, tmp + got);
-    fclose(f);
-    return true;
 }
 
 int world_fail(svo_world *w, const std::string &msg) {

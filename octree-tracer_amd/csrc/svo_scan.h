@@ -1,5 +1,5 @@
 // svo_scan.h -- the scan pieces of the GPU tree passes (svo_proc.hip, svo_build.hip): the tile shape, a block-wide
-// exclusive scan and the one-block scan of the tile sums.  Everything sits in an anonymous namespace, so every pass file
+// exclusive scan and minimum and the one-block scan of the tile sums.  Everything sits in an anonymous namespace, so every pass file
 // that includes this header compiles its own copies, as it did when each file had its own.  The other shared device
 // pieces: svo_morton.h (the Morton convention), svo_mip.h (mip colours); the host ones are in svo_ctx.h.
 #pragma once
@@ -29,6 +29,22 @@ __device__ inline uint32_t block_exclusive_scan(uint32_t v, uint32_t *total) {
     }
     if (total) *total = s[N - 1];
     const uint32_t r = s[t] - v;
+    __syncthreads();  // (a following call reuses s)
+    return r;
+}
+
+// the minimum of v over the block's N threads, in every thread
+template <int N>
+__device__ inline uint32_t block_min(uint32_t v) {
+    __shared__ uint32_t s[N];
+    const int t = threadIdx.x;
+    s[t] = v;
+    __syncthreads();
+    for (int off = N / 2; off > 0; off >>= 1) {
+        if (t < off) s[t] = min(s[t], s[t + off]);
+        __syncthreads();
+    }
+    const uint32_t r = s[0];
     __syncthreads();  // (a following call reuses s)
     return r;
 }

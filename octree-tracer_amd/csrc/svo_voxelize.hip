@@ -27,7 +27,7 @@
 #include <string>
 
 #include "svo_ctx.h"
-#include "svo_scan.h"  // (kThreads, kTile, block_exclusive_scan, tile_offsets_kernel)
+#include "svo_scan.h"  // (kThreads, kTile, block_exclusive_scan, block_min, tile_offsets_kernel)
 
 namespace {
 
@@ -45,19 +45,6 @@ __device__ inline uint64_t cell_pack(uint32_t x, uint32_t y, uint32_t z) { retur
 __device__ inline uint32_t cell_x(uint64_t c) { return uint32_t(c >> 42); }
 __device__ inline uint32_t cell_y(uint64_t c) { return uint32_t(c >> 21) & 0x1FFFFFu; }
 __device__ inline uint32_t cell_z(uint64_t c) { return uint32_t(c) & 0x1FFFFFu; }
-
-template <int N>
-__device__ inline uint32_t block_min(uint32_t v) {
-    __shared__ uint32_t s[N];
-    const int t = threadIdx.x;
-    s[t] = v;
-    __syncthreads();
-    for (int off = N / 2; off > 0; off >>= 1) {
-        if (t < off) s[t] = min(s[t], s[t + off]);
-        __syncthreads();
-    }
-    return s[0];
-}
 
 // One lane per triangle.  tv gets its doubled coordinates (of a bad triangle: those of q = 0, so that every later pass
 // runs on it without harm until the host has read the verdict), the pair arrays the root pair.

@@ -97,6 +97,12 @@ class Gpu:
         the call (svo_voxelize_timing)"""
         return self._timing(lib().svo_voxelize_timing, 5)
 
+    def structure_timing(self):
+        """ms of the last Render.column_tops / structure_sites / stamp_structures call into the library that ran: count
+        (column tops: the kernel; sites and stamp: checks, sums and scan with the read-back), fill (device events), host
+        wall time of the call (svo_structure_timing)"""
+        return self._timing(lib().svo_structure_timing, 3)
+
     def world_build_timing(self):
         """ms of the last CpuOctree.build / World.build_world: keys, sort, levels, count read-back, emit, mips (device
         events), chunk read-back, chunk files and root (CpuOctree.build: the tree), host wall time of the call

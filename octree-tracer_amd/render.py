@@ -6,7 +6,7 @@ import torch
 
 from . import sharding
 from ._device import device_u32, voxel_list, wait_for_torch
-from ._lib import BuildParams, CompactParams, EditParams, ListParams, SampleParams, Uniforms, lib
+from ._lib import BuildParams, CompactParams, EditParams, ListParams, SampleParams, SitesParams, StampParams, TopsParams, Uniforms, lib
 from .camera import camera_matrices
 
 F_PAUSE_ADAPTIVE, F_SHOW_STEPS, F_SHOW_HITS, F_SHADOWS, F_MISC_BOOL = 1, 2, 4, 8, 16
@@ -16,6 +16,10 @@ EMPTY_WORD = (1 << 27) << 4  # an empty slot: (VOXEL_OFFSET + colour 0) << 4
 # what sample_voxels / sample_dense return in place of a value (svo_hip.h): the tree is interior at `depth` in the cell; a
 # coordinate is outside the grid; the path met a pointer that is unaligned or leaves the tree's words
 SAMPLE_FINER, SAMPLE_OUTSIDE, SAMPLE_BROKEN = 1 << 28, 1 << 29, 1 << 30
+TOP_NONE = -1  # what column_tops returns for a column that holds nothing: SVO_TOP_NONE = 0xFFFFFFFF read as int32
+# structure_sites and stamp_structures know a bound of their list before they call (the columns, placements x voxels): up
+# to this many entries they fill room for the bound in one call and return its first part, without the count query
+ONE_CALL_ENTRIES = 1 << 20
 
 
 class Render:
@@ -234,6 +238,126 @@ class Render:
         self.gpu.check(lib().svo_nodes_sample_dense(self.gpu._h, C.byref(p), (C.c_uint32 * 3)(*o), (C.c_uint32 * 3)(*s), room.data_ptr()))
         self.gpu.sync()
         return grid
+
+    def _depth(self, depth):
+        return max(0, int(self.gpu.tree_depth if depth is None else depth))
+
+    def column_tops(self, origin_xz, size_xz, depth=None, y_range=None, with_values=False):
+        """The highest occupied cell of each column of a rectangle of the `depth` grid, found on the GPU (svo_nodes_column_tops,
+        DESIGN.md 22): an int32 device tensor of shape size_xz, indexed [x, z], holding the y of the first cell from
+        y_range[1] - 1 down to y_range[0] whose sample_voxels value is not 0, or TOP_NONE (-1).  with_values: (tops, values),
+        values that cell's value: a colour, SAMPLE_FINER where the tree is refined below `depth` (occupied, and said so),
+        SAMPLE_BROKEN, 0 under TOP_NONE.  y_range=None: the whole height; depth=None: the depth declared for this tree.
+        Raises SvoError for a rectangle that leaves the grid or a bad y range.  The node buffer is only read."""
+        dev = self.gpu.torch_device
+        o, s = [int(v) for v in origin_xz], [int(v) for v in size_xz]
+        if len(o) != 2 or len(s) != 2 or min(o + s) < 0 or max(o + s) >= 1 << 32:
+            raise ValueError(f"origin_xz and size_xz must be 2 values in [0, 2^32) each, got {o} and {s}")
+        p = TopsParams()
+        p.depth, p.n_words = self._depth(depth), int(self.node_length)
+        lo, hi = (0, 1 << min(p.depth, 31)) if y_range is None else (int(v) for v in y_range)
+        if min(lo, hi) < 0 or max(lo, hi) >= 1 << 32:
+            raise ValueError(f"y_range must be 2 values in [0, 2^32), got {(lo, hi)}")
+        p.y_lo, p.y_hi = lo, hi
+        # a rectangle the call will refuse gets no memory first: the library decides and words the refusal
+        fits = 1 <= p.depth <= 21 and all(a + b <= 1 << p.depth for a, b in zip(o, s)) and s[0] * s[1] < 1 << 31
+        tops = torch.empty(s if fits else (0, 0), dtype=torch.int32, device=dev)
+        values = torch.empty_like(tops) if with_values else None
+        room = tops if tops.numel() else torch.empty(1, dtype=torch.int32, device=dev)  # (nothing is written to it)
+        wait_for_torch(self.gpu)
+        self.gpu.check(lib().svo_nodes_column_tops(self.gpu._h, C.byref(p), (C.c_uint32 * 2)(*o), (C.c_uint32 * 2)(*s), room.data_ptr(),
+                                                   values.data_ptr() if with_values and values.numel() else None))
+        self.gpu.sync()
+        return (tops, values) if with_values else tops
+
+    def structure_sites(self, tops, values, origin_xz, one_in, seed=0, on_value=0, lift=1, rotate=True):
+        """The columns of a rectangle that get a structure, picked on the GPU (svo_structures_sites) from what
+        column_tops(origin_xz, tops.shape, ..., with_values=True) returned (values may be None when on_value is 0): the
+        column (x, z) is a site when it has a top whose value is a plain value (not FINER, not BROKEN) and, with on_value,
+        that value, and when lowbias32(lowbias32(x + seed) ^ z) % one_in == 0.  Returns (origins (N, 3) int32 = (x, top +
+        lift, z), rots (N) int32 in 0..3, all 0 without `rotate`), device tensors in the arrays' order, ready for
+        stamp_structures."""
+        dev = self.gpu.torch_device
+        top = device_u32(tops, dev, what="tops")
+        val = device_u32(values, dev, what="values") if values is not None else None
+        if top.dim() != 2 or (val is not None and val.shape != top.shape):
+            raise ValueError(f"tops and values must be (size_x, size_z), got {tuple(top.shape)} and {None if val is None else tuple(val.shape)}")
+        o = [int(v) for v in origin_xz]
+        if len(o) != 2 or min(o) < 0 or max(o) >= 1 << 32:
+            raise ValueError(f"origin_xz must be 2 values in [0, 2^32), got {o}")
+        p = SitesParams()
+        p.flags, p.seed, p.one_in = 1 if rotate else 0, int(seed) & 0xFFFFFFFF, max(0, int(one_in))
+        p.on_value, p.lift = int(on_value) & 0xFFFFFFFF, int(lift)
+        args = (top.data_ptr() if top.numel() else None, val.data_ptr() if val is not None and val.numel() else None,
+                (C.c_uint32 * 2)(*o), (C.c_uint32 * 2)(*top.shape))
+        n = C.c_uint64(top.numel())
+        wait_for_torch(self.gpu)
+        if n.value > ONE_CALL_ENTRIES:
+            self.gpu.check(lib().svo_structures_sites(self.gpu._h, C.byref(p), *args, None, None, C.byref(n)))  # the count
+        room = n.value
+        origins = torch.empty((room, 3), dtype=torch.int32, device=dev)
+        rots = torch.empty(room, dtype=torch.int32, device=dev)
+        if room:
+            p.max_sites = room
+            wait_for_torch(self.gpu)
+            self.gpu.check(lib().svo_structures_sites(self.gpu._h, C.byref(p), *args, origins.data_ptr(), rots.data_ptr(), C.byref(n)))
+        self.gpu.sync()  # (the inputs may be released by the caller)
+        return origins[:n.value], rots[:n.value]
+
+    def stamp_structures(self, structure, origins, depth=None, rots=None, with_placement=False):
+        """The voxel list of `structure` (structure.Structure) placed at every origin, made on the GPU (svo_structures_stamp,
+        DESIGN.md 22).  origins: (K, 3) integers, the cell the structure's offset (0, 0, 0) lands on, each in [-2^22, 2^22);
+        rots: K quarter turns about +y in 0..3 (None: none), turning an offset (dx, dy, dz) into (dz, dy, -dx) each.
+        Returns device tensors (coords (N, 3) int32, colours (N) int32[, placements (N) int32]): placement by placement, the
+        structure's voxels in their order, those outside the `depth` grid clipped.  The list is what edit_nodes and
+        build_nodes take: a later placement wins a shared cell, a colour of 0 removes the cell."""
+        dev = self.gpu.torch_device
+        offsets, colours = structure.on(dev)
+        org = device_u32(origins, dev, what="origins", signed=True)
+        if org.dim() != 2 or org.shape[1] != 3:
+            raise ValueError(f"origins must be (K, 3), got {tuple(org.shape)}")
+        k, m = org.shape[0], offsets.shape[0]
+        rot = device_u32(rots, dev, what="rots", clamp=True).reshape(-1) if rots is not None else None
+        if rot is not None and rot.numel() != k:
+            raise ValueError(f"{rot.numel()} rotations for {k} placements")
+        p = StampParams()
+        p.depth = self._depth(depth)
+        args = (offsets.data_ptr() if m else None, colours.data_ptr() if m else None, m, org.data_ptr() if k else None,
+                rot.data_ptr() if rot is not None and k else None, k)
+        n = C.c_uint64(k * m)
+        wait_for_torch(self.gpu)
+        if n.value > ONE_CALL_ENTRIES:
+            self.gpu.check(lib().svo_structures_stamp(self.gpu._h, C.byref(p), *args, None, None, None, C.byref(n)))  # the count
+        room = n.value
+        coords = torch.empty((room, 3), dtype=torch.int32, device=dev)
+        out_colours = torch.empty(room, dtype=torch.int32, device=dev)
+        placements = torch.empty(room, dtype=torch.int32, device=dev) if with_placement else None
+        if room:
+            p.max_voxels = room
+            wait_for_torch(self.gpu)
+            self.gpu.check(lib().svo_structures_stamp(self.gpu._h, C.byref(p), *args, coords.data_ptr(), out_colours.data_ptr(),
+                                                      placements.data_ptr() if with_placement else None, C.byref(n)))
+        self.gpu.sync()  # (the inputs may be released by the caller)
+        out = (coords[:n.value], out_colours[:n.value]) + ((placements[:n.value],) if with_placement else ())
+        return out
+
+    def place_structures(self, structure, origins, depth=None, rots=None, max_words=None):
+        """stamp_structures, then edit_nodes with the list: the structure put into the tree at every origin, in place.
+        Returns the new length (node_length)."""
+        depth = self._depth(depth)
+        coords, colours = self.stamp_structures(structure, origins, depth, rots)
+        return self.edit_nodes(coords, depth, colours, max_words=max_words)
+
+    def scatter_structures(self, structure, origin_xz, size_xz, one_in, seed=0, depth=None, y_range=None, on_value=0, lift=1,
+                           rotate=True, max_words=None):
+        """A structure scattered over the ground of a rectangle without the tree leaving the device: column_tops, then
+        structure_sites, then place_structures.  Returns the sites (origins, rots) and leaves node_length as edit_nodes
+        does."""
+        depth = self._depth(depth)
+        tops, values = self.column_tops(origin_xz, size_xz, depth, y_range, with_values=True)
+        origins, rots = self.structure_sites(tops, values, origin_xz, one_in, seed, on_value, lift, rotate)
+        self.place_structures(structure, origins, depth, rots, max_words)
+        return origins, rots
 
     def build_nodes_dense(self, grid, max_words=None):
         """Build the tree of a dense (side, side, side) colour grid indexed [x, y, z] (non-zero = voxel, low 24 bits the
