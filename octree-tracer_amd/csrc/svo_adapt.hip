@@ -312,33 +312,32 @@ __global__ __launch_bounds__(kThreads) void unsub_apply_kernel(Tree t, const uin
 // A frontier entry is node index | depth << 27: an index is below 2^27 (SVO_VOXEL_OFFSET), a depth at most 31.
 constexpr uint32_t kDepthShift = 27, kIndexMask = (1u << kDepthShift) - 1u;
 
-// A stable compaction of the words in[0, n), in tiles of kTile with kPer consecutive words per lane: the count kernel sums
-// keep(word) per tile, tile_offsets_kernel scans the sums, and the emit kernel calls emit(i, word, rank) for every kept
-// word, which it holds in registers from the test on.
-template <class Keep>
-__global__ __launch_bounds__(kThreads) void compact_count_kernel(const uint32_t *in, uint32_t n, Keep keep, uint32_t *tile_sum) {
-    const uint32_t i0 = blockIdx.x * kTile + threadIdx.x * kPer;
-    uint32_t c = 0;
-    for (uint32_t j = 0; j < kPer; j++)
-        if (i0 + j < n && keep(in[i0 + j])) c++;
-    uint32_t total;
-    block_exclusive_scan<kThreads>(c, &total);
-    if (threadIdx.x == 0) tile_sum[blockIdx.x] = total;
-}
+// A stable compaction of the words in[0, n) as a tile pass (svo_scan.h), its items and its emit in one: the state is a
+// thread's words and the mask of those that keep(word) keeps, and emit(i, word, rank) is called for every kept word, which
+// is in registers from the test on.
+struct KeptWords {
+    uint32_t w[kPer], kept;
+};
 
 template <class Keep, class Emit>
-__global__ __launch_bounds__(kThreads) void compact_emit_kernel(const uint32_t *in, uint32_t n, Keep keep, Emit emit,
-                                                                const uint32_t *tile_off) {
-    const uint32_t i0 = blockIdx.x * kTile + threadIdx.x * kPer;
-    uint32_t w[kPer], kept = 0;
-    for (uint32_t j = 0; j < kPer; j++) {
-        w[j] = i0 + j < n ? in[i0 + j] : 0u;
-        if (i0 + j < n && keep(w[j])) kept |= 1u << j;
+struct Compaction {
+    const uint32_t *in;
+    Keep keep;
+    Emit emit;
+    __device__ KeptWords load(uint32_t i0, uint32_t n) const {
+        KeptWords s{};
+        for (uint32_t j = 0; j < kPer; j++) {
+            s.w[j] = i0 + j < n ? in[i0 + j] : 0u;
+            if (i0 + j < n && keep(s.w[j])) s.kept |= 1u << j;
+        }
+        return s;
     }
-    uint32_t r = block_exclusive_scan<kThreads>(__popc(kept), nullptr) + tile_off[blockIdx.x];
-    for (uint32_t j = 0; j < kPer; j++)
-        if ((kept >> j) & 1u) emit(i0 + j, w[j], r++);
-}
+    __device__ uint32_t count(const KeptWords &s) const { return __popc(s.kept); }
+    __device__ void operator()(const Compaction &, uint32_t i0, const KeptWords &s, uint32_t r) const {
+        for (uint32_t j = 0; j < kPer; j++)
+            if ((s.kept >> j) & 1u) emit(i0 + j, s.w[j], r++);
+    }
+};
 
 // The initial frontier: every leaf of [0, len) with the depth of the walk to its position, in index order.  The count
 // only tests the words, the emit walks.
@@ -603,7 +602,7 @@ int subdivide_pass(svo_ctx *ctx, uint32_t n, uint32_t limit, svo_adaptive_result
     }
     // ranks among the successes; flag[n] = 0 makes flag[n] the total after the scan
     HIP_TRY(ctx, hipMemsetAsync(a->flag + n, 0, sizeof(uint32_t), ctx->stream));
-    if ((rc = svo_build_scan_u32(ctx, a->flag, n + 1))) return rc;
+    if ((rc = svo_scan_u32(ctx, a->flag, n + 1))) return rc;
     if (a->n_holes)
         sub_popped_kernel<<<svo_div_up(std::min(n, a->n_holes), kThreads), kThreads, 0, ctx->stream>>>(a->holes, a->n_holes, list, n,
                                                                                                        a->flag + n, a->st.dev);
@@ -652,7 +651,7 @@ int unsubdivide_pass(svo_ctx *ctx, uint32_t n, svo_adaptive_result *out) {
         HIP_TRY(ctx, hipGetLastError());
     }
     HIP_TRY(ctx, hipMemsetAsync(a->flag + n, 0, sizeof(uint32_t), ctx->stream));
-    if ((rc = svo_build_scan_u32(ctx, a->flag, n + 1))) return rc;
+    if ((rc = svo_scan_u32(ctx, a->flag, n + 1))) return rc;
     if ((rc = read_status(ctx, a->flag + n))) return rc;
     if (a->st.host()->err != kNone) return entry_fail(ctx, SVO_ERR_STATE, a->st.host()->err, "unsubdivide");
     const uint32_t done = a->st.host()->total;
@@ -701,10 +700,8 @@ int timed_compaction(svo_ctx *ctx, int stage, const uint32_t *in, uint32_t n, Ke
     int rc = svo_grow(ctx, nt + 1, &a->tiles);
     if (rc || (rc = clear_status(ctx))) return rc;
     HIP_TRY(ctx, hipEventRecord(a->ev[0], ctx->stream));
-    compact_count_kernel<<<nt, kThreads, 0, ctx->stream>>>(in, n, keep, a->tiles);
-    tile_offsets_kernel<<<1, kTopThreads, 0, ctx->stream>>>(a->tiles, nt, nullptr, 0, &a->st.dev->total);
-    compact_emit_kernel<<<nt, kThreads, 0, ctx->stream>>>(in, n, keep, emit, a->tiles);
-    HIP_TRY(ctx, hipGetLastError());
+    const Compaction<Keep, Emit> pass{in, keep, emit};
+    if ((rc = svo_tile_pass(ctx, pass, pass, nt, nullptr, n, a->tiles, &a->st.dev->total))) return rc;
     HIP_TRY(ctx, hipEventRecord(a->ev[1], ctx->stream));
     if ((rc = read_status(ctx, nullptr))) return rc;
     float ms = 0.0f;

@@ -7,8 +7,8 @@
 //            coordinate outside [0, 2^depth) sets the error word
 //   sort     stable LSD radix sort, 8-bit digits: per-tile digit counts, one scan of the counts, a stable scatter that
 //            ranks a tile's items with wave64 ballots.  Stability keeps equal keys in input order
-//   levels   per level a flag on the LAST element of every run of equal keys, a scan of the flags (tile counts, one
-//            block over the tile counts, tile re-scan) and a compaction to the next level up.  The first pass (leaf
+//   levels   per level a flag on the LAST element of every run of equal keys, a scan of the flags and a compaction to
+//            the next level up, as one tile pass of svo_scan.h (Level<M>, LevelEmit<M>).  The first pass (leaf
 //            level) keeps the last voxel of a run of equal cells: repeated put(), last one wins.  The counts of all
 //            levels are read back in one copy and checked against the cap before anything is written
 //   emit     the level passes again, top level last, now also writing every node's slot,
@@ -23,10 +23,10 @@
 // nodes per chunk, which the shared mip pass (svo_mip.h) colours bottom-up before they are staged chunk by chunk.
 //
 // The list entry points share one front end (check_list, list_leaves: keys, sort, leaf pass), level_bounds and
-// read_counts.  Shared with the other passes: the tile shape and scans (svo_scan.h), the Morton convention
-// (svo_morton.h), mip_of and the mip pass (svo_mip.h), svo_grow (svo_ctx.h).  This file also holds what the others
-// borrow: svo_build_sort_u32 / svo_build_scan_u32 (svo_adapt.hip), svo_build_list_leaves (svo_edit.hip) and svo_world_writer, the one place that lays out a
-// generated world's directory (svo_world_build here, svo_world_generate in svo_proc.hip).
+// read_counts.  Shared with the other passes: the tile pass and svo_scan_u32 (svo_scan.h), the Morton convention
+// (svo_morton.h), mip_of and the mip pass (svo_mip.h), svo_grow (svo_ctx.h).  This file also holds what the others borrow:
+// svo_build_sort_u32 (svo_adapt.hip), svo_build_list_leaves (svo_edit.hip) and svo_world_writer, the one place that lays
+// out a generated world's directory (svo_world_build here, svo_world_generate in svo_proc.hip).
 #include <hip/hip_runtime.h>
 
 #include <sys/stat.h>
@@ -144,31 +144,6 @@ __global__ __launch_bounds__(kThreads) void build_scatter_kernel(const uint64_t 
     }
 }
 
-// ---- generic exclusive scan of a u32 array (the digit counts), tiles of kTile ----
-__global__ __launch_bounds__(kThreads) void build_sum_kernel(const uint32_t *a, uint32_t n, uint32_t *tile_sum) {
-    const uint32_t i0 = blockIdx.x * kTile + threadIdx.x * kPer;
-    uint32_t s = 0;
-    for (uint32_t j = 0; j < kPer; j++)
-        if (i0 + j < n) s += a[i0 + j];
-    uint32_t total;
-    block_exclusive_scan<kThreads>(s, &total);
-    if (threadIdx.x == 0) tile_sum[blockIdx.x] = total;
-}
-
-__global__ __launch_bounds__(kThreads) void build_add_kernel(uint32_t *a, uint32_t n, const uint32_t *tile_off) {
-    const uint32_t i0 = blockIdx.x * kTile + threadIdx.x * kPer;
-    uint32_t v[kPer], s = 0;
-    for (uint32_t j = 0; j < kPer; j++) {
-        v[j] = i0 + j < n ? a[i0 + j] : 0u;
-        s += v[j];
-    }
-    uint32_t r = block_exclusive_scan<kThreads>(s, nullptr) + tile_off[blockIdx.x];
-    for (uint32_t j = 0; j < kPer; j++) {
-        if (i0 + j < n) a[i0 + j] = r;
-        r += v[j];
-    }
-}
-
 // ---- levels: flags, scans, compaction, emit ----
 struct LevelIn {
     const uint64_t *keys;     // kDedupe: sorted keys; kParent: this level's unique keys
@@ -201,87 +176,87 @@ struct LevelOut {
     uint32_t cshift, level, stride;  // level: this level's chunk-local number L
 };
 
-// Loads thread t's 16 consecutive items and their flags (bit j: item i0 + j ends a run / is kept).
+// A thread's 16 consecutive items of the m live ones: their keys and flags (bit j: item i0 + j ends a run / is kept).
+struct LevelItems {
+    uint64_t k[kPer];
+    uint32_t f, m;
+};
+
+// The tile pass's items (svo_scan.h) of a level in mode M.
 template <int M>
-__device__ inline uint32_t load_flags(const LevelIn &in, uint32_t m, uint32_t i0, uint64_t *k) {
-    uint32_t f = 0;
-    if (M == kDense) {
-        const uint32_t side = 1u << in.depth;
+struct Level {
+    LevelIn in;
+    __device__ LevelItems load(uint32_t i0, uint32_t m) const {
+        LevelItems s;
+        s.f = 0;
+        s.m = m;
+        if (M == kDense) {
+            const uint32_t side = 1u << in.depth;
+            for (uint32_t j = 0; j < kPer; j++) {
+                const uint32_t i = i0 + j;
+                s.k[j] = 0;
+                if (i >= m) continue;
+                uint32_t x, y, z;
+                morton_decode(i, in.depth, x, y, z);
+                const uint32_t c = in.colours[(size_t(x) * side + y) * side + z];
+                s.k[j] = i | uint64_t(c) << 32;  // (the cell's value rides in the high half)
+                if (c) s.f |= 1u << j;
+            }
+            return s;
+        }
+        const uint32_t shift = M == kParent || M == kChunk ? 3u : 0u;
+        for (uint32_t j = 0; j < kPer; j++) s.k[j] = i0 + j < m ? in.keys[i0 + j] : 0ull;
+        const uint64_t after = i0 + kPer < m ? in.keys[i0 + kPer] : 0ull;
         for (uint32_t j = 0; j < kPer; j++) {
             const uint32_t i = i0 + j;
-            k[j] = 0;
-            if (i >= m) continue;
-            uint32_t x, y, z;
-            morton_decode(i, in.depth, x, y, z);
-            const uint32_t c = in.colours[(size_t(x) * side + y) * side + z];
-            k[j] = i | uint64_t(c) << 32;  // (the cell's value rides in the high half)
-            if (c) f |= 1u << j;
+            if (i >= m) break;
+            const bool end = i + 1 == m || (s.k[j] >> shift) != ((j + 1 < kPer ? s.k[j + 1] : after) >> shift);
+            s.f |= uint32_t(end) << j;
         }
-        return f;
+        return s;
     }
-    const uint32_t shift = M == kParent || M == kChunk ? 3u : 0u;
-    for (uint32_t j = 0; j < kPer; j++) k[j] = i0 + j < m ? in.keys[i0 + j] : 0ull;
-    const uint64_t after = i0 + kPer < m ? in.keys[i0 + kPer] : 0ull;
-    for (uint32_t j = 0; j < kPer; j++) {
-        const uint32_t i = i0 + j;
-        if (i >= m) break;
-        const bool end = i + 1 == m || (k[j] >> shift) != ((j + 1 < kPer ? k[j + 1] : after) >> shift);
-        f |= uint32_t(end) << j;
-    }
-    return f;
-}
+    __device__ uint32_t count(const LevelItems &s) const { return __popc(s.f); }
+};
 
+// Its emit: the compaction of the flagged items to the next level up and, in an emitting pass, every item's node.
 template <int M>
-__global__ __launch_bounds__(kThreads) void build_count_kernel(LevelIn in, uint32_t *tile_sum) {
-    const uint32_t m = input_count(in.m_dev, in.m_max);
-    if (blockIdx.x * kTile >= m) return;  // (the grid covers the bound; the top kernel reads only the live tiles)
-    uint64_t k[kPer];
-    const uint32_t f = load_flags<M>(in, m, blockIdx.x * kTile + threadIdx.x * kPer, k);
-    uint32_t total;
-    block_exclusive_scan<kThreads>(__popc(f), &total);
-    if (threadIdx.x == 0) tile_sum[blockIdx.x] = total;
-}
-
-template <int M>
-__global__ __launch_bounds__(kThreads) void build_compact_kernel(LevelIn in, const uint32_t *tile_off, LevelOut out) {
-    const uint32_t m = input_count(in.m_dev, in.m_max);
-    if (blockIdx.x * kTile >= m) return;
-    const uint32_t i0 = blockIdx.x * kTile + threadIdx.x * kPer;
-    uint64_t k[kPer];
-    const uint32_t f = load_flags<M>(in, m, i0, k);
-    uint32_t r = block_exclusive_scan<kThreads>(__popc(f), nullptr) + tile_off[blockIdx.x];
-    for (uint32_t j = 0; j < kPer; j++) {
-        const uint32_t i = i0 + j;
-        if (i >= m) break;
-        if (M == kParent && out.words) {  // node i of this level: its parent's rank is r
-            const uint32_t dst = out.base + 8u * r + uint32_t(k[j] & 7u);
-            const uint32_t word = out.last ? (SVO_VOXEL_OFFSET + (in.vals[i] & 0xFFFFFFu)) << 4 : (out.base_next + 8u * i) << 4;
-            if (dst < out.n_words) out.words[dst] = word;  // (always: the counts and the ranks come from the same flags)
-        }
-        if (M == kChunk && out.nodes) {  // node i of this level, in chunk c: its parent's rank within the chunk is r - start_up[c]
-            const uint32_t c = uint32_t(k[j] >> out.cshift);
-            const uint32_t *b = out.cbase + size_t(c) * out.stride;
-            const uint64_t dst = out.coff[c] + b[out.level] + 8u * (r - out.start_up[c]) + uint32_t(k[j] & 7u);
-            uint2 node;
-            if (out.last) {  // leaf: SVO_CHUNK_OFFSET, r g b of 0x00RRGGBB (Rgb::cpu_value)
-                const uint32_t v = in.vals[i];
-                node = make_uint2(SVO_CHUNK_OFFSET, (v >> 16 & 0xFFu) | (v & 0xFF00u) | (v & 0xFFu) << 16);
-            } else {  // interior: its child group, behind this level in the chunk; rgb comes from the mip pass
-                node = make_uint2(b[out.level + 1] + 8u * (i - out.start_here[c]), 0u);
+struct LevelEmit {
+    LevelOut out;
+    __device__ void operator()(const Level<M> &level, uint32_t i0, const LevelItems &s, uint32_t r) const {
+        const LevelIn &in = level.in;
+        for (uint32_t j = 0; j < kPer; j++) {
+            const uint32_t i = i0 + j;
+            if (i >= s.m) break;
+            if (M == kParent && out.words) {  // node i of this level: its parent's rank is r
+                const uint32_t dst = out.base + 8u * r + uint32_t(s.k[j] & 7u);
+                const uint32_t word = out.last ? (SVO_VOXEL_OFFSET + (in.vals[i] & 0xFFFFFFu)) << 4 : (out.base_next + 8u * i) << 4;
+                if (dst < out.n_words) out.words[dst] = word;  // (always: the counts and the ranks come from the same flags)
             }
-            if (dst < out.n_nodes) out.nodes[dst] = node;  // (always, as above)
-        }
-        if ((f >> j) & 1u) {
-            if (r < out.cap) {
-                out.keys[r] = M == kParent || M == kChunk ? k[j] >> 3 : (M == kDense ? k[j] & 0xFFFFFFFFu : k[j]);
-                if (M == kDedupe) out.colours[r] = (in.colours ? in.colours[in.vals[i]] : in.colour) & 0xFFFFFFu;
-                if (M == kDedupe && out.index) out.index[r] = in.vals[i];
-                if (M == kDense) out.colours[r] = uint32_t(k[j] >> 32) & 0xFFFFFFu;
+            if (M == kChunk && out.nodes) {  // node i of this level, in chunk c: its parent's rank within the chunk is r - start_up[c]
+                const uint32_t c = uint32_t(s.k[j] >> out.cshift);
+                const uint32_t *b = out.cbase + size_t(c) * out.stride;
+                const uint64_t dst = out.coff[c] + b[out.level] + 8u * (r - out.start_up[c]) + uint32_t(s.k[j] & 7u);
+                uint2 node;
+                if (out.last) {  // leaf: SVO_CHUNK_OFFSET, r g b of 0x00RRGGBB (Rgb::cpu_value)
+                    const uint32_t v = in.vals[i];
+                    node = make_uint2(SVO_CHUNK_OFFSET, (v >> 16 & 0xFFu) | (v & 0xFF00u) | (v & 0xFFu) << 16);
+                } else {  // interior: its child group, behind this level in the chunk; rgb comes from the mip pass
+                    node = make_uint2(b[out.level + 1] + 8u * (i - out.start_here[c]), 0u);
+                }
+                if (dst < out.n_nodes) out.nodes[dst] = node;  // (always, as above)
             }
-            r++;
+            if ((s.f >> j) & 1u) {
+                if (r < out.cap) {
+                    out.keys[r] = M == kParent || M == kChunk ? s.k[j] >> 3 : (M == kDense ? s.k[j] & 0xFFFFFFFFu : s.k[j]);
+                    if (M == kDedupe) out.colours[r] = (in.colours ? in.colours[in.vals[i]] : in.colour) & 0xFFFFFFu;
+                    if (M == kDedupe && out.index) out.index[r] = in.vals[i];
+                    if (M == kDense) out.colours[r] = uint32_t(s.k[j] >> 32) & 0xFFFFFFu;
+                }
+                r++;
+            }
         }
     }
-}
+};
 
 // ---- chunk trees ----
 // The runs of a level's sorted unique keys per chunk (c = key >> shift < n_chunks): start[c] = the first index of chunk c,
@@ -343,7 +318,7 @@ struct svo_build_state {
     svo_dev<uint32_t> leaf_colours;
     size_t items() const { return leaf_colours.size(); }  // room in every one of them (the last one allocated)
     svo_dev<uint32_t> hist;   // the sort's digit counts, 256 per tile
-    svo_dev<uint32_t> tiles;  // tile sums / offsets of a scan
+    svo_dev<uint32_t> tiles;  // tile sums / offsets of a level pass
     svo_mirrored<> counts;      // kCountSlots words: unique nodes per level, error word
     svo_pass_timer<kEvs, SVO_BUILD_TIMES> timer;  // (spans: kBuildSlots, the sort's only when the last build sorted)
     // chunk trees (svo_world_build, svo_cpu_octree_build)
@@ -363,7 +338,7 @@ struct svo_build_state {
 
 namespace {
 
-// workspace for `items` keys (and the tile sums of scans over at most `scan_items` items)
+// workspace for `items` keys (and the tile sums of level passes over at most `scan_items` items)
 int ensure_state(svo_ctx *ctx, size_t items, size_t scan_items, size_t hist_items) {
     int rc = svo_workspace_ensure(ctx, ctx->build);
     if (rc) return rc;
@@ -374,17 +349,6 @@ int ensure_state(svo_ctx *ctx, size_t items, size_t scan_items, size_t hist_item
     return rc;
 }
 
-// Exclusive scan of hist[0, n) in place.
-int scan_u32(svo_ctx *ctx, uint32_t *a, uint32_t n) {
-    svo_build_state *s = ctx->build.get();
-    const uint32_t nt = svo_div_up(n, kTile);
-    build_sum_kernel<<<nt, kThreads, 0, ctx->stream>>>(a, n, s->tiles);
-    tile_offsets_kernel<<<1, kTopThreads, 0, ctx->stream>>>(s->tiles, nt, nullptr, 0, s->counts.dev + kErrSlot + 1);
-    build_add_kernel<<<nt, kThreads, 0, ctx->stream>>>(a, n, s->tiles);
-    HIP_TRY(ctx, hipGetLastError());
-    return SVO_OK;
-}
-
 // `passes` stable 8-bit radix passes over the n items in keys[0] / vals[0]; the result is in keys[passes & 1] / vals[passes & 1].
 int sort_passes(svo_ctx *ctx, uint32_t n, uint32_t passes) {
     svo_build_state *s = ctx->build.get();
@@ -393,7 +357,7 @@ int sort_passes(svo_ctx *ctx, uint32_t n, uint32_t passes) {
         const uint32_t a = k & 1;
         build_hist_kernel<<<nt, kThreads, 0, ctx->stream>>>(s->keys[a], n, 8 * k, s->hist, nt);
         HIP_TRY(ctx, hipGetLastError());
-        int rc = scan_u32(ctx, s->hist, 256 * nt);
+        int rc = svo_scan_u32(ctx, s->hist, 256 * nt);
         if (rc) return rc;
         build_scatter_kernel<<<nt, kThreads, 0, ctx->stream>>>(s->keys[a], s->vals[a], n, 8 * k, s->hist, nt, s->keys[a ^ 1],
                                                                s->vals[a ^ 1]);
@@ -402,17 +366,13 @@ int sort_passes(svo_ctx *ctx, uint32_t n, uint32_t passes) {
     return SVO_OK;
 }
 
-// One level pass: flags, tile counts, scan (the total goes to *total), compaction (and, with out.words, emit).
+// One level pass: flags, tile counts, scan (the total goes to *total), compaction (and, with out.words or out.nodes, emit).
 // `bound` is the host's bound of the input count: the grid covers it.
 template <int M>
 int level_pass(svo_ctx *ctx, const LevelIn &in, const LevelOut &out, uint64_t bound, uint32_t *total) {
     svo_build_state *s = ctx->build.get();
     const uint32_t nt = std::max(svo_div_up(bound, kTile), 1u);
-    build_count_kernel<M><<<nt, kThreads, 0, ctx->stream>>>(in, s->tiles);
-    tile_offsets_kernel<<<1, kTopThreads, 0, ctx->stream>>>(s->tiles, nt, in.m_dev, in.m_max, total);
-    build_compact_kernel<M><<<nt, kThreads, 0, ctx->stream>>>(in, s->tiles, out);
-    HIP_TRY(ctx, hipGetLastError());
-    return SVO_OK;
+    return svo_tile_pass(ctx, Level<M>{in}, LevelEmit<M>{out}, nt, in.m_dev, in.m_max, s->tiles, total);
 }
 
 // A chunked build: chunk c of level L's keys is key >> 3 * (L - world_depth).  Counting passes (nodes null)
@@ -505,7 +465,7 @@ uint64_t word_limit(const svo_ctx *ctx, const svo_build_params *p) {
 int list_leaves(svo_ctx *ctx, const uint32_t *xyz, const uint32_t *colours, size_t n, uint32_t depth, uint32_t default_colour,
                 size_t runs_items, bool keep_index = false) {
     const uint32_t nt = svo_div_up(n, kTile);
-    int rc = ensure_state(ctx, n, std::max<uint64_t>(n, 256ull * nt), 256ull * nt);
+    int rc = ensure_state(ctx, n, n, 256ull * nt);
     if (rc) return rc;
     svo_build_state *s = ctx->build.get();
     if ((rc = svo_grow(ctx, runs_items, &s->runs))) return rc;
@@ -622,11 +582,11 @@ __global__ __launch_bounds__(kThreads) void build_narrow_kernel(const uint64_t *
 
 }  // namespace
 
-// The radix sort and the scan above, for other passes on the ctx stream (svo_adapt.hip sorts its node lists with them).
+// The radix sort above, for other passes on the ctx stream (svo_adapt.hip sorts its node lists with it).
 int svo_build_sort_u32(svo_ctx *ctx, const uint32_t *in, uint32_t n, uint32_t *out) {
     if (!n) return SVO_OK;
     const uint32_t nt = svo_div_up(n, kTile), grid = svo_div_up(n, kThreads);
-    int rc = ensure_state(ctx, n, std::max<uint64_t>(n, 256ull * nt), 256ull * nt);
+    int rc = ensure_state(ctx, n, 0, 256ull * nt);
     if (rc) return rc;
     svo_build_state *s = ctx->build.get();
     build_widen_kernel<<<grid, kThreads, 0, ctx->stream>>>(in, n, s->keys[0], s->vals[0]);
@@ -635,13 +595,6 @@ int svo_build_sort_u32(svo_ctx *ctx, const uint32_t *in, uint32_t n, uint32_t *o
     build_narrow_kernel<<<grid, kThreads, 0, ctx->stream>>>(s->keys[0], n, out);
     HIP_TRY(ctx, hipGetLastError());
     return SVO_OK;
-}
-
-int svo_build_scan_u32(svo_ctx *ctx, uint32_t *a, uint32_t n) {
-    if (!n) return SVO_OK;
-    int rc = ensure_state(ctx, 0, n, 0);
-    if (rc) return rc;
-    return scan_u32(ctx, a, n);
 }
 
 // The list front end for other passes (svo_edit.hip): the argument checks of the list entry points, then keys, sort and

@@ -5,7 +5,7 @@
 // read, and its interior mask is its byte of the wave's ballot.
 //
 //   discover  top-down, one launch set per level: the frontier (old group starts, order[off .. off + F)) counts its
-//             interior words per group, an exclusive scan of the counts (the builder's scan) gives every group the place
+//             interior words per group, an exclusive scan of the counts (svo_scan_u32)       gives every group the place
 //             of its first child in the next frontier, and the scatter appends the children behind the frontier at
 //             scan + (interior lanes below), which keeps the order of the parents.  first_child[k] = the index in `order`
 //             of group k's first interior child.  A pointer that is no multiple of 8 or leaves the words sets a status
@@ -28,7 +28,7 @@
 
 #include "svo_ctx.h"
 #include "svo_group.h"  // (group_lane: 8 lanes per group; kMaxWords)
-#include "svo_scan.h"   // (kThreads)
+#include "svo_scan.h"   // (svo_scan_u32)
 
 namespace {
 
@@ -158,7 +158,7 @@ int svo_tree_discover(svo_ctx *ctx, uint64_t n_words_in, svo_tree_walk *w, hipEv
         const uint32_t grid = svo_div_up(8ull * n, kThreads);
         compact_count_kernel<<<grid, kThreads, 0, ctx->stream>>>(ctx->nodes, n_words, w->order + off, n, w->scan, w->status.dev);
         HIP_TRY(ctx, hipGetLastError());
-        if ((rc = svo_build_scan_u32(ctx, w->scan, n))) return rc;
+        if ((rc = svo_scan_u32(ctx, w->scan, n))) return rc;
         compact_scatter_kernel<<<grid, kThreads, 0, ctx->stream>>>(ctx->nodes, w->order, off, n, w->scan, w->first_child, cap, w->status.dev);
         HIP_TRY(ctx, hipGetLastError());
         if ((rc = w->status.read(ctx))) return rc;
@@ -237,7 +237,7 @@ int svo_nodes_compact(svo_ctx *ctx, const svo_compact_params *p, uint32_t *perm_
 
     // emit
     HIP_TRY(ctx, hipMemcpyAsync(s->number, s->live, total * sizeof(uint32_t), hipMemcpyDeviceToDevice, ctx->stream));
-    if ((rc = svo_build_scan_u32(ctx, s->number, total))) return rc;
+    if ((rc = svo_scan_u32(ctx, s->number, total))) return rc;
     compact_total_kernel<<<1, 1, 0, ctx->stream>>>(s->number, s->live, total, s->status.dev);
     HIP_TRY(ctx, hipGetLastError());
     if ((rc = s->status.read(ctx))) return rc;

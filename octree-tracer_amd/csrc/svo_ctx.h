@@ -5,10 +5,10 @@
 // holds, as svo_dev / svo_pinned (an allocation and its size), svo_events (events) or svo_stream (a stream).  The passes
 // share the rest as their host frame: svo_grow / svo_grow_pinned / svo_grow_keep (workspaces, by the buffers' own
 // sizes), svo_mirrored (device words with a pinned mirror), svo_pass_timer (events and times), svo_workspace_ensure
-// (creation) and the svo_check_* argument checks; then the builder's sort and scan and svo_world_writer (a generated
-// world's directory).
-// svo_scan.h, svo_group.h, svo_mip.h and svo_morton.h hold the device pieces, svo_rules.h the walks and rules that
-// svo_host.cpp and svo_adapt.hip both run.
+// (creation) and the svo_check_* argument checks; then the builder's sort and svo_world_writer (a generated world's
+// directory).
+// svo_scan.h (the tiled count, scan and emit with their launches), svo_group.h, svo_mip.h and svo_morton.h hold the device
+// pieces, svo_rules.h the walks and rules that svo_host.cpp and svo_adapt.hip both run.
 // Internal: not part of the boundary.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -189,6 +189,7 @@ struct svo_ctx {
     bool scan_clears = false;
     int fused_shadows = 2;  // 0: off, 1: on, 2: automatic (see fuse_shadow_rays)
     svo_dev<uint32_t> scatter_buf;  // svo_nodes_scatter: indices, then values
+    svo_dev<uint32_t> scan_tiles;   // svo_scan_u32 (svo_scan.h): the tile sums of an in-place scan, whichever pass asks
     uint32_t block_w_log2 = 3;  // 64-pixel blocks of 8x8
     uint32_t tree_depth = 16;  // caller's bound on the octree depth (the reference's Settings.octree_depth)
     // scheduling feedback (strip order from an earlier frame of the same work layout); slot 1: shadow rays.  What is decided per
@@ -411,10 +412,9 @@ int svo_store_note_write(svo_ctx *ctx);
 // svo_comm.cpp
 void svo_comm_release(svo_ctx *ctx);
 // svo_build.hip
-// the builder's stable radix sort of n u32 keys (in -> out, may alias) and in-place exclusive scan of n u32, for other
-// passes on the ctx stream; both use the builder's workspace
+// the builder's stable radix sort of n u32 keys (in -> out, may alias), for other passes on the ctx stream; it uses the
+// builder's workspace
 int svo_build_sort_u32(svo_ctx *ctx, const uint32_t *in, uint32_t n, uint32_t *out);
-int svo_build_scan_u32(svo_ctx *ctx, uint32_t *a, uint32_t n);
 // the front end of the builder's list entry points, for other passes over a voxel list (svo_edit.hip): the checks of
 // depth (null: no params), n and xyz with the builder's messages, then keys, the stable sort and the leaf pass on the ctx
 // stream.  Everything in svo_build_leaves lives in the builder's workspace and holds until the next call that uses it.

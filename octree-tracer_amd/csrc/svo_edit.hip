@@ -10,7 +10,7 @@
 //            level of the leaf the host finds when it gets to voxel k: every earlier voxel split the path down to the
 //            prefix it shares with k, and in Morton order no earlier voxel shares more with k than its predecessor.
 //            Voxel k creates depth - l groups
-//   scan     exclusive scan of the group counts (the builder's scan): start_k.  One block then finds the first voxel
+//   scan     exclusive scan of the group counts (svo_scan_u32): start_k.  One block then finds the first voxel
 //            that cannot be taken and the total; both come back with the counts in one small copy, and the cap is
 //            checked on the host before anything is written
 //   fill     the new groups [n_words, n_words + 8 * total) become empty words
@@ -27,7 +27,7 @@
 
 #include "svo_ctx.h"
 #include "svo_morton.h"  // (the key's convention; the refused voxel's cell)
-#include "svo_scan.h"    // (kThreads, block_exclusive_scan, input_count; svo_group.h: kEmptyWord, kMaxWords)
+#include "svo_scan.h"    // (svo_scan_u32, block_exclusive_scan, input_count; svo_group.h: kEmptyWord, kMaxWords)
 
 namespace {
 
@@ -193,7 +193,7 @@ int svo_nodes_edit(svo_ctx *ctx, const uint32_t *xyz, const uint32_t *colours, s
     if ((rc = svo_store_order_after_write(ctx))) return rc;
     edit_plan_kernel<<<n_blocks, kThreads, 0, ctx->stream>>>(ctx->nodes, n_words, lv.keys, lv.count, bound, depth, lvl, start, at, bad);
     HIP_TRY(ctx, hipGetLastError());
-    if ((rc = svo_build_scan_u32(ctx, start, bound))) return rc;
+    if ((rc = svo_scan_u32(ctx, start, bound))) return rc;
     edit_status_kernel<<<1, kTopThreads, 0, ctx->stream>>>(bad, n_blocks, lv.count, bound, lv.range_err, depth, lvl, start, lv.keys,
                                                           lv.index, s->status.dev);
     HIP_TRY(ctx, hipGetLastError());

@@ -27,9 +27,8 @@
 #include <vector>
 
 #include "svo_ctx.h"
-#include "svo_group.h"   // (group_lane: 8 lanes per group; kMaxWords)
+#include "svo_group.h"   // (kThreads; group_lane: 8 lanes per group; kMaxWords)
 #include "svo_morton.h"  // (morton_decode)
-#include "svo_scan.h"    // (kThreads)
 
 namespace {
 

@@ -6,14 +6,14 @@
 //   classify   one lane per cell, lanes in Morton order (a wave64 covers a 4x4x4 brick): sdf, "above" sdf for solid
 //              cells, one class byte per cell; __ballot(solid) is the child masks of the brick's 8 parents
 //   reduce     child masks level by level up to the root (a node is interior iff its mask is non-zero)
-//   ranks      per level, an exclusive scan of the interior flags in Morton order (tile counts, one-block scan of
-//              the tile counts, tile re-scan): every interior node's rank, hence its child group's index, and the
-//              exact node count, which is read back and checked before anything is emitted
+//   ranks      per level, an exclusive scan of the interior flags in Morton order (a tile pass of svo_scan.h): every
+//              interior node's rank, hence its child group's index, and the exact node count, which is read back and
+//              checked before anything is emitted
 //   emit       one lane per interior parent: its 8-node group in the 8-byte <id>.bin layout
 //   mips       (svo_world_generate only) block leaves take their block's top_mip, then svo_mip.h's pass bottom-up
 //
 // All work runs on the context's stream.  Sizes come from the count pass; there are no atomics and no retries.
-// Shared with the tree builder: the tile shape and scans (svo_scan.h), the Morton convention (svo_morton.h), the mip pass
+// Shared with the tree builder: the tile pass (svo_scan.h), the Morton convention (svo_morton.h), the mip pass
 // (svo_mip.h), svo_grow for the workspace and svo_world_writer for svo_world_generate's directory (svo_ctx.h; the writer
 // itself is in svo_build.hip).
 #include <hip/hip_runtime.h>
@@ -166,8 +166,8 @@ __device__ inline uint32_t classify_cell(const ChunkGeom &g, uint32_t x, uint32_
 }
 
 // Lane m = Morton index of the cell.  n_cells is a multiple of 64 (chunk_depth >= 2), so every wave is whole.
-__global__ __launch_bounds__(256) void proc_classify_kernel(ChunkGeom g, uint32_t n_cells, uint8_t *cls, uint8_t *parent_masks) {
-    const uint32_t m = blockIdx.x * 256u + threadIdx.x;
+__global__ __launch_bounds__(kThreads) void proc_classify_kernel(ChunkGeom g, uint32_t n_cells, uint8_t *cls, uint8_t *parent_masks) {
+    const uint32_t m = blockIdx.x * kThreads + threadIdx.x;
     if (m >= n_cells) return;
     uint32_t x, y, z;
     morton_decode(m, g.depth, x, y, z);
@@ -186,8 +186,8 @@ __device__ inline uint32_t nonzero_bytes(uint32_t w) {  // bit 8k set iff byte k
 }
 
 // mask of parent p at level L-1 from the 8 child masks of level L
-__global__ __launch_bounds__(256) void proc_reduce_kernel(const uint8_t *child_masks, uint32_t n_parents, uint8_t *parent_masks) {
-    const uint32_t p = blockIdx.x * 256u + threadIdx.x;
+__global__ __launch_bounds__(kThreads) void proc_reduce_kernel(const uint8_t *child_masks, uint32_t n_parents, uint8_t *parent_masks) {
+    const uint32_t p = blockIdx.x * kThreads + threadIdx.x;
     if (p >= n_parents) return;
     const uint2 v = reinterpret_cast<const uint2 *>(child_masks)[p];
     const uint32_t lo = nonzero_bytes(v.x), hi = nonzero_bytes(v.y);
@@ -196,42 +196,41 @@ __global__ __launch_bounds__(256) void proc_reduce_kernel(const uint8_t *child_m
     parent_masks[p] = (uint8_t)mask;
 }
 
-__device__ inline uint32_t count16(const uint4 q) {
-    return __popc(nonzero_bytes(q.x)) + __popc(nonzero_bytes(q.y)) + __popc(nonzero_bytes(q.z)) + __popc(nonzero_bytes(q.w));
-}
-
-// ranks, phase 1: interior nodes per tile (the level's mask bytes are zero-padded to whole tiles)
-__global__ __launch_bounds__(256) void proc_tile_count_kernel(const uint8_t *masks, uint32_t *tile_sum) {
-    const uint4 q = reinterpret_cast<const uint4 *>(masks)[blockIdx.x * 256u + threadIdx.x];
-    uint32_t total;
-    block_exclusive_scan<256>(count16(q), &total);
-    if (threadIdx.x == 0) tile_sum[blockIdx.x] = total;
-}
-
-// ranks, phase 3: every node's exclusive rank among the interior nodes of its level
-__global__ __launch_bounds__(256) void proc_tile_rank_kernel(const uint8_t *masks, const uint32_t *tile_off, uint32_t *rank) {
-    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
-    const uint4 q = reinterpret_cast<const uint4 *>(masks)[i];
-    uint32_t r = block_exclusive_scan<256>(count16(q), nullptr) + tile_off[blockIdx.x];
-    const uint32_t w[4] = {nonzero_bytes(q.x), nonzero_bytes(q.y), nonzero_bytes(q.z), nonzero_bytes(q.w)};
-    uint4 *out = reinterpret_cast<uint4 *>(rank) + 4u * i;
-    for (int k = 0; k < 4; k++) {
-        uint4 o;
-        o.x = r; r += w[k] & 1u;
-        o.y = r; r += (w[k] >> 8) & 1u;
-        o.z = r; r += (w[k] >> 16) & 1u;
-        o.w = r; r += (w[k] >> 24) & 1u;
-        out[k] = o;
+// The ranks as a tile pass (svo_scan.h) over a level's mask bytes, which are zero-padded to whole tiles: a thread's
+// kPer masks are one uint4, and the interior nodes (non-zero masks) are counted.
+static_assert(kTile == kThreads * sizeof(uint4), "a tile is kThreads uint4 loads of mask bytes");
+struct LevelMasks {
+    const uint8_t *masks;
+    __device__ uint4 load(uint32_t i0, uint32_t) const { return reinterpret_cast<const uint4 *>(masks)[i0 / kPer]; }
+    __device__ uint32_t count(const uint4 &q) const {
+        return __popc(nonzero_bytes(q.x)) + __popc(nonzero_bytes(q.y)) + __popc(nonzero_bytes(q.z)) + __popc(nonzero_bytes(q.w));
     }
-}
+};
+
+// every node's exclusive rank among the interior nodes of its level
+struct WriteRanks {
+    uint32_t *rank;
+    __device__ void operator()(const LevelMasks &, uint32_t i0, const uint4 &q, uint32_t r) const {
+        const uint32_t w[4] = {nonzero_bytes(q.x), nonzero_bytes(q.y), nonzero_bytes(q.z), nonzero_bytes(q.w)};
+        uint4 *out = reinterpret_cast<uint4 *>(rank + i0);
+        for (int k = 0; k < 4; k++) {
+            uint4 o;
+            o.x = r; r += w[k] & 1u;
+            o.y = r; r += (w[k] >> 8) & 1u;
+            o.z = r; r += (w[k] >> 16) & 1u;
+            o.w = r; r += (w[k] >> 24) & 1u;
+            out[k] = o;
+        }
+    }
+};
 
 // One lane per node p of level L-1: an interior p owns the group base_l + 8 * rank(p) of level L.  Its 8 words: an
 // interior child's pointer (base_next + 8 * its rank), CHUNK_OFFSET + class at the last level, CHUNK_OFFSET when empty.
 // Nodes are written in the 8-byte <id>.bin layout (pointer, r g b = 0, pad = 0).
-__global__ __launch_bounds__(256) void proc_emit_kernel(const uint8_t *parent_masks, const uint32_t *parent_rank, uint32_t n_parents,
+__global__ __launch_bounds__(kThreads) void proc_emit_kernel(const uint8_t *parent_masks, const uint32_t *parent_rank, uint32_t n_parents,
                                                        const uint8_t *child_bytes, const uint32_t *child_rank, uint32_t last,
                                                        uint32_t base_l, uint32_t base_next, uint32_t n_nodes, uint4 *out) {
-    const uint32_t p = blockIdx.x * 256u + threadIdx.x;
+    const uint32_t p = blockIdx.x * kThreads + threadIdx.x;
     if (p >= n_parents || parent_masks[p] == 0) return;
     const uint32_t dst = base_l + 8u * parent_rank[p];
     if (dst + 8u > n_nodes) return;  // (cannot happen: the ranks and n_nodes come from the same counts)
@@ -245,8 +244,8 @@ __global__ __launch_bounds__(256) void proc_emit_kernel(const uint8_t *parent_ma
     for (int k = 0; k < 4; k++) o[k] = make_uint4(w[2 * k], 0u, w[2 * k + 1], 0u);
 }
 
-__global__ __launch_bounds__(256) void proc_sdf_kernel(const float *xyz, uint32_t n, float *out) {
-    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+__global__ __launch_bounds__(kThreads) void proc_sdf_kernel(const float *xyz, uint32_t n, float *out) {
+    const uint32_t i = blockIdx.x * kThreads + threadIdx.x;
     if (i >= n) return;
     out[i] = sdf::eval(xyz[3u * i], xyz[3u * i + 1u], xyz[3u * i + 2u]);
 }
@@ -255,8 +254,8 @@ __global__ __launch_bounds__(256) void proc_sdf_kernel(const float *xyz, uint32_
 struct BlockMips {
     uint32_t rgb[9];
 };
-__global__ __launch_bounds__(256) void proc_block_mips_kernel(uint2 *nodes, uint32_t first, uint32_t count, BlockMips table) {
-    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+__global__ __launch_bounds__(kThreads) void proc_block_mips_kernel(uint2 *nodes, uint32_t first, uint32_t count, BlockMips table) {
+    const uint32_t i = blockIdx.x * kThreads + threadIdx.x;
     if (i >= count) return;
     const uint32_t b = nodes[first + i].x - kChunkOffset;
     if (b < 9u) nodes[first + i].y = table.rgb[b];
@@ -342,7 +341,7 @@ int launch_classify(svo_ctx *ctx, const svo_proc_params *p) {
     svo_proc_state *s = ctx->proc.get();
     const uint32_t n_cells = 1u << (3 * p->chunk_depth);
     HIP_TRY(ctx, hipMemsetAsync(s->masks, 0, s->mask_bytes, ctx->stream));
-    proc_classify_kernel<<<svo_div_up(n_cells, 256), 256, 0, ctx->stream>>>(geom_of(p), n_cells, s->cls,
+    proc_classify_kernel<<<svo_div_up(n_cells, kThreads), kThreads, 0, ctx->stream>>>(geom_of(p), n_cells, s->cls,
                                                                          s->masks + s->mask_off[p->chunk_depth - 1]);
     HIP_TRY(ctx, hipGetLastError());
     return SVO_OK;
@@ -362,7 +361,7 @@ int svo_proc_sdf(svo_ctx *ctx, const float *xyz, size_t n, float *out) {
     HIP_TRY(ctx, d.alloc(n * 4));
     hipError_t e = hipMemcpyAsync(d, xyz, n * 3 * sizeof(float), hipMemcpyHostToDevice, ctx->stream);
     if (e == hipSuccess) {
-        proc_sdf_kernel<<<svo_div_up(n, 256), 256, 0, ctx->stream>>>(d, (uint32_t)n, d + 3 * n);
+        proc_sdf_kernel<<<svo_div_up(n, kThreads), kThreads, 0, ctx->stream>>>(d, (uint32_t)n, d + 3 * n);
         e = hipGetLastError();
     }
     if (e == hipSuccess) e = hipMemcpyAsync(out, d + 3 * n, n * sizeof(float), hipMemcpyDeviceToHost, ctx->stream);
@@ -410,17 +409,15 @@ int emit_chunk(svo_ctx *ctx, const svo_proc_params *params, double t0, uint64_t 
     // occupancy pyramid: level L-1's masks from level L's
     for (uint32_t l = depth - 1; l >= 1; l--) {
         const uint32_t n_par = 1u << (3 * (l - 1));
-        proc_reduce_kernel<<<svo_div_up(n_par, 256), 256, 0, ctx->stream>>>(s->masks + s->mask_off[l], n_par, s->masks + s->mask_off[l - 1]);
+        proc_reduce_kernel<<<svo_div_up(n_par, kThreads), kThreads, 0, ctx->stream>>>(s->masks + s->mask_off[l], n_par, s->masks + s->mask_off[l - 1]);
         HIP_TRY(ctx, hipGetLastError());
     }
     // ranks of the interior nodes of every level, and their counts
     for (uint32_t l = 0; l < depth; l++) {
-        const uint8_t *m = s->masks + s->mask_off[l];
-        uint32_t *tiles = s->tiles + s->tile_off[l];
-        proc_tile_count_kernel<<<s->n_tiles[l], 256, 0, ctx->stream>>>(m, tiles);
-        tile_offsets_kernel<<<1, kTopThreads, 0, ctx->stream>>>(tiles, s->n_tiles[l], nullptr, 0, s->totals.dev + l);
-        proc_tile_rank_kernel<<<s->n_tiles[l], 256, 0, ctx->stream>>>(m, tiles, s->ranks + s->rank_off[l]);
-        HIP_TRY(ctx, hipGetLastError());
+        const uint32_t nt = s->n_tiles[l];
+        if ((rc = svo_tile_pass(ctx, LevelMasks{s->masks + s->mask_off[l]}, WriteRanks{s->ranks + s->rank_off[l]}, nt, nullptr, nt * kTile,
+                                s->tiles + s->tile_off[l], s->totals.dev + l)))
+            return rc;
     }
     HIP_TRY(ctx, hipEventRecord(s->ev[2], ctx->stream));
     if ((rc = s->totals.read(ctx, depth))) return rc;
@@ -442,7 +439,7 @@ int emit_chunk(svo_ctx *ctx, const svo_proc_params *params, double t0, uint64_t 
     for (uint32_t l = 1; l <= depth; l++) {
         const uint32_t n_par = 1u << (3 * (l - 1));
         const bool last = l == depth;
-        proc_emit_kernel<<<svo_div_up(n_par, 256), 256, 0, ctx->stream>>>(
+        proc_emit_kernel<<<svo_div_up(n_par, kThreads), kThreads, 0, ctx->stream>>>(
             s->masks + s->mask_off[l - 1], s->ranks + s->rank_off[l - 1], n_par, last ? s->cls : s->masks + s->mask_off[l],
             last ? nullptr : s->ranks + s->rank_off[l], last ? 1u : 0u, (uint32_t)base[l], (uint32_t)base[l + 1], (uint32_t)n_nodes, s->out);
         HIP_TRY(ctx, hipGetLastError());
@@ -542,10 +539,10 @@ int svo_world_generate(svo_ctx *ctx, svo_world *w, uint32_t world_depth, uint32_
                 uint2 *nodes = reinterpret_cast<uint2 *>(s->out.get());
                 HIP_TRY(ctx, hipEventRecord(s->mev[0], ctx->stream));
                 const uint32_t leaves = uint32_t(base[chunk_depth + 1] - base[chunk_depth]);
-                proc_block_mips_kernel<<<svo_div_up(leaves, 256), 256, 0, ctx->stream>>>(nodes, (uint32_t)base[chunk_depth], leaves, blocks);
+                proc_block_mips_kernel<<<svo_div_up(leaves, kThreads), kThreads, 0, ctx->stream>>>(nodes, (uint32_t)base[chunk_depth], leaves, blocks);
                 for (uint32_t l = chunk_depth - 1; l >= 1; l--) {
                     const uint32_t count = uint32_t(base[l + 1] - base[l]);
-                    mip_level_kernel<<<svo_div_up(count, 256), 256, 0, ctx->stream>>>(nodes, (uint32_t)base[l], count, (uint32_t)n_nodes);
+                    mip_level_kernel<<<svo_div_up(count, kThreads), kThreads, 0, ctx->stream>>>(nodes, (uint32_t)base[l], count, (uint32_t)n_nodes);
                 }
                 HIP_TRY(ctx, hipGetLastError());
                 HIP_TRY(ctx, hipEventRecord(s->mev[1], ctx->stream));

@@ -12,14 +12,11 @@
 //            of the highest bit in which their y differ.  A coloured leaf, an interior word at `depth` (FINER) or a pointer
 //            that fails svo_nodes_sample's check (BROKEN) ends the column; no pointer is followed before that check, and
 //            every step either goes one level down, `depth` at the most, or moves y down
-//   sites    a tile is kTile columns, 16 consecutive ones per thread: the sum kernel counts each tile's sites, the tile
-//            sums are scanned by one block (svo_scan.h), the emit kernel counts again, scans over the block and writes
-//            every thread's sites behind the tile's offset, in the arrays' order
+//   sites    a tile pass of svo_scan.h over the columns (count, scan, emit), with "the column is a site" as the flag
 //   stamp    the entries (placement p, voxel v) are numbered p * m + v, which is the contract's order.  A check kernel
 //            finds the lowest placement and voxel whose numbers are out of range (block minima, then one block over them).
-//            Sum and emit as for the sites, with the entry inside the grid as the flag; the emit leaves the tile's offsets
-//            in LDS and takes the entries in rows of kThreads, so that lanes next to each other read and write next to
-//            each other.  Every entry is tested, also those of a placement that lies wholly inside the grid
+//            Then a tile pass over the entries with the entry inside the grid as the flag, its emit the row-wise one
+//            (tile_scatter_kernel).  Every entry is tested, also those of a placement that lies wholly inside the grid
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -27,7 +24,7 @@
 
 #include "svo_ctx.h"
 #include "svo_morton.h"  // (morton_child)
-#include "svo_scan.h"    // (kThreads, kPer, kTile, block_exclusive_scan, block_min, tile_offsets_kernel)
+#include "svo_scan.h"    // (kThreads, kPer, kTile, block_min, min_of_blocks_kernel, the tile pass)
 
 namespace {
 
@@ -38,7 +35,6 @@ constexpr uint32_t kReach = 1u << 22;  // origins lie in [-kReach, kReach), offs
 // the words read back: the scan's total; the lowest placement with a bad origin, with a bad rotation, the lowest voxel
 // with a bad offset
 enum Status { kStTotal, kStBadOrigin, kStBadRot, kStBadOffset, kStWords };
-static_assert(kPer == 16, "a thread's flags of the stamp's emit are one 16-bit mask");
 
 struct Columns {
     uint32_t ox, oz, sz;  // the rectangle's origin, its size along z
@@ -103,79 +99,95 @@ struct Sites {
     Columns c;
     uint32_t seed, one_in, on_value, rotate;
     int32_t lift;
+
+    // whether column i is a site; its coordinates, top and hash
+    __device__ bool at(uint32_t i, uint32_t &x, uint32_t &z, uint32_t &t, uint32_t &h) const {
+        if (i >= c.n) return false;
+        t = top[i];
+        if (t == SVO_TOP_NONE) return false;
+        if (value) {
+            const uint32_t v = value[i];
+            if (v >= SVO_VOXEL_OFFSET || (on_value && v != on_value)) return false;
+        }
+        x = c.ox + i / c.sz;
+        z = c.oz + i % c.sz;
+        h = lowbias32(lowbias32(x + seed) ^ z);
+        return h % one_in == 0u;
+    }
+    // the tile pass's items (svo_scan.h): the state is the mask of a thread's columns that are sites
+    __device__ uint32_t load(uint32_t i0, uint32_t) const {
+        uint32_t mask = 0, x, z, t, h;
+        for (uint32_t k = 0; k < kPer; k++) mask |= at(i0 + k, x, z, t, h) ? 1u << k : 0u;
+        return mask;
+    }
+    __device__ uint32_t count(uint32_t mask) const { return __popc(mask); }
 };
 
-// whether column i is a site; its coordinates, top and hash
-__device__ inline bool site_at(const Sites &s, uint32_t i, uint32_t &x, uint32_t &z, uint32_t &top, uint32_t &h) {
-    if (i >= s.c.n) return false;
-    top = s.top[i];
-    if (top == SVO_TOP_NONE) return false;
-    if (s.value) {
-        const uint32_t value = s.value[i];
-        if (value >= SVO_VOXEL_OFFSET || (s.on_value && value != s.on_value)) return false;
+struct SitesOut {
+    uint32_t room;
+    int32_t *origins;
+    uint32_t *rots;  // or null
+    __device__ void operator()(const Sites &s, uint32_t i0, uint32_t mask, uint32_t o) const {
+        for (uint32_t x, z, top, h; mask; mask &= mask - 1u, o++) {
+            if (o >= room) break;  // (never: room is the scan's total)
+            s.at(i0 + __ffs(mask) - 1u, x, z, top, h);
+            origins[3ull * o] = int32_t(x);
+            origins[3ull * o + 1] = int32_t(top + uint32_t(s.lift));
+            origins[3ull * o + 2] = int32_t(z);
+            if (rots) rots[o] = s.rotate ? lowbias32(h + 0x9E3779B9u) >> 30 : 0u;
+        }
     }
-    x = s.c.ox + i / s.c.sz;
-    z = s.c.oz + i % s.c.sz;
-    h = lowbias32(lowbias32(x + s.seed) ^ z);
-    return h % s.one_in == 0u;
-}
-
-__global__ __launch_bounds__(kThreads) void sites_sum_kernel(Sites s, uint32_t *tile_sum) {
-    const uint32_t i0 = blockIdx.x * kTile + threadIdx.x * kPer;
-    uint32_t count = 0, x, z, top, h;
-    for (uint32_t k = 0; k < kPer; k++) count += site_at(s, i0 + k, x, z, top, h) ? 1u : 0u;
-    uint32_t total;
-    block_exclusive_scan<kThreads>(count, &total);
-    if (threadIdx.x == 0) tile_sum[blockIdx.x] = total;
-}
-
-__global__ __launch_bounds__(kThreads) void sites_emit_kernel(Sites s, const uint32_t *__restrict__ tile_off, uint32_t room,
-                                                              int32_t *__restrict__ origins, uint32_t *__restrict__ rots) {
-    const uint32_t i0 = blockIdx.x * kTile + threadIdx.x * kPer;
-    uint32_t mask = 0, x, z, top, h;
-    for (uint32_t k = 0; k < kPer; k++) mask |= site_at(s, i0 + k, x, z, top, h) ? 1u << k : 0u;
-    uint32_t o = tile_off[blockIdx.x] + block_exclusive_scan<kThreads>(__popc(mask), nullptr);
-    for (; mask; mask &= mask - 1u, o++) {
-        if (o >= room) break;  // (never: room is the scan's total)
-        site_at(s, i0 + __ffs(mask) - 1u, x, z, top, h);
-        origins[3ull * o] = int32_t(x);
-        origins[3ull * o + 1] = int32_t(top + uint32_t(s.lift));
-        origins[3ull * o + 2] = int32_t(z);
-        if (rots) rots[o] = s.rotate ? lowbias32(h + 0x9E3779B9u) >> 30 : 0u;
-    }
-}
+};
 
 struct Stamp {
     const int32_t *offsets, *origins;
     const uint32_t *colours, *rots;  // rots may be null
     uint32_t m, k, n;                // voxels, placements, entries = k * m
     uint32_t depth;
+
+    // The cell of entry (p, v), in wrapping arithmetic: what the check kernel refuses never gets to the outputs.
+    __device__ bool cell(uint32_t p, uint32_t v, uint32_t &cx, uint32_t &cy, uint32_t &cz) const {
+        const uint32_t dx = uint32_t(offsets[3ull * v]), dy = uint32_t(offsets[3ull * v + 1]), dz = uint32_t(offsets[3ull * v + 2]);
+        const uint32_t r = rots ? rots[p] & 3u : 0u;
+        // R (dx, dy, dz) = (dz, dy, -dx), r times
+        const uint32_t rx = r == 0 ? dx : r == 1 ? dz : r == 2 ? 0u - dx : 0u - dz;
+        const uint32_t rz = r == 0 ? dz : r == 1 ? 0u - dx : r == 2 ? 0u - dz : dx;
+        cx = uint32_t(origins[3ull * p]) + rx;
+        cy = uint32_t(origins[3ull * p + 1]) + dy;
+        cz = uint32_t(origins[3ull * p + 2]) + rz;
+        return ((cx | cy | cz) >> depth) == 0u;
+    }
+    // the tile pass's items (svo_scan.h): the state is the mask of a thread's entries that lie inside the grid
+    __device__ uint32_t load(uint32_t i0, uint32_t) const {
+        uint32_t mask = 0, cx, cy, cz;
+        if (i0 >= n) return 0u;
+        uint32_t p = i0 / m, v = i0 % m;
+        for (uint32_t j = 0; j < kPer && i0 + j < n; j++) {
+            mask |= cell(p, v, cx, cy, cz) ? 1u << j : 0u;
+            if (++v == m) v = 0u, p++;
+        }
+        return mask;
+    }
+    __device__ uint32_t count(uint32_t mask) const { return __popc(mask); }
+    __device__ uint32_t flags(uint32_t mask, uint32_t j) const { return mask >> j & 1u; }
 };
 
-// The cell of entry (p, v), in wrapping arithmetic: what the check kernel refuses never gets to the outputs.
-__device__ inline bool stamp_cell(const Stamp &s, uint32_t p, uint32_t v, uint32_t &cx, uint32_t &cy, uint32_t &cz) {
-    const uint32_t dx = uint32_t(s.offsets[3ull * v]), dy = uint32_t(s.offsets[3ull * v + 1]), dz = uint32_t(s.offsets[3ull * v + 2]);
-    const uint32_t r = s.rots ? s.rots[p] & 3u : 0u;
-    // R (dx, dy, dz) = (dz, dy, -dx), r times
-    const uint32_t rx = r == 0 ? dx : r == 1 ? dz : r == 2 ? 0u - dx : 0u - dz;
-    const uint32_t rz = r == 0 ? dz : r == 1 ? 0u - dx : r == 2 ? 0u - dz : dx;
-    cx = uint32_t(s.origins[3ull * p]) + rx;
-    cy = uint32_t(s.origins[3ull * p + 1]) + dy;
-    cz = uint32_t(s.origins[3ull * p + 2]) + rz;
-    return ((cx | cy | cz) >> s.depth) == 0u;
-}
-
-// the flags of a thread's kPer consecutive entries from i0 on
-__device__ inline uint32_t stamp_flags(const Stamp &s, uint32_t i0) {
-    uint32_t mask = 0, cx, cy, cz;
-    if (i0 >= s.n) return 0u;
-    uint32_t p = i0 / s.m, v = i0 % s.m;
-    for (uint32_t k = 0; k < kPer && i0 + k < s.n; k++) {
-        mask |= stamp_cell(s, p, v, cx, cy, cz) ? 1u << k : 0u;
-        if (++v == s.m) v = 0u, p++;
+struct StampOut {
+    uint32_t room;
+    uint32_t *xyz, *colour, *placement;  // placement may be null
+    __device__ void operator()(const Stamp &s, uint32_t i, uint32_t, uint32_t o) const {
+        if (o >= room) return;  // (never: room is the scan's total)
+        const uint32_t p = i / s.m, v = i % s.m;
+        uint32_t cx, cy, cz;
+        s.cell(p, v, cx, cy, cz);
+        const uint32_t c = s.colours[v];  // (with the cell's loads, not behind the stores that may alias it)
+        xyz[3ull * o] = cx;
+        xyz[3ull * o + 1] = cy;
+        xyz[3ull * o + 2] = cz;
+        colour[o] = c;
+        if (placement) placement[o] = p;
     }
-    return mask;
-}
+};
 
 // One lane per placement and per voxel: block_bad[3 * block + {0, 1, 2}] the block's lowest placement with a bad origin,
 // with a bad rotation, its lowest voxel with a bad offset.
@@ -197,54 +209,6 @@ __global__ __launch_bounds__(kThreads) void stamp_check_kernel(Stamp s, uint32_t
         block_bad[3ull * blockIdx.x] = bad_origin;
         block_bad[3ull * blockIdx.x + 1] = bad_rot;
         block_bad[3ull * blockIdx.x + 2] = bad_offset;
-    }
-}
-
-__global__ __launch_bounds__(kTopThreads) void stamp_bad_kernel(const uint32_t *block_bad, uint32_t n_blocks, uint32_t *status) {
-    for (uint32_t j = 0; j < 3; j++) {
-        uint32_t bad = kNoBad;
-        for (uint32_t i = threadIdx.x; i < n_blocks; i += kTopThreads) bad = min(bad, block_bad[3ull * i + j]);
-        bad = block_min<kTopThreads>(bad);
-        if (threadIdx.x == 0) status[kStBadOrigin + j] = bad;
-    }
-}
-
-__global__ __launch_bounds__(kThreads) void stamp_sum_kernel(Stamp s, uint32_t *tile_sum) {
-    uint32_t total;
-    block_exclusive_scan<kThreads>(__popc(stamp_flags(s, blockIdx.x * kTile + threadIdx.x * kPer)), &total);
-    if (threadIdx.x == 0) tile_sum[blockIdx.x] = total;
-}
-
-__global__ __launch_bounds__(kThreads) void stamp_emit_kernel(Stamp s, const uint32_t *__restrict__ tile_off, uint32_t room,
-                                                              uint32_t *__restrict__ xyz, uint32_t *__restrict__ colour,
-                                                              uint32_t *__restrict__ placement) {
-    // per entry of the tile: its offset in the tile << 1 | its flag; one word of padding per 32, so that the threads'
-    // runs of kPer words fall on different banks
-    __shared__ uint32_t at[kTile + kTile / 32];
-    const uint32_t tile0 = blockIdx.x * kTile;
-    const uint32_t mask = stamp_flags(s, tile0 + threadIdx.x * kPer);
-    uint32_t run = block_exclusive_scan<kThreads>(__popc(mask), nullptr);
-#pragma unroll
-    for (uint32_t k = 0; k < kPer; k++) {
-        const uint32_t j = threadIdx.x * kPer + k, bit = mask >> k & 1u;
-        at[j + (j >> 5)] = run << 1 | bit;
-        run += bit;
-    }
-    __syncthreads();
-    const uint32_t base = tile_off[blockIdx.x];
-    for (uint32_t row = 0; row < kPer; row++) {
-        const uint32_t j = row * kThreads + threadIdx.x, i = tile0 + j;
-        if (i >= s.n) break;
-        const uint32_t mine = at[j + (j >> 5)], o = base + (mine >> 1);
-        if (!(mine & 1u) || o >= room) continue;  // (o < room always: room is the scan's total)
-        const uint32_t p = i / s.m, v = i % s.m;
-        uint32_t cx, cy, cz;
-        stamp_cell(s, p, v, cx, cy, cz);
-        xyz[3ull * o] = cx;
-        xyz[3ull * o + 1] = cy;
-        xyz[3ull * o + 2] = cz;
-        colour[o] = s.colours[v];
-        if (placement) placement[o] = p;
     }
 }
 
@@ -361,16 +325,14 @@ int svo_structures_sites(svo_ctx *ctx, const svo_sites_params *p, const uint32_t
     const uint32_t n_tiles = svo_div_up(columns, kTile);
     if ((rc = svo_grow(ctx, (size_t)n_tiles, &s->tiles))) return rc;
     HIP_TRY(ctx, s->timer.mark(ctx, kEvStart));
-    sites_sum_kernel<<<n_tiles, kThreads, 0, ctx->stream>>>(sites, s->tiles);
-    tile_offsets_kernel<<<1, kTopThreads, 0, ctx->stream>>>(s->tiles, n_tiles, nullptr, 0, s->status.dev + kStTotal);
-    HIP_TRY(ctx, hipGetLastError());
+    if ((rc = svo_tile_count(ctx, sites, n_tiles, nullptr, c.n, s->tiles, s->status.dev + kStTotal))) return rc;
     if ((rc = s->status.read(ctx))) return rc;
     const uint64_t count = s->status.host()[kStTotal];
     if (origins_out_dev && count > p->max_sites) return svo_fail(ctx, SVO_ERR_CAP, cap_message("sites", count, "max_sites", p->max_sites));
     HIP_TRY(ctx, s->timer.mark(ctx, kEvCount));
     s->no_fill();
     if (origins_out_dev && count) {
-        sites_emit_kernel<<<n_tiles, kThreads, 0, ctx->stream>>>(sites, s->tiles, (uint32_t)count, origins_out_dev, rots_out_dev);
+        tile_emit_kernel<<<n_tiles, kThreads, 0, ctx->stream>>>(sites, SitesOut{(uint32_t)count, origins_out_dev, rots_out_dev}, nullptr, c.n, s->tiles);
         HIP_TRY(ctx, hipGetLastError());
         HIP_TRY(ctx, s->fill_done(ctx));
     }
@@ -409,10 +371,8 @@ int svo_structures_stamp(svo_ctx *ctx, const svo_stamp_params *p, const int32_t 
     if ((rc = svo_grow(ctx, (size_t)n_tiles, &s->tiles)) || (rc = svo_grow(ctx, 3 * (size_t)n_check, &s->bad))) return rc;
     HIP_TRY(ctx, s->timer.mark(ctx, kEvStart));
     stamp_check_kernel<<<n_check, kThreads, 0, ctx->stream>>>(stamp, s->bad);
-    stamp_bad_kernel<<<1, kTopThreads, 0, ctx->stream>>>(s->bad, n_check, s->status.dev);
-    stamp_sum_kernel<<<n_tiles, kThreads, 0, ctx->stream>>>(stamp, s->tiles);
-    tile_offsets_kernel<<<1, kTopThreads, 0, ctx->stream>>>(s->tiles, n_tiles, nullptr, 0, s->status.dev + kStTotal);
-    HIP_TRY(ctx, hipGetLastError());
+    min_of_blocks_kernel<3><<<1, kTopThreads, 0, ctx->stream>>>(s->bad, n_check, s->status.dev + kStBadOrigin);
+    if ((rc = svo_tile_count(ctx, stamp, n_tiles, nullptr, stamp.n, s->tiles, s->status.dev + kStTotal))) return rc;
     if ((rc = s->status.read(ctx))) return rc;
     if (st[kStBadOrigin] != kNoBad)
         return svo_fail(ctx, SVO_ERR_ARG, "placement " + std::to_string(st[kStBadOrigin]) + " has an origin component outside [-2^22, 2^22)");
@@ -425,7 +385,8 @@ int svo_structures_stamp(svo_ctx *ctx, const svo_stamp_params *p, const int32_t 
     HIP_TRY(ctx, s->timer.mark(ctx, kEvCount));
     s->no_fill();
     if (xyz_out_dev && count) {
-        stamp_emit_kernel<<<n_tiles, kThreads, 0, ctx->stream>>>(stamp, s->tiles, (uint32_t)count, xyz_out_dev, colour_out_dev, placement_out_dev);
+        tile_scatter_kernel<<<n_tiles, kThreads, 0, ctx->stream>>>(stamp, StampOut{(uint32_t)count, xyz_out_dev, colour_out_dev, placement_out_dev},
+                                                                   stamp.n, s->tiles);
         HIP_TRY(ctx, hipGetLastError());
         HIP_TRY(ctx, s->fill_done(ctx));
     }

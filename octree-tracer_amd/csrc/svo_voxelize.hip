@@ -10,13 +10,12 @@
 //            bounding box lies in one cell of the level is inside that cell, which is a child of the pair's: a shift and
 //            a compare.  Otherwise the 13 separating axes, with everything that does not depend on the child (edges,
 //            normal, the plane's and the edges' projections relative to the parent's centre) outside the 8-child loop
-//   sum      per tile of kTile pairs the number of set bits; vox_total_kernel adds the tiles' in 64 bits (8 children
-//            of up to 2^31 pairs do not fit 32) before tile_offsets_kernel (svo_scan.h) scans them; the total comes back
-//            to the host, which refuses a level over the cap before anything is allocated for it
-//   scatter  per tile: the pairs' offsets from one block scan over 16 consecutive masks per thread, left in LDS; then the
-//            lanes take the tile's pairs in rows of kThreads and write each pair's children in child order behind the
-//            tile's offset: the input order by triangle and the child order within a pair are the contract's order.
-//            The last level writes the caller's outputs instead of the next pair array
+//   sum      a tile pass of svo_scan.h over the pairs' masks, whose set bits are counted; vox_total_kernel adds the
+//            tiles' sums in 64 bits (8 children of up to 2^31 pairs do not fit 32) before tile_offsets_kernel scans
+//            them; the total comes back to the host, which refuses a level over the cap before anything is allocated
+//   scatter  the pass's row-wise emit (tile_scatter_kernel): each pair's children in child order behind the pair's
+//            rank: the input order by triangle and the child order within a pair are the contract's order.  The last
+//            level writes the caller's outputs instead of the next pair array
 //
 // The arithmetic is exact (include/svo_hip.h): doubled coordinates are odd and below 2^28, a cell's bounds even.  Edge
 // tests fit int64 (terms below 2^58), the plane test takes 128-bit products.  No float anywhere.
@@ -27,16 +26,14 @@
 #include <string>
 
 #include "svo_ctx.h"
-#include "svo_scan.h"  // (kThreads, kTile, block_exclusive_scan, block_min, tile_offsets_kernel)
+#include "svo_scan.h"  // (kThreads, kTile, block_min, min_of_blocks_kernel, the tile pass's kernels)
 
 namespace {
 
 constexpr uint64_t kMaxEntries = 1ull << 31;
 constexpr uint32_t kNoBad = 0xFFFFFFFFu;
-// the words read back: the first bad triangle << 1 | (0: a vertex index, 1: a coordinate), the level's pair count in two
-// halves, tile_offsets_kernel's own 32-bit total (not used)
-enum Status { kStBad, kStCountLo, kStCountHi, kStTotal32, kStWords };
-static_assert(kPer == 16, "a thread of the sum and scatter kernels loads its masks as one uint4");
+// the words read back: the first bad triangle << 1 | (0: a vertex index, 1: a coordinate), the level's pair count in two halves
+enum Status { kStBad, kStCountLo, kStCountHi, kStWords };
 
 typedef __int128 i128;
 
@@ -74,13 +71,6 @@ __global__ __launch_bounds__(kThreads) void vox_setup_kernel(const uint32_t *__r
     }
     bad = block_min<kThreads>(bad);
     if (threadIdx.x == 0) block_bad[blockIdx.x] = bad;
-}
-
-__global__ __launch_bounds__(kTopThreads) void vox_bad_kernel(const uint32_t *block_bad, uint32_t n_blocks, uint32_t *status) {
-    uint32_t bad = kNoBad;
-    for (uint32_t i = threadIdx.x; i < n_blocks; i += kTopThreads) bad = min(bad, block_bad[i]);
-    bad = block_min<kTopThreads>(bad);
-    if (threadIdx.x == 0) status[kStBad] = bad;
 }
 
 __device__ inline int64_t abs64(int64_t v) { return v < 0 ? -v : v; }
@@ -181,24 +171,27 @@ __global__ __launch_bounds__(kThreads) void vox_test_kernel(const int32_t *__res
     mask[i] = uint8_t(child_mask(v, cell_x(cell), cell_y(cell), cell_z(cell), hs));
 }
 
-// the children of a thread's kPer consecutive pairs of the tile; the mask array is padded to whole tiles, and what lies
-// behind m is not counted
-__device__ inline uint4 tile_masks(const uint8_t *mask, uint32_t m, uint32_t i0) {
-    uint4 w = *reinterpret_cast<const uint4 *>(mask + i0);
-    const auto live = [&](uint32_t first) { return first >= m ? 0u : m - first >= 4 ? 0xFFFFFFFFu : (1u << 8 * (m - first)) - 1u; };
-    w.x &= live(i0);
-    w.y &= live(i0 + 4);
-    w.z &= live(i0 + 8);
-    w.w &= live(i0 + 12);
-    return w;
-}
-
-__global__ __launch_bounds__(kThreads) void vox_sum_kernel(const uint8_t *__restrict__ mask, uint32_t m, uint32_t *tile_sum) {
-    const uint4 w = tile_masks(mask, m, blockIdx.x * kTile + threadIdx.x * kPer);
-    uint32_t total;
-    block_exclusive_scan<kThreads>(__popc(w.x) + __popc(w.y) + __popc(w.z) + __popc(w.w), &total);
-    if (threadIdx.x == 0) tile_sum[blockIdx.x] = total;
-}
+// The tile pass's items (svo_scan.h): a level's pairs with their child masks.  The state is the masks of a thread's kPer
+// consecutive pairs; the mask array is padded to whole tiles, and what lies behind m is not counted.
+struct Pairs {
+    const uint32_t *tri;
+    const uint64_t *cell;
+    const uint8_t *mask;
+    __device__ uint4 load(uint32_t i0, uint32_t m) const {
+        uint4 w = *reinterpret_cast<const uint4 *>(mask + i0);
+        const auto live = [&](uint32_t first) { return first >= m ? 0u : m - first >= 4 ? 0xFFFFFFFFu : (1u << 8 * (m - first)) - 1u; };
+        w.x &= live(i0);
+        w.y &= live(i0 + 4);
+        w.z &= live(i0 + 8);
+        w.w &= live(i0 + 12);
+        return w;
+    }
+    __device__ uint32_t count(const uint4 &w) const { return __popc(w.x) + __popc(w.y) + __popc(w.z) + __popc(w.w); }
+    __device__ uint32_t flags(const uint4 &w, uint32_t k) const {
+        const uint32_t q[4] = {w.x, w.y, w.z, w.w};
+        return q[k / 4] >> 8 * (k % 4);
+    }
+};
 
 // before tile_offsets_kernel, which scans the sums in place: their total in 64 bits
 __global__ __launch_bounds__(kTopThreads) void vox_total_kernel(const uint32_t *tile_sum, uint32_t n_tiles, uint32_t *status) {
@@ -226,34 +219,13 @@ struct VoxOut {
     uint32_t room;  // entries the outputs hold: the level's total, which the host has checked
 };
 
+// the children `bits` of pair i, in child order from output o on
 template <bool kEmit>
-__global__ __launch_bounds__(kThreads) void vox_scatter_kernel(const uint32_t *__restrict__ pair_tri, const uint64_t *__restrict__ pair_cell,
-                                                               const uint8_t *__restrict__ mask, uint32_t m,
-                                                               const uint32_t *__restrict__ tile_off, VoxOut out) {
-    // per pair of the tile: its children's offset in the tile << 8 | its mask; one word of padding per 32, so that the
-    // threads' runs of kPer words fall on different banks
-    __shared__ uint32_t at[kTile + kTile / 32];
-    const uint32_t tile0 = blockIdx.x * kTile;
-    const uint4 w = tile_masks(mask, m, tile0 + threadIdx.x * kPer);
-    uint32_t run = block_exclusive_scan<kThreads>(__popc(w.x) + __popc(w.y) + __popc(w.z) + __popc(w.w), nullptr);
-    const uint32_t q[4] = {w.x, w.y, w.z, w.w};
-#pragma unroll
-    for (uint32_t k = 0; k < kPer; k++) {
-        const uint32_t bits = q[k / 4] >> 8 * (k % 4) & 0xFFu;
-        const uint32_t j = threadIdx.x * kPer + k;
-        at[j + (j >> 5)] = run << 8 | bits;
-        run += __popc(bits);
-    }
-    __syncthreads();
-    const uint32_t base = tile_off[blockIdx.x];
-    for (uint32_t row = 0; row < kPer; row++) {
-        const uint32_t j = row * kThreads + threadIdx.x, i = tile0 + j;
-        if (i >= m) break;
-        const uint32_t mine = at[j + (j >> 5)];
-        uint32_t bits = mine & 0xFFu, o = base + (mine >> 8);
-        if (!bits) continue;
-        const uint32_t t = pair_tri[i];
-        const uint64_t cell = pair_cell[i];
+struct Children {
+    VoxOut out;
+    __device__ void operator()(const Pairs &p, uint32_t i, uint32_t bits, uint32_t o) const {
+        const uint32_t t = p.tri[i];
+        const uint64_t cell = p.cell[i];
         const uint32_t x = cell_x(cell) << 1, y = cell_y(cell) << 1, z = cell_z(cell) << 1;
         uint32_t colour = 0;
         if (kEmit) colour = (out.tri_colours ? out.tri_colours[t] : out.default_colour) & 0xFFFFFFu;
@@ -273,7 +245,7 @@ __global__ __launch_bounds__(kThreads) void vox_scatter_kernel(const uint32_t *_
             }
         }
     }
-}
+};
 
 enum Ev { kEvStart, kEvSetup, kEvRefine, kEvCount, kEvEmit, kEvs };
 
@@ -331,7 +303,7 @@ int svo_mesh_voxelize(svo_ctx *ctx, const svo_voxelize_params *p, const uint32_t
     HIP_TRY(ctx, s->timer.mark(ctx, kEvStart));
     vox_setup_kernel<<<n_blocks, kThreads, 0, ctx->stream>>>(vq_dev, p->n_vertices, tri_dev, n, depth, s->tv, s->pair_tri[0],
                                                              s->pair_cell[0], s->tiles);
-    vox_bad_kernel<<<1, kTopThreads, 0, ctx->stream>>>(s->tiles, n_blocks, s->status.dev);
+    min_of_blocks_kernel<1><<<1, kTopThreads, 0, ctx->stream>>>(s->tiles, n_blocks, s->status.dev + kStBad);
     HIP_TRY(ctx, hipGetLastError());
     HIP_TRY(ctx, s->timer.mark(ctx, kEvSetup));
 
@@ -341,10 +313,11 @@ int svo_mesh_voxelize(svo_ctx *ctx, const svo_voxelize_params *p, const uint32_t
         const uint32_t n_tiles = svo_div_up(m, kTile), hs = depth - l + SVO_VOX_SUBBITS;
         if ((rc = svo_grow(ctx, size_t(n_tiles) * kTile, &s->mask))) return rc;
         if ((rc = svo_grow(ctx, (size_t)n_tiles, &s->tiles))) return rc;
+        const Pairs pairs{s->pair_tri[cur], s->pair_cell[cur], s->mask};
         vox_test_kernel<<<svo_div_up(m, kThreads), kThreads, 0, ctx->stream>>>(s->tv, s->pair_tri[cur], s->pair_cell[cur], m, hs, s->mask);
-        vox_sum_kernel<<<n_tiles, kThreads, 0, ctx->stream>>>(s->mask, m, s->tiles);
+        tile_count_kernel<<<n_tiles, kThreads, 0, ctx->stream>>>(pairs, nullptr, m, s->tiles);
         vox_total_kernel<<<1, kTopThreads, 0, ctx->stream>>>(s->tiles, n_tiles, s->status.dev);
-        tile_offsets_kernel<<<1, kTopThreads, 0, ctx->stream>>>(s->tiles, n_tiles, nullptr, 0, s->status.dev + kStTotal32);
+        tile_offsets_kernel<<<1, kTopThreads, 0, ctx->stream>>>(s->tiles, n_tiles, nullptr, 0, nullptr);
         HIP_TRY(ctx, hipGetLastError());
         if ((rc = s->status.read(ctx))) return rc;
         if (l == 1 && st[kStBad] != kNoBad)
@@ -365,7 +338,7 @@ int svo_mesh_voxelize(svo_ctx *ctx, const svo_voxelize_params *p, const uint32_t
             if ((rc = svo_grow(ctx, (size_t)count, &s->pair_tri[next], &s->pair_cell[next]))) return rc;
             out.pair_tri = s->pair_tri[next];
             out.pair_cell = s->pair_cell[next];
-            vox_scatter_kernel<false><<<n_tiles, kThreads, 0, ctx->stream>>>(s->pair_tri[cur], s->pair_cell[cur], s->mask, m, s->tiles, out);
+            tile_scatter_kernel<<<n_tiles, kThreads, 0, ctx->stream>>>(pairs, Children<false>{out}, m, s->tiles);
             HIP_TRY(ctx, hipGetLastError());
             m = (uint32_t)count;
             cur = next;
@@ -378,7 +351,7 @@ int svo_mesh_voxelize(svo_ctx *ctx, const svo_voxelize_params *p, const uint32_t
             out.tri = tri_out_dev;
             out.tri_colours = tri_colours_dev;
             out.default_colour = p->default_colour;
-            vox_scatter_kernel<true><<<n_tiles, kThreads, 0, ctx->stream>>>(s->pair_tri[cur], s->pair_cell[cur], s->mask, m, s->tiles, out);
+            tile_scatter_kernel<<<n_tiles, kThreads, 0, ctx->stream>>>(pairs, Children<true>{out}, m, s->tiles);
             HIP_TRY(ctx, hipGetLastError());
         }
         HIP_TRY(ctx, s->timer.mark(ctx, kEvEmit));

@@ -34,6 +34,13 @@ def _resources(name):
     return out
 
 
+def _instances(kernels, kernel, *functors):
+    """The entries of `kernels` (mangled name -> figures) that are `kernel`, instantiated with the functor types `functors`:
+    a type's name stands in the mangled symbol behind its length."""
+    parts = [f"{len(p)}{p}" for p in (kernel,) + functors]
+    return {k: r for k, r in kernels.items() if all(p in k for p in parts)}
+
+
 @pytest.mark.skipif(shutil.which(HIPCC) is None, reason="hipcc not installed")
 def test_no_listing_kernel_uses_scratch():
     res = _resources("svo_list.hip")

@@ -350,6 +350,29 @@ def test_sites(pkg, own_gpu):
         assert raw_sites(pkg, own_gpu, None, None, origin, size, out) == (0, 0) and out.untouched_from(0)
 
 
+@pytest.mark.parametrize("columns", (4095, 4096, 4097))
+def test_sites_at_the_edges_of_a_scan_tile(pkg, own_gpu, columns):
+    """the last thread of a tile, an exactly full tile, one column in a second tile: the shared tile kernels (svo_scan.h)"""
+    tops = (np.arange(columns, dtype=np.uint32) * 7) % 90
+    tops[::3] = R.TOP_NONE
+    tops[[0, 15, 16, 4079, 4080, 4094, columns - 1]] = [5, 6, 7, 8, 9, 10, 11]  # the ends of the first and the last threads' runs
+    every, _ = check_sites(pkg, own_gpu, tops.reshape(1, -1), None, (3, 9), f"{columns} columns along z")
+    assert len(every) == int((tops != R.TOP_NONE).sum()) and every[-1].tolist() == [3, 12, 9 + columns - 1]
+    values = np.where(np.arange(columns) % 5 == 0, S.FINER, 2).astype(np.uint32)
+    picked, _ = check_sites(pkg, own_gpu, tops.reshape(-1, 1), values.reshape(-1, 1), (3, 9), f"{columns} columns along x", one_in=2, seed=columns)
+    assert 0 < len(picked) < len(every)
+
+
+def test_sites_over_more_tiles_than_the_top_scan_has_threads(pkg, own_gpu):
+    """4 199 425 columns are 1 026 tiles: the one block that scans the tile sums takes more than one per thread"""
+    shape = (1025, 4097)
+    rng = np.random.default_rng(1025)
+    tops = rng.integers(0, 1 << 20, shape).astype(np.uint32)
+    tops[rng.random(shape) < 0.1] = R.TOP_NONE
+    origins, rots = check_sites(pkg, own_gpu, tops, None, (11, 5), "1 026 tiles", one_in=7)
+    assert len(origins) == 539_616 and set(rots.tolist()) == {0, 1, 2, 3}  # (the restatement's count for this seed)
+
+
 # ---- stamp ----
 
 def raw_stamp(pkg, gpu, offsets, colours, m, origins, rots, k, depth, out, max_voxels=0, flags=0, params=True, give_n=True):
