@@ -293,6 +293,18 @@ int svo_diag_strip_classes(svo_ctx *ctx, uint8_t *host_out, size_t n_strips);
 int svo_diag_deal(svo_ctx *ctx, uint32_t status_out[16], uint32_t *table_out, size_t table_words, uint32_t *stamps_out,
                   size_t stamps_words);
 
+/* Diagnostic for the strip schedule, read-only and blocking: what schedule slot `slot` (0: primary frames, 1:
+ * shadow and secondary rays) holds after the frames traced so far.  info_out: strips of the slot's work layout, entries reserved
+ * per list, blocks per row the builder ranks column-major by (0: strip order), then the slot's state -- valid, lists filtered,
+ * age, frames fed back, floored -- and zeros.  The first three describe the work layout of the slot's last rebuild (0 strips before the
+ * first one) and say something about the buffers only while `valid` is set.  classes_out / classes_now_out (or NULL): the first n_classes class bytes as the
+ * post pass measured them, and as the last filtered or floored build used them (0xFF: not in a list).  lists_out (or NULL): the
+ * first list_words words of the 8 list lengths followed by the 8 lists (entries-per-list words each).  balance_out: the first 32
+ * balance words -- [0..8] the cumulative shares, [18] updates, [20] best time, [21..29] best shares.  SVO_ERR_STATE when the
+ * slot has no buffers (no scheduled STACK frame yet). */
+int svo_diag_schedule(svo_ctx *ctx, int slot, uint32_t info_out[16], uint8_t *classes_out, size_t n_classes, uint8_t *classes_now_out,
+                      uint32_t *lists_out, size_t list_words, uint32_t balance_out[32]);
+
 /* Counter scan (compute.wgsl).  Lists hold `capacity` words: slot 0 = count, slots 1.. = indices. */
 int svo_scan_dispatch(svo_ctx *ctx, uint32_t node_length);
 int svo_scan_read(svo_ctx *ctx, uint32_t *sub, uint32_t *n_sub, uint32_t *unsub, uint32_t *n_unsub,

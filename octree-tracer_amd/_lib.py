@@ -207,6 +207,7 @@ DEVICE_SIGNATURES = {
     "svo_diag_gather": (C.c_int, (vp, u32, u32)),
     "svo_diag_strip_classes": (C.c_int, (vp, vp, sz)),
     "svo_diag_deal": (C.c_int, (vp, vp, vp, sz, vp, sz)),
+    "svo_diag_schedule": (C.c_int, (vp, C.c_int, vp, vp, sz, vp, vp, sz, vp)),
     "svo_scan_dispatch": (C.c_int, (vp, u32)),
     "svo_scan_read": (C.c_int, (vp, vp, C.POINTER(u32), vp, C.POINTER(u32), sz)),
     "svo_proc_generate_chunk": (C.c_int, (vp, C.POINTER(ProcParams), C.POINTER(vp))),

@@ -1058,6 +1058,27 @@ int svo_diag_strip_classes(svo_ctx *ctx, uint8_t *host_out, size_t n_strips) {
     return SVO_OK;
 }
 
+int svo_diag_schedule(svo_ctx *ctx, int slot, uint32_t info_out[16], uint8_t *classes_out, size_t n_classes, uint8_t *classes_now_out,
+                      uint32_t *lists_out, size_t list_words, uint32_t balance_out[32]) {
+    if (!ctx || !info_out || !balance_out || slot < 0 || slot > 1) return SVO_ERR_ARG;
+    const svo_ctx::Sched &sc = ctx->sched[slot];
+    if (!sc.cost || !sc.cls_now || !sc.order || !sc.balance) return svo_fail(ctx, SVO_ERR_STATE, "the schedule slot has no buffers: no scheduled frame yet");
+    int rc = bind(ctx);
+    if (rc) return rc;
+    const uint32_t n_strips = (sc.key.n_items + 63u) / 64u, cap = svo::order_list_cap(n_strips);
+    const uint32_t info[16] = {n_strips, cap, svo::order_bpr(sc.key, n_strips), sc.state.valid, sc.state.order_filtered, sc.state.age,
+                               sc.state.balance_frames, sc.state.floored};
+    memcpy(info_out, info, sizeof info);
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    n_classes = std::min(n_classes, sc.cap);
+    if (classes_out && n_classes) HIP_TRY(ctx, hipMemcpy(classes_out, sc.cost, n_classes, hipMemcpyDeviceToHost));
+    if (classes_now_out && n_classes) HIP_TRY(ctx, hipMemcpy(classes_now_out, sc.cls_now, n_classes, hipMemcpyDeviceToHost));
+    list_words = std::min(list_words, sc.order.size());
+    if (lists_out && list_words) HIP_TRY(ctx, hipMemcpy(lists_out, sc.order, list_words * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    HIP_TRY(ctx, hipMemcpy(balance_out, sc.balance, 32 * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    return SVO_OK;
+}
+
 int svo_scan_dispatch(svo_ctx *ctx, uint32_t node_length) {
     if (!ctx) return SVO_ERR_ARG;
     if (!ctx->nodes) return svo_fail(ctx, SVO_ERR_STATE, "svo_nodes_alloc not called");

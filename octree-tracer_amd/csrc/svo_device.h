@@ -102,17 +102,18 @@ constexpr uint32_t kMaxScheduledStrips = 1u << 20;  // (2^26 items / 64)
 #endif
 constexpr uint32_t kCostShift = SVO_COST_SHIFT, kCostClasses = 128u >> SVO_COST_SHIFT;
 constexpr uint32_t kOrderHistWords = 64 * kCostClasses;  // chunk histograms of the schedule builder, stored behind the class bytes
-// list-share feedback of a schedule (balance_step): [0..8] cumulative shares of the 8 lists (16-bit fractions, [0] = 0, [8] = 65536),
-// then the words below; behind them (kBalanceHead) one end stamp per workgroup of the trace launch (workgroup b started on list b % 8)
-constexpr uint32_t kBalanceStart = 9;         // start stamp of the last frame's first workgroup
-constexpr uint32_t kBalanceUpdates = 18;      // updates so far
-constexpr uint32_t kBalanceStamps = 19;       // the last trace launch's workgroups
-constexpr uint32_t kBalanceBestTime = 20;     // the shortest frame so far (ticks; 0: none yet)
-constexpr uint32_t kBalanceBestShares = 21;   // [21..29] the shares it was traced with
-constexpr uint32_t kBalanceHead = 32, kBalanceSlots = 4096, kBalanceWords = kBalanceHead + kBalanceSlots;
-// entries reserved per list of a schedule: a list holds its share of every cost class -- an eighth, or what the feedback gives it
-// (at most twice that)
+// (the list-share feedback's balance words, kBalance*: svo_sched.h, beside the share step)
+// entries reserved per list of a schedule: a list holds its share of every cost class -- an eighth, or what the feedback gives it.
+// The bound this needs: no list's share exceeds 2/8 (16384 of 65536).  Then its part of class c is at most
+// (total_c * 16384 + 32768 >> 16) + 1 <= total_c / 4 + 1 strips after both of its bounds are rounded, n / 4 + kCostClasses over all
+// classes.  The share step's constants kShareMin, kShareMax and kShareStepMin give it: the proof is beside balance_share_step in
+// svo_sched.h; tests/test_sched_host.py holds the step to the bound and the list build to the cap.
 inline uint32_t order_list_cap(uint32_t n_strips) { return (n_strips + 3u) / 4u + kCostClasses; }
+// blocks per row for the schedule builder's column-major ranks (0: rank in strip order): frames of one rectangle of whole pixel blocks
+inline uint32_t order_bpr(const WorkDesc &w, uint32_t n_strips) {
+    if (w.mode == 2 || w.n_rects > 1u || w.bpr == 0u || n_strips % w.bpr != 0u || n_strips * 64u != w.n_items) return 0u;
+    return w.bpr;
+}
 // the device buffers of one schedule slot (svo_ctx::Sched)
 struct SchedBuffers {
     uint8_t *cost;      // the strips' cost classes; kOrderHistWords words of chunk histograms behind them

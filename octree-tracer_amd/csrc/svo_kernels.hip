@@ -1484,39 +1484,9 @@ __device__ __forceinline__ void balance_step(uint32_t *bal, float gain, uint32_t
     }
     __syncthreads();
     if (threadIdx.x != 0u) return;
-    if (update <= kBalanceLearnFrames && t_last != 0u && (update == 1u || bal[kBalanceBestTime] == 0u || t_last < bal[kBalanceBestTime])) {
-        bal[kBalanceBestTime] = t_last;
-        for (int k = 0; k <= 8; k++) bal[kBalanceBestShares + k] = bal[k];
-    }
-    if (update == kBalanceLearnFrames && bal[kBalanceBestTime] != 0u) {  // the schedule built next is the one a resting view keeps
-        for (int k = 0; k <= 8; k++) bal[k] = bal[kBalanceBestShares + k];
-        bal[kBalanceUpdates] += 1u;
-        return;
-    }
-    float T[8], w[8], mean = 0.0f;
-    bool ok = true;
-    for (int k = 0; k < 8; k++) {
-        ok = ok && t_n[k] > 0.0f;
-        T[k] = ok ? t_sum[k] / t_n[k] : 1.0f;
-        w[k] = (float)(bal[k + 1] - bal[k]);
-        mean += T[k] * 0.125f;
-    }
-    if (!ok) return;
-    float sum = 0.0f;
-    for (int k = 0; k < 8; k++) {
-        const float r = fminf(fmaxf(mean / T[k], 0.8f), 1.25f);
-        w[k] = fminf(fmaxf(w[k] * (1.0f + gain * (r - 1.0f)), 0.6f * 8192.0f), 1.6f * 8192.0f);
-        sum += w[k];
-    }
-    uint32_t acc = 0u;
-    float run = 0.0f;
-    for (int k = 0; k < 8; k++) {
-        bal[k] = acc;
-        run += w[k];
-        acc = k == 7 ? 65536u : (uint32_t)(run / sum * 65536.0f + 0.5f);
-    }
-    bal[8] = 65536u;
-    bal[kBalanceUpdates] += 1u;
+    float T[8];  // (every counted stamp is positive, so a mean of 0 says that a list left none)
+    for (int k = 0; k < 8; k++) T[k] = t_n[k] > 0.0f ? t_sum[k] / t_n[k] : 0.0f;
+    balance_share_step(bal, T, t_last, gain, update);  // svo_sched.h: keep-best, restore, step, renormalise
 }
 
 __global__ __launch_bounds__(256) void post_kernel(TraceArgs a, uint32_t *claim_counters, const uint32_t *list,

@@ -2,6 +2,7 @@
 // what the post pass measures and rebuilds after it.  Plain C++ (no HIP): the host glue in svo_abi.cpp (trace_launch) measures the
 // facts and runs the launches, tests/test_schedule_plan.py replays frame sequences through these two functions.
 #pragma once
+#include <cmath>
 #include <cstdint>
 
 namespace svo {
@@ -49,6 +50,71 @@ struct PostPlan {
     uint32_t motion_floor = 0;     // non-zero: strips near the long ones of this frame are not scheduled as cheap (strip_danger_kernel)
     uint32_t balance_update = 0;   // n > 0: the n-th frame fed back steps the shares (balance_step)
 };
+
+// list-share feedback of a schedule (balance_step): [0..8] cumulative shares of the 8 lists (16-bit fractions, [0] = 0, [8] = 65536),
+// then the words below; behind them (kBalanceHead) one end stamp per workgroup of the trace launch (workgroup b started on list b % 8)
+constexpr uint32_t kBalanceStart = 9;         // start stamp of the last frame's first workgroup
+constexpr uint32_t kBalanceUpdates = 18;      // updates so far
+constexpr uint32_t kBalanceStamps = 19;       // the last trace launch's workgroups
+constexpr uint32_t kBalanceBestTime = 20;     // the shortest frame so far (ticks; 0: none yet)
+constexpr uint32_t kBalanceBestShares = 21;   // [21..29] the shares it was traced with
+constexpr uint32_t kBalanceHead = 32, kBalanceSlots = 4096, kBalanceWords = kBalanceHead + kBalanceSlots;
+// a list's share of a cost class stays within these factors of an eighth, and moves by at most kShareStepMax per update
+constexpr float kShareMin = 0.6f, kShareMax = 1.6f, kShareStepMin = 0.8f, kShareStepMax = 1.25f;
+
+#if defined(__HIPCC__)
+#define SVO_SCHED_HD __host__ __device__
+#else
+#define SVO_SCHED_HD
+#endif
+
+// The share step of one fed-back frame, after its stamps are reduced (svo_kernels.hip: balance_step, one thread; tests/test_sched_host.py
+// drives it on the host).  T[k]: the mean time of list k's sampled workgroups (0: none of them left a stamp), t_last: the latest
+// stamp (the frame's time; 0: none), update: n = the n-th frame fed back, bal: the kBalanceHead head words.
+// Keep-best: the shares the frame was traced with are noted when it beat every frame since the layout was new; update
+// kBalanceLearnFrames puts the best ones back and steps no more.  Otherwise share *= 1 + gain (mean / T - 1), the ratio clamped to
+// kShareStepMin .. kShareStepMax and the share to kShareMin .. kShareMax eighths, and the eight are renormalised to cumulative 16-bit
+// fractions.  No step when a list has no stamp.
+// After it bal[0] = 0 < bal[1] < ... < bal[8] = 65536 and no share exceeds a quarter (16384), which is what order_list_cap relies on.
+// By induction from the equal shares: a share leaves the clamp at no more than kShareMax / 8 = 13107.2, while the other seven sum to
+// at least 65536 - 16384 = 49152 before the step.  A step takes gain * (1 - kShareStepMin) = 12 % of a share at the largest gain
+// (0.6), and the upper clamp takes more only from a share above 13107.2 / 0.88 = 14894.  No share is ever below 3072 (the lower
+// clamp, 4915.2, of a sum of at most 8 * 13107.2), so the seven lose most when they are 16384, 16384, 4096 and four times 3072:
+// they keep 2 * 13107.2 + 0.88 * 16384 = 40632, and the renormalised share is at most 13107.2 / (13107.2 + 40632) = 0.2439,
+// 15984 of 65536 -- 400 below 16384, where rounding the cumulative fractions adds at most one.  Lists that stay fastest settle
+// near 0.227 (tests/test_sched_host.py holds every update to the bound).
+SVO_SCHED_HD inline void balance_share_step(uint32_t *bal, const float T[8], uint32_t t_last, float gain, uint32_t update) {
+    if (update <= kBalanceLearnFrames && t_last != 0u && (update == 1u || bal[kBalanceBestTime] == 0u || t_last < bal[kBalanceBestTime])) {
+        bal[kBalanceBestTime] = t_last;
+        for (int k = 0; k <= 8; k++) bal[kBalanceBestShares + k] = bal[k];
+    }
+    if (update == kBalanceLearnFrames && bal[kBalanceBestTime] != 0u) {  // the schedule built next is the one a resting view keeps
+        for (int k = 0; k <= 8; k++) bal[k] = bal[kBalanceBestShares + k];
+        bal[kBalanceUpdates] += 1u;
+        return;
+    }
+    float w[8], mean = 0.0f;
+    for (int k = 0; k < 8; k++) {
+        if (!(T[k] > 0.0f)) return;
+        w[k] = (float)(bal[k + 1] - bal[k]);
+        mean += T[k] * 0.125f;
+    }
+    float sum = 0.0f;
+    for (int k = 0; k < 8; k++) {
+        const float r = fminf(fmaxf(mean / T[k], kShareStepMin), kShareStepMax);
+        w[k] = fminf(fmaxf(w[k] * (1.0f + gain * (r - 1.0f)), kShareMin * 8192.0f), kShareMax * 8192.0f);
+        sum += w[k];
+    }
+    uint32_t acc = 0u;
+    float run = 0.0f;
+    for (int k = 0; k < 8; k++) {
+        bal[k] = acc;
+        run += w[k];
+        acc = k == 7 ? 65536u : (uint32_t)(run / sum * 65536.0f + 0.5f);
+    }
+    bal[8] = 65536u;
+    bal[kBalanceUpdates] += 1u;
+}
 
 inline bool stored_lists(const SchedState &s) { return s.valid && !s.order_filtered; }
 

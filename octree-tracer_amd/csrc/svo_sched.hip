@@ -244,12 +244,6 @@ __global__ __launch_bounds__(256) void strip_cull_kernel(TraceArgs a, const uint
     }
 }
 
-// blocks per row for the schedule builder's column-major ranks (0: rank in strip order): frames of one rectangle of whole pixel blocks
-static uint32_t order_bpr(const WorkDesc &w, uint32_t n_strips) {
-    if (w.mode == 2 || w.n_rects > 1u || w.bpr == 0u || n_strips % w.bpr != 0u || n_strips * 64u != w.n_items) return 0u;
-    return w.bpr;
-}
-
 // the two kernels of the schedule builder for the class bytes `cls` (the chunk histograms live behind them)
 static void launch_order_pair(const WorkDesc &w, const uint8_t *cls, uint32_t *sched, uint32_t n_strips, uint32_t cap, hipStream_t stream,
                               const uint32_t *shares = nullptr) {

@@ -139,6 +139,25 @@ class Gpu:
             out["stamps"] = stp
         return out
 
+    SCHEDULE_INFO = ("n_strips", "cap", "bpr", "valid", "order_filtered", "age", "balance_frames", "floored")
+
+    def schedule_status(self, slot=0):
+        """what schedule slot `slot` (0: primary frames, 1: shadow and secondary rays) holds, read-only (svo_diag_schedule): a dict
+        of SCHEDULE_INFO and the numpy arrays classes (the measured cost classes), classes_now (those of the last filtered or
+        floored build; 0xFF: in no list), lengths (8), lists (8 x cap strip numbers; entries behind a list's length are stale)
+        and balance (32 words: [0..8] cumulative shares, [18] updates, [20] best time, [21..29] best shares); diagnostics"""
+        import numpy as np
+        info, bal = np.zeros(16, dtype=np.uint32), np.zeros(32, dtype=np.uint32)
+        ptr = lambda a: a.ctypes.data_as(C.c_void_p)
+        self.check(lib().svo_diag_schedule(self._h, slot, ptr(info), None, 0, None, None, 0, ptr(bal)))
+        n, cap = int(info[0]), int(info[1])
+        cls, now = np.zeros(n, dtype=np.uint8), np.zeros(n, dtype=np.uint8)
+        words = np.zeros(8 + 8 * cap, dtype=np.uint32)
+        self.check(lib().svo_diag_schedule(self._h, slot, ptr(info), ptr(cls), n, ptr(now), ptr(words), words.size, ptr(bal)))
+        out = dict(zip(self.SCHEDULE_INFO, (int(v) for v in info)))
+        out.update(classes=cls, classes_now=now, lengths=words[:8].copy(), lists=words[8:].reshape(8, cap), balance=bal)
+        return out
+
     def timing_collect(self, cap=65536):
         """durations (ms) of the trace launches recorded since the last collect"""
         import numpy as np
