@@ -500,6 +500,56 @@ int svo_nodes_list_voxels(svo_ctx *ctx, const svo_list_params *p, uint32_t *xyz_
 #define SVO_LIST_TIMES 5
 int svo_list_timing(svo_ctx *ctx, float ms_out[SVO_LIST_TIMES]);
 
+/* ---- the visible surface of the tree in the node buffer, found on the device ----
+ * Which faces of the voxels that svo_nodes_list_voxels lists are exposed.  The tree is the first n_words words of the node
+ * buffer rooted at group 0; the word test, the levels, the child index x * 4 + y * 2 + z, the coordinates on the `depth`
+ * grid and the Morton order are exactly the listing's, and the low 4 bits of a word never matter.
+ * A voxel word at level l is a cube with cell c on the level-l grid.  Its faces are numbered f = 0 .. 5: -x, +x, -y, +y,
+ * -z, +z, and the cell behind face f is n = c - 1 (even f) or c + 1 (odd f) on axis f >> 1.
+ *     n leaves [0, 2^l) on that axis:   the face is exposed; with SVO_SURFACE_CLOSED_BOUNDARY it is covered
+ *     otherwise walk from group 0 towards n for at most l levels, by the sampler's rule (svo_nodes_sample):
+ *         the walk stops on a voxel word (value > 0) at a level <= l:   covered
+ *         it stops on the empty word:                                   exposed
+ *         the word at level l is interior (the neighbour is finer):     exposed
+ * The rule is conservative: a face reported covered is covered in every cell of it; a face reported exposed touches an
+ * empty cell or finer detail.  It is exact for a tree whose voxels all sit at `depth`.
+ * flags without SVO_SURFACE_KEEP_HIDDEN and SVO_SURFACE_QUADS: one entry per voxel with at least one exposed face, in the
+ * listing's order (ascending Morton key of the minimum corner at `depth`): xyz the minimum corner, value and level as
+ * in the listing, face the 6-bit mask, bit f set when face f is exposed.
+ * SVO_SURFACE_KEEP_HIDDEN: the voxels with mask 0 are kept too: xyz, value and level are byte-identical to
+ * svo_nodes_list_voxels with flags 0, and face lines up with them.
+ * SVO_SURFACE_QUADS: one entry per exposed face, the voxels in the listing's order and the faces of a voxel in ascending
+ * f: xyz, value and level are the voxel's, face is f (0..5).  Not together with SVO_SURFACE_KEEP_HIDDEN.
+ * xyz_out_dev == NULL is a count query: *n_out gets the number of entries, nothing else is written and max_entries is
+ * ignored.  Otherwise xyz_out_dev (3 * max_entries u32), value_out_dev, level_out_dev (or NULL) and face_out_dev
+ * (max_entries u32 each) are DEVICE pointers of which only the entries [0, *n_out) are written.  The node buffer is never
+ * written.  No atomics: the same bytes on every run and for every layout of the same tree.
+ * Errors are decided before any write to the outputs and leave them and *n_out as they were; they are the listing's, in
+ * its order and with its wording: SVO_ERR_ARG: NULL p or n_out; unknown or incompatible flag bits; depth outside 1..21;
+ * NULL face_out_dev or value_out_dev with xyz_out_dev given; SVO_ERR_STATE: no node buffer; SVO_ERR_ARG: n_words; SVO_ERR_STATE:
+ * the "malformed tree: ..." causes; SVO_ERR_ARG: a voxel or an interior word at a level deeper than `depth`; SVO_ERR_CAP, with
+ * the exact count in svo_last_error: 2^31 voxels or more, then more entries than max_entries (not for a count query) or
+ * 2^31 entries or more.  A device adaptive state attached to the context is no obstacle.
+ * Runs on the ctx stream behind the store's last write, whichever context issued it, and records no write of its own.
+ * Blocks where the listing blocks, once per level of the tree and once for the counts, and once more for the number of
+ * entries; the fill is enqueued (svo_sync before the outputs are read on another stream). */
+#define SVO_SURFACE_CLOSED_BOUNDARY 1u  /* the grid's own boundary covers the faces on it */
+#define SVO_SURFACE_KEEP_HIDDEN     2u  /* voxels without an exposed face are listed too */
+#define SVO_SURFACE_QUADS           4u  /* one entry per exposed face */
+typedef struct svo_surface_params {
+    uint32_t flags;        /* SVO_SURFACE_* */
+    uint32_t depth;        /* 1..21: the grid the coordinates are given on */
+    uint64_t n_words;      /* the tree: words [0, n_words) of the node buffer, rooted at group 0 */
+    uint64_t max_entries;  /* room in the output arrays, in entries */
+} svo_surface_params;
+int svo_nodes_list_surface(svo_ctx *ctx, const svo_surface_params *p, uint32_t *xyz_out_dev, uint32_t *value_out_dev,
+                           uint32_t *level_out_dev /* may be null */, uint32_t *face_out_dev, uint64_t *n_out);
+/* Times (ms) of the last surface call: [0] discover (with its per-level read-backs), [1] count (with its read-back), [2]
+ * offsets, [3] mask, [4] the compaction's count (with its read-back), [5] emit (device events; waits for the emit; 0 for a
+ * count query), [6] host wall time of the call.  A refused call leaves the times of the last call that ran. */
+#define SVO_SURFACE_TIMES 7
+int svo_surface_timing(svo_ctx *ctx, float ms_out[SVO_SURFACE_TIMES]);
+
 /* ---- the tree in the node buffer sampled on the device ----
  * What is at a cell of the `depth` grid, read from the first n_words words of the node buffer as a tree rooted at group 0;
  * coordinates, child index and levels are those of svo_nodes_build, svo_nodes_edit and svo_nodes_list_voxels.  For the

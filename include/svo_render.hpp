@@ -316,6 +316,20 @@ class Render {  // render.rs:3-285
         gpu_.poll_wait();
         return n;
     }
+    // the visible surface of that tree, found on the GPU (svo_nodes_list_surface): list_voxels' entries that
+    // show a face, in its order, with faces_dev (max_entries) the 6-bit mask of the exposed faces (bit f: -x, +x, -y, +y,
+    // -z, +z); flags: SVO_SURFACE_CLOSED_BOUNDARY (the grid's boundary covers), SVO_SURFACE_KEEP_HIDDEN (masks of 0 stay)
+    // or SVO_SURFACE_QUADS (one entry per exposed face, faces_dev its number 0..5).  A face is covered when a leaf of the
+    // same or a coarser level stands behind it.  All outputs are DEVICE pointers; returns the entry count; xyz_dev null:
+    // the count alone.  Throws, with nothing written, for what list_voxels throws and for more entries than max_entries.
+    uint64_t list_surface(uint64_t n_words, uint32_t depth, uint32_t *xyz_dev, uint32_t *values_dev, uint32_t *faces_dev,
+                          uint64_t max_entries, uint32_t flags = 0, uint32_t *levels_dev = nullptr) {
+        const svo_surface_params p{flags, depth, n_words, max_entries};
+        uint64_t n = 0;
+        gpu_.check(svo_nodes_list_surface(gpu_.ctx(), &p, xyz_dev, values_dev, levels_dev, faces_dev, &n));
+        gpu_.poll_wait();
+        return n;
+    }
     // a triangle mesh voxelised on the GPU, conservatively and exactly (svo_mesh_voxelize): vq_dev
     // (3 * n_vertices quantised coordinates, 64 per cell of the 2^depth grid), tri_dev (3 * n_tris vertex indices),
     // tri_colours_dev (n_tris x 0x00RRGGBB, or null: `colour`) and the outputs xyz_dev (3 * max_voxels u32), colours_dev

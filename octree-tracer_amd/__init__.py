@@ -12,7 +12,8 @@ C ABI of libsvo_hip.so:
     procedural.Procedural <- src/procedural.rs Procedural {generate_chunk} (deterministic: DESIGN.md 11)
     adaptive           <- src/adaptive.rs  process_subdivision / process_unsubdivision
     scenes             deterministic benchmark scene generators (no reference counterpart)
-    mesh               triangle meshes voxelised on the GPU into voxel lists, a Wavefront reader, mesh generators (no reference counterpart)
+    mesh               triangle meshes voxelised on the GPU into voxel lists, a tree's visible surface as a triangle mesh, a Wavefront
+                       reader and writer, mesh generators (no reference counterpart)
     structure.Structure <- src/cpu_octree.rs CpuOctree::load_structure: a .vox model as offsets, block indices and colours
 The package directory name contains a hyphen; import it through __graft_entry__.load_package(),
 which registers it as module `octree_tracer_amd`.

@@ -1,8 +1,9 @@
 // svo_ctx.h -- the device context behind the opaque `svo_ctx` of include/svo_hip.h, and the host helpers of the files that
 // use it: svo_abi.cpp (trace / scan dispatch), svo_comm.cpp (RCCL frame gather) and the GPU tree passes (svo_proc.hip,
 // svo_build.hip, svo_edit.hip, svo_compact.hip, svo_list.hip, svo_sample.hip, svo_voxelize.hip, svo_structure.hip,
-// svo_adapt.hip).  One rule of ownership for the context, the node store and every pass's state: a member owns what it
-// holds, as svo_dev / svo_pinned (an allocation and its size), svo_events (events) or svo_stream (a stream).  The passes
+// svo_surface.hip, svo_adapt.hip).  One rule of ownership for the context, the node store and every pass's state: a
+// member owns what it holds, as svo_dev / svo_pinned (an allocation and its size), svo_events (events) or svo_stream (a
+// stream).  The passes
 // share the rest as their host frame: svo_grow / svo_grow_pinned / svo_grow_keep (workspaces, by the buffers' own
 // sizes), svo_mirrored (device words with a pinned mirror), svo_pass_timer (events and times), svo_workspace_ensure
 // (creation) and the svo_check_* argument checks; then the builder's sort and svo_world_writer (a generated world's
@@ -142,6 +143,7 @@ struct svo_list_state;
 struct svo_sample_state;
 struct svo_voxelize_state;
 struct svo_structure_state;
+struct svo_surface_state;
 template <typename T>
 using svo_workspace = std::unique_ptr<T, void (*)(T *)>;
 template <typename T>
@@ -251,6 +253,7 @@ struct svo_ctx {
     svo_workspace<svo_sample_state> sample{nullptr, nullptr};  // sampling's events and times (svo_sample.hip)
     svo_workspace<svo_voxelize_state> voxelize{nullptr, nullptr};  // mesh voxeliser's workspace (svo_voxelize.hip)
     svo_workspace<svo_structure_state> structure{nullptr, nullptr};  // structure scattering's workspace (svo_structure.hip)
+    svo_workspace<svo_surface_state> surface{nullptr, nullptr};  // surface extraction's workspace (svo_surface.hip)
     std::string err;
 };
 
@@ -448,6 +451,29 @@ struct svo_tree_walk {
     std::vector<uint32_t> level_off;
 };
 int svo_tree_discover(svo_ctx *ctx, uint64_t n_words, svo_tree_walk *w, hipEvent_t discovered);
+// svo_list.hip
+// The plan of a listing, for svo_nodes_list_voxels and the surface pass (svo_surface.hip), each with a plan
+// of its own: the discovery's workspace, then per group k of order its entry and record counts (cnt, rcnt), the place of
+// its first entry and record in the list (start, rstart) and its Morton prefix (key: a leading 1, then 3 bits per level
+// above the group's words).  create() makes the status words, grow() room for `groups` groups.  svo_list_plan_count, on
+// the ctx stream: the discovery (`discovered`, or null, is recorded behind it), the counts bottom-up and their read-back;
+// it refuses, with the listing's messages and in its order, a malformed tree, a voxel or an interior word deeper than
+// `depth`, and 2^31 entries or more; then level_off (level l: order[level_off[l - 1], level_off[l])), listed = min(levels,
+// depth), count and n_rec hold.  svo_list_plan_offsets enqueues the top-down pass: start, rstart and key of the groups of
+// the levels 1..listed.
+struct svo_list_plan {
+    svo_dev<uint32_t> order, first_child, new_of, scan;  // the discovery's
+    svo_dev<uint32_t> rcnt, start, rstart;
+    svo_dev<uint64_t> cnt, key;
+    svo_mirrored<> status;
+    std::vector<uint32_t> level_off;
+    uint32_t listed = 0, n_rec = 0;
+    uint64_t count = 0;
+    int create(svo_ctx *ctx);
+    int grow(svo_ctx *ctx, size_t groups);
+};
+int svo_list_plan_count(svo_ctx *ctx, svo_list_plan *plan, uint64_t n_words, uint32_t depth, bool expand, hipEvent_t discovered);
+int svo_list_plan_offsets(svo_ctx *ctx, svo_list_plan *plan, uint32_t depth, bool expand);
 // The one writer of a generated world's directory (svo_build.hip), for svo_world_build and
 // svo_world_generate: create() makes the directory and the empty root; add_chunk() writes <id>.bin (id = SVO_CHUNK_OFFSET
 // / 2 + i) from `bytes` in the <id>.bin layout, keeps the chunk in w as a node-less CpuOctree carrying its top_mip (the

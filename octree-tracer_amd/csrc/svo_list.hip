@@ -20,6 +20,8 @@
 //             Morton suffix is the entry's distance from the record's start
 //
 // Every error is decided before the offsets, so it leaves the outputs as they were.  The node buffer is only read.
+// Discover, count and offsets stand behind svo_list_plan_count and svo_list_plan_offsets (svo_ctx.h): the surface pass
+// (svo_surface.hip) runs them too, on a plan of its own.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -28,16 +30,13 @@
 
 #include "svo_ctx.h"
 #include "svo_group.h"   // (kThreads; group_lane: 8 lanes per group; kMaxWords)
-#include "svo_morton.h"  // (morton_decode)
+#include "svo_morton.h"  // (morton_decode, key_bits)
 
 namespace {
 
 constexpr uint64_t kMaxEntries = 1ull << 31;
 // the words read back: the discovery's (svo_ctx.h), the root's counts, one note per level below `depth`
 enum Status { kStCountLo = SVO_WALK_STATUS, kStCountHi, kStRecords, kStPad, kStDeep, kStWords = kStDeep + 32 };
-
-// the level of the words of a group with Morton prefix `key`, or of a word with cell key `key`, minus one
-__device__ inline uint32_t key_bits(uint64_t key) { return (63u - (uint32_t)__clzll((long long)key)) / 3u; }
 
 // What a word adds to its group's entry and record counts; `leaf` entries per voxel of this level, `coarse`: such a
 // voxel is a record.  Every lane of the wave must get here with group_lane's result.
@@ -194,34 +193,77 @@ __global__ __launch_bounds__(kThreads) void list_expand_kernel(uint32_t depth, L
 
 enum Ev { kEvStart, kEvDiscover, kEvCount, kEvOffsets, kEvEmit, kEvs };
 
+// the entries a voxel of `level` gives, and whether it is a record of the expansion
+uint64_t leaf_entries(bool expand, uint32_t depth, uint32_t level) { return expand ? 1ull << 3u * (depth - level) : 1ull; }
+uint32_t coarse_records(bool expand, uint32_t depth, uint32_t level) { return expand && level < depth ? 1u : 0u; }
+
 }  // namespace
 
-// Per-context workspace of the listing (svo_ctx::list): eleven u32 per group, four per record.
+// Per-context workspace of the listing (svo_ctx::list): its plan (svo_ctx.h: eleven u32 per group), four u32 per record.
 struct svo_list_state {
-    svo_dev<uint32_t> order, first_child, new_of, scan;  // the discovery's
-    svo_dev<uint32_t> rcnt, start, rstart;
-    svo_dev<uint64_t> cnt, key;
+    svo_list_plan plan;
     svo_dev<uint32_t> rec_start, rec_value;
     svo_dev<uint64_t> rec_key;
-    svo_mirrored<> status;  // kStWords words
     svo_pass_timer<kEvs, SVO_LIST_TIMES> timer;
 
     int create(svo_ctx *ctx) {
         HIP_TRY(ctx, timer.create());
-        return status.alloc(ctx, kStWords);
+        return plan.create(ctx);
     }
 };
 
-namespace {
+int svo_list_plan::create(svo_ctx *ctx) { return status.alloc(ctx, kStWords); }
 
-int ensure_state(svo_ctx *ctx, size_t groups) {
-    if (int rc = svo_workspace_ensure(ctx, ctx->list)) return rc;
-    svo_list_state *s = ctx->list.get();
-    return svo_grow(ctx, groups, &s->order, &s->first_child, &s->new_of, &s->scan, &s->rcnt, &s->start, &s->rstart,
-                    &s->cnt, &s->key);
+int svo_list_plan::grow(svo_ctx *ctx, size_t groups) {
+    return svo_grow(ctx, groups, &order, &first_child, &new_of, &scan, &rcnt, &start, &rstart, &cnt, &key);
 }
 
-}  // namespace
+int svo_list_plan_count(svo_ctx *ctx, svo_list_plan *s, uint64_t n_words, uint32_t depth, bool expand, hipEvent_t discovered) {
+    const uint32_t *st = s->status.host();
+    HIP_TRY(ctx, s->status.zero(ctx));
+
+    // discover and check
+    svo_tree_walk walk{s->order, s->first_child, s->new_of, s->scan, s->status, {}};
+    if (int rc = svo_tree_discover(ctx, n_words, &walk, discovered)) return rc;
+    s->level_off = std::move(walk.level_off);  // level l: order[level_off[l - 1], level_off[l])
+    const std::vector<uint32_t> &level_off = s->level_off;
+    const uint32_t n_levels = (uint32_t)level_off.size() - 1;
+    s->listed = std::min(n_levels, depth);
+
+    // count
+    for (uint32_t l = n_levels; l >= 1; l--) {
+        const uint32_t off = level_off[l - 1], m = level_off[l] - off;
+        const bool deep = l > depth;
+        list_count_kernel<<<svo_div_up(8ull * m, kThreads), kThreads, 0, ctx->stream>>>(
+            ctx->nodes, s->order, off, m, s->first_child, deep ? 0ull : leaf_entries(expand, depth, l),
+            deep ? 0u : coarse_records(expand, depth, l), s->cnt, s->rcnt, deep ? s->status.dev + kStDeep + l : nullptr);
+    }
+    list_root_kernel<<<1, 1, 0, ctx->stream>>>(s->cnt, s->rcnt, s->status.dev, s->start, s->rstart, s->key);
+    HIP_TRY(ctx, hipGetLastError());
+    if (int rc = s->status.read(ctx)) return rc;
+    if (st[SVO_WALK_DUP]) return svo_fail(ctx, SVO_ERR_STATE, "malformed tree: a group is reached twice");
+    for (uint32_t l = n_levels; l > depth; l--)
+        if (st[kStDeep + l])
+            return svo_fail(ctx, SVO_ERR_ARG, "the tree holds a voxel or an interior word at level " + std::to_string(l) +
+                                                  ", deeper than depth = " + std::to_string(depth));
+    s->count = uint64_t(st[kStCountHi]) << 32 | st[kStCountLo];
+    s->n_rec = st[kStRecords];
+    if (s->count >= kMaxEntries)
+        return svo_fail(ctx, SVO_ERR_CAP, "the list has " + std::to_string(s->count) + " entries, 2^31 or more");
+    return SVO_OK;
+}
+
+int svo_list_plan_offsets(svo_ctx *ctx, svo_list_plan *s, uint32_t depth, bool expand) {
+    // the levels that have listed levels below them
+    for (uint32_t l = 1; l < s->listed; l++) {
+        const uint32_t off = s->level_off[l - 1], m = s->level_off[l] - off;
+        list_offsets_kernel<<<svo_div_up(8ull * m, kThreads), kThreads, 0, ctx->stream>>>(
+            ctx->nodes, s->order, off, m, s->first_child, leaf_entries(expand, depth, l), coarse_records(expand, depth, l), s->cnt,
+            s->rcnt, s->start, s->rstart, s->key);
+    }
+    HIP_TRY(ctx, hipGetLastError());
+    return SVO_OK;
+}
 
 extern "C" {
 
@@ -238,43 +280,17 @@ int svo_nodes_list_voxels(svo_ctx *ctx, const svo_list_params *p, uint32_t *xyz_
     const double t0 = svo_now_ms();
     const uint32_t n_words = (uint32_t)std::min<uint64_t>(p->n_words, kMaxWords), depth = p->depth;
     const bool expand = p->flags & SVO_LIST_EXPAND;
-    if ((rc = ensure_state(ctx, n_words / 8))) return rc;
+    if ((rc = svo_workspace_ensure(ctx, ctx->list))) return rc;
     svo_list_state *s = ctx->list.get();
-    if ((rc = s->timer.begin(ctx))) return rc;
-    const uint32_t *st = s->status.host();
+    if ((rc = s->plan.grow(ctx, n_words / 8)) || (rc = s->timer.begin(ctx))) return rc;
 
     // the passes read the words: behind every earlier write to the store, whichever context issued it
     if ((rc = svo_store_order_after_write(ctx))) return rc;
     HIP_TRY(ctx, s->timer.mark(ctx, kEvStart));
-    HIP_TRY(ctx, s->status.zero(ctx));
-
-    // discover and check
-    svo_tree_walk walk{s->order, s->first_child, s->new_of, s->scan, s->status, {}};
-    if ((rc = svo_tree_discover(ctx, p->n_words, &walk, s->timer.ev[kEvDiscover]))) return rc;
-    const std::vector<uint32_t> &level_off = walk.level_off;  // level l: order[level_off[l - 1], level_off[l])
-    const uint32_t n_levels = (uint32_t)level_off.size() - 1, listed = std::min(n_levels, depth);
-    const auto leaf = [&](uint32_t level) { return expand ? 1ull << 3u * (depth - level) : 1ull; };
-    const auto coarse = [&](uint32_t level) { return expand && level < depth ? 1u : 0u; };
-
-    // count
-    for (uint32_t l = n_levels; l >= 1; l--) {
-        const uint32_t off = level_off[l - 1], m = level_off[l] - off;
-        const bool deep = l > depth;
-        list_count_kernel<<<svo_div_up(8ull * m, kThreads), kThreads, 0, ctx->stream>>>(
-            ctx->nodes, s->order, off, m, s->first_child, deep ? 0ull : leaf(l), deep ? 0u : coarse(l), s->cnt, s->rcnt,
-            deep ? s->status.dev + kStDeep + l : nullptr);
-    }
-    list_root_kernel<<<1, 1, 0, ctx->stream>>>(s->cnt, s->rcnt, s->status.dev, s->start, s->rstart, s->key);
-    HIP_TRY(ctx, hipGetLastError());
-    if ((rc = s->status.read(ctx))) return rc;
-    if (st[SVO_WALK_DUP]) return svo_fail(ctx, SVO_ERR_STATE, "malformed tree: a group is reached twice");
-    for (uint32_t l = n_levels; l > depth; l--)
-        if (st[kStDeep + l])
-            return svo_fail(ctx, SVO_ERR_ARG, "the tree holds a voxel or an interior word at level " + std::to_string(l) +
-                                                  ", deeper than depth = " + std::to_string(depth));
-    const uint64_t count = uint64_t(st[kStCountHi]) << 32 | st[kStCountLo];
-    const uint32_t n_rec = st[kStRecords];
-    if (count >= kMaxEntries) return svo_fail(ctx, SVO_ERR_CAP, "the list has " + std::to_string(count) + " entries, 2^31 or more");
+    if ((rc = svo_list_plan_count(ctx, &s->plan, p->n_words, depth, expand, s->timer.ev[kEvDiscover]))) return rc;
+    const svo_list_plan &pl = s->plan;
+    const uint64_t count = pl.count;
+    const uint32_t n_rec = pl.n_rec;
     if (xyz_out_dev && count > p->max_voxels)
         return svo_fail(ctx, SVO_ERR_CAP, "the list has " + std::to_string(count) + " entries, more than max_voxels = " +
                                               std::to_string(p->max_voxels));
@@ -282,20 +298,14 @@ int svo_nodes_list_voxels(svo_ctx *ctx, const svo_list_params *p, uint32_t *xyz_
 
     if (xyz_out_dev && count) {
         if ((rc = svo_grow(ctx, (size_t)n_rec, &s->rec_start, &s->rec_value, &s->rec_key))) return rc;
-        // offsets: the levels that have listed levels below them
-        for (uint32_t l = 1; l < listed; l++) {
-            const uint32_t off = level_off[l - 1], m = level_off[l] - off;
-            list_offsets_kernel<<<svo_div_up(8ull * m, kThreads), kThreads, 0, ctx->stream>>>(
-                ctx->nodes, s->order, off, m, s->first_child, leaf(l), coarse(l), s->cnt, s->rcnt, s->start, s->rstart, s->key);
-        }
-        HIP_TRY(ctx, hipGetLastError());
+        if ((rc = svo_list_plan_offsets(ctx, &s->plan, depth, expand))) return rc;
         HIP_TRY(ctx, s->timer.mark(ctx, kEvOffsets));
 
         // emit
         const ListOut out{xyz_out_dev, value_out_dev, level_out_dev, (uint32_t)count, s->rec_start, s->rec_value, s->rec_key, n_rec};
-        const uint32_t m = level_off[listed];
-        list_emit_kernel<<<svo_div_up(8ull * m, kThreads), kThreads, 0, ctx->stream>>>(ctx->nodes, s->order, m, s->first_child, s->cnt,
-                                                                                       s->rcnt, s->start, s->rstart, s->key, depth, expand,
+        const uint32_t m = pl.level_off[pl.listed];
+        list_emit_kernel<<<svo_div_up(8ull * m, kThreads), kThreads, 0, ctx->stream>>>(ctx->nodes, pl.order, m, pl.first_child, pl.cnt,
+                                                                                       pl.rcnt, pl.start, pl.rstart, pl.key, depth, expand,
                                                                                        out);
         if (n_rec) list_expand_kernel<<<svo_div_up(count, kThreads), kThreads, 0, ctx->stream>>>(depth, out);
         HIP_TRY(ctx, hipGetLastError());

@@ -1,7 +1,8 @@
 // svo_scan.h -- the tiled count, scan and emit of the GPU passes: svo_proc.hip (a level's ranks), svo_build.hip (the
-// level passes, the sort's digit counts), svo_adapt.hip (the expand's compactions), svo_structure.hip (sites, stamp) and
-// svo_voxelize.hip (a level's pairs); svo_compact.hip, svo_list.hip (through svo_tree_discover), svo_edit.hip and
-// svo_adapt.hip scan an array in place with svo_scan_u32.  No atomics: an output's place depends on the inputs alone.
+// level passes, the sort's digit counts), svo_adapt.hip (the expand's compactions), svo_structure.hip (sites, stamp),
+// svo_voxelize.hip (a level's pairs) and svo_surface.hip (the kept entries or faces); svo_compact.hip, svo_list.hip
+// (through svo_tree_discover), svo_edit.hip and svo_adapt.hip scan an array in place with svo_scan_u32.  No atomics: an
+// output's place depends on the inputs alone.
 // A tile is kTile items, kPer consecutive ones per thread, so ranks follow the items' order.  A pass is three launches:
 //   tile_count_kernel<Items>          a thread loads the state of its items; the block adds their counts into the tile's sum
 //   tile_offsets_kernel               one block scans the tile sums in place and writes their total

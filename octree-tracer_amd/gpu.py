@@ -86,6 +86,12 @@ class Gpu:
         or refused): discover, count, offsets, emit (device events), host wall time of the call (svo_list_timing)"""
         return self._timing(lib().svo_list_timing, 5)
 
+    def surface_timing(self):
+        """ms of the last Render.list_surface / surface_quads call into the library (its fill, or its count query when the
+        list was empty or refused): discover, count, offsets, mask, the compaction's count, emit (device events), host
+        wall time of the call (svo_surface_timing)"""
+        return self._timing(lib().svo_surface_timing, 7)
+
     def sample_timing(self):
         """ms of the last Render.sample_voxels / sample_dense call that ran: the kernel (device events), host wall time of
         the call (svo_sample_timing)"""

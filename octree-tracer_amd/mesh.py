@@ -5,7 +5,9 @@ svo_mesh_voxelize, the quantisation it works on, a minimal Wavefront reader and 
     voxelize           mesh -> device voxel list (coords, colours[, triangles]) for build_nodes, edit_nodes, CpuOctree.build
                        and World.build_world: one entry per (triangle, cell) that meet, triangles in order, cells in
                        Morton order; the highest triangle index colours a shared cell
-    load_obj           v / f lines of a Wavefront file
+    quads_to_mesh      the exposed faces of a tree (Render.surface_quads) -> an indexed triangle mesh
+    extract_surface    the two in one call: the inverse of voxelize
+    load_obj, save_obj v / f lines of a Wavefront file, read and written
     fit_to_cube        uniform scale and centring into the cube
     icosphere, torus   generators for tests and tools/voxelize_probe.py
 """
@@ -101,6 +103,72 @@ def load_obj(path):
     t = np.array(triangles, dtype=np.int32).reshape(-1, 3)
     colours = np.array(rgb, dtype=np.float32).reshape(-1, 3) if rgb and all(c is not None for c in rgb) else None
     return v, t, colours
+
+
+def save_obj(path, vertices, triangles, vertex_rgb=None):
+    """Writes `v x y z [r g b]` and `f a b c` lines (indices from 1) that load_obj reads back as the same arrays, bit for
+    bit: a float32 is written as repr of the same number as a Python float, which names it exactly."""
+    v = np.asarray(vertices.cpu() if isinstance(vertices, torch.Tensor) else vertices, dtype=np.float32).reshape(-1, 3)
+    t = np.asarray(triangles.cpu() if isinstance(triangles, torch.Tensor) else triangles, dtype=np.int64).reshape(-1, 3)
+    rows = v if vertex_rgb is None else np.concatenate(
+        [v, np.asarray(vertex_rgb.cpu() if isinstance(vertex_rgb, torch.Tensor) else vertex_rgb, dtype=np.float32).reshape(-1, 3)], axis=1)
+    if t.size and (t.min() < 0 or t.max() >= len(v)):
+        raise ValueError(f"a triangle names a vertex outside the {len(v)} vertices")
+    with open(path, "w") as f:
+        f.writelines("v " + " ".join(repr(x) for x in row) + "\n" for row in rows.astype(np.float64).tolist())
+        f.writelines(f"f {a + 1} {b + 1} {c + 1}\n" for a, b, c in t.tolist())
+
+
+def _face_corners():
+    """[f][k]: corner k of face f as unit steps along x, y, z from the leaf's minimum corner"""
+    table = np.zeros((6, 4, 3), dtype=np.int64)
+    for f in range(6):
+        a = f >> 1
+        corners = ((0, 0), (1, 0), (1, 1), (0, 1))  # in (u, v) for an odd face; an even face takes them in reverse
+        for k, (cu, cv) in enumerate(corners if f & 1 else corners[::-1]):
+            table[f, k, a], table[f, k, (a + 1) % 3], table[f, k, (a + 2) % 3] = f & 1, cu, cv
+    return table
+
+
+def quads_to_mesh(coords, faces, levels, depth, colours=None, weld=True, integer=False):
+    """The quads of Render.surface_quads as an indexed triangle mesh, in plain torch on the tensors' device.  coords (Q, 3),
+    faces (Q), levels (Q), colours (Q) or None.  A quad of a leaf at level l has side s = 2^(depth - l); with a = f >> 1,
+    u = (a + 1) % 3, v = (a + 2) % 3 it lies in the plane min[a] + (f & 1) * s, and its corners are (0, 0), (s, 0), (s, s),
+    (0, s) in (u, v) for odd f and in the reverse order for even f, so its normal points out of the leaf; its triangles
+    are the corners (0, 1, 2) and (0, 2, 3).  Returns (vertices, triangles (T, 3) int32, triangle_colours (T) or None):
+    vertices float32 cell / 2^depth * 2 - 1 (exact for depth <= 21), or with integer=True the int32 grid coordinates;
+    weld: equal vertices are merged (torch.unique, sorted), else every quad keeps its own four."""
+    depth = int(depth)
+    if not 1 <= depth <= 21:
+        raise ValueError(f"depth must be 1..21 (got {depth})")
+    c = torch.as_tensor(coords).to(torch.int64).reshape(-1, 3)
+    f = torch.as_tensor(faces).to(torch.int64).reshape(-1).to(c.device)
+    side = torch.bitwise_left_shift(torch.ones_like(f), depth - torch.as_tensor(levels).to(torch.int64).reshape(-1).to(c.device))
+    if not (len(f) == len(c) == len(side)):
+        raise ValueError(f"coords, faces and levels must have one row per quad (got {len(c)}, {len(f)}, {len(side)})")
+    if len(f) and not bool(((f >= 0) & (f < 6)).all()):
+        raise ValueError("a face number outside 0..5")
+    step = torch.from_numpy(_face_corners()).to(c.device)[f]  # (Q, 4, 3)
+    cells = (c[:, None, :] + step * side[:, None, None]).reshape(-1, 3)  # (4 Q, 3) grid coordinates in [0, 2^depth]
+    index = torch.arange(4 * len(c), device=c.device)
+    if weld:
+        cells, index = torch.unique(cells, dim=0, sorted=True, return_inverse=True)
+    quad = index.reshape(-1, 4)
+    triangles = torch.stack([quad[:, [0, 1, 2]], quad[:, [0, 2, 3]]], dim=1).reshape(-1, 3).to(torch.int32)
+    if integer:
+        vertices = cells.to(torch.int32)
+    else:  # (an integer below 2^22 over a power of two: every step is exact in float32)
+        vertices = cells.to(torch.float32) / float(1 << depth) * 2.0 - 1.0
+    tri_colours = None if colours is None else torch.as_tensor(colours).reshape(-1).to(c.device).repeat_interleave(2)
+    return vertices, triangles, tri_colours
+
+
+def extract_surface(render, depth=None, closed_boundary=False, weld=True):
+    """The visible surface of the tree in render's node buffer as a triangle mesh: Render.surface_quads, then
+    quads_to_mesh, both on the GPU.  Returns (vertices float32, triangles int32, triangle_colours int32)."""
+    d = int(render.gpu.tree_depth if depth is None else depth)
+    coords, colours, faces, levels = render.surface_quads(d, closed_boundary)
+    return quads_to_mesh(coords, faces, levels, d, colours, weld=weld)
 
 
 def fit_to_cube(vertices, margin=0.02):

@@ -6,7 +6,7 @@ import torch
 
 from . import sharding
 from ._device import device_u32, voxel_list, wait_for_torch
-from ._lib import BuildParams, CompactParams, EditParams, ListParams, SampleParams, SitesParams, StampParams, TopsParams, Uniforms, lib
+from ._lib import BuildParams, CompactParams, EditParams, ListParams, SampleParams, SitesParams, StampParams, SurfaceParams, TopsParams, Uniforms, lib
 from .camera import camera_matrices
 
 F_PAUSE_ADAPTIVE, F_SHOW_STEPS, F_SHOW_HITS, F_SHADOWS, F_MISC_BOOL = 1, 2, 4, 8, 16
@@ -191,6 +191,46 @@ class Render:
                                                        levels.data_ptr() if with_levels else None, C.byref(n)))
             self.gpu.sync()
         return (coords, colours, levels) if with_levels else (coords, colours)
+
+    def _surface(self, flags, depth, with_levels):
+        """count query, then fill, of svo_nodes_list_surface: (coords, colours, faces, levels or None)"""
+        dev = self.gpu.torch_device
+        p = SurfaceParams()
+        p.flags = flags
+        p.depth = max(0, int(self.gpu.tree_depth if depth is None else depth))
+        p.n_words = int(self.node_length)
+        n = C.c_uint64()
+        self.gpu.check(lib().svo_nodes_list_surface(self.gpu._h, C.byref(p), None, None, None, None, C.byref(n)))  # the count
+        count = n.value
+        coords = torch.empty((count, 3), dtype=torch.int32, device=dev)
+        colours, faces = (torch.empty(count, dtype=torch.int32, device=dev) for _ in range(2))
+        levels = torch.empty(count, dtype=torch.int32, device=dev) if with_levels else None
+        if count:
+            p.max_entries = count
+            wait_for_torch(self.gpu)
+            self.gpu.check(lib().svo_nodes_list_surface(self.gpu._h, C.byref(p), coords.data_ptr(), colours.data_ptr(),
+                                                        levels.data_ptr() if with_levels else None, faces.data_ptr(), C.byref(n)))
+            self.gpu.sync()
+        return coords, colours, faces, levels
+
+    def list_surface(self, depth=None, closed_boundary=False, keep_hidden=False, with_levels=False):
+        """The voxels of the tree that show a face, found on the GPU (svo_nodes_list_surface).  Returns device
+        int32 tensors (coords, colours, masks[, levels]): list_voxels' entries, in its order, that have at least one exposed
+        face, and per entry the 6-bit mask of its exposed faces (bit f: -x, +x, -y, +y, -z, +z).  A face is covered when a
+        leaf of the same or a coarser level stands behind it; empty space, finer detail and the grid's boundary expose it
+        (closed_boundary: the boundary covers).  keep_hidden: every entry of list_voxels, masks of 0 included.  depth=None:
+        the depth declared for this tree, as in list_voxels.  Raises SvoError as list_voxels does.  The node buffer is
+        only read."""
+        flags = (1 if closed_boundary else 0) | (2 if keep_hidden else 0)
+        coords, colours, masks, levels = self._surface(flags, depth, with_levels)
+        return (coords, colours, masks, levels) if with_levels else (coords, colours, masks)
+
+    def surface_quads(self, depth=None, closed_boundary=False):
+        """The exposed faces of the tree, one entry each, found on the GPU (svo_nodes_list_surface with SVO_SURFACE_QUADS,
+        DESIGN.md 23).  Returns device int32 tensors (coords, colours, faces, levels): the leaf's minimum corner on the
+        `depth` grid, its colour, the face's number 0..5 (-x, +x, -y, +y, -z, +z) and the leaf's level, the leaves in
+        list_voxels' order and a leaf's faces in ascending number: what mesh.quads_to_mesh takes."""
+        return self._surface(4 | (1 if closed_boundary else 0), depth, True)
 
     def _sample_params(self, depth):
         p = SampleParams()
