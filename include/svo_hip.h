@@ -100,6 +100,13 @@ typedef struct svo_ctx svo_ctx;
  * measured slower than SVO_VARIANT_STACK on every scene and left the library in round 4; the source is kept under
  * tools/experiments/ with its logs in profiles/r03_*, DESIGN.md Appendix A.  Values 2 and 3 are refused.) */
 
+/* SVO_OPT_DEBUG_BUFFER: the buffer is two regions of SVO_DEBUG_WAVES rows of SVO_DEBUG_ROW_WORDS words, one row per wave of
+ * the trace launch in each.  While the buffer is set, a trace launch has at most SVO_DEBUG_WAVES waves: a larger
+ * SVO_OPT_GRID_BLOCKS is cut back to that (the automatic grid is far below it). */
+#define SVO_DEBUG_WAVES 16384u
+#define SVO_DEBUG_ROW_WORDS 16u
+#define SVO_DEBUG_BUFFER_WORDS (2u * SVO_DEBUG_WAVES * SVO_DEBUG_ROW_WORDS)
+
 typedef enum svo_option {
     SVO_OPT_VARIANT = 0,
     SVO_OPT_TIMING = 1,      /* n > 0: bracket trace launches with HIP events on the launch stream (ring of n) */
@@ -117,7 +124,7 @@ typedef enum svo_option {
                                 completes, svo_sync returns SVO_ERR_STATE (svo_last_error says so) and the frame's records are not to be used
                                 (tests/test_parity_gpu.py: test_tree_deeper_than_declared_is_refused) */
     SVO_OPT_BLOCK_SHAPE = 10, /* log2 of the width of the 64-pixel blocks a wave works on (3: 8x8, 4: 16x4, ...) */
-    SVO_OPT_DEBUG_BUFFER = 7, /* device pointer to 2 x 16384 x 16 words.  First region, 16 words per wave: start, queue-dry, end (10 ns
+    SVO_OPT_DEBUG_BUFFER = 7, /* device pointer to SVO_DEBUG_BUFFER_WORDS words (0: off).  First region, 16 words per wave: start, queue-dry, end (10 ns
                                  ticks), rounds, ..., shader cycles per phase (refill, descent, step), descent-loop shape; second region
                                  (round 5), 16 words per wave: loop entry, the first 14 ray generations (10 ns ticks), XCC / hardware id
                                  (tools/wave_timeline.py, tools/timeline_by_xcd.py) */

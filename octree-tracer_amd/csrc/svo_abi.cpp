@@ -738,7 +738,7 @@ int svo_set_option(svo_ctx *ctx, int option, int64_t value) {
         case SVO_OPT_PAIR_TABLE:  // (the table left the library in round 3)
             return SVO_OK;
         case SVO_OPT_DEBUG_BUFFER:
-            ctx->debug_buf = (uint32_t *)(uintptr_t)value;  // device pointer, 64 B per wave of the grid; 0 = off
+            ctx->debug_buf = (uint32_t *)(uintptr_t)value;  // device pointer to SVO_DEBUG_BUFFER_WORDS words (two rows of 64 B per wave); 0 = off
             return SVO_OK;
         case SVO_OPT_BLOCK_SHAPE:
             if (value < 0 || value > 6) return svo_fail(ctx, SVO_ERR_ARG, "block width log2 must be 0..6");

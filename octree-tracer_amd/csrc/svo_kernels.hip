@@ -306,93 +306,54 @@ struct StackLds {
     static constexpr int top = 1 << (3 * K);                                                          // top table
     static constexpr int lut = top;                                                                   // the walk's bit-spreading table, 64 words
     static constexpr int pools = lut + 64;                                                            // [BLOCK / 64][kPoolWords][64]
-    static constexpr int counting = pools + (BLOCK / 64) * (kPoolWords * 64);                         // CNT: queues, saturation tags, per-cell flags
-    static constexpr int stacks = counting + (CNT ? (BLOCK / 64) * kCountQueue + kSatTags + (1 << (3 * K)) / 8 : 0);  // [NS][BLOCK], last
+    static constexpr int counting = pools + (BLOCK / 64) * (kPoolWords * 64);                         // CNT (CountQueue): ...
+    static constexpr int queues = counting;                                                           // ... [BLOCK / 64][kCountQueue]
+    static constexpr int sat_tags = queues + (BLOCK / 64) * kCountQueue;                              // ... kSatTags saturation tags
+    static constexpr int top_sat = sat_tags + kSatTags;                                               // ... 4 flag bits per level-K cell
+    static constexpr int stacks = CNT ? top_sat + top / 8 : counting;                                 // [NS][BLOCK], last
     static constexpr int total = stacks + NS * BLOCK;
 };
 #if defined(__HIP_DEVICE_COMPILE__) && !defined(__gfx950__)
 #error "svo_kernels.hip is written for gfx950: the walk relies on its handling of LDS accesses beyond the allocation and on v_rcp_f32 + one Newton step being the IEEE reciprocal (tools/rcptest_gpu.hip)"
 #endif
 
-// CNT: hit counters live (adaptive mode, shader.wgsl:157-161), see step 3a in the loop.
-// The body of both trace kernels (they follow it): trace_stack_kernel claims its strips from the lists' counters, REPLAY = false;
-// trace_stack_replay_kernel reads them from the wave's row of a deal table (svo_deal.h, DESIGN.md 4.9), REPLAY = true -- the claim code
-// (the reserved first entry, the atomics, the probe of the 64 counters, entry_of and home) is compiled out, work_counter is not read,
-// and the wave leaves two time stamps for the deal's step.  Everything else is the same text.
-template <int BLOCK, int NS, int K, bool GE, bool DBG, bool CNT, bool SHD, bool REPLAY>
-__device__ __forceinline__ void trace_stack_body(const TraceArgs &a, uint32_t strip_items, uint32_t *work_counter, uint32_t *defer) {
-    static_assert(!REPLAY || (!DBG && !CNT && !SHD), "the replay kernel exists for the plain static frame only");
-    constexpr bool DBGH = DBG && SVO_DBG_LIGHT == 0;  // the timeline build's phase clocks and tallies (the light build keeps the time stamps only)
-    constexpr int D = kPathBits;
-    constexpr int SBASE = K + 2;       // first level kept on the LDS stack
-    constexpr int SMAX = K + 1 + NS;   // last level kept on the LDS stack = deepest level resolved
-    static_assert(SMAX <= D - 1, "stack deeper than the path codes");
-    constexpr int TBL = 1 << (3 * K);
-    using Lds = StackLds<BLOCK, NS, K, CNT>;  // (the layout: one definition for kernel and launch)
-    constexpr int kLutWords = 64;
-    constexpr int LOFF = Lds::lut;
-    constexpr int TOFF = Lds::pools;  // LDS words in front of the ray pools
-    constexpr bool kLut = NS <= 12;
-    constexpr int SOFF = Lds::stacks;
-    static_assert(Lds::total == SOFF + NS * BLOCK, "the ancestor stacks are the last LDS region (see StackLds)");
-    static_assert(D == 23, "2^D + code must be an f32 with unit spacing");
-    constexpr float kScale = (float)(1 << (D - 1));  // 2^22: grid units per unit of the cube
-    constexpr float kInvScale = 1.0f / kScale;
-    constexpr float kMagic = (float)(1 << D);        // 2^23: as_uint(kMagic + U) = 0x4B000000 | U for an integer 0 <= U < 2^23
-    constexpr float kNudge = 0.000002f * kScale;     // |voxel_pos nudge| (shader.wgsl:235) in grid units (exact: a power-of-two multiple)
-    // SHD: direction of every shadow ray, -normalize(sun_dir) (wave-uniform, kept in scalar registers)
-    float shadow_d0 = 0.0f, shadow_d1 = 0.0f, shadow_d2 = 0.0f;
-    float sDr0 = 1.0f, sDr1 = 1.0f, sDr2 = 1.0f, sY0 = 1.0f, sY1 = 1.0f, sY2 = 1.0f;  // what ray_enter and the pick-up make of it
-    float sS0 = 1.0f, sS1 = 1.0f, sS2 = 1.0f;
-    if (SHD) {
-        auto uni = [](float x) { return __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(x))); };
-        float sun[3];
-        sun_direction(a.u, sun);
-        shadow_d0 = uni(-sun[0]); shadow_d1 = uni(-sun[1]); shadow_d2 = uni(-sun[2]);
-        sDr0 = uni((shadow_d0 + ((shadow_d0 == 0.0f) ? 1.0f : 0.0f) * 0.000001f) * kScale);  // octree_ray's bias (ray_enter), then grid units
-        sDr1 = uni((shadow_d1 + ((shadow_d1 == 0.0f) ? 1.0f : 0.0f) * 0.000001f) * kScale);
-        sDr2 = uni((shadow_d2 + ((shadow_d2 == 0.0f) ? 1.0f : 0.0f) * 0.000001f) * kScale);
-        sY0 = uni(1.0f / sDr0); sY1 = uni(1.0f / sDr1); sY2 = uni(1.0f / sDr2);
-        sS0 = uni(copysign_bits(1.0f, sDr0)); sS1 = uni(copysign_bits(1.0f, sDr1)); sS2 = uni(copysign_bits(1.0f, sDr2));
-    }
-    extern __shared__ uint32_t lds[];
-    uint32_t *pool_all = lds + TOFF;  // [BLOCK / 64][kPoolWords][64]; behind them the counting queues and tables (CNT), then the stacks [NS][BLOCK]
-    // CNT: level-1 / level-2 cell -> child group (kTopAuxEntries words behind the top table): read from global memory, where the
-    // 288 bytes stay in the L1 -- in LDS they cost the sixth workgroup per CU (the allocation granule)
-    const uint32_t *aux = a.top_table + TBL;
+// ---- CNT: the queue of hit-counter visits (step 3a of the loop) ----
+// The visits of a round are not added to the counters on the spot -- a compare-and-swap is executed at the memory
+// side (the L2s of the 8 XCDs are not coherent with each other), its answer takes 0.4 - 1.3 us under this kernel's load,
+// and a round that waits for one answer per level took 8 us instead of 2.  Final counters are min(15, old + visits) in
+// whatever order the visits arrive, so every wave queues its (word, visits) pairs in LDS and adds them 64 at a time,
+// all lanes in parallel: one wait per 64 - 192 pairs instead of one per level and round.
+// What a lane learns only there -- that a word has reached 15 -- goes into a direct-mapped table of word indices shared
+// by the workgroup (exact: an entry is the index itself); step 3a looks a word up before it queues a visit, so the
+// hundreds of later visits of a word near the root cost one LDS read each, on whichever lane and ray they happen.
+// ... and what the table said about the words of levels 1..K -- which the walk never reads -- is kept per level-K cell (4 bits
+// each: bit l = the level-l word on the way to this cell is saturated): every ray picked up and every ray that crosses a
+// level-K boundary would otherwise look those words up one level per loop iteration (half of the loop's iterations), and a
+// direct-mapped table forgets.
+#ifndef SVO_COUNT_FLUSH_AT   // (A/B: flush once the queue holds more than this many records; at most kCountQueue - 64, a push adds up to 64)
+#define SVO_COUNT_FLUSH_AT (kCountQueue - 64)
+#endif
+template <int BLOCK, int NS, int K>
+struct CountQueue {
+    using Lds = StackLds<BLOCK, NS, K, true>;  // (the launch allocates the three regions for the counting instantiations only)
+    uint32_t *cq, *sat_tags, *top_sat;  // the wave's queue; the workgroup's tags and per-cell flags
+    uint32_t n = 0u;                    // records in the queue (wave-uniform)
 
-    const uint32_t tid = threadIdx.x;
-    const uint32_t lane = tid & 63u;
-    uint32_t *pool = pool_all + (tid >> 6) * (kPoolWords * 64);
-    const rsrc_t rs = make_rsrc(a.nodes, a.n_words);
-    // (the same descriptor as four scalar words, for the hand-written loop of the walk: raw buffer, stride 0, size in bytes)
-    typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-    const u32x4 rs_asm = {(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(uintptr_t)a.nodes),
-                          (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)((uintptr_t)a.nodes >> 32)) & 0xFFFFu,
-                          (uint32_t)__builtin_amdgcn_readfirstlane((int)(a.n_words << 2)), 0x00020000u};
-    uint32_t c_refill = 0, c_desc = 0, c_step = 0, c_gen = 0, dbg_desc_iters = 0, dbg_desc_lanes = 0, dbg_desc_rounds = 0, dbg_desc_start = 0;
-    // CNT: the visits of a round are not added to the counters on the spot -- a compare-and-swap is executed at the memory
-    // side (the L2s of the 8 XCDs are not coherent with each other), its answer takes 0.4 - 1.3 us under this kernel's load,
-    // and a round that waits for one answer per level took 8 us instead of 2.  Final counters are min(15, old + visits) in
-    // whatever order the visits arrive, so every wave queues its (word, visits) pairs in LDS and adds them 64 at a time,
-    // all lanes in parallel: one wait per 64 - 192 pairs instead of one per level and round.
-    // What a lane learns only there -- that a word has reached 15 -- goes into a direct-mapped table of word indices shared
-    // by the workgroup (exact: an entry is the index itself); step 3a looks a word up before it queues a visit, so the
-    // hundreds of later visits of a word near the root cost one LDS read each, on whichever lane and ray they happen.
-    uint32_t *cq = pool_all + (BLOCK / 64) * (kPoolWords * 64) + (tid >> 6) * kCountQueue;  // (CNT only: the launch allocates both)
-    uint32_t *sat_tags = pool_all + (BLOCK / 64) * (kPoolWords * 64) + (BLOCK / 64) * kCountQueue;
-    auto sat_slot = [](uint32_t p) -> uint32_t { return (p ^ (p >> 9)) & (uint32_t)(kSatTags - 1); };  // (no multiply: quarter rate)
-    // ... and what the table said about the words of levels 1..K -- which the walk never reads -- is kept per level-K cell (4 bits
-    // each: bit l = the level-l word on the way to this cell is saturated): every ray picked up and every ray that crosses a
-    // level-K boundary would otherwise look those words up one level per loop iteration (half of the loop's iterations), and a
-    // direct-mapped table forgets
-    uint32_t *top_sat = sat_tags + kSatTags;  // TBL / 8 words
-    if (CNT) {
+    __device__ __forceinline__ CountQueue(uint32_t *pools, uint32_t wave)  // (addressed from the ray pools, like the wave's own pool: one multiply-add)
+        : cq(pools + (Lds::queues - Lds::pools) + wave * kCountQueue), sat_tags(pools + (Lds::sat_tags - Lds::pools)), top_sat(sat_tags + (Lds::top_sat - Lds::sat_tags)) {}
+    __device__ __forceinline__ void init(uint32_t tid) {  // all threads of the workgroup
         for (uint32_t i = tid; i < (uint32_t)kSatTags; i += BLOCK) sat_tags[i] = 0xFFFFFFFFu;
-        for (uint32_t i = tid; i < (uint32_t)(TBL / 8); i += BLOCK) top_sat[i] = 0u;
+        for (uint32_t i = tid; i < (uint32_t)(Lds::top / 8); i += BLOCK) top_sat[i] = 0u;
         __syncthreads();
     }
-    uint32_t cq_n = 0u;
+    static __device__ __forceinline__ uint32_t sat_slot(uint32_t p) { return (p ^ (p >> 9)) & (uint32_t)(kSatTags - 1); }  // (no multiply: quarter rate)
+    // has some lane of the workgroup seen word p reach 15?
+    __device__ __forceinline__ bool saturated(uint32_t p) const { return sat_tags[sat_slot(p)] == p; }
+    // the levels (bit l = level l) of the path to level-K cell `cell` whose words are known to be saturated ...
+    __device__ __forceinline__ uint32_t top_known(uint32_t cell) const { return top_sat[cell >> 3] >> ((cell & 7u) * 4u); }
+    // ... and a note that level l is one of them
+    __device__ __forceinline__ void note_top(uint32_t cell, uint32_t l) { atomicOr(&top_sat[cell >> 3], (1u << l) << ((cell & 7u) * 4u)); }
+
     // A flush takes the whole queue, two records per lane.  Four in ten of 64 consecutive records name a word that another
     // of them names too (the same leaf or ancestor visited in consecutive rounds, or by lanes that were not neighbours): as
     // two compare-and-swaps of one wave on one word, the second is bound to fail and costs the wave another round trip.
@@ -402,9 +363,9 @@ __device__ __forceinline__ void trace_stack_body(const TraceArgs &a, uint32_t st
     // finds neither its word nor a free entry within four probes goes alone -- correct, just not merged.  The device-scope
     // loads of both halves travel together, and so do their compare-and-swaps.
     static_assert(kCountQueue == 128, "the flush holds the queue in two registers per lane");
-    auto cq_flush = [&]() {
+    __device__ __forceinline__ void flush(const TraceArgs &a, uint32_t lane) {
         constexpr uint32_t kFree = 0xFFFFFFFFu, kWord = 0x07FFFFFFu;
-        const bool v0 = lane < cq_n, v1 = 64u + lane < cq_n;
+        const bool v0 = lane < n, v1 = 64u + lane < n;
         const uint32_t rec0 = v0 ? cq[lane] : 0u, rec1 = v1 ? cq[64u + lane] : 0u;
         cq[lane] = kFree;
         cq[64u + lane] = kFree;
@@ -458,24 +419,91 @@ __device__ __forceinline__ void trace_stack_body(const TraceArgs &a, uint32_t st
         if (c1 == 16u) c1 = count_add(a.count_nodes, p1, s1, n1);
         if (i0 && c0 == 15u) sat_tags[sat_slot(p0)] = p0;
         if (i1 && c1 == 15u) sat_tags[sat_slot(p1)] = p1;
-        cq_n = 0u;
-    };
+        n = 0u;
+    }
     // all lanes call this (uniform control flow); `mine` = the lane has a visit of word p (value `word`) to report
-    auto cq_push = [&](bool mine, uint32_t p, uint32_t word) {
-        const uint32_t n = visit_groups<true>(a.n_words, p, mine ? word : 15u);
-        const uint64_t m = __ballot(n != 0u);
+    // (before, after: the timeline build's probes around a flush that the push sets off; what `before` returns is handed to `after`)
+    template <class B, class A>
+    __device__ __forceinline__ void push(const TraceArgs &a, uint32_t lane, bool mine, uint32_t p, uint32_t word, B &&before, A &&after) {
+        const uint32_t v = visit_groups<true>(a.n_words, p, mine ? word : 15u);
+        const uint64_t m = __ballot(v != 0u);
         if (!m) return;
-#ifndef SVO_COUNT_FLUSH_AT   // (A/B: flush once the queue holds more than this many records; at most kCountQueue - 64, a push adds up to 64)
-#define SVO_COUNT_FLUSH_AT (kCountQueue - 64)
-#endif
-        if (cq_n > (uint32_t)(SVO_COUNT_FLUSH_AT)) {
-            if (DBGH) dbg_desc_rounds += 1u;  // (CNT: slot 14 = queue flushes, slot 13 = cycles in them)
-            const uint64_t c_f0 = DBGH ? __builtin_amdgcn_s_memtime() : 0ull;
-            cq_flush();
-            if (DBGH && lane == 0u) dbg_desc_lanes += (uint32_t)(__builtin_amdgcn_s_memtime() - c_f0);
+        if (n > (uint32_t)(SVO_COUNT_FLUSH_AT)) {
+            const uint64_t began = before();
+            flush(a, lane);
+            after(began);
         }
-        if (n) cq[cq_n + __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u))] = p | (min(n, 15u) << 27);
-        cq_n += (uint32_t)__popcll(m);
+        if (v) cq[n + __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u))] = p | (min(v, 15u) << 27);
+        n += (uint32_t)__popcll(m);
+    }
+};
+
+// CNT: hit counters live (adaptive mode, shader.wgsl:157-161), see step 3a in the loop and CountQueue above.
+// The body of both trace kernels (they follow it): trace_stack_kernel claims its strips from the lists' counters, REPLAY = false;
+// trace_stack_replay_kernel reads them from the wave's row of a deal table (svo_deal.h, DESIGN.md 4.9), REPLAY = true -- the claim code
+// (the reserved first entry, the atomics, the probe of the 64 counters, entry_of and home) is compiled out, work_counter is not read,
+// and the wave leaves two time stamps for the deal's step.  Everything else is the same text.
+template <int BLOCK, int NS, int K, bool GE, bool DBG, bool CNT, bool SHD, bool REPLAY>
+__device__ __forceinline__ void trace_stack_body(const TraceArgs &a, uint32_t strip_items, uint32_t *work_counter, uint32_t *defer) {
+    static_assert(!REPLAY || (!DBG && !CNT && !SHD), "the replay kernel exists for the plain static frame only");
+    constexpr bool DBGH = DBG && SVO_DBG_LIGHT == 0;  // the timeline build's phase clocks and tallies (the light build keeps the time stamps only)
+    constexpr int D = kPathBits;
+    constexpr int SBASE = K + 2;       // first level kept on the LDS stack
+    constexpr int SMAX = K + 1 + NS;   // last level kept on the LDS stack = deepest level resolved
+    static_assert(SMAX <= D - 1, "stack deeper than the path codes");
+    constexpr int TBL = 1 << (3 * K);
+    using Lds = StackLds<BLOCK, NS, K, CNT>;  // (the layout: one definition for kernel and launch)
+    constexpr int kLutWords = 64;
+    constexpr int LOFF = Lds::lut;
+    constexpr int TOFF = Lds::pools;  // LDS words in front of the ray pools
+    constexpr bool kLut = NS <= 12;
+    constexpr int SOFF = Lds::stacks;
+    static_assert(Lds::total == SOFF + NS * BLOCK, "the ancestor stacks are the last LDS region (see StackLds)");
+    static_assert(D == 23, "2^D + code must be an f32 with unit spacing");
+    constexpr float kScale = (float)(1 << (D - 1));  // 2^22: grid units per unit of the cube
+    constexpr float kInvScale = 1.0f / kScale;
+    constexpr float kMagic = (float)(1 << D);        // 2^23: as_uint(kMagic + U) = 0x4B000000 | U for an integer 0 <= U < 2^23
+    constexpr float kNudge = 0.000002f * kScale;     // |voxel_pos nudge| (shader.wgsl:235) in grid units (exact: a power-of-two multiple)
+    // SHD: direction of every shadow ray, -normalize(sun_dir) (wave-uniform, kept in scalar registers)
+    float shadow_d0 = 0.0f, shadow_d1 = 0.0f, shadow_d2 = 0.0f;
+    float sDr0 = 1.0f, sDr1 = 1.0f, sDr2 = 1.0f, sY0 = 1.0f, sY1 = 1.0f, sY2 = 1.0f;  // what ray_enter and the pick-up make of it
+    float sS0 = 1.0f, sS1 = 1.0f, sS2 = 1.0f;
+    if (SHD) {
+        auto uni = [](float x) { return __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(x))); };
+        float sun[3];
+        sun_direction(a.u, sun);
+        shadow_d0 = uni(-sun[0]); shadow_d1 = uni(-sun[1]); shadow_d2 = uni(-sun[2]);
+        sDr0 = uni((shadow_d0 + ((shadow_d0 == 0.0f) ? 1.0f : 0.0f) * 0.000001f) * kScale);  // octree_ray's bias (ray_enter), then grid units
+        sDr1 = uni((shadow_d1 + ((shadow_d1 == 0.0f) ? 1.0f : 0.0f) * 0.000001f) * kScale);
+        sDr2 = uni((shadow_d2 + ((shadow_d2 == 0.0f) ? 1.0f : 0.0f) * 0.000001f) * kScale);
+        sY0 = uni(1.0f / sDr0); sY1 = uni(1.0f / sDr1); sY2 = uni(1.0f / sDr2);
+        sS0 = uni(copysign_bits(1.0f, sDr0)); sS1 = uni(copysign_bits(1.0f, sDr1)); sS2 = uni(copysign_bits(1.0f, sDr2));
+    }
+    extern __shared__ uint32_t lds[];
+    uint32_t *pool_all = lds + TOFF;  // [BLOCK / 64][kPoolWords][64]
+    // CNT: level-1 / level-2 cell -> child group (kTopAuxEntries words behind the top table): read from global memory, where the
+    // 288 bytes stay in the L1 -- in LDS they cost the sixth workgroup per CU (the allocation granule)
+    const uint32_t *aux = a.top_table + TBL;
+
+    const uint32_t tid = threadIdx.x;
+    const uint32_t lane = tid & 63u;
+    uint32_t *pool = pool_all + (tid >> 6) * (kPoolWords * 64);
+    const rsrc_t rs = make_rsrc(a.nodes, a.n_words);
+    // (the same descriptor as four scalar words, for the hand-written loop of the walk: raw buffer, stride 0, size in bytes)
+    typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+    const u32x4 rs_asm = {(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(uintptr_t)a.nodes),
+                          (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)((uintptr_t)a.nodes >> 32)) & 0xFFFFu,
+                          (uint32_t)__builtin_amdgcn_readfirstlane((int)(a.n_words << 2)), 0x00020000u};
+    uint32_t c_refill = 0, c_desc = 0, c_step = 0, c_gen = 0, dbg_desc_iters = 0, dbg_desc_lanes = 0, dbg_desc_rounds = 0, dbg_desc_start = 0;
+    CountQueue<BLOCK, NS, K> counts(pool_all, tid >> 6);  // (CNT only)
+    if (CNT) counts.init(tid);
+    // around a flush that a push sets off (timeline build, CNT: slot 14 = queue flushes, slot 13 = cycles in them)
+    auto flush_begins = [&]() -> uint64_t {
+        if (DBGH) dbg_desc_rounds += 1u;
+        return DBGH ? __builtin_amdgcn_s_memtime() : 0ull;
+    };
+    auto flush_ends = [&](uint64_t c_f0) {
+        if (DBGH && lane == 0u) dbg_desc_lanes += (uint32_t)(__builtin_amdgcn_s_memtime() - c_f0);
     };
 
     for (uint32_t i = tid; i < (uint32_t)TBL; i += BLOCK) lds[i] = a.top_table[i];
@@ -496,7 +524,7 @@ __device__ __forceinline__ void trace_stack_body(const TraceArgs &a, uint32_t st
     // dealt round-robin over the 8 XCDs, so the waves sharing an L2 work on one screen region and walk it in
     // order -- and moves on to the next region when its own is exhausted (work stealing keeps the tail short;
     // a single counter would serialise at ~88 claims/us).  Static mode: strips dealt round-robin to waves.
-    constexpr uint32_t kShards = 8, kShardStride = (uint32_t)kCounterStride;  // (svo_device.h: 64 KB + 128 B apart)
+    constexpr uint32_t kShardStride = (uint32_t)kCounterStride;  // (svo_device.h: 64 KB + 128 B apart; kShards, kSubs: svo_sched.h)
     // Every list has kSubs claim counters, each handing out every kSubs-th of the list's entries (counter j: entries
     // reserved + j, reserved + j + kSubs, ...: every counter walks the whole list, longest strips first); a wave starts
     // with counter (blockIdx / kShards) % kSubs of its list, takes the list's counters in turn, and moves on to the next
@@ -504,7 +532,6 @@ __device__ __forceinline__ void trace_stack_body(const TraceArgs &a, uint32_t st
     // rays the waves finish their strips in step, 768 claims arrive at one counter together, and the last of them
     // waited 8 us -- half of such a frame was spent waiting for claims (wave_timeline: 90 k of 187 k cycles per wave on
     // config 2).
-    constexpr uint32_t kSubs = 8;
     static_assert(kShards * kSubs == 64, "the stealing probe reads one counter per lane");
     const uint32_t n_strips = (n_items + strip_items - 1) / strip_items;
     // a.order (optional): strip numbers sorted by the cost they had in the previous frame, longest rays first
@@ -520,16 +547,12 @@ __device__ __forceinline__ void trace_stack_body(const TraceArgs &a, uint32_t st
     // ends up in scratch memory, inside the hot loop: `next` == 0xFFFFFFFE says that a claim is in flight, 0xFFFFFFFF that
     // the frame has no more strips for this wave.  The stealing code exists once, in the refill step.)
     // (REPLAY: home is the position in the wave's row of the entry asked for last, pend that entry itself, wave-uniform)
-    uint32_t home = REPLAY ? 0u : (blockIdx.x % kShards) * kSubs + (blockIdx.x / kShards) % kSubs;  // the claim counter (list * kSubs + counter) this wave draws from
+    uint32_t home = REPLAY ? 0u : starting_counter(blockIdx.x);  // the claim counter (list * kSubs + counter) this wave draws from
     uint32_t pend = 0;                // lane 0: what the atomic returned
     uint32_t next, strip_end;
     auto entry_of = [=](uint32_t sh, uint32_t k) -> uint32_t {  // strip behind entry k of list sh (0xFFFFFFFF: past the end)
         if (order) return k < order[sh] ? order[kShards + sh * a.order_cap + k] : 0xFFFFFFFFu;
-        // no schedule yet (the first frame of a layout): runs of 16 consecutive strips dealt round-robin to the 8 lists, so that the
-        // lists are equally long in work whatever part of the screen is expensive (8 contiguous regions left whole lists of sky
-        // idle early and their waves stealing, one probe and one synchronous claim per strip)
-        const uint32_t cand = (((k >> 4) * kShards + sh) << 4) | (k & 15u);
-        return cand < n_strips ? cand : 0xFFFFFFFFu;
+        return dealt_strip(sh, k, n_strips);  // no schedule yet (the first frame of a layout)
     };
     // the wave's row of the deal table: strips in the order it traces them, 0xFFFFFFFF behind the last (read-only for the launch)
     // (the load is all the caller pays for: like a claim's answer, the entry is looked at -- readfirstlane -- only when it is needed)
@@ -542,7 +565,7 @@ __device__ __forceinline__ void trace_stack_body(const TraceArgs &a, uint32_t st
         next = s0 != 0xFFFFFFFFu ? s0 * strip_items : 0xFFFFFFFFu;  // (an empty row: the frame has nothing for this wave)
         strip_end = s0 != 0xFFFFFFFFu ? min(next + strip_items, n_items) : 0xFFFFFFFFu;
     } else {
-        const uint32_t my_rank = (blockIdx.x / kShards) * (uint32_t)(BLOCK / 64) + __builtin_amdgcn_readfirstlane(tid >> 6);  // among the waves that start on my list
+        const uint32_t my_rank = starting_rank(blockIdx.x, __builtin_amdgcn_readfirstlane(tid >> 6), BLOCK / 64);  // among the waves that start on my list
         const uint32_t s0 = __builtin_amdgcn_readfirstlane(entry_of(blockIdx.x % kShards, my_rank));
         if (s0 != 0xFFFFFFFFu) {
             next = s0 * strip_items;
@@ -900,7 +923,7 @@ __device__ __forceinline__ void trace_stack_body(const TraceArgs &a, uint32_t st
         }
     }
 
-    // timeline build, second region of the debug buffer (16 words per wave behind the first 16384 x 16): slot 0 = the moment the wave
+    // timeline build, second region of the debug buffer (SVO_DEBUG_ROW_WORDS words per wave behind the first SVO_DEBUG_WAVES rows): slot 0 = the moment the wave
     // enters its main loop (top table staged, the camera's walk made), slots 1..14 = the moments of its first fourteen ray generations, slot 15 = where it runs
     // list-share feedback (launch_post): when the frame started -- the first workgroup's stamp (plain stores, here and at the end) --
     {
@@ -910,7 +933,7 @@ __device__ __forceinline__ void trace_stack_body(const TraceArgs &a, uint32_t st
         }
     }
     if (DBG) {
-        uint32_t *const ev = fresh_args().debug + 16u * 16384u + 16u * wave_id;
+        uint32_t *const ev = fresh_args().debug + SVO_DEBUG_ROW_WORDS * SVO_DEBUG_WAVES + SVO_DEBUG_ROW_WORDS * wave_id;
         if (lane == 0u) ev[0] = (uint32_t)__builtin_amdgcn_s_memrealtime();
         // slot 15: where the wave runs -- HW_REG_XCC_ID[3:0] << 16 | HW_REG_HW_ID[15:0] (wave, SIMD, pipe, CU, SH, SE)
         if (lane == 0u) ev[15] = (((uint32_t)__builtin_amdgcn_s_getreg((4 - 1) << 11 | 0 << 6 | 20)) << 16) | (uint32_t)__builtin_amdgcn_s_getreg((16 - 1) << 11 | 0 << 6 | 4);
@@ -950,7 +973,7 @@ __device__ __forceinline__ void trace_stack_body(const TraceArgs &a, uint32_t st
                 }
                 uint32_t lst = home / kSubs;
                 // (REPLAY: the answer is the row's next entry, asked for when the last strip became pool rays; nothing to probe or steal)
-                uint32_t s = REPLAY ? pend : entry_of(lst, __builtin_amdgcn_readfirstlane(pend) * kSubs + home % kSubs + ((gridDim.x + kShards - 1u - lst) / kShards) * (uint32_t)(BLOCK / 64));
+                uint32_t s = REPLAY ? pend : entry_of(lst, claimed_entry(__builtin_amdgcn_readfirstlane(pend), home % kSubs, waves_starting_on(lst, gridDim.x, BLOCK / 64)));
                 // The home counter ran out: lane i looks at counter i -- one load for all 64 -- and the wave draws from the first
                 // counter that still has entries, starting behind its own (the other counters of its list, then list by list), and
                 // makes that counter its home: later claims from it are issued ahead of time again (frames whose lists differ
@@ -961,22 +984,15 @@ __device__ __forceinline__ void trace_stack_body(const TraceArgs &a, uint32_t st
                     if (DBG && !DBGH && lane == 0u) dbg_desc_iters += 1u;  // (light timeline build, slot 12: probes of the 64 claim counters)
                     const uint32_t l = lane / kSubs;
                     const uint32_t cv = __hip_atomic_load(work_counter + lane * kShardStride, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    const uint32_t res_l = ((gridDim.x + kShards - 1u - l) / kShards) * (uint32_t)(BLOCK / 64);
-                    uint32_t len_l;
-                    if (order) {
-                        len_l = order[l];
-                    } else {  // (entry_of's deal: runs of 16 strips, run g belongs to list g mod 8; the last run may be short)
-                        const uint32_t runs = (n_strips + 15u) >> 4, mine = runs > l ? (runs - l + kShards - 1u) / kShards : 0u;
-                        len_l = (mine << 4) - ((runs != 0u && (runs - 1u) % kShards == l) ? (runs << 4) - n_strips : 0u);
-                    }
-                    const uint64_t has = __ballot((uint64_t)cv * kSubs + lane % kSubs + res_l < (uint64_t)len_l);
+                    const uint32_t len_l = order ? order[l] : dealt_length(l, n_strips);
+                    const uint64_t has = __ballot(counter_has_entry(cv, lane % kSubs, waves_starting_on(l, gridDim.x, BLOCK / 64), len_l));
                     if (!has) break;
                     const uint64_t rot = home ? ((has >> home) | (has << (64u - home))) : has;
                     home = (home + (uint32_t)__ffsll((unsigned long long)rot) - 1u) & 63u;
                     lst = home / kSubs;
                     uint32_t k = 0u;
                     if (lane == 0) k = atomicAdd(work_counter + home * kShardStride, 1u);
-                    s = entry_of(lst, __builtin_amdgcn_readfirstlane(k) * kSubs + home % kSubs + ((gridDim.x + kShards - 1u - lst) / kShards) * (uint32_t)(BLOCK / 64));
+                    s = entry_of(lst, claimed_entry(__builtin_amdgcn_readfirstlane(k), home % kSubs, waves_starting_on(lst, gridDim.x, BLOCK / 64)));
                 }
                 // the next claim goes to the list's next counter: every wave of a list draws from all of its counters in turn, so
                 // the counters advance together and the list is consumed front to back, as with one counter (waves tied to one
@@ -995,7 +1011,7 @@ __device__ __forceinline__ void trace_stack_body(const TraceArgs &a, uint32_t st
                 if (pool_n == 0u) {
                     if (DBG) dbg_gens += 1;
                     if (DBG && dbg_gens <= 14u) {
-                        uint32_t *const ev = fresh_args().debug + 16u * 16384u + 16u * wave_id + dbg_gens;
+                        uint32_t *const ev = fresh_args().debug + SVO_DEBUG_ROW_WORDS * SVO_DEBUG_WAVES + SVO_DEBUG_ROW_WORDS * wave_id + dbg_gens;
                         if (lane == 0u) ev[0] = (uint32_t)__builtin_amdgcn_s_memrealtime();
                     }
                     const uint64_t c_g0 = DBGH ? __builtin_amdgcn_s_memtime() : 0ull;
@@ -1154,7 +1170,7 @@ __device__ __forceinline__ void trace_stack_body(const TraceArgs &a, uint32_t st
             // + child index from the path codes.  A counter stops at 15, and near the root that happens within the
             // first rounds of a frame, so each lane remembers which words of its current path it has seen saturated
             // (satm: set by the walk, which reads every word from level K+1 down anyway; a restart at level r keeps the
-            // bits of the levels above r; and the workgroup's table of saturated words, see the queue above) and only
+            // bits of the levels above r; and the workgroup's table of saturated words, see CountQueue) and only
             // reports the others.  Nothing is loaded here: the words of levels 1..K, which the walk never reads (the top
             // table stands for them), are reported until the table knows them -- a compare-and-swap that finds a 15 does nothing.
             // Final counters = min(15, old + visits), like the RESTART kernel.
@@ -1172,7 +1188,7 @@ __device__ __forceinline__ void trace_stack_body(const TraceArgs &a, uint32_t st
                 };
                 if (__ballot((todo & kTopLv) != 0u) != 0ull) {  // (rays picked up, rays that crossed a top-level boundary)
                     const uint32_t cellK = cell_k(mu0, mu1, mu2);
-                    const uint32_t known = (todo & kTopLv) ? ((top_sat[cellK >> 3] >> ((cellK & 7u) * 4u)) & todo & kTopLv) : 0u;
+                    const uint32_t known = (todo & kTopLv) ? (counts.top_known(cellK) & todo & kTopLv) : 0u;
                     satm |= known;
                     todo &= ~known;
                 }
@@ -1196,18 +1212,17 @@ __device__ __forceinline__ void trace_stack_body(const TraceArgs &a, uint32_t st
                     uint32_t p = g + ((__builtin_amdgcn_ubfe(mu0, bit, 1u) << 2) | (__builtin_amdgcn_ubfe(mu1, bit, 1u) << 1) |
                                       __builtin_amdgcn_ubfe(mu2, bit, 1u));
                     p = l == 0u ? leaf_off >> 2 : p;
-                    if (mine && sat_tags[sat_slot(p)] == p) {  // some lane of the workgroup has seen it reach 15
+                    if (mine && counts.saturated(p)) {  // some lane of the workgroup has seen it reach 15
                         satm |= (1u << l) & ~1u;
                         mine = false;
                         if (l - 1u < (uint32_t)K) {
                             uint32_t x0 = mu0, x1 = mu1, x2 = mu2;
                             // (the cell's arithmetic stays in this rare branch: the compiler had moved it in front of the loop, eight instructions a round)
                             asm volatile("" : "+v"(x0), "+v"(x1), "+v"(x2));
-                            const uint32_t cellK = cell_k(x0, x1, x2);
-                            atomicOr(&top_sat[cellK >> 3], (1u << l) << ((cellK & 7u) * 4u));
+                            counts.note_top(cell_k(x0, x1, x2), l);
                         }
                     }
-                    cq_push(mine, p, 0u);
+                    counts.push(a, lane, mine, p, 0u, flush_begins, flush_ends);
                 }
             }
             if (DBGH) dbg_desc_start += (uint32_t)(__builtin_amdgcn_s_memtime() - c_c0);  // (CNT: slot 15 = cycles spent counting)
@@ -1285,7 +1300,7 @@ __device__ __forceinline__ void trace_stack_body(const TraceArgs &a, uint32_t st
         }
         if (DBGH) c_step += (uint32_t)(__builtin_amdgcn_s_memtime() - c_mark);
     }
-    if (CNT) cq_flush();
+    if (CNT) counts.flush(a, lane);
     if (DBGH) {  // wave totals of the per-lane tallies
 #pragma unroll
         for (int o = 32; o > 0; o >>= 1) {
@@ -1312,7 +1327,7 @@ __device__ __forceinline__ void trace_stack_body(const TraceArgs &a, uint32_t st
     }
     if (DBG && lane == 0) {
         uint64_t t_end = __builtin_amdgcn_s_memrealtime();
-        uint32_t *d = a.debug + 16u * wave_id;
+        uint32_t *d = a.debug + SVO_DEBUG_ROW_WORDS * wave_id;
         d[8] = c_refill;         // shader cycles in the refill section (ray generation included)
         d[9] = c_desc;           // ... in the descent loop
         d[10] = c_step;          // ... in the step section
@@ -1731,6 +1746,8 @@ static hipError_t launch_stack(const TraceArgs &args, const LaunchInfo &li, hipS
     }
     uint32_t blocks = (uint32_t)li.num_cus * (uint32_t)blocks_per_cu;
     if (li.grid_blocks > 0) blocks = (uint32_t)li.grid_blocks;
+    // (the timeline's buffer has a row for SVO_DEBUG_WAVES waves: a grid override beyond that is cut back while the buffer is set)
+    if (args.debug && blocks > SVO_DEBUG_WAVES / (kStackBlock / 64)) blocks = SVO_DEBUG_WAVES / (kStackBlock / 64);
     uint32_t n_strips = (args.work.n_items + strip_items - 1) / strip_items;
     uint32_t need = (n_strips + (kStackBlock / 64) - 1) / (kStackBlock / 64);
     if (blocks > need) blocks = need;

@@ -1,6 +1,7 @@
 // svo_sched.h -- the strip schedule's per-frame policy: which lists a STACK frame is traced with, and
 // what the post pass measures and rebuilds after it.  Plain C++ (no HIP): the host glue in svo_abi.cpp (trace_launch) measures the
-// facts and runs the launches, tests/test_schedule_plan.py replays frame sequences through these two functions.
+// facts and runs the launches, tests/test_schedule_plan.py replays frame sequences through these two functions.  Also the arithmetic
+// of the trace kernel's strip claims (which entry of which list a wave gets), stated once for the kernel and for a host test.
 #pragma once
 #include <cmath>
 #include <cstdint>
@@ -116,6 +117,51 @@ SVO_SCHED_HD inline void balance_share_step(uint32_t *bal, const float T[8], uin
     bal[kBalanceUpdates] += 1u;
 }
 
+// ---- strip claims: which entry of which list a wave of the trace kernel gets (svo_kernels.hip: trace_stack_body and its entry_of; tests/test_claims_host.py
+// holds these functions to each other) ----
+// A frame's strips stand in kShards lists, one per XCD.  The first entries of a list are RESERVED, one per wave that starts on
+// it; behind them each of the list's kSubs claim counters hands out every kSubs-th entry.
+// (inlined before anything is simplified: the trace kernel's claim code is then compiled as if it were written out in place)
+#define SVO_SCHED_INLINE inline __attribute__((always_inline))
+constexpr uint32_t kShards = 8, kSubs = 8;
+constexpr uint32_t kDealRun = 16;            // the no-schedule deal: consecutive strips that go to one list
+constexpr uint32_t kNoStrip = 0xFFFFFFFFu;   // "past the end of the list"
+
+// Waves that start on list l in a grid of `blocks` workgroups of `waves_per_block` waves (workgroup b starts on list b % kShards):
+// the list's reserved entries.
+SVO_SCHED_HD SVO_SCHED_INLINE uint32_t waves_starting_on(uint32_t l, uint32_t blocks, uint32_t waves_per_block) {
+    return ((blocks + kShards - 1u - l) / kShards) * waves_per_block;
+}
+// Where a wave starts: workgroup b on list b % kShards, its wave w with the reserved entry of its rank among the list's waves, and
+// with the list's counter (b / kShards) % kSubs -- as one number, list * kSubs + counter, the way the kernel keeps it.
+SVO_SCHED_HD SVO_SCHED_INLINE uint32_t starting_rank(uint32_t b, uint32_t w, uint32_t waves_per_block) { return (b / kShards) * waves_per_block + w; }
+SVO_SCHED_HD SVO_SCHED_INLINE uint32_t starting_counter(uint32_t b) { return (b % kShards) * kSubs + (b / kShards) % kSubs; }
+// The list entry that the k-th answer of a list's counter j stands for.
+SVO_SCHED_HD SVO_SCHED_INLINE uint32_t claimed_entry(uint32_t k, uint32_t j, uint32_t reserved) { return k * kSubs + j + reserved; }
+// The stealing probe's question: has counter j of a list of `len` entries, read as cv, an entry left to hand out?
+SVO_SCHED_HD SVO_SCHED_INLINE bool counter_has_entry(uint32_t cv, uint32_t j, uint32_t reserved, uint32_t len) {
+    return (uint64_t)cv * kSubs + j + reserved < (uint64_t)len;
+}
+// No schedule yet (the first frame of a layout): runs of kDealRun consecutive strips dealt round-robin to the lists, so that the
+// lists are equally long in work whatever part of the screen is expensive (8 contiguous regions left whole lists of sky idle
+// early and their waves stealing, one probe and one synchronous claim per strip).
+// The strip behind entry k of list l (kNoStrip: past the end) ...
+SVO_SCHED_HD SVO_SCHED_INLINE uint32_t dealt_strip(uint32_t l, uint32_t k, uint32_t n_strips) {
+    const uint32_t cand = ((k / kDealRun) * kShards + l) * kDealRun + k % kDealRun;
+    return cand < n_strips ? cand : kNoStrip;
+}
+// ... where a strip stands ...
+SVO_SCHED_HD SVO_SCHED_INLINE void dealt_place(uint32_t strip, uint32_t &l, uint32_t &k) {
+    const uint32_t run = strip / kDealRun;
+    l = run % kShards;
+    k = (run / kShards) * kDealRun + strip % kDealRun;
+}
+// ... and how long list l is: run g belongs to list g mod kShards, and the last run may be short.
+SVO_SCHED_HD SVO_SCHED_INLINE uint32_t dealt_length(uint32_t l, uint32_t n_strips) {
+    const uint32_t runs = (n_strips + kDealRun - 1u) / kDealRun, mine = runs > l ? (runs - l + kShards - 1u) / kShards : 0u;
+    return mine * kDealRun - ((runs != 0u && (runs - 1u) % kShards == l) ? runs * kDealRun - n_strips : 0u);
+}
+
 inline bool stored_lists(const SchedState &s) { return s.valid && !s.order_filtered; }
 
 inline TracePlan plan_before_trace(SchedState &s, const FrameFacts &f) {
@@ -162,5 +208,7 @@ inline PostPlan plan_after_trace(SchedState &s, const FrameFacts &f) {
     }
     return p;
 }
+
+#undef SVO_SCHED_INLINE
 
 }  // namespace svo

@@ -8,6 +8,9 @@ from ._lib import SvoError, lib
 
 OPT_VARIANT, OPT_TIMING, OPT_GRID_BLOCKS, OPT_REFILL_MIN, OPT_STRIP_ITEMS, OPT_DYNAMIC_STRIPS, OPT_PRIO_STEPS, OPT_DEBUG_BUFFER, OPT_SCHEDULE, OPT_TREE_DEPTH, OPT_BLOCK_SHAPE, OPT_SCAN_CLEARS_COUNTERS, OPT_FUSED_SHADOWS, OPT_PAIR_TABLE, OPT_CULL, OPT_CAMERA_SHORTCUT, OPT_SCHEDULE_MOTION, OPT_STATIC_DEAL = range(18)
 VARIANT_RESTART, VARIANT_STACK = 0, 1
+# OPT_DEBUG_BUFFER (include/svo_hip.h: SVO_DEBUG_WAVES, SVO_DEBUG_ROW_WORDS, SVO_DEBUG_BUFFER_WORDS): two regions of DEBUG_WAVES rows
+DEBUG_WAVES, DEBUG_ROW_WORDS = 16384, 16
+DEBUG_BUFFER_WORDS = 2 * DEBUG_WAVES * DEBUG_ROW_WORDS
 
 
 class Gpu:

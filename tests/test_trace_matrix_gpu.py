@@ -10,7 +10,10 @@ layout and its own copy of the walk.
 The frames are the lattice cameras of tests/trace_matrix_scenes.py: every ray starts on a tie, so > and >= part ways in records
 and in counter words (tests/test_trace_matrix_host.py holds the scenes to that).  Which kernel a cell launches follows from
 launch_stack's rules; that the deep instantiation was needed is shown by the same frame being refused under a declared depth
-of 16.  The RESTART kernel runs every cell's flags too: a mismatch it does not share is the stack kernel's."""
+of 16.  The RESTART kernel runs every cell's flags too: a mismatch it does not share is the stack kernel's.
+
+The eight timeline instantiations (DBG, with SVO_OPT_DEBUG_BUFFER set: GE x NS x CNT, launch_stack has none with fused shadows)
+run the same frames: the same records and counter words, and a timeline that is consistent with the frame."""
 import types
 
 import numpy as np
@@ -69,7 +72,7 @@ def wanted(O):
     return want
 
 
-def two_frames(pkg, gpu, w, shade):
+def two_frames(pkg, gpu, w, shade, before_frame=None, after_frame=None):
     """Two frames of w's view into poisoned buffers, the second from the first one's schedule and on its counters.
     Returns per frame (records, image or None, node words)."""
     W, H = S.SIZE
@@ -80,8 +83,12 @@ def two_frames(pkg, gpu, w, shade):
         buf = render.alloc_hits(W * H)
         buf.fill_(-1)  # 0xFF bytes: a ray nobody traced keeps them
         rgba = render.alloc_rgba(W * H).fill_(-1) if shade else None
+        if before_frame:
+            before_frame()
         render.render(hits=buf, rgba=rgba)
         gpu.sync()
+        if after_frame:
+            after_frame(frame)
         img = rgba.cpu().numpy().view(np.uint8).reshape(H, W, 4) if shade else None
         out.append((pkg.render.hits_to_numpy(buf), img, render.read_nodes(w.words.size)))
     return out
@@ -145,6 +152,91 @@ def test_cell(pkg, mgpu, O, wanted, ge, depth, cnt, shd):
         mgpu.set_option(G.OPT_VARIANT, G.VARIANT_STACK)
         mgpu.set_option(G.OPT_FUSED_SHADOWS, 2)  # the default (automatic)
         mgpu.set_option(G.OPT_TREE_DEPTH, 16)
+
+
+POISON = 0xAAAAAAAA
+
+
+def check_timeline(dbg, G, what):
+    """the debug buffer after one frame of S.SIZE: rows of waves that did not run keep the poison, every other wave's stamps are
+    in order (10 ns ticks, compared as wrapped 32-bit differences), and the waves generated the frame's strips between them"""
+    d = dbg.reshape(2, G.DEBUG_WAVES, G.DEBUG_ROW_WORDS)
+    ran = (d[0] != POISON).any(axis=1)
+    n = int(ran.sum())
+    assert n >= 4 and n % 4 == 0 and ran[:n].all(), f"{what}: the rows written are not those of a grid's waves: {np.flatnonzero(ran)[:8]} ... ({n})"
+    assert (d[:, n:] == POISON).all(), f"{what}: a row beyond the grid's {n} waves was written"
+    row, ev = d[0, :n], d[1, :n]
+    assert (row != POISON).all(), f"{what}: a wave left a slot of its row unwritten"
+    start, dry, end, enter = row[:, 0], row[:, 1], row[:, 2], ev[:, 0]
+
+    def ordered(a, b):  # a <= b on the wrapping clock
+        return (b - a).astype(np.uint32) < 0x80000000
+    assert ordered(start, enter).all() and ordered(enter, end).all(), f"{what}: start <= loop entry <= end"
+    # (a wave that learned it was dry stored that stamp with bit 0 set: one tick late at most)
+    assert ordered(start, dry).all() and ordered(dry & ~np.uint32(1), end).all(), f"{what}: start <= dry <= end"
+    gens = row[:, 7]
+    print(f"{what}: {n} waves, {int(gens.sum())} generations, rounds {int(row[:, 3].sum())}, slots 12..15 summed {[int(row[:, k].astype(np.uint64).sum()) for k in (12, 13, 14, 15)]}")
+    W, H = S.SIZE
+    assert W * H % 64 == 0
+    assert int(gens.sum()) == W * H // 64, f"{what}: {int(gens.sum())} generations of 64 items for {W * H // 64} strips"
+    # the first fourteen generations of a wave left their stamps, the others of the fourteen slots keep the poison
+    for k in range(1, 15):
+        assert ((ev[:, k] != POISON) == (gens >= k)).all(), f"{what}: generation stamp {k}"
+
+
+@pytest.mark.parametrize("cnt", [0, 1], ids=["static", "cnt"])
+@pytest.mark.parametrize("depth", [16, 17], ids=["ns12_d16", "ns18_d17"])
+@pytest.mark.parametrize("ge", [0, 1], ids=["gt", "ge"])
+def test_timeline_cell(pkg, mgpu, O, wanted, ge, depth, cnt):
+    """trace_stack_kernel<.., DBG = true, CNT, SHD = false>: the plain cell's records and counter words, and its timeline"""
+    import torch
+    G = pkg.gpu
+    w = wanted(depth, S.flags_of(O, ge, cnt, 0))
+    what = f"timeline GE {ge} depth {depth} CNT {cnt}"
+    dbg = torch.empty(G.DEBUG_BUFFER_WORDS, dtype=torch.int32, device="cuda")
+    seen = []
+    try:
+        mgpu.set_option(G.OPT_TREE_DEPTH, depth)
+        mgpu.set_option(G.OPT_DEBUG_BUFFER, dbg.data_ptr())
+        frames = two_frames(pkg, mgpu, w, shade=False, before_frame=lambda: dbg.fill_(POISON - (1 << 32)),
+                            after_frame=lambda k: seen.append(dbg.cpu().numpy().view(np.uint32).copy()))
+        check_against_oracle(frames, w, what)
+        for k, d in enumerate(seen):
+            check_timeline(d, G, f"{what}, frame {k}")
+    finally:
+        mgpu.set_option(G.OPT_DEBUG_BUFFER, 0)
+        mgpu.sync()
+        mgpu.set_option(G.OPT_TREE_DEPTH, 16)
+
+
+def test_timeline_grid_override_is_cut_back_to_the_buffers_rows(pkg, mgpu, O):
+    """SVO_OPT_GRID_BLOCKS beyond DEBUG_WAVES / 4 workgroups while the debug buffer is set: the launch has DEBUG_WAVES waves, every
+    row of both regions is theirs, and the words behind the buffer (room for the waves the override asked for) keep the poison"""
+    import torch
+    G = pkg.gpu
+    size = (1024, 1024)  # 16384 strips of 64 pixels: work for 4096 workgroups of four waves, and more would be launched
+    asked = G.DEBUG_WAVES // 4 + 1000
+    sc = S.scene(16)
+    u = sc.uniforms(O, O.F_PAUSE_ADAPTIVE, size=size)
+    tail = 2 * 4 * 1000 * G.DEBUG_ROW_WORDS
+    dbg = torch.empty(G.DEBUG_BUFFER_WORDS + tail, dtype=torch.int32, device="cuda").fill_(POISON - (1 << 32))
+    try:
+        mgpu.set_option(G.OPT_GRID_BLOCKS, asked)
+        mgpu.set_option(G.OPT_DEBUG_BUFFER, dbg.data_ptr())
+        render = pkg.Render(mgpu, size, sc.words, capacity=max(sc.words.size, 1024))
+        set_uniforms_from_oracle(render, u)
+        render.render()
+        mgpu.sync()
+    finally:
+        mgpu.set_option(G.OPT_DEBUG_BUFFER, 0)
+        mgpu.set_option(G.OPT_GRID_BLOCKS, 0)
+        mgpu.sync()
+    d = dbg.cpu().numpy().view(np.uint32)
+    assert (d[G.DEBUG_BUFFER_WORDS:] == POISON).all(), "words behind the buffer were written"
+    rows = d[:G.DEBUG_BUFFER_WORDS].reshape(2, G.DEBUG_WAVES, G.DEBUG_ROW_WORDS)
+    assert (rows[0] != POISON).all(), "a wave of the cut-back grid left no row"
+    assert (rows[1, :, 0] != POISON).all() and (rows[1, :, 15] != POISON).all()
+    assert int(rows[0, :, 7].sum()) == size[0] * size[1] // 64
 
 
 @pytest.mark.parametrize("depth", [17, 21])

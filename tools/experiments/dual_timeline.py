@@ -44,7 +44,7 @@ def main():
     for o in a.opt:
         k, v = o.split("=")
         gpu.set_option(getattr(pkg.gpu, "OPT_" + k), int(v))
-    dbg = torch.zeros((16384, 16), dtype=torch.int32, device="cuda")
+    dbg = torch.zeros((pkg.gpu.DEBUG_BUFFER_WORDS // pkg.gpu.DEBUG_ROW_WORDS, pkg.gpu.DEBUG_ROW_WORDS), dtype=torch.int32, device="cuda")  # (the kernel writes both regions)
     hits = render.alloc_hits(W * H)
     gpu.set_option(pkg.gpu.OPT_TIMING, 8)
     for _ in range(4):
@@ -57,7 +57,7 @@ def main():
     gpu.sync()
     gpu.set_option(pkg.gpu.OPT_DEBUG_BUFFER, 0)
     h = pkg.render.hits_to_numpy(hits)
-    d = dbg.cpu().numpy().view(np.uint32)
+    d = dbg.cpu().numpy().view(np.uint32)[:pkg.gpu.DEBUG_WAVES]  # (the first region: one row per wave)
     d = d[d[:, 2] != 0].astype(np.int64)
     t0 = d[:, 0].min()
     start, dry, end = (d[:, 0] - t0) * 0.01, (d[:, 1] - t0) * 0.01, (d[:, 2] - t0) * 0.01  # us

@@ -68,7 +68,8 @@ def main():
     for o in a.opt:
         k, v = o.split("=")
         gpu.set_option(getattr(pkg.gpu, "OPT_" + k), int(v))
-    dbg = torch.zeros((2 * 16384, 16), dtype=torch.int32, device="cuda")  # second half: per-wave event stamps (round 5)
+    NW, RW = pkg.gpu.DEBUG_WAVES, pkg.gpu.DEBUG_ROW_WORDS
+    dbg = torch.zeros((pkg.gpu.DEBUG_BUFFER_WORDS // RW, RW), dtype=torch.int32, device="cuda")  # second half: per-wave event stamps (round 5)
     hits = render.alloc_hits(W * H)
     gpu.set_option(pkg.gpu.OPT_TIMING, 8)
     for _ in range(a.frames or (8 if a.carry else 24)):
@@ -91,9 +92,9 @@ def main():
     steps_mean = float((h["info"] & 0xFF).mean())
     hit_frac = float(((h["info"] >> 16) & 1).mean())
     d_all = dbg.cpu().numpy().view(np.uint32)
-    live = d_all[:16384, 2] != 0
-    ev = d_all[16384:][live].astype(np.int64)
-    d = d_all[:16384][live].astype(np.int64)
+    live = d_all[:NW, 2] != 0
+    ev = d_all[NW:][live].astype(np.int64)
+    d = d_all[:NW][live].astype(np.int64)
     t0 = d[:, 0].min()
     if a.raw:
         np.savez_compressed(a.raw, d=d, ev=ev, wave=np.nonzero(live)[0])
