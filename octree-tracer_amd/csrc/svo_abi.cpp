@@ -141,6 +141,18 @@ struct TraceOpts {
     svo_hit *shadow_out = nullptr;  // STACK: trace the shadow ray of every hit inside this launch, records here
 };
 
+// What the choice of the trace kernel goes by (svo_sched.h: kernel_kind, fuse_allowed, launch_choice).
+svo::TraceFacts trace_facts(const svo_ctx *ctx) {
+    svo::TraceFacts f;
+    f.restart_variant = ctx->variant == SVO_VARIANT_RESTART;
+    f.tree_depth = ctx->tree_depth;
+    f.pause_adaptive = (ctx->uniforms.flags & SVO_F_PAUSE_ADAPTIVE) != 0;
+    f.show_hits = (ctx->uniforms.flags & SVO_F_SHOW_HITS) != 0;
+    f.misc_bool = (ctx->uniforms.flags & SVO_F_MISC_BOOL) != 0;
+    f.fused_shadows = ctx->fused_shadows != 0;
+    return f;
+}
+
 // The arguments every launch over the context's tree starts from: nodes, uniforms, work layout and records.
 svo::TraceArgs trace_args(const svo_ctx *ctx, const svo::WorkDesc &work, svo_hit *hits) {
     svo::TraceArgs a{};
@@ -199,20 +211,18 @@ int schedule_before(svo_ctx *ctx, svo_ctx::Sched &sc, const svo::FrameFacts &f, 
 
 // A resting view's static deal, before the trace (svo_deal.h: deal_before_trace): the frame's facts, the buffers and the seed when
 // the plan asks for one, and the table in the launch arguments when the replay kernel traces this frame.  Called with the launch
-// as it will be made, after schedule_before.
-int deal_before(svo_ctx *ctx, svo_ctx::Sched &sc, const svo::FrameFacts &ff, svo::TraceArgs &a, const svo::LaunchInfo &li, int sched_slot,
+// as it is planned, after schedule_before; the replay kernel takes over the claiming kernel's grid.
+int deal_before(svo_ctx *ctx, svo_ctx::Sched &sc, const svo::FrameFacts &ff, svo::TraceArgs &a, svo::TraceLaunch &launch, int sched_slot,
                 svo::DealPlan &plan) {
     svo_ctx::Sched::DealBuffers &db = sc.deal;
     svo::DealFacts f;
     f.enabled = ctx->static_deal;
-    f.plain_static = sched_slot == 0 && a.work.mode != 2 && a.hits && !a.skip && !a.count_nodes && !a.shadow_hits && !a.debug && !li.deep_stack;
+    f.plain_static = sched_slot == 0 && a.work.mode != 2 && a.hits && !a.skip && svo::replay_eligible(launch.choice);
     f.stored_lists = ff.schedule && !ff.filtered && a.order != nullptr && a.balance != nullptr;
     f.at_rest = sc.built_nodes_version == ctx->store->version && memcmp(&sc.built_uniforms, &ctx->uniforms, sizeof(svo_uniforms)) == 0;
     f.balance_frames = sc.state.balance_frames;
     if (f.enabled && f.plain_static && f.stored_lists && f.at_rest) {
-        svo::LaunchInfo ask = li;
-        ask.blocks_out = &f.grid_blocks;
-        HIP_TRY(ctx, svo::launch_trace(a, ask, ctx->stream));
+        f.grid_blocks = launch.blocks;
         f.row_cap = svo::deal_row_cap(a.order_cap, f.grid_blocks);
     }
     if (db.seen_pending && hipEventQuery(db.seen_ev[0]) == hipSuccess) {  // (never waited for: not there yet = not seen yet)
@@ -245,6 +255,7 @@ int deal_before(svo_ctx *ctx, svo_ctx::Sched &sc, const svo::FrameFacts &ff, svo
         HIP_TRY(ctx, svo::launch_deal_seed(db.view(a.order_cap, ctx->deal_pairs_div), sc.order, claimed_before ? sc.balance.get() : nullptr, ctx->stream));
     }
     if (plan.replay) {
+        launch.choice.replay = true;
         a.deal_table = db.table;
         a.deal_row_cap = db.state.row_cap;
         a.deal_stamps = db.stamps;
@@ -290,18 +301,22 @@ int schedule_after(svo_ctx *ctx, svo_ctx::Sched &sc, svo::FrameFacts &f, const s
 int trace_launch(svo_ctx *ctx, const svo::WorkDesc &work, const float *rays, svo_hit *hits, const TraceOpts &opt) {
     int rc = bind(ctx);
     if (rc) return rc;
-    // the kernel that runs: STACK resolves the levels its integer path codes cover (SVO_OPT_TREE_DEPTH says how deep the
-    // caller's tree may be); deeper trees, and the debug view that reads counter bits, take the general RESTART kernel
-    const bool want_stack = ctx->variant != SVO_VARIANT_RESTART && ctx->tree_depth <= (uint32_t)svo::stack_max_depth(true);
-    if (want_stack) {
+    // the kernel that runs (svo_sched.h)
+    const svo::TraceFacts facts = trace_facts(ctx);
+    svo::LaunchFacts lf;
+    lf.mode = work.mode;
+    lf.count_rays = opt.count_rays;
+    lf.fused = opt.shadow_out != nullptr;
+    lf.debug_buffer = ctx->debug_buf != nullptr;
+    const svo::TraceChoice choice = svo::launch_choice(facts, lf);
+    const bool stack = choice.stack;
+    if (svo::stack_wanted(facts)) {
         rc = ensure_top_table(ctx);
         if (rc) return rc;
     } else {
         rc = order_after_last_write(ctx);
         if (rc) return rc;
     }
-    const bool debug_hits = (ctx->uniforms.flags & SVO_F_PAUSE_ADAPTIVE) && (ctx->uniforms.flags & SVO_F_SHOW_HITS);
-    const bool stack = want_stack && !debug_hits;
     svo::WorkDesc wd = work;
     auto magic = [](uint32_t d) -> uint32_t { return d <= 1u ? 0u : (uint32_t)(0x100000000ull / d) + 1u; };
     wd.magic_bpr = magic(wd.bpr);
@@ -316,10 +331,8 @@ int trace_launch(svo_ctx *ctx, const svo::WorkDesc &work, const float *rays, svo
     a.cam_shortcut = ctx->cam_shortcut ? 1u : 0u;
     a.debug = ctx->debug_buf;
     a.skip = opt.skip;
-    // shader.wgsl:159: counters are live unless pause_adaptive; rays handed in by the caller (svo_trace_rays) never count
-    const bool counting = (work.mode != 2 || opt.count_rays) && !(ctx->uniforms.flags & SVO_F_PAUSE_ADAPTIVE);
-    a.count_nodes = counting ? ctx->nodes : nullptr;
-    a.shadow_hits = stack ? opt.shadow_out : nullptr;
+    a.count_nodes = choice.cnt ? ctx->nodes : nullptr;
+    a.shadow_hits = choice.shd ? opt.shadow_out : nullptr;
 
     const uint32_t n_strips = (wd.n_items + 63u) / 64u;
     svo_ctx::Sched &sc = ctx->sched[opt.sched_slot & 1];
@@ -338,11 +351,9 @@ int trace_launch(svo_ctx *ctx, const svo::WorkDesc &work, const float *rays, svo
     }
 
     svo::LaunchInfo li{};
-    li.variant = stack ? SVO_VARIANT_STACK : SVO_VARIANT_RESTART;
     li.grid_blocks = ctx->grid_blocks;
     li.num_cus = ctx->num_cus;
     li.strip_items = ctx->strip_items;
-    li.deep_stack = ctx->tree_depth > (uint32_t)svo::stack_max_depth(false);
     li.occupancy = ctx->occupancy;
     if (stack && ctx->defer_items < wd.n_items) {
         HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
@@ -361,15 +372,17 @@ int trace_launch(svo_ctx *ctx, const svo::WorkDesc &work, const float *rays, svo
         li.defer = lists + (ctx->frame_parity ? stride : 0);
         li.next_defer_count = lists + (ctx->frame_parity ? 0 : stride);
     }
+    svo::TraceLaunch launch;
+    HIP_TRY(ctx, svo::plan_trace(a, li, choice, launch));
     svo::DealPlan deal;
     if (stack) {
-        rc = deal_before(ctx, sc, f, a, li, opt.sched_slot, deal);
+        rc = deal_before(ctx, sc, f, a, launch, opt.sched_slot, deal);
         if (rc) return rc;
     }
     const size_t slot = ctx->ev_slots ? (ctx->ev_count % ctx->ev_slots) : 0;
     const bool timed = ctx->ev_slots && opt.sched_slot == 0;  // the timing ring records the primary trace launches
     if (timed) HIP_TRY(ctx, hipEventRecord(ctx->ev[slot][0], ctx->stream));
-    HIP_TRY(ctx, svo::launch_trace(a, li, ctx->stream));
+    HIP_TRY(ctx, svo::launch_trace(a, li, launch, ctx->stream));
     if (timed) {
         HIP_TRY(ctx, hipEventRecord(ctx->ev[slot][1], ctx->stream));
         ctx->ev_count++;
@@ -388,8 +401,7 @@ int trace_launch(svo_ctx *ctx, const svo::WorkDesc &work, const float *rays, svo
 // of the depth-16 terrain was 5 % slower fused and the automatic mode fused only deep trees, 4K frames and counting frames;
 // since then: 1080p 0.646 -> 0.581 ms, 4K 2.04 -> 1.78 ms, depth-20 fractal -24 %.)
 bool fuse_shadow_rays(const svo_ctx *ctx) {
-    const bool want = ctx->fused_shadows != 0;
-    if (!want || ctx->variant == SVO_VARIANT_RESTART || ctx->tree_depth > (uint32_t)svo::stack_max_depth(true)) return false;
+    if (!svo::fuse_allowed(trace_facts(ctx))) return false;
     const float *sd = ctx->uniforms.sun_dir;
     const float sl = sqrtf((sd[0] * sd[0] + sd[1] * sd[1]) + sd[2] * sd[2]);
     for (int k = 0; k < 3; k++) {
@@ -471,8 +483,7 @@ int trace_secondary(svo_ctx *ctx, const svo::WorkDesc &work, uint32_t n_secondar
     rc = svo_grow(ctx, n * n_secondary * 6, &ctx->shade_rays);
     if (rc) return rc;
     // ray 0, the shadow ray, can run inside the primary launch (its records go straight to the first set)
-    const bool debug_view = (ctx->uniforms.flags & SVO_F_PAUSE_ADAPTIVE) && (ctx->uniforms.flags & SVO_F_SHOW_HITS);
-    const bool fused = !debug_view && fuse_shadow_rays(ctx);
+    const bool fused = fuse_shadow_rays(ctx);
     const uint32_t k_first = fused ? 1u : 0u;
     TraceOpts popt;
     popt.aux_t = ctx->shade_aux;

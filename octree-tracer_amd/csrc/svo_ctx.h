@@ -10,6 +10,9 @@
 // directory).
 // svo_scan.h (the tiled count, scan and emit with their launches), svo_group.h, svo_mip.h and svo_morton.h hold the device
 // pieces, svo_rules.h the walks and rules that svo_host.cpp and svo_adapt.hip both run.
+// What a frame launches is decided in plain C++ beside the context, not in it: svo_sched.h (the schedule's plans, the trace
+// kernel and its grid) and svo_deal.h (the static deal).  The context keeps what those decisions go by between frames: the
+// options, the schedule slots, and per STACK instantiation the resident workgroups per CU that the runtime answered.
 // Internal: not part of the boundary.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -186,7 +189,7 @@ struct svo_ctx {
     // options
     int variant = SVO_VARIANT_STACK;
     int grid_blocks = 0;
-    int occupancy[16] = {};  // resident workgroups per CU of each STACK instantiation on this device (0: not asked yet)
+    int occupancy[svo::kTraceSlots] = {};  // resident workgroups per CU of each STACK instantiation on this device, by svo::trace_slot (0: not asked yet)
     uint32_t refill_min = 32;  // (round 5: 16 until the schedule's locality work; profiles/r05_refill_sweep.log)
     bool scan_clears = false;
     int fused_shadows = 2;  // 0: off, 1: on, 2: automatic (see fuse_shadow_rays)

@@ -1,5 +1,7 @@
 // svo_device.h -- internal launch interface between the C ABI (svo_abi.cpp) and the gfx950
 // kernels (svo_kernels.hip).  Not part of the public boundary (include/svo_hip.h).
+// A trace is planned, then launched: svo_sched.h says which kernel a frame gets (TraceChoice) and how its grid is worked out,
+// plan_trace turns a choice into a TraceLaunch for this device, launch_trace launches it.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -11,7 +13,6 @@ namespace svo {
 
 constexpr uint32_t kVoxelOffset = 134217728u;  // octree.rs:5
 constexpr uint32_t kMaxDescent = 31;           // descent guard (see oracle/svo_oracle.c)
-constexpr int kTopLevels = 3;                  // K: octree levels folded into the LDS top table
 constexpr int kTopEntries = 1 << (3 * kTopLevels);
 constexpr int kTopAuxEntries = 8 + 64;  // level-1 and level-2 cells -> child group of the next level (kTopLevels = 3)
 constexpr int kPathBits = 23;                  // D: path-code bits per axis (grid units: 2^(D-1) per unit of the reference's cube, so that
@@ -75,23 +76,29 @@ struct TraceArgs {
     uint32_t *deal_stamps;      // per wave: when it began its last strip, when it ended (10 ns ticks)
 };
 
+static_assert(kTimelineWaves == SVO_DEBUG_WAVES, "svo_sched.h caps the grid by the timeline buffer's rows");
+
 struct LaunchInfo {
-    int variant;
     int grid_blocks;         // 0 = auto
     int num_cus;
-    int *occupancy;          // STACK: the context's cache of resident workgroups per CU, one slot per instantiation
-    bool deep_stack;         // STACK: 19-level ancestor stack (trees deeper than 16 levels)
+    int *occupancy;          // STACK: the context's cache of resident workgroups per CU, kTraceSlots of them (trace_slot)
     uint32_t strip_items;    // STACK: pixel slots a wave claims at a time (multiple of 64)
     uint32_t *counters;      // STACK: kCounterWords claim-counter words, zero when a frame starts
     uint32_t *defer;         // STACK: this frame's deferred list: count, then one slot per item handed to RESTART
     uint32_t *next_defer_count;  // STACK: count word of the other list (lists alternate between frames)
-    uint32_t *blocks_out;    // STACK, optional (host): launch nothing, only say how many workgroups this frame's trace kernel gets
+};
+// A trace launch as it will be made.  STACK: the slot of its kernel (trace_slot), the dynamic LDS of a workgroup and the pixel
+// slots a wave claims at a time; RESTART: the workgroups alone.
+struct TraceLaunch {
+    TraceChoice choice;
+    uint32_t slot, blocks, lds_bytes, strip_items;
 };
 
 hipError_t launch_build_top_table(const uint32_t *nodes, uint32_t n_words, uint32_t *top_table,
                                   hipStream_t stream);
-hipError_t launch_trace(const TraceArgs &args, const LaunchInfo &li, hipStream_t stream);
-int stack_max_depth(bool deep);
+// plan_trace asks the runtime for the kernel's resident workgroups per CU the first time a context launches it, and launches nothing
+hipError_t plan_trace(const TraceArgs &args, const LaunchInfo &li, const TraceChoice &choice, TraceLaunch &launch);
+hipError_t launch_trace(const TraceArgs &args, const LaunchInfo &li, const TraceLaunch &launch, hipStream_t stream);
 // after a STACK trace: deferred rays, per-strip costs (cost != nullptr) and the next schedule; re-arms the counters
 constexpr uint32_t kMaxScheduledStrips = 1u << 20;  // (2^26 items / 64)
 // cost class of a strip = (largest step count among its rays) >> kCostShift: 4 steps per class -- with 8 the cheapest two classes of the

@@ -1710,84 +1710,82 @@ hipError_t launch_build_top_table(const uint32_t *nodes, uint32_t n_words, uint3
     return hipGetLastError();
 }
 
-constexpr int kStackBlock = 256;
-constexpr int kStackLevels = 12;      // default: resolves levels up to 3 + 1 + 12 = 16
-constexpr int kStackLevelsDeep = 18;  // deep trees: up to level 22 = kPathBits - 1
-
-int stack_max_depth(bool deep) { return kTopLevels + 1 + (deep ? kStackLevelsDeep : kStackLevels); }
-
-template <bool GE, int NS>
-static hipError_t launch_stack(const TraceArgs &args, const LaunchInfo &li, hipStream_t stream) {
-    const uint32_t strip_items = args.order ? 64u : (li.strip_items ? li.strip_items : 64u);
-    const bool shd = args.shadow_hits != nullptr;  // fused shadow rays (no timeline build of that one)
-    auto kern = shd ? (args.count_nodes ? trace_stack_kernel<kStackBlock, NS, kTopLevels, GE, false, true, true>
-                                        : trace_stack_kernel<kStackBlock, NS, kTopLevels, GE, false, false, true>)
-                    : (args.count_nodes
-                           ? (args.debug ? trace_stack_kernel<kStackBlock, NS, kTopLevels, GE, true, true, false>
-                                         : trace_stack_kernel<kStackBlock, NS, kTopLevels, GE, false, true, false>)
-                           : (args.debug ? trace_stack_kernel<kStackBlock, NS, kTopLevels, GE, true, false, false>
-                                         : trace_stack_kernel<kStackBlock, NS, kTopLevels, GE, false, false, false>));
-    const size_t lds_bytes = sizeof(uint32_t) * (size_t)(args.count_nodes ? StackLds<kStackBlock, NS, kTopLevels, true>::total
-                                                                               : StackLds<kStackBlock, NS, kTopLevels, false>::total);
-    // cached per context (= per device): [deep stack?][fused shadows?][counting instantiation?]
-    int &blocks_per_cu = li.occupancy[(args.debug ? 8 : 0) + (NS == kStackLevelsDeep ? 4 : 0) + (shd ? 2 : 0) + (args.count_nodes ? 1 : 0)];
-    if (blocks_per_cu == 0) {
-        int n = 0;
-        hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, kern, kStackBlock, lds_bytes);
-        if (e != hipSuccess) return e;
-        blocks_per_cu = n > 0 ? n : 1;
-        // The occupancy query does not round LDS up to the allocation granule; measured on MI355X, 336 bytes on top of
-        // 26 KiB per workgroup already cost the sixth workgroup per CU.  Workgroups that are not resident at launch
-        // start when the first ones end and bring their reserved (longest) strips with them, so overestimating is
-        // far worse than underestimating.  The granule is 1280 bytes (320 dwords): 512 bytes on top of this kernel's 22 KiB keep the
-        // seventh workgroup per CU, 528 lose it (profiles/r04_lds_granule_ab.log).
-        const int by_lds = (int)((160u * 1024u) / (((lds_bytes + 1279u) / 1280u) * 1280u));
-        if (by_lds >= 1 && by_lds < blocks_per_cu) blocks_per_cu = by_lds;
+// The STACK kernels by slot (svo_sched.h: trace_slot): the claiming instantiation, the LDS a workgroup of it needs and, for the plain
+// default ones, the replay twin.
+struct StackKernel {
+    void (*claim)(TraceArgs, uint32_t, uint32_t *, uint32_t *);
+    void (*replay)(TraceArgs, uint32_t, uint32_t *);
+    uint32_t lds_bytes;
+};
+struct StackKernels {
+    StackKernel at[kTraceSlots] = {};
+    template <bool GE, int NS, bool DBG, bool CNT, bool SHD>
+    void add() {
+        TraceChoice c;
+        c.stack = true, c.ge = GE, c.deep = NS == kStackLevelsDeep, c.dbg = DBG, c.cnt = CNT, c.shd = SHD;
+        StackKernel &k = at[trace_slot(c)];
+        k.claim = trace_stack_kernel<kStackBlock, NS, kTopLevels, GE, DBG, CNT, SHD>;
+        k.lds_bytes = (uint32_t)sizeof(uint32_t) * StackLds<kStackBlock, NS, kTopLevels, CNT>::total;
+        if constexpr (NS == kStackLevels && !DBG && !CNT && !SHD) k.replay = trace_stack_replay_kernel<kStackBlock, NS, kTopLevels, GE>;
     }
-    uint32_t blocks = (uint32_t)li.num_cus * (uint32_t)blocks_per_cu;
-    if (li.grid_blocks > 0) blocks = (uint32_t)li.grid_blocks;
-    // (the timeline's buffer has a row for SVO_DEBUG_WAVES waves: a grid override beyond that is cut back while the buffer is set)
-    if (args.debug && blocks > SVO_DEBUG_WAVES / (kStackBlock / 64)) blocks = SVO_DEBUG_WAVES / (kStackBlock / 64);
-    uint32_t n_strips = (args.work.n_items + strip_items - 1) / strip_items;
-    uint32_t need = (n_strips + (kStackBlock / 64) - 1) / (kStackBlock / 64);
-    if (blocks > need) blocks = need;
-    if (li.blocks_out) {  // (the caller only asks what grid this frame would get: svo_abi.cpp sizes and seeds the deal table from it)
-        *li.blocks_out = blocks;
+    template <bool GE, int NS>
+    void add_all() {
+        add<GE, NS, false, false, false>();
+        add<GE, NS, false, true, false>();
+        add<GE, NS, true, false, false>();
+        add<GE, NS, true, true, false>();
+        add<GE, NS, false, false, true>();
+        add<GE, NS, false, true, true>();
+    }
+    StackKernels() {
+        add_all<false, kStackLevels>();
+        add_all<true, kStackLevels>();
+        add_all<false, kStackLevelsDeep>();
+        add_all<true, kStackLevelsDeep>();
+    }
+};
+static const StackKernels stack_kernels;
+
+hipError_t plan_trace(const TraceArgs &args, const LaunchInfo &li, const TraceChoice &choice, TraceLaunch &launch) {
+    launch = TraceLaunch{};
+    launch.choice = choice;
+    if (!choice.stack) {
+        launch.blocks = (args.work.n_items + 255u) / 256u;
+        const uint32_t cap = li.grid_blocks > 0 ? (uint32_t)li.grid_blocks : (uint32_t)li.num_cus * 8u;
+        if (launch.blocks > cap) launch.blocks = cap;
         return hipSuccess;
     }
-    if (args.deal_table != nullptr) {
-        // the replay twin: same grid, same LDS, same occupancy slot as the default instantiation whose claims it replaces
-        if constexpr (NS == kStackLevels) {
-            if (shd || args.count_nodes || args.debug) return hipErrorInvalidValue;
-            hipLaunchKernelGGL((trace_stack_replay_kernel<kStackBlock, NS, kTopLevels, GE>), dim3(blocks), dim3(kStackBlock), lds_bytes, stream, args,
-                               strip_items, li.defer);
-            return hipGetLastError();
-        }
-        return hipErrorInvalidValue;
+    launch.slot = trace_slot(choice);
+    const StackKernel &k = stack_kernels.at[launch.slot];
+    launch.lds_bytes = k.lds_bytes;
+    launch.strip_items = args.order ? 64u : (li.strip_items ? li.strip_items : 64u);
+    int &blocks_per_cu = li.occupancy[launch.slot];  // cached per context (= per device)
+    if (blocks_per_cu == 0) {
+        int n = 0;
+        hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k.claim, kStackBlock, k.lds_bytes);
+        if (e != hipSuccess) return e;
+        blocks_per_cu = resident_workgroups(n, k.lds_bytes);
     }
-    hipLaunchKernelGGL(kern, dim3(blocks), dim3(kStackBlock), lds_bytes, stream, args, strip_items, li.counters, li.defer);
-    return hipGetLastError();
+    launch.blocks = stack_grid_blocks((uint32_t)li.num_cus, (uint32_t)blocks_per_cu, li.grid_blocks > 0 ? (uint32_t)li.grid_blocks : 0u,
+                                      args.debug != nullptr, args.work.n_items, launch.strip_items);
+    return hipSuccess;
 }
 
-hipError_t launch_trace(const TraceArgs &args, const LaunchInfo &li, hipStream_t stream) {
+hipError_t launch_trace(const TraceArgs &args, const LaunchInfo &li, const TraceLaunch &launch, hipStream_t stream) {
     (void)hipGetLastError();
     if (args.work.n_items == 0) return hipSuccess;
-    const bool counter_hits = (args.u.flags & SVO_F_PAUSE_ADAPTIVE) && (args.u.flags & SVO_F_SHOW_HITS);
-    // the debug hit test reads counter bits: it needs the reference-shaped walk
-    if (li.variant == SVO_VARIANT_RESTART || counter_hits) {
-        uint32_t blocks = (args.work.n_items + 255u) / 256u;
-        uint32_t cap = (uint32_t)li.num_cus * 8u;
-        if (li.grid_blocks > 0) cap = (uint32_t)li.grid_blocks;
-        if (blocks > cap) blocks = cap;
-        hipLaunchKernelGGL(trace_restart_kernel, dim3(blocks), dim3(256), 0, stream, args, (const uint32_t *)nullptr);
+    if (!launch.choice.stack) {
+        hipLaunchKernelGGL(trace_restart_kernel, dim3(launch.blocks), dim3(256), 0, stream, args, (const uint32_t *)nullptr);
         return hipGetLastError();
     }
     // li.counters = {64 claim counters (kCounterStride words apart), deferred-ray count, deferred items}: zero when a frame
     // starts (armed at allocation and re-armed by the last kernel of the previous frame)
-    const bool ge = (args.u.flags & SVO_F_MISC_BOOL) != 0;
-    if (li.deep_stack)  // trees deeper than kTopLevels + 1 + kStackLevels: more LDS per workgroup, fewer resident waves
-        return ge ? launch_stack<true, kStackLevelsDeep>(args, li, stream) : launch_stack<false, kStackLevelsDeep>(args, li, stream);
-    return ge ? launch_stack<true, kStackLevels>(args, li, stream) : launch_stack<false, kStackLevels>(args, li, stream);
+    const StackKernel &k = stack_kernels.at[launch.slot];
+    if (launch.choice.replay)
+        hipLaunchKernelGGL(k.replay, dim3(launch.blocks), dim3(kStackBlock), launch.lds_bytes, stream, args, launch.strip_items, li.defer);
+    else
+        hipLaunchKernelGGL(k.claim, dim3(launch.blocks), dim3(kStackBlock), launch.lds_bytes, stream, args, launch.strip_items, li.counters, li.defer);
+    return hipGetLastError();
 }
 
 // After the STACK kernel: deferred rays, per-strip cost classes (unless the plan reuses the slot's), counter re-arm; and, when the

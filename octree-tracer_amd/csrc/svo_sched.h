@@ -1,9 +1,12 @@
 // svo_sched.h -- the strip schedule's per-frame policy: which lists a STACK frame is traced with, and
 // what the post pass measures and rebuilds after it.  Plain C++ (no HIP): the host glue in svo_abi.cpp (trace_launch) measures the
 // facts and runs the launches, tests/test_schedule_plan.py replays frame sequences through these two functions.  Also the arithmetic
-// of the trace kernel's strip claims (which entry of which list a wave gets), stated once for the kernel and for a host test.
+// of the trace kernel's strip claims (which entry of which list a wave gets), stated once for the kernel and for a host test.  And
+// which kernel traces a frame, with how many workgroups (TraceChoice, trace_slot, resident_workgroups, stack_grid_blocks): the one
+// statement of those rules, for svo_abi.cpp, for svo_kernels.hip's launcher and for tests/test_trace_choice_host.py.
 #pragma once
 #include <cmath>
+#include <cstddef>
 #include <cstdint>
 
 namespace svo {
@@ -207,6 +210,110 @@ inline PostPlan plan_after_trace(SchedState &s, const FrameFacts &f) {
         s.age++;
     }
     return p;
+}
+
+// ---- the trace kernel of a frame and its grid: svo_abi.cpp asks (trace_launch and the callers that allocate by the answer),
+// svo_kernels.hip launches what it is told (plan_trace, launch_trace); tests/test_trace_choice_host.py holds both to a restatement ----
+constexpr int kTopLevels = 3;         // K: octree levels folded into the LDS top table
+constexpr int kStackBlock = 256;      // threads of a STACK workgroup
+constexpr int kStackLevels = 12;      // default: resolves levels up to 3 + 1 + 12 = 16
+constexpr int kStackLevelsDeep = 18;  // deep trees: up to level 22 = kPathBits - 1
+constexpr int stack_max_depth(bool deep) { return kTopLevels + 1 + (deep ? kStackLevelsDeep : kStackLevels); }
+constexpr uint32_t kTimelineWaves = 16384;  // SVO_DEBUG_WAVES of include/svo_hip.h (svo_device.h holds the two to each other)
+
+// What the host knows before it traces a call's frames (the uniforms' flags as they are set; the options as the caller left them).
+struct TraceFacts {
+    bool restart_variant = false;  // SVO_OPT_VARIANT is SVO_VARIANT_RESTART
+    uint32_t tree_depth = 16;      // SVO_OPT_TREE_DEPTH: the caller's bound on the octree's depth
+    bool pause_adaptive = false, show_hits = false, misc_bool = false;  // SVO_F_*
+    bool fused_shadows = false;    // SVO_OPT_FUSED_SHADOWS is not 0
+};
+// ... and of one launch
+struct LaunchFacts {
+    uint32_t mode = 0;          // of the WorkDesc
+    bool count_rays = false;    // explicit rays that count like primary ones (shadow and secondary rays)
+    bool fused = false;         // the caller fused the shadow rays (fuse_allowed, and its own test of the sun's direction)
+    bool debug_buffer = false;  // SVO_OPT_DEBUG_BUFFER is set
+};
+
+// What runs.  RESTART: the reference-shaped walk, general to depth 31; of the fields below only cnt means something (the hit
+// counters are live).  STACK: trace_stack_kernel<.., ge, dbg, cnt, shd> with the default or the deep ancestor stack, or the
+// replay twin of the plain default one.
+struct TraceChoice {
+    bool stack = false;
+    bool ge = false;      // SVO_F_MISC_BOOL: the hit test is >=
+    bool deep = false;    // 19-level ancestor stack (trees deeper than 16 levels): more LDS per workgroup, fewer resident waves
+    bool dbg = false;     // the timeline build
+    bool cnt = false;     // hit counters live
+    bool shd = false;     // fused shadow rays
+    bool replay = false;  // a resting view's static deal (svo_deal.h): no claims
+};
+
+// The debug view that reads counter bits needs the reference-shaped walk: RESTART, and nothing fused into it.
+inline bool debug_view(const TraceFacts &f) { return f.pause_adaptive && f.show_hits; }
+// STACK resolves the levels its integer path codes cover; deeper trees take the general RESTART kernel.  (Wanted is not chosen:
+// the debug view has its top table built and is then traced by RESTART.)
+// The ancestor stack's levels for a tree of the declared depth (0: deeper than either stack resolves).
+inline int stack_levels_for(uint32_t tree_depth) {
+    if (tree_depth <= (uint32_t)stack_max_depth(false)) return kStackLevels;
+    return tree_depth <= (uint32_t)stack_max_depth(true) ? kStackLevelsDeep : 0;
+}
+inline bool stack_wanted(const TraceFacts &f) { return !f.restart_variant && stack_levels_for(f.tree_depth) != 0; }
+// The kind of kernel every launch of the call gets; the per-launch fields are launch_choice's.
+inline TraceChoice kernel_kind(const TraceFacts &f) {
+    TraceChoice c;
+    c.stack = stack_wanted(f) && !debug_view(f);
+    c.ge = f.misc_bool;
+    c.deep = stack_levels_for(f.tree_depth) == kStackLevelsDeep;
+    return c;
+}
+// May the primary launch trace the shadow rays too?  (The caller adds what only it can test: the sun's direction.)
+inline bool fuse_allowed(const TraceFacts &f) { return f.fused_shadows && kernel_kind(f).stack; }
+inline TraceChoice launch_choice(const TraceFacts &f, const LaunchFacts &l) {
+    TraceChoice c = kernel_kind(f);
+    // shader.wgsl:159: counters are live unless pause_adaptive; rays handed in by the caller (svo_trace_rays) never count
+    c.cnt = (l.mode != 2u || l.count_rays) && !f.pause_adaptive;
+    c.shd = c.stack && l.fused;
+    c.dbg = c.stack && l.debug_buffer && !c.shd;  // (there is no timeline build with fused shadows)
+    return c;
+}
+// The launches the replay kernel can serve (the rest of a plain static frame is the deal's own: svo_abi.cpp, deal_before).  With
+// shd excluded, dbg says whether the debug buffer is set.
+inline bool replay_eligible(const TraceChoice &c) { return c.stack && !c.cnt && !c.shd && !c.dbg && !c.deep; }
+
+// One slot per STACK instantiation, for the table of kernels and the context's cache of resident workgroups per CU.  The
+// replay twin has the slot of the default instantiation whose claims it replaces: same grid, same LDS.
+constexpr uint32_t kTraceSlots = 24;
+inline uint32_t trace_slot(const TraceChoice &c) {
+    const uint32_t kind = c.shd ? 4u + c.cnt : 2u * c.dbg + c.cnt;
+    return (c.ge ? 12u : 0u) + (c.deep ? 6u : 0u) + kind;
+}
+
+// Resident workgroups per CU of a kernel that asks for lds_bytes per workgroup, from the runtime's answer.
+// The occupancy query does not round LDS up to the allocation granule; measured on MI355X, 336 bytes on top of
+// 26 KiB per workgroup already cost the sixth workgroup per CU.  Workgroups that are not resident at launch
+// start when the first ones end and bring their reserved (longest) strips with them, so overestimating is
+// far worse than underestimating.  The granule is 1280 bytes (320 dwords): 512 bytes on top of the default kernel's 22 KiB keep the
+// seventh workgroup per CU, 528 lose it (profiles/r04_lds_granule_ab.log).
+inline int resident_workgroups(int by_runtime, size_t lds_bytes) {
+    const int n = by_runtime > 0 ? by_runtime : 1;
+    const size_t granules = (lds_bytes + 1279u) / 1280u;
+    const int by_lds = granules ? (int)((160u * 1024u) / (granules * 1280u)) : 0;
+    return by_lds >= 1 && by_lds < n ? by_lds : n;
+}
+// Workgroups of a STACK launch: every CU full (or SVO_OPT_GRID_BLOCKS, when not 0), and no more than the frame has strips for
+// its waves.
+inline uint32_t stack_grid_blocks(uint32_t num_cus, uint32_t resident_per_cu, uint32_t grid_override, bool debug_buffer, uint32_t n_items,
+                                  uint32_t strip_items) {
+    constexpr uint32_t waves = kStackBlock / 64;
+    uint32_t blocks = num_cus * resident_per_cu;
+    if (grid_override > 0u) blocks = grid_override;
+    // (the timeline's buffer has a row for kTimelineWaves waves: a grid override beyond that is cut back while the buffer is set,
+    // also for the fused kernel, which writes no timeline)
+    if (debug_buffer && blocks > kTimelineWaves / waves) blocks = kTimelineWaves / waves;
+    const uint32_t n_strips = (n_items + strip_items - 1u) / strip_items;
+    const uint32_t need = (n_strips + waves - 1u) / waves;
+    return blocks > need ? need : blocks;
 }
 
 #undef SVO_SCHED_INLINE

@@ -1,4 +1,4 @@
-"""Every instantiation of the STACK trace kernel against the oracle (csrc/svo_kernels.hip, launch_stack): the sixteen cells
+"""Every instantiation of the STACK trace kernel against the oracle (csrc/svo_kernels.hip, stack_kernels): the sixteen cells
 GE x NS x CNT x SHD of trace_stack_kernel and the two of trace_stack_replay_kernel, each its own code object with its own LDS
 layout and its own copy of the walk.
 
@@ -8,11 +8,12 @@ layout and its own copy of the walk.
   SHD  fused shadow rays               SVO_F_SHADOWS with SVO_OPT_FUSED_SHADOWS = 1, in a call that shades
 
 The frames are the lattice cameras of tests/trace_matrix_scenes.py: every ray starts on a tie, so > and >= part ways in records
-and in counter words (tests/test_trace_matrix_host.py holds the scenes to that).  Which kernel a cell launches follows from
-launch_stack's rules; that the deep instantiation was needed is shown by the same frame being refused under a declared depth
-of 16.  The RESTART kernel runs every cell's flags too: a mismatch it does not share is the stack kernel's.
+and in counter words (tests/test_trace_matrix_host.py holds the scenes to that).  Which kernel a cell launches is held on the
+host: tests/test_trace_choice_host.py drives the one statement of those rules (csrc/svo_sched.h: launch_choice, trace_slot)
+over every combination of what they depend on; that the deep instantiation was needed is shown by the same frame being refused
+under a declared depth of 16.  The RESTART kernel runs every cell's flags too: a mismatch it does not share is the stack kernel's.
 
-The eight timeline instantiations (DBG, with SVO_OPT_DEBUG_BUFFER set: GE x NS x CNT, launch_stack has none with fused shadows)
+The eight timeline instantiations (DBG, with SVO_OPT_DEBUG_BUFFER set: GE x NS x CNT, there is none with fused shadows)
 run the same frames: the same records and counter words, and a timeline that is consistent with the frame."""
 import types
 
