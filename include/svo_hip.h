@@ -654,6 +654,59 @@ int svo_mesh_voxelize(svo_ctx *ctx, const svo_voxelize_params *p,
 #define SVO_VOXELIZE_TIMES 5
 int svo_voxelize_timing(svo_ctx *ctx, float ms_out[SVO_VOXELIZE_TIMES]);
 
+/* ---- closed meshes voxelised solid on the GPU ----
+ * The cells of the 2^depth grid that lie inside a triangle mesh, as a voxel list for svo_nodes_build and svo_nodes_edit
+ * or as y-spans.  Units, vertices and their checks are svo_mesh_voxelize's: a vertex is V = 2q + 1 in doubled units, a
+ * cell c spans [128c, 128(c + 1)] per axis and its centre is C = 128c + 64.  A cell is judged at its centre moved by a
+ * symbolic (dx, dy, dz) with 1 >> dy >> dx >> dz > 0, a generic point: every tie has one answer, the same for every
+ * triangle.  For a triangle with edges e_i = V_(i+1) - V_i and n = e0 x e1:
+ *   edge-on     n.y == 0: it covers no column and contributes nothing.
+ *   covers the column (cx, cz) iff s * sgn_i > 0 for i = 0, 1, 2, with s = sign(-n.y),
+ *               F_i = e_i.x (Cz - V_i.z) - e_i.z (Cx - V_i.x) (int64, below 2^57) and sgn_i = sign(F_i), or for F_i == 0
+ *               sign(-e_i.z), or for e_i.z == 0 too sign(e_i.x).
+ *   crosses above the centre cy iff D = n . (C - V0) (below 2^87: 128 bits) is non-zero and sign(D) != sign(n.y); a
+ *               centre on the plane is above it.  D is monotone in Cy, so these cy are {0 .. k - 1}: k in [0, 2^depth] is
+ *               the triangle's height in the column.
+ *   w           sign(n.y).
+ * The cell (cx, cy, cz) is inside under SVO_SOLID_EVENODD iff the number of covering triangles with k > cy is odd, under
+ * SVO_SOLID_NONZERO iff the sum of their w is non-zero.  A column is open when that holds below every height (at cy = -1:
+ * an odd number of covering triangles, or a non-zero sum of w); a watertight mesh has none, and the cells of an open
+ * column are still the rule's.  The order of the triangles does not matter to the result at all.
+ * With SVO_SOLID_SPANS the output is the maximal runs [y0, y1) of inside cells of a column as (x, z, y0, y1), ascending in
+ * (x, z, y0); without, their cells (x, y, z), ascending in (x, z, y).  No float and no atomic takes part: the same bytes on
+ * every run.  out_dev == NULL is a count query: *n_out gets the number of entries (cells, or spans), *n_open_out (when
+ * given) the number of open columns, nothing else is written and max_out is ignored.  Otherwise out_dev gets the entries
+ * [0, *n_out) and nothing behind them.  n_tris == 0 succeeds with 0.
+ * All pointers but p, n_out and n_open_out are DEVICE pointers on the ctx's device.  The call needs no node buffer and
+ * never touches one.  Runs on the ctx stream; blocks once per level of the column refinement and once per count (spans,
+ * cells); the fill is enqueued: inputs and outputs must stay valid until svo_sync.
+ * A refused call leaves out_dev, *n_out and *n_open_out as they were.  Of several causes the first in this order is
+ * reported.  SVO_ERR_ARG: NULL p or n_out; unknown flag bits or non-zero reserved; depth outside 1..21; n_tris >= 2^31;
+ * NULL vq_dev or tri_dev with n_tris > 0; checked on the device, with svo_mesh_voxelize's messages: a vertex index >=
+ * n_vertices or a coordinate >= 2^(depth + 6).  SVO_ERR_CAP: a level's count of (triangle, column square) pairs passes
+ * max_pairs (the message names the level and the count; the counts of the levels below the last never fall, so this is
+ * the first such level and no wider one is allocated; the last level counts the crossings); the entry count passes
+ * max_out (not in a count query) or reaches 2^31 (always), with the exact count in the message. */
+#define SVO_SOLID_EVENODD 0u
+#define SVO_SOLID_NONZERO 1u
+#define SVO_SOLID_SPANS   2u
+typedef struct svo_solid_params {
+    uint32_t depth;        /* 1..21 */
+    uint32_t flags;
+    uint32_t n_vertices;
+    uint32_t reserved;     /* 0 */
+    uint64_t max_out;      /* room in the output, in entries (cells, or spans); ignored by a count query */
+    uint64_t max_pairs;    /* cap on (triangle, column-square) pairs of any level; 0 = 2^27 */
+} svo_solid_params;
+int svo_mesh_voxelize_solid(svo_ctx *ctx, const svo_solid_params *p, const uint32_t *vq_dev, const uint32_t *tri_dev, size_t n_tris,
+                            uint32_t *out_dev /* cells: 3 u32 (x, y, z); spans: 4 u32 (x, z, y0, y1); NULL = count query */,
+                            uint64_t *n_out, uint64_t *n_open_out /* may be NULL */);
+/* Times (ms) of the last solid voxelisation that ran: [0] setup, [1] the column levels (with the crossings' emit), [2] the
+ * sort, [3] spans (heads, intervals, runs and their read-back; in cell mode the cells' count too), [4] emit (0 for a
+ * count query), [5] host wall time of the call.  A refused call leaves the times of the last one that ran. */
+#define SVO_SOLID_TIMES 6  /* setup, column levels, sort, spans, emit, host wall */
+int svo_solid_timing(svo_ctx *ctx, float ms_out[SVO_SOLID_TIMES]);
+
 /* ---- voxel structures scattered over the tree in the node buffer ----
  * Three calls that together populate a terrain without the tree leaving the device: where the ground is in every
  * column of a rectangle (svo_nodes_column_tops), which columns get a structure (svo_structures_sites), and the voxel

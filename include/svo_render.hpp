@@ -346,6 +346,21 @@ class Render {  // render.rs:3-285
         gpu_.poll_wait();  // the inputs may go away
         return n;
     }
+    // the cells inside a closed triangle mesh, on the GPU and exactly (svo_mesh_voxelize_solid): vq_dev and
+    // tri_dev as voxelize_mesh takes them; flags: SVO_SOLID_EVENODD or SVO_SOLID_NONZERO, with SVO_SOLID_SPANS the y-spans
+    // (x, z, y0, y1) instead of the cells (x, y, z); out_dev (3, or 4, u32 per entry, max_out entries) is a DEVICE pointer.
+    // Returns the entry count; out_dev null: the count alone.  *n_open (when given) gets the number of open columns: 0 for
+    // a watertight mesh.  Needs no node buffer.  Throws, with nothing written, for a bad vertex index or coordinate, a
+    // level of more than max_pairs (triangle, column square) pairs (0: 2^27) or more entries than max_out.
+    uint64_t voxelize_mesh_solid(const uint32_t *vq_dev, uint32_t n_vertices, const uint32_t *tri_dev, size_t n_tris, uint32_t depth,
+                                 uint32_t *out_dev, uint64_t max_out, uint32_t flags = SVO_SOLID_EVENODD, uint64_t *n_open = nullptr,
+                                 uint64_t max_pairs = 0) {
+        const svo_solid_params p{depth, flags, n_vertices, 0u, max_out, max_pairs};
+        uint64_t n = 0;
+        gpu_.check(svo_mesh_voxelize_solid(gpu_.ctx(), &p, vq_dev, tri_dev, n_tris, out_dev, &n, n_open));
+        gpu_.poll_wait();  // the inputs may go away
+        return n;
+    }
     // what the tree in the first n_words words of the node buffer holds at n cells of the `depth` grid, looked up on the
     // GPU (svo_nodes_sample): xyz_dev (3 * n u32, as build_nodes takes them), values_dev (n u32) and
     // levels_dev, indices_dev (n u32 each, or null) are DEVICE pointers; a value is the leaf's, 0 for empty, or one of

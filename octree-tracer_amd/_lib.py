@@ -115,6 +115,18 @@ class VoxelizeParams(C.Structure):
     ]
 
 
+class SolidParams(C.Structure):
+    """svo_solid_params: a closed triangle mesh voxelised solid on the device (include/svo_hip.h)."""
+    _fields_ = [
+        ("depth", C.c_uint32),
+        ("flags", C.c_uint32),
+        ("n_vertices", C.c_uint32),
+        ("reserved", C.c_uint32),
+        ("max_out", C.c_uint64),
+        ("max_pairs", C.c_uint64),
+    ]
+
+
 class TopsParams(C.Structure):
     """svo_tops_params: the highest occupied cell of each column of the tree in the node buffer (include/svo_hip.h)."""
     _fields_ = [
@@ -245,6 +257,8 @@ DEVICE_SIGNATURES = {
     "svo_sample_timing": (C.c_int, (vp, fp)),
     "svo_mesh_voxelize": (C.c_int, (vp, C.POINTER(VoxelizeParams), vp, vp, vp, sz, vp, vp, vp, C.POINTER(u64))),
     "svo_voxelize_timing": (C.c_int, (vp, fp)),
+    "svo_mesh_voxelize_solid": (C.c_int, (vp, C.POINTER(SolidParams), vp, vp, sz, vp, C.POINTER(u64), C.POINTER(u64))),
+    "svo_solid_timing": (C.c_int, (vp, fp)),
     "svo_nodes_column_tops": (C.c_int, (vp, C.POINTER(TopsParams), C.POINTER(u32), C.POINTER(u32), vp, vp)),
     "svo_structures_sites": (C.c_int, (vp, C.POINTER(SitesParams), vp, vp, C.POINTER(u32), C.POINTER(u32), vp, vp, C.POINTER(u64))),
     "svo_structures_stamp": (C.c_int, (vp, C.POINTER(StampParams), vp, vp, sz, vp, vp, sz, vp, vp, vp, C.POINTER(u64))),

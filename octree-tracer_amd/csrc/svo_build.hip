@@ -349,21 +349,28 @@ int ensure_state(svo_ctx *ctx, size_t items, size_t scan_items, size_t hist_item
     return rc;
 }
 
-// `passes` stable 8-bit radix passes over the n items in keys[0] / vals[0]; the result is in keys[passes & 1] / vals[passes & 1].
-int sort_passes(svo_ctx *ctx, uint32_t n, uint32_t passes) {
+// `passes` stable 8-bit radix passes over the n items in keys[0] / vals[0], which take turns with keys[1] / vals[1]; the
+// result is in keys[passes & 1] / vals[passes & 1].  The digit counts are the builder's (hist: 256 per tile).
+int sort_passes(svo_ctx *ctx, uint32_t n, uint32_t passes, uint64_t *const keys[2], uint32_t *const vals[2]) {
     svo_build_state *s = ctx->build.get();
     const uint32_t nt = svo_div_up(n, kTile);
     for (uint32_t k = 0; k < passes; k++) {
         const uint32_t a = k & 1;
-        build_hist_kernel<<<nt, kThreads, 0, ctx->stream>>>(s->keys[a], n, 8 * k, s->hist, nt);
+        build_hist_kernel<<<nt, kThreads, 0, ctx->stream>>>(keys[a], n, 8 * k, s->hist, nt);
         HIP_TRY(ctx, hipGetLastError());
         int rc = svo_scan_u32(ctx, s->hist, 256 * nt);
         if (rc) return rc;
-        build_scatter_kernel<<<nt, kThreads, 0, ctx->stream>>>(s->keys[a], s->vals[a], n, 8 * k, s->hist, nt, s->keys[a ^ 1],
-                                                               s->vals[a ^ 1]);
+        build_scatter_kernel<<<nt, kThreads, 0, ctx->stream>>>(keys[a], vals[a], n, 8 * k, s->hist, nt, keys[a ^ 1], vals[a ^ 1]);
         HIP_TRY(ctx, hipGetLastError());
     }
     return SVO_OK;
+}
+// the builder's own buffers
+int sort_passes(svo_ctx *ctx, uint32_t n, uint32_t passes) {
+    svo_build_state *s = ctx->build.get();
+    uint64_t *const keys[2] = {s->keys[0], s->keys[1]};
+    uint32_t *const vals[2] = {s->vals[0], s->vals[1]};
+    return sort_passes(ctx, n, passes, keys, vals);
 }
 
 // One level pass: flags, tile counts, scan (the total goes to *total), compaction (and, with out.words or out.nodes, emit).
@@ -594,6 +601,25 @@ int svo_build_sort_u32(svo_ctx *ctx, const uint32_t *in, uint32_t n, uint32_t *o
     if ((rc = sort_passes(ctx, n, 4))) return rc;  // (4 passes of 8 bits: the result is back in keys[0])
     build_narrow_kernel<<<grid, kThreads, 0, ctx->stream>>>(s->keys[0], n, out);
     HIP_TRY(ctx, hipGetLastError());
+    return SVO_OK;
+}
+
+// The same sort of n (key, value) pairs by the keys' low `bits` bits, in place, for other passes on the ctx stream
+// (svo_solid.hip sorts its crossings with it): ceil(bits / 8) passes between the caller's arrays and the builder's
+// keys[1] / vals[1].  Nothing is copied back: *keys_dev and *vals_dev come back pointing at the sorted arrays, the
+// caller's own after an even number of passes, the builder's after an odd one; those have room for n + 1 items and hold
+// until the next call that uses the builder's workspace.
+int svo_build_sort_u64(svo_ctx *ctx, uint64_t **keys_dev, uint32_t **vals_dev, uint32_t n, uint32_t bits) {
+    if (!n) return SVO_OK;
+    int rc = ensure_state(ctx, (size_t)n + 1, 0, 256ull * svo_div_up(n, kTile));
+    if (rc) return rc;
+    svo_build_state *s = ctx->build.get();
+    const uint32_t passes = (bits + 7) / 8;
+    uint64_t *const keys[2] = {*keys_dev, s->keys[1]};
+    uint32_t *const vals[2] = {*vals_dev, s->vals[1]};
+    if ((rc = sort_passes(ctx, n, passes, keys, vals))) return rc;
+    *keys_dev = keys[passes & 1];
+    *vals_dev = vals[passes & 1];
     return SVO_OK;
 }
 

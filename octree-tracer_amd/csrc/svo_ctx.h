@@ -1,9 +1,9 @@
 // svo_ctx.h -- the device context behind the opaque `svo_ctx` of include/svo_hip.h, and the host helpers of the files that
 // use it: svo_abi.cpp (trace / scan dispatch), svo_comm.cpp (RCCL frame gather) and the GPU tree passes (svo_proc.hip,
-// svo_build.hip, svo_edit.hip, svo_compact.hip, svo_list.hip, svo_sample.hip, svo_voxelize.hip, svo_structure.hip,
-// svo_surface.hip, svo_adapt.hip).  One rule of ownership for the context, the node store and every pass's state: a
-// member owns what it holds, as svo_dev / svo_pinned (an allocation and its size), svo_events (events) or svo_stream (a
-// stream).  The passes
+// svo_build.hip, svo_edit.hip, svo_compact.hip, svo_list.hip, svo_sample.hip, svo_voxelize.hip, svo_solid.hip,
+// svo_structure.hip, svo_surface.hip, svo_adapt.hip).  One rule of ownership for the context, the node store and every
+// pass's state: a member owns what it holds, as svo_dev / svo_pinned (an allocation and its size), svo_events (events) or
+// svo_stream (a stream).  The passes
 // share the rest as their host frame: svo_grow / svo_grow_pinned / svo_grow_keep (workspaces, by the buffers' own
 // sizes), svo_mirrored (device words with a pinned mirror), svo_pass_timer (events and times), svo_workspace_ensure
 // (creation) and the svo_check_* argument checks; then the builder's sort and svo_world_writer (a generated world's
@@ -145,6 +145,7 @@ struct svo_compact_state;
 struct svo_list_state;
 struct svo_sample_state;
 struct svo_voxelize_state;
+struct svo_solid_state;
 struct svo_structure_state;
 struct svo_surface_state;
 template <typename T>
@@ -255,6 +256,7 @@ struct svo_ctx {
     svo_workspace<svo_list_state> list{nullptr, nullptr};  // voxel listing's workspace (svo_list.hip)
     svo_workspace<svo_sample_state> sample{nullptr, nullptr};  // sampling's events and times (svo_sample.hip)
     svo_workspace<svo_voxelize_state> voxelize{nullptr, nullptr};  // mesh voxeliser's workspace (svo_voxelize.hip)
+    svo_workspace<svo_solid_state> solid{nullptr, nullptr};  // solid voxeliser's workspace (svo_solid.hip)
     svo_workspace<svo_structure_state> structure{nullptr, nullptr};  // structure scattering's workspace (svo_structure.hip)
     svo_workspace<svo_surface_state> surface{nullptr, nullptr};  // surface extraction's workspace (svo_surface.hip)
     std::string err;
@@ -421,6 +423,10 @@ void svo_comm_release(svo_ctx *ctx);
 // the builder's stable radix sort of n u32 keys (in -> out, may alias), for other passes on the ctx stream; it uses the
 // builder's workspace
 int svo_build_sort_u32(svo_ctx *ctx, const uint32_t *in, uint32_t n, uint32_t *out);
+// the same sort of n (u64 key, u32 value) pairs by the keys' low `bits` bits, in ceil(bits / 8) passes; the two pointers
+// come back pointing at the sorted arrays: the caller's own, or (an odd number of passes) the builder's, which have room
+// for n + 1 items and hold until the next call that uses the builder's workspace
+int svo_build_sort_u64(svo_ctx *ctx, uint64_t **keys_dev, uint32_t **vals_dev, uint32_t n, uint32_t bits);
 // the front end of the builder's list entry points, for other passes over a voxel list (svo_edit.hip): the checks of
 // depth (null: no params), n and xyz with the builder's messages, then keys, the stable sort and the leaf pass on the ctx
 // stream.  Everything in svo_build_leaves lives in the builder's workspace and holds until the next call that uses it.

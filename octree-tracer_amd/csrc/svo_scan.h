@@ -1,6 +1,7 @@
 // svo_scan.h -- the tiled count, scan and emit of the GPU passes: svo_proc.hip (a level's ranks), svo_build.hip (the
 // level passes, the sort's digit counts), svo_adapt.hip (the expand's compactions), svo_structure.hip (sites, stamp),
-// svo_voxelize.hip (a level's pairs) and svo_surface.hip (the kept entries or faces); svo_compact.hip, svo_list.hip
+// svo_voxelize.hip (a level's pairs), svo_solid.hip (a level's pairs, heads, intervals, runs) and svo_surface.hip (the
+// kept entries or faces); svo_compact.hip, svo_list.hip
 // (through svo_tree_discover), svo_edit.hip and svo_adapt.hip scan an array in place with svo_scan_u32.  No atomics: an
 // output's place depends on the inputs alone.
 // A tile is kTile items, kPer consecutive ones per thread, so ranks follow the items' order.  A pass is three launches:
@@ -138,6 +139,46 @@ __global__ __launch_bounds__(kThreads) void tile_scatter_kernel(Items items, Emi
         if (i >= m) break;
         const uint32_t mine = at[j + (j >> 5)];
         if (mine & 0xFFu) emit(items, i, mine & 0xFFu, base + (mine >> 8));
+    }
+}
+
+// ---- the scatter's items whose flags are a byte array (the child masks of a level's pairs: svo_voxelize.hip, svo_solid.hip) ----
+// The state is the bytes of a thread's kPer consecutive items as one uint4; the array is padded to whole tiles, and what
+// lies behind m is not counted.
+struct FlagBytes {
+    const uint8_t *mask;
+    __device__ uint4 load(uint32_t i0, uint32_t m) const {
+        uint4 w = *reinterpret_cast<const uint4 *>(mask + i0);
+        const auto live = [&](uint32_t first) { return first >= m ? 0u : m - first >= 4 ? 0xFFFFFFFFu : (1u << 8 * (m - first)) - 1u; };
+        w.x &= live(i0);
+        w.y &= live(i0 + 4);
+        w.z &= live(i0 + 8);
+        w.w &= live(i0 + 12);
+        return w;
+    }
+    __device__ uint32_t count(const uint4 &w) const { return __popc(w.x) + __popc(w.y) + __popc(w.z) + __popc(w.w); }
+    __device__ uint32_t flags(const uint4 &w, uint32_t k) const {
+        const uint32_t q[4] = {w.x, w.y, w.z, w.w};
+        return q[k / 4] >> 8 * (k % 4);
+    }
+};
+
+// The sum of v[0, n) in 64 bits by the one block of kTopThreads that calls it, into out[0] (the low half) and out[1]: for
+// a total that tile_offsets_kernel's 32 bits may not hold, before it is compared with a cap.
+template <typename T>
+__device__ inline void block_total64(const T *v, uint32_t n, uint32_t *out) {
+    __shared__ uint64_t s[kTopThreads];
+    uint64_t sum = 0;
+    for (uint32_t i = threadIdx.x; i < n; i += kTopThreads) sum += v[i];
+    s[threadIdx.x] = sum;
+    __syncthreads();
+    for (uint32_t off = kTopThreads / 2; off > 0; off >>= 1) {
+        if (threadIdx.x < off) s[threadIdx.x] += s[threadIdx.x + off];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        out[0] = uint32_t(s[0]);
+        out[1] = uint32_t(s[0] >> 32);
     }
 }
 

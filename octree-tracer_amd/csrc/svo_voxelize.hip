@@ -26,12 +26,13 @@
 #include <string>
 
 #include "svo_ctx.h"
+#include "svo_mesh.h"  // (the triangles' check and gather, shared with svo_solid.hip)
 #include "svo_scan.h"  // (kThreads, kTile, block_min, min_of_blocks_kernel, the tile pass's kernels)
 
 namespace {
 
 constexpr uint64_t kMaxEntries = 1ull << 31;
-constexpr uint32_t kNoBad = 0xFFFFFFFFu;
+constexpr uint32_t kNoBad = kNoBadTriangle;
 // the words read back: the first bad triangle << 1 | (0: a vertex index, 1: a coordinate), the level's pair count in two halves
 enum Status { kStBad, kStCountLo, kStCountHi, kStWords };
 
@@ -52,20 +53,9 @@ __global__ __launch_bounds__(kThreads) void vox_setup_kernel(const uint32_t *__r
     const uint32_t t = blockIdx.x * kThreads + threadIdx.x;
     uint32_t bad = kNoBad;
     if (t < n_tris) {
-        uint32_t q[9];
-        bool index_ok = true, coord_ok = true;
-        for (uint32_t j = 0; j < 3; j++) {
-            const uint32_t v = tri[3ull * t + j];
-            const bool ok = v < n_vertices;
-            index_ok &= ok;
-            for (uint32_t a = 0; a < 3; a++) {
-                q[3 * j + a] = ok ? vq[3ull * v + a] : 0u;
-                coord_ok &= (q[3 * j + a] >> (depth + SVO_VOX_SUBBITS)) == 0;
-            }
-        }
-        if (!index_ok) bad = t << 1;
-        else if (!coord_ok) bad = t << 1 | 1u;
-        for (uint32_t k = 0; k < 9; k++) tv[9ull * t + k] = bad == kNoBad ? int32_t(2u * q[k] + 1u) : 1;
+        int32_t v[9];
+        bad = mesh_gather_triangle(vq, n_vertices, tri, t, depth, v);
+        for (uint32_t k = 0; k < 9; k++) tv[9ull * t + k] = v[k];
         pair_tri[t] = t;
         pair_cell[t] = 0;
     }
@@ -171,43 +161,16 @@ __global__ __launch_bounds__(kThreads) void vox_test_kernel(const int32_t *__res
     mask[i] = uint8_t(child_mask(v, cell_x(cell), cell_y(cell), cell_z(cell), hs));
 }
 
-// The tile pass's items (svo_scan.h): a level's pairs with their child masks.  The state is the masks of a thread's kPer
-// consecutive pairs; the mask array is padded to whole tiles, and what lies behind m is not counted.
-struct Pairs {
+// The tile pass's items: a level's pairs with their child masks, one byte per pair (svo_scan.h: FlagBytes).
+struct Pairs : FlagBytes {
     const uint32_t *tri;
     const uint64_t *cell;
-    const uint8_t *mask;
-    __device__ uint4 load(uint32_t i0, uint32_t m) const {
-        uint4 w = *reinterpret_cast<const uint4 *>(mask + i0);
-        const auto live = [&](uint32_t first) { return first >= m ? 0u : m - first >= 4 ? 0xFFFFFFFFu : (1u << 8 * (m - first)) - 1u; };
-        w.x &= live(i0);
-        w.y &= live(i0 + 4);
-        w.z &= live(i0 + 8);
-        w.w &= live(i0 + 12);
-        return w;
-    }
-    __device__ uint32_t count(const uint4 &w) const { return __popc(w.x) + __popc(w.y) + __popc(w.z) + __popc(w.w); }
-    __device__ uint32_t flags(const uint4 &w, uint32_t k) const {
-        const uint32_t q[4] = {w.x, w.y, w.z, w.w};
-        return q[k / 4] >> 8 * (k % 4);
-    }
 };
 
 // before tile_offsets_kernel, which scans the sums in place: their total in 64 bits
+static_assert(kStCountHi == kStCountLo + 1, "block_total64 writes the two halves side by side");
 __global__ __launch_bounds__(kTopThreads) void vox_total_kernel(const uint32_t *tile_sum, uint32_t n_tiles, uint32_t *status) {
-    __shared__ uint64_t s[kTopThreads];
-    uint64_t sum = 0;
-    for (uint32_t i = threadIdx.x; i < n_tiles; i += kTopThreads) sum += tile_sum[i];
-    s[threadIdx.x] = sum;
-    __syncthreads();
-    for (uint32_t off = kTopThreads / 2; off > 0; off >>= 1) {
-        if (threadIdx.x < off) s[threadIdx.x] += s[threadIdx.x + off];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) {
-        status[kStCountLo] = uint32_t(s[0]);
-        status[kStCountHi] = uint32_t(s[0] >> 32);
-    }
+    block_total64(tile_sum, n_tiles, status + kStCountLo);
 }
 
 struct VoxOut {
@@ -313,7 +276,7 @@ int svo_mesh_voxelize(svo_ctx *ctx, const svo_voxelize_params *p, const uint32_t
         const uint32_t n_tiles = svo_div_up(m, kTile), hs = depth - l + SVO_VOX_SUBBITS;
         if ((rc = svo_grow(ctx, size_t(n_tiles) * kTile, &s->mask))) return rc;
         if ((rc = svo_grow(ctx, (size_t)n_tiles, &s->tiles))) return rc;
-        const Pairs pairs{s->pair_tri[cur], s->pair_cell[cur], s->mask};
+        const Pairs pairs{{s->mask}, s->pair_tri[cur], s->pair_cell[cur]};
         vox_test_kernel<<<svo_div_up(m, kThreads), kThreads, 0, ctx->stream>>>(s->tv, s->pair_tri[cur], s->pair_cell[cur], m, hs, s->mask);
         tile_count_kernel<<<n_tiles, kThreads, 0, ctx->stream>>>(pairs, nullptr, m, s->tiles);
         vox_total_kernel<<<1, kTopThreads, 0, ctx->stream>>>(s->tiles, n_tiles, s->status.dev);
@@ -321,11 +284,7 @@ int svo_mesh_voxelize(svo_ctx *ctx, const svo_voxelize_params *p, const uint32_t
         HIP_TRY(ctx, hipGetLastError());
         if ((rc = s->status.read(ctx))) return rc;
         if (l == 1 && st[kStBad] != kNoBad)
-            return svo_fail(ctx, SVO_ERR_ARG, "triangle " + std::to_string(st[kStBad] >> 1) +
-                                                  (st[kStBad] & 1u ? " has a coordinate outside [0, 2^(depth + 6) = " +
-                                                                         std::to_string(1ull << (depth + SVO_VOX_SUBBITS)) + ")"
-                                                                   : " has a vertex index outside [0, n_vertices = " +
-                                                                         std::to_string(p->n_vertices) + ")"));
+            return svo_fail(ctx, SVO_ERR_ARG, mesh_bad_triangle(st[kStBad], depth, p->n_vertices));
         const uint64_t count = uint64_t(st[kStCountHi]) << 32 | st[kStCountLo];
         if (count > cap)
             return svo_fail(ctx, SVO_ERR_CAP, "level " + std::to_string(l) + " has " + std::to_string(count) + " (triangle, cell) pairs, " +

@@ -106,6 +106,12 @@ class Gpu:
         the call (svo_voxelize_timing)"""
         return self._timing(lib().svo_voxelize_timing, 5)
 
+    def solid_timing(self):
+        """ms of the last mesh.voxelize_solid call into the library that ran (its fill, or its count query when the mesh
+        has no interior): setup, the column levels, the sort, spans, emit (device events), host wall time of the call
+        (svo_solid_timing)"""
+        return self._timing(lib().svo_solid_timing, 6)
+
     def structure_timing(self):
         """ms of the last Render.column_tops / structure_sites / stamp_structures call into the library that ran: count
         (column tops: the kernel; sites and stamp: checks, sums and scan with the read-back), fill (device events), host

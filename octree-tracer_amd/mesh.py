@@ -5,6 +5,8 @@ svo_mesh_voxelize, the quantisation it works on, a minimal Wavefront reader and 
     voxelize           mesh -> device voxel list (coords, colours[, triangles]) for build_nodes, edit_nodes, CpuOctree.build
                        and World.build_world: one entry per (triangle, cell) that meet, triangles in order, cells in
                        Morton order; the highest triangle index colours a shared cell
+    voxelize_solid     closed mesh -> the device list of the cells inside it, or their y-spans: with
+                       voxelize's list behind it, a solid model with its surface's colours (Render.from_mesh(solid=True))
     quads_to_mesh      the exposed faces of a tree (Render.surface_quads) -> an indexed triangle mesh
     extract_surface    the two in one call: the inverse of voxelize
     load_obj, save_obj v / f lines of a Wavefront file, read and written
@@ -17,7 +19,7 @@ import numpy as np
 import torch
 
 from ._device import device_u32, voxel_list, wait_for_torch
-from ._lib import VoxelizeParams, lib
+from ._lib import SolidParams, VoxelizeParams, lib
 
 SUBBITS = 6  # SVO_VOX_SUBBITS: a cell is 64 quantised steps wide
 
@@ -71,6 +73,47 @@ def voxelize(gpu, vertices, triangles, depth, colours=None, colour=0xFFFFFF, wit
                                           out_tris.data_ptr() if with_triangles else None, C.byref(n)))
     gpu.sync()  # (the inputs may be released by the caller)
     return (coords, out_colours, out_tris) if with_triangles else (coords, out_colours)
+
+
+SOLID_RULES = {"evenodd": 0, "nonzero": 1}  # SVO_SOLID_EVENODD, SVO_SOLID_NONZERO
+SOLID_SPANS = 2  # SVO_SOLID_SPANS
+
+
+def voxelize_solid(gpu, vertices, triangles, depth, rule="evenodd", spans=False, with_open=False, quantized=False, max_pairs=None):
+    """The cells inside a closed triangle mesh, on the GPU and exactly (svo_mesh_voxelize_solid): a cell is
+    inside when the triangles above its centre are odd in number (rule "evenodd") or their orientations do not cancel
+    ("nonzero"); ties are decided as for a centre moved by an infinitesimal generic offset, so the order of the triangles
+    never matters.  vertices and triangles as voxelize takes them.  Returns a device int32 tensor: (N, 3) cells (x, y, z)
+    ascending in (x, z, y), the list build_nodes and edit_nodes take, or with spans=True (N, 4) runs (x, z, y0, y1) of
+    inside cells [y0, y1) of a column, ascending in (x, z, y0); with with_open=True a pair of it and the number of open
+    columns: columns where the mesh is not closed (0 for a watertight mesh).  A count query and then a fill, like voxelize.
+    max_pairs caps the (triangle, column square) pairs of a level (None: 2^27).  Raises SvoError for a bad vertex index or
+    coordinate, for a level over max_pairs and for 2^31 entries or more."""
+    if rule not in SOLID_RULES:
+        raise ValueError(f"rule must be one of {sorted(SOLID_RULES)} (got {rule!r})")
+    dev = gpu.torch_device
+    depth = int(depth)
+    vq = device_u32(vertices if quantized else quantize_vertices(vertices, depth), dev, clamp=True, what="vertices")
+    if vq.dim() != 2 or vq.shape[1] != 3:
+        raise ValueError(f"vertices must be (V, 3), got {tuple(vq.shape)}")
+    tri, _, n_tris, tri_ptr, _ = voxel_list(gpu, triangles, None, noun="triangles", what="triangles", rows="T")
+    p = SolidParams()
+    p.depth = max(0, depth)
+    p.flags = SOLID_RULES[rule] | (SOLID_SPANS if spans else 0)
+    p.n_vertices = vq.shape[0]
+    p.max_pairs = 0 if max_pairs is None else int(max_pairs)
+    args = (vq.data_ptr() if vq.numel() else None, tri_ptr, n_tris)
+    n, n_open = C.c_uint64(), C.c_uint64()
+    wait_for_torch(gpu)
+    gpu.check(lib().svo_mesh_voxelize_solid(gpu._h, C.byref(p), *args, None, C.byref(n), C.byref(n_open)))  # the count
+    count = n.value
+    out = torch.empty((count, 4 if spans else 3), dtype=torch.int32, device=dev)
+    if count:
+        p.max_out = count
+        wait_for_torch(gpu)
+        gpu.check(lib().svo_mesh_voxelize_solid(gpu._h, C.byref(p), *args, out.data_ptr(), C.byref(n), C.byref(n_open)))
+    gpu.sync()  # (the inputs may be released by the caller)
+    return (out, n_open.value) if with_open else out
 
 
 def load_obj(path):

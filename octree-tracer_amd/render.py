@@ -98,19 +98,31 @@ class Render:
         return self
 
     @classmethod
-    def from_mesh(cls, gpu, size, vertices, triangles, depth, colours=None, capacity=None):
+    def from_mesh(cls, gpu, size, vertices, triangles, depth, colours=None, capacity=None, solid=False, fill_colour=None,
+                  rule="evenodd", allow_open=False):
         """A Render whose tree is a triangle mesh voxelised and built on the GPU (build_nodes_mesh)."""
         self = cls(gpu, size, np.full(8, EMPTY_WORD, dtype=np.uint32), capacity)
-        self.build_nodes_mesh(vertices, triangles, depth, colours)
+        self.build_nodes_mesh(vertices, triangles, depth, colours, solid=solid, fill_colour=fill_colour, rule=rule, allow_open=allow_open)
         return self
 
-    def build_nodes_mesh(self, vertices, triangles, depth, colours=None, colour=0xFFFFFF, max_words=None, quantized=False):
+    def build_nodes_mesh(self, vertices, triangles, depth, colours=None, colour=0xFFFFFF, max_words=None, quantized=False,
+                         solid=False, fill_colour=None, rule="evenodd", allow_open=False):
         """Voxelise a triangle mesh on the GPU (mesh.voxelize) and build the tree of its cells into the node
         buffer from word 0 (build_nodes).  vertices: (V, 3) floats in [-1, 1), or with quantized=True the integers of
         mesh.quantize_vertices; triangles: (T, 3) vertex indices; colours: T values 0x00RRGGBB or None (every triangle
-        `colour`).  The highest triangle index colours a cell that several triangles touch.  Returns the word count."""
-        from .mesh import voxelize
+        `colour`).  The highest triangle index colours a cell that several triangles touch.  solid: the cells inside the
+        mesh (mesh.voxelize_solid with `rule`) in fill_colour (None: `colour`) stand in front of the surface's
+        list, so the surface keeps its triangles' colours (the last entry in input order wins); a mesh with open columns
+        raises ValueError unless allow_open.  Returns the word count."""
+        from .mesh import voxelize, voxelize_solid
         coords, cell_colours = voxelize(self.gpu, vertices, triangles, depth, colours, colour, quantized=quantized)
+        if solid:
+            inner, n_open = voxelize_solid(self.gpu, vertices, triangles, depth, rule, with_open=True, quantized=quantized)
+            if n_open and not allow_open:
+                raise ValueError(f"the mesh is not closed: {n_open} columns are open (allow_open=True fills them by the rule all the same)")
+            fill = int(colour if fill_colour is None else fill_colour) & 0xFFFFFF
+            coords = torch.cat([inner, coords])
+            cell_colours = torch.cat([torch.full((len(inner),), fill, dtype=torch.int32, device=inner.device), cell_colours])
         return self.build_nodes(coords, depth, cell_colours, max_words=max_words)
 
     def build_nodes(self, coords, depth, colours=None, colour=0xFFFFFF, max_words=None):
