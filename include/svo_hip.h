@@ -400,8 +400,8 @@ int svo_build_timing(svo_ctx *ctx, float ms_out[SVO_BUILD_TIMES]);
  * and nothing at or behind *n_words_out is touched.  The same words on every run and for any order of distinct cells.
  * SVO_ERR_STATE, nothing written, when a cell is an interior node at `depth` (the tree is finer there than the edit; the
  * host's put never ends on that input): svo_last_error names the input index of the first such voxel in key order.
- * Replacing a subtree by a coarser leaf and reusing free groups are not done; groups that became all-empty or were cut
- * off are pruned and dropped afterwards, by svo_nodes_compact.
+ * Replacing a subtree by a coarser leaf (svo_nodes_edit_region does that) and reusing free groups are not done; groups that
+ * became all-empty or were cut off are pruned and dropped afterwards, by svo_nodes_compact.
  * The other errors leave the node buffer untouched too, all decided by a read-only plan pass before any write:
  * SVO_ERR_ARG for a bad depth, n >= 2^31, NULL xyz with n > 0, a coordinate outside [0, 2^depth) (checked on the device),
  * or n_words not a positive multiple of 8 or above the capacity; SVO_ERR_CAP when the exact new length exceeds max_words,
@@ -423,6 +423,75 @@ int svo_nodes_edit(svo_ctx *ctx, const uint32_t *xyz, const uint32_t *colours, s
  * link (device events; waits for the link), [5] host wall time of the call.  All 0 after an empty edit. */
 #define SVO_EDIT_TIMES 6
 int svo_edit_timing(svo_ctx *ctx, float ms_out[SVO_EDIT_TIMES]);
+
+/* ---- a tree in the node buffer edited by shapes: boxes and balls filled, carved and painted ----
+ * Edits the first n_words words of the node buffer in place, top-down, touching only the tree along the shapes' surfaces.
+ * Per cell c of the `depth` grid the call means this:
+ *     v = what svo_nodes_sample returns at c
+ *     for each shape, in input order:
+ *         if c is inside the shape and (v == 0 ? mode & SVO_REGION_EMPTY : mode & SVO_REGION_VOXELS):  v = colour & 0xFFFFFF
+ * and afterwards the tree samples to the final v in every cell.  Inside a box: lo <= c < hi on every axis (half-open, lo <
+ * hi <= 2^depth).  Inside a ball: the cell's centre lies within the radius; with the centre and the radius given in HALF
+ * cells that is sum over the axes of (2 c + 1 - centre2)^2 <= radius2^2, in 64-bit integers (a term is below 2^46): no float
+ * anywhere.  A ball of radius 0 on an odd centre is one cell, on an even centre none.
+ * The words are deterministic, the same bytes on every run (no atomics: the order is the contract), by this rule.  A word of
+ * level l with cell q covers the cells [q << s, (q + 1) << s), s = depth - l.  Against that cube a shape is FULL (every cell
+ * inside), OUT (none) or PART; for a ball the class is exact: per axis the centres run over the odd integers a = 2 (q << s)
+ * + 1 .. b = 2 ((q + 1) << s) - 1, the farthest is at max(|a - C|, |b - C|), the nearest at a - C (C < a), C - b (C > b), else
+ * 0 (C odd) or 1 (C even); FULL iff sum far^2 <= r^2, OUT iff sum near^2 > r^2.  At l == depth nothing is PART.
+ * The tree is processed level by level from the root group; the frontier of level l + 1 is the eight children, by child
+ * index, of every word of level l that was opened or split, those taken in frontier order.  For one word:
+ *     every shape OUT:  the word and everything below it keep all 32 bits
+ *     otherwise j = the last shape that is FULL with mode SVO_REGION_SET, or none, and
+ *     a leaf of value v0 (a voxel, the empty word, or a virtual child of a split):
+ *         v = colour_j (v0 without a j); for each shape k behind j, in order: FULL: apply it to v as above; PART: when
+ *         applying it would change v, the leaf is SPLIT.  Not split: v != v0 writes the leaf word of v, counter 0; v == v0
+ *         leaves the word untouched.  Split: a new group of eight leaf words OF v0, counter 0, is made, the word becomes the
+ *         pointer to it, and the eight virtual children join the next frontier.  THE COLOUR IS CARRIED DOWN -- unlike
+ *         svo_nodes_edit, which splits a coarse leaf into empty children
+ *     an interior word:  with a j and every later shape OUT it COLLAPSES to the leaf word of colour_j (its subtree is cut off,
+ *         for svo_nodes_compact to drop); otherwise it is opened.  Opening at l == depth is refused: SVO_ERR_STATE, nothing
+ *         written, svo_last_error names the last shape that touches the cell and the cell
+ * New groups are appended by level and within a level in frontier order: the g-th split gets the group n_words + 8 g, and
+ * *n_words_out = n_words + 8 * splits.  Nothing at or behind *n_words_out is touched.  A second identical call on the result
+ * writes nothing and appends nothing.  Merging equal siblings, reusing free groups and other shapes are not done.
+ * `shapes` is HOST memory, read before the call returns.  Every error is decided by the read-only plan before any write.
+ * SVO_ERR_ARG: NULL p or n_words_out, NULL shapes with n_shapes > 0, n_shapes > SVO_REGION_MAX_SHAPES, depth outside 1..21, an
+ * unknown kind, a mode outside 1..3, a box with lo >= hi or hi > 2^depth on an axis, a ball with a centre coordinate above
+ * 2^(depth + 1) or a radius above 2^23 half cells, n_words not a positive multiple of 8 or above the capacity.  SVO_ERR_STATE: no
+ * node buffer; a device adaptive state attached to the context (subtrees are cut off under its positions); the "malformed
+ * tree: ..." causes with svo_nodes_compact's wording, on the words that the shapes make the call open (an interior pointer
+ * that is not a multiple of 8 or with pointer + 8 > n_words, a group reached twice); the refusal above.  SVO_ERR_CAP when the exact new length exceeds
+ * max_words, the capacity or 2^27.  n_shapes == 0 succeeds and returns n_words.
+ * Runs on the ctx stream; blocks once per level, to read back the next frontier's size and the level's split count, and once
+ * more for the status.  The fill and the writes are enqueued (a following svo_render on the stream sees the edit), ordered and
+ * recorded like svo_nodes_write, so every context sharing the buffer rebuilds its top table and schedule. */
+#define SVO_REGION_BOX  0u
+#define SVO_REGION_BALL 1u
+#define SVO_REGION_EMPTY  1u   /* the shape applies to cells that are empty */
+#define SVO_REGION_VOXELS 2u   /* ... to cells that hold a voxel */
+#define SVO_REGION_SET    3u   /* both: fill (colour != 0) or carve (colour 0) */
+#define SVO_REGION_MAX_SHAPES 1024u
+typedef struct svo_region_shape {   /* 32 bytes, HOST memory */
+    uint16_t kind;    /* SVO_REGION_BOX or SVO_REGION_BALL */
+    uint16_t mode;    /* 1, 2 or 3 */
+    uint32_t colour;  /* 0x00RRGGBB, the low 24 bits count; 0 = empty */
+    uint32_t a[3];    /* box: lo (cells);  ball: the centre in HALF cells, [0, 2^(depth+1)] */
+    uint32_t b[3];    /* box: hi (cells);  ball: b[0] = the radius in half cells, <= 2^23, b[1] = b[2] = 0 */
+} svo_region_shape;
+typedef struct svo_region_params {
+    uint32_t depth;      /* 1..21: the grid the shapes are given on */
+    uint32_t reserved;
+    uint64_t n_words;    /* the tree's current length: a multiple of 8, at least 8 */
+    uint64_t max_words;  /* 0 = the node buffer's capacity; never above SVO_VOXEL_OFFSET */
+} svo_region_params;
+int svo_nodes_edit_region(svo_ctx *ctx, const svo_region_shape *shapes, size_t n_shapes, const svo_region_params *p,
+                          uint64_t *n_words_out);
+/* Times (ms) of the last shape edit: [0] plan (with its per-level read-backs), [1] status, [2] fill, [3] write (device
+ * events; waits for the write), [4] host wall time of the call.  All 0 after a call without shapes; a refused call leaves
+ * the times of the last one that ran. */
+#define SVO_REGION_TIMES 5
+int svo_region_timing(svo_ctx *ctx, float ms_out[SVO_REGION_TIMES]);
 
 /* ---- the tree in the node buffer compacted in place ----
  * Reads the first n_words words of the node buffer as a tree rooted at group 0.  E = SVO_VOXEL_OFFSET << 4 is the empty

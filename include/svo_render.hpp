@@ -292,6 +292,21 @@ class Render {  // render.rs:3-285
         gpu_.poll_wait();  // the inputs may go away
         return new_words;
     }
+    // the first n_words words of the node buffer edited by n_shapes boxes and balls (host memory), in place and in input
+    // order (svo_nodes_edit_region): a cell inside a shape whose mode names its state takes the shape's
+    // colour, 0 empties it; returns the new length.  Throws, with nothing written, where the tree is finer than depth
+    // under a shape that does not replace it.
+    uint64_t edit_region(uint64_t n_words, const svo_region_shape *shapes, size_t n_shapes, uint32_t depth, uint64_t max_words = 0) {
+        if (depth > declared_depth_) {
+            gpu_.set_option(SVO_OPT_TREE_DEPTH, depth);
+            declared_depth_ = depth;
+        }
+        const svo_region_params p{depth, 0u, n_words, max_words};
+        uint64_t new_words = 0;
+        gpu_.check(svo_nodes_edit_region(gpu_.ctx(), shapes, n_shapes, &p, &new_words));
+        gpu_.poll_wait();
+        return new_words;
+    }
     // the first n_words words of the node buffer compacted in place (svo_nodes_compact): unreachable groups
     // dropped, with `prune` also the groups that hold nothing, the rest in the builder's breadth-first order; returns the
     // new length.  perm_dev (device, n_words u32, or null): perm[new word] = old word.  Throws, with nothing written, for

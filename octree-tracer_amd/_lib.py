@@ -66,6 +66,27 @@ class EditParams(C.Structure):
     ]
 
 
+class RegionShape(C.Structure):
+    """svo_region_shape: one box or ball of a shape edit, 32 bytes (include/svo_hip.h)."""
+    _fields_ = [
+        ("kind", C.c_uint16),
+        ("mode", C.c_uint16),
+        ("colour", C.c_uint32),
+        ("a", C.c_uint32 * 3),
+        ("b", C.c_uint32 * 3),
+    ]
+
+
+class RegionParams(C.Structure):
+    """svo_region_params: the tree in the node buffer edited by shapes (include/svo_hip.h)."""
+    _fields_ = [
+        ("depth", C.c_uint32),
+        ("reserved", C.c_uint32),
+        ("n_words", C.c_uint64),
+        ("max_words", C.c_uint64),
+    ]
+
+
 class CompactParams(C.Structure):
     """svo_compact_params: the tree in the node buffer compacted in place (include/svo_hip.h)."""
     _fields_ = [
@@ -246,6 +267,8 @@ DEVICE_SIGNATURES = {
     "svo_world_build_timing": (C.c_int, (vp, fp)),
     "svo_nodes_edit": (C.c_int, (vp, vp, vp, sz, C.POINTER(EditParams), C.POINTER(u64))),
     "svo_edit_timing": (C.c_int, (vp, fp)),
+    "svo_nodes_edit_region": (C.c_int, (vp, C.POINTER(RegionShape), sz, C.POINTER(RegionParams), C.POINTER(u64))),
+    "svo_region_timing": (C.c_int, (vp, fp)),
     "svo_nodes_compact": (C.c_int, (vp, C.POINTER(CompactParams), vp, C.POINTER(u64))),
     "svo_compact_timing": (C.c_int, (vp, fp)),
     "svo_nodes_list_voxels": (C.c_int, (vp, C.POINTER(ListParams), vp, vp, vp, C.POINTER(u64))),

@@ -1,6 +1,6 @@
 // svo_ctx.h -- the device context behind the opaque `svo_ctx` of include/svo_hip.h, and the host helpers of the files that
 // use it: svo_abi.cpp (trace / scan dispatch), svo_comm.cpp (RCCL frame gather) and the GPU tree passes (svo_proc.hip,
-// svo_build.hip, svo_edit.hip, svo_compact.hip, svo_list.hip, svo_sample.hip, svo_voxelize.hip, svo_solid.hip,
+// svo_build.hip, svo_edit.hip, svo_region.hip, svo_compact.hip, svo_list.hip, svo_sample.hip, svo_voxelize.hip, svo_solid.hip,
 // svo_structure.hip, svo_surface.hip, svo_adapt.hip).  One rule of ownership for the context, the node store and every
 // pass's state: a member owns what it holds, as svo_dev / svo_pinned (an allocation and its size), svo_events (events) or
 // svo_stream (a stream).  The passes
@@ -142,6 +142,7 @@ struct svo_build_state;
 struct svo_adapt_state;
 struct svo_edit_state;
 struct svo_compact_state;
+struct svo_region_state;
 struct svo_list_state;
 struct svo_sample_state;
 struct svo_voxelize_state;
@@ -253,6 +254,7 @@ struct svo_ctx {
     svo_workspace<svo_adapt_state> adapt{nullptr, nullptr};  // device adaptive state (svo_adapt.hip)
     svo_workspace<svo_edit_state> edit{nullptr, nullptr};    // in-place edits' workspace (svo_edit.hip)
     svo_workspace<svo_compact_state> compact{nullptr, nullptr};  // compaction's workspace (svo_compact.hip)
+    svo_workspace<svo_region_state> region{nullptr, nullptr};  // shape edits' workspace (svo_region.hip)
     svo_workspace<svo_list_state> list{nullptr, nullptr};  // voxel listing's workspace (svo_list.hip)
     svo_workspace<svo_sample_state> sample{nullptr, nullptr};  // sampling's events and times (svo_sample.hip)
     svo_workspace<svo_voxelize_state> voxelize{nullptr, nullptr};  // mesh voxeliser's workspace (svo_voxelize.hip)

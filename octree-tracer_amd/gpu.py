@@ -79,6 +79,11 @@ class Gpu:
         time of the call (svo_edit_timing)"""
         return self._timing(lib().svo_edit_timing, 6)
 
+    def region_timing(self):
+        """ms of the last Render.edit_region: plan (with its per-level read-backs), status, fill, write (device events),
+        host wall time of the call (svo_region_timing)"""
+        return self._timing(lib().svo_region_timing, 5)
+
     def compact_timing(self):
         """ms of the last Render.compact_nodes: discover, check, prune, emit, copy back (device events), host wall time
         of the call (svo_compact_timing)"""

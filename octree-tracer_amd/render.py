@@ -6,7 +6,7 @@ import torch
 
 from . import sharding
 from ._device import device_u32, voxel_list, wait_for_torch
-from ._lib import BuildParams, CompactParams, EditParams, ListParams, SampleParams, SitesParams, StampParams, SurfaceParams, TopsParams, Uniforms, lib
+from ._lib import BuildParams, CompactParams, EditParams, ListParams, RegionParams, SampleParams, SitesParams, StampParams, SurfaceParams, TopsParams, Uniforms, lib
 from .camera import camera_matrices
 
 F_PAUSE_ADAPTIVE, F_SHOW_STEPS, F_SHOW_HITS, F_SHADOWS, F_MISC_BOOL = 1, 2, 4, 8, 16
@@ -155,6 +155,29 @@ class Render:
         wait_for_torch(self.gpu)
         self.gpu.check(lib().svo_nodes_edit(self.gpu._h, xyz_ptr, col_ptr, n, C.byref(p), C.byref(out)))
         self.gpu.sync()  # (the inputs may be released by the caller)
+        self.node_length = out.value
+        return out.value
+
+    def edit_region(self, shapes, depth=None, max_words=None):
+        """Fill, carve and paint the tree that is in the node buffer by shapes, in place (svo_nodes_edit_region, DESIGN.md
+        25).  shapes: region.box(...) and region.ball(...) in the order they apply, at most 1 024; per cell of the `depth`
+        grid a shape inside which the cell lies, and whose mode names the cell's state, sets the cell to its colour (0
+        empties it).  A node wholly inside a SET shape becomes one leaf, a node wholly outside is not looked at, a coarse
+        leaf on a shape's surface is split and keeps its colour in the children.  Boxes are clipped to the grid.  Where the
+        tree is finer than `depth` under a shape that does not replace it, SvoError is raised and nothing is written.
+        depth=None: the depth declared for this tree.  Returns the new length (node_length)."""
+        from .region import pack
+        depth = int(self.gpu.tree_depth if depth is None else depth)
+        arr, n = pack(shapes, depth)
+        self.gpu.declare_depth(depth)
+        p = RegionParams()
+        p.depth = max(0, depth)
+        p.n_words = int(self.node_length)
+        p.max_words = int(max_words or 0)
+        out = C.c_uint64()
+        wait_for_torch(self.gpu)
+        self.gpu.check(lib().svo_nodes_edit_region(self.gpu._h, arr, n, C.byref(p), C.byref(out)))
+        self.gpu.sync()
         self.node_length = out.value
         return out.value
 
