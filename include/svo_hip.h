@@ -529,6 +529,61 @@ int svo_nodes_compact(svo_ctx *ctx, const svo_compact_params *p, uint32_t *perm_
 #define SVO_COMPACT_TIMES 6
 int svo_compact_timing(svo_ctx *ctx, float ms_out[SVO_COMPACT_TIMES]);
 
+/* ---- the tree in the node buffer simplified: uniform subtrees merged, the tree cut to a level by mip ----
+ * Reads the first n_words words of the node buffer as a tree rooted at group 0.  Levels are svo_nodes_list_voxels': the root
+ * group's words are level 1, the words of the group an interior word of level l points at are level l + 1.  f = word >> 4
+ * is a word's field: the word is interior when f < SVO_VOXEL_OFFSET, otherwise a leaf of value f - SVO_VOXEL_OFFSET.  The
+ * low 4 bits (hit counters) never take part in a comparison.  Two rewrites apply, in this order, then the layout:
+ * 1. SVO_SIMPLIFY_CUT (lossy).  S(W) of a leaf is its value.  S(W) of an interior word pointing at group G: with s_c =
+ *    S(G[c]) and n the number of c with s_c != 0, S = 0 when n == 0, otherwise per byte b in {0, 8, 16} ch_b = max(1, (sum
+ *    over the c with s_c != 0 of (s_c >> b) & 0xFF) / n) in integer division and S = ch_0 | ch_8 << 8 | ch_16 << 16: on 24-bit
+ *    colours the mip colour of svo_world_generate_mip_tree, applied bottom-up to averaged children, except that a subtree
+ *    without a voxel gives 0.  Every interior word at level cut_level becomes the leaf word (SVO_VOXEL_OFFSET + S(W)) << 4,
+ *    counter 0: a cube becomes solid when it holds any voxel.  Leaves at or above cut_level are untouched, and a tree no
+ *    deeper than cut_level is unchanged.
+ * 2. SVO_SIMPLIFY_MERGE (lossless), on the tree step 1 leaves.  U(W) of a leaf is its field f, all 28 bits (values above
+ *    24 bits merge only with themselves).  U(W) of an interior word at level l pointing at G is f when l >= min_level and
+ *    all eight U(G[c]) are defined and equal f, and undefined otherwise.  Every interior word with U defined becomes f << 4,
+ *    counter 0.  The root group has no parent word and always stays.  With f the empty field this is
+ *    SVO_COMPACT_PRUNE_EMPTY's rule; every cell of the tree samples (svo_nodes_sample) to what it sampled before.
+ * 3. The result is svo_nodes_compact with flags == 0 of the rewritten words: the groups still reachable breadth-first, each
+ *    level in the order of its parents, pointers rewritten, every kept word keeping its 4 counter bits.  perm_out_dev
+ *    (DEVICE, at least n_words u32, or NULL): perm[new word] = old word for [0, *n_words_out), also for a word that was
+ *    rewritten into a leaf.
+ * out_dev == NULL writes in place, as the compaction does: afterwards the words [*n_words_out, n_words) hold the empty word,
+ * nothing at or behind n_words is touched, and the write is ordered and recorded like svo_nodes_write.  out_dev != NULL
+ * (DEVICE, out_cap words) gets the words [0, *n_words_out): the node buffer is only read, no write is recorded, and an
+ * attached adaptive state is no obstacle -- a level-of-detail copy that another context takes with svo_nodes_bind_device
+ * or svo_nodes_write.  *n_words_out <= n_words always, and the result is the same bytes on every run and for every layout
+ * of the same tree (no atomics: the order is the contract).
+ * THE TRAP: svo_nodes_edit splits a coarse leaf into EMPTY children (the reference's put_in_voxel), so voxels put into a
+ * merged solid by cell list lose the solid's colour around the edit.  svo_nodes_edit_region carries the colour down, and
+ * min_level bounds how coarse the merge goes.
+ * Errors are decided before any write and leave the node buffer, out_dev and perm_out_dev as they were; of several causes
+ * the first in this order is reported: NULL p or n_words_out (SVO_ERR_ARG); flags 0 or with unknown bits, cut_level outside
+ * 1..31 with CUT or not 0 without, min_level not 0 without MERGE, reserved not 0 (SVO_ERR_ARG); no node buffer
+ * (SVO_ERR_STATE); a device adaptive state attached, for an in-place call (SVO_ERR_STATE); n_words not a positive multiple
+ * of 8 or above the capacity (SVO_ERR_ARG); the "malformed tree: ..." causes with svo_nodes_compact's wording
+ * (SVO_ERR_STATE); SVO_ERR_CAP, with the exact length in svo_last_error, when *n_words_out > out_cap for an out-of-place call.
+ * Runs on the ctx stream; blocks once per level of the tree (the discovery) and once before the emit. */
+#define SVO_SIMPLIFY_MERGE 1u   /* lossless: an interior word whose whole subtree holds one leaf value becomes that leaf */
+#define SVO_SIMPLIFY_CUT   2u   /* lossy: every interior word at level cut_level becomes a leaf of its subtree's mip colour */
+typedef struct svo_simplify_params {
+    uint32_t flags;       /* 1, 2 or 3; 0 and unknown bits: SVO_ERR_ARG (flags 0 is svo_nodes_compact's job) */
+    uint32_t cut_level;   /* with CUT: 1..31; without: must be 0 */
+    uint32_t min_level;   /* MERGE makes no leaf at a level below this; 0 or 1 = no limit; without MERGE must be 0 */
+    uint32_t reserved;    /* 0 */
+    uint64_t n_words;     /* the tree: words [0, n_words) of the node buffer, rooted at group 0 */
+    uint64_t out_cap;     /* room in out_dev, in words; ignored when out_dev is NULL */
+} svo_simplify_params;
+int svo_nodes_simplify(svo_ctx *ctx, const svo_simplify_params *p, uint32_t *out_dev /* may be null */,
+                       uint32_t *perm_out_dev /* may be null */, uint64_t *n_words_out);
+/* Times (ms) of the last simplification: [0] discover (with its per-level read-backs), [1] check, [2] reduce, [3] emit,
+ * [4] copy back (device events; waits for it; next to nothing out of place), [5] host wall time of the call.  A refused
+ * call leaves the times of the last simplification that ran. */
+#define SVO_SIMPLIFY_TIMES 6   /* discover, check, reduce, emit, copy back, host wall */
+int svo_simplify_timing(svo_ctx *ctx, float ms_out[SVO_SIMPLIFY_TIMES]);
+
 /* ---- the voxels of the tree in the node buffer listed on the device ----
  * The inverse of svo_nodes_build.  Reads the first n_words words of the node buffer as a tree rooted at group 0.
  * E = SVO_VOXEL_OFFSET << 4; a word is interior when word >> 4 < SVO_VOXEL_OFFSET and a *voxel* when word >> 4 >

@@ -318,6 +318,23 @@ class Render {  // render.rs:3-285
         gpu_.poll_wait();
         return new_words;
     }
+    // the first n_words words of the node buffer simplified (svo_nodes_simplify): with `merge` an interior
+    // word whose whole subtree holds one leaf value becomes that leaf (lossless; no merged leaf above min_level), with
+    // cut_level != 0 every interior word of that level becomes a leaf of its subtree's mip colour; the rest in the
+    // compaction's breadth-first order; returns the new length.  out_dev null: in place, as compact_nodes; otherwise the
+    // new tree goes to out_dev (device, out_cap words) and the node buffer is only read.  perm_dev (device, n_words u32,
+    // or null): perm[new word] = old word.  Throws, with nothing written, for a malformed tree, for an in-place call with
+    // a device adaptive state attached, or for more words than out_cap.  Mind that edit_nodes splits a coarse leaf into
+    // EMPTY children: voxels put into a merged solid by cell list lose its colour around them; edit_region carries it down.
+    uint64_t simplify_nodes(uint64_t n_words, bool merge = true, uint32_t cut_level = 0, uint32_t min_level = 0,
+                            uint32_t *out_dev = nullptr, uint64_t out_cap = 0, uint32_t *perm_dev = nullptr) {
+        const svo_simplify_params p{(merge ? SVO_SIMPLIFY_MERGE : 0u) | (cut_level ? SVO_SIMPLIFY_CUT : 0u), cut_level, min_level, 0u,
+                                    n_words, out_cap};
+        uint64_t new_words = 0;
+        gpu_.check(svo_nodes_simplify(gpu_.ctx(), &p, out_dev, perm_dev, &new_words));
+        gpu_.poll_wait();
+        return new_words;
+    }
     // the voxels of the tree in the first n_words words of the node buffer listed on the GPU (svo_nodes_list_voxels,
     // DESIGN.md 18), the inverse of build_nodes: xyz_dev (3 * max_voxels u32), values_dev (max_voxels) and levels_dev
     // (max_voxels, or null) are DEVICE pointers; entries in ascending Morton order on the `depth` grid, with `expand` a

@@ -96,6 +96,18 @@ class CompactParams(C.Structure):
     ]
 
 
+class SimplifyParams(C.Structure):
+    """svo_simplify_params: the tree in the node buffer simplified, in place or into a copy (include/svo_hip.h)."""
+    _fields_ = [
+        ("flags", C.c_uint32),
+        ("cut_level", C.c_uint32),
+        ("min_level", C.c_uint32),
+        ("reserved", C.c_uint32),
+        ("n_words", C.c_uint64),
+        ("out_cap", C.c_uint64),
+    ]
+
+
 class ListParams(C.Structure):
     """svo_list_params: the voxels of the tree in the node buffer listed on the device (include/svo_hip.h)."""
     _fields_ = [
@@ -271,6 +283,8 @@ DEVICE_SIGNATURES = {
     "svo_region_timing": (C.c_int, (vp, fp)),
     "svo_nodes_compact": (C.c_int, (vp, C.POINTER(CompactParams), vp, C.POINTER(u64))),
     "svo_compact_timing": (C.c_int, (vp, fp)),
+    "svo_nodes_simplify": (C.c_int, (vp, C.POINTER(SimplifyParams), vp, vp, C.POINTER(u64))),
+    "svo_simplify_timing": (C.c_int, (vp, fp)),
     "svo_nodes_list_voxels": (C.c_int, (vp, C.POINTER(ListParams), vp, vp, vp, C.POINTER(u64))),
     "svo_list_timing": (C.c_int, (vp, fp)),
     "svo_nodes_list_surface": (C.c_int, (vp, C.POINTER(SurfaceParams), vp, vp, vp, vp, C.POINTER(u64))),

@@ -1,6 +1,6 @@
 // svo_ctx.h -- the device context behind the opaque `svo_ctx` of include/svo_hip.h, and the host helpers of the files that
 // use it: svo_abi.cpp (trace / scan dispatch), svo_comm.cpp (RCCL frame gather) and the GPU tree passes (svo_proc.hip,
-// svo_build.hip, svo_edit.hip, svo_region.hip, svo_compact.hip, svo_list.hip, svo_sample.hip, svo_voxelize.hip, svo_solid.hip,
+// svo_build.hip, svo_edit.hip, svo_region.hip, svo_compact.hip, svo_simplify.hip, svo_list.hip, svo_sample.hip, svo_voxelize.hip, svo_solid.hip,
 // svo_structure.hip, svo_surface.hip, svo_adapt.hip).  One rule of ownership for the context, the node store and every
 // pass's state: a member owns what it holds, as svo_dev / svo_pinned (an allocation and its size), svo_events (events) or
 // svo_stream (a stream).  The passes
@@ -142,6 +142,7 @@ struct svo_build_state;
 struct svo_adapt_state;
 struct svo_edit_state;
 struct svo_compact_state;
+struct svo_simplify_state;
 struct svo_region_state;
 struct svo_list_state;
 struct svo_sample_state;
@@ -254,6 +255,7 @@ struct svo_ctx {
     svo_workspace<svo_adapt_state> adapt{nullptr, nullptr};  // device adaptive state (svo_adapt.hip)
     svo_workspace<svo_edit_state> edit{nullptr, nullptr};    // in-place edits' workspace (svo_edit.hip)
     svo_workspace<svo_compact_state> compact{nullptr, nullptr};  // compaction's workspace (svo_compact.hip)
+    svo_workspace<svo_simplify_state> simplify{nullptr, nullptr};  // simplification's workspace (svo_simplify.hip)
     svo_workspace<svo_region_state> region{nullptr, nullptr};  // shape edits' workspace (svo_region.hip)
     svo_workspace<svo_list_state> list{nullptr, nullptr};  // voxel listing's workspace (svo_list.hip)
     svo_workspace<svo_sample_state> sample{nullptr, nullptr};  // sampling's events and times (svo_sample.hip)
@@ -448,7 +450,7 @@ int svo_build_list_leaves(svo_ctx *ctx, const uint32_t *xyz, const uint32_t *col
                           uint32_t default_colour, svo_build_leaves *out);
 // svo_compact.hip
 // The discovery of the tree in the first n_words words of the node buffer, for the
-// compaction and the voxel listing (svo_list.hip), on the ctx stream.  The caller owns the workspace: order, first_child,
+// compaction, the simplification (svo_simplify.hip) and the voxel listing (svo_list.hip), on the ctx stream.  The caller owns the workspace: order, first_child,
 // new_of and scan of n_words / 8 u32 each, and status words that it has zeroed on the stream; the first SVO_WALK_STATUS
 // of them are the discovery's, and all of them come back once per level.  Afterwards
 // order[level_off[l], level_off[l + 1]) holds the old group starts of level l + 1 in the order of their parents,

@@ -1,5 +1,5 @@
 // svo_group.h -- the constants of the tree passes, and what those that walk the tree in the node buffer
-// (svo_compact.hip, svo_list.hip) share on the device: 8 lanes per group, one word per lane, so a wave64 handles 8
+// (svo_compact.hip, svo_simplify.hip, svo_list.hip) share on the device: 8 lanes per group, one word per lane, so a wave64 handles 8
 // groups, a group is one 32-byte read and its interior mask is its byte of the wave's ballot.  Everything sits in an
 // anonymous namespace, like svo_scan.h, which includes this header.
 #pragma once

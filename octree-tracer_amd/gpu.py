@@ -89,6 +89,11 @@ class Gpu:
         of the call (svo_compact_timing)"""
         return self._timing(lib().svo_compact_timing, 6)
 
+    def simplify_timing(self):
+        """ms of the last Render.simplify_nodes: discover, check, reduce, emit, copy back (device events), host wall time
+        of the call (svo_simplify_timing)"""
+        return self._timing(lib().svo_simplify_timing, 6)
+
     def list_timing(self):
         """ms of the last Render.list_voxels call into the library (its fill, or its count query when the list was empty
         or refused): discover, count, offsets, emit (device events), host wall time of the call (svo_list_timing)"""

@@ -6,7 +6,7 @@ import torch
 
 from . import sharding
 from ._device import device_u32, voxel_list, wait_for_torch
-from ._lib import BuildParams, CompactParams, EditParams, ListParams, RegionParams, SampleParams, SitesParams, StampParams, SurfaceParams, TopsParams, Uniforms, lib
+from ._lib import BuildParams, CompactParams, EditParams, ListParams, RegionParams, SampleParams, SimplifyParams, SitesParams, StampParams, SurfaceParams, TopsParams, Uniforms, lib
 from .camera import camera_matrices
 
 F_PAUSE_ADAPTIVE, F_SHOW_STEPS, F_SHOW_HITS, F_SHADOWS, F_MISC_BOOL = 1, 2, 4, 8, 16
@@ -99,21 +99,24 @@ class Render:
 
     @classmethod
     def from_mesh(cls, gpu, size, vertices, triangles, depth, colours=None, capacity=None, solid=False, fill_colour=None,
-                  rule="evenodd", allow_open=False):
+                  rule="evenodd", allow_open=False, merge=False):
         """A Render whose tree is a triangle mesh voxelised and built on the GPU (build_nodes_mesh)."""
         self = cls(gpu, size, np.full(8, EMPTY_WORD, dtype=np.uint32), capacity)
-        self.build_nodes_mesh(vertices, triangles, depth, colours, solid=solid, fill_colour=fill_colour, rule=rule, allow_open=allow_open)
+        self.build_nodes_mesh(vertices, triangles, depth, colours, solid=solid, fill_colour=fill_colour, rule=rule, allow_open=allow_open,
+                              merge=merge)
         return self
 
     def build_nodes_mesh(self, vertices, triangles, depth, colours=None, colour=0xFFFFFF, max_words=None, quantized=False,
-                         solid=False, fill_colour=None, rule="evenodd", allow_open=False):
+                         solid=False, fill_colour=None, rule="evenodd", allow_open=False, merge=False):
         """Voxelise a triangle mesh on the GPU (mesh.voxelize) and build the tree of its cells into the node
         buffer from word 0 (build_nodes).  vertices: (V, 3) floats in [-1, 1), or with quantized=True the integers of
         mesh.quantize_vertices; triangles: (T, 3) vertex indices; colours: T values 0x00RRGGBB or None (every triangle
         `colour`).  The highest triangle index colours a cell that several triangles touch.  solid: the cells inside the
         mesh (mesh.voxelize_solid with `rule`) in fill_colour (None: `colour`) stand in front of the surface's
         list, so the surface keeps its triangles' colours (the last entry in input order wins); a mesh with open columns
-        raises ValueError unless allow_open.  Returns the word count."""
+        raises ValueError unless allow_open.  merge: the lossless simplify_nodes() after the build, so that a solid model
+        comes in with coarse interior leaves (mind its docstring before putting voxels in by edit_nodes).  Returns the
+        word count."""
         from .mesh import voxelize, voxelize_solid
         coords, cell_colours = voxelize(self.gpu, vertices, triangles, depth, colours, colour, quantized=quantized)
         if solid:
@@ -123,7 +126,8 @@ class Render:
             fill = int(colour if fill_colour is None else fill_colour) & 0xFFFFFF
             coords = torch.cat([inner, coords])
             cell_colours = torch.cat([torch.full((len(inner),), fill, dtype=torch.int32, device=inner.device), cell_colours])
-        return self.build_nodes(coords, depth, cell_colours, max_words=max_words)
+        n = self.build_nodes(coords, depth, cell_colours, max_words=max_words)
+        return self.simplify_nodes() if merge else n
 
     def build_nodes(self, coords, depth, colours=None, colour=0xFFFFFF, max_words=None):
         """Build the tree of a voxel list on the GPU into the node buffer from word 0 (svo_nodes_build).
@@ -198,6 +202,43 @@ class Render:
         self.gpu.sync()
         self.node_length = out.value
         return (out.value, perm[: out.value]) if with_perm else out.value
+
+    def simplify_nodes(self, merge=True, cut_level=None, min_level=None, out_of_place=False, with_perm=False):
+        """Simplify the tree in the first node_length words of the node buffer on the GPU (svo_nodes_simplify, DESIGN.md
+        26).  merge (lossless): an interior word whose whole subtree holds one leaf value becomes that leaf, so eight equal
+        sibling leaves are one again, level after level; every cell samples to what it sampled before.  min_level: no
+        merged leaf coarser than that level (the root group's words are level 1, so 3 keeps levels 1 and 2 interior).  cut_level (lossy): every interior word of that
+        level becomes a leaf of its subtree's mip colour (the average of the non-empty children per channel, bottom-up),
+        a level-of-detail copy when out_of_place.  The result is in compact_nodes' canonical breadth-first layout, the same
+        bytes for every layout of the same tree.
+        In place: sets node_length to the new length and returns it, the freed tail holds the empty word; raises SvoError,
+        with nothing written, for a malformed tree or with a device adaptive state attached.  out_of_place: returns (words,
+        length), words a device int32 tensor of the new tree; the node buffer is only read and node_length stays.
+        with_perm: perm, a device int32 tensor with perm[new word] = old word, comes last in the result.
+        The trap: edit_nodes splits a coarse leaf into EMPTY children, as the reference's put_in_voxel does, so voxels put
+        into a merged solid by cell list lose the solid's colour around the edit.  edit_region carries the colour down, and
+        min_level bounds how coarse the merge goes."""
+        dev = self.gpu.torch_device
+        p = SimplifyParams()
+        p.flags = (1 if merge else 0) | (2 if cut_level is not None else 0)
+        p.cut_level = 0 if cut_level is None else max(0, int(cut_level))
+        p.min_level = 0 if min_level is None else max(0, int(min_level))
+        p.n_words = int(self.node_length)
+        room = max(int(self.node_length), 1)
+        words = torch.empty(room, dtype=torch.int32, device=dev) if out_of_place else None
+        perm = torch.empty(room, dtype=torch.int32, device=dev) if with_perm else None
+        p.out_cap = room if out_of_place else 0
+        out = C.c_uint64()
+        if out_of_place or with_perm:
+            wait_for_torch(self.gpu)
+        self.gpu.check(lib().svo_nodes_simplify(self.gpu._h, C.byref(p), words.data_ptr() if out_of_place else None,
+                                                perm.data_ptr() if with_perm else None, C.byref(out)))
+        self.gpu.sync()
+        n = out.value
+        if not out_of_place:
+            self.node_length = n
+        res = ((words[:n], n) if out_of_place else (n,)) + ((perm[:n],) if with_perm else ())
+        return res if len(res) > 1 else n
 
     def list_voxels(self, depth=None, expand=False, with_levels=False):
         """The voxels of the tree in the first node_length words of the node buffer, listed on the GPU (svo_nodes_list_voxels,

@@ -1,0 +1,476 @@
+"""Trees simplified on the GPU (csrc/svo_simplify.hip): words and perm against the restatements of the contract
+(tests/simplify_ref.py) on the host test's scenes, for MERGE, CUT and both, in place and out of place, with and without
+perm; the same bytes for every layout of a tree and on every run; level sizes around the wave and the block, a depth-1
+tree and a depth-21 chain; counters, the freed tail, nothing written behind n_words, out of place nothing written at all
+and no sharing context disturbed; every error in its order with all buffers unchanged; the cells and the expanded list
+before and after a merge; edits and compactions of a merged tree; frames of merged and cut trees against the oracle; a
+solid mesh merged at the build."""
+import ctypes as C
+import os
+import re
+
+import numpy as np
+import pytest
+
+import build_ref as B
+import compact_ref as K
+import edit_ref as E
+import region_ref as G
+import simplify_ref as R
+from conftest import ROOT as REPO, assert_hits_equal, load_vox_fixture
+from pass_frame import SENTINEL, SentinelOut, assert_words, last_error, own_gpu  # noqa: F401
+from test_compact_host import malformed_cases
+from test_edit_gpu import CAPACITY, PAD, ROOT, frame, poison, set_base
+from test_simplify_host import assert_frames_alike, scenes
+
+pytestmark = pytest.mark.gpu
+
+ERR_ARG, ERR_STATE, ERR_CAP = -1, -3, -6
+VO = B.VOXEL_OFFSET
+K_THREADS = int(re.search(r"kThreads = (\d+);", open(os.path.join(REPO, "octree-tracer_amd", "csrc", "svo_group.h")).read()).group(1))
+# (merge, cut_level, min_level): flags 1, 2 and 3, and the limits
+MODES = ((True, None, 0), (False, 3, 0), (True, 3, 0), (True, 4, 3), (True, None, 3))
+SCENES = ("ball6", "box6", "field6", "columns5", "sparse5", "ball6_shapes", "box6_edited", "ball6_merged_edited", "field6_counters",
+          "ball6_high")
+
+
+@pytest.fixture(scope="module")
+def render(pkg, own_gpu):
+    return pkg.Render(own_gpu, (64, 64), ROOT, capacity=CAPACITY)
+
+
+def raw_simplify(pkg, gpu, n_words, flags=1, cut_level=0, min_level=0, reserved=0, out=None, out_cap=None, perm=None, params=True,
+                 n_out=True):
+    p = pkg._lib.SimplifyParams()
+    p.flags, p.cut_level, p.min_level, p.reserved, p.n_words = flags, cut_level, min_level, reserved, n_words
+    p.out_cap = (out.numel() if out is not None else 0) if out_cap is None else out_cap
+    n = C.c_uint64(12345)
+    rc = pkg._lib.lib().svo_nodes_simplify(gpu._h, C.byref(p) if params else None, out.data_ptr() if out is not None else None,
+                                           perm.data_ptr() if perm is not None else None, C.byref(n) if n_out else None)
+    gpu.sync()
+    return rc, n.value
+
+
+def mode_args(mode):
+    merge, cut_level, min_level = mode
+    return dict(flags=(R.MERGE if merge else 0) | (R.CUT if cut_level is not None else 0), cut_level=cut_level or 0, min_level=min_level)
+
+
+def check_simplify(pkg, render, words, mode, what, in_place=True, with_perm=True, want=None):
+    """words -> simplified on the GPU == the reference, words and perm.  In place: the freed tail holds the empty word and
+    the words behind n_words keep what they held.  Out of place: the node buffer keeps every word, the output and the
+    perm behind the new length keep the sentinel."""
+    gpu = render.gpu
+    want, want_perm = want if want is not None else R.simplify_parallel(words, words.size, *mode)
+    set_base(render, words)
+    before = render.read_nodes(words.size + PAD)
+    outs = SentinelOut(gpu, [words.size if with_perm else None, None if in_place else words.size])
+    perm = outs.t[0]
+    out = outs.t[1]
+    rc, n = raw_simplify(pkg, gpu, words.size, out=out, perm=perm, **mode_args(mode))
+    assert rc == 0, f"{what}: status {rc}: {last_error(pkg, gpu)}"
+    assert n == want.size, f"{what}: length {n}, want {want.size}"
+    got = render.read_nodes(words.size + PAD)
+    if in_place:
+        assert_words(got[:n], want, what)
+        assert (got[n:words.size] == B.EMPTY).all(), f"{what}: the freed tail is not empty"
+        assert np.array_equal(got[words.size:], poison(PAD)), f"{what}: words behind n_words were written"
+    else:
+        assert np.array_equal(got, before), f"{what}: an out-of-place call wrote to the node buffer"
+        o = out.cpu().numpy().view(np.uint32)
+        assert_words(o[:n], want, what)
+        assert (o[n:] == SENTINEL).all(), f"{what}: the output was written behind the new length"
+    if with_perm:
+        p = perm.cpu().numpy().view(np.uint32)
+        assert np.array_equal(p[:n], want_perm), f"{what}: perm"
+        assert (p[n:] == SENTINEL).all(), f"{what}: perm written behind the new length"
+    return want, want_perm
+
+
+@pytest.mark.parametrize("name", SCENES)
+def test_scenes_equal_the_reference(pkg, render, name):
+    words, _ = scenes()[name]
+    for k, mode in enumerate(MODES):
+        want = R.simplify_parallel(words, words.size, *mode)
+        check_simplify(pkg, render, words, mode, f"{name} {mode} in place", True, True, want)
+        check_simplify(pkg, render, words, mode, f"{name} {mode} out of place", False, False, want)
+        if k == 0:
+            check_simplify(pkg, render, words, mode, f"{name} {mode} in place, no perm", True, False, want)
+            check_simplify(pkg, render, words, mode, f"{name} {mode} out of place, perm", False, True, want)
+    # counters: kept words keep their 4 bits, rewritten words have 0 (the reference says so; here it is said of the scene)
+    out, perm = R.simplify_parallel(words, words.size)
+    rewritten = (words[perm] >> 4 < VO) & (out >> 4 >= VO)
+    assert np.array_equal((out & 15)[~rewritten], (words[perm] & 15)[~rewritten]) and not (out & 15)[rewritten].any()
+
+
+def shuffled(words, rng):
+    """the same tree with its groups (but the root) in a random order, and 3 unreachable groups of noise between them"""
+    n = words.size // 8
+    place = np.concatenate([[0], 1 + rng.permutation(n + 2)])[:n]  # group g goes to place[g] of n + 3
+    out = rng.integers(0, 1 << 32, 8 * (n + 3), dtype=np.uint64).astype(np.uint32)
+    g = words.reshape(n, 8)
+    moved = np.where(g >> 4 < VO, (8 * place[np.minimum(g >> 4, words.size - 8) // 8]).astype(np.uint32) << 4 | g & 15, g)
+    out.reshape(n + 3, 8)[place] = moved
+    return out
+
+
+def test_every_layout_and_every_run_give_the_same_bytes(pkg, render):
+    coords, colours = two_halves()
+    canonical = B.build(coords, 6, colours)
+    half = len(coords) // 2
+    first = B.build(coords[:half], 6, colours[:half])
+    put = E.edit(first, first.size, coords[half:], 6, colours[half:])
+    layouts = {"canonical": canonical, "put order": put, "compacted": K.compact(put, put.size, False)[0],
+               "shuffled": shuffled(canonical, np.random.default_rng(1))}
+    assert not np.array_equal(put[:canonical.size], canonical) and np.array_equal(layouts["compacted"], canonical)
+    for mode in MODES[:3]:
+        want = R.simplify_parallel(canonical, canonical.size, *mode)[0]
+        assert want.size < canonical.size
+        for name, words in layouts.items():
+            for run in range(2):
+                set_base(render, words)
+                got = render.simplify_nodes(merge=mode[0], cut_level=mode[1], min_level=mode[2])
+                assert got == want.size == render.node_length
+                assert_words(render.read_nodes(), want, f"{name}, {mode}, run {run}")
+
+
+def two_halves():
+    """a solid box of one colour with stray voxels, shuffled, to be put in two halves: it merges, and put order differs
+    from breadth-first"""
+    rng = np.random.default_rng(21)
+    box = np.stack(np.meshgrid(*[np.arange(8, 40)] * 3, indexing="ij"), -1).reshape(-1, 3)
+    stray = rng.integers(0, 64, (200, 3))
+    coords = np.concatenate([box, stray])
+    colours = np.full(len(coords), 0x336699)
+    order = rng.permutation(len(coords))
+    return coords[order], colours[order]
+
+
+def level_tree(counts, rng, uniform_every=3):
+    """a canonical tree whose level l + 1 has counts[l] groups (counts[0] == 1): the interior words are dealt to the
+    parents round-robin, the leaves are of 3 colours or empty, every uniform_every-th group of the last level holds
+    one colour in all eight words and so do the parents' leaves next to it"""
+    assert counts[0] == 1 and all(b <= 8 * a for a, b in zip(counts, counts[1:]))
+    starts = np.concatenate([[0], np.cumsum(counts)])
+    palette = np.array([B.EMPTY, (VO + 0x111111) << 4, (VO + 0x2222FF) << 4, (VO + 0x111111) << 4], dtype=np.uint32)
+    words = palette[rng.integers(0, 4, 8 * starts[-1])]
+    for l, n in enumerate(counts[:-1]):
+        kids = counts[l + 1]
+        per = np.full(n, kids // n) + (np.arange(n) < kids % n)
+        child = starts[l + 1]
+        for g in range(n):
+            base = 8 * (starts[l] + g)
+            slots = np.sort(rng.choice(8, per[g], replace=False))
+            for s in slots:
+                words[base + s] = (8 * child) << 4 | int(rng.integers(0, 16))
+                child += 1
+    last = starts[-2]
+    for g in range(last, starts[-1], uniform_every):
+        words[8 * g:8 * g + 8] = palette[1] | rng.integers(0, 16, 8).astype(np.uint32)
+    # the parents of the last level: leaves of the same colour, so that some merges cascade
+    lo, hi = 8 * starts[max(len(counts) - 2, 0)], 8 * starts[-2]
+    leaf = np.flatnonzero(words[lo:hi] >> 4 >= VO) + lo
+    words[leaf[::2]] = palette[1]
+    return words
+
+
+def test_level_sizes_around_the_wave_and_the_block(pkg, render):
+    per_block = K_THREADS // 8
+    assert per_block == 32
+    rng = np.random.default_rng(33)
+    for counts in ([1, 1], [1, 7], [1, 8], [1, 2, 9], [1, 5, per_block + 1], [1, 8, per_block + 1, 2 * per_block + 1],
+                   [1, 8, 9, per_block, per_block - 1]):
+        for uniform_every in (1, 3):
+            words = level_tree(counts, rng, uniform_every)
+            for mode in ((True, None, 0), (False, 2, 0), (True, len(counts), 2), (True, 2, 0))[:4 if uniform_every == 1 else 2]:
+                want = check_simplify(pkg, render, words, mode, f"levels {counts}, {mode}")[0]
+                check_simplify(pkg, render, words, mode, f"levels {counts}, {mode}, out of place", in_place=False)
+                assert np.array_equal(want, R.simplify(words, words.size, *mode)[0])
+            if uniform_every == 1:
+                assert R.simplify(words, words.size)[0].size < words.size
+
+
+def test_depth_1_and_the_depth_21_chain(pkg, render):
+    x = (VO + 0xABCDEF) << 4
+    # depth 1: eight equal leaves stay eight leaves, the root group has no parent word
+    for words in (np.full(8, x, dtype=np.uint32), ROOT, np.arange(8, dtype=np.uint32) + np.uint32(x)):
+        for mode in ((True, None, 0), (True, 1, 0), (False, 1, 0), (False, 31, 0)):
+            want = check_simplify(pkg, render, words, mode, f"depth 1, {mode}")[0]
+            assert np.array_equal(want, words)
+    # a chain of 21 groups, each seven leaves of one colour and the pointer to the next, the last one full
+    chain = np.full(8 * 21, x, dtype=np.uint32) | (np.arange(8 * 21) % 16).astype(np.uint32)
+    at = np.arange(20) * 8 + (np.arange(20) * 5 + 3) % 8
+    chain[at] = ((np.arange(1, 21) * 8) << 4 | 9).astype(np.uint32)
+    want = check_simplify(pkg, render, chain, (True, None, 0), "depth-21 chain")[0]
+    assert want.size == 8 and (want >> 4 == x >> 4).all() and want[3] == x and (np.delete(want, 3) == np.delete(chain[:8], 3)).all()
+    # min_level in the middle: the words of the levels above 11 stay interior
+    want = check_simplify(pkg, render, chain, (True, None, 11), "depth-21 chain, min_level 11")[0]
+    assert want.size == 8 * 11 and (want[80:] >> 4 == x >> 4).all() and (want[:80] >> 4 < VO).sum() == 10
+    # one other colour at the end: nothing merges
+    chain[-1] = (VO + 1) << 4
+    assert check_simplify(pkg, render, chain, (True, None, 0), "depth-21 chain, not uniform")[0].size == chain.size
+    # cut in the middle of the chain: the cube becomes solid in the colour of what it holds
+    want = check_simplify(pkg, render, chain, (False, 7, 0), "depth-21 chain, cut at 7")[0]
+    assert want.size == 8 * 7 and (want[48:] >> 4 >= VO).all()
+    # cells of the depth-21 grid, some of them down the chain, sample alike before and after
+    chain[-1] = x
+    cells = np.concatenate([np.random.default_rng(21).integers(0, 1 << 21, (64, 3)), [[0, 0, 0]], chain_cells(at)])
+    for min_level in (None, 11):
+        set_base(render, chain)
+        before = render.sample_voxels(cells, 21).cpu().numpy()
+        assert render.simplify_nodes(min_level=min_level) == (8 if min_level is None else 88)
+        assert (before == 0xABCDEF).all() and np.array_equal(render.sample_voxels(cells, 21).cpu().numpy(), before)
+
+
+def chain_cells(at):
+    """the minimum corner, on the depth-21 grid, of the cube of every group of the chain"""
+    cells, cell = [], np.zeros(3, dtype=np.int64)
+    for level, c in enumerate(at % 8, start=1):
+        cell = cell + (np.array([c >> 2 & 1, c >> 1 & 1, c & 1]) << (21 - level))
+        cells.append(cell)
+    return np.array(cells)
+
+
+def test_cells_and_the_expanded_list_survive_a_merge(pkg, render):
+    for name in ("ball6", "ball6_shapes", "box6_edited", "field6_counters"):
+        words, depth = scenes()[name]
+        set_base(render, words)
+        cells = render.sample_dense((0, 0, 0), (1 << depth,) * 3, depth).cpu().numpy()
+        listed = [t.cpu().numpy() for t in render.list_voxels(depth, expand=True)]
+        n = render.simplify_nodes()
+        assert n == render.node_length < words.size
+        assert np.array_equal(render.sample_dense((0, 0, 0), (1 << depth,) * 3, depth).cpu().numpy(), cells), name
+        for a, b in zip(listed, render.list_voxels(depth, expand=True)):
+            assert np.array_equal(a, b.cpu().numpy()), name
+        # a cut shows every cell S of its cube
+        set_base(render, words)
+        lod, length = render.simplify_nodes(merge=False, cut_level=4, out_of_place=True)
+        assert render.node_length == words.size and length == len(lod)
+        lod = lod.cpu().numpy().view(np.uint32)
+        assert np.array_equal(R.cells(lod, lod.size, depth), R.cut_cells(words, words.size, depth, 4)), name
+
+
+def test_edits_and_compactions_of_a_merged_tree(pkg, render):
+    words, depth = scenes()["ball6"]
+    merged = R.simplify_parallel(words, words.size)[0]
+    sh = [G.box((20, 20, 20), (44, 30, 44), 0), G.ball((64, 64, 64), 21, 0xCC2200), G.box((0, 0, 0), (64, 64, 33), 0x00AA00, G.MODE_VOXELS)]
+    want, tally = G.edit(merged, merged.size, G.shapes(sh), depth)
+    assert tally["splits"] > 10  # coarse leaves on the shapes' surfaces are split and keep their colour
+    set_base(render, words, want.size)
+    assert render.simplify_nodes() == merged.size
+    shapes = [pkg.region.box((20, 20, 20), (44, 30, 44), 0), pkg.region.ball((32, 32, 32), 10.5, 0xCC2200),
+              pkg.region.box((0, 0, 0), (64, 64, 33), 0x00AA00, pkg.region.VOXELS)]
+    assert render.edit_region(shapes, depth) == want.size
+    assert_words(render.read_nodes(), want, "a merged tree edited by shapes")
+    for prune in (False, True):
+        ref = K.compact(want, want.size, prune)[0]
+        set_base(render, want)
+        assert render.compact_nodes(prune=prune) == ref.size
+        assert_words(render.read_nodes(), ref, f"a merged, edited tree compacted, prune {prune}")
+    # merged again: what the shapes made uniform is one leaf again
+    again = R.simplify_parallel(want, want.size)[0]
+    set_base(render, want)
+    assert render.simplify_nodes() == again.size < K.compact(want, want.size, True)[0].size
+    assert_words(render.read_nodes(), again, "merged, edited, merged again")
+    # the trap: a cell list put into a merged solid splits the coarse leaf into empty children
+    set_base(render, merged, 8 * 8)
+    cell = [[32, 32, 32]]
+    n = render.edit_nodes(cell, depth, [0xFF00FF])
+    assert_words(render.read_nodes(), E.edit(merged, merged.size, cell, depth, [0xFF00FF]), "a merged tree edited by a cell list")
+    around = render.sample_voxels([[32, 32, 33], [33, 33, 33], [32, 32, 32]], depth).cpu().tolist()
+    assert n > merged.size and around == [0, 0, 0xFF00FF]
+
+
+def test_out_of_place_disturbs_no_sharing_context(pkg, O):
+    import torch
+    if not torch.cuda.is_available():
+        pytest.skip("no GPU")
+    words, _ = scenes()["ball6"]
+    g1, g2 = pkg.Gpu(0), pkg.Gpu(0)
+    try:
+        r1 = pkg.Render(g1, (64, 64), words, capacity=words.size + PAD)
+        g1.sync()
+        r2 = pkg.Render.share_nodes(g2, r1)
+        u = O.make_uniforms(width=64, height=64, flags=O.F_PAUSE_ADAPTIVE)
+        want = O.trace_frame(words, u, threads=4)
+        for _ in range(40):  # until the schedule of the sharing context has settled and only ages
+            got = frame(pkg, r2, u)
+            age = g2.schedule_status()["age"]
+            if age >= 2:
+                break
+        assert 2 <= age < 60
+        assert_hits_equal(got, want, "before")
+        lod, n = r1.simplify_nodes(out_of_place=True)
+        assert r1.node_length == words.size and n < words.size and np.array_equal(r1.read_nodes(), words)
+        assert_hits_equal(frame(pkg, r2, u), want, "after the out-of-place call")
+        assert g2.schedule_status()["age"] == age + 1  # no write was recorded: nothing was rebuilt
+        # the copy is a tree of its own for another context
+        g3 = pkg.Gpu(0)
+        try:
+            r3 = pkg.Render(g3, (64, 64), lod.cpu().numpy().view(np.uint32), capacity=max(n, 1024))
+            assert_hits_equal(frame(pkg, r3, u), O.trace_frame(lod.cpu().numpy().view(np.uint32), u, threads=4), "the copy")
+        finally:
+            g3.close()
+        # in place, for comparison: the write is recorded and the sharing context rebuilds
+        assert r1.simplify_nodes() == n
+        g1.sync()
+        r2.node_length = n
+        merged = r1.read_nodes()
+        assert_hits_equal(frame(pkg, r2, u), O.trace_frame(merged, u, threads=4), "after the in-place call")
+        assert g2.schedule_status()["age"] == 0
+    finally:
+        g2.close()
+        g1.close()
+
+
+def test_errors_in_their_order_write_nothing(pkg, render, own_gpu):
+    import torch
+    err = lambda g=own_gpu: last_error(pkg, g)  # noqa: E731
+    base, _ = scenes()["box6"]
+    set_base(render, base)
+    before = render.read_nodes(base.size + PAD)
+    outs = SentinelOut(own_gpu, [base.size, base.size])
+    perm, out = outs.t
+    for o in (None, out):
+        kw = dict(out=o, perm=perm)
+        # 1. NULL p or n_words_out, before the flags are looked at
+        assert raw_simplify(pkg, own_gpu, base.size, flags=0, params=False, **kw)[0] == ERR_ARG and "null" in err()
+        assert raw_simplify(pkg, own_gpu, 12, flags=0, n_out=False, **kw)[0] == ERR_ARG and "null" in err()
+        # 2. flags, cut_level, min_level, reserved, before n_words is looked at
+        for flags in (0, 4, 1 | 1 << 31, 8 | 2):
+            assert raw_simplify(pkg, own_gpu, 12, flags=flags, cut_level=3 if flags & 2 else 0, **kw) == (ERR_ARG, 0) and "flag" in err()
+        for flags, cut_level in ((2, 0), (3, 0), (2, 32), (3, 1 << 31), (1, 3)):
+            assert raw_simplify(pkg, own_gpu, 12, flags=flags, cut_level=cut_level, **kw) == (ERR_ARG, 0) and "cut_level" in err()
+        assert raw_simplify(pkg, own_gpu, 12, flags=2, cut_level=3, min_level=2, **kw) == (ERR_ARG, 0) and "min_level" in err()
+        assert raw_simplify(pkg, own_gpu, 12, flags=1, reserved=1, **kw) == (ERR_ARG, 0) and "reserved" in err()
+        # 5. n_words
+        for n in (0, 12, base.size + 4, CAPACITY + 8):
+            assert raw_simplify(pkg, own_gpu, n, **kw) == (ERR_ARG, 0) and "n_words" in err()
+    # 7. the room of an out-of-place call, with the exact length
+    want = R.simplify_parallel(base, base.size)[0]
+    for cap in (0, 8, want.size - 8):
+        assert raw_simplify(pkg, own_gpu, base.size, out=out, out_cap=cap, perm=perm) == (ERR_CAP, 0)
+        assert f"{want.size} words" in err() and f"out_cap = {cap}" in err()
+    assert raw_simplify(pkg, own_gpu, base.size, out=out, out_cap=want.size, perm=None) == (0, want.size)
+    assert_words(out.cpu().numpy().view(np.uint32)[:want.size], want, "exactly the room it needs")
+    out.fill_(SENTINEL)
+    torch.cuda.synchronize()
+    assert np.array_equal(render.read_nodes(base.size + PAD), before) and outs.untouched_from(0)
+
+    # 6. the malformed trees, with the compaction's wording; before the room is looked at
+    causes = {"a pointer with pointer + 8 > n_words": "leaves the first n_words", "an unaligned pointer": "not a multiple of 8",
+              "two parents sharing one group": "reached twice", "a cycle through the root": "reached twice", "32 levels": "deeper than 31"}
+    cases = malformed_cases()
+    assert set(cases) == set(causes)
+    for name, words in cases.items():
+        set_base(render, words)
+        before = render.read_nodes(words.size + PAD)
+        for mode in MODES[:3]:
+            for o in (None, out):
+                assert raw_simplify(pkg, own_gpu, words.size, out=o, out_cap=0, perm=perm, **mode_args(mode)) == (ERR_STATE, 0), name
+                assert "malformed tree: " in err() and causes[name] in err(), f"{name}: {err()}"
+        for kw in (dict(), dict(out_of_place=True)):
+            with pytest.raises(pkg.SvoError):
+                render.simplify_nodes(**kw)
+        assert render.node_length == words.size
+        assert np.array_equal(render.read_nodes(words.size + PAD), before), name
+    assert outs.untouched_from(0)
+
+    # 3. no node buffer, before n_words is looked at and behind the flags
+    fresh = pkg.Gpu(0)
+    try:
+        assert raw_simplify(pkg, fresh, 12)[0] == ERR_STATE and "svo_nodes_alloc" in err(fresh)
+        assert raw_simplify(pkg, fresh, 8, flags=0)[0] == ERR_ARG and "flag" in err(fresh)
+    finally:
+        fresh.close()
+    # 4. a device adaptive state: refused in place, before n_words is looked at; no obstacle out of place
+    size, xyzi, pal, _, _ = load_vox_fixture("monu9")
+    world = pkg.adaptive.World(pkg.CpuOctree.from_voxels(size, xyzi, pal))
+    octree = world.root_octree()
+    g = pkg.Gpu(0)
+    try:
+        g.set_option(pkg.gpu.OPT_SCAN_CLEARS_COUNTERS, 1)
+        r = pkg.Render.new(g, (64, 64), octree, capacity=4096)
+        attached = pkg.adaptive.DeviceAdaptive(g, r, octree, world)
+        before = r.read_nodes()
+        for n in (r.node_length, 12):
+            assert raw_simplify(pkg, g, n)[0] == ERR_STATE and "adaptive" in err(g)
+        with pytest.raises(pkg.SvoError):
+            r.simplify_nodes()
+        assert r.node_length == before.size and np.array_equal(r.read_nodes(), before)
+        want = R.simplify_parallel(before, before.size)[0]
+        lod, n = r.simplify_nodes(out_of_place=True)
+        assert n == want.size and r.node_length == before.size
+        assert_words(lod.cpu().numpy().view(np.uint32), want, "out of place beside an adaptive state")
+        assert np.array_equal(r.read_nodes(), before)
+        del attached
+    finally:
+        g.close()
+
+
+def test_merged_and_cut_trees_trace_like_the_oracle(pkg, O):
+    import torch
+    if not torch.cuda.is_available():
+        pytest.skip("no GPU")
+    words, _ = scenes()["ball7"]
+    g = pkg.Gpu(0)
+    try:
+        r = pkg.Render(g, (64, 64), words, capacity=words.size + PAD)
+        views = (((0.1, 0.2, -1.5), (0.0, 0.0, 1.5)), ((1.4, 1.2, 1.3), (-1.0, -0.8, -1.0)), ((0.9, 0.85, -0.9), (-1.0, -1.0, 1.0)))
+        us = [O.make_uniforms(pos=pos, look=look, width=64, height=64, flags=O.F_PAUSE_ADAPTIVE) for pos, look in views]
+        plain = [frame(pkg, r, u) for u in us]
+        for u, got in zip(us, plain):
+            assert_hits_equal(got, O.trace_frame(words, u, threads=4), "the unmerged ball")
+        assert r.simplify_nodes() < words.size // 4
+        merged = r.read_nodes()
+        assert_words(merged, R.simplify_parallel(words, words.size)[0], "the merged ball")
+        for variant in (pkg.gpu.VARIANT_STACK, pkg.gpu.VARIANT_RESTART):
+            g.set_option(pkg.gpu.OPT_VARIANT, variant)
+            for k, u in enumerate(us):
+                got = frame(pkg, r, u)
+                assert_hits_equal(got, O.trace_frame(merged, u, threads=4), f"the merged ball, view {k}, variant {variant}")
+                # merged against unmerged: the same rays hit the same colours at the same place; index and depth differ
+                assert_frames_alike(O, plain[k], words, got, merged, f"merged against unmerged, view {k}")
+        for level in (3, 5):
+            r.write_nodes(words)
+            r.node_length = words.size
+            n = r.simplify_nodes(merge=level == 5, cut_level=level)
+            cut = r.read_nodes()
+            assert n == cut.size < merged.size
+            for k, u in enumerate(us):
+                assert_hits_equal(frame(pkg, r, u), O.trace_frame(cut, u, threads=4), f"cut at {level}, view {k}")
+    finally:
+        g.close()
+
+
+def test_a_solid_mesh_merged_at_the_build(pkg, own_gpu):
+    v, t = pkg.mesh.icosphere(2, 0.6, (0.05, -0.1, 0.2))
+    colours = 0x010000 + np.arange(len(t))
+    plain = pkg.Render.from_mesh(own_gpu, (64, 64), v, t, 7, colours, capacity=1 << 22, solid=True, fill_colour=0x00BEEF)
+    unmerged = plain.read_nodes()
+    assert plain.simplify_nodes() == plain.node_length
+    merged = pkg.Render.from_mesh(own_gpu, (64, 64), v, t, 7, colours, capacity=1 << 22, solid=True, fill_colour=0x00BEEF, merge=True)
+    assert merged.node_length == plain.node_length < unmerged.size // 2
+    assert_words(merged.read_nodes(), plain.read_nodes(), "from_mesh(merge=True) against from_mesh, then simplify_nodes")
+    assert_words(merged.read_nodes(), R.simplify_parallel(unmerged, unmerged.size)[0], "against the reference")
+    assert merged.build_nodes_mesh(v, t, 7, colours, solid=True, fill_colour=0x00BEEF) == unmerged.size  # the default merges nothing
+
+
+def test_timing(pkg, render, own_gpu):
+    words, _ = scenes()["ball6"]
+    set_base(render, words)
+    render.simplify_nodes()
+    ms = own_gpu.simplify_timing()
+    assert len(ms) == 6 and all(t >= 0 for t in ms) and ms[5] > 0
+    assert ms == own_gpu.simplify_timing()
+    # a refused call in between leaves the times of the last simplification that ran
+    bad = malformed_cases()["two parents sharing one group"]
+    set_base(render, bad)
+    assert raw_simplify(pkg, own_gpu, bad.size)[0] == ERR_STATE
+    assert ms == own_gpu.simplify_timing()
+    fresh = pkg.Gpu(0)
+    try:
+        with pytest.raises(pkg.SvoError):
+            fresh.simplify_timing()
+    finally:
+        fresh.close()
