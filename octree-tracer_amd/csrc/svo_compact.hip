@@ -12,14 +12,19 @@
 //             word; the next frontier's size comes back with the status, once per level
 //   check     new_of[order[k] / 8] = k by plain stores, then a launch of its own tests new_of[order[k] / 8] == k: of two
 //             groups k that share an old group one store wins and the other k sees it, whichever it is
-//   prune     bottom-up, one launch per level: live[k] = any word is a non-empty leaf or an interior word whose child
-//             is live; live[0] = 1.  Without the flag every group is live
-//   emit      one exclusive scan of live over all of order gives every live group its new number (level-major, and a
-//             live group's ancestors are live: still breadth-first).  The groups are written into a workspace image, not
-//             into the node buffer they are read from; the optional perm is written here
-//   copy back one device-to-device copy of the image and one fill of the freed tail with the empty word
+//   prune     bottom-up, one launch per level: a group is live when any word is a non-empty leaf or an interior word
+//             whose child is live, and the root is.  number[k] = live, fate[k] = keep or, of a dead group, the empty
+//             field that its parent's word becomes.  Without the flag the two arrays are filled: every group is live
+//   emit      one exclusive scan of number over the candidates gives every kept group its new number (level-major, and a
+//             kept group's ancestors are kept: still breadth-first).  A kept group's lane writes its word, an interior
+//             lane the pointer to its child's new place or the leaf of the child's fate.  In place the groups are
+//             written into a workspace image, not into the node buffer they are read from; the optional perm is written here
+//   copy back in place: one device-to-device copy of the image and one fill of the freed tail with the empty word
 //
-// Every error is decided before the emit, so it leaves the node buffer and the perm as they were.
+// Discover and check are svo_tree_discover, for the voxel listing too (svo_list.hip).  Everything but the prune is
+// svo_tree_rewrite (svo_ctx.h), the frame that the simplification (svo_simplify.hip) runs around its reduce: begin() up to
+// the check, finish() from the scan on.  Every error is decided before the emit, so it leaves the node buffer, the
+// caller's buffer and the perm as they were.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -33,8 +38,8 @@
 namespace {
 
 constexpr uint32_t kMaxLevels = 31;               // as svo_nodes_relayout and svo_nodes_max_depth
-// the words read back: the discovery's (svo_ctx.h), then the compaction's own
-enum Status { kStAlign = SVO_WALK_ALIGN, kStRange = SVO_WALK_RANGE, kStNext = SVO_WALK_NEXT, kStDup = SVO_WALK_DUP, kStLive = SVO_WALK_STATUS, kStWords };
+// the words read back: the discovery's (svo_ctx.h), then the rewrite's own
+enum Status { kStAlign = SVO_WALK_ALIGN, kStRange = SVO_WALK_RANGE, kStNext = SVO_WALK_NEXT, kStDup = SVO_WALK_DUP, kStKept = SVO_WALK_STATUS, kStWords };
 
 // The frontier order[0, n) (the caller passes order + off): count[k] = interior words of group k; the pointers are checked.
 __global__ __launch_bounds__(kThreads) void compact_count_kernel(const uint32_t *words, uint32_t n_words, const uint32_t *order,
@@ -74,32 +79,39 @@ __global__ __launch_bounds__(kThreads) void compact_check_kernel(const uint32_t 
     if (k < n && new_of[order[k] >> 3] != k) status[kStDup] = 1u;
 }
 
-// The level order[off, off + n), behind the launches of the levels below it.
+// The level order[off, off + n), behind the launches of the levels below it: number[k] = the group is live, and its fate.
 __global__ __launch_bounds__(kThreads) void compact_live_kernel(const uint32_t *words, const uint32_t *order, uint32_t off, uint32_t n,
-                                                                const uint32_t *first_child, uint32_t *live) {
+                                                                const uint32_t *first_child, uint32_t *number, uint32_t *fate) {
     const uint32_t i = blockIdx.x * kThreads + threadIdx.x, k = i >> 3, c = i & 7u;
     const bool valid = k < n;
     const GroupLane g = group_lane(words, order + off, k, c, valid);
-    const bool keeps = valid && (g.interior ? live[first_child[off + k] + g.below] != 0u : g.pointer != SVO_VOXEL_OFFSET);
+    const bool keeps = valid && (g.interior ? number[first_child[off + k] + g.below] != 0u : g.pointer != SVO_VOXEL_OFFSET);
     const uint32_t any = uint32_t(__ballot(keeps) >> (__lane_id() & ~7u)) & 0xFFu;
-    if (valid && c == 0) live[off + k] = (any || off + k == 0) ? 1u : 0u;
+    if (valid && c == 0) {
+        const bool live = any || off + k == 0;  // the root group has no parent word
+        number[off + k] = live ? 1u : 0u;
+        fate[off + k] = live ? SVO_FATE_KEEP : SVO_VOXEL_OFFSET;  // (the parent's word becomes the empty word)
+    }
 }
 
-__global__ void compact_total_kernel(const uint32_t *number, const uint32_t *live, uint32_t n, uint32_t *status) {
-    status[kStLive] = number[n - 1] + live[n - 1];
+// behind the scan of number[0, n): how many groups stay
+__global__ void rewrite_total_kernel(const uint32_t *number, const uint32_t *fate, uint32_t n, uint32_t *status) {
+    status[kStKept] = number[n - 1] + (fate[n - 1] == SVO_FATE_KEEP ? 1u : 0u);
 }
 
-__global__ __launch_bounds__(kThreads) void compact_emit_kernel(const uint32_t *words, const uint32_t *order, uint32_t n,
-                                                                const uint32_t *first_child, const uint32_t *live,
+// The candidates order[0, n): a kept group's words, an interior word as the pointer to its child's new place or as the
+// leaf of the child's fate.
+__global__ __launch_bounds__(kThreads) void rewrite_emit_kernel(const uint32_t *words, const uint32_t *order, uint32_t n,
+                                                                const uint32_t *first_child, const uint32_t *fate,
                                                                 const uint32_t *number, uint32_t n_out, uint32_t *image, uint32_t *perm) {
     const uint32_t i = blockIdx.x * kThreads + threadIdx.x, k = i >> 3, c = i & 7u;
     const bool valid = k < n;
     const GroupLane g = group_lane(words, order, k, c, valid);
-    if (!valid || !live[k]) return;
+    if (!valid || fate[k] != SVO_FATE_KEEP) return;
     uint32_t out = g.word;
     if (g.interior) {
-        const uint32_t child = first_child[k] + g.below;
-        out = live[child] ? ((8u * number[child]) << 4 | (g.word & 15u)) : kEmptyWord;
+        const uint32_t child = first_child[k] + g.below, to = fate[child];  // (a child behind the candidates has a fate too)
+        out = to == SVO_FATE_KEEP ? ((8u * number[child]) << 4 | (g.word & 15u)) : to << 4;
     }
     const uint32_t at = 8u * number[k] + c;
     if (at < n_out) {  // (always: n_out is the scan's total)
@@ -108,43 +120,19 @@ __global__ __launch_bounds__(kThreads) void compact_emit_kernel(const uint32_t *
     }
 }
 
-enum Ev { kEvStart, kEvDiscover, kEvCheck, kEvPrune, kEvEmit, kEvEnd, kEvs };
-
-}  // namespace
-
-// Per-context workspace of the compaction (svo_ctx::compact): the image and five u32 per group.
-struct svo_compact_state {
-    svo_dev<uint32_t> image;  // the compacted words before they are copied back
-    svo_dev<uint32_t> order, first_child, new_of, live, number;
-    svo_mirrored<> status;  // kStWords words
-    svo_pass_timer<kEvs, SVO_COMPACT_TIMES> timer;
-
-    int create(svo_ctx *ctx) {
-        HIP_TRY(ctx, timer.create());
-        return status.alloc(ctx, kStWords);
-    }
-};
-
-namespace {
-
-int ensure_state(svo_ctx *ctx, size_t words, size_t groups) {
-    int rc = svo_workspace_ensure(ctx, ctx->compact);
-    if (rc) return rc;
-    svo_compact_state *s = ctx->compact.get();
-    rc = svo_grow(ctx, words, &s->image);
-    if (!rc) rc = svo_grow(ctx, groups, &s->order, &s->first_child, &s->new_of, &s->live, &s->number);
-    return rc;
-}
-
 int malformed(svo_ctx *ctx, const std::string &why) { return svo_fail(ctx, SVO_ERR_STATE, "malformed tree: " + why); }
 
 }  // namespace
 
-// The discovery and the check of the tree in the first n_words_in words of the node buffer, for the compaction and for
-// svo_list.hip, on the ctx stream into the caller's workspace (svo_ctx.h).  Blocks once per level.
+// Per-context workspace of the compaction (svo_ctx::compact): the rewrite's (svo_ctx.h), the image and five u32 per group.
+struct svo_compact_state : svo_tree_rewrite {};
+
+// The discovery and the check of the tree in the first n_words_in words of the node buffer, on the ctx stream into the
+// walk's workspace (svo_ctx.h), which the caller has grown.  Blocks once per level.
 int svo_tree_discover(svo_ctx *ctx, uint64_t n_words_in, svo_tree_walk *w, hipEvent_t discovered) {
     // no pointer reaches a group behind 2^27, so the words behind it hold no reachable group
     const uint32_t n_words = (uint32_t)std::min<uint64_t>(n_words_in, kMaxWords), cap = n_words / 8;
+    w->n_words = n_words, w->cap = cap;
     const uint32_t *st = w->status.host();
     int rc;
     HIP_TRY(ctx, hipMemsetAsync(w->order, 0, sizeof(uint32_t), ctx->stream));  // level 1: group 0
@@ -187,6 +175,60 @@ int svo_tree_discover(svo_ctx *ctx, uint64_t n_words_in, svo_tree_walk *w, hipEv
     return SVO_OK;
 }
 
+int svo_tree_rewrite::create(svo_ctx *ctx) {
+    HIP_TRY(ctx, timer.create());
+    return walk.create(ctx, kStWords);
+}
+
+int svo_tree_rewrite::begin(svo_ctx *ctx, uint64_t n_words_in, bool in_place) {
+    t0 = svo_now_ms();
+    const size_t n_words = (size_t)std::min<uint64_t>(n_words_in, kMaxWords);
+    int rc;
+    if (in_place && (rc = svo_grow(ctx, n_words, &image))) return rc;
+    if ((rc = walk.grow(ctx, n_words / 8)) || (rc = svo_grow(ctx, n_words / 8, &fate))) return rc;
+    if ((rc = timer.begin(ctx))) return rc;
+    // the passes read the words: behind every earlier write to the store, whichever context issued it
+    if ((rc = svo_store_order_after_write(ctx))) return rc;
+    HIP_TRY(ctx, timer.mark(ctx, SVO_REWRITE_START));
+    HIP_TRY(ctx, walk.status.zero(ctx));
+    if ((rc = svo_tree_discover(ctx, n_words_in, &walk, timer.ev[SVO_REWRITE_DISCOVER]))) return rc;
+    HIP_TRY(ctx, timer.mark(ctx, SVO_REWRITE_CHECK));
+    return SVO_OK;
+}
+
+int svo_tree_rewrite::finish(svo_ctx *ctx, uint32_t total, uint32_t *out_dev, uint64_t out_cap, uint32_t *perm_out_dev,
+                             uint64_t n_words_in, uint64_t *n_words_out) {
+    const uint32_t *st = walk.status.host();
+    int rc;
+    if ((rc = svo_scan_u32(ctx, number(), total))) return rc;
+    rewrite_total_kernel<<<1, 1, 0, ctx->stream>>>(number(), fate, total, walk.status.dev);
+    HIP_TRY(ctx, hipGetLastError());
+    if ((rc = walk.status.read(ctx))) return rc;
+    if (st[kStDup]) return malformed(ctx, "a group is reached twice");
+    const uint32_t n_out = 8u * st[kStKept];
+    if (!n_out || n_out > walk.n_words) return svo_fail(ctx, SVO_ERR_HIP, "the kept groups' scan is out of range");  // (never: the root stays)
+    if (out_dev && n_out > out_cap)
+        return svo_fail(ctx, SVO_ERR_CAP, "the simplified tree has " + std::to_string(n_out) + " words, more than out_cap = " +
+                                              std::to_string(out_cap));
+    rewrite_emit_kernel<<<svo_div_up(8ull * total, kThreads), kThreads, 0, ctx->stream>>>(
+        ctx->nodes, walk.order, total, walk.first_child, fate, number(), n_out, out_dev ? out_dev : image.get(), perm_out_dev);
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, timer.mark(ctx, SVO_REWRITE_EMIT));
+
+    if (!out_dev) {
+        // copy back: behind every earlier write to the store (another context may have written while this one waited)
+        if ((rc = svo_store_order_after_write(ctx))) return rc;
+        HIP_TRY(ctx, hipMemcpyAsync(ctx->nodes, image, size_t(n_out) * sizeof(uint32_t), hipMemcpyDeviceToDevice, ctx->stream));
+        if (n_words_in > n_out)
+            HIP_TRY(ctx, hipMemsetD32Async((hipDeviceptr_t)(ctx->nodes + n_out), (int)kEmptyWord, n_words_in - n_out, ctx->stream));
+    }
+    HIP_TRY(ctx, timer.mark(ctx, SVO_REWRITE_END));
+    if (!out_dev && (rc = svo_store_note_write(ctx))) return rc;
+    *n_words_out = n_out;
+    timer.finish(t0);
+    return SVO_OK;
+}
+
 extern "C" {
 
 int svo_nodes_compact(svo_ctx *ctx, const svo_compact_params *p, uint32_t *perm_out_dev, uint64_t *n_words_out) {
@@ -201,64 +243,26 @@ int svo_nodes_compact(svo_ctx *ctx, const svo_compact_params *p, uint32_t *perm_
                                             "that a compaction replaces");
     if ((rc = svo_check_n_words(ctx, p->n_words))) return rc;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const double t0 = svo_now_ms();
-    // no pointer reaches a group behind 2^27, so the words behind it hold no reachable group
-    const uint32_t n_words = (uint32_t)std::min<uint64_t>(p->n_words, kMaxWords), cap = n_words / 8;
-    if ((rc = ensure_state(ctx, n_words, cap))) return rc;
+    if ((rc = svo_workspace_ensure(ctx, ctx->compact))) return rc;
     svo_compact_state *s = ctx->compact.get();
-    if ((rc = s->timer.begin(ctx))) return rc;
-    const uint32_t *st = s->status.host();
-    const bool prune = p->flags & SVO_COMPACT_PRUNE_EMPTY;
-
-    // the passes read the words: behind every earlier write to the store, whichever context issued it
-    if ((rc = svo_store_order_after_write(ctx))) return rc;
-    HIP_TRY(ctx, s->timer.mark(ctx, kEvStart));
-    HIP_TRY(ctx, s->status.zero(ctx));
-    // discover and check
-    svo_tree_walk walk{s->order, s->first_child, s->new_of, s->number, s->status, {}};
-    if ((rc = svo_tree_discover(ctx, p->n_words, &walk, s->timer.ev[kEvDiscover]))) return rc;
-    const std::vector<uint32_t> &level_off = walk.level_off;
+    if ((rc = s->begin(ctx, p->n_words, true))) return rc;
+    const std::vector<uint32_t> &level_off = s->walk.level_off;
     const uint32_t n_levels = (uint32_t)level_off.size() - 1, total = level_off[n_levels];
-    const uint32_t word_grid = svo_div_up(8ull * total, kThreads);
-    HIP_TRY(ctx, s->timer.mark(ctx, kEvCheck));
 
     // prune
-    if (prune) {
+    if (p->flags & SVO_COMPACT_PRUNE_EMPTY) {
         for (uint32_t l = n_levels; l-- > 0;) {
             const uint32_t m = level_off[l + 1] - level_off[l];
-            compact_live_kernel<<<svo_div_up(8ull * m, kThreads), kThreads, 0, ctx->stream>>>(ctx->nodes, s->order, level_off[l], m,
-                                                                                             s->first_child, s->live);
+            compact_live_kernel<<<svo_div_up(8ull * m, kThreads), kThreads, 0, ctx->stream>>>(ctx->nodes, s->walk.order, level_off[l], m,
+                                                                                             s->walk.first_child, s->number(), s->fate);
         }
         HIP_TRY(ctx, hipGetLastError());
     } else {
-        HIP_TRY(ctx, hipMemsetD32Async((hipDeviceptr_t)s->live, 1, total, ctx->stream));
+        HIP_TRY(ctx, hipMemsetD32Async((hipDeviceptr_t)s->number(), 1, total, ctx->stream));
+        HIP_TRY(ctx, hipMemsetD32Async((hipDeviceptr_t)s->fate.get(), (int)SVO_FATE_KEEP, total, ctx->stream));
     }
-    HIP_TRY(ctx, s->timer.mark(ctx, kEvPrune));
-
-    // emit
-    HIP_TRY(ctx, hipMemcpyAsync(s->number, s->live, total * sizeof(uint32_t), hipMemcpyDeviceToDevice, ctx->stream));
-    if ((rc = svo_scan_u32(ctx, s->number, total))) return rc;
-    compact_total_kernel<<<1, 1, 0, ctx->stream>>>(s->number, s->live, total, s->status.dev);
-    HIP_TRY(ctx, hipGetLastError());
-    if ((rc = s->status.read(ctx))) return rc;
-    if (st[kStDup]) return malformed(ctx, "a group is reached twice");
-    const uint32_t n_out = 8u * st[kStLive];
-    if (!n_out || n_out > n_words) return svo_fail(ctx, SVO_ERR_HIP, "the live groups' scan is out of range");  // (never: live[0] = 1)
-    compact_emit_kernel<<<word_grid, kThreads, 0, ctx->stream>>>(ctx->nodes, s->order, total, s->first_child, s->live, s->number, n_out,
-                                                                s->image, perm_out_dev);
-    HIP_TRY(ctx, hipGetLastError());
-    HIP_TRY(ctx, s->timer.mark(ctx, kEvEmit));
-
-    // copy back: behind every earlier write to the store (another context may have written while this one waited)
-    if ((rc = svo_store_order_after_write(ctx))) return rc;
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->nodes, s->image, size_t(n_out) * sizeof(uint32_t), hipMemcpyDeviceToDevice, ctx->stream));
-    if (p->n_words > n_out)
-        HIP_TRY(ctx, hipMemsetD32Async((hipDeviceptr_t)(ctx->nodes + n_out), (int)kEmptyWord, p->n_words - n_out, ctx->stream));
-    HIP_TRY(ctx, s->timer.mark(ctx, kEvEnd));
-    if ((rc = svo_store_note_write(ctx))) return rc;
-    *n_words_out = n_out;
-    s->timer.finish(t0);
-    return SVO_OK;
+    HIP_TRY(ctx, s->timer.mark(ctx, SVO_REWRITE_MIDDLE));
+    return s->finish(ctx, total, nullptr, 0, perm_out_dev, p->n_words, n_words_out);
 }
 
 int svo_compact_timing(svo_ctx *ctx, float ms_out[SVO_COMPACT_TIMES]) {

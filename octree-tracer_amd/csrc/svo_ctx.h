@@ -6,8 +6,10 @@
 // svo_stream (a stream).  The passes
 // share the rest as their host frame: svo_grow / svo_grow_pinned / svo_grow_keep (workspaces, by the buffers' own
 // sizes), svo_mirrored (device words with a pinned mirror), svo_pass_timer (events and times), svo_workspace_ensure
-// (creation) and the svo_check_* argument checks; then the builder's sort and svo_world_writer (a generated world's
-// directory).
+// (creation) and the svo_check_* argument checks; then what several passes run: the builder's sort and list front end,
+// svo_tree_walk (the discovery of a tree in the node buffer, with the workspace it owns), svo_tree_rewrite (a tree
+// rewritten into the canonical layout: the compaction's and the simplification's workspace and host frame),
+// svo_list_plan (a listing's counts and offsets) and svo_world_writer (a generated world's directory).
 // svo_scan.h (the tiled count, scan and emit with their launches), svo_group.h, svo_mip.h and svo_morton.h hold the device
 // pieces, svo_rules.h the walks and rules that svo_host.cpp and svo_adapt.hip both run.
 // What a frame launches is decided in plain C++ beside the context, not in it: svo_sched.h (the schedule's plans, the trace
@@ -450,36 +452,65 @@ int svo_build_list_leaves(svo_ctx *ctx, const uint32_t *xyz, const uint32_t *col
                           uint32_t default_colour, svo_build_leaves *out);
 // svo_compact.hip
 // The discovery of the tree in the first n_words words of the node buffer, for the
-// compaction, the simplification (svo_simplify.hip) and the voxel listing (svo_list.hip), on the ctx stream.  The caller owns the workspace: order, first_child,
-// new_of and scan of n_words / 8 u32 each, and status words that it has zeroed on the stream; the first SVO_WALK_STATUS
-// of them are the discovery's, and all of them come back once per level.  Afterwards
-// order[level_off[l], level_off[l + 1]) holds the old group starts of level l + 1 in the order of their parents,
-// first_child[k] the index in order of group k's first interior child, and level_off has one entry per level and the
-// total.  `discovered` (or null) is recorded before the check; the check's verdict is status[SVO_WALK_DUP] at the
-// caller's next read-back.  Malformed trees are refused here with the compaction's messages (SVO_ERR_STATE).
+// compaction, the simplification (svo_simplify.hip) and the voxel listing (svo_list.hip), on the ctx stream, into its
+// workspace: svo_tree_walk owns the four arrays of a u32 per group (grown together by grow(); scan is the scratch of the
+// discovery's scans and free afterwards) and the status words that create() allocates and the caller zeroes on the
+// stream; the first SVO_WALK_STATUS of them are the discovery's, and all of them come back once per level.  Afterwards order[level_off[l], level_off[l + 1]) holds the old
+// group starts of level l + 1 in the order of their parents, first_child[k] the index in order of group k's first
+// interior child, level_off has one entry per level and the total, and n_words and cap say what was walked: the words
+// clamped to 2^27 (no pointer reaches further) and the groups they hold.  `discovered` (or null) is recorded before the
+// check; the check's verdict is status[SVO_WALK_DUP] at the caller's next read-back.  Malformed trees are refused here
+// with the compaction's messages (SVO_ERR_STATE).
 enum { SVO_WALK_ALIGN, SVO_WALK_RANGE, SVO_WALK_NEXT, SVO_WALK_DUP, SVO_WALK_STATUS };
 struct svo_tree_walk {
-    uint32_t *order, *first_child, *new_of, *scan;
-    svo_mirrored<> &status;
-    std::vector<uint32_t> level_off;
-};
-int svo_tree_discover(svo_ctx *ctx, uint64_t n_words, svo_tree_walk *w, hipEvent_t discovered);
-// svo_list.hip
-// The plan of a listing (DESIGN.md 18), for svo_nodes_list_voxels and the surface pass (svo_surface.hip), each with a plan
-// of its own: the discovery's workspace, then per group k of order its entry and record counts (cnt, rcnt), the place of
-// its first entry and record in the list (start, rstart) and its Morton prefix (key: a leading 1, then 3 bits per level
-// above the group's words).  create() makes the status words, grow() room for `groups` groups.  svo_list_plan_count, on
-// the ctx stream: the discovery (`discovered`, or null, is recorded behind it), the counts bottom-up and their read-back;
-// it refuses, with the listing's messages and in its order, a malformed tree, a voxel or an interior word deeper than
-// `depth`, and 2^31 entries or more; then level_off (level l: order[level_off[l - 1], level_off[l])), listed = min(levels,
-// depth), count and n_rec hold.  svo_list_plan_offsets enqueues the top-down pass: start, rstart and key of the groups of
-// the levels 1..listed.
-struct svo_list_plan {
-    svo_dev<uint32_t> order, first_child, new_of, scan;  // the discovery's
-    svo_dev<uint32_t> rcnt, start, rstart;
-    svo_dev<uint64_t> cnt, key;
+    svo_dev<uint32_t> order, first_child, new_of, scan;
     svo_mirrored<> status;
     std::vector<uint32_t> level_off;
+    uint32_t n_words = 0, cap = 0;  // of the last discovery
+    int create(svo_ctx *ctx, size_t status_words) { return status.alloc(ctx, status_words); }
+    int grow(svo_ctx *ctx, size_t groups) { return svo_grow(ctx, groups, &order, &first_child, &new_of, &scan); }
+};
+int svo_tree_discover(svo_ctx *ctx, uint64_t n_words, svo_tree_walk *w, hipEvent_t discovered);
+// A tree rewritten into the canonical breadth-first layout, the workspace and the host
+// frame of the compaction and the simplification, each with an instance of its own: the walk, whose scan array is
+// `number`, a fate per group, the image of an in-place call, the six events and the status (the walk's words and the
+// kept groups' total).  The caller checks its arguments, then
+//   begin()   the workspace for n_words words (the image only in place), behind the store's last write: the start event,
+//             the status reset, the discovery and the check, the check's event
+//   middle    the caller's own launches give every group k of order[0, total) number[k] = 1 when it stays and 0 when it
+//             goes, and fate[k] = SVO_FATE_KEEP or the 28-bit field that its parent's word becomes (a child of one of
+//             them behind `total` has a fate too), then mark SVO_REWRITE_MIDDLE
+//   finish()  the scan of number, the read-back and the refusals (a group reached twice; out of place, more words than
+//             out_cap), all before the first write; the emit into the image or out_dev; in place the copy back, the fill
+//             of the freed tail [n_out, n_words_in) with the empty word and the note of the write; *n_words_out, the times
+enum { SVO_REWRITE_START, SVO_REWRITE_DISCOVER, SVO_REWRITE_CHECK, SVO_REWRITE_MIDDLE, SVO_REWRITE_EMIT, SVO_REWRITE_END, SVO_REWRITE_EVENTS };
+constexpr uint32_t SVO_FATE_KEEP = 0xFFFFFFFFu;  // (a field has 28 bits)
+struct svo_tree_rewrite {
+    svo_tree_walk walk;
+    svo_dev<uint32_t> image, fate;
+    svo_pass_timer<SVO_REWRITE_EVENTS, SVO_COMPACT_TIMES> timer;  // discover, check, the middle, emit, copy back, host wall
+    double t0 = 0.0;
+    uint32_t *number() const { return walk.scan; }
+    int create(svo_ctx *ctx);
+    int begin(svo_ctx *ctx, uint64_t n_words, bool in_place);
+    int finish(svo_ctx *ctx, uint32_t total, uint32_t *out_dev, uint64_t out_cap, uint32_t *perm_out_dev, uint64_t n_words_in,
+               uint64_t *n_words_out);
+};
+static_assert(SVO_SIMPLIFY_TIMES == SVO_COMPACT_TIMES, "the two rewrites share their timer");
+// svo_list.hip
+// The plan of a listing (DESIGN.md 18), for svo_nodes_list_voxels and the surface pass (svo_surface.hip), each with a plan
+// of its own: the discovery's workspace (walk), then per group k of order its entry and record counts (cnt, rcnt), the
+// place of its first entry and record in the list (start, rstart) and its Morton prefix (key: a leading 1, then 3 bits
+// per level above the group's words).  create() makes the status words, grow() room for `groups` groups.  svo_list_plan_count, on
+// the ctx stream: the discovery (`discovered`, or null, is recorded behind it), the counts bottom-up and their read-back;
+// it refuses, with the listing's messages and in its order, a malformed tree, a voxel or an interior word deeper than
+// `depth`, and 2^31 entries or more; then walk.level_off (level l: order[level_off[l - 1], level_off[l])), listed =
+// min(levels, depth), count and n_rec hold.  svo_list_plan_offsets enqueues the top-down pass: start, rstart and key of the
+// groups of the levels 1..listed.
+struct svo_list_plan {
+    svo_tree_walk walk;
+    svo_dev<uint32_t> rcnt, start, rstart;
+    svo_dev<uint64_t> cnt, key;
     uint32_t listed = 0, n_rec = 0;
     uint64_t count = 0;
     int create(svo_ctx *ctx);

@@ -5,7 +5,8 @@
 // not depend on where the groups sit in the buffer or on the run.  Every tree kernel gives 8 lanes to a group, one
 // word per lane (svo_group.h); sums and prefixes over a group are cross-lane operations inside its 8-lane segment.
 //
-//   discover  svo_tree_discover (svo_compact.hip): order, first_child, the levels; pointer checks, the reached-twice check
+//   discover  svo_tree_discover (svo_compact.hip) into the plan's svo_tree_walk: order, first_child, the levels; pointer
+//             checks, the reached-twice check
 //   count     bottom-up, one launch per level: cnt[k] = sum over the group's words of the entries a voxel gives (1, or
 //             8^(depth - level) with expand), cnt[child] for an interior word, 0 for the empty word; rcnt[k] the same
 //             for the voxels above `depth` that the expansion handles as records.  A level below `depth` only notes
@@ -199,7 +200,8 @@ uint32_t coarse_records(bool expand, uint32_t depth, uint32_t level) { return ex
 
 }  // namespace
 
-// Per-context workspace of the listing (svo_ctx::list): its plan (svo_ctx.h: eleven u32 per group), four u32 per record.
+// Per-context workspace of the listing (svo_ctx::list): its plan (svo_ctx.h: the walk's four u32 per group and seven of
+// its own), four u32 per record.
 struct svo_list_state {
     svo_list_plan plan;
     svo_dev<uint32_t> rec_start, rec_value;
@@ -212,21 +214,21 @@ struct svo_list_state {
     }
 };
 
-int svo_list_plan::create(svo_ctx *ctx) { return status.alloc(ctx, kStWords); }
+int svo_list_plan::create(svo_ctx *ctx) { return walk.create(ctx, kStWords); }
 
 int svo_list_plan::grow(svo_ctx *ctx, size_t groups) {
-    return svo_grow(ctx, groups, &order, &first_child, &new_of, &scan, &rcnt, &start, &rstart, &cnt, &key);
+    if (int rc = walk.grow(ctx, groups)) return rc;
+    return svo_grow(ctx, groups, &rcnt, &start, &rstart, &cnt, &key);
 }
 
 int svo_list_plan_count(svo_ctx *ctx, svo_list_plan *s, uint64_t n_words, uint32_t depth, bool expand, hipEvent_t discovered) {
-    const uint32_t *st = s->status.host();
-    HIP_TRY(ctx, s->status.zero(ctx));
+    svo_tree_walk &w = s->walk;
+    const uint32_t *st = w.status.host();
+    HIP_TRY(ctx, w.status.zero(ctx));
 
     // discover and check
-    svo_tree_walk walk{s->order, s->first_child, s->new_of, s->scan, s->status, {}};
-    if (int rc = svo_tree_discover(ctx, n_words, &walk, discovered)) return rc;
-    s->level_off = std::move(walk.level_off);  // level l: order[level_off[l - 1], level_off[l])
-    const std::vector<uint32_t> &level_off = s->level_off;
+    if (int rc = svo_tree_discover(ctx, n_words, &w, discovered)) return rc;
+    const std::vector<uint32_t> &level_off = w.level_off;  // level l: order[level_off[l - 1], level_off[l])
     const uint32_t n_levels = (uint32_t)level_off.size() - 1;
     s->listed = std::min(n_levels, depth);
 
@@ -235,12 +237,12 @@ int svo_list_plan_count(svo_ctx *ctx, svo_list_plan *s, uint64_t n_words, uint32
         const uint32_t off = level_off[l - 1], m = level_off[l] - off;
         const bool deep = l > depth;
         list_count_kernel<<<svo_div_up(8ull * m, kThreads), kThreads, 0, ctx->stream>>>(
-            ctx->nodes, s->order, off, m, s->first_child, deep ? 0ull : leaf_entries(expand, depth, l),
-            deep ? 0u : coarse_records(expand, depth, l), s->cnt, s->rcnt, deep ? s->status.dev + kStDeep + l : nullptr);
+            ctx->nodes, w.order, off, m, w.first_child, deep ? 0ull : leaf_entries(expand, depth, l),
+            deep ? 0u : coarse_records(expand, depth, l), s->cnt, s->rcnt, deep ? w.status.dev + kStDeep + l : nullptr);
     }
-    list_root_kernel<<<1, 1, 0, ctx->stream>>>(s->cnt, s->rcnt, s->status.dev, s->start, s->rstart, s->key);
+    list_root_kernel<<<1, 1, 0, ctx->stream>>>(s->cnt, s->rcnt, w.status.dev, s->start, s->rstart, s->key);
     HIP_TRY(ctx, hipGetLastError());
-    if (int rc = s->status.read(ctx)) return rc;
+    if (int rc = w.status.read(ctx)) return rc;
     if (st[SVO_WALK_DUP]) return svo_fail(ctx, SVO_ERR_STATE, "malformed tree: a group is reached twice");
     for (uint32_t l = n_levels; l > depth; l--)
         if (st[kStDeep + l])
@@ -255,10 +257,11 @@ int svo_list_plan_count(svo_ctx *ctx, svo_list_plan *s, uint64_t n_words, uint32
 
 int svo_list_plan_offsets(svo_ctx *ctx, svo_list_plan *s, uint32_t depth, bool expand) {
     // the levels that have listed levels below them
+    const svo_tree_walk &w = s->walk;
     for (uint32_t l = 1; l < s->listed; l++) {
-        const uint32_t off = s->level_off[l - 1], m = s->level_off[l] - off;
+        const uint32_t off = w.level_off[l - 1], m = w.level_off[l] - off;
         list_offsets_kernel<<<svo_div_up(8ull * m, kThreads), kThreads, 0, ctx->stream>>>(
-            ctx->nodes, s->order, off, m, s->first_child, leaf_entries(expand, depth, l), coarse_records(expand, depth, l), s->cnt,
+            ctx->nodes, w.order, off, m, w.first_child, leaf_entries(expand, depth, l), coarse_records(expand, depth, l), s->cnt,
             s->rcnt, s->start, s->rstart, s->key);
     }
     HIP_TRY(ctx, hipGetLastError());
@@ -303,8 +306,8 @@ int svo_nodes_list_voxels(svo_ctx *ctx, const svo_list_params *p, uint32_t *xyz_
 
         // emit
         const ListOut out{xyz_out_dev, value_out_dev, level_out_dev, (uint32_t)count, s->rec_start, s->rec_value, s->rec_key, n_rec};
-        const uint32_t m = pl.level_off[pl.listed];
-        list_emit_kernel<<<svo_div_up(8ull * m, kThreads), kThreads, 0, ctx->stream>>>(ctx->nodes, pl.order, m, pl.first_child, pl.cnt,
+        const uint32_t m = pl.walk.level_off[pl.listed];
+        list_emit_kernel<<<svo_div_up(8ull * m, kThreads), kThreads, 0, ctx->stream>>>(ctx->nodes, pl.walk.order, m, pl.walk.first_child, pl.cnt,
                                                                                        pl.rcnt, pl.start, pl.rstart, pl.key, depth, expand,
                                                                                        out);
         if (n_rec) list_expand_kernel<<<svo_div_up(count, kThreads), kThreads, 0, ctx->stream>>>(depth, out);

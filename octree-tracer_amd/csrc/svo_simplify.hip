@@ -1,10 +1,11 @@
 // svo_simplify.hip -- the tree in the node buffer simplified: SVO_SIMPLIFY_MERGE turns an interior word
 // whose whole subtree holds one leaf value into that leaf, SVO_SIMPLIFY_CUT turns every interior word of one level into a
 // leaf of its subtree's mip colour; the rest comes out in the compaction's canonical breadth-first layout, in place or
-// into a buffer of the caller's.  The compaction's discovery and its 8 lanes per group (svo_group.h) with a reduce in
-// the place of its prune:
+// into a buffer of the caller's.  The compaction's frame (svo_tree_rewrite, svo_compact.hip) and its 8 lanes per group
+// (svo_group.h) with a reduce in the place of its prune:
 //
-//   discover  svo_tree_discover (svo_compact.hip): order, first_child, the levels; pointer checks, the reached-twice check
+//   begin     svo_tree_rewrite::begin: the workspace, the discovery (order, first_child, the levels; the pointer checks)
+//             and the reached-twice check
 //   reduce    bottom-up, one launch per level behind the launches of the levels below it.  A group of a level BELOW
 //             cut_level gets val[k] = S, the mip of its eight words: byte sums and the count of the non-zero values packed
 //             into two registers and added over the group's 8 lanes by three shuffles each.  A group AT or ABOVE cut_level
@@ -13,12 +14,11 @@
 //             when the level may merge), compares it with the group's first lane, and the group's byte of the ballot
 //             decides.  The same launch gives every child its fate: the field its parent word is rewritten to, or kKeep,
 //             and number[child] = kept
-//   emit      the groups whose words lie at or above cut_level are the candidates.  One exclusive scan of number gives
-//             every kept group its new number; a kept group's ancestors are kept (a word is rewritten only together with
-//             every word below it), so the order is still breadth-first.  An interior lane whose child is not kept writes
-//             the leaf word of the child's fate: the tree is rewritten on the fly, never in the node buffer
-//   copy back in place only: one device-to-device copy of the image and one fill of the freed tail with the empty word.
-//             Out of place the emit writes the caller's buffer and the node buffer is only read
+//   finish    svo_tree_rewrite::finish over the candidates, the groups whose words lie at or above cut_level: the scan of
+//             number, the refusals, the emit and, in place only, the copy back.  A kept group's ancestors are kept (a word
+//             is rewritten only together with every word below it), so the order is still breadth-first; an interior lane
+//             whose child is not kept writes the leaf word of the child's fate: the tree is rewritten on the fly, never
+//             in the node buffer.  Out of place the emit writes the caller's buffer and the node buffer is only read
 //
 // No atomics and no LDS: the order is the contract.  Every error is decided before the emit.
 #include <hip/hip_runtime.h>
@@ -28,14 +28,12 @@
 #include <vector>
 
 #include "svo_ctx.h"
-#include "svo_group.h"  // (group_lane: 8 lanes per group; kMaxWords)
-#include "svo_scan.h"   // (svo_scan_u32)
+#include "svo_group.h"  // (group_lane: 8 lanes per group)
 
 namespace {
 
 constexpr uint32_t kNone = 0xFFFFFFFFu;  // val: no uniform field (a field has 28 bits)
-constexpr uint32_t kKeep = 0xFFFFFFFFu;  // fate: the group stays
-enum Status { kStLive = SVO_WALK_STATUS, kStWords };
+constexpr uint32_t kKeep = SVO_FATE_KEEP;  // fate: the group stays
 enum Mode { kModeMip, kModeCut, kModeMerge };  // a level below cut_level, cut_level itself, any other
 
 // The level order[off, off + n), behind the launches of the levels below it.  may_merge: SVO_SIMPLIFY_MERGE is set and
@@ -81,46 +79,12 @@ __global__ __launch_bounds__(kThreads) void simplify_reduce_kernel(const uint32_
     }
 }
 
-__global__ void simplify_total_kernel(const uint32_t *number, const uint32_t *fate, uint32_t n, uint32_t *status) {
-    status[kStLive] = number[n - 1] + (fate[n - 1] == kKeep ? 1u : 0u);
-}
-
-// The candidates order[0, n): a kept group's words, an interior word as the pointer to its child's new place or as the
-// leaf of the child's fate.
-__global__ __launch_bounds__(kThreads) void simplify_emit_kernel(const uint32_t *words, const uint32_t *order, uint32_t n,
-                                                                 const uint32_t *first_child, const uint32_t *fate,
-                                                                 const uint32_t *number, uint32_t n_out, uint32_t *image, uint32_t *perm) {
-    const uint32_t i = blockIdx.x * kThreads + threadIdx.x, k = i >> 3, c = i & 7u;
-    const bool valid = k < n;
-    const GroupLane g = group_lane(words, order, k, c, valid);
-    if (!valid || fate[k] != kKeep) return;
-    uint32_t out = g.word;
-    if (g.interior) {
-        const uint32_t child = first_child[k] + g.below, to = fate[child];  // (a child behind the candidates has a fate too)
-        out = to == kKeep ? ((8u * number[child]) << 4 | (g.word & 15u)) : to << 4;
-    }
-    const uint32_t at = 8u * number[k] + c;
-    if (at < n_out) {  // (always: n_out is the scan's total)
-        image[at] = out;
-        if (perm) perm[at] = order[k] + c;
-    }
-}
-
-enum Ev { kEvStart, kEvDiscover, kEvCheck, kEvReduce, kEvEmit, kEvEnd, kEvs };
-
 }  // namespace
 
-// Per-context workspace of the simplification (svo_ctx::simplify): the image and six u32 per group.
-struct svo_simplify_state {
-    svo_dev<uint32_t> image;  // the words of an in-place call before they are copied back
-    svo_dev<uint32_t> order, first_child, new_of, number, val, fate;
-    svo_mirrored<> status;  // kStWords words
-    svo_pass_timer<kEvs, SVO_SIMPLIFY_TIMES> timer;
-
-    int create(svo_ctx *ctx) {
-        HIP_TRY(ctx, timer.create());
-        return status.alloc(ctx, kStWords);
-    }
+// Per-context workspace of the simplification (svo_ctx::simplify): the rewrite's (svo_ctx.h: five u32 per group and, for
+// in-place calls, the image) and a sixth u32 per group.
+struct svo_simplify_state : svo_tree_rewrite {
+    svo_dev<uint32_t> val;  // the mip or the uniform field of a group
 };
 
 extern "C" {
@@ -144,66 +108,26 @@ int svo_nodes_simplify(svo_ctx *ctx, const svo_simplify_params *p, uint32_t *out
                                             "that an in-place simplification replaces");
     if ((rc = svo_check_n_words(ctx, p->n_words))) return rc;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const double t0 = svo_now_ms();
-    // no pointer reaches a group behind 2^27, so the words behind it hold no reachable group
-    const uint32_t n_words = (uint32_t)std::min<uint64_t>(p->n_words, kMaxWords), cap = n_words / 8;
     if ((rc = svo_workspace_ensure(ctx, ctx->simplify))) return rc;
     svo_simplify_state *s = ctx->simplify.get();
-    if (!out_dev && (rc = svo_grow(ctx, n_words, &s->image))) return rc;
-    if ((rc = svo_grow(ctx, cap, &s->order, &s->first_child, &s->new_of, &s->number, &s->val, &s->fate))) return rc;
-    if ((rc = s->timer.begin(ctx))) return rc;
-    const uint32_t *st = s->status.host();
-
-    // the passes read the words: behind every earlier write to the store, whichever context issued it
-    if ((rc = svo_store_order_after_write(ctx))) return rc;
-    HIP_TRY(ctx, s->timer.mark(ctx, kEvStart));
-    HIP_TRY(ctx, s->status.zero(ctx));
-    // discover and check
-    svo_tree_walk walk{s->order, s->first_child, s->new_of, s->number, s->status, {}};
-    if ((rc = svo_tree_discover(ctx, p->n_words, &walk, s->timer.ev[kEvDiscover]))) return rc;
-    const std::vector<uint32_t> &level_off = walk.level_off;
+    if ((rc = s->begin(ctx, p->n_words, !out_dev)) || (rc = svo_grow(ctx, s->walk.cap, &s->val))) return rc;
+    const std::vector<uint32_t> &level_off = s->walk.level_off;
     const uint32_t n_levels = (uint32_t)level_off.size() - 1;
-    HIP_TRY(ctx, s->timer.mark(ctx, kEvCheck));
 
     // reduce: the words of order[level_off[l], level_off[l + 1]) are of level l + 1
     for (uint32_t l = n_levels; l-- > 0;) {
         const uint32_t level = l + 1, m = level_off[l + 1] - level_off[l];
         const int mode = cut && level > p->cut_level ? kModeMip : cut && level == p->cut_level ? kModeCut : kModeMerge;
         simplify_reduce_kernel<<<svo_div_up(8ull * m, kThreads), kThreads, 0, ctx->stream>>>(
-            ctx->nodes, s->order, level_off[l], m, s->first_child, mode, merge && level >= p->min_level, merge, s->val, s->fate, s->number);
+            ctx->nodes, s->walk.order, level_off[l], m, s->walk.first_child, mode, merge && level >= p->min_level, merge, s->val, s->fate,
+            s->number());
     }
     HIP_TRY(ctx, hipGetLastError());
-    HIP_TRY(ctx, s->timer.mark(ctx, kEvReduce));
+    HIP_TRY(ctx, s->timer.mark(ctx, SVO_REWRITE_MIDDLE));
 
-    // emit: the groups below cut_level are cut off
+    // the candidates of the emit: the groups below cut_level are cut off
     const uint32_t total = level_off[cut ? std::min(n_levels, p->cut_level) : n_levels];
-    if ((rc = svo_scan_u32(ctx, s->number, total))) return rc;
-    simplify_total_kernel<<<1, 1, 0, ctx->stream>>>(s->number, s->fate, total, s->status.dev);
-    HIP_TRY(ctx, hipGetLastError());
-    if ((rc = s->status.read(ctx))) return rc;
-    if (st[SVO_WALK_DUP]) return svo_fail(ctx, SVO_ERR_STATE, "malformed tree: a group is reached twice");
-    const uint32_t n_out = 8u * st[kStLive];
-    if (!n_out || n_out > n_words) return svo_fail(ctx, SVO_ERR_HIP, "the kept groups' scan is out of range");  // (never: the root stays)
-    if (out_dev && n_out > p->out_cap)
-        return svo_fail(ctx, SVO_ERR_CAP, "the simplified tree has " + std::to_string(n_out) + " words, more than out_cap = " +
-                                              std::to_string(p->out_cap));
-    simplify_emit_kernel<<<svo_div_up(8ull * total, kThreads), kThreads, 0, ctx->stream>>>(
-        ctx->nodes, s->order, total, s->first_child, s->fate, s->number, n_out, out_dev ? out_dev : s->image.get(), perm_out_dev);
-    HIP_TRY(ctx, hipGetLastError());
-    HIP_TRY(ctx, s->timer.mark(ctx, kEvEmit));
-
-    if (!out_dev) {
-        // copy back: behind every earlier write to the store (another context may have written while this one waited)
-        if ((rc = svo_store_order_after_write(ctx))) return rc;
-        HIP_TRY(ctx, hipMemcpyAsync(ctx->nodes, s->image, size_t(n_out) * sizeof(uint32_t), hipMemcpyDeviceToDevice, ctx->stream));
-        if (p->n_words > n_out)
-            HIP_TRY(ctx, hipMemsetD32Async((hipDeviceptr_t)(ctx->nodes + n_out), (int)kEmptyWord, p->n_words - n_out, ctx->stream));
-    }
-    HIP_TRY(ctx, s->timer.mark(ctx, kEvEnd));
-    if (!out_dev && (rc = svo_store_note_write(ctx))) return rc;
-    *n_words_out = n_out;
-    s->timer.finish(t0);
-    return SVO_OK;
+    return s->finish(ctx, total, out_dev, p->out_cap, perm_out_dev, p->n_words, n_words_out);
 }
 
 int svo_simplify_timing(svo_ctx *ctx, float ms_out[SVO_SIMPLIFY_TIMES]) {

@@ -268,9 +268,9 @@ int svo_nodes_list_surface(svo_ctx *ctx, const svo_surface_params *p, uint32_t *
         if ((rc = svo_list_plan_offsets(ctx, &s->plan, depth, false))) return rc;
         HIP_TRY(ctx, s->timer.mark(ctx, kEvOffsets));
 
-        const uint32_t m = pl.level_off[pl.listed];
+        const uint32_t m = pl.walk.level_off[pl.listed];
         surface_mask_kernel<<<svo_div_up(m, kThreads), kThreads, 0, ctx->stream>>>(
-            ctx->nodes, pl.order, m, pl.first_child, pl.cnt, pl.start, pl.key, p->flags & SVO_SURFACE_CLOSED_BOUNDARY ? 1u : 0u, n_list,
+            ctx->nodes, pl.walk.order, m, pl.walk.first_child, pl.cnt, pl.start, pl.key, p->flags & SVO_SURFACE_CLOSED_BOUNDARY ? 1u : 0u, n_list,
             s->ent_key, s->ent_value, s->ent_mask);
         HIP_TRY(ctx, hipGetLastError());
         HIP_TRY(ctx, s->timer.mark(ctx, kEvMask));

@@ -4,17 +4,23 @@ compact()          from the contract, sequentially: the groups reachable from gr
                    order of its parents; with `prune` a group is dead when each word, counter ignored, is the empty word
                    or points at a dead group (the root never is), a word pointing at a dead group becomes the empty
                    word and dead groups are dropped; pointers rewritten, counters kept.
-compact_parallel() the same result the way the kernels reach it: per level the interior counts of the frontier, their
-                   exclusive scan, the children scattered behind the frontier; plain stores of new_of and the test for
-                   a group reached twice; live bottom-up per level; one scan of live; the emit.
+compact_parallel() the same result the way the kernels reach it: discover(), live bottom-up per level, emit().
+discover()         the walk that the compaction, the simplification and the listing share (svo_tree_discover): per level
+                   the interior counts of the frontier, their exclusive scan, the children scattered behind the
+                   frontier; plain stores of new_of and the test for a group reached twice.  simplify_ref and list_ref
+                   call it.
+emit()             the canonical layout that the compaction and the simplification share (svo_tree_rewrite::finish): one
+                   scan of the kept groups, then every kept group's words with the interior ones rewritten by the
+                   child's fate.
 
-Both return (out, perm) with perm[new word] = old word and raise Malformed on a tree the device refuses.
+compact() and compact_parallel() return (out, perm) with perm[new word] = old word and raise Malformed on a tree the device refuses.
 """
 import numpy as np
 
 from build_ref import EMPTY, VOXEL_OFFSET
 
 MAX_LEVELS = 31
+KEEP = 0xFFFFFFFF  # a group's fate: it stays (any other: the 28-bit field that its parent's word becomes)
 
 
 class Malformed(ValueError):
@@ -76,30 +82,24 @@ def exclusive_scan(a):
     return np.cumsum(a) - a
 
 
-def compact_parallel(words, n_words, prune):
-    check_length(words, n_words)
-    w = np.asarray(words, dtype=np.uint32)[:n_words].astype(np.int64)
+def discover(w, n_words):
+    """the discovery and the check of the int64 words w (svo_tree_discover): (order, first_child, level_off).  order grows
+    by one frontier per level, first_child[k] indexes order, order[level_off[l]:level_off[l + 1]] is level l + 1"""
     cap = n_words // 8
     lanes = np.arange(8)
-
-    def groups(starts):  # (groups, 8) words and their interior masks
-        g = w[starts[:, None] + lanes]
-        return g, (g >> 4) < VOXEL_OFFSET
-
-    # discover: order grows by one frontier per level; first_child[k] indexes order
     order = np.zeros(1, dtype=np.int64)
     first_child = np.zeros(0, dtype=np.int64)
     level_off = [0]
     off, n, level = 0, 1, 1
     while True:
-        g, interior = groups(order[off:off + n])
+        g = w[order[off:off + n, None] + lanes]
+        interior = (g >> 4) < VOXEL_OFFSET
         pointers = g[interior] >> 4  # row-major: scan + the interior lanes below
         if (pointers % 8).any():
             raise Malformed("a pointer is not a multiple of 8")
         if (pointers + 8 > n_words).any():
             raise Malformed("a pointer leaves the words")
-        count = interior.sum(axis=1)
-        first_child = np.concatenate([first_child, off + n + exclusive_scan(count)])
+        first_child = np.concatenate([first_child, off + n + exclusive_scan(interior.sum(axis=1))])
         if off + n + pointers.size > cap:
             raise Malformed("a group is reached twice (more groups than n_words / 8)")
         order = np.concatenate([order, pointers])
@@ -110,27 +110,48 @@ def compact_parallel(words, n_words, prune):
         if level == MAX_LEVELS:
             raise Malformed(f"deeper than {MAX_LEVELS} levels")
         n, level = pointers.size, level + 1
-    total = off
     # check: whichever of two stores wins, one of the two groups sees the other's number
     new_of = np.full(cap, -1, dtype=np.int64)
-    new_of[order // 8] = np.arange(total)
-    if (new_of[order // 8] != np.arange(total)).any():
+    new_of[order // 8] = np.arange(off)
+    if (new_of[order // 8] != np.arange(off)).any():
         raise Malformed("a group is reached twice")
+    return order, first_child, level_off
+
+
+def group_words(w, order, first_child):
+    """per group of order its (groups, 8) words, their interior mask and the children's indices in order (0 where the
+    word is not interior)"""
+    g = w[order[:, None] + np.arange(8)]
+    interior = (g >> 4) < VOXEL_OFFSET
+    return g, interior, np.where(interior, first_child[:, None] + np.cumsum(interior, axis=1) - interior, 0)
+
+
+def emit(w, order, first_child, fate, cand):
+    """the emit of the canonical layout (svo_tree_rewrite::finish): of the candidates order[:cand] the groups with fate KEEP
+    stay, numbered by one scan; an interior word links its child's new place or becomes the leaf of the child's fate"""
+    g, interior, child = (a[:cand] for a in group_words(w, order, first_child))
+    kept = fate[:cand] == KEEP
+    number = np.zeros(order.size, dtype=np.int64)
+    number[:cand] = exclusive_scan(kept.astype(np.int64))
+    to = fate[child]  # (a child behind the candidates has a fate too)
+    linked = np.where(to == KEEP, (8 * number[child]) << 4 | g & 15, to << 4)
+    out = np.where(interior, linked, g)[kept].reshape(-1)
+    perm = (order[:cand, None] + np.arange(8))[kept].reshape(-1)
+    return out.astype(np.uint32), perm.astype(np.uint32)
+
+
+def compact_parallel(words, n_words, prune):
+    check_length(words, n_words)
+    w = np.asarray(words, dtype=np.uint32)[:n_words].astype(np.int64)
+    order, first_child, level_off = discover(w, n_words)
     # prune: bottom-up, a launch per level
-    live = np.ones(total, dtype=np.int64)
-    g, interior = groups(order)
-    child = first_child[:, None] + np.cumsum(interior, axis=1) - interior  # (valid where interior)
+    live = np.ones(order.size, dtype=np.int64)
     if prune:
+        g, interior, child = group_words(w, order, first_child)
         for l in range(len(level_off) - 2, -1, -1):
             lo, hi = level_off[l], level_off[l + 1]
-            keeps = np.where(interior[lo:hi], live[np.where(interior[lo:hi], child[lo:hi], 0)] != 0, (g[lo:hi] >> 4) != VOXEL_OFFSET)
+            keeps = np.where(interior[lo:hi], live[child[lo:hi]] != 0, (g[lo:hi] >> 4) != VOXEL_OFFSET)
             live[lo:hi] = keeps.any(axis=1)
         live[0] = 1
-    # emit
-    number = exclusive_scan(live)
-    safe = np.where(interior, child, 0)
-    linked = np.where(live[safe] != 0, (8 * number[safe]) << 4 | g & 15, EMPTY)
-    rows = live != 0
-    out = np.where(interior, linked, g)[rows].reshape(-1)
-    perm = (order[:, None] + lanes)[rows].reshape(-1)
-    return out.astype(np.uint32), perm.astype(np.uint32)
+    # emit: a dead group's parent word becomes the empty word
+    return emit(w, order, first_child, np.where(live != 0, KEEP, VOXEL_OFFSET), order.size)

@@ -3,7 +3,7 @@
 list_voxels()   from the contract, sequentially: a depth-first walk from group 0 by child index; every voxel word
                 (word >> 4 > VOXEL_OFFSET, counter ignored) is an entry (minimum corner on the `depth` grid, value, level);
                 with `expand` a voxel above `depth` becomes its cells of the `depth` grid in Morton order.
-list_parallel() the same result the way the kernels reach it: the compaction's discovery (frontier per level, order,
+list_parallel() the same result the way the kernels reach it: compact_ref.discover() (frontier per level, order,
                 first_child, the reached-twice test), entry and record counts bottom-up per level, starts and Morton
                 prefixes top-down per level, the emit, and for the expansion the search of the record that covers an entry.
 
@@ -14,7 +14,7 @@ of several causes the first in that order.
 import numpy as np
 
 from build_ref import VOXEL_OFFSET
-from compact_ref import MAX_LEVELS, Malformed, check_length, exclusive_scan
+from compact_ref import MAX_LEVELS, Malformed, check_length, discover, exclusive_scan, group_words
 
 MAX_ENTRIES = 1 << 31
 
@@ -107,42 +107,13 @@ def list_parallel(words, n_words, depth, expand=False):
     if not 1 <= depth <= 21:
         raise ValueError(f"depth must be 1..21 (got {depth})")
     w = np.asarray(words, dtype=np.uint32)[:n_words].astype(np.int64)
-    cap = n_words // 8
-    lanes = np.arange(8)
 
-    # discover and check: compact_ref.compact_parallel's, cut down to what the listing keeps
-    order = np.zeros(1, dtype=np.int64)
-    first_child = np.zeros(0, dtype=np.int64)
-    level_off = [0]
-    off, n, level = 0, 1, 1
-    while True:
-        g = w[order[off:off + n, None] + lanes]
-        interior = (g >> 4) < VOXEL_OFFSET
-        pointers = g[interior] >> 4
-        if (pointers % 8).any():
-            raise Malformed("a pointer is not a multiple of 8")
-        if (pointers + 8 > n_words).any():
-            raise Malformed("a pointer leaves the words")
-        first_child = np.concatenate([first_child, off + n + exclusive_scan(interior.sum(axis=1))])
-        if off + n + pointers.size > cap:
-            raise Malformed("a group is reached twice (more groups than n_words / 8)")
-        order = np.concatenate([order, pointers])
-        off += n
-        level_off.append(off)
-        if not pointers.size:
-            break
-        if level == MAX_LEVELS:
-            raise Malformed(f"deeper than {MAX_LEVELS} levels")
-        n, level = pointers.size, level + 1
-    total, n_levels = off, len(level_off) - 1
-    new_of = np.full(cap, -1, dtype=np.int64)
-    new_of[order // 8] = np.arange(total)
-    dup = (new_of[order // 8] != np.arange(total)).any()
-
-    g = w[order[:, None] + lanes]
+    # discover and check; a group reached twice is refused here, ahead of the counts, which refuse nothing themselves
+    order, first_child, level_off = discover(w, n_words)
+    total, n_levels = order.size, len(level_off) - 1
+    g, interior, child = group_words(w, order, first_child)
     pointer = g >> 4
-    interior, voxel = pointer < VOXEL_OFFSET, pointer > VOXEL_OFFSET
-    child = np.where(interior, first_child[:, None] + np.cumsum(interior, axis=1) - interior, 0)
+    voxel = pointer > VOXEL_OFFSET
     leaf = lambda l: 8 ** (depth - l) if expand else 1  # noqa: E731
     coarse = lambda l: 1 if expand and l < depth else 0  # noqa: E731
 
@@ -157,8 +128,6 @@ def list_parallel(words, n_words, depth, expand=False):
             continue
         cnt[lo:hi] = np.where(interior[lo:hi], cnt[child[lo:hi]], np.where(voxel[lo:hi], leaf(l), 0).astype(object)).sum(axis=1)
         rcnt[lo:hi] = np.where(interior[lo:hi], rcnt[child[lo:hi]], np.where(voxel[lo:hi], coarse(l), 0)).sum(axis=1)
-    if dup:
-        raise Malformed("a group is reached twice")
     if deep:
         raise TooDeep(deep, depth)
     count, n_rec = int(cnt[0]), int(rcnt[0])

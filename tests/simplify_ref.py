@@ -2,9 +2,9 @@
 
 simplify()          from the contract, sequentially: S and U computed recursively, the words rewritten (CUT, then MERGE),
                     then compact_ref.compact(words, n, prune=False) of the rewritten words.
-simplify_parallel() the same result the way the kernels reach it: the discovery, per level bottom-up the reduce over
-                    order / first_child (the mip below cut_level, the uniform field and the children's fates at and above
-                    it), one scan of the kept groups, the emit that rewrites on the fly.
+simplify_parallel() the same result the way the kernels reach it: compact_ref.discover(), per level bottom-up the reduce
+                    over order / first_child (the mip below cut_level, the uniform field and the children's fates at and
+                    above it), then compact_ref.emit() over the candidates, which rewrites on the fly.
 merged_cells() /    the per-cell statement on a dense grid: after MERGE every cell samples to what it sampled before; after
 cut_cells()         CUT at L every cell samples to S of its level-L cube, or to its old value where the tree ended above L.
 mip_pyramid()       S of every cube of every level straight from a dense grid of unit cells, without the tree.
@@ -18,7 +18,7 @@ import compact_ref as K
 import sample_ref as S_
 from build_ref import VOXEL_OFFSET
 
-NONE = 0xFFFFFFFF  # no uniform field; as a fate: the group stays
+NONE = K.KEEP  # no uniform field; as a fate: the group stays
 MERGE, CUT = 1, 2
 
 
@@ -113,51 +113,13 @@ def tally(words, n_words, merge=True, cut_level=None, min_level=0):
     return rewrite(words, n_words, merge, cut_level, min_level)[1]
 
 
-def discover(w, n_words):
-    """compact_ref.compact_parallel's discovery and check: (order, first_child, level_off)"""
-    cap = n_words // 8
-    lanes = np.arange(8)
-    order = np.zeros(1, dtype=np.int64)
-    first_child = np.zeros(0, dtype=np.int64)
-    level_off = [0]
-    off, n, level = 0, 1, 1
-    while True:
-        g = w[order[off:off + n, None] + lanes]
-        interior = (g >> 4) < VOXEL_OFFSET
-        pointers = g[interior] >> 4
-        if (pointers % 8).any():
-            raise K.Malformed("a pointer is not a multiple of 8")
-        if (pointers + 8 > n_words).any():
-            raise K.Malformed("a pointer leaves the words")
-        count = interior.sum(axis=1)
-        first_child = np.concatenate([first_child, off + n + K.exclusive_scan(count)])
-        if off + n + pointers.size > cap:
-            raise K.Malformed("a group is reached twice (more groups than n_words / 8)")
-        order = np.concatenate([order, pointers])
-        off += n
-        level_off.append(off)
-        if not pointers.size:
-            break
-        if level == K.MAX_LEVELS:
-            raise K.Malformed(f"deeper than {K.MAX_LEVELS} levels")
-        n, level = pointers.size, level + 1
-    new_of = np.full(cap, -1, dtype=np.int64)
-    new_of[order // 8] = np.arange(off)
-    if (new_of[order // 8] != np.arange(off)).any():
-        raise K.Malformed("a group is reached twice")
-    return order, first_child, level_off
-
-
 def simplify_parallel(words, n_words, merge=True, cut_level=None, min_level=0):
     check_params(merge, cut_level, min_level)
     K.check_length(words, n_words)
     w = np.asarray(words, dtype=np.uint32)[:n_words].astype(np.int64)
-    lanes = np.arange(8)
-    order, first_child, level_off = discover(w, n_words)
+    order, first_child, level_off = K.discover(w, n_words)
     n_levels, total = len(level_off) - 1, level_off[-1]
-    g = w[order[:, None] + lanes]
-    interior = (g >> 4) < VOXEL_OFFSET
-    child = np.where(interior, first_child[:, None] + np.cumsum(interior, axis=1) - interior, 0)
+    g, interior, child = K.group_words(w, order, first_child)
     # reduce: bottom-up, a launch per level; the words of order[level_off[l], level_off[l + 1]) are of level l + 1
     val = np.zeros(total, dtype=np.int64)
     fate = np.full(total, NONE, dtype=np.int64)
@@ -184,16 +146,9 @@ def simplify_parallel(words, n_words, merge=True, cut_level=None, min_level=0):
         same = (field == field[:, :1]).all(axis=1) & (field[:, 0] != NONE)
         val[lo:hi] = np.where(same, field[:, 0], NONE) if merge else NONE
     fate[0] = NONE
-    # emit: the groups below cut_level are cut off; one scan of the kept groups
+    # emit: the groups below cut_level are cut off
     cand = level_off[min(n_levels, cut_level)] if cut_level is not None else total
-    kept = fate[:cand] == NONE
-    number = np.zeros(total, dtype=np.int64)
-    number[:cand] = K.exclusive_scan(kept.astype(np.int64))
-    to = fate[child[:cand]]
-    linked = np.where(to == NONE, (8 * number[child[:cand]]) << 4 | g[:cand] & 15, to << 4)
-    out = np.where(interior[:cand], linked, g[:cand])[kept].reshape(-1)
-    perm = (order[:cand, None] + lanes)[kept].reshape(-1)
-    return out.astype(np.uint32), perm.astype(np.uint32)
+    return K.emit(w, order, first_child, fate, cand)
 
 
 def cells(words, n_words, depth):

@@ -1,7 +1,7 @@
 """Trees simplified on the GPU (csrc/svo_simplify.hip): words and perm against the restatements of the contract
 (tests/simplify_ref.py) on the host test's scenes, for MERGE, CUT and both, in place and out of place, with and without
-perm; the same bytes for every layout of a tree and on every run; level sizes around the wave and the block, a depth-1
-tree and a depth-21 chain; counters, the freed tail, nothing written behind n_words, out of place nothing written at all
+perm; the same bytes for every layout of a tree and on every run; level sizes around the wave and the block, a merge
+that rewrites nothing against the compaction's bytes, a depth-1 tree and a depth-21 chain; counters, the freed tail, nothing written behind n_words, out of place nothing written at all
 and no sharing context disturbed; every error in its order with all buffers unchanged; the cells and the expanded list
 before and after a merge; edits and compactions of a merged tree; frames of merged and cut trees against the oracle; a
 solid mesh merged at the build."""
@@ -19,6 +19,7 @@ import region_ref as G
 import simplify_ref as R
 from conftest import ROOT as REPO, assert_hits_equal, load_vox_fixture
 from pass_frame import SENTINEL, SentinelOut, assert_words, last_error, own_gpu  # noqa: F401
+from test_compact_gpu import tree7  # noqa: F401
 from test_compact_host import malformed_cases
 from test_edit_gpu import CAPACITY, PAD, ROOT, frame, poison, set_base
 from test_simplify_host import assert_frames_alike, scenes
@@ -188,6 +189,21 @@ def test_level_sizes_around_the_wave_and_the_block(pkg, render):
                 assert np.array_equal(want, R.simplify(words, words.size, *mode)[0])
             if uniform_every == 1:
                 assert R.simplify(words, words.size)[0].size < words.size
+
+
+def test_a_simplification_that_merges_nothing_is_the_compaction(pkg, render, tree7):
+    """both entries run one emit: on the compaction's depth-7 tree (more than a scan tile of groups in a level, levels that
+    end in partial waves) a merge that may not start above level 8 rewrites no word, and what is left is the layout"""
+    words = tree7["words"]
+    want, want_perm = tree7[False]
+    set_base(render, words)
+    n, perm = render.simplify_nodes(merge=True, min_level=8, with_perm=True)
+    assert n == want.size == render.node_length
+    got = render.read_nodes(words.size + PAD)
+    assert_words(got[:n], want, "depth 7 edited, nothing to merge")
+    assert (got[n:words.size] == B.EMPTY).all(), "the freed tail is not empty"
+    assert np.array_equal(got[words.size:], poison(PAD)), "words behind n_words were written"
+    assert np.array_equal(perm.cpu().numpy().view(np.uint32), want_perm), "perm"
 
 
 def test_depth_1_and_the_depth_21_chain(pkg, render):
