@@ -493,6 +493,75 @@ int svo_nodes_edit_region(svo_ctx *ctx, const svo_region_shape *shapes, size_t n
 #define SVO_REGION_TIMES 5
 int svo_region_timing(svo_ctx *ctx, float ms_out[SVO_REGION_TIMES]);
 
+/* ---- two device trees combined: paste, fill, paint, carve and mask by a tree ----
+ * Edits the scene A, the first n_words words of the node buffer, in place by the source B, the src_words words at src_dev (a
+ * DEVICE buffer on the ctx's device, rooted at group 0, ONLY READ), top-down, touching only the words where both trees have
+ * something to say.  A leaf's value is (word >> 4) - SVO_VOXEL_OFFSET, all bits; 0 means empty; the source's hit counters are
+ * ignored.  The source's root cube is the scene's cell `at` of level at_level (0: the whole cube).  Per cell, with s = depth -
+ * at_level: a cell c of the `depth` grid with c >> s == at samples (svo_nodes_sample) afterwards to f(a, b), a = what the scene
+ * sampled at c before, b = what the source samples at c - (at << s) on a grid of depth s, and f by op:
+ *     OVER   b ? b : a          UNDER  a ? a : b          PAINT    (a && b) ? b : a
+ *     CARVE  b ? 0 : a          KEEP   b ? a : 0          REPLACE  b
+ * Every cell outside the cube samples as before.
+ * The words are deterministic, the same bytes on every run (no atomics: the order is the contract), by this rule.  The tree is
+ * processed level by level from the root group; the frontier of level l + 1 is the eight children, by child index, of every
+ * word of level l that was opened or split, those taken in frontier order.  A frontier entry pairs a scene word -- real, or a
+ * virtual child of a split, which holds one leaf value -- with what the source has for the same cube: OUT (the cube lies outside
+ * the source's), PATH (a level above at_level on the way to `at`: as an interior word whose child towards `at` is PATH again, or
+ * at at_level the source's root, an interior word pointing at the source's group 0, and whose seven other children are OUT), a
+ * source leaf b or the constant b carried down from one, or a source interior word.  With at_level == 0 the level-1 frontier is
+ * the scene's root group against the source's root group.  For one entry:
+ *     source OUT:  the scene word and everything below it keep all 32 bits
+ *     source leaf or constant b, scene leaf a:  v = f(a, b); v != a writes the leaf word of v, counter 0; otherwise untouched
+ *     source leaf or constant b, scene interior:  by f(., b).  The identity (OVER, UNDER, PAINT, CARVE with b == 0; KEEP with b
+ *         != 0): untouched with its subtree.  A constant c (OVER with b != 0: b; CARVE with b != 0: 0; KEEP with b == 0: 0;
+ *         REPLACE: b): the word COLLAPSES to the leaf word of c (its subtree is cut off, for svo_nodes_compact to drop).
+ *         Otherwise (UNDER, PAINT with b != 0) it is OPENED: its eight children are each paired with the constant b
+ *     source interior or PATH, scene interior:  both are opened, their children paired by child index
+ *     source interior or PATH, scene leaf a (real or virtual):  when f(a, .) is a whatever the source holds (UNDER with a != 0;
+ *         PAINT, CARVE, KEEP with a == 0) untouched, and the source below is not looked at.  Otherwise it is SPLIT: a new group
+ *         of eight leaf words OF a, counter 0, is made, the word becomes the pointer to it, and the eight virtual children are
+ *         paired with the source's children.  THE COLOUR IS CARRIED DOWN, as in svo_nodes_edit_region and unlike svo_nodes_edit
+ * Opening or splitting at level `depth` is refused: SVO_ERR_STATE, nothing written, svo_last_error names the cell and which
+ * tree is finer there.  No word below level `depth` is made or opened.
+ * New groups are appended by level and within a level in frontier order: the g-th split gets the group n_words + 8 g, and
+ * *n_words_out = n_words + 8 * splits.  Nothing at or behind *n_words_out is touched.  A second identical call on the result
+ * writes nothing and appends nothing.  Merging equal siblings is svo_nodes_simplify's job afterwards; free groups are not
+ * reused.  A source group reached through two pointers is allowed: the source is only read, the result holds copies, and
+ * `depth` ends any cycle.
+ * Every error is decided by a read-only plan before any write; of several causes the first in this order is reported.
+ * SVO_ERR_ARG: NULL p, n_words_out or src_dev; op > 5; depth outside 1..21; at_level >= depth; an `at` coordinate >= 2^at_level.
+ * SVO_ERR_STATE: no node buffer; a device adaptive state attached to the context.  SVO_ERR_ARG: n_words not a positive multiple
+ * of 8 or above the capacity; src_words not a positive multiple of 8 or above 2^27; [src_dev, src_dev + src_words) overlapping
+ * the node buffer's allocation.  SVO_ERR_STATE: the "malformed tree: ..." causes with svo_nodes_compact's wording, on the scene
+ * words that the call opens (an interior pointer that is not a multiple of 8 or with pointer + 8 > n_words, a group reached
+ * twice); "malformed source: ..." for a source pointer that the call follows and that is not a multiple of 8 or has pointer + 8
+ * > src_words; the refusal above.  SVO_ERR_CAP when the exact new length exceeds max_words, the capacity or 2^27.
+ * Runs on the ctx stream; the source's words must be complete when the call is made.  Blocks once per level, to read back the
+ * next frontier's size and the level's split count, and once more for the status.  The fill and the writes are enqueued (a
+ * following svo_render on the stream sees the result), ordered and recorded like svo_nodes_write, so every context sharing the
+ * buffer rebuilds its top table and schedule. */
+#define SVO_COMBINE_OVER    0u  /* f(a,b) = b ? b : a        paste: the source's voxels over the scene */
+#define SVO_COMBINE_UNDER   1u  /* f(a,b) = a ? a : b        fill: the source's voxels into the scene's empty cells */
+#define SVO_COMBINE_PAINT   2u  /* f(a,b) = (a && b) ? b : a recolour the scene's voxels where the source has one */
+#define SVO_COMBINE_CARVE   3u  /* f(a,b) = b ? 0 : a        remove the scene where the source is solid */
+#define SVO_COMBINE_KEEP    4u  /* f(a,b) = b ? a : 0        keep the scene only where the source is solid */
+#define SVO_COMBINE_REPLACE 5u  /* f(a,b) = b                the source's cube as it is, empties included */
+typedef struct svo_combine_params {
+    uint32_t op;         /* 0..5 */
+    uint32_t depth;      /* 1..21: the scene grid; no word below this level is made or opened */
+    uint32_t at_level;   /* 0..depth-1: the source's root cube is the scene's cell `at` of this level (0: the whole cube) */
+    uint32_t at[3];      /* < 2^at_level each */
+    uint64_t n_words;    /* the scene: words [0, n_words) of the node buffer */
+    uint64_t src_words;  /* the source: words [0, src_words) at src_dev, rooted at group 0 */
+    uint64_t max_words;  /* 0 = the capacity; never above SVO_VOXEL_OFFSET */
+} svo_combine_params;
+int svo_nodes_combine(svo_ctx *ctx, const uint32_t *src_dev, const svo_combine_params *p, uint64_t *n_words_out);
+/* Times (ms) of the last combine: [0] plan (with its per-level read-backs), [1] status, [2] fill, [3] write (device events;
+ * waits for the write), [4] host wall time of the call.  A refused call leaves the times of the last one that ran. */
+#define SVO_COMBINE_TIMES 5   /* plan (with its per-level read-backs), status, fill, write, host wall */
+int svo_combine_timing(svo_ctx *ctx, float ms_out[SVO_COMBINE_TIMES]);
+
 /* ---- the tree in the node buffer compacted in place ----
  * Reads the first n_words words of the node buffer as a tree rooted at group 0.  E = SVO_VOXEL_OFFSET << 4 is the empty
  * word; a word is interior when word >> 4 < SVO_VOXEL_OFFSET.

@@ -307,6 +307,23 @@ class Render {  // render.rs:3-285
         gpu_.poll_wait();
         return new_words;
     }
+    // the first n_words words of the node buffer, the scene, combined in place with the source tree in the src_words words at
+    // src_dev (device, only read) (svo_nodes_combine): per cell op (SVO_COMBINE_OVER .. SVO_COMBINE_REPLACE)
+    // decides between the scene's value and the source's; the source's cube is the scene's cell `at` of level at_level (null
+    // and 0: the whole scene).  Coarse leaves stay coarse, a split leaf keeps its colour; returns the new length.  Throws,
+    // with nothing written, where either tree is finer than depth and the op has to look below.
+    uint64_t combine_nodes(uint64_t n_words, const uint32_t *src_dev, uint64_t src_words, uint32_t op, uint32_t depth,
+                           const uint32_t *at = nullptr, uint32_t at_level = 0, uint64_t max_words = 0) {
+        if (depth > declared_depth_) {
+            gpu_.set_option(SVO_OPT_TREE_DEPTH, depth);
+            declared_depth_ = depth;
+        }
+        const svo_combine_params p{op, depth, at_level, {at ? at[0] : 0u, at ? at[1] : 0u, at ? at[2] : 0u}, n_words, src_words, max_words};
+        uint64_t new_words = 0;
+        gpu_.check(svo_nodes_combine(gpu_.ctx(), src_dev, &p, &new_words));
+        gpu_.poll_wait();  // the source may go away
+        return new_words;
+    }
     // the first n_words words of the node buffer compacted in place (svo_nodes_compact): unreachable groups
     // dropped, with `prune` also the groups that hold nothing, the rest in the builder's breadth-first order; returns the
     // new length.  perm_dev (device, n_words u32, or null): perm[new word] = old word.  Throws, with nothing written, for

@@ -87,6 +87,19 @@ class RegionParams(C.Structure):
     ]
 
 
+class CombineParams(C.Structure):
+    """svo_combine_params: the tree in the node buffer combined with a second tree (include/svo_hip.h)."""
+    _fields_ = [
+        ("op", C.c_uint32),
+        ("depth", C.c_uint32),
+        ("at_level", C.c_uint32),
+        ("at", C.c_uint32 * 3),
+        ("n_words", C.c_uint64),
+        ("src_words", C.c_uint64),
+        ("max_words", C.c_uint64),
+    ]
+
+
 class CompactParams(C.Structure):
     """svo_compact_params: the tree in the node buffer compacted in place (include/svo_hip.h)."""
     _fields_ = [
@@ -281,6 +294,8 @@ DEVICE_SIGNATURES = {
     "svo_edit_timing": (C.c_int, (vp, fp)),
     "svo_nodes_edit_region": (C.c_int, (vp, C.POINTER(RegionShape), sz, C.POINTER(RegionParams), C.POINTER(u64))),
     "svo_region_timing": (C.c_int, (vp, fp)),
+    "svo_nodes_combine": (C.c_int, (vp, vp, C.POINTER(CombineParams), C.POINTER(u64))),
+    "svo_combine_timing": (C.c_int, (vp, fp)),
     "svo_nodes_compact": (C.c_int, (vp, C.POINTER(CompactParams), vp, C.POINTER(u64))),
     "svo_compact_timing": (C.c_int, (vp, fp)),
     "svo_nodes_simplify": (C.c_int, (vp, C.POINTER(SimplifyParams), vp, vp, C.POINTER(u64))),

@@ -1,6 +1,6 @@
 // svo_ctx.h -- the device context behind the opaque `svo_ctx` of include/svo_hip.h, and the host helpers of the files that
 // use it: svo_abi.cpp (trace / scan dispatch), svo_comm.cpp (RCCL frame gather) and the GPU tree passes (svo_proc.hip,
-// svo_build.hip, svo_edit.hip, svo_region.hip, svo_compact.hip, svo_simplify.hip, svo_list.hip, svo_sample.hip, svo_voxelize.hip, svo_solid.hip,
+// svo_build.hip, svo_edit.hip, svo_region.hip, svo_combine.hip, svo_compact.hip, svo_simplify.hip, svo_list.hip, svo_sample.hip, svo_voxelize.hip, svo_solid.hip,
 // svo_structure.hip, svo_surface.hip, svo_adapt.hip).  One rule of ownership for the context, the node store and every
 // pass's state: a member owns what it holds, as svo_dev / svo_pinned (an allocation and its size), svo_events (events) or
 // svo_stream (a stream).  The passes
@@ -10,8 +10,8 @@
 // svo_tree_walk (the discovery of a tree in the node buffer, with the workspace it owns), svo_tree_rewrite (a tree
 // rewritten into the canonical layout: the compaction's and the simplification's workspace and host frame),
 // svo_list_plan (a listing's counts and offsets) and svo_world_writer (a generated world's directory).
-// svo_scan.h (the tiled count, scan and emit with their launches), svo_group.h, svo_mip.h and svo_morton.h hold the device
-// pieces, svo_rules.h the walks and rules that svo_host.cpp and svo_adapt.hip both run.
+// svo_scan.h (the tiled count, scan and emit with their launches), svo_frontier.h (the check and the commit of the two
+// top-down edits), svo_group.h, svo_mip.h and svo_morton.h hold the device pieces, svo_rules.h the walks and rules that svo_host.cpp and svo_adapt.hip both run.
 // What a frame launches is decided in plain C++ beside the context, not in it: svo_sched.h (the schedule's plans, the trace
 // kernel and its grid) and svo_deal.h (the static deal).  The context keeps what those decisions go by between frames: the
 // options, the schedule slots, and per STACK instantiation the resident workgroups per CU that the runtime answered.
@@ -146,6 +146,7 @@ struct svo_edit_state;
 struct svo_compact_state;
 struct svo_simplify_state;
 struct svo_region_state;
+struct svo_combine_state;
 struct svo_list_state;
 struct svo_sample_state;
 struct svo_voxelize_state;
@@ -259,6 +260,7 @@ struct svo_ctx {
     svo_workspace<svo_compact_state> compact{nullptr, nullptr};  // compaction's workspace (svo_compact.hip)
     svo_workspace<svo_simplify_state> simplify{nullptr, nullptr};  // simplification's workspace (svo_simplify.hip)
     svo_workspace<svo_region_state> region{nullptr, nullptr};  // shape edits' workspace (svo_region.hip)
+    svo_workspace<svo_combine_state> combine{nullptr, nullptr};  // the workspace of two trees combined (svo_combine.hip)
     svo_workspace<svo_list_state> list{nullptr, nullptr};  // voxel listing's workspace (svo_list.hip)
     svo_workspace<svo_sample_state> sample{nullptr, nullptr};  // sampling's events and times (svo_sample.hip)
     svo_workspace<svo_voxelize_state> voxelize{nullptr, nullptr};  // mesh voxeliser's workspace (svo_voxelize.hip)

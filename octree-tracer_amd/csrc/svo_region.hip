@@ -25,13 +25,13 @@
 #include <string>
 
 #include "svo_ctx.h"
+#include "svo_frontier.h"  // (kNone, leaf_word, the mark and check kernels, the fill and write kernels, grow_list: shared with svo_combine.hip)
 #include "svo_scan.h"  // (svo_scan_u32, block_min, min_of_blocks_kernel; svo_group.h: kThreads, kEmptyWord, kMaxWords)
 
 static_assert(sizeof(svo_region_shape) == 32, "a shape is two uint4 in LDS");
 
 namespace {
 
-constexpr uint32_t kNone = 0xFFFFFFFFu;
 constexpr uint32_t kCellBits = 21, kCellMask = (1u << kCellBits) - 1u;  // a record's cell: x << 42 | y << 21 | z
 enum Class : uint32_t { kOut, kPart, kFull };
 enum Code : uint32_t { kOpen = 1u, kSplit = 2u };  // kOpen: eight children in the next frontier; kSplit: ... of a new group
@@ -66,7 +66,6 @@ __host__ __device__ inline uint32_t shape_class(const uint4 &p, const uint4 &q, 
 }
 
 __host__ __device__ inline bool mode_applies(uint32_t mode, uint32_t v) { return (v ? mode & SVO_REGION_VOXELS : mode & SVO_REGION_EMPTY) != 0u; }
-__host__ __device__ inline uint32_t leaf_word(uint32_t v) { return (uint32_t(SVO_VOXEL_OFFSET) + v) << 4; }
 
 // What the lane of frontier word i knows of it: where it is, the word as it stands and the word's cell on its level.
 struct Entry {
@@ -196,41 +195,8 @@ __global__ __launch_bounds__(kThreads) void region_emit_kernel(const uint32_t *_
     next_key[k] = uint64_t(e.x) << (2 * kCellBits) | uint64_t(e.y) << kCellBits | e.z;
 }
 
-// A group reached through a pointer is reached once: the groups [0, n) of a frontier, numbered from `first_id` on, mark
-// themselves in new_of (kNone: not reached yet).  A mark that is there already, from an earlier level or from another lane
-// of this launch, is a second path; so is a mark that another lane of this launch overwrote, which the check finds.
-__global__ __launch_bounds__(kThreads) void region_mark_kernel(const uint32_t *__restrict__ gbase, const uint32_t *__restrict__ gvirt, uint32_t n,
-                                                               uint32_t first_id, uint32_t cap, uint32_t *new_of, uint32_t *status) {
-    const uint32_t k = blockIdx.x * kThreads + threadIdx.x;
-    if (k >= n || gvirt[k] || (gbase[k] >> 3) >= cap) return;
-    if (new_of[gbase[k] >> 3] != kNone) status[kStDup] = 1u;
-    else new_of[gbase[k] >> 3] = first_id + k;
-}
-__global__ __launch_bounds__(kThreads) void region_check_kernel(const uint32_t *__restrict__ gbase, const uint32_t *__restrict__ gvirt, uint32_t n,
-                                                                uint32_t first_id, uint32_t cap, const uint32_t *__restrict__ new_of,
-                                                                uint32_t *status) {
-    const uint32_t k = blockIdx.x * kThreads + threadIdx.x;
-    if (k >= n || gvirt[k] || (gbase[k] >> 3) >= cap) return;
-    if (new_of[gbase[k] >> 3] != first_id + k) status[kStDup] = 1u;
-}
-
-// The commit: the eight leaf words of every new group, one lane per word ...
-__global__ __launch_bounds__(kThreads) void region_fill_kernel(uint32_t *__restrict__ words, uint32_t new_words, const uint32_t *__restrict__ list_at,
-                                                               const uint32_t *__restrict__ list_word, const uint32_t *__restrict__ list_fill,
-                                                               uint32_t n) {
-    const uint32_t t = blockIdx.x * kThreads + threadIdx.x, i = t >> 3, c = t & 7u;
-    if (i >= n || list_at[i] == kNone) return;
-    const uint32_t pointer = list_word[i] >> 4;
-    if (pointer < SVO_VOXEL_OFFSET && uint64_t(pointer) + 8u <= new_words) words[pointer + c] = list_fill[i];  // (a split's entry)
-}
-// ... and then the list, one lane per entry.
-__global__ __launch_bounds__(kThreads) void region_write_kernel(uint32_t *__restrict__ words, uint32_t new_words, const uint32_t *__restrict__ list_at,
-                                                                const uint32_t *__restrict__ list_word, uint32_t n) {
-    const uint32_t i = blockIdx.x * kThreads + threadIdx.x;
-    if (i >= n) return;
-    const uint32_t at = list_at[i];
-    if (at < new_words) words[at] = list_word[i];  // (kNone is not below it)
-}
+// (region_mark_kernel and region_check_kernel, a group reached twice, and the commit's region_fill_kernel and
+// region_write_kernel: svo_frontier.h)
 
 enum Ev { kEvStart, kEvPlan, kEvStatus, kEvFill, kEvEnd, kEvs };
 
@@ -279,15 +245,6 @@ int check_shapes(svo_ctx *ctx, const svo_region_shape *shapes, size_t n, uint32_
         if (s.kind == SVO_REGION_BALL && s.b[0] > (1u << 23))
             return svo_fail(ctx, SVO_ERR_ARG, who + ": a ball's radius is at most 2^23 half cells (got " + std::to_string(s.b[0]) + ")");
     }
-    return SVO_OK;
-}
-
-// room for `want` items in a list whose first `keep` items stay, at least doubled so that the levels' growth copies little
-int grow_list(svo_ctx *ctx, size_t want, size_t keep, svo_dev<uint32_t> *a, svo_dev<uint32_t> *b, svo_dev<uint32_t> *c) {
-    if (a->size() >= want) return SVO_OK;  // (the three grow together)
-    want = std::max(want, 2 * a->size());
-    for (svo_dev<uint32_t> *buf : {a, b, c})
-        if (int rc = svo_grow_keep(ctx, want, buf, keep)) return rc;
     return SVO_OK;
 }
 

@@ -6,7 +6,7 @@ import torch
 
 from . import sharding
 from ._device import device_u32, voxel_list, wait_for_torch
-from ._lib import BuildParams, CompactParams, EditParams, ListParams, RegionParams, SampleParams, SimplifyParams, SitesParams, StampParams, SurfaceParams, TopsParams, Uniforms, lib
+from ._lib import BuildParams, CombineParams, CompactParams, EditParams, ListParams, RegionParams, SampleParams, SimplifyParams, SitesParams, StampParams, SurfaceParams, TopsParams, Uniforms, lib
 from .camera import camera_matrices
 
 F_PAUSE_ADAPTIVE, F_SHOW_STEPS, F_SHOW_HITS, F_SHADOWS, F_MISC_BOOL = 1, 2, 4, 8, 16
@@ -20,6 +20,7 @@ TOP_NONE = -1  # what column_tops returns for a column that holds nothing: SVO_T
 # structure_sites and stamp_structures know a bound of their list before they call (the columns, placements x voxels): up
 # to this many entries they fill room for the bound in one call and return its first part, without the count query
 ONE_CALL_ENTRIES = 1 << 20
+COMBINE_OPS = ("over", "under", "paint", "carve", "keep", "replace")  # combine_nodes: SVO_COMBINE_OVER .. SVO_COMBINE_REPLACE
 
 
 class Render:
@@ -182,6 +183,55 @@ class Render:
         wait_for_torch(self.gpu)
         self.gpu.check(lib().svo_nodes_edit_region(self.gpu._h, arr, n, C.byref(p), C.byref(out)))
         self.gpu.sync()
+        self.node_length = out.value
+        return out.value
+
+    def combine_nodes(self, source, op="over", depth=None, at=(0, 0, 0), at_level=0, max_words=None):
+        """Combine the tree that is in the node buffer, the scene, with a second device tree, the source, in place
+        (svo_nodes_combine).  source: another Render on the same device (its first node_length words), a
+        device int32 tensor of words, or a (tensor, length) pair as simplify_nodes(out_of_place=True) returns; it is only
+        read.  op, a name of COMBINE_OPS or its number, per cell with a the scene's value and b the source's: "over" b or
+        else a (paste), "under" a or else b (fill the empty cells), "paint" b where both hold a voxel, "carve" empty where
+        the source holds a voxel, "keep" empty where it holds none, "replace" b.  The source's cube is the scene's cell `at`
+        of level at_level (0: the whole scene) and is `depth - at_level` levels deep; the cells outside it stay as they are.
+        Coarse leaves stay coarse: a subtree that the source decides as a whole becomes one leaf, a leaf on the source's
+        surface is split and keeps its colour in the children.  Where either tree is finer than `depth` and the op has to
+        look below, SvoError is raised and nothing is written.  depth=None: the depth declared for this tree.  Returns the
+        new length (node_length)."""
+        depth = int(self.gpu.tree_depth if depth is None else depth)
+        if isinstance(op, str):
+            if op not in COMBINE_OPS:
+                raise ValueError(f"op must be one of {', '.join(COMBINE_OPS)} (got {op!r})")
+            op = COMBINE_OPS.index(op)
+        if isinstance(source, Render):
+            if source.gpu.device != self.gpu.device:
+                raise ValueError(f"the source is on device {source.gpu.device}, the scene on device {self.gpu.device}")
+            ptr, room = C.c_void_p(), C.c_size_t()
+            source.gpu.check(lib().svo_nodes_device_ptr(source.gpu._h, C.byref(ptr), C.byref(room)))
+            source.gpu.sync()  # (its words may still be on their way on its own stream)
+            src_ptr, src_words = ptr.value, int(source.node_length)
+        else:
+            words, length = source if isinstance(source, tuple) else (source, None)
+            words = device_u32(words, self.gpu.torch_device, what="source").reshape(-1)
+            src_words = int(words.numel() if length is None else length)
+            if src_words > words.numel():
+                raise ValueError(f"the source holds {words.numel()} words, fewer than its length {src_words}")
+            src_ptr = words.data_ptr() if words.numel() else None
+        if len(at) != 3:
+            raise ValueError(f"at must be three cell coordinates, got {at!r}")
+        self.gpu.declare_depth(depth)
+        p = CombineParams()
+        p.op = max(0, int(op))
+        p.depth = max(0, depth)
+        p.at_level = max(0, int(at_level))
+        p.at[:] = [min(max(0, int(v)), 0xFFFFFFFF) for v in at]
+        p.n_words = int(self.node_length)
+        p.src_words = src_words
+        p.max_words = int(max_words or 0)
+        out = C.c_uint64()
+        wait_for_torch(self.gpu)
+        self.gpu.check(lib().svo_nodes_combine(self.gpu._h, src_ptr, C.byref(p), C.byref(out)))
+        self.gpu.sync()  # (the source may be released by the caller)
         self.node_length = out.value
         return out.value
 
