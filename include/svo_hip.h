@@ -750,6 +750,57 @@ int svo_nodes_list_surface(svo_ctx *ctx, const svo_surface_params *p, uint32_t *
 #define SVO_SURFACE_TIMES 7
 int svo_surface_timing(svo_ctx *ctx, float ms_out[SVO_SURFACE_TIMES]);
 
+/* ---- the visible surface merged into rectangles on the device ----
+ * Input: the exposed faces of the tree [0, n_words), exactly as svo_nodes_list_surface with SVO_SURFACE_QUADS defines them;
+ * the same rule, boundary flag and errors apply.  A face f of a leaf at level l with minimum corner m on the `depth` grid
+ * has s = 2^(depth - l), a = f >> 1, ua = (a + 1) % 3 and va = (a + 2) % 3, and is the rectangle
+ *     face = f, plane = m[a] + (f & 1) * s (0 .. 2^depth), u0 = m[ua], v0 = m[va], w = h = s, value.
+ * The input rectangles of one (face, plane) are pairwise disjoint.
+ * Merge: one round is a U phase followed by a V phase.
+ *     U phase: among rectangles with equal (face, plane, v0, h), B follows A when B.u0 == A.u0 + A.w and B.value ==
+ *     A.value.  Every maximal chain becomes one rectangle (u0 of the first, w = the sum of the widths).
+ *     V phase: the same with u and v, w and h exchanged: the class is (face, plane, u0, w), and B follows A when
+ *     B.v0 == A.v0 + A.h.
+ * rounds is 1 to 4; 1 is the classic two-pass greedy mesher.  Later rounds matter only for mixed-level trees, where a
+ * 2 x 2 made of unit faces can then join a coarse leaf's 2 x 2.  The phases are defined on sets, so the result does not
+ * depend on the input order or on the tree's layout.  SVO_SURFACE_MERGE_ANY_VALUE drops the value condition and reports
+ * value 0 for every rectangle (collision and occluder meshes).
+ * Output: rect_out_dev has 6 u32 per entry: face, plane, u0, v0, w, h; value_out_dev has 1 u32 per entry.  The entries
+ * ascend by (face, plane, u0, w, v0), the last V phase's order, which is unique because the rectangles are disjoint.
+ * rect_out_dev == NULL is a count query: *n_out gets the number of entries, nothing else is written and max_entries is
+ * ignored.  Otherwise both are DEVICE pointers with room for max_entries entries, of which only the entries [0, *n_out) are
+ * written.  The node buffer is never written.  No atomics: the same bytes on every run and for every layout of the same
+ * tree; the low 4 bits of a word never matter.
+ * Errors are decided before any write to the outputs and leave them and *n_out as they were; they are
+ * svo_nodes_list_surface's, in its order and with its wording: SVO_ERR_ARG: NULL p or n_out; unknown or incompatible flag
+ * bits, which here covers rounds outside 1..4 too; depth outside 1..21; NULL value_out_dev with rect_out_dev given;
+ * SVO_ERR_STATE: no node buffer; SVO_ERR_ARG: n_words; SVO_ERR_STATE: the "malformed tree: ..." causes; SVO_ERR_ARG: a voxel
+ * or an interior word at a level deeper than `depth`; SVO_ERR_CAP, with the exact count in svo_last_error: 2^31 voxels or
+ * more, 2^31 exposed faces or more, then more rectangles than max_entries (not for a count query).  A device adaptive
+ * state attached to the context is no obstacle.
+ * Runs on the ctx stream behind the store's last write, whichever context issued it, and records no write of its own.
+ * Blocks where svo_nodes_list_surface blocks (once per level of the tree, once for the counts, once for the number of
+ * faces) and once per phase for the number of rectangles it leaves, 2 * rounds times at most: a round that joins nothing
+ * is the last.  The fill is enqueued (svo_sync before the outputs are read on another stream).  The pass has a surface
+ * workspace of its own and sorts in the builder's (svo_nodes_build), whose times it leaves alone. */
+#define SVO_SURFACE_MERGE_ANY_VALUE 8u  /* rectangles join whatever their values; every value comes out 0 */
+typedef struct svo_surface_merge_params {
+    uint32_t flags;        /* SVO_SURFACE_CLOSED_BOUNDARY, SVO_SURFACE_MERGE_ANY_VALUE */
+    uint32_t depth;        /* 1..21: the grid the coordinates are given on */
+    uint32_t rounds;       /* 1..4 */
+    uint32_t reserved;     /* not looked at */
+    uint64_t n_words;      /* the tree: words [0, n_words) of the node buffer, rooted at group 0 */
+    uint64_t max_entries;  /* room in the output arrays, in entries */
+} svo_surface_merge_params;
+int svo_nodes_merge_surface(svo_ctx *ctx, const svo_surface_merge_params *p, uint32_t *rect_out_dev, uint32_t *value_out_dev,
+                            uint64_t *n_out);
+/* Times (ms) of the last merge: [0] the quads (svo_nodes_list_surface's passes, with their read-backs), then four per
+ * phase, the U phase of round 1 first: [1 + 4 k] keys, [2 + 4 k] the two sorts and the gather, [3 + 4 k] flags and scan
+ * (with its read-back), [4 + 4 k] emit (0 for a phase that did not run), [33] the output's fill (device events; waits for
+ * it; next to 0 for a count query), [34] host wall time of the call.  A refused call leaves the times of the last call that ran. */
+#define SVO_SURFACE_MERGE_TIMES 35
+int svo_surface_merge_timing(svo_ctx *ctx, float ms_out[SVO_SURFACE_MERGE_TIMES]);
+
 /* ---- the tree in the node buffer sampled on the device ----
  * What is at a cell of the `depth` grid, read from the first n_words words of the node buffer as a tree rooted at group 0;
  * coordinates, child index and levels are those of svo_nodes_build, svo_nodes_edit and svo_nodes_list_voxels.  For the

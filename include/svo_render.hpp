@@ -379,6 +379,20 @@ class Render {  // render.rs:3-285
         gpu_.poll_wait();
         return n;
     }
+    // that surface merged into rectangles on the GPU (svo_nodes_merge_surface): the exposed faces of
+    // SVO_SURFACE_QUADS, joined along u and then along v, `rounds` (1..4) times, where faces of one plane and one value
+    // touch; rects_dev (6 * max_entries u32: face, plane, u0, v0, w, h) and values_dev (max_entries) are DEVICE pointers;
+    // flags: SVO_SURFACE_CLOSED_BOUNDARY, SVO_SURFACE_MERGE_ANY_VALUE (faces join whatever their values; every value 0).
+    // Returns the entry count; rects_dev null: the count alone.  Throws, with nothing written, for what list_surface
+    // throws and for more rectangles than max_entries.
+    uint64_t surface_rects(uint64_t n_words, uint32_t depth, uint32_t *rects_dev, uint32_t *values_dev, uint64_t max_entries,
+                           uint32_t flags = 0, uint32_t rounds = 1) {
+        const svo_surface_merge_params p{flags, depth, rounds, 0u, n_words, max_entries};
+        uint64_t n = 0;
+        gpu_.check(svo_nodes_merge_surface(gpu_.ctx(), &p, rects_dev, values_dev, &n));
+        gpu_.poll_wait();
+        return n;
+    }
     // a triangle mesh voxelised on the GPU, conservatively and exactly (svo_mesh_voxelize): vq_dev
     // (3 * n_vertices quantised coordinates, 64 per cell of the 2^depth grid), tri_dev (3 * n_tris vertex indices),
     // tri_colours_dev (n_tris x 0x00RRGGBB, or null: `colour`) and the outputs xyz_dev (3 * max_voxels u32), colours_dev

@@ -141,6 +141,18 @@ class SurfaceParams(C.Structure):
     ]
 
 
+class SurfaceMergeParams(C.Structure):
+    """svo_surface_merge_params: the visible surface merged into rectangles (include/svo_hip.h)."""
+    _fields_ = [
+        ("flags", C.c_uint32),
+        ("depth", C.c_uint32),
+        ("rounds", C.c_uint32),
+        ("reserved", C.c_uint32),
+        ("n_words", C.c_uint64),
+        ("max_entries", C.c_uint64),
+    ]
+
+
 class SampleParams(C.Structure):
     """svo_sample_params: the tree in the node buffer sampled on the device (include/svo_hip.h)."""
     _fields_ = [
@@ -304,6 +316,8 @@ DEVICE_SIGNATURES = {
     "svo_list_timing": (C.c_int, (vp, fp)),
     "svo_nodes_list_surface": (C.c_int, (vp, C.POINTER(SurfaceParams), vp, vp, vp, vp, C.POINTER(u64))),
     "svo_surface_timing": (C.c_int, (vp, fp)),
+    "svo_nodes_merge_surface": (C.c_int, (vp, C.POINTER(SurfaceMergeParams), vp, vp, C.POINTER(u64))),
+    "svo_surface_merge_timing": (C.c_int, (vp, fp)),
     "svo_nodes_sample": (C.c_int, (vp, C.POINTER(SampleParams), vp, sz, vp, vp, vp)),
     "svo_nodes_sample_dense": (C.c_int, (vp, C.POINTER(SampleParams), C.POINTER(u32), C.POINTER(u32), vp)),
     "svo_sample_timing": (C.c_int, (vp, fp)),

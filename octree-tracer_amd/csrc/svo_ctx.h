@@ -1,7 +1,7 @@
 // svo_ctx.h -- the device context behind the opaque `svo_ctx` of include/svo_hip.h, and the host helpers of the files that
 // use it: svo_abi.cpp (trace / scan dispatch), svo_comm.cpp (RCCL frame gather) and the GPU tree passes (svo_proc.hip,
 // svo_build.hip, svo_edit.hip, svo_region.hip, svo_combine.hip, svo_compact.hip, svo_simplify.hip, svo_list.hip, svo_sample.hip, svo_voxelize.hip, svo_solid.hip,
-// svo_structure.hip, svo_surface.hip, svo_adapt.hip).  One rule of ownership for the context, the node store and every
+// svo_structure.hip, svo_surface.hip, svo_surface_merge.hip, svo_adapt.hip).  One rule of ownership for the context, the node store and every
 // pass's state: a member owns what it holds, as svo_dev / svo_pinned (an allocation and its size), svo_events (events) or
 // svo_stream (a stream).  The passes
 // share the rest as their host frame: svo_grow / svo_grow_pinned / svo_grow_keep (workspaces, by the buffers' own
@@ -153,6 +153,7 @@ struct svo_voxelize_state;
 struct svo_solid_state;
 struct svo_structure_state;
 struct svo_surface_state;
+struct svo_surface_merge_state;
 template <typename T>
 using svo_workspace = std::unique_ptr<T, void (*)(T *)>;
 template <typename T>
@@ -267,6 +268,7 @@ struct svo_ctx {
     svo_workspace<svo_solid_state> solid{nullptr, nullptr};  // solid voxeliser's workspace (svo_solid.hip)
     svo_workspace<svo_structure_state> structure{nullptr, nullptr};  // structure scattering's workspace (svo_structure.hip)
     svo_workspace<svo_surface_state> surface{nullptr, nullptr};  // surface extraction's workspace (svo_surface.hip)
+    svo_workspace<svo_surface_merge_state> surface_merge{nullptr, nullptr};  // the merged surface's workspace (svo_surface_merge.hip)
     std::string err;
 };
 
@@ -520,6 +522,18 @@ struct svo_list_plan {
 };
 int svo_list_plan_count(svo_ctx *ctx, svo_list_plan *plan, uint64_t n_words, uint32_t depth, bool expand, hipEvent_t discovered);
 int svo_list_plan_offsets(svo_ctx *ctx, svo_list_plan *plan, uint32_t depth, bool expand);
+// svo_surface.hip
+// The exposed faces of the tree as svo_nodes_list_surface with SVO_SURFACE_QUADS lists them, for the merge
+// (svo_surface_merge.hip): the plan, the mask and the compaction run on the ctx stream in the surface workspace `slot`, the
+// caller's own (made here when it is null), and the quads stay in it: n entries of xyz (3 u32 each), value, level and
+// face, which hold until the next call with that slot.  The caller has checked depth, the store and n_words; the
+// refusals are the surface call's, from the malformed tree on, and it blocks where that call blocks.
+struct svo_surface_quads {
+    const uint32_t *xyz, *value, *level, *face;
+    uint32_t n;
+};
+int svo_surface_list_quads(svo_ctx *ctx, svo_workspace<svo_surface_state> &slot, uint32_t closed_boundary, uint32_t depth,
+                           uint64_t n_words, svo_surface_quads *out);
 // The one writer of a generated world's directory (svo_build.hip), for svo_world_build and
 // svo_world_generate: create() makes the directory and the empty root; add_chunk() writes <id>.bin (id = SVO_CHUNK_OFFSET
 // / 2 + i) from `bytes` in the <id>.bin layout, keeps the chunk in w as a node-less CpuOctree carrying its top_mip (the

@@ -1,7 +1,7 @@
 // svo_scan.h -- the tiled count, scan and emit of the GPU passes: svo_proc.hip (a level's ranks), svo_build.hip (the
 // level passes, the sort's digit counts), svo_adapt.hip (the expand's compactions), svo_structure.hip (sites, stamp),
-// svo_voxelize.hip (a level's pairs), svo_solid.hip (a level's pairs, heads, intervals, runs) and svo_surface.hip (the
-// kept entries or faces); svo_compact.hip, svo_list.hip
+// svo_voxelize.hip (a level's pairs), svo_solid.hip (a level's pairs, heads, intervals, runs), svo_surface.hip (the
+// kept entries or faces) and svo_surface_merge.hip (the runs of rectangles); svo_compact.hip, svo_list.hip
 // (through svo_tree_discover), svo_edit.hip and svo_adapt.hip scan an array in place with svo_scan_u32.  No atomics: an
 // output's place depends on the inputs alone.
 // A tile is kTile items, kPer consecutive ones per thread, so ranks follow the items' order.  A pass is three launches:
@@ -142,7 +142,8 @@ __global__ __launch_bounds__(kThreads) void tile_scatter_kernel(Items items, Emi
     }
 }
 
-// ---- the scatter's items whose flags are a byte array (the child masks of a level's pairs: svo_voxelize.hip, svo_solid.hip) ----
+// ---- the scatter's items whose flags are a byte array (the child masks of a level's pairs: svo_voxelize.hip, svo_solid.hip;
+// the head bytes of svo_surface_merge.hip's runs, in a count and an emit) ----
 // The state is the bytes of a thread's kPer consecutive items as one uint4; the array is padded to whole tiles, and what
 // lies behind m is not counted.
 struct FlagBytes {

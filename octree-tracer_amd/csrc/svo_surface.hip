@@ -23,6 +23,8 @@
 // No pointer is checked here: the walks start at groups on the path of a discovered group and follow only words of groups
 // they reached that way, and the discovery has checked every pointer in every reachable group before the mask pass runs.
 // Every error is decided before the emit, so it leaves the outputs as they were.  The node buffer is only read.
+// svo_surface_list_quads (svo_ctx.h) runs the same pass for the merge (svo_surface_merge.hip), in a workspace of the merge's
+// own, and leaves the quads there.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -213,13 +215,14 @@ enum Ev { kEvStart, kEvDiscover, kEvCount, kEvOffsets, kEvMask, kEvScan, kEvEmit
 }  // namespace
 
 // Per-context workspace of the surface pass (svo_ctx::surface): a listing plan of its own, 13 bytes per list entry, the
-// tile sums.
+// tile sums; in the merge's instance (svo_surface_list_quads) the quads too, 24 bytes each.
 struct svo_surface_state {
     svo_list_plan plan;
     svo_dev<uint64_t> ent_key;
     svo_dev<uint32_t> ent_value;
     svo_dev<uint8_t> ent_mask;
     svo_dev<uint32_t> tile_sum;
+    svo_dev<uint32_t> quad_xyz, quad_value, quad_level, quad_face;
     svo_mirrored<> status;  // kStWords words
     svo_pass_timer<kEvs, SVO_SURFACE_TIMES> timer;
 
@@ -230,27 +233,19 @@ struct svo_surface_state {
     }
 };
 
-extern "C" {
+namespace {
 
-int svo_nodes_list_surface(svo_ctx *ctx, const svo_surface_params *p, uint32_t *xyz_out_dev, uint32_t *value_out_dev,
-                           uint32_t *level_out_dev, uint32_t *face_out_dev, uint64_t *n_out) {
-    if (!ctx) return SVO_ERR_ARG;
-    if (!p) return svo_fail(ctx, SVO_ERR_ARG, "null params");
-    if (!n_out) return svo_fail(ctx, SVO_ERR_ARG, "null n_out");
-    const uint32_t known = SVO_SURFACE_CLOSED_BOUNDARY | SVO_SURFACE_KEEP_HIDDEN | SVO_SURFACE_QUADS;
-    if ((p->flags & ~known) || ((p->flags & SVO_SURFACE_QUADS) && (p->flags & SVO_SURFACE_KEEP_HIDDEN)))
-        return svo_fail(ctx, SVO_ERR_ARG, "unknown or incompatible flag bits " + std::to_string(p->flags));
-    int rc = svo_check_depth(ctx, p->depth, 21);
-    if (rc) return rc;
-    if (xyz_out_dev && (!value_out_dev || !face_out_dev))
-        return svo_fail(ctx, SVO_ERR_ARG, "null face_out_dev or value_out_dev with xyz_out_dev given");
-    if ((rc = svo_check_store(ctx)) || (rc = svo_check_n_words(ctx, p->n_words))) return rc;
+// The pass behind its argument checks, in the workspace `slot`: into the caller's outputs, or, with `own`, the quads into
+// the workspace's own arrays, whatever their number.
+int list_surface(svo_ctx *ctx, svo_workspace<svo_surface_state> &slot, const svo_surface_params *p, uint32_t *xyz_out_dev,
+                 uint32_t *value_out_dev, uint32_t *level_out_dev, uint32_t *face_out_dev, uint64_t *n_out, svo_surface_quads *own) {
+    int rc;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const double t0 = svo_now_ms();
     const uint32_t n_words = (uint32_t)std::min<uint64_t>(p->n_words, kMaxWords), depth = p->depth;
     const uint32_t mode = p->flags & SVO_SURFACE_QUADS ? kModeQuads : p->flags & SVO_SURFACE_KEEP_HIDDEN ? kModeAll : kModeSurface;
-    if ((rc = svo_workspace_ensure(ctx, ctx->surface))) return rc;
-    svo_surface_state *s = ctx->surface.get();
+    if ((rc = svo_workspace_ensure(ctx, slot))) return rc;
+    svo_surface_state *s = slot.get();
     if ((rc = s->plan.grow(ctx, n_words / 8)) || (rc = s->timer.begin(ctx))) return rc;
 
     // the passes read the words: behind every earlier write to the store, whichever context issued it
@@ -284,11 +279,17 @@ int svo_nodes_list_surface(svo_ctx *ctx, const svo_surface_params *p, uint32_t *
         HIP_TRY(ctx, s->timer.mark(ctx, kEvMask));
     }
     if (total >= kMaxEntries) return svo_fail(ctx, SVO_ERR_CAP, "the list has " + std::to_string(total) + " entries, 2^31 or more");
-    if (xyz_out_dev && total > p->max_entries)
+    if (xyz_out_dev && !own && total > p->max_entries)
         return svo_fail(ctx, SVO_ERR_CAP, "the list has " + std::to_string(total) + " entries, more than max_entries = " +
                                               std::to_string(p->max_entries));
     HIP_TRY(ctx, s->timer.mark(ctx, kEvScan));
 
+    if (own) {
+        if ((rc = svo_grow(ctx, 3 * (size_t)total, &s->quad_xyz)) || (rc = svo_grow(ctx, (size_t)total, &s->quad_value, &s->quad_level, &s->quad_face)))
+            return rc;
+        xyz_out_dev = s->quad_xyz, value_out_dev = s->quad_value, level_out_dev = s->quad_level, face_out_dev = s->quad_face;
+        *own = svo_surface_quads{xyz_out_dev, value_out_dev, level_out_dev, face_out_dev, (uint32_t)total};
+    }
     if (xyz_out_dev && total) {
         const Faces live{s->ent_mask, mode};
         const FacesOut out{s->ent_key, s->ent_value, depth, (uint32_t)total, xyz_out_dev, value_out_dev, level_out_dev, face_out_dev};
@@ -296,9 +297,36 @@ int svo_nodes_list_surface(svo_ctx *ctx, const svo_surface_params *p, uint32_t *
         HIP_TRY(ctx, hipGetLastError());
     }
     HIP_TRY(ctx, s->timer.mark(ctx, kEvEmit));
-    *n_out = total;
+    if (n_out) *n_out = total;
     s->timer.finish(t0);
     return SVO_OK;
+}
+
+}  // namespace
+
+// The exposed faces as SVO_SURFACE_QUADS lists them, for the merge (svo_surface_merge.hip), which has checked the arguments.
+int svo_surface_list_quads(svo_ctx *ctx, svo_workspace<svo_surface_state> &slot, uint32_t closed_boundary, uint32_t depth,
+                           uint64_t n_words, svo_surface_quads *out) {
+    const svo_surface_params p{SVO_SURFACE_QUADS | (closed_boundary ? SVO_SURFACE_CLOSED_BOUNDARY : 0u), depth, n_words, 0};
+    return list_surface(ctx, slot, &p, nullptr, nullptr, nullptr, nullptr, nullptr, out);
+}
+
+extern "C" {
+
+int svo_nodes_list_surface(svo_ctx *ctx, const svo_surface_params *p, uint32_t *xyz_out_dev, uint32_t *value_out_dev,
+                           uint32_t *level_out_dev, uint32_t *face_out_dev, uint64_t *n_out) {
+    if (!ctx) return SVO_ERR_ARG;
+    if (!p) return svo_fail(ctx, SVO_ERR_ARG, "null params");
+    if (!n_out) return svo_fail(ctx, SVO_ERR_ARG, "null n_out");
+    const uint32_t known = SVO_SURFACE_CLOSED_BOUNDARY | SVO_SURFACE_KEEP_HIDDEN | SVO_SURFACE_QUADS;
+    if ((p->flags & ~known) || ((p->flags & SVO_SURFACE_QUADS) && (p->flags & SVO_SURFACE_KEEP_HIDDEN)))
+        return svo_fail(ctx, SVO_ERR_ARG, "unknown or incompatible flag bits " + std::to_string(p->flags));
+    int rc = svo_check_depth(ctx, p->depth, 21);
+    if (rc) return rc;
+    if (xyz_out_dev && (!value_out_dev || !face_out_dev))
+        return svo_fail(ctx, SVO_ERR_ARG, "null face_out_dev or value_out_dev with xyz_out_dev given");
+    if ((rc = svo_check_store(ctx)) || (rc = svo_check_n_words(ctx, p->n_words))) return rc;
+    return list_surface(ctx, ctx->surface, p, xyz_out_dev, value_out_dev, level_out_dev, face_out_dev, n_out, nullptr);
 }
 
 int svo_surface_timing(svo_ctx *ctx, float ms_out[SVO_SURFACE_TIMES]) {

@@ -110,6 +110,13 @@ class Gpu:
         wall time of the call (svo_surface_timing)"""
         return self._timing(lib().svo_surface_timing, 7)
 
+    def surface_merge_timing(self):
+        """ms of the last Render.surface_rects call into the library (its fill, or its count query when there was nothing
+        to fill or the call was refused): the quads, then keys, sort, flags and scan, emit for each of the 8 phases a
+        call can have (U and V of round 1 first; 0 for a phase that did not run), the output's fill (device events),
+        host wall time of the call (svo_surface_merge_timing)"""
+        return self._timing(lib().svo_surface_merge_timing, 35)
+
     def sample_timing(self):
         """ms of the last Render.sample_voxels / sample_dense call that ran: the kernel (device events), host wall time of
         the call (svo_sample_timing)"""

@@ -8,7 +8,8 @@ svo_mesh_voxelize, the quantisation it works on, a minimal Wavefront reader and 
     voxelize_solid     closed mesh -> the device list of the cells inside it, or their y-spans: with
                        voxelize's list behind it, a solid model with its surface's colours (Render.from_mesh(solid=True))
     quads_to_mesh      the exposed faces of a tree (Render.surface_quads) -> an indexed triangle mesh
-    extract_surface    the two in one call: the inverse of voxelize
+    rects_to_mesh      the same faces merged into rectangles (Render.surface_rects) -> an indexed triangle mesh
+    extract_surface    quads or rectangles and their mesh in one call: the inverse of voxelize
     load_obj, save_obj v / f lines of a Wavefront file, read and written
     fit_to_cube        uniform scale and centring into the cube
     icosphere, torus   generators for tests and tools/voxelize_probe.py
@@ -192,7 +193,12 @@ def quads_to_mesh(coords, faces, levels, depth, colours=None, weld=True, integer
     if len(f) and not bool(((f >= 0) & (f < 6)).all()):
         raise ValueError("a face number outside 0..5")
     step = torch.from_numpy(_face_corners()).to(c.device)[f]  # (Q, 4, 3)
-    cells = (c[:, None, :] + step * side[:, None, None]).reshape(-1, 3)  # (4 Q, 3) grid coordinates in [0, 2^depth]
+    return _mesh(c, step * side[:, None, None], depth, colours, weld, integer)
+
+
+def _mesh(c, step, depth, colours, weld, integer):
+    """the mesh of the faces at the corners c whose corner k is step[:, k] away: what quads_to_mesh documents"""
+    cells = (c[:, None, :] + step).reshape(-1, 3)  # (4 Q, 3) grid coordinates in [0, 2^depth]
     index = torch.arange(4 * len(c), device=c.device)
     if weld:
         cells, index = torch.unique(cells, dim=0, sorted=True, return_inverse=True)
@@ -206,10 +212,43 @@ def quads_to_mesh(coords, faces, levels, depth, colours=None, weld=True, integer
     return vertices, triangles, tri_colours
 
 
-def extract_surface(render, depth=None, closed_boundary=False, weld=True):
+def rects_to_mesh(rects, values, depth, colours=None, weld=True, integer=False):
+    """The rectangles of Render.surface_rects as an indexed triangle mesh, in plain torch on the tensors' device.  rects
+    (R, 6): face, plane, u0, v0, w, h; values (R): the triangles' colours unless `colours` (R) is given (both None: no
+    colours).  With a = face >> 1, u = (a + 1) % 3, v = (a + 2) % 3 a rectangle lies in the plane `plane` of axis a, and its
+    corners are (0, 0), (w, 0), (w, h), (0, h) from (u0, v0) in (u, v) for an odd face and in the reverse order for an
+    even one, so its normal points out of the leaves behind it.  Triangles, vertices, weld and integer are quads_to_mesh's,
+    and for rectangles with w = h = s the result is what quads_to_mesh returns for the same quads.  The rectangles of a
+    merged surface meet in T-junctions: the mesh covers the surface exactly but is no longer edge to edge."""
+    depth = int(depth)
+    if not 1 <= depth <= 21:
+        raise ValueError(f"depth must be 1..21 (got {depth})")
+    r = torch.as_tensor(rects).to(torch.int64).reshape(-1, 6)
+    if colours is None:
+        colours = values
+    if colours is not None and len(torch.as_tensor(colours).reshape(-1)) != len(r):
+        raise ValueError(f"rects and values must have one row per rectangle (got {len(r)}, {len(torch.as_tensor(colours).reshape(-1))})")
+    f = r[:, 0]
+    if len(f) and not bool(((f >= 0) & (f < 6)).all()):
+        raise ValueError("a face number outside 0..5")
+    a = f >> 1
+    rows = torch.arange(len(r), device=r.device)
+    c = torch.zeros((len(r), 3), dtype=torch.int64, device=r.device)
+    c[rows, a], c[rows, (a + 1) % 3], c[rows, (a + 2) % 3] = r[:, 1], r[:, 2], r[:, 3]
+    unit = torch.from_numpy(_face_corners()).to(r.device)[f]  # (R, 4, 3): 0 or 1 along each axis; along a it is the face's parity
+    extent = torch.zeros((len(r), 3), dtype=torch.int64, device=r.device)
+    extent[rows, (a + 1) % 3], extent[rows, (a + 2) % 3] = r[:, 4], r[:, 5]
+    return _mesh(c, unit * extent[:, None, :], depth, colours, weld, integer)
+
+
+def extract_surface(render, depth=None, closed_boundary=False, weld=True, merge=False, rounds=1):
     """The visible surface of the tree in render's node buffer as a triangle mesh: Render.surface_quads, then
-    quads_to_mesh, both on the GPU.  Returns (vertices float32, triangles int32, triangle_colours int32)."""
+    quads_to_mesh, both on the GPU; with merge=True Render.surface_rects (with `rounds`) and rects_to_mesh: the same
+    surface in fewer triangles.  Returns (vertices float32, triangles int32, triangle_colours int32)."""
     d = int(render.gpu.tree_depth if depth is None else depth)
+    if merge:
+        rects, values = render.surface_rects(d, closed_boundary, rounds)
+        return rects_to_mesh(rects, values, d, weld=weld)
     coords, colours, faces, levels = render.surface_quads(d, closed_boundary)
     return quads_to_mesh(coords, faces, levels, d, colours, weld=weld)
 

@@ -6,7 +6,7 @@ import torch
 
 from . import sharding
 from ._device import device_u32, voxel_list, wait_for_torch
-from ._lib import BuildParams, CombineParams, CompactParams, EditParams, ListParams, RegionParams, SampleParams, SimplifyParams, SitesParams, StampParams, SurfaceParams, TopsParams, Uniforms, lib
+from ._lib import BuildParams, CombineParams, CompactParams, EditParams, ListParams, RegionParams, SampleParams, SimplifyParams, SitesParams, StampParams, SurfaceMergeParams, SurfaceParams, TopsParams, Uniforms, lib
 from .camera import camera_matrices
 
 F_PAUSE_ADAPTIVE, F_SHOW_STEPS, F_SHOW_HITS, F_SHADOWS, F_MISC_BOOL = 1, 2, 4, 8, 16
@@ -357,6 +357,33 @@ class Render:
         `depth` grid, its colour, the face's number 0..5 (-x, +x, -y, +y, -z, +z) and the leaf's level, the leaves in
         list_voxels' order and a leaf's faces in ascending number: what mesh.quads_to_mesh takes."""
         return self._surface(4 | (1 if closed_boundary else 0), depth, True)
+
+    def surface_rects(self, depth=None, closed_boundary=False, rounds=1, any_value=False):
+        """The exposed faces of the tree merged into rectangles on the GPU (svo_nodes_merge_surface).  Returns
+        device int32 tensors (rects (N, 6), values (N)): per rectangle face (0..5, as in surface_quads), plane (its
+        coordinate along the face's axis a = face >> 1), u0 and v0 (its minimum corner along the axes (a + 1) % 3 and
+        (a + 2) % 3), w and h (its extents along them), all on the `depth` grid, and the value its faces share; ascending
+        in (face, plane, u0, w, v0): what mesh.rects_to_mesh takes.  A round joins surface_quads' faces of one plane and
+        one value along u, then along v; rounds (1..4) beyond the first matter only in a tree of mixed levels.
+        any_value: faces join whatever their values, and every value comes back 0.  depth=None: the depth declared for
+        this tree, as in list_voxels.  Raises SvoError as surface_quads does.  The node buffer is only read."""
+        dev = self.gpu.torch_device
+        p = SurfaceMergeParams()
+        p.flags = (1 if closed_boundary else 0) | (8 if any_value else 0)
+        p.depth = max(0, int(self.gpu.tree_depth if depth is None else depth))
+        p.rounds = max(0, int(rounds))
+        p.n_words = int(self.node_length)
+        n = C.c_uint64()
+        self.gpu.check(lib().svo_nodes_merge_surface(self.gpu._h, C.byref(p), None, None, C.byref(n)))  # the count
+        count = n.value
+        rects = torch.empty((count, 6), dtype=torch.int32, device=dev)
+        values = torch.empty(count, dtype=torch.int32, device=dev)
+        if count:
+            p.max_entries = count
+            wait_for_torch(self.gpu)
+            self.gpu.check(lib().svo_nodes_merge_surface(self.gpu._h, C.byref(p), rects.data_ptr(), values.data_ptr(), C.byref(n)))
+            self.gpu.sync()
+        return rects, values
 
     def _sample_params(self, depth):
         p = SampleParams()
