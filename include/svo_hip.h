@@ -801,6 +801,68 @@ int svo_nodes_merge_surface(svo_ctx *ctx, const svo_surface_merge_params *p, uin
 #define SVO_SURFACE_MERGE_TIMES 35
 int svo_surface_merge_timing(svo_ctx *ctx, float ms_out[SVO_SURFACE_MERGE_TIMES]);
 
+/* ---- the connected components of the tree in the node buffer, labelled on the device ----
+ * Which voxels of the tree hang together.  The entries are exactly those of svo_nodes_list_voxels with flags 0: the word
+ * test, the levels, the child index x * 4 + y * 2 + z, the `depth` grid, the Morton order and the disregard for the low 4
+ * bits of a word are the listing's.  Entry i is a voxel word at level l with cell c on the level-l grid.
+ * Links: for each face f = 0 .. 5 of entry i (-x, +x, -y, +y, -z, +z) let n be the cell behind it, as svo_nodes_list_surface
+ * defines it: c - 1 (even f) or c + 1 (odd f) on axis f >> 1.
+ *     n leaves [0, 2^l) on that axis:   no link (the grid's boundary links nothing)
+ *     otherwise walk from group 0 towards n for at most l levels, by the sampler's rule (svo_nodes_sample):
+ *         the walk stops on a voxel word (value > 0) at a level <= l:   that word is entry j of the listing; i and j are linked
+ *         it stops on the empty word:                                   no link
+ *         the word at level l is interior (the neighbour is finer):     no link from this side; the finer voxels link from theirs
+ * With SVO_COMPONENTS_SAME_VALUE a link also needs equal values ((word >> 4) of both).  The cubes of a tree are disjoint, so
+ * two entries are linked exactly when their cubes share a piece of a face: the components are those of 6-connectivity of
+ * the cubes (per value, with the flag).  Cubes that touch along an edge or at a corner only are not linked.
+ * Outputs, all DEVICE pointers of max_entries u32 each, of which only the entries [0, *n_out) are written:
+ *     label_out_dev[i]   the rank of the first entry (smallest rank) of i's component: label[i] <= i, label[label[i]] == label[i]
+ *     id_out_dev[i]      (may be NULL) the component's number 0 .. C - 1; the components are numbered by ascending first entry
+ *     index_out_dev[i]   (may be NULL) the index of the entry's word in the node buffer, as svo_nodes_sample reports it: the
+ *                        address svo_nodes_scatter_device takes.  It is the one output that names a place
+ *     *n_out the number of entries, *n_components_out the number of components C
+ * label_out_dev == NULL is a count query for both numbers: nothing else is written and max_entries is ignored.
+ * The result is the same bytes on every run and for every layout of the same tree (put order, compacted, canonical
+ * rebuild), index excepted.  The union uses atomicMin on the pass's own workspace; its fixed point, the smallest rank of
+ * each component, does not depend on the order they land in.
+ * Errors are decided before any write to the outputs and leave them, *n_out and *n_components_out as they were; they are
+ * the listing's, in its order and with its wording: SVO_ERR_ARG: NULL p; NULL n_out or n_components_out; unknown flag bits;
+ * depth outside 1..21; SVO_ERR_STATE: no node buffer; SVO_ERR_ARG: n_words; SVO_ERR_STATE: the "malformed tree: ..." causes;
+ * SVO_ERR_ARG: a voxel or an interior word at a level deeper than `depth`; SVO_ERR_CAP, with the exact count in
+ * svo_last_error: 2^31 entries or more, then more entries than max_entries (not for a count query).  A device adaptive
+ * state attached to the context is no obstacle.  The node buffer is never written.
+ * Runs on the ctx stream behind the store's last write, whichever context issued it, and records no write of its own.
+ * Blocks where the listing blocks, once per round of the union (a round that needs a second compress pass, once more per
+ * pass) and once for the number of components; the fill is enqueued (svo_sync before the outputs are read on another stream). */
+#define SVO_COMPONENTS_SAME_VALUE 1u  /* a link needs equal values: components of one colour */
+typedef struct svo_components_params {
+    uint32_t flags;        /* 0 or SVO_COMPONENTS_SAME_VALUE */
+    uint32_t depth;        /* 1..21: the grid of the listing */
+    uint64_t n_words;      /* the tree: words [0, n_words) of the node buffer, rooted at group 0 */
+    uint64_t max_entries;  /* room in the output arrays, in entries */
+} svo_components_params;
+int svo_nodes_label_components(svo_ctx *ctx, const svo_components_params *p, uint32_t *label_out_dev,
+                               uint32_t *id_out_dev /* may be null */, uint32_t *index_out_dev /* may be null */, uint64_t *n_out,
+                               uint64_t *n_components_out);
+/* Times (ms) of the last labelling: [0] plan (discover, count and offsets, with their read-backs), [1] link, [2] union
+ * (with a read-back per round), [3] ids (the count of the roots, with its read-back), [4] the fill (device events; waits
+ * for it; next to 0 for a count query), [5] host wall time of the call; *rounds_out (may be NULL) the rounds of the
+ * union, the last one, which hooks nothing, included (0 for a tree without a voxel).  A refused call leaves the times of
+ * the last call that ran. */
+#define SVO_COMPONENTS_TIMES 6
+int svo_components_timing(svo_ctx *ctx, float ms_out[SVO_COMPONENTS_TIMES], uint32_t *rounds_out /* may be null */);
+
+/* The device twin of svo_nodes_scatter: words_dev[i], or the one word `fill` when words_dev is NULL, goes to word
+ * index_dev[i] of the node buffer, for n entries (DEVICE pointers).  An index >= n_words (the sampler's 0xFFFFFFFF
+ * included) is skipped.  Of duplicate indices with different words, which one lands is unspecified.  Nothing is read
+ * back and the call does not block: both arrays must stay valid until svo_sync.  It does to the store what
+ * svo_nodes_scatter does: the write is ordered behind the store's last write and recorded, so a later frame, and other
+ * contexts sharing the store, wait for it and rebuild what they derived, and a resting view's replay is not reused.
+ * Errors are decided on the host, the first in this order: SVO_ERR_ARG: NULL index_dev with n > 0; n >= 2^31.
+ * SVO_ERR_STATE: no node buffer.  SVO_ERR_ARG: n_words not a positive multiple of 8 or above the capacity. */
+int svo_nodes_scatter_device(svo_ctx *ctx, const uint32_t *index_dev, const uint32_t *words_dev /* may be null */, uint32_t fill,
+                             size_t n, uint64_t n_words);
+
 /* ---- the tree in the node buffer sampled on the device ----
  * What is at a cell of the `depth` grid, read from the first n_words words of the node buffer as a tree rooted at group 0;
  * coordinates, child index and levels are those of svo_nodes_build, svo_nodes_edit and svo_nodes_list_voxels.  For the

@@ -393,6 +393,70 @@ class Render {  // render.rs:3-285
         gpu_.poll_wait();
         return n;
     }
+    // the connected components of that tree's voxels, labelled on the GPU (svo_nodes_label_components):
+    // list_voxels' entries (without expand), in its order; two leaves are linked when their cubes share a piece of a face,
+    // with same_value only when their values are equal.  labels_dev (max_entries u32: the rank of the first entry of the
+    // entry's component), ids_dev (the component's number, by ascending first entry; or null) and indices_dev (the index
+    // of the entry's word in the node buffer, what scatter_nodes_device takes; or null) are DEVICE pointers.  Returns the
+    // entry count, *n_components (when given) the number of components; labels_dev null: the counts alone.  Throws, with
+    // nothing written, for what list_voxels throws and for more entries than max_entries.
+    uint64_t label_components(uint64_t n_words, uint32_t depth, uint32_t *labels_dev, uint32_t *ids_dev, uint32_t *indices_dev,
+                              uint64_t max_entries, bool same_value = false, uint64_t *n_components = nullptr) {
+        const svo_components_params p{same_value ? SVO_COMPONENTS_SAME_VALUE : 0u, depth, n_words, max_entries};
+        uint64_t n = 0, c = 0;
+        gpu_.check(svo_nodes_label_components(gpu_.ctx(), &p, labels_dev, ids_dev, indices_dev, &n, &c));
+        gpu_.poll_wait();
+        if (n_components) *n_components = c;
+        return n;
+    }
+    // words_dev[i], or the one word `fill` when words_dev is null, to the node buffer at indices_dev[i], n DEVICE entries
+    // (svo_nodes_scatter_device); an index >= n_words is skipped.  Does not block: the arrays stay valid until gpu.poll_wait().
+    void scatter_nodes_device(const uint32_t *indices_dev, const uint32_t *words_dev, uint32_t fill, size_t n, uint64_t n_words) {
+        gpu_.check(svo_nodes_scatter_device(gpu_.ctx(), indices_dev, words_dev, fill, n, n_words));
+    }
+    // What a drop_floating call did.
+    struct Dropped {
+        uint64_t components, dropped_components, dropped_leaves;
+    };
+    // the leaves of every component that does not meet the anchor box [lo, hi) of the `depth` grid get the empty word
+    // (label_components, then scatter_nodes_device); lo and hi null: the floor layer y == 0, y being up.  The labels and the
+    // listing stay on the device but for the ids, corners and levels, which the host reads to decide which components
+    // hold.  The groups this leaves empty are compact_nodes' (prune) to drop.
+    Dropped drop_floating(uint64_t n_words, uint32_t depth, const uint32_t *lo = nullptr, const uint32_t *hi = nullptr,
+                          bool same_value = false) {
+        uint64_t c = 0;
+        const uint64_t n = label_components(n_words, depth, nullptr, nullptr, nullptr, 0, same_value, &c);
+        if (!n) return {0, 0, 0};
+        const uint64_t side = 1ull << depth;
+        const uint64_t box_lo[3] = {lo ? lo[0] : 0, lo ? lo[1] : 0, lo ? lo[2] : 0};
+        const uint64_t box_hi[3] = {hi ? hi[0] : side, hi ? hi[1] : 1, hi ? hi[2] : side};
+        Scratch labels(gpu_, n), ids(gpu_, n), indices(gpu_, n), xyz(gpu_, 3 * n), values(gpu_, n), levels(gpu_, n);
+        label_components(n_words, depth, labels.u32(), ids.u32(), indices.u32(), n, same_value);
+        list_voxels(n_words, depth, xyz.u32(), values.u32(), n, false, levels.u32());
+        std::vector<uint32_t> id(n), at(n), corner(3 * n), level(n);
+        gpu_.check(svo_buffer_read(gpu_.ctx(), ids.u32(), id.data(), n * 4));
+        gpu_.check(svo_buffer_read(gpu_.ctx(), indices.u32(), at.data(), n * 4));
+        gpu_.check(svo_buffer_read(gpu_.ctx(), xyz.u32(), corner.data(), 3 * n * 4));
+        gpu_.check(svo_buffer_read(gpu_.ctx(), levels.u32(), level.data(), n * 4));
+        std::vector<char> held(c, 0);
+        for (uint64_t i = 0; i < n; i++) {
+            const uint64_t size = 1ull << (depth - level[i]);
+            bool meets = true;
+            for (int a = 0; a < 3; a++) meets = meets && corner[3 * i + a] < box_hi[a] && corner[3 * i + a] + size > box_lo[a];
+            if (meets) held[id[i]] = 1;
+        }
+        std::vector<uint32_t> gone;
+        for (uint64_t i = 0; i < n; i++)
+            if (!held[id[i]]) gone.push_back(at[i]);
+        Dropped d{c, 0, gone.size()};
+        for (char h : held) d.dropped_components += !h;
+        if (!gone.empty()) {
+            gpu_.check(svo_buffer_write(gpu_.ctx(), indices.u32(), gone.data(), gone.size() * 4));
+            scatter_nodes_device(indices.u32(), nullptr, SVO_VOXEL_OFFSET << 4, gone.size(), n_words);
+            gpu_.poll_wait();  // (the indices go with this call)
+        }
+        return d;
+    }
     // a triangle mesh voxelised on the GPU, conservatively and exactly (svo_mesh_voxelize): vq_dev
     // (3 * n_vertices quantised coordinates, 64 per cell of the 2^depth grid), tri_dev (3 * n_tris vertex indices),
     // tri_colours_dev (n_tris x 0x00RRGGBB, or null: `colour`) and the outputs xyz_dev (3 * max_voxels u32), colours_dev

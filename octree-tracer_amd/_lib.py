@@ -153,6 +153,16 @@ class SurfaceMergeParams(C.Structure):
     ]
 
 
+class ComponentsParams(C.Structure):
+    """svo_components_params: the connected components of the tree in the node buffer (include/svo_hip.h)."""
+    _fields_ = [
+        ("flags", C.c_uint32),
+        ("depth", C.c_uint32),
+        ("n_words", C.c_uint64),
+        ("max_entries", C.c_uint64),
+    ]
+
+
 class SampleParams(C.Structure):
     """svo_sample_params: the tree in the node buffer sampled on the device (include/svo_hip.h)."""
     _fields_ = [
@@ -318,6 +328,9 @@ DEVICE_SIGNATURES = {
     "svo_surface_timing": (C.c_int, (vp, fp)),
     "svo_nodes_merge_surface": (C.c_int, (vp, C.POINTER(SurfaceMergeParams), vp, vp, C.POINTER(u64))),
     "svo_surface_merge_timing": (C.c_int, (vp, fp)),
+    "svo_nodes_label_components": (C.c_int, (vp, C.POINTER(ComponentsParams), vp, vp, vp, C.POINTER(u64), C.POINTER(u64))),
+    "svo_components_timing": (C.c_int, (vp, fp, C.POINTER(u32))),
+    "svo_nodes_scatter_device": (C.c_int, (vp, vp, vp, u32, sz, u64)),
     "svo_nodes_sample": (C.c_int, (vp, C.POINTER(SampleParams), vp, sz, vp, vp, vp)),
     "svo_nodes_sample_dense": (C.c_int, (vp, C.POINTER(SampleParams), C.POINTER(u32), C.POINTER(u32), vp)),
     "svo_sample_timing": (C.c_int, (vp, fp)),

@@ -1,7 +1,7 @@
 // svo_ctx.h -- the device context behind the opaque `svo_ctx` of include/svo_hip.h, and the host helpers of the files that
 // use it: svo_abi.cpp (trace / scan dispatch), svo_comm.cpp (RCCL frame gather) and the GPU tree passes (svo_proc.hip,
 // svo_build.hip, svo_edit.hip, svo_region.hip, svo_combine.hip, svo_compact.hip, svo_simplify.hip, svo_list.hip, svo_sample.hip, svo_voxelize.hip, svo_solid.hip,
-// svo_structure.hip, svo_surface.hip, svo_surface_merge.hip, svo_adapt.hip).  One rule of ownership for the context, the node store and every
+// svo_structure.hip, svo_surface.hip, svo_surface_merge.hip, svo_components.hip, svo_adapt.hip).  One rule of ownership for the context, the node store and every
 // pass's state: a member owns what it holds, as svo_dev / svo_pinned (an allocation and its size), svo_events (events) or
 // svo_stream (a stream).  The passes
 // share the rest as their host frame: svo_grow / svo_grow_pinned / svo_grow_keep (workspaces, by the buffers' own
@@ -154,6 +154,7 @@ struct svo_solid_state;
 struct svo_structure_state;
 struct svo_surface_state;
 struct svo_surface_merge_state;
+struct svo_components_state;
 template <typename T>
 using svo_workspace = std::unique_ptr<T, void (*)(T *)>;
 template <typename T>
@@ -269,6 +270,7 @@ struct svo_ctx {
     svo_workspace<svo_structure_state> structure{nullptr, nullptr};  // structure scattering's workspace (svo_structure.hip)
     svo_workspace<svo_surface_state> surface{nullptr, nullptr};  // surface extraction's workspace (svo_surface.hip)
     svo_workspace<svo_surface_merge_state> surface_merge{nullptr, nullptr};  // the merged surface's workspace (svo_surface_merge.hip)
+    svo_workspace<svo_components_state> components{nullptr, nullptr};  // the component labelling's workspace (svo_components.hip)
     std::string err;
 };
 
@@ -502,8 +504,8 @@ struct svo_tree_rewrite {
 };
 static_assert(SVO_SIMPLIFY_TIMES == SVO_COMPACT_TIMES, "the two rewrites share their timer");
 // svo_list.hip
-// The plan of a listing, for svo_nodes_list_voxels and the surface pass (svo_surface.hip), each with a plan
-// of its own: the discovery's workspace (walk), then per group k of order its entry and record counts (cnt, rcnt), the
+// The plan of a listing, for svo_nodes_list_voxels, the surface pass (svo_surface.hip) and the component
+// labelling (svo_components.hip), each with a plan of its own: the discovery's workspace (walk), then per group k of order its entry and record counts (cnt, rcnt), the
 // place of its first entry and record in the list (start, rstart) and its Morton prefix (key: a leading 1, then 3 bits
 // per level above the group's words).  create() makes the status words, grow() room for `groups` groups.  svo_list_plan_count, on
 // the ctx stream: the discovery (`discovered`, or null, is recorded behind it), the counts bottom-up and their read-back;

@@ -1,7 +1,7 @@
 // svo_scan.h -- the tiled count, scan and emit of the GPU passes: svo_proc.hip (a level's ranks), svo_build.hip (the
 // level passes, the sort's digit counts), svo_adapt.hip (the expand's compactions), svo_structure.hip (sites, stamp),
 // svo_voxelize.hip (a level's pairs), svo_solid.hip (a level's pairs, heads, intervals, runs), svo_surface.hip (the
-// kept entries or faces) and svo_surface_merge.hip (the runs of rectangles); svo_compact.hip, svo_list.hip
+// kept entries or faces), svo_surface_merge.hip (the runs of rectangles) and svo_components.hip (the roots); svo_compact.hip, svo_list.hip
 // (through svo_tree_discover), svo_edit.hip and svo_adapt.hip scan an array in place with svo_scan_u32.  No atomics: an
 // output's place depends on the inputs alone.
 // A tile is kTile items, kPer consecutive ones per thread, so ranks follow the items' order.  A pass is three launches:

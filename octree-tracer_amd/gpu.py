@@ -117,6 +117,14 @@ class Gpu:
         host wall time of the call (svo_surface_merge_timing)"""
         return self._timing(lib().svo_surface_merge_timing, 35)
 
+    def components_timing(self):
+        """(ms, rounds) of the last Render.label_components call into the library (its fill, or its count query when there
+        was nothing to fill or the call was refused): ms = plan, link, union, ids, the fill (device events), host wall time
+        of the call; rounds = the rounds of the union, the last, which hooks nothing, included (svo_components_timing)"""
+        ms, rounds = (C.c_float * 6)(), C.c_uint32()
+        self.check(lib().svo_components_timing(self._h, ms, C.byref(rounds)))
+        return list(ms), rounds.value
+
     def sample_timing(self):
         """ms of the last Render.sample_voxels / sample_dense call that ran: the kernel (device events), host wall time of
         the call (svo_sample_timing)"""

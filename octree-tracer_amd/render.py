@@ -6,7 +6,7 @@ import torch
 
 from . import sharding
 from ._device import device_u32, voxel_list, wait_for_torch
-from ._lib import BuildParams, CombineParams, CompactParams, EditParams, ListParams, RegionParams, SampleParams, SimplifyParams, SitesParams, StampParams, SurfaceMergeParams, SurfaceParams, TopsParams, Uniforms, lib
+from ._lib import BuildParams, CombineParams, CompactParams, ComponentsParams, EditParams, ListParams, RegionParams, SampleParams, SimplifyParams, SitesParams, StampParams, SurfaceMergeParams, SurfaceParams, TopsParams, Uniforms, lib
 from .camera import camera_matrices
 
 F_PAUSE_ADAPTIVE, F_SHOW_STEPS, F_SHOW_HITS, F_SHADOWS, F_MISC_BOOL = 1, 2, 4, 8, 16
@@ -384,6 +384,93 @@ class Render:
             self.gpu.check(lib().svo_nodes_merge_surface(self.gpu._h, C.byref(p), rects.data_ptr(), values.data_ptr(), C.byref(n)))
             self.gpu.sync()
         return rects, values
+
+    def label_components(self, depth=None, same_value=False, with_ids=True, with_indices=False, with_sizes=False):
+        """The connected components of the tree's voxels, labelled on the GPU (svo_nodes_label_components).
+        The entries are list_voxels' (without expand), in its order; two leaves are linked when their cubes share a piece
+        of a face (6-connectivity; a coarse leaf is linked to every finer leaf on its faces), with same_value only when
+        their colours are equal.  Returns device tensors (labels, ids, n_components[, indices][, sizes]): labels (N)
+        int32, the rank of the first entry of the entry's component (labels[i] <= i); ids (N) int32, the component's number
+        0..n_components - 1, numbered by ascending first entry (None without with_ids); indices (N) int32, the index of the
+        entry's word in the node buffer, what scatter_nodes_device takes; sizes (n_components) int64, the cells of the
+        `depth` grid per component.  The same for every layout of the same tree and on every run, indices excepted.
+        depth=None: the depth declared for this tree, as in list_voxels.  Raises SvoError as list_voxels does.  The node
+        buffer is only read."""
+        dev = self.gpu.torch_device
+        p = ComponentsParams()
+        p.flags = 1 if same_value else 0
+        p.depth = self._depth(depth)
+        p.n_words = int(self.node_length)
+        n, c = C.c_uint64(), C.c_uint64()
+        fn = lib().svo_nodes_label_components
+        # the count query is the listing's: the entries are its entries, and it stops before the union
+        q = ListParams()
+        q.depth, q.n_words = p.depth, p.n_words
+        self.gpu.check(lib().svo_nodes_list_voxels(self.gpu._h, C.byref(q), None, None, None, C.byref(n)))
+        count = n.value
+        want_ids = with_ids or with_sizes
+        labels = torch.empty(count, dtype=torch.int32, device=dev)
+        ids = torch.empty(count, dtype=torch.int32, device=dev) if want_ids else None
+        indices = torch.empty(count, dtype=torch.int32, device=dev) if with_indices else None
+        if count:
+            p.max_entries = count
+            wait_for_torch(self.gpu)
+            self.gpu.check(fn(self.gpu._h, C.byref(p), labels.data_ptr(), ids.data_ptr() if want_ids else None,
+                              indices.data_ptr() if with_indices else None, C.byref(n), C.byref(c)))
+            self.gpu.sync()
+        out = (labels, ids if with_ids else None, c.value) + ((indices,) if with_indices else ())
+        if with_sizes:
+            # integer adds commute: exact, and the same on every run
+            levels = self.list_voxels(p.depth, with_levels=True)[2].to(torch.int64)
+            sizes = torch.zeros(c.value, dtype=torch.int64, device=dev)
+            sizes.index_add_(0, ids.to(torch.int64), torch.ones_like(levels) << (3 * (p.depth - levels)))
+            out += (sizes,)
+        return out
+
+    def scatter_nodes_device(self, indices, words=None, fill=None):
+        """words[i], or the one word `fill`, to the node buffer at indices[i] without leaving the device
+        (svo_nodes_scatter_device): indices as sample_voxels(with_indices=True) and label_components(with_indices=True)
+        give them, device tensors (or numpy, copied there); an index behind node_length, -1 included, is skipped.  Of
+        duplicate indices with different words, which one lands is unspecified.  A later frame waits for the write."""
+        if (words is None) == (fill is None):
+            raise ValueError("give words or fill, not both")
+        dev = self.gpu.torch_device
+        idx = device_u32(indices, dev, what="indices").reshape(-1)
+        n = idx.numel()
+        w = device_u32(words, dev, what="words").reshape(-1) if words is not None else None
+        if w is not None and w.numel() != n:
+            raise ValueError(f"{w.numel()} words for {n} indices")
+        wait_for_torch(self.gpu)
+        self.gpu.check(lib().svo_nodes_scatter_device(self.gpu._h, idx.data_ptr() if n else None, w.data_ptr() if w is not None and n else None,
+                                                      int(fill or 0) & 0xFFFFFFFF, n, int(self.node_length)))
+        self.gpu.sync()  # (the inputs may be released by the caller)
+
+    def drop_floating(self, depth=None, anchor=None, same_value=False):
+        """Empty the leaves of every component that is not anchored, on the GPU (label_components, then
+        scatter_nodes_device).  anchor: a box (lo, hi) in cells of the `depth` grid, hi exclusive; None: the
+        floor layer ((0, 0, 0), (2^depth, 1, 2^depth)), y being up as in column_tops.  A component is anchored when the
+        cube of at least one of its leaves meets the box; the leaves of every other component get the empty word.
+        Returns (n_components, n_dropped_components, n_dropped_leaves).  The groups this leaves empty stay where they
+        are: compact_nodes(prune=True) drops them."""
+        depth = self._depth(depth)
+        side = 1 << min(depth, 31)
+        lo, hi = ((0, 0, 0), (side, 1, side)) if anchor is None else ([int(v) for v in anchor[0]], [int(v) for v in anchor[1]])
+        if len(lo) != 3 or len(hi) != 3:
+            raise ValueError(f"anchor must be two corners of three cells each, got {anchor!r}")
+        _, ids, n_components, indices = self.label_components(depth, same_value, with_indices=True)
+        if not n_components:
+            return 0, 0, 0
+        coords, _, levels = self.list_voxels(depth, with_levels=True)
+        dev = self.gpu.torch_device
+        first = coords.to(torch.int64)
+        last = first + (torch.ones_like(levels, dtype=torch.int64) << (depth - levels.to(torch.int64)))[:, None]
+        meets = ((first < torch.tensor(hi, device=dev)) & (last > torch.tensor(lo, device=dev))).all(dim=1)
+        held = torch.zeros(n_components, dtype=torch.int64, device=dev).index_add_(0, ids.to(torch.int64), meets.to(torch.int64)) > 0
+        drop = ~held[ids.to(torch.int64)]
+        n_dropped, n_leaves = int((~held).sum()), int(drop.sum())
+        if n_leaves:
+            self.scatter_nodes_device(indices[drop], fill=EMPTY_WORD)
+        return n_components, n_dropped, n_leaves
 
     def _sample_params(self, depth):
         p = SampleParams()
