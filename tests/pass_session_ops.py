@@ -19,6 +19,11 @@ A session is generated and modelled in one go, because what an op means depends 
 word short of what the call needs): session(name) returns its steps, one dict per op with the concrete inputs of the call,
 what it must return, the words the device must hold after it and what the host test tallies.  The model also keeps a second state,
 a dense grid of cell values that only the per-cell contracts update; after every mutating op the words, sampled, must equal it.
+
+The passes that came later -- combine, rects (surface_rects), components (label_components) and drop (drop_floating), their
+refusal kinds and the sessions seed301..seed303 and worst_combinations() -- stand in pass_session_ops2.py, which reuses Gen and
+Model.  PASSES, SHARED, REFUSALS and the seven sessions here stay as they are: a name added to them would reshuffle
+all_pairs() and with it every session, and tests/golden/pass_session_ops.txt pins their op lines.
 """
 import collections
 import functools

@@ -8,7 +8,15 @@ model's words (the second from stored lists).  After every query: every returned
 order and dtype, one in five by a raw call into sentinel-filled buffers whose tail must stay.  After every refused call: the
 library's message, the words and node_length as they were.  In a rest of the owner: every frame bit-exact and the static deal
 replaying when and only when session_ops.Tracker says the ops determine it.  Nothing that depends on a measured time is
-asserted.  A failure names the session, the op and the twelve ops before it: a prefix of the session replays it."""
+asserted.  A failure names the session, the op and the twelve ops before it: a prefix of the session replays it.
+
+The second table (tests/pass_session_ops2.py) adds four sessions, seed301..seed303 and worst_combinations, of 70 to 85 calls
+with the same discipline: combine_nodes with all six ops from a third Render on a context of its own, from a bare tensor and
+from the pair of an out-of-place simplification of the scene (a combine mutates: return value, node_length, the words, the
+source's words unchanged, two frames by the context that did not write); drop_floating (its triple; when it drops a leaf it is
+a write like any other, when it drops none a query that is always followed by a comparison of the words); surface_rects and
+label_components as queries, one in five raw into sentinel-filled buffers; and the refusals of REFUSALS2, after which the
+source of a combine holds what it held."""
 import collections
 import ctypes as C
 import time
@@ -17,6 +25,7 @@ import numpy as np
 import pytest
 
 import pass_session_ops as P
+import pass_session_ops2 as P2
 import session_ops as S
 from conftest import assert_hits_equal, set_uniforms_from_oracle
 from pass_frame import SLACK, SentinelOut
@@ -33,15 +42,18 @@ def driver(tmp_path_factory):
 
 @pytest.fixture
 def contexts(pkg):
-    """a context of the case's own, and the second one that shares its node buffer (on a stream of its own)"""
+    """a context of the case's own, the second one that shares its node buffer (on a stream of its own), and a third one
+    with a node buffer of its own for the sources of the combines"""
     import torch
     if not torch.cuda.is_available():
         pytest.skip("no GPU")
     if HALT:
         pytest.fail(f"not started: an earlier session met a device error ({HALT[0]})")
-    owner, other = pkg.Gpu(0), pkg.Gpu(0)
+    owner, other, third = pkg.Gpu(0), pkg.Gpu(0), pkg.Gpu(0)
     other.use_own_stream()
-    yield owner, other
+    third.use_own_stream()
+    yield owner, other, third
+    third.close()
     other.close()
     owner.close()
 
@@ -54,13 +66,14 @@ class PassSession:
     def __init__(self, pkg, O, driver, name, steps, gpus):
         import torch
         self.torch, self.pkg, self.O, self.name, self.steps = torch, pkg, O, name, steps
-        self.gpu, self.gpu2 = gpus
+        self.gpu, self.gpu2, self.gpu3 = gpus
         self.views = P.Views(O)
         self.plan = S.Tracker(self.views).plan(P.owner_ops(steps)[0], driver)
         self.next_frame = 0
         self.render = pkg.Render(self.gpu, (64, 64), np.full(8, P.B.EMPTY, dtype=np.uint32), capacity=P.CAPACITY)
         self.gpu.sync()
         self.share = pkg.Render.share_nodes(self.gpu2, self.render)
+        self.source = pkg.Render(self.gpu3, (64, 64), np.full(8, P.B.EMPTY, dtype=np.uint32), capacity=P2.SRC_CAPACITY)
         offsets, index, colours = P.tree_structure()
         self.structure = pkg.Structure(offsets, index, colours)
         self.words = np.full(8, P.B.EMPTY, dtype=np.uint32)  # the model's words after the last mutating step, up to its high-water
@@ -86,8 +99,9 @@ class PassSession:
     def run(self):
         began = time.perf_counter()
         try:
+            slowest = (0.0, 0)
             for self.at, step in enumerate(self.steps):
-                op = step["op"]
+                op, t0 = step["op"], time.perf_counter()
                 if op.kind == "frame":
                     self.frames(self.render, self.gpu, step["pose"], op.args[1], f"{op!r}", owner=True)
                 elif step["refused"]:
@@ -97,8 +111,9 @@ class PassSession:
                 else:
                     self.query(step)
                 assert self.gpu.tree_depth == step["declared"] and self.gpu2.tree_depth == step["declared"], "the declared depth moved"
+                slowest = max(slowest, (time.perf_counter() - t0, self.at))
             assert self.next_frame == len(self.plan)
-            print(f"{self.name}: {time.perf_counter() - began:.1f} s, {dict(self.tally)}")
+            print(f"{self.name}: {time.perf_counter() - began:.1f} s (the slowest op, {slowest[1]}: {slowest[0]:.2f} s), {dict(self.tally)}")
         except AssertionError as e:
             raise AssertionError(f"{e}\n{self.context()}") from None
         except self.pkg.SvoError as e:  # (nothing more is asked of the device, the deal's state included)
@@ -194,6 +209,14 @@ class PassSession:
             ret = r.simplify_nodes(merge=a["merge"], cut_level=a["cut_level"], min_level=a["min_level"])
         elif kind == "stamp":
             ret = self.stamp(r, a, want, f"{op!r}")
+        elif kind == "combine":
+            src, held = self.combine_source(r, other, a, f"{op!r}")
+            ret = r.combine_nodes(src, a["op"], a["depth"], at=a["at"], at_level=a["at_level"])
+            held(f"{op!r}")
+        elif kind == "drop":
+            got = r.drop_floating(a["depth"], a["anchor"], a["same_value"])
+            assert got == want["triple"], f"{op!r} returned {got}, want {want['triple']}"
+            ret = r.node_length
         else:
             raise ValueError(op)
         assert ret == want["ret"] == r.node_length, f"{op!r} returned {ret}, node_length {r.node_length}, want {want['ret']}"
@@ -205,6 +228,35 @@ class PassSession:
         self.frames(other, other_gpu, step["pose"], 2, f"behind {op!r}", owner=step["via"])
         self.tally["writes"] += 1
         self.tally["writes through the sharing context"] += step["via"]
+
+    def combine_source(self, r, other, a, what):
+        """(what combine_nodes takes as the source, a check that the source still holds its words) for a["form"]: the third
+        Render holding the words, a bare tensor of them, the pair of the scene's own out-of-place simplification, or -- for
+        the refusal -- the Render on the other context of the pair, which shares the node buffer"""
+        form, words = a["form"], a["src"]
+        if form == "sharing":
+            return other, lambda what: None  # (the words of the node buffer are compared after every refusal)
+        if form == "render":
+            self.source.write_nodes(words)
+            self.source.node_length = words.size
+
+            def held(what):
+                assert self.source.node_length == words.size, f"{what}: the source's node_length moved"
+                assert np.array_equal(self.source.read_nodes(words.size), words), f"{what}: the source's words changed"
+            return self.source, held
+        if form == "pair":
+            t, n = r.simplify_nodes(merge=a["merge"], cut_level=a["cut_level"], out_of_place=True)
+            assert n == words.size == len(t) and r.node_length == self.length, f"{what}: the out-of-place simplification has {n} words, want {words.size}"
+            self.same((t,), (words,), f"{what}: the out-of-place simplification")
+            src = (t, n)
+        else:
+            t = self.torch.from_numpy(np.ascontiguousarray(words).view(np.int32)).to(r.gpu.torch_device)
+            self.torch.cuda.current_stream(r.gpu.torch_device).synchronize()
+            src = t
+
+        def held(what):
+            assert np.array_equal(u32(t), words), f"{what}: the source's words changed"
+        return src, held
 
     def shapes(self, shapes):
         R = self.pkg.region
@@ -243,7 +295,7 @@ class PassSession:
         r, g, _, _ = self.through(False)
         kind, what = op.kind, f"{op!r}"
         self.queries += kind != "simplify"
-        raw = kind != "simplify" and self.queries % 5 == 0
+        raw = kind not in ("simplify", "drop") and self.queries % 5 == 0
         if kind == "simplify":  # out of place: the buffer is only read, and no rest ends
             words, n = r.simplify_nodes(merge=a["merge"], cut_level=a["cut_level"], min_level=a["min_level"], out_of_place=True)
             assert n == step["want"]["words"].size == len(words) and r.node_length == self.length, what
@@ -283,6 +335,27 @@ class PassSession:
                 self.raw_box(out[0].size, out, what, lambda t: self.pkg._lib.lib().svo_nodes_column_tops(
                     self.gpu._h, C.byref(p), (C.c_uint32 * 2)(*a["origin"]), (C.c_uint32 * 2)(*a["size"]), t[0].data_ptr(), t[1].data_ptr()))
             self.same(r.column_tops(a["origin"], a["size"], step["depth"], a["y_range"], with_values=True), out, what)
+        elif kind == "rects":
+            if raw:
+                self.raw_rects(a, out, what)
+            self.same(r.surface_rects(a["depth"], a["closed"], a["rounds"], a["any_value"]), out, what)
+        elif kind == "components":
+            label, ids, n, indices, sizes = step["want"]["out"]
+            if raw:
+                self.raw_components(a, (label, ids, indices), n, what)
+            got = r.label_components(a["depth"], a["same_value"], True, a["with_indices"], a["with_sizes"])
+            assert len(got) == 3 + a["with_indices"] + a["with_sizes"] and got[2] == n, f"{what}: {got[2]} components, want {n}"
+            self.same(got[:2] + ((got[3],) if a["with_indices"] else ()), (label, ids) + ((indices,) if a["with_indices"] else ()), what)
+            if a["with_sizes"]:
+                t = got[-1]
+                assert t.dtype == self.torch.int64 and t.is_cuda and tuple(t.shape) == sizes.shape, f"{what}: sizes are {t.dtype}, {tuple(t.shape)}"
+                assert np.array_equal(t.cpu().numpy(), sizes), f"{what}: the sizes differ"
+                self.tally["result arrays compared"] += 1
+        elif kind == "drop":  # one that drops nothing: a query, and always held to have written nothing
+            got = r.drop_floating(a["depth"], a["anchor"], a["same_value"])
+            assert got == step["want"]["triple"], f"{what} returned {got}, want {step['want']['triple']}"
+            assert r.node_length == self.length, f"{what}: node_length moved to {r.node_length}"
+            self.nodes(f"after {what}: nothing floats, nothing is written")
         else:
             raise ValueError(op)
         self.tally["queries"] += 1
@@ -309,6 +382,42 @@ class PassSession:
         for got, w in zip(out.host(), want):
             assert np.array_equal(got[:n_want], w), f"{what}: the raw call's entries differ"
 
+    def raw_rects(self, a, want, what):
+        """svo_nodes_merge_surface: the count query, then the fill into buffers SLACK entries longer than the count"""
+        rects, values = want
+        n_want = len(values)
+        p = self.pkg._lib.SurfaceMergeParams()
+        p.flags = (1 if a["closed"] else 0) | (8 if a["any_value"] else 0)
+        p.depth, p.rounds, p.n_words = self.gpu.tree_depth if a["depth"] is None else a["depth"], a["rounds"], self.length
+        n = C.c_uint64(0xAAAA)
+        fn = self.pkg._lib.lib().svo_nodes_merge_surface
+        self.gpu.check(fn(self.gpu._h, C.byref(p), None, None, C.byref(n)))
+        assert n.value == n_want, f"{what}: the count query gives {n.value}, want {n_want}"
+        out = SentinelOut(self.gpu, [(n_want + SLACK, 6), n_want + SLACK])
+        p.max_entries = n_want
+        if n_want:
+            self.gpu.check(fn(self.gpu._h, C.byref(p), *[t.data_ptr() for t in out.t], C.byref(n)))
+            self.gpu.sync()
+        assert n.value == n_want and out.untouched_from(n_want), f"{what}: the fill wrote behind its {n_want} entries"
+        for got, w in zip(out.host(), (rects, values)):
+            assert np.array_equal(got[:n_want], w), f"{what}: the raw call's entries differ"
+
+    def raw_components(self, a, want, n_components, what):
+        """svo_nodes_label_components into buffers SLACK entries longer than the listing's count"""
+        n_want = len(want[0])
+        p = self.pkg._lib.ComponentsParams()
+        p.flags, p.depth = (1 if a["same_value"] else 0), self.gpu.tree_depth if a["depth"] is None else a["depth"]
+        p.n_words, p.max_entries = self.length, n_want
+        n, c = C.c_uint64(0xAAAA), C.c_uint64(0xAAAA)
+        out = SentinelOut(self.gpu, [n_want + SLACK] * 3)
+        ptrs = [t.data_ptr() for t in out.t] if n_want else [None] * 3
+        self.gpu.check(self.pkg._lib.lib().svo_nodes_label_components(self.gpu._h, C.byref(p), *ptrs, C.byref(n), C.byref(c)))
+        self.gpu.sync()
+        assert (n.value, c.value) == (n_want, n_components), f"{what}: the raw call gives {n.value} entries in {c.value} components, want {n_want} in {n_components}"
+        assert out.untouched_from(n_want), f"{what}: the raw call wrote behind its {n_want} entries"
+        for got, w in zip(out.host(), want):
+            assert np.array_equal(got[:n_want], np.asarray(w).astype(np.uint32)), f"{what}: the raw call's entries differ"
+
     def raw_box(self, n, want, what, call):
         """a dense result of n entries per array into flat buffers SLACK entries longer"""
         out = SentinelOut(self.gpu, [n + SLACK] * len(want))
@@ -334,8 +443,19 @@ class PassSession:
         pkg, a, op = self.pkg, step["action"], step["op"]
         kind = op.args[0]
         _, cls, fragment = step["refused"]
-        r, g, _, _ = self.through(step["via"])
+        r, g, other, _ = self.through(step["via"])
+        held = None
+        if step["refused"][0] == "combine":
+            src, held = self.combine_source(r, other, a, f"{op!r}")
         calls = {
+            "combine_finer": lambda: r.combine_nodes(src, a["op"], a["depth"]),
+            "max_words_combine": lambda: r.combine_nodes(src, a["op"], a["depth"], max_words=a["max_words"]),
+            "combine_overlap": lambda: r.combine_nodes(src, a["op"], a["depth"]),
+            "source_malformed": lambda: r.combine_nodes(src, a["op"], a["depth"]),
+            "rects_depth": lambda: r.surface_rects(a["depth"]),
+            "components_depth": lambda: r.label_components(a["depth"]),
+            "max_entries_rects": lambda: self.raw_short(r, "rects", a),
+            "max_entries_components": lambda: self.raw_short(r, "components", a),
             "max_words_build": lambda: r.build_nodes(a["coords"], a["depth"], a["colours"], max_words=a["max_words"]),
             "max_words_edit": lambda: r.edit_nodes(a["coords"], a["depth"], a["colours"], max_words=a["max_words"]),
             "max_words_region": lambda: r.edit_region(self.shapes(a["shapes"]), a["depth"], max_words=a["max_words"]),
@@ -348,7 +468,9 @@ class PassSession:
         }
         if kind.startswith("malformed"):  # one interior pointer off the multiple of 8 for the call, then back
             calls[kind] = {"compact": r.compact_nodes, "simplify": r.simplify_nodes, "list": lambda: r.list_voxels(a["depth"]),
-                           "surface": lambda: r.list_surface(a["depth"])}[step["refused"][0]]
+                           "surface": lambda: r.list_surface(a["depth"]), "rects": lambda: r.surface_rects(a["depth"], rounds=2),
+                           "components": lambda: r.label_components(a["depth"], with_indices=True),
+                           "combine": lambda: r.combine_nodes(src, a["op"], a["depth"])}[step["refused"][0]]
             r.scatter_nodes([a["at"]], [a["bad"]])
         try:
             with pytest.raises(getattr(pkg, cls)) as e:
@@ -359,9 +481,32 @@ class PassSession:
         assert fragment in str(e.value), f"{op!r}: the refusal says {e.value}, want '{fragment}'"
         assert r.node_length == self.length, f"{op!r}: a refused call moved node_length to {r.node_length}"
         self.nodes(f"after {op!r}: a refused call writes nothing")
+        if held:
+            held(f"after {op!r}")
         self.tally["refused calls"] += 1
 
 
-@pytest.mark.parametrize("name", P.NAMES)
+    def raw_short(self, r, which, a):
+        """the raw entry point with outputs of max_entries = the count less one: refused, and nothing written to them"""
+        n, c = C.c_uint64(0), C.c_uint64(0)
+        cap = a["max_entries"]
+        if which == "rects":
+            p = self.pkg._lib.SurfaceMergeParams()
+            p.flags, p.depth, p.rounds, p.n_words, p.max_entries = 0, a["depth"], a["rounds"], self.length, cap
+            out = SentinelOut(r.gpu, [(cap + SLACK, 6), cap + SLACK])
+            rc = self.pkg._lib.lib().svo_nodes_merge_surface(r.gpu._h, C.byref(p), *[t.data_ptr() for t in out.t], C.byref(n))
+        else:
+            p = self.pkg._lib.ComponentsParams()
+            p.flags, p.depth, p.n_words, p.max_entries = 0, a["depth"], self.length, cap
+            out = SentinelOut(r.gpu, [cap + SLACK] * 3)
+            rc = self.pkg._lib.lib().svo_nodes_label_components(r.gpu._h, C.byref(p), *[t.data_ptr() for t in out.t], C.byref(n), C.byref(c))
+        try:
+            r.gpu.check(rc)
+        finally:
+            r.gpu.sync()
+            assert out.untouched_from(0), f"{which}: a call refused for max_entries wrote to its outputs"
+
+
+@pytest.mark.parametrize("name", P2.ALL_NAMES)
 def test_pass_session(pkg, O, driver, contexts, name):
-    PassSession(pkg, O, driver, name, P.session(name), contexts).run()
+    PassSession(pkg, O, driver, name, P2.session(name), contexts).run()
