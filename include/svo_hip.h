@@ -562,6 +562,71 @@ int svo_nodes_combine(svo_ctx *ctx, const uint32_t *src_dev, const svo_combine_p
 #define SVO_COMBINE_TIMES 5   /* plan (with its per-level read-backs), status, fill, write, host wall */
 int svo_combine_timing(svo_ctx *ctx, float ms_out[SVO_COMBINE_TIMES]);
 
+/* ---- a device tree placed into the scene at any cell offset and orientation ----
+ * svo_nodes_combine without the condition that the source's cube is a cell of the scene's octree.  The scene A is the first
+ * n_words words of the node buffer on a grid of depth `depth` (side N); the source B is the src_words words at src_dev (DEVICE,
+ * rooted at group 0, ONLY READ, hit counters ignored) on a grid of depth src_depth (side S) WITH THE SAME CELLS: one cell of the
+ * source is one cell of the scene.  `offset` is in cells.  orient = 8 p + 4 fx + 2 fy + fz is one of the cube's 48 symmetries:
+ * p indexes the axis permutations in lexicographic order, (0,1,2) (0,2,1) (1,0,2) (1,2,0) (2,0,1) (2,1,0), and the ORIENTED
+ * source has at cell r what the source has at q, with r[i] = f_i ? S - 1 - q[perm[i]] : q[perm[i]]; 0 is the identity.
+ * Per cell c of the `depth` grid, with r = c - offset: when r lies in [0, S)^3 the cell samples (svo_nodes_sample) afterwards
+ * to f(a, b), a = what the scene sampled at c before, b = the oriented source at r, f by op as svo_nodes_combine's
+ * (SVO_COMBINE_OVER .. SVO_COMBINE_REPLACE).  Every other cell samples as before: a source partly outside the scene is clipped,
+ * one wholly outside writes nothing and *n_words_out = n_words.
+ * The words are deterministic, the same bytes on every run (no atomics: the order is the contract), by this rule.  The walk is
+ * svo_nodes_combine's: level by level from the scene's root group, the frontier of level l + 1 the eight children, by child
+ * index, of every word of level l that was opened or split, those taken in frontier order; the g-th split gets the group
+ * n_words + 8 g, *n_words_out = n_words + 8 * splits, and nothing at or behind *n_words_out is touched.
+ * ITEMS.  A scene word of level l has cells of z = 2^(depth - l) and faces the cells of size z of the oriented source's grid
+ * that its cube overlaps: per axis one when (-offset) mod z == 0 and two otherwise, so 1, 2, 4 or 8, the same count for every
+ * word of a level, and one at level `depth`.  Each such item is OUT (outside the source's cube), a constant b (a source leaf,
+ * or carried down from one), a source interior word, or, when z >= S, the cell at the origin that holds the source's cube:
+ * with z == S the root, as an interior word pointing at the source's group 0, and with z > S a virtual word whose child
+ * (0,0,0) leads on towards the root and whose other seven are OUT.  A virtual word holds the source's cube in its corner and
+ * nothing else, so only a scene word whose cube overlaps the source's cube faces it: for a word beside the cube (x z - offset
+ * >= S on an axis) the item is OUT.  A group's record holds the eight items of its parent's
+ * cell; a word's items are children of those: per axis, with h = ((-offset) mod 2 z) >= z, item j (0, or 1 where there are
+ * two) of child c is the child (c + h + j) & 1 of the parent's item (c + h + j) >> 1.  The oriented child index r maps to the
+ * source's child index by one fixed permutation of 0..7, the same at every level (bit perm[i] of the source's index is bit i
+ * of r, flipped when f_i); it is not applied above the root.
+ * NORMALISATION, THEN THE DECISION.  For OVER, UNDER, PAINT and CARVE, where f(a, 0) = a, OUT counts as the constant 0; for KEEP
+ * and REPLACE it stays a kind of its own.  For CARVE and KEEP every b != 0 counts as one value.  Then:
+ *     all items OUT:  the scene word and everything below it keep all 32 bits
+ *     all items one constant b:  svo_nodes_combine's "source leaf or constant b" rule: overwrite, identity, collapse, or open
+ *         with the children facing the children of the same items
+ *     anything else:  svo_nodes_combine's "source interior" rule: a scene interior word is opened; a scene leaf a stays
+ *         untouched when f(a, .) is a whatever the source holds; any other leaf is SPLIT, its colour carried into eight new leaf
+ *         words, counter 0, and the children are paired with their own items.  A coarse leaf may so be split where all cells
+ *         come out equal again (its items differed only in kind); svo_nodes_simplify merges those afterwards
+ * Opening or splitting at level `depth` is refused as svo_nodes_combine refuses it: the scene is finer there than `depth`, or
+ * the source finer than src_depth.  SVO_ERR_STATE, nothing written, svo_last_error names the cell and the finer tree.
+ * With orient 0, src_depth = depth - at_level and offset = at << src_depth the words are byte for byte those of
+ * svo_nodes_combine: above at_level the words that overlap the source's cube are the path to `at`.  A second identical call on
+ * the result writes nothing and appends nothing.
+ * Every error is decided by a read-only plan before any write; of several causes the first in this order is reported.
+ * SVO_ERR_ARG: NULL p, n_words_out or src_dev; op > 5; depth outside 1..21; src_depth outside 1..depth; orient >= 48; an offset
+ * outside [-2^21, 2^21].  Then svo_nodes_combine's, from "no node buffer" on, with "malformed source: ..." for a source pointer
+ * that the call follows: an interior item of a word that is opened or split.
+ * Stream ordering, blocking (once per level and once for the status) and the recording of the write for the contexts that share
+ * the buffer are svo_nodes_combine's. */
+#define SVO_PLACE_ORIENTS 48u
+typedef struct svo_place_params {
+    uint32_t op;         /* SVO_COMBINE_OVER .. SVO_COMBINE_REPLACE */
+    uint32_t depth;      /* 1..21: the scene grid; no word below this level is made or opened */
+    uint32_t src_depth;  /* 1..depth: the source's cube has 2^src_depth cells a side */
+    uint32_t orient;     /* 0..47: 8 p + 4 fx + 2 fy + fz; 0 = as it is */
+    int32_t offset[3];   /* the scene cell of the oriented source's cell (0,0,0): -2^21..2^21 each */
+    uint32_t reserved;
+    uint64_t n_words;    /* the scene: words [0, n_words) of the node buffer */
+    uint64_t src_words;  /* the source: words [0, src_words) at src_dev, rooted at group 0 */
+    uint64_t max_words;  /* 0 = the capacity; never above SVO_VOXEL_OFFSET */
+} svo_place_params;
+int svo_nodes_place(svo_ctx *ctx, const uint32_t *src_dev, const svo_place_params *p, uint64_t *n_words_out);
+/* Times (ms) of the last placement: [0] plan (with its per-level read-backs), [1] status, [2] fill, [3] write (device events;
+ * waits for the write), [4] host wall time of the call.  A refused call leaves the times of the last one that ran. */
+#define SVO_PLACE_TIMES 5   /* plan (with its per-level read-backs), status, fill, write, host wall */
+int svo_place_timing(svo_ctx *ctx, float ms_out[SVO_PLACE_TIMES]);
+
 /* ---- the tree in the node buffer compacted in place ----
  * Reads the first n_words words of the node buffer as a tree rooted at group 0.  E = SVO_VOXEL_OFFSET << 4 is the empty
  * word; a word is interior when word >> 4 < SVO_VOXEL_OFFSET.

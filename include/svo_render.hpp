@@ -324,6 +324,23 @@ class Render {  // render.rs:3-285
         gpu_.poll_wait();  // the source may go away
         return new_words;
     }
+    // the source tree, a cube of 2^src_depth cells a side with the scene's cells, placed into the scene at any cell offset
+    // (null: 0, 0, 0) and in any of the cube's 48 orientations (svo_nodes_place): combine_nodes without the
+    // condition that the source's cube is a cell of the scene's octree.  The part outside the scene is clipped; returns the new
+    // length.  Throws, with nothing written, where either tree is finer than its depth and the op has to look below.
+    uint64_t place_nodes(uint64_t n_words, const uint32_t *src_dev, uint64_t src_words, uint32_t op, uint32_t depth, uint32_t src_depth,
+                         const int32_t *offset = nullptr, uint32_t orient = 0, uint64_t max_words = 0) {
+        if (depth > declared_depth_) {
+            gpu_.set_option(SVO_OPT_TREE_DEPTH, depth);
+            declared_depth_ = depth;
+        }
+        const svo_place_params p{op, depth, src_depth, orient, {offset ? offset[0] : 0, offset ? offset[1] : 0, offset ? offset[2] : 0}, 0u,
+                                 n_words, src_words, max_words};
+        uint64_t new_words = 0;
+        gpu_.check(svo_nodes_place(gpu_.ctx(), src_dev, &p, &new_words));
+        gpu_.poll_wait();  // the source may go away
+        return new_words;
+    }
     // the first n_words words of the node buffer compacted in place (svo_nodes_compact): unreachable groups
     // dropped, with `prune` also the groups that hold nothing, the rest in the builder's breadth-first order; returns the
     // new length.  perm_dev (device, n_words u32, or null): perm[new word] = old word.  Throws, with nothing written, for

@@ -100,6 +100,21 @@ class CombineParams(C.Structure):
     ]
 
 
+class PlaceParams(C.Structure):
+    """svo_place_params: a second tree placed into the tree in the node buffer at a cell offset and orientation (include/svo_hip.h)."""
+    _fields_ = [
+        ("op", C.c_uint32),
+        ("depth", C.c_uint32),
+        ("src_depth", C.c_uint32),
+        ("orient", C.c_uint32),
+        ("offset", C.c_int32 * 3),
+        ("reserved", C.c_uint32),
+        ("n_words", C.c_uint64),
+        ("src_words", C.c_uint64),
+        ("max_words", C.c_uint64),
+    ]
+
+
 class CompactParams(C.Structure):
     """svo_compact_params: the tree in the node buffer compacted in place (include/svo_hip.h)."""
     _fields_ = [
@@ -318,6 +333,8 @@ DEVICE_SIGNATURES = {
     "svo_region_timing": (C.c_int, (vp, fp)),
     "svo_nodes_combine": (C.c_int, (vp, vp, C.POINTER(CombineParams), C.POINTER(u64))),
     "svo_combine_timing": (C.c_int, (vp, fp)),
+    "svo_nodes_place": (C.c_int, (vp, vp, C.POINTER(PlaceParams), C.POINTER(u64))),
+    "svo_place_timing": (C.c_int, (vp, fp)),
     "svo_nodes_compact": (C.c_int, (vp, C.POINTER(CompactParams), vp, C.POINTER(u64))),
     "svo_compact_timing": (C.c_int, (vp, fp)),
     "svo_nodes_simplify": (C.c_int, (vp, C.POINTER(SimplifyParams), vp, vp, C.POINTER(u64))),

@@ -29,6 +29,7 @@
 #include <cstring>
 #include <string>
 
+#include "svo_combine_rules.h"  // (combine_value, whole_subtree, whole_constant, leaf_stays)
 #include "svo_ctx.h"
 #include "svo_frontier.h"  // (kNone, leaf_word, region_mark_kernel, region_check_kernel, region_fill_kernel, region_write_kernel, grow_list)
 #include "svo_scan.h"  // (svo_scan_u32, block_min, min_of_blocks_kernel; svo_group.h: kThreads, kEmptyWord, kMaxWords)
@@ -44,37 +45,7 @@ enum Code : uint32_t { kOpen = 1u, kSplit = 2u, kSceneFiner = 4u, kSourceFiner =
 // the words read back: the discovery's names for the first four (svo_ctx.h), then this pass's own
 enum Status { kStAlign = SVO_WALK_ALIGN, kStRange = SVO_WALK_RANGE, kStNext = SVO_WALK_NEXT, kStDup = SVO_WALK_DUP, kStSplits, kStBad, kStSrcAlign, kStSrcRange, kStWords };
 
-// ---- the rule's tables over (op, the scene's value empty or not, the source's value empty or not) ----
-// f(a, b) per cell
-__host__ __device__ inline uint32_t combine_value(uint32_t op, uint32_t a, uint32_t b) {
-    switch (op) {
-    case SVO_COMBINE_OVER: return b ? b : a;
-    case SVO_COMBINE_UNDER: return a ? a : b;
-    case SVO_COMBINE_PAINT: return a && b ? b : a;
-    case SVO_COMBINE_CARVE: return b ? 0u : a;
-    case SVO_COMBINE_KEEP: return b ? a : 0u;
-    default: return b;  // SVO_COMBINE_REPLACE
-    }
-}
-// an interior scene word against the source's leaf or constant b: f(., b) is the identity, a constant or neither; two bits
-// per (op, b != 0)
-enum Whole : uint32_t { kIdentity, kConstant, kOpenIt };
-__host__ __device__ inline uint32_t whole_subtree(uint32_t op, bool b_set) {
-    constexpr uint32_t table = kIdentity << 0 | kConstant << 2 |   // OVER: b == 0, b != 0
-                               kIdentity << 4 | kOpenIt << 6 |     // UNDER
-                               kIdentity << 8 | kOpenIt << 10 |    // PAINT
-                               kIdentity << 12 | kConstant << 14 | // CARVE
-                               kConstant << 16 | kIdentity << 18 | // KEEP
-                               kConstant << 20 | kConstant << 22;  // REPLACE
-    return table >> (4u * op + 2u * uint32_t(b_set)) & 3u;
-}
-// ... and the constant: b for OVER and REPLACE, empty for CARVE and KEEP
-__host__ __device__ inline uint32_t whole_constant(uint32_t op, uint32_t b) { return op == SVO_COMBINE_OVER || op == SVO_COMBINE_REPLACE ? b : 0u; }
-// a scene leaf a against an interior source word: f(a, .) is a whatever the source holds; one bit per (op, a != 0)
-__host__ __device__ inline bool leaf_stays(uint32_t op, bool a_set) {
-    constexpr uint32_t table = 1u << (2 * SVO_COMBINE_UNDER + 1) | 1u << (2 * SVO_COMBINE_PAINT) | 1u << (2 * SVO_COMBINE_CARVE) | 1u << (2 * SVO_COMBINE_KEEP);
-    return table >> (2u * op + uint32_t(a_set)) & 1u;
-}
+// (the rule's tables over the op and whether either value is empty: svo_combine_rules.h, shared with svo_place.hip)
 
 // The call's constants, by value to the kernels.
 struct Placement {

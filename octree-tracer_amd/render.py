@@ -6,7 +6,7 @@ import torch
 
 from . import sharding
 from ._device import device_u32, voxel_list, wait_for_torch
-from ._lib import BuildParams, CombineParams, CompactParams, ComponentsParams, EditParams, ListParams, RegionParams, SampleParams, SimplifyParams, SitesParams, StampParams, SurfaceMergeParams, SurfaceParams, TopsParams, Uniforms, lib
+from ._lib import BuildParams, CombineParams, CompactParams, ComponentsParams, EditParams, ListParams, PlaceParams, RegionParams, SampleParams, SimplifyParams, SitesParams, StampParams, SurfaceMergeParams, SurfaceParams, TopsParams, Uniforms, lib
 from .camera import camera_matrices
 
 F_PAUSE_ADAPTIVE, F_SHOW_STEPS, F_SHOW_HITS, F_SHADOWS, F_MISC_BOOL = 1, 2, 4, 8, 16
@@ -186,6 +186,23 @@ class Render:
         self.node_length = out.value
         return out.value
 
+    def _source_tree(self, source):
+        """a second device tree that a pass only reads, in the three forms combine_nodes and place_nodes take: -> (address,
+        length in words, what keeps the words alive until the call returns)"""
+        if isinstance(source, Render):
+            if source.gpu.device != self.gpu.device:
+                raise ValueError(f"the source is on device {source.gpu.device}, the scene on device {self.gpu.device}")
+            ptr, room = C.c_void_p(), C.c_size_t()
+            source.gpu.check(lib().svo_nodes_device_ptr(source.gpu._h, C.byref(ptr), C.byref(room)))
+            source.gpu.sync()  # (its words may still be on their way on its own stream)
+            return ptr.value, int(source.node_length), source
+        words, length = source if isinstance(source, tuple) else (source, None)
+        words = device_u32(words, self.gpu.torch_device, what="source").reshape(-1)
+        src_words = int(words.numel() if length is None else length)
+        if src_words > words.numel():
+            raise ValueError(f"the source holds {words.numel()} words, fewer than its length {src_words}")
+        return (words.data_ptr() if words.numel() else None), src_words, words
+
     def combine_nodes(self, source, op="over", depth=None, at=(0, 0, 0), at_level=0, max_words=None):
         """Combine the tree that is in the node buffer, the scene, with a second device tree, the source, in place
         (svo_nodes_combine).  source: another Render on the same device (its first node_length words), a
@@ -203,20 +220,7 @@ class Render:
             if op not in COMBINE_OPS:
                 raise ValueError(f"op must be one of {', '.join(COMBINE_OPS)} (got {op!r})")
             op = COMBINE_OPS.index(op)
-        if isinstance(source, Render):
-            if source.gpu.device != self.gpu.device:
-                raise ValueError(f"the source is on device {source.gpu.device}, the scene on device {self.gpu.device}")
-            ptr, room = C.c_void_p(), C.c_size_t()
-            source.gpu.check(lib().svo_nodes_device_ptr(source.gpu._h, C.byref(ptr), C.byref(room)))
-            source.gpu.sync()  # (its words may still be on their way on its own stream)
-            src_ptr, src_words = ptr.value, int(source.node_length)
-        else:
-            words, length = source if isinstance(source, tuple) else (source, None)
-            words = device_u32(words, self.gpu.torch_device, what="source").reshape(-1)
-            src_words = int(words.numel() if length is None else length)
-            if src_words > words.numel():
-                raise ValueError(f"the source holds {words.numel()} words, fewer than its length {src_words}")
-            src_ptr = words.data_ptr() if words.numel() else None
+        src_ptr, src_words, _held = self._source_tree(source)
         if len(at) != 3:
             raise ValueError(f"at must be three cell coordinates, got {at!r}")
         self.gpu.declare_depth(depth)
@@ -231,6 +235,42 @@ class Render:
         out = C.c_uint64()
         wait_for_torch(self.gpu)
         self.gpu.check(lib().svo_nodes_combine(self.gpu._h, src_ptr, C.byref(p), C.byref(out)))
+        self.gpu.sync()  # (the source may be released by the caller)
+        self.node_length = out.value
+        return out.value
+
+    def place_nodes(self, source, op="over", depth=None, offset=(0, 0, 0), orient=0, src_depth=None, max_words=None):
+        """Place a second device tree, the source, into the tree that is in the node buffer, the scene, at any cell offset and
+        in any of the cube's 48 orientations, in place (svo_nodes_place): combine_nodes without the condition
+        that the source's cube is a cell of the scene's octree.  source and op are combine_nodes'.  The source is a cube of
+        2^src_depth cells a side (None: `depth`) whose cells are the scene's; oriented by `orient` (orientation.orientation,
+        from_matrix, quarter_turns_y; 0: as it is) about its own cube, its cell (0, 0, 0) then lies on the scene's cell
+        `offset`, which may be negative or hang over the scene's edge: the part outside is clipped, the cells outside the
+        source's cube stay as they are.  Coarse leaves stay coarse where both trees allow it; equal siblings that a split
+        leaves behind are simplify_nodes' to merge.  Where either tree is finer than its depth and the op has to look
+        below, SvoError is raised and nothing is written.  depth=None: the depth declared for this tree.  Returns the new
+        length (node_length)."""
+        depth = int(self.gpu.tree_depth if depth is None else depth)
+        if isinstance(op, str):
+            if op not in COMBINE_OPS:
+                raise ValueError(f"op must be one of {', '.join(COMBINE_OPS)} (got {op!r})")
+            op = COMBINE_OPS.index(op)
+        src_ptr, src_words, _held = self._source_tree(source)
+        if len(offset) != 3:
+            raise ValueError(f"offset must be three cell coordinates, got {offset!r}")
+        self.gpu.declare_depth(depth)
+        p = PlaceParams()
+        p.op = max(0, int(op))
+        p.depth = max(0, depth)
+        p.src_depth = max(0, int(depth if src_depth is None else src_depth))
+        p.orient = min(max(0, int(orient)), 0xFFFFFFFF)
+        p.offset[:] = [min(max(-0x80000000, int(v)), 0x7FFFFFFF) for v in offset]
+        p.n_words = int(self.node_length)
+        p.src_words = src_words
+        p.max_words = int(max_words or 0)
+        out = C.c_uint64()
+        wait_for_torch(self.gpu)
+        self.gpu.check(lib().svo_nodes_place(self.gpu._h, src_ptr, C.byref(p), C.byref(out)))
         self.gpu.sync()  # (the source may be released by the caller)
         self.node_length = out.value
         return out.value
