@@ -627,6 +627,70 @@ int svo_nodes_place(svo_ctx *ctx, const uint32_t *src_dev, const svo_place_param
 #define SVO_PLACE_TIMES 5   /* plan (with its per-level read-backs), status, fill, write, host wall */
 int svo_place_timing(svo_ctx *ctx, float ms_out[SVO_PLACE_TIMES]);
 
+/* ---- one step of morphology on the device tree: grow, shrink ----
+ * Edits the first n_words words of the node buffer in place, on a grid of depth `depth`, by one step of dilation (GROW) or
+ * erosion (SHRINK) under conn = 6, 18 or 26 neighbours: the offsets d in {-1,0,1}^3, d != 0, with |dx| + |dy| + |dz| <= 1, 2, 3.
+ * Per cell c of the grid, with a = what svo_nodes_sample gives at c before the call, the tree samples afterwards to
+ *     GROW    a != 0: a.  Otherwise take conn's offsets in PRIORITY ORDER, ascending (|d|_1, dx, dy, dz) with -1 < 0 < 1 (faces
+ *             before edges before corners), and let b be the value before the call at the first c + d that lies inside the grid
+ *             and is not empty: the cell becomes colour ? colour : b (colour 0 INHERITS the neighbour's value); without such
+ *             a d it stays 0
+ *     SHRINK  a == 0: 0.  Otherwise 0 when some d of conn has c + d empty before the call -- with SVO_MORPH_OPEN_BOUNDARY a
+ *             c + d outside the grid counts as empty too -- and a when none has
+ * Without the flag the outside is neutral for both ops: it never changes a cell.
+ * The words are deterministic, the same bytes on every run (no atomics: the order is the contract), by this rule.  The tree is
+ * processed level by level from the root group; the frontier of level l + 1 is the eight children, by child index, of every
+ * word of level l that was opened or split, those taken in frontier order.  A frontier entry is a scene word -- real, or a
+ * virtual child of a split, which holds one leaf value -- with 27 ITEMS: for each e in {-1,0,1}^3 the cell q + e of the word's
+ * own level, q its cell, as it was BEFORE the call.  An item is OUT (outside the grid), a constant (a leaf's value, carried down
+ * unchanged from a coarser leaf) or an interior word of the scene.  A group's record holds the 27 items of its parent's cell;
+ * item d of child c is, per axis with t = c + d in -1..2, the child t & 1 of the parent's item floor(t / 2).  The root group's
+ * parent is the whole grid, an interior word pointing at group 0 with OUT on all sides.
+ * NORMALISATION, THEN THE DECISION.  For GROW, OUT is the constant 0; for SHRINK a constant that is set, or 0 with
+ * SVO_MORPH_OPEN_BOUNDARY.  An item is QUIET when it is a constant that cannot change the word: 0 for GROW, any set value for
+ * SHRINK.  Only the items with d in conn COUNT, on coarse levels too: every neighbour of a cell of the word lies in the word or in
+ * one of those.  For one entry:
+ *     an interior word:  opened.  At level `depth` that is the refusal below: the tree is finer than `depth` there
+ *     a leaf that the op cannot change (GROW: a voxel; SHRINK: the empty word):  untouched; its items are not looked at
+ *     any other leaf, every counting item quiet:  untouched
+ *     any other leaf at level `depth`, some counting item not quiet:  a counting item that is interior is the REFUSAL:
+ *         SVO_ERR_STATE, nothing written, svo_last_error says "finer than depth" and names the cell.  Otherwise the leaf word
+ *         of the per-cell value is written, counter 0
+ *     any other leaf above level `depth`, some counting item not quiet:  SPLIT: a new group of eight leaf words OF ITS VALUE,
+ *         counter 0, is made, the word becomes the pointer to it as svo_nodes_edit_region writes it, and the eight virtual
+ *         children join the next frontier.  A coarse leaf may so be split where its cells come out equal again
+ * New groups are appended by level and within a level in frontier order: the g-th split gets the group n_words + 8 g, and
+ * *n_words_out = n_words + 8 * splits.  Nothing at or behind *n_words_out is touched; untouched words keep all 32 bits.  Merging
+ * the equal siblings that splits leave behind is svo_nodes_simplify's job afterwards; free groups are not reused.  THE WHOLE TREE
+ * IS WALKED, every interior word being opened: a merged tree (svo_nodes_simplify) is the cheap input.
+ * Every error is decided by a read-only plan before any write; of several causes the first in this order is reported.
+ * SVO_ERR_ARG: NULL p or n_words_out; op > 1; conn not 6, 18 or 26; depth outside 1..21; unknown flag bits; colour != 0 with
+ * SHRINK.  SVO_ERR_STATE: no node buffer; a device adaptive state attached to the context.  SVO_ERR_ARG: n_words not a positive
+ * multiple of 8 or above the capacity.  SVO_ERR_STATE: the "malformed tree: ..." causes with svo_nodes_compact's wording (an
+ * interior pointer that is not a multiple of 8 or with pointer + 8 > n_words, a group reached twice), on every word that the call
+ * opens and on every interior item it reads behind, each checked before the level that follows it; the refusal above.
+ * SVO_ERR_CAP when the exact new length exceeds max_words, the capacity or 2^27.
+ * Stream ordering, blocking (once per level and once for the status) and the recording of the write for the contexts that share
+ * the buffer are svo_nodes_edit_region's. */
+#define SVO_MORPH_GROW   0u
+#define SVO_MORPH_SHRINK 1u
+#define SVO_MORPH_OPEN_BOUNDARY 1u   /* flags: outside the grid counts as empty (only SHRINK can tell) */
+typedef struct svo_morph_params {
+    uint32_t op;         /* SVO_MORPH_GROW, SVO_MORPH_SHRINK */
+    uint32_t conn;       /* 6, 18 or 26 */
+    uint32_t depth;      /* 1..21: the grid of the cells; no word below this level is made or opened */
+    uint32_t flags;      /* SVO_MORPH_OPEN_BOUNDARY */
+    uint32_t colour;     /* GROW: the value of new cells, low 24 bits; 0 = inherit.  SHRINK: must be 0 */
+    uint32_t reserved;
+    uint64_t n_words;    /* the tree's current length: a multiple of 8, at least 8 */
+    uint64_t max_words;  /* 0 = the node buffer's capacity; never above SVO_VOXEL_OFFSET */
+} svo_morph_params;
+int svo_nodes_morph(svo_ctx *ctx, const svo_morph_params *p, uint64_t *n_words_out);
+/* Times (ms) of the last morphology step: [0] plan (with its per-level read-backs), [1] status, [2] fill, [3] write (device
+ * events; waits for the write), [4] host wall time of the call.  A refused call leaves the times of the last one that ran. */
+#define SVO_MORPH_TIMES 5   /* plan (with its per-level read-backs), status, fill, write, host wall */
+int svo_morph_timing(svo_ctx *ctx, float ms_out[SVO_MORPH_TIMES]);
+
 /* ---- the tree in the node buffer compacted in place ----
  * Reads the first n_words words of the node buffer as a tree rooted at group 0.  E = SVO_VOXEL_OFFSET << 4 is the empty
  * word; a word is interior when word >> 4 < SVO_VOXEL_OFFSET.

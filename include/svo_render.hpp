@@ -341,6 +341,24 @@ class Render {  // render.rs:3-285
         gpu_.poll_wait();  // the source may go away
         return new_words;
     }
+    // `steps` steps of morphology on the first n_words words of the node buffer, in place (svo_nodes_morph): op
+    // SVO_MORPH_GROW adds every empty cell with a voxel among its conn (6, 18 or 26) neighbours, in `colour` or with 0 in its
+    // first neighbour's value, SVO_MORPH_SHRINK empties every voxel with an empty cell among them (open_boundary: or the grid's
+    // outside).  Closing is grows, then as many shrinks; opening the reverse.  Returns the new length.  Throws where the tree is
+    // finer than `depth`; the steps before that one stay.  A merged tree (simplify_nodes) is the cheap input.
+    uint64_t morph_nodes(uint64_t n_words, uint32_t op, uint32_t depth, uint32_t steps = 1, uint32_t conn = 26, uint32_t colour = 0,
+                         bool open_boundary = false, uint64_t max_words = 0) {
+        if (depth > declared_depth_) {
+            gpu_.set_option(SVO_OPT_TREE_DEPTH, depth);
+            declared_depth_ = depth;
+        }
+        for (uint32_t step = 0; step < steps; step++) {
+            const svo_morph_params p{op, conn, depth, open_boundary ? SVO_MORPH_OPEN_BOUNDARY : 0u, op == SVO_MORPH_GROW ? colour & 0xFFFFFFu : 0u, 0u,
+                                     n_words, max_words};
+            gpu_.check(svo_nodes_morph(gpu_.ctx(), &p, &n_words));
+        }
+        return n_words;
+    }
     // the first n_words words of the node buffer compacted in place (svo_nodes_compact): unreachable groups
     // dropped, with `prune` also the groups that hold nothing, the rest in the builder's breadth-first order; returns the
     // new length.  perm_dev (device, n_words u32, or null): perm[new word] = old word.  Throws, with nothing written, for

@@ -115,6 +115,20 @@ class PlaceParams(C.Structure):
     ]
 
 
+class MorphParams(C.Structure):
+    """svo_morph_params: one step of morphology on the tree in the node buffer (include/svo_hip.h)."""
+    _fields_ = [
+        ("op", C.c_uint32),
+        ("conn", C.c_uint32),
+        ("depth", C.c_uint32),
+        ("flags", C.c_uint32),
+        ("colour", C.c_uint32),
+        ("reserved", C.c_uint32),
+        ("n_words", C.c_uint64),
+        ("max_words", C.c_uint64),
+    ]
+
+
 class CompactParams(C.Structure):
     """svo_compact_params: the tree in the node buffer compacted in place (include/svo_hip.h)."""
     _fields_ = [
@@ -335,6 +349,8 @@ DEVICE_SIGNATURES = {
     "svo_combine_timing": (C.c_int, (vp, fp)),
     "svo_nodes_place": (C.c_int, (vp, vp, C.POINTER(PlaceParams), C.POINTER(u64))),
     "svo_place_timing": (C.c_int, (vp, fp)),
+    "svo_nodes_morph": (C.c_int, (vp, C.POINTER(MorphParams), C.POINTER(u64))),
+    "svo_morph_timing": (C.c_int, (vp, fp)),
     "svo_nodes_compact": (C.c_int, (vp, C.POINTER(CompactParams), vp, C.POINTER(u64))),
     "svo_compact_timing": (C.c_int, (vp, fp)),
     "svo_nodes_simplify": (C.c_int, (vp, C.POINTER(SimplifyParams), vp, vp, C.POINTER(u64))),

@@ -6,7 +6,7 @@ import torch
 
 from . import sharding
 from ._device import device_u32, voxel_list, wait_for_torch
-from ._lib import BuildParams, CombineParams, CompactParams, ComponentsParams, EditParams, ListParams, PlaceParams, RegionParams, SampleParams, SimplifyParams, SitesParams, StampParams, SurfaceMergeParams, SurfaceParams, TopsParams, Uniforms, lib
+from ._lib import BuildParams, CombineParams, CompactParams, ComponentsParams, EditParams, ListParams, MorphParams, PlaceParams, RegionParams, SampleParams, SimplifyParams, SitesParams, StampParams, SurfaceMergeParams, SurfaceParams, TopsParams, Uniforms, lib
 from .camera import camera_matrices
 
 F_PAUSE_ADAPTIVE, F_SHOW_STEPS, F_SHOW_HITS, F_SHADOWS, F_MISC_BOOL = 1, 2, 4, 8, 16
@@ -21,6 +21,7 @@ TOP_NONE = -1  # what column_tops returns for a column that holds nothing: SVO_T
 # to this many entries they fill room for the bound in one call and return its first part, without the count query
 ONE_CALL_ENTRIES = 1 << 20
 COMBINE_OPS = ("over", "under", "paint", "carve", "keep", "replace")  # combine_nodes: SVO_COMBINE_OVER .. SVO_COMBINE_REPLACE
+MORPH_OPS = ("grow", "shrink", "close", "open")  # morph_nodes: SVO_MORPH_GROW, SVO_MORPH_SHRINK and their two compositions
 
 
 class Render:
@@ -274,6 +275,63 @@ class Render:
         self.gpu.sync()  # (the source may be released by the caller)
         self.node_length = out.value
         return out.value
+
+    def _morph_step(self, op, conn, colour, depth, open_boundary, max_words):
+        """one svo_nodes_morph call"""
+        p = MorphParams()
+        p.op = op
+        p.conn = min(max(0, int(conn)), 0xFFFFFFFF)
+        p.depth = max(0, depth)
+        p.flags = 1 if open_boundary else 0
+        p.colour = colour
+        p.n_words = int(self.node_length)
+        p.max_words = int(max_words or 0)
+        out = C.c_uint64()
+        self.gpu.check(lib().svo_nodes_morph(self.gpu._h, C.byref(p), C.byref(out)))
+        self.gpu.sync()
+        self.node_length = out.value
+        return out.value
+
+    def morph_nodes(self, op, steps=1, conn=26, colour=None, depth=None, open_boundary=False, max_words=None):
+        """Mathematical morphology on the tree that is in the node buffer, in place (svo_nodes_morph).  op, a
+        name of MORPH_OPS: "grow" adds to the voxels every empty cell that has a voxel among its `conn` (6, 18 or 26)
+        neighbours, "shrink" empties every voxel that has an empty cell among them; `steps` such steps are the cube (26),
+        the 18-cell shape or the octahedron (6) of radius `steps`.  "close" is `steps` grows and then `steps` shrinks (it
+        fills holes and gaps narrower than the shape), "open" the reverse (it removes bridges and specks).  A new cell gets
+        `colour`; None or 0: the value of its first neighbour in the order faces, edges, corners, each ascending in (dx,
+        dy, dz).  The grid's outside never changes a cell, unless open_boundary lets a shrink take it for empty.  Coarse
+        leaves stay coarse away from the surface; equal siblings that a split leaves behind are simplify_nodes' to merge,
+        and as every step walks the whole tree a merged tree is the cheap input.  Where the tree is finer than `depth`,
+        SvoError is raised by the step that meets it and the steps before it stay.  depth=None: the depth declared for
+        this tree.  Returns the new length (node_length)."""
+        if op not in MORPH_OPS:
+            raise ValueError(f"op must be one of {', '.join(MORPH_OPS)} (got {op!r})")
+        steps = int(steps)
+        if steps < 0:
+            raise ValueError(f"steps must not be negative (got {steps})")
+        depth = int(self.gpu.tree_depth if depth is None else depth)
+        self.gpu.declare_depth(depth)
+        colour = 0 if colour is None else int(colour) & 0xFFFFFF
+        order = {"grow": (0,), "shrink": (1,), "close": (0, 1), "open": (1, 0)}[op]
+        for step_op in order:
+            for _ in range(steps):
+                self._morph_step(step_op, conn, 0 if step_op else colour, depth, open_boundary, max_words)
+        return int(self.node_length)
+
+    def shell_nodes(self, thickness=1, conn=6, depth=None, closed_boundary=False, max_words=None):
+        """Hollow the tree that is in the node buffer to a shell, in place and on the device: every voxel that
+        `thickness` shrinks under `conn` would keep is emptied, so `thickness` layers of the solid stay.  The grid's
+        boundary exposes (closed_boundary: it covers), as in list_surface: with conn=6 and thickness=1 the voxels left are
+        exactly the cells of the leaves that list_surface reports.  Made of a snapshot (simplify_nodes out of place), the
+        shrinks, a second snapshot, and two combine_nodes: the first snapshot back by "replace", the second carved out of
+        it.  Raises as those do; an error leaves the shrunk tree of the steps that ran.  Returns the new length
+        (node_length); simplify_nodes merges the interior that the carve emptied."""
+        depth = int(self.gpu.tree_depth if depth is None else depth)
+        whole = self.simplify_nodes(out_of_place=True)
+        self.morph_nodes("shrink", steps=thickness, conn=conn, depth=depth, open_boundary=not closed_boundary, max_words=max_words)
+        core = self.simplify_nodes(out_of_place=True)
+        self.combine_nodes(whole, "replace", depth=depth, max_words=max_words)
+        return self.combine_nodes(core, "carve", depth=depth, max_words=max_words)
 
     def compact_nodes(self, prune=True, with_perm=False):
         """Compact the first node_length words of the node buffer in place (svo_nodes_compact): unreachable
