@@ -691,6 +691,85 @@ int svo_nodes_morph(svo_ctx *ctx, const svo_morph_params *p, uint64_t *n_words_o
 #define SVO_MORPH_TIMES 5   /* plan (with its per-level read-backs), status, fill, write, host wall */
 int svo_morph_timing(svo_ctx *ctx, float ms_out[SVO_MORPH_TIMES]);
 
+/* ---- a tree in the node buffer shaped by a height map: terrain raised, lowered and layered ----
+ * Edits the first n_words words of the node buffer in place, top-down, touching only the tree along the ground's surface.
+ * heights_dev (DEVICE, size_xz[0] * size_xz[1] u32, ONLY READ): heights_dev[i * size_xz[1] + k] is the height of the column
+ * (origin_xz[0] + i, origin_xz[1] + k) of the `depth` grid, z fastest as in svo_nodes_column_tops and y up.  h = min(height,
+ * 2^depth) is the column's number of ground cells: the cells y < h are below the ground, h == 0 is a column with none; a height
+ * above the grid, 0xFFFFFFFF included, is clamped and no error.  With T_k = thickness_0 + .. + thickness_k (64 bits) the call
+ * means this per cell c = (x, y, z) of the grid, v being what svo_nodes_sample returns at c:
+ *     the column (x, z) outside the rectangle:  v stays
+ *     y <  h and (v == 0 ? mode_below & SVO_REGION_EMPTY : mode_below & SVO_REGION_VOXELS):  v = layers[k].colour & 0xFFFFFF, k the
+ *               first layer with h - 1 - y < T_k, or n_layers - 1 without one: the last layer's thickness is ignored, it reaches
+ *               down to y = 0; a thickness of 0 elsewhere is a band that holds no cell; a layer of colour 0 is empty
+ *     y >= h and (v == 0 ? mode_above & SVO_REGION_EMPTY : mode_above & SVO_REGION_VOXELS):  v = colour_above & 0xFFFFFF
+ * and afterwards the tree samples to that v in every cell.  A mode of 0 leaves its side of the ground alone.
+ * The words are deterministic, the same bytes on every run (no atomics: the order is the contract), by this rule.  The frontier,
+ * its order and the appends are svo_nodes_edit_region's.  A word of level l with cell q covers the cube of S = 2^s cells, s =
+ * depth - l, at (x0, y0, z0) = q << s.  `meets`: the cube's xz footprint meets the rectangle; `inside`: it lies within it; hmin,
+ * hmax: the extremes of h over the footprint's columns WITHIN THE RECTANGLE; band(d): the layer index above.  Then
+ *     k_lo = band(max(hmin - y0 - S, 0)),  k_hi = band(max(hmax - 1 - y0, 0))
+ *     has_above = meets && y0 + S > hmin,  has_below = meets && y0 < hmax
+ *     all_above = meets && y0 >= hmax,     all_below = meets && y0 + S <= hmin && k_lo == k_hi
+ * The word's candidates are (mode_above, colour_above) when has_above && mode_above, and (mode_below, layers[k].colour) for k_lo
+ * <= k <= k_hi when has_below && mode_below.  For one word:
+ *     no candidate:  the word and everything below it keep all 32 bits
+ *     UNIFORM, `inside` and (all_above or all_below), the one candidate (mode, colour):
+ *         a leaf takes the colour when the mode applies to its value, and is written only when that changes it, counter 0
+ *         an interior word COLLAPSES to the leaf word of the colour when the mode is SVO_REGION_SET (its subtree is cut off, for
+ *         svo_nodes_compact to drop); otherwise it is opened
+ *     otherwise (mixed):
+ *         an interior word is opened
+ *         a leaf of value v0 is SPLIT iff some candidate's mode applies to v0 with a colour other than v0: a new group of eight
+ *         leaf words OF v0, counter 0, is made, THE COLOUR CARRIED DOWN, the word becomes the pointer to it, and the eight virtual
+ *         children join the next frontier; otherwise it is untouched
+ * At l == depth a footprint is one column, so nothing is mixed; an interior word that would be opened there is the REFUSAL:
+ * SVO_ERR_STATE, nothing written, svo_last_error names the cell.  It occurs only under the modes 1 and 2: SVO_REGION_SET
+ * collapses the word.  The test by the extremes is conservative: a leaf may be split whose children all end unchanged.
+ * New groups are appended by level and within a level in frontier order: the g-th split gets the group n_words + 8 g, and
+ * *n_words_out = n_words + 8 * splits.  Nothing at or behind *n_words_out is touched.  A second identical call on the result
+ * writes nothing and appends nothing.  Merging equal siblings (svo_nodes_simplify does) and reusing free groups are not done.
+ * Every error is decided before any write; of several causes the first in this order is reported.  SVO_ERR_ARG: NULL p or
+ * n_words_out, NULL heights_dev unless a size is 0 or both modes are 0; reserved != 0; depth outside 1..21; a mode above 3;
+ * n_layers > SVO_HEIGHTMAP_MAX_LAYERS, or 0 with a mode_below; origin + size > 2^depth on an axis; 2^31 columns or more.
+ * SVO_ERR_STATE: no node buffer; a device adaptive state attached to the context.  SVO_ERR_ARG: n_words not a positive multiple of
+ * 8 or above the capacity.  SVO_ERR_STATE: the "malformed tree: ..." causes with svo_nodes_compact's wording, on the words that
+ * the call opens; the refusal above.  SVO_ERR_CAP when the exact new length exceeds max_words, the capacity or 2^27.  A size of 0
+ * or two modes of 0 succeed, return n_words and enqueue nothing.
+ * Runs on the ctx stream: the min/max pyramid below, then the levels; blocks once per level and once more for the status, so
+ * heights_dev may be freed on return.  The fill and the writes are enqueued, ordered and recorded like svo_nodes_write. */
+#define SVO_HEIGHTMAP_MAX_LAYERS 8u
+typedef struct svo_heightmap_layer {   /* HOST memory */
+    uint32_t thickness;  /* cells, counted down from the ground's top cell; the last layer's is ignored */
+    uint32_t colour;     /* 0x00RRGGBB, the low 24 bits count; 0 = empty */
+} svo_heightmap_layer;
+typedef struct svo_heightmap_params {
+    uint32_t depth;            /* 1..21: the grid the columns stand on */
+    uint32_t n_layers;         /* 0..8; at least 1 when mode_below != 0 */
+    uint64_t n_words;          /* the tree's current length: a multiple of 8, at least 8 */
+    uint64_t max_words;        /* 0 = the node buffer's capacity; never above SVO_VOXEL_OFFSET */
+    uint32_t origin_xz[2];     /* the map's rectangle of columns: its first column ... */
+    uint32_t size_xz[2];       /* ... and its size; origin + size <= 2^depth */
+    uint32_t mode_below;       /* 0 (leave alone) or SVO_REGION_EMPTY / _VOXELS / _SET */
+    uint32_t mode_above;       /* the same for the cells at and above the height */
+    uint32_t colour_above;     /* low 24 bits; 0 = carve what stands above the ground */
+    uint32_t reserved;         /* 0 */
+    svo_heightmap_layer layers[SVO_HEIGHTMAP_MAX_LAYERS];
+} svo_heightmap_params;
+int svo_nodes_edit_heightmap(svo_ctx *ctx, const svo_heightmap_params *p, const uint32_t *heights_dev, uint64_t *n_words_out);
+/* The min/max pyramid that the edit walks by, for callers that cull or pick a level of detail by it: level s (1..depth) has one
+ * entry per octree-aligned tile (tx, tz) of 2^s x 2^s columns with origin >> s <= t <= (origin + size - 1) >> s on each axis --
+ * aligned in the SCENE's coordinates, not the map's -- holding the minimum and the maximum of the clamped heights of the
+ * rectangle's columns in the tile.  minmax_out_dev (DEVICE, two u32 per entry) receives level s as (min, max) pairs, tz fastest.
+ * Of p only depth, origin_xz and size_xz matter, the rest is checked as above.  SVO_ERR_ARG as above, and for s outside 1..depth
+ * and a NULL minmax_out_dev.  Enqueued on the ctx stream; does not block.  A size of 0 succeeds and enqueues nothing. */
+int svo_heightmap_minmax(svo_ctx *ctx, const svo_heightmap_params *p, const uint32_t *heights_dev, uint32_t s, uint32_t *minmax_out_dev);
+/* Times (ms) of the last height-map edit: [0] the pyramid, [1] plan (with its per-level read-backs), [2] status, [3] fill, [4]
+ * write (device events; waits for the write), [5] host wall time of the call.  All 0 after a call with nothing to edit; a
+ * refused call leaves the times of the last one that ran. */
+#define SVO_HEIGHTMAP_TIMES 6   /* pyramid, plan, status, fill, write, host wall */
+int svo_heightmap_timing(svo_ctx *ctx, float ms_out[SVO_HEIGHTMAP_TIMES]);
+
 /* ---- the tree in the node buffer compacted in place ----
  * Reads the first n_words words of the node buffer as a tree rooted at group 0.  E = SVO_VOXEL_OFFSET << 4 is the empty
  * word; a word is interior when word >> 4 < SVO_VOXEL_OFFSET.

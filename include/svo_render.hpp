@@ -359,6 +359,27 @@ class Render {  // render.rs:3-285
         }
         return n_words;
     }
+    // the first n_words words of the node buffer shaped by the height map heights_dev (device, size_xz[0] * size_xz[1] u32, z
+    // fastest, only read) over the columns from origin_xz on, in place (svo_nodes_edit_heightmap): the cells
+    // below a column's height that mode_below names take their layer's colour, the cells at and above it that mode_above
+    // names take colour_above (modes: 0 leaves the side alone, SVO_REGION_EMPTY, _VOXELS, _SET).  Coarse leaves stay coarse
+    // away from the ground's surface, a split leaf keeps its colour; returns the new length.  Throws, with nothing written,
+    // where the tree is finer than depth under a mode that does not replace it.
+    uint64_t edit_heightmap(uint64_t n_words, const uint32_t *heights_dev, const uint32_t origin_xz[2], const uint32_t size_xz[2], uint32_t depth,
+                            const svo_heightmap_layer *layers, uint32_t n_layers, uint32_t mode_below = SVO_REGION_SET, uint32_t mode_above = 0,
+                            uint32_t colour_above = 0, uint64_t max_words = 0) {
+        if (depth > declared_depth_) {
+            gpu_.set_option(SVO_OPT_TREE_DEPTH, depth);
+            declared_depth_ = depth;
+        }
+        svo_heightmap_params p{depth, n_layers, n_words, max_words, {origin_xz[0], origin_xz[1]}, {size_xz[0], size_xz[1]}, mode_below, mode_above,
+                               colour_above, 0u, {}};
+        for (uint32_t k = 0; k < n_layers && k < SVO_HEIGHTMAP_MAX_LAYERS; k++) p.layers[k] = layers[k];
+        uint64_t new_words = 0;
+        gpu_.check(svo_nodes_edit_heightmap(gpu_.ctx(), &p, heights_dev, &new_words));
+        gpu_.poll_wait();
+        return new_words;
+    }
     // the first n_words words of the node buffer compacted in place (svo_nodes_compact): unreachable groups
     // dropped, with `prune` also the groups that hold nothing, the rest in the builder's breadth-first order; returns the
     // new length.  perm_dev (device, n_words u32, or null): perm[new word] = old word.  Throws, with nothing written, for

@@ -27,7 +27,7 @@ from .cpu_octree import CHUNK_OFFSET, CpuOctree
 from .camera import Character, Settings, camera_matrices
 from .gpu import Gpu
 from .render import Render, HIT_DTYPE, F_PAUSE_ADAPTIVE, F_SHOW_STEPS, F_SHOW_HITS, F_SHADOWS, F_MISC_BOOL
-from .render import SAMPLE_FINER, SAMPLE_OUTSIDE, SAMPLE_BROKEN, TOP_NONE, MORPH_OPS
+from .render import SAMPLE_FINER, SAMPLE_OUTSIDE, SAMPLE_BROKEN, TOP_NONE, MORPH_OPS, HEIGHTMAP_MODES
 from .structure import Structure, load_structure
 from .compute import Compute
 from .world import World
@@ -42,4 +42,4 @@ from . import sharding
 from . import adaptive
 
 __all__ = ["Gpu", "Render", "Compute", "Octree", "CpuOctree", "Voxel", "World", "Procedural", "Uniforms", "Character", "Settings",
-           "SvoError", "SAMPLE_FINER", "SAMPLE_OUTSIDE", "SAMPLE_BROKEN", "TOP_NONE", "MORPH_OPS", "Structure", "load_structure", "VOXEL_OFFSET", "CHUNK_OFFSET", "HIT_DTYPE", "create_node", "camera_matrices", "scenes", "mesh", "region", "orientation", "structure", "sharding", "adaptive", "procedural"]
+           "SvoError", "SAMPLE_FINER", "SAMPLE_OUTSIDE", "SAMPLE_BROKEN", "TOP_NONE", "MORPH_OPS", "HEIGHTMAP_MODES", "Structure", "load_structure", "VOXEL_OFFSET", "CHUNK_OFFSET", "HIT_DTYPE", "create_node", "camera_matrices", "scenes", "mesh", "region", "orientation", "structure", "sharding", "adaptive", "procedural"]

@@ -129,6 +129,31 @@ class MorphParams(C.Structure):
     ]
 
 
+class HeightmapLayer(C.Structure):
+    """svo_heightmap_layer: one band of ground below a height map's surface (include/svo_hip.h)."""
+    _fields_ = [
+        ("thickness", C.c_uint32),
+        ("colour", C.c_uint32),
+    ]
+
+
+class HeightmapParams(C.Structure):
+    """svo_heightmap_params: the tree in the node buffer shaped by a height map (include/svo_hip.h)."""
+    _fields_ = [
+        ("depth", C.c_uint32),
+        ("n_layers", C.c_uint32),
+        ("n_words", C.c_uint64),
+        ("max_words", C.c_uint64),
+        ("origin_xz", C.c_uint32 * 2),
+        ("size_xz", C.c_uint32 * 2),
+        ("mode_below", C.c_uint32),
+        ("mode_above", C.c_uint32),
+        ("colour_above", C.c_uint32),
+        ("reserved", C.c_uint32),
+        ("layers", HeightmapLayer * 8),
+    ]
+
+
 class CompactParams(C.Structure):
     """svo_compact_params: the tree in the node buffer compacted in place (include/svo_hip.h)."""
     _fields_ = [
@@ -351,6 +376,9 @@ DEVICE_SIGNATURES = {
     "svo_place_timing": (C.c_int, (vp, fp)),
     "svo_nodes_morph": (C.c_int, (vp, C.POINTER(MorphParams), C.POINTER(u64))),
     "svo_morph_timing": (C.c_int, (vp, fp)),
+    "svo_nodes_edit_heightmap": (C.c_int, (vp, C.POINTER(HeightmapParams), vp, C.POINTER(u64))),
+    "svo_heightmap_minmax": (C.c_int, (vp, C.POINTER(HeightmapParams), vp, u32, vp)),
+    "svo_heightmap_timing": (C.c_int, (vp, fp)),
     "svo_nodes_compact": (C.c_int, (vp, C.POINTER(CompactParams), vp, C.POINTER(u64))),
     "svo_compact_timing": (C.c_int, (vp, fp)),
     "svo_nodes_simplify": (C.c_int, (vp, C.POINTER(SimplifyParams), vp, vp, C.POINTER(u64))),

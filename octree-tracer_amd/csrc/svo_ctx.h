@@ -1,6 +1,6 @@
 // svo_ctx.h -- the device context behind the opaque `svo_ctx` of include/svo_hip.h, and the host helpers of the files that
 // use it: svo_abi.cpp (trace / scan dispatch), svo_comm.cpp (RCCL frame gather) and the GPU tree passes (svo_proc.hip,
-// svo_build.hip, svo_edit.hip, svo_region.hip, svo_combine.hip, svo_place.hip, svo_morph.hip, svo_compact.hip, svo_simplify.hip, svo_list.hip, svo_sample.hip, svo_voxelize.hip, svo_solid.hip,
+// svo_build.hip, svo_edit.hip, svo_region.hip, svo_combine.hip, svo_place.hip, svo_morph.hip, svo_heightmap.hip, svo_compact.hip, svo_simplify.hip, svo_list.hip, svo_sample.hip, svo_voxelize.hip, svo_solid.hip,
 // svo_structure.hip, svo_surface.hip, svo_surface_merge.hip, svo_components.hip, svo_adapt.hip).  One rule of ownership for the context, the node store and every
 // pass's state: a member owns what it holds, as svo_dev / svo_pinned (an allocation and its size), svo_events (events) or
 // svo_stream (a stream).  The passes
@@ -149,6 +149,7 @@ struct svo_region_state;
 struct svo_combine_state;
 struct svo_place_state;
 struct svo_morph_state;
+struct svo_heightmap_state;
 struct svo_list_state;
 struct svo_sample_state;
 struct svo_voxelize_state;
@@ -267,6 +268,7 @@ struct svo_ctx {
     svo_workspace<svo_combine_state> combine{nullptr, nullptr};  // the workspace of two trees combined (svo_combine.hip)
     svo_workspace<svo_place_state> place{nullptr, nullptr};  // the workspace of a tree placed at an offset and orientation (svo_place.hip)
     svo_workspace<svo_morph_state> morph{nullptr, nullptr};  // the workspace of a morphology step (svo_morph.hip)
+    svo_workspace<svo_heightmap_state> heightmap{nullptr, nullptr};  // the workspace of a height-map edit and its pyramid (svo_heightmap.hip)
     svo_workspace<svo_list_state> list{nullptr, nullptr};  // voxel listing's workspace (svo_list.hip)
     svo_workspace<svo_sample_state> sample{nullptr, nullptr};  // sampling's events and times (svo_sample.hip)
     svo_workspace<svo_voxelize_state> voxelize{nullptr, nullptr};  // mesh voxeliser's workspace (svo_voxelize.hip)

@@ -99,6 +99,11 @@ class Gpu:
         events), host wall time of the call (svo_morph_timing)"""
         return self._timing(lib().svo_morph_timing, 5)
 
+    def heightmap_timing(self):
+        """ms of the last Render.edit_heightmap: the min/max pyramid, plan (with its per-level read-backs), status, fill,
+        write (device events), host wall time of the call (svo_heightmap_timing)"""
+        return self._timing(lib().svo_heightmap_timing, 6)
+
     def compact_timing(self):
         """ms of the last Render.compact_nodes: discover, check, prune, emit, copy back (device events), host wall time
         of the call (svo_compact_timing)"""

@@ -6,7 +6,7 @@ import torch
 
 from . import sharding
 from ._device import device_u32, voxel_list, wait_for_torch
-from ._lib import BuildParams, CombineParams, CompactParams, ComponentsParams, EditParams, ListParams, MorphParams, PlaceParams, RegionParams, SampleParams, SimplifyParams, SitesParams, StampParams, SurfaceMergeParams, SurfaceParams, TopsParams, Uniforms, lib
+from ._lib import BuildParams, CombineParams, CompactParams, ComponentsParams, EditParams, HeightmapParams, ListParams, MorphParams, PlaceParams, RegionParams, SampleParams, SimplifyParams, SitesParams, StampParams, SurfaceMergeParams, SurfaceParams, TopsParams, Uniforms, lib
 from .camera import camera_matrices
 
 F_PAUSE_ADAPTIVE, F_SHOW_STEPS, F_SHOW_HITS, F_SHADOWS, F_MISC_BOOL = 1, 2, 4, 8, 16
@@ -22,6 +22,13 @@ TOP_NONE = -1  # what column_tops returns for a column that holds nothing: SVO_T
 ONE_CALL_ENTRIES = 1 << 20
 COMBINE_OPS = ("over", "under", "paint", "carve", "keep", "replace")  # combine_nodes: SVO_COMBINE_OVER .. SVO_COMBINE_REPLACE
 MORPH_OPS = ("grow", "shrink", "close", "open")  # morph_nodes: SVO_MORPH_GROW, SVO_MORPH_SHRINK and their two compositions
+HEIGHTMAP_MODES = (None, "empty", "voxels", "set")  # edit_heightmap's below / above: 0, SVO_REGION_EMPTY, _VOXELS, _SET
+
+
+def _heightmap_mode(mode, which):
+    if mode not in HEIGHTMAP_MODES:
+        raise ValueError(f"{which} must be None, 'empty', 'voxels' or 'set' (got {mode!r})")
+    return HEIGHTMAP_MODES.index(mode)
 
 
 class Render:
@@ -186,6 +193,92 @@ class Render:
         self.gpu.sync()
         self.node_length = out.value
         return out.value
+
+    def _heightmap(self, heights, layers, origin_xz, depth):
+        """the height map and its rectangle as the library takes them: -> (params without modes and lengths, the int32
+        device tensor [sx, sz] of u32 bit patterns, its address or None)"""
+        depth = int(self.gpu.tree_depth if depth is None else depth)
+        if not isinstance(heights, torch.Tensor):
+            heights = np.ascontiguousarray(heights)
+            if heights.dtype.kind == "u":  # (torch has no arithmetic for the wide unsigned types)
+                heights = np.minimum(heights, 0xFFFFFFFF).astype(np.int64)
+        t = torch.as_tensor(heights)
+        if t.dtype.is_floating_point or t.dtype.is_complex or t.dtype == torch.bool:
+            raise TypeError(f"heights: integer input expected, got {t.dtype}")
+        if t.dim() != 2:
+            raise ValueError(f"heights must be (size_x, size_z), got {tuple(t.shape)}")
+        t = t.to(self.gpu.torch_device)
+        if t.dtype != torch.int32:  # a negative height is 0, one above 2^32 - 1 is that: the library clamps to the grid
+            t = t.to(torch.int64).clamp(0, 0xFFFFFFFF)
+            t = torch.where(t >= 1 << 31, t - (1 << 32), t)
+        t = t.to(torch.int32).contiguous()
+        o = [int(v) for v in origin_xz]
+        if len(o) != 2 or min(o) < 0 or max(o) >= 1 << 32:
+            raise ValueError(f"origin_xz must be 2 values in [0, 2^32), got {o}")
+        layers = [(int(th), int(colour)) for th, colour in layers]
+        if len(layers) > len(HeightmapParams().layers):
+            raise ValueError(f"{len(layers)} layers, more than {len(HeightmapParams().layers)}")
+        if any(th < 0 or th >= 1 << 32 for th, _ in layers):
+            raise ValueError(f"a layer's thickness must be in [0, 2^32), got {[th for th, _ in layers]}")
+        p = HeightmapParams()
+        p.depth = max(0, depth)
+        p.n_layers = len(layers)
+        p.origin_xz[:] = o
+        p.size_xz[:] = list(t.shape)
+        for k, (th, colour) in enumerate(layers):
+            p.layers[k].thickness, p.layers[k].colour = th, colour & 0xFFFFFF
+        return p, t, (t.data_ptr() if t.numel() else None)
+
+    def edit_heightmap(self, heights, layers=((0, 0xFFFFFF),), origin_xz=(0, 0), depth=None, below="set", above=None, above_colour=0,
+                       max_words=None):
+        """Shape the tree that is in the node buffer by a height map, in place (svo_nodes_edit_heightmap):
+        raise, lower and layer terrain.  heights: a device int32 tensor [size_x, size_z] (u32 bit patterns; or numpy or any
+        integer tensor, copied there, negative values taken as 0), the number of ground cells of the column (origin_xz[0] +
+        i, origin_xz[1] + k) of the `depth` grid, y up; a height above the grid is clamped.  layers: up to 8 (thickness,
+        colour) from the ground's top cell down; the last one's thickness is ignored, it reaches down to y = 0; a colour of
+        0 is empty.  below / above: what the cells under the ground / at and above it must be to be set, None (leave that
+        side alone), "empty", "voxels" or "set" (both); the cells under the ground get their layer's colour, the others
+        above_colour (0 carves).  Coarse leaves stay coarse away from the ground's surface: a cube wholly below, within one
+        layer, or wholly above becomes or stays one leaf, a leaf on the surface is split and keeps its colour in the
+        children; equal siblings that a split leaves behind are simplify_nodes' to merge.  Where the tree is finer than
+        `depth` under a mode that does not replace it, SvoError is raised and nothing is written.  depth=None: the depth
+        declared for this tree.  Returns the new length (node_length)."""
+        p, t, ptr = self._heightmap(heights, layers, origin_xz, depth)
+        self.gpu.declare_depth(p.depth)
+        p.mode_below, p.mode_above = _heightmap_mode(below, "below"), _heightmap_mode(above, "above")
+        p.colour_above = int(above_colour) & 0xFFFFFF
+        p.n_words = int(self.node_length)
+        p.max_words = int(max_words or 0)
+        out = C.c_uint64()
+        wait_for_torch(self.gpu)
+        self.gpu.check(lib().svo_nodes_edit_heightmap(self.gpu._h, C.byref(p), ptr, C.byref(out)))
+        self.gpu.sync()  # (the map may be released by the caller)
+        self.node_length = out.value
+        return out.value
+
+    def height_minmax(self, heights, s, origin_xz=(0, 0), depth=None):
+        """Level s (1..depth) of the min/max pyramid that edit_heightmap walks by (svo_heightmap_minmax): an
+        int32 device tensor [nx, nz, 2] with one (min, max) pair of the clamped heights per octree-aligned tile of 2^s x
+        2^s columns that meets the map's rectangle, tile (origin >> s) + (i, k) at [i, k]; the columns outside the
+        rectangle do not count.  heights, origin_xz and depth as in edit_heightmap."""
+        p, t, ptr = self._heightmap(heights, (), origin_xz, depth)
+        s = int(s)
+        fits = 1 <= s <= p.depth <= 21 and t.numel() and all(a + b <= 1 << p.depth for a, b in zip(p.origin_xz, p.size_xz))
+        shape = [((a + b - 1) >> s) - (a >> s) + 1 for a, b in zip(p.origin_xz, p.size_xz)] if fits else [0, 0]
+        out = torch.empty(shape + [2], dtype=torch.int32, device=self.gpu.torch_device)
+        room = out if out.numel() else torch.empty(2, dtype=torch.int32, device=self.gpu.torch_device)  # (nothing is written to it)
+        wait_for_torch(self.gpu)
+        self.gpu.check(lib().svo_heightmap_minmax(self.gpu._h, C.byref(p), ptr, min(max(s, 0), 0xFFFFFFFF), room.data_ptr()))
+        self.gpu.sync()  # (the map may be released by the caller)
+        return out
+
+    @classmethod
+    def from_heightmap(cls, gpu, size, heights, depth, layers=((0, 0xFFFFFF),), capacity=None):
+        """A Render whose tree is the solid terrain of a height map over the whole `depth` grid's floor, made on the GPU from
+        the empty root group (edit_heightmap): its coarse leaves never existed as cells."""
+        self = cls(gpu, size, np.full(8, EMPTY_WORD, dtype=np.uint32), capacity)
+        self.edit_heightmap(heights, layers, (0, 0), depth)
+        return self
 
     def _source_tree(self, source):
         """a second device tree that a pass only reads, in the three forms combine_nodes and place_nodes take: -> (address,
