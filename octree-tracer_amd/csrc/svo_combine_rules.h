@@ -1,14 +1,28 @@
 // svo_combine_rules.h -- the rule of two trees combined, as tables over (op, the scene's value empty or not, the source's
 // value empty or not): what svo_combine.hip and svo_place.hip decide a word by, stated once.
-// include/svo_hip.h has the rule in words.  In an anonymous namespace: a copy per file.
+// include/svo_hip.h has the rule in words.  Then what the two passes add to the frontier walk (svo_frontier.h) alike: the
+// flags and the words of a refusal, and the status words and refusals of a malformed source.  In an anonymous namespace: a
+// copy per file.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include <string>
 
+#include "svo_frontier.h"
 #include "svo_hip.h"  // (SVO_COMBINE_OVER .. SVO_COMBINE_REPLACE)
 
 namespace {
+
+const char *const kOpNames[] = {"over", "under", "paint", "carve", "keep", "replace"};
+enum Src : uint32_t { kOut, kLeaf, kNode };  // what the source has for a frontier word's cube
+// a word's flags above the walk's (svo_frontier.h): at level `depth`, where a word is neither opened nor split, which tree
+// is finer under the refused word; and the same in words
+constexpr uint32_t kSceneFiner = 4u, kSourceFiner = 8u;
+inline const char *finer_trees(uint32_t cd) {
+    return (cd & kSceneFiner) && (cd & kSourceFiner) ? "the scene and the source are interior nodes" :
+           (cd & kSceneFiner) ? "the scene is an interior node" : "the source is an interior node";
+}
 
 // f(a, b) per cell
 __host__ __device__ inline uint32_t combine_value(uint32_t op, uint32_t a, uint32_t b) {
@@ -40,5 +54,19 @@ __host__ __device__ inline bool leaf_stays(uint32_t op, bool a_set) {
     constexpr uint32_t table = 1u << (2 * SVO_COMBINE_UNDER + 1) | 1u << (2 * SVO_COMBINE_PAINT) | 1u << (2 * SVO_COMBINE_CARVE) | 1u << (2 * SVO_COMBINE_KEEP);
     return table >> (2u * op + uint32_t(a_set)) & 1u;
 }
+
+// The walk's hooks of a pass with a source tree: a followed source pointer is checked by the pass's emit kernel as the
+// discovery checks a scene's, into two status words of the pass's own, which are tested behind the walk's.
+enum { kStSrcAlign = kStWords, kStSrcRange };
+struct SourcePass : FrontierPass {
+    static constexpr bool kWantsCode = true;
+    uint64_t src_words = 0;
+    int check(svo_ctx *ctx, const uint32_t *st, uint32_t level) {
+        const std::string where = "malformed source: an interior pointer at level " + std::to_string(level);
+        if (st[kStSrcAlign]) return svo_fail(ctx, SVO_ERR_STATE, where + " is not a multiple of 8");
+        if (st[kStSrcRange]) return svo_fail(ctx, SVO_ERR_STATE, where + " leaves the first src_words = " + std::to_string(src_words) + " words");
+        return SVO_OK;
+    }
+};
 
 }  // namespace

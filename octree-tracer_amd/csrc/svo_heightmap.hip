@@ -1,9 +1,9 @@
 // svo_heightmap.hip -- the tree in the node buffer shaped by a height map: per column of a rectangle the
 // cells below the ground are filled in layers and the cells above it carved, filled or painted, top-down, so that only
 // the words along the ground's surface are looked at.  include/svo_hip.h has the rule for one word; this file applies it
-// level by level with the frontier, the scans, the check and the commit of the shape edit (svo_region.hip,
-// svo_frontier.h).  What differs is the plan: where the shape edit classifies a cube against every shape, this one asks
-// for the lowest and the highest ground under the cube's footprint, one lookup in a min/max pyramid over the map.
+// level by level with the walk of svo_frontier.h.  Its own is the plan: where the shape edit (svo_region.hip)
+// classifies a cube against every shape, this one asks for the lowest and the highest ground under the cube's footprint, one
+// lookup in a min/max pyramid over the map.
 //
 //   pyramid   level s >= 1 holds one (min, max) pair per octree-aligned tile of 2^s x 2^s columns that meets the map's
 //             rectangle, tz fastest; level 0 is the map itself, clamped where it is read.  One launch makes up to six
@@ -13,9 +13,7 @@
 //             scene's coordinates; what lies outside the rectangle contributes the identity (min ~0, max 0).  The next
 //             launch starts from the sixth level.  Every height is read once; no atomics
 //   plan      per level, reading only, one lane per frontier word: the word's cube against the extremes of its footprint
-//             (heightmap_plan_kernel), then the two scans, the emit, the mark and the check as in the shape edit
-//   status    the first refused word of level `depth` in frontier order, read back
-//   commit    region_fill_kernel, region_write_kernel (svo_frontier.h)
+//             (heightmap_plan_kernel)
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -24,16 +22,11 @@
 #include <vector>
 
 #include "svo_ctx.h"
-#include "svo_frontier.h"  // (kNone, leaf_word, the mark and check kernels, the fill and write kernels, grow_list)
-#include "svo_scan.h"  // (svo_scan_u32, block_min, min_of_blocks_kernel; svo_group.h: kThreads, kEmptyWord, kMaxWords)
+#include "svo_frontier.h"  // (the walk: Entry, PlanOut, emit_head, Walk; kNone, leaf_word, mode_applies)
 
 static_assert(sizeof(svo_heightmap_layer) == 8 && sizeof(svo_heightmap_params) == 120, "the header's layout");
 
 namespace {
-
-constexpr uint32_t kCellBits = 21, kCellMask = (1u << kCellBits) - 1u;  // a record's cell: x << 42 | y << 21 | z
-enum Code : uint32_t { kOpen = 1u, kSplit = 2u };  // kOpen: eight children in the next frontier; kSplit: ... of a new group
-enum Status { kStAlign = SVO_WALK_ALIGN, kStRange = SVO_WALK_RANGE, kStNext = SVO_WALK_NEXT, kStDup = SVO_WALK_DUP, kStSplits, kStBad, kStWords };
 
 constexpr uint32_t kPyrLevels = 6;  // levels per pyramid launch: two in registers, two across lanes, two through LDS
 constexpr uint32_t kPyrTile = 64;   // entries of the input level along each axis of a workgroup's tile
@@ -139,8 +132,6 @@ struct PlanArgs {
     uint32_t colour[SVO_HEIGHTMAP_MAX_LAYERS], T[SVO_HEIGHTMAP_MAX_LAYERS];
 };
 
-__host__ __device__ inline bool mode_applies(uint32_t mode, uint32_t v) { return (v ? mode & SVO_REGION_VOXELS : mode & SVO_REGION_EMPTY) != 0u; }
-
 // the layer of the cell d cells below the ground's top cell: the first k with d < T[k]
 __device__ inline uint32_t band(const PlanArgs &a, uint32_t d) {
     uint32_t k = 0;
@@ -149,37 +140,12 @@ __device__ inline uint32_t band(const PlanArgs &a, uint32_t d) {
     return k;
 }
 
-// What the lane of frontier word i knows of it: where it is, the word as it stands and the word's cell on its level.
-struct Entry {
-    uint32_t at, word, x, y, z;
-};
-__device__ inline Entry frontier_entry(const uint32_t *__restrict__ words, const uint32_t *__restrict__ gbase, const uint64_t *__restrict__ gkey,
-                                       const uint32_t *__restrict__ gvirt, uint32_t i) {
-    const uint32_t g = i >> 3, c = i & 7u, virt = gvirt[g];
-    const uint64_t key = gkey[g];
-    Entry e;
-    e.at = gbase[g] + c;
-    e.word = virt ? virt : words[e.at];  // (a real group's pointer passed the check: below n_words)
-    e.x = (uint32_t(key >> (2 * kCellBits)) & kCellMask) * 2u + (c >> 2);
-    e.y = (uint32_t(key >> kCellBits) & kCellMask) * 2u + ((c >> 1) & 1u);
-    e.z = (uint32_t(key) & kCellMask) * 2u + (c & 1u);
-    return e;
-}
-
-// The rule for the n frontier words of a.level; the outputs are region_plan_kernel's: code[i] = the word's flags, also as
-// the two scans' inputs; list_at[i] = the word's address when something is written there (kNone: nothing), list_word[i] =
-// what (a split's pointer comes from heightmap_emit_kernel), list_fill[i] = the leaf word a split's new group is filled
-// with; bad[block] = the block's first word, in frontier order, that would be opened at level == depth.
-__global__ __launch_bounds__(kThreads) void heightmap_plan_kernel(const uint32_t *__restrict__ words, PlanArgs a, const uint32_t *__restrict__ gbase,
-                                                                  const uint64_t *__restrict__ gkey, const uint32_t *__restrict__ gvirt, uint32_t n,
-                                                                  uint32_t *__restrict__ code, uint32_t *__restrict__ open_scan,
-                                                                  uint32_t *__restrict__ split_scan, uint32_t *__restrict__ list_at,
-                                                                  uint32_t *__restrict__ list_word, uint32_t *__restrict__ list_fill,
-                                                                  uint32_t *__restrict__ bad) {
+// The rule for the frontier words of a.level; a word that would be opened at level == depth is refused.
+__global__ __launch_bounds__(kThreads) void heightmap_plan_kernel(const uint32_t *__restrict__ words, PlanArgs a, Frontier f, PlanOut o) {
     const uint32_t i = blockIdx.x * kThreads + threadIdx.x, s = a.depth - a.level, S = 1u << s;
     uint32_t refused = kNone;
-    if (i < n) {
-        const Entry e = frontier_entry(words, gbase, gkey, gvirt, i);
+    if (i < f.n) {
+        const Entry e = frontier_entry(words, f, i);
         const uint32_t x0 = e.x << s, y0 = e.y << s, z0 = e.z << s;
         const bool leaf = (e.word >> 4) >= SVO_VOXEL_OFFSET;
         // the footprint meets the rectangle iff its tile is one of the level's entries
@@ -228,78 +194,35 @@ __global__ __launch_bounds__(kThreads) void heightmap_plan_kernel(const uint32_t
                 }
             }
         }
-        code[i] = cd;
-        open_scan[i] = cd & kOpen;
-        split_scan[i] = (cd & kSplit) >> 1;
-        list_at[i] = at;
-        list_word[i] = out;
-        list_fill[i] = fill;
+        plan_store(o, i, cd, at, out, fill);
     }
-    const uint32_t first = block_min<kThreads>(refused);
-    if (threadIdx.x == 0) bad[blockIdx.x] = first;
+    plan_refused(o, refused);
 }
 
-// Behind the two scans, as svo_region.hip's region_emit_kernel: the records of the next frontier's groups, in the order of
-// their parents, the pointers of the splits, whose groups start at `first_new` in the order of the scan, and the two
-// totals.  A pointer that is followed is checked as the discovery checks it.
-__global__ __launch_bounds__(kThreads) void heightmap_emit_kernel(const uint32_t *__restrict__ words, const uint32_t *__restrict__ gbase,
-                                                                  const uint64_t *__restrict__ gkey, const uint32_t *__restrict__ gvirt, uint32_t n,
-                                                                  const uint32_t *__restrict__ code, const uint32_t *__restrict__ open_scan,
-                                                                  const uint32_t *__restrict__ split_scan, uint32_t n_words, uint32_t first_new,
-                                                                  uint32_t *__restrict__ list_word, uint32_t *__restrict__ next_base,
-                                                                  uint64_t *__restrict__ next_key, uint32_t *__restrict__ next_virt,
-                                                                  uint32_t *__restrict__ status) {
-    const uint32_t i = blockIdx.x * kThreads + threadIdx.x;
-    if (i >= n) return;
-    const uint32_t cd = code[i], k = open_scan[i];
-    if (i == n - 1) {
-        status[kStNext] = k + (cd & kOpen);
-        status[kStSplits] = split_scan[i] + ((cd & kSplit) >> 1);
-    }
-    if (!(cd & kOpen) || k >= n) return;  // (k < n always: a word opens one group at the most)
-    const Entry e = frontier_entry(words, gbase, gkey, gvirt, i);
-    uint32_t base, virt = 0;
-    if (cd & kSplit) {
-        base = first_new + 8u * split_scan[i];
-        virt = e.word & ~15u;
-        list_word[i] = base << 4;
-    } else {
-        base = e.word >> 4;
-        if (base & 7u) status[kStAlign] = 1u;  // (every writer stores the same value)
-        else if (uint64_t(base) + 8u > n_words) status[kStRange] = 1u;
-    }
-    next_base[k] = base;
-    next_virt[k] = virt;
-    next_key[k] = uint64_t(e.x) << (2 * kCellBits) | uint64_t(e.y) << kCellBits | e.z;
+// Behind the two scans: the records of the next frontier's groups, in the order of their parents.
+__global__ __launch_bounds__(kThreads) void heightmap_emit_kernel(const uint32_t *__restrict__ words, Frontier f, EmitArgs a) {
+    Opened o;
+    if (emit_head(words, f, a, o)) emit_record(a, o);
 }
 
 enum Ev { kEvStart, kEvPyramid, kEvPlan, kEvStatus, kEvFill, kEvEnd, kEvs };
 
 }  // namespace
 
-// Per-context workspace of the height-map edit (svo_ctx::heightmap): the pyramid and its levels, then the shape edit's
-// arrays: two sets of frontier records that the levels take turns in, the per-word arrays of one level, the write list
-// of all levels, and the marks.
+// What the height-map edit keeps per context beside the walk's workspace (svo_ctx::heightmap): the pyramid, its levels and
+// the times.
 struct svo_heightmap_state {
     svo_dev<uint2> pyramid;
     std::vector<PyrLevel> levels;  // of the last pyramid: [0] the map, [s] the level s
-    svo_dev<uint32_t> gbase[2], gvirt[2];
-    svo_dev<uint64_t> gkey[2];
-    svo_dev<uint32_t> code, open_scan, split_scan, bad;
-    svo_dev<uint32_t> list_at, list_word, list_fill;
-    svo_dev<uint32_t> new_of;
-    svo_mirrored<> status;  // kStWords words
     svo_pass_timer<kEvs, SVO_HEIGHTMAP_TIMES> timer;
 
     int create(svo_ctx *ctx) {
         HIP_TRY(ctx, timer.create());
-        return status.alloc(ctx, kStWords);
+        return SVO_OK;
     }
 };
 
 namespace {
-
-int malformed(svo_ctx *ctx, const std::string &why) { return svo_fail(ctx, SVO_ERR_STATE, "malformed tree: " + why); }
 
 // the argument errors of both entry points, in the header's order
 int check_params(svo_ctx *ctx, const svo_heightmap_params *p) {
@@ -378,12 +301,19 @@ int svo_nodes_edit_heightmap(svo_ctx *ctx, const svo_heightmap_params *p, const 
     }
     const double t0 = svo_now_ms();
     if ((rc = s->timer.begin(ctx))) return rc;
-    // no pointer reaches a group behind 2^27, so the words behind it hold no reachable group
-    const uint32_t depth = p->depth, n_words = (uint32_t)std::min<uint64_t>(p->n_words, kMaxWords), cap = n_words / 8;
-    if ((rc = svo_grow(ctx, (size_t)cap, &s->new_of))) return rc;
-    const uint32_t *st = s->status.host();
-
-    PlanArgs plan{};
+    const uint32_t depth = p->depth;
+    struct : FrontierPass {
+        svo_heightmap_state *s;
+        PlanArgs args{};
+        void plan(svo_ctx *ctx, const Level &l) {
+            args.level = l.level;
+            args.at = s->levels[args.depth - l.level];
+            heightmap_plan_kernel<<<l.blocks, kThreads, 0, ctx->stream>>>(ctx->nodes, args, l.at, l.out);
+        }
+        void emit(svo_ctx *ctx, const Level &l) { heightmap_emit_kernel<<<l.blocks, kThreads, 0, ctx->stream>>>(ctx->nodes, l.at, l.emit); }
+    } pass;
+    pass.s = s;
+    PlanArgs &plan = pass.args;
     plan.depth = depth, plan.clamp = 1u << depth;
     plan.ox = p->origin_xz[0], plan.oz = p->origin_xz[1], plan.sx = p->size_xz[0], plan.sz = p->size_xz[1];
     plan.mode_below = p->mode_below, plan.mode_above = p->mode_above, plan.colour_above = p->colour_above & 0xFFFFFFu;
@@ -395,106 +325,16 @@ int svo_nodes_edit_heightmap(svo_ctx *ctx, const svo_heightmap_params *p, const 
         plan.T[k] = last ? kNone : (uint32_t)std::min<uint64_t>(sum, kNone);
         plan.colour[k] = p->n_layers ? l.colour & 0xFFFFFFu : 0u;
     }
-
-    // the pyramid and the plan read the words and the map: behind every earlier write to the store, whichever context issued it
-    if ((rc = svo_store_order_after_write(ctx))) return rc;
-    HIP_TRY(ctx, s->timer.mark(ctx, kEvStart));
-    if ((rc = build_pyramid(ctx, s, p, heights_dev))) return rc;
+    Walk walk;
+    // (the pyramid reads the map behind the store's last write too)
+    if ((rc = walk.begin(ctx, p->n_words, depth, "edited", s->timer.ev[kEvStart])) || (rc = build_pyramid(ctx, s, p, heights_dev))) return rc;
     HIP_TRY(ctx, s->timer.mark(ctx, kEvPyramid));
-    HIP_TRY(ctx, s->status.zero(ctx));
-    HIP_TRY(ctx, hipMemsetAsync(s->new_of, 0xFF, size_t(cap) * sizeof(uint32_t), ctx->stream));
-    HIP_TRY(ctx, hipMemsetAsync(s->new_of, 0, sizeof(uint32_t), ctx->stream));  // the root group is group 0 of the frontiers
-    if ((rc = svo_grow(ctx, 1, &s->gbase[0], &s->gvirt[0])) || (rc = svo_grow(ctx, 1, &s->gkey[0]))) return rc;
-    HIP_TRY(ctx, hipMemsetAsync(s->gbase[0], 0, sizeof(uint32_t), ctx->stream));  // level 1: the root group, real, its parent the cell 0
-    HIP_TRY(ctx, hipMemsetAsync(s->gvirt[0], 0, sizeof(uint32_t), ctx->stream));
-    HIP_TRY(ctx, hipMemsetAsync(s->gkey[0], 0, sizeof(uint64_t), ctx->stream));
-
-    // plan: off = the frontier words of the levels above (the list's entries so far), n = this level's
-    uint64_t off = 0, groups_seen = 1, splits = 0;
-    uint32_t n = 8, last_blocks = 0, last_level = 0;
-    int cur = 0;
-    for (uint32_t level = 1; level <= depth && n; level++, cur ^= 1) {
-        // every frontier word is a word of its own of the edited tree
-        if (off + n > kMaxWords + 8ull * cap)
-            return svo_fail(ctx, SVO_ERR_CAP, "the edited tree needs more than 2^27 words, over the limit (max_words, the node buffer's capacity, 2^27)");
-        const int nx = cur ^ 1;
-        const uint32_t blocks = svo_div_up(n, kThreads);
-        if ((rc = svo_grow(ctx, (size_t)n, &s->code, &s->open_scan, &s->split_scan)) || (rc = svo_grow(ctx, (size_t)blocks, &s->bad)) ||
-            (rc = svo_grow(ctx, (size_t)n, &s->gbase[nx], &s->gvirt[nx])) || (rc = svo_grow(ctx, (size_t)n, &s->gkey[nx])) ||
-            (rc = grow_list(ctx, off + n, off, &s->list_at, &s->list_word, &s->list_fill)))
-            return rc;
-        plan.level = level;
-        plan.at = s->levels[depth - level];
-        heightmap_plan_kernel<<<blocks, kThreads, 0, ctx->stream>>>(ctx->nodes, plan, s->gbase[cur], s->gkey[cur], s->gvirt[cur], n, s->code,
-                                                                   s->open_scan, s->split_scan, s->list_at + off, s->list_word + off,
-                                                                   s->list_fill + off, s->bad);
-        HIP_TRY(ctx, hipGetLastError());
-        if ((rc = svo_scan_u32(ctx, s->open_scan, n)) || (rc = svo_scan_u32(ctx, s->split_scan, n))) return rc;
-        heightmap_emit_kernel<<<blocks, kThreads, 0, ctx->stream>>>(ctx->nodes, s->gbase[cur], s->gkey[cur], s->gvirt[cur], n, s->code, s->open_scan,
-                                                                   s->split_scan, n_words, uint32_t(p->n_words + 8 * splits), s->list_word + off,
-                                                                   s->gbase[nx], s->gkey[nx], s->gvirt[nx], s->status.dev);
-        HIP_TRY(ctx, hipGetLastError());
-        if ((rc = s->status.read(ctx))) return rc;
-        if (st[kStAlign]) return malformed(ctx, "an interior pointer at level " + std::to_string(level) + " is not a multiple of 8");
-        if (st[kStRange])
-            return malformed(ctx, "an interior pointer at level " + std::to_string(level) + " leaves the first n_words = " +
-                                      std::to_string(p->n_words) + " words");
-        if (st[kStDup]) return malformed(ctx, "a group is reached twice");  // (the marks of the level above)
-        const uint32_t next = st[kStNext];
-        if (next > n) return svo_fail(ctx, SVO_ERR_HIP, "the next frontier's scan is out of range");  // (never: a word opens one group at the most)
-        off += n;
-        last_blocks = blocks, last_level = level;
-        splits += st[kStSplits];
-        if (next) {
-            const uint32_t grid = svo_div_up(next, kThreads);
-            region_mark_kernel<<<grid, kThreads, 0, ctx->stream>>>(s->gbase[nx], s->gvirt[nx], next, (uint32_t)groups_seen, cap, s->new_of, s->status.dev);
-            region_check_kernel<<<grid, kThreads, 0, ctx->stream>>>(s->gbase[nx], s->gvirt[nx], next, (uint32_t)groups_seen, cap, s->new_of,
-                                                                     s->status.dev);
-            HIP_TRY(ctx, hipGetLastError());
-            groups_seen += next;
-        }
-        n = 8u * next;  // (next <= the level's words <= 2^27 + n_words: no wrap)
-    }
-    HIP_TRY(ctx, s->timer.mark(ctx, kEvPlan));
-
-    // status: the last level's groups reached twice, and the first refused word of level `depth`
-    if (last_level == depth) min_of_blocks_kernel<1><<<1, kTopThreads, 0, ctx->stream>>>(s->bad, last_blocks, s->status.dev + kStBad);
-    HIP_TRY(ctx, hipGetLastError());
-    HIP_TRY(ctx, s->status.copy(ctx));
-    HIP_TRY(ctx, s->timer.mark(ctx, kEvStatus));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    if (st[kStDup]) return malformed(ctx, "a group is reached twice");
-    if (last_level == depth && st[kStBad] != kNone) {
-        // the refused word's cell from its group's record
-        const uint32_t i = st[kStBad], c = i & 7u;
-        uint64_t key = 0;
-        HIP_TRY(ctx, hipMemcpyAsync(&key, s->gkey[cur ^ 1].get() + (i >> 3), sizeof key, hipMemcpyDeviceToHost, ctx->stream));
-        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        const uint32_t x = (uint32_t(key >> (2 * kCellBits)) & kCellMask) * 2u + (c >> 2), y = (uint32_t(key >> kCellBits) & kCellMask) * 2u + ((c >> 1) & 1u),
-                       z = (uint32_t(key) & kCellMask) * 2u + (c & 1u);
-        return svo_fail(ctx, SVO_ERR_STATE, "the height map meets cell (" + std::to_string(x) + ", " + std::to_string(y) + ", " + std::to_string(z) +
-                                                "), which is an interior node at depth " + std::to_string(depth) +
+    if ((rc = walk.run(ctx, pass, s->timer.ev[kEvPlan], s->timer.ev[kEvStatus]))) return rc;
+    if (walk.refused)
+        return svo_fail(ctx, SVO_ERR_STATE, "the height map meets cell (" + std::to_string(walk.cell.x) + ", " + std::to_string(walk.cell.y) + ", " +
+                                                std::to_string(walk.cell.z) + "), which is an interior node at depth " + std::to_string(depth) +
                                                 ": the tree is finer there than the edit, and the mode does not replace the subtree");
-    }
-    uint64_t limit = std::min<uint64_t>(ctx->capacity, kMaxWords);
-    if (p->max_words) limit = std::min<uint64_t>(limit, p->max_words);
-    const uint64_t new_words = p->n_words + 8 * splits;
-    if (new_words > limit)
-        return svo_fail(ctx, SVO_ERR_CAP, "the edited tree needs " + std::to_string(new_words) + " words, over the limit of " + std::to_string(limit) +
-                                              " (max_words, the node buffer's capacity, 2^27)");
-
-    // commit: behind every earlier write to the store (another context may have written while this one waited)
-    if ((rc = svo_store_order_after_write(ctx))) return rc;
-    const uint32_t entries = (uint32_t)off;
-    region_fill_kernel<<<svo_div_up(8ull * entries, kThreads), kThreads, 0, ctx->stream>>>(ctx->nodes, (uint32_t)new_words, s->list_at, s->list_word,
-                                                                                         s->list_fill, entries);
-    HIP_TRY(ctx, hipGetLastError());
-    HIP_TRY(ctx, s->timer.mark(ctx, kEvFill));
-    region_write_kernel<<<svo_div_up(entries, kThreads), kThreads, 0, ctx->stream>>>(ctx->nodes, (uint32_t)new_words, s->list_at, s->list_word, entries);
-    HIP_TRY(ctx, hipGetLastError());
-    HIP_TRY(ctx, s->timer.mark(ctx, kEvEnd));
-    if ((rc = svo_store_note_write(ctx))) return rc;
-    *n_words_out = new_words;
+    if ((rc = walk.commit(ctx, p->max_words, s->timer.ev[kEvFill], s->timer.ev[kEvEnd], n_words_out))) return rc;
     s->timer.finish(t0);
     return SVO_OK;
 }

@@ -1,9 +1,9 @@
 // svo_morph.hip -- one step of mathematical morphology on the tree in the node buffer: grow it by the cells
 // that touch a voxel, or shrink it by the voxels that touch an empty cell, under 6, 18 or 26 neighbours.  include/svo_hip.h has
-// the rule for one cell and for one word; this file applies it level by level in svo_place.hip's frame, with its frontier,
-// plan, scans, check and commit.  Where a placed scene word faces up to 2 x 2 x 2 cells of a second tree, a word here faces
-// the 3 x 3 x 3 cells of its own level of the scene itself: the plan never writes, so the tree is its own neighbour as it was
-// before the call.
+// the rule for one cell and for one word; this file applies it level by level with the walk of svo_frontier.h.
+// Where a placed scene word (svo_place.hip) faces up to 2 x 2 x 2 cells of a second tree, a word here faces the 3 x 3 x 3
+// cells of its own level of the scene itself: the plan never writes, so the tree is its own neighbour as it was before the
+// call.
 //
 //   items     one word each: OUT (outside the grid) or a scene word without its counter (a leaf: a constant, carried down as
 //             it is; an interior word: a group of the scene).  A frontier group's record holds, beside the scene's side as in
@@ -14,25 +14,21 @@
 //   plan      per level, reading only, one lane per frontier word.  An interior word is opened; a leaf that the op cannot
 //             change is done; any other leaf folds its counting items, in the order of the per-cell rule, into three numbers
 //             (not quiet, interior among those, the first value set) and is left, overwritten, split or refused by them
-//   scan, check, status, commit   the placement's, with svo_frontier.h's kernels and svo_scan.h's scans; a pointer that a later
-//             level follows is every interior item written into a record, checked where it is written
+//   emit      a pointer that a later level follows is every interior item written into a record, checked where it is written
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <string>
 
 #include "svo_ctx.h"
-#include "svo_frontier.h"  // (kNone, leaf_word, region_mark_kernel, region_check_kernel, region_fill_kernel, region_write_kernel, grow_list)
-#include "svo_scan.h"  // (svo_scan_u32, block_min, min_of_blocks_kernel; svo_group.h: kThreads, kEmptyWord, kMaxWords)
+#include "svo_frontier.h"  // (the walk: Entry, PlanOut, emit_head, Walk; kNone, leaf_word)
 
 namespace {
 
-constexpr uint32_t kCellBits = 21, kCellMask = (1u << kCellBits) - 1u;  // a record's cell: x << 42 | y << 21 | z
 constexpr uint32_t kItems = 27, kCentre = 13;
 constexpr uint32_t kItemOut = 1u;  // an item's low four bits: 0 = a scene word without its counter
-// a word's flags, as svo_combine.hip's; kFiner: an interior word at level `depth`, or a leaf there that an interior item would change
-enum Code : uint32_t { kOpen = 1u, kSplit = 2u, kFiner = 4u };
-enum Status { kStAlign = SVO_WALK_ALIGN, kStRange = SVO_WALK_RANGE, kStNext = SVO_WALK_NEXT, kStDup = SVO_WALK_DUP, kStSplits, kStBad, kStWords };
+// a word's flag above the walk's: an interior word at level `depth`, or a leaf there that an interior item would change
+constexpr uint32_t kFiner = 4u;
 
 // The call's constants, by value to the kernels.  reach: 1, 2 or 3, the largest |d|_1 of conn's offsets.
 struct Morph {
@@ -59,18 +55,15 @@ __global__ __launch_bounds__(32) void morph_root_kernel(uint32_t *__restrict__ g
     if (j < kItems) gitem[j] = j == kCentre ? 0u : kItemOut;
 }
 
-// The rule for the n frontier words of a level.
-__global__ __launch_bounds__(kThreads) void morph_plan_kernel(const uint32_t *__restrict__ words, Morph m, uint32_t level,
-                                                              const uint32_t *__restrict__ gbase, const uint32_t *__restrict__ gvirt,
-                                                              const uint32_t *__restrict__ gitem, uint32_t n, uint32_t *__restrict__ code,
-                                                              uint32_t *__restrict__ open_scan, uint32_t *__restrict__ split_scan,
-                                                              uint32_t *__restrict__ list_at, uint32_t *__restrict__ list_word,
-                                                              uint32_t *__restrict__ list_fill, uint32_t *__restrict__ bad) {
+// The rule for the frontier words of a level.
+__global__ __launch_bounds__(kThreads) void morph_plan_kernel(const uint32_t *__restrict__ words, Morph m, uint32_t level, Frontier f,
+                                                              const uint32_t *__restrict__ gitem, PlanOut o) {
     const uint32_t i = blockIdx.x * kThreads + threadIdx.x;
     uint32_t refused = kNone;
-    if (i < n) {
-        const uint32_t g = i >> 3, c = i & 7u, virt = gvirt[g], here = gbase[g] + c;
-        const uint32_t word = virt ? virt : words[here];  // (a real group's pointer passed the check: below n_words)
+    if (i < f.n) {
+        const uint32_t g = i >> 3, c = i & 7u;
+        const Entry e = frontier_entry(words, f, i);
+        const uint32_t here = e.at, word = e.word;
         const bool grow = m.op == SVO_MORPH_GROW;
         uint32_t cd = 0, at = kNone, out = 0, fill = 0;
         if ((word >> 4) < SVO_VOXEL_OFFSET) cd = level == m.depth ? kFiner : kOpen;
@@ -105,47 +98,18 @@ __global__ __launch_bounds__(kThreads) void morph_plan_kernel(const uint32_t *__
             }
         }
         if (cd & kFiner) refused = i;
-        code[i] = cd;
-        open_scan[i] = cd & kOpen;
-        split_scan[i] = (cd & kSplit) >> 1;
-        list_at[i] = at;
-        list_word[i] = out;
-        list_fill[i] = fill;
+        plan_store(o, i, cd, at, out, fill);
     }
-    const uint32_t first_bad = block_min<kThreads>(refused);
-    if (threadIdx.x == 0) bad[blockIdx.x] = first_bad;
+    plan_refused(o, refused);
 }
 
-// Behind the two scans: the records of the next frontier's groups with their items, the pointers of the splits and the two
-// totals, as svo_place.hip's place_emit_kernel.  A pointer that is followed is checked as the discovery checks it: the
-// word's own, and every interior item's.
-__global__ __launch_bounds__(kThreads) void morph_emit_kernel(const uint32_t *__restrict__ words, Morph m, const uint32_t *__restrict__ gbase,
-                                                              const uint64_t *__restrict__ gkey, const uint32_t *__restrict__ gvirt,
-                                                              const uint32_t *__restrict__ gitem, uint32_t n, const uint32_t *__restrict__ code,
-                                                              const uint32_t *__restrict__ open_scan, const uint32_t *__restrict__ split_scan,
-                                                              uint32_t n_words, uint32_t first_new, uint32_t *__restrict__ list_word,
-                                                              uint32_t *__restrict__ next_base, uint64_t *__restrict__ next_key,
-                                                              uint32_t *__restrict__ next_virt, uint32_t *__restrict__ next_item,
-                                                              uint32_t *__restrict__ status) {
-    const uint32_t i = blockIdx.x * kThreads + threadIdx.x;
-    if (i >= n) return;
-    const uint32_t cd = code[i], k = open_scan[i];
-    if (i == n - 1) {
-        status[kStNext] = k + (cd & kOpen);
-        status[kStSplits] = split_scan[i] + ((cd & kSplit) >> 1);
-    }
-    if (!(cd & kOpen) || k >= n) return;  // (k < n always: a word opens one group at the most)
-    const uint32_t g = i >> 3, c = i & 7u, virt = gvirt[g];
-    const uint64_t key = gkey[g];
-    const uint32_t word = virt ? virt : words[gbase[g] + c];
-    uint32_t base, next_v = 0;
-    if (cd & kSplit) {
-        base = first_new + 8u * split_scan[i];
-        next_v = word & ~15u;
-        list_word[i] = base << 4;
-    } else {
-        base = word >> 4;
-    }
+// Behind the two scans: the records of the next frontier's groups with their items.  A pointer that is followed is checked
+// as the discovery checks it: the word's own by emit_head, and every interior item's here.  (The centre item of an opened
+// word of a real group is that word, so its pointer is checked twice, to the same end.)
+__global__ __launch_bounds__(kThreads) void morph_emit_kernel(const uint32_t *__restrict__ words, Morph m, Frontier f, const uint32_t *__restrict__ gitem,
+                                                              EmitArgs a, uint32_t *__restrict__ next_item) {
+    Opened o;
+    if (!emit_head(words, f, a, o)) return;
     // the word's cell and its neighbours: the cell itself is the word, a split's the constant it hands down
 #pragma unroll
     for (int dx = -1; dx <= 1; dx++)
@@ -154,44 +118,33 @@ __global__ __launch_bounds__(kThreads) void morph_emit_kernel(const uint32_t *__
 #pragma unroll
             for (int dz = -1; dz <= 1; dz++) {
                 if (uint32_t((dx != 0) + (dy != 0) + (dz != 0)) > m.reach) continue;  // (the same for the whole launch)
-                const uint32_t item = child_item(words, gitem, g, c, dx, dy, dz);
+                const uint32_t item = child_item(words, gitem, o.i >> 3, o.i & 7u, dx, dy, dz);
                 if (item != kItemOut && (item >> 4) < SVO_VOXEL_OFFSET) {
-                    if ((item >> 4) & 7u) status[kStAlign] = 1u;  // (every writer stores the same value)
-                    else if (uint64_t(item >> 4) + 8u > n_words) status[kStRange] = 1u;
+                    if ((item >> 4) & 7u) a.status[kStAlign] = 1u;  // (every writer stores the same value)
+                    else if (uint64_t(item >> 4) + 8u > a.n_words) a.status[kStRange] = 1u;
                 }
-                next_item[size_t(kItems) * k + uint32_t(9 * (dx + 1) + 3 * (dy + 1) + dz + 1)] = item;
+                next_item[size_t(kItems) * o.k + uint32_t(9 * (dx + 1) + 3 * (dy + 1) + dz + 1)] = item;
             }
-    next_base[k] = base;
-    next_virt[k] = next_v;
-    const uint32_t x = (uint32_t(key >> (2 * kCellBits)) & kCellMask) * 2u + (c >> 2), y = (uint32_t(key >> kCellBits) & kCellMask) * 2u + ((c >> 1) & 1u),
-                   z = (uint32_t(key) & kCellMask) * 2u + (c & 1u);
-    next_key[k] = uint64_t(x) << (2 * kCellBits) | uint64_t(y) << kCellBits | z;
+    emit_record(a, o);
 }
 
 enum Ev { kEvStart, kEvPlan, kEvStatus, kEvFill, kEvEnd, kEvs };
 
 }  // namespace
 
-// Per-context workspace of the morphology (svo_ctx::morph): svo_place_state's, with 27 items per group record.  The records
-// are kept for two levels at a time, the list for the whole walk.
+// What the morphology keeps per context beside the walk's workspace (svo_ctx::morph): the 27 items per group of the two
+// sets of frontier records, and the times.
 struct svo_morph_state {
-    svo_dev<uint32_t> gbase[2], gvirt[2], gitem[2];
-    svo_dev<uint64_t> gkey[2];
-    svo_dev<uint32_t> code, open_scan, split_scan, bad;
-    svo_dev<uint32_t> list_at, list_word, list_fill;
-    svo_dev<uint32_t> new_of;
-    svo_mirrored<> status;  // kStWords words
+    svo_dev<uint32_t> gitem[2];
     svo_pass_timer<kEvs, SVO_MORPH_TIMES> timer;
 
     int create(svo_ctx *ctx) {
         HIP_TRY(ctx, timer.create());
-        return status.alloc(ctx, kStWords);
+        return SVO_OK;
     }
 };
 
 namespace {
-
-int malformed(svo_ctx *ctx, const std::string &why) { return svo_fail(ctx, SVO_ERR_STATE, "malformed tree: " + why); }
 
 const char *const kOpNames[] = {"grow", "shrink"};
 
@@ -219,106 +172,32 @@ int svo_nodes_morph(svo_ctx *ctx, const svo_morph_params *p, uint64_t *n_words_o
     svo_morph_state *s = ctx->morph.get();
     const double t0 = svo_now_ms();
     if ((rc = s->timer.begin(ctx))) return rc;
-    // no pointer reaches a group behind 2^27, so the words behind it hold no reachable group
-    const uint32_t depth = p->depth, n_words = (uint32_t)std::min<uint64_t>(p->n_words, kMaxWords), cap = n_words / 8;
-    const Morph morph = {p->op, p->conn == 6 ? 1u : p->conn == 18 ? 2u : 3u, depth, p->flags & SVO_MORPH_OPEN_BOUNDARY, p->colour & 0xFFFFFFu};
-    if ((rc = svo_grow(ctx, (size_t)cap, &s->new_of))) return rc;
-    const uint32_t *st = s->status.host();
-
-    // the plan reads the words: behind every earlier write to the store, whichever context issued it
-    if ((rc = svo_store_order_after_write(ctx))) return rc;
-    HIP_TRY(ctx, s->timer.mark(ctx, kEvStart));
-    HIP_TRY(ctx, s->status.zero(ctx));
-    HIP_TRY(ctx, hipMemsetAsync(s->new_of, 0xFF, size_t(cap) * sizeof(uint32_t), ctx->stream));
-    HIP_TRY(ctx, hipMemsetAsync(s->new_of, 0, sizeof(uint32_t), ctx->stream));  // the root group is group 0 of the frontiers
-    if ((rc = svo_grow(ctx, 1, &s->gbase[0], &s->gvirt[0])) || (rc = svo_grow(ctx, kItems, &s->gitem[0])) || (rc = svo_grow(ctx, 1, &s->gkey[0]))) return rc;
-    morph_root_kernel<<<1, 32, 0, ctx->stream>>>(s->gbase[0], s->gkey[0], s->gvirt[0], s->gitem[0]);
-    HIP_TRY(ctx, hipGetLastError());
-
-    // plan: off = the frontier words of the levels above (the list's entries so far), n = this level's
-    uint64_t off = 0, groups_seen = 1, splits = 0;
-    uint32_t n = 8, last_blocks = 0, last_level = 0;
-    int cur = 0;
-    for (uint32_t level = 1; level <= depth && n; level++, cur ^= 1) {
-        // every frontier word is a word of its own of the new tree
-        if (off + n > kMaxWords + 8ull * cap)
-            return svo_fail(ctx, SVO_ERR_CAP, "the new tree needs more than 2^27 words, over the limit (max_words, the node buffer's capacity, 2^27)");
-        const int nx = cur ^ 1;
-        const uint32_t blocks = svo_div_up(n, kThreads);
-        if ((rc = svo_grow(ctx, (size_t)n, &s->code, &s->open_scan, &s->split_scan)) || (rc = svo_grow(ctx, (size_t)blocks, &s->bad)) ||
-            (rc = svo_grow(ctx, (size_t)n, &s->gbase[nx], &s->gvirt[nx])) || (rc = svo_grow(ctx, kItems * (size_t)n, &s->gitem[nx])) ||
-            (rc = svo_grow(ctx, (size_t)n, &s->gkey[nx])) || (rc = grow_list(ctx, off + n, off, &s->list_at, &s->list_word, &s->list_fill)))
-            return rc;
-        morph_plan_kernel<<<blocks, kThreads, 0, ctx->stream>>>(ctx->nodes, morph, level, s->gbase[cur], s->gvirt[cur], s->gitem[cur], n, s->code,
-                                                               s->open_scan, s->split_scan, s->list_at + off, s->list_word + off, s->list_fill + off,
-                                                               s->bad);
-        HIP_TRY(ctx, hipGetLastError());
-        if ((rc = svo_scan_u32(ctx, s->open_scan, n)) || (rc = svo_scan_u32(ctx, s->split_scan, n))) return rc;
-        morph_emit_kernel<<<blocks, kThreads, 0, ctx->stream>>>(ctx->nodes, morph, s->gbase[cur], s->gkey[cur], s->gvirt[cur], s->gitem[cur], n, s->code,
-                                                               s->open_scan, s->split_scan, n_words, uint32_t(p->n_words + 8 * splits),
-                                                               s->list_word + off, s->gbase[nx], s->gkey[nx], s->gvirt[nx], s->gitem[nx], s->status.dev);
-        HIP_TRY(ctx, hipGetLastError());
-        if ((rc = s->status.read(ctx))) return rc;
-        if (st[kStAlign]) return malformed(ctx, "an interior pointer at level " + std::to_string(level) + " is not a multiple of 8");
-        if (st[kStRange])
-            return malformed(ctx, "an interior pointer at level " + std::to_string(level) + " leaves the first n_words = " + std::to_string(p->n_words) +
-                                      " words");
-        if (st[kStDup]) return malformed(ctx, "a group is reached twice");  // (the marks of the level above)
-        const uint32_t next = st[kStNext];
-        if (next > n) return svo_fail(ctx, SVO_ERR_HIP, "the next frontier's scan is out of range");  // (never: a word opens one group at the most)
-        off += n;
-        last_blocks = blocks, last_level = level;
-        splits += st[kStSplits];
-        if (next) {
-            const uint32_t grid = svo_div_up(next, kThreads);
-            region_mark_kernel<<<grid, kThreads, 0, ctx->stream>>>(s->gbase[nx], s->gvirt[nx], next, (uint32_t)groups_seen, cap, s->new_of, s->status.dev);
-            region_check_kernel<<<grid, kThreads, 0, ctx->stream>>>(s->gbase[nx], s->gvirt[nx], next, (uint32_t)groups_seen, cap, s->new_of,
-                                                                      s->status.dev);
-            HIP_TRY(ctx, hipGetLastError());
-            groups_seen += next;
+    const uint32_t depth = p->depth;
+    struct : FrontierPass {
+        svo_morph_state *s;
+        Morph morph;
+        int grow(svo_ctx *ctx, int set, size_t groups) { return svo_grow(ctx, kItems * groups, &s->gitem[set]); }
+        int root(svo_ctx *ctx, svo_frontier_walk &w) {
+            morph_root_kernel<<<1, 32, 0, ctx->stream>>>(w.gbase[0], w.gkey[0], w.gvirt[0], s->gitem[0]);
+            return SVO_OK;
         }
-        n = 8u * next;  // (next <= the level's words <= 2^27 + n_words: no wrap)
-    }
-    HIP_TRY(ctx, s->timer.mark(ctx, kEvPlan));
-
-    // status: the last level's groups reached twice, and the first refused word of level `depth`
-    if (last_level == depth) min_of_blocks_kernel<1><<<1, kTopThreads, 0, ctx->stream>>>(s->bad, last_blocks, s->status.dev + kStBad);
-    HIP_TRY(ctx, hipGetLastError());
-    HIP_TRY(ctx, s->status.copy(ctx));
-    HIP_TRY(ctx, s->timer.mark(ctx, kEvStatus));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    if (st[kStDup]) return malformed(ctx, "a group is reached twice");
-    if (last_level == depth && st[kStBad] != kNone) {
-        // the refused word's cell from its group's record (the last level's records are the current ones: nothing was emitted behind them)
-        const uint32_t i = st[kStBad], c = i & 7u;
-        uint64_t key = 0;
-        HIP_TRY(ctx, hipMemcpyAsync(&key, s->gkey[cur ^ 1].get() + (i >> 3), sizeof key, hipMemcpyDeviceToHost, ctx->stream));
-        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        const uint32_t x = (uint32_t(key >> (2 * kCellBits)) & kCellMask) * 2u + (c >> 2), y = (uint32_t(key >> kCellBits) & kCellMask) * 2u + ((c >> 1) & 1u),
-                       z = (uint32_t(key) & kCellMask) * 2u + (c & 1u);
-        return svo_fail(ctx, SVO_ERR_STATE, std::string(kOpNames[p->op]) + " meets cell (" + std::to_string(x) + ", " + std::to_string(y) + ", " +
-                                                std::to_string(z) + "), where the tree is finer than depth " + std::to_string(depth) +
+        void plan(svo_ctx *ctx, const Level &l) {
+            morph_plan_kernel<<<l.blocks, kThreads, 0, ctx->stream>>>(ctx->nodes, morph, l.level, l.at, s->gitem[l.cur], l.out);
+        }
+        void emit(svo_ctx *ctx, const Level &l) {
+            morph_emit_kernel<<<l.blocks, kThreads, 0, ctx->stream>>>(ctx->nodes, morph, l.at, s->gitem[l.cur], l.emit, s->gitem[l.nx]);
+        }
+    } pass;
+    pass.s = s;
+    pass.morph = {p->op, p->conn == 6 ? 1u : p->conn == 18 ? 2u : 3u, depth, p->flags & SVO_MORPH_OPEN_BOUNDARY, p->colour & 0xFFFFFFu};
+    Walk walk;
+    if ((rc = walk.begin(ctx, p->n_words, depth, "new", s->timer.ev[kEvStart])) || (rc = walk.run(ctx, pass, s->timer.ev[kEvPlan], s->timer.ev[kEvStatus])))
+        return rc;
+    if (walk.refused)
+        return svo_fail(ctx, SVO_ERR_STATE, std::string(kOpNames[p->op]) + " meets cell (" + std::to_string(walk.cell.x) + ", " + std::to_string(walk.cell.y) +
+                                                ", " + std::to_string(walk.cell.z) + "), where the tree is finer than depth " + std::to_string(depth) +
                                                 ": the cell or a neighbour that would change it is an interior node there");
-    }
-    uint64_t limit = std::min<uint64_t>(ctx->capacity, kMaxWords);
-    if (p->max_words) limit = std::min<uint64_t>(limit, p->max_words);
-    const uint64_t new_words = p->n_words + 8 * splits;
-    if (new_words > limit)
-        return svo_fail(ctx, SVO_ERR_CAP, "the new tree needs " + std::to_string(new_words) + " words, over the limit of " + std::to_string(limit) +
-                                              " (max_words, the node buffer's capacity, 2^27)");
-
-    // commit: behind every earlier write to the store (another context may have written while this one waited)
-    if ((rc = svo_store_order_after_write(ctx))) return rc;
-    const uint32_t entries = (uint32_t)off;
-    region_fill_kernel<<<svo_div_up(8ull * entries, kThreads), kThreads, 0, ctx->stream>>>(ctx->nodes, (uint32_t)new_words, s->list_at, s->list_word,
-                                                                                          s->list_fill, entries);
-    HIP_TRY(ctx, hipGetLastError());
-    HIP_TRY(ctx, s->timer.mark(ctx, kEvFill));
-    region_write_kernel<<<svo_div_up(entries, kThreads), kThreads, 0, ctx->stream>>>(ctx->nodes, (uint32_t)new_words, s->list_at, s->list_word, entries);
-    HIP_TRY(ctx, hipGetLastError());
-    HIP_TRY(ctx, s->timer.mark(ctx, kEvEnd));
-    if ((rc = svo_store_note_write(ctx))) return rc;
-    *n_words_out = new_words;
+    if ((rc = walk.commit(ctx, p->max_words, s->timer.ev[kEvFill], s->timer.ev[kEvEnd], n_words_out))) return rc;
     s->timer.finish(t0);
     return SVO_OK;
 }
