@@ -627,6 +627,68 @@ int svo_nodes_place(svo_ctx *ctx, const uint32_t *src_dev, const svo_place_param
 #define SVO_PLACE_TIMES 5   /* plan (with its per-level read-backs), status, fill, write, host wall */
 int svo_place_timing(svo_ctx *ctx, float ms_out[SVO_PLACE_TIMES]);
 
+/* ---- a device tree placed into the scene under any affine map: free turns, scale, shear ----
+ * svo_nodes_place with the signed permutation and the cell offset replaced by a fixed-point affine map FROM SCENE CELLS TO
+ * SOURCE CELLS, sampled at cell centres, nearest cell.  The scene A is the first n_words words of the node buffer on a grid of
+ * depth `depth`; the source B is the src_words words at src_dev (DEVICE, rooted at group 0, ONLY READ, hit counters ignored) on a
+ * grid of depth src_depth (side S), which `depth` does not bound: the source's cells need not be the scene's, the matrix says
+ * how they relate.  matrix is row-major Q16 (value / 65536), translate Q16 in source cells.  The map is the one the rule needs,
+ * scene to source (the inverse of "turn the model, then put it there"); a singular matrix is allowed, it is still a sampling rule.
+ * Per cell c of the `depth` grid, in int64:
+ *     P_i = sum_j matrix[i][j] * (2 c_j + 1) + 2 translate[i]      2^17 times A (c + 1/2) + t
+ *     q_i = P_i >> 17                                               an arithmetic shift: floor
+ * When q lies in [0, S)^3 the cell samples (svo_nodes_sample) afterwards to f(a, b), a = what the scene sampled at c before,
+ * b = what the source samples at q, the leaf that holds q, coarse leaves included, f by op as svo_nodes_combine's
+ * (SVO_COMBINE_OVER .. SVO_COMBINE_REPLACE).  Every other cell samples as before.  With the bounds below |P| < 2^45: nothing
+ * overflows.  Point sampling aliases where the map shrinks the source; svo_nodes_simplify with a cut level on the source first
+ * is the remedy.
+ * The words are deterministic, the same bytes on every run (integers only, scans, no atomics), by this rule.  The walk is
+ * svo_nodes_combine's: level by level from the scene's root group, the frontier of level l + 1 the eight children, by child
+ * index, of every word of level l that was opened or split, those taken in frontier order; the g-th split gets the group
+ * n_words + 8 g, *n_words_out = n_words + 8 * splits, and nothing at or behind *n_words_out is touched.
+ * A WORD'S SOURCE BOX.  A scene word of level l with cell (x, y, z) has zc = 2^(depth - l) cells a side.  All source cells that
+ * its cells can sample lie in a box, per source axis i:
+ *     mid_i = sum_j matrix[i][j] * (2 cell_j zc + zc) + 2 translate[i]        rad_i = (zc - 1) * sum_j |matrix[i][j]|
+ *     qlo_i = (mid_i - rad_i) >> 17                                           qhi_i = (mid_i + rad_i) >> 17
+ * exact interval arithmetic over the cube's cell centres; at level `depth` the box is the one cell q above.
+ * ITEMS.  With e = max_i (qhi_i - qlo_i + 1), s = min(src_depth, ceil(log2 e)) and k = src_depth - s, the word faces the cells
+ * of the source's level-k grid, continued beyond the cube, that the box meets: the indices qlo_i >> s .. qhi_i >> s per axis, at
+ * most two per axis unless e > S.  Each such item is OUT (outside [0, 2^k)^3), a constant b (a source leaf on the way down from
+ * the root, carried down, or a leaf at level k) or a source interior word; at k = 0 the root, as an interior word pointing at
+ * the source's group 0.  Only the set of kinds and values matters: with e > S every met cell but index 0 is OUT, and OUT counts
+ * once.
+ * NORMALISATION, THEN THE DECISION are svo_nodes_place's, word for word: all items OUT, the word and everything below keep all
+ * 32 bits; all items one constant, svo_nodes_combine's leaf rule; anything else its interior rule, which opens an interior
+ * word, leaves a leaf that f(a, .) = a lets stay and splits any other leaf with its colour carried.  Opening or splitting at
+ * level `depth` is refused as svo_nodes_place refuses it: SVO_ERR_STATE, nothing written, svo_last_error names the cell and the
+ * finer tree.
+ * With the matrix a signed permutation times 65536 and a whole-cell translation, matrix[perm[i]][i] = f_i ? -65536 : 65536 and
+ * translate[perm[i]] = 65536 * (f_i ? S + offset_i : -offset_i) in svo_nodes_place's terms, the words are byte for byte those
+ * of svo_nodes_place: then e == zc on every level, so the level-k cells are the cells of the word's own size and the items are
+ * svo_nodes_place's.
+ * Every error is decided by a read-only plan before any write; of several causes the first in this order is reported.
+ * SVO_ERR_ARG: NULL p, n_words_out or src_dev; op > 5; depth outside 1..21; src_depth outside 1..21; a matrix entry outside
+ * [-2^20, 2^20]; a translation outside [-2^40, 2^40].  Then svo_nodes_place's, from "no node buffer" on, with "malformed
+ * source: ..." for a source pointer that the call follows, unaligned or leaving src_words: one on the way down to a word's
+ * items, or an interior item of a word that is opened or split.  No source pointer is followed before it is checked.
+ * Stream ordering, blocking (once per level and once for the status) and the recording of the write for the contexts that share
+ * the buffer are svo_nodes_combine's. */
+typedef struct svo_transform_params {
+    uint32_t op;           /* SVO_COMBINE_OVER .. SVO_COMBINE_REPLACE */
+    uint32_t depth;        /* 1..21: the scene grid; no word below this level is made or opened */
+    uint32_t src_depth;    /* 1..21: the source's cube has 2^src_depth cells a side; not bound by depth */
+    int32_t matrix[9];     /* scene cells -> source cells, row-major Q16: -2^20..2^20 each */
+    int64_t translate[3];  /* Q16, in source cells: -2^40..2^40 each */
+    uint64_t n_words;      /* the scene: words [0, n_words) of the node buffer */
+    uint64_t src_words;    /* the source: words [0, src_words) at src_dev, rooted at group 0 */
+    uint64_t max_words;    /* 0 = the capacity; never above SVO_VOXEL_OFFSET */
+} svo_transform_params;
+int svo_nodes_transform(svo_ctx *ctx, const uint32_t *src_dev, const svo_transform_params *p, uint64_t *n_words_out);
+/* Times (ms) of the last transform: [0] plan (with its per-level read-backs), [1] status, [2] fill, [3] write (device events;
+ * waits for the write), [4] host wall time of the call.  A refused call leaves the times of the last one that ran. */
+#define SVO_TRANSFORM_TIMES 5   /* plan (with its per-level read-backs), status, fill, write, host wall */
+int svo_transform_timing(svo_ctx *ctx, float ms_out[SVO_TRANSFORM_TIMES]);
+
 /* ---- one step of morphology on the device tree: grow, shrink ----
  * Edits the first n_words words of the node buffer in place, on a grid of depth `depth`, by one step of dilation (GROW) or
  * erosion (SHRINK) under conn = 6, 18 or 26 neighbours: the offsets d in {-1,0,1}^3, d != 0, with |dx| + |dy| + |dz| <= 1, 2, 3.

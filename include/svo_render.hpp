@@ -341,6 +341,27 @@ class Render {  // render.rs:3-285
         gpu_.poll_wait();  // the source may go away
         return new_words;
     }
+    // the source tree, a cube of 2^src_depth cells a side, placed into the scene under an affine map from scene cells to source
+    // cells (svo_nodes_transform): matrix, 9 row-major entries, and translate are Q16; the scene cell c samples
+    // the source's cell floor(A (c + 1/2) + t) and stays as it is where that lies outside the source's cube.  Free turns, scale
+    // and shear; returns the new length.  Throws, with nothing written, where either tree is finer than its depth and the op
+    // has to look below.
+    uint64_t transform_nodes(uint64_t n_words, const uint32_t *src_dev, uint64_t src_words, uint32_t op, uint32_t depth, uint32_t src_depth,
+                             const int32_t matrix[9], const int64_t translate[3], uint64_t max_words = 0) {
+        if (depth > declared_depth_) {
+            gpu_.set_option(SVO_OPT_TREE_DEPTH, depth);
+            declared_depth_ = depth;
+        }
+        svo_transform_params p{};
+        p.op = op, p.depth = depth, p.src_depth = src_depth;
+        for (int i = 0; i < 9; i++) p.matrix[i] = matrix[i];
+        for (int i = 0; i < 3; i++) p.translate[i] = translate[i];
+        p.n_words = n_words, p.src_words = src_words, p.max_words = max_words;
+        uint64_t new_words = 0;
+        gpu_.check(svo_nodes_transform(gpu_.ctx(), src_dev, &p, &new_words));
+        gpu_.poll_wait();  // the source may go away
+        return new_words;
+    }
     // `steps` steps of morphology on the first n_words words of the node buffer, in place (svo_nodes_morph): op
     // SVO_MORPH_GROW adds every empty cell with a voxel among its conn (6, 18 or 26) neighbours, in `colour` or with 0 in its
     // first neighbour's value, SVO_MORPH_SHRINK empties every voxel with an empty cell among them (open_boundary: or the grid's

@@ -115,6 +115,20 @@ class PlaceParams(C.Structure):
     ]
 
 
+class TransformParams(C.Structure):
+    """svo_transform_params: a second tree placed into the tree in the node buffer under an affine map (include/svo_hip.h)."""
+    _fields_ = [
+        ("op", C.c_uint32),
+        ("depth", C.c_uint32),
+        ("src_depth", C.c_uint32),
+        ("matrix", C.c_int32 * 9),
+        ("translate", C.c_int64 * 3),
+        ("n_words", C.c_uint64),
+        ("src_words", C.c_uint64),
+        ("max_words", C.c_uint64),
+    ]
+
+
 class MorphParams(C.Structure):
     """svo_morph_params: one step of morphology on the tree in the node buffer (include/svo_hip.h)."""
     _fields_ = [
@@ -374,6 +388,8 @@ DEVICE_SIGNATURES = {
     "svo_combine_timing": (C.c_int, (vp, fp)),
     "svo_nodes_place": (C.c_int, (vp, vp, C.POINTER(PlaceParams), C.POINTER(u64))),
     "svo_place_timing": (C.c_int, (vp, fp)),
+    "svo_nodes_transform": (C.c_int, (vp, vp, C.POINTER(TransformParams), C.POINTER(u64))),
+    "svo_transform_timing": (C.c_int, (vp, fp)),
     "svo_nodes_morph": (C.c_int, (vp, C.POINTER(MorphParams), C.POINTER(u64))),
     "svo_morph_timing": (C.c_int, (vp, fp)),
     "svo_nodes_edit_heightmap": (C.c_int, (vp, C.POINTER(HeightmapParams), vp, C.POINTER(u64))),

@@ -1,6 +1,6 @@
 // svo_combine_rules.h -- the rule of two trees combined, as tables over (op, the scene's value empty or not, the source's
-// value empty or not): what svo_combine.hip and svo_place.hip decide a word by, stated once.
-// include/svo_hip.h has the rule in words.  Then what the two passes add to the frontier walk (svo_frontier.h) alike: the
+// value empty or not): what svo_combine.hip, svo_place.hip and svo_transform.hip decide a word by, stated once.
+// include/svo_hip.h has the rule in words.  Then what the three passes add to the frontier walk (svo_frontier.h) alike: the
 // flags and the words of a refusal, and the status words and refusals of a malformed source.  In an anonymous namespace: a
 // copy per file.
 #pragma once
@@ -55,7 +55,7 @@ __host__ __device__ inline bool leaf_stays(uint32_t op, bool a_set) {
     return table >> (2u * op + uint32_t(a_set)) & 1u;
 }
 
-// The walk's hooks of a pass with a source tree: a followed source pointer is checked by the pass's emit kernel as the
+// The walk's hooks of a pass with a source tree: a followed source pointer is checked by the pass's emit kernel (svo_transform.hip: by its plan kernel too) as the
 // discovery checks a scene's, into two status words of the pass's own, which are tested behind the walk's.
 enum { kStSrcAlign = kStWords, kStSrcRange };
 struct SourcePass : FrontierPass {

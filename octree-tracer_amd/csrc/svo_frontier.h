@@ -1,6 +1,6 @@
 // svo_frontier.h -- the one home of the top-down walk that edits the tree in the node buffer, for the shape
-// edit (svo_region.hip), the combine (svo_combine.hip), the placement (svo_place.hip), the morphology step (svo_morph.hip)
-// and the height-map edit (svo_heightmap.hip).  A pass has a plan and an emit kernel of its own, which hold its rule;
+// edit (svo_region.hip), the combine (svo_combine.hip), the placement (svo_place.hip), the affine placement
+// (svo_transform.hip), the morphology step (svo_morph.hip) and the height-map edit (svo_heightmap.hip).  A pass has a plan and an emit kernel of its own, which hold its rule;
 // everything around them stands here, once:
 //
 //   frontier  the words of a level that the pass may touch, as groups of eight: the group's first word (in the buffer, or
@@ -18,7 +18,7 @@
 //   commit    a fill launch writes the eight leaf words of every new group, then one launch writes the list.  No two
 //             entries name the same word
 //
-// svo_frontier_walk is the workspace, one per context (svo_ctx::frontier), that the five passes take turns in: nothing in
+// svo_frontier_walk is the workspace, one per context (svo_ctx::frontier), that the six passes take turns in: nothing in
 // it is read after the call that wrote it returns.  It is one type for all files.  What launches kernels is in an anonymous
 // namespace like them, a copy per file: the kernels under the names they had in svo_region.hip, and Walk, one call's walk
 // in that workspace.

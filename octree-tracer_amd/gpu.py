@@ -94,6 +94,11 @@ class Gpu:
         host wall time of the call (svo_place_timing)"""
         return self._timing(lib().svo_place_timing, 5)
 
+    def transform_timing(self):
+        """ms of the last Render.transform_nodes: plan (with its per-level read-backs), status, fill, write (device events),
+        host wall time of the call (svo_transform_timing)"""
+        return self._timing(lib().svo_transform_timing, 5)
+
     def morph_timing(self):
         """ms of the last step of Render.morph_nodes: plan (with its per-level read-backs), status, fill, write (device
         events), host wall time of the call (svo_morph_timing)"""

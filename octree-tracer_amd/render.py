@@ -6,7 +6,7 @@ import torch
 
 from . import sharding
 from ._device import device_u32, voxel_list, wait_for_torch
-from ._lib import BuildParams, CombineParams, CompactParams, ComponentsParams, EditParams, HeightmapParams, ListParams, MorphParams, PlaceParams, RegionParams, SampleParams, SimplifyParams, SitesParams, StampParams, SurfaceMergeParams, SurfaceParams, TopsParams, Uniforms, lib
+from ._lib import BuildParams, CombineParams, CompactParams, ComponentsParams, EditParams, HeightmapParams, ListParams, MorphParams, PlaceParams, RegionParams, SampleParams, SimplifyParams, SitesParams, StampParams, SurfaceMergeParams, SurfaceParams, TopsParams, TransformParams, Uniforms, lib
 from .camera import camera_matrices
 
 F_PAUSE_ADAPTIVE, F_SHOW_STEPS, F_SHOW_HITS, F_SHADOWS, F_MISC_BOOL = 1, 2, 4, 8, 16
@@ -365,6 +365,46 @@ class Render:
         out = C.c_uint64()
         wait_for_torch(self.gpu)
         self.gpu.check(lib().svo_nodes_place(self.gpu._h, src_ptr, C.byref(p), C.byref(out)))
+        self.gpu.sync()  # (the source may be released by the caller)
+        self.node_length = out.value
+        return out.value
+
+    def transform_nodes(self, source, op="over", depth=None, matrix=(65536, 0, 0, 0, 65536, 0, 0, 0, 65536), translate=(0, 0, 0), src_depth=None,
+                        max_words=None):
+        """Place a second device tree, the source, into the tree that is in the node buffer, the scene, under any affine map,
+        in place (svo_nodes_transform): place_nodes with free turns, scale and shear, and a source whose cells
+        need not be the scene's.  source and op are combine_nodes'.  matrix (9 integers, row-major) and translate (3) are
+        Q16 and map SCENE cells to SOURCE cells: the scene cell c samples the source's cell floor(A (c + 1/2) + t), the
+        nearest cell to its centre, and stays as it is where that lies outside the source's cube of 2^src_depth cells a side
+        (None: `depth`).  transform.fixed makes the numbers from a forward map ("turn the model by F about this point, put
+        it there"), transform.from_orientation from place_nodes' arguments, transform.source_cell predicts q.  Coarse
+        leaves stay coarse where both trees allow it; equal siblings that a split leaves behind are simplify_nodes' to
+        merge.  Point sampling aliases where the map shrinks the source: simplify_nodes(cut_level=...) on the source first.
+        Where either tree is finer than its depth and the op has to look below, SvoError is raised and nothing is written.
+        depth=None: the depth declared for this tree.  Returns the new length (node_length)."""
+        depth = int(self.gpu.tree_depth if depth is None else depth)
+        if isinstance(op, str):
+            if op not in COMBINE_OPS:
+                raise ValueError(f"op must be one of {', '.join(COMBINE_OPS)} (got {op!r})")
+            op = COMBINE_OPS.index(op)
+        src_ptr, src_words, _held = self._source_tree(source)
+        from .transform import whole_numbers
+        matrix, translate = whole_numbers(matrix, "matrix"), whole_numbers(translate, "translate")
+        if len(matrix) != 9 or len(translate) != 3:
+            raise ValueError(f"matrix must hold 9 numbers and translate 3, got {len(matrix)} and {len(translate)}")
+        self.gpu.declare_depth(depth)
+        p = TransformParams()
+        p.op = max(0, int(op))
+        p.depth = max(0, depth)
+        p.src_depth = max(0, int(depth if src_depth is None else src_depth))
+        p.matrix[:] = [min(max(-0x80000000, v), 0x7FFFFFFF) for v in matrix]
+        p.translate[:] = [min(max(-(1 << 63), v), (1 << 63) - 1) for v in translate]
+        p.n_words = int(self.node_length)
+        p.src_words = src_words
+        p.max_words = int(max_words or 0)
+        out = C.c_uint64()
+        wait_for_torch(self.gpu)
+        self.gpu.check(lib().svo_nodes_transform(self.gpu._h, src_ptr, C.byref(p), C.byref(out)))
         self.gpu.sync()  # (the source may be released by the caller)
         self.node_length = out.value
         return out.value
