@@ -1180,6 +1180,69 @@ int svo_nodes_sample_dense(svo_ctx *ctx, const svo_sample_params *p, const uint3
 #define SVO_SAMPLE_TIMES 2
 int svo_sample_timing(svo_ctx *ctx, float ms_out[SVO_SAMPLE_TIMES]);
 
+/* ---- exact distance fields of the tree in the node buffer ----
+ * How far is a cell from the nearest voxel, and which voxel is it: the exact squared Euclidean distance transform of the
+ * tree on the `depth` grid, in integers, for every cell of a box, with the nearest site.
+ * A cell of the grid is OCCUPIED when svo_nodes_sample gives it a value other than 0 (svo_nodes_column_tops' rule): a
+ * colour counts, a coarse leaf's too, and so do SVO_SAMPLE_FINER and SVO_SAMPLE_BROKEN.  Every cell outside
+ * [0, 2^depth)^3 is empty.  The SITES of a call, by mode:
+ *     SVO_DISTANCE_TO_VOXELS  the occupied cells
+ *     SVO_DISTANCE_TO_EMPTY   the empty cells, those outside the grid included (the grid's boundary exposes, as in
+ *                             svo_nodes_list_surface)
+ *     SVO_DISTANCE_SIGNED     for an empty cell the occupied cells, for an occupied cell the empty cells
+ * For every cell c of the box [origin, origin + size), with R = max_distance: among the sites s with |s - c|^2 <= R^2 take
+ * the one that is smallest by (|s - c|^2, s.x, s.y, s.z), lexicographically.  The cell itself, sites outside the box and
+ * sites outside the grid all take part: a voxel one cell behind the box's face gives that face distance 1.
+ *     d2_out_dev[(i * size[1] + j) * size[2] + k]     (svo_nodes_sample_dense's layout) gets |s - c|^2, or
+ *                                                     SVO_DISTANCE_FAR when there is no such site; in signed mode an
+ *                                                     occupied cell gets the negated value (-SVO_DISTANCE_FAR for none),
+ *                                                     so a signed field is never 0
+ *     site_out_dev[the same index]   (may be NULL)    ((dx + 128) << 16) | ((dy + 128) << 8) | (dz + 128) with (dx, dy, dz)
+ *                                                     = s - c, or SVO_DISTANCE_NO_SITE
+ * The lexicographic minimum decomposes over the axes (the best site is the best over x' of the best over y' of the best
+ * over z'), so three one-dimensional passes give exactly this rule, ties included.
+ * The call only reads the node buffer, runs on the ctx stream behind the store's last write, whichever context issued it,
+ * records no write and DOES NOT BLOCK: nothing is read back, and the outputs must stay valid until svo_sync.  Only the
+ * size[0] * size[1] * size[2] entries of each output are written; a size with a 0 succeeds and writes nothing.  No
+ * atomics: the same bytes on every run and for every layout of the same tree.  No pointer is followed before it passed
+ * svo_nodes_sample's check, and the depth bound ends every walk on a cyclic tree.  A device adaptive state attached to
+ * the context is no obstacle.
+ * WORKSPACE, owned by the context, grown on demand and reused.  With g[a] = size[a] + 2 R and w = the number of aligned
+ * runs of 64 cells along z that meet [origin[2] - R, origin[2] + size[2] + R) (at most (size[2] + 2 R) / 64 + 2):
+ *     occupancy bits          g[0] * g[1] * w * 8 bytes, for the box grown by R on every side
+ *     the y pass's output     m * g[0] * t * size[2] * 4 bytes, m = 2 in signed mode and 1 otherwise
+ * The call works in SLABS of t rows of the box along y, one after the other through the same buffer:
+ * t = max(1, min(size[1], SVO_DISTANCE_SLAB_CELLS / (g[0] * size[2]))).  A box whose two terms together exceed
+ * SVO_DISTANCE_MAX_WORKSPACE bytes is refused.
+ * Errors are decided on the host from the arguments before anything is enqueued; the first in this order is reported, and a
+ * refused call writes nothing:
+ * SVO_ERR_ARG: NULL p; non-zero flags; depth outside 1..21; mode above 2; max_distance outside 1..SVO_DISTANCE_MAX_RADIUS;
+ * NULL origin, size or d2_out_dev; a box with origin + size > 2^depth on an axis; a box with 2^31 cells or more; a box
+ * whose workspace exceeds SVO_DISTANCE_MAX_WORKSPACE.  SVO_ERR_STATE: no node buffer.  SVO_ERR_ARG: n_words not a positive
+ * multiple of 8 or above the capacity. */
+#define SVO_DISTANCE_TO_VOXELS 0u
+#define SVO_DISTANCE_TO_EMPTY  1u
+#define SVO_DISTANCE_SIGNED    2u
+#define SVO_DISTANCE_MAX_RADIUS 127u
+#define SVO_DISTANCE_FAR     0x7FFFFFFF   /* in d2: no site within max_distance */
+#define SVO_DISTANCE_NO_SITE 0xFFFFFFFFu  /* in site: the same */
+#define SVO_DISTANCE_SLAB_CELLS (1u << 21)        /* entries of the y pass's output that a slab holds, when a row fits */
+#define SVO_DISTANCE_MAX_WORKSPACE (1ull << 30)   /* bytes */
+typedef struct svo_distance_params {
+    uint32_t flags;         /* 0 */
+    uint32_t mode;          /* SVO_DISTANCE_TO_VOXELS, _TO_EMPTY or _SIGNED */
+    uint32_t depth;         /* 1..21: the grid the box is given on */
+    uint32_t max_distance;  /* R, 1..SVO_DISTANCE_MAX_RADIUS: sites further than R cells away are not looked for */
+    uint64_t n_words;       /* the tree: words [0, n_words) of the node buffer, rooted at group 0 */
+} svo_distance_params;
+int svo_nodes_distance(svo_ctx *ctx, const svo_distance_params *p, const uint32_t origin[3], const uint32_t size[3],
+                       int32_t *d2_out_dev, uint32_t *site_out_dev /* may be null */);
+/* Times (ms) of the last distance call that ran (device events; waits for them): [0] the occupancy bits, [1] the first
+ * slab's z and y pass, [2] the first slab's x pass, [3] all slabs, the first included, [4] host wall time of the call.  A
+ * refused call, and one with nothing to do, leaves them.  SVO_ERR_STATE on a context that never ran the pass. */
+#define SVO_DISTANCE_TIMES 5
+int svo_distance_timing(svo_ctx *ctx, float ms_out[SVO_DISTANCE_TIMES]);
+
 /* ---- triangle meshes voxelised on the GPU ----
  * Conservative voxelisation of a triangle mesh on the 2^depth grid into the voxel list that svo_nodes_build,
  * svo_nodes_edit, svo_cpu_octree_build and svo_world_build take.  The geometry is exact.  A quantised coordinate q lies

@@ -583,6 +583,18 @@ class Render {  // render.rs:3-285
         gpu_.check(svo_nodes_sample_dense(gpu_.ctx(), &p, origin, size, grid_dev));
         gpu_.poll_wait();
     }
+    // the exact squared distance of every cell of the box [origin, origin + size) of the `depth` grid to its nearest site
+    // within max_distance (1..SVO_DISTANCE_MAX_RADIUS) cells (svo_nodes_distance): d2_dev holds size[0] *
+    // size[1] * size[2] i32 of DEVICE memory, z fastest like sample_dense's grid, sites_dev (or null) as many u32 for the
+    // packed offset to that site.  mode: SVO_DISTANCE_TO_VOXELS, _TO_EMPTY or _SIGNED.  SVO_DISTANCE_FAR and
+    // SVO_DISTANCE_NO_SITE where no site is that near.  Throws for a box that leaves the grid, has 2^31 cells or more or
+    // needs more workspace than SVO_DISTANCE_MAX_WORKSPACE.  The node buffer is only read.
+    void distance_dense(uint64_t n_words, uint32_t depth, const uint32_t origin[3], const uint32_t size[3], uint32_t max_distance,
+                        int32_t *d2_dev, uint32_t *sites_dev = nullptr, uint32_t mode = SVO_DISTANCE_TO_VOXELS) {
+        const svo_distance_params p{0u, mode, depth, max_distance, n_words};
+        gpu_.check(svo_nodes_distance(gpu_.ctx(), &p, origin, size, d2_dev, sites_dev));
+        gpu_.poll_wait();
+    }
     // the highest occupied cell of each column of a rectangle of the `depth` grid (svo_nodes_column_tops):
     // tops_dev and values_dev (or null) hold size_xz[0] * size_xz[1] u32 of DEVICE memory, z fastest; a top is the y of
     // the first cell from y_hi - 1 down to y_lo that sample_voxels gives a value other than 0, or SVO_TOP_NONE.  y_hi 0:

@@ -16,6 +16,7 @@ C ABI of libsvo_hip.so:
                        reader and writer, mesh generators (no reference counterpart)
     region             boxes and balls for Render.edit_region: fill, carve and paint a device tree by shapes (no reference counterpart)
     orientation        the cube's 48 symmetries as Render.place_nodes numbers them (no reference counterpart)
+    distance           what Render.distance_dense returns, taken apart: FAR, NO_SITE, the packed sites, radius masks (no reference counterpart)
     transform          affine maps in Q16 as Render.transform_nodes takes them: turns, scale, shear (no reference counterpart)
     structure.Structure <- src/cpu_octree.rs CpuOctree::load_structure: a .vox model as offsets, block indices and colours
 The package directory name contains a hyphen; import it through __graft_entry__.load_package(),
@@ -39,9 +40,10 @@ from . import mesh
 from . import region
 from . import orientation
 from . import transform
+from . import distance
 from . import structure
 from . import sharding
 from . import adaptive
 
 __all__ = ["Gpu", "Render", "Compute", "Octree", "CpuOctree", "Voxel", "World", "Procedural", "Uniforms", "Character", "Settings",
-           "SvoError", "SAMPLE_FINER", "SAMPLE_OUTSIDE", "SAMPLE_BROKEN", "TOP_NONE", "MORPH_OPS", "HEIGHTMAP_MODES", "Structure", "load_structure", "VOXEL_OFFSET", "CHUNK_OFFSET", "HIT_DTYPE", "create_node", "camera_matrices", "scenes", "mesh", "region", "orientation", "transform", "structure", "sharding", "adaptive", "procedural"]
+           "SvoError", "SAMPLE_FINER", "SAMPLE_OUTSIDE", "SAMPLE_BROKEN", "TOP_NONE", "MORPH_OPS", "HEIGHTMAP_MODES", "Structure", "load_structure", "VOXEL_OFFSET", "CHUNK_OFFSET", "HIT_DTYPE", "create_node", "camera_matrices", "scenes", "mesh", "region", "orientation", "transform", "distance", "structure", "sharding", "adaptive", "procedural"]

@@ -240,6 +240,17 @@ class SampleParams(C.Structure):
     ]
 
 
+class DistanceParams(C.Structure):
+    """svo_distance_params: the exact distance field of the tree in the node buffer (include/svo_hip.h)."""
+    _fields_ = [
+        ("flags", C.c_uint32),
+        ("mode", C.c_uint32),
+        ("depth", C.c_uint32),
+        ("max_distance", C.c_uint32),
+        ("n_words", C.c_uint64),
+    ]
+
+
 class VoxelizeParams(C.Structure):
     """svo_voxelize_params: a triangle mesh voxelised on the device (include/svo_hip.h)."""
     _fields_ = [
@@ -411,6 +422,8 @@ DEVICE_SIGNATURES = {
     "svo_nodes_sample": (C.c_int, (vp, C.POINTER(SampleParams), vp, sz, vp, vp, vp)),
     "svo_nodes_sample_dense": (C.c_int, (vp, C.POINTER(SampleParams), C.POINTER(u32), C.POINTER(u32), vp)),
     "svo_sample_timing": (C.c_int, (vp, fp)),
+    "svo_nodes_distance": (C.c_int, (vp, C.POINTER(DistanceParams), C.POINTER(u32), C.POINTER(u32), vp, vp)),
+    "svo_distance_timing": (C.c_int, (vp, fp)),
     "svo_mesh_voxelize": (C.c_int, (vp, C.POINTER(VoxelizeParams), vp, vp, vp, sz, vp, vp, vp, C.POINTER(u64))),
     "svo_voxelize_timing": (C.c_int, (vp, fp)),
     "svo_mesh_voxelize_solid": (C.c_int, (vp, C.POINTER(SolidParams), vp, vp, sz, vp, C.POINTER(u64), C.POINTER(u64))),

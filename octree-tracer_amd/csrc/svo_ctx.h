@@ -1,6 +1,6 @@
 // svo_ctx.h -- the device context behind the opaque `svo_ctx` of include/svo_hip.h, and the host helpers of the files that
 // use it: svo_abi.cpp (trace / scan dispatch), svo_comm.cpp (RCCL frame gather) and the GPU tree passes (svo_proc.hip,
-// svo_build.hip, svo_edit.hip, svo_region.hip, svo_combine.hip, svo_place.hip, svo_transform.hip, svo_morph.hip, svo_heightmap.hip, svo_compact.hip, svo_simplify.hip, svo_list.hip, svo_sample.hip, svo_voxelize.hip, svo_solid.hip,
+// svo_build.hip, svo_edit.hip, svo_region.hip, svo_combine.hip, svo_place.hip, svo_transform.hip, svo_morph.hip, svo_heightmap.hip, svo_compact.hip, svo_simplify.hip, svo_list.hip, svo_sample.hip, svo_distance.hip, svo_voxelize.hip, svo_solid.hip,
 // svo_structure.hip, svo_surface.hip, svo_surface_merge.hip, svo_components.hip, svo_adapt.hip).  One rule of ownership for the context, the node store and every
 // pass's state: a member owns what it holds, as svo_dev / svo_pinned (an allocation and its size), svo_events (events) or
 // svo_stream (a stream).  The passes
@@ -154,6 +154,7 @@ struct svo_heightmap_state;
 struct svo_frontier_walk;
 struct svo_list_state;
 struct svo_sample_state;
+struct svo_distance_state;
 struct svo_voxelize_state;
 struct svo_solid_state;
 struct svo_structure_state;
@@ -276,6 +277,7 @@ struct svo_ctx {
     svo_workspace<svo_heightmap_state> heightmap{nullptr, nullptr};  // a height-map edit's pyramid (svo_heightmap.hip)
     svo_workspace<svo_list_state> list{nullptr, nullptr};  // voxel listing's workspace (svo_list.hip)
     svo_workspace<svo_sample_state> sample{nullptr, nullptr};  // sampling's events and times (svo_sample.hip)
+    svo_workspace<svo_distance_state> distance{nullptr, nullptr};  // the distance pass's bits, its y pass's output and its times (svo_distance.hip)
     svo_workspace<svo_voxelize_state> voxelize{nullptr, nullptr};  // mesh voxeliser's workspace (svo_voxelize.hip)
     svo_workspace<svo_solid_state> solid{nullptr, nullptr};  // solid voxeliser's workspace (svo_solid.hip)
     svo_workspace<svo_structure_state> structure{nullptr, nullptr};  // structure scattering's workspace (svo_structure.hip)

@@ -13,9 +13,9 @@
 //            four lanes of a brick's z row read words of two 32-byte groups per level.  A lane of a brick that was not
 //            settled finishes its own last two levels from the brick's group.
 //
-// The walk is this file's own: svo_edit.hip's plan walks the same path but answers another question (the first leaf,
-// an address check without the alignment rule, a refusal at an interior word), and one function for both would have to
-// branch on its caller.
+// The walk is the sampler's own (svo_sample_walk.h, which svo_distance.hip includes too): svo_edit.hip's plan walks the same
+// path but answers another question (the first leaf, an address check without the alignment rule, a refusal at an interior
+// word), and one function for both would have to branch on its caller.
 #include <hip/hip_runtime.h>
 
 #include <string>
@@ -23,6 +23,7 @@
 #include "svo_ctx.h"
 #include "svo_group.h"   // (kThreads, kEmptyWord; not svo_scan.h: this file needs none of its kernels)
 #include "svo_morton.h"  // (morton_child)
+#include "svo_sample_walk.h"  // (Sample, sample_walk: the rule for one cell, which svo_distance.hip walks too)
 
 namespace {
 
@@ -31,24 +32,6 @@ constexpr uint32_t kRun = 4;             // bricks along z per wave
 constexpr uint32_t kSettled = 0xFFFFFFFFu;  // in Brick::group: every cell of the brick has Brick::value
 static_assert(kThreads % 64 == 0, "whole waves per workgroup");
 static_assert(kEmptyWord >> 4 == SVO_VOXEL_OFFSET, "an empty word is a leaf of value 0");
-
-struct Sample {
-    uint32_t value, level, index;
-};
-
-// The rule for one cell (include/svo_hip.h) from `level` on, `group` being the group of that level on the cell's path.
-// Every index read is below n_words: group is 0 (n_words >= 8) or a pointer that passed the check.
-__device__ inline Sample sample_walk(const uint32_t *__restrict__ words, uint64_t n_words, uint32_t x, uint32_t y, uint32_t z,
-                                     uint32_t depth, uint32_t level, uint32_t group) {
-    for (;; level++) {
-        const uint32_t i = group + morton_child(x, y, z, depth - level);
-        const uint32_t pointer = words[i] >> 4;
-        if (pointer >= SVO_VOXEL_OFFSET) return {pointer - SVO_VOXEL_OFFSET, level, i};
-        if (level >= depth) return {SVO_SAMPLE_FINER, level, i};
-        if ((pointer & 7u) || uint64_t(pointer) + 8u > n_words) return {SVO_SAMPLE_BROKEN, level, i};
-        group = pointer;
-    }
-}
 
 __global__ __launch_bounds__(kThreads) void sample_cells_kernel(const uint32_t *__restrict__ words, uint64_t n_words,
                                                                 const uint32_t *__restrict__ xyz, uint32_t n, uint32_t depth,

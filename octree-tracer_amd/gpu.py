@@ -150,6 +150,11 @@ class Gpu:
         the call (svo_sample_timing)"""
         return self._timing(lib().svo_sample_timing, 2)
 
+    def distance_timing(self):
+        """ms of the last Render.distance_dense call that ran: the occupancy bits, the first slab's z and y pass, the first
+        slab's x pass, all slabs (device events), host wall time of the call (svo_distance_timing)"""
+        return self._timing(lib().svo_distance_timing, 5)
+
     def voxelize_timing(self):
         """ms of the last mesh.voxelize call into the library that ran (its fill, or its count query when the list was
         empty): setup, the levels above the last, the last level's test and scan, emit (device events), host wall time of

@@ -6,7 +6,7 @@ import torch
 
 from . import sharding
 from ._device import device_u32, voxel_list, wait_for_torch
-from ._lib import BuildParams, CombineParams, CompactParams, ComponentsParams, EditParams, HeightmapParams, ListParams, MorphParams, PlaceParams, RegionParams, SampleParams, SimplifyParams, SitesParams, StampParams, SurfaceMergeParams, SurfaceParams, TopsParams, TransformParams, Uniforms, lib
+from ._lib import BuildParams, CombineParams, CompactParams, ComponentsParams, DistanceParams, EditParams, HeightmapParams, ListParams, MorphParams, PlaceParams, RegionParams, SampleParams, SimplifyParams, SitesParams, StampParams, SurfaceMergeParams, SurfaceParams, TopsParams, TransformParams, SvoError, Uniforms, lib
 from .camera import camera_matrices
 
 F_PAUSE_ADAPTIVE, F_SHOW_STEPS, F_SHOW_HITS, F_SHADOWS, F_MISC_BOOL = 1, 2, 4, 8, 16
@@ -749,6 +749,115 @@ class Render:
         self.gpu.check(lib().svo_nodes_sample_dense(self.gpu._h, C.byref(p), (C.c_uint32 * 3)(*o), (C.c_uint32 * 3)(*s), room.data_ptr()))
         self.gpu.sync()
         return grid
+
+    def distance_dense(self, origin, size, max_distance, depth=None, mode="voxels", with_sites=False):
+        """The exact squared Euclidean distance of every cell of the box [origin, origin + size) of the `depth` grid to its
+        nearest site within max_distance (1..127) cells, computed from the tree on the GPU (svo_nodes_distance, DESIGN.md
+        35), as an int32 device tensor of shape `size`, indexed [x, y, z] like sample_dense's.  mode, a name of
+        distance.MODES: "voxels" the sites are the occupied cells (every cell that sample_dense gives a value other than
+        0), "empty" the empty cells, those outside the grid included, "signed" the voxels for an empty cell and the empty
+        cells for an occupied one, which gets the negated value.  distance.FAR (-FAR) where no site is that near.  Sites
+        outside the box count.  with_sites: (d2, sites), sites the offset to the nearest site, the lowest (x, y, z) among
+        equally near ones, packed as distance.unpack_sites and distance.site_cells take it.  Raises SvoError for a box that
+        leaves the grid, has 2^31 cells or more or needs more workspace than the library allows.  The node buffer is
+        only read."""
+        from .distance import MODES
+        dev = self.gpu.torch_device
+        o, s = [int(v) for v in origin], [int(v) for v in size]
+        if len(o) != 3 or len(s) != 3 or min(o + s) < 0 or max(o + s) >= 1 << 32:
+            raise ValueError(f"origin and size must be 3 values in [0, 2^32) each, got {o} and {s}")
+        if mode not in MODES:
+            raise ValueError(f"mode must be one of {', '.join(MODES)} (got {mode!r})")
+        p = DistanceParams()
+        p.mode, p.depth, p.n_words = MODES.index(mode), self._depth(depth), int(self.node_length)
+        p.max_distance = min(max(0, int(max_distance)), 0xFFFFFFFF)
+        # a box the call will refuse gets no memory first: the library decides and words the refusal
+        r = p.max_distance
+        fits = (1 <= p.depth <= 21 and 1 <= r <= 127 and all(a + b <= 1 << p.depth for a, b in zip(o, s)) and s[0] * s[1] * s[2] < 1 << 31
+                and self._distance_workspace(o, s, r, mode == "signed") <= 1 << 30)
+        d2 = torch.empty(s if fits else (0,), dtype=torch.int32, device=dev)
+        sites = torch.empty(s if fits else (0,), dtype=torch.int32, device=dev) if with_sites else None
+        room = d2 if d2.numel() else torch.empty(1, dtype=torch.int32, device=dev)  # (nothing is written to it)
+        wait_for_torch(self.gpu)
+        self.gpu.check(lib().svo_nodes_distance(self.gpu._h, C.byref(p), (C.c_uint32 * 3)(*o), (C.c_uint32 * 3)(*s), room.data_ptr(),
+                                                sites.data_ptr() if with_sites and sites.numel() else None))
+        self.gpu.sync()
+        return (d2, sites) if with_sites else d2
+
+    @staticmethod
+    def _distance_workspace(o, s, r, signed):
+        """the bytes of workspace that svo_nodes_distance takes for a box (svo_hip.h's formula)"""
+        if not s[0] * s[1] * s[2]:
+            return 0
+        gx, gy = s[0] + 2 * r, s[1] + 2 * r
+        z0 = (o[2] - r) // 64 * 64
+        words = (o[2] + s[2] + r - 1 - z0) // 64 + 1
+        slab = max(1, min(s[1], (1 << 21) // (gx * s[2])))
+        return gx * gy * words * 8 + (2 if signed else 1) * gx * slab * s[2] * 4
+
+    def morph_ball(self, op, radius, origin, size, colour=None, depth=None, max_words=None):
+        """Grow or shrink the tree that is in the node buffer by a ball of `radius` (1..127) cells inside the box [origin,
+        origin + size) of the `depth` grid, in place and on the device: morph_nodes with a round shape, and
+        one pass whatever the radius.  op "grow": every empty cell of the box with a voxel within `radius` (Euclidean,
+        voxels outside the box count) becomes a voxel of `colour`; None or 0: the value of its nearest voxel, the lowest
+        (x, y, z) among equally near ones.  op "shrink": every occupied cell of the box with an empty cell within `radius`
+        is emptied; the grid's outside is empty.  Every other cell of the grid samples exactly as before, the cells of a
+        coarse leaf included, which keeps its colour where it is split.
+        Made of distance_dense over the box (with the sites for a grow that takes its colours from them), sample_voxels at
+        the sites, a dense cube of the changed cells built by build_nodes_dense on a context of its own, and one
+        place_nodes of that cube: "under" for a grow, "carve" for a shrink.  The cube covers the changed cells' bounding
+        box alone (its corner moved down to a multiple of 8 cells), with the side 2^k >= that box's longest side, and k <= 9: A BOX SIDE ABOVE 512 CELLS IS REFUSED with
+        ValueError, as is a radius outside 1..127.  A grow whose colours would
+        come from a cell that samples to a mark (SAMPLE_FINER, SAMPLE_BROKEN) raises SvoError before anything is written;
+        otherwise raises as distance_dense and place_nodes do, nothing written.  "close" and "open" are two calls with a
+        box grown by the radius.  depth=None: the depth declared for this tree.  Returns the new length (node_length);
+        equal siblings that a split leaves behind are simplify_nodes' to merge."""
+        from .distance import FAR, site_cells
+        from .gpu import Gpu
+        if op not in ("grow", "shrink"):
+            raise ValueError(f"op must be grow or shrink (got {op!r})")
+        o, s = [int(v) for v in origin], [int(v) for v in size]
+        if len(o) != 3 or len(s) != 3 or min(o + s) < 0:
+            raise ValueError(f"origin and size must be 3 values, none negative, got {o} and {s}")
+        if max(s) > 512:
+            raise ValueError(f"the box's sides must be at most 512 cells: the changed cells are placed as a dense cube (got {s})")
+        radius = int(radius)
+        if not 1 <= radius <= 127:
+            raise ValueError(f"radius must be 1..127 (got {radius})")
+        depth = self._depth(depth)
+        colour = 0 if colour is None else int(colour) & 0xFFFFFF
+        grow = op == "grow"
+        from_sites = grow and not colour
+        got = self.distance_dense(o, s, radius, depth, "voxels" if grow else "empty", with_sites=from_sites)
+        d2 = got[0] if from_sites else got
+        changed = (d2 > 0) & (d2 != FAR)
+        n = int(changed.sum())
+        if not n:
+            return int(self.node_length)
+        if from_sites:
+            cells, _ = site_cells(got[1], o)
+            values = self.sample_voxels(cells[changed], depth)
+            if int(values.max()) >= SAMPLE_FINER:
+                raise SvoError(f"morph_ball: a nearest voxel samples to a mark (SAMPLE_FINER or SAMPLE_BROKEN) at depth {depth}: "
+                                   "it has no colour to give")
+        at = changed.nonzero()
+        lo, hi = at.min(dim=0).values.tolist(), (at.max(dim=0).values + 1).tolist()  # the changed cells' bounding box
+        low = [((a + v) & ~7) - a for a, v in zip(o, lo)]  # from a cell of level depth - 3 on: the cube's groups then lie on the scene's
+        if max(b - a for a, b in zip(low, hi)) <= 512:
+            lo = low
+        k = max(1, (max(b - a for a, b in zip(lo, hi)) - 1).bit_length())
+        cube = torch.zeros((1 << k,) * 3, dtype=torch.int32, device=self.gpu.torch_device)
+        at = at - at.new_tensor(lo)
+        cube[at[:, 0], at[:, 1], at[:, 2]] = values if from_sites else (colour if grow else 1)
+        words = min(8 * (n * k + 1), (8 << 3 * k) // 7 + 8)
+        own = Gpu(self.gpu.device)
+        try:
+            source = Render(own, (8, 8), np.full(8, EMPTY_WORD, dtype=np.uint32), capacity=max(1024, -(-words // 8) * 8))
+            source.build_nodes_dense(cube)
+            return self.place_nodes(source, "under" if grow else "carve", depth, offset=[a + b for a, b in zip(o, lo)], src_depth=k,
+                                    max_words=max_words)
+        finally:
+            own.close()
 
     def _depth(self, depth):
         return max(0, int(self.gpu.tree_depth if depth is None else depth))
